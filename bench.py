@@ -8,7 +8,7 @@ covariance assembly + bordered Cholesky (factorisation + solve fused) + reductio
 fit's inputs (locs, X, z) already resident in HBM.  Cholesky fp64 TFLOP/s is reported
 beside it (n^3/3 flop per evaluation).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--n 10000] [--mode shard|replica]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--n 10000] [--mode shard|replica] [--dump-outputs DIR]
 
 N = 1 : one GPU evaluates the whole thing.
 N > 1 : one rank per GPU.  Started by torch.distributed.run (the ranks read RANK / LOCAL_RANK /
@@ -25,7 +25,9 @@ N > 1 : one rank per GPU.  Started by torch.distributed.run (the ranks read RANK
         Mode "replica" (explicit): every rank evaluates its own theta (what optimParallel's 1+2P
         finite-difference points are) -> "weak".
 
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  With --dump-outputs DIR rank 0 also writes what the last timed step returned to a caller,
+float64: DIR/neg2loglik.npy (the -2 log-likelihood, shape (1,)) and DIR/neg2loglik_parts.npy (sum(log(diag(chol))) and the
+r quadratic forms).  The inputs are fixed (grid, seeded z), so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -254,6 +256,8 @@ def main():
     ap.add_argument("--inflight", type=int, default=2,
                     help="extra measurement at N=1: this many independent evaluations in flight on the GPU "
                          "(separate fit handles / streams, as optimParallel's workers issue them); 0 = skip")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (neg2loglik, neg2loglik_parts) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -337,7 +341,7 @@ def main():
             fit.init_rccl(dist, rank, world, group=ctl)               # RCCL communicator inside the library
 
         def step():
-            return fit.neg2loglik_core(th)[0]
+            return fit.neg2loglik_core(th)
     else:
         fit = ca.CoconsFit(locs, X, z, wl.SMOOTH_LIMITS, device=local_rank)
         if world > 1:      # replica mode: every rank its own finite-difference point
@@ -345,7 +349,7 @@ def main():
             th["std.dev"][0] += 1.22e-4 * rank
 
         def step():
-            return fit.neg2loglik_core(th)[0]
+            return fit.neg2loglik_core(th)
 
     # N > 1, sharded: what RCCL itself says about the communicator of every rank (ncclCommCount / UserRank / CuDevice)
     comm = None
@@ -361,14 +365,17 @@ def main():
             sys.exit("bench.py: RCCL reports %d ranks on %d distinct devices, expected %d"
                      % (comm["rccl_ranks"], comm["distinct_devices"], world))
 
-    val = None
+    res = None
     for _ in range(args.warmup):
-        val = step()
+        res = step()
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        val = step()
+        res = step()
     barrier()
+    val = res[0] if res is not None else None
+    last_outputs = {"neg2loglik": np.array([res[0]], dtype=np.float64),
+                    "neg2loglik_parts": np.asarray(res[1], dtype=np.float64).copy()} if res is not None else None
     dt = max_over_ranks(time.perf_counter() - t0)
     evals = args.steps * (world if (world > 1 and not shard_mode) else 1)
     evals_per_s = evals / dt
@@ -667,6 +674,12 @@ def main():
             "assembly": assembly,
             "cpu_baseline": cpu,
         }
+        if args.dump_outputs:
+            if last_outputs is None:
+                sys.exit("bench.py: --dump-outputs needs at least one step")
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, arr in last_outputs.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
         print(json.dumps(out))
         sys.stdout.flush()
     if dist is not None:
