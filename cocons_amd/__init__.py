@@ -18,6 +18,7 @@ from .host import (  # noqa: F401
     cocoPredict_sparse,
     cocoSim_cond_dense,
     cocoSim_dense,
+    cocoSim_sparse,
     cov_rns,
     cov_rns_classic,
     cov_rns_pred,

@@ -63,6 +63,8 @@ SIGNATURES = {
     "cocons_neg2loglik_reml": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp]),
     "cocons_predict_dense": (c_int, [c_vp, c_dp, c_dp, c_int, c_int, c_dp, c_dp, c_dp, c_dp]),
     "cocons_sim_dense": (c_int, [c_vp, c_dp, c_dp, c_int, c_int, c_dp, c_dp]),
+    "cocons_sim_taper": (c_int, [c_vp, c_dp, c_dp, c_int, c_dp, ctypes.POINTER(c_int), c_dp]),
+    "cocons_fit_taper_order": (c_int, [c_vp, ctypes.POINTER(c_int)]),
     "cocons_sim_cond_dense": (c_int, [c_vp, c_dp, c_dp, c_int, c_int, c_dp, c_dp, c_dp, c_int, c_dp, c_dp]),
     "cocons_chol_solve": (c_int, [c_int, c_dp, c_int, c_dp, c_dp, c_dp, c_dp]),
     "cocons_fit_profile": (c_int, [c_vp, c_dp, c_dp, c_int, c_dp]),
@@ -96,6 +98,7 @@ DIAG_SIGNATURES = {
     "cocons_debug_host_enqueue": (c_int, [c_vp, c_dp]),
     "cocons_debug_dag_words": (c_int, [c_vp, c_int, ctypes.POINTER(ctypes.c_uint)]),
     "cocons_debug_assembly_loop": (c_int, [c_vp, c_dp, c_int, c_dp]),
+    "cocons_debug_sim_taper_ms": (c_int, [c_vp, c_int, c_dp]),
     "cocons_debug_dag_trace": (ctypes.c_longlong, [c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
                                                    ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
 }

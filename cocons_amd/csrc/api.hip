@@ -328,6 +328,11 @@ struct cocons_fit {
                                   // `skew` (= taper_maxband) tile rows from its diagonal tile down plus the rows under the
                                   // matrix -- O(n x bandwidth) doubles instead of n^2
     std::vector<int> *taper_inv;  // position of the caller's observation i in the handle's order (reverse Cuthill-McKee)
+    std::vector<int> *h_trp, *h_tci;   // host copy of the full (symmetric) pattern and taper entries in the handle's order:
+    std::vector<double> *h_tval;       // what a twin in another order is built from (O(nnz))
+    cocons_fit *taper_twin;       // lazily created taper handle in the order of the last pivot cocons_sim_taper was given
+    std::vector<int> *twin_perm;  // that order: twin position k holds the observation at position twin_perm[k] of this handle
+    float sim_ms[3];              // last cocons_sim_taper: assembly + factorisation, band product, gather (device events)
     // collectives of the natively sharded evaluation (see "native sharded evaluation" below)
     int coll_kind;                // 0 none, 1 RCCL communicator, 2 caller-provided transport
     int coll_rank, coll_world;
@@ -437,11 +442,13 @@ extern "C" void cocons_fit_destroy(cocons_fit *f)
         if (f->comm && f->comm_own) rccl_comm_destroy(f->comm);
         if (f->slots) { for (auto c : *f->slots) cocons_fit_destroy(c); delete f->slots; f->slots = nullptr; }
         if (f->unsorted) { cocons_fit_destroy(f->unsorted); f->unsorted = nullptr; }
+        if (f->taper_twin) { cocons_fit_destroy(f->taper_twin); f->taper_twin = nullptr; }
         if (f->stream2) hipStreamDestroy(f->stream2);
         if (f->own_stream && f->stream) hipStreamDestroy(f->stream);
     }
     delete f->h_locs; delete f->h_X; delete f->h_z; delete f->h_xb;
     delete f->taper_hi; delete f->taper_inv;
+    delete f->h_trp; delete f->h_tci; delete f->h_tval; delete f->twin_perm;
     delete f->op_mu;
     delete f;
 }
@@ -641,6 +648,11 @@ extern "C" cocons_fit *cocons_fit_create(int n, int p, int r, int q, const doubl
 // the value spam's sparse Cholesky gives, obtained here through the DENSE factorisation of S (zeros stored):
 // valid while n^2 doubles fit the device, and an n = 10^4 evaluation costs what a dense one costs.  The
 // observations keep the caller's order (the pattern refers to it).
+static cocons_fit *taper_create_ordered(int n, int p, int r, const double *locs, const double *X, const double *z,
+                                        const double *smooth_limits, int device, int nnz, const int *colindices,
+                                        const int *rowpointers, const double *taper_entries, const std::vector<int> &perm,
+                                        bool check_fit);
+
 extern "C" cocons_fit *cocons_fit_create_taper(int n, int p, int r, const double *locs, const double *X, const double *z,
                                                const double *smooth_limits, int device, int nnz, const int *colindices,
                                                const int *rowpointers, const double *taper_entries)
@@ -670,7 +682,7 @@ extern "C" cocons_fit *cocons_fit_create_taper(int n, int p, int r, const double
     // Order the observations by reverse Cuthill-McKee on the pattern (COCONS_TAPER_RCM=0: keep the caller's order):
     // the value does not depend on the order, the envelope of the factor does, and the factorisation below
     // only touches tiles inside it.
-    std::vector<int> perm(n), inv(n);            // perm[new] = old, inv[old] = new
+    std::vector<int> perm(n);                    // perm[new] = old
     {
         const char *e = getenv("COCONS_TAPER_RCM");
         const bool rcm = e ? atoi(e) != 0 : true;
@@ -710,8 +722,21 @@ extern "C" cocons_fit *cocons_fit_create_taper(int n, int p, int r, const double
             }
             for (int i = 0; i < n; ++i) perm[i] = order[n - 1 - i];
         }
-        for (int i = 0; i < n; ++i) inv[perm[i]] = i;
     }
+    return taper_create_ordered(n, p, r, locs, X, z, smooth_limits, device, nnz, colindices, rowpointers, taper_entries, perm,
+                                false);
+}
+
+// The taper handle of a validated pattern with its observations in the order perm (perm[new] = index in the order the
+// arguments come in).  check_fit: refuse, with a message that says so, a buffer larger than the device's free memory
+// (an order with a wide envelope: cocons_sim_taper's twin) before any allocation is tried.
+static cocons_fit *taper_create_ordered(int n, int p, int r, const double *locs, const double *X, const double *z,
+                                        const double *smooth_limits, int device, int nnz, const int *colindices,
+                                        const int *rowpointers, const double *taper_entries, const std::vector<int> &perm,
+                                        bool check_fit)
+{
+    std::vector<int> inv(n);                     // inv[old] = new
+    for (int i = 0; i < n; ++i) inv[perm[i]] = i;
     std::vector<double> pl((size_t)2 * n), pX((size_t)p * n), pz((size_t)r * n);
     for (int i = 0; i < n; ++i) {
         const int o = perm[i];
@@ -736,6 +761,9 @@ extern "C" cocons_fit *cocons_fit_create_taper(int n, int p, int r, const double
     // envelope per tile column: row i of the factor is non-zero from its first stored column on
     f->taper_hi = new std::vector<int>(f->nt, 0);
     f->taper_inv = new std::vector<int>(inv);
+    f->h_trp = new std::vector<int>(prp);
+    f->h_tci = new std::vector<int>(pci);
+    f->h_tval = new std::vector<double>(pte);
     {
         std::vector<int> &hi = *f->taper_hi;
         for (int c = 0; c < f->nt; ++c) hi[c] = c + 1 < f->nt ? c + 1 : f->nt;
@@ -769,6 +797,20 @@ extern "C" cocons_fit *cocons_fit_create_taper(int n, int p, int r, const double
             // packed band storage unless switched off (COCONS_TAPER_PACKED=0: the dense n x n buffer, only its band used)
             const char *pk = getenv("COCONS_TAPER_PACKED");
             if (!(pk && atoi(pk) == 0) && f->taper_maxband < f->nt) f->skew = f->taper_maxband;
+        }
+    }
+    if (check_fit) {
+        const size_t bytes = ((size_t)(f->skew > 0 ? f->skew * TILE : f->npad) + (size_t)round_up(r + p, TILE)) *
+                             (size_t)f->npad * sizeof(double);
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes > free_b) {
+            char msg[192];
+            snprintf(msg, sizeof msg, "%.2f GB (envelope of %d tile rows), %.2f GB free", bytes * 1e-9,
+                     f->taper_maxband > 0 ? f->taper_maxband : f->nt, free_b * 1e-9);
+            fail(-4, "the factor buffer of this order does not fit the device: %s", msg);
+            f->op_mu->unlock();
+            cocons_fit_destroy(f);
+            return nullptr;
         }
     }
     if (fit_alloc_matrix(f, r + p) != 0) { f->op_mu->unlock(); cocons_fit_destroy(f); return nullptr; }
@@ -1893,6 +1935,11 @@ extern "C" int cocons_fit_engine_state(cocons_fit *f, int *out)
             out[1] += c->engine_retries;
             if (!out[2]) out[2] = c->engine_last_abort;
         }
+    // (so are the twin of cocons_sim_taper's pivot route)
+    if (cocons_fit *c = f->taper_twin) {
+        out[1] += c->engine_retries;
+        if (!out[2]) out[2] = c->engine_last_abort;
+    }
     return 0;
 }
 
@@ -2674,6 +2721,156 @@ extern "C" int cocons_predict_taper(cocons_fit *f, const double *theta, const do
     hipStreamSynchronize(s);
     hipFree(dci); hipFree(drp); hipFree(dtv);
     return st;
+}
+
+// ---------------------------------------------------------------------------
+// Sparse branch of cocoSim (R/sim.R:177-217) on a taper handle: S = taper o cov_rns_taper(theta) assembled and factored as
+// the objective does (the band schedule of the handle's envelope), then Y = L E + trend by band_trmm_kernel and the rows
+// of Y gathered into the caller's order.  pos[i] = position of the caller's observation i in f's order.  Y in the handle's
+// order: (L E)[k, s] + (X mean)[k], k a position of f.
+extern "C" int cocons_fit_taper_order(cocons_fit *f, int *pivot_out)
+{
+    FIT_ENTER(f);
+    if (f->taper_nnz <= 0) return fail(-1, "cocons_fit_taper_order: not a taper fit");
+    if (!pivot_out) return fail(-1, "cocons_fit_taper_order: null argument");
+    const std::vector<int> &inv = *f->taper_inv;
+    for (int i = 0; i < f->n; ++i) pivot_out[inv[i]] = i + 1;
+    return 0;
+}
+
+static int sim_taper_run(cocons_fit *f, const double *theta, const double *mean, int nsim, const double *iiderrors,
+                         const std::vector<int> &pos, double *out)
+{
+    const int n = f->n, p = f->p;
+    const size_t ne = (size_t)n * nsim;
+    double *dE = nullptr, *dY = nullptr, *dO = nullptr, *dtr = nullptr;
+    int *dpos = nullptr;
+    hipStream_t s = f->stream;
+    int rc = 0;
+    do {
+        hipError_t e;
+#define CKS(expr) if ((e = (expr)) != hipSuccess) { rc = fail(-100 - (int)e, "cocons_sim_taper: %s", hipGetErrorString(e)); break; }
+        CKS(hipMalloc(&dE, ne * sizeof(double)));
+        CKS(hipMalloc(&dY, ne * sizeof(double)));
+        CKS(hipMalloc(&dO, ne * sizeof(double)));
+        CKS(hipMalloc(&dtr, (size_t)n * sizeof(double)));
+        CKS(hipMalloc(&dpos, (size_t)n * sizeof(int)));
+        {
+            // the draws through the same NaN canonicalisation as the handle's own data (no all-ones NaN enters the device)
+            std::vector<double> hE(ne);
+            for (size_t i = 0; i < ne; ++i) hE[i] = canon_nan(iiderrors[i]);
+            // trend = X %*% mean on the host (O(n p)), in the handle's order (h_X is stored in it), as cocons_sim_dense does
+            std::vector<double> tr(n, 0.0);
+            for (int j = 0; j < p; ++j)
+                for (int i = 0; i < n; ++i) tr[i] += (*f->h_X)[(size_t)i + (size_t)j * n] * mean[j];
+            for (int i = 0; i < n; ++i) tr[i] = canon_nan(tr[i]);
+            CKS(hipMemcpyAsync(dE, hE.data(), ne * sizeof(double), hipMemcpyHostToDevice, s));
+            CKS(hipMemcpyAsync(dtr, tr.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
+            CKS(hipMemcpyAsync(dpos, pos.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+            CKS(hipStreamSynchronize(s));      // the staging vectors go out of scope
+        }
+        for (;;) {
+            if ((rc = fit_alloc_matrix(f, 1))) break;
+            if ((rc = reset_info(f))) break;
+            f->nrhs_cur = 0;
+            CKS(hipEventRecord(f->ev[4], s));
+            if ((rc = assemble_sigma_taper(f, theta))) break;
+            {   // no right-hand sides: clear the rows under the matrix
+                RhsArgs ra;
+                memset(&ra, 0, sizeof ra);
+                ra.n = n; ra.p = p; ra.X = f->dX; ra.ldx = n; ra.src = f->dX; ra.lds = n;
+                ra.out = f->dA; ra.ld = f->lda; ra.row0 = f->npad; ra.nrows = 0; ra.nrows_zero = f->rhs_act;
+                ra.col0 = 0; ra.ncols_out = f->npad;
+                ra.skew = f->skew; ra.npad = f->npad;
+                launch_rhs_rows(ra, s);
+            }
+            if ((rc = factorize(f, main_view(f), nullptr))) break;
+            CKS(hipEventRecord(f->ev[5], s));
+            launch_band_trmm(f->dA, f->lda, f->skew, f->npad, f->d_thi, f->nt, n, dE, n, nsim, dtr, dY, n, s);
+            CKS(hipEventRecord(f->ev[6], s));
+            launch_gather_rows(dY, n, dpos, n, nsim, dO, n, s);
+            CKS(hipEventRecord(f->ev[7], s));
+            CKS(hipMemcpyAsync(out, dO, ne * sizeof(double), hipMemcpyDeviceToHost, s));
+            CKS(hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+            CKS(hipGetLastError());
+            CKS(hipStreamSynchronize(s));
+            rc = info_status(f);
+            if (engine_retry(f, rc)) continue;
+            if (rc == 0)
+                for (int q = 0; q < 3; ++q) CKS(hipEventElapsedTime(&f->sim_ms[q], f->ev[4 + q], f->ev[5 + q]));
+            break;
+        }
+#undef CKS
+    } while (0);
+    hipStreamSynchronize(s);
+    hipFree(dE); hipFree(dY); hipFree(dO); hipFree(dtr); hipFree(dpos);
+    return rc;
+}
+
+extern "C" int cocons_sim_taper(cocons_fit *f, const double *theta, const double *mean, int nsim, const double *iiderrors,
+                                const int *pivot, double *out)
+{
+    FIT_ENTER(f);
+    if (f->taper_nnz <= 0) return fail(-1, "cocons_sim_taper: not a taper fit (cocons_sim_dense simulates on a dense handle)");
+    if (!theta || !mean || nsim <= 0 || !iiderrors || !out) return fail(-1, "cocons_sim_taper: bad argument");
+    const int n = f->n;
+    const std::vector<int> &inv = *f->taper_inv;          // inv[caller index] = position in f's order
+    std::vector<int> tperm;                               // pivot route: twin position k <- position tperm[k] of f
+    bool own = true;
+    if (pivot) {
+        std::vector<char> seen(n, 0);
+        tperm.resize(n);
+        for (int k = 0; k < n; ++k) {
+            const int o = pivot[k] - 1;
+            if (o < 0 || o >= n || seen[o]) return fail(-1, "cocons_sim_taper: pivot is not a permutation of 1..n");
+            seen[o] = 1;
+            tperm[k] = inv[o];
+            if (tperm[k] != k) own = false;
+        }
+    }
+    std::vector<int> pos(n);
+    if (own) {                                            // the handle's own order: no twin
+        for (int i = 0; i < n; ++i) pos[i] = inv[i];
+        return sim_taper_run(f, theta, mean, nsim, iiderrors, pos, out);
+    }
+    // draw-equal route: the factor of S[pivot, pivot] -- a taper handle in that order, built once and kept while the callers
+    // pass the same pivot (the fill-reducing order of spam's chol: computed once per coco object)
+    if (!f->taper_twin || *f->twin_perm != tperm) {
+        if (f->taper_twin) { cocons_fit_destroy(f->taper_twin); f->taper_twin = nullptr; }
+        delete f->twin_perm; f->twin_perm = nullptr;
+        cocons_fit *t = taper_create_ordered(n, f->p, f->r, f->h_locs->data(), f->h_X->data(), f->h_z->data(), f->smooth_limits,
+                                             f->device, (int)f->h_tci->size(), f->h_tci->data(), f->h_trp->data(),
+                                             f->h_tval->data(), tperm, true);
+        if (!t) {
+            const std::string why = g_err;
+            return fail(-4, "cocons_sim_taper: no taper handle in the given pivot order (%s); pivot = NULL simulates in the "
+                            "handle's own order (same distribution, another field for the same draws)", why.c_str());
+        }
+        f->taper_twin = t;
+        f->twin_perm = new std::vector<int>(tperm);
+    }
+    for (int k = 0; k < n; ++k) pos[pivot[k] - 1] = k;
+    std::lock_guard<std::recursive_mutex> twin_guard(*f->taper_twin->op_mu);
+    if (int rc = fit_check(f->taper_twin)) return rc;
+    return sim_taper_run(f->taper_twin, theta, mean, nsim, iiderrors, pos, out);
+}
+
+// (diagnostics) device times of the last successful cocons_sim_taper on the handle, in ms: assembly + factorisation,
+// band product, gather into the caller's order (the twin's, when that call took the pivot route); out4[3] = the 128 x 128
+// tiles of the envelope band_trmm_kernel reads per block of 64 draws
+extern "C" int cocons_debug_sim_taper_ms(cocons_fit *f, int twin, double *out4)
+{
+    FIT_ENTER(f);
+    if (!out4) return fail(-1, "cocons_debug_sim_taper_ms: null argument");
+    const cocons_fit *g = twin ? f->taper_twin : f;
+    if (!g) return fail(-1, "cocons_debug_sim_taper_ms: the handle has no twin");
+    if (g->taper_nnz <= 0) return fail(-1, "cocons_debug_sim_taper_ms: not a taper fit");
+    for (int q = 0; q < 3; ++q) out4[q] = g->sim_ms[q];
+    double tiles = 0;
+    if (g->taper_hi->empty()) tiles = 0.5 * g->nt * (g->nt + 1.0);
+    else for (int c = 0; c < g->nt; ++c) tiles += (*g->taper_hi)[c] - c;
+    out4[3] = tiles;
+    return 0;
 }
 
 // ---------------------------------------------------------------------------

@@ -2513,6 +2513,134 @@ void launch_trmm_lower(const double *A, size_t lda, int n, const double *E, int 
 }
 
 // ---------------------------------------------------------------------------
+// Y = L E + trend for the factor a band-limited factorisation leaves (taper handles: cocoSim's sparse branch,
+// (t(iiderrors) %*% cholS) + trend, R/sim.R:214-216).  One workgroup per (128-row tile row I, block of BT_COLS draws):
+// it walks the tile columns c of row I inside the envelope (hi[c] > I, hi monotone: a suffix of [0, I]), stages the
+// 128 x 64 block of E that column c multiplies in LDS and multiplies the band tile L(I, c) into it on
+// v_mfma_f64_16x16x4_f64, so each band tile is read once per BT_COLS draws.  Wave w owns rows 32 w .. 32 w + 31 of the
+// tile row (two 16-row blocks) and all four 16-column draw blocks: eight accumulators in blk layout.  Only the lower
+// triangle of the diagonal tile is read; E's rows >= n and columns >= nsim are staged as zeros and never read, rows and
+// columns of Y beyond n / nsim are not written.  The sum order of every element is fixed (c ascending, then the 16-column
+// k blocks, then the MFMA's own order): two launches give identical bits.
+constexpr int BT_COLS = 64;
+constexpr size_t BT_LDS_BYTES = (size_t)TILE * BT_COLS * sizeof(double);      // 64 KiB
+
+// E staged for the Q operand of blk_mma: 16 x 16 blocks (k block kb = obs / 16, draw block jb = draw / 16) of 256 doubles,
+// element (draw j, obs k) of a block at k * 16 + (j ^ k): the XOR spreads the staging stores (consecutive obs) over the
+// banks and leaves every read of lds_blk's shape a permutation of 64 contiguous doubles
+__device__ __forceinline__ int bt_lds_index(int k, int j)
+{
+    return (((k >> 4) * (BT_COLS / 16) + (j >> 4)) << 8) + ((k & 15) << 4) + ((j ^ k) & 15);
+}
+
+__global__ void __launch_bounds__(256)
+band_trmm_kernel(const double *A, size_t lda, int skew, int npad, const int *hi, int n, const double *E, int lde,
+                 int nsim, const double *trend, double *Y, int ldy)
+{
+    extern __shared__ double Es[];
+    const int I = blockIdx.x, s0 = blockIdx.y * BT_COLS;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // first tile column whose envelope reaches tile row I (hi[I] > I always)
+    int c0 = 0;
+    if (hi) {
+        int lo = 0, up = I;
+        while (lo < up) {
+            const int mid = (lo + up) >> 1;
+            if (hi[mid] > I) up = mid; else lo = mid + 1;
+        }
+        c0 = lo;
+    }
+    d4 acc[2][4];
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int jb = 0; jb < 4; ++jb) acc[rb][jb] = d4{0.0, 0.0, 0.0, 0.0};
+    const int row0 = I * TILE + 32 * wave;        // first row of the wave's two 16-row blocks
+    for (int c = c0; c <= I; ++c) {
+        __syncthreads();                          // every wave is done with the previous block of E
+        for (int e = threadIdx.x; e < TILE * BT_COLS; e += 256) {
+            const int k = e & (TILE - 1), j = e >> 7;
+            const int gk = c * TILE + k, gj = s0 + j;
+            Es[bt_lds_index(k, j)] = (gk < n && gj < nsim) ? E[(size_t)gk + (size_t)gj * lde] : 0.0;
+        }
+        __syncthreads();
+        // tile column c addressed by global row and column indices (kernels.h band_index / band_base)
+        const double *Ac = skew ? A - (ptrdiff_t)TILE * c : A;
+        const bool diag = c == I;
+#pragma unroll
+        for (int kb = 0; kb < TILE / 16; ++kb) {
+            if (diag && kb > 2 * wave + 1) break;          // above the diagonal for both of the wave's row blocks
+            d4 P[2];
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb) {
+                const int lb = 2 * wave + rb;              // 16-row block inside the tile
+                if (diag && kb > lb) { P[rb] = d4{0.0, 0.0, 0.0, 0.0}; continue; }
+                P[rb] = glb_blk(Ac, lda, row0 + 16 * rb, c * TILE + 16 * kb, lane);
+                if (diag && kb == lb) {                    // lower triangle of the diagonal block: row lane & 15, col 4 r + lane >> 4
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (4 * r + (lane >> 4) > (lane & 15)) P[rb][r] = 0.0;
+                }
+            }
+#pragma unroll
+            for (int jb = 0; jb < 4; ++jb) {
+                const double *blk = Es + ((kb * (BT_COLS / 16) + jb) << 8);
+                d4 Q;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int k = (lane >> 4) + 4 * r, j = lane & 15;
+                    Q[r] = blk[(k << 4) + ((j ^ k) & 15)];
+                }
+                blk_mma(acc[0][jb], P[0], Q);
+                blk_mma(acc[1][jb], P[1], Q);
+            }
+        }
+    }
+    // acc[rb][jb] in blk layout: row (lane & 15) of the 16-row block, draw 4 r + (lane >> 4) of the 16-draw block
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb) {
+        const int i = row0 + 16 * rb + (lane & 15);
+        if (i >= n) continue;
+        const double t = trend[i];
+#pragma unroll
+        for (int jb = 0; jb < 4; ++jb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int j = s0 + 16 * jb + 4 * r + (lane >> 4);
+                if (j < nsim) Y[(size_t)i + (size_t)j * ldy] = acc[rb][jb][r] + t;
+            }
+    }
+}
+
+static void set_dynamic_lds_once(const void *kernel, size_t bytes, std::atomic<unsigned long long> &done_mask);
+void launch_band_trmm(const double *A, size_t lda, int skew, int npad, const int *d_hi, int nt, int n, const double *E,
+                      int lde, int nsim, const double *trend, double *Y, int ldy, hipStream_t s)
+{
+    if (n <= 0 || nsim <= 0 || nt <= 0) return;
+    static std::atomic<unsigned long long> attr_done{0};
+    set_dynamic_lds_once((const void *)band_trmm_kernel, BT_LDS_BYTES, attr_done);
+    hipLaunchKernelGGL(band_trmm_kernel, dim3(nt, (nsim + BT_COLS - 1) / BT_COLS), dim3(256), BT_LDS_BYTES, s,
+                       A, lda, skew, npad, d_hi, n, E, lde, nsim, trend, Y, ldy);
+}
+
+// out[i + s ldo] = Y[pos[i] + s ldy], i < n, s < ncol: rows of Y (the handle's order) back to the caller's order
+__global__ void __launch_bounds__(256)
+gather_rows_kernel(const double *Y, int ldy, const int *pos, int n, int ncol, double *out, int ldo)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int k = pos[i];
+    for (int s = blockIdx.y; s < ncol; s += gridDim.y) out[(size_t)i + (size_t)s * ldo] = Y[(size_t)k + (size_t)s * ldy];
+}
+
+void launch_gather_rows(const double *Y, int ldy, const int *pos, int n, int ncol, double *out, int ldo, hipStream_t s)
+{
+    if (n <= 0 || ncol <= 0) return;
+    const int gy = ncol < 64 ? ncol : 64;
+    hipLaunchKernelGGL(gather_rows_kernel, dim3((n + 255) / 256, gy), dim3(256), 0, s, Y, ldy, pos, n, ncol, out, ldo);
+}
+
+// ---------------------------------------------------------------------------
 // the attribute that allows more than 64 KB of dynamic LDS is per kernel and device: set once, not per launch
 static void set_dynamic_lds_once(const void *kernel, size_t bytes, std::atomic<unsigned long long> &done_mask)
 {

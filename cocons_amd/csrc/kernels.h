@@ -266,5 +266,13 @@ void launch_row_reduce(const double *A, size_t lda, int n, int rowy, int row0, i
 // Y = L E + trend (lower factor L in A), E n x nsim, Y n x nsim
 void launch_trmm_lower(const double *A, size_t lda, int n, const double *E, int lde, int nsim,
                        const double *trend, double *Y, int ldy, hipStream_t s);
+// the same for the factor of a band-limited factorisation (taper handles): A as the factorisation leaves it -- packed band
+// (skew > 0) or dense (skew = 0) --, d_hi the device copy of its envelope (FactorView::hi; nullptr = every tile c <= I),
+// nt tile columns; reads only tiles inside the envelope, only the lower triangle of diagonal tiles, only rows < n of E.
+// Each band tile is read once per 64 draws; the sum order is fixed (bit-identical launches).
+void launch_band_trmm(const double *A, size_t lda, int skew, int npad, const int *d_hi, int nt, int n, const double *E,
+                      int lde, int nsim, const double *trend, double *Y, int ldy, hipStream_t s);
+// out[i + s ldo] = Y[pos[i] + s ldy] for i < n, s < ncol
+void launch_gather_rows(const double *Y, int ldy, const int *pos, int n, int ncol, double *out, int ldo, hipStream_t s);
 
 }  // namespace cocons

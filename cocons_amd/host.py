@@ -384,6 +384,48 @@ class CoconsTaperFit(CoconsFit):
         return st, qf
 
 
+    def sim_core(self, theta_list, iiderrors, pivot=None):
+        """Fields of the sparse branch of cocoSim (R/sim.R:177-217), n x nsim: (L_P E)[k] + (X mean) scattered to rows
+        pivot[k] - 1, L_P L_P' = S[pivot, pivot].  pivot = None: the handle's own order (same distribution, another field
+        for the same draws); spam's ordering(chol(ref_taper)): the reference's fields to rounding."""
+        E = _f(np.asarray(iiderrors, dtype=np.float64).reshape(self.n, -1))
+        T = theta_table(theta_list)
+        mean = np.ascontiguousarray(np.asarray(theta_list["mean"], dtype=np.float64))
+        piv = None
+        if pivot is not None:
+            piv = np.ascontiguousarray(np.asarray(pivot).ravel(), dtype=np.int32)
+            if piv.size != self.n:
+                raise ValueError("pivot must have length n")
+        out = np.empty(E.shape, order="F")
+        _lib.check(self._L.cocons_sim_taper(self._h, _p(T), _p(mean), E.shape[1], _p(E), None if piv is None else _ip(piv),
+                                            _p(out)), "cocons_sim_taper")
+        return out
+
+    def order(self):
+        """The handle's own order of the observations: 1-based caller indices by position (reverse Cuthill-McKee)."""
+        piv = np.empty(self.n, dtype=np.int32)
+        _lib.check(self._L.cocons_fit_taper_order(self._h, _ip(piv)), "cocons_fit_taper_order")
+        return piv
+
+
+def cocoSim_sparse(theta_list, locs, X_std, smooth_limits, z, ref_taper, iiderrors, pivot=None, fit=None):
+    """Sparse branch of cocoSim, R/sim.R:177-217, from the point where the scaled design matrix, the theta list and
+    ref_taper ((colindices, rowpointers, entries)) exist.  `iiderrors` is the n x nsim matrix of N(0,1) draws; with
+    pivot = spam::ordering(spam::chol(ref_taper)) the fields equal the reference's to rounding.  The sparse branch has
+    no fixed-smoothness override (:141-145 belong to the dense branch).  Returns n x nsim."""
+    E = np.asarray(iiderrors, dtype=np.float64)
+    n = np.asarray(X_std).shape[0]
+    f, own = (fit, False) if fit is not None else (CoconsTaperFit(locs, X_std, z, smooth_limits, *ref_taper), True)
+    try:
+        try:
+            return f.sim_core(theta_list, E.reshape(n, -1), pivot=pivot)
+        except CholeskyError:
+            raise RuntimeError("Cholesky error")          # spam::chol's error propagates in the reference
+    finally:
+        if own:
+            f.close()
+
+
 def cocoPredict_sparse(theta_list, locs, newlocs, X_std, X_pred_std, smooth_limits, z, ref_taper, pred_taper,
                        type="pred", fit=None):
     """Sparse branch of cocoPredict, R/predict.R:190-283, from the point where the scaled design matrices, the

@@ -161,3 +161,14 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
   if (res[[1]] > 0L) stop("Cholesky error")
   res[[2]]
 }
+
+# sparse branch of cocoSim (R/sim.R:177-217): the lines from cov_rns_taper to the sweep (:193-216) become
+#   fields <- .cocons.hip.sim.taper(fit, theta_list, iiderrors, pivot)     # fit: cocons_hip_taper_fit(...)
+# pivot = spam::ordering(spam::chol(ref_taper)) gives the reference's fields to rounding (MMD depends only on the pattern:
+# compute it once per coco object); pivot = NULL simulates in the handle's own order -- same distribution, other fields
+.cocons.hip.sim.taper <- function(fit, theta_list, iiderrors, pivot = NULL) {
+  if (!is.null(pivot)) pivot <- as.integer(pivot)
+  res <- .Call(`_cocons_hip_sim_taper`, fit, theta_list[-1], theta_list$mean, as.matrix(iiderrors), pivot)
+  if (res[[1]] > 0L) stop("Cholesky error")
+  res[[2]]
+}

@@ -609,6 +609,26 @@ SEXP _cocons_hip_predict_taper(SEXP fitp, SEXP theta, SEXP mean, SEXP z_col, SEX
     return out;
 }
 
+/* sparse branch of cocoSim (R/sim.R:177-217) on a taper handle: iiderrors n x nsim -> list(status, n x nsim fields).
+ * pivot: R NULL (the handle's own order: same distribution, another field for the same draws) or an integer vector,
+ * spam::ordering(spam::chol(ref_taper)) for the reference's fields to rounding */
+SEXP _cocons_hip_sim_taper(SEXP fitp, SEXP theta, SEXP mean, SEXP iiderrors, SEXP pivot)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), n = fit_n(fitp), nsim = Rf_ncols(iiderrors);
+    if (Rf_nrows(iiderrors) != n) Rf_error("iiderrors must have n rows");
+    if (!Rf_isNull(pivot) && (!Rf_isInteger(pivot) || XLENGTH(pivot) != (R_xlen_t)n))
+        Rf_error("pivot must be NULL or an integer vector of length n");
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    SEXP v = PROTECT(Rf_allocMatrix(REALSXP, n, nsim));
+    int rc = cocons_sim_taper(f, T, REAL(mean), nsim, REAL(iiderrors), Rf_isNull(pivot) ? NULL : INTEGER(pivot), REAL(v));
+    hip_check(rc, "cocoSim (sparse)");
+    SEXP out = status_value(rc, v);
+    UNPROTECT(1);
+    return out;
+}
+
 /* ---- registration (replaces src/RcppExports.cpp:105-118) --------------------------------------- */
 static const R_CallMethodDef CallEntries[] = {
     {"_cocons_sumsmoothlone", (DL_FUNC)&_cocons_sumsmoothlone, 3},
@@ -632,6 +652,7 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_predict_taper", (DL_FUNC)&_cocons_hip_predict_taper, 9},
     {"_cocons_hip_sim", (DL_FUNC)&_cocons_hip_sim, 5},
     {"_cocons_hip_sim_cond", (DL_FUNC)&_cocons_hip_sim_cond, 8},
+    {"_cocons_hip_sim_taper", (DL_FUNC)&_cocons_hip_sim_taper, 5},
     {"_cocons_hip_cov_rows", (DL_FUNC)&_cocons_hip_cov_rows, 5},
     {"_cocons_hip_multi_create", (DL_FUNC)&_cocons_hip_multi_create, 5},
     {"_cocons_hip_multi_neg2loglik", (DL_FUNC)&_cocons_hip_multi_neg2loglik, 3},

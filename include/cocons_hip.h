@@ -107,6 +107,21 @@ int cocons_predict_taper(cocons_fit *fit, const double *theta, const double *mea
                          const int *rowpointers_pred, const double *taper_entries_pred,
                          double *stochastic, double *quadform);
 
+/* Sparse branch of cocoSim (R/sim.R:177-217) on a taper handle.  S = taper o cov_rns_taper(theta) (the handle's pattern
+ * and taper entries), ordered by `pivot` (1-based permutation of 1..n, spam's `ordering(cholS)`; NULL = the handle's own
+ * order, see cocons_fit_taper_order).  With L_P L_P' = S[pivot, pivot] and E = iiderrors (n x nsim, column-major, used
+ * as given):   out[pivot[k]-1 + s*n] = (L_P E)[k, s] + (X mean)[pivot[k]-1]
+ * -- exactly (t(iiderrors) %*% cholS)[, iord] + trend of :216 when pivot is spam's.  0 / k > 0 (failing minor, in the
+ * pivoted order) / < 0.  Refused on a dense handle.
+ * pivot = NULL (or the handle's own order): the handle's reverse Cuthill-McKee order and narrow envelope -- a field with
+ * covariance S, but for the same draws not the reference's field (the factor of a permuted matrix is not the permuted
+ * factor).  Any other pivot: a second taper handle in that order, built on first use, kept while calls pass the same
+ * pivot and destroyed with this one; an order whose envelope does not fit the device is refused (< 0), never replaced. */
+int cocons_sim_taper(cocons_fit *fit, const double *theta, const double *mean, int nsim,
+                     const double *iiderrors, const int *pivot, double *out);
+/* the handle's own order (RCM unless COCONS_TAPER_RCM=0): pivot_out[k] = 1-based caller index at position k */
+int cocons_fit_taper_order(cocons_fit *fit, int *pivot_out);
+
 /* ---- fit handle: everything that is constant over an optimisation -------------
  * Created once per cocoOptim / getHessian call from the arguments the reference
  * passes unchanged to every GetNeg2loglikelihood* evaluation

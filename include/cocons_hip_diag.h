@@ -56,6 +56,11 @@ int cocons_debug_assembly_loop(struct cocons_fit *fit, const double *theta, int 
  * out[4] = steps.  tools/dag_replay.py.  */
 int cocons_debug_dag_replay(struct cocons_fit *fit, const double *theta, const double *mean, int reps, double *out5);
 
+/* Device times of the last successful cocons_sim_taper on the handle (twin != 0: on its pivot-order twin), out4[0..2] in ms:
+ * assembly + factorisation, the band product (band_trmm_kernel), the gather into the caller's order; out4[3] = the
+ * 128 x 128 envelope tiles the product reads per block of 64 draws.  tools/sim_taper_timing.py */
+int cocons_debug_sim_taper_ms(struct cocons_fit *fit, int twin, double *out4);
+
 #ifdef __cplusplus
 }
 #endif
