@@ -14,6 +14,7 @@
 
 #include <algorithm>
 #include <limits>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -94,6 +95,59 @@ static inline double canon_nan(double v)
     memcpy(&b, &v, sizeof b);
     return b == ~0ull ? std::numeric_limits<double>::quiet_NaN() : v;
 }
+
+// Host-to-device copy of caller or host-computed doubles through canon_nan.  The normal case is the plain copy; only when an
+// all-ones NaN is present is a canonical host copy staged, and the stream drained before that copy goes out of scope.
+static hipError_t upload_canon(double *dst, const double *src, size_t count, hipStream_t s)
+{
+    size_t first = 0;
+    for (unsigned long long b; first < count; ++first) {
+        memcpy(&b, src + first, sizeof b);
+        if (b == ~0ull) break;
+    }
+    if (first == count) return hipMemcpyAsync(dst, src, count * sizeof(double), hipMemcpyHostToDevice, s);
+    std::vector<double> stage(src, src + count);
+    for (size_t i = first; i < count; ++i) stage[i] = canon_nan(stage[i]);
+    hipError_t e = hipMemcpyAsync(dst, stage.data(), count * sizeof(double), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return e;
+}
+
+// One device allocation of a one-shot entry point, freed on every way out of it.
+template <class T> class DevBuf {
+    T *p_ = nullptr;
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p_, o.p_); return *this; }
+    ~DevBuf() { hipFree(p_); }
+    hipError_t alloc(size_t count) { hipFree(p_); p_ = nullptr; return hipMalloc(&p_, count * sizeof(T)); }
+    T *get() const { return p_; }
+    operator T *() const { return p_; }
+};
+
+// Declared AFTER a function's DevBufs, so that its destructor -- draining the stream the buffers are used on -- runs before
+// theirs, on every way out.  own: the stream was created for this call and is destroyed as well.
+struct StreamDrain {
+    hipStream_t s;
+    bool own;
+    ~StreamDrain()
+    {
+        if (!s) return;
+        hipStreamSynchronize(s);
+        if (own) hipStreamDestroy(s);
+    }
+    operator hipStream_t() const { return s; }
+};
+
+// HIPCHK for the one-shot entry points: the message names the entry point, the code is -100 - hipError_t
+#define HIPCHK_AT(who, expr)                                                                     \
+    do {                                                                                         \
+        hipError_t e__ = (expr);                                                                 \
+        if (e__ != hipSuccess) return fail(-100 - (int)e__, who ": %s", hipGetErrorString(e__)); \
+    } while (0)
 
 static void make_theta_vecs(const double *theta_in, int p, ThetaVecs &tv)
 {
@@ -1935,11 +1989,12 @@ extern "C" int cocons_fit_engine_state(cocons_fit *f, int *out)
             out[1] += c->engine_retries;
             if (!out[2]) out[2] = c->engine_last_abort;
         }
-    // (so are the twin of cocons_sim_taper's pivot route)
-    if (cocons_fit *c = f->taper_twin) {
-        out[1] += c->engine_retries;
-        if (!out[2]) out[2] = c->engine_last_abort;
-    }
+    // (so are the twin of cocons_sim_taper's pivot route and the unsorted clone cocons_sim_dense runs on)
+    for (cocons_fit *c : {f->taper_twin, f->unsorted})
+        if (c) {
+            out[1] += c->engine_retries;
+            if (!out[2]) out[2] = c->engine_last_abort;
+        }
     return 0;
 }
 
@@ -2266,41 +2321,43 @@ extern "C" int cocons_fit_profile(cocons_fit *f, const double *theta, const doub
     FIT_ENTER(f);
     if (int rc = no_taper(f, "cocons_fit_profile")) return rc;
     if (!theta || !mean || !ms || reps < 1) return fail(-1, "cocons_fit_profile: bad argument");
-    double acc[7] = {0, 0, 0, 0, 0, 0, 0};
-    double dag_ms = 0.0;
-    for (int it = 0; it < reps; ++it) {
-        std::vector<hipEvent_t> ev;
-        f->upd_flops = 0.0;
-        f->dag_flops = 0.0; f->dag_events = 0;
-        if (int rc = enqueue_eval(f, theta, mean, true, nullptr, 0, &ev, true)) return rc;
-        HIPCHK(hipStreamSynchronize(f->stream));
-        float t01, t12, t23, t03;
-        HIPCHK(hipEventElapsedTime(&t01, f->ev[0], f->ev[1]));
-        HIPCHK(hipEventElapsedTime(&t12, f->ev[1], f->ev[2]));
-        HIPCHK(hipEventElapsedTime(&t23, f->ev[2], f->ev[3]));
-        HIPCHK(hipEventElapsedTime(&t03, f->ev[0], f->ev[3]));
-        acc[0] += t01; acc[1] += t12; acc[2] += t23; acc[3] += t03;
-        double sum = 0;
-        for (size_t i = 0; i + 1 < ev.size(); i += 2) {
-            float t;
-            HIPCHK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-            sum += t;
-            if (i == 0 && f->dag_events) dag_ms += t;
+    for (;;) {
+        double acc[7] = {0, 0, 0, 0, 0, 0, 0};
+        double dag_ms = 0.0;
+        for (int it = 0; it < reps; ++it) {
+            std::vector<hipEvent_t> ev;
+            f->upd_flops = 0.0;
+            f->dag_flops = 0.0; f->dag_events = 0;
+            if (int rc = enqueue_eval(f, theta, mean, true, nullptr, 0, &ev, true)) return rc;
+            HIPCHK(hipStreamSynchronize(f->stream));
+            float t01, t12, t23, t03;
+            HIPCHK(hipEventElapsedTime(&t01, f->ev[0], f->ev[1]));
+            HIPCHK(hipEventElapsedTime(&t12, f->ev[1], f->ev[2]));
+            HIPCHK(hipEventElapsedTime(&t23, f->ev[2], f->ev[3]));
+            HIPCHK(hipEventElapsedTime(&t03, f->ev[0], f->ev[3]));
+            acc[0] += t01; acc[1] += t12; acc[2] += t23; acc[3] += t03;
+            double sum = 0;
+            for (size_t i = 0; i + 1 < ev.size(); i += 2) {
+                float t;
+                HIPCHK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
+                sum += t;
+                if (i == 0 && f->dag_events) dag_ms += t;
+            }
+            acc[6] += sum;
+            acc[5] = (double)(ev.size() / 2);
+            for (auto e : ev) hipEventDestroy(e);
         }
-        acc[6] += sum;
-        acc[5] = (double)(ev.size() / 2);
-        for (auto e : ev) hipEventDestroy(e);
+        for (int i = 0; i < 4; ++i) ms[i] = acc[i] / reps;
+        ms[5] = acc[5];
+        ms[6] = acc[6] / reps;
+        ms[4] = acc[5] > 0 ? ms[6] / acc[5] : 0.0;
+        ms[7] = f->upd_flops;
+        ms[8] = dag_ms / reps;
+        ms[9] = f->dag_flops;
+        int st = info_status(f);
+        if (engine_retry(f, st)) continue;
+        return st;
     }
-    for (int i = 0; i < 4; ++i) ms[i] = acc[i] / reps;
-    ms[5] = acc[5];
-    ms[6] = acc[6] / reps;
-    ms[4] = acc[5] > 0 ? ms[6] / acc[5] : 0.0;
-    ms[7] = f->upd_flops;
-    ms[8] = dag_ms / reps;
-    ms[9] = f->dag_flops;
-    int st = info_status(f);
-    if (engine_retry(f, st)) return cocons_fit_profile(f, theta, mean, reps, ms);
-    return st;
 }
 
 // (diagnostics) the covariance assembly of an evaluation ALONE, `reps` times back to back on the handle's stream between two
@@ -2337,58 +2394,43 @@ static int cov_common(int which, int n, int m, int p, const double *theta, const
     ThetaVecs tv;
     make_theta_vecs(theta, p, tv);
     ModeSel ms = select_mode(theta, p, sl, which);
-    hipStream_t s = nullptr;     // own non-blocking stream (the library never launches on the NULL stream)
-    double *dX = nullptr, *dl = nullptr, *dloc = nullptr, *dXp = nullptr, *dlp = nullptr, *dlocp = nullptr, *dout = nullptr;
     const size_t rows = which == 2 ? (size_t)m : (size_t)n;
-    int rc = 0;
-#define CKG(expr)                                                                 \
-    do {                                                                          \
-        hipError_t e__ = (expr);                                                  \
-        if (e__ != hipSuccess) {                                                  \
-            rc = fail(-100 - (int)e__, "cov_rns*: %s", hipGetErrorString(e__));   \
-            goto done;                                                            \
-        }                                                                         \
-    } while (0)
-    CKG(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    CKG(hipMalloc(&dX, (size_t)n * p * sizeof(double)));
-    CKG(hipMalloc(&dl, (size_t)n * 2 * sizeof(double)));
-    CKG(hipMalloc(&dloc, (size_t)LOCP_FIELDS * n * sizeof(double)));
-    CKG(hipMalloc(&dout, rows * (size_t)n * sizeof(double)));
-    CKG(hipMemcpyAsync(dX, X, (size_t)n * p * sizeof(double), hipMemcpyHostToDevice, s));
-    CKG(hipMemcpyAsync(dl, locs, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice, s));
-    {
-        LocArgs la;
-        la.n = n; la.p = p; la.X = dX; la.ldx = n; la.locs = dl; la.ldl = n;
-        la.out = dloc; la.stride = n; la.smooth_kind = ms.smooth_kind;
-        la.smooth_min = sl[0]; la.smooth_max = sl[1]; la.th = tv;
-        launch_loc_params(la, s);
-        PairArgs pa;
-        memset(&pa, 0, sizeof pa);
-        pa.n = n; pa.cols = dloc; pa.stride = n; pa.out = dout; pa.gr = ms.gr; pa.nu_fixed = ms.nu_fixed;
-        if (which == 2) {
-            CKG(hipMalloc(&dXp, (size_t)m * p * sizeof(double)));
-            CKG(hipMalloc(&dlp, (size_t)m * 2 * sizeof(double)));
-            CKG(hipMalloc(&dlocp, (size_t)LOCP_FIELDS * m * sizeof(double)));
-            CKG(hipMemcpyAsync(dXp, X_pred, (size_t)m * p * sizeof(double), hipMemcpyHostToDevice, s));
-            CKG(hipMemcpyAsync(dlp, locs_pred, (size_t)m * 2 * sizeof(double), hipMemcpyHostToDevice, s));
-            LocArgs lp = la;
-            lp.n = m; lp.X = dXp; lp.ldx = m; lp.locs = dlp; lp.ldl = m; lp.out = dlocp; lp.stride = m;
-            launch_loc_params(lp, s);
-            pa.m = m; pa.rows = dlocp; pa.stride_rows = m; pa.ld = m; pa.nrows_out = m; pa.ncols_out = n;
-            launch_pair_rect(ms.mode, pa, s);
-        } else {
-            pa.m = n; pa.rows = dloc; pa.stride_rows = n; pa.ld = n; pa.nrows_out = n; pa.ncols_out = n;
-            launch_pair_sym(ms.mode, true, pa, s);
-        }
+    DevBuf<double> dX, dl, dloc, dXp, dlp, dlocp, dout;
+    StreamDrain s{nullptr, true};     // own non-blocking stream (the library never launches on the NULL stream)
+    HIPCHK_AT("cov_rns*", hipStreamCreateWithFlags(&s.s, hipStreamNonBlocking));
+    HIPCHK_AT("cov_rns*", dX.alloc((size_t)n * p));
+    HIPCHK_AT("cov_rns*", dl.alloc((size_t)n * 2));
+    HIPCHK_AT("cov_rns*", dloc.alloc((size_t)LOCP_FIELDS * n));
+    HIPCHK_AT("cov_rns*", dout.alloc(rows * (size_t)n));
+    HIPCHK_AT("cov_rns*", upload_canon(dX, X, (size_t)n * p, s));
+    HIPCHK_AT("cov_rns*", upload_canon(dl, locs, (size_t)n * 2, s));
+    LocArgs la;
+    la.n = n; la.p = p; la.X = dX; la.ldx = n; la.locs = dl; la.ldl = n;
+    la.out = dloc; la.stride = n; la.smooth_kind = ms.smooth_kind;
+    la.smooth_min = sl[0]; la.smooth_max = sl[1]; la.th = tv;
+    launch_loc_params(la, s);
+    PairArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.n = n; pa.cols = dloc; pa.stride = n; pa.out = dout; pa.gr = ms.gr; pa.nu_fixed = ms.nu_fixed;
+    if (which == 2) {
+        HIPCHK_AT("cov_rns*", dXp.alloc((size_t)m * p));
+        HIPCHK_AT("cov_rns*", dlp.alloc((size_t)m * 2));
+        HIPCHK_AT("cov_rns*", dlocp.alloc((size_t)LOCP_FIELDS * m));
+        HIPCHK_AT("cov_rns*", upload_canon(dXp, X_pred, (size_t)m * p, s));
+        HIPCHK_AT("cov_rns*", upload_canon(dlp, locs_pred, (size_t)m * 2, s));
+        LocArgs lp = la;
+        lp.n = m; lp.X = dXp; lp.ldx = m; lp.locs = dlp; lp.ldl = m; lp.out = dlocp; lp.stride = m;
+        launch_loc_params(lp, s);
+        pa.m = m; pa.rows = dlocp; pa.stride_rows = m; pa.ld = m; pa.nrows_out = m; pa.ncols_out = n;
+        launch_pair_rect(ms.mode, pa, s);
+    } else {
+        pa.m = n; pa.rows = dloc; pa.stride_rows = n; pa.ld = n; pa.nrows_out = n; pa.ncols_out = n;
+        launch_pair_sym(ms.mode, true, pa, s);
     }
-    CKG(hipGetLastError());
-    CKG(hipMemcpyAsync(out, dout, rows * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
-    CKG(hipStreamSynchronize(s));
-done:
-    if (s) { hipStreamSynchronize(s); hipStreamDestroy(s); }
-    hipFree(dX); hipFree(dl); hipFree(dloc); hipFree(dXp); hipFree(dlp); hipFree(dlocp); hipFree(dout);
-#undef CKG
-    return rc;
+    HIPCHK_AT("cov_rns*", hipGetLastError());
+    HIPCHK_AT("cov_rns*", hipMemcpyAsync(out, dout, rows * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK_AT("cov_rns*", hipStreamSynchronize(s));
+    return 0;
 }
 
 extern "C" int cocons_cov_rns(int n, int p, const double *theta, const double *locs, const double *X,
@@ -2428,58 +2470,43 @@ static int taper_common(bool pred, int n, int m, int p, const double *theta, con
     for (int i = 0; i < p; ++i) tv.two_scale_je[i] = 2 * theta[TH_SCALE * p + i];   // FULL scale vector (cocons_taper.cpp:207)
     // smoothness dispatch of cov_rns_taper (:183-201); the prediction variant always takes the Bessel branch
     ModeSel ms = select_mode(theta, p, smooth_limits, pred ? 2 : 0);
-    hipStream_t s = nullptr;
-    double *dX = nullptr, *dl = nullptr, *dloc = nullptr, *dXp = nullptr, *dlp = nullptr, *dlocp = nullptr, *dout = nullptr;
-    int *dci = nullptr, *drp = nullptr;
-    int rc = 0;
-#define CKT(expr)                                                                 \
-    do {                                                                          \
-        hipError_t e__ = (expr);                                                  \
-        if (e__ != hipSuccess) {                                                  \
-            rc = fail(-100 - (int)e__, "cov_rns_taper*: %s", hipGetErrorString(e__)); \
-            goto done;                                                            \
-        }                                                                         \
-    } while (0)
-    CKT(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    CKT(hipMalloc(&dX, (size_t)n * p * sizeof(double)));
-    CKT(hipMalloc(&dl, (size_t)n * 2 * sizeof(double)));
-    CKT(hipMalloc(&dloc, (size_t)LOCP_FIELDS * n * sizeof(double)));
-    CKT(hipMalloc(&dout, (size_t)(nnz > 0 ? nnz : 1) * sizeof(double)));
-    CKT(hipMalloc(&dci, (size_t)(nnz > 0 ? nnz : 1) * sizeof(int)));
-    CKT(hipMalloc(&drp, (size_t)(nrows + 1) * sizeof(int)));
-    CKT(hipMemcpyAsync(dX, X, (size_t)n * p * sizeof(double), hipMemcpyHostToDevice, s));
-    CKT(hipMemcpyAsync(dl, locs, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice, s));
-    CKT(hipMemcpyAsync(dci, colindices, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, s));
-    CKT(hipMemcpyAsync(drp, rowpointers, (size_t)(nrows + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-    {
-        LocArgs la;
-        la.n = n; la.p = p; la.X = dX; la.ldx = n; la.locs = dl; la.ldl = n;
-        la.out = dloc; la.stride = n; la.smooth_kind = ms.smooth_kind;
-        la.smooth_min = smooth_limits[0]; la.smooth_max = smooth_limits[1]; la.th = tv;
-        launch_loc_params(la, s);
-        if (pred) {
-            CKT(hipMalloc(&dXp, (size_t)m * p * sizeof(double)));
-            CKT(hipMalloc(&dlp, (size_t)m * 2 * sizeof(double)));
-            CKT(hipMalloc(&dlocp, (size_t)LOCP_FIELDS * m * sizeof(double)));
-            CKT(hipMemcpyAsync(dXp, X_pred, (size_t)m * p * sizeof(double), hipMemcpyHostToDevice, s));
-            CKT(hipMemcpyAsync(dlp, locs_pred, (size_t)m * 2 * sizeof(double), hipMemcpyHostToDevice, s));
-            LocArgs lp = la;
-            lp.n = m; lp.X = dXp; lp.ldx = m; lp.locs = dlp; lp.ldl = m; lp.out = dlocp; lp.stride = m;
-            launch_loc_params(lp, s);
-            launch_taper(MODE_GEOM, true, m, nnz, dci, drp, dlocp, m, dloc, n, 0.0, dout, s);
-        } else {
-            launch_taper(ms.mode, false, n, nnz, dci, drp, dloc, n, dloc, n, ms.nu_fixed, dout, s);
-        }
+    const size_t nz = nnz > 0 ? (size_t)nnz : 1;
+    DevBuf<double> dX, dl, dloc, dXp, dlp, dlocp, dout;
+    DevBuf<int> dci, drp;
+    StreamDrain s{nullptr, true};
+    HIPCHK_AT("cov_rns_taper*", hipStreamCreateWithFlags(&s.s, hipStreamNonBlocking));
+    HIPCHK_AT("cov_rns_taper*", dX.alloc((size_t)n * p));
+    HIPCHK_AT("cov_rns_taper*", dl.alloc((size_t)n * 2));
+    HIPCHK_AT("cov_rns_taper*", dloc.alloc((size_t)LOCP_FIELDS * n));
+    HIPCHK_AT("cov_rns_taper*", dout.alloc(nz));
+    HIPCHK_AT("cov_rns_taper*", dci.alloc(nz));
+    HIPCHK_AT("cov_rns_taper*", drp.alloc((size_t)nrows + 1));
+    HIPCHK_AT("cov_rns_taper*", upload_canon(dX, X, (size_t)n * p, s));
+    HIPCHK_AT("cov_rns_taper*", upload_canon(dl, locs, (size_t)n * 2, s));
+    HIPCHK_AT("cov_rns_taper*", hipMemcpyAsync(dci, colindices, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK_AT("cov_rns_taper*", hipMemcpyAsync(drp, rowpointers, (size_t)(nrows + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+    LocArgs la;
+    la.n = n; la.p = p; la.X = dX; la.ldx = n; la.locs = dl; la.ldl = n;
+    la.out = dloc; la.stride = n; la.smooth_kind = ms.smooth_kind;
+    la.smooth_min = smooth_limits[0]; la.smooth_max = smooth_limits[1]; la.th = tv;
+    launch_loc_params(la, s);
+    if (pred) {
+        HIPCHK_AT("cov_rns_taper*", dXp.alloc((size_t)m * p));
+        HIPCHK_AT("cov_rns_taper*", dlp.alloc((size_t)m * 2));
+        HIPCHK_AT("cov_rns_taper*", dlocp.alloc((size_t)LOCP_FIELDS * m));
+        HIPCHK_AT("cov_rns_taper*", upload_canon(dXp, X_pred, (size_t)m * p, s));
+        HIPCHK_AT("cov_rns_taper*", upload_canon(dlp, locs_pred, (size_t)m * 2, s));
+        LocArgs lp = la;
+        lp.n = m; lp.X = dXp; lp.ldx = m; lp.locs = dlp; lp.ldl = m; lp.out = dlocp; lp.stride = m;
+        launch_loc_params(lp, s);
+        launch_taper(MODE_GEOM, true, m, nnz, dci, drp, dlocp, m, dloc, n, 0.0, dout, s);
+    } else {
+        launch_taper(ms.mode, false, n, nnz, dci, drp, dloc, n, dloc, n, ms.nu_fixed, dout, s);
     }
-    CKT(hipGetLastError());
-    if (nnz > 0) CKT(hipMemcpyAsync(out, dout, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost, s));
-    CKT(hipStreamSynchronize(s));
-done:
-    if (s) { hipStreamSynchronize(s); hipStreamDestroy(s); }
-    hipFree(dX); hipFree(dl); hipFree(dloc); hipFree(dXp); hipFree(dlp); hipFree(dlocp); hipFree(dout);
-    hipFree(dci); hipFree(drp);
-#undef CKT
-    return rc;
+    HIPCHK_AT("cov_rns_taper*", hipGetLastError());
+    if (nnz > 0) HIPCHK_AT("cov_rns_taper*", hipMemcpyAsync(out, dout, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK_AT("cov_rns_taper*", hipStreamSynchronize(s));
+    return 0;
 }
 
 extern "C" int cocons_cov_rns_taper(int n, int p, const double *theta, const double *locs, const double *X,
@@ -2514,38 +2541,47 @@ extern "C" int cocons_cov_rows(cocons_fit *f, const double *theta, int classic, 
     ThetaVecs tv;
     make_theta_vecs(theta, p, tv);
     ModeSel ms = select_mode(theta, p, f->smooth_limits, classic ? 1 : 0);
-    hipStream_t s = f->stream;
-    double *dX = nullptr, *dl = nullptr, *dloc = nullptr, *dout = nullptr;
-    int *didx = nullptr;
-    int rc = 0;
-    do {
-        hipError_t e;
-#define CKR(expr) if ((e = (expr)) != hipSuccess) { rc = fail(-100 - (int)e, "cocons_cov_rows: %s", hipGetErrorString(e)); break; }
-        CKR(hipMalloc(&dX, (size_t)n * p * sizeof(double)));
-        CKR(hipMalloc(&dl, (size_t)n * 2 * sizeof(double)));
-        CKR(hipMalloc(&dloc, (size_t)LOCP_FIELDS * n * sizeof(double)));
-        CKR(hipMalloc(&dout, (size_t)nidx * n * sizeof(double)));
-        CKR(hipMalloc(&didx, (size_t)nidx * sizeof(int)));
-        CKR(hipMemcpyAsync(dX, f->h_X->data(), (size_t)n * p * sizeof(double), hipMemcpyHostToDevice, s));
-        CKR(hipMemcpyAsync(dl, f->h_locs->data(), (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice, s));
-        CKR(hipMemcpyAsync(didx, idx, (size_t)nidx * sizeof(int), hipMemcpyHostToDevice, s));
-        LocArgs la;
-        la.n = n; la.p = p; la.X = dX; la.ldx = n; la.locs = dl; la.ldl = n;
-        la.out = dloc; la.stride = n; la.smooth_kind = ms.smooth_kind;
-        la.smooth_min = f->smooth_limits[0]; la.smooth_max = f->smooth_limits[1]; la.th = tv;
-        launch_loc_params(la, s);
-        launch_cov_rows(ms.mode, n, nidx, didx, dloc, n, ms.gr, ms.nu_fixed, cor, dout, s);
-        CKR(hipGetLastError());
-        CKR(hipMemcpyAsync(out, dout, (size_t)nidx * n * sizeof(double), hipMemcpyDeviceToHost, s));
-        CKR(hipStreamSynchronize(s));
-#undef CKR
-    } while (0);
-    hipStreamSynchronize(s);
-    hipFree(dX); hipFree(dl); hipFree(dloc); hipFree(dout); hipFree(didx);
-    return rc;
+    DevBuf<double> dX, dl, dloc, dout;
+    DevBuf<int> didx;
+    StreamDrain s{f->stream, false};
+    HIPCHK_AT("cocons_cov_rows", dX.alloc((size_t)n * p));
+    HIPCHK_AT("cocons_cov_rows", dl.alloc((size_t)n * 2));
+    HIPCHK_AT("cocons_cov_rows", dloc.alloc((size_t)LOCP_FIELDS * n));
+    HIPCHK_AT("cocons_cov_rows", dout.alloc((size_t)nidx * n));
+    HIPCHK_AT("cocons_cov_rows", didx.alloc((size_t)nidx));
+    HIPCHK_AT("cocons_cov_rows", upload_canon(dX, f->h_X->data(), (size_t)n * p, s));
+    HIPCHK_AT("cocons_cov_rows", upload_canon(dl, f->h_locs->data(), (size_t)n * 2, s));
+    HIPCHK_AT("cocons_cov_rows", hipMemcpyAsync(didx, idx, (size_t)nidx * sizeof(int), hipMemcpyHostToDevice, s));
+    LocArgs la;
+    la.n = n; la.p = p; la.X = dX; la.ldx = n; la.locs = dl; la.ldl = n;
+    la.out = dloc; la.stride = n; la.smooth_kind = ms.smooth_kind;
+    la.smooth_min = f->smooth_limits[0]; la.smooth_max = f->smooth_limits[1]; la.th = tv;
+    launch_loc_params(la, s);
+    launch_cov_rows(ms.mode, n, nidx, didx, dloc, n, ms.gr, ms.nu_fixed, cor, dout, s);
+    HIPCHK_AT("cocons_cov_rows", hipGetLastError());
+    HIPCHK_AT("cocons_cov_rows", hipMemcpyAsync(out, dout, (size_t)nidx * n * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK_AT("cocons_cov_rows", hipStreamSynchronize(s));
+    return 0;
 }
 
 // ---------------------------------------------------------------------------
+// the handle's buffers of the prediction entries, grown to m new locations
+static int pred_reserve(cocons_fit *f, int m)
+{
+    if (m <= f->pred_cap) return 0;
+    hipFree(f->dlocp); hipFree(f->dXp); hipFree(f->dlocsp); hipFree(f->dstoch); hipFree(f->dquad); hipFree(f->dred);
+    f->dlocp = f->dXp = f->dlocsp = f->dstoch = f->dquad = f->dred = nullptr;
+    f->pred_cap = 0;
+    HIPCHK(hipMalloc(&f->dlocp, (size_t)LOCP_FIELDS * m * sizeof(double)));
+    HIPCHK(hipMalloc(&f->dXp, (size_t)m * f->p * sizeof(double)));
+    HIPCHK(hipMalloc(&f->dlocsp, (size_t)m * 2 * sizeof(double)));
+    HIPCHK(hipMalloc(&f->dstoch, (size_t)m * sizeof(double)));
+    HIPCHK(hipMalloc(&f->dquad, (size_t)m * sizeof(double)));
+    HIPCHK(hipMalloc(&f->dred, row_reduce_scratch_doubles(f->n, m) * sizeof(double)));
+    f->pred_cap = m;
+    return 0;
+}
+
 // kriging core: rows under the matrix = [ (z - X mean)' ; cov_rns_pred (m x n) ]
 extern "C" int cocons_predict_dense(cocons_fit *f, const double *theta, const double *mean, int z_col,
                                     int m, const double *locs_pred, const double *X_pred,
@@ -2556,30 +2592,19 @@ extern "C" int cocons_predict_dense(cocons_fit *f, const double *theta, const do
     if (!theta || !mean || m <= 0 || !locs_pred || !X_pred || !stochastic || !quadform || z_col < 0 || z_col >= f->r)
         return fail(-1, "cocons_predict_dense: bad argument");
     const int p = f->p, n = f->n;
-    if (m > f->pred_cap) {
-        hipFree(f->dlocp); hipFree(f->dXp); hipFree(f->dlocsp); hipFree(f->dstoch); hipFree(f->dquad); hipFree(f->dred);
-        f->dlocp = f->dXp = f->dlocsp = f->dstoch = f->dquad = f->dred = nullptr;
-        f->pred_cap = 0;
-        HIPCHK(hipMalloc(&f->dlocp, (size_t)LOCP_FIELDS * m * sizeof(double)));
-        HIPCHK(hipMalloc(&f->dXp, (size_t)m * p * sizeof(double)));
-        HIPCHK(hipMalloc(&f->dlocsp, (size_t)m * 2 * sizeof(double)));
-        HIPCHK(hipMalloc(&f->dstoch, (size_t)m * sizeof(double)));
-        HIPCHK(hipMalloc(&f->dquad, (size_t)m * sizeof(double)));
-        HIPCHK(hipMalloc(&f->dred, row_reduce_scratch_doubles(n, m) * sizeof(double)));
-        f->pred_cap = m;
-    }
+    if (int rc = pred_reserve(f, m)) return rc;
     if (int rc = fit_alloc_matrix(f, m + 1)) return rc;
     hipStream_t s = f->stream;
-    HIPCHK(hipMemcpyAsync(f->dXp, X_pred, (size_t)m * p * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(f->dlocsp, locs_pred, (size_t)m * 2 * sizeof(double), hipMemcpyHostToDevice, s));
-    if (int rc = reset_info(f)) return rc;
-    assemble_sigma(f, theta, 0, 0, f->npad);
-    // row npad: residual of realization z_col; rows npad+1 .. npad+m: cross-covariance
-    {
+    HIPCHK_AT("cocons_predict_dense", upload_canon(f->dXp, X_pred, (size_t)m * p, s));
+    HIPCHK_AT("cocons_predict_dense", upload_canon(f->dlocsp, locs_pred, (size_t)m * 2, s));
+    for (;;) {
+        if (int rc = reset_info(f)) return rc;
+        assemble_sigma(f, theta, 0, 0, f->npad);
+        // row npad: residual of realization z_col; rows npad+1 .. npad+m: cross-covariance
         RhsArgs ra;
         memset(&ra, 0, sizeof ra);
         ra.n = n; ra.p = p; ra.X = f->dX; ra.ldx = n; ra.use_trend = 1;
-        for (int i = 0; i < p; ++i) ra.mean[i] = mean[i];
+        for (int i = 0; i < p; ++i) ra.mean[i] = canon_nan(mean[i]);
         ra.src = f->dz + (size_t)z_col * n; ra.lds = n;
         ra.out = f->dA; ra.ld = f->lda; ra.row0 = f->npad; ra.nrows = 1;
         ra.nrows_zero = f->rhs_act - 1;      // also clears padding rows and columns >= n
@@ -2606,22 +2631,22 @@ extern "C" int cocons_predict_dense(cocons_fit *f, const double *theta, const do
         ModeSel ms0 = select_mode(theta, p, f->smooth_limits, 0);
         if (ms0.smooth_kind != ms.smooth_kind) launch_loc_params(lo, s);
         launch_pair_rect(MODE_GEOM, pa, s);
+        // (the dependency-driven schedule may take the head of this factorisation too -- round 6: the row reductions below read the
+        // factor from both buffers like the objectives' do; with m rows under the matrix every step is a long one)
+        FactorView pv = main_view(f);
+        pv.dag_ok = true;
+        if (int rc = factorize(f, pv, nullptr)) return rc;
+        launch_row_reduce(f->dA, f->lda, n, f->npad, f->npad + 1, m, f->dstoch, f->dquad, f->dred, s, 0, 0,
+                          f->dag_used ? f->dP : nullptr, f->dag_used ? 2 * TILE * f->dag_nsteps : 0);
+        HIPCHK(hipMemcpyAsync(stochastic, f->dstoch, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(quadform, f->dquad, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(s));
+        int st = info_status(f);
+        if (engine_retry(f, st)) continue;
+        return st;
     }
-    // (the dependency-driven schedule may take the head of this factorisation too -- round 6: the row reductions below read the
-    // factor from both buffers like the objectives' do; with m rows under the matrix every step is a long one)
-    FactorView pv = main_view(f);
-    pv.dag_ok = true;
-    if (int rc = factorize(f, pv, nullptr)) return rc;
-    launch_row_reduce(f->dA, f->lda, n, f->npad, f->npad + 1, m, f->dstoch, f->dquad, f->dred, s, 0, 0,
-                      f->dag_used ? f->dP : nullptr, f->dag_used ? 2 * TILE * f->dag_nsteps : 0);
-    HIPCHK(hipMemcpyAsync(stochastic, f->dstoch, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(quadform, f->dquad, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s));
-    int st = info_status(f);
-    if (engine_retry(f, st)) return cocons_predict_dense(f, theta, mean, z_col, m, locs_pred, X_pred, stochastic, quadform);
-    return st;
 }
 
 // Kriging core of the sparse branch of cocoPredict (R/predict.R:216-283) on a taper handle: S = taper o
@@ -2643,84 +2668,63 @@ extern "C" int cocons_predict_taper(cocons_fit *f, const double *theta, const do
         return fail(-1, "cocons_predict_taper: rowpointers do not match nnz (1-based CSR expected)");
     for (int w = 0; w < nnz_pred; ++w)
         if (colindices_pred[w] < 1 || colindices_pred[w] > n) return fail(-1, "cocons_predict_taper: column index out of range");
-    if (m > f->pred_cap) {
-        hipFree(f->dlocp); hipFree(f->dXp); hipFree(f->dlocsp); hipFree(f->dstoch); hipFree(f->dquad); hipFree(f->dred);
-        f->dlocp = f->dXp = f->dlocsp = f->dstoch = f->dquad = f->dred = nullptr;
-        f->pred_cap = 0;
-        HIPCHK(hipMalloc(&f->dlocp, (size_t)LOCP_FIELDS * m * sizeof(double)));
-        HIPCHK(hipMalloc(&f->dXp, (size_t)m * p * sizeof(double)));
-        HIPCHK(hipMalloc(&f->dlocsp, (size_t)m * 2 * sizeof(double)));
-        HIPCHK(hipMalloc(&f->dstoch, (size_t)m * sizeof(double)));
-        HIPCHK(hipMalloc(&f->dquad, (size_t)m * sizeof(double)));
-        HIPCHK(hipMalloc(&f->dred, row_reduce_scratch_doubles(n, m) * sizeof(double)));
-        f->pred_cap = m;
-    }
+    if (int rc = pred_reserve(f, m)) return rc;
     if (int rc = fit_alloc_matrix(f, m + 1)) return rc;
-    hipStream_t s = f->stream;
-    int *dci = nullptr, *drp = nullptr;
-    double *dtv = nullptr;
     const size_t nz = nnz_pred > 0 ? (size_t)nnz_pred : 1;
-    int st = 0;
-    do {
-#define CKP(expr) { hipError_t e__ = (expr); if (e__ != hipSuccess) { st = fail(-100 - (int)e__, "cocons_predict_taper: %s", hipGetErrorString(e__)); break; } }
-        CKP(hipMalloc(&dci, nz * sizeof(int)));
-        CKP(hipMalloc(&drp, (size_t)(m + 1) * sizeof(int)));
-        CKP(hipMalloc(&dtv, nz * sizeof(double)));
-        CKP(hipMemcpyAsync(f->dXp, X_pred, (size_t)m * p * sizeof(double), hipMemcpyHostToDevice, s));
-        CKP(hipMemcpyAsync(f->dlocsp, locs_pred, (size_t)m * 2 * sizeof(double), hipMemcpyHostToDevice, s));
-        CKP(hipMemcpyAsync(drp, rowpointers_pred, (size_t)(m + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-        std::vector<int> mapped;                    // the pattern's columns in the handle's order of the observations
-        if (nnz_pred > 0) {
-            mapped.resize(nnz_pred);
-            for (int w = 0; w < nnz_pred; ++w) mapped[w] = (*f->taper_inv)[colindices_pred[w] - 1] + 1;
-            CKP(hipMemcpy(dci, mapped.data(), (size_t)nnz_pred * sizeof(int), hipMemcpyHostToDevice));
-            CKP(hipMemcpyAsync(dtv, taper_entries_pred, (size_t)nnz_pred * sizeof(double), hipMemcpyHostToDevice, s));
-        }
-#undef CKP
-        for (;;) {
-            if ((st = reset_info(f))) break;
-            if ((st = assemble_sigma_taper(f, theta))) break;          // zeroes the whole buffer, border rows included
-            RhsArgs ra;
-            memset(&ra, 0, sizeof ra);
-            ra.n = n; ra.p = p; ra.X = f->dX; ra.ldx = n; ra.use_trend = 1;
-            for (int i = 0; i < p; ++i) ra.mean[i] = mean[i];
-            ra.src = f->dz + (size_t)z_col * n; ra.lds = n;
-            ra.out = f->dA; ra.ld = f->lda; ra.row0 = f->npad; ra.nrows = 1;
-            ra.skew = f->skew; ra.npad = f->npad;
-            ra.nrows_zero = f->rhs_act - 1;
-            ra.col0 = 0; ra.ncols_out = f->npad;
-            launch_rhs_rows(ra, s);
-            // parameters as cocons_cov_rns_taper_pred prepares them: FULL scale vector, prediction-branch smoothness
-            ThetaVecs tv;
-            make_theta_vecs(theta, p, tv);
-            for (int i = 0; i < p; ++i) tv.two_scale_je[i] = 2 * theta[TH_SCALE * p + i];
-            ModeSel ms = select_mode(theta, p, f->smooth_limits, 2);
-            LocArgs lp;
-            lp.n = m; lp.p = p; lp.X = f->dXp; lp.ldx = m; lp.locs = f->dlocsp; lp.ldl = m;
-            lp.out = f->dlocp; lp.stride = m; lp.smooth_kind = ms.smooth_kind;
-            lp.smooth_min = f->smooth_limits[0]; lp.smooth_max = f->smooth_limits[1]; lp.th = tv;
-            launch_loc_params(lp, s);
-            LocArgs lo = lp;
-            lo.n = n; lo.X = f->dX; lo.ldx = n; lo.locs = f->dlocs; lo.ldl = n; lo.out = f->dloc; lo.stride = f->npad;
-            launch_loc_params(lo, s);                                   // (after the entries of S were computed: stream order)
-            launch_taper(MODE_GEOM, true, m, nnz_pred, dci, drp, f->dlocp, m, f->dloc, f->npad, 0.0, nullptr, s,
-                         dtv, f->dA, f->lda, f->npad + 1, f->skew, f->npad);
-            factorize(f, main_view(f), nullptr);
-            launch_row_reduce(f->dA, f->lda, n, f->npad, f->npad + 1, m, f->dstoch, f->dquad, f->dred, s, f->skew, f->npad);
-            hipMemcpyAsync(stochastic, f->dstoch, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s);
-            hipMemcpyAsync(quadform, f->dquad, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s);
-            hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s);
-            hipError_t e = hipGetLastError();
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) { st = fail(-100 - (int)e, "cocons_predict_taper: %s", hipGetErrorString(e)); break; }
-            st = info_status(f);
-            if (engine_retry(f, st)) continue;
-            break;
-        }
-    } while (0);
-    hipStreamSynchronize(s);
-    hipFree(dci); hipFree(drp); hipFree(dtv);
-    return st;
+    DevBuf<int> dci, drp;
+    DevBuf<double> dtv;
+    StreamDrain s{f->stream, false};
+    HIPCHK_AT("cocons_predict_taper", dci.alloc(nz));
+    HIPCHK_AT("cocons_predict_taper", drp.alloc((size_t)m + 1));
+    HIPCHK_AT("cocons_predict_taper", dtv.alloc(nz));
+    HIPCHK_AT("cocons_predict_taper", upload_canon(f->dXp, X_pred, (size_t)m * p, s));
+    HIPCHK_AT("cocons_predict_taper", upload_canon(f->dlocsp, locs_pred, (size_t)m * 2, s));
+    HIPCHK_AT("cocons_predict_taper", hipMemcpyAsync(drp, rowpointers_pred, (size_t)(m + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+    if (nnz_pred > 0) {
+        std::vector<int> mapped(nnz_pred);          // the pattern's columns in the handle's order of the observations
+        for (int w = 0; w < nnz_pred; ++w) mapped[w] = (*f->taper_inv)[colindices_pred[w] - 1] + 1;
+        HIPCHK_AT("cocons_predict_taper", hipMemcpy(dci, mapped.data(), (size_t)nnz_pred * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK_AT("cocons_predict_taper", upload_canon(dtv, taper_entries_pred, (size_t)nnz_pred, s));
+    }
+    for (;;) {
+        if (int rc = reset_info(f)) return rc;
+        if (int rc = assemble_sigma_taper(f, theta)) return rc;      // zeroes the whole buffer, border rows included
+        RhsArgs ra;
+        memset(&ra, 0, sizeof ra);
+        ra.n = n; ra.p = p; ra.X = f->dX; ra.ldx = n; ra.use_trend = 1;
+        for (int i = 0; i < p; ++i) ra.mean[i] = canon_nan(mean[i]);
+        ra.src = f->dz + (size_t)z_col * n; ra.lds = n;
+        ra.out = f->dA; ra.ld = f->lda; ra.row0 = f->npad; ra.nrows = 1;
+        ra.skew = f->skew; ra.npad = f->npad;
+        ra.nrows_zero = f->rhs_act - 1;
+        ra.col0 = 0; ra.ncols_out = f->npad;
+        launch_rhs_rows(ra, s);
+        // parameters as cocons_cov_rns_taper_pred prepares them: FULL scale vector, prediction-branch smoothness
+        ThetaVecs tv;
+        make_theta_vecs(theta, p, tv);
+        for (int i = 0; i < p; ++i) tv.two_scale_je[i] = 2 * theta[TH_SCALE * p + i];
+        ModeSel ms = select_mode(theta, p, f->smooth_limits, 2);
+        LocArgs lp;
+        lp.n = m; lp.p = p; lp.X = f->dXp; lp.ldx = m; lp.locs = f->dlocsp; lp.ldl = m;
+        lp.out = f->dlocp; lp.stride = m; lp.smooth_kind = ms.smooth_kind;
+        lp.smooth_min = f->smooth_limits[0]; lp.smooth_max = f->smooth_limits[1]; lp.th = tv;
+        launch_loc_params(lp, s);
+        LocArgs lo = lp;
+        lo.n = n; lo.X = f->dX; lo.ldx = n; lo.locs = f->dlocs; lo.ldl = n; lo.out = f->dloc; lo.stride = f->npad;
+        launch_loc_params(lo, s);                                   // (after the entries of S were computed: stream order)
+        launch_taper(MODE_GEOM, true, m, nnz_pred, dci, drp, f->dlocp, m, f->dloc, f->npad, 0.0, nullptr, s,
+                     dtv, f->dA, f->lda, f->npad + 1, f->skew, f->npad);
+        if (int rc = factorize(f, main_view(f), nullptr)) return rc;
+        launch_row_reduce(f->dA, f->lda, n, f->npad, f->npad + 1, m, f->dstoch, f->dquad, f->dred, s, f->skew, f->npad);
+        HIPCHK_AT("cocons_predict_taper", hipMemcpyAsync(stochastic, f->dstoch, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT("cocons_predict_taper", hipMemcpyAsync(quadform, f->dquad, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT("cocons_predict_taper", hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT("cocons_predict_taper", hipGetLastError());
+        HIPCHK_AT("cocons_predict_taper", hipStreamSynchronize(s));
+        int st = info_status(f);
+        if (engine_retry(f, st)) continue;
+        return st;
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -2743,68 +2747,52 @@ static int sim_taper_run(cocons_fit *f, const double *theta, const double *mean,
 {
     const int n = f->n, p = f->p;
     const size_t ne = (size_t)n * nsim;
-    double *dE = nullptr, *dY = nullptr, *dO = nullptr, *dtr = nullptr;
-    int *dpos = nullptr;
-    hipStream_t s = f->stream;
-    int rc = 0;
-    do {
-        hipError_t e;
-#define CKS(expr) if ((e = (expr)) != hipSuccess) { rc = fail(-100 - (int)e, "cocons_sim_taper: %s", hipGetErrorString(e)); break; }
-        CKS(hipMalloc(&dE, ne * sizeof(double)));
-        CKS(hipMalloc(&dY, ne * sizeof(double)));
-        CKS(hipMalloc(&dO, ne * sizeof(double)));
-        CKS(hipMalloc(&dtr, (size_t)n * sizeof(double)));
-        CKS(hipMalloc(&dpos, (size_t)n * sizeof(int)));
-        {
-            // the draws through the same NaN canonicalisation as the handle's own data (no all-ones NaN enters the device)
-            std::vector<double> hE(ne);
-            for (size_t i = 0; i < ne; ++i) hE[i] = canon_nan(iiderrors[i]);
-            // trend = X %*% mean on the host (O(n p)), in the handle's order (h_X is stored in it), as cocons_sim_dense does
-            std::vector<double> tr(n, 0.0);
-            for (int j = 0; j < p; ++j)
-                for (int i = 0; i < n; ++i) tr[i] += (*f->h_X)[(size_t)i + (size_t)j * n] * mean[j];
-            for (int i = 0; i < n; ++i) tr[i] = canon_nan(tr[i]);
-            CKS(hipMemcpyAsync(dE, hE.data(), ne * sizeof(double), hipMemcpyHostToDevice, s));
-            CKS(hipMemcpyAsync(dtr, tr.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
-            CKS(hipMemcpyAsync(dpos, pos.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
-            CKS(hipStreamSynchronize(s));      // the staging vectors go out of scope
+    // trend = X %*% mean on the host (O(n p)), in the handle's order (h_X is stored in it), as cocons_sim_dense does
+    std::vector<double> tr(n, 0.0);
+    for (int j = 0; j < p; ++j)
+        for (int i = 0; i < n; ++i) tr[i] += (*f->h_X)[(size_t)i + (size_t)j * n] * mean[j];
+    DevBuf<double> dE, dY, dO, dtr;
+    DevBuf<int> dpos;
+    StreamDrain s{f->stream, false};
+    HIPCHK_AT("cocons_sim_taper", dE.alloc(ne));
+    HIPCHK_AT("cocons_sim_taper", dY.alloc(ne));
+    HIPCHK_AT("cocons_sim_taper", dO.alloc(ne));
+    HIPCHK_AT("cocons_sim_taper", dtr.alloc((size_t)n));
+    HIPCHK_AT("cocons_sim_taper", dpos.alloc((size_t)n));
+    HIPCHK_AT("cocons_sim_taper", upload_canon(dE, iiderrors, ne, s));
+    HIPCHK_AT("cocons_sim_taper", upload_canon(dtr, tr.data(), (size_t)n, s));
+    HIPCHK_AT("cocons_sim_taper", hipMemcpyAsync(dpos, pos.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    for (;;) {
+        if (int rc = fit_alloc_matrix(f, 1)) return rc;
+        if (int rc = reset_info(f)) return rc;
+        f->nrhs_cur = 0;
+        HIPCHK_AT("cocons_sim_taper", hipEventRecord(f->ev[4], s));
+        if (int rc = assemble_sigma_taper(f, theta)) return rc;
+        {   // no right-hand sides: clear the rows under the matrix
+            RhsArgs ra;
+            memset(&ra, 0, sizeof ra);
+            ra.n = n; ra.p = p; ra.X = f->dX; ra.ldx = n; ra.src = f->dX; ra.lds = n;
+            ra.out = f->dA; ra.ld = f->lda; ra.row0 = f->npad; ra.nrows = 0; ra.nrows_zero = f->rhs_act;
+            ra.col0 = 0; ra.ncols_out = f->npad;
+            ra.skew = f->skew; ra.npad = f->npad;
+            launch_rhs_rows(ra, s);
         }
-        for (;;) {
-            if ((rc = fit_alloc_matrix(f, 1))) break;
-            if ((rc = reset_info(f))) break;
-            f->nrhs_cur = 0;
-            CKS(hipEventRecord(f->ev[4], s));
-            if ((rc = assemble_sigma_taper(f, theta))) break;
-            {   // no right-hand sides: clear the rows under the matrix
-                RhsArgs ra;
-                memset(&ra, 0, sizeof ra);
-                ra.n = n; ra.p = p; ra.X = f->dX; ra.ldx = n; ra.src = f->dX; ra.lds = n;
-                ra.out = f->dA; ra.ld = f->lda; ra.row0 = f->npad; ra.nrows = 0; ra.nrows_zero = f->rhs_act;
-                ra.col0 = 0; ra.ncols_out = f->npad;
-                ra.skew = f->skew; ra.npad = f->npad;
-                launch_rhs_rows(ra, s);
-            }
-            if ((rc = factorize(f, main_view(f), nullptr))) break;
-            CKS(hipEventRecord(f->ev[5], s));
-            launch_band_trmm(f->dA, f->lda, f->skew, f->npad, f->d_thi, f->nt, n, dE, n, nsim, dtr, dY, n, s);
-            CKS(hipEventRecord(f->ev[6], s));
-            launch_gather_rows(dY, n, dpos, n, nsim, dO, n, s);
-            CKS(hipEventRecord(f->ev[7], s));
-            CKS(hipMemcpyAsync(out, dO, ne * sizeof(double), hipMemcpyDeviceToHost, s));
-            CKS(hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-            CKS(hipGetLastError());
-            CKS(hipStreamSynchronize(s));
-            rc = info_status(f);
-            if (engine_retry(f, rc)) continue;
-            if (rc == 0)
-                for (int q = 0; q < 3; ++q) CKS(hipEventElapsedTime(&f->sim_ms[q], f->ev[4 + q], f->ev[5 + q]));
-            break;
-        }
-#undef CKS
-    } while (0);
-    hipStreamSynchronize(s);
-    hipFree(dE); hipFree(dY); hipFree(dO); hipFree(dtr); hipFree(dpos);
-    return rc;
+        if (int rc = factorize(f, main_view(f), nullptr)) return rc;
+        HIPCHK_AT("cocons_sim_taper", hipEventRecord(f->ev[5], s));
+        launch_band_trmm(f->dA, f->lda, f->skew, f->npad, f->d_thi, f->nt, n, dE, n, nsim, dtr, dY, n, s);
+        HIPCHK_AT("cocons_sim_taper", hipEventRecord(f->ev[6], s));
+        launch_gather_rows(dY, n, dpos, n, nsim, dO, n, s);
+        HIPCHK_AT("cocons_sim_taper", hipEventRecord(f->ev[7], s));
+        HIPCHK_AT("cocons_sim_taper", hipMemcpyAsync(out, dO, ne * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT("cocons_sim_taper", hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT("cocons_sim_taper", hipGetLastError());
+        HIPCHK_AT("cocons_sim_taper", hipStreamSynchronize(s));
+        int rc = info_status(f);
+        if (engine_retry(f, rc)) continue;
+        if (rc == 0)
+            for (int q = 0; q < 3; ++q) HIPCHK_AT("cocons_sim_taper", hipEventElapsedTime(&f->sim_ms[q], f->ev[4 + q], f->ev[5 + q]));
+        return rc;
+    }
 }
 
 extern "C" int cocons_sim_taper(cocons_fit *f, const double *theta, const double *mean, int nsim, const double *iiderrors,
@@ -2894,25 +2882,20 @@ extern "C" int cocons_sim_dense(cocons_fit *f, const double *theta, const double
         return cocons_sim_dense(f->unsorted, theta, mean, classic, nsim, iiderrors, out);
     }
     const int n = f->n, p = f->p;
-    double *dE = nullptr, *dY = nullptr, *dtr = nullptr;
-    int rc = 0;
-    hipStream_t s = f->stream;
-    do {
-        if ((rc = fit_alloc_matrix(f, 1))) break;
-        hipError_t e;
-#define CKS(expr) if ((e = (expr)) != hipSuccess) { rc = fail(-100 - (int)e, "cocons_sim_dense: %s", hipGetErrorString(e)); break; }
-        CKS(hipMalloc(&dE, (size_t)n * nsim * sizeof(double)));
-        CKS(hipMalloc(&dY, (size_t)n * nsim * sizeof(double)));
-        CKS(hipMalloc(&dtr, (size_t)n * sizeof(double)));
-        CKS(hipMemcpyAsync(dE, iiderrors, (size_t)n * nsim * sizeof(double), hipMemcpyHostToDevice, s));
-        {   // trend = X %*% mean on the host (O(n p)), as the reference does (:170)
-            std::vector<double> tr(n, 0.0);
-            for (int j = 0; j < p; ++j)
-                for (int i = 0; i < n; ++i) tr[i] += (*f->h_X)[(size_t)i + (size_t)j * n] * mean[j];
-            CKS(hipMemcpyAsync(dtr, tr.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
-            CKS(hipStreamSynchronize(s));
-        }
-        if ((rc = reset_info(f))) break;
+    if (int rc = fit_alloc_matrix(f, 1)) return rc;
+    // trend = X %*% mean on the host (O(n p)), as the reference does (:170)
+    std::vector<double> tr(n, 0.0);
+    for (int j = 0; j < p; ++j)
+        for (int i = 0; i < n; ++i) tr[i] += (*f->h_X)[(size_t)i + (size_t)j * n] * mean[j];
+    DevBuf<double> dE, dY, dtr;
+    StreamDrain s{f->stream, false};
+    HIPCHK_AT("cocons_sim_dense", dE.alloc((size_t)n * nsim));
+    HIPCHK_AT("cocons_sim_dense", dY.alloc((size_t)n * nsim));
+    HIPCHK_AT("cocons_sim_dense", dtr.alloc((size_t)n));
+    HIPCHK_AT("cocons_sim_dense", upload_canon(dE, iiderrors, (size_t)n * nsim, s));
+    HIPCHK_AT("cocons_sim_dense", upload_canon(dtr, tr.data(), (size_t)n, s));
+    for (;;) {
+        if (int rc = reset_info(f)) return rc;
         f->nrhs_cur = 0;
         assemble_sigma(f, theta, classic ? 1 : 0, 0, f->npad);
         {   // no right-hand sides: clear the rows under the matrix
@@ -2923,18 +2906,16 @@ extern "C" int cocons_sim_dense(cocons_fit *f, const double *theta, const double
             ra.col0 = 0; ra.ncols_out = f->npad;
             launch_rhs_rows(ra, s);
         }
-        factorize(f, main_view(f), nullptr);
+        if (int rc = factorize(f, main_view(f), nullptr)) return rc;
         launch_trmm_lower(f->dA, f->lda, n, dE, n, nsim, dtr, dY, n, s);
-        CKS(hipMemcpyAsync(out, dY, (size_t)n * nsim * sizeof(double), hipMemcpyDeviceToHost, s));
-        CKS(hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-        CKS(hipGetLastError());
-        CKS(hipStreamSynchronize(s));
-#undef CKS
-        rc = info_status(f);
-    } while (0);
-    hipFree(dE); hipFree(dY); hipFree(dtr);
-    if (engine_retry(f, rc)) return cocons_sim_dense(f, theta, mean, classic, nsim, iiderrors, out);
-    return rc;
+        HIPCHK_AT("cocons_sim_dense", hipMemcpyAsync(out, dY, (size_t)n * nsim * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT("cocons_sim_dense", hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT("cocons_sim_dense", hipGetLastError());
+        HIPCHK_AT("cocons_sim_dense", hipStreamSynchronize(s));
+        int rc = info_status(f);
+        if (engine_retry(f, rc)) continue;
+        return rc;
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -2956,30 +2937,27 @@ extern "C" int cocons_sim_cond_dense(cocons_fit *f, const double *theta, const d
     const int n = f->n, p = f->p, npad = f->npad;
     const int mpad = round_up(m, TILE), N = npad + mpad;
     const size_t ldj = (size_t)N + TILE;
-    double *dJ = nullptr, *dXp = nullptr, *dlp = nullptr, *dlu = nullptr, *dlocp = nullptr, *dlocu = nullptr;
-    double *dE = nullptr, *dY = nullptr, *dmu = nullptr, *dst = nullptr, *dq = nullptr, *dred = nullptr;
-    hipStream_t s = f->stream;
-    int rc = 0;
-    do {
-        hipError_t e;
-#define CKS(expr) if ((e = (expr)) != hipSuccess) { rc = fail(-100 - (int)e, "cocons_sim_cond_dense: %s", hipGetErrorString(e)); break; }
-        CKS(hipMalloc(&dJ, ldj * (size_t)N * sizeof(double)));
-        CKS(hipMalloc(&dXp, (size_t)m * p * sizeof(double)));
-        CKS(hipMalloc(&dlp, (size_t)m * 2 * sizeof(double)));
-        CKS(hipMalloc(&dlu, (size_t)m * 2 * sizeof(double)));
-        CKS(hipMalloc(&dlocp, (size_t)LOCP_FIELDS * mpad * sizeof(double)));
-        CKS(hipMalloc(&dlocu, (size_t)LOCP_FIELDS * mpad * sizeof(double)));
-        CKS(hipMalloc(&dE, (size_t)m * nsim * sizeof(double)));
-        CKS(hipMalloc(&dY, (size_t)m * nsim * sizeof(double)));
-        CKS(hipMalloc(&dmu, (size_t)m * sizeof(double)));
-        CKS(hipMalloc(&dst, (size_t)m * sizeof(double)));
-        CKS(hipMalloc(&dq, (size_t)m * sizeof(double)));
-        CKS(hipMalloc(&dred, row_reduce_scratch_doubles(n, m) * sizeof(double)));
-        CKS(hipMemcpyAsync(dXp, X_pred, (size_t)m * p * sizeof(double), hipMemcpyHostToDevice, s));
-        CKS(hipMemcpyAsync(dlp, locs_pred, (size_t)m * 2 * sizeof(double), hipMemcpyHostToDevice, s));
-        CKS(hipMemcpyAsync(dlu, locs_unobs, (size_t)m * 2 * sizeof(double), hipMemcpyHostToDevice, s));
-        CKS(hipMemcpyAsync(dE, iiderrors, (size_t)m * nsim * sizeof(double), hipMemcpyHostToDevice, s));
-        if ((rc = reset_info(f))) break;
+    std::vector<double> mu(m), stv(m);
+    DevBuf<double> dJ, dXp, dlp, dlu, dlocp, dlocu, dE, dY, dmu, dst, dq, dred;
+    StreamDrain s{f->stream, false};
+    HIPCHK_AT("cocons_sim_cond_dense", dJ.alloc(ldj * (size_t)N));
+    HIPCHK_AT("cocons_sim_cond_dense", dXp.alloc((size_t)m * p));
+    HIPCHK_AT("cocons_sim_cond_dense", dlp.alloc((size_t)m * 2));
+    HIPCHK_AT("cocons_sim_cond_dense", dlu.alloc((size_t)m * 2));
+    HIPCHK_AT("cocons_sim_cond_dense", dlocp.alloc((size_t)LOCP_FIELDS * mpad));
+    HIPCHK_AT("cocons_sim_cond_dense", dlocu.alloc((size_t)LOCP_FIELDS * mpad));
+    HIPCHK_AT("cocons_sim_cond_dense", dE.alloc((size_t)m * nsim));
+    HIPCHK_AT("cocons_sim_cond_dense", dY.alloc((size_t)m * nsim));
+    HIPCHK_AT("cocons_sim_cond_dense", dmu.alloc((size_t)m));
+    HIPCHK_AT("cocons_sim_cond_dense", dst.alloc((size_t)m));
+    HIPCHK_AT("cocons_sim_cond_dense", dq.alloc((size_t)m));
+    HIPCHK_AT("cocons_sim_cond_dense", dred.alloc(row_reduce_scratch_doubles(n, m)));
+    HIPCHK_AT("cocons_sim_cond_dense", upload_canon(dXp, X_pred, (size_t)m * p, s));
+    HIPCHK_AT("cocons_sim_cond_dense", upload_canon(dlp, locs_pred, (size_t)m * 2, s));
+    HIPCHK_AT("cocons_sim_cond_dense", upload_canon(dlu, locs_unobs, (size_t)m * 2, s));
+    HIPCHK_AT("cocons_sim_cond_dense", upload_canon(dE, iiderrors, (size_t)m * nsim, s));
+    for (;;) {
+        if (int rc = reset_info(f)) return rc;
         f->nrhs_cur = 1;
         ThetaVecs tv;
         make_theta_vecs(theta, p, tv);
@@ -3018,7 +2996,7 @@ extern "C" int cocons_sim_cond_dense(cocons_fit *f, const double *theta, const d
             RhsArgs ra;
             memset(&ra, 0, sizeof ra);
             ra.n = n; ra.p = p; ra.X = f->dX; ra.ldx = n; ra.use_trend = 1;
-            for (int i = 0; i < p; ++i) ra.mean[i] = mean[i];
+            for (int i = 0; i < p; ++i) ra.mean[i] = canon_nan(mean[i]);
             ra.src = f->dz + (size_t)z_col * n; ra.lds = n;
             ra.out = dJ; ra.ld = ldj; ra.row0 = N; ra.nrows = 1; ra.nrows_zero = TILE - 1;
             ra.col0 = 0; ra.ncols_out = N;
@@ -3026,33 +3004,27 @@ extern "C" int cocons_sim_cond_dense(cocons_fit *f, const double *theta, const d
         }
         FactorView v;
         v.A = dJ; v.lda = ldj; v.nt = N / TILE; v.mt = N / TILE + 1;
-        factorize(f, v, nullptr);
+        if (int rc = factorize(f, v, nullptr)) return rc;
         // kriging mean: stochastic_i = sum_{c<n} J(npad+i, c) J(N, c);  tmp_mu = X_pred mean + stochastic
         launch_row_reduce(dJ, ldj, n, N, npad, m, dst, dq, dred, s);
-        std::vector<double> mu(m), stv(m);
-        CKS(hipMemcpyAsync(stv.data(), dst, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
-        CKS(hipStreamSynchronize(s));
+        HIPCHK_AT("cocons_sim_cond_dense", hipMemcpyAsync(stv.data(), dst, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT("cocons_sim_cond_dense", hipStreamSynchronize(s));
         for (int i = 0; i < m; ++i) {
             double sys = 0;
             for (int j = 0; j < p; ++j) sys += X_pred[(size_t)i + (size_t)j * m] * mean[j];
             mu[i] = sys + stv[i];
         }
-        CKS(hipMemcpyAsync(dmu, mu.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK_AT("cocons_sim_cond_dense", upload_canon(dmu, mu.data(), (size_t)m, s));
         // fields = L_S E + tmp_mu with L_S = lower-right block of the joint factor
         launch_trmm_lower(dJ + (size_t)npad + (size_t)npad * ldj, ldj, m, dE, m, nsim, dmu, dY, m, s);
-        CKS(hipMemcpyAsync(out, dY, (size_t)m * nsim * sizeof(double), hipMemcpyDeviceToHost, s));
-        CKS(hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-        CKS(hipGetLastError());
-        CKS(hipStreamSynchronize(s));
-#undef CKS
-        rc = info_status(f);
-        if (rc > n) rc = n;    // a failure inside the Schur block is still "Cholesky error"
-    } while (0);
-    hipFree(dJ); hipFree(dXp); hipFree(dlp); hipFree(dlu); hipFree(dlocp); hipFree(dlocu);
-    hipFree(dE); hipFree(dY); hipFree(dmu); hipFree(dst); hipFree(dq); hipFree(dred);
-    if (engine_retry(f, rc))
-        return cocons_sim_cond_dense(f, theta, mean, z_col, m, locs_pred, X_pred, locs_unobs, nsim, iiderrors, out);
-    return rc;
+        HIPCHK_AT("cocons_sim_cond_dense", hipMemcpyAsync(out, dY, (size_t)m * nsim * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT("cocons_sim_cond_dense", hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT("cocons_sim_cond_dense", hipGetLastError());
+        HIPCHK_AT("cocons_sim_cond_dense", hipStreamSynchronize(s));
+        int rc = info_status(f);
+        if (engine_retry(f, rc)) continue;
+        return rc > n ? n : rc;    // a failure inside the Schur block is still "Cholesky error"
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -3063,43 +3035,40 @@ extern "C" int cocons_chol_solve(int n, const double *Ain, int nrhs, const doubl
     // reuse the fit machinery with a dummy 1-column design
     std::vector<double> locs((size_t)2 * n, 0.0), X((size_t)n, 1.0);
     double sl[2] = {0.5, 0.5};
-    cocons_fit *f = fit_create_impl(n, 1, 0, 0, locs.data(), X.data(), nullptr, nullptr, sl, -1, false);   // caller's order,
-    if (!f) return -1;                                                                                       // padding behind
+    std::unique_ptr<cocons_fit, void (*)(cocons_fit *)> owner(
+        fit_create_impl(n, 1, 0, 0, locs.data(), X.data(), nullptr, nullptr, sl, -1, false), cocons_fit_destroy);   // caller's order,
+    cocons_fit *f = owner.get();                                                                                   // padding behind
+    if (!f) return -1;
     f->engine_ok = false;     // one-shot handle whose input is uploaded once: plain schedule
-    int rc = 0;
-    do {
-        if ((rc = fit_alloc_matrix(f, nrhs > 0 ? nrhs : 1))) break;
-        hipStream_t s = f->stream;
-        // identity everywhere in the padded square, zero rhs rows, then copy A and rhs^T in
-        std::vector<double> hostA(f->lda * (size_t)f->npad, 0.0);
-        for (int c = 0; c < f->npad; ++c) hostA[(size_t)c + (size_t)c * f->lda] = 1.0;
-        for (int c = 0; c < n; ++c) {
-            for (int r_ = c; r_ < n; ++r_) hostA[(size_t)r_ + (size_t)c * f->lda] = Ain[(size_t)r_ + (size_t)c * n];
-            for (int k = 0; k < nrhs; ++k) hostA[(size_t)(f->npad + k) + (size_t)c * f->lda] = rhs[(size_t)c + (size_t)k * n];
-        }
-        hipError_t e = hipMemcpyAsync(f->dA, hostA.data(), hostA.size() * sizeof(double), hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) { rc = fail(-100, "cocons_chol_solve: %s", hipGetErrorString(e)); break; }
-        if ((rc = reset_info(f))) break;
-        factorize(f, main_view(f), nullptr);
-        launch_finalize(f->dA, f->lda, n, f->npad, 0, f->dout, s);
-        e = hipMemcpyAsync(hostA.data(), f->dA, hostA.size() * sizeof(double), hipMemcpyDeviceToHost, s);
-        if (e != hipSuccess) { rc = fail(-100, "cocons_chol_solve: %s", hipGetErrorString(e)); break; }
-        hipMemcpyAsync(f->hout, f->dout, sizeof(double), hipMemcpyDeviceToHost, s);
-        hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s);
-        e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { rc = fail(-100, "cocons_chol_solve: %s", hipGetErrorString(e)); break; }
-        if ((rc = info_status(f))) break;
-        if (logdet_half) *logdet_half = f->hout[0];
-        if (L)
-            for (int c = 0; c < n; ++c)
-                for (int r_ = 0; r_ < n; ++r_)
-                    L[(size_t)r_ + (size_t)c * n] = (r_ >= c) ? hostA[(size_t)r_ + (size_t)c * f->lda] : 0.0;
-        if (Y)
-            for (int k = 0; k < nrhs; ++k)
-                for (int c = 0; c < n; ++c) Y[(size_t)c + (size_t)k * n] = hostA[(size_t)(f->npad + k) + (size_t)c * f->lda];
-    } while (0);
-    cocons_fit_destroy(f);
-    return rc;
+    if (int rc = fit_alloc_matrix(f, nrhs > 0 ? nrhs : 1)) return rc;
+    // identity everywhere in the padded square, zero rhs rows, then copy A and rhs^T in
+    std::vector<double> hostA(f->lda * (size_t)f->npad, 0.0);
+    for (int c = 0; c < f->npad; ++c) hostA[(size_t)c + (size_t)c * f->lda] = 1.0;
+    for (int c = 0; c < n; ++c) {
+        for (int r_ = c; r_ < n; ++r_) hostA[(size_t)r_ + (size_t)c * f->lda] = Ain[(size_t)r_ + (size_t)c * n];
+        for (int k = 0; k < nrhs; ++k) hostA[(size_t)(f->npad + k) + (size_t)c * f->lda] = rhs[(size_t)c + (size_t)k * n];
+    }
+    StreamDrain s{f->stream, false};
+    hipError_t e = upload_canon(f->dA, hostA.data(), hostA.size(), s);
+    if (e != hipSuccess) return fail(-100, "cocons_chol_solve: %s", hipGetErrorString(e));
+    if (int rc = reset_info(f)) return rc;
+    if (int rc = factorize(f, main_view(f), nullptr)) return rc;
+    launch_finalize(f->dA, f->lda, n, f->npad, 0, f->dout, s);
+    e = hipMemcpyAsync(hostA.data(), f->dA, hostA.size() * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(f->hout, f->dout, sizeof(double), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(-100, "cocons_chol_solve: %s", hipGetErrorString(e));
+    if (int rc = info_status(f)) return rc;
+    if (logdet_half) *logdet_half = f->hout[0];
+    if (L)
+        for (int c = 0; c < n; ++c)
+            for (int r_ = 0; r_ < n; ++r_)
+                L[(size_t)r_ + (size_t)c * n] = (r_ >= c) ? hostA[(size_t)r_ + (size_t)c * f->lda] : 0.0;
+    if (Y)
+        for (int k = 0; k < nrhs; ++k)
+            for (int c = 0; c < n; ++c) Y[(size_t)c + (size_t)k * n] = hostA[(size_t)(f->npad + k) + (size_t)c * f->lda];
+    return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -3892,6 +3861,99 @@ panel_diff_kernel(const double *P, const double *L, size_t lda, int c0, int c1, 
     atomicMax(out + 1, (unsigned long long)__double_as_longlong(ml));
 }
 
+// (3) of cocons_debug_dag_replay: fv is the factor's view, prepared for the DAG schedule
+static int dag_replay_run(cocons_fit *f, const FactorView &fv, bool slots, const double *theta, const double *mean, int reps,
+                          double *out)
+{
+    static const char *const tiles_failed = "cocons_debug_dag_replay: copying the diagonal tiles failed";
+    const int nrhs = f->r;
+    const size_t lda = fv.lda;
+    const int nt_head = 2 * f->dag_nsteps + 2;                 // diagonal tiles 2 .. nt_head - 1 belong to the head's blocks
+    std::vector<double> tile((size_t)TILE * TILE), W((size_t)TILE * TILE);
+    DevBuf<double> Lcopy;
+    DevBuf<unsigned long long> dcmp;
+    struct Events {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~Events() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
+    } ev;
+    StreamDrain M{f->stream, false};
+    // (2) what the engine would publish
+    HIPCHK_AT("cocons_debug_dag_replay", Lcopy.alloc(lda * (size_t)f->npad));
+    HIPCHK_AT("cocons_debug_dag_replay", hipMemcpyAsync(Lcopy, f->dA, lda * (size_t)f->npad * sizeof(double), hipMemcpyDeviceToDevice, M));
+    for (int t = 2; t < nt_head && t < fv.nt; ++t) {
+        const double *src = f->dA + (size_t)t * TILE + (size_t)t * TILE * lda;
+        if (hipMemcpy2DAsync(tile.data(), TILE * sizeof(double), src, lda * sizeof(double), TILE * sizeof(double), TILE,
+                             hipMemcpyDeviceToHost, M) != hipSuccess || hipStreamSynchronize(M) != hipSuccess) return fail(-100, tiles_failed);
+        std::fill(W.begin(), W.end(), 0.0);
+        for (int j = 0; j < TILE; ++j)                     // column j of W = L^-1: forward substitution on e_j
+            for (int i = j; i < TILE; ++i) {
+                double sacc = i == j ? 1.0 : 0.0;
+                for (int k = j; k < i; ++k) sacc -= tile[(size_t)i + (size_t)k * TILE] * W[(size_t)k + (size_t)j * TILE];
+                W[(size_t)i + (size_t)j * TILE] = sacc / tile[(size_t)i + (size_t)i * TILE];
+            }
+        if (hipMemcpyAsync(f->dWt + (size_t)t * TILE * TILE, W.data(), W.size() * sizeof(double), hipMemcpyHostToDevice, M) != hipSuccess ||
+            hipStreamSynchronize(M) != hipSuccess) return fail(-100, tiles_failed);
+        if ((t & 1) == 0 && t + 1 < fv.nt) {               // X(t+1,t) = L(t+1,t): the engine's second copy, in P
+            const size_t off = (size_t)(t + 1) * TILE + (size_t)t * TILE * lda;
+            if (hipMemcpy2DAsync(f->dP + off, lda * sizeof(double), f->dA + off, lda * sizeof(double), TILE * sizeof(double), TILE,
+                                 hipMemcpyDeviceToDevice, M) != hipSuccess) return fail(-100, tiles_failed);
+        }
+    }
+    HIPCHK_AT("cocons_debug_dag_replay", dcmp.alloc(2));
+    // (3) the launch, alone
+    const size_t T64 = 2 * (size_t)fv.mt;
+    unsigned *in = f->dflags, *outw = f->dflags + f->flags_cap, *xr = f->dflags + 2 * (size_t)f->flags_cap;
+    unsigned *abort_word = (unsigned *)(f->dinfo + 1);
+    unsigned *queue = f->ddag, *tdone = f->ddag + 64, *pdone = tdone + T64 * (T64 + 1) / 2;
+    unsigned *pall = pdone + ((size_t)f->dag_nsteps + 2) * T64;
+    unsigned *dcount = pall + (size_t)f->dag_nsteps + 64;
+    f->upd_flops = 0.0;
+    f->nrhs_cur = nrhs;
+    for (int s2 = 0; s2 < f->dag_nsteps; ++s2) count_update_flops(f, 2, 2 * s2 + 2);
+    const double flops = f->upd_flops;
+    HIPCHK_AT("cocons_debug_dag_replay", hipEventCreate(&ev.a));
+    HIPCHK_AT("cocons_debug_dag_replay", hipEventCreate(&ev.b));
+    double ms_sum = 0.0;
+    for (int it = 0; it < reps; ++it) {
+        if (int rc = reset_info(f)) return rc;
+        assemble_sigma(f, theta, 0, 0, f->npad);
+        assemble_rhs(f, mean, true, nullptr, 0, 0, f->npad, true, slots);
+        launch_front_identity(fv.A, fv.lda, f->pad0, fv.mt * TILE, M);
+        panel_ops(f, fv, 0, M);
+        HIPCHK_AT("cocons_debug_dag_replay", hipMemsetAsync(f->ddag, 0, f->ddag_words * sizeof(unsigned), M));
+        HIPCHK_AT("cocons_debug_dag_replay", hipMemsetD32Async((hipDeviceptr_t)f->dflags, 0x3fffffff, 3 * (size_t)f->flags_cap, M));   // in / out / xr: all raised
+        // (as many workgroups take part as in a real evaluation: the engine and its partner are entered on XCD 0 by hand)
+        unsigned *alive_w = f->dflags + 3 * (size_t)f->flags_cap;
+        static const unsigned pair_on_xcd0 = 2u;
+        HIPCHK_AT("cocons_debug_dag_replay", hipMemcpyAsync(alive_w + 16, &pair_on_xcd0, sizeof(unsigned), hipMemcpyHostToDevice, M));
+        HIPCHK_AT("cocons_debug_dag_replay", hipEventRecord(ev.a, M));
+        launch_dag(fv.A, fv.lda, f->dP, f->dWt, (const DagStepHost *)f->ddag_steps, f->dag_nsteps, f->dag_ntasks, queue, tdone,
+                   pdone, (int)T64, pall, f->dpart, dcount, in, outw, xr, abort_word, M, nullptr, alive_w, dag_xcc_quota(), nullptr,
+                   f->dag_have_ftab ? f->ddag_ftab : nullptr, f->dag_xcd_g, f->ddag + f->ddag_xcnt_off);
+        HIPCHK_AT("cocons_debug_dag_replay", hipEventRecord(ev.b, M));
+        HIPCHK_AT("cocons_debug_dag_replay", hipGetLastError());
+        HIPCHK_AT("cocons_debug_dag_replay", hipStreamSynchronize(M));
+        float ms = 0;
+        HIPCHK_AT("cocons_debug_dag_replay", hipEventElapsedTime(&ms, ev.a, ev.b));
+        ms_sum += ms;
+    }
+    HIPCHK_AT("cocons_debug_dag_replay", hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, M));
+    HIPCHK_AT("cocons_debug_dag_replay", hipStreamSynchronize(M));
+    if (f->hinfo[1] != 0) return fail(ENGINE_ABORT, "cocons_debug_dag_replay: a wait of the replayed launch ran out");
+    // the check: every panel the launch formed (blocks 1 .. nsteps - 1) against the plain factor
+    HIPCHK_AT("cocons_debug_dag_replay", hipMemsetAsync(dcmp, 0, 2 * sizeof(unsigned long long), M));
+    const int c0 = 2 * TILE, c1 = 2 * TILE * f->dag_nsteps, rend = fv.mt * TILE - 64 * fv.trim;
+    hipLaunchKernelGGL(panel_diff_kernel, dim3(c1 - c0), dim3(256), 0, M, (const double *)f->dP, (const double *)Lcopy, lda, c0, c1, rend,
+                       dcmp.get());
+    unsigned long long h[2] = {0, 0};
+    HIPCHK_AT("cocons_debug_dag_replay", hipMemcpyAsync(h, dcmp, sizeof h, hipMemcpyDeviceToHost, M));
+    HIPCHK_AT("cocons_debug_dag_replay", hipStreamSynchronize(M));
+    double md, ml;
+    memcpy(&md, &h[0], 8); memcpy(&ml, &h[1], 8);
+    out[0] = ms_sum / reps; out[1] = flops; out[2] = ml > 0 ? md / ml : NAN; out[3] = (double)f->dag_ntasks; out[4] = (double)f->dag_nsteps;
+    return 0;
+}
+
 extern "C" int cocons_debug_dag_replay(cocons_fit *f, const double *theta, const double *mean, int reps, double *out)
 {
     FIT_ENTER(f);
@@ -3914,97 +3976,7 @@ extern "C" int cocons_debug_dag_replay(cocons_fit *f, const double *theta, const
     if (int rc = flags_reset(f, fv.nt)) return rc;
     if (int prc = dag_prepare(f, fv)) return prc;
     if (f->dag_nsteps < 2) return fail(-1, "cocons_debug_dag_replay: problem too small for a DAG head");
-    hipStream_t M = f->stream;
-    const size_t lda = fv.lda;
-    const int nt_head = 2 * f->dag_nsteps + 2;                 // diagonal tiles 2 .. nt_head - 1 belong to the head's blocks
-    // (2) what the engine would publish
-    double *Lcopy = nullptr;
-    HIPCHK(hipMalloc(&Lcopy, lda * (size_t)f->npad * sizeof(double)));
-    int rc = 0;
-    std::vector<double> tile((size_t)TILE * TILE), W((size_t)TILE * TILE);
-    unsigned long long *dcmp = nullptr;
-    do {
-#define CKR(expr) { hipError_t e__ = (expr); if (e__ != hipSuccess) { rc = fail(-100 - (int)e__, "cocons_debug_dag_replay: %s", hipGetErrorString(e__)); break; } }
-        CKR(hipMemcpyAsync(Lcopy, f->dA, lda * (size_t)f->npad * sizeof(double), hipMemcpyDeviceToDevice, M));
-        bool bad = false;
-        for (int t = 2; t < nt_head && t < fv.nt && !bad; ++t) {
-            const double *src = f->dA + (size_t)t * TILE + (size_t)t * TILE * lda;
-            if (hipMemcpy2DAsync(tile.data(), TILE * sizeof(double), src, lda * sizeof(double), TILE * sizeof(double), TILE,
-                                 hipMemcpyDeviceToHost, M) != hipSuccess || hipStreamSynchronize(M) != hipSuccess) { bad = true; break; }
-            std::fill(W.begin(), W.end(), 0.0);
-            for (int j = 0; j < TILE; ++j)                     // column j of W = L^-1: forward substitution on e_j
-                for (int i = j; i < TILE; ++i) {
-                    double sacc = i == j ? 1.0 : 0.0;
-                    for (int k = j; k < i; ++k) sacc -= tile[(size_t)i + (size_t)k * TILE] * W[(size_t)k + (size_t)j * TILE];
-                    W[(size_t)i + (size_t)j * TILE] = sacc / tile[(size_t)i + (size_t)i * TILE];
-                }
-            if (hipMemcpyAsync(f->dWt + (size_t)t * TILE * TILE, W.data(), W.size() * sizeof(double), hipMemcpyHostToDevice, M) != hipSuccess ||
-                hipStreamSynchronize(M) != hipSuccess) { bad = true; break; }
-            if ((t & 1) == 0 && t + 1 < fv.nt) {               // X(t+1,t) = L(t+1,t): the engine's second copy, in P
-                const size_t off = (size_t)(t + 1) * TILE + (size_t)t * TILE * lda;
-                if (hipMemcpy2DAsync(f->dP + off, lda * sizeof(double), f->dA + off, lda * sizeof(double), TILE * sizeof(double), TILE,
-                                     hipMemcpyDeviceToDevice, M) != hipSuccess) { bad = true; break; }
-            }
-        }
-        if (bad) { rc = fail(-100, "cocons_debug_dag_replay: copying the diagonal tiles failed"); break; }
-        CKR(hipMalloc(&dcmp, 2 * sizeof(unsigned long long)));
-        // (3) the launch, alone
-        const size_t T64 = 2 * (size_t)fv.mt;
-        unsigned *in = f->dflags, *outw = f->dflags + f->flags_cap, *xr = f->dflags + 2 * (size_t)f->flags_cap;
-        unsigned *abort_word = (unsigned *)(f->dinfo + 1);
-        unsigned *queue = f->ddag, *tdone = f->ddag + 64, *pdone = tdone + T64 * (T64 + 1) / 2;
-        unsigned *pall = pdone + ((size_t)f->dag_nsteps + 2) * T64;
-        unsigned *dcount = pall + (size_t)f->dag_nsteps + 64;
-        f->upd_flops = 0.0;
-        f->nrhs_cur = nrhs;
-        for (int s2 = 0; s2 < f->dag_nsteps; ++s2) count_update_flops(f, 2, 2 * s2 + 2);
-        const double flops = f->upd_flops;
-        hipEvent_t ea = nullptr, eb = nullptr;
-        CKR(hipEventCreate(&ea));
-        CKR(hipEventCreate(&eb));
-        double ms_sum = 0.0;
-        for (int it = 0; it < reps && rc == 0; ++it) {
-            if ((rc = reset_info(f))) break;
-            assemble_sigma(f, theta, 0, 0, f->npad);
-            assemble_rhs(f, mean, true, nullptr, 0, 0, f->npad, true, slots);
-            launch_front_identity(fv.A, fv.lda, f->pad0, fv.mt * TILE, M);
-            panel_ops(f, fv, 0, M);
-            CKR(hipMemsetAsync(f->ddag, 0, f->ddag_words * sizeof(unsigned), M));
-            CKR(hipMemsetD32Async((hipDeviceptr_t)f->dflags, 0x3fffffff, 3 * (size_t)f->flags_cap, M));   // in / out / xr: all raised
-            // (as many workgroups take part as in a real evaluation: the engine and its partner are entered on XCD 0 by hand)
-            unsigned *alive_w = f->dflags + 3 * (size_t)f->flags_cap;
-            static const unsigned pair_on_xcd0 = 2u;
-            CKR(hipMemcpyAsync(alive_w + 16, &pair_on_xcd0, sizeof(unsigned), hipMemcpyHostToDevice, M));
-            CKR(hipEventRecord(ea, M));
-            launch_dag(fv.A, fv.lda, f->dP, f->dWt, (const DagStepHost *)f->ddag_steps, f->dag_nsteps, f->dag_ntasks, queue, tdone,
-                       pdone, (int)T64, pall, f->dpart, dcount, in, outw, xr, abort_word, M, nullptr, alive_w, dag_xcc_quota(), nullptr,
-                       f->dag_have_ftab ? f->ddag_ftab : nullptr, f->dag_xcd_g, f->ddag + f->ddag_xcnt_off);
-            CKR(hipEventRecord(eb, M));
-            CKR(hipGetLastError());
-            CKR(hipStreamSynchronize(M));
-            float ms = 0;
-            CKR(hipEventElapsedTime(&ms, ea, eb));
-            ms_sum += ms;
-        }
-        if (ea) hipEventDestroy(ea);
-        if (eb) hipEventDestroy(eb);
-        if (rc) break;
-        CKR(hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, M));
-        CKR(hipStreamSynchronize(M));
-        if (f->hinfo[1] != 0) { rc = fail(ENGINE_ABORT, "cocons_debug_dag_replay: a wait of the replayed launch ran out"); break; }
-        // the check: every panel the launch formed (blocks 1 .. nsteps - 1) against the plain factor
-        CKR(hipMemsetAsync(dcmp, 0, 2 * sizeof(unsigned long long), M));
-        const int c0 = 2 * TILE, c1 = 2 * TILE * f->dag_nsteps, rend = fv.mt * TILE - 64 * fv.trim;
-        hipLaunchKernelGGL(panel_diff_kernel, dim3(c1 - c0), dim3(256), 0, M, (const double *)f->dP, (const double *)Lcopy, lda, c0, c1, rend, dcmp);
-        unsigned long long h[2] = {0, 0};
-        CKR(hipMemcpyAsync(h, dcmp, sizeof h, hipMemcpyDeviceToHost, M));
-        CKR(hipStreamSynchronize(M));
-        double md, ml;
-        memcpy(&md, &h[0], 8); memcpy(&ml, &h[1], 8);
-        out[0] = ms_sum / reps; out[1] = flops; out[2] = ml > 0 ? md / ml : NAN; out[3] = (double)f->dag_ntasks; out[4] = (double)f->dag_nsteps;
-#undef CKR
-    } while (0);
-    hipFree(Lcopy); hipFree(dcmp);
+    const int rc = dag_replay_run(f, fv, slots, theta, mean, reps, out);
     f->border_clean = -1; f->border_pending = -1;        // (the buffer holds a half-done factorisation)
     f->dag_used = false;
     return rc;
@@ -4015,24 +3987,15 @@ extern "C" int cocons_debug_dag_replay(cocons_fit *f, const double *theta, const
 extern "C" int cocons_debug_matern(int n, const double *nu, const double *u, double *out)
 {
     if (n <= 0 || !nu || !u || !out) return fail(-1, "cocons_debug_matern: bad argument");
-    hipStream_t s = nullptr;
-    double *d = nullptr;
-    int rc = 0;
-    do {
-        hipError_t e;
-#define CKD(expr) if ((e = (expr)) != hipSuccess) { rc = fail(-100 - (int)e, "cocons_debug_matern: %s", hipGetErrorString(e)); break; }
-        CKD(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        CKD(hipMalloc(&d, (size_t)3 * n * sizeof(double)));
-        CKD(hipMemcpyAsync(d, nu, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
-        CKD(hipMemcpyAsync(d + n, u, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
-        launch_matern_points(n, d, d + n, d + 2 * (size_t)n, s);
-        CKD(hipGetLastError());
-        CKD(hipMemcpyAsync(out, d + 2 * (size_t)n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
-        CKD(hipStreamSynchronize(s));
-#undef CKD
-    } while (0);
-    if (s) { hipStreamSynchronize(s); hipStreamDestroy(s); }
-    hipFree(d);
-    return rc;
+    DevBuf<double> d;
+    StreamDrain s{nullptr, true};
+    HIPCHK_AT("cocons_debug_matern", hipStreamCreateWithFlags(&s.s, hipStreamNonBlocking));
+    HIPCHK_AT("cocons_debug_matern", d.alloc((size_t)3 * n));
+    HIPCHK_AT("cocons_debug_matern", upload_canon(d, nu, (size_t)n, s));
+    HIPCHK_AT("cocons_debug_matern", upload_canon(d + n, u, (size_t)n, s));
+    launch_matern_points(n, d, d + n, d + 2 * (size_t)n, s);
+    HIPCHK_AT("cocons_debug_matern", hipGetLastError());
+    HIPCHK_AT("cocons_debug_matern", hipMemcpyAsync(out, d + 2 * (size_t)n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK_AT("cocons_debug_matern", hipStreamSynchronize(s));
+    return 0;
 }
-
