@@ -415,6 +415,22 @@ struct cocons_fit {
                                   // handle's stream self-test while it launches probe kernels on this handle's streams
                                   // (engine_warm: try_lock under the registry's lock -- a busy handle is not probed, a probed one
                                   // can neither be used nor destroyed until the probe is over).  A pointer: the struct is memset
+    struct KrigeState *krige;     // kriging state (cocons_krige_prepare): one factor of Sigma(theta) held apart from dA
+};
+
+// Kriging state of a dense handle (cocons_krige_prepare / _apply / _release).  Everything apply reads lives here, owned by
+// the state, so no other entry point on the handle -- predict growing dA, the batch slots, engine retries -- can touch it.
+struct KrigeState {
+    DevBuf<double> L;             // packed lower tiles of the factor: nt (nt + 1) / 2 tiles of 128 x 128 (kernels.h launch_krige_pack)
+    DevBuf<double> Q;             // nt x 2048: the triangular-solve operands of every diagonal tile
+    DevBuf<double> w;             // npad: L^-1 (z[:, z_col] - X mean), zero in the padding and slot columns
+    DevBuf<double> loc;           // LOCP_FIELDS x npad: observation-side SoA in the prediction branch's smoothness
+    DevBuf<double> C;             // rows x npad: one chunk of cross-covariance rows, solved in place
+    DevBuf<double> Xp, lp, locp;  // the chunk's X_pred (rows x p), locations (rows x 2) and SoA (LOCP_FIELDS x rows)
+    DevBuf<double> st, qd;        // rows: the chunk's outputs
+    std::vector<double> theta;    // 6 p: the prepared theta (canonicalised)
+    int rows = 0;                 // rows per chunk (a multiple of 64)
+    long long bytes = 0;          // device bytes held
 };
 
 static void shard_state_free(struct ShardState *S);
@@ -497,6 +513,7 @@ extern "C" void cocons_fit_destroy(cocons_fit *f)
         if (f->slots) { for (auto c : *f->slots) cocons_fit_destroy(c); delete f->slots; f->slots = nullptr; }
         if (f->unsorted) { cocons_fit_destroy(f->unsorted); f->unsorted = nullptr; }
         if (f->taper_twin) { cocons_fit_destroy(f->taper_twin); f->taper_twin = nullptr; }
+        delete f->krige; f->krige = nullptr;                    // (its buffers: the main stream is drained above)
         if (f->stream2) hipStreamDestroy(f->stream2);
         if (f->own_stream && f->stream) hipStreamDestroy(f->stream);
     }
@@ -2649,6 +2666,174 @@ extern "C" int cocons_predict_dense(cocons_fit *f, const double *theta, const do
     }
 }
 
+// ---------------------------------------------------------------------------
+// Kriging from a held factor: cocons_krige_prepare factors Sigma(theta) once (residual row of z_col as the one right-hand
+// side) and keeps the factor in the handle's KrigeState; cocons_krige_apply then predicts any number of new locations in
+// chunks of `rows` against it -- cross-covariance chunk (pair_rect), V = C L^-T with both reductions fused
+// (launch_krige_solve) -- with device memory independent of m.  Outputs as cocons_predict_dense's.
+static constexpr size_t KRIGE_CHUNK_BYTES = (size_t)1 << 30;      // max_rows = 0: the chunk buffers stay within 1 GiB
+static constexpr int KRIGE_ROWS_CAP = 16384;                       // ... and within 16384 rows
+
+static size_t krige_row_bytes(const cocons_fit *f)
+{
+    return ((size_t)f->npad + (size_t)f->p + 2 + LOCP_FIELDS + 2) * sizeof(double);     // C, Xp, lp, locp, st, qd
+}
+
+static int krige_rows(const cocons_fit *f, int max_rows)
+{
+    size_t r = max_rows > 0 ? (size_t)max_rows : std::min<size_t>(KRIGE_CHUNK_BYTES / krige_row_bytes(f), KRIGE_ROWS_CAP);
+    r = r / 64 * 64;                    // chunks of whole 64-row strips: a row's position in its strip never depends on the split
+    return (int)std::max<size_t>(r, 64);
+}
+
+static int krige_sharded(cocons_fit *f, const char *who)
+{
+    if (f->coll_kind && f->coll_world > 1) return fail(-1, "%s: not available on a sharded handle (world > 1)", who);
+    return 0;
+}
+
+extern "C" int cocons_krige_prepare(cocons_fit *f, const double *theta, const double *mean, int z_col, int max_rows)
+{
+    if (!f) return fail(-1, "cocons_krige_prepare: null fit handle");
+    FIT_ENTER(f);
+    if (int rc = no_taper(f, "cocons_krige_prepare")) return rc;
+    if (int rc = krige_sharded(f, "cocons_krige_prepare")) return rc;
+    if (!theta || !mean || z_col < 0 || z_col >= f->r || max_rows < 0) return fail(-1, "cocons_krige_prepare: bad argument");
+    delete f->krige;                    // replaced -- and gone if this prepare fails
+    f->krige = nullptr;
+    const int p = f->p, n = f->n, npad = f->npad, nt = f->nt;
+    std::unique_ptr<KrigeState> K(new KrigeState());
+    K->rows = krige_rows(f, max_rows);
+    K->theta.resize((size_t)6 * p);
+    for (int i = 0; i < 6 * p; ++i) K->theta[i] = canon_nan(theta[i]);
+    const size_t R = (size_t)K->rows, ntile = (size_t)nt * (nt + 1) / 2;
+    StreamDrain s{f->stream, false};
+    HIPCHK_AT("cocons_krige_prepare", K->L.alloc(ntile * TILE * TILE));
+    HIPCHK_AT("cocons_krige_prepare", K->Q.alloc((size_t)nt * 2048));
+    HIPCHK_AT("cocons_krige_prepare", K->w.alloc((size_t)npad));
+    HIPCHK_AT("cocons_krige_prepare", K->loc.alloc((size_t)LOCP_FIELDS * npad));
+    HIPCHK_AT("cocons_krige_prepare", K->C.alloc(R * npad));
+    HIPCHK_AT("cocons_krige_prepare", K->Xp.alloc(R * p));
+    HIPCHK_AT("cocons_krige_prepare", K->lp.alloc(R * 2));
+    HIPCHK_AT("cocons_krige_prepare", K->locp.alloc(R * LOCP_FIELDS));
+    HIPCHK_AT("cocons_krige_prepare", K->st.alloc(R));
+    HIPCHK_AT("cocons_krige_prepare", K->qd.alloc(R));
+    K->bytes = (long long)((ntile * TILE * TILE + (size_t)nt * 2048 + (size_t)npad * (1 + LOCP_FIELDS)) * sizeof(double) +
+                           R * krige_row_bytes(f));
+    // the padding and slot columns of a chunk are never written by the assembly: zero once
+    HIPCHK_AT("cocons_krige_prepare", hipMemsetAsync(K->C, 0, R * npad * sizeof(double), s));
+    const double *th = K->theta.data();
+    if (int rc = fit_alloc_matrix(f, 1)) return rc;
+    for (;;) {
+        if (int rc = reset_info(f)) return rc;
+        f->nrhs_cur = 1;
+        assemble_sigma(f, th, 0, 0, npad);
+        // row npad: residual of realization z_col (the rows under it and the columns >= n cleared)
+        RhsArgs ra;
+        memset(&ra, 0, sizeof ra);
+        ra.n = n; ra.p = p; ra.X = f->dX; ra.ldx = n; ra.use_trend = 1;
+        for (int i = 0; i < p; ++i) ra.mean[i] = canon_nan(mean[i]);
+        ra.src = f->dz + (size_t)z_col * n; ra.lds = n;
+        ra.out = f->dA; ra.ld = f->lda; ra.row0 = npad; ra.nrows = 1;
+        ra.nrows_zero = f->rhs_act - 1;
+        ra.col0 = 0; ra.ncols_out = npad;
+        launch_rhs_rows(ra, s);
+        // the plain schedules (dag_ok = false): the factor lies whole in dA, with L^-1 r in row npad
+        if (int rc = factorize(f, main_view(f), nullptr)) return rc;
+        launch_krige_pack(f->dA, f->lda, nt, npad, f->pad0, n, K->L, K->Q, K->w, s);
+        HIPCHK_AT("cocons_krige_prepare", hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT("cocons_krige_prepare", hipGetLastError());
+        HIPCHK_AT("cocons_krige_prepare", hipStreamSynchronize(s));
+        int st = info_status(f);
+        if (engine_retry(f, st)) continue;
+        if (st) return st;              // failing minor: no state (K's buffers are freed on the way out)
+        break;
+    }
+    // observation-side SoA in the smoothness of cov_rns_pred (always logistic + sqrt, see cocons_predict_dense)
+    ThetaVecs tv;
+    make_theta_vecs(th, p, tv);
+    const ModeSel ms = select_mode(th, p, f->smooth_limits, 2);
+    LocArgs lo;
+    lo.n = n; lo.p = p; lo.X = f->dX; lo.ldx = n; lo.locs = f->dlocs; lo.ldl = n;
+    lo.out = K->loc; lo.stride = npad; lo.smooth_kind = ms.smooth_kind;
+    lo.smooth_min = f->smooth_limits[0]; lo.smooth_max = f->smooth_limits[1]; lo.th = tv;
+    launch_loc_params(lo, s);
+    HIPCHK_AT("cocons_krige_prepare", hipGetLastError());
+    HIPCHK_AT("cocons_krige_prepare", hipStreamSynchronize(s));
+    f->krige = K.release();
+    return 0;
+}
+
+extern "C" int cocons_krige_apply(cocons_fit *f, int m, const double *locs_pred, const double *X_pred,
+                                  double *stochastic, double *quadform)
+{
+    if (m < 0 || (m > 0 && (!locs_pred || !X_pred || !stochastic || !quadform)))
+        return fail(-1, "cocons_krige_apply: bad argument (m < 0 or a null pointer)");
+    if (!f) return fail(-1, "cocons_krige_apply: null fit handle");
+    FIT_ENTER(f);
+    if (int rc = no_taper(f, "cocons_krige_apply")) return rc;
+    if (int rc = krige_sharded(f, "cocons_krige_apply")) return rc;
+    KrigeState *K = f->krige;
+    if (!K) return fail(-1, "cocons_krige_apply: no kriging state on this handle (call cocons_krige_prepare first)");
+    const int p = f->p, rows = K->rows;
+    const double *th = K->theta.data();
+    ThetaVecs tv;
+    make_theta_vecs(th, p, tv);
+    const ModeSel ms = select_mode(th, p, f->smooth_limits, 2);
+    std::vector<double> hX((size_t)rows * p), hl((size_t)rows * 2);
+    StreamDrain s{f->stream, false};
+    for (int b = 0; b < m; b += rows) {
+        const int mc = std::min(rows, m - b);
+        // the chunk's rows of the caller's column-major m x p and m x 2 (drained below before the staging is reused)
+        for (int j = 0; j < p; ++j) memcpy(&hX[(size_t)j * mc], X_pred + b + (size_t)j * m, (size_t)mc * sizeof(double));
+        for (int j = 0; j < 2; ++j) memcpy(&hl[(size_t)j * mc], locs_pred + b + (size_t)j * m, (size_t)mc * sizeof(double));
+        HIPCHK_AT("cocons_krige_apply", upload_canon(K->Xp, hX.data(), (size_t)mc * p, s));
+        HIPCHK_AT("cocons_krige_apply", upload_canon(K->lp, hl.data(), (size_t)mc * 2, s));
+        LocArgs lp;
+        lp.n = mc; lp.p = p; lp.X = K->Xp; lp.ldx = mc; lp.locs = K->lp; lp.ldl = mc;
+        lp.out = K->locp; lp.stride = rows; lp.smooth_kind = ms.smooth_kind;
+        lp.smooth_min = f->smooth_limits[0]; lp.smooth_max = f->smooth_limits[1]; lp.th = tv;
+        launch_loc_params(lp, s);
+        // cross-covariance of the chunk with the caller's observations only: columns [pad0, n) in the handle's order
+        PairArgs pa;
+        memset(&pa, 0, sizeof pa);
+        pa.n = f->n_user; pa.m = mc; pa.rows = K->locp; pa.stride_rows = rows;
+        pa.cols = K->loc + f->pad0; pa.stride = f->npad;
+        pa.out = K->C + (size_t)f->pad0 * rows; pa.ld = rows; pa.nrows_out = mc; pa.ncols_out = f->n_user;
+        pa.gr = ms.gr; pa.nu_fixed = 0.0;
+        launch_pair_rect(MODE_GEOM, pa, s);
+        launch_krige_solve(K->L, K->Q, K->w, f->nt, K->C, rows, mc, f->pad0, f->n, K->st, K->qd, s);
+        HIPCHK_AT("cocons_krige_apply", hipMemcpyAsync(stochastic + b, K->st, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT("cocons_krige_apply", hipMemcpyAsync(quadform + b, K->qd, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT("cocons_krige_apply", hipGetLastError());
+        HIPCHK_AT("cocons_krige_apply", hipStreamSynchronize(s));
+    }
+    return 0;
+}
+
+extern "C" int cocons_krige_release(cocons_fit *f)
+{
+    if (!f) return fail(-1, "cocons_krige_release: null fit handle");
+    FIT_ENTER(f);
+    delete f->krige;                    // (every entry point drains the main stream before it returns: nothing in flight uses it)
+    f->krige = nullptr;
+    return 0;
+}
+
+// out4 = { prepared (0 / 1), device bytes held, rows per chunk, n }
+extern "C" int cocons_krige_info(cocons_fit *f, long long *out4)
+{
+    if (!f) return fail(-1, "cocons_krige_info: null fit handle");
+    if (!out4) return fail(-1, "cocons_krige_info: null argument");
+    FIT_ENTER(f);
+    const KrigeState *K = f->krige;
+    out4[0] = K ? 1 : 0;
+    out4[1] = K ? K->bytes : 0;
+    out4[2] = K ? K->rows : 0;
+    out4[3] = f->n_user;
+    return 0;
+}
+
 // Kriging core of the sparse branch of cocoPredict (R/predict.R:216-283) on a taper handle: S = taper o
 // cov_rns_taper(theta) as in the objective, C = pred_taper o cov_rns_taper_pred(theta) (m x n, its own pattern);
 // one bordered DENSE factorisation replaces  inv_cov <- spam::solve(S, t(C))  ("memory intensive", :244) and gives
@@ -2825,6 +3010,7 @@ extern "C" int cocons_sim_taper(cocons_fit *f, const double *theta, const double
     // pass the same pivot (the fill-reducing order of spam's chol: computed once per coco object)
     if (!f->taper_twin || *f->twin_perm != tperm) {
         if (f->taper_twin) { cocons_fit_destroy(f->taper_twin); f->taper_twin = nullptr; }
+        delete f->krige; f->krige = nullptr;                    // (its buffers: the main stream is drained above)
         delete f->twin_perm; f->twin_perm = nullptr;
         cocons_fit *t = taper_create_ordered(n, f->p, f->r, f->h_locs->data(), f->h_X->data(), f->h_z->data(), f->smooth_limits,
                                              f->device, (int)f->h_tci->size(), f->h_tci->data(), f->h_trp->data(),

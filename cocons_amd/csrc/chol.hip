@@ -3096,5 +3096,203 @@ void launch_row_reduce(const double *A, size_t lda, int n, int rowy, int row0, i
                        scratch, m, nchunks, stoch, quad);
 }
 
+
+// ---------------------------------------------------------------------------
+// Kriging from a held factor (cocons_krige_*): V = C L^-T for a chunk C of cross-covariance rows (M x npad, column-major,
+// ld ldc), with stoch[i] = V(i,:) w and quad[i] = V(i,:) V(i,:)' taken as V is formed; V itself overwrites C.
+//
+// The factor is held PACKED: lower tile (I, J), I >= J, of 128 x 128 doubles (column-major, ld 128) at tile index
+// I (I + 1) / 2 + J, strict upper triangle of the diagonal tiles zero.  Per diagonal tile the solve also keeps the
+// 4 x 4 inverse operands of trsm16 (2048 doubles, the layout fetch_factor_tile reads: [16-block j][group s][lane]).
+//
+// Right-looking over the 128-column tiles J = 0 .. nt-1, two launches per tile:
+//   krige_diag_kernel   V_J = R_J L_JJ^-T   one workgroup per 64-row strip (a wave 16 rows): trsm_tile_kernel's block
+//                       substitution in registers, then the strip's partial reductions, added to stoch / quad in J order
+//   krige_update_kernel R_I -= V_J L_IJ^T  for every I > J: one workgroup per (64-row strip, tile I), K = 128 on
+//                       v_mfma_f64_16x16x4_f64; L_IJ streams through LDS in four 32-column slices
+// Every element's sum order is fixed by J, the 16-column blocks and the MFMA's own order, and a row never meets another
+// row: the outputs of a row do not depend on M, on the chunk split or on the other rows (bit for bit, given the row's
+// position modulo 64 -- the caller's chunks are multiples of 64 rows).
+// Columns outside [c_lo, c_hi) (the handle's front padding and slots) are zero in V whatever C holds there.
+
+// (I, J) of packed tile t
+__device__ __forceinline__ void krige_tile_ij(int t, int &I, int &J)
+{
+    int i = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
+    while ((i + 1) * (i + 2) / 2 <= t) ++i;
+    while (i * (i + 1) / 2 > t) --i;
+    I = i; J = t - i * (i + 1) / 2;
+}
+
+__global__ void __launch_bounds__(256)
+krige_pack_kernel(const double *A, size_t lda, double *Lp)
+{
+    int I, J;
+    krige_tile_ij((int)blockIdx.x, I, J);
+    const double *src = A + (size_t)I * TILE + (size_t)J * TILE * lda;
+    double *dst = Lp + (size_t)blockIdx.x * TILE * TILE;
+    for (int e = threadIdx.x; e < TILE * TILE; e += 256) {
+        const int r = e & (TILE - 1), c = e >> 7;
+        const double v = src[(size_t)r + (size_t)c * lda];
+        dst[e] = (I == J && r < c) ? 0.0 : v;
+    }
+}
+
+// per diagonal tile J: the trsm16 operands (inverse of every 4 x 4 diagonal sub-block, formed as potrf16_step forms it,
+// with 1 / l for the pivot reciprocals) and w's 128 entries (row `rowy` of A, zero outside [c_lo, c_hi))
+__global__ void __launch_bounds__(256)
+krige_qprep_kernel(const double *A, size_t lda, int rowy, int c_lo, int c_hi, double *Qp, double *w)
+{
+    const int J = blockIdx.x, tid = threadIdx.x;
+    if (tid < TILE) {
+        const int c = J * TILE + tid;
+        w[c] = (c >= c_lo && c < c_hi) ? A[(size_t)rowy + (size_t)c * lda] : 0.0;
+    }
+    for (int e = tid; e < 8 * 256; e += 256) {
+        const int jb = e >> 8, s = (e >> 6) & 3, lane = e & 63;
+        const int m = lane & 15, k = lane >> 4, c = m & 3;
+        double q = 0.0;
+        if ((m >> 2) == s && k <= c) {
+            const double *L = A + (size_t)(J * TILE + 16 * jb + 4 * s) * (1 + lda);      // the 4 x 4 diagonal sub-block
+            const double l10 = L[1], l20 = L[2], l30 = L[3], l21 = L[2 + lda], l31 = L[3 + lda], l32 = L[3 + 2 * lda];
+            const double r0 = 1.0 / L[0], r1 = 1.0 / L[1 + lda], r2 = 1.0 / L[2 + 2 * lda], r3 = 1.0 / L[3 + 3 * lda];
+            const double m00 = r0, m11 = r1, m22 = r2, m33 = r3;
+            const double m10 = -(l10 * m00) * r1;
+            const double m21 = -(l21 * m11) * r2;
+            const double m32 = -(l32 * m22) * r3;
+            const double m20 = -fma(l21, m10, l20 * m00) * r2;
+            const double m31 = -fma(l32, m21, l31 * m11) * r3;
+            const double m30 = -fma(l32, m20, fma(l31, m10, l30 * m00)) * r3;
+            q = sel_lower4(c, k, m00, m10, m11, m20, m21, m22, m30, m31, m32, m33);
+        }
+        Qp[(size_t)J * 2048 + e] = q;
+    }
+}
+
+// LDS 90 KiB (the 36 lower 16 x 16 blocks of L_JJ and its trsm16 operands): one workgroup per CU.  There are only
+// M / 64 of them per launch and each is short; the update launches carry the arithmetic.
+__global__ void __launch_bounds__(256)
+krige_diag_kernel(const double *Lp, const double *Qp, const double *w, double *C, size_t ldc, int J, int c_lo, int c_hi,
+                  double *stoch, double *quad)
+{
+    __shared__ double SL[36 * 256];
+    __shared__ double QS[8 * 256];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    fetch_factor_tile<false>(Lp + (size_t)(J * (J + 1) / 2 + J) * TILE * TILE, TILE, 0, Qp + (size_t)J * 2048, SL, QS, tid);
+    const int rs = 64 * (int)blockIdx.x + 16 * wave, c0 = J * TILE;
+    d4 B[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        B[j] = glb_blk(C, ldc, rs, c0 + 16 * j, lane);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int c = c0 + 16 * j + 4 * r + (lane >> 4);
+            if (c < c_lo || c >= c_hi) B[j][r] = 0.0;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        d4 L = lds_blk(SL + (j * (j + 1) / 2 + j) * 256, lane);
+        double Q[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) Q[s] = QS[j * 256 + s * 64 + lane];
+        trsm16(B[j], L, Q);
+        d4 NX = -B[j];
+#pragma unroll
+        for (int jj = j + 1; jj < 8; ++jj) {
+            d4 Lb = lds_blk(SL + (jj * (jj + 1) / 2 + j) * 256, lane);
+            blk_mma(B[jj], NX, Lb);
+        }
+    }
+    // row (lane & 15) of the wave's 16 rows, columns 16 j + 4 r + (lane >> 4): partial sums in (j, r) order, then the four
+    // column groups of a row combined in a fixed tree
+    double sp = 0.0, qp = 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int c = c0 + 16 * j + 4 * r + (lane >> 4);
+            const double v = (c < c_lo || c >= c_hi) ? 0.0 : B[j][r];
+            B[j][r] = v;
+            sp = fma(v, w[c], sp);
+            qp = fma(v, v, qp);
+        }
+    sp += __shfl_xor(sp, 16);
+    qp += __shfl_xor(qp, 16);
+    sp += __shfl_xor(sp, 32);
+    qp += __shfl_xor(qp, 32);
+    if (lane < 16) {
+        const int i = rs + lane;
+        if (J == 0) { stoch[i] = sp; quad[i] = qp; }
+        else { stoch[i] += sp; quad[i] += qp; }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) glb_blk_store(C, ldc, rs, c0 + 16 * j, lane, B[j]);
+}
+
+// R_I -= V_J L_IJ^T, I = J + 1 + blockIdx.y, rows 64 blockIdx.x .. + 63 (a wave 16 rows, all 128 columns of tile I in
+// eight accumulators).  LDS 32 KiB (a 128 x 32 slice of L_IJ as 16 x 16 blocks in lds_blk layout).  188 VGPRs + 64 AGPRs
+// (the register-staged slice included): 2 waves per SIMD, 2 workgroups per CU; no scratch.
+constexpr int KU_KC = 32;
+__global__ void __launch_bounds__(256)
+krige_update_kernel(const double *Lp, double *C, size_t ldc, int J)
+{
+    __shared__ double LS[TILE * KU_KC];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int I = J + 1 + (int)blockIdx.y;
+    const double *Lt = Lp + (size_t)(I * (I + 1) / 2 + J) * TILE * TILE;
+    const int rs = 64 * (int)blockIdx.x + 16 * wave;
+    d4 acc[8];
+#pragma unroll
+    for (int jb = 0; jb < 8; ++jb) acc[jb] = glb_blk(C, ldc, rs, I * TILE + 16 * jb, lane);
+    for (int kc = 0; kc < TILE / KU_KC; ++kc) {
+        double v[TILE * KU_KC / 256];
+#pragma unroll
+        for (int q = 0; q < TILE * KU_KC / 256; ++q) {
+            const int e = tid + 256 * q, j = e & (TILE - 1), k = e >> 7;
+            v[q] = Lt[(size_t)j + (size_t)(KU_KC * kc + k) * TILE];
+        }
+        __syncthreads();                  // every wave is done with the previous slice
+#pragma unroll
+        for (int q = 0; q < TILE * KU_KC / 256; ++q) {
+            const int e = tid + 256 * q, j = e & (TILE - 1), k = e >> 7;
+            LS[(((j >> 4) * (KU_KC / 16) + (k >> 4)) << 8) + ((k & 15) << 4) + (j & 15)] = v[q];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kb = 0; kb < KU_KC / 16; ++kb) {
+            const d4 NP = -glb_blk(C, ldc, rs, J * TILE + KU_KC * kc + 16 * kb, lane);
+#pragma unroll
+            for (int jb = 0; jb < 8; ++jb) {
+                const d4 Q = lds_blk(LS + ((jb * (KU_KC / 16) + kb) << 8), lane);
+                blk_mma(acc[jb], NP, Q);
+            }
+        }
+    }
+#pragma unroll
+    for (int jb = 0; jb < 8; ++jb) glb_blk_store(C, ldc, rs, I * TILE + 16 * jb, lane, acc[jb]);
+}
+
+void launch_krige_pack(const double *A, size_t lda, int nt, int rowy, int c_lo, int c_hi, double *Lp, double *Qp, double *w,
+                       hipStream_t s)
+{
+    if (nt <= 0) return;
+    hipLaunchKernelGGL(krige_pack_kernel, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, s, A, lda, Lp);
+    hipLaunchKernelGGL(krige_qprep_kernel, dim3(nt), dim3(256), 0, s, A, lda, rowy, c_lo, c_hi, Qp, w);
+}
+
+void launch_krige_solve(const double *Lp, const double *Qp, const double *w, int nt, double *C, size_t ldc, int rows,
+                        int c_lo, int c_hi, double *stoch, double *quad, hipStream_t s)
+{
+    if (rows <= 0 || nt <= 0) return;
+    const unsigned strips = (unsigned)((rows + 63) / 64);
+    for (int J = 0; J < nt; ++J) {
+        hipLaunchKernelGGL(krige_diag_kernel, dim3(strips), dim3(256), 0, s, Lp, Qp, w, C, ldc, J, c_lo, c_hi, stoch, quad);
+        if (J + 1 < nt)
+            hipLaunchKernelGGL(krige_update_kernel, dim3(strips, (unsigned)(nt - 1 - J)), dim3(256), 0, s, Lp, C, ldc, J);
+    }
+}
+
 }  // namespace cocons
 

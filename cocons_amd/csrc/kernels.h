@@ -272,6 +272,16 @@ void launch_trmm_lower(const double *A, size_t lda, int n, const double *E, int 
 // Each band tile is read once per 64 draws; the sum order is fixed (bit-identical launches).
 void launch_band_trmm(const double *A, size_t lda, int skew, int npad, const int *d_hi, int nt, int n, const double *E,
                       int lde, int nsim, const double *trend, double *Y, int ldy, hipStream_t s);
+// Kriging from a held factor (cocons_krige_*).  pack: the lower tiles of the factor in A (nt x nt tiles) into Lp
+// (nt (nt + 1) / 2 tiles of 128 x 128, tile (I, J) at I (I + 1) / 2 + J, diagonal tiles' upper triangle zero), the
+// triangular-solve operands of every diagonal tile into Qp (nt x 2048) and w[c] = A(rowy, c) for c in [c_lo, c_hi), else 0
+// (npad doubles).  solve: V = C L^-T for rows [0, rows) of C (column-major, ld ldc >= rows rounded up to 64, npad columns;
+// V overwrites C), stoch[i] = V(i,:) w, quad[i] = V(i,:) V(i,:)'; columns outside [c_lo, c_hi) count as zero.  Rows are
+// independent and every sum order is fixed (bit-identical per row whatever else the chunk holds).
+void launch_krige_pack(const double *A, size_t lda, int nt, int rowy, int c_lo, int c_hi, double *Lp, double *Qp, double *w,
+                       hipStream_t s);
+void launch_krige_solve(const double *Lp, const double *Qp, const double *w, int nt, double *C, size_t ldc, int rows,
+                        int c_lo, int c_hi, double *stoch, double *quad, hipStream_t s);
 // out[i + s ldo] = Y[pos[i] + s ldy] for i < n, s < ncol
 void launch_gather_rows(const double *Y, int ldy, const int *pos, int n, int ncol, double *out, int ldo, hipStream_t s);
 

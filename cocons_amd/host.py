@@ -290,6 +290,31 @@ class CoconsFit:
                                                 _p(st), _p(qf)), "cocons_predict_dense")
         return st, qf
 
+    def krige_prepare(self, theta_list, z_col=0, max_rows=0):
+        """Factor Sigma(theta) once and keep the factor on the handle (cocons_krige_prepare): krige_core then predicts
+        at any number of new locations without factoring again.  max_rows: rows per chunk (0: the library's default)."""
+        T = theta_table(theta_list)
+        mean = np.ascontiguousarray(np.asarray(theta_list["mean"], dtype=np.float64))
+        _lib.check(self._L.cocons_krige_prepare(self._h, _p(T), _p(mean), int(z_col), int(max_rows)),
+                   "cocons_krige_prepare")
+
+    def krige_core(self, locs_pred, x_covariates_pred):
+        """(stochastic, quadform) at the new locations against the prepared factor, as predict_core gives them."""
+        lp, Xp = _f(locs_pred), _f(x_covariates_pred)
+        m = Xp.shape[0]
+        st, qf = np.empty(m), np.empty(m)
+        _lib.check(self._L.cocons_krige_apply(self._h, m, _p(lp), _p(Xp), _p(st), _p(qf)), "cocons_krige_apply")
+        return st, qf
+
+    def krige_release(self):
+        _lib.check(self._L.cocons_krige_release(self._h), "cocons_krige_release")
+
+    def krige_info(self):
+        """{prepared, bytes, rows, n}: whether a state is held, its device bytes, rows per chunk, observations."""
+        out = (ctypes.c_longlong * 4)()
+        _lib.check(self._L.cocons_krige_info(self._h, out), "cocons_krige_info")
+        return {"prepared": bool(out[0]), "bytes": int(out[1]), "rows": int(out[2]), "n": int(out[3])}
+
     def cov_rows(self, theta_list, index, cor=False, classic=False):
         """Rows `index` (0-based) of cov_rns / cov_rns_classic at the fit's locations, or of cov2cor of it,
         without the n x n matrix (what plot(type = "correlations") reads, R/methods.R:161-165)."""
@@ -684,3 +709,35 @@ def cocoPredict_dense(theta_list, locs, newlocs, X_std, X_pred_std, smooth_limit
     neg = unc < 1e-10
     unc[neg] = np.abs(unc[neg])                                                            # :175-177
     return {"systematic": systematic, "stochastic": st, "sd.pred": np.sqrt(unc)}
+
+
+def _predict_outputs(theta_list, X_pred_std, st, qf, type):
+    """cocoPredict_dense's host lines after the kriging core (R/predict.R:165-183)."""
+    Xp = np.asarray(X_pred_std, dtype=np.float64)
+    systematic = Xp @ np.asarray(theta_list["mean"], dtype=np.float64)
+    if type == "mean":
+        return {"systematic": systematic, "stochastic": st}
+    with np.errstate(invalid="ignore"):
+        unc = 1 / np.exp(-(Xp @ theta_list["std.dev"])) + np.exp(Xp @ theta_list["nugget"])   # :170-171
+    unc = unc - qf                                                                         # :173
+    neg = unc < 1e-10
+    unc[neg] = np.abs(unc[neg])                                                            # :175-177
+    return {"systematic": systematic, "stochastic": st, "sd.pred": np.sqrt(unc)}
+
+
+def cocoPredict_dense_chunked(theta_list, locs, newlocs, X_std, X_pred_std, smooth_limits, z, type="pred", fit=None,
+                              max_rows=0):
+    """cocoPredict_dense from one held factor: Sigma(theta) is factored once (krige_prepare) and the new locations are
+    predicted in chunks of at most max_rows rows (0: the library's default), so that device memory does not grow with
+    their number.  Same arguments and outputs as cocoPredict_dense; the handle's kriging state is released on return."""
+    f, own = _with_fit(fit, locs, X_std, z, smooth_limits)
+    try:
+        f.krige_prepare(theta_list, max_rows=max_rows)
+        try:
+            st, qf = f.krige_core(newlocs, X_pred_std)
+        finally:
+            f.krige_release()
+    finally:
+        if own:
+            f.close()
+    return _predict_outputs(theta_list, X_pred_std, st, qf, type)

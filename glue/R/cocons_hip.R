@@ -101,6 +101,23 @@ GetNeg2loglikelihoodREML <- function(theta, par.pos, locs, x_covariates, x_betas
   res[[2]]
 }
 
+# the same core at any number of new locations from ONE factorisation (a map grid, several newdatasets, a map in pieces):
+#   .cocons.hip.krige.prepare(fit, theta_list)            # Sigma(theta) factored once, the factor kept on the handle
+#   kr <- .cocons.hip.krige(fit, newlocs, X_pred_std)     # as often as needed: chunked, device memory independent of m
+#   .cocons.hip.krige.release(fit)                        # (or when the handle is closed)
+.cocons.hip.krige.prepare <- function(fit, theta_list, z_col = 1L, max_rows = 0L) {
+  res <- .Call(`_cocons_hip_krige_prepare`, fit, theta_list[-1], theta_list$mean, as.integer(z_col), as.integer(max_rows))
+  if (res[[1]] > 0L) stop("Cholesky error")
+  invisible(NULL)
+}
+
+.cocons.hip.krige <- function(fit, newlocs, X_pred) {
+  res <- .Call(`_cocons_hip_krige`, fit, newlocs, X_pred)
+  res[[2]]
+}
+
+.cocons.hip.krige.release <- function(fit) invisible(.Call(`_cocons_hip_krige_release`, fit))
+
 # rows of cov2cor(cov_rns(...)) for plot(type = "correlations") (R/methods.R:161-165): tmp_cov[ww, ]
 .cocons.hip.cor.rows <- function(fit, theta_list, index, classic = FALSE)
   .Call(`_cocons_hip_cov_rows`, fit, theta_list[-1], classic, as.integer(index), TRUE)

@@ -452,6 +452,41 @@ SEXP _cocons_hip_predict(SEXP fitp, SEXP theta, SEXP mean, SEXP z_col, SEXP locs
     return out;
 }
 
+/* kriging from a held factor: factor Sigma(theta) once for realization z_col (1-based) and keep it on the handle;
+ * max_rows = 0: the library's default chunk.  list(status, NULL) -- status > 0: the failing minor, no state kept */
+SEXP _cocons_hip_krige_prepare(SEXP fitp, SEXP theta, SEXP mean, SEXP z_col, SEXP max_rows)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp);
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    if (XLENGTH(mean) != p) Rf_error("theta$mean must have length %d", p);
+    int rc = cocons_krige_prepare(f, T, REAL(mean), Rf_asInteger(z_col) - 1, Rf_asInteger(max_rows));
+    hip_check(rc, "cocoPredict (krige prepare)");
+    return status_value(rc, R_NilValue);
+}
+
+/* kriging core at new locations against the held factor: list(status, cbind(stochastic, quadform)) */
+SEXP _cocons_hip_krige(SEXP fitp, SEXP locs_pred, SEXP X_pred)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), m = Rf_nrows(X_pred);
+    if (Rf_ncols(X_pred) != p || Rf_nrows(locs_pred) != m || Rf_ncols(locs_pred) != 2)
+        Rf_error("prediction design / locations do not match the fit");
+    SEXP v = PROTECT(Rf_allocMatrix(REALSXP, m, 2));
+    int rc = cocons_krige_apply(f, m, REAL(locs_pred), REAL(X_pred), REAL(v), REAL(v) + m);
+    hip_check(rc, "cocoPredict (krige)");
+    SEXP out = status_value(rc, v);
+    UNPROTECT(1);
+    return out;
+}
+
+SEXP _cocons_hip_krige_release(SEXP fitp)
+{
+    hip_check(cocons_krige_release(fit_of(fitp)), "cocoPredict (krige release)");
+    return R_NilValue;
+}
+
 /* marginal simulation core (R/sim.R:147-172): iiderrors n x nsim -> list(status, n x nsim fields) */
 SEXP _cocons_hip_sim(SEXP fitp, SEXP theta, SEXP mean, SEXP classic, SEXP iiderrors)
 {
@@ -650,6 +685,9 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_neg2loglik_reml", (DL_FUNC)&_cocons_hip_neg2loglik_reml, 3},
     {"_cocons_hip_predict", (DL_FUNC)&_cocons_hip_predict, 6},
     {"_cocons_hip_predict_taper", (DL_FUNC)&_cocons_hip_predict_taper, 9},
+    {"_cocons_hip_krige_prepare", (DL_FUNC)&_cocons_hip_krige_prepare, 5},
+    {"_cocons_hip_krige", (DL_FUNC)&_cocons_hip_krige, 3},
+    {"_cocons_hip_krige_release", (DL_FUNC)&_cocons_hip_krige_release, 1},
     {"_cocons_hip_sim", (DL_FUNC)&_cocons_hip_sim, 5},
     {"_cocons_hip_sim_cond", (DL_FUNC)&_cocons_hip_sim_cond, 8},
     {"_cocons_hip_sim_taper", (DL_FUNC)&_cocons_hip_sim_taper, 5},

@@ -97,6 +97,24 @@ cocons_fit *cocons_fit_create_taper(int n, int p, int r, const double *locs, con
                                     const double *smooth_limits, int device, int nnz, const int *colindices,
                                     const int *rowpointers, const double *taper_entries);
 
+/* Kriging from a held factor: cocoPredict (R/predict.R:136-183) at any number of new locations for one theta.
+ * cocons_krige_prepare assembles Sigma(theta), factors it once with (z[:, z_col] - X mean)' as the one right-hand side and
+ * keeps, in buffers of its own on the handle: the lower factor in packed 128 x 128 tiles (nt (nt + 1) / 2 of them, not the
+ * factorisation buffer), w = L^-1 r, the solve's operands per diagonal tile, the observation side of cov_rns_pred and
+ * the chunk buffers.  It replaces any earlier state; on a non-positive pivot it returns the failing minor and leaves no state.
+ * cocons_krige_apply then gives, for m >= 0 new locations (locs_pred m x 2, X_pred m x p, column-major),
+ *   stochastic[i] = c_i' Sigma^-1 (z - X mean),  quadform[i] = c_i' Sigma^-1 c_i      (as cocons_predict_dense)
+ * in chunks of at most `max_rows` rows (rounded down to a multiple of 64, at least 64; 0: as many as keep the chunk
+ * buffers within 1 GiB, at most 16384) -- no factorisation, and device memory that does not depend on m.  A row's
+ * outputs do not depend on the chunk size or on the other rows (bit for bit).  No other entry point touches the state;
+ * cocons_krige_release and cocons_fit_destroy free it.  cocons_krige_info: out4 = {prepared, device bytes held, rows per
+ * chunk, n}.  Refused (< 0, with a message) on taper and sharded handles, and apply without a state.                  */
+int cocons_krige_prepare(cocons_fit *fit, const double *theta, const double *mean, int z_col, int max_rows);
+int cocons_krige_apply(cocons_fit *fit, int m, const double *locs_pred, const double *X_pred,
+                       double *stochastic, double *quadform);
+int cocons_krige_release(cocons_fit *fit);
+int cocons_krige_info(cocons_fit *fit, long long *out4);
+
 /* Kriging core of the sparse branch of cocoPredict (R/predict.R:216-283) on a taper handle: replaces
  * cov_rns_taper / cov_rns_taper_pred times their tapers, inv_cov <- spam::solve(taper_two, t(pred_taper)) (:244),
  * crossprod(resid, inv_cov) (:252) and rowSums(pred_taper * t(inv_cov)) (:267).  pred_taper's slots go in as they
