@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
+#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -28,10 +29,13 @@ using namespace cocons;
 
 static thread_local std::string g_err;
 
-static int fail(int code, const char *fmt, const char *what = "")
+static int fail(int code, const char *fmt, ...)
 {
     char buf[512];
-    snprintf(buf, sizeof buf, fmt, what);
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
     g_err = buf;
     return code;
 }
@@ -143,13 +147,14 @@ struct StreamDrain {
 };
 
 // HIPCHK for the one-shot entry points: the message names the entry point, the code is -100 - hipError_t
-#define HIPCHK_AT(who, expr)                                                                     \
-    do {                                                                                         \
-        hipError_t e__ = (expr);                                                                 \
-        if (e__ != hipSuccess) return fail(-100 - (int)e__, who ": %s", hipGetErrorString(e__)); \
+#define HIPCHK_AT(who, expr)                                                                        \
+    do {                                                                                            \
+        hipError_t e__ = (expr);                                                                    \
+        if (e__ != hipSuccess) return fail(-100 - (int)e__, "%s: %s", who, hipGetErrorString(e__)); \
     } while (0)
 
-static void make_theta_vecs(const double *theta_in, int p, ThetaVecs &tv)
+// full_scale: the taper entries' FULL scale vector in two_scale_je (cocons_taper.cpp:207), the first scale included
+static void make_theta_vecs(const double *theta_in, int p, ThetaVecs &tv, bool full_scale = false)
 {
     double theta[6 * COCONS_P_MAX];
     for (int i = 0; i < 6 * p; ++i) theta[i] = canon_nan(theta_in[i]);
@@ -157,7 +162,7 @@ static void make_theta_vecs(const double *theta_in, int p, ThetaVecs &tv)
     for (int i = 0; i < p; ++i) {
         double sje = (i == 0) ? 0.0 : theta[TH_SCALE * p + i];      // cocons_full.cpp:49,64
         tv.tilt[i] = theta[TH_TILT * p + i];
-        tv.two_scale_je[i] = 2 * sje;                               // :101
+        tv.two_scale_je[i] = 2 * (full_scale ? theta[TH_SCALE * p + i] : sje);      // :101
         tv.aniso[i] = theta[TH_ANISO * p + i];
         tv.sqrt_vector[i] = 2 * sje + theta[TH_ANISO * p + i];      // :66
         tv.half_sd[i] = 0.5 * theta[TH_SD * p + i];                 // :104
@@ -191,6 +196,21 @@ static ModeSel select_mode(const double *theta, int p, const double *smooth_limi
         m.smooth_kind = SMOOTH_LOGISTIC_SQRT;
     }
     return m;
+}
+
+// loc_params arguments of n locations: X (n x p) and locs (n x 2) column-major with leading dimension n, the SoA to out
+static LocArgs loc_args(int n, int p, const double *X, const double *locs, double *out, size_t stride, const ThetaVecs &tv,
+                        int smooth_kind, const double *smooth_limits)
+{
+    LocArgs la;
+    la.n = n; la.p = p;
+    la.X = X; la.ldx = n;
+    la.locs = locs; la.ldl = n;
+    la.out = out; la.stride = stride;
+    la.smooth_kind = smooth_kind;
+    la.smooth_min = smooth_limits[0]; la.smooth_max = smooth_limits[1];
+    la.th = tv;
+    return la;
 }
 
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
@@ -965,15 +985,7 @@ static void assemble_sigma(cocons_fit *f, const double *theta, int which, int co
     ThetaVecs tv;
     make_theta_vecs(theta, f->p, tv);
     ModeSel ms = select_mode(theta, f->p, f->smooth_limits, which);
-    LocArgs la;
-    la.n = f->n; la.p = f->p;
-    la.X = f->dX; la.ldx = f->n;
-    la.locs = f->dlocs; la.ldl = f->n;
-    la.out = f->dloc; la.stride = f->npad;
-    la.smooth_kind = ms.smooth_kind;
-    la.smooth_min = f->smooth_limits[0]; la.smooth_max = f->smooth_limits[1];
-    la.th = tv;
-    launch_loc_params(la, f->stream);
+    launch_loc_params(loc_args(f->n, f->p, f->dX, f->dlocs, f->dloc, f->npad, tv, ms.smooth_kind, f->smooth_limits), f->stream);
     PairArgs pa;
     memset(&pa, 0, sizeof pa);
     pa.n = f->n; pa.m = f->n;
@@ -993,18 +1005,9 @@ static void assemble_sigma(cocons_fit *f, const double *theta, int which, int co
 static int assemble_sigma_taper(cocons_fit *f, const double *theta)
 {
     ThetaVecs tv;
-    make_theta_vecs(theta, f->p, tv);
-    for (int i = 0; i < f->p; ++i) tv.two_scale_je[i] = canon_nan(2 * theta[TH_SCALE * f->p + i]);
+    make_theta_vecs(theta, f->p, tv, true);
     ModeSel ms = select_mode(theta, f->p, f->smooth_limits, 0);
-    LocArgs la;
-    la.n = f->n; la.p = f->p;
-    la.X = f->dX; la.ldx = f->n;
-    la.locs = f->dlocs; la.ldl = f->n;
-    la.out = f->dloc; la.stride = f->npad;
-    la.smooth_kind = ms.smooth_kind;
-    la.smooth_min = f->smooth_limits[0]; la.smooth_max = f->smooth_limits[1];
-    la.th = tv;
-    launch_loc_params(la, f->stream);
+    launch_loc_params(loc_args(f->n, f->p, f->dX, f->dlocs, f->dloc, f->npad, tv, ms.smooth_kind, f->smooth_limits), f->stream);
     // zero what the factorisation will read: the tiles inside the envelope (the rows under the matrix are written in
     // full by the right-hand-side kernel), or the whole buffer when the factorisation is not band-limited
     if (f->d_thi) launch_band_zero(f->dA, f->lda, f->d_thi, f->nt, f->taper_maxband, f->stream, f->skew);
@@ -1045,6 +1048,44 @@ static void assemble_rhs(cocons_fit *f, const double *mean, bool use_trend, cons
         ra.nrows_zero = zero_rest ? f->rhs_act - f->r - nxb : 0;
         launch_rhs_rows(ra, f->stream);
     }
+}
+
+// row row0 of out: the residual z[:, z_col] - X mean over the columns [0, ncols), then nrows_zero rows cleared.  out is in
+// the handle's layout (skew; a dense handle's is 0, the layout of cocons_sim_cond_dense's own buffer too)
+static void residual_row(cocons_fit *f, const double *mean, int z_col, double *out, size_t ld, int row0, int nrows_zero,
+                         int ncols)
+{
+    RhsArgs ra;
+    memset(&ra, 0, sizeof ra);
+    ra.n = f->n; ra.p = f->p; ra.X = f->dX; ra.ldx = f->n; ra.use_trend = 1;
+    for (int i = 0; i < f->p; ++i) ra.mean[i] = canon_nan(mean[i]);
+    ra.src = f->dz + (size_t)z_col * f->n; ra.lds = f->n;
+    ra.out = out; ra.ld = ld; ra.row0 = row0; ra.nrows = 1; ra.nrows_zero = nrows_zero;
+    ra.col0 = 0; ra.ncols_out = ncols;
+    ra.skew = f->skew; ra.npad = f->npad;
+    launch_rhs_rows(ra, f->stream);
+}
+
+// no right-hand sides: clear the rows under the matrix
+static void clear_border(cocons_fit *f)
+{
+    RhsArgs ra;
+    memset(&ra, 0, sizeof ra);
+    ra.n = f->n; ra.p = f->p; ra.X = f->dX; ra.ldx = f->n; ra.src = f->dX; ra.lds = f->n;
+    ra.out = f->dA; ra.ld = f->lda; ra.row0 = f->npad; ra.nrows = 0; ra.nrows_zero = f->rhs_act;
+    ra.col0 = 0; ra.ncols_out = f->npad;
+    ra.skew = f->skew; ra.npad = f->npad;
+    launch_rhs_rows(ra, f->stream);
+}
+
+// trend X %*% mean of the simulations on the host (O(n p)), as the reference does (R/sim.R:170), in the handle's order
+static std::vector<double> host_trend(const cocons_fit *f, const double *mean)
+{
+    const int n = f->n;
+    std::vector<double> tr(n, 0.0);
+    for (int j = 0; j < f->p; ++j)
+        for (int i = 0; i < n; ++i) tr[i] += (*f->h_X)[(size_t)i + (size_t)j * n] * mean[j];
+    return tr;
 }
 
 // Bordered right-looking factorisation, outer block = 2 tiles (256 columns).
@@ -1888,75 +1929,79 @@ static int enqueue_eval_impl(cocons_fit *f, const double *theta, const double *m
     return 0;
 }
 
-static int info_status(cocons_fit *f)
+// COCONS_DEBUG_ABORT=1: say which wait gave up (0x1tt / 0x2tt engine waiting for tile tt, 0x3tt panel solve waiting for the
+// engine's tile tt, 0x5.. in-panel update, 0x600 the gate waiting for the engine to be resident, 0x900 the reductions waiting
+// for the engine's last tile: kernels.h, abort_code / abort_class)
+static void debug_abort_report(cocons_fit *f)
 {
-    // COCONS_DEBUG_ABORT=1: say which wait gave up (0x1tt / 0x2tt engine waiting for tile tt, 0x3tt panel solve
-    // waiting for the engine's tile tt, 0x5.. in-panel update, 0x600 the gate waiting for the engine to be resident,
-    // 0x900 the reductions waiting for the engine's last tile: kernels.h, abort_code / abort_class)
-    if (f->hinfo[1] != 0 && getenv("COCONS_DEBUG_ABORT")) {
-        fprintf(stderr, "cocons: hand-off time-out, code 0x%x\n", f->hinfo[1]);
-        if (f->dag_used && f->ddag && (f->hinfo[1] & 0xf00) >= 0xa00) {
-            // a wait of the DAG launch: what it waited for (dag_wait's record) and what the word holds NOW
-            unsigned rec[7] = {0, 0, 0, 0, 0, 0, 0}, now = 0, qn = 0;
-            hipMemcpyAsync(rec, f->ddag + 8, sizeof rec, hipMemcpyDeviceToHost, f->stream);
+    fprintf(stderr, "cocons: hand-off time-out, code 0x%x\n", f->hinfo[1]);
+    const unsigned cls = abort_class((unsigned)f->hinfo[1]);
+    if (!f->dag_used || !f->ddag || cls < ABORT_DAG_FIRST || cls > ABORT_DAG_LAST) return;
+    // a wait of the DAG launch: what it waited for (dag_wait's record) and what the word holds NOW
+    unsigned rec[7] = {0, 0, 0, 0, 0, 0, 0}, now = 0, qn = 0;
+    hipMemcpyAsync(rec, f->ddag + 8, sizeof rec, hipMemcpyDeviceToHost, f->stream);
+    hipStreamSynchronize(f->stream);
+    if (rec[2] < f->ddag_words) hipMemcpyAsync(&now, f->ddag + rec[2], sizeof now, hipMemcpyDeviceToHost, f->stream);
+    hipMemcpyAsync(&qn, f->ddag, sizeof qn, hipMemcpyDeviceToHost, f->stream);
+    hipStreamSynchronize(f->stream);
+    fprintf(stderr, "cocons: DAG wait: task %u (of %u, counter now %u) code 0x%x waited for word %u >= %u, saw %u, holds %u now; "
+            "%.1f ms, %u polls\n", rec[0], f->dag_ntasks, qn, rec[1], rec[2], rec[3], rec[4], now, rec[5] * 1e-5, rec[6]);
+    if (const char *dump = getenv("COCONS_DEBUG_ABORT_DUMP")) {
+        // everything an offline look needs (tools/dag_abort.py): header, record, step table, all task words, the engine's
+        // flag words, and with tracing on the stamps of every task and of the engine
+        static int ndump = 0;
+        char path[512];
+        snprintf(path, sizeof path, "%s.%d", dump, ndump++);
+        if (FILE *fp = fopen(path, "wb")) {
+            const unsigned ntr = f->dag_trace_tasks ? 1u : 0u;
+            unsigned hdr[16] = {0xDA6D0001u, (unsigned)f->nt, (unsigned)f->dag_nsteps, f->dag_ntasks, (unsigned)f->ddag_words,
+                                (unsigned)f->flags_cap, ntr, (unsigned)f->hinfo[1], qn, now, 0, 0, 0, 0, 0, 0};
+            fwrite(hdr, sizeof hdr, 1, fp);
+            fwrite(rec, sizeof rec, 1, fp);
+            std::vector<DagStepHost> sh((size_t)f->dag_nsteps);
+            hipMemcpyAsync(sh.data(), f->ddag_steps, sh.size() * sizeof(DagStepHost), hipMemcpyDeviceToHost, f->stream);
+            std::vector<unsigned> w((size_t)f->ddag_words), fl(4 * (size_t)f->flags_cap + 64);
+            hipMemcpyAsync(w.data(), f->ddag, w.size() * sizeof(unsigned), hipMemcpyDeviceToHost, f->stream);
+            hipMemcpyAsync(fl.data(), f->dflags, fl.size() * sizeof(unsigned), hipMemcpyDeviceToHost, f->stream);
             hipStreamSynchronize(f->stream);
-            if (rec[2] < f->ddag_words) hipMemcpyAsync(&now, f->ddag + rec[2], sizeof now, hipMemcpyDeviceToHost, f->stream);
-            hipMemcpyAsync(&qn, f->ddag, sizeof qn, hipMemcpyDeviceToHost, f->stream);
-            hipStreamSynchronize(f->stream);
-            fprintf(stderr, "cocons: DAG wait: task %u (of %u, counter now %u) code 0x%x waited for word %u >= %u, saw %u, holds %u now; "
-                    "%.1f ms, %u polls\n", rec[0], f->dag_ntasks, qn, rec[1], rec[2], rec[3], rec[4], now, rec[5] * 1e-5, rec[6]);
-            if (const char *dump = getenv("COCONS_DEBUG_ABORT_DUMP")) {
-                // everything an offline look needs (tools/dag_abort.py): header, record, step table, all task words, the engine's
-                // flag words, and with tracing on the stamps of every task and of the engine
-                static int ndump = 0;
-                char path[512];
-                snprintf(path, sizeof path, "%s.%d", dump, ndump++);
-                if (FILE *fp = fopen(path, "wb")) {
-                    const unsigned ntr = f->dag_trace_tasks ? 1u : 0u;
-                    unsigned hdr[16] = {0xDA6D0001u, (unsigned)f->nt, (unsigned)f->dag_nsteps, f->dag_ntasks, (unsigned)f->ddag_words,
-                                        (unsigned)f->flags_cap, ntr, (unsigned)f->hinfo[1], qn, now, 0, 0, 0, 0, 0, 0};
-                    fwrite(hdr, sizeof hdr, 1, fp);
-                    fwrite(rec, sizeof rec, 1, fp);
-                    std::vector<DagStepHost> sh((size_t)f->dag_nsteps);
-                    hipMemcpyAsync(sh.data(), f->ddag_steps, sh.size() * sizeof(DagStepHost), hipMemcpyDeviceToHost, f->stream);
-                    std::vector<unsigned> w((size_t)f->ddag_words), fl(4 * (size_t)f->flags_cap + 64);
-                    hipMemcpyAsync(w.data(), f->ddag, w.size() * sizeof(unsigned), hipMemcpyDeviceToHost, f->stream);
-                    hipMemcpyAsync(fl.data(), f->dflags, fl.size() * sizeof(unsigned), hipMemcpyDeviceToHost, f->stream);
-                    hipStreamSynchronize(f->stream);
-                    fwrite(sh.data(), sizeof(DagStepHost), sh.size(), fp);
-                    fwrite(w.data(), sizeof(unsigned), w.size(), fp);
-                    fwrite(fl.data(), sizeof(unsigned), fl.size(), fp);
-                    if (ntr) {
-                        std::vector<unsigned long long> st((size_t)f->dag_ntasks * 5 + 8 * (size_t)(f->nt + 2));
-                        hipMemcpyAsync(st.data(), f->ddag_trace, st.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream);
-                        hipStreamSynchronize(f->stream);
-                        fwrite(st.data(), sizeof(unsigned long long), st.size(), fp);
-                    }
-                    fclose(fp);
-                    fprintf(stderr, "cocons: state written to %s\n", path);
-                }
-            }
-            if (f->dag_trace_tasks && !getenv("COCONS_DEBUG_ABORT_DUMP")) {
-                // which tasks were drawn and never finished (stamps: drawn, inputs complete, product done, stored)
-                std::vector<unsigned long long> st((size_t)f->dag_ntasks * 4);
+            fwrite(sh.data(), sizeof(DagStepHost), sh.size(), fp);
+            fwrite(w.data(), sizeof(unsigned), w.size(), fp);
+            fwrite(fl.data(), sizeof(unsigned), fl.size(), fp);
+            if (ntr) {
+                std::vector<unsigned long long> st((size_t)f->dag_ntasks * 5 + 8 * (size_t)(f->nt + 2));
                 hipMemcpyAsync(st.data(), f->ddag_trace, st.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream);
                 hipStreamSynchronize(f->stream);
-                unsigned long long tmin = ~0ull;
-                for (size_t i = 0; i < st.size(); i += 4) if (st[i] && st[i] < tmin) tmin = st[i];
-                int shown = 0;
-                for (unsigned L = 0; L < f->dag_ntasks && shown < 40; ++L) {
-                    const unsigned long long *q = &st[(size_t)L * 4];
-                    if (q[0] && !q[3]) {
-                        fprintf(stderr, "   unfinished task %u: drawn %.1f us, inputs %s, product %s\n", L, (q[0] - tmin) * 0.01,
-                                q[1] ? "complete" : "WAITING", q[2] ? "done" : "-");
-                        ++shown;
-                    }
-                }
+                fwrite(st.data(), sizeof(unsigned long long), st.size(), fp);
+            }
+            fclose(fp);
+            fprintf(stderr, "cocons: state written to %s\n", path);
+        }
+    }
+    if (f->dag_trace_tasks && !getenv("COCONS_DEBUG_ABORT_DUMP")) {
+        // which tasks were drawn and never finished (stamps: drawn, inputs complete, product done, stored)
+        std::vector<unsigned long long> st((size_t)f->dag_ntasks * 4);
+        hipMemcpyAsync(st.data(), f->ddag_trace, st.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream);
+        hipStreamSynchronize(f->stream);
+        unsigned long long tmin = ~0ull;
+        for (size_t i = 0; i < st.size(); i += 4) if (st[i] && st[i] < tmin) tmin = st[i];
+        int shown = 0;
+        for (unsigned L = 0; L < f->dag_ntasks && shown < 40; ++L) {
+            const unsigned long long *q = &st[(size_t)L * 4];
+            if (q[0] && !q[3]) {
+                fprintf(stderr, "   unfinished task %u: drawn %.1f us, inputs %s, product %s\n", L, (q[0] - tmin) * 0.01,
+                        q[1] ? "complete" : "WAITING", q[2] ? "done" : "-");
+                ++shown;
             }
         }
     }
-    if (f->hinfo[1] != 0)
+}
+
+static int info_status(cocons_fit *f)
+{
+    if (f->hinfo[1] != 0) {
+        if (getenv("COCONS_DEBUG_ABORT")) debug_abort_report(f);
         return fail(ENGINE_ABORT, "hand-off between the diagonal-tile engine and the main stream timed out");
+    }
     // the operation ran to its end on the schedule factorize chose: book-keeping of the engine's back-off
     f->engine_active_last = f->engine_used;
     if (f->engine_used) f->engine_fails = 0;
@@ -1990,6 +2035,34 @@ static bool engine_retry(cocons_fit *f, int st)
     f->engine_used = false;
     if (f->stream2) hipStreamSynchronize(f->stream2);
     return true;
+}
+
+// One evaluation of the objective, repeated after a hand-off time-out.  enqueue_eval brings the info words home together
+// with the outputs (one copy); 0, a failing minor or an error.
+static int run_eval(cocons_fit *f, const double *theta, const double *mean, bool use_trend, const double *xb, int nxb)
+{
+    for (;;) {
+        if (int rc = enqueue_eval(f, theta, mean, use_trend, xb, nxb, nullptr, false)) return rc;
+        HIPCHK(hipStreamSynchronize(f->stream));
+        const int st = info_status(f);
+        if (!engine_retry(f, st)) return st;
+    }
+}
+
+// One operation of a one-shot entry that factors on the handle: enqueue() puts everything of it but the info words on the
+// handle's stream (assembly, factorisation, the entry's own kernels and result copies; 0 or an error); it is run again after a
+// hand-off time-out.  0, a failing minor or an error.
+template <class F> static int run_op(cocons_fit *f, const char *who, F &&enqueue)
+{
+    for (;;) {
+        if (int rc = reset_info(f)) return rc;
+        if (int rc = enqueue()) return rc;
+        HIPCHK_AT(who, hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, f->stream));
+        HIPCHK_AT(who, hipGetLastError());
+        HIPCHK_AT(who, hipStreamSynchronize(f->stream));
+        const int st = info_status(f);
+        if (!engine_retry(f, st)) return st;
+    }
 }
 
 // out[0] = 1 if the last completed operation of the handle ran on the engine schedule, out[1] = hand-off time-outs
@@ -2027,14 +2100,7 @@ extern "C" int cocons_neg2loglik_dense(cocons_fit *f, const double *theta, const
     if (f->r < 1) return fail(-1, "cocons_neg2loglik_dense: fit has no z");
     if (f->coll_kind < 0) return fail(-7, "cocons_neg2loglik_dense: the communicator of this fit was aborted after an error");
     if (f->coll_kind) return sharded_eval(f, theta, mean, sum_logliks, parts);    // (also with one rank: the caller asked for it)
-    for (;;) {
-        if (int rc = enqueue_eval(f, theta, mean, true, nullptr, 0, nullptr, false)) return rc;
-        HIPCHK(hipStreamSynchronize(f->stream));
-        int st = info_status(f);
-        if (engine_retry(f, st)) continue;
-        if (st) return st;
-        break;
-    }
+    if (int st = run_eval(f, theta, mean, true, nullptr, 0)) return st;
     dense_collect(f, sum_logliks, parts);
     return 0;
 }
@@ -2304,14 +2370,7 @@ extern "C" int cocons_neg2loglik_profile(cocons_fit *f, const double *theta, dou
     if (int rc = no_taper(f, "cocons_neg2loglik_profile")) return rc;
     if (!theta || !sum_logliks) return fail(-1, "cocons_neg2loglik_profile: null argument");
     if (f->r < 1 || f->q < 1) return fail(-1, "cocons_neg2loglik_profile: fit needs z and x_betas");
-    for (;;) {
-        if (int rc = enqueue_eval(f, theta, nullptr, false, f->dxb, f->q, nullptr, false)) return rc;
-        HIPCHK(hipStreamSynchronize(f->stream));
-        int st = info_status(f);
-        if (engine_retry(f, st)) continue;
-        if (st) return st;
-        break;
-    }
+    if (int st = run_eval(f, theta, nullptr, false, f->dxb, f->q)) return st;
     return profile_tail(f, f->q, (double)f->n_user, false, sum_logliks, parts);   // R/neg2loglikelihood.R:155-160
 }
 
@@ -2321,14 +2380,7 @@ extern "C" int cocons_neg2loglik_reml(cocons_fit *f, const double *theta, int ra
     if (int rc = no_taper(f, "cocons_neg2loglik_reml")) return rc;
     if (!theta || !sum_logliks) return fail(-1, "cocons_neg2loglik_reml: null argument");
     if (f->r < 1) return fail(-1, "cocons_neg2loglik_reml: fit has no z");
-    for (;;) {
-        if (int rc = enqueue_eval(f, theta, nullptr, false, f->dX, f->p, nullptr, false)) return rc;
-        HIPCHK(hipStreamSynchronize(f->stream));
-        int st = info_status(f);
-        if (engine_retry(f, st)) continue;
-        if (st) return st;
-        break;
-    }
+    if (int st = run_eval(f, theta, nullptr, false, f->dX, f->p)) return st;
     return profile_tail(f, f->p, (double)(f->n_user - rank), true, sum_logliks, parts);   // :283-287
 }
 
@@ -2421,11 +2473,7 @@ static int cov_common(int which, int n, int m, int p, const double *theta, const
     HIPCHK_AT("cov_rns*", dout.alloc(rows * (size_t)n));
     HIPCHK_AT("cov_rns*", upload_canon(dX, X, (size_t)n * p, s));
     HIPCHK_AT("cov_rns*", upload_canon(dl, locs, (size_t)n * 2, s));
-    LocArgs la;
-    la.n = n; la.p = p; la.X = dX; la.ldx = n; la.locs = dl; la.ldl = n;
-    la.out = dloc; la.stride = n; la.smooth_kind = ms.smooth_kind;
-    la.smooth_min = sl[0]; la.smooth_max = sl[1]; la.th = tv;
-    launch_loc_params(la, s);
+    launch_loc_params(loc_args(n, p, dX, dl, dloc, n, tv, ms.smooth_kind, sl), s);
     PairArgs pa;
     memset(&pa, 0, sizeof pa);
     pa.n = n; pa.cols = dloc; pa.stride = n; pa.out = dout; pa.gr = ms.gr; pa.nu_fixed = ms.nu_fixed;
@@ -2435,9 +2483,7 @@ static int cov_common(int which, int n, int m, int p, const double *theta, const
         HIPCHK_AT("cov_rns*", dlocp.alloc((size_t)LOCP_FIELDS * m));
         HIPCHK_AT("cov_rns*", upload_canon(dXp, X_pred, (size_t)m * p, s));
         HIPCHK_AT("cov_rns*", upload_canon(dlp, locs_pred, (size_t)m * 2, s));
-        LocArgs lp = la;
-        lp.n = m; lp.X = dXp; lp.ldx = m; lp.locs = dlp; lp.ldl = m; lp.out = dlocp; lp.stride = m;
-        launch_loc_params(lp, s);
+        launch_loc_params(loc_args(m, p, dXp, dlp, dlocp, m, tv, ms.smooth_kind, sl), s);
         pa.m = m; pa.rows = dlocp; pa.stride_rows = m; pa.ld = m; pa.nrows_out = m; pa.ncols_out = n;
         launch_pair_rect(ms.mode, pa, s);
     } else {
@@ -2483,8 +2529,7 @@ static int taper_common(bool pred, int n, int m, int p, const double *theta, con
     for (int w = 0; w < nnz; ++w)
         if (colindices[w] < 1 || colindices[w] > n) return fail(-1, "cov_rns_taper*: column index out of range");
     ThetaVecs tv;
-    make_theta_vecs(theta, p, tv);
-    for (int i = 0; i < p; ++i) tv.two_scale_je[i] = 2 * theta[TH_SCALE * p + i];   // FULL scale vector (cocons_taper.cpp:207)
+    make_theta_vecs(theta, p, tv, true);                                  // FULL scale vector (cocons_taper.cpp:207)
     // smoothness dispatch of cov_rns_taper (:183-201); the prediction variant always takes the Bessel branch
     ModeSel ms = select_mode(theta, p, smooth_limits, pred ? 2 : 0);
     const size_t nz = nnz > 0 ? (size_t)nnz : 1;
@@ -2502,20 +2547,14 @@ static int taper_common(bool pred, int n, int m, int p, const double *theta, con
     HIPCHK_AT("cov_rns_taper*", upload_canon(dl, locs, (size_t)n * 2, s));
     HIPCHK_AT("cov_rns_taper*", hipMemcpyAsync(dci, colindices, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK_AT("cov_rns_taper*", hipMemcpyAsync(drp, rowpointers, (size_t)(nrows + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-    LocArgs la;
-    la.n = n; la.p = p; la.X = dX; la.ldx = n; la.locs = dl; la.ldl = n;
-    la.out = dloc; la.stride = n; la.smooth_kind = ms.smooth_kind;
-    la.smooth_min = smooth_limits[0]; la.smooth_max = smooth_limits[1]; la.th = tv;
-    launch_loc_params(la, s);
+    launch_loc_params(loc_args(n, p, dX, dl, dloc, n, tv, ms.smooth_kind, smooth_limits), s);
     if (pred) {
         HIPCHK_AT("cov_rns_taper*", dXp.alloc((size_t)m * p));
         HIPCHK_AT("cov_rns_taper*", dlp.alloc((size_t)m * 2));
         HIPCHK_AT("cov_rns_taper*", dlocp.alloc((size_t)LOCP_FIELDS * m));
         HIPCHK_AT("cov_rns_taper*", upload_canon(dXp, X_pred, (size_t)m * p, s));
         HIPCHK_AT("cov_rns_taper*", upload_canon(dlp, locs_pred, (size_t)m * 2, s));
-        LocArgs lp = la;
-        lp.n = m; lp.X = dXp; lp.ldx = m; lp.locs = dlp; lp.ldl = m; lp.out = dlocp; lp.stride = m;
-        launch_loc_params(lp, s);
+        launch_loc_params(loc_args(m, p, dXp, dlp, dlocp, m, tv, ms.smooth_kind, smooth_limits), s);
         launch_taper(MODE_GEOM, true, m, nnz, dci, drp, dlocp, m, dloc, n, 0.0, dout, s);
     } else {
         launch_taper(ms.mode, false, n, nnz, dci, drp, dloc, n, dloc, n, ms.nu_fixed, dout, s);
@@ -2569,11 +2608,7 @@ extern "C" int cocons_cov_rows(cocons_fit *f, const double *theta, int classic, 
     HIPCHK_AT("cocons_cov_rows", upload_canon(dX, f->h_X->data(), (size_t)n * p, s));
     HIPCHK_AT("cocons_cov_rows", upload_canon(dl, f->h_locs->data(), (size_t)n * 2, s));
     HIPCHK_AT("cocons_cov_rows", hipMemcpyAsync(didx, idx, (size_t)nidx * sizeof(int), hipMemcpyHostToDevice, s));
-    LocArgs la;
-    la.n = n; la.p = p; la.X = dX; la.ldx = n; la.locs = dl; la.ldl = n;
-    la.out = dloc; la.stride = n; la.smooth_kind = ms.smooth_kind;
-    la.smooth_min = f->smooth_limits[0]; la.smooth_max = f->smooth_limits[1]; la.th = tv;
-    launch_loc_params(la, s);
+    launch_loc_params(loc_args(n, p, dX, dl, dloc, n, tv, ms.smooth_kind, f->smooth_limits), s);
     launch_cov_rows(ms.mode, n, nidx, didx, dloc, n, ms.gr, ms.nu_fixed, cor, dout, s);
     HIPCHK_AT("cocons_cov_rows", hipGetLastError());
     HIPCHK_AT("cocons_cov_rows", hipMemcpyAsync(out, dout, (size_t)nidx * n * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -2614,39 +2649,26 @@ extern "C" int cocons_predict_dense(cocons_fit *f, const double *theta, const do
     hipStream_t s = f->stream;
     HIPCHK_AT("cocons_predict_dense", upload_canon(f->dXp, X_pred, (size_t)m * p, s));
     HIPCHK_AT("cocons_predict_dense", upload_canon(f->dlocsp, locs_pred, (size_t)m * 2, s));
-    for (;;) {
-        if (int rc = reset_info(f)) return rc;
+    ThetaVecs tv;
+    make_theta_vecs(theta, p, tv);
+    const ModeSel ms = select_mode(theta, p, f->smooth_limits, 2);
+    const ModeSel ms0 = select_mode(theta, p, f->smooth_limits, 0);
+    return run_op(f, "cocons_predict_dense", [&]() -> int {
         assemble_sigma(f, theta, 0, 0, f->npad);
-        // row npad: residual of realization z_col; rows npad+1 .. npad+m: cross-covariance
-        RhsArgs ra;
-        memset(&ra, 0, sizeof ra);
-        ra.n = n; ra.p = p; ra.X = f->dX; ra.ldx = n; ra.use_trend = 1;
-        for (int i = 0; i < p; ++i) ra.mean[i] = canon_nan(mean[i]);
-        ra.src = f->dz + (size_t)z_col * n; ra.lds = n;
-        ra.out = f->dA; ra.ld = f->lda; ra.row0 = f->npad; ra.nrows = 1;
-        ra.nrows_zero = f->rhs_act - 1;      // also clears padding rows and columns >= n
-        ra.col0 = 0; ra.ncols_out = f->npad;
-        launch_rhs_rows(ra, s);
-        ThetaVecs tv;
-        make_theta_vecs(theta, p, tv);
-        ModeSel ms = select_mode(theta, p, f->smooth_limits, 2);
-        LocArgs lp;
-        lp.n = m; lp.p = p; lp.X = f->dXp; lp.ldx = m; lp.locs = f->dlocsp; lp.ldl = m;
-        lp.out = f->dlocp; lp.stride = m; lp.smooth_kind = ms.smooth_kind;
-        lp.smooth_min = f->smooth_limits[0]; lp.smooth_max = f->smooth_limits[1]; lp.th = tv;
-        launch_loc_params(lp, s);
-        // the observation-side SoA must use the pred-branch smoothness (always logistic+sqrt, :381)
-        LocArgs lo = lp;
-        lo.n = n; lo.X = f->dX; lo.ldx = n; lo.locs = f->dlocs; lo.ldl = n; lo.out = f->dloc; lo.stride = f->npad;
+        // row npad: residual of realization z_col (also clears padding rows and columns >= n); rows npad+1 .. npad+m:
+        // cross-covariance
+        residual_row(f, mean, z_col, f->dA, f->lda, f->npad, f->rhs_act - 1, f->npad);
+        launch_loc_params(loc_args(m, p, f->dXp, f->dlocsp, f->dlocp, m, tv, ms.smooth_kind, f->smooth_limits), s);
         PairArgs pa;
         memset(&pa, 0, sizeof pa);
         pa.n = n; pa.m = m; pa.rows = f->dlocp; pa.stride_rows = m; pa.cols = f->dloc; pa.stride = f->npad;
         pa.out = f->dA + f->npad + 1; pa.ld = f->lda; pa.nrows_out = m; pa.ncols_out = n;
         pa.gr = ms.gr; pa.nu_fixed = 0.0;
         // Sigma was assembled from dloc above (stream order); rebuild dloc only if cov_rns used a
-        // different smoothness vector (fixed-nu branch) than cov_rns_pred does.
-        ModeSel ms0 = select_mode(theta, p, f->smooth_limits, 0);
-        if (ms0.smooth_kind != ms.smooth_kind) launch_loc_params(lo, s);
+        // different smoothness vector (fixed-nu branch) than cov_rns_pred does: the observation-side SoA must use the
+        // pred-branch smoothness (always logistic+sqrt, :381)
+        if (ms0.smooth_kind != ms.smooth_kind)
+            launch_loc_params(loc_args(n, p, f->dX, f->dlocs, f->dloc, f->npad, tv, ms.smooth_kind, f->smooth_limits), s);
         launch_pair_rect(MODE_GEOM, pa, s);
         // (the dependency-driven schedule may take the head of this factorisation too -- round 6: the row reductions below read the
         // factor from both buffers like the objectives' do; with m rows under the matrix every step is a long one)
@@ -2655,15 +2677,10 @@ extern "C" int cocons_predict_dense(cocons_fit *f, const double *theta, const do
         if (int rc = factorize(f, pv, nullptr)) return rc;
         launch_row_reduce(f->dA, f->lda, n, f->npad, f->npad + 1, m, f->dstoch, f->dquad, f->dred, s, 0, 0,
                           f->dag_used ? f->dP : nullptr, f->dag_used ? 2 * TILE * f->dag_nsteps : 0);
-        HIPCHK(hipMemcpyAsync(stochastic, f->dstoch, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(quadform, f->dquad, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(s));
-        int st = info_status(f);
-        if (engine_retry(f, st)) continue;
-        return st;
-    }
+        HIPCHK_AT("cocons_predict_dense", hipMemcpyAsync(stochastic, f->dstoch, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT("cocons_predict_dense", hipMemcpyAsync(quadform, f->dquad, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+        return 0;
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -2724,40 +2741,22 @@ extern "C" int cocons_krige_prepare(cocons_fit *f, const double *theta, const do
     HIPCHK_AT("cocons_krige_prepare", hipMemsetAsync(K->C, 0, R * npad * sizeof(double), s));
     const double *th = K->theta.data();
     if (int rc = fit_alloc_matrix(f, 1)) return rc;
-    for (;;) {
-        if (int rc = reset_info(f)) return rc;
+    const int st = run_op(f, "cocons_krige_prepare", [&]() -> int {
         f->nrhs_cur = 1;
         assemble_sigma(f, th, 0, 0, npad);
         // row npad: residual of realization z_col (the rows under it and the columns >= n cleared)
-        RhsArgs ra;
-        memset(&ra, 0, sizeof ra);
-        ra.n = n; ra.p = p; ra.X = f->dX; ra.ldx = n; ra.use_trend = 1;
-        for (int i = 0; i < p; ++i) ra.mean[i] = canon_nan(mean[i]);
-        ra.src = f->dz + (size_t)z_col * n; ra.lds = n;
-        ra.out = f->dA; ra.ld = f->lda; ra.row0 = npad; ra.nrows = 1;
-        ra.nrows_zero = f->rhs_act - 1;
-        ra.col0 = 0; ra.ncols_out = npad;
-        launch_rhs_rows(ra, s);
+        residual_row(f, mean, z_col, f->dA, f->lda, npad, f->rhs_act - 1, npad);
         // the plain schedules (dag_ok = false): the factor lies whole in dA, with L^-1 r in row npad
         if (int rc = factorize(f, main_view(f), nullptr)) return rc;
         launch_krige_pack(f->dA, f->lda, nt, npad, f->pad0, n, K->L, K->Q, K->w, s);
-        HIPCHK_AT("cocons_krige_prepare", hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK_AT("cocons_krige_prepare", hipGetLastError());
-        HIPCHK_AT("cocons_krige_prepare", hipStreamSynchronize(s));
-        int st = info_status(f);
-        if (engine_retry(f, st)) continue;
-        if (st) return st;              // failing minor: no state (K's buffers are freed on the way out)
-        break;
-    }
+        return 0;
+    });
+    if (st) return st;                  // failing minor: no state (K's buffers are freed on the way out)
     // observation-side SoA in the smoothness of cov_rns_pred (always logistic + sqrt, see cocons_predict_dense)
     ThetaVecs tv;
     make_theta_vecs(th, p, tv);
     const ModeSel ms = select_mode(th, p, f->smooth_limits, 2);
-    LocArgs lo;
-    lo.n = n; lo.p = p; lo.X = f->dX; lo.ldx = n; lo.locs = f->dlocs; lo.ldl = n;
-    lo.out = K->loc; lo.stride = npad; lo.smooth_kind = ms.smooth_kind;
-    lo.smooth_min = f->smooth_limits[0]; lo.smooth_max = f->smooth_limits[1]; lo.th = tv;
-    launch_loc_params(lo, s);
+    launch_loc_params(loc_args(n, p, f->dX, f->dlocs, K->loc, npad, tv, ms.smooth_kind, f->smooth_limits), s);
     HIPCHK_AT("cocons_krige_prepare", hipGetLastError());
     HIPCHK_AT("cocons_krige_prepare", hipStreamSynchronize(s));
     f->krige = K.release();
@@ -2789,11 +2788,7 @@ extern "C" int cocons_krige_apply(cocons_fit *f, int m, const double *locs_pred,
         for (int j = 0; j < 2; ++j) memcpy(&hl[(size_t)j * mc], locs_pred + b + (size_t)j * m, (size_t)mc * sizeof(double));
         HIPCHK_AT("cocons_krige_apply", upload_canon(K->Xp, hX.data(), (size_t)mc * p, s));
         HIPCHK_AT("cocons_krige_apply", upload_canon(K->lp, hl.data(), (size_t)mc * 2, s));
-        LocArgs lp;
-        lp.n = mc; lp.p = p; lp.X = K->Xp; lp.ldx = mc; lp.locs = K->lp; lp.ldl = mc;
-        lp.out = K->locp; lp.stride = rows; lp.smooth_kind = ms.smooth_kind;
-        lp.smooth_min = f->smooth_limits[0]; lp.smooth_max = f->smooth_limits[1]; lp.th = tv;
-        launch_loc_params(lp, s);
+        launch_loc_params(loc_args(mc, p, K->Xp, K->lp, K->locp, rows, tv, ms.smooth_kind, f->smooth_limits), s);
         // cross-covariance of the chunk with the caller's observations only: columns [pad0, n) in the handle's order
         PairArgs pa;
         memset(&pa, 0, sizeof pa);
@@ -2871,45 +2866,24 @@ extern "C" int cocons_predict_taper(cocons_fit *f, const double *theta, const do
         HIPCHK_AT("cocons_predict_taper", hipMemcpy(dci, mapped.data(), (size_t)nnz_pred * sizeof(int), hipMemcpyHostToDevice));
         HIPCHK_AT("cocons_predict_taper", upload_canon(dtv, taper_entries_pred, (size_t)nnz_pred, s));
     }
-    for (;;) {
-        if (int rc = reset_info(f)) return rc;
+    // parameters as cocons_cov_rns_taper_pred prepares them: FULL scale vector, prediction-branch smoothness
+    ThetaVecs tv;
+    make_theta_vecs(theta, p, tv, true);
+    const ModeSel ms = select_mode(theta, p, f->smooth_limits, 2);
+    return run_op(f, "cocons_predict_taper", [&]() -> int {
         if (int rc = assemble_sigma_taper(f, theta)) return rc;      // zeroes the whole buffer, border rows included
-        RhsArgs ra;
-        memset(&ra, 0, sizeof ra);
-        ra.n = n; ra.p = p; ra.X = f->dX; ra.ldx = n; ra.use_trend = 1;
-        for (int i = 0; i < p; ++i) ra.mean[i] = canon_nan(mean[i]);
-        ra.src = f->dz + (size_t)z_col * n; ra.lds = n;
-        ra.out = f->dA; ra.ld = f->lda; ra.row0 = f->npad; ra.nrows = 1;
-        ra.skew = f->skew; ra.npad = f->npad;
-        ra.nrows_zero = f->rhs_act - 1;
-        ra.col0 = 0; ra.ncols_out = f->npad;
-        launch_rhs_rows(ra, s);
-        // parameters as cocons_cov_rns_taper_pred prepares them: FULL scale vector, prediction-branch smoothness
-        ThetaVecs tv;
-        make_theta_vecs(theta, p, tv);
-        for (int i = 0; i < p; ++i) tv.two_scale_je[i] = 2 * theta[TH_SCALE * p + i];
-        ModeSel ms = select_mode(theta, p, f->smooth_limits, 2);
-        LocArgs lp;
-        lp.n = m; lp.p = p; lp.X = f->dXp; lp.ldx = m; lp.locs = f->dlocsp; lp.ldl = m;
-        lp.out = f->dlocp; lp.stride = m; lp.smooth_kind = ms.smooth_kind;
-        lp.smooth_min = f->smooth_limits[0]; lp.smooth_max = f->smooth_limits[1]; lp.th = tv;
-        launch_loc_params(lp, s);
-        LocArgs lo = lp;
-        lo.n = n; lo.X = f->dX; lo.ldx = n; lo.locs = f->dlocs; lo.ldl = n; lo.out = f->dloc; lo.stride = f->npad;
-        launch_loc_params(lo, s);                                   // (after the entries of S were computed: stream order)
+        residual_row(f, mean, z_col, f->dA, f->lda, f->npad, f->rhs_act - 1, f->npad);
+        launch_loc_params(loc_args(m, p, f->dXp, f->dlocsp, f->dlocp, m, tv, ms.smooth_kind, f->smooth_limits), s);
+        // (the observation side after the entries of S were computed from it: stream order)
+        launch_loc_params(loc_args(n, p, f->dX, f->dlocs, f->dloc, f->npad, tv, ms.smooth_kind, f->smooth_limits), s);
         launch_taper(MODE_GEOM, true, m, nnz_pred, dci, drp, f->dlocp, m, f->dloc, f->npad, 0.0, nullptr, s,
                      dtv, f->dA, f->lda, f->npad + 1, f->skew, f->npad);
         if (int rc = factorize(f, main_view(f), nullptr)) return rc;
         launch_row_reduce(f->dA, f->lda, n, f->npad, f->npad + 1, m, f->dstoch, f->dquad, f->dred, s, f->skew, f->npad);
         HIPCHK_AT("cocons_predict_taper", hipMemcpyAsync(stochastic, f->dstoch, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
         HIPCHK_AT("cocons_predict_taper", hipMemcpyAsync(quadform, f->dquad, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK_AT("cocons_predict_taper", hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK_AT("cocons_predict_taper", hipGetLastError());
-        HIPCHK_AT("cocons_predict_taper", hipStreamSynchronize(s));
-        int st = info_status(f);
-        if (engine_retry(f, st)) continue;
-        return st;
-    }
+        return 0;
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -2930,12 +2904,9 @@ extern "C" int cocons_fit_taper_order(cocons_fit *f, int *pivot_out)
 static int sim_taper_run(cocons_fit *f, const double *theta, const double *mean, int nsim, const double *iiderrors,
                          const std::vector<int> &pos, double *out)
 {
-    const int n = f->n, p = f->p;
+    const int n = f->n;
     const size_t ne = (size_t)n * nsim;
-    // trend = X %*% mean on the host (O(n p)), in the handle's order (h_X is stored in it), as cocons_sim_dense does
-    std::vector<double> tr(n, 0.0);
-    for (int j = 0; j < p; ++j)
-        for (int i = 0; i < n; ++i) tr[i] += (*f->h_X)[(size_t)i + (size_t)j * n] * mean[j];
+    const std::vector<double> tr = host_trend(f, mean);
     DevBuf<double> dE, dY, dO, dtr;
     DevBuf<int> dpos;
     StreamDrain s{f->stream, false};
@@ -2947,21 +2918,12 @@ static int sim_taper_run(cocons_fit *f, const double *theta, const double *mean,
     HIPCHK_AT("cocons_sim_taper", upload_canon(dE, iiderrors, ne, s));
     HIPCHK_AT("cocons_sim_taper", upload_canon(dtr, tr.data(), (size_t)n, s));
     HIPCHK_AT("cocons_sim_taper", hipMemcpyAsync(dpos, pos.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
-    for (;;) {
-        if (int rc = fit_alloc_matrix(f, 1)) return rc;
-        if (int rc = reset_info(f)) return rc;
+    if (int rc = fit_alloc_matrix(f, 1)) return rc;
+    const int st = run_op(f, "cocons_sim_taper", [&]() -> int {
         f->nrhs_cur = 0;
         HIPCHK_AT("cocons_sim_taper", hipEventRecord(f->ev[4], s));
         if (int rc = assemble_sigma_taper(f, theta)) return rc;
-        {   // no right-hand sides: clear the rows under the matrix
-            RhsArgs ra;
-            memset(&ra, 0, sizeof ra);
-            ra.n = n; ra.p = p; ra.X = f->dX; ra.ldx = n; ra.src = f->dX; ra.lds = n;
-            ra.out = f->dA; ra.ld = f->lda; ra.row0 = f->npad; ra.nrows = 0; ra.nrows_zero = f->rhs_act;
-            ra.col0 = 0; ra.ncols_out = f->npad;
-            ra.skew = f->skew; ra.npad = f->npad;
-            launch_rhs_rows(ra, s);
-        }
+        clear_border(f);
         if (int rc = factorize(f, main_view(f), nullptr)) return rc;
         HIPCHK_AT("cocons_sim_taper", hipEventRecord(f->ev[5], s));
         launch_band_trmm(f->dA, f->lda, f->skew, f->npad, f->d_thi, f->nt, n, dE, n, nsim, dtr, dY, n, s);
@@ -2969,15 +2931,11 @@ static int sim_taper_run(cocons_fit *f, const double *theta, const double *mean,
         launch_gather_rows(dY, n, dpos, n, nsim, dO, n, s);
         HIPCHK_AT("cocons_sim_taper", hipEventRecord(f->ev[7], s));
         HIPCHK_AT("cocons_sim_taper", hipMemcpyAsync(out, dO, ne * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK_AT("cocons_sim_taper", hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK_AT("cocons_sim_taper", hipGetLastError());
-        HIPCHK_AT("cocons_sim_taper", hipStreamSynchronize(s));
-        int rc = info_status(f);
-        if (engine_retry(f, rc)) continue;
-        if (rc == 0)
-            for (int q = 0; q < 3; ++q) HIPCHK_AT("cocons_sim_taper", hipEventElapsedTime(&f->sim_ms[q], f->ev[4 + q], f->ev[5 + q]));
-        return rc;
-    }
+        return 0;
+    });
+    if (st == 0)
+        for (int q = 0; q < 3; ++q) HIPCHK_AT("cocons_sim_taper", hipEventElapsedTime(&f->sim_ms[q], f->ev[4 + q], f->ev[5 + q]));
+    return st;
 }
 
 extern "C" int cocons_sim_taper(cocons_fit *f, const double *theta, const double *mean, int nsim, const double *iiderrors,
@@ -3067,12 +3025,9 @@ extern "C" int cocons_sim_dense(cocons_fit *f, const double *theta, const double
         }
         return cocons_sim_dense(f->unsorted, theta, mean, classic, nsim, iiderrors, out);
     }
-    const int n = f->n, p = f->p;
+    const int n = f->n;
     if (int rc = fit_alloc_matrix(f, 1)) return rc;
-    // trend = X %*% mean on the host (O(n p)), as the reference does (:170)
-    std::vector<double> tr(n, 0.0);
-    for (int j = 0; j < p; ++j)
-        for (int i = 0; i < n; ++i) tr[i] += (*f->h_X)[(size_t)i + (size_t)j * n] * mean[j];
+    const std::vector<double> tr = host_trend(f, mean);
     DevBuf<double> dE, dY, dtr;
     StreamDrain s{f->stream, false};
     HIPCHK_AT("cocons_sim_dense", dE.alloc((size_t)n * nsim));
@@ -3080,28 +3035,15 @@ extern "C" int cocons_sim_dense(cocons_fit *f, const double *theta, const double
     HIPCHK_AT("cocons_sim_dense", dtr.alloc((size_t)n));
     HIPCHK_AT("cocons_sim_dense", upload_canon(dE, iiderrors, (size_t)n * nsim, s));
     HIPCHK_AT("cocons_sim_dense", upload_canon(dtr, tr.data(), (size_t)n, s));
-    for (;;) {
-        if (int rc = reset_info(f)) return rc;
+    return run_op(f, "cocons_sim_dense", [&]() -> int {
         f->nrhs_cur = 0;
         assemble_sigma(f, theta, classic ? 1 : 0, 0, f->npad);
-        {   // no right-hand sides: clear the rows under the matrix
-            RhsArgs ra;
-            memset(&ra, 0, sizeof ra);
-            ra.n = n; ra.p = p; ra.X = f->dX; ra.ldx = n; ra.src = f->dX; ra.lds = n;
-            ra.out = f->dA; ra.ld = f->lda; ra.row0 = f->npad; ra.nrows = 0; ra.nrows_zero = f->rhs_act;
-            ra.col0 = 0; ra.ncols_out = f->npad;
-            launch_rhs_rows(ra, s);
-        }
+        clear_border(f);
         if (int rc = factorize(f, main_view(f), nullptr)) return rc;
         launch_trmm_lower(f->dA, f->lda, n, dE, n, nsim, dtr, dY, n, s);
         HIPCHK_AT("cocons_sim_dense", hipMemcpyAsync(out, dY, (size_t)n * nsim * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK_AT("cocons_sim_dense", hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK_AT("cocons_sim_dense", hipGetLastError());
-        HIPCHK_AT("cocons_sim_dense", hipStreamSynchronize(s));
-        int rc = info_status(f);
-        if (engine_retry(f, rc)) continue;
-        return rc;
-    }
+        return 0;
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -3142,24 +3084,17 @@ extern "C" int cocons_sim_cond_dense(cocons_fit *f, const double *theta, const d
     HIPCHK_AT("cocons_sim_cond_dense", upload_canon(dlp, locs_pred, (size_t)m * 2, s));
     HIPCHK_AT("cocons_sim_cond_dense", upload_canon(dlu, locs_unobs, (size_t)m * 2, s));
     HIPCHK_AT("cocons_sim_cond_dense", upload_canon(dE, iiderrors, (size_t)m * nsim, s));
-    for (;;) {
-        if (int rc = reset_info(f)) return rc;
+    ThetaVecs tv;
+    make_theta_vecs(theta, p, tv);
+    const ModeSel ms0 = select_mode(theta, p, f->smooth_limits, 0);   // cov_rns semantics
+    const ModeSel msp = select_mode(theta, p, f->smooth_limits, 2);   // cov_rns_pred semantics
+    const int st = run_op(f, "cocons_sim_cond_dense", [&]() -> int {
         f->nrhs_cur = 1;
-        ThetaVecs tv;
-        make_theta_vecs(theta, p, tv);
-        const ModeSel ms0 = select_mode(theta, p, f->smooth_limits, 0);   // cov_rns semantics
-        const ModeSel msp = select_mode(theta, p, f->smooth_limits, 2);   // cov_rns_pred semantics
-        LocArgs lo;   // observed side
-        lo.n = n; lo.p = p; lo.X = f->dX; lo.ldx = n; lo.locs = f->dlocs; lo.ldl = n;
-        lo.out = f->dloc; lo.stride = npad; lo.smooth_kind = ms0.smooth_kind;
-        lo.smooth_min = f->smooth_limits[0]; lo.smooth_max = f->smooth_limits[1]; lo.th = tv;
-        LocArgs lu = lo;   // new locations with the coordinates handed to cov_rns (covmat_unobs)
-        lu.n = m; lu.X = dXp; lu.ldx = m; lu.locs = dlu; lu.ldl = m; lu.out = dlocu; lu.stride = mpad;
-        LocArgs lp = lu;   // new locations with newlocs (cov_rns_pred), always logistic + sqrt
-        lp.locs = dlp; lp.out = dlocp; lp.smooth_kind = msp.smooth_kind;
-        launch_loc_params(lo, s);
-        launch_loc_params(lu, s);
-        launch_loc_params(lp, s);
+        // the observed side, then the new locations twice: with the coordinates handed to cov_rns (covmat_unobs) and with
+        // newlocs (cov_rns_pred, always logistic + sqrt)
+        launch_loc_params(loc_args(n, p, f->dX, f->dlocs, f->dloc, npad, tv, ms0.smooth_kind, f->smooth_limits), s);
+        launch_loc_params(loc_args(m, p, dXp, dlu, dlocu, mpad, tv, ms0.smooth_kind, f->smooth_limits), s);
+        launch_loc_params(loc_args(m, p, dXp, dlp, dlocp, mpad, tv, msp.smooth_kind, f->smooth_limits), s);
         PairArgs pa;
         // Sigma_oo  (rows/cols [0, npad))
         memset(&pa, 0, sizeof pa);
@@ -3173,21 +3108,14 @@ extern "C" int cocons_sim_cond_dense(cocons_fit *f, const double *theta, const d
         pa.gr = ms0.gr; pa.nu_fixed = ms0.nu_fixed;
         launch_pair_sym(ms0.mode, false, pa, s);
         // cross block (rows [npad, N) x cols [0, npad)): observed side needs the pred-branch smoothness
-        if (ms0.smooth_kind != msp.smooth_kind) { lo.smooth_kind = msp.smooth_kind; launch_loc_params(lo, s); }
+        if (ms0.smooth_kind != msp.smooth_kind)
+            launch_loc_params(loc_args(n, p, f->dX, f->dlocs, f->dloc, npad, tv, msp.smooth_kind, f->smooth_limits), s);
         memset(&pa, 0, sizeof pa);
         pa.n = n; pa.m = m; pa.rows = dlocp; pa.stride_rows = mpad; pa.cols = f->dloc; pa.stride = npad;
         pa.out = dJ + npad; pa.ld = ldj; pa.nrows_out = mpad; pa.ncols_out = npad; pa.gr = msp.gr;
         launch_pair_rect(MODE_GEOM, pa, s);
-        {   // border row N: residual of realization z_col over the observed columns, zero elsewhere
-            RhsArgs ra;
-            memset(&ra, 0, sizeof ra);
-            ra.n = n; ra.p = p; ra.X = f->dX; ra.ldx = n; ra.use_trend = 1;
-            for (int i = 0; i < p; ++i) ra.mean[i] = canon_nan(mean[i]);
-            ra.src = f->dz + (size_t)z_col * n; ra.lds = n;
-            ra.out = dJ; ra.ld = ldj; ra.row0 = N; ra.nrows = 1; ra.nrows_zero = TILE - 1;
-            ra.col0 = 0; ra.ncols_out = N;
-            launch_rhs_rows(ra, s);
-        }
+        // border row N: residual of realization z_col over the observed columns, zero elsewhere
+        residual_row(f, mean, z_col, dJ, ldj, N, TILE - 1, N);
         FactorView v;
         v.A = dJ; v.lda = ldj; v.nt = N / TILE; v.mt = N / TILE + 1;
         if (int rc = factorize(f, v, nullptr)) return rc;
@@ -3204,13 +3132,9 @@ extern "C" int cocons_sim_cond_dense(cocons_fit *f, const double *theta, const d
         // fields = L_S E + tmp_mu with L_S = lower-right block of the joint factor
         launch_trmm_lower(dJ + (size_t)npad + (size_t)npad * ldj, ldj, m, dE, m, nsim, dmu, dY, m, s);
         HIPCHK_AT("cocons_sim_cond_dense", hipMemcpyAsync(out, dY, (size_t)m * nsim * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK_AT("cocons_sim_cond_dense", hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK_AT("cocons_sim_cond_dense", hipGetLastError());
-        HIPCHK_AT("cocons_sim_cond_dense", hipStreamSynchronize(s));
-        int rc = info_status(f);
-        if (engine_retry(f, rc)) continue;
-        return rc > n ? n : rc;    // a failure inside the Schur block is still "Cholesky error"
-    }
+        return 0;
+    });
+    return st > n ? n : st;    // a failure inside the Schur block is still "Cholesky error"
 }
 
 // ---------------------------------------------------------------------------
@@ -3408,12 +3332,8 @@ static int shard_begin(cocons_fit *f, const double *theta, const double *mean, i
     ThetaVecs tv;
     make_theta_vecs(theta, f->p, tv);
     ModeSel ms = select_mode(theta, f->p, f->smooth_limits, 0);
-    LocArgs la;
-    la.n = f->n; la.p = f->p; la.X = f->dX; la.ldx = f->n; la.locs = f->dlocs; la.ldl = f->n;
-    la.out = f->dloc; la.stride = f->npad; la.smooth_kind = ms.smooth_kind;
-    la.smooth_min = f->smooth_limits[0]; la.smooth_max = f->smooth_limits[1];
-    la.th = tv;
-    launch_loc_params(la, f->stream);                  // (replicated: O(n p))
+    launch_loc_params(loc_args(f->n, f->p, f->dX, f->dlocs, f->dloc, f->npad, tv, ms.smooth_kind, f->smooth_limits),
+                      f->stream);                      // (replicated: O(n p))
     PairArgs pa;
     pa.n = f->n; pa.m = f->n; pa.rows = f->dloc; pa.cols = f->dloc;
     pa.stride = f->npad; pa.stride_rows = f->npad; pa.out = f->dA; pa.ld = f->lda;

@@ -149,7 +149,8 @@ void launch_potrf_engine(double *A, size_t lda, int t0, int nt, double *dinv, in
 //   0xa00 .. 0xe00  waits of the persistent launch (dag_kernel: index = step)  0xf00  next-diagonal-block workgroups of the
 //   panel launch waiting in the strip mailbox
 constexpr unsigned ABORT_ENGINE_IN0 = 0x100u, ABORT_ENGINE_IN1 = 0x200u, ABORT_PANEL = 0x300u, ABORT_XCHG = 0x400u, ABORT_INPANEL = 0x500u,
-                   ABORT_GATE = 0x600u, ABORT_PARTNER = 0x700u, ABORT_FOLLOW = 0x800u, ABORT_LAST_TILE = 0x900u, ABORT_STRIPBOX = 0xf00u;
+                   ABORT_GATE = 0x600u, ABORT_PARTNER = 0x700u, ABORT_FOLLOW = 0x800u, ABORT_LAST_TILE = 0x900u, ABORT_STRIPBOX = 0xf00u,
+                   ABORT_DAG_FIRST = 0xa00u, ABORT_DAG_LAST = 0xe00u;      // (the classes of the persistent launch: a range)
 __host__ __device__ inline unsigned abort_code(unsigned cls, unsigned index) { return cls | (index & 0xffu); }
 inline unsigned abort_class(unsigned code) { return code & 0xf00u; }
 constexpr size_t ENGINE_MBOX_DOUBLES = 44 * 256;
