@@ -14,6 +14,7 @@ from .host import (  # noqa: F401
     GetNeg2loglikelihoodProfile,
     GetNeg2loglikelihoodREML,
     GetNeg2loglikelihood_batch,
+    GetNeg2loglikelihood_grad,
     cocoPredict_dense,
     cocoPredict_dense_chunked,
     cocoPredict_sparse,
@@ -28,7 +29,9 @@ from .host import (  # noqa: F401
     getBetas_profile,
     getHessian_dense,
     getModelLists,
+    getModelLists_grad,
     getPen,
+    getPen_grad,
     getScale,
     sumsmoothlone,
 )

@@ -58,6 +58,7 @@ SIGNATURES = {
                                        ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_dp]),
     "cocons_fit_destroy": (None, [c_vp]),
     "cocons_neg2loglik_dense": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp]),
+    "cocons_neg2loglik_grad_dense": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "cocons_neg2loglik_batch": (c_int, [c_vp, c_int, c_dp, c_dp, c_dp, ctypes.POINTER(c_int)]),
     "cocons_neg2loglik_profile": (c_int, [c_vp, c_dp, c_dp, c_dp]),
     "cocons_neg2loglik_reml": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp]),
@@ -97,6 +98,9 @@ SIGNATURES = {
 # every symbol include/cocons_hip_diag.h declares (probes and pointwise diagnostics: not the drop-in boundary)
 DIAG_SIGNATURES = {
     "cocons_debug_matern": (c_int, [c_int, c_dp, c_dp, c_dp]),
+    "cocons_debug_matern_grad": (c_int, [c_int, c_dp, c_dp, c_dp]),
+    "cocons_debug_sigma_inverse": (c_int, [c_vp, c_dp, c_dp]),
+    "cocons_debug_fit_memory": (c_int, [c_vp, ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_debug_tune": (c_int, [ctypes.c_char_p, c_int]),
     "cocons_debug_dag_replay": (c_int, [c_vp, c_dp, c_dp, c_int, c_dp]),
     "cocons_debug_host_enqueue": (c_int, [c_vp, c_dp]),

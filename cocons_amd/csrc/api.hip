@@ -326,6 +326,7 @@ struct cocons_fit {
     double *dX, *dlocs, *dz, *dxb;
     double *dloc;            // LOCP_FIELDS x npad
     double *dA;
+    size_t dA_elems;         // doubles allocated at dA: lda * npad, or more once a gradient call has grown it (grad_prepare)
     double *dinv;            // 2 x 8 x 256
     int *dinfo;
     double *dout;            // reductions
@@ -436,6 +437,7 @@ struct cocons_fit {
                                   // (engine_warm: try_lock under the registry's lock -- a busy handle is not probed, a probed one
                                   // can neither be used nor destroyed until the probe is over).  A pointer: the struct is memset
     struct KrigeState *krige;     // kriging state (cocons_krige_prepare): one factor of Sigma(theta) held apart from dA
+    struct GradState *grad;       // scratch of cocons_neg2loglik_grad_dense (allocated on first use)
 };
 
 // Kriging state of a dense handle (cocons_krige_prepare / _apply / _release).  Everything apply reads lives here, owned by
@@ -454,6 +456,7 @@ struct KrigeState {
 };
 
 static void shard_state_free(struct ShardState *S);
+static void grad_state_free(cocons_fit *f);
 
 // Every live handle of the process: engine_warm tests a new handle's streams against the streams of the others (a resident
 // engine of one handle must not share a hardware queue with the main stream of another: the batch slots and callers with
@@ -490,10 +493,11 @@ static int fit_alloc_matrix(cocons_fit *f, int rhs_rows)
     f->rhs_act = cap;        // a buffer grown by an earlier predict call must not slow later evaluations
     f->border_clean = -1; f->border_pending = -1;      // every user of the rows under the matrix comes through here
     if (f->dA && cap <= f->rhs_cap) return 0;
-    if (f->dA) { HIPCHK(hipFree(f->dA)); f->dA = nullptr; }
+    if (f->dA) { HIPCHK(hipFree(f->dA)); f->dA = nullptr; f->dA_elems = 0; }
     f->rhs_cap = cap;
     f->lda = (size_t)(f->skew > 0 ? f->skew * TILE : f->npad) + cap;
     HIPCHK(hipMalloc(&f->dA, f->lda * (size_t)f->npad * sizeof(double)));
+    f->dA_elems = f->lda * (size_t)f->npad;
     // never-written parts must not hold NaN bit patterns: a band-limited factorisation only clears its envelope, and
     // 0 * garbage must stay 0 whatever the allocator hands back
     HIPCHK(hipMemsetAsync(f->dA, 0, f->lda * (size_t)f->npad * sizeof(double), f->stream));
@@ -534,6 +538,7 @@ extern "C" void cocons_fit_destroy(cocons_fit *f)
         if (f->unsorted) { cocons_fit_destroy(f->unsorted); f->unsorted = nullptr; }
         if (f->taper_twin) { cocons_fit_destroy(f->taper_twin); f->taper_twin = nullptr; }
         delete f->krige; f->krige = nullptr;                    // (its buffers: the main stream is drained above)
+        grad_state_free(f);
         if (f->stream2) hipStreamDestroy(f->stream2);
         if (f->own_stream && f->stream) hipStreamDestroy(f->stream);
     }
@@ -4086,6 +4091,228 @@ extern "C" int cocons_debug_dag_replay(cocons_fit *f, const double *theta, const
     f->border_clean = -1; f->border_pending = -1;        // (the buffer holds a half-done factorisation)
     f->dag_used = false;
     return rc;
+}
+
+// ---------------------------------------------------------------------------
+// Analytic gradient of the dense -2 log-likelihood.  One bordered factorisation of
+//     [ Sigma ; R' ; I ]      (R = z - X mean, the residual rows in the first tile under the matrix, the unit rows behind it)
+// on the plain schedules (dag_ok = false: the whole factor stays in dA) leaves L^-1 R and B = L^-T under the factor, by the
+// trailing-update kernel itself.  Then the log-determinant and the quadratic forms (launch_finalize, as the objective),
+// A = Sigma^-1 R = B L^-1 R, -Sigma^-1 = -B B' into the square the factor held (launch_grad_syrk), and the pair contraction
+// (grad.hip).
+// Memory: the bordered matrix needs rt + npad rows under the matrix.  It lives in the SAME allocation as every other
+// operation's matrix -- dA grows once to hold it (one extra npad^2) -- with a leading dimension of its own for the duration
+// of one gradient operation only (GradLayout).  f->lda, and with it the DAG schedule's second buffer (dag_prepare sizes dP
+// from the view's lda), keeps the objective's value: a gradient call moves nothing else on the handle.
+struct GradState {
+    DevBuf<double> scratch;       // grad_scratch_doubles(npad)
+    DevBuf<double> AR;            // npad x r: Sigma^-1 R
+    DevBuf<double> ARpart;        // its partial sums (grad_sigma_r_scratch_doubles)
+    DevBuf<double> site;          // GSITE_FIELDS x npad
+    DevBuf<double> out;           // 7 p: theta-table gradient, mean gradient
+    long long bytes = 0;          // device bytes of the buffers above
+};
+
+static size_t grad_lda(const cocons_fit *f)
+{
+    return (size_t)f->npad + (size_t)round_up(f->r > 0 ? f->r : 1, TILE) + (size_t)f->npad;
+}
+
+// f->lda / f->rhs_act in the gradient's layout while one gradient operation runs, the objective's afterwards (every way
+// out); the rows under the matrix then hold nothing the objective may rely on (border_clean unknown)
+struct GradLayout {
+    cocons_fit *f;
+    size_t lda;
+    int rhs_act;
+    explicit GradLayout(cocons_fit *f_) : f(f_), lda(f_->lda), rhs_act(f_->rhs_act)
+    {
+        f->lda = grad_lda(f);
+        f->rhs_act = (int)(f->lda - (size_t)f->npad);
+        f->border_clean = -1; f->border_pending = -1;
+    }
+    ~GradLayout()
+    {
+        f->lda = lda; f->rhs_act = rhs_act;
+        f->border_clean = -1; f->border_pending = -1;
+    }
+};
+
+static void grad_state_free(cocons_fit *f)
+{
+    delete f->grad;
+    f->grad = nullptr;
+}
+
+static int grad_refuse(cocons_fit *f, const char *who)
+{
+    if (int rc = no_taper(f, who)) return rc;
+    if (f->coll_kind) return fail(-1, "%s: not available on a sharded handle", who);
+    return 0;
+}
+
+// everything of one gradient operation on the handle's stream (run_op repeats it after a hand-off time-out); full = false
+// stops once -Sigma^-1 is in the leading square (cocons_debug_sigma_inverse)
+static int grad_enqueue(cocons_fit *f, const double *theta, const double *mean, bool full, double *hgrad)
+{
+    const int npad = f->npad, nr = f->r, rt = round_up(nr > 0 ? nr : 1, TILE), p = f->p;
+    hipStream_t s = f->stream;
+    GradState *G = f->grad;
+    f->nrhs_cur = nr;
+    assemble_sigma(f, theta, 0, 0, npad);
+    // rows npad.. : R' and zeros up to npad + rt; then the unit rows e_i', i < npad
+    RhsArgs ra;
+    memset(&ra, 0, sizeof ra);
+    ra.n = f->n; ra.p = p; ra.X = f->dX; ra.ldx = f->n; ra.use_trend = 1;
+    for (int i = 0; i < p; ++i) ra.mean[i] = canon_nan(mean[i]);
+    ra.src = f->dz ? f->dz : f->dX; ra.lds = f->n;
+    ra.out = f->dA; ra.ld = f->lda; ra.row0 = npad; ra.nrows = nr; ra.nrows_zero = rt - nr;
+    ra.col0 = 0; ra.ncols_out = npad;
+    launch_rhs_rows(ra, s);
+    launch_grad_fill(f->dA, f->lda, npad + rt, npad, npad, npad + rt, s);
+    if (int rc = factorize(f, main_view(f), nullptr)) return rc;
+    launch_finalize(f->dA, f->lda, f->n, npad, nr, f->dout, s);
+    HIPCHK(hipMemcpyAsync(f->hout, f->dout, (size_t)(1 + nr * nr) * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (nr > 0) launch_grad_sigma_r(f->dA, f->lda, npad, npad, nr, npad + rt, G->ARpart, G->AR, s);
+    launch_grad_fill(f->dA, f->lda, 0, npad, npad, -1, s);
+    launch_grad_syrk(f->dA, f->lda, npad, npad + rt, s);
+    if (!full) return 0;
+    ThetaVecs tv;
+    make_theta_vecs(theta, p, tv);
+    const ModeSel ms = select_mode(theta, p, f->smooth_limits, 0);
+    const int smooth_free = ms.smooth_kind == SMOOTH_LOGISTIC_SQRT && f->smooth_limits[1] != f->smooth_limits[0];
+    launch_grad_site(loc_args(f->n, p, f->dX, f->dlocs, G->site, npad, tv, ms.smooth_kind, f->smooth_limits), G->site, npad,
+                     smooth_free, s);
+    GradArgs g;
+    memset(&g, 0, sizeof g);
+    g.n = f->n; g.pad0 = f->pad0; g.npad = npad; g.p = p;
+    g.S = f->dA; g.lds = f->lda;
+    g.AR = G->AR; g.ldar = npad; g.nr = nr;
+    g.loc = f->dloc; g.stride = npad; g.site = G->site;
+    g.X = f->dX; g.ldx = f->n;
+    g.gr = ms.gr; g.nu_fixed = ms.nu_fixed; g.smooth_free = smooth_free;
+    const size_t T = (size_t)npad / 64, ntile = T * (T + 1) / 2;
+    g.part_row = G->scratch; g.part_col = g.part_row + ntile * 6 * 64; g.part_glob = g.part_col + ntile * 6 * 64;
+    g.gsite = g.part_glob + ntile;
+    g.out = G->out;
+    launch_grad_pairs(ms.mode, g, s);
+    HIPCHK(hipMemcpyAsync(hgrad, G->out, (size_t)7 * p * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int grad_prepare(cocons_fit *f, const char *who)
+{
+    const int r1 = f->r > 0 ? f->r : 1;
+    if (!f->grad) {
+        std::unique_ptr<GradState> G(new GradState());
+        const size_t sc = grad_scratch_doubles(f->npad), ar = (size_t)f->npad * r1, arp = grad_sigma_r_scratch_doubles(f->npad, r1),
+                     si = (size_t)GSITE_FIELDS * f->npad, ou = (size_t)7 * f->p;
+        HIPCHK_AT(who, G->scratch.alloc(sc));
+        HIPCHK_AT(who, G->AR.alloc(ar));
+        HIPCHK_AT(who, G->ARpart.alloc(arp));
+        HIPCHK_AT(who, G->site.alloc(si));
+        HIPCHK_AT(who, G->out.alloc(ou));
+        G->bytes = (long long)((sc + ar + arp + si + ou) * sizeof(double));
+        f->grad = G.release();
+    }
+    if (!f->dA) return fail(-1, "%s: the handle has no matrix buffer", who);
+    // dA large enough for the gradient's layout: grown once, f->lda unchanged (GradLayout); the contents need not survive
+    // (every operation assembles its matrix anew)
+    const size_t need = grad_lda(f) * (size_t)f->npad;
+    if (f->dA_elems < need) {
+        HIPCHK_AT(who, hipStreamSynchronize(f->stream));
+        if (f->stream2) HIPCHK_AT(who, hipStreamSynchronize(f->stream2));
+        HIPCHK_AT(who, hipFree(f->dA));
+        f->dA = nullptr; f->dA_elems = 0;
+        HIPCHK_AT(who, hipMalloc(&f->dA, need * sizeof(double)));
+        HIPCHK_AT(who, hipMemsetAsync(f->dA, 0, need * sizeof(double), f->stream));
+        HIPCHK_AT(who, hipStreamSynchronize(f->stream));
+        f->dA_elems = need;
+        f->border_clean = -1; f->border_pending = -1;
+    }
+    return 0;
+}
+
+extern "C" int cocons_neg2loglik_grad_dense(cocons_fit *f, const double *theta, const double *mean, double *sum_logliks,
+                                            double *parts, double *grad_theta, double *grad_mean)
+{
+    const char *who = "cocons_neg2loglik_grad_dense";
+    if (!f) return fail(-1, "%s: null fit handle", who);
+    if (!theta || !mean || !sum_logliks || !grad_theta || !grad_mean) return fail(-1, "%s: null argument", who);
+    FIT_ENTER(f);
+    if (int rc = grad_refuse(f, who)) return rc;
+    if (f->r < 1) return fail(-1, "%s: fit has no z", who);
+    if (int rc = grad_prepare(f, who)) return rc;
+    std::vector<double> hg((size_t)7 * f->p);
+    GradLayout layout(f);
+    const int st = run_op(f, who, [&]() -> int { return grad_enqueue(f, theta, mean, true, hg.data()); });
+    if (st) return st;                  // failing minor: nothing written
+    dense_collect(f, sum_logliks, parts);
+    memcpy(grad_theta, hg.data(), (size_t)6 * f->p * sizeof(double));
+    memcpy(grad_mean, hg.data() + (size_t)6 * f->p, (size_t)f->p * sizeof(double));
+    return 0;
+}
+
+extern "C" int cocons_debug_sigma_inverse(cocons_fit *f, const double *theta, double *out)
+{
+    const char *who = "cocons_debug_sigma_inverse";
+    if (!f) return fail(-1, "%s: null fit handle", who);
+    if (!theta || !out) return fail(-1, "%s: null argument", who);
+    FIT_ENTER(f);
+    if (int rc = grad_refuse(f, who)) return rc;
+    if (f->sorted) {
+        // the caller's observation order: through the clone that keeps it (as cocons_sim_dense)
+        if (!f->unsorted) {
+            f->unsorted = fit_create_impl(f->n_user, f->p, f->r, 0, f->h_locs->data(), f->h_X->data(),
+                                          f->r > 0 ? f->h_z->data() : nullptr, nullptr, f->smooth_limits,
+                                          f->device, false);
+            if (!f->unsorted) return -1;
+        }
+        return cocons_debug_sigma_inverse(f->unsorted, theta, out);
+    }
+    if (int rc = grad_prepare(f, who)) return rc;
+    const std::vector<double> zero((size_t)f->p, 0.0);
+    GradLayout layout(f);
+    const int st = run_op(f, who, [&]() -> int { return grad_enqueue(f, theta, zero.data(), false, nullptr); });
+    if (st) return st;
+    const size_t n = (size_t)f->n_user;
+    HIPCHK_AT(who, hipMemcpy2DAsync(out, n * sizeof(double), f->dA, f->lda * sizeof(double), n * sizeof(double), n,
+                                    hipMemcpyDeviceToHost, f->stream));
+    HIPCHK_AT(who, hipStreamSynchronize(f->stream));
+    for (size_t j = 0; j < n; ++j)                  // the square holds -Sigma^-1 below its diagonal, zeros above
+        for (size_t i = 0; i < n; ++i) out[i + j * n] = i >= j ? -out[i + j * n] : 0.0;
+    return 0;
+}
+
+// out4 = { bytes allocated for the matrix buffer dA, bytes of the DAG schedule's second buffer dP, bytes of the gradient's
+// scratch, the leading dimension the objective uses }
+extern "C" int cocons_debug_fit_memory(cocons_fit *f, long long *out4)
+{
+    if (!f) return fail(-1, "cocons_debug_fit_memory: null fit handle");
+    if (!out4) return fail(-1, "cocons_debug_fit_memory: null argument");
+    FIT_ENTER(f);
+    out4[0] = (long long)(f->dA_elems * sizeof(double));
+    out4[1] = (long long)(f->dP_elems * sizeof(double));
+    out4[2] = f->grad ? f->grad->bytes : 0;
+    out4[3] = (long long)f->lda;
+    return 0;
+}
+
+extern "C" int cocons_debug_matern_grad(int n, const double *nu, const double *u, double *out)
+{
+    if (n <= 0 || !nu || !u || !out) return fail(-1, "cocons_debug_matern_grad: bad argument");
+    DevBuf<double> d;
+    StreamDrain s{nullptr, true};
+    HIPCHK_AT("cocons_debug_matern_grad", hipStreamCreateWithFlags(&s.s, hipStreamNonBlocking));
+    HIPCHK_AT("cocons_debug_matern_grad", d.alloc((size_t)5 * n));
+    HIPCHK_AT("cocons_debug_matern_grad", upload_canon(d, nu, (size_t)n, s));
+    HIPCHK_AT("cocons_debug_matern_grad", upload_canon(d + n, u, (size_t)n, s));
+    launch_matern_grad_points(n, d, d + n, d + 2 * (size_t)n, s);
+    HIPCHK_AT("cocons_debug_matern_grad", hipGetLastError());
+    HIPCHK_AT("cocons_debug_matern_grad", hipMemcpyAsync(out, d + 2 * (size_t)n, (size_t)3 * n * sizeof(double),
+                                                          hipMemcpyDeviceToHost, s));
+    HIPCHK_AT("cocons_debug_matern_grad", hipStreamSynchronize(s));
+    return 0;
 }
 
 // ---------------------------------------------------------------------------

@@ -1,0 +1,448 @@
+// grad.hip -- analytic gradient of the dense -2 log-likelihood (cocons_neg2loglik_grad_dense), gfx950.
+//
+//   grad_fill_kernel     : unit rows under the matrix (the bordered factorisation solves L^-T beside the residuals), zeros
+//   grad_sigma_r_kernel  : A = Sigma^-1 R = L^-T (L^-1 R) from the solved rows
+//   launch_grad_syrk     : -Sigma^-1 = -L^-T L^-1 (lower tiles) by the trailing-update kernel, 256 columns of L^-T at a time
+//   grad_site_kernel     : per-site derivative factors beside loc_params_kernel's SoA (tilt, smoothness, std.dev)
+//   grad_pair_kernel     : W = r Sigma^-1 - A A' contracted with dSigma/d(site predictors) over the 64 x 64 lower tiles
+//   grad_reduce_kernel / grad_xt_kernel : fixed-order sums per site, then X' g and the mean gradient
+//
+// Every sum has a fixed order (no floating-point atomics): two calls give bit-identical gradients.
+// Compile with -ffp-contract=off (matern_device.hpp).
+#include <hip/hip_runtime.h>
+#include "kernels.h"
+#include "matern_device.hpp"
+
+namespace cocons {
+
+constexpr int GTS = 64;            // pair tile edge (as pair_sym_kernel)
+constexpr int GFAM = 6;            // site families: std.dev, scale, aniso, tilt, smooth, nugget (theta's row order)
+constexpr int TH_SD_ = 0, TH_SCALE_ = 1, TH_NG_ = 5;
+
+// ---------------------------------------------------------------------------
+// 2^(1-nu)/Gamma(nu) u^nu K_nu(u) and its u-derivative -2^(1-nu)/Gamma(nu) u^nu K_{nu-1}(u), 0 < u < 706, nu > 0.
+// Temme's series (u <= 2) or Steed's CF2 (u > 2) give K_mu, K_{mu+1} with mu = nu - round(nu); the forward recurrence
+// up to order nu keeps the order below it (matern_bessel's scheme, with the neighbouring order kept).
+__device__ __noinline__ void matern_pair(double nu, double u, double &M, double &Mu)
+{
+    const double tol = 2.220446049250313e-16;
+    const double pi = 3.14159265358979323846;
+    const int n = (int)floor(nu + 0.5);
+    const double mu = nu - n, mu2 = mu * mu;
+    double gam1 = 0.0, gam2 = 0.0;
+    for (int j = RG_NTERMS - 1; j >= 0; --j) {
+        gam1 = fma(gam1, mu2, c_rg_odd[j]);
+        gam2 = fma(gam2, mu2, c_rg_even[j]);
+    }
+    const double gampl = gam2 - mu * gam1;   // 1/Gamma(1+mu)
+    const double gammi = gam2 + mu * gam1;   // 1/Gamma(1-mu)
+    double kmu, kmu1;
+    bool scaled;                             // K values carry the factor e^u (CF2)
+    if (u <= 2.0) {
+        const double x2 = 0.5 * u, pimu = pi * mu;
+        const double fact = fabs(pimu) < tol ? 1.0 : pimu / sin(pimu);
+        double d = -log(x2);
+        double e = mu * d;
+        const double fact2 = fabs(e) < tol ? 1.0 : sinh(e) / e;
+        double ff = fact * (gam1 * cosh(e) + gam2 * fact2 * d);
+        double sum = ff;
+        e = exp(e);
+        double pp = 0.5 * e / gampl, q = 0.5 / (e * gammi), c = 1.0;
+        d = x2 * x2;
+        double sum1 = pp;
+        for (int i = 1; i < 500; ++i) {
+            const double di = (double)i;
+            ff = (di * ff + pp + q) / ((di - mu) * (di + mu));
+            c *= d / di;
+            pp /= (di - mu);
+            q /= (di + mu);
+            const double del = c * ff;
+            sum += del;
+            sum1 += c * (pp - di * ff);
+            if (fabs(del) < fabs(sum) * tol) break;
+        }
+        kmu = sum;
+        kmu1 = sum1 * (2.0 / u);
+        scaled = false;
+    } else {
+        double a = mu2 - 0.25;
+        double b = 2.0 * (u + 1.0), D = 1.0 / b, f = D, delta = D;
+        double Ak = -a, Bk = 0.0;
+        double Q = Ak, S = 1.0 + Q * delta;
+        for (int k = 2; k < 500; ++k) {
+            a -= 2 * (k - 1);
+            b += 2.0;
+            D = 1.0 / (a * D + b);
+            delta *= b * D - 1.0;
+            f += delta;
+            const double An = -(Bk - (b - 2.0) * Ak) / (double)k;
+            Bk = -(a / (double)k) * Ak;
+            Ak = An;
+            Q += Ak;
+            const double qd = Q * delta;
+            S += qd;
+            if (fabs(qd) < fabs(S) * tol) break;
+        }
+        kmu = sqrt(pi / (2.0 * u)) / S;
+        kmu1 = kmu * (0.5 + mu + u + (mu2 - 0.25) * f) / u;
+        scaled = true;
+    }
+    // K_{nu-1}, K_nu: n >= 1 keeps the order below nu from the recurrence; n = 0 takes K_{mu-1} = K_{mu+1} - (2 mu / u) K_mu
+    double klo = kmu1 - (2.0 * mu / u) * kmu, khi = kmu;
+    if (n >= 1) { klo = kmu; khi = kmu1; }
+    for (int k = 1; k < n; ++k) {
+        const double next = (2.0 * (mu + k) / u) * khi + klo;
+        klo = khi;
+        khi = next;
+    }
+    double prod = 1.0;
+    for (int k = 1; k < n; ++k) prod *= (mu + k);
+    const double rg = ((n == 0) ? mu * gampl : gampl) / prod;      // 1/Gamma(nu)
+    const double ex = nu * log2(u) + 1.0 - nu;
+    const double pre = (scaled ? pow2a_expmu(ex, u) : exp2(ex)) * rg;
+    M = pre * khi;
+    Mu = -pre * klo;
+}
+
+// dM/dnu at fixed u: four-point central difference (step 1e-3 nu: truncation ~1e-11 relative, rounding ~1e-12)
+__device__ double matern_dnu(double nu, double u)
+{
+    const double h = 1e-3 * nu;
+    double m1, m2, m3, m4, t;
+    matern_pair(nu + h, u, m1, t);
+    matern_pair(nu - h, u, m2, t);
+    matern_pair(nu + 2 * h, u, m3, t);
+    matern_pair(nu - 2 * h, u, m4, t);
+    return (8.0 * (m1 - m2) - (m3 - m4)) / (12.0 * h);
+}
+
+__global__ void __launch_bounds__(64)
+matern_grad_points_kernel(int n, const double *nu, const double *u, double *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double v = nu[i], x = u[i];
+    double M, Mu, Mn;
+    if (x >= 706.0) { M = matern_bessel(v, x); Mu = 0.0; Mn = 0.0; }      // the reference's stand-in: derivatives round to 0
+    else { matern_pair(v, x, M, Mu); Mn = matern_dnu(v, x); }
+    out[i] = M;
+    out[i + n] = Mu;
+    out[i + 2 * (size_t)n] = Mn;
+}
+
+void launch_matern_grad_points(int n, const double *nu, const double *u, double *out, hipStream_t s)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(matern_grad_points_kernel, dim3((n + 63) / 64), dim3(64), 0, s, n, nu, u, out);
+}
+
+// ---------------------------------------------------------------------------
+// rows [row0, row0 + nrows) x columns [0, ncols) of A: 1 where row - row_id == column, else 0 (row_id < 0: all zero).
+// Lanes along the rows: every wave store is 512 contiguous bytes.
+__global__ void __launch_bounds__(256)
+grad_fill_kernel(double *A, size_t lda, int row0, int nrows, int ncols, int row_id)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nrows) return;
+    const int c1 = min(ncols, (int)(blockIdx.y + 1) * 64);
+    for (int c = blockIdx.y * 64; c < c1; ++c)
+        A[(size_t)(row0 + i) + (size_t)c * lda] = (row_id >= 0 && row0 + i - row_id == c) ? 1.0 : 0.0;
+}
+
+void launch_grad_fill(double *A, size_t lda, int row0, int nrows, int ncols, int row_id, hipStream_t s)
+{
+    if (nrows <= 0 || ncols <= 0) return;
+    hipLaunchKernelGGL(grad_fill_kernel, dim3((nrows + 255) / 256, (ncols + 63) / 64), dim3(256), 0, s, A, lda, row0, nrows,
+                       ncols, row_id);
+}
+
+// AR[i + c npad] = sum_k B(i, k) w_c(k): B = L^-T in rows brow0.., w_c = L^-1 r_c in row wrow0 + c.  Stage 1: the 64 rows
+// of a block over one of GRAD_KSPLIT column chunks (B is upper triangular: chunks left of the rows are zero and skipped)
+// into part; stage 2: the chunks summed in order.
+constexpr int GRAD_KSPLIT = 16;
+__global__ void __launch_bounds__(64)
+grad_sigma_r_kernel(const double *A, size_t lda, int npad, int wrow0, int nr, int brow0, double *part)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    const int chunk = (npad + GRAD_KSPLIT - 1) / GRAD_KSPLIT;
+    const int k0 = blockIdx.y * chunk, k1 = min(npad, k0 + chunk);
+    for (int c = 0; c < nr; ++c) {
+        double s = 0.0;
+        for (int k = max(k0, (int)blockIdx.x * 64); k < k1; ++k)
+            s = fma(A[(size_t)(brow0 + i) + (size_t)k * lda], A[(size_t)(wrow0 + c) + (size_t)k * lda], s);
+        part[((size_t)blockIdx.y * nr + c) * npad + i] = s;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+grad_sigma_r_sum_kernel(const double *part, int npad, int nr, double *AR)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npad) return;
+    for (int c = 0; c < nr; ++c) {
+        double s = 0.0;
+        for (int q = 0; q < GRAD_KSPLIT; ++q) s += part[((size_t)q * nr + c) * npad + i];
+        AR[(size_t)i + (size_t)c * npad] = s;
+    }
+}
+
+size_t grad_sigma_r_scratch_doubles(int npad, int nr) { return (size_t)GRAD_KSPLIT * nr * npad; }
+
+void launch_grad_sigma_r(const double *A, size_t lda, int npad, int wrow0, int nr, int brow0, double *part, double *AR,
+                         hipStream_t s)
+{
+    hipLaunchKernelGGL(grad_sigma_r_kernel, dim3(npad / 64, GRAD_KSPLIT), dim3(64), 0, s, A, lda, npad, wrow0, nr, brow0, part);
+    hipLaunchKernelGGL(grad_sigma_r_sum_kernel, dim3((npad + 255) / 256), dim3(256), 0, s, part, npad, nr, AR);
+}
+
+// C(i, j) -= sum_k B(i, k) B(j, k) over the lower tiles of the leading npad x npad square (zero beforehand): -Sigma^-1.
+// B is upper triangular, so the 256 columns from k0 on only reach the tile rows below k0 + 256: about n^3 / 3 flops.
+void launch_grad_syrk(double *A, size_t lda, int npad, int brow0, hipStream_t s)
+{
+    const int nt = npad / TILE;
+    for (int t = 0; t < nt; t += 2) {
+        const int kw = (t + 2 <= nt) ? 2 : 1;
+        const int t1 = t + kw;
+        launch_update_from(A, lda, A + brow0 + (size_t)t * TILE * lda, lda, kw * TILE, 0, t1, 0, t1, true, s, 1, 1, 0);
+    }
+}
+
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+grad_site_kernel(LocArgs a, double *out, size_t stride, int smooth_free)
+{
+    const int w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= a.n) return;
+    double t_tilt = 0, t_sm = 0, t_sd = 0;
+    for (int i = 0; i < a.p; ++i) {           // as loc_params_kernel
+        const double x = a.X[w + (size_t)i * a.ldx];
+        t_tilt = fma(x, a.th.tilt[i], t_tilt);
+        t_sm = fma(x, a.th.smooth[i], t_sm);
+        t_sd = fma(x, a.th.sd[i], t_sd);
+    }
+    const double pi = 3.14159265358979323846;
+    const double et = exp(-t_tilt), st = 1.0 / (1.0 + et);
+    const double tilt = pi * st;
+    out[w + 0 * stride] = pi * st * (et * st);                       // dt/deta = pi s (1 - s)
+    out[w + 1 * stride] = cos(tilt) / sin(tilt);
+    double dnu = 0.0;
+    if (smooth_free) {
+        const double es = exp(-t_sm), ss = 1.0 / (1.0 + es);
+        const double span = a.smooth_max - a.smooth_min;
+        const double nu = span * ss + a.smooth_min;
+        dnu = span * ss * (es * ss) / (2.0 * nu);                      // dlog(nu_ij)/deta_i = dnu_i / (2 nu_i)
+    }
+    out[w + 2 * stride] = dnu;
+    out[w + 3 * stride] = exp(t_sd);
+}
+
+void launch_grad_site(const LocArgs &a, double *out, size_t stride, int smooth_free, hipStream_t s)
+{
+    if (a.n <= 0) return;
+    hipLaunchKernelGGL(grad_site_kernel, dim3((a.n + 255) / 256), dim3(256), 0, s, a, out, stride, smooth_free);
+}
+
+// ---------------------------------------------------------------------------
+// Partials of one off-diagonal entry C(ii = ia, jj = ib) with respect to the site predictors of both sides and the global
+// range, branch for branch as pair_value_idx evaluates it (pair_sym_kernel: u <= eps gives the ii site's diagonal).
+template <int MODE>
+__device__ __forceinline__ void pair_partials(const GradArgs &g, int ia, int ib, double da[GFAM], double db[GFAM], double &dglob)
+{
+    const double eps = 2.220446049250313e-16;
+    const double *L = g.loc;
+    const size_t sl = g.stride;
+#define LF(f, i) L[(size_t)(f) * sl + (i)]
+#define GF(f, i) g.site[(size_t)(f) * sl + (i)]
+    for (int f = 0; f < GFAM; ++f) { da[f] = 0.0; db[f] = 0.0; }
+    dglob = 0.0;
+    const double rda = LF(2, ia), an2a = LF(3, ia), raa = LF(4, ia), cta = LF(5, ia), sta = LF(6, ia);
+    const double rdb = LF(2, ib), an2b = LF(3, ib), rab = LF(4, ib), ctb = LF(5, ib), stb = LF(6, ib);
+    const double s11 = 0.5 * (rda + rdb), s22 = 0.5 * (rda * an2a + rdb * an2b), s12 = 0.5 * (raa * cta + rab * ctb);
+    const double D = s11 * s22 - s12 * s12;
+    const double dx = LF(0, ia) - LF(0, ib), dy = LF(1, ia) - LF(1, ib);
+    const double dxx = dx * dx, dyy = dy * dy, dxy = dx * dy;
+    const double q = s22 * dxx + s11 * dyy - 2.0 * s12 * dxy;
+    const double nu = (MODE == MODE_GEOM) ? LF(10, ia) * LF(10, ib) : g.nu_fixed;
+    const double u = sqrt(8.0 * nu * q / (g.gr * D));
+    if (u <= eps) {                       // coincident: C = exp(eta_sd) + ng of the ii site alone
+        da[TH_SD_] = GF(3, ia);
+        da[TH_NG_] = LF(12, ia);
+        return;
+    }
+    if (u >= 706.0) return;               // the reference's stand-in: rounds to 0
+    double M, Mu, Mn = 0.0;
+    if (MODE == MODE_HALF) { M = exp(-u); Mu = -M; }
+    else if (MODE == MODE_THREEHALF) { const double e = exp(-u); M = (1.0 + u) * e; Mu = -u * e; }
+    else if (MODE == MODE_FIVEHALF) { const double e = exp(-u); M = (1.0 + u + u * u / 3.0) * e; Mu = -(u / 3.0) * (1.0 + u) * e; }
+    else {
+        matern_pair(nu, u, M, Mu);
+        if (g.smooth_free) Mn = matern_dnu(nu, u);
+    }
+    const double P = LF(9, ia) * LF(9, ib) * sqrt(LF(8, ia) * LF(8, ib) / D);
+    const double C = M * P, U = P * Mu * u;                 // U = dC / dlog u
+    dglob = -U;                                             // gr = e^(2 theta_scale,0): dlog u = -1
+    auto side = [&](int i, double rd, double an2, double ra, double ct, double st, double *d) {
+        const double tp = GF(0, i), cot = GF(1, i);
+        // (s11', s22', s12') of the three geometric predictors, then dlog u = (q'/q - D'/D) / 2 and the amplitude's
+        // dlog = dlog(rd a sin t) / 2 - D'/(2 D)
+        const double s11p[3] = {0.5 * rd, 0.0, 0.0};
+        const double s22p[3] = {0.5 * rd * an2, rd * an2, 0.0};
+        const double s12p[3] = {0.5 * ra * ct, 0.5 * ra * ct, -0.5 * ra * st * tp};
+        const double amp[3] = {0.5, 0.5, 0.5 * cot * tp};
+        for (int k = 0; k < 3; ++k) {
+            const double Dp = s11p[k] * s22 + s11 * s22p[k] - 2.0 * s12 * s12p[k];
+            const double qp = s22p[k] * dxx + s11p[k] * dyy - 2.0 * s12p[k] * dxy;
+            const double dlu = 0.5 * (qp / q - Dp / D);
+            const double dlp = amp[k] - 0.5 * Dp / D;
+            d[1 + k] = U * dlu + C * dlp;
+        }
+        d[TH_SD_] = 0.5 * C;
+        if (g.smooth_free) {
+            const double dl = GF(2, i);                        // dlog nu_ij
+            d[4] = P * Mn * nu * dl + U * 0.5 * dl;
+        }
+    };
+    side(ia, rda, an2a, raa, cta, sta, da);
+    side(ib, rdb, an2b, rab, ctb, stb, db);
+#undef LF
+#undef GF
+}
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// One workgroup per 64 x 64 tile (bi >= bj) of the lower triangle, lane = row, each wave 16 columns.  Entry (r, c), r > c,
+// is the pair ii = c, jj = r.  Outputs per tile: the row sites' sums (over its columns), the column sites' sums (over its
+// rows), per family, and the tile's global-range sum.
+template <int MODE>
+__global__ void __launch_bounds__(256)
+grad_pair_kernel(GradArgs g)
+{
+    const int bi = blockIdx.x, bj = blockIdx.y;
+    if (bi < bj) return;
+    __shared__ double rows[4][GTS][GFAM];
+    __shared__ double cols[GTS][GFAM];
+    __shared__ double red[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = bi * GTS + lane;
+    const bool rin = r >= g.pad0 && r < g.n;
+    double racc[GFAM] = {0, 0, 0, 0, 0, 0};
+    double gacc = 0.0;
+    for (int cc = 0; cc < GTS / 4; ++cc) {
+        const int cl = wave * (GTS / 4) + cc;
+        const int c = bj * GTS + cl;
+        const bool cin = c >= g.pad0 && c < g.n;
+        double dcol[GFAM] = {0, 0, 0, 0, 0, 0};
+        if (rin && cin && r >= c) {
+            double W = -(double)g.nr * g.S[(size_t)r + (size_t)c * g.lds];
+            for (int k = 0; k < g.nr; ++k) W -= g.AR[(size_t)r + (size_t)k * g.ldar] * g.AR[(size_t)c + (size_t)k * g.ldar];
+            if (r == c) {
+                racc[TH_SD_] += W * g.site[3 * g.stride + r];
+                racc[TH_NG_] += W * g.loc[12 * g.stride + r];
+            } else {
+                double da[GFAM], db[GFAM], dg;
+                pair_partials<MODE>(g, c, r, da, db, dg);
+                const double w2 = 2.0 * W;
+                for (int f = 0; f < GFAM; ++f) { racc[f] += w2 * db[f]; dcol[f] = w2 * da[f]; }
+                gacc += w2 * dg;
+            }
+        }
+        for (int f = 0; f < GFAM; ++f) {            // (every lane of the wave takes part: the loop is wave-uniform)
+            const double s = wave_sum(dcol[f]);
+            if (lane == 0) cols[cl][f] = s;
+        }
+    }
+    for (int f = 0; f < GFAM; ++f) rows[wave][lane][f] = racc[f];
+    const double gw = wave_sum(gacc);
+    if (lane == 0) red[wave] = gw;
+    __syncthreads();
+    const size_t tile = (size_t)bi * (bi + 1) / 2 + bj;
+    double *prow = g.part_row + tile * GFAM * GTS, *pcol = g.part_col + tile * GFAM * GTS;
+    for (int e = threadIdx.x; e < GFAM * GTS; e += 256) {
+        const int f = e / GTS, l = e % GTS;
+        prow[e] = ((rows[0][l][f] + rows[1][l][f]) + rows[2][l][f]) + rows[3][l][f];
+        pcol[e] = cols[l][f];
+    }
+    if (threadIdx.x == 0) g.part_glob[tile] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// g[f][i] for every site: its tile row's row sums, then its tile column's column sums, in tile order.  rsum[i] = sum_c A(i, c).
+__global__ void __launch_bounds__(256)
+grad_reduce_kernel(GradArgs g)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int T = g.npad / GTS;
+    if (i >= g.npad) return;
+    const int t = i / GTS, l = i % GTS;
+    for (int f = 0; f < GFAM; ++f) {
+        double s = 0.0;
+        for (int bj = 0; bj <= t; ++bj) s += g.part_row[((size_t)t * (t + 1) / 2 + bj) * GFAM * GTS + f * GTS + l];
+        for (int bi = t; bi < T; ++bi) s += g.part_col[((size_t)bi * (bi + 1) / 2 + t) * GFAM * GTS + f * GTS + l];
+        g.gsite[(size_t)f * g.npad + i] = s;
+    }
+    double a = 0.0;
+    for (int k = 0; k < g.nr; ++k) a += g.AR[(size_t)i + (size_t)k * g.ldar];
+    g.gsite[(size_t)GFAM * g.npad + i] = a;
+}
+
+__device__ double block_sum256(double v, double *red)
+{
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// out[t p + k] = c_{t,k} sum_i X(i, k) g_t(i)  (t < 6; c = 2 for scale k >= 1, 0 for scale k = 0 which takes the global
+// sum instead, 1 otherwise); out[6 p + k] = -2 sum_i X(i, k) rsum(i).  One workgroup per output.
+__global__ void __launch_bounds__(256)
+grad_xt_kernel(GradArgs g)
+{
+    __shared__ double red[256];
+    const int o = blockIdx.x, p = g.p;
+    const int t = o / p, k = o % p;
+    double s = 0.0;
+    if (t == TH_SCALE_ && k == 0) {
+        const int T = g.npad / GTS;
+        const size_t ntile = (size_t)T * (T + 1) / 2;
+        for (size_t e = threadIdx.x; e < ntile; e += 256) s += g.part_glob[e];
+    } else {
+        const double *gv = g.gsite + (size_t)(t < GFAM ? t : GFAM) * g.npad;
+        for (int i = g.pad0 + threadIdx.x; i < g.n; i += 256) s = fma(g.X[(size_t)i + (size_t)k * g.ldx], gv[i], s);
+    }
+    s = block_sum256(s, red);
+    if (threadIdx.x == 0) {
+        double c = 1.0;
+        if (t == TH_SCALE_ && k > 0) c = 2.0;
+        if (t == GFAM) c = -2.0;
+        g.out[o] = c * s;
+    }
+}
+
+void launch_grad_pairs(int mode, const GradArgs &g, hipStream_t s)
+{
+    const int T = g.npad / GTS;
+    dim3 grid(T, T), blk(256);
+    switch (mode) {
+    case MODE_HALF: hipLaunchKernelGGL(grad_pair_kernel<MODE_HALF>, grid, blk, 0, s, g); break;
+    case MODE_THREEHALF: hipLaunchKernelGGL(grad_pair_kernel<MODE_THREEHALF>, grid, blk, 0, s, g); break;
+    case MODE_FIVEHALF: hipLaunchKernelGGL(grad_pair_kernel<MODE_FIVEHALF>, grid, blk, 0, s, g); break;
+    default: hipLaunchKernelGGL(grad_pair_kernel<MODE_GEOM>, grid, blk, 0, s, g); break;
+    }
+    hipLaunchKernelGGL(grad_reduce_kernel, dim3((g.npad + 255) / 256), dim3(256), 0, s, g);
+    hipLaunchKernelGGL(grad_xt_kernel, dim3(7 * g.p), dim3(256), 0, s, g);
+}
+
+size_t grad_scratch_doubles(int npad)
+{
+    const size_t T = (size_t)npad / GTS, ntile = T * (T + 1) / 2;
+    return 2 * ntile * GFAM * GTS + ntile + (size_t)(GFAM + 1) * npad;
+}
+
+}  // namespace cocons

@@ -286,4 +286,34 @@ void launch_krige_solve(const double *Lp, const double *Qp, const double *w, int
 // out[i + s ldo] = Y[pos[i] + s ldy] for i < n, s < ncol
 void launch_gather_rows(const double *Y, int ldy, const int *pos, int n, int ncol, double *out, int ldo, hipStream_t s);
 
+// ---- analytic gradient of the dense -2 log-likelihood (grad.hip) ----------------------------------------------------------
+constexpr int GSITE_FIELDS = 4;    // launch_grad_site: dtilt/deta, cot(tilt), dlog(nu_ij)/deta_smooth, exp(eta_sd)
+struct GradArgs {
+    int n, pad0, npad, p;          // internal order: sites [pad0, n) are the caller's
+    const double *S; size_t lds;   // -Sigma^-1, lower triangle (launch_grad_syrk)
+    const double *AR; size_t ldar; int nr;    // A = Sigma^-1 R, npad x nr
+    const double *loc; size_t stride;         // loc_params_kernel's SoA
+    const double *site;                       // launch_grad_site's SoA (GSITE_FIELDS x stride)
+    const double *X; int ldx;
+    double gr, nu_fixed;
+    int smooth_free;               // the smoothness varies (logistic branch with hi > lo): the smooth row is formed
+    double *part_row, *part_col, *part_glob, *gsite;   // scratch: grad_scratch_doubles(npad), in this order
+    double *out;                   // 6 p theta-table gradient (row-major) then p mean gradient
+};
+// rows [row0, row0 + nrows) x columns [0, ncols) of A: the unit vectors e_(row - row_id)' (row_id < 0: zeros)
+void launch_grad_fill(double *A, size_t lda, int row0, int nrows, int ncols, int row_id, hipStream_t s);
+// AR (npad x nr) = B W', B = the npad solved rows from brow0 (L^-T), W = the nr solved rows from wrow0 (L^-1 R)';
+// part: grad_sigma_r_scratch_doubles(npad, nr) doubles
+size_t grad_sigma_r_scratch_doubles(int npad, int nr);
+void launch_grad_sigma_r(const double *A, size_t lda, int npad, int wrow0, int nr, int brow0, double *part, double *AR,
+                         hipStream_t s);
+// the leading npad x npad square of A (lower tiles, zero beforehand) -= B B', B = rows brow0.. (upper triangular)
+void launch_grad_syrk(double *A, size_t lda, int npad, int brow0, hipStream_t s);
+void launch_grad_site(const LocArgs &a, double *out, size_t stride, int smooth_free, hipStream_t s);
+size_t grad_scratch_doubles(int npad);
+// pair contraction, per-site sums and X' g into g.out (7 p doubles)
+void launch_grad_pairs(int mode, const GradArgs &g, hipStream_t s);
+// out[i], out[n + i], out[2 n + i] = M, dM/du, dM/dnu of the gradient's device code
+void launch_matern_grad_points(int n, const double *nu, const double *u, double *out, hipStream_t s);
+
 }  // namespace cocons

@@ -54,6 +54,66 @@ GetNeg2loglikelihood <- function(theta, par.pos, locs, x_covariates, smooth.limi
   val + .cocons.getPen(n * dim(as.matrix(z))[2], lambda, theta_list, smooth.limits)          # :220
 }
 
+# value and analytic gradient of the -2 log-likelihood core (no penalty): list(value, table = 6 x p gradient over
+# std.dev, scale, aniso, tilt, smooth, nugget as getModelLists(type = "diff") gives them, mean = gradient over theta$mean);
+# NULL after a failing Cholesky under safe.  INTEGRATION.md shows the gr = of cocoOptim built on it.
+.cocons.hip.neg2loglik.grad <- function(fit, theta_list, safe = TRUE) {
+  res <- .cocons.hip.result(.Call(`_cocons_hip_neg2loglik_grad`, fit, theta_list[-1], theta_list$mean), safe)
+  if (is.null(res)) return(NULL)
+  list(value = res[[1]], table = res[[2]], mean = res[[3]])
+}
+
+# derivative of sumsmoothlone (src/cocons_full.cpp:12-30) per element: sign(x) off the smooth branch, tanh(alpha x / 2) on it
+.cocons.hip.dsumsmoothlone <- function(x, lambda, alpha = 1e6) {
+  lambda * ifelse(abs(x) > 1e-4, sign(x), tanh(alpha * x / 2))
+}
+
+# d .cocons.getPen / d (entries of theta_list) (R/checkFunctions.R:474-492): a list shaped like theta_list
+.cocons.hip.getPen.grad <- function(n, lambda, theta_list, smooth.limits) {
+  g <- lapply(theta_list, function(v) numeric(length(v)))
+  span <- smooth.limits[2] - smooth.limits[1]
+  s <- 1 / (1 + exp(-theta_list$smooth[1]))
+  nu0 <- span * s + smooth.limits[1]
+  g$scale[1] <- g$scale[1] + lambda[3] * exp(theta_list$scale[1]) * sqrt(nu0)
+  g$smooth[1] <- g$smooth[1] + lambda[3] * exp(theta_list$scale[1]) * span * s * (1 - s) / (2 * sqrt(nu0))
+  for (ii in 1:6) {                               # names[1] with lambda[2], names[2:6] with lambda[1], as getPen
+    v <- theta_list[[ii]]
+    if (length(v) > 1)
+      g[[ii]][-1] <- g[[ii]][-1] + .cocons.hip.dsumsmoothlone(v[-1], if (ii == 1) lambda[2] else lambda[1])
+  }
+  lapply(g, function(v) 2 * n * v)
+}
+
+# chain rule through getModelLists(type = "diff") (R/getFunctions.R:570-616): gradient over the list entries -> gradient over
+# the optimiser's vector (where std.dev and scale are both free: d/d raw_sd = (g_sd + g_sc) / 2, d/d raw_sc = (g_sd - g_sc) / 2)
+.cocons.hip.diff.grad <- function(G, par.pos) {
+  if (is.logical(par.pos$std.dev) && is.logical(par.pos$scale)) {
+    both <- par.pos$std.dev & par.pos$scale
+    sd <- G$std.dev; sc <- G$scale
+    G$std.dev[both] <- (sd[both] + sc[both]) / 2
+    G$scale[both] <- (sd[both] - sc[both]) / 2
+  }
+  unlist(lapply(names(par.pos), function(k) {
+    pp <- par.pos[[k]]
+    if (is.logical(pp)) G[[k]][seq_along(pp)][pp] else NULL
+  }))
+}
+
+# gradient of GetNeg2loglikelihood over theta (the optimiser's vector): what cocoOptim can pass as `gr` (INTEGRATION.md);
+# zeros after a failing Cholesky under safe (where GetNeg2loglikelihood returns 1e6)
+GetNeg2loglikelihoodGrad <- function(theta, par.pos, locs, x_covariates, smooth.limits, z, n, lambda,
+                                     safe = TRUE, fit = NULL) {
+  theta_list <- cocons::getModelLists(theta = theta, par.pos = par.pos, type = "diff")
+  if (is.null(fit)) fit <- .cocons.hip.cached(locs, x_covariates, z, smooth.limits)
+  g <- .cocons.hip.neg2loglik.grad(fit, theta_list, safe)
+  if (is.null(g)) return(rep(0, length(theta)))
+  G <- .cocons.hip.getPen.grad(n * dim(as.matrix(z))[2], lambda, theta_list, smooth.limits)
+  G$mean <- G$mean + g$mean
+  aspects <- c("std.dev", "scale", "aniso", "tilt", "smooth", "nugget")
+  for (t in seq_along(aspects)) G[[aspects[t]]] <- G[[aspects[t]]] + g$table[t, ]
+  .cocons.hip.diff.grad(G, par.pos)
+}
+
 # the 1 + 2P points of one finite-difference gradient, or getHessian's 3P(P+1)/2 (R/getFunctions.R:979-1016)
 GetNeg2loglikelihoodBatch <- function(thetas, par.pos, locs, x_covariates, smooth.limits, z, n, lambda,
                                       safe = TRUE, fit = NULL) {

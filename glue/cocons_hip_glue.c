@@ -368,6 +368,31 @@ SEXP _cocons_hip_neg2loglik(SEXP fitp, SEXP theta, SEXP mean)
     return status_value(rc, Rf_ScalarReal(val));
 }
 
+/* value and analytic gradient (cocons_neg2loglik_grad_dense): list(status, list(value, grad_table 6 x p, grad_mean p)),
+ * the table's rows in the order std.dev, scale, aniso, tilt, smooth, nugget */
+SEXP _cocons_hip_neg2loglik_grad(SEXP fitp, SEXP theta, SEXP mean)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp);
+    double T[6 * COCONS_P_MAX], G[6 * COCONS_P_MAX] = {0}, val = NA_REAL;
+    theta_table(theta, p, T);
+    if (XLENGTH(mean) != p) Rf_error("theta$mean must have length %d", p);
+    SEXP gt = PROTECT(Rf_allocMatrix(REALSXP, 6, p));
+    SEXP gm = PROTECT(Rf_allocVector(REALSXP, p));
+    for (int k = 0; k < p; ++k) REAL(gm)[k] = 0.0;
+    int rc = cocons_neg2loglik_grad_dense(f, T, REAL(mean), &val, NULL, G, REAL(gm));
+    hip_check(rc, "GetNeg2loglikelihood (gradient)");
+    for (int t = 0; t < 6; ++t)         /* (a failing minor writes nothing: G stays zero) */
+        for (int k = 0; k < p; ++k) REAL(gt)[t + 6 * k] = G[t * p + k];
+    SEXP res = PROTECT(Rf_allocVector(VECSXP, 3));
+    SET_VECTOR_ELT(res, 0, Rf_ScalarReal(val));
+    SET_VECTOR_ELT(res, 1, gt);
+    SET_VECTOR_ELT(res, 2, gm);
+    SEXP out = status_value(rc, res);
+    UNPROTECT(3);
+    return out;
+}
+
 /* the same with its parts: list(status, c(sum_logliks, logdet_half, quad_1 .. quad_r)) -- what
  * GetNeg2loglikelihoodTaperProfile (R/neg2loglikelihood.R:98-106) is formed from on a taper handle */
 SEXP _cocons_hip_neg2loglik_parts(SEXP fitp, SEXP theta, SEXP mean)
@@ -680,6 +705,7 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_fit_close", (DL_FUNC)&_cocons_hip_fit_close, 1},
     {"_cocons_hip_neg2loglik_parts", (DL_FUNC)&_cocons_hip_neg2loglik_parts, 3},
     {"_cocons_hip_neg2loglik", (DL_FUNC)&_cocons_hip_neg2loglik, 3},
+    {"_cocons_hip_neg2loglik_grad", (DL_FUNC)&_cocons_hip_neg2loglik_grad, 3},
     {"_cocons_hip_neg2loglik_batch", (DL_FUNC)&_cocons_hip_neg2loglik_batch, 3},
     {"_cocons_hip_neg2loglik_profile", (DL_FUNC)&_cocons_hip_neg2loglik_profile, 2},
     {"_cocons_hip_neg2loglik_reml", (DL_FUNC)&_cocons_hip_neg2loglik_reml, 3},

@@ -163,6 +163,18 @@ void cocons_fit_destroy(cocons_fit *fit);
 int cocons_neg2loglik_dense(cocons_fit *fit, const double *theta, const double *mean,
                             double *sum_logliks, double *parts);
 
+/* The value of cocons_neg2loglik_dense and its analytic gradient in one call: sum_logliks and parts as
+ * there, grad_theta[t * p + k] = d sum_logliks / d theta[t * p + k] (6 x p, the table layout of theta: std.dev, scale,
+ * aniso, tilt, smooth, nugget, as the kernels see them) and grad_mean[k] = d sum_logliks / d mean[k].  One factorisation
+ * with the identity bordered under Sigma (L^-T beside L^-1 R), Sigma^-1 from it, one pass over the pairs; the sums have
+ * a fixed order, so repeated calls agree bit for bit.  0, the failing minor k > 0 (no output written), or < 0 with a
+ * message.  Refused (-1) on taper and sharded handles and on a handle without z.  The first call grows the handle's
+ * matrix allocation once by n_pad^2 doubles (n_pad = n rounded up to 128), kept for the handle's lifetime; the
+ * objective's own layout (its leading dimension, the second buffer of its factorisation schedule) does not change.   */
+int cocons_neg2loglik_grad_dense(cocons_fit *fit, const double *theta, const double *mean,
+                                 double *sum_logliks, double *parts,
+                                 double *grad_theta, double *grad_mean);
+
 /* Batch of nb independent evaluations of the same fit (the 1 + 2P points of one
  * finite-difference gradient, R/optim.R:237-259 with R/profile.R:11-12; getHessian's
  * 3 P (P+1)/2 points, R/getFunctions.R:979-1016).  thetas: nb x (6 p) row-major tables,

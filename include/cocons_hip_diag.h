@@ -20,6 +20,17 @@ extern "C" {
  * tests/golden/besselk_grid.json (host arrays in, host array out).                    */
 int cocons_debug_matern(int n, const double *nu, const double *u, double *out);
 
+/* Diagnostics of cocons_neg2loglik_grad_dense: the lower triangle of the Sigma(theta)^-1 the gradient uses, in the caller's
+ * observation order (n x n column-major host array, zeros above the diagonal; 0, a failing minor k > 0, or < 0), and
+ * M, dM/du, dM/dnu of the gradient's device routine at n points (out3n[i], out3n[n + i], out3n[2 n + i]; dM/dnu by a
+ * four-point central difference in nu; u >= 706: the reference's stand-in for M, zero derivatives).                */
+int cocons_debug_sigma_inverse(struct cocons_fit *fit, const double *theta, double *out_nxn);
+int cocons_debug_matern_grad(int n, const double *nu, const double *u, double *out3n);
+
+/* Device memory of a dense handle: out4 = { bytes allocated for the matrix buffer, bytes of the dependency-driven schedule's
+ * second buffer, bytes of the gradient's scratch, the leading dimension the objective's matrix uses }.              */
+int cocons_debug_fit_memory(struct cocons_fit *fit, long long *out4);
+
 /* Schedule switches of the factorisation, settable at run time (the library reads the COCONS_* environment variables
  * of the same meaning once per process; DESIGN.md section 6 lists them): "engine", "engine_block0", "engine_pair", "panel_fused", "panel_follow",
  * "panel_diag", "panel_split", "potrf_follow", "upd_dynamic", "upd_waves", "w8_max_tiles", "dag", "dag_min_tiles", "dag_split",

@@ -1,0 +1,341 @@
+"""Analytic gradient of the dense -2 log-likelihood on the GPU (cocons_neg2loglik_grad_dense): against the numpy / scipy
+statement (tests/grad_reference.py), against the GPU's own Richardson differences, an exact scaling identity, the mean
+gradient, the value, bit-identical repeats, fixed smoothness, odd sizes, failing minors, the krige state, refusals and
+the diagnostics (Sigma^-1, Matern partials)."""
+import ctypes
+import os
+import sys
+from collections import OrderedDict
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import grad_reference as GR  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+
+def _setup(n, r, seed=3, mean=(0.3, -0.15, 0.2), coincident=False):
+    from cocons_amd import workloads as wl
+    rng = np.random.default_rng(seed)
+    locs = rng.uniform(0, 1, size=(n, 2))
+    if coincident:
+        locs[7] = locs[3]
+    X = wl.design_from_locs(locs)["std.covs"]
+    if coincident:
+        X[7] = X[3] + [0.0, 0.5, 0.5]
+    th = wl.theta_full(scale0=np.log(0.2))
+    th["mean"] = np.array(mean, dtype=float)
+    z = rng.standard_normal((n, r))
+    return locs, X, th, z
+
+
+def _fit(locs, X, z, sl=None):
+    from cocons_amd import CoconsFit, workloads as wl
+    return CoconsFit(locs, X, z, wl.SMOOTH_LIMITS if sl is None else sl)
+
+
+def _inf(a):
+    return float(np.max(np.abs(a)))
+
+
+@pytest.mark.parametrize("n,r", [(300, 1), (300, 3), (2116, 1), (2116, 3)])
+def test_against_reference(n, r):
+    from cocons_amd import host, workloads as wl
+    locs, X, th, z = _setup(n, r, coincident=(n == 300))
+    fit = _fit(locs, X, z)
+    try:
+        val, parts, gt, gm = fit.neg2loglik_grad_core(th)
+    finally:
+        fit.close()
+    f, rgt, rgm = GR.neg2loglik_grad(host.theta_table(th), th["mean"], locs, X, z, wl.SMOOTH_LIMITS)
+    assert abs(val - f) <= 1e-10 * abs(f)
+    g = np.concatenate([gt.ravel(), gm])
+    rg = np.concatenate([rgt.ravel(), rgm])
+    assert _inf(g - rg) <= 1e-7 * _inf(rg), (_inf(g - rg), _inf(rg))
+
+
+@pytest.mark.parametrize("n", [2116, 4096])
+def test_against_gpu_richardson(n):
+    from cocons_amd import host
+    locs, X, th, z = _setup(n, 1, seed=5)
+    fit = _fit(locs, X, z)
+    try:
+        val, parts, gt, gm = fit.neg2loglik_grad_core(th)
+        T0, m0 = host.theta_table(th), np.array(th["mean"], float)
+        h = 1e-4
+        pts = []
+        for t in range(7):
+            for k in range(3):
+                for s in (h, -h, h / 2, -h / 2):
+                    tl = OrderedDict((kk, np.array(v, float)) for kk, v in th.items())
+                    if t < 6:
+                        tl[host.COV_ASPECTS[t]][k] += s
+                    else:
+                        tl["mean"][k] += s
+                    pts.append(tl)
+        vals, st = fit.neg2loglik_batch_core(pts)
+        assert np.all(st == 0)
+    finally:
+        fit.close()
+    v = vals.reshape(21, 4)
+    num = (4 * (v[:, 2] - v[:, 3]) / h - (v[:, 0] - v[:, 1]) / (2 * h)) / 3
+    ana = np.concatenate([gt.ravel(), gm])
+    assert _inf(ana - num) <= 1e-6 * _inf(num), (ana, num)
+
+
+@pytest.mark.parametrize("n,tol", [(2116, 1e-9), (10000, 1e-8)])
+def test_scaling_identity(n, tol):
+    """Sigma(sd0 + d, ng0 + d) = e^d Sigma: d f / d sd0 + d f / d ng0 = r n - sum_c quadform_c."""
+    locs, X, th, z = _setup(n, 1, seed=9)
+    fit = _fit(locs, X, z)
+    try:
+        val, parts, gt, gm = fit.neg2loglik_grad_core(th)
+    finally:
+        fit.close()
+    lhs = gt[0, 0] + gt[5, 0]
+    rhs = 1 * n - np.sum(parts[1:])
+    assert abs(lhs - rhs) <= tol * n, (lhs, rhs)
+
+
+def test_mean_gradient_value_parts_and_repeats(oracle):
+    from cocons_amd import workloads as wl
+    n, r = 300, 2
+    locs, X, th, z = _setup(n, r)
+    fit = _fit(locs, X, z)
+    try:
+        val, parts, gt, gm = fit.neg2loglik_grad_core(th)
+        val2, parts2, gt2, gm2 = fit.neg2loglik_grad_core(th)
+        dval, dparts = fit.neg2loglik_core(th)
+    finally:
+        fit.close()
+    S = oracle.cov_rns(th, locs, X, wl.SMOOTH_LIMITS)
+    R = z - (X @ th["mean"])[:, None]
+    want = -2 * X.T @ np.linalg.solve(S, R).sum(axis=1)
+    assert _inf(gm - want) <= 1e-10 * max(1.0, _inf(want))
+    assert abs(val - dval) <= 1e-12 * abs(dval)
+    assert np.max(np.abs(parts - dparts) / np.abs(dparts)) <= 1e-12
+    assert val == val2 and np.array_equal(parts, parts2)
+    assert np.array_equal(gt, gt2) and np.array_equal(gm, gm2)
+
+
+@pytest.mark.parametrize("nu", [0.5, 1.5, 2.5, 1.0])
+def test_fixed_smoothness(nu):
+    from cocons_amd import host
+    n = 300
+    locs, X, th, z = _setup(n, 1)
+    th["smooth"] = np.zeros(3)
+    sl = (nu, nu)
+    if nu == 1.0:                   # hi == lo on the general branch: a varying smooth vector with zero span
+        th["smooth"] = np.array([0.0, 0.5, -0.5])
+    fit = _fit(locs, X, z, sl)
+    try:
+        val, parts, gt, gm = fit.neg2loglik_grad_core(th)
+    finally:
+        fit.close()
+    assert np.all(gt[4] == 0.0)
+    f, rgt, rgm = GR.neg2loglik_grad(host.theta_table(th), th["mean"], locs, X, z, sl)
+    g, rg = np.concatenate([gt.ravel(), gm]), np.concatenate([rgt.ravel(), rgm])
+    assert _inf(g - rg) <= 1e-7 * _inf(rg), (g, rg)
+
+
+@pytest.mark.parametrize("n", [1000, 2117])
+def test_odd_sizes(n):
+    from cocons_amd import host, workloads as wl
+    locs, X, th, z = _setup(n, 1)
+    fit = _fit(locs, X, z)
+    try:
+        val, parts, gt, gm = fit.neg2loglik_grad_core(th)
+    finally:
+        fit.close()
+    f, rgt, rgm = GR.neg2loglik_grad(host.theta_table(th), th["mean"], locs, X, z, wl.SMOOTH_LIMITS)
+    g, rg = np.concatenate([gt.ravel(), gm]), np.concatenate([rgt.ravel(), rgm])
+    assert _inf(g - rg) <= 1e-7 * _inf(rg)
+
+
+def test_failing_minor_then_success_and_krige_untouched():
+    from cocons_amd import CholeskyError, _lib
+    from cocons_amd.host import _p, theta_table
+    n = 1000
+    locs, X, th, z = _setup(n, 1)
+    fit = _fit(locs, X, z)
+    try:
+        fit.krige_prepare(th)
+        rng = np.random.default_rng(1)
+        lp = rng.uniform(0, 1, size=(200, 2))
+        from cocons_amd import workloads as wl
+        Xp = wl.design_from_locs(lp)["std.covs"]
+        s0, q0 = fit.krige_core(lp, Xp)
+        bad = OrderedDict((k, np.array(v, float)) for k, v in th.items())
+        bad["nugget"] = np.array([-np.inf, 0.0, 0.0])
+        bad["scale"][0] = np.log(50.0)             # a near-constant covariance without nugget: not positive definite
+        T = theta_table(bad)
+        mean = np.ascontiguousarray(bad["mean"])
+        val = ctypes.c_double(7.0)
+        parts = np.full(2, 7.0)
+        gt, gm = np.full(18, 7.0), np.full(3, 7.0)
+        rc = fit._L.cocons_neg2loglik_grad_dense(fit._h, _p(T), _p(mean), ctypes.byref(val), _p(parts), _p(gt), _p(gm))
+        assert rc > 0
+        assert val.value == 7.0 and np.all(parts == 7.0) and np.all(gt == 7.0) and np.all(gm == 7.0)
+        with pytest.raises(CholeskyError):
+            fit.neg2loglik_grad_core(bad)
+        v1 = fit.neg2loglik_grad_core(th)
+        v0, _ = fit.neg2loglik_core(th)
+        assert abs(v1[0] - v0) <= 1e-12 * abs(v0)
+        s1, q1 = fit.krige_core(lp, Xp)
+        assert np.array_equal(s0, s1) and np.array_equal(q0, q1)
+        assert _lib is not None
+    finally:
+        fit.close()
+
+
+def test_taper_and_sharded_handles_refused():
+    from cocons_amd import CoconsTaperFit, workloads as wl, _lib
+    from cocons_amd.host import _p, theta_table
+    n = 200
+    locs, X, th, z = _setup(n, 1)
+    ci = np.arange(1, n + 1, dtype=np.int32)
+    rp = np.arange(1, n + 2, dtype=np.int32)
+    tf = CoconsTaperFit(locs, X, z, wl.SMOOTH_LIMITS, ci, rp, np.ones(n))
+    T, mean = theta_table(th), np.ascontiguousarray(th["mean"])
+    val, parts, gt, gm = ctypes.c_double(0), np.zeros(2), np.zeros(18), np.zeros(3)
+    try:
+        rc = tf._L.cocons_neg2loglik_grad_dense(tf._h, _p(T), _p(mean), ctypes.byref(val), _p(parts), _p(gt), _p(gm))
+        assert rc == -1 and "cocons_neg2loglik_grad_dense" in _lib.last_error()
+    finally:
+        tf.close()
+    fit = _fit(locs, X, z)
+    try:
+        L = fit._L
+        noop_b = _lib.BCAST_FN(lambda *a: 0)
+        noop_r = _lib.ALLREDUCE_FN(lambda *a: 0)
+        assert L.cocons_fit_set_collectives(fit._h, 0, 2, ctypes.cast(noop_b, ctypes.c_void_p),
+                                            ctypes.cast(noop_r, ctypes.c_void_p), None) == 0
+        rc = L.cocons_neg2loglik_grad_dense(fit._h, _p(T), _p(mean), ctypes.byref(val), _p(parts), _p(gt), _p(gm))
+        assert rc == -1 and "sharded" in _lib.last_error()
+    finally:
+        fit.close()
+
+
+def test_debug_matern_grad():
+    from scipy import special
+    from cocons_amd import _lib
+    D = _lib.load()
+    nus = np.linspace(0.5, 2.5, 17)
+    us = np.concatenate([np.geomspace(1e-3, 700, 60), [1.999, 2.0, 2.001, 19.99, 20.0, 20.01]])
+    NU, U = np.meshgrid(nus, us)
+    NU, U = np.ascontiguousarray(NU.ravel()), np.ascontiguousarray(U.ravel())
+    out = np.zeros(3 * NU.size)
+    dp = _lib.c_dp
+    assert D.cocons_debug_matern_grad(NU.size, NU.ctypes.data_as(dp), U.ctypes.data_as(dp), out.ctypes.data_as(dp)) == 0
+    M, Mu, Mn = out.reshape(3, -1)
+    rM, rMu, rMn = GR.matern_and_partials(NU, U)
+    scale = np.maximum(np.abs(rM), np.maximum(np.abs(rMu), np.abs(rMn)))
+    mask = scale > 1e-290
+    for got, want in ((M, rM), (Mu, rMu), (Mn, rMn)):
+        err = np.abs(got - want)[mask] / scale[mask]
+        assert np.max(err) <= 1e-8, (np.max(err), NU[mask][np.argmax(err)], U[mask][np.argmax(err)])
+    assert special is not None
+
+
+@pytest.mark.parametrize("n", [1000, 2116])
+def test_debug_sigma_inverse(oracle, n):
+    from cocons_amd import _lib
+    from cocons_amd.host import _p, theta_table
+    from cocons_amd import workloads as wl
+    locs, X, th, z = _setup(n, 1)
+    fit = _fit(locs, X, z)
+    try:
+        out = np.zeros((n, n), order="F")
+        T = theta_table(th)
+        assert fit._L.cocons_debug_sigma_inverse(fit._h, _p(T), out.ctypes.data_as(_lib.c_dp)) == 0
+    finally:
+        fit.close()
+    S = oracle.cov_rns(th, locs, X, wl.SMOOTH_LIMITS)
+    want = np.tril(np.linalg.inv(S))
+    assert _inf(out - want) <= 1e-10 * _inf(want)
+
+
+def test_host_entry_value_penalty_and_safe_paths():
+    """host.GetNeg2loglikelihood_grad: value against GetNeg2loglikelihood, gradient (penalty and diff chain rule included,
+    lambda != 0) against Richardson differences of it, and the (1e6, zeros) / RuntimeError paths of a failing Cholesky."""
+    from cocons_amd import host, workloads as wl
+    n = 300
+    locs, X, th, z = _setup(n, 1, mean=(0.0, 0.0, 0.0))
+    z = z[:, 0]
+    pp = wl.par_pos_full()
+    x0 = wl.theta_vector_from_lists(th, pp)
+    lam = (0.05, 0.02, 0.3)
+    fit = _fit(locs, X, z)
+    try:
+        def val(x):
+            return host.GetNeg2loglikelihood(x, pp, locs, X, wl.SMOOTH_LIMITS, z, n, lam, safe=False, fit=fit)
+
+        v, g = host.GetNeg2loglikelihood_grad(x0, pp, locs, X, wl.SMOOTH_LIMITS, z, n, lam, safe=False, fit=fit)
+        assert abs(v - val(x0)) <= 1e-12 * abs(v)
+        h = 1e-4
+        num = np.zeros_like(x0)
+        for i in range(x0.size):
+            def d(step):
+                xp, xm = x0.copy(), x0.copy()
+                xp[i] += step
+                xm[i] -= step
+                return (val(xp) - val(xm)) / (2 * step)
+            num[i] = (4 * d(h / 2) - d(h)) / 3
+        assert g.shape == x0.shape
+        assert _inf(g - num) <= 1e-6 * _inf(num), (g, num)
+    finally:
+        fit.close()
+    # a covariance without nugget and with a range far beyond the domain: not positive definite in floating point at
+    # n = 1000 (the problem of test_failing_minor_then_success_and_krige_untouched)
+    n = 1000
+    locs, X, th, z = _setup(n, 1)
+    bad = OrderedDict((k, np.array(v_, float)) for k, v_ in th.items())
+    bad["nugget"] = np.array([-np.inf, 0.0, 0.0])
+    bad["scale"][0] = np.log(50.0)
+    xb = wl.theta_vector_from_lists(bad, pp)
+    fit = _fit(locs, X, z)
+    try:
+        vb, gb = host.GetNeg2loglikelihood_grad(xb, pp, locs, X, wl.SMOOTH_LIMITS, z, n, lam, fit=fit)
+        assert vb == 1e6 and gb.shape == xb.shape and np.all(gb == 0)
+        with pytest.raises(RuntimeError, match="Cholesky error"):
+            host.GetNeg2loglikelihood_grad(xb, pp, locs, X, wl.SMOOTH_LIMITS, z, n, lam, safe=False, fit=fit)
+    finally:
+        fit.close()
+
+
+def _fit_memory(fit):
+    out = (ctypes.c_longlong * 4)()
+    assert fit._L.cocons_debug_fit_memory(fit._h, out) == 0
+    return list(out)
+
+
+def test_memory_and_objective_across_gradient_calls():
+    """A gradient call grows the matrix allocation once, by the n_pad^2 of its unit rows, and moves nothing else: the
+    objective keeps its leading dimension, the DAG schedule's second buffer keeps its size, and the objective's value is
+    bit-identical before and after, whatever the order of objective and gradient calls."""
+    n = 4096
+    locs, X, th, z = _setup(n, 1, seed=4)
+    npad = (n + 127) // 128 * 128
+    fit = _fit(locs, X, z)
+    try:
+        v0, p0 = fit.neg2loglik_core(th)
+        m0 = _fit_memory(fit)
+        assert m0[1] > 0                               # the objective ran on the dependency-driven schedule
+        fit.neg2loglik_grad_core(th)
+        m1 = _fit_memory(fit)
+        v1, p1 = fit.neg2loglik_core(th)
+        m2 = _fit_memory(fit)
+        g2 = fit.neg2loglik_grad_core(th)
+        v3, p3 = fit.neg2loglik_core(th)
+        m3 = _fit_memory(fit)
+    finally:
+        fit.close()
+    assert v1 == v0 and v3 == v0 and np.array_equal(p1, p0) and np.array_equal(p3, p0)
+    assert m1 == m2 == m3
+    assert m1[3] == m0[3] and m1[1] == m0[1]             # lda and dP unchanged
+    grown = m1[0] - m0[0]
+    assert 0 < grown <= npad * npad * 8, (grown, npad * npad * 8)
+    assert m1[2] <= 0.2 * npad * npad * 8               # the gradient's scratch: per-tile partial sums
+    assert g2[0] > 0
