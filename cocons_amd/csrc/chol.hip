@@ -34,6 +34,8 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 // the same with the first operand negated: for the fp64 forms the instruction's blgp field holds NEG bits
 // (neg:[a,b,c]; bit 0 = first source), so D = C - A B costs no extra instruction
 #define MFMA64_NEGA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 1)
+// LDS address space: the destination of global_load_lds (LDS-DMA)
+#define LDS_T __attribute__((address_space(3)))
 
 __device__ __forceinline__ void blk_mma(d4 &acc, const d4 &P, const d4 &Q)
 {
@@ -1991,12 +1993,11 @@ __device__ __forceinline__ bool dag_wait(const DagArgs &a, unsigned *word, unsig
 __global__ void __launch_bounds__(256, 8)
 dag_kernel(DagArgs a)
 {
-    constexpr int TM = 64, KC = 8, LDT = TM + 16, TPC = 256 / KC, RPT = TM / TPC;
-    static_assert(RPT == 2, "one 16-byte load per thread, side and chunk");
-    typedef double d2 __attribute__((ext_vector_type(2)));
-    __shared__ double sI[2][KC * LDT];
-    __shared__ double sJ[2][KC * LDT];
-    unsigned *share = (unsigned *)&sI[0][TM];          // (padding of the first staged column: see update_kernel)
+    constexpr int TM = 64, KC = 4, RING = 4, STG = 2 * KC * TM;   // a stage: KC columns of I, then of J (4 KB)
+    // ONE __shared__ array (a second object beside the LDS-DMA ring can make the compiler wait for every DMA in flight
+    // before each LDS read): the ring, then the control words
+    __shared__ double smem[RING * STG + 2];
+    unsigned *share = (unsigned *)&smem[RING * STG];
     const int tid = threadIdx.x;
     const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);
     const DagStep *__restrict__ steps = a.steps;
@@ -2209,50 +2210,65 @@ dag_kernel(DagArgs a)
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
         const int wave = wave_s, t2 = 64 * wave + lane;
         const int wi = wave & 1, wj = wave >> 1;
-        const int kc = t2 / TPC, rg = (t2 % TPC) * RPT;
-        const int ro = (lane >> 4) * LDT + (lane & 15);
-        const char *pI = (const char *)gIb + (8u * (unsigned)rg + (unsigned)kc * ldib);
-        const char *pJ = (const char *)gJb + (8u * (unsigned)rg + (unsigned)kc * ldjb);
-        const unsigned cIb = (unsigned)KC * ldib, cJb = (unsigned)KC * ldjb;
-        const int nch = K / KC;
-        d2 stI, stJ;
+        // ---- the product acc = sum_k I(:, k) J(:, k)^T, streamed through a ring of RING stages of KC panel columns by
+        // LDS-DMA (global_load_lds: no registers, no LDS writes, no barrier that drains the loads): while stage ch is
+        // multiplied, stages ch + 1 .. ch + RING - 1 are in flight -- 12 columns instead of the 8 of one register-staged
+        // chunk.  A stage holds columns of 64 doubles (I's KC, then J's KC); wave w fills columns 2 (w & 1), +1 of operand
+        // w >> 1 with ONE 16-byte-per-lane DMA: lane l writes doubles 2 (l & 31), +1 of column l >> 5.  The image is
+        // lane-linear, so the swizzle that keeps the MFMA operand reads free of bank conflicts without padding goes on the
+        // SOURCE: odd columns hold row r at position r ^ 16 (lanes l and l + 16 read columns k and k + 1 of the same 16
+        // rows: 32 banks apart).  i_wt operands keep their loads' L1 bypass (aux 16: sc1, as load_wt).
+        const bool opJ = wave >= 2;
+        const char *gsrc = opJ ? (const char *)gJb : (const char *)gIb;
+        const unsigned ldg = opJ ? ldjb : ldib, cstep = (unsigned)KC * ldg;
+        const bool wt = i_wt && !opJ;
+        const int sc = (lane >> 5) & 1;
+        const char *src = gsrc + ((unsigned)(2 * (wave & 1) + sc) * ldg + 8u * (unsigned)((2 * (lane & 31)) ^ (16 * sc)));
+        LDS_T double *ldst = (LDS_T double *)(smem + 128 * wave);
+        const int nch = K / KC;                              // 16, 32 or 64: a multiple of the ring
+#define DAG_STAGE(slot)                                                                                                     \
+        do {                                                                                                                \
+            if (wt) __builtin_amdgcn_global_load_lds((const void *)src, (LDS_T void *)(ldst + STG * (slot)), 16, 0, 16);   \
+            else __builtin_amdgcn_global_load_lds((const void *)src, (LDS_T void *)(ldst + STG * (slot)), 16, 0, 0);       \
+            src += cstep;                                                                                                   \
+        } while (0)
+        // operand reads: lane l takes column l >> 4 of the stage, rows (l & 15) + 32 wi (I) / 32 wj (J), + 16 for the
+        // second block -- at the swizzled positions
+        const int kq = lane >> 4, kodd = kq & 1, rl = (lane & 15) + TM * kq;
+        const int aI0 = rl + (TM / 2) * wi + 16 * kodd, aI1 = rl + (TM / 2) * wi + 16 * (kodd ^ 1);
+        const int aJ0 = KC * TM + rl + (TM / 2) * wj + 16 * kodd, aJ1 = KC * TM + rl + (TM / 2) * wj + 16 * (kodd ^ 1);
         d4 acc[2][2];
 #pragma unroll
         for (int x = 0; x < 2; ++x)
 #pragma unroll
             for (int y = 0; y < 2; ++y) acc[x][y] = (d4){0.0, 0.0, 0.0, 0.0};
-        if (i_wt) { stI[0] = load_wt((const double *)pI); stI[1] = load_wt((const double *)pI + 1); }
-        else stI = *(const d2 *)pI;
-        stJ = *(const d2 *)pJ;
-        *(d2 *)(&sI[0][kc * LDT + rg]) = stI;
-        *(d2 *)(&sJ[0][kc * LDT + rg]) = stJ;
-        __syncthreads();
-        for (int ch = 0; ch < nch; ++ch) {
-            const int cur = ch & 1;
-            if (ch + 1 < nch) {
-                const char *qI = pI + (unsigned)(ch + 1) * cIb;
-                const char *qJ = pJ + (unsigned)(ch + 1) * cJb;
-                if (i_wt) { stI[0] = load_wt((const double *)qI); stI[1] = load_wt((const double *)qI + 1); }
-                else stI = *(const d2 *)qI;
-                stJ = *(const d2 *)qJ;
-            }
-            const double *bI = &sI[cur][ro + (TM / 2) * wi];
-            const double *bJ = &sJ[cur][ro + (TM / 2) * wj];
+        DAG_STAGE(0);
+        DAG_STAGE(1);
+        DAG_STAGE(2);
+        for (int c0 = 0; c0 < nch; c0 += RING) {
 #pragma unroll
-            for (int k4 = 0; k4 < KC / 4; ++k4) {
-                const double p0 = bI[k4 * 4 * LDT], p1 = bI[k4 * 4 * LDT + 16];
-                const double q0 = bJ[k4 * 4 * LDT], q1 = bJ[k4 * 4 * LDT + 16];
+            for (int r = 0; r < RING; ++r) {
+                const int ch = c0 + r;
+                // this wave's DMA of stage ch has landed (later stages stay in flight: one DMA per wave and stage, and
+                // nothing else goes to memory inside the loop); the barrier then says every wave's has, and that every
+                // wave has read stage ch - 1, whose slot is refilled next
+                if (ch + 2 < nch) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+                else if (ch + 1 < nch) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+                if (ch + RING - 1 < nch) DAG_STAGE((r + RING - 1) % RING);
+                const double *bs = smem + STG * r;
+                const double p0 = bs[aI0], p1 = bs[aI1];
+                const double q0 = bs[aJ0], q1 = bs[aJ1];
                 acc[0][0] = MFMA64(q0, p0, acc[0][0]);
                 acc[0][1] = MFMA64(q1, p0, acc[0][1]);
                 acc[1][0] = MFMA64(q0, p1, acc[1][0]);
                 acc[1][1] = MFMA64(q1, p1, acc[1][1]);
             }
-            if (ch + 1 < nch) {
-                *(d2 *)(&sI[cur ^ 1][kc * LDT + rg]) = stI;
-                *(d2 *)(&sJ[cur ^ 1][kc * LDT + rg]) = stJ;
-            }
-            __syncthreads();
         }
+#undef DAG_STAGE
         // ---- the next task is asked for now (see update_kernel), and the C tile's previous version must be there
         if (t2 == 0) {
             // (the draw, the look at another XCD's counter and the first poll of `we` are issued back to back and waited for
