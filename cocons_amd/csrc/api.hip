@@ -373,7 +373,7 @@ struct cocons_fit {
     double *dpart;                // early halves of the split diagonal-block tiles (2 x 16 x 64 x 64 doubles)
     unsigned *ddag; size_t ddag_words;      // [queue (64 words)] [tdone] [pdone]
     void *ddag_steps; int dag_nsteps; unsigned dag_ntasks;
-    int dag_key[13];              // (nt, mt, trim, kskip, lead, min_tiles, split, lead2, lead3, order, xcd, bw, bh) the step table was built for
+    int dag_key[12];              // (nt, mt, trim, kskip, lead, min_tiles, lead2, lead3, order, xcd, bw, bh) the step table was built for
     unsigned *ddag_ftab; size_t ddag_ftab_words;   // which tile every far tile task is (dag_build_steps' table), device copy
     int dag_xcd_g;                // chunk exponent of the XCD-aware deal the table was built for (0: one counter)
     bool dag_have_ftab;           // the current step table comes with a far-tile table
@@ -382,7 +382,6 @@ struct cocons_fit {
     size_t dag_trace_elems;       // allocated 64-bit words of ddag_trace (5 per task + 8 per tile pair)
     bool dag_next;                // the engine launched by engine_start is the DAG schedule's (publishes W and the second X)
     int engine_pair_live;         // 1: the engine launched for the next factorisation has a pair partner (it counts itself in alive[2])
-    int engine_t0;                // first tile of the engine launched for the next factorisation: 0 (it factors the first diagonal block too) or 2
     size_t smb_off, smb_elems;           // inside dmbox: strip mailboxes, one per diagonal block (the panel launch's next-diagonal-block
                                          // update), and xmb_off: the panel launch's exchange mailboxes, one per 64-row strip (split panel)
     size_t xmb_off, xmb_elems;
@@ -1175,7 +1174,6 @@ static void panel_ops(cocons_fit *f, const FactorView &v, int k, hipStream_t s)
 // diagnostics header) so that variants can be timed in alternation inside ONE process on ONE device.
 struct Tunables {
     int engine = 1;          // COCONS_ENGINE: 1 = diagonal blocks are factored by the resident engine beside the updates
-    int upd_dynamic = 1;     // COCONS_UPD_DYNAMIC
     int dag = 1;             // COCONS_DAG: 1 = the head of the factorisation under the dependency-driven schedule (one persistent
                              // launch for its updates and panels, dag_kernel); 0 = the classic schedule throughout
     // where a step's panel tasks sit in its list: `lead` far tiles, T1 (+ early halves), `lead2` far tiles, T2, `lead3` far
@@ -1188,7 +1186,6 @@ struct Tunables {
                              // (n = 10^4: 24 of the 39 steps, 94 % of the flops; below n ~ 4200 no step at all).  3000 until the
                              // engine became a pair (round 5): with the shorter chain the break-even moved back, 1400 .. 2200
                              // measure alike, +0.4 % over 3000)
-    int dag_split = 1;       // COCONS_DAG_SPLIT: the diagonal-block tiles of a DAG step in two halves, the first one off the chain
     int dag_xcd = 1;         // COCONS_DAG_XCD: 1 = XCD-aware task order of the persistent launch (round 6; chol.hip: dag_position) -- list
                              // positions dealt to the XCDs in chunks of 32, the far tiles of a step dealt so that one XCD's tiles in
                              // flight form one block of dag_bw x dag_bh tiles, a class that falls behind helped by the others: fetched
@@ -1198,23 +1195,17 @@ struct Tunables {
     int dag_xcd_min_quota = 128;
     int dag_xcc_quota = -1;  // workgroups of the DAG launch that take part on the engine's XCD (of the 255 that land there; 0: all;
                              // -1: derived from the device, dag_xcc_quota() -- 208 on MI355X)
-    int engine_block0 = 1;   // COCONS_ENGINE_BLOCK0: 1 = the engine factors the FIRST diagonal block too (its input words raised by the gate
-                             // kernel) and that block's panel is the one-launch panel of every other block; 0 = the first block on the
-                             // plain schedule (tile | solve | in-panel update | tile | solve on the main stream), the engine from block 1
     int engine_pair = 1;     // COCONS_ENGINE_PAIR: 1 = the engine is a PAIR of workgroups -- the second one follows the first tile's
                              // factorisation column block by column block (strip solve, tile update) and factors the second tile
                              // (chol.hip: engine_partner_loop); 0 = one workgroup does the four passes one behind the other
-    int panel_fused = 1;     // COCONS_PANEL_FUSED: 1 = the panel of a two-tile block of the engine schedule is ONE launch (chol.hip:
-                             // panel_pair_kernel); 0 = solve | in-panel update | solve, three launches
-    int panel_follow = 1;    // COCONS_PANEL_FOLLOW: 1 = the one-launch panel's strips follow the engine's tiles through their mailboxes
-                             // (pair mode) instead of waiting for out[t] / out[t+1] and fetching the factor
+    int panel_fused = 1;     // COCONS_PANEL_FUSED: 1 = the panel of a two-tile block of the engine schedule is ONE launch whose strips
+                             // follow the engine pair's tiles through their mailboxes (chol.hip: panel_pair_kernel); 0, or without
+                             // the pair: solve | in-panel update | solve, three launches
     int panel_split = 32;    // COCONS_PANEL_SPLIT: a strip of the one-launch panel is TWO workgroups -- the first follows tile t (X0), the second
                              // follows the first through an exchange mailbox (the in-panel product while X0 is being formed), then tile
                              // t+1 -- in panels of at least this many 64-row strips (0: never, 1: always).  It pays where the panel stands
                              // exposed behind a long update launch (n = 4096: +1.9 %, 6400: +1.5 %, 10^4: +0.6 %) and costs where the engine
                              // is the bound anyway (always on: n = 2116 -4.3 %, n = 1024 -2.2 %); an update of 32 strips' trapezoid is ~30 us
-    int panel_diag = 1;      // COCONS_PANEL_DIAG: 1 = the one-launch panel also updates the NEXT diagonal block (extra workgroups that
-                             // follow its first strips through a strip mailbox) and the update launch behind it leaves those tiles alone
     int potrf_follow = 1;    // COCONS_POTRF_FOLLOW: 1 = a tile factorisation and the panel solve below it are ONE launch whose solve
                              // workgroups follow the factorisation through a mailbox (chol.hip: potrf_follow_kernel; the plain and
                              // the band-limited schedule); 0 = two launches
@@ -1228,33 +1219,40 @@ struct Tunables {
     int host_delay_us = 0, host_delay_tile = -1, engine_in_wait_ms = 0;
     bool init = false;
 };
+// The table of the switches above: tune name (cocons_debug_tune), environment variable (read once, at the first use; nullptr:
+// tests and tools only) and the least value the switch takes (a smaller one is raised to it)
+struct TuneRow { const char *name, *env; int Tunables::*field; int lo; };
+static const TuneRow tune_rows[] = {
+    {"engine", "COCONS_ENGINE", &Tunables::engine, INT_MIN},
+    {"dag", "COCONS_DAG", &Tunables::dag, INT_MIN},
+    {"dag_lead", "COCONS_DAG_LEAD", &Tunables::dag_lead, INT_MIN},
+    {"dag_lead2", "COCONS_DAG_LEAD2", &Tunables::dag_lead2, INT_MIN},
+    {"dag_lead3", "COCONS_DAG_LEAD3", &Tunables::dag_lead3, INT_MIN},
+    {"dag_min_tiles", "COCONS_DAG_MIN_TILES", &Tunables::dag_min_tiles, INT_MIN},
+    {"dag_xcc_quota", "COCONS_DAG_XCC_QUOTA", &Tunables::dag_xcc_quota, INT_MIN},
+    {"dag_xcd", "COCONS_DAG_XCD", &Tunables::dag_xcd, INT_MIN},
+    {"dag_order", "COCONS_DAG_ORDER", &Tunables::dag_order, INT_MIN},
+    {"dag_xcd_min_quota", nullptr, &Tunables::dag_xcd_min_quota, INT_MIN},
+    {"dag_bw", "COCONS_DAG_BW", &Tunables::dag_bw, 1},        // (0 would make dag_build_far_table loop forever)
+    {"dag_bh", "COCONS_DAG_BH", &Tunables::dag_bh, 1},
+    {"dag_trace", nullptr, &Tunables::dag_trace, INT_MIN},
+    {"engine_pair", "COCONS_ENGINE_PAIR", &Tunables::engine_pair, INT_MIN},
+    {"panel_fused", "COCONS_PANEL_FUSED", &Tunables::panel_fused, INT_MIN},
+    {"potrf_follow", "COCONS_POTRF_FOLLOW", &Tunables::potrf_follow, INT_MIN},
+    {"panel_split", "COCONS_PANEL_SPLIT", &Tunables::panel_split, INT_MIN},
+    {"gate_sabotage", nullptr, &Tunables::gate_sabotage, INT_MIN},
+    {"host_delay_us", "COCONS_DEBUG_HOST_DELAY_US", &Tunables::host_delay_us, INT_MIN},
+    {"host_delay_tile", "COCONS_DEBUG_HOST_DELAY_TILE", &Tunables::host_delay_tile, INT_MIN},
+    {"engine_in_wait_ms", nullptr, &Tunables::engine_in_wait_ms, INT_MIN},
+};
+static void tune_set(Tunables &t, const TuneRow &r, int value) { t.*r.field = value < r.lo ? r.lo : value; }
+
 static Tunables &tun()
 {
     static Tunables t;
     if (!t.init) {
-        auto rd = [](const char *name, int &v) { const char *e = getenv(name); if (e) v = atoi(e); };
-        rd("COCONS_ENGINE", t.engine);
-        rd("COCONS_UPD_DYNAMIC", t.upd_dynamic);
-        rd("COCONS_DAG", t.dag);
-        rd("COCONS_DAG_LEAD", t.dag_lead);
-        rd("COCONS_DAG_LEAD2", t.dag_lead2);
-        rd("COCONS_DAG_LEAD3", t.dag_lead3);
-        rd("COCONS_DAG_MIN_TILES", t.dag_min_tiles);
-        rd("COCONS_DAG_SPLIT", t.dag_split);
-        rd("COCONS_DAG_XCC_QUOTA", t.dag_xcc_quota);
-        rd("COCONS_DAG_XCD", t.dag_xcd);
-        rd("COCONS_DAG_ORDER", t.dag_order);
-        rd("COCONS_DAG_BW", t.dag_bw);
-        rd("COCONS_DAG_BH", t.dag_bh);
-        rd("COCONS_ENGINE_PAIR", t.engine_pair);
-        rd("COCONS_ENGINE_BLOCK0", t.engine_block0);
-        rd("COCONS_PANEL_FUSED", t.panel_fused);
-        rd("COCONS_POTRF_FOLLOW", t.potrf_follow);
-        rd("COCONS_PANEL_FOLLOW", t.panel_follow);
-        rd("COCONS_PANEL_DIAG", t.panel_diag);
-        rd("COCONS_PANEL_SPLIT", t.panel_split);
-        rd("COCONS_DEBUG_HOST_DELAY_US", t.host_delay_us);
-        rd("COCONS_DEBUG_HOST_DELAY_TILE", t.host_delay_tile);
+        for (const TuneRow &r : tune_rows)
+            if (const char *e = r.env ? getenv(r.env) : nullptr) tune_set(t, r, atoi(e));
         t.init = true;
     }
     return t;
@@ -1271,33 +1269,9 @@ extern "C" int cocons_debug_tune(const char *name, int value)
     if (!name) return fail(-1, "cocons_debug_tune: null name");
     Tunables &t = tun();
     std::string k(name);
-    if (k == "engine") t.engine = value;
-    else if (k == "upd_dynamic") t.upd_dynamic = value;
-    else if (k == "dag") t.dag = value;
-    else if (k == "dag_lead") t.dag_lead = value;
-    else if (k == "dag_lead2") t.dag_lead2 = value;
-    else if (k == "dag_lead3") t.dag_lead3 = value;
-    else if (k == "dag_min_tiles") t.dag_min_tiles = value;
-    else if (k == "dag_split") t.dag_split = value;
-    else if (k == "dag_xcc_quota") t.dag_xcc_quota = value;
-    else if (k == "dag_xcd") t.dag_xcd = value;
-    else if (k == "dag_order") t.dag_order = value;
-    else if (k == "dag_xcd_min_quota") t.dag_xcd_min_quota = value;
-    else if (k == "dag_bw") t.dag_bw = value < 1 ? 1 : value;
-    else if (k == "dag_bh") t.dag_bh = value < 1 ? 1 : value;
-    else if (k == "dag_trace") t.dag_trace = value;
-    else if (k == "engine_pair") t.engine_pair = value;
-    else if (k == "engine_block0") t.engine_block0 = value;
-    else if (k == "panel_fused") t.panel_fused = value;
-    else if (k == "potrf_follow") t.potrf_follow = value;
-    else if (k == "panel_follow") t.panel_follow = value;
-    else if (k == "panel_diag") t.panel_diag = value;
-    else if (k == "panel_split") t.panel_split = value;
-    else if (k == "gate_sabotage") t.gate_sabotage = value;
-    else if (k == "host_delay_us") t.host_delay_us = value;
-    else if (k == "host_delay_tile") t.host_delay_tile = value;
-    else if (k == "engine_in_wait_ms") t.engine_in_wait_ms = value;
-    else if (k == "upd_waves") set_update_waves(value);
+    for (const TuneRow &r : tune_rows)
+        if (k == r.name) { tune_set(t, r, value); return 0; }
+    if (k == "upd_waves") set_update_waves(value);
     else if (k == "w8_max_tiles") set_update_w8_max_tiles(value);
     else if (k == "c_wt") set_update_c_wt(value);
     else return fail(-1, "cocons_debug_tune: unknown switch %s", name);
@@ -1323,15 +1297,25 @@ static int dag_xcc_quota()
     if (tun().dag_xcc_quota >= 0) return tun().dag_xcc_quota;
     static int derived = -1;
     if (derived < 0) {
-        int dev = 0, cus = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        const int cus = device_cus();
         const int xcds = 8;                                 // gfx950: eight accelerator dies (no HIP attribute reports it)
         const int cpx = cus % xcds == 0 ? cus / xcds : 32;
         derived = (cpx - 1) * 7 - 9;
         if (derived < 8) derived = 8;
     }
     return derived;
+}
+
+// Chunk exponent of the XCD-aware deal of the persistent launch's task list (chol.hip: dag_position; 0 = one counter for all).
+// The deal assumes the eight XCDs of the whole chip -- a partitioned device keeps the one counter -- and XCDs that contribute
+// comparable numbers of workgroups: a class of list positions whose XCD holds almost none is carried by the others only while
+// they are free to draw, and with everybody waiting at that class's tasks the launch crawls at the pace of its few workgroups
+// until a bounded wait ends it (tools/diag/quota_stress.py) -- a quota below dag_xcd_min_quota (half an XCD's share), which
+// only the tests set, keeps the one counter too.
+static int dag_xcd_group()
+{
+    const int q = dag_xcc_quota();
+    return (tun().dag_xcd && device_cus() == 256 && (q == 0 || q >= tun().dag_xcd_min_quota)) ? 5 : 0;
 }
 
 // COCONS_ENGINE: 1 (default) = diagonal tiles are factored by the resident engine while the trailing
@@ -1409,8 +1393,8 @@ static int mbox_reset(cocons_fit *f, int nt, bool engine_schedule = true)
     // one allocation, one fill: the tiles' mailboxes | the strip mailboxes (0.5 MB per diagonal block) | the exchange mailboxes of
     // the split panel (64 KB per 64-row strip of the matrix and the rows under it)
     const size_t tiles = ((size_t)nt + 2) * ENGINE_MBOX_DOUBLES;
-    const bool panel = tun().panel_follow && tun().panel_fused && tun().engine_pair;
-    const size_t smb = panel && tun().panel_diag ? ((size_t)nt / 2 + 2) * PANEL_SMBOX_DOUBLES : 0;
+    const bool panel = tun().panel_fused && tun().engine_pair;        // (the one-launch panel follows the pair's tiles)
+    const size_t smb = panel ? ((size_t)nt / 2 + 2) * PANEL_SMBOX_DOUBLES : 0;
     const size_t xmb = panel && tun().panel_split ? (2 * ((size_t)nt + 2) + 4) * PANEL_XMBOX_DOUBLES : 0;
     const size_t need = tiles + smb + xmb;
     if (f->dmbox_elems < need) {
@@ -1427,11 +1411,10 @@ static int mbox_reset(cocons_fit *f, int nt, bool engine_schedule = true)
     return 0;
 }
 
-// one tile counter per trailing update: see update_kernel's dynamic tile order (COCONS_UPD_DYNAMIC=0: static)
+// one tile counter per trailing update: see update_kernel's dynamic tile order
 static unsigned *tile_queue(cocons_fit *f, int k)
 {
-    const int dyn = tun().upd_dynamic;
-    return dyn ? f->dflags + 3 * (size_t)f->flags_cap + 64 + k / 2 : nullptr;
+    return f->dflags + 3 * (size_t)f->flags_cap + 64 + k / 2;
 }
 
 // Warm-up of the engine's stream at handle creation: ONE launch of the engine kernel that raises its alive word and
@@ -1573,20 +1556,14 @@ static int dag_prepare(cocons_fit *f, const FactorView &v)
         f->dWt_tiles = v.nt;
     }
     const int kskip = (f->pad0 / 16) * 16;
-    // (the XCD-aware deal assumes the eight XCDs of the whole chip -- a partitioned device keeps the one counter -- and XCDs that
-    // contribute comparable numbers of workgroups: a class of list positions whose XCD holds almost none is carried by the
-    // others only while they are free to draw, and with everybody waiting at that class's tasks the launch crawls at the pace
-    // of its few workgroups until a bounded wait ends it (tools/diag/quota_stress.py) -- a quota below half an XCD's share, which
-    // only the tests set, keeps the one counter too)
-    const int q_all = dag_xcc_quota();
-    const int xcd_g = (tun().dag_xcd && device_cus() == 256 && (q_all == 0 || q_all >= tun().dag_xcd_min_quota)) ? 5 : 0;
-    const int key[13] = {v.nt, v.mt, v.trim, kskip, tun().dag_lead, tun().dag_min_tiles, tun().dag_split, tun().dag_lead2, tun().dag_lead3,
+    const int xcd_g = dag_xcd_group();
+    const int key[12] = {v.nt, v.mt, v.trim, kskip, tun().dag_lead, tun().dag_min_tiles, tun().dag_lead2, tun().dag_lead3,
                          tun().dag_order, xcd_g, tun().dag_bw, tun().dag_bh};
     if (memcmp(key, f->dag_key, sizeof key) != 0 || !f->ddag_steps) {
         std::vector<DagStepHost> steps;
         std::vector<unsigned> ftab;
         const bool want_tab = tun().dag_order != 0 || xcd_g > 0;
-        const unsigned ntasks = dag_build_steps(v.nt, v.mt, v.trim, kskip, tun().dag_lead, tun().dag_min_tiles, tun().dag_split, steps,
+        const unsigned ntasks = dag_build_steps(v.nt, v.mt, v.trim, kskip, tun().dag_lead, tun().dag_min_tiles, steps,
                                                 tun().dag_lead2, tun().dag_lead3, want_tab ? &ftab : nullptr, xcd_g,
                                                 tun().dag_order ? tun().dag_bw : 0, tun().dag_bh);
         HIPCHK(hipStreamSynchronize(f->stream));
@@ -1694,8 +1671,9 @@ static int engine_start(cocons_fit *f, const FactorView &v)
     HIPCHK(hipEventRecord(f->ev_eng, M));                    // (behind the resets of the flag and task words, and of W / P when new)
     HIPCHK(hipStreamWaitEvent(f->stream2, f->ev_eng, 0));
     unsigned *alive_w = f->dflags + 3 * (size_t)f->flags_cap;
-    f->engine_t0 = (tun().engine_block0 && !v.hi) ? 0 : 2;
-    launch_potrf_engine(v.A, v.lda, f->engine_t0, nt, f->dinv, f->dinfo, in, out, xr, (unsigned *)(f->dinfo + 1),
+    // (from tile 0: the engine factors the first diagonal block too, its input words raised by the gate kernel -- band-limited
+    // views, whose first block is not the engine's, never get the engine: fit_create_taper)
+    launch_potrf_engine(v.A, v.lda, 0, nt, f->dinv, f->dinfo, in, out, xr, (unsigned *)(f->dinfo + 1),
                         alive_w, f->stream2, f->dag_next ? f->dWt : nullptr,
                         f->dag_next ? f->dP : nullptr, f->dag_next ? 2 * f->dag_nsteps : 0,
                         (f->dag_next && f->dag_trace_tasks) ? f->ddag_trace + 4 * (size_t)f->dag_ntasks : nullptr,
@@ -1772,31 +1750,28 @@ static int factorize(cocons_fit *f, const FactorView &v, std::vector<hipEvent_t>
     unsigned *abort_word = (unsigned *)(f->dinfo + 1);
     unsigned *alive = f->dflags + 3 * (size_t)f->flags_cap;
     if (tun().gate_sabotage > 0) { --tun().gate_sabotage; alive += 1; }      // (tests: a word that stays zero)
-    const bool block0 = f->engine_t0 == 0;           // the engine factors the first diagonal block too: the gate raises its input words
+    // (the engine factors the first diagonal block too: the gate raises its input words)
     launch_engine_gate(alive, abort_word, M, false, f->engine_ops++ == 0,
                        f->engine_pair_live,       // (the pair partner counts itself)
-                       (block0 && tun().gate_sabotage == 0 && alive == f->dflags + 3 * (size_t)f->flags_cap) ? in : nullptr);
+                       (tun().gate_sabotage == 0 && alive == f->dflags + 3 * (size_t)f->flags_cap) ? in : nullptr);
     const int rend = mt * TILE - 64 * v.trim;         // one past the last row any panel kernel touches
-    // the panel of the block at tile t (behind the engine's factorisation of it): one launch or three; returns the tiles of the NEXT
-    // diagonal block that the launch has updated (the update launch behind it then leaves them alone)
+    // the panel of the block at tile t (behind the engine's factorisation of it): one launch whose strips follow the pair's tiles
+    // through their mailboxes, or three launches that wait for the tiles; returns the tiles of the NEXT diagonal block that the
+    // launch has updated (the update launch behind it then leaves them alone)
     auto panel_for = [&](int t, bool allow_diag) -> int {
         const bool two = t + 1 < nt;                 // the block has a second tile
         const int r0 = two ? t + 2 : t + 1;          // first tile row below the diagonal block
         const int hb = band_hi(v, t);                // rows of block t's panel: [r0, hb) and the rows under the matrix
         const int br = hb >= 0 ? hb * TILE : -1, er = nt * TILE;
-        if (two && hb < 0 && tun().panel_fused) {
-            const bool fol = f->engine_pair_live && tun().panel_follow && f->dmbox != nullptr;
+        if (two && hb < 0 && tun().panel_fused && f->engine_pair_live && f->dmbox != nullptr) {
             // the next diagonal block (tiles t + 2, t + 3), when there is one, is updated inside this launch
             const int next_tiles = t + 2 < nt ? (t + 3 < nt ? 2 : 1) : 0;
-            const bool dg = allow_diag && fol && tun().panel_diag && next_tiles > 0 &&
-                            ((size_t)(t >> 1) + 1) * PANEL_SMBOX_DOUBLES <= f->smb_elems;
+            const bool dg = allow_diag && next_tiles > 0 && ((size_t)(t >> 1) + 1) * PANEL_SMBOX_DOUBLES <= f->smb_elems;
             const int nstrips = (rend - r0 * TILE) / 64;
-            const bool sp = fol && tun().panel_split > 0 && nstrips >= tun().panel_split &&
+            const bool sp = tun().panel_split > 0 && nstrips >= tun().panel_split &&
                             (size_t)nstrips * PANEL_XMBOX_DOUBLES <= f->xmb_elems;
-            launch_panel_pair(v.A, v.lda, t * TILE, r0 * TILE, rend, f->dinv + (size_t)(t & 1) * 2048,
-                              f->dinv + (size_t)((t + 1) & 1) * 2048, out + t, xr + t, out + t + 1, abort_word, M,
-                              fol ? f->dmbox + (size_t)t * ENGINE_MBOX_DOUBLES : nullptr,
-                              fol ? f->dmbox + (size_t)(t + 1) * ENGINE_MBOX_DOUBLES : nullptr,
+            launch_panel_pair(v.A, v.lda, t * TILE, r0 * TILE, rend, xr + t, abort_word, M,
+                              f->dmbox + (size_t)t * ENGINE_MBOX_DOUBLES, f->dmbox + (size_t)(t + 1) * ENGINE_MBOX_DOUBLES,
                               dg ? f->dmbox + f->smb_off + (size_t)(t >> 1) * PANEL_SMBOX_DOUBLES : nullptr,
                               dg ? (next_tiles == 2 ? 10 : 3) : 0, in, t + 2, sp ? f->dmbox + f->xmb_off : nullptr);
             return (dg && nstrips >= (next_tiles == 2 ? 4 : 2)) ? next_tiles : 0;
@@ -1811,9 +1786,9 @@ static int factorize(cocons_fit *f, const FactorView &v, std::vector<hipEvent_t>
         }
         return 0;
     };
-    int diag_done = 0;                                // tiles of the diagonal block at t that the previous panel's launch has updated
-    if (block0) diag_done = panel_for(0, !f->dag_next);          // (the persistent launch updates its first diagonal block itself)
-    else panel_ops(f, v, 0, M);
+    // tiles of the diagonal block at t that the previous panel's launch has updated (the persistent launch updates its first
+    // diagonal block itself)
+    int diag_done = panel_for(0, !f->dag_next);
     f->dag_used = f->dag_next;
     int k_first = 0;                 // first block step the classic loop below runs in full
     if (f->dag_next) {
@@ -1844,8 +1819,8 @@ static int factorize(cocons_fit *f, const FactorView &v, std::vector<hipEvent_t>
     // (Running the panel kernels on a stream of their own behind near-tile flags, so that they start in the tail of the
     // update that feeds them, was built and measured in round 3: slower -- a 90 KB-LDS solve is not placed beside eight
     // update workgroups per CU, the event back to the main stream costs 12 us -- and removed; so were three forms of the
-    // panel as products with explicit inverses published by the engine (round 3's COCONS_PANEL_MODE 1-3: +-1 %, deleted
-    // in round 4))
+    // panel as products with explicit inverses published by the engine (round 3: +-1 %, deleted in round 4); DESIGN.md
+    // section 8.)
     for (int k = k_first > 0 ? k_first - 2 : 0; k + 2 < nt; k += 2) {
         const int t = k + 2;
         // (tests: a late host -- whatever raises in[host_delay_tile], the panel launch of block t or the update launch behind it,

@@ -1141,23 +1141,22 @@ __device__ __forceinline__ void fetch_factor_tile(const double *A, size_t lda, i
 }
 
 // ---------------------------------------------------------------------------
-// Panel of a two-tile block in ONE launch (engine schedule, round 5): for the rows below the diagonal block
+// Panel of a two-tile block in ONE launch (engine schedule with the engine pair, round 5): for the rows below the diagonal block
 //     X0 = B0 L(t)^-T  |  B1 -= X0 X(t+1,t)^T  |  X1 = B1 L(t+1)^-T
-// -- until now three launches (trsm_tile_kernel, the in-panel update_kernel, trsm_tile_kernel), each of which read its strip
-// from memory and wrote it back, the second and third behind a drained chip.  A workgroup owns 64 rows (a wave 16) for the whole
-// sequence: both 16 x 128 strips stay in registers, the three waits -- out[t], xr[t], out[t+1] -- are met where the data is needed,
-// and the rows are done ~8 us after the engine's second tile instead of ~16 + a boundary.  Same operations on the same operands
+// -- otherwise three launches (trsm_tile_kernel, the in-panel update_kernel, trsm_tile_kernel), each of which reads its strip
+// from memory and writes it back, the second and third behind a drained chip.  A workgroup owns 64 rows (a wave 16) for the whole
+// sequence: both 16 x 128 strips stay in registers, the two solves FOLLOW the tiles through their mailboxes mb0 / mb1 (the engine
+// pair publishes them while it forms them) and the in-panel product waits for xr[t] where it needs X(t+1,t).  Same operations on the same operands
 // in the same order as the three kernels (the product accumulated from zero over ascending k and subtracted once, as
 // update_kernel does): bit-identical.
 __global__ void __launch_bounds__(256)
-panel_pair_kernel(double *A, size_t lda, int c0, int r0, const double *q0, const double *q1, unsigned *out0, unsigned *xrw,
-                  unsigned *out1, unsigned *abort_word, const double *mb0, const double *mb1,
+panel_pair_kernel(double *A, size_t lda, int c0, int r0, unsigned *xrw, unsigned *abort_word, const double *mb0, const double *mb1,
                   double *smb, int nstrip, int npub, unsigned *sig, int sig_tile, double *xmb)
 {
-    // 136 KB: L of the current tile (36 blocks) and its Q operands (8) -- or, between the two solves, all 64 blocks of X(t+1,t)
+    // 136 KB: the two stages of a followed tile (9 blocks each) -- or, between the two solves, all 64 blocks of X(t+1,t)
     __shared__ double SM[68 * 256];
     __shared__ int ok;
-    double *SL = SM, *QS = SM + 36 * 256, *XS = SM;
+    double *XS = SM;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c1 = c0 + TILE;
     // Split panel (COCONS_PANEL_SPLIT, xmb != null): a strip is TWO workgroups.  The first (role A, block index = strip) follows tile
@@ -1170,7 +1169,7 @@ panel_pair_kernel(double *A, size_t lda, int c0, int r0, const double *q0, const
     const bool split = xmb != nullptr;
     const int nfirst = split ? 2 * nstrip : nstrip;        // workgroups in front of the diagonal-tile ones
     if ((int)blockIdx.x >= nfirst) {
-        // ---- the NEXT diagonal block's update, inside this launch (COCONS_PANEL_DIAG): workgroup nfirst + dd takes the dd-th of its
+        // ---- the NEXT diagonal block's update, inside this launch: workgroup nfirst + dd takes the dd-th of its
         // ten (three) 64 x 64 tiles, C(ta, tb) -= sum_k X(ta, k) X(tb, k)^T over the sixteen 16-column blocks of this panel -- and
         // FOLLOWS the strips that form them: the first npub strip workgroups publish every finished 16 x 16 block of X in a strip
         // mailbox (smb: strip, column block, wave; filled with ~0 like the tiles' mailboxes), and a wave here reads its five blocks
@@ -1339,11 +1338,11 @@ panel_pair_kernel(double *A, size_t lda, int c0, int r0, const double *q0, const
         }
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) B1[jj] = B1[jj] - acc[jj];
+        __syncthreads();                 // (every wave is done with X(t+1,t): the stages overlay it; and the product's verdict is in)
+        if (!ok) return;
         {
             const double *mb = mb1;
             double v9[3][9];
-            __syncthreads();             // (every wave is done with X(t+1,t): the stages overlay it; and the product's verdict is in)
-            if (!ok) return;
             MBOX_FETCH256V(0, v9[0])
             MBOX_FETCH256V(1, v9[1])
 #pragma unroll
@@ -1381,16 +1380,15 @@ panel_pair_kernel(double *A, size_t lda, int c0, int r0, const double *q0, const
 #pragma unroll
         for (int j = 0; j < 8; ++j) B1[j] = glb_blk(A, lda, rs, c1 + 16 * j, lane);
     }
-    // ---- X0 = B0 L(t)^-T
+    // ---- X0 = B0 L(t)^-T: the strip FOLLOWS the tile column block by column block (like potrf_follow_kernel's workgroups) and is
+    // solved a round trip behind the tile's last block, where waiting for out[t], fetching the factor and solving took ~8 us behind it
     int *okp = &ok;
-    if (mb0) {
-        // the engine's pair mode: both tiles are published in mailboxes while they are formed -- the strip FOLLOWS the tile column
-        // block by column block (like potrf_follow_kernel's workgroups) and is solved a round trip behind the tile's last block,
-        // where waiting for out[t], fetching the factor and solving took ~8 us behind it
+    if (tid == 0) ok = 1;
+    __syncthreads();
+    {
         const double *mb = mb0;
         double v9[3][9];             // (TWO column blocks in flight: with the tile already there a column block costs its solve,
-        if (tid == 0) ok = 1;        // not a round trip)
-        __syncthreads();
+                                     // not a round trip)
         MBOX_FETCH256V(0, v9[0])
         MBOX_FETCH256V(1, v9[1])
 #pragma unroll
@@ -1417,27 +1415,6 @@ panel_pair_kernel(double *A, size_t lda, int c0, int r0, const double *q0, const
                 blk_mma(B0[jj], NX, Lb);
             }
         }
-    } else {
-    if (tid == 0) ok = wait_ge<false>(out0, 1u, abort_word, abort_code(ABORT_PANEL, (unsigned)(c0 / TILE))) ? 1 : 0;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (!ok) return;
-    fetch_factor_tile<true>(A, lda, c0, q0, SL, QS, tid);
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        d4 L = lds_blk(SL + (j * (j + 1) / 2 + j) * 256, lane);
-        double Q[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) Q[s] = QS[j * 256 + s * 64 + lane];
-        trsm16(B0[j], L, Q);
-        d4 NX = -B0[j];
-#pragma unroll
-        for (int jj = j + 1; jj < 8; ++jj) {
-            d4 Lb = lds_blk(SL + (jj * (jj + 1) / 2 + j) * 256, lane);
-            blk_mma(B0[jj], NX, Lb);
-        }
-    }
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) glb_blk_store(A, lda, rs, c0 + 16 * j, lane, B0[j]);
@@ -1479,10 +1456,10 @@ panel_pair_kernel(double *A, size_t lda, int c0, int r0, const double *q0, const
         }
     }
     // ---- X1 = B1 L(t+1)^-T
-    if (mb1) {
+    __syncthreads();                 // (every wave is done with X(t+1,t): the stages overlay it)
+    {
         const double *mb = mb1;
         double v9[3][9];
-        __syncthreads();             // (every wave is done with X(t+1,t): the stages overlay it)
         MBOX_FETCH256V(0, v9[0])
         MBOX_FETCH256V(1, v9[1])
 #pragma unroll
@@ -1508,27 +1485,6 @@ panel_pair_kernel(double *A, size_t lda, int c0, int r0, const double *q0, const
                 blk_mma(B1[jj], NX, Lb);
             }
         }
-    } else {
-    if (tid == 0) ok = wait_ge<false>(out1, 1u, abort_word, abort_code(ABORT_PANEL, (unsigned)(c1 / TILE))) ? 1 : 0;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();                 // (also: every wave is done with X(t+1,t))
-    if (!ok) return;
-    fetch_factor_tile<true>(A, lda, c1, q1, SL, QS, tid);
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        d4 L = lds_blk(SL + (j * (j + 1) / 2 + j) * 256, lane);
-        double Q[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) Q[s] = QS[j * 256 + s * 64 + lane];
-        trsm16(B1[j], L, Q);
-        d4 NX = -B1[j];
-#pragma unroll
-        for (int jj = j + 1; jj < 8; ++jj) {
-            d4 Lb = lds_blk(SL + (jj * (jj + 1) / 2 + j) * 256, lane);
-            blk_mma(B1[jj], NX, Lb);
-        }
-    }
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) glb_blk_store(A, lda, rs, c1 + 16 * j, lane, B1[j]);
@@ -2786,19 +2742,17 @@ void launch_potrf_follow(double *A, size_t lda, int c0, int r0, int r1, double *
                        ext_r0, nstrips, abort_word);
 }
 
-void launch_panel_pair(double *A, size_t lda, int c0, int r0, int r1, const double *q0, const double *q1, unsigned *out0,
-                       unsigned *xr, unsigned *out1, unsigned *abort_word, hipStream_t s, const double *mb0, const double *mb1,
-                       double *smb, int ndiag, unsigned *sig, int sig_tile, double *xmb)
+void launch_panel_pair(double *A, size_t lda, int c0, int r0, int r1, unsigned *xr, unsigned *abort_word, hipStream_t s,
+                       const double *mb0, const double *mb1, double *smb, int ndiag, unsigned *sig, int sig_tile, double *xmb)
 {
     const int nb = (r1 - r0) / 64;
     if (nb <= 0) return;
-    const bool split = xmb && mb0 && mb1;         // (two workgroups per strip: see the kernel)
+    const bool split = xmb != nullptr;            // (two workgroups per strip: see the kernel)
     // (ndiag = 10 or 3: the next diagonal block -- two tiles or one -- is updated by as many extra workgroups, which follow the
-    // first 4 or 2 strips through the strip mailbox smb; needs the tiles' mailboxes)
-    const bool diag = smb && mb0 && mb1 && ndiag > 0 && nb >= (ndiag == 10 ? 4 : 2);
-    hipLaunchKernelGGL(panel_pair_kernel, dim3((split ? 2 * nb : nb) + (diag ? ndiag : 0)), dim3(256), 0, s, A, lda, c0, r0, q0, q1,
-                       out0, xr, out1, abort_word, mb0, mb1, diag ? smb : nullptr, nb, diag ? (ndiag == 10 ? 4 : 2) : 0, sig, sig_tile,
-                       split ? xmb : nullptr);
+    // first 4 or 2 strips through the strip mailbox smb)
+    const bool diag = smb && ndiag > 0 && nb >= (ndiag == 10 ? 4 : 2);
+    hipLaunchKernelGGL(panel_pair_kernel, dim3((split ? 2 * nb : nb) + (diag ? ndiag : 0)), dim3(256), 0, s, A, lda, c0, r0,
+                       xr, abort_word, mb0, mb1, diag ? smb : nullptr, nb, diag ? (ndiag == 10 ? 4 : 2) : 0, sig, sig_tile, xmb);
 }
 
 // waves per workgroup of the trailing update (COCONS_UPD_WAVES: 4 or 8, see update_kernel's NW)
@@ -2977,7 +2931,7 @@ static void dag_build_far_table(const std::vector<DagStepHost> &steps, std::vect
 // Steps for a factorisation with nt column tiles and mt row tiles (trim64: the last 64 rows hold nothing), first panel
 // (tiles 0, 1) already formed in place; kskip leading columns of it are unit vectors (front padding) and are skipped.
 // lead: far tiles of a step in front of its panel tasks.  Returns the number of tasks.
-unsigned dag_build_steps(int nt, int mt, int trim64, int kskip, int lead, int min_tiles, int split, std::vector<DagStepHost> &out,
+unsigned dag_build_steps(int nt, int mt, int trim64, int kskip, int lead, int min_tiles, std::vector<DagStepHost> &out,
                          int lead2, int lead3, std::vector<unsigned> *ftab, int xcd_g, int bw, int bh)
 {
     out.clear();
@@ -3017,12 +2971,11 @@ unsigned dag_build_steps(int nt, int mt, int trim64, int kskip, int lead, int mi
     }
     // the diagonal-block tiles of step s + 1 in two halves: the early one rides in step s's list behind its T1 tasks.  (steps
     // from 1 on: K = 256 there; step s must form the panel of s + 1, i.e. have panel tasks)
-    if (split)
-        for (size_t s = 0; s + 1 < out.size(); ++s)
-            if (out[s].nstrip > 0 && out[s].two) {
-                out[s].nd_next = out[s + 1].two ? 10 : 3;
-                out[s + 1].split = 1;
-            }
+    for (size_t s = 0; s + 1 < out.size(); ++s)
+        if (out[s].nstrip > 0 && out[s].two) {
+            out[s].nd_next = out[s + 1].two ? 10 : 3;
+            out[s + 1].split = 1;
+        }
     for (auto &st : out) {
         const long long ntile = (long long)st.W * st.H - (long long)st.W * (st.W - 1) / 2;
         st.nT += (unsigned)st.nd_next;

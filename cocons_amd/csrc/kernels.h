@@ -170,12 +170,11 @@ void launch_trsm_tile(double *A, size_t lda, int c0, int r0, int r1, const doubl
                       unsigned *wait_word = nullptr, unsigned *abort_word = nullptr, int band_r1 = -1, int ext_r0 = 0,
                       int own_world = 0, int own_rank = 0, int own_group = 1);
 // The panel of a two-tile block of the engine schedule in one launch: rows [r0, r1) of the tile columns at c0 and c0 + 128,
-// X0 = B0 L(c0)^-T | B1 -= X0 X(t+1,t)^T | X1 = B1 L(c0+128)^-T, waiting for out0 / xr / out1 where each is needed (dense, unsharded;
-// q0, q1: the Q operands of the two diagonal tiles).  Bit-identical to launch_trsm_tile | launch_update (K = 128) | launch_trsm_tile.
-// mb0, mb1 (both or neither): the two tiles' mailboxes (the engine's pair mode): the strips follow the tiles while they are formed
-void launch_panel_pair(double *A, size_t lda, int c0, int r0, int r1, const double *q0, const double *q1, unsigned *out0,
-                       unsigned *xr, unsigned *out1, unsigned *abort_word, hipStream_t s, const double *mb0 = nullptr,
-                       const double *mb1 = nullptr,
+// X0 = B0 L(c0)^-T | B1 -= X0 X(t+1,t)^T | X1 = B1 L(c0+128)^-T (dense, unsharded).  The strips follow the two tiles through their
+// mailboxes mb0, mb1 (the engine's pair mode) and the in-panel product waits for xr.  Bit-identical to launch_trsm_tile |
+// launch_update (K = 128) | launch_trsm_tile.
+void launch_panel_pair(double *A, size_t lda, int c0, int r0, int r1, unsigned *xr, unsigned *abort_word, hipStream_t s,
+                       const double *mb0, const double *mb1,
                        double *smb = nullptr, int ndiag = 0, unsigned *sig = nullptr, int sig_tile = 0,
                        double *xmb = nullptr);   // split panel: exchange mailboxes, PANEL_XMBOX_DOUBLES per 64-row strip, every byte
                                                  // 0xff (the second workgroup of a strip puts the pattern back as it reads)
@@ -230,10 +229,10 @@ struct DagStepHost {
 };
 // only the leading steps with at least min_tiles update tiles are taken (the head of the factorisation); the last of them has
 // no panel tasks: the panel behind it is left to the caller's classic kernels
-// split != 0: the diagonal-block tiles of the steps from 1 on are computed in two halves (nd_next / split, see DagStep)
+// the diagonal-block tiles of the steps from 1 on are computed in two halves (nd_next / split, see DagStep)
 // lead: far tiles of a step in front of its T1 tasks (and the early halves); lead2 / lead3: far tiles between them and the T2
 // tasks, between those and the T3 tasks
-unsigned dag_build_steps(int nt, int mt, int trim64, int kskip, int lead, int min_tiles, int split, std::vector<DagStepHost> &out,
+unsigned dag_build_steps(int nt, int mt, int trim64, int kskip, int lead, int min_tiles, std::vector<DagStepHost> &out,
                          int lead2 = 0, int lead3 = 0,
                          std::vector<unsigned> *ftab = nullptr,    // out: which tile every FAR tile task is (launch_dag's ftab; chol.hip:
                                                                    // dag_build_far_table) for tasks dealt to the XCDs in chunks of

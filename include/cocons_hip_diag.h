@@ -32,10 +32,10 @@ int cocons_debug_matern_grad(int n, const double *nu, const double *u, double *o
 int cocons_debug_fit_memory(struct cocons_fit *fit, long long *out4);
 
 /* Schedule switches of the factorisation, settable at run time (the library reads the COCONS_* environment variables
- * of the same meaning once per process; DESIGN.md section 6 lists them): "engine", "engine_block0", "engine_pair", "panel_fused", "panel_follow",
- * "panel_diag", "panel_split", "potrf_follow", "upd_dynamic", "upd_waves", "w8_max_tiles", "dag", "dag_min_tiles", "dag_split",
- * "dag_lead" / "dag_lead2" / "dag_lead3", "dag_xcc_quota", "dag_xcd", "dag_order", "dag_bw", "dag_bh", "dag_trace" (and, for the tests, "gate_sabotage", "host_delay_us",
- * "host_delay_tile", "engine_in_wait_ms", "dag_xcd_min_quota").
+ * of the same meaning once per process; DESIGN.md section 6 lists them): "engine", "engine_pair", "panel_fused", "panel_split",
+ * "potrf_follow", "upd_waves", "w8_max_tiles", "dag", "dag_min_tiles", "dag_lead" / "dag_lead2" / "dag_lead3", "dag_xcc_quota",
+ * "dag_xcd", "dag_order", "dag_bw", "dag_bh" (both at least 1), "dag_trace" (and, for the tests, "gate_sabotage", "host_delay_us",
+ * "host_delay_tile", "engine_in_wait_ms", "dag_xcd_min_quota").  An unknown name returns -1.
  * For timing variants in alternation inside one process (tools/ab_modes.py); results do not depend on them beyond the
  * rounding of a different summation order.                                                                        */
 int cocons_debug_tune(const char *name, int value);

@@ -168,3 +168,30 @@ def test_block_ownership_deal_matches_the_python_twin():
         assert owners == [(b // g) % world for b in range(40)]
         assert all(0 <= o < world for o in owners)
     assert lib.cocons_shard_block_owner(-1, 2) == -1 and lib.cocons_shard_block_owner(0, 0) == -1
+
+
+def test_debug_tune_knows_the_switch_table_and_refuses_retired_names():
+    """cocons_debug_tune (no GPU call) walks the same table as the environment read: every switch of the table takes its
+    default (or what the environment asked for at start-up, so the process keeps its schedule), retired switches are unknown
+    names -- -1 and a message, as for any other unknown name."""
+    from cocons_amd import _lib
+    lib = _lib.load()
+    table = {  # tune name: (environment variable or None, default)
+        "engine": ("COCONS_ENGINE", 1), "dag": ("COCONS_DAG", 1), "dag_lead": ("COCONS_DAG_LEAD", 1600),
+        "dag_lead2": ("COCONS_DAG_LEAD2", 600), "dag_lead3": ("COCONS_DAG_LEAD3", 1800),
+        "dag_min_tiles": ("COCONS_DAG_MIN_TILES", 2000), "dag_xcc_quota": ("COCONS_DAG_XCC_QUOTA", -1),
+        "dag_xcd": ("COCONS_DAG_XCD", 1), "dag_order": ("COCONS_DAG_ORDER", 1), "dag_xcd_min_quota": (None, 128),
+        "dag_bw": ("COCONS_DAG_BW", 16), "dag_bh": ("COCONS_DAG_BH", 16), "dag_trace": (None, 0),
+        "engine_pair": ("COCONS_ENGINE_PAIR", 1), "panel_fused": ("COCONS_PANEL_FUSED", 1),
+        "potrf_follow": ("COCONS_POTRF_FOLLOW", 1), "panel_split": ("COCONS_PANEL_SPLIT", 32), "gate_sabotage": (None, 0),
+        "host_delay_us": ("COCONS_DEBUG_HOST_DELAY_US", 0), "host_delay_tile": ("COCONS_DEBUG_HOST_DELAY_TILE", -1),
+        "engine_in_wait_ms": (None, 0),
+        "upd_waves": ("COCONS_UPD_WAVES", 8), "w8_max_tiles": ("COCONS_UPD_W8_MAX_TILES", 3500), "c_wt": (None, 0),
+    }
+    for name, (env, default) in table.items():
+        value = int(os.environ.get(env, default)) if env else default
+        assert lib.cocons_debug_tune(name.encode(), value) == 0, (name, _lib.last_error())
+    for name in ("engine_block0", "panel_follow", "panel_diag", "upd_dynamic", "dag_split", "no_such_switch"):
+        assert lib.cocons_debug_tune(name.encode(), 1) == -1, name
+        assert _lib.last_error() == "cocons_debug_tune: unknown switch %s" % name
+    assert lib.cocons_debug_tune(None, 1) == -1

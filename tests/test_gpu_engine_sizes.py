@@ -251,11 +251,11 @@ def test_late_host_is_waited_for_and_a_short_bound_records_0x112(oracle):
         st = fit.engine_state()
         # (the engine waits for in[18], its partner for in[19] -- both raised by the late launches: whichever of the two runs out
         # first leaves its code, 0x112 or 0x212)
-        # (with the next diagonal block updated by the update launch instead of inside the panel's -- COCONS_PANEL_DIAG=0, or a switch
-        # that implies it -- the late launches are the ones that raise in[16] / in[17]: 0x110 / 0x210)
+        # (with three-launch panels -- COCONS_PANEL_FUSED=0, or COCONS_ENGINE_PAIR=0 -- the next diagonal block is updated by the
+        # update launch instead of inside the panel's, and the late launches are the ones that raise in[16] / in[17]: 0x110 / 0x210)
         code = st["last_abort"]
         assert st["retries"] == 1 and (code & 0xf00) in (0x100, 0x200) and (code & 0xff) in (16, 17, 18, 19) and not st["active"], st
-        if not any(os.environ.get(k) for k in ("COCONS_PANEL_DIAG", "COCONS_PANEL_FUSED", "COCONS_PANEL_FOLLOW", "COCONS_ENGINE_PAIR")):
+        if not any(os.environ.get(k) for k in ("COCONS_PANEL_FUSED", "COCONS_ENGINE_PAIR")):
             assert code in (0x112, 0x212), hex(code)
         assert abs(v2 - want) <= N2LL_RTOL * abs(want)
     finally:
@@ -441,9 +441,10 @@ def test_engine_pair_same_bits_as_one_workgroup(gx, gy):
 
 
 @pytest.mark.parametrize("gx,gy", [(33, 31), (45, 47), (64, 64), (72, 64)])
-def test_fused_panel_same_bits_as_three_launches(gx, gy):
-    """The panel of a two-tile block in one launch (COCONS_PANEL_FUSED, chol.hip panel_pair_kernel: solve | in-panel update | solve
-    with both strips in registers) against the three launches it replaces: same operations, same order -- identical bits."""
+def test_following_panel_same_bits_as_three_launches(gx, gy):
+    """The panel of a two-tile block in one launch whose strips follow the engine pair's tiles (COCONS_PANEL_FUSED, chol.hip
+    panel_pair_kernel: solve | in-panel update | solve with both strips in registers), with two workgroups per strip in every
+    panel and with one, against the three launches it replaces: same operations, same order -- identical bits."""
     import cocons_amd as ca
     from cocons_amd import _lib, workloads as wl
     if ENGINE_OFF:
@@ -465,20 +466,12 @@ def test_fused_panel_same_bits_as_three_launches(gx, gy):
         _lib.check(L.cocons_debug_tune(b"panel_split", 0), "tune")       # (one workgroup per strip instead of two)
         v4, p4 = fit.neg2loglik_core(th)
         assert v4 == v1 and np.array_equal(p4, p1)
-        _lib.check(L.cocons_debug_tune(b"panel_diag", 0), "tune")        # (the next diagonal block by the update launch again)
-        v3, p3 = fit.neg2loglik_core(th)
-        assert v3 == v1 and np.array_equal(p3, p1)
-        _lib.check(L.cocons_debug_tune(b"panel_follow", 0), "tune")      # (its strips wait for out[t] / out[t+1] and fetch the factor)
-        v2, p2 = fit.neg2loglik_core(th)
         _lib.check(L.cocons_debug_tune(b"panel_fused", 0), "tune")
         v0, p0 = fit.neg2loglik_core(th)
         assert fit.engine_state()["active"]
         assert v1 == v0 and np.array_equal(p1, p0)
-        assert v2 == v0 and np.array_equal(p2, p0)
     finally:
         _lib.check(L.cocons_debug_tune(b"panel_fused", int(os.environ.get("COCONS_PANEL_FUSED", "1"))), "tune")
-        _lib.check(L.cocons_debug_tune(b"panel_follow", int(os.environ.get("COCONS_PANEL_FOLLOW", "1"))), "tune")
-        _lib.check(L.cocons_debug_tune(b"panel_diag", int(os.environ.get("COCONS_PANEL_DIAG", "1"))), "tune")
         _lib.check(L.cocons_debug_tune(b"panel_split", int(os.environ.get("COCONS_PANEL_SPLIT", "32"))), "tune")
 
 
