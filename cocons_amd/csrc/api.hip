@@ -117,17 +117,50 @@ static hipError_t upload_canon(double *dst, const double *src, size_t count, hip
     return e;
 }
 
-// One device allocation of a one-shot entry point, freed on every way out of it.
+// One owned device allocation and its element count: a local of a one-shot entry point (freed on every way out of it) or a
+// member of a handle or of one of its states (freed with it).  Empty: null with count 0 -- also after an allocation failed.
+// A buffer frees its memory only in the process that allocated it: a forked child that drops a handle abandons the
+// parent's device memory and makes no HIP call on a runtime it does not own (cocons_fit_destroy).
 template <class T> class DevBuf {
     T *p_ = nullptr;
+    size_t n_ = 0;
+    pid_t pid_ = 0;
 public:
     DevBuf() = default;
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
-    DevBuf(DevBuf &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
-    DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p_, o.p_); return *this; }
-    ~DevBuf() { hipFree(p_); }
-    hipError_t alloc(size_t count) { hipFree(p_); p_ = nullptr; return hipMalloc(&p_, count * sizeof(T)); }
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_), n_(o.n_), pid_(o.pid_) { o.p_ = nullptr; o.n_ = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p_, o.p_); std::swap(n_, o.n_); std::swap(pid_, o.pid_); return *this; }
+    ~DevBuf() { reset(); }
+    void reset()
+    {
+        if (p_ && pid_ == getpid()) hipFree(p_);
+        p_ = nullptr; n_ = 0;
+    }
+    hipError_t alloc(size_t count)
+    {
+        reset();
+        hipError_t e = hipMalloc(&p_, count * sizeof(T));
+        if (e != hipSuccess) { p_ = nullptr; return e; }
+        n_ = count; pid_ = getpid();
+        return e;
+    }
+    // Hold at least (exact: exactly) count elements.  Nothing to do: no HIP call at all -- this sits on the path of every
+    // evaluation.  Otherwise: drain the handle's main stream s and its engine's stream s2 (may be null) -- work in flight may
+    // still use the old memory --, free, allocate and, with fill >= 0, set every byte to fill on s (not waited for).
+    // *grew (may be null): whether the buffer is a new allocation.
+    hipError_t reserve(size_t count, hipStream_t s, hipStream_t s2, int fill = -1, bool exact = false, bool *grew = nullptr)
+    {
+        if (grew) *grew = false;
+        if (exact ? n_ == count : n_ >= count) return hipSuccess;
+        hipError_t e = hipStreamSynchronize(s);
+        if (e == hipSuccess && s2) e = hipStreamSynchronize(s2);
+        if (e == hipSuccess) e = alloc(count);
+        if (e == hipSuccess && fill >= 0) e = hipMemsetAsync(p_, fill, count * sizeof(T), s);
+        if (grew) *grew = e == hipSuccess;
+        return e;
+    }
+    size_t count() const { return n_; }
     T *get() const { return p_; }
     operator T *() const { return p_; }
 };
@@ -314,129 +347,130 @@ static void rccl_comm_destroy(ncclComm_t c)
     } while (0)
 
 // ---------------------------------------------------------------------------
+// Every device buffer of the handle is a DevBuf member (freed with the handle, cocons_fit_destroy), every host container a
+// member by value; a feature that needs another buffer declares one.
 struct cocons_fit {
-    int n, p, r, q, device;
-    pid_t pid;
-    int npad, nt;            // padded order, tiles of 128
-    int rhs_cap;             // rows reserved under the matrix (multiple of 128)
-    int rhs_act;             // rows under the matrix the CURRENT operation uses (multiple of 128, <= rhs_cap)
-    size_t lda;
-    hipStream_t stream;
-    bool own_stream;
-    double *dX, *dlocs, *dz, *dxb;
-    double *dloc;            // LOCP_FIELDS x npad
-    double *dA;
-    size_t dA_elems;         // doubles allocated at dA: lda * npad, or more once a gradient call has grown it (grad_prepare)
-    double *dinv;            // 2 x 8 x 256
-    int *dinfo;
-    double *dout;            // reductions
-    double *hout;            // pinned mirror
-    int *hinfo, *hinfo_init = nullptr;
-    double smooth_limits[2];
-    size_t out_cap;
-    // predict scratch
-    double *dlocp, *dXp, *dlocsp, *dstoch, *dquad, *dred;
-    int pred_cap;
+    cocons_fit();
+    ~cocons_fit();           // (both defined behind GradState: the states held by unique_ptr are complete types there)
+    int n = 0, p = 0, r = 0, q = 0, device = 0;
+    pid_t pid = 0;
+    int npad = 0, nt = 0;    // padded order, tiles of 128
+    int rhs_cap = 0;         // rows reserved under the matrix (multiple of 128)
+    int rhs_act = 0;         // rows under the matrix the CURRENT operation uses (multiple of 128, <= rhs_cap)
+    size_t lda = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    DevBuf<double> dX, dlocs, dz, dxb;
+    DevBuf<double> dloc;     // LOCP_FIELDS x npad
+    DevBuf<double> dA;       // lda * npad doubles, or more once a gradient call has grown it (grad_prepare)
+    DevBuf<double> dinv;     // 2 x 8 x 256
+    DevBuf<double> dinfo_out;     // ONE allocation: the two info words, then the reductions
+    int *dinfo = nullptr;         // (view of dinfo_out)
+    double *dout = nullptr;       // reductions (view of dinfo_out)
+    double *hout = nullptr;       // pinned mirror (hinfo, hout, hinfo_init: one pinned allocation, freed through hinfo)
+    int *hinfo = nullptr, *hinfo_init = nullptr;
+    double smooth_limits[2] = {0, 0};
+    size_t out_cap = 0;
+    // predict scratch (pred_reserve)
+    DevBuf<double> dlocp, dXp, dlocsp, dstoch, dquad, dred;
     // sharded state
-    int rank, world, nrhs_cur;
-    int nslot;                    // > 0: the last nslot of the npad rows / columns are SLOTS (npad = n + nslot): columns with a huge
+    int rank = 0, world = 1, nrhs_cur = 0;
+    int nslot = 0;                // > 0: the last nslot of the npad rows / columns are SLOTS (npad = n + nslot): columns with a huge
                                   // diagonal and nothing else, rows that hold the right-hand sides of an evaluation (at most nslot
                                   // of them) INSIDE the last tile of the matrix -- no tile row under the matrix (enqueue_eval)
-    int n_user, pad0;             // n = pad0 + n_user: dense handles keep pad0 = npad - n_user placeholder observations IN FRONT
+    int n_user = 0, pad0 = 0;     // n = pad0 + n_user: dense handles keep pad0 = npad - n_user placeholder observations IN FRONT
                                   // of the caller's (their columns are made unit vectors before every factorisation,
                                   // launch_front_identity), so that n == npad and no padding sits in the trailing matrix
-    double *xbuf[2];
-    size_t xbuf_bytes;
-    bool xbuf_own;
-    hipEvent_t ev[8];
-    hipStream_t stream2;          // stream the resident diagonal-tile engine is launched on
-    hipEvent_t ev_eng;            // orders the engine launch behind the reset of its flag words
-    unsigned *dflags;             // flags_cap words each: in[t], out[t], xr[t] (see launch_potrf_engine); 64: the alive word;
+    DevBuf<double> xbuf[2];       // exchange buffers of the sharded evaluation (shard_prepare)
+    hipEvent_t ev[8] = {};
+    hipStream_t stream2 = nullptr;     // stream the resident diagonal-tile engine is launched on
+    hipEvent_t ev_eng = nullptr;  // orders the engine launch behind the reset of its flag words
+    DevBuf<unsigned> dflags;      // flags_cap words each: in[t], out[t], xr[t] (see launch_potrf_engine); 64: the alive word;
                                   // flags_cap: tile counters of the trailing updates
-    int flags_cap;
-    bool engine_ok;               // false: this handle never uses the resident engine (batch slots, band-limited taper fits)
-    bool engine_live;             // the engine of the NEXT factorize call is already launched (engine_start)
-    bool engine_used;             // the factorisation enqueued last runs on the engine schedule
+    int flags_cap = 0;            // (also the stride between in[], out[] and xr[]: not just dflags' count)
+    bool engine_ok = false;       // false: this handle never uses the resident engine (batch slots, band-limited taper fits)
+    bool engine_live = false;     // the engine of the NEXT factorize call is already launched (engine_start)
+    bool engine_used = false;     // the factorisation enqueued last runs on the engine schedule
     int border_clean = -1;        // nr >= 0: the rows [nr, rhs_act) under the matrix are known to be exactly zero in every column
                                   // (they were zeroed, and a SUCCESSFUL factorisation keeps zero rows zero): the next
                                   // evaluation with the same nr does not zero them again (-1: unknown)
     int border_pending = -1;      // what border_clean becomes when the operation in flight turns out to have succeeded
-    bool engine_active_last;      // the last COMPLETED operation ran on the engine schedule (cocons_fit_engine_state)
-    int engine_skip;              // operations still to run on the plain schedule after a hand-off timed out (back-off)
-    int engine_fails;             // consecutive time-outs (the back-off doubles with each, up to 64 operations)
-    int engine_retries;           // time-outs in the life of the handle, each answered by one repeat on the plain schedule
-    int engine_last_abort;        // abort word of the last time-out (who gave up: see info_status)
-    long long engine_ops;         // operations enqueued on the engine schedule so far (the first one's gate is patient)
+    bool engine_active_last = false;   // the last COMPLETED operation ran on the engine schedule (cocons_fit_engine_state)
+    int engine_skip = 0;          // operations still to run on the plain schedule after a hand-off timed out (back-off)
+    int engine_fails = 0;         // consecutive time-outs (the back-off doubles with each, up to 64 operations)
+    int engine_retries = 0;       // time-outs in the life of the handle, each answered by one repeat on the plain schedule
+    int engine_last_abort = 0;    // abort word of the last time-out (who gave up: see info_status)
+    long long engine_ops = 0;     // operations enqueued on the engine schedule so far (the first one's gate is patient)
     // dependency-driven schedule (factorize_dag): second buffer shaped like dA, tile inverses, task words, step table
-    double *dP; size_t dP_elems;
-    double *dWt; int dWt_tiles;
-    double *dpart;                // early halves of the split diagonal-block tiles (2 x 16 x 64 x 64 doubles)
-    unsigned *ddag; size_t ddag_words;      // [queue (64 words)] [tdone] [pdone]
-    void *ddag_steps; int dag_nsteps; unsigned dag_ntasks;
-    int dag_key[12];              // (nt, mt, trim, kskip, lead, min_tiles, lead2, lead3, order, xcd, bw, bh) the step table was built for
-    unsigned *ddag_ftab; size_t ddag_ftab_words;   // which tile every far tile task is (dag_build_steps' table), device copy
-    int dag_xcd_g;                // chunk exponent of the XCD-aware deal the table was built for (0: one counter)
-    bool dag_have_ftab;           // the current step table comes with a far-tile table
-    size_t ddag_xcnt_off;         // offset (words) of the XCDs' task counters inside ddag
-    unsigned long long *ddag_trace; size_t dag_trace_tasks;   // diagnostics (cocons_debug_tune("dag_trace", 1)): 4 stamps per task
-    size_t dag_trace_elems;       // allocated 64-bit words of ddag_trace (5 per task + 8 per tile pair)
-    bool dag_next;                // the engine launched by engine_start is the DAG schedule's (publishes W and the second X)
-    int engine_pair_live;         // 1: the engine launched for the next factorisation has a pair partner (it counts itself in alive[2])
-    size_t smb_off, smb_elems;           // inside dmbox: strip mailboxes, one per diagonal block (the panel launch's next-diagonal-block
+    DevBuf<double> dP;
+    DevBuf<double> dWt;           // one 128 x 128 tile per tile column
+    DevBuf<double> dpart;         // early halves of the split diagonal-block tiles (2 x 16 x 64 x 64 doubles)
+    DevBuf<unsigned> ddag;        // [queue (64 words)] [tdone] [pdone]
+    DevBuf<DagStepHost> ddag_steps; int dag_nsteps = 0; unsigned dag_ntasks = 0;
+    int dag_key[12] = {};         // (nt, mt, trim, kskip, lead, min_tiles, lead2, lead3, order, xcd, bw, bh) the step table was built for
+    DevBuf<unsigned> ddag_ftab;   // which tile every far tile task is (dag_build_steps' table), device copy
+    int dag_xcd_g = 0;            // chunk exponent of the XCD-aware deal the table was built for (0: one counter)
+    bool dag_have_ftab = false;   // the current step table comes with a far-tile table
+    size_t ddag_xcnt_off = 0;     // offset (words) of the XCDs' task counters inside ddag
+    DevBuf<unsigned long long> ddag_trace;   // diagnostics (cocons_debug_tune("dag_trace", 1)): 4 stamps per task, 5 words per
+    size_t dag_trace_tasks = 0;              // task + 8 per tile pair allocated
+    bool dag_next = false;        // the engine launched by engine_start is the DAG schedule's (publishes W and the second X)
+    int engine_pair_live = 0;     // 1: the engine launched for the next factorisation has a pair partner (it counts itself in alive[2])
+    size_t smb_off = 0, smb_elems = 0;   // inside dmbox: strip mailboxes, one per diagonal block (the panel launch's next-diagonal-block
                                          // update), and xmb_off: the panel launch's exchange mailboxes, one per 64-row strip (split panel)
-    size_t xmb_off, xmb_elems;
-    double *dmbox; size_t dmbox_elems;   // one mailbox per tile (mbox_reset): the engine's pair mode, the panel kernel and potrf_solve's
+    size_t xmb_off = 0, xmb_elems = 0;
+    DevBuf<double> dmbox;                // one mailbox per tile (mbox_reset): the engine's pair mode, the panel kernel and potrf_solve's
                                          // followers read a tile's factor from there while it is being formed
-    bool follow_used, follow_off;        // the operation being enqueued used launch_potrf_follow; it timed out once on this handle: off
-    double enq_host_us; long long enq_calls;      // (diagnostics) host time spent enqueueing evaluations, calls: cocons_debug_host_enqueue
-    bool dag_used;                // the factorisation enqueued last ran the DAG schedule: its factor is split over dA and dP
-    double dag_flops; int dag_events;   // profile runs: update flops inside the DAG launch; 1 = the first event pair is that launch
+    bool follow_used = false, follow_off = false;   // the operation being enqueued used launch_potrf_follow; it timed out once on this handle: off
+    double enq_host_us = 0; long long enq_calls = 0;   // (diagnostics) host time spent enqueueing evaluations, calls: cocons_debug_host_enqueue
+    bool dag_used = false;        // the factorisation enqueued last ran the DAG schedule: its factor is split over dA and dP
+    double dag_flops = 0; int dag_events = 0;   // profile runs: update flops inside the DAG launch; 1 = the first event pair is that launch
     // taper fit (cocons_fit_create_taper): the spam pattern (1-based CSR) with the taper's entries; the
     // -2 log-likelihood is then that of the TAPERED covariance, evaluated through the dense factorisation
-    int taper_nnz;                // > 0: taper fit
-    int *d_tci, *d_trp;
-    double *d_tval;               // taper entries (constant)
-    std::vector<int> *taper_hi;   // envelope of the (reordered) pattern per tile column: see FactorView::hi
-    int *d_thi; int taper_maxband; // device copy of taper_hi and max_c (hi[c] - c)
-    int skew;                     // > 0: the factorisation buffer is PACKED (kernels.h band_index): every tile column keeps
+    int taper_nnz = 0;            // > 0: taper fit
+    DevBuf<int> d_tci, d_trp;
+    DevBuf<double> d_tval;        // taper entries (constant)
+    std::vector<int> taper_hi;    // envelope of the (reordered) pattern per tile column: see FactorView::hi (empty: none)
+    DevBuf<int> d_thi; int taper_maxband = 0; // device copy of taper_hi and max_c (hi[c] - c)
+    int skew = 0;                 // > 0: the factorisation buffer is PACKED (kernels.h band_index): every tile column keeps
                                   // `skew` (= taper_maxband) tile rows from its diagonal tile down plus the rows under the
                                   // matrix -- O(n x bandwidth) doubles instead of n^2
-    std::vector<int> *taper_inv;  // position of the caller's observation i in the handle's order (reverse Cuthill-McKee)
-    std::vector<int> *h_trp, *h_tci;   // host copy of the full (symmetric) pattern and taper entries in the handle's order:
-    std::vector<double> *h_tval;       // what a twin in another order is built from (O(nnz))
-    cocons_fit *taper_twin;       // lazily created taper handle in the order of the last pivot cocons_sim_taper was given
-    std::vector<int> *twin_perm;  // that order: twin position k holds the observation at position twin_perm[k] of this handle
-    float sim_ms[3];              // last cocons_sim_taper: assembly + factorisation, band product, gather (device events)
+    std::vector<int> taper_inv;   // position of the caller's observation i in the handle's order (reverse Cuthill-McKee)
+    std::vector<int> h_trp, h_tci;     // host copy of the full (symmetric) pattern and taper entries in the handle's order:
+    std::vector<double> h_tval;        // what a twin in another order is built from (O(nnz))
+    cocons_fit *taper_twin = nullptr;  // lazily created taper handle in the order of the last pivot cocons_sim_taper was given
+    std::vector<int> twin_perm;   // that order: twin position k holds the observation at position twin_perm[k] of this handle
+    float sim_ms[3] = {0, 0, 0};  // last cocons_sim_taper: assembly + factorisation, band product, gather (device events)
     // collectives of the natively sharded evaluation (see "native sharded evaluation" below)
-    int coll_kind;                // 0 none, 1 RCCL communicator, 2 caller-provided transport
-    int coll_rank, coll_world;
-    ncclComm_t comm;
-    bool comm_own;                // the communicator was created by cocons_fit_comm_init (destroy it with the fit)
-    cocons_bcast_fn cb_bcast;
-    cocons_allreduce_fn cb_allreduce;
-    cocons_allgather_fn cb_allgather;
-    struct ShardState *shard;     // plan, buffers and events of the sharded evaluation (row-block ownership)
-    void *cb_user;
-    hipStream_t cstream;          // stream the bulk exchange (all-gather of the solved rows) is issued on
-    hipStream_t cstream_l;        // stream the 0.56 MB broadcasts of the factored diagonal blocks are issued on: the chain from one
+    int coll_kind = 0;            // 0 none, 1 RCCL communicator, 2 caller-provided transport
+    int coll_rank = 0, coll_world = 0;
+    ncclComm_t comm = nullptr;
+    bool comm_own = false;        // the communicator was created by cocons_fit_comm_init (destroy it with the fit)
+    cocons_bcast_fn cb_bcast = nullptr;
+    cocons_allreduce_fn cb_allreduce = nullptr;
+    cocons_allgather_fn cb_allgather = nullptr;
+    std::unique_ptr<struct ShardState> shard;   // plan, buffers and events of the sharded evaluation (row-block ownership)
+    void *cb_user = nullptr;
+    hipStream_t cstream = nullptr;     // stream the bulk exchange (all-gather of the solved rows) is issued on
+    hipStream_t cstream_l = nullptr;   // stream the 0.56 MB broadcasts of the factored diagonal blocks are issued on: the chain from one
                                   // diagonal block to the next never queues behind an all-gather (== cstream when the
                                   // broadcasts have no communicator of their own)
-    ncclComm_t comm_l;            // RCCL: a second communicator over the same ranks (ncclCommSplit) for those broadcasts --
+    ncclComm_t comm_l = nullptr;  // RCCL: a second communicator over the same ranks (ncclCommSplit) for those broadcasts --
                                   // operations of ONE communicator are serialised whatever stream they are given; null: comm
-    bool comm_l_own;
-    double *dcoll;                // device staging of the final all-reduce (RCCL)
-    double upd_flops;             // algorithmic flops of the event-timed trailing updates (profile runs)
+    bool comm_l_own = false;
+    DevBuf<double> dcoll;         // device staging of the final all-reduce (RCCL)
+    double upd_flops = 0;         // algorithmic flops of the event-timed trailing updates (profile runs)
     // host copies of the inputs + lazily created clones: the slots of cocons_neg2loglik_batch
-    std::vector<double> *h_locs, *h_X, *h_z, *h_xb;
-    std::vector<cocons_fit *> *slots;
-    bool sorted;                  // observations are stored in Morton order (see fit_create_impl)
-    cocons_fit *unsorted;         // lazily created clone in the ORIGINAL order (marginal simulation)
-    std::recursive_mutex *op_mu;  // held by every entry point for as long as it works on this handle (FIT_ENTER), and by another
+    std::vector<double> h_locs, h_X, h_z, h_xb;
+    std::vector<cocons_fit *> slots;
+    bool sorted = false;          // observations are stored in Morton order (see fit_create_impl)
+    cocons_fit *unsorted = nullptr;    // lazily created clone in the ORIGINAL order (marginal simulation)
+    std::recursive_mutex op_mu;   // held by every entry point for as long as it works on this handle (FIT_ENTER), and by another
                                   // handle's stream self-test while it launches probe kernels on this handle's streams
                                   // (engine_warm: try_lock under the registry's lock -- a busy handle is not probed, a probed one
-                                  // can neither be used nor destroyed until the probe is over).  A pointer: the struct is memset
-    struct KrigeState *krige;     // kriging state (cocons_krige_prepare): one factor of Sigma(theta) held apart from dA
-    struct GradState *grad;       // scratch of cocons_neg2loglik_grad_dense (allocated on first use)
+                                  // can neither be used nor destroyed until the probe is over)
+    std::unique_ptr<struct KrigeState> krige;   // kriging state (cocons_krige_prepare): one factor of Sigma(theta) held apart from dA
+    std::unique_ptr<struct GradState> grad;     // scratch of cocons_neg2loglik_grad_dense (allocated on first use)
 };
 
 // Kriging state of a dense handle (cocons_krige_prepare / _apply / _release).  Everything apply reads lives here, owned by
@@ -454,8 +488,7 @@ struct KrigeState {
     long long bytes = 0;          // device bytes held
 };
 
-static void shard_state_free(struct ShardState *S);
-static void grad_state_free(cocons_fit *f);
+static void shard_events_destroy(struct ShardState *S);
 
 // Every live handle of the process: engine_warm tests a new handle's streams against the streams of the others (a resident
 // engine of one handle must not share a hardware queue with the main stream of another: the batch slots and callers with
@@ -484,7 +517,7 @@ static int fit_check(cocons_fit *f)
 // same handle waits here --; different handles may be used, created and destroyed from different threads concurrently.
 #define FIT_ENTER(f)                                                   \
     if (int rc__ = fit_check(f)) return rc__;                          \
-    std::lock_guard<std::recursive_mutex> op_guard__(*(f)->op_mu)
+    std::lock_guard<std::recursive_mutex> op_guard__((f)->op_mu)
 
 static int fit_alloc_matrix(cocons_fit *f, int rhs_rows)
 {
@@ -492,13 +525,12 @@ static int fit_alloc_matrix(cocons_fit *f, int rhs_rows)
     f->rhs_act = cap;        // a buffer grown by an earlier predict call must not slow later evaluations
     f->border_clean = -1; f->border_pending = -1;      // every user of the rows under the matrix comes through here
     if (f->dA && cap <= f->rhs_cap) return 0;
-    if (f->dA) { HIPCHK(hipFree(f->dA)); f->dA = nullptr; f->dA_elems = 0; }
     f->rhs_cap = cap;
     f->lda = (size_t)(f->skew > 0 ? f->skew * TILE : f->npad) + cap;
-    HIPCHK(hipMalloc(&f->dA, f->lda * (size_t)f->npad * sizeof(double)));
-    f->dA_elems = f->lda * (size_t)f->npad;
+    // (exactly lda * npad: a buffer that a gradient call had grown goes back to the objective's size with the new shape)
+    HIPCHK(f->dA.reserve(f->lda * (size_t)f->npad, f->stream, f->stream2, -1, true));
     // never-written parts must not hold NaN bit patterns: a band-limited factorisation only clears its envelope, and
-    // 0 * garbage must stay 0 whatever the allocator hands back
+    // 0 * garbage must stay 0 whatever the allocator hands back (every time the buffer takes a new shape)
     HIPCHK(hipMemsetAsync(f->dA, 0, f->lda * (size_t)f->npad * sizeof(double), f->stream));
     HIPCHK(hipStreamSynchronize(f->stream));
     return 0;
@@ -510,42 +542,33 @@ extern "C" void cocons_fit_destroy(cocons_fit *f)
     // out of the registry first (no stream self-test of another thread can find the handle any more), then wait for one that
     // found it earlier and is still launching probe kernels on its streams (engine_warm holds op_mu for that long)
     registry_remove(f);
-    if (f->op_mu) { f->op_mu->lock(); f->op_mu->unlock(); }
+    f->op_mu.lock(); f->op_mu.unlock();
+    // Only the process that created the handle touches the device.  A forked child makes NO HIP call here, on a runtime it
+    // does not own: streams, events, the pinned mirror and the clones are left alone, and `delete f` below gives back host
+    // memory only -- a DevBuf abandons memory that another process allocated instead of freeing it.
+    hipStream_t last[2] = {nullptr, nullptr};
     if (f->pid == getpid()) {
         hipSetDevice(f->device);
         if (f->stream) hipStreamSynchronize(f->stream);
         if (f->stream2) hipStreamSynchronize(f->stream2);
-        hipFree(f->dX); hipFree(f->dlocs); hipFree(f->dz); hipFree(f->dxb); hipFree(f->dloc);
-        hipFree(f->dA); hipFree(f->dinv); hipFree(f->dinfo);      // (dout is part of dinfo's allocation)
-        hipFree(f->dlocp); hipFree(f->dXp); hipFree(f->dlocsp); hipFree(f->dstoch); hipFree(f->dquad); hipFree(f->dred);
-        if (f->xbuf_own) { hipFree(f->xbuf[0]); hipFree(f->xbuf[1]); }
         hipHostFree(f->hinfo);                                  // (hout, hinfo_init: the same allocation)
         for (auto &e : f->ev) if (e) hipEventDestroy(e);
         if (f->ev_eng) hipEventDestroy(f->ev_eng);
-        hipFree(f->dflags);
-        if (f->dmbox) hipFree(f->dmbox);
-        hipFree(f->dP); hipFree(f->dWt); hipFree(f->ddag); hipFree(f->ddag_steps); hipFree(f->ddag_trace); hipFree(f->dpart);
-        hipFree(f->ddag_ftab);
-        hipFree(f->d_tci); hipFree(f->d_trp); hipFree(f->d_tval); hipFree(f->d_thi);
         if (f->cstream_l && f->cstream_l != f->cstream) { hipStreamSynchronize(f->cstream_l); hipStreamDestroy(f->cstream_l); }
         if (f->cstream) { hipStreamSynchronize(f->cstream); hipStreamDestroy(f->cstream); }
-        shard_state_free(f->shard);
-        hipFree(f->dcoll);
+        shard_events_destroy(f->shard.get());
         if (f->comm_l && f->comm_l_own) rccl_comm_destroy(f->comm_l);
         if (f->comm && f->comm_own) rccl_comm_destroy(f->comm);
-        if (f->slots) { for (auto c : *f->slots) cocons_fit_destroy(c); delete f->slots; f->slots = nullptr; }
-        if (f->unsorted) { cocons_fit_destroy(f->unsorted); f->unsorted = nullptr; }
-        if (f->taper_twin) { cocons_fit_destroy(f->taper_twin); f->taper_twin = nullptr; }
-        delete f->krige; f->krige = nullptr;                    // (its buffers: the main stream is drained above)
-        grad_state_free(f);
-        if (f->stream2) hipStreamDestroy(f->stream2);
-        if (f->own_stream && f->stream) hipStreamDestroy(f->stream);
+        for (auto c : f->slots) cocons_fit_destroy(c);
+        if (f->unsorted) cocons_fit_destroy(f->unsorted);
+        if (f->taper_twin) cocons_fit_destroy(f->taper_twin);
+        last[0] = f->stream2;
+        if (f->own_stream) last[1] = f->stream;
     }
-    delete f->h_locs; delete f->h_X; delete f->h_z; delete f->h_xb;
-    delete f->taper_hi; delete f->taper_inv;
-    delete f->h_trp; delete f->h_tci; delete f->h_tval; delete f->twin_perm;
-    delete f->op_mu;
+    // Every device buffer goes HERE -- the DevBuf members of the handle and of its krige, gradient and shard states --: after
+    // every stream that used them was drained (above), before the engine's and the own main stream are destroyed (below, last).
     delete f;
+    for (hipStream_t s : last) if (s) hipStreamDestroy(s);
 }
 
 static int engine_warm(cocons_fit *f);
@@ -561,8 +584,6 @@ static cocons_fit *fit_create_impl(int n, int p, int r, int q, const double *loc
         return nullptr;
     }
     cocons_fit *f = new cocons_fit();
-    memset(f, 0, sizeof *f);
-    f->op_mu = new std::recursive_mutex();
     f->n = n; f->p = p; f->r = r; f->q = q;
     f->device = device < 0 ? 0 : device;
     f->pid = getpid();
@@ -570,7 +591,6 @@ static cocons_fit *fit_create_impl(int n, int p, int r, int q, const double *loc
     f->nt = f->npad / TILE;
     f->smooth_limits[0] = smooth_limits[0];
     f->smooth_limits[1] = smooth_limits[1];
-    f->world = 1;
 #define CK(expr)                                                                  \
     do {                                                                          \
         hipError_t e__ = (expr);                                                  \
@@ -636,13 +656,10 @@ static cocons_fit *fit_create_impl(int n, int p, int r, int q, const double *loc
             }
         }
     }
-    f->h_locs = new std::vector<double>(locs, locs + (size_t)2 * n);      // host copies: ORIGINAL order
-    f->h_X = new std::vector<double>(X, X + (size_t)n * p);
-    f->h_z = new std::vector<double>();
-    if (r > 0) f->h_z->assign(z, z + (size_t)n * r);
-    f->h_xb = new std::vector<double>();
-    if (q > 0) f->h_xb->assign(x_betas, x_betas + (size_t)n * q);
-    f->sorted = false;
+    f->h_locs.assign(locs, locs + (size_t)2 * n);      // host copies: ORIGINAL order
+    f->h_X.assign(X, X + (size_t)n * p);
+    if (r > 0) f->h_z.assign(z, z + (size_t)n * r);
+    if (q > 0) f->h_xb.assign(x_betas, x_betas + (size_t)n * q);
     for (int i = 0; i < n; ++i)
         if (perm[i] != i) { f->sorted = true; break; }
     // Identity padding in FRONT (handles whose internal order is theirs to choose, i.e. allow_sort): pad0 placeholder
@@ -681,30 +698,30 @@ static cocons_fit *fit_create_impl(int n, int p, int r, int q, const double *loc
     if (q > 0) x_betas = pxb.data();
     n = nint;                     // from here on: the internal problem
     f->n = n;
-    CK(hipMalloc(&f->dX, (size_t)n * p * sizeof(double)));
-    CK(hipMalloc(&f->dlocs, (size_t)n * 2 * sizeof(double)));
+    CK(f->dX.alloc((size_t)n * p));
+    CK(f->dlocs.alloc((size_t)n * 2));
     CK(hipMemcpyAsync(f->dX, X, (size_t)n * p * sizeof(double), hipMemcpyHostToDevice, f->stream));
     CK(hipMemcpyAsync(f->dlocs, locs, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice, f->stream));
     if (r > 0) {
-        CK(hipMalloc(&f->dz, (size_t)n * r * sizeof(double)));
+        CK(f->dz.alloc((size_t)n * r));
         CK(hipMemcpyAsync(f->dz, z, (size_t)n * r * sizeof(double), hipMemcpyHostToDevice, f->stream));
     }
     if (q > 0) {
-        CK(hipMalloc(&f->dxb, (size_t)n * q * sizeof(double)));
+        CK(f->dxb.alloc((size_t)n * q));
         CK(hipMemcpyAsync(f->dxb, x_betas, (size_t)n * q * sizeof(double), hipMemcpyHostToDevice, f->stream));
     }
     CK(hipStreamSynchronize(f->stream));      // the staging vectors above go out of scope
-    CK(hipMalloc(&f->dloc, (size_t)LOCP_FIELDS * f->npad * sizeof(double)));
-    CK(hipMalloc(&f->dinv, 2 * 8 * 256 * sizeof(double)));
+    CK(f->dloc.alloc((size_t)LOCP_FIELDS * f->npad));
+    CK(f->dinv.alloc(2 * 8 * 256));
     // the two info words -- [0] failing minor (atomicMin), [1] abort word of the engine hand-offs -- sit in the 8 bytes in
     // front of the reduction outputs, on the device and in the pinned host mirror: an evaluation brings both home in ONE copy
     int nr_max = r + (q > p ? q : p);
     f->out_cap = (size_t)(1 + nr_max * nr_max) * (size_t)(f->nt + 2);
     {
-        double *dbase = nullptr, *hbase = nullptr;
-        CK(hipMalloc(&dbase, (f->out_cap + 1) * sizeof(double)));
+        double *hbase = nullptr;
+        CK(f->dinfo_out.alloc(f->out_cap + 1));
         CK(hipHostMalloc(&hbase, (f->out_cap + 2) * sizeof(double)));
-        f->dinfo = (int *)dbase; f->dout = dbase + 1;
+        f->dinfo = (int *)f->dinfo_out.get(); f->dout = f->dinfo_out + 1;
         f->hinfo = (int *)hbase; f->hout = hbase + 1;
         f->hinfo_init = (int *)(hbase + 1 + f->out_cap);      // constant {0x7f7f7f7f, 0}: reset_info's source
         f->hinfo_init[0] = 0x7f7f7f7f; f->hinfo_init[1] = 0;
@@ -724,7 +741,7 @@ static cocons_fit *fit_create_impl(int n, int p, int r, int q, const double *loc
     if (engine_warm(f) != 0) { cocons_fit_destroy(f); return nullptr; }
     // (return_locked: the caller goes on building the handle -- a batch slot, whose main stream may still be redrawn --, so it
     // enters the registry with its operation lock held and no other thread's stream self-test can touch it before it is done)
-    if (return_locked) f->op_mu->lock();
+    if (return_locked) f->op_mu.lock();
     registry_add(f);
     return f;
 }
@@ -822,6 +839,32 @@ extern "C" cocons_fit *cocons_fit_create_taper(int n, int p, int r, const double
                                 false);
 }
 
+// Device copies of a taper handle's pattern (lower triangle, nnz entries), taper entries and envelope (hi may be null: none):
+// from host vectors (taper_create_ordered) or device to device from another handle (clone_for_slot) on f's stream, drained.
+static int taper_pattern_to_device(cocons_fit *f, size_t nnz, const int *ci, const int *rp, const double *val, const int *hi,
+                                   bool from_host)
+{
+    auto copy = [&](void *dst, const void *src, size_t bytes) {
+        // (from the host: synchronous copies, i.e. on the NULL stream the library otherwise stays off, DESIGN.md section 4a --
+        // kept as it is: which hardware queue a process touches first is behaviour, see dag_prepare)
+        return from_host ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice)
+                         : hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, f->stream);
+    };
+    HIPCHK(f->d_tci.alloc(nnz));
+    HIPCHK(f->d_trp.alloc((size_t)f->n + 1));
+    HIPCHK(f->d_tval.alloc(nnz));
+    HIPCHK(copy(f->d_tci, ci, nnz * sizeof(int)));
+    HIPCHK(copy(f->d_trp, rp, ((size_t)f->n + 1) * sizeof(int)));
+    HIPCHK(copy(f->d_tval, val, nnz * sizeof(double)));
+    if (hi) {
+        HIPCHK(f->d_thi.alloc((size_t)f->nt));
+        HIPCHK(copy(f->d_thi, hi, (size_t)f->nt * sizeof(int)));
+    }
+    if (!from_host) HIPCHK(hipStreamSynchronize(f->stream));
+    f->taper_nnz = (int)nnz;
+    return 0;
+}
+
 // The taper handle of a validated pattern with its observations in the order perm (perm[new] = index in the order the
 // arguments come in).  check_fit: refuse, with a message that says so, a buffer larger than the device's free memory
 // (an order with a wide envelope: cocons_sim_taper's twin) before any allocation is tried.
@@ -854,13 +897,13 @@ static cocons_fit *taper_create_ordered(int n, int p, int r, const double *locs,
                                     true, true);       // (registered with its operation lock held: it is still being built)
     if (!f) return nullptr;
     // envelope per tile column: row i of the factor is non-zero from its first stored column on
-    f->taper_hi = new std::vector<int>(f->nt, 0);
-    f->taper_inv = new std::vector<int>(inv);
-    f->h_trp = new std::vector<int>(prp);
-    f->h_tci = new std::vector<int>(pci);
-    f->h_tval = new std::vector<double>(pte);
+    f->taper_hi.assign(f->nt, 0);
+    f->taper_inv = inv;
+    f->h_trp = prp;
+    f->h_tci = pci;
+    f->h_tval = pte;
     {
-        std::vector<int> &hi = *f->taper_hi;
+        std::vector<int> &hi = f->taper_hi;
         for (int c = 0; c < f->nt; ++c) hi[c] = c + 1 < f->nt ? c + 1 : f->nt;
         for (int i = 0; i < n; ++i) {
             int first = i;
@@ -903,12 +946,12 @@ static cocons_fit *taper_create_ordered(int n, int p, int r, const double *locs,
             snprintf(msg, sizeof msg, "%.2f GB (envelope of %d tile rows), %.2f GB free", bytes * 1e-9,
                      f->taper_maxband > 0 ? f->taper_maxband : f->nt, free_b * 1e-9);
             fail(-4, "the factor buffer of this order does not fit the device: %s", msg);
-            f->op_mu->unlock();
+            f->op_mu.unlock();
             cocons_fit_destroy(f);
             return nullptr;
         }
     }
-    if (fit_alloc_matrix(f, r + p) != 0) { f->op_mu->unlock(); cocons_fit_destroy(f); return nullptr; }
+    if (fit_alloc_matrix(f, r + p) != 0) { f->op_mu.unlock(); cocons_fit_destroy(f); return nullptr; }
     // the device keeps the lower triangle of the pattern only (the upper half is never evaluated)
     {
         int w2 = 0;
@@ -921,26 +964,16 @@ static cocons_fit *taper_create_ordered(int n, int p, int r, const double *locs,
         prp[n] = w2 + 1;
         nnz = w2;
     }
-    bool ok = hipMalloc(&f->d_tci, (size_t)nnz * sizeof(int)) == hipSuccess &&
-              hipMalloc(&f->d_trp, (size_t)(n + 1) * sizeof(int)) == hipSuccess &&
-              hipMalloc(&f->d_tval, (size_t)nnz * sizeof(double)) == hipSuccess &&
-              hipMemcpy(f->d_tci, pci.data(), (size_t)nnz * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(f->d_trp, prp.data(), (size_t)(n + 1) * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(f->d_tval, pte.data(), (size_t)nnz * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && !f->taper_hi->empty())
-        ok = hipMalloc(&f->d_thi, (size_t)f->nt * sizeof(int)) == hipSuccess &&
-             hipMemcpy(f->d_thi, f->taper_hi->data(), (size_t)f->nt * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) {
-        fail(-100, "cocons_fit_create_taper: device allocation or upload failed");
-        f->op_mu->unlock();
+    if (taper_pattern_to_device(f, nnz, pci.data(), prp.data(), pte.data(), f->taper_hi.empty() ? nullptr : f->taper_hi.data(),
+                                true) != 0) {
+        f->op_mu.unlock();
         cocons_fit_destroy(f);
         return nullptr;
     }
-    f->taper_nnz = nnz;
     // inside a narrow envelope the trailing updates are too short to hide the engine's hand-offs behind (4.9 against
     // 4.7 ms at n = 10^4): plain schedule
-    if (!f->taper_hi->empty()) f->engine_ok = false;
-    f->op_mu->unlock();
+    if (!f->taper_hi.empty()) f->engine_ok = false;
+    f->op_mu.unlock();
     return f;
 }
 
@@ -952,11 +985,11 @@ extern "C" int cocons_fit_same_data(cocons_fit *f, int n, int p, int r, int q, c
     if (!f || !locs || !X || !smooth_limits || f->taper_nnz > 0) return 0;
     if (f->n_user != n || f->p != p || f->r != r || f->q != q) return 0;
     if (f->smooth_limits[0] != smooth_limits[0] || f->smooth_limits[1] != smooth_limits[1]) return 0;
-    if (memcmp(f->h_locs->data(), locs, (size_t)2 * n * sizeof(double)) != 0) return 0;
-    if (memcmp(f->h_X->data(), X, (size_t)n * p * sizeof(double)) != 0) return 0;
-    if (r > 0 && (!z || memcmp(f->h_z->data(), z, (size_t)n * r * sizeof(double)) != 0)) return 0;
-    if (q > 0 && (!x_betas || f->h_xb->size() != (size_t)n * q ||
-                  memcmp(f->h_xb->data(), x_betas, (size_t)n * q * sizeof(double)) != 0)) return 0;
+    if (memcmp(f->h_locs.data(), locs, (size_t)2 * n * sizeof(double)) != 0) return 0;
+    if (memcmp(f->h_X.data(), X, (size_t)n * p * sizeof(double)) != 0) return 0;
+    if (r > 0 && (!z || memcmp(f->h_z.data(), z, (size_t)n * r * sizeof(double)) != 0)) return 0;
+    if (q > 0 && (!x_betas || f->h_xb.size() != (size_t)n * q ||
+                  memcmp(f->h_xb.data(), x_betas, (size_t)n * q * sizeof(double)) != 0)) return 0;
     return 1;
 }
 
@@ -1088,7 +1121,7 @@ static std::vector<double> host_trend(const cocons_fit *f, const double *mean)
     const int n = f->n;
     std::vector<double> tr(n, 0.0);
     for (int j = 0; j < f->p; ++j)
-        for (int i = 0; i < n; ++i) tr[i] += (*f->h_X)[(size_t)i + (size_t)j * n] * mean[j];
+        for (int i = 0; i < n; ++i) tr[i] += f->h_X[(size_t)i + (size_t)j * n] * mean[j];
     return tr;
 }
 
@@ -1117,7 +1150,7 @@ static FactorView main_view(cocons_fit *f)
 {
     FactorView v;
     v.A = f->dA; v.lda = f->lda; v.nt = f->nt; v.mt = f->nt + f->rhs_act / TILE;
-    v.hi = (f->taper_hi && !f->taper_hi->empty()) ? f->taper_hi->data() : nullptr;
+    v.hi = f->taper_hi.empty() ? nullptr : f->taper_hi.data();
     v.skew = f->skew;
     return v;
 }
@@ -1377,10 +1410,9 @@ static bool engine_wanted(cocons_fit *f, const FactorView &v)
 static int flags_reset(cocons_fit *f, int nt)
 {
     if (f->flags_cap < nt) {
-        if (f->stream2) HIPCHK(hipStreamSynchronize(f->stream2));
-        if (f->dflags) { HIPCHK(hipFree(f->dflags)); f->dflags = nullptr; }
-        f->flags_cap = round_up(nt + 8, 64);
-        HIPCHK(hipMalloc(&f->dflags, (4 * (size_t)f->flags_cap + 64) * sizeof(unsigned)));
+        const int cap = round_up(nt + 8, 64);
+        HIPCHK(f->dflags.reserve(4 * (size_t)cap + 64, f->stream, f->stream2));
+        f->flags_cap = cap;
     }
     HIPCHK(hipMemsetAsync(f->dflags, 0, (4 * (size_t)f->flags_cap + 64) * sizeof(unsigned), f->stream));
     return 0;
@@ -1397,13 +1429,7 @@ static int mbox_reset(cocons_fit *f, int nt, bool engine_schedule = true)
     const size_t smb = panel ? ((size_t)nt / 2 + 2) * PANEL_SMBOX_DOUBLES : 0;
     const size_t xmb = panel && tun().panel_split ? (2 * ((size_t)nt + 2) + 4) * PANEL_XMBOX_DOUBLES : 0;
     const size_t need = tiles + smb + xmb;
-    if (f->dmbox_elems < need) {
-        HIPCHK(hipStreamSynchronize(f->stream));
-        if (f->stream2) HIPCHK(hipStreamSynchronize(f->stream2));
-        if (f->dmbox) { HIPCHK(hipFree(f->dmbox)); f->dmbox = nullptr; f->dmbox_elems = 0; }
-        HIPCHK(hipMalloc(&f->dmbox, need * sizeof(double)));
-        f->dmbox_elems = need;
-    }
+    HIPCHK(f->dmbox.reserve(need, f->stream, f->stream2));
     f->smb_off = tiles; f->smb_elems = smb;
     f->xmb_off = tiles + smb; f->xmb_elems = xmb;
     // (the plain schedule uses the tiles' mailboxes only)
@@ -1467,10 +1493,10 @@ static int engine_warm(cocons_fit *f)
                 for (size_t i = g_registry.size(); i-- > 0 && others.size() < 4;) {      // the four most recent ones
                     cocons_fit *o = g_registry[i];
                     if (o == f || o->pid != f->pid || o->device != f->device || !o->own_stream || !o->stream || !o->stream2 ||
-                        !o->engine_ok || !o->op_mu->try_lock())
+                        !o->engine_ok || !o->op_mu.try_lock())
                         continue;
                     if (hipStreamQuery(o->stream) == hipSuccess && hipStreamQuery(o->stream2) == hipSuccess) others.push_back(o);
-                    else o->op_mu->unlock();
+                    else o->op_mu.unlock();
                 }
             }
             (void)hipGetLastError();
@@ -1485,7 +1511,7 @@ static int engine_warm(cocons_fit *f)
                     if (b == 0) { clash = 2; break; }
                 }
             }
-            for (cocons_fit *o : others) o->op_mu->unlock();      // (streams_run_concurrently drains both streams before it returns)
+            for (cocons_fit *o : others) o->op_mu.unlock();      // (streams_run_concurrently drains both streams before it returns)
             if (ok != 1 || clash == 0) break;
             hipStream_t &mine = clash == 1 ? f->stream2 : f->stream;
             losers.push_back(mine);
@@ -1538,23 +1564,9 @@ static bool dag_wanted(cocons_fit *f, const FactorView &v)
 static int dag_prepare(cocons_fit *f, const FactorView &v)
 {
     const size_t elems = v.lda * (size_t)f->npad;
-    if (f->dP_elems != elems) {
-        HIPCHK(hipStreamSynchronize(f->stream));
-        if (f->stream2) HIPCHK(hipStreamSynchronize(f->stream2));
-        if (f->dP) { HIPCHK(hipFree(f->dP)); f->dP = nullptr; f->dP_elems = 0; }
-        HIPCHK(hipMalloc(&f->dP, elems * sizeof(double)));
-        HIPCHK(hipMemsetAsync(f->dP, 0, elems * sizeof(double), f->stream));
-        f->dP_elems = elems;
-    }
-    if (!f->dpart) HIPCHK(hipMalloc(&f->dpart, (size_t)2 * 16 * 64 * 64 * sizeof(double)));
-    if (f->dWt_tiles < v.nt) {
-        HIPCHK(hipStreamSynchronize(f->stream));
-        if (f->stream2) HIPCHK(hipStreamSynchronize(f->stream2));
-        if (f->dWt) { HIPCHK(hipFree(f->dWt)); f->dWt = nullptr; }
-        HIPCHK(hipMalloc(&f->dWt, (size_t)v.nt * TILE * TILE * sizeof(double)));
-        HIPCHK(hipMemsetAsync(f->dWt, 0, (size_t)v.nt * TILE * TILE * sizeof(double), f->stream));   // zero above the diagonals, for good
-        f->dWt_tiles = v.nt;
-    }
+    HIPCHK(f->dP.reserve(elems, f->stream, f->stream2, 0, true));       // (the shape of the view exactly; zeroed when new)
+    if (!f->dpart) HIPCHK(f->dpart.alloc((size_t)2 * 16 * 64 * 64));
+    HIPCHK(f->dWt.reserve((size_t)v.nt * TILE * TILE, f->stream, f->stream2, 0));   // zero above the diagonals, for good
     const int kskip = (f->pad0 / 16) * 16;
     const int xcd_g = dag_xcd_group();
     const int key[12] = {v.nt, v.mt, v.trim, kskip, tun().dag_lead, tun().dag_min_tiles, tun().dag_lead2, tun().dag_lead3,
@@ -1566,18 +1578,13 @@ static int dag_prepare(cocons_fit *f, const FactorView &v)
         const unsigned ntasks = dag_build_steps(v.nt, v.mt, v.trim, kskip, tun().dag_lead, tun().dag_min_tiles, steps,
                                                 tun().dag_lead2, tun().dag_lead3, want_tab ? &ftab : nullptr, xcd_g,
                                                 tun().dag_order ? tun().dag_bw : 0, tun().dag_bh);
-        HIPCHK(hipStreamSynchronize(f->stream));
+        HIPCHK(hipStreamSynchronize(f->stream));      // (the table in place may be in use, whether or not a buffer below grows)
         if (f->stream2) HIPCHK(hipStreamSynchronize(f->stream2));
-        if (f->ddag_steps) { HIPCHK(hipFree(f->ddag_steps)); f->ddag_steps = nullptr; }
-        HIPCHK(hipMalloc(&f->ddag_steps, (steps.size() + 1) * sizeof(DagStepHost)));
+        HIPCHK(f->ddag_steps.reserve(steps.size() + 1, f->stream, f->stream2, -1, true));
         // (on the handle's own stream: the library never touches the NULL stream -- a synchronous hipMemcpy here gave it a
         // hardware queue of its own and shifted every later stream's assignment)
         HIPCHK(hipMemcpyAsync(f->ddag_steps, steps.data(), steps.size() * sizeof(DagStepHost), hipMemcpyHostToDevice, f->stream));
-        if (f->ddag_ftab_words < ftab.size()) {
-            if (f->ddag_ftab) { HIPCHK(hipFree(f->ddag_ftab)); f->ddag_ftab = nullptr; f->ddag_ftab_words = 0; }
-            HIPCHK(hipMalloc(&f->ddag_ftab, ftab.size() * sizeof(unsigned)));
-            f->ddag_ftab_words = ftab.size();
-        }
+        HIPCHK(f->ddag_ftab.reserve(ftab.size(), f->stream, f->stream2));
         if (!ftab.empty())
             HIPCHK(hipMemcpyAsync(f->ddag_ftab, ftab.data(), ftab.size() * sizeof(unsigned), hipMemcpyHostToDevice, f->stream));
         f->dag_xcd_g = want_tab ? xcd_g : 0;
@@ -1590,23 +1597,13 @@ static int dag_prepare(cocons_fit *f, const FactorView &v)
         words = (words + 31) / 32 * 32;
         f->ddag_xcnt_off = words;              // the XCDs' own task counters: eight cache lines behind everything else
         words += 8 * 32;
-        if (f->ddag_words < words) {
-            if (f->ddag) { HIPCHK(hipFree(f->ddag)); f->ddag = nullptr; }
-            HIPCHK(hipMalloc(&f->ddag, words * sizeof(unsigned)));
-            f->ddag_words = words;
-        }
+        HIPCHK(f->ddag.reserve(words, f->stream, f->stream2));
     }
-    HIPCHK(hipMemsetAsync(f->ddag, 0, f->ddag_words * sizeof(unsigned), f->stream));
+    HIPCHK(hipMemsetAsync(f->ddag, 0, f->ddag.count() * sizeof(unsigned), f->stream));
     // trace buffer: 4 stamps + one word of hw_where() pairs per task, 8 stamps per tile pair of the engine -- sized by BOTH
     // the task count and the tile count of THIS step table (a later table with fewer tasks and more tiles must not run past it)
     const size_t trace_elems = (size_t)f->dag_ntasks * 5 + 8 * (size_t)(v.nt + 2);
-    if (tun().dag_trace && f->dag_trace_elems < trace_elems) {
-        HIPCHK(hipStreamSynchronize(f->stream));
-        if (f->stream2) HIPCHK(hipStreamSynchronize(f->stream2));
-        if (f->ddag_trace) { HIPCHK(hipFree(f->ddag_trace)); f->ddag_trace = nullptr; f->dag_trace_elems = 0; }
-        HIPCHK(hipMalloc(&f->ddag_trace, trace_elems * sizeof(unsigned long long)));
-        f->dag_trace_elems = trace_elems;
-    }
+    if (tun().dag_trace) HIPCHK(f->ddag_trace.reserve(trace_elems, f->stream, f->stream2));
     f->dag_trace_tasks = (tun().dag_trace && f->ddag_trace) ? f->dag_ntasks : 0;      // 0: the buffer does not describe this table
     if (f->dag_trace_tasks)
         HIPCHK(hipMemsetAsync(f->ddag_trace, 0, trace_elems * sizeof(unsigned long long), f->stream));
@@ -1646,7 +1643,7 @@ extern "C" long long cocons_debug_dag_trace(cocons_fit *f, int *nsteps_out, int 
 extern "C" int cocons_debug_dag_words(cocons_fit *f, int count, unsigned *out)
 {
     FIT_ENTER(f);
-    if (!f->ddag || !out || count < 1 || (size_t)count > f->ddag_words) return fail(-1, "cocons_debug_dag_words: bad argument or no DAG factorisation yet");
+    if (!f->ddag || !out || count < 1 || (size_t)count > f->ddag.count()) return fail(-1, "cocons_debug_dag_words: bad argument or no DAG factorisation yet");
     HIPCHK(hipStreamSynchronize(f->stream));
     HIPCHK(hipMemcpyAsync(out, f->ddag, (size_t)count * sizeof(unsigned), hipMemcpyDeviceToHost, f->stream));
     HIPCHK(hipStreamSynchronize(f->stream));
@@ -1809,7 +1806,7 @@ static int factorize(cocons_fit *f, const FactorView &v, std::vector<hipEvent_t>
             hipEventCreate(&ea); hipEventCreate(&eb);
             hipEventRecord(ea, M);
         }
-        launch_dag(v.A, v.lda, f->dP, f->dWt, (const DagStepHost *)f->ddag_steps, f->dag_nsteps, f->dag_ntasks, queue, tdone,
+        launch_dag(v.A, v.lda, f->dP, f->dWt, f->ddag_steps, f->dag_nsteps, f->dag_ntasks, queue, tdone,
                    pdone, (int)T64, pall, f->dpart, dcount, in, out, xr, abort_word, M, f->dag_trace_tasks ? f->ddag_trace : nullptr,
                    alive, dag_xcc_quota(), f->dag_trace_tasks ? (unsigned *)(f->ddag_trace + 4 * (size_t)f->dag_ntasks + 8 * (size_t)(v.nt + 2)) : nullptr,
                    f->dag_have_ftab ? f->ddag_ftab : nullptr, f->dag_xcd_g, f->ddag + f->ddag_xcnt_off);
@@ -1864,7 +1861,7 @@ extern "C" int cocons_debug_host_enqueue(cocons_fit *f, double *out)
 {
     if (!f || !out) return fail(-1, "cocons_debug_host_enqueue: null argument");
     double us = f->enq_host_us; long long n = f->enq_calls;
-    if (f->slots) for (cocons_fit *c : *f->slots) { us += c->enq_host_us; n += c->enq_calls; }
+    for (cocons_fit *c : f->slots) { us += c->enq_host_us; n += c->enq_calls; }
     out[0] = n ? us / (double)n : 0.0; out[1] = (double)n;
     return 0;
 }
@@ -1921,7 +1918,7 @@ static void debug_abort_report(cocons_fit *f)
     unsigned rec[7] = {0, 0, 0, 0, 0, 0, 0}, now = 0, qn = 0;
     hipMemcpyAsync(rec, f->ddag + 8, sizeof rec, hipMemcpyDeviceToHost, f->stream);
     hipStreamSynchronize(f->stream);
-    if (rec[2] < f->ddag_words) hipMemcpyAsync(&now, f->ddag + rec[2], sizeof now, hipMemcpyDeviceToHost, f->stream);
+    if (rec[2] < f->ddag.count()) hipMemcpyAsync(&now, f->ddag + rec[2], sizeof now, hipMemcpyDeviceToHost, f->stream);
     hipMemcpyAsync(&qn, f->ddag, sizeof qn, hipMemcpyDeviceToHost, f->stream);
     hipStreamSynchronize(f->stream);
     fprintf(stderr, "cocons: DAG wait: task %u (of %u, counter now %u) code 0x%x waited for word %u >= %u, saw %u, holds %u now; "
@@ -1934,13 +1931,13 @@ static void debug_abort_report(cocons_fit *f)
         snprintf(path, sizeof path, "%s.%d", dump, ndump++);
         if (FILE *fp = fopen(path, "wb")) {
             const unsigned ntr = f->dag_trace_tasks ? 1u : 0u;
-            unsigned hdr[16] = {0xDA6D0001u, (unsigned)f->nt, (unsigned)f->dag_nsteps, f->dag_ntasks, (unsigned)f->ddag_words,
+            unsigned hdr[16] = {0xDA6D0001u, (unsigned)f->nt, (unsigned)f->dag_nsteps, f->dag_ntasks, (unsigned)f->ddag.count(),
                                 (unsigned)f->flags_cap, ntr, (unsigned)f->hinfo[1], qn, now, 0, 0, 0, 0, 0, 0};
             fwrite(hdr, sizeof hdr, 1, fp);
             fwrite(rec, sizeof rec, 1, fp);
             std::vector<DagStepHost> sh((size_t)f->dag_nsteps);
             hipMemcpyAsync(sh.data(), f->ddag_steps, sh.size() * sizeof(DagStepHost), hipMemcpyDeviceToHost, f->stream);
-            std::vector<unsigned> w((size_t)f->ddag_words), fl(4 * (size_t)f->flags_cap + 64);
+            std::vector<unsigned> w((size_t)f->ddag.count()), fl(4 * (size_t)f->flags_cap + 64);
             hipMemcpyAsync(w.data(), f->ddag, w.size() * sizeof(unsigned), hipMemcpyDeviceToHost, f->stream);
             hipMemcpyAsync(fl.data(), f->dflags, fl.size() * sizeof(unsigned), hipMemcpyDeviceToHost, f->stream);
             hipStreamSynchronize(f->stream);
@@ -2054,11 +2051,10 @@ extern "C" int cocons_fit_engine_state(cocons_fit *f, int *out)
     out[1] = f->engine_retries;
     out[2] = f->engine_last_abort;
     // (the slots of cocons_neg2loglik_batch are handles of their own: their time-outs count for this handle)
-    if (f->slots)
-        for (cocons_fit *c : *f->slots) {
-            out[1] += c->engine_retries;
-            if (!out[2]) out[2] = c->engine_last_abort;
-        }
+    for (cocons_fit *c : f->slots) {
+        out[1] += c->engine_retries;
+        if (!out[2]) out[2] = c->engine_last_abort;
+    }
     // (so are the twin of cocons_sim_taper's pivot route and the unsorted clone cocons_sim_dense runs on)
     for (cocons_fit *c : {f->taper_twin, f->unsorted})
         if (c) {
@@ -2118,7 +2114,7 @@ static void slot_stream_apart(cocons_fit *f, cocons_fit *c)
     for (int attempt = 0; attempt < 8; ++attempt) {
         bool clash = false;
         std::vector<cocons_fit *> peers{f};
-        if (f->slots) for (cocons_fit *o : *f->slots) if (o != c) peers.push_back(o);
+        for (cocons_fit *o : f->slots) if (o != c) peers.push_back(o);
         for (cocons_fit *o : peers) {
             if (hipStreamQuery(o->stream) != hipSuccess) { (void)hipGetLastError(); continue; }      // (busy: not probed)
             const int r = streams_run_concurrently(o->stream, c->stream, words);
@@ -2141,44 +2137,32 @@ static cocons_fit *clone_for_slot(cocons_fit *f, bool want_engine)
     // (a clone enters the registry with its operation lock held -- fit_create_impl(..., return_locked) -- and keeps it until it
     // is complete: its main stream may still be redrawn below, which no other thread's stream self-test may see half done)
     if (f->taper_nnz <= 0) {
-        cocons_fit *c = fit_create_impl(f->n_user, f->p, f->r, 0, f->h_locs->data(), f->h_X->data(), f->h_z->data(), nullptr,
+        cocons_fit *c = fit_create_impl(f->n_user, f->p, f->r, 0, f->h_locs.data(), f->h_X.data(), f->h_z.data(), nullptr,
                                         f->smooth_limits, f->device, true, false, want_engine, true);
         if (c) {
-            if (!c->dflags && flags_reset(c, c->nt) != 0) { c->op_mu->unlock(); cocons_fit_destroy(c); return nullptr; }
+            if (!c->dflags && flags_reset(c, c->nt) != 0) { c->op_mu.unlock(); cocons_fit_destroy(c); return nullptr; }
             hipStreamSynchronize(c->stream);
             slot_stream_apart(f, c);
             c->engine_ok = c->engine_ok && c->stream2 != nullptr;
-            c->op_mu->unlock();
+            c->op_mu.unlock();
         }
         return c;
     }
-    cocons_fit *c = fit_create_impl(f->n_user, f->p, f->r, 0, f->h_locs->data(), f->h_X->data(), f->h_z->data(), nullptr,
+    cocons_fit *c = fit_create_impl(f->n_user, f->p, f->r, 0, f->h_locs.data(), f->h_X.data(), f->h_z.data(), nullptr,
                                     f->smooth_limits, f->device, false, true, false, true);      // h_* of a taper handle are in ITS order;
     if (!c) return nullptr;                                                                  // band-limited: never an engine
-    struct Unlock { cocons_fit *c; ~Unlock() { if (c) c->op_mu->unlock(); } } unlock{c};
-    auto drop = [&]() { unlock.c = nullptr; c->op_mu->unlock(); cocons_fit_destroy(c); return (cocons_fit *)nullptr; };
+    struct Unlock { cocons_fit *c; ~Unlock() { if (c) c->op_mu.unlock(); } } unlock{c};
+    auto drop = [&]() { unlock.c = nullptr; c->op_mu.unlock(); cocons_fit_destroy(c); return (cocons_fit *)nullptr; };
     if (!c->dflags && flags_reset(c, c->nt) != 0) return drop();
     hipStreamSynchronize(c->stream);
     slot_stream_apart(f, c);
     c->skew = f->skew;                        // the same (packed) buffer layout as the original
     if (fit_alloc_matrix(c, f->r + f->p) != 0) return drop();
-    const size_t nnz = (size_t)f->taper_nnz;
-    bool ok = hipMalloc(&c->d_tci, nnz * sizeof(int)) == hipSuccess &&
-              hipMalloc(&c->d_trp, (size_t)(f->n + 1) * sizeof(int)) == hipSuccess &&
-              hipMalloc(&c->d_tval, nnz * sizeof(double)) == hipSuccess &&
-              // (asynchronous on the clone's own stream: the library makes no call on the NULL stream)
-              hipMemcpyAsync(c->d_tci, f->d_tci, nnz * sizeof(int), hipMemcpyDeviceToDevice, c->stream) == hipSuccess &&
-              hipMemcpyAsync(c->d_trp, f->d_trp, (size_t)(f->n + 1) * sizeof(int), hipMemcpyDeviceToDevice, c->stream) == hipSuccess &&
-              hipMemcpyAsync(c->d_tval, f->d_tval, nnz * sizeof(double), hipMemcpyDeviceToDevice, c->stream) == hipSuccess;
-    c->taper_hi = new std::vector<int>(*f->taper_hi);
-    c->taper_inv = new std::vector<int>(*f->taper_inv);
+    c->taper_hi = f->taper_hi;
+    c->taper_inv = f->taper_inv;
     c->taper_maxband = f->taper_maxband;
-    if (ok && f->d_thi)
-        ok = hipMalloc(&c->d_thi, (size_t)f->nt * sizeof(int)) == hipSuccess &&
-             hipMemcpyAsync(c->d_thi, f->d_thi, (size_t)f->nt * sizeof(int), hipMemcpyDeviceToDevice, c->stream) == hipSuccess;
-    if (ok) ok = hipStreamSynchronize(c->stream) == hipSuccess;
-    if (!ok) return drop();
-    c->taper_nnz = f->taper_nnz;
+    // (asynchronous on the clone's own stream: the library makes no call on the NULL stream)
+    if (taper_pattern_to_device(c, (size_t)f->taper_nnz, f->d_tci, f->d_trp, f->d_tval, f->d_thi, false) != 0) return drop();
     // a band-limited handle never uses the engine, nor do its clones; a taper handle WITHOUT an envelope (COCONS_TAPER_BAND=0)
     // may -- but this clone was created without an engine stream (want_engine = false), and an engine launched on a null
     // stream would land on the NULL stream the library never touches (round 5's regression, the advisor's finding)
@@ -2214,31 +2198,30 @@ extern "C" int cocons_neg2loglik_batch(cocons_fit *f, int nb, const double *thet
     const bool eng_mode = batch_engine >= 0 ? batch_engine == 1 : false;
     const int nslots = nslots_env > 0 ? nslots_env : (eng_mode ? 2 : 4);
     int S = nb < nslots ? (nb > 0 ? nb : 1) : nslots;
-    if (!f->slots) f->slots = new std::vector<cocons_fit *>();
     // every extra slot is a clone of the handle with its own n x n factorisation buffer
     // (lda * npad * 8 bytes: 0.83 GB at n = 10^4); if one cannot be created (out of memory) the
     // batch runs on the slots that exist -- slot 0 is the fit itself, so it always completes
     // (the slots are handles of their own in the registry: held for the whole call, like the handle itself, so that no other
     // thread's stream self-test launches probe kernels between their evaluations)
     std::vector<std::unique_lock<std::recursive_mutex>> slot_locks;
-    for (cocons_fit *c : *f->slots) slot_locks.emplace_back(*c->op_mu);
-    while ((int)f->slots->size() < S - 1) {
+    for (cocons_fit *c : f->slots) slot_locks.emplace_back(c->op_mu);
+    while ((int)f->slots.size() < S - 1) {
         cocons_fit *c = clone_for_slot(f, eng_mode);
         if (!c) { (void)hipGetLastError(); break; }
-        slot_locks.emplace_back(*c->op_mu);
-        f->slots->push_back(c);
+        slot_locks.emplace_back(c->op_mu);
+        f->slots.push_back(c);
     }
     const bool engine_saved = f->engine_ok;
     if (!eng_mode) {
         if (S > 1) f->engine_ok = false;
-        for (auto c : *f->slots) c->engine_ok = false;
+        for (auto c : f->slots) c->engine_ok = false;
     }
-    if (S > (int)f->slots->size() + 1) S = (int)f->slots->size() + 1;
+    if (S > (int)f->slots.size() + 1) S = (int)f->slots.size() + 1;
     for (int i = 0; i < nb; ++i) { values[i] = NAN; status[i] = -1; }   // never left unwritten
     std::vector<int> pending(S, -1);
     const int tp = 6 * f->p;
     int rc_all = 0;
-    auto slot_of = [&](int s) { return s == 0 ? f : (*f->slots)[s - 1]; };
+    auto slot_of = [&](int s) { return s == 0 ? f : f->slots[s - 1]; };
     auto collect = [&](int s) -> int {
         cocons_fit *c = slot_of(s);
         int i = pending[s];
@@ -2585,8 +2568,8 @@ extern "C" int cocons_cov_rows(cocons_fit *f, const double *theta, int classic, 
     HIPCHK_AT("cocons_cov_rows", dloc.alloc((size_t)LOCP_FIELDS * n));
     HIPCHK_AT("cocons_cov_rows", dout.alloc((size_t)nidx * n));
     HIPCHK_AT("cocons_cov_rows", didx.alloc((size_t)nidx));
-    HIPCHK_AT("cocons_cov_rows", upload_canon(dX, f->h_X->data(), (size_t)n * p, s));
-    HIPCHK_AT("cocons_cov_rows", upload_canon(dl, f->h_locs->data(), (size_t)n * 2, s));
+    HIPCHK_AT("cocons_cov_rows", upload_canon(dX, f->h_X.data(), (size_t)n * p, s));
+    HIPCHK_AT("cocons_cov_rows", upload_canon(dl, f->h_locs.data(), (size_t)n * 2, s));
     HIPCHK_AT("cocons_cov_rows", hipMemcpyAsync(didx, idx, (size_t)nidx * sizeof(int), hipMemcpyHostToDevice, s));
     launch_loc_params(loc_args(n, p, dX, dl, dloc, n, tv, ms.smooth_kind, f->smooth_limits), s);
     launch_cov_rows(ms.mode, n, nidx, didx, dloc, n, ms.gr, ms.nu_fixed, cor, dout, s);
@@ -2600,17 +2583,12 @@ extern "C" int cocons_cov_rows(cocons_fit *f, const double *theta, int classic, 
 // the handle's buffers of the prediction entries, grown to m new locations
 static int pred_reserve(cocons_fit *f, int m)
 {
-    if (m <= f->pred_cap) return 0;
-    hipFree(f->dlocp); hipFree(f->dXp); hipFree(f->dlocsp); hipFree(f->dstoch); hipFree(f->dquad); hipFree(f->dred);
-    f->dlocp = f->dXp = f->dlocsp = f->dstoch = f->dquad = f->dred = nullptr;
-    f->pred_cap = 0;
-    HIPCHK(hipMalloc(&f->dlocp, (size_t)LOCP_FIELDS * m * sizeof(double)));
-    HIPCHK(hipMalloc(&f->dXp, (size_t)m * f->p * sizeof(double)));
-    HIPCHK(hipMalloc(&f->dlocsp, (size_t)m * 2 * sizeof(double)));
-    HIPCHK(hipMalloc(&f->dstoch, (size_t)m * sizeof(double)));
-    HIPCHK(hipMalloc(&f->dquad, (size_t)m * sizeof(double)));
-    HIPCHK(hipMalloc(&f->dred, row_reduce_scratch_doubles(f->n, m) * sizeof(double)));
-    f->pred_cap = m;
+    HIPCHK(f->dlocp.reserve((size_t)LOCP_FIELDS * m, f->stream, f->stream2));
+    HIPCHK(f->dXp.reserve((size_t)m * f->p, f->stream, f->stream2));
+    HIPCHK(f->dlocsp.reserve((size_t)m * 2, f->stream, f->stream2));
+    HIPCHK(f->dstoch.reserve((size_t)m, f->stream, f->stream2));
+    HIPCHK(f->dquad.reserve((size_t)m, f->stream, f->stream2));
+    HIPCHK(f->dred.reserve(row_reduce_scratch_doubles(f->n, m), f->stream, f->stream2));
     return 0;
 }
 
@@ -2696,8 +2674,7 @@ extern "C" int cocons_krige_prepare(cocons_fit *f, const double *theta, const do
     if (int rc = no_taper(f, "cocons_krige_prepare")) return rc;
     if (int rc = krige_sharded(f, "cocons_krige_prepare")) return rc;
     if (!theta || !mean || z_col < 0 || z_col >= f->r || max_rows < 0) return fail(-1, "cocons_krige_prepare: bad argument");
-    delete f->krige;                    // replaced -- and gone if this prepare fails
-    f->krige = nullptr;
+    f->krige.reset();                   // replaced -- and gone if this prepare fails
     const int p = f->p, n = f->n, npad = f->npad, nt = f->nt;
     std::unique_ptr<KrigeState> K(new KrigeState());
     K->rows = krige_rows(f, max_rows);
@@ -2739,7 +2716,7 @@ extern "C" int cocons_krige_prepare(cocons_fit *f, const double *theta, const do
     launch_loc_params(loc_args(n, p, f->dX, f->dlocs, K->loc, npad, tv, ms.smooth_kind, f->smooth_limits), s);
     HIPCHK_AT("cocons_krige_prepare", hipGetLastError());
     HIPCHK_AT("cocons_krige_prepare", hipStreamSynchronize(s));
-    f->krige = K.release();
+    f->krige = std::move(K);
     return 0;
 }
 
@@ -2752,7 +2729,7 @@ extern "C" int cocons_krige_apply(cocons_fit *f, int m, const double *locs_pred,
     FIT_ENTER(f);
     if (int rc = no_taper(f, "cocons_krige_apply")) return rc;
     if (int rc = krige_sharded(f, "cocons_krige_apply")) return rc;
-    KrigeState *K = f->krige;
+    KrigeState *K = f->krige.get();
     if (!K) return fail(-1, "cocons_krige_apply: no kriging state on this handle (call cocons_krige_prepare first)");
     const int p = f->p, rows = K->rows;
     const double *th = K->theta.data();
@@ -2790,8 +2767,7 @@ extern "C" int cocons_krige_release(cocons_fit *f)
 {
     if (!f) return fail(-1, "cocons_krige_release: null fit handle");
     FIT_ENTER(f);
-    delete f->krige;                    // (every entry point drains the main stream before it returns: nothing in flight uses it)
-    f->krige = nullptr;
+    f->krige.reset();                   // (every entry point drains the main stream before it returns: nothing in flight uses it)
     return 0;
 }
 
@@ -2801,7 +2777,7 @@ extern "C" int cocons_krige_info(cocons_fit *f, long long *out4)
     if (!f) return fail(-1, "cocons_krige_info: null fit handle");
     if (!out4) return fail(-1, "cocons_krige_info: null argument");
     FIT_ENTER(f);
-    const KrigeState *K = f->krige;
+    const KrigeState *K = f->krige.get();
     out4[0] = K ? 1 : 0;
     out4[1] = K ? K->bytes : 0;
     out4[2] = K ? K->rows : 0;
@@ -2842,7 +2818,7 @@ extern "C" int cocons_predict_taper(cocons_fit *f, const double *theta, const do
     HIPCHK_AT("cocons_predict_taper", hipMemcpyAsync(drp, rowpointers_pred, (size_t)(m + 1) * sizeof(int), hipMemcpyHostToDevice, s));
     if (nnz_pred > 0) {
         std::vector<int> mapped(nnz_pred);          // the pattern's columns in the handle's order of the observations
-        for (int w = 0; w < nnz_pred; ++w) mapped[w] = (*f->taper_inv)[colindices_pred[w] - 1] + 1;
+        for (int w = 0; w < nnz_pred; ++w) mapped[w] = f->taper_inv[colindices_pred[w] - 1] + 1;
         HIPCHK_AT("cocons_predict_taper", hipMemcpy(dci, mapped.data(), (size_t)nnz_pred * sizeof(int), hipMemcpyHostToDevice));
         HIPCHK_AT("cocons_predict_taper", upload_canon(dtv, taper_entries_pred, (size_t)nnz_pred, s));
     }
@@ -2876,7 +2852,7 @@ extern "C" int cocons_fit_taper_order(cocons_fit *f, int *pivot_out)
     FIT_ENTER(f);
     if (f->taper_nnz <= 0) return fail(-1, "cocons_fit_taper_order: not a taper fit");
     if (!pivot_out) return fail(-1, "cocons_fit_taper_order: null argument");
-    const std::vector<int> &inv = *f->taper_inv;
+    const std::vector<int> &inv = f->taper_inv;
     for (int i = 0; i < f->n; ++i) pivot_out[inv[i]] = i + 1;
     return 0;
 }
@@ -2925,7 +2901,7 @@ extern "C" int cocons_sim_taper(cocons_fit *f, const double *theta, const double
     if (f->taper_nnz <= 0) return fail(-1, "cocons_sim_taper: not a taper fit (cocons_sim_dense simulates on a dense handle)");
     if (!theta || !mean || nsim <= 0 || !iiderrors || !out) return fail(-1, "cocons_sim_taper: bad argument");
     const int n = f->n;
-    const std::vector<int> &inv = *f->taper_inv;          // inv[caller index] = position in f's order
+    const std::vector<int> &inv = f->taper_inv;          // inv[caller index] = position in f's order
     std::vector<int> tperm;                               // pivot route: twin position k <- position tperm[k] of f
     bool own = true;
     if (pivot) {
@@ -2946,23 +2922,23 @@ extern "C" int cocons_sim_taper(cocons_fit *f, const double *theta, const double
     }
     // draw-equal route: the factor of S[pivot, pivot] -- a taper handle in that order, built once and kept while the callers
     // pass the same pivot (the fill-reducing order of spam's chol: computed once per coco object)
-    if (!f->taper_twin || *f->twin_perm != tperm) {
+    if (!f->taper_twin || f->twin_perm != tperm) {
         if (f->taper_twin) { cocons_fit_destroy(f->taper_twin); f->taper_twin = nullptr; }
-        delete f->krige; f->krige = nullptr;                    // (its buffers: the main stream is drained above)
-        delete f->twin_perm; f->twin_perm = nullptr;
-        cocons_fit *t = taper_create_ordered(n, f->p, f->r, f->h_locs->data(), f->h_X->data(), f->h_z->data(), f->smooth_limits,
-                                             f->device, (int)f->h_tci->size(), f->h_tci->data(), f->h_trp->data(),
-                                             f->h_tval->data(), tperm, true);
+        f->krige.reset();                                       // (its buffers: the main stream is drained above)
+        f->twin_perm.clear();
+        cocons_fit *t = taper_create_ordered(n, f->p, f->r, f->h_locs.data(), f->h_X.data(), f->h_z.data(), f->smooth_limits,
+                                             f->device, (int)f->h_tci.size(), f->h_tci.data(), f->h_trp.data(),
+                                             f->h_tval.data(), tperm, true);
         if (!t) {
             const std::string why = g_err;
             return fail(-4, "cocons_sim_taper: no taper handle in the given pivot order (%s); pivot = NULL simulates in the "
                             "handle's own order (same distribution, another field for the same draws)", why.c_str());
         }
         f->taper_twin = t;
-        f->twin_perm = new std::vector<int>(tperm);
+        f->twin_perm = tperm;
     }
     for (int k = 0; k < n; ++k) pos[pivot[k] - 1] = k;
-    std::lock_guard<std::recursive_mutex> twin_guard(*f->taper_twin->op_mu);
+    std::lock_guard<std::recursive_mutex> twin_guard(f->taper_twin->op_mu);
     if (int rc = fit_check(f->taper_twin)) return rc;
     return sim_taper_run(f->taper_twin, theta, mean, nsim, iiderrors, pos, out);
 }
@@ -2979,8 +2955,8 @@ extern "C" int cocons_debug_sim_taper_ms(cocons_fit *f, int twin, double *out4)
     if (g->taper_nnz <= 0) return fail(-1, "cocons_debug_sim_taper_ms: not a taper fit");
     for (int q = 0; q < 3; ++q) out4[q] = g->sim_ms[q];
     double tiles = 0;
-    if (g->taper_hi->empty()) tiles = 0.5 * g->nt * (g->nt + 1.0);
-    else for (int c = 0; c < g->nt; ++c) tiles += (*g->taper_hi)[c] - c;
+    if (g->taper_hi.empty()) tiles = 0.5 * g->nt * (g->nt + 1.0);
+    else for (int c = 0; c < g->nt; ++c) tiles += g->taper_hi[c] - c;
     out4[3] = tiles;
     return 0;
 }
@@ -2998,8 +2974,8 @@ extern "C" int cocons_sim_dense(cocons_fit *f, const double *theta, const double
         // L E depends on the ORDER of the observations (the factor of a permuted matrix is not the
         // permuted factor): the field for given draws is only reproduced in the caller's order
         if (!f->unsorted) {
-            f->unsorted = fit_create_impl(f->n_user, f->p, f->r, 0, f->h_locs->data(), f->h_X->data(),
-                                          f->r > 0 ? f->h_z->data() : nullptr, nullptr, f->smooth_limits,
+            f->unsorted = fit_create_impl(f->n_user, f->p, f->r, 0, f->h_locs.data(), f->h_X.data(),
+                                          f->r > 0 ? f->h_z.data() : nullptr, nullptr, f->smooth_limits,
                                           f->device, false);
             if (!f->unsorted) return -1;
         }
@@ -3234,18 +3210,18 @@ static void shard_make_plan(ShardPlan &P, int nt, int mt, int world, int group)
 
 struct ShardState {
     ShardPlan plan;
-    int *d_pmap = nullptr;
-    double *lkk[2] = {nullptr, nullptr};
+    DevBuf<int> d_pmap;
+    DevBuf<double> lkk[2];
     hipEvent_t ev_main_L = nullptr, ev_comm_L[2] = {nullptr, nullptr}, ev_main_X[2] = {nullptr, nullptr},
                ev_comm_X[2] = {nullptr, nullptr};
     hipEvent_t ev_main_U[2] = {nullptr, nullptr};    // main stream: the received L_kk in lkk[k & 1] has been unpacked (the buffer may be
     bool unpacked[2] = {false, false};               // overwritten by the broadcast of L_(k+2)); unpacked[b]: recorded this evaluation
 };
 
-static void shard_state_free(ShardState *S)
+// (the events only: the buffers go with the state, cocons_fit_destroy)
+static void shard_events_destroy(ShardState *S)
 {
     if (!S) return;
-    hipFree(S->d_pmap); hipFree(S->lkk[0]); hipFree(S->lkk[1]);
     if (S->ev_main_L) hipEventDestroy(S->ev_main_L);
     for (int b = 0; b < 2; ++b) {
         if (S->ev_comm_L[b]) hipEventDestroy(S->ev_comm_L[b]);
@@ -3253,7 +3229,6 @@ static void shard_state_free(ShardState *S)
         if (S->ev_comm_X[b]) hipEventDestroy(S->ev_comm_X[b]);
         if (S->ev_main_U[b]) hipEventDestroy(S->ev_main_U[b]);
     }
-    delete S;
 }
 
 extern "C" int cocons_fit_world(cocons_fit *f) { return (f && f->coll_kind) ? f->coll_world : 1; }
@@ -3264,29 +3239,20 @@ static int shard_prepare(cocons_fit *f, int rank, int world)
     f->rank = rank; f->world = world; f->nrhs_cur = f->r;
     if (int rc = fit_alloc_matrix(f, f->r)) return rc;
     const int mt = f->nt + f->rhs_act / TILE;
-    if (!f->shard) f->shard = new ShardState();
-    ShardState *S = f->shard;
+    if (!f->shard) f->shard.reset(new ShardState());
+    ShardState *S = f->shard.get();
     if (S->plan.nt != f->nt || S->plan.mt != mt || S->plan.world != world || S->plan.group != shard_group()) {
         HIPCHK(hipStreamSynchronize(f->stream));
         if (f->cstream) HIPCHK(hipStreamSynchronize(f->cstream));
         shard_make_plan(S->plan, f->nt, mt, world, shard_group());
-        if (S->d_pmap) { HIPCHK(hipFree(S->d_pmap)); S->d_pmap = nullptr; }
-        HIPCHK(hipMalloc(&S->d_pmap, S->plan.pmap.size() * sizeof(int)));
+        HIPCHK(S->d_pmap.alloc(S->plan.pmap.size()));      // (both streams that use the old map were drained just above)
         HIPCHK(hipMemcpyAsync(S->d_pmap, S->plan.pmap.data(), S->plan.pmap.size() * sizeof(int), hipMemcpyHostToDevice, f->stream));
         HIPCHK(hipStreamSynchronize(f->stream));
-        const size_t bytes = S->plan.max_elems * sizeof(double);
-        if (f->xbuf_bytes < bytes) {
-            if (f->xbuf_own) { hipFree(f->xbuf[0]); hipFree(f->xbuf[1]); }
-            f->xbuf[0] = f->xbuf[1] = nullptr;
-            HIPCHK(hipMalloc(&f->xbuf[0], bytes));
-            HIPCHK(hipMalloc(&f->xbuf[1], bytes));
-            HIPCHK(hipMemsetAsync(f->xbuf[0], 0, bytes, f->stream));      // (slot padding is exchanged too: no NaN patterns)
-            HIPCHK(hipMemsetAsync(f->xbuf[1], 0, bytes, f->stream));
-            f->xbuf_bytes = bytes; f->xbuf_own = true;
-        }
+        for (int b = 0; b < 2; ++b)      // (zeroed when new: slot padding is exchanged too, no NaN patterns)
+            HIPCHK(f->xbuf[b].reserve(S->plan.max_elems, f->stream, f->stream2, 0));
     }
     for (int b = 0; b < 2; ++b) {
-        if (!S->lkk[b]) HIPCHK(hipMalloc(&S->lkk[b], LKK_DOUBLES * sizeof(double)));
+        if (!S->lkk[b]) HIPCHK(S->lkk[b].alloc(LKK_DOUBLES));
         if (!S->ev_comm_L[b]) HIPCHK(hipEventCreateWithFlags(&S->ev_comm_L[b], hipEventDisableTiming));
         if (!S->ev_main_X[b]) HIPCHK(hipEventCreateWithFlags(&S->ev_main_X[b], hipEventDisableTiming));
         if (!S->ev_comm_X[b]) HIPCHK(hipEventCreateWithFlags(&S->ev_comm_X[b], hipEventDisableTiming));
@@ -3334,7 +3300,7 @@ static int shard_begin(cocons_fit *f, const double *theta, const double *mean, i
 // the owner factors the diagonal block of block k in place and packs it (with the Q operands) for the broadcast
 static int shard_factor_diag(cocons_fit *f, int k)
 {
-    ShardState *S = f->shard;
+    ShardState *S = f->shard.get();
     const int t = k * PT, w = S->plan.ncols[k] / TILE;
     hipStream_t s = f->stream;
     double *A = f->dA, *q0 = f->dinv, *q1 = f->dinv + 2048;
@@ -3392,7 +3358,7 @@ static int coll_prepare(cocons_fit *f)
         if (own) HIPCHK(hipStreamCreateWithFlags(&f->cstream_l, hipStreamNonBlocking));
         else f->cstream_l = f->cstream;
     }
-    if (!f->dcoll) HIPCHK(hipMalloc(&f->dcoll, (size_t)(2 + (COCONS_P_MAX + f->r) * (COCONS_P_MAX + f->r)) * sizeof(double)));
+    if (!f->dcoll) HIPCHK(f->dcoll.alloc((size_t)(2 + (COCONS_P_MAX + f->r) * (COCONS_P_MAX + f->r))));
     return 0;
 }
 
@@ -3459,7 +3425,7 @@ extern "C" int cocons_fit_set_allgather(cocons_fit *f, cocons_allgather_fn allga
 // broadcast of L_kk (packed by shard_factor_diag on its owner) on the communication stream
 static int coll_bcast_L(cocons_fit *f, int k, bool in_group)
 {
-    ShardState *S = f->shard;
+    ShardState *S = f->shard.get();
     const int b = k & 1, owner = shard_owner(k, f->coll_world);
     hipStream_t cs = f->cstream_l;
     // the owner's copy is packed on its main stream; a receiver's buffer was last read by the unpack of L_(k-2) on ITS main
@@ -3481,7 +3447,7 @@ static int coll_bcast_L(cocons_fit *f, int k, bool in_group)
 // all-gather of the solved rows of panel k: every rank's slot of the owner-packed buffer
 static int coll_allgather_X(cocons_fit *f, int k, bool in_group)
 {
-    ShardState *S = f->shard;
+    ShardState *S = f->shard.get();
     const int b = k & 1;
     const size_t cnt = (size_t)S->plan.srows[k] * (size_t)S->plan.ncols[k];
     HIPCHK(hipStreamWaitEvent(f->cstream, S->ev_main_X[b], 0));
@@ -3503,7 +3469,7 @@ static int coll_allgather_X(cocons_fit *f, int k, bool in_group)
 //   its own rows, factored, packed | own rows packed into the gathered buffer
 static int shard_step_pre(cocons_fit *f, int k, int nb)
 {
-    ShardState *S = f->shard;
+    ShardState *S = f->shard.get();
     const ShardPlan &P = S->plan;
     const int W = f->coll_world, rank = f->coll_rank, G = shard_group();
     const int t = k * PT, w = P.ncols[k] / TILE, tn = t + w;           // tn: first tile below / right of the block
@@ -3545,7 +3511,7 @@ static int shard_step_pre(cocons_fit *f, int k, int nb)
 // ... and behind it: the own rows of the trailing matrix updated with the gathered panel
 static int shard_step_post(cocons_fit *f, int k, int nb)
 {
-    ShardState *S = f->shard;
+    ShardState *S = f->shard.get();
     const ShardPlan &P = S->plan;
     const int W = f->coll_world, rank = f->coll_rank, G = shard_group();
     const int t = k * PT, w = P.ncols[k] / TILE, tn = t + w;
@@ -3745,7 +3711,7 @@ extern "C" int cocons_multi_neg2loglik_dense(cocons_multi *m, const double *thet
     if (!R) return -1;
     const int W = m->ndev;
     std::vector<std::unique_lock<std::recursive_mutex>> op_locks;       // (this entry point drives the ranks' handles directly)
-    for (int d = 0; d < W; ++d) op_locks.emplace_back(*m->fits[d]->op_mu);
+    for (int d = 0; d < W; ++d) op_locks.emplace_back(m->fits[d]->op_mu);
     for (int d = 0; d < W; ++d) {
         if (int rc = fit_check(m->fits[d])) return rc;
         if (int rc = shard_begin(m->fits[d], theta, mean, d, W)) return rc;
@@ -3767,7 +3733,7 @@ extern "C" int cocons_multi_neg2loglik_dense(cocons_multi *m, const double *thet
         NCCLCHK(ge);
         for (int d = 0; d < W; ++d) {
             if (int rc = fit_check(m->fits[d])) return rc;
-            ShardState *S = m->fits[d]->shard;
+            ShardState *S = m->fits[d]->shard.get();
             HIPCHK(hipEventRecord(gather ? S->ev_comm_X[k & 1] : S->ev_comm_L[k & 1],
                                   gather ? m->fits[d]->cstream : m->fits[d]->cstream_l));
         }
@@ -4006,14 +3972,14 @@ static int dag_replay_run(cocons_fit *f, const FactorView &fv, bool slots, const
         assemble_rhs(f, mean, true, nullptr, 0, 0, f->npad, true, slots);
         launch_front_identity(fv.A, fv.lda, f->pad0, fv.mt * TILE, M);
         panel_ops(f, fv, 0, M);
-        HIPCHK_AT("cocons_debug_dag_replay", hipMemsetAsync(f->ddag, 0, f->ddag_words * sizeof(unsigned), M));
+        HIPCHK_AT("cocons_debug_dag_replay", hipMemsetAsync(f->ddag, 0, f->ddag.count() * sizeof(unsigned), M));
         HIPCHK_AT("cocons_debug_dag_replay", hipMemsetD32Async((hipDeviceptr_t)f->dflags, 0x3fffffff, 3 * (size_t)f->flags_cap, M));   // in / out / xr: all raised
         // (as many workgroups take part as in a real evaluation: the engine and its partner are entered on XCD 0 by hand)
         unsigned *alive_w = f->dflags + 3 * (size_t)f->flags_cap;
         static const unsigned pair_on_xcd0 = 2u;
         HIPCHK_AT("cocons_debug_dag_replay", hipMemcpyAsync(alive_w + 16, &pair_on_xcd0, sizeof(unsigned), hipMemcpyHostToDevice, M));
         HIPCHK_AT("cocons_debug_dag_replay", hipEventRecord(ev.a, M));
-        launch_dag(fv.A, fv.lda, f->dP, f->dWt, (const DagStepHost *)f->ddag_steps, f->dag_nsteps, f->dag_ntasks, queue, tdone,
+        launch_dag(fv.A, fv.lda, f->dP, f->dWt, f->ddag_steps, f->dag_nsteps, f->dag_ntasks, queue, tdone,
                    pdone, (int)T64, pall, f->dpart, dcount, in, outw, xr, abort_word, M, nullptr, alive_w, dag_xcc_quota(), nullptr,
                    f->dag_have_ftab ? f->ddag_ftab : nullptr, f->dag_xcd_g, f->ddag + f->ddag_xcnt_off);
         HIPCHK_AT("cocons_debug_dag_replay", hipEventRecord(ev.b, M));
@@ -4112,11 +4078,8 @@ struct GradLayout {
     }
 };
 
-static void grad_state_free(cocons_fit *f)
-{
-    delete f->grad;
-    f->grad = nullptr;
-}
+cocons_fit::cocons_fit() = default;
+cocons_fit::~cocons_fit() = default;
 
 static int grad_refuse(cocons_fit *f, const char *who)
 {
@@ -4131,7 +4094,7 @@ static int grad_enqueue(cocons_fit *f, const double *theta, const double *mean, 
 {
     const int npad = f->npad, nr = f->r, rt = round_up(nr > 0 ? nr : 1, TILE), p = f->p;
     hipStream_t s = f->stream;
-    GradState *G = f->grad;
+    GradState *G = f->grad.get();
     f->nrhs_cur = nr;
     assemble_sigma(f, theta, 0, 0, npad);
     // rows npad.. : R' and zeros up to npad + rt; then the unit rows e_i', i < npad
@@ -4188,21 +4151,16 @@ static int grad_prepare(cocons_fit *f, const char *who)
         HIPCHK_AT(who, G->site.alloc(si));
         HIPCHK_AT(who, G->out.alloc(ou));
         G->bytes = (long long)((sc + ar + arp + si + ou) * sizeof(double));
-        f->grad = G.release();
+        f->grad = std::move(G);
     }
     if (!f->dA) return fail(-1, "%s: the handle has no matrix buffer", who);
     // dA large enough for the gradient's layout: grown once, f->lda unchanged (GradLayout); the contents need not survive
     // (every operation assembles its matrix anew)
     const size_t need = grad_lda(f) * (size_t)f->npad;
-    if (f->dA_elems < need) {
+    bool grew = false;
+    HIPCHK_AT(who, f->dA.reserve(need, f->stream, f->stream2, 0, false, &grew));
+    if (grew) {
         HIPCHK_AT(who, hipStreamSynchronize(f->stream));
-        if (f->stream2) HIPCHK_AT(who, hipStreamSynchronize(f->stream2));
-        HIPCHK_AT(who, hipFree(f->dA));
-        f->dA = nullptr; f->dA_elems = 0;
-        HIPCHK_AT(who, hipMalloc(&f->dA, need * sizeof(double)));
-        HIPCHK_AT(who, hipMemsetAsync(f->dA, 0, need * sizeof(double), f->stream));
-        HIPCHK_AT(who, hipStreamSynchronize(f->stream));
-        f->dA_elems = need;
         f->border_clean = -1; f->border_pending = -1;
     }
     return 0;
@@ -4238,8 +4196,8 @@ extern "C" int cocons_debug_sigma_inverse(cocons_fit *f, const double *theta, do
     if (f->sorted) {
         // the caller's observation order: through the clone that keeps it (as cocons_sim_dense)
         if (!f->unsorted) {
-            f->unsorted = fit_create_impl(f->n_user, f->p, f->r, 0, f->h_locs->data(), f->h_X->data(),
-                                          f->r > 0 ? f->h_z->data() : nullptr, nullptr, f->smooth_limits,
+            f->unsorted = fit_create_impl(f->n_user, f->p, f->r, 0, f->h_locs.data(), f->h_X.data(),
+                                          f->r > 0 ? f->h_z.data() : nullptr, nullptr, f->smooth_limits,
                                           f->device, false);
             if (!f->unsorted) return -1;
         }
@@ -4266,8 +4224,8 @@ extern "C" int cocons_debug_fit_memory(cocons_fit *f, long long *out4)
     if (!f) return fail(-1, "cocons_debug_fit_memory: null fit handle");
     if (!out4) return fail(-1, "cocons_debug_fit_memory: null argument");
     FIT_ENTER(f);
-    out4[0] = (long long)(f->dA_elems * sizeof(double));
-    out4[1] = (long long)(f->dP_elems * sizeof(double));
+    out4[0] = (long long)(f->dA.count() * sizeof(double));
+    out4[1] = (long long)(f->dP.count() * sizeof(double));
     out4[2] = f->grad ? f->grad->bytes : 0;
     out4[3] = (long long)f->lda;
     return 0;
