@@ -13,6 +13,8 @@ from .host import (  # noqa: F401
     GetNeg2loglikelihoodTaperProfile,
     GetNeg2loglikelihoodProfile,
     GetNeg2loglikelihoodREML,
+    GetNeg2loglikelihoodProfile_grad,
+    GetNeg2loglikelihoodREML_grad,
     GetNeg2loglikelihood_batch,
     GetNeg2loglikelihood_grad,
     cocoPredict_dense,

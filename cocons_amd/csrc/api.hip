@@ -4051,12 +4051,20 @@ struct GradState {
     DevBuf<double> ARpart;        // its partial sums (grad_sigma_r_scratch_doubles)
     DevBuf<double> site;          // GSITE_FIELDS x npad
     DevBuf<double> out;           // 7 p: theta-table gradient, mean gradient
+    // Profile / REML gradients only (allocated by their first call, for a border of pcols = r + max(p, q) rows)
+    DevBuf<double> SX;            // npad x pcols: Sigma^-1 [Z | Xb]
+    DevBuf<double> SXpart;        // its partial sums
+    DevBuf<double> LR;            // npad x pcols: the low-rank block [U | sqrt(r) C]
+    DevBuf<double> gls;           // chol(Xb' Sigma^-1 Xb) and beta (grad_gls_doubles)
+    int pcols = 0;
     long long bytes = 0;          // device bytes of the buffers above
 };
 
-static size_t grad_lda(const cocons_fit *f)
+// leading dimension of the gradient's layout with nb rows (residuals, or Z' and Xb') in front of the unit rows; while nb <= 128
+// it does not depend on nb
+static size_t grad_lda(const cocons_fit *f, int nb)
 {
-    return (size_t)f->npad + (size_t)round_up(f->r > 0 ? f->r : 1, TILE) + (size_t)f->npad;
+    return (size_t)f->npad + (size_t)round_up(nb > 0 ? nb : 1, TILE) + (size_t)f->npad;
 }
 
 // f->lda / f->rhs_act in the gradient's layout while one gradient operation runs, the objective's afterwards (every way
@@ -4065,9 +4073,9 @@ struct GradLayout {
     cocons_fit *f;
     size_t lda;
     int rhs_act;
-    explicit GradLayout(cocons_fit *f_) : f(f_), lda(f_->lda), rhs_act(f_->rhs_act)
+    GradLayout(cocons_fit *f_, int nb) : f(f_), lda(f_->lda), rhs_act(f_->rhs_act)
     {
-        f->lda = grad_lda(f);
+        f->lda = grad_lda(f, nb);
         f->rhs_act = (int)(f->lda - (size_t)f->npad);
         f->border_clean = -1; f->border_pending = -1;
     }
@@ -4085,6 +4093,41 @@ static int grad_refuse(cocons_fit *f, const char *who)
 {
     if (int rc = no_taper(f, who)) return rc;
     if (f->coll_kind) return fail(-1, "%s: not available on a sharded handle", who);
+    return 0;
+}
+
+// the end of every gradient operation: -Sigma^-1 into the leading square (the unit rows, now L^-T, start rt rows under the
+// matrix), then -- with hgrad -- the site factors and the contraction of W = coef Sigma^-1 - LR LR' (LR: npad x ncol) with
+// dSigma/dtheta; the 7 p results (6 x p table, then the dense gradient's mean row) go to hgrad
+static int grad_contract(cocons_fit *f, const double *theta, int rt, const double *LR, int ncol, double coef, double *hgrad)
+{
+    const int npad = f->npad, p = f->p;
+    hipStream_t s = f->stream;
+    GradState *G = f->grad.get();
+    launch_grad_fill(f->dA, f->lda, 0, npad, npad, -1, s);
+    launch_grad_syrk(f->dA, f->lda, npad, npad + rt, s);
+    if (!hgrad) return 0;
+    ThetaVecs tv;
+    make_theta_vecs(theta, p, tv);
+    const ModeSel ms = select_mode(theta, p, f->smooth_limits, 0);
+    const int smooth_free = ms.smooth_kind == SMOOTH_LOGISTIC_SQRT && f->smooth_limits[1] != f->smooth_limits[0];
+    launch_grad_site(loc_args(f->n, p, f->dX, f->dlocs, G->site, npad, tv, ms.smooth_kind, f->smooth_limits), G->site, npad,
+                     smooth_free, s);
+    GradArgs g;
+    memset(&g, 0, sizeof g);
+    g.n = f->n; g.pad0 = f->pad0; g.npad = npad; g.p = p;
+    g.S = f->dA; g.lds = f->lda;
+    g.AR = LR; g.ldar = npad; g.nr = ncol; g.coef = coef;
+    g.loc = f->dloc; g.stride = npad; g.site = G->site;
+    g.X = f->dX; g.ldx = f->n;
+    g.gr = ms.gr; g.nu_fixed = ms.nu_fixed; g.smooth_free = smooth_free;
+    const size_t T = (size_t)npad / 64, ntile = T * (T + 1) / 2;
+    g.part_row = G->scratch; g.part_col = g.part_row + ntile * 6 * 64; g.part_glob = g.part_col + ntile * 6 * 64;
+    g.gsite = g.part_glob + ntile;
+    g.out = G->out;
+    launch_grad_pairs(ms.mode, g, s);
+    HIPCHK(hipMemcpyAsync(hgrad, G->out, (size_t)7 * p * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -4111,34 +4154,40 @@ static int grad_enqueue(cocons_fit *f, const double *theta, const double *mean, 
     launch_finalize(f->dA, f->lda, f->n, npad, nr, f->dout, s);
     HIPCHK(hipMemcpyAsync(f->hout, f->dout, (size_t)(1 + nr * nr) * sizeof(double), hipMemcpyDeviceToHost, s));
     if (nr > 0) launch_grad_sigma_r(f->dA, f->lda, npad, npad, nr, npad + rt, G->ARpart, G->AR, s);
-    launch_grad_fill(f->dA, f->lda, 0, npad, npad, -1, s);
-    launch_grad_syrk(f->dA, f->lda, npad, npad + rt, s);
-    if (!full) return 0;
-    ThetaVecs tv;
-    make_theta_vecs(theta, p, tv);
-    const ModeSel ms = select_mode(theta, p, f->smooth_limits, 0);
-    const int smooth_free = ms.smooth_kind == SMOOTH_LOGISTIC_SQRT && f->smooth_limits[1] != f->smooth_limits[0];
-    launch_grad_site(loc_args(f->n, p, f->dX, f->dlocs, G->site, npad, tv, ms.smooth_kind, f->smooth_limits), G->site, npad,
-                     smooth_free, s);
-    GradArgs g;
-    memset(&g, 0, sizeof g);
-    g.n = f->n; g.pad0 = f->pad0; g.npad = npad; g.p = p;
-    g.S = f->dA; g.lds = f->lda;
-    g.AR = G->AR; g.ldar = npad; g.nr = nr;
-    g.loc = f->dloc; g.stride = npad; g.site = G->site;
-    g.X = f->dX; g.ldx = f->n;
-    g.gr = ms.gr; g.nu_fixed = ms.nu_fixed; g.smooth_free = smooth_free;
-    const size_t T = (size_t)npad / 64, ntile = T * (T + 1) / 2;
-    g.part_row = G->scratch; g.part_col = g.part_row + ntile * 6 * 64; g.part_glob = g.part_col + ntile * 6 * 64;
-    g.gsite = g.part_glob + ntile;
-    g.out = G->out;
-    launch_grad_pairs(ms.mode, g, s);
-    HIPCHK(hipMemcpyAsync(hgrad, G->out, (size_t)7 * p * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipGetLastError());
-    return 0;
+    return grad_contract(f, theta, rt, G->AR, nr, (double)nr, full ? hgrad : nullptr);
 }
 
-static int grad_prepare(cocons_fit *f, const char *who)
+// The same operation for the Profile (reml = false, Xb = x_betas) and REML (Xb = x_covariates) objectives: the border is
+// [Z' ; Xb'] without a trend (as the value entries' run_eval), its Gram matrix gives value and parts (profile_tail, on the
+// host once the operation is complete) and, on the device, beta and chol(Xb' Sigma^-1 Xb); the contraction runs on
+//     W = r Sigma^-1 - U U' [- r C C'],   U = Sigma^-1 (Z - Xb beta),  C = Sigma^-1 Xb chol(Xb' Sigma^-1 Xb)^-T.
+static int profile_grad_enqueue(cocons_fit *f, const double *theta, const double *dxb, int nxb, bool reml, double *hgrad)
+{
+    const int npad = f->npad, r = f->r, nb = r + nxb, rt = round_up(nb, TILE), p = f->p;
+    hipStream_t s = f->stream;
+    GradState *G = f->grad.get();
+    f->nrhs_cur = nb;
+    assemble_sigma(f, theta, 0, 0, npad);
+    RhsArgs ra;
+    memset(&ra, 0, sizeof ra);
+    ra.n = f->n; ra.p = p; ra.X = f->dX; ra.ldx = f->n; ra.use_trend = 0;
+    ra.src = f->dz; ra.lds = f->n;
+    ra.out = f->dA; ra.ld = f->lda; ra.row0 = npad; ra.nrows = r; ra.nrows_zero = 0;
+    ra.col0 = 0; ra.ncols_out = npad;
+    launch_rhs_rows(ra, s);
+    ra.src = dxb; ra.row0 = npad + r; ra.nrows = nxb; ra.nrows_zero = rt - nb;
+    launch_rhs_rows(ra, s);
+    launch_grad_fill(f->dA, f->lda, npad + rt, npad, npad, npad + rt, s);
+    if (int rc = factorize(f, main_view(f), nullptr)) return rc;
+    launch_finalize(f->dA, f->lda, f->n, npad, nb, f->dout, s);
+    HIPCHK(hipMemcpyAsync(f->hout, f->dout, (size_t)(1 + nb * nb) * sizeof(double), hipMemcpyDeviceToHost, s));
+    launch_grad_sigma_r(f->dA, f->lda, npad, npad, nb, npad + rt, G->SXpart, G->SX, s);
+    launch_grad_lowrank(f->dout, G->SX, npad, r, nxb, reml ? 1 : 0, G->gls, G->LR, s);
+    return grad_contract(f, theta, rt, G->LR, reml ? nb : r, (double)r, hgrad);
+}
+
+// nb: rows in front of the unit rows (the dense gradient's r); pcols > 0: the Profile / REML buffers for that many columns
+static int grad_prepare(cocons_fit *f, const char *who, int nb, int pcols = 0)
 {
     const int r1 = f->r > 0 ? f->r : 1;
     if (!f->grad) {
@@ -4153,10 +4202,22 @@ static int grad_prepare(cocons_fit *f, const char *who)
         G->bytes = (long long)((sc + ar + arp + si + ou) * sizeof(double));
         f->grad = std::move(G);
     }
+    if (pcols > f->grad->pcols) {
+        GradState *G = f->grad.get();
+        const size_t sx = (size_t)f->npad * pcols, sxp = grad_sigma_r_scratch_doubles(f->npad, pcols),
+                     gl = grad_gls_doubles(f->r, pcols - f->r);
+        HIPCHK_AT(who, hipStreamSynchronize(f->stream));
+        HIPCHK_AT(who, G->SX.alloc(sx));
+        HIPCHK_AT(who, G->SXpart.alloc(sxp));
+        HIPCHK_AT(who, G->LR.alloc(sx));
+        HIPCHK_AT(who, G->gls.alloc(gl));
+        G->bytes += (long long)((2 * sx + sxp + gl) * sizeof(double));
+        G->pcols = pcols;
+    }
     if (!f->dA) return fail(-1, "%s: the handle has no matrix buffer", who);
     // dA large enough for the gradient's layout: grown once, f->lda unchanged (GradLayout); the contents need not survive
     // (every operation assembles its matrix anew)
-    const size_t need = grad_lda(f) * (size_t)f->npad;
+    const size_t need = grad_lda(f, nb) * (size_t)f->npad;
     bool grew = false;
     HIPCHK_AT(who, f->dA.reserve(need, f->stream, f->stream2, 0, false, &grew));
     if (grew) {
@@ -4175,15 +4236,59 @@ extern "C" int cocons_neg2loglik_grad_dense(cocons_fit *f, const double *theta, 
     FIT_ENTER(f);
     if (int rc = grad_refuse(f, who)) return rc;
     if (f->r < 1) return fail(-1, "%s: fit has no z", who);
-    if (int rc = grad_prepare(f, who)) return rc;
+    if (int rc = grad_prepare(f, who, f->r)) return rc;
     std::vector<double> hg((size_t)7 * f->p);
-    GradLayout layout(f);
+    GradLayout layout(f, f->r);
     const int st = run_op(f, who, [&]() -> int { return grad_enqueue(f, theta, mean, true, hg.data()); });
     if (st) return st;                  // failing minor: nothing written
     dense_collect(f, sum_logliks, parts);
     memcpy(grad_theta, hg.data(), (size_t)6 * f->p * sizeof(double));
     memcpy(grad_mean, hg.data() + (size_t)6 * f->p, (size_t)f->p * sizeof(double));
     return 0;
+}
+
+// Profile / REML: value and parts from profile_tail (the value entries' own tail, on the Gram matrix of this operation's
+// border), the 6 x p table from the contraction.  Nothing is written unless everything succeeded.
+static int profile_grad_entry(cocons_fit *f, const char *who, const double *theta, const double *dxb, int nxb, double n_eff,
+                              bool reml, double *sum_logliks, double *parts, double *grad_theta)
+{
+    const int nb = f->r + nxb;
+    if (int rc = grad_prepare(f, who, nb, f->r + (f->q > f->p ? f->q : f->p))) return rc;
+    std::vector<double> hg((size_t)7 * f->p), pt((size_t)2 + nb);
+    double val = 0.0;
+    GradLayout layout(f, nb);
+    const int st = run_op(f, who, [&]() -> int { return profile_grad_enqueue(f, theta, dxb, nxb, reml, hg.data()); });
+    if (st) return st;                  // failing minor: nothing written
+    if (profile_tail(f, nxb, n_eff, reml, &val, pt.data()))
+        return fail(-4, "%s: X' Sigma^-1 X is not positive definite", who);
+    *sum_logliks = val;
+    if (parts) memcpy(parts, pt.data(), pt.size() * sizeof(double));
+    memcpy(grad_theta, hg.data(), (size_t)6 * f->p * sizeof(double));
+    return 0;
+}
+
+extern "C" int cocons_neg2loglik_profile_grad(cocons_fit *f, const double *theta, double *sum_logliks, double *parts,
+                                              double *grad_theta)
+{
+    const char *who = "cocons_neg2loglik_profile_grad";
+    if (!f) return fail(-1, "%s: null fit handle", who);
+    if (!theta || !sum_logliks || !grad_theta) return fail(-1, "%s: null argument", who);
+    FIT_ENTER(f);
+    if (int rc = grad_refuse(f, who)) return rc;
+    if (f->r < 1 || f->q < 1) return fail(-1, "%s: fit needs z and x_betas", who);
+    return profile_grad_entry(f, who, theta, f->dxb, f->q, (double)f->n_user, false, sum_logliks, parts, grad_theta);
+}
+
+extern "C" int cocons_neg2loglik_reml_grad(cocons_fit *f, const double *theta, int rank, double *sum_logliks, double *parts,
+                                           double *grad_theta)
+{
+    const char *who = "cocons_neg2loglik_reml_grad";
+    if (!f) return fail(-1, "%s: null fit handle", who);
+    if (!theta || !sum_logliks || !grad_theta) return fail(-1, "%s: null argument", who);
+    FIT_ENTER(f);
+    if (int rc = grad_refuse(f, who)) return rc;
+    if (f->r < 1) return fail(-1, "%s: fit has no z", who);
+    return profile_grad_entry(f, who, theta, f->dX, f->p, (double)(f->n_user - rank), true, sum_logliks, parts, grad_theta);
 }
 
 extern "C" int cocons_debug_sigma_inverse(cocons_fit *f, const double *theta, double *out)
@@ -4203,9 +4308,9 @@ extern "C" int cocons_debug_sigma_inverse(cocons_fit *f, const double *theta, do
         }
         return cocons_debug_sigma_inverse(f->unsorted, theta, out);
     }
-    if (int rc = grad_prepare(f, who)) return rc;
+    if (int rc = grad_prepare(f, who, f->r)) return rc;
     const std::vector<double> zero((size_t)f->p, 0.0);
-    GradLayout layout(f);
+    GradLayout layout(f, f->r);
     const int st = run_op(f, who, [&]() -> int { return grad_enqueue(f, theta, zero.data(), false, nullptr); });
     if (st) return st;
     const size_t n = (size_t)f->n_user;

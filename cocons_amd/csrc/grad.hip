@@ -2,6 +2,8 @@
 //
 //   grad_fill_kernel     : unit rows under the matrix (the bordered factorisation solves L^-T beside the residuals), zeros
 //   grad_sigma_r_kernel  : A = Sigma^-1 R = L^-T (L^-1 R) from the solved rows
+//   grad_gls_kernel / grad_lowrank_kernel : Profile / REML: beta and chol(Xb' Sigma^-1 Xb) from the border's Gram matrix, then
+//                          the low-rank block [Sigma^-1 (Z - Xb beta) | sqrt(r) V chol(W)^-T] the pair kernel takes as its A
 //   launch_grad_syrk     : -Sigma^-1 = -L^-T L^-1 (lower tiles) by the trailing-update kernel, 256 columns of L^-T at a time
 //   grad_site_kernel     : per-site derivative factors beside loc_params_kernel's SoA (tilt, smoothness, std.dev)
 //   grad_pair_kernel     : W = r Sigma^-1 - A A' contracted with dSigma/d(site predictors) over the 64 x 64 lower tiles
@@ -195,6 +197,98 @@ void launch_grad_sigma_r(const double *A, size_t lda, int npad, int wrow0, int n
     hipLaunchKernelGGL(grad_sigma_r_sum_kernel, dim3((npad + 255) / 256), dim3(256), 0, s, part, npad, nr, AR);
 }
 
+// ---------------------------------------------------------------------------
+// Profile / REML: the generalised-least-squares step between Sigma^-1 [Z | Xb] and the pair contraction.
+// G = fin + 1 is the (r + q)^2 Gram matrix of the border [Z' ; Xb'] (row-major): W = G[r.., r..] = Xb' Sigma^-1 Xb,
+// g_k = G[k, r..] = Xb' Sigma^-1 z_k.  One workgroup; the Cholesky factor and the two triangular solves run in the order of
+// the host's solve of the same matrix (profile_tail), so a pivot fails here exactly when it fails there.
+// gls[0] = 1 (W positive definite) or 0, gls[2 ..] = chol(W) (q x q column-major, lower), then beta (q x r, column k = beta_k).
+constexpr int GLS_L0 = 2;
+size_t grad_gls_doubles(int r, int q) { return (size_t)GLS_L0 + (size_t)q * q + (size_t)q * r; }
+
+__global__ void __launch_bounds__(64)
+grad_gls_kernel(const double *fin, int r, int q, double *gls)
+{
+    __shared__ double W[COCONS_P_MAX * COCONS_P_MAX];
+    __shared__ int ok;
+    const int t = threadIdx.x, nb = r + q;
+    const double *G = fin + 1;
+    for (int e = t; e < q * q; e += 64) W[e] = G[(size_t)(r + e % q) * nb + (r + e / q)];
+    if (t == 0) ok = 1;
+    __syncthreads();
+    for (int j = 0; j < q; ++j) {
+        if (t == 0) {
+            double d = W[j + j * q];
+            for (int k = 0; k < j; ++k) d -= W[j + k * q] * W[j + k * q];
+            if (!(d > 0)) ok = 0;
+            else W[j + j * q] = sqrt(d);
+        }
+        __syncthreads();
+        if (!ok) break;
+        if (t > j && t < q) {
+            double s = W[t + j * q];
+            for (int k = 0; k < j; ++k) s -= W[t + k * q] * W[j + k * q];
+            W[t + j * q] = s / W[j + j * q];
+        }
+        __syncthreads();
+    }
+    double *L = gls + GLS_L0, *beta = L + (size_t)q * q;
+    for (int e = t; e < q * q; e += 64) L[e] = (ok && e % q >= e / q) ? W[e] : 0.0;
+    for (int c = t; c < r; c += 64) {
+        double *b = beta + (size_t)c * q;
+        for (int i = 0; i < q; ++i) b[i] = ok ? G[(size_t)c * nb + (r + i)] : 0.0;
+        if (!ok) continue;
+        for (int i = 0; i < q; ++i) {
+            double s = b[i];
+            for (int k = 0; k < i; ++k) s -= W[i + k * q] * b[k];
+            b[i] = s / W[i + i * q];
+        }
+        for (int i = q - 1; i >= 0; --i) {
+            double s = b[i];
+            for (int k = i + 1; k < q; ++k) s -= W[k + i * q] * b[k];
+            b[i] = s / W[i + i * q];
+        }
+    }
+    if (t == 0) { gls[0] = ok ? 1.0 : 0.0; gls[1] = 0.0; }
+}
+
+// LR(i, k) = A_z(i, k) - sum_a V(i, a) beta(a, k), k < r; with reml LR(i, r + a) = sqrt(r) c_a, L c = V(i, .)' (forward
+// substitution per site: C = V L^-T).  One thread per site, fixed order.
+__global__ void __launch_bounds__(256)
+grad_lowrank_kernel(const double *SX, int npad, int r, int q, int reml, const double *gls, double *LR)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npad) return;
+    const bool ok = gls[0] != 0.0;
+    const double *L = gls + GLS_L0, *beta = L + (size_t)q * q;
+    const double *V = SX + (size_t)r * npad;
+    for (int k = 0; k < r; ++k) {
+        double s = SX[(size_t)i + (size_t)k * npad];
+        for (int a = 0; a < q; ++a) s -= V[(size_t)i + (size_t)a * npad] * beta[a + (size_t)k * q];
+        LR[(size_t)i + (size_t)k * npad] = ok ? s : 0.0;
+    }
+    if (!reml) return;
+    double *C = LR + (size_t)r * npad;
+    if (!ok) {
+        for (int a = 0; a < q; ++a) C[(size_t)i + (size_t)a * npad] = 0.0;
+        return;
+    }
+    for (int a = 0; a < q; ++a) {           // (c_b, b < a, is read back from this thread's own stores)
+        double s = V[(size_t)i + (size_t)a * npad];
+        for (int b = 0; b < a; ++b) s -= L[a + b * q] * C[(size_t)i + (size_t)b * npad];
+        C[(size_t)i + (size_t)a * npad] = s / L[a + a * q];
+    }
+    const double sr = sqrt((double)r);
+    for (int a = 0; a < q; ++a) C[(size_t)i + (size_t)a * npad] *= sr;
+}
+
+void launch_grad_lowrank(const double *fin, const double *SX, int npad, int r, int q, int reml, double *gls, double *LR,
+                         hipStream_t s)
+{
+    hipLaunchKernelGGL(grad_gls_kernel, dim3(1), dim3(64), 0, s, fin, r, q, gls);
+    hipLaunchKernelGGL(grad_lowrank_kernel, dim3((npad + 255) / 256), dim3(256), 0, s, SX, npad, r, q, reml, gls, LR);
+}
+
 // C(i, j) -= sum_k B(i, k) B(j, k) over the lower tiles of the leading npad x npad square (zero beforehand): -Sigma^-1.
 // B is upper triangular, so the 256 columns from k0 on only reach the tile rows below k0 + 256: about n^3 / 3 flops.
 void launch_grad_syrk(double *A, size_t lda, int npad, int brow0, hipStream_t s)
@@ -337,7 +431,7 @@ grad_pair_kernel(GradArgs g)
         const bool cin = c >= g.pad0 && c < g.n;
         double dcol[GFAM] = {0, 0, 0, 0, 0, 0};
         if (rin && cin && r >= c) {
-            double W = -(double)g.nr * g.S[(size_t)r + (size_t)c * g.lds];
+            double W = -g.coef * g.S[(size_t)r + (size_t)c * g.lds];
             for (int k = 0; k < g.nr; ++k) W -= g.AR[(size_t)r + (size_t)k * g.ldar] * g.AR[(size_t)c + (size_t)k * g.ldar];
             if (r == c) {
                 racc[TH_SD_] += W * g.site[3 * g.stride + r];

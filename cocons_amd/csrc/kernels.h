@@ -290,7 +290,8 @@ constexpr int GSITE_FIELDS = 4;    // launch_grad_site: dtilt/deta, cot(tilt), d
 struct GradArgs {
     int n, pad0, npad, p;          // internal order: sites [pad0, n) are the caller's
     const double *S; size_t lds;   // -Sigma^-1, lower triangle (launch_grad_syrk)
-    const double *AR; size_t ldar; int nr;    // A = Sigma^-1 R, npad x nr
+    const double *AR; size_t ldar; int nr;    // the low-rank block, npad x nr: A = Sigma^-1 R (dense), [U | sqrt(r) C] (Profile / REML)
+    double coef;                   // W = coef Sigma^-1 - AR AR': nr for the dense gradient, r for Profile / REML
     const double *loc; size_t stride;         // loc_params_kernel's SoA
     const double *site;                       // launch_grad_site's SoA (GSITE_FIELDS x stride)
     const double *X; int ldx;
@@ -308,6 +309,13 @@ void launch_grad_sigma_r(const double *A, size_t lda, int npad, int wrow0, int n
                          hipStream_t s);
 // the leading npad x npad square of A (lower tiles, zero beforehand) -= B B', B = rows brow0.. (upper triangular)
 void launch_grad_syrk(double *A, size_t lda, int npad, int brow0, hipStream_t s);
+// Profile / REML: fin = launch_finalize's output of a border [Z' ; Xb'] (log-determinant, then the
+// (r + q)^2 Gram matrix), SX (npad x (r + q)) = Sigma^-1 [Z | Xb] = [A_z | V].  W = Xb' Sigma^-1 Xb is factored in one
+// workgroup (gls: grad_gls_doubles(r, q) doubles of scratch), then LR (npad x (r [+ q])) = [A_z - V beta | sqrt(r) V chol(W)^-T]
+// (the second block with reml only).  A pivot of W that is not positive leaves LR all zero.
+size_t grad_gls_doubles(int r, int q);
+void launch_grad_lowrank(const double *fin, const double *SX, int npad, int r, int q, int reml, double *gls, double *LR,
+                         hipStream_t s);
 void launch_grad_site(const LocArgs &a, double *out, size_t stride, int smooth_free, hipStream_t s);
 size_t grad_scratch_doubles(int npad);
 // pair contraction, per-site sums and X' g into g.out (7 p doubles)

@@ -337,6 +337,27 @@ class CoconsFit:
                    "cocons_neg2loglik_reml")
         return val.value, parts
 
+    def neg2loglik_profile_grad_core(self, theta_list):
+        """The value and parts of `neg2loglik_profile_core` and the analytic gradient over the 6 x p table
+        (cocons_neg2loglik_profile_grad): (value, parts, grad_table).  The mean is profiled out: no mean gradient."""
+        T = theta_table(theta_list)
+        val = ctypes.c_double(0.0)
+        parts = np.zeros(2 + self.r + self.q)
+        gt = np.zeros((6, self.p))
+        _lib.check(self._L.cocons_neg2loglik_profile_grad(self._h, _p(T), ctypes.byref(val), _p(parts), _p(gt)),
+                   "cocons_neg2loglik_profile_grad")
+        return val.value, parts, gt
+
+    def neg2loglik_reml_grad_core(self, theta_list, rank):
+        """The same for `neg2loglik_reml_core` (cocons_neg2loglik_reml_grad)."""
+        T = theta_table(theta_list)
+        val = ctypes.c_double(0.0)
+        parts = np.zeros(2 + self.r + self.p)
+        gt = np.zeros((6, self.p))
+        _lib.check(self._L.cocons_neg2loglik_reml_grad(self._h, _p(T), int(rank), ctypes.byref(val), _p(parts), _p(gt)),
+                   "cocons_neg2loglik_reml_grad")
+        return val.value, parts, gt
+
     def predict_core(self, theta_list, locs_pred, x_covariates_pred, z_col=0):
         T = theta_table(theta_list)
         mean = np.ascontiguousarray(np.asarray(theta_list["mean"], dtype=np.float64))
@@ -714,6 +735,50 @@ def GetNeg2loglikelihoodREML(theta, par_pos, locs, x_covariates, x_betas, smooth
                 return 1e6
             raise RuntimeError("Cholesky error")
         return val + getPen((n - rank) * f.r, lam, tl, smooth_limits)
+    finally:
+        if own:
+            f.close()
+
+
+def _profile_grad_result(theta, par_pos, tl, core, N, lam, smooth_limits, safe):
+    """(value, gradient over the optimiser's vector) from a Profile / REML core call: the table plus the penalty's gradient
+    through getModelLists(type="diff"); the contract of GetNeg2loglikelihood_grad after a failing Cholesky."""
+    try:
+        val, _, gt = core()
+    except CholeskyError:
+        if safe:
+            return 1e6, np.zeros(np.asarray(theta).size)
+        raise RuntimeError("Cholesky error")
+    g = getPen_grad(N, lam, tl, smooth_limits)
+    for t, k in enumerate(COV_ASPECTS):
+        g[k] = g[k] + gt[t]
+    return val + getPen(N, lam, tl, smooth_limits), getModelLists_grad(g, par_pos)
+
+
+def GetNeg2loglikelihoodProfile_grad(theta, par_pos, locs, x_covariates, smooth_limits, z, n, x_betas, lam,
+                                     safe=True, fit=None):
+    """`GetNeg2loglikelihoodProfile` and its gradient over the optimiser's vector in one call: (value, gradient)
+    (cocons_neg2loglik_profile_grad; the mean is profiled out, so `par_pos["mean"]` holds no free entry)."""
+    tl = getModelLists(theta, par_pos, "diff")
+    f, own = _with_fit(fit, locs, x_covariates, z, smooth_limits, x_betas=x_betas)
+    try:
+        return _profile_grad_result(theta, par_pos, tl, lambda: f.neg2loglik_profile_grad_core(tl), n * f.r, lam,
+                                    smooth_limits, safe)
+    finally:
+        if own:
+            f.close()
+
+
+def GetNeg2loglikelihoodREML_grad(theta, par_pos, locs, x_covariates, x_betas, smooth_limits, z, n, lam,
+                                  safe=True, fit=None):
+    """`GetNeg2loglikelihoodREML` and its gradient over the optimiser's vector in one call: (value, gradient)
+    (cocons_neg2loglik_reml_grad; x_betas is accepted and unused, as there)."""
+    tl = getModelLists(theta, par_pos, "diff")
+    f, own = _with_fit(fit, locs, x_covariates, z, smooth_limits)
+    try:
+        rank = int(np.linalg.matrix_rank(np.asarray(x_covariates, dtype=np.float64)))
+        return _profile_grad_result(theta, par_pos, tl, lambda: f.neg2loglik_reml_grad_core(tl, rank), (n - rank) * f.r,
+                                    lam, smooth_limits, safe)
     finally:
         if own:
             f.close()

@@ -147,6 +147,35 @@ GetNeg2loglikelihoodREML <- function(theta, par.pos, locs, x_covariates, x_betas
   v[1] + .cocons.getPen(n * dim(as.matrix(z))[2], lambda, theta_list, smooth.limits)
 }
 
+# gradient over theta (the optimiser's vector) from a Profile / REML value + gradient call: res = list(v, table 6 x p) or
+# NULL after a failing Cholesky under safe (zeros, where the value functions return 1e6); N as the value function's getPen
+.cocons.hip.profile.grad <- function(res, theta, theta_list, par.pos, N, lambda, smooth.limits) {
+  if (is.null(res)) return(rep(0, length(theta)))
+  G <- .cocons.hip.getPen.grad(N, lambda, theta_list, smooth.limits)
+  aspects <- c("std.dev", "scale", "aniso", "tilt", "smooth", "nugget")
+  for (t in seq_along(aspects)) G[[aspects[t]]] <- G[[aspects[t]]] + res[[2]][t, ]
+  .cocons.hip.diff.grad(G, par.pos)
+}
+
+# gradients of GetNeg2loglikelihoodProfile / GetNeg2loglikelihoodREML over theta, with their signatures: what cocoOptim's
+# pml / reml branch can pass as `gr` (INTEGRATION.md).  The mean is profiled out (par.pos$mean all FALSE there).
+GetNeg2loglikelihoodProfileGrad <- function(theta, par.pos, locs, x_covariates, smooth.limits, z, n, x_betas,
+                                            lambda, safe = TRUE, fit = NULL) {
+  theta_list <- cocons::getModelLists(theta = theta, par.pos = par.pos, type = "diff")
+  if (is.null(fit)) fit <- .cocons.hip.cached(locs, x_covariates, z, smooth.limits, x_betas)
+  res <- .cocons.hip.result(.Call(`_cocons_hip_neg2loglik_profile_grad`, fit, theta_list[-1]), safe)
+  .cocons.hip.profile.grad(res, theta, theta_list, par.pos, n * dim(as.matrix(z))[2], lambda, smooth.limits)
+}
+
+GetNeg2loglikelihoodREMLGrad <- function(theta, par.pos, locs, x_covariates, x_betas, smooth.limits, z, n,
+                                         lambda, safe = TRUE, fit = NULL) {
+  theta_list <- cocons::getModelLists(theta = theta, par.pos = par.pos, type = "diff")
+  if (is.null(fit)) fit <- .cocons.hip.cached(locs, x_covariates, z, smooth.limits)
+  res <- .cocons.hip.result(.Call(`_cocons_hip_neg2loglik_reml_grad`, fit, theta_list[-1],
+                                  as.integer(qr(x_covariates)$rank)), safe)
+  .cocons.hip.profile.grad(res, theta, theta_list, par.pos, n * dim(as.matrix(z))[2], lambda, smooth.limits)
+}
+
 # GLS coefficients after a pml / reml fit (R/optim.R:329-341) without a second chol:
 # v = c(sum_logliks, logdet, logdet_W, quad_1..r, beta_1..) as returned by the cores above
 .cocons.hip.betas <- function(v, r) v[-seq_len(3 + r)]

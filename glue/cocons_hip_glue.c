@@ -461,6 +461,51 @@ SEXP _cocons_hip_neg2loglik_reml(SEXP fitp, SEXP theta, SEXP rank)
     return out;
 }
 
+/* list(status, list(v, 6 x p gradient table)) of a Profile / REML value + gradient call: v = c(sum_logliks, parts...) as the
+ * value entries return it (a failing minor writes nothing: the table stays zero) */
+static SEXP profile_grad_result(int rc, SEXP v, const double *G, int p)
+{
+    SEXP gt = PROTECT(Rf_allocMatrix(REALSXP, 6, p));
+    for (int t = 0; t < 6; ++t)
+        for (int k = 0; k < p; ++k) REAL(gt)[t + 6 * k] = G[t * p + k];
+    SEXP res = PROTECT(Rf_allocVector(VECSXP, 2));
+    SET_VECTOR_ELT(res, 0, v);
+    SET_VECTOR_ELT(res, 1, gt);
+    SEXP out = status_value(rc, res);
+    UNPROTECT(2);
+    return out;
+}
+
+/* Profile value and analytic gradient (cocons_neg2loglik_profile_grad) */
+SEXP _cocons_hip_neg2loglik_profile_grad(SEXP fitp, SEXP theta)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), r = fit_r(fitp), q = fit_q(fitp);
+    double T[6 * COCONS_P_MAX], G[6 * COCONS_P_MAX] = {0};
+    theta_table(theta, p, T);
+    SEXP v = PROTECT(Rf_allocVector(REALSXP, 1 + 2 + r + q));
+    int rc = cocons_neg2loglik_profile_grad(f, T, REAL(v), REAL(v) + 1, G);
+    hip_check(rc, "GetNeg2loglikelihoodProfile (gradient)");
+    SEXP out = profile_grad_result(rc, v, G, p);
+    UNPROTECT(1);
+    return out;
+}
+
+/* REML value and analytic gradient (cocons_neg2loglik_reml_grad); rank = qr(x_covariates)$rank */
+SEXP _cocons_hip_neg2loglik_reml_grad(SEXP fitp, SEXP theta, SEXP rank)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), r = fit_r(fitp);
+    double T[6 * COCONS_P_MAX], G[6 * COCONS_P_MAX] = {0};
+    theta_table(theta, p, T);
+    SEXP v = PROTECT(Rf_allocVector(REALSXP, 1 + 2 + r + p));
+    int rc = cocons_neg2loglik_reml_grad(f, T, Rf_asInteger(rank), REAL(v), REAL(v) + 1, G);
+    hip_check(rc, "GetNeg2loglikelihoodREML (gradient)");
+    SEXP out = profile_grad_result(rc, v, G, p);
+    UNPROTECT(1);
+    return out;
+}
+
 /* dense kriging core (R/predict.R:136-183): list(status, cbind(stochastic, quadform)) */
 SEXP _cocons_hip_predict(SEXP fitp, SEXP theta, SEXP mean, SEXP z_col, SEXP locs_pred, SEXP X_pred)
 {
@@ -709,6 +754,8 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_neg2loglik_batch", (DL_FUNC)&_cocons_hip_neg2loglik_batch, 3},
     {"_cocons_hip_neg2loglik_profile", (DL_FUNC)&_cocons_hip_neg2loglik_profile, 2},
     {"_cocons_hip_neg2loglik_reml", (DL_FUNC)&_cocons_hip_neg2loglik_reml, 3},
+    {"_cocons_hip_neg2loglik_profile_grad", (DL_FUNC)&_cocons_hip_neg2loglik_profile_grad, 2},
+    {"_cocons_hip_neg2loglik_reml_grad", (DL_FUNC)&_cocons_hip_neg2loglik_reml_grad, 3},
     {"_cocons_hip_predict", (DL_FUNC)&_cocons_hip_predict, 6},
     {"_cocons_hip_predict_taper", (DL_FUNC)&_cocons_hip_predict_taper, 9},
     {"_cocons_hip_krige_prepare", (DL_FUNC)&_cocons_hip_krige_prepare, 5},

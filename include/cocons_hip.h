@@ -199,6 +199,21 @@ int cocons_neg2loglik_profile(cocons_fit *fit, const double *theta,
 int cocons_neg2loglik_reml(cocons_fit *fit, const double *theta, int rank,
                            double *sum_logliks, double *parts);
 
+/* The values of cocons_neg2loglik_profile / _reml and their analytic gradients in one call.  sum_logliks and
+ * parts (may be NULL; 2 + r + nxb doubles, GLS coefficients included) exactly as the value entries define them; grad_theta is
+ * the 6 x p table in theta's layout, as cocons_neg2loglik_grad_dense returns it.  There is no mean gradient: the mean is
+ * profiled out.  One factorisation with [Z' ; Xb' ; I] bordered under Sigma; the contraction of the dense gradient runs on
+ *   profile:  W = r Sigma^-1 - U U'                  U = Sigma^-1 (Z - Xb beta)
+ *   reml:     W = r Sigma^-1 - U U' - r C C'         C = Sigma^-1 Xb chol(Xb' Sigma^-1 Xb)^-T
+ * with fixed-order sums: repeated calls agree bit for bit.  0, the failing minor k > 0, -4 when Xb' Sigma^-1 Xb is not
+ * positive definite, or < 0 with a message that starts with the entry's name; outputs are written on 0 only.  Refused (-1)
+ * on taper and sharded handles, on a handle without z and (profile) without x_betas.  Memory as for
+ * cocons_neg2loglik_grad_dense: while r + nxb <= 128 the matrix allocation is the one that entry grows.              */
+int cocons_neg2loglik_profile_grad(cocons_fit *fit, const double *theta,
+                                   double *sum_logliks, double *parts, double *grad_theta);
+int cocons_neg2loglik_reml_grad(cocons_fit *fit, const double *theta, int rank,
+                                double *sum_logliks, double *parts, double *grad_theta);
+
 /* Dense kriging core: replaces R/predict.R:136-183
  *   observed_cov <- cov_rns(...); cov_pred <- cov_rns_pred(...);
  *   inv_cov <- solve(observed_cov, t(cov_pred)); crossprod(resid, inv_cov);

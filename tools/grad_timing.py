@@ -6,8 +6,11 @@ analytic gradient against the central-difference gradient through the batch: ite
 Stage times come from a run of `--stages-only N --reps K` under rocprofv3 --kernel-trace --stats -f csv, summarised with
 `--stats-csv FILE --n N --calls K`: the trailing updates (factorisation, L^-T border and the product -L^-T L^-1 share one
 kernel and are reported together, at their executed and their useful TFLOP/s), panels, assembly, Sigma^-1 R, contraction.
+--objective pml | reml does the same for cocons_neg2loglik_profile_grad / _reml_grad (x_betas = X, the mean profiled out):
+one value call, one value + gradient call, the 1 + 2P sequential value calls of a central difference, the dense gradient call
+on the same handle, and the L-BFGS-B comparison with and without the analytic gradient.
 One JSON line.
-usage: tools/grad_timing.py [--sizes 4096,10000] [--reps 5] [--no-optim] [--stages-only N] [--stats-csv FILE --n N --calls K]"""
+usage: tools/grad_timing.py [--objective ml|pml|reml] [--sizes 4096,10000] [--reps 5] [--no-optim] [--stages-only N] [--stats-csv FILE --n N --calls K]"""
 import argparse
 import csv
 import json
@@ -95,7 +98,78 @@ def optim(n, maxiter):
     return res
 
 
-PEAK_F64_MFMA = 78.6e12     # TFLOP/s of v_mfma_f64_16x16x4_f64 over the chip
+def _profiled(objective, locs, X, z, n):
+    """(fit, par_pos, x0, value(x), value_and_gradient(x), core value call, core gradient call) of --objective pml | reml:
+    x_betas = X (q = p = 3), the mean profiled out (par_pos["mean"] all False)."""
+    pp = wl.par_pos_full()
+    pp["mean"] = [False] * X.shape[1]
+    x0 = wl.theta_vector_from_lists(wl.theta_full(), pp)
+    lam = (0.0, 0.0, 0.0)
+    fit = ca.CoconsFit(locs, X, z, wl.SMOOTH_LIMITS, x_betas=X)
+    rank = int(np.linalg.matrix_rank(X))
+    if objective == "pml":
+        def value(x):
+            return host.GetNeg2loglikelihoodProfile(x, pp, locs, X, wl.SMOOTH_LIMITS, z, n, X, lam, fit=fit)
+
+        def fg(x):
+            return host.GetNeg2loglikelihoodProfile_grad(x, pp, locs, X, wl.SMOOTH_LIMITS, z, n, X, lam, fit=fit)
+        core, core_grad = fit.neg2loglik_profile_core, fit.neg2loglik_profile_grad_core
+    else:
+        def value(x):
+            return host.GetNeg2loglikelihoodREML(x, pp, locs, X, X, wl.SMOOTH_LIMITS, z, n, lam, fit=fit)
+
+        def fg(x):
+            return host.GetNeg2loglikelihoodREML_grad(x, pp, locs, X, X, wl.SMOOTH_LIMITS, z, n, lam, fit=fit)
+
+        def core(tl):
+            return fit.neg2loglik_reml_core(tl, rank)
+
+        def core_grad(tl):
+            return fit.neg2loglik_reml_grad_core(tl, rank)
+    return fit, pp, x0, value, fg, core, core_grad
+
+
+def time_size_profiled(objective, n, reps):
+    """One value call, one value + gradient call, the 1 + 2P SEQUENTIAL value calls of a central difference (there is no
+    batch entry for these objectives), and the dense gradient call on the same handle for comparison."""
+    locs, X, z = problem(n)
+    fit, pp, x0, value, fg, core, core_grad = _profiled(objective, locs, X, z, n)
+    try:
+        tl = host.getModelLists(x0, pp, "diff")
+        tls = [host.getModelLists(y, pp, "diff") for y in fd_points(x0, 1.2e-4)]
+        out = {"n": n, "objective": objective, "points": len(tls),
+               "value_ms": best(lambda: core(tl), reps),
+               "grad_ms": best(lambda: core_grad(tl), reps),
+               "sequential_ms": best(lambda: [core(t) for t in tls], max(1, reps // 2)),
+               "dense_grad_ms": best(lambda: fit.neg2loglik_grad_core(tl), reps)}
+    finally:
+        fit.close()
+    out["grad_over_value"] = out["grad_ms"] / out["value_ms"]
+    out["grad_over_sequential"] = out["grad_ms"] / out["sequential_ms"]
+    return out
+
+
+def optim_profiled(objective, n, maxiter):
+    from scipy.optimize import minimize
+    locs, X, z = problem(n)
+    fit, pp, x0, value, fg, core, core_grad = _profiled(objective, locs, X, z, n)
+    res = {}
+    try:
+        def fg_fd(x, h=1.2e-4):
+            v = np.array([value(y) for y in fd_points(x, h)])
+            return v[0], (v[1::2] - v[2::2]) / (2 * h)
+
+        for name, fun in (("analytic", fg), ("central_difference", fg_fd)):
+            t0 = time.perf_counter()
+            r = minimize(fun, x0, jac=True, method="L-BFGS-B", options={"maxiter": maxiter})
+            res[name] = {"iterations": int(r.nit), "evaluations": int(r.nfev), "value": float(r.fun),
+                         "wall_s": time.perf_counter() - t0, "message": str(r.message)}
+    finally:
+        fit.close()
+    return res
+
+
+PEAK_F64_MFMA = 78.6e12    # TFLOP/s of v_mfma_f64_16x16x4_f64 over the chip (DESIGN.md §6)
 
 
 def stages(csv_path, n, calls):
@@ -139,9 +213,26 @@ def main():
     ap.add_argument("--stats-csv", default="")
     ap.add_argument("--n", type=int, default=10000)
     ap.add_argument("--calls", type=int, default=3, help="gradient calls of the --stages-only run the stats cover")
+    ap.add_argument("--objective", choices=("ml", "pml", "reml"), default="ml",
+                    help="pml / reml: the Profile / REML value and gradient entries against 1 + 2P sequential value calls")
     a = ap.parse_args()
     if a.stats_csv:
         print(json.dumps(stages(a.stats_csv, a.n, a.calls)))
+        return
+    if a.objective != "ml":
+        if a.stages_only:
+            locs, X, z = problem(a.stages_only)
+            fit, pp, x0, value, fg, core, core_grad = _profiled(a.objective, locs, X, z, a.stages_only)
+            tl = host.getModelLists(x0, pp, "diff")
+            for _ in range(a.reps):
+                core_grad(tl)
+            fit.close()
+            return
+        out = {"objective": a.objective,
+               "sizes": [time_size_profiled(a.objective, int(float(s)), a.reps) for s in a.sizes.split(",")]}
+        if not a.no_optim:
+            out["lbfgsb_n4096"] = optim_profiled(a.objective, 4096, a.maxiter)
+        print(json.dumps(out))
         return
     if a.stages_only:
         locs, X, z = problem(a.stages_only)
