@@ -11,6 +11,8 @@ from .host import (  # noqa: F401
     GetNeg2loglikelihood,
     GetNeg2loglikelihoodTaper,
     GetNeg2loglikelihoodTaperProfile,
+    GetNeg2loglikelihoodTaperProfile_grad,
+    GetNeg2loglikelihoodTaper_grad,
     GetNeg2loglikelihoodProfile,
     GetNeg2loglikelihoodREML,
     GetNeg2loglikelihoodProfile_grad,

@@ -471,6 +471,7 @@ struct cocons_fit {
                                   // can neither be used nor destroyed until the probe is over)
     std::unique_ptr<struct KrigeState> krige;   // kriging state (cocons_krige_prepare): one factor of Sigma(theta) held apart from dA
     std::unique_ptr<struct GradState> grad;     // scratch of cocons_neg2loglik_grad_dense (allocated on first use)
+    std::unique_ptr<struct TaperGradState> tgrad;   // taper fit: state of cocons_neg2loglik_grad_taper (allocated on first use)
 };
 
 // Kriging state of a dense handle (cocons_krige_prepare / _apply / _release).  Everything apply reads lives here, owned by
@@ -4086,6 +4087,20 @@ struct GradLayout {
     }
 };
 
+// State of cocons_neg2loglik_grad_taper on a taper handle: the selected inverse goes to a second buffer of
+// the band's shape, the factor in dA is consumed by the sweep (every operation on the handle assembles its matrix anew).
+struct TaperGradState {
+    DevBuf<double> Z;             // S^-1 on the tile envelope: ldz x npad, ldz = skew * 128 (packed) or npad
+    DevBuf<double> AR;            // npad x r: S^-1 R
+    DevBuf<double> ent;           // 6 x nnz: per stored entry, the weighted partials (grad.hip taper_grad_entry_kernel)
+    DevBuf<double> site;          // GSITE_FIELDS x npad
+    DevBuf<double> gsite;         // 9 x npad
+    DevBuf<double> out;           // 9 p
+    DevBuf<int> tcp, tidx, trow;  // transposed index of the device pattern (built on the host, once)
+    size_t ldz = 0;
+    long long bytes = 0;          // device bytes of the buffers above
+};
+
 cocons_fit::cocons_fit() = default;
 cocons_fit::~cocons_fit() = default;
 
@@ -4368,5 +4383,180 @@ extern "C" int cocons_debug_matern(int n, const double *nu, const double *u, dou
     HIPCHK_AT("cocons_debug_matern", hipGetLastError());
     HIPCHK_AT("cocons_debug_matern", hipMemcpyAsync(out, d + 2 * (size_t)n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK_AT("cocons_debug_matern", hipStreamSynchronize(s));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Analytic gradient of the tapered -2 log-likelihood.  One operation: the objective's assembly and band
+// factorisation with the residuals under the matrix, the log-determinant and quadratic forms (launch_finalize, as the
+// objective), then the selected inverse on the tile envelope with the back-substitution A = L^-T (L^-1 R) in the same
+// sweep (selinv.hip), and the contraction over the stored pattern (grad.hip).
+static int taper_grad_prepare(cocons_fit *f, const char *who)
+{
+    if (f->tgrad) return 0;
+    std::unique_ptr<TaperGradState> G(new TaperGradState());
+    const size_t npad = (size_t)f->npad, nnz = (size_t)f->taper_nnz, n = (size_t)f->n;
+    G->ldz = f->skew > 0 ? (size_t)f->skew * TILE : npad;
+    // transposed index of the device pattern: the lower triangle of the handle's pattern, numbered row by row as
+    // taper_create_ordered filters it; column j's entries in ascending row order
+    std::vector<int> tcp(n + 1, 0), tidx(nnz), trow(nnz);
+    {
+        const std::vector<int> &rp = f->h_trp, &ci = f->h_tci;
+        if (rp.size() != n + 1) return fail(-1, "%s: the handle keeps no host copy of its pattern", who);
+        size_t cnt = 0;
+        for (size_t i = 0; i < n; ++i)
+            for (int w = rp[i] - 1; w < rp[i + 1] - 1; ++w)
+                if (ci[w] - 1 <= (int)i) { ++tcp[ci[w]]; ++cnt; }
+        if (cnt != nnz) return fail(-1, "%s: the host copy of the pattern does not match the device's", who);
+        for (size_t j = 0; j < n; ++j) tcp[j + 1] += tcp[j];
+        std::vector<int> fill(tcp.begin(), tcp.end() - 1);
+        int w2 = 0;
+        for (size_t i = 0; i < n; ++i)
+            for (int w = rp[i] - 1; w < rp[i + 1] - 1; ++w)
+                if (ci[w] - 1 <= (int)i) {
+                    const int t = fill[ci[w] - 1]++;
+                    tidx[t] = w2++; trow[t] = (int)i;
+                }
+    }
+    const size_t zc = G->ldz * npad, ar = npad * (size_t)f->r, en = 6 * nnz, si = (size_t)GSITE_FIELDS * npad, gs = 9 * npad,
+                 ou = (size_t)9 * f->p;
+    HIPCHK_AT(who, G->Z.alloc(zc));
+    HIPCHK_AT(who, G->AR.alloc(ar));
+    HIPCHK_AT(who, G->ent.alloc(en));
+    HIPCHK_AT(who, G->site.alloc(si));
+    HIPCHK_AT(who, G->gsite.alloc(gs));
+    HIPCHK_AT(who, G->out.alloc(ou));
+    HIPCHK_AT(who, G->tcp.alloc(n + 1));
+    HIPCHK_AT(who, G->tidx.alloc(nnz));
+    HIPCHK_AT(who, G->trow.alloc(nnz));
+    HIPCHK_AT(who, hipMemcpyAsync(G->tcp, tcp.data(), (n + 1) * sizeof(int), hipMemcpyHostToDevice, f->stream));
+    HIPCHK_AT(who, hipMemcpyAsync(G->tidx, tidx.data(), nnz * sizeof(int), hipMemcpyHostToDevice, f->stream));
+    HIPCHK_AT(who, hipMemcpyAsync(G->trow, trow.data(), nnz * sizeof(int), hipMemcpyHostToDevice, f->stream));
+    // (the padding rows of A and of the site sums are read by nothing, the envelope tiles of Z are written before they are
+    // read; cleared once all the same, so that no never-written byte is ever a NaN pattern)
+    HIPCHK_AT(who, hipMemsetAsync(G->Z, 0, zc * sizeof(double), f->stream));
+    HIPCHK_AT(who, hipMemsetAsync(G->AR, 0, ar * sizeof(double), f->stream));
+    HIPCHK_AT(who, hipMemsetAsync(G->gsite, 0, gs * sizeof(double), f->stream));
+    HIPCHK_AT(who, hipStreamSynchronize(f->stream));      // the staging vectors go out of scope
+    G->bytes = (long long)((zc + ar + en + si + gs + ou) * sizeof(double) + (n + 1 + 2 * nnz) * sizeof(int));
+    f->tgrad = std::move(G);
+    return 0;
+}
+
+// everything of one operation on the handle's stream (run_op repeats it after a hand-off time-out); hgrad = null stops once
+// Z = S^-1 is complete (cocons_debug_taper_selinv)
+static int taper_grad_enqueue(cocons_fit *f, const double *theta, const double *mean, double *hgrad)
+{
+    const int npad = f->npad, nr = f->r, p = f->p;
+    hipStream_t s = f->stream;
+    TaperGradState *G = f->tgrad.get();
+    f->nrhs_cur = nr;
+    if (int rc = fit_alloc_matrix(f, nr)) return rc;
+    if (int rc = assemble_sigma_taper(f, theta)) return rc;
+    assemble_rhs(f, mean, true, nullptr, 0, 0, npad, true, false);
+    if (int rc = factorize(f, main_view(f), nullptr)) return rc;      // (dag_ok = false: the whole factor stays in dA)
+    launch_finalize(f->dA, f->lda, f->n, npad, nr, f->dout, s, f->skew, npad);
+    HIPCHK(hipMemcpyAsync(f->hout, f->dout, (size_t)(1 + nr * nr) * sizeof(double), hipMemcpyDeviceToHost, s));
+    SelinvArgs sa;
+    memset(&sa, 0, sizeof sa);
+    sa.L = f->dA; sa.ldl = f->lda; sa.Z = G->Z; sa.ldz = G->ldz;
+    sa.skew = f->skew; sa.npad = npad; sa.nt = f->nt;
+    sa.d_hi = f->d_thi; sa.nr = nr; sa.AR = G->AR;
+    launch_selinv(sa, f->taper_hi.empty() ? nullptr : f->taper_hi.data(), f->taper_hi.empty() ? f->nt : f->taper_maxband, s);
+    HIPCHK(hipGetLastError());
+    if (!hgrad) return 0;
+    ThetaVecs tv;
+    make_theta_vecs(theta, p, tv, true);
+    const ModeSel ms = select_mode(theta, p, f->smooth_limits, 0);
+    const int smooth_free = ms.smooth_kind == SMOOTH_LOGISTIC_SQRT && f->smooth_limits[1] != f->smooth_limits[0];
+    launch_grad_site(loc_args(f->n, p, f->dX, f->dlocs, G->site, npad, tv, ms.smooth_kind, f->smooth_limits), G->site, npad,
+                     smooth_free, s);
+    TaperGradArgs g;
+    memset(&g, 0, sizeof g);
+    g.n = f->n; g.npad = npad; g.p = p; g.nnz = f->taper_nnz; g.nr = nr;
+    g.ci = f->d_tci; g.rp = f->d_trp; g.tcp = G->tcp; g.tidx = G->tidx; g.trow = G->trow; g.tapv = f->d_tval;
+    g.Z = G->Z; g.ldz = G->ldz; g.skew = f->skew;
+    g.AR = G->AR; g.coef = (double)nr;
+    g.loc = f->dloc; g.stride = npad; g.site = G->site;
+    g.X = f->dX; g.ldx = f->n;
+    g.nu_fixed = ms.nu_fixed; g.smooth_free = smooth_free;
+    g.ent = G->ent; g.gsite = G->gsite; g.out = G->out;
+    launch_taper_grad(ms.mode, g, s);
+    HIPCHK(hipMemcpyAsync(hgrad, G->out, (size_t)9 * p * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int taper_grad_refuse(cocons_fit *f, const char *who)
+{
+    if (f->taper_nnz <= 0) return fail(-1, "%s: not a taper fit (cocons_neg2loglik_grad_dense serves a dense handle)", who);
+    if (f->coll_kind) return fail(-1, "%s: not available on a sharded handle", who);
+    if (f->r < 1) return fail(-1, "%s: fit has no z", who);
+    return 0;
+}
+
+extern "C" int cocons_neg2loglik_grad_taper(cocons_fit *f, const double *theta, const double *mean, double *sum_logliks,
+                                            double *parts, double *grad_theta, double *grad_quad, double *grad_mean)
+{
+    const char *who = "cocons_neg2loglik_grad_taper";
+    if (!f) return fail(-1, "%s: null fit handle", who);
+    if (!theta || !mean || !sum_logliks || !grad_theta || !grad_mean) return fail(-1, "%s: null argument", who);
+    FIT_ENTER(f);
+    if (int rc = taper_grad_refuse(f, who)) return rc;
+    if (int rc = taper_grad_prepare(f, who)) return rc;
+    const int p = f->p;
+    std::vector<double> hg((size_t)9 * p);
+    const int st = run_op(f, who, [&]() -> int { return taper_grad_enqueue(f, theta, mean, hg.data()); });
+    f->border_clean = -1; f->border_pending = -1;
+    if (st) return st;                  // failing minor: nothing written
+    dense_collect(f, sum_logliks, parts);
+    // device rows: part (log-determinant, quadratic form) x family (std.dev, scale, smooth, nugget); aniso and tilt do not
+    // enter the taper model: exactly zero
+    static const int fam_row[4] = {TH_SD, TH_SCALE, TH_SMOOTH, TH_NUGGET};
+    for (int e = 0; e < 6 * p; ++e) { grad_theta[e] = 0.0; if (grad_quad) grad_quad[e] = 0.0; }
+    for (int fm = 0; fm < 4; ++fm)
+        for (int k = 0; k < p; ++k) {
+            const double ld = hg[(size_t)fm * p + k], qd = hg[(size_t)(4 + fm) * p + k];
+            grad_theta[fam_row[fm] * p + k] = ld + qd;
+            if (grad_quad) grad_quad[fam_row[fm] * p + k] = qd;
+        }
+    memcpy(grad_mean, hg.data() + (size_t)8 * p, (size_t)p * sizeof(double));
+    return 0;
+}
+
+// (diagnostics) (S^-1)_ij at every stored entry of the pattern the handle was created with, in the caller's CSR order
+// (out_nnz: as many doubles as that pattern has entries), by the gradient's selected inverse; bytes_out (may be null): the
+// device bytes the gradient holds on the handle
+extern "C" int cocons_debug_taper_selinv(cocons_fit *f, const double *theta, double *out_nnz, long long *bytes_out)
+{
+    const char *who = "cocons_debug_taper_selinv";
+    if (!f) return fail(-1, "%s: null fit handle", who);
+    if (!theta || !out_nnz) return fail(-1, "%s: null argument", who);
+    FIT_ENTER(f);
+    if (int rc = taper_grad_refuse(f, who)) return rc;
+    if (int rc = taper_grad_prepare(f, who)) return rc;
+    const std::vector<double> zero((size_t)f->p, 0.0);
+    const int st = run_op(f, who, [&]() -> int { return taper_grad_enqueue(f, theta, zero.data(), nullptr); });
+    f->border_clean = -1; f->border_pending = -1;
+    if (st) return st;
+    // the caller's entry w of row o is the entry at the same place of row taper_inv[o] of the handle's pattern
+    const int n = f->n;
+    const size_t full = f->h_tci.size();
+    std::vector<int> ij(2 * full);
+    size_t w = 0;
+    for (int o = 0; o < n; ++o) {
+        const int i = f->taper_inv[o];
+        for (int t = f->h_trp[i] - 1; t < f->h_trp[i + 1] - 1; ++t, ++w) { ij[2 * w] = i; ij[2 * w + 1] = f->h_tci[t] - 1; }
+    }
+    DevBuf<int> dij;
+    DevBuf<double> dv;
+    HIPCHK_AT(who, dij.alloc(2 * full));
+    HIPCHK_AT(who, dv.alloc(full));
+    HIPCHK_AT(who, hipMemcpyAsync(dij, ij.data(), 2 * full * sizeof(int), hipMemcpyHostToDevice, f->stream));
+    launch_selinv_gather(f->tgrad->Z, f->tgrad->ldz, f->skew, f->npad, dij, full, dv, f->stream);
+    HIPCHK_AT(who, hipGetLastError());
+    HIPCHK_AT(who, hipMemcpyAsync(out_nnz, dv, full * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    HIPCHK_AT(who, hipStreamSynchronize(f->stream));
+    if (bytes_out) *bytes_out = f->tgrad->bytes;
     return 0;
 }

@@ -9,6 +9,8 @@
 //   grad_pair_kernel     : W = r Sigma^-1 - A A' contracted with dSigma/d(site predictors) over the 64 x 64 lower tiles
 //   grad_reduce_kernel / grad_xt_kernel : fixed-order sums per site, then X' g and the mean gradient
 //
+//   taper_grad_*_kernel : the taper fit's contraction over its CSR pattern (cocons_neg2loglik_grad_taper; selinv.hip gives S^-1)
+//
 // Every sum has a fixed order (no floating-point atomics): two calls give bit-identical gradients.
 // Compile with -ffp-contract=off (matern_device.hpp).
 #include <hip/hip_runtime.h>
@@ -537,6 +539,163 @@ size_t grad_scratch_doubles(int npad)
 {
     const size_t T = (size_t)npad / GTS, ntile = T * (T + 1) / 2;
     return 2 * ntile * GFAM * GTS + ntile + (size_t)(GFAM + 1) * npad;
+}
+
+// ---------------------------------------------------------------------------
+// Taper fit (cocons_neg2loglik_grad_taper): S = T o C(theta) on a CSR pattern, C = cov_rns_taper (matern_device.hpp
+// taper_value_idx: isotropic, rho = e^(2 eta_scale) with the FULL scale vector).  With Z = S^-1 on the pattern (selinv.hip)
+// and A = S^-1 R the weight of entry (i, j) is W = r Z_ij - sum_c A_ic A_jc; its two terms -- the log-determinant part and
+// the quadratic-form part -- are carried apart.
+//   taper_grad_entry_kernel : one thread per stored (lower) entry: W T times (C, U = P u dM/du, P nu dM/dnu + U / 2), the
+//                             three numbers both sites' partials are made of; off-diagonal entries count twice
+//   taper_grad_site_kernel  : one thread per site: its CSR row (row side), then its column through the transposed index
+//                             (column side), in index order
+//   taper_grad_xt_kernel    : X' g per part and family, and the mean gradient -2 X' A 1
+constexpr int TG_SD = 0, TG_SCALE = 1, TG_SMOOTH = 2, TG_NG = 3, TG_FAM = 4;
+
+// u of the pair (ia = row site, ib = column site) in taper_value_idx's arithmetic: both passes take the same branch
+template <int MODE>
+__device__ __forceinline__ double taper_u(const TaperGradArgs &g, int ia, int ib, double &nu)
+{
+    const double *L = g.loc;
+    const size_t sl = g.stride;
+    const double ax = L[ia], ay = L[sl + ia], bx = L[ib], by = L[sl + ib];
+    const double ri = L[2 * sl + ia], rj = L[2 * sl + ib];
+    nu = (MODE == MODE_GEOM) ? L[10 * sl + ia] * L[10 * sl + ib] : g.nu_fixed;
+    const double global_range = (ri + rj) / 2;
+    const double dx = ax - bx, dy = ay - by;
+    return sqrt(8 * nu) * sqrt(dx * dx + dy * dy) / sqrt(global_range);
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256)
+taper_grad_entry_kernel(TaperGradArgs g)
+{
+    const double eps = 2.220446049250313e-16;
+    const int w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= g.nnz) return;
+    int lo = 0, hi = g.n - 1;                 // largest ii with rp[ii] - 1 <= w (taper_kernel)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (g.rp[mid] - 1 <= w) lo = mid; else hi = mid - 1;
+    }
+    const int ii = lo, jj = g.ci[w] - 1;
+    const double *L = g.loc;
+    const size_t sl = g.stride;
+    double e0 = 0.0, e1 = 0.0, e2 = 0.0;
+    const double t = g.tapv[w];
+    if (ii == jj) {
+        e0 = t * g.site[3 * sl + ii];
+        e1 = t * L[12 * sl + ii];
+    } else {
+        double nu;
+        const double u = taper_u<MODE>(g, ii, jj, nu);
+        if (u <= eps) {                       // coincident: the row site's diagonal value
+            e0 = 2.0 * t * g.site[3 * sl + ii];
+            e1 = 2.0 * t * L[12 * sl + ii];
+        } else if (!(u >= 706.0)) {           // (beyond: the reference's stand-in, derivatives round to 0)
+            double M, Mu, Mn = 0.0;
+            if (MODE == MODE_HALF) { M = exp(-u); Mu = -M; }
+            else if (MODE == MODE_THREEHALF) { const double e = exp(-u); M = (1.0 + u) * e; Mu = -u * e; }
+            else if (MODE == MODE_FIVEHALF) { const double e = exp(-u); M = (1.0 + u + u * u / 3.0) * e; Mu = -(u / 3.0) * (1.0 + u) * e; }
+            else {
+                matern_pair(nu, u, M, Mu);
+                if (g.smooth_free) Mn = matern_dnu(nu, u);
+            }
+            const double ri = L[2 * sl + ii], rj = L[2 * sl + jj];
+            const double P = (2 * sqrt(ri) * sqrt(rj)) / (ri + rj) * L[9 * sl + ii] * L[9 * sl + jj];
+            const double U = P * Mu * u;
+            e0 = 2.0 * t * (P * M);
+            e1 = 2.0 * t * U;
+            if (g.smooth_free) e2 = 2.0 * t * (P * Mn * nu + 0.5 * U);
+        }
+    }
+    const double wl = g.coef * g.Z[band_index(ii, jj, g.ldz, g.skew, g.npad)];
+    double wq = 0.0;
+    for (int c = 0; c < g.nr; ++c) wq -= g.AR[(size_t)ii + (size_t)c * g.npad] * g.AR[(size_t)jj + (size_t)c * g.npad];
+    const size_t nz = (size_t)g.nnz;
+    g.ent[w] = wl * e0; g.ent[nz + w] = wl * e1; g.ent[2 * nz + w] = wl * e2;
+    g.ent[3 * nz + w] = wq * e0; g.ent[4 * nz + w] = wq * e1; g.ent[5 * nz + w] = wq * e2;
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256)
+taper_grad_site_kernel(TaperGradArgs g)
+{
+    const double eps = 2.220446049250313e-16;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= g.n) return;
+    const size_t nz = (size_t)g.nnz, sl = g.stride;
+    const double ri = g.loc[2 * sl + i];
+    double acc[2][TG_FAM] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+    auto side = [&](size_t w, int other) {        // an ordinary off-diagonal entry, seen from site i
+        const double phi = ri / (ri + g.loc[2 * sl + other]);
+        for (int q = 0; q < 2; ++q) {
+            const double e0 = g.ent[(3 * q) * nz + w], e1 = g.ent[(3 * q + 1) * nz + w], e2 = g.ent[(3 * q + 2) * nz + w];
+            acc[q][TG_SD] += 0.5 * e0;
+            acc[q][TG_SCALE] += e0 * (1.0 - 2.0 * phi) - e1 * phi;
+            acc[q][TG_SMOOTH] += e2;
+        }
+    };
+    for (int w = g.rp[i] - 1; w < g.rp[i + 1] - 1; ++w) {          // row side
+        const int j = g.ci[w] - 1;
+        double nu;
+        if (j == i || taper_u<MODE>(g, i, j, nu) <= eps) {
+            for (int q = 0; q < 2; ++q) { acc[q][TG_SD] += g.ent[(3 * q) * nz + w]; acc[q][TG_NG] += g.ent[(3 * q + 1) * nz + w]; }
+        } else side((size_t)w, j);
+    }
+    for (int t = g.tcp[i]; t < g.tcp[i + 1]; ++t) {                 // column side
+        const int row = g.trow[t];
+        double nu;
+        if (row == i || taper_u<MODE>(g, row, i, nu) <= eps) continue;
+        side((size_t)g.tidx[t], row);
+    }
+    const double dl = g.site[2 * sl + i];
+    for (int q = 0; q < 2; ++q) {
+        acc[q][TG_SMOOTH] *= dl;
+        for (int f = 0; f < TG_FAM; ++f) g.gsite[(size_t)(q * TG_FAM + f) * g.npad + i] = acc[q][f];
+    }
+    double s = 0.0;
+    for (int c = 0; c < g.nr; ++c) s += g.AR[(size_t)i + (size_t)c * g.npad];
+    g.gsite[(size_t)(2 * TG_FAM) * g.npad + i] = s;
+}
+
+// out[(q 4 + f) p + k] = sum_i X(i, k) g_qf(i); out[8 p + k] = -2 sum_i X(i, k) rsum(i).  One workgroup per output.
+__global__ void __launch_bounds__(256)
+taper_grad_xt_kernel(TaperGradArgs g)
+{
+    __shared__ double red[256];
+    const int o = blockIdx.x, v = o / g.p, k = o % g.p;
+    const double *gv = g.gsite + (size_t)v * g.npad;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < g.n; i += 256) s = fma(g.X[(size_t)i + (size_t)k * g.ldx], gv[i], s);
+    s = block_sum256(s, red);
+    if (threadIdx.x == 0) g.out[o] = (v == 2 * TG_FAM ? -2.0 : 1.0) * s;
+}
+
+void launch_taper_grad(int mode, const TaperGradArgs &g, hipStream_t s)
+{
+    if (g.nnz <= 0 || g.n <= 0) return;
+    dim3 ge((g.nnz + 255) / 256), gs((g.n + 255) / 256), blk(256);
+    switch (mode) {
+    case MODE_HALF:
+        hipLaunchKernelGGL(taper_grad_entry_kernel<MODE_HALF>, ge, blk, 0, s, g);
+        hipLaunchKernelGGL(taper_grad_site_kernel<MODE_HALF>, gs, blk, 0, s, g);
+        break;
+    case MODE_THREEHALF:
+        hipLaunchKernelGGL(taper_grad_entry_kernel<MODE_THREEHALF>, ge, blk, 0, s, g);
+        hipLaunchKernelGGL(taper_grad_site_kernel<MODE_THREEHALF>, gs, blk, 0, s, g);
+        break;
+    case MODE_FIVEHALF:
+        hipLaunchKernelGGL(taper_grad_entry_kernel<MODE_FIVEHALF>, ge, blk, 0, s, g);
+        hipLaunchKernelGGL(taper_grad_site_kernel<MODE_FIVEHALF>, gs, blk, 0, s, g);
+        break;
+    default:
+        hipLaunchKernelGGL(taper_grad_entry_kernel<MODE_GEOM>, ge, blk, 0, s, g);
+        hipLaunchKernelGGL(taper_grad_site_kernel<MODE_GEOM>, gs, blk, 0, s, g);
+        break;
+    }
+    hipLaunchKernelGGL(taper_grad_xt_kernel, dim3((2 * TG_FAM + 1) * g.p), blk, 0, s, g);
 }
 
 }  // namespace cocons

@@ -323,4 +323,41 @@ void launch_grad_pairs(int mode, const GradArgs &g, hipStream_t s);
 // out[i], out[n + i], out[2 n + i] = M, dM/du, dM/dnu of the gradient's device code
 void launch_matern_grad_points(int n, const double *nu, const double *u, double *out, hipStream_t s);
 
+// ---- analytic gradient of the tapered -2 log-likelihood (selinv.hip, grad.hip) -------------------------------------------
+// Selected inverse on the tile envelope of a taper handle's factor.  L: the factorisation's buffer as it leaves it (leading
+// dimension ldl, the nr rows under the matrix hold (L^-1 R)'); Z: a buffer of the band's shape without rows under it
+// (leading dimension ldz = skew * 128, or npad when skew = 0); both in the layout band_index(., ., ld, skew, npad).
+// d_hi: device copy of the envelope (null: hi[c] = nt).  After launch_selinv Z holds S^-1 on every envelope tile (lower
+// tiles, diagonal tiles in full), AR (npad x nr, column-major) holds S^-1 R, and L is consumed.
+struct SelinvArgs {
+    double *L; size_t ldl;
+    double *Z; size_t ldz;
+    int skew, npad, nt;
+    const int *d_hi;
+    int nr;
+    double *AR;
+};
+// h_hi: host copy of the envelope (null: none); maxband = max_c (hi[c] - c)
+void launch_selinv(const SelinvArgs &a, const int *h_hi, int maxband, hipStream_t s);
+// out[w] = Z(max(i, j), min(i, j)) for the 0-based index pairs ij[2 w], ij[2 w + 1]
+void launch_selinv_gather(const double *Z, size_t ldz, int skew, int npad, const int *ij, size_t count, double *out, hipStream_t s);
+struct TaperGradArgs {
+    int n, npad, p, nnz, nr;
+    const int *ci, *rp;            // the device pattern: lower triangle, 1-based CSR
+    const int *tcp, *tidx, *trow;  // its transposed index: column j's entries tidx[tcp[j] .. tcp[j + 1]) and their rows trow[.]
+    const double *tapv;
+    const double *Z; size_t ldz; int skew;    // S^-1 (launch_selinv)
+    const double *AR;              // S^-1 R, npad x nr
+    double coef;                   // W = coef Z - AR AR'
+    const double *loc; size_t stride;         // loc_params_kernel's SoA
+    const double *site;            // launch_grad_site's SoA
+    const double *X; int ldx;
+    double nu_fixed;
+    int smooth_free;
+    double *ent;                   // 6 nnz: per entry, (log-determinant part, quadratic part) x 3
+    double *gsite;                 // 9 npad: per site, 2 parts x (std.dev, scale, smooth, nugget), then sum_c A(i, c)
+    double *out;                   // 9 p: 2 parts x 4 families x p, then the mean gradient
+};
+void launch_taper_grad(int mode, const TaperGradArgs &g, hipStream_t s);
+
 }  // namespace cocons

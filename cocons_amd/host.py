@@ -470,6 +470,22 @@ class CoconsTaperFit(CoconsFit):
         if not self._h:
             raise _lib.CoconsHipError("cocons_fit_create_taper failed: " + _lib.last_error())
 
+    def neg2loglik_grad_core(self, theta_list):
+        """The value of `neg2loglik_core` on this handle and its analytic gradient (cocons_neg2loglik_grad_taper): returns
+        (value, parts, grad_table, grad_quad, grad_mean) -- the 6 x p table of the whole value in the order std.dev, scale,
+        aniso, tilt, smooth, nugget (aniso and tilt rows zero), the same table for the quadratic forms alone (the
+        log-determinant's part is grad_table - grad_quad), and the mean gradient."""
+        T = theta_table(theta_list)
+        mean = np.ascontiguousarray(np.asarray(theta_list["mean"], dtype=np.float64))
+        val = ctypes.c_double(0.0)
+        parts = np.zeros(1 + self.r)
+        gt = np.zeros((6, self.p))
+        gq = np.zeros((6, self.p))
+        gm = np.zeros(self.p)
+        _lib.check(self._L.cocons_neg2loglik_grad_taper(self._h, _p(T), _p(mean), ctypes.byref(val), _p(parts), _p(gt),
+                                                         _p(gq), _p(gm)),
+                   "cocons_neg2loglik_grad_taper")
+        return val.value, parts, gt, gq, gm
 
     def predict_core(self, theta_list, locs_pred, x_covariates_pred, pred_taper, z_col=0):
         """(stochastic, quadform) of the sparse branch of cocoPredict; pred_taper = (colindices, rowpointers,
@@ -591,6 +607,66 @@ def GetNeg2loglikelihoodTaperProfile(theta, par_pos, ref_taper, locs, x_covariat
         logdet, sum_in = parts[0], float(np.sum(parts[1:]))
         return (r * n * np.log(2 * np.pi) + r * n + r * 2 * logdet + r * n * np.log(sum_in / (r * n))
                 + getPen(n * r, lam, tl, smooth_limits))    # :102-106
+    finally:
+        if own:
+            f.close()
+
+
+def GetNeg2loglikelihoodTaper_grad(theta, par_pos, ref_taper, locs, x_covariates, smooth_limits, z, n, lam, safe=True,
+                                   fit=None):
+    """`GetNeg2loglikelihoodTaper` and its gradient over the optimiser's vector `theta` in one call: (value, gradient).
+    The gradient is that of the tapered -2 log-likelihood (cocons_neg2loglik_grad_taper) plus the penalty's, carried
+    through getModelLists(type="diff").  A failing Cholesky gives (1e6, zeros) under `safe`, RuntimeError otherwise."""
+    tl = getModelLists(theta, par_pos, "diff")
+    f, own = (fit, False) if fit is not None else (CoconsTaperFit(locs, x_covariates, z, smooth_limits, *ref_taper), True)
+    try:
+        try:
+            val, _, gt, _, gm = f.neg2loglik_grad_core(tl)
+        except CholeskyError:
+            if safe:
+                return 1e6, np.zeros(np.asarray(theta).size)
+            raise RuntimeError("Cholesky error")
+        N = n * f.r
+        g = getPen_grad(N, lam, tl, smooth_limits)
+        g["mean"] = g["mean"] + gm
+        for t, k in enumerate(COV_ASPECTS):
+            g[k] = g[k] + gt[t]
+        return val + getPen(N, lam, tl, smooth_limits), getModelLists_grad(g, par_pos)
+    finally:
+        if own:
+            f.close()
+
+
+def GetNeg2loglikelihoodTaperProfile_grad(theta, par_pos, ref_taper, locs, x_covariates, smooth_limits, z, n, lam,
+                                          safe=True, fit=None):
+    """`GetNeg2loglikelihoodTaperProfile` and its gradient over `theta`: (value, gradient).  With Q the sum of the quadratic
+    forms the value is r 2 logdet + r n log(Q / (r n)) + constants, so its gradient is the log-determinant's part of the
+    core's plus r n / Q times the quadratic forms' part (the mean gradient scaled likewise).  std.dev[0] is overwritten
+    with 0 after getModelLists: its table gradient is zero (where std.dev and scale are both free the raw pair still
+    moves scale[0])."""
+    tl = getModelLists(theta, par_pos, "diff")
+    sd = np.array(tl["std.dev"], dtype=np.float64, copy=True)
+    sd[0] = 0.0
+    tl["std.dev"] = sd
+    f, own = (fit, False) if fit is not None else (CoconsTaperFit(locs, x_covariates, z, smooth_limits, *ref_taper), True)
+    try:
+        try:
+            _, parts, gt, gq, gm = f.neg2loglik_grad_core(tl)
+        except CholeskyError:
+            if safe:
+                return 1e6, np.zeros(np.asarray(theta).size)
+            raise RuntimeError("Cholesky error")
+        r = f.r
+        logdet, sum_in = parts[0], float(np.sum(parts[1:]))
+        val = (r * n * np.log(2 * np.pi) + r * n + r * 2 * logdet + r * n * np.log(sum_in / (r * n))
+               + getPen(n * r, lam, tl, smooth_limits))
+        w = r * n / sum_in
+        g = getPen_grad(n * r, lam, tl, smooth_limits)
+        g["mean"] = g["mean"] + w * gm
+        for t, k in enumerate(COV_ASPECTS):
+            g[k] = g[k] + (gt[t] - gq[t]) + w * gq[t]
+        g["std.dev"][0] = 0.0
+        return val, getModelLists_grad(g, par_pos)
     finally:
         if own:
             f.close()

@@ -258,6 +258,45 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
     .cocons.getPen(n * r, lambda, theta_list, smooth.limits)
 }
 
+# value, parts and analytic gradient of the tapered -2 log-likelihood core on a taper handle (no penalty):
+# list(v = c(sum_logliks, logdet_half, quad_1 .. quad_r), table, quad = 6 x p gradients of the whole value and of the
+# quadratic forms alone, mean); NULL after a failing Cholesky under safe
+.cocons.hip.neg2loglik.taper.grad <- function(fit, theta_list, safe = TRUE) {
+  res <- .cocons.hip.result(.Call(`_cocons_hip_neg2loglik_taper_grad`, fit, theta_list[-1], theta_list$mean), safe)
+  if (is.null(res)) return(NULL)
+  list(v = res[[1]], table = res[[2]], quad = res[[3]], mean = res[[4]])
+}
+
+# gradients of GetNeg2loglikelihoodTaper / GetNeg2loglikelihoodTaperProfile over theta (the optimiser's vector), with the
+# bodies' signatures: what cocoOptim's sparse branches can pass as `gr` (INTEGRATION.md); zeros after a failing Cholesky
+# under safe (where the value functions return 1e6)
+.cocons.hip.GetNeg2loglikelihoodTaperGrad <- function(theta, par.pos, fit, smooth.limits, z, n, lambda, safe = TRUE) {
+  theta_list <- getModelLists(theta = theta, par.pos = par.pos, type = "diff")
+  g <- .cocons.hip.neg2loglik.taper.grad(fit, theta_list, safe)
+  if (is.null(g)) return(rep(0, length(theta)))
+  G <- .cocons.hip.getPen.grad(n * dim(z)[2], lambda, theta_list, smooth.limits)
+  G$mean <- G$mean + g$mean
+  aspects <- c("std.dev", "scale", "aniso", "tilt", "smooth", "nugget")
+  for (t in seq_along(aspects)) G[[aspects[t]]] <- G[[aspects[t]]] + g$table[t, ]
+  .cocons.hip.diff.grad(G, par.pos)
+}
+
+# the Profile form is r 2 logdet + r n log(Q / (r n)) + constants, Q the sum of the quadratic forms: its gradient is the
+# log-determinant's share plus r n / Q times the quadratic forms' share; std.dev[1] is overwritten with 0, so its entry is 0
+.cocons.hip.GetNeg2loglikelihoodTaperProfileGrad <- function(theta, par.pos, fit, smooth.limits, z, n, lambda, safe = TRUE) {
+  theta_list <- getModelLists(theta = theta, par.pos = par.pos, type = "diff")
+  theta_list$std.dev[1] <- 0
+  g <- .cocons.hip.neg2loglik.taper.grad(fit, theta_list, safe)
+  if (is.null(g)) return(rep(0, length(theta)))
+  r <- dim(z)[2]; w <- r * n / sum(g$v[-(1:2)])
+  G <- .cocons.hip.getPen.grad(n * r, lambda, theta_list, smooth.limits)
+  G$mean <- G$mean + w * g$mean
+  aspects <- c("std.dev", "scale", "aniso", "tilt", "smooth", "nugget")
+  for (t in seq_along(aspects)) G[[aspects[t]]] <- G[[aspects[t]]] + (g$table[t, ] - g$quad[t, ]) + w * g$quad[t, ]
+  G$std.dev[1] <- 0
+  .cocons.hip.diff.grad(G, par.pos)
+}
+
 # sparse branch of cocoPredict (R/predict.R:216-283): the lines from cov_rns_taper to rowSums(pred_taper * t(inv_cov)) become
 #   kr <- .cocons.hip.predict.taper(fit, theta_list, newlocs, X_pred_std, pred_taper)   # pred_taper: the spam object of :229-231
 #   stochastic_part <- kr[, 1];  uncertainty_some <- uncertainty_some - kr[, 2]

@@ -506,6 +506,36 @@ SEXP _cocons_hip_neg2loglik_reml_grad(SEXP fitp, SEXP theta, SEXP rank)
     return out;
 }
 
+/* taper handle: value, parts and analytic gradient (cocons_neg2loglik_grad_taper):
+ * list(status, list(c(sum_logliks, logdet_half, quad_1 .. quad_r), grad_table 6 x p, grad_quad 6 x p, grad_mean p)); grad_quad
+ * is the quadratic forms' share of grad_table (GetNeg2loglikelihoodTaperProfile's gradient combines the two) */
+SEXP _cocons_hip_neg2loglik_taper_grad(SEXP fitp, SEXP theta, SEXP mean)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), r = fit_r(fitp);
+    double T[6 * COCONS_P_MAX], G[6 * COCONS_P_MAX] = {0}, Q[6 * COCONS_P_MAX] = {0};
+    theta_table(theta, p, T);
+    if (XLENGTH(mean) != p) Rf_error("theta$mean must have length %d", p);
+    SEXP v = PROTECT(Rf_allocVector(REALSXP, 2 + r));
+    SEXP gt = PROTECT(Rf_allocMatrix(REALSXP, 6, p));
+    SEXP gq = PROTECT(Rf_allocMatrix(REALSXP, 6, p));
+    SEXP gm = PROTECT(Rf_allocVector(REALSXP, p));
+    for (int k = 0; k < 2 + r; ++k) REAL(v)[k] = NA_REAL;
+    for (int k = 0; k < p; ++k) REAL(gm)[k] = 0.0;
+    int rc = cocons_neg2loglik_grad_taper(f, T, REAL(mean), REAL(v), REAL(v) + 1, G, Q, REAL(gm));
+    hip_check(rc, "GetNeg2loglikelihoodTaper (gradient)");
+    for (int t = 0; t < 6; ++t)         /* (a failing minor writes nothing: the tables stay zero) */
+        for (int k = 0; k < p; ++k) { REAL(gt)[t + 6 * k] = G[t * p + k]; REAL(gq)[t + 6 * k] = Q[t * p + k]; }
+    SEXP res = PROTECT(Rf_allocVector(VECSXP, 4));
+    SET_VECTOR_ELT(res, 0, v);
+    SET_VECTOR_ELT(res, 1, gt);
+    SET_VECTOR_ELT(res, 2, gq);
+    SET_VECTOR_ELT(res, 3, gm);
+    SEXP out = status_value(rc, res);
+    UNPROTECT(5);
+    return out;
+}
+
 /* dense kriging core (R/predict.R:136-183): list(status, cbind(stochastic, quadform)) */
 SEXP _cocons_hip_predict(SEXP fitp, SEXP theta, SEXP mean, SEXP z_col, SEXP locs_pred, SEXP X_pred)
 {
@@ -756,6 +786,7 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_neg2loglik_reml", (DL_FUNC)&_cocons_hip_neg2loglik_reml, 3},
     {"_cocons_hip_neg2loglik_profile_grad", (DL_FUNC)&_cocons_hip_neg2loglik_profile_grad, 2},
     {"_cocons_hip_neg2loglik_reml_grad", (DL_FUNC)&_cocons_hip_neg2loglik_reml_grad, 3},
+    {"_cocons_hip_neg2loglik_taper_grad", (DL_FUNC)&_cocons_hip_neg2loglik_taper_grad, 3},
     {"_cocons_hip_predict", (DL_FUNC)&_cocons_hip_predict, 6},
     {"_cocons_hip_predict_taper", (DL_FUNC)&_cocons_hip_predict_taper, 9},
     {"_cocons_hip_krige_prepare", (DL_FUNC)&_cocons_hip_krige_prepare, 5},

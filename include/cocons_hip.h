@@ -214,6 +214,21 @@ int cocons_neg2loglik_profile_grad(cocons_fit *fit, const double *theta,
 int cocons_neg2loglik_reml_grad(cocons_fit *fit, const double *theta, int rank,
                                 double *sum_logliks, double *parts, double *grad_theta);
 
+/* The tapered -2 log-likelihood of a taper handle (what cocons_neg2loglik_dense returns on it) and its analytic gradient
+ * in one call.  S = T o C(theta) on the handle's pattern; with A = S^-1 R and W = r S^-1 - A A'
+ *   d f / d theta_a = sum over the pattern of W_ij T_ij dC_ij / d theta_a,      d f / d mean = -2 X' A 1.
+ * S^-1 is formed only where the pattern can be non-zero: a selected inverse on the tile envelope of the band factor, kept in
+ * a second buffer of the band's shape (allocated by the first call, kept on the handle, freed with it).
+ * sum_logliks and parts (may be NULL; 1 + r doubles) as cocons_neg2loglik_dense gives them on the same handle; grad_theta
+ * the 6 x p table of the whole value in theta's layout (the aniso and tilt rows are exactly zero: they do not enter the
+ * taper model); grad_quad (may be NULL) the same table for the quadratic forms alone, so that the log-determinant's part is
+ * grad_theta - grad_quad (GetNeg2loglikelihoodTaperProfile's gradient is a combination of the two); grad_mean p doubles.
+ * Fixed-order sums: repeated calls agree bit for bit.  0, the failing minor k > 0, or < 0 with a message that starts with
+ * the entry's name; outputs are written on 0 only.  Refused (-1) on a dense handle, a sharded handle, a handle without z. */
+int cocons_neg2loglik_grad_taper(cocons_fit *fit, const double *theta, const double *mean,
+                                 double *sum_logliks, double *parts,
+                                 double *grad_theta, double *grad_quad, double *grad_mean);
+
 /* Dense kriging core: replaces R/predict.R:136-183
  *   observed_cov <- cov_rns(...); cov_pred <- cov_rns_pred(...);
  *   inv_cov <- solve(observed_cov, t(cov_pred)); crossprod(resid, inv_cov);

@@ -31,6 +31,11 @@ int cocons_debug_matern_grad(int n, const double *nu, const double *u, double *o
  * second buffer, bytes of the gradient's scratch, the leading dimension the objective's matrix uses }.              */
 int cocons_debug_fit_memory(struct cocons_fit *fit, long long *out4);
 
+/* Diagnostics of cocons_neg2loglik_grad_taper: (S(theta)^-1)_ij at every stored entry of the pattern the taper handle was
+ * created with, in the caller's CSR order (out_nnz: one double per entry of that pattern), by the gradient's selected
+ * inverse; bytes_out (may be NULL): the device bytes the gradient holds on the handle.  0, a failing minor k > 0, or < 0. */
+int cocons_debug_taper_selinv(struct cocons_fit *fit, const double *theta, double *out_nnz, long long *bytes_out);
+
 /* Schedule switches of the factorisation, settable at run time (the library reads the COCONS_* environment variables
  * of the same meaning once per process; DESIGN.md section 6 lists them): "engine", "engine_pair", "panel_fused", "panel_split",
  * "potrf_follow", "upd_waves", "w8_max_tiles", "dag", "dag_min_tiles", "dag_lead" / "dag_lead2" / "dag_lead3", "dag_xcc_quota",
