@@ -26,7 +26,10 @@ constexpr int TH_SD_ = 0, TH_SCALE_ = 1, TH_NG_ = 5;
 // ---------------------------------------------------------------------------
 // 2^(1-nu)/Gamma(nu) u^nu K_nu(u) and its u-derivative -2^(1-nu)/Gamma(nu) u^nu K_{nu-1}(u), 0 < u < 706, nu > 0.
 // Temme's series (u <= 2) or Steed's CF2 (u > 2) give K_mu, K_{mu+1} with mu = nu - round(nu); the forward recurrence
-// up to order nu keeps the order below it (matern_bessel's scheme, with the neighbouring order kept).
+// up to order nu keeps the order below it (matern_bessel's scheme, with the neighbouring order kept).  nu < 1/2 (n = 0) needs
+// K_{nu-1} = K_{1-mu}: both schemes give it directly, as the neighbour K_{(-mu)+1} of K_{-mu} = K_mu (Temme's sum with q in the
+// place of p; the continued fraction's ratio at -mu).  K_{mu+1} - (2 mu / u) K_mu is the same number, but its two terms agree
+// to leading order at small u and leave a relative error of eps (2 / u)^(2 nu): 3e-6 at nu -> 1/2, u = 1e-10.
 __device__ __noinline__ void matern_pair(double nu, double u, double &M, double &Mu)
 {
     const double tol = 2.220446049250313e-16;
@@ -53,7 +56,7 @@ __device__ __noinline__ void matern_pair(double nu, double u, double &M, double 
         e = exp(e);
         double pp = 0.5 * e / gampl, q = 0.5 / (e * gammi), c = 1.0;
         d = x2 * x2;
-        double sum1 = pp;
+        double sum1 = (n == 0) ? q : pp;
         for (int i = 1; i < 500; ++i) {
             const double di = (double)i;
             ff = (di * ff + pp + q) / ((di - mu) * (di + mu));
@@ -62,7 +65,7 @@ __device__ __noinline__ void matern_pair(double nu, double u, double &M, double 
             q /= (di + mu);
             const double del = c * ff;
             sum += del;
-            sum1 += c * (pp - di * ff);
+            sum1 += c * (((n == 0) ? q : pp) - di * ff);
             if (fabs(del) < fabs(sum) * tol) break;
         }
         kmu = sum;
@@ -88,11 +91,11 @@ __device__ __noinline__ void matern_pair(double nu, double u, double &M, double 
             if (fabs(qd) < fabs(S) * tol) break;
         }
         kmu = sqrt(pi / (2.0 * u)) / S;
-        kmu1 = kmu * (0.5 + mu + u + (mu2 - 0.25) * f) / u;
+        kmu1 = kmu * (0.5 + ((n == 0) ? -mu : mu) + u + (mu2 - 0.25) * f) / u;
         scaled = true;
     }
-    // K_{nu-1}, K_nu: n >= 1 keeps the order below nu from the recurrence; n = 0 takes K_{mu-1} = K_{mu+1} - (2 mu / u) K_mu
-    double klo = kmu1 - (2.0 * mu / u) * kmu, khi = kmu;
+    // K_{nu-1}, K_nu: n >= 1 keeps the order below nu from the recurrence; n = 0 has K_{1-mu} = K_{mu-1} in kmu1
+    double klo = kmu1, khi = kmu;
     if (n >= 1) { klo = kmu; khi = kmu1; }
     for (int k = 1; k < n; ++k) {
         const double next = (2.0 * (mu + k) / u) * khi + klo;

@@ -154,6 +154,68 @@ def test_odd_sizes(n):
     assert _inf(g - rg) <= 1e-7 * _inf(rg)
 
 
+def _general_problem(n, p, r, seed):
+    """any n and p: the design matrix of test_widest_design_matrix (an intercept and p - 1 random covariates in every
+    aspect, smaller effects for the widest designs), a nugget covariate effect, r realisations"""
+    rng = np.random.default_rng(seed)
+    locs = rng.uniform(0, 1, size=(n, 2))
+    X = np.column_stack([np.ones(n)] + [rng.standard_normal(n) * 0.3 for _ in range(p - 1)])
+    sm = 0.03 if p > 8 else 0.1
+    th = OrderedDict()
+    th["mean"] = rng.standard_normal(p) * 0.1
+    th["std.dev"] = np.r_[0.1, rng.standard_normal(p - 1) * sm]
+    th["scale"] = np.r_[np.log(0.3), rng.standard_normal(p - 1) * sm]
+    th["aniso"] = np.r_[0.0, rng.standard_normal(p - 1) * sm]
+    th["tilt"] = np.r_[0.1, rng.standard_normal(p - 1) * sm]
+    th["smooth"] = np.r_[0.2, rng.standard_normal(p - 1) * sm]
+    th["nugget"] = np.r_[np.log(0.05), rng.standard_normal(p - 1) * sm]
+    z = rng.standard_normal((n, r))
+    return locs, X, th, z
+
+
+def _zero_matrix_theta(th):
+    """std.dev and nugget intercepts at -Inf: Sigma = 0, the first minor fails at every n"""
+    bad = OrderedDict((k, np.array(v, float)) for k, v in th.items())
+    bad["std.dev"][0] = -np.inf
+    bad["nugget"][0] = -np.inf
+    return bad
+
+
+SHAPES = [(300, 1, 1), (300, 2, 3), (300, 7, 1), (300, 32, 3), (300, 32, 1)] + \
+         [(n, 1, 3) for n in (1, 2, 63, 64, 65, 127, 129)] + [(n, 5, r) for n, r in ((63, 1), (64, 3), (65, 1), (127, 3), (129, 1))]
+
+
+@pytest.mark.parametrize("n,p,r", SHAPES)
+def test_shapes_against_reference(n, p, r):
+    """p from 1 to COCONS_P_MAX = 32, n on both sides of the 64-wide pair tiles and the 128-wide factorisation tiles down to
+    1, r = 1 and 3: value, gradient table and mean gradient against the numpy statement at the tolerances of
+    test_against_reference; a failing first minor returns its index and leaves every output untouched; the next call on
+    the handle gives the first call's bits."""
+    from cocons_amd import host, workloads as wl
+    from cocons_amd.host import _p, theta_table
+    locs, X, th, z = _general_problem(n, p, r, 7000 + 40 * n + p)
+    fit = _fit(locs, X, z)
+    try:
+        val, parts, gt, gm = fit.neg2loglik_grad_core(th)
+        T = theta_table(_zero_matrix_theta(th))
+        mean = np.ascontiguousarray(th["mean"])
+        v7 = ctypes.c_double(7.0)
+        p7, g7, m7 = np.full(1 + r, 7.0), np.full(6 * p, 7.0), np.full(p, 7.0)
+        rc = fit._L.cocons_neg2loglik_grad_dense(fit._h, _p(T), _p(mean), ctypes.byref(v7), _p(p7), _p(g7), _p(m7))
+        assert rc == 1
+        assert v7.value == 7.0 and np.all(p7 == 7.0) and np.all(g7 == 7.0) and np.all(m7 == 7.0)
+        again = fit.neg2loglik_grad_core(th)
+    finally:
+        fit.close()
+    assert again[0] == val and all(np.array_equal(a, b) for a, b in zip(again[1:], (parts, gt, gm)))
+    assert gt.shape == (6, p) and gm.shape == (p,) and parts.shape == (1 + r,)
+    f, rgt, rgm = GR.neg2loglik_grad(host.theta_table(th), th["mean"], locs, X, z, wl.SMOOTH_LIMITS)
+    g, rg = np.concatenate([gt.ravel(), gm]), np.concatenate([rgt.ravel(), rgm])
+    print("n=%d p=%d r=%d value %.2e gradient %.2e" % (n, p, r, abs(val - f) / abs(f), _inf(g - rg) / _inf(rg)))
+    assert abs(val - f) <= 1e-10 * abs(f)
+    assert _inf(g - rg) <= 1e-7 * _inf(rg), (_inf(g - rg), _inf(rg))
+
+
 def test_failing_minor_then_success_and_krige_untouched():
     from cocons_amd import CholeskyError, _lib
     from cocons_amd.host import _p, theta_table

@@ -14,6 +14,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import grad_profile_reference as GPR  # noqa: E402
+from test_gpu_grad import SHAPES, _general_problem, _zero_matrix_theta  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -154,6 +155,58 @@ def test_fixed_smoothness(obj, nu):
 @pytest.mark.parametrize("obj", OBJECTIVES)
 def test_odd_sizes(obj, n):
     _check_reference(obj, n, 1, 3)
+
+
+@pytest.mark.parametrize("n,p,r", SHAPES)
+@pytest.mark.parametrize("obj", OBJECTIVES)
+def test_shapes_against_reference(obj, n, p, r):
+    """The shapes of tests/test_gpu_grad.py::test_shapes_against_reference (p from 1 to 32, n from 1 across the tile edges,
+    r = 1 and 3); Profile with q = max(1, p // 2) columns of x_betas.  Tolerances of test_against_reference; a failing first
+    minor returns its index and leaves every output untouched; the next call gives the first call's bits."""
+    from cocons_amd import CoconsFit, workloads as wl
+    from cocons_amd.host import _p, theta_table
+    locs, X, th, z = _general_problem(n, p, r, 7000 + 40 * n + p)
+    z = z + 0.4 * X[:, [p - 1]] - 0.2
+    q = max(1, p // 2) if obj == "pml" else p
+    xb = np.ascontiguousarray(X[:, :q])
+
+    def grad(t):
+        return fit.neg2loglik_profile_grad_core(t) if obj == "pml" else fit.neg2loglik_reml_grad_core(t, p)
+
+    fit = CoconsFit(locs, X, z, wl.SMOOTH_LIMITS, x_betas=xb)
+    try:
+        val, parts, gt = grad(th)
+        T = theta_table(_zero_matrix_theta(th))
+        v7 = ctypes.c_double(7.0)
+        p7, g7 = np.full(2 + r + q, 7.0), np.full(6 * p, 7.0)
+        if obj == "pml":
+            rc = fit._L.cocons_neg2loglik_profile_grad(fit._h, _p(T), ctypes.byref(v7), _p(p7), _p(g7))
+        else:
+            rc = fit._L.cocons_neg2loglik_reml_grad(fit._h, _p(T), p, ctypes.byref(v7), _p(p7), _p(g7))
+        assert rc == 1
+        assert v7.value == 7.0 and np.all(p7 == 7.0) and np.all(g7 == 7.0)
+        again = grad(th)
+    finally:
+        fit.close()
+    assert again[0] == val and np.array_equal(again[1], parts) and np.array_equal(again[2], gt)
+    assert gt.shape == (6, p) and parts.shape == (2 + r + q,)
+    if obj == "pml":
+        f, rgt, beta, quad = GPR.profile_grad(th, locs, X, z, xb, wl.SMOOTH_LIMITS)
+    else:
+        f, rgt, beta, quad = GPR.reml_grad(th, locs, X, z, wl.SMOOTH_LIMITS)
+    if obj == "reml" and n == p:
+        # no residual degree of freedom: log det Sigma + log det W = 2 log |X| and the quadratic forms vanish, so the
+        # objective is constant in theta (r log x^2 at n = p = 1) and its gradient zero.  Relative tolerances have nothing
+        # to refer to: the same fractions of what cancels instead -- r |log det Sigma| + r |log det W| in the value, r Sigma^-1
+        # dSigma = O(r) per table entry in the gradient
+        print(obj, n, p, r, "constant objective: value", val, f, "gradient", _inf(gt))
+        assert _inf(rgt) <= 1e-12 * r
+        assert abs(val - f) <= 1e-10 * 2 * r * (abs(parts[0]) + abs(parts[1]) + 1.0)
+        assert _inf(gt) <= 1e-7 * r, gt
+        return
+    print(obj, n, p, r, "value", abs(val - f) / abs(f), "gradient", _inf(gt - rgt) / _inf(rgt))
+    assert abs(val - f) <= 1e-10 * abs(f)
+    assert _inf(gt - rgt) <= 1e-7 * _inf(rgt), (_inf(gt - rgt), _inf(rgt))
 
 
 def _fit_memory(fit):

@@ -94,6 +94,40 @@ def test_value_and_gradient_vs_reference(n, r):
     assert abs(ident) <= 1e-9 * r * n
 
 
+@pytest.mark.parametrize("p,r", [(1, 1), (2, 3), (7, 1), (32, 3)])
+def test_design_widths_against_reference(p, r):
+    """p from 1 to COCONS_P_MAX = 32 covariates in every aspect (the design matrix of test_widest_design_matrix), r = 1 and 3,
+    n = 300 with taper range 0.25: grad_theta, grad_quad and grad_mean against the numpy statement at the tolerances of
+    test_value_and_gradient_vs_reference; a failing first minor leaves every output untouched and the next call gives the
+    first call's bits."""
+    from cocons_amd import workloads as wl
+    from cocons_amd.host import _p, theta_table
+    from test_gpu_grad import _general_problem, _zero_matrix_theta
+    n = 300
+    locs, X, th, z = _general_problem(n, p, r, 7100 + p)
+    ref_taper = _taper_pattern(locs, 0.25)
+    fit = _taper_fit(locs, X, z, ref_taper)
+    try:
+        v, parts, gt, gq, gm = fit.neg2loglik_grad_core(th)
+        bad = _zero_matrix_theta(th)
+        val = ctypes.c_double(-7.0)
+        outs = [np.full(k, -7.0) for k in (1 + r, 6 * p, 6 * p, p)]
+        rc = fit._L.cocons_neg2loglik_grad_taper(fit._h, _p(theta_table(bad)), _p(np.ascontiguousarray(bad["mean"])),
+                                                 ctypes.byref(val), *[_p(o) for o in outs])
+        assert rc > 0 and val.value == -7.0 and all(np.all(o == -7.0) for o in outs)
+        again = fit.neg2loglik_grad_core(th)
+    finally:
+        fit.close()
+    assert again[0] == v and all(np.array_equal(a, b) for a, b in zip(again[1:], (parts, gt, gq, gm)))
+    assert gt.shape == (6, p) and gq.shape == (6, p) and gm.shape == (p,)
+    assert np.all(gt[2] == 0) and np.all(gt[3] == 0) and np.all(gq[2] == 0) and np.all(gq[3] == 0)
+    f, rparts, rl, rq, rm = GT.neg2loglik_taper_grad(fit_table(th), th["mean"], locs, X, z, wl.SMOOTH_LIMITS, ref_taper)
+    assert abs(v - f) <= 1e-9 * abs(f)
+    for name, got, want in (("grad_theta", gt, rl + rq), ("grad_quad", gq, rq), ("grad_mean", gm, rm)):
+        print("p=%d r=%d %s: %.3e of %.3e" % (p, r, name, _inf(got - want), _inf(want)))
+        assert _inf(got - want) <= 1e-7 * _inf(want), (name, _inf(got - want), _inf(want))
+
+
 def fit_table(th):
     from cocons_amd.host import theta_table
     return theta_table(th)
