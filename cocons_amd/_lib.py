@@ -104,6 +104,7 @@ DIAG_SIGNATURES = {
     "cocons_debug_matern_grad": (c_int, [c_int, c_dp, c_dp, c_dp]),
     "cocons_debug_sigma_inverse": (c_int, [c_vp, c_dp, c_dp]),
     "cocons_debug_fit_memory": (c_int, [c_vp, ctypes.POINTER(ctypes.c_longlong)]),
+    "cocons_debug_rhs_layout": (c_int, [c_vp, c_int, ctypes.POINTER(c_int)]),
     "cocons_debug_taper_selinv": (c_int, [c_vp, c_dp, c_dp, ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_debug_tune": (c_int, [ctypes.c_char_p, c_int]),
     "cocons_debug_dag_replay": (c_int, [c_vp, c_dp, c_dp, c_int, c_dp]),

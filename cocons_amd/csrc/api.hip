@@ -520,9 +520,12 @@ static int fit_check(cocons_fit *f)
     if (int rc__ = fit_check(f)) return rc__;                          \
     std::lock_guard<std::recursive_mutex> op_guard__((f)->op_mu)
 
+// rows under the matrix that an operation with rhs_rows right-hand sides reserves: whole tiles
+static int rhs_rows_cap(int rhs_rows) { return round_up(rhs_rows > 0 ? rhs_rows : 1, TILE); }
+
 static int fit_alloc_matrix(cocons_fit *f, int rhs_rows)
 {
-    int cap = round_up(rhs_rows > 0 ? rhs_rows : 1, TILE);
+    int cap = rhs_rows_cap(rhs_rows);
     f->rhs_act = cap;        // a buffer grown by an earlier predict call must not slow later evaluations
     f->border_clean = -1; f->border_pending = -1;      // every user of the rows under the matrix comes through here
     if (f->dA && cap <= f->rhs_cap) return 0;
@@ -1153,6 +1156,36 @@ static FactorView main_view(cocons_fit *f)
     v.A = f->dA; v.lda = f->lda; v.nt = f->nt; v.mt = f->nt + f->rhs_act / TILE;
     v.hi = f->taper_hi.empty() ? nullptr : f->taper_hi.data();
     v.skew = f->skew;
+    return v;
+}
+
+// Where the nrhs right-hand-side rows of an evaluation sit -- the ONE place that decides it (enqueue_eval_impl, the replay
+// diagnostic and cocons_debug_rhs_layout all ask here):
+//   slots   they ride in the slot rows of the matrix's last tile (the handle keeps nslot >= nrhs of them): no rows under it;
+//   border  otherwise in tile_rows = ceil(nrhs / 128) tile rows under the matrix (what fit_alloc_matrix makes of rhs_act),
+//           and trim says that the last 64 of those rows hold nothing: no kernel of the factorisation touches them.
+struct RhsLayout {
+    bool slots;
+    int tile_rows;
+    int trim;
+};
+
+static RhsLayout rhs_layout(const cocons_fit *f, int nrhs)
+{
+    RhsLayout l;
+    l.slots = f->nslot >= nrhs && f->nslot > 0;
+    const int act = rhs_rows_cap(nrhs);
+    l.tile_rows = l.slots ? 0 : act / TILE;
+    l.trim = (!l.slots && act - nrhs >= 64) ? 1 : 0;
+    return l;
+}
+
+// the view of the matrix an evaluation with this layout factors (after fit_alloc_matrix(f, nrhs))
+static FactorView rhs_view(cocons_fit *f, const RhsLayout &l)
+{
+    FactorView v = main_view(f);
+    v.mt = v.nt + l.tile_rows;
+    v.trim = l.trim;
     return v;
 }
 
@@ -1887,10 +1920,9 @@ static int enqueue_eval_impl(cocons_fit *f, const double *theta, const double *m
     // the engine becomes resident while the (short) right-hand-side kernel runs: not earlier -- a second
     // queue with a resident kernel cuts the workgroup dispatch rate of every other launch to a quarter
     // (tools/diag/occupancy_probe.hip), which costs the 12,000-workgroup assembly 6 % -- and not later, see engine_start
-    const bool slots = f->nslot >= nrhs && f->nslot > 0;      // the right-hand sides ride in the matrix's last tile
-    FactorView fv = main_view(f);
-    if (slots) fv.mt = fv.nt;                         // no rows under the matrix
-    else fv.trim = (f->rhs_act - nrhs >= 64) ? 1 : 0; // at most 64 of the 128 rows under the matrix are in use
+    const RhsLayout lay = rhs_layout(f, nrhs);
+    const bool slots = lay.slots;
+    FactorView fv = rhs_view(f, lay);
     fv.dag_ok = true;                                 // (the reductions below read the factor from both buffers)
     if (engine_wanted(f, fv))
         if (int rc = engine_start(f, fv)) return rc;
@@ -1904,6 +1936,15 @@ static int enqueue_eval_impl(cocons_fit *f, const double *theta, const double *m
                           hipMemcpyDeviceToHost, f->stream));
     if (stage_events) hipEventRecord(f->ev[3], f->stream);
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// (diagnostics, no HIP call) where an operation with r + nxb right-hand sides puts them on this handle: rhs_layout itself
+extern "C" int cocons_debug_rhs_layout(cocons_fit *f, int nxb, int *out5)
+{
+    if (!f || !out5 || nxb < 0) return fail(-1, "cocons_debug_rhs_layout: bad argument");
+    const RhsLayout l = rhs_layout(f, f->r + nxb);
+    out5[0] = f->pad0; out5[1] = f->nslot; out5[2] = l.slots ? 1 : 0; out5[3] = l.tile_rows; out5[4] = l.trim;
     return 0;
 }
 
@@ -4021,9 +4062,9 @@ extern "C" int cocons_debug_dag_replay(cocons_fit *f, const double *theta, const
     tun().engine = engine_saved;
     if (st) return st;
     const int nrhs = f->r;
-    const bool slots = f->nslot >= nrhs && f->nslot > 0;
-    FactorView fv = main_view(f);
-    if (slots) fv.mt = fv.nt; else fv.trim = (f->rhs_act - nrhs >= 64) ? 1 : 0;
+    const RhsLayout lay = rhs_layout(f, nrhs);
+    const bool slots = lay.slots;
+    FactorView fv = rhs_view(f, lay);
     fv.dag_ok = true;
     if (!(tun().dag != 0 && !fv.hi && !fv.skew && fv.nt > 4)) return fail(-1, "cocons_debug_dag_replay: the DAG schedule does not apply to this fit");
     if (int rc = flags_reset(f, fv.nt)) return rc;

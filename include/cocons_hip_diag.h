@@ -31,6 +31,13 @@ int cocons_debug_matern_grad(int n, const double *nu, const double *u, double *o
  * second buffer, bytes of the gradient's scratch, the leading dimension the objective's matrix uses }.              */
 int cocons_debug_fit_memory(struct cocons_fit *fit, long long *out4);
 
+/* Where an operation with r + nxb right-hand sides (nxb = 0: the dense objective, q: Profile, p: REML) carries them through the
+ * factorisation on this handle, from the function every evaluation asks: out5 = { pad0 (placeholder observations in front),
+ * nslot (slot rows the handle keeps in the matrix's last tile), 1 if these right-hand sides ride in the slots, tile rows of
+ * 128 under the matrix it factors (0 with slots), trim (1: the last 64 of those rows hold nothing) }.  Host only: no HIP
+ * call.  0, or -1 on a null argument or nxb < 0.                                                                          */
+int cocons_debug_rhs_layout(struct cocons_fit *fit, int nxb, int *out5);
+
 /* Diagnostics of cocons_neg2loglik_grad_taper: (S(theta)^-1)_ij at every stored entry of the pattern the taper handle was
  * created with, in the caller's CSR order (out_nnz: one double per entry of that pattern), by the gradient's selected
  * inverse; bytes_out (may be NULL): the device bytes the gradient holds on the handle.  0, a failing minor k > 0, or < 0. */

@@ -81,6 +81,9 @@ def test_bad_arguments_return_error_codes_without_touching_the_gpu():
     assert not lib.cocons_fit_create(0, 1, 1, 0, p, p, p, None, p, 0)
     assert lib.cocons_neg2loglik_dense(None, p, p, p, None) < 0
     assert "null fit handle" in _lib.last_error()
+    out5 = (ctypes.c_int * 5)()
+    assert lib.cocons_debug_rhs_layout(None, 0, out5) == -1           # (a diagnostic that makes no HIP call at all)
+    assert _lib.last_error().startswith("cocons_debug_rhs_layout:")
 
 
 def test_glue_covers_the_reference_call_surface():

@@ -268,7 +268,15 @@ def _free_port():
     return p
 
 
-def _shard_worker(rank, world, port, g, out_dir, predict_first=False, group=None):
+def _shard_z(n, r):
+    """r = 2: the two columns every sharded test here uses; more: one synthetic column per seed"""
+    from cocons_amd import workloads as wl
+    if r == 2:
+        return np.column_stack([wl.synthetic_z(n), wl.synthetic_z(n, seed=5)])
+    return np.column_stack([wl.synthetic_z(n, seed=k) for k in range(r)])
+
+
+def _shard_worker(rank, world, port, g, out_dir, predict_first=False, group=None, r=2):
     sys.path.insert(0, ROOT)
     if group is not None:
         os.environ["COCONS_SHARD_GROUP"] = str(group)      # read once, when the library is first used
@@ -283,7 +291,7 @@ def _shard_worker(rank, world, port, g, out_dir, predict_first=False, group=None
     X = wl.design_from_locs(locs)["std.covs"]
     th = wl.theta_full()
     th["mean"] = np.array([0.1, -0.2, 0.05])
-    z = np.column_stack([wl.synthetic_z(g * g), wl.synthetic_z(g * g, seed=5)])
+    z = _shard_z(g * g, r)
     fit = ShardedFit(locs, X, z, wl.SMOOTH_LIMITS, device=0)     # every rank on the one GPU of the box
     if predict_first:
         # grows the handle's border (leading dimension) before the sharded evaluation: the packed panels
@@ -297,30 +305,35 @@ def _shard_worker(rank, world, port, g, out_dir, predict_first=False, group=None
     dist.destroy_process_group()
 
 
+_SHARD_CASES = [(2, 40, False, None, 2), (3, 50, False, None, 2), (4, 15, False, None, 2), (2, 40, True, None, 2),
+                (2, 100, False, None, 2), (2, 40, False, 1, 2), (3, 50, False, 2, 2), (4, 50, False, 3, 2),
+                (2, 28, False, None, 70)]
+
+
 @pytest.mark.shared_gpu
-@pytest.mark.parametrize("world,g,predict_first,group", [(2, 40, False, None), (3, 50, False, None), (4, 15, False, None),
-                                                         (2, 40, True, None), (2, 100, False, None),
-                                                         (2, 40, False, 1), (3, 50, False, 2), (4, 50, False, 3)])
-def test_native_sharded_evaluation_shared_gpu(tmp_path, world, g, predict_first, group):
+@pytest.mark.parametrize("world,g,predict_first,group,r", _SHARD_CASES,
+                         ids=["-".join(str(v) for v in c[:4]) + ("" if c[4] == 2 else "-r%d" % c[4]) for c in _SHARD_CASES])
+def test_native_sharded_evaluation_shared_gpu(tmp_path, world, g, predict_first, group, r):
     """The production sharded path -- the schedule inside the HIP library (sharded_eval: panel ownership,
     look-ahead, communication stream, double-buffered exchange, final all-reduce) -- with `world` ranks
     sharing this box's single GPU.  RCCL refuses several ranks on one device, so the library's
     broadcast / all-reduce hooks are served by gloo through host memory; everything else is the code the
     RCCL build runs.  Must reproduce the single-GPU value.  (2, 100) is BASELINE config C3 at its full
     size n = 10 000 in sharded form.  `group` = panels per ownership group (None: the library's default, 4;
-    1: the cyclic deal of rounds 1-2)."""
+    1: the cyclic deal of rounds 1-2).  r = 70 at n = 784: an ensemble -- 70 right-hand sides, more than the trimmed
+    half tile, ride through the sharded schedule's packed panels."""
     import torch.multiprocessing as mp
     import cocons_amd as ca
     from cocons_amd import workloads as wl
-    mp.spawn(_shard_worker, args=(world, _free_port(), g, str(tmp_path), predict_first, group), nprocs=world, join=True)
-    res = [np.load(os.path.join(str(tmp_path), "rank%d.npy" % r)) for r in range(world)]
-    for r in res[1:]:
-        assert np.array_equal(r, res[0])
+    mp.spawn(_shard_worker, args=(world, _free_port(), g, str(tmp_path), predict_first, group, r), nprocs=world, join=True)
+    res = [np.load(os.path.join(str(tmp_path), "rank%d.npy" % k)) for k in range(world)]
+    for other in res[1:]:
+        assert np.array_equal(other, res[0])
     locs = wl.grid_locs(g)
     X = wl.design_from_locs(locs)["std.covs"]
     th = wl.theta_full()
     th["mean"] = np.array([0.1, -0.2, 0.05])
-    z = np.column_stack([wl.synthetic_z(g * g), wl.synthetic_z(g * g, seed=5)])
+    z = _shard_z(g * g, r)
     val, parts = ca.CoconsFit(locs, X, z, wl.SMOOTH_LIMITS).neg2loglik_core(th)
     assert abs(res[0][0] - val) < 1e-10 * abs(val)
     assert np.allclose(res[0][1:], parts, rtol=1e-10, atol=0)
