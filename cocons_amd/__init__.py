@@ -31,6 +31,7 @@ from .host import (  # noqa: F401
     cov_rns_taper,
     cov_rns_taper_pred,
     getBetas_profile,
+    getFisher_dense,
     getHessian_dense,
     getModelLists,
     getModelLists_grad,

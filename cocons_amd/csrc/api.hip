@@ -4152,6 +4152,27 @@ static int grad_refuse(cocons_fit *f, const char *who)
     return 0;
 }
 
+// the site factors beside loc_params_kernel's SoA (launch_grad_site) and everything the pair partials read, into g (the rest
+// of it zero); the pair mode
+static int grad_pair_args(cocons_fit *f, const double *theta, GradArgs &g)
+{
+    const int npad = f->npad, p = f->p;
+    GradState *G = f->grad.get();
+    ThetaVecs tv;
+    make_theta_vecs(theta, p, tv);
+    const ModeSel ms = select_mode(theta, p, f->smooth_limits, 0);
+    const int smooth_free = ms.smooth_kind == SMOOTH_LOGISTIC_SQRT && f->smooth_limits[1] != f->smooth_limits[0];
+    launch_grad_site(loc_args(f->n, p, f->dX, f->dlocs, G->site, npad, tv, ms.smooth_kind, f->smooth_limits), G->site, npad,
+                     smooth_free, f->stream);
+    memset(&g, 0, sizeof g);
+    g.n = f->n; g.pad0 = f->pad0; g.npad = npad; g.p = p;
+    g.S = f->dA; g.lds = f->lda;
+    g.loc = f->dloc; g.stride = npad; g.site = G->site;
+    g.X = f->dX; g.ldx = f->n;
+    g.gr = ms.gr; g.nu_fixed = ms.nu_fixed; g.smooth_free = smooth_free;
+    return ms.mode;
+}
+
 // the end of every gradient operation: -Sigma^-1 into the leading square (the unit rows, now L^-T, start rt rows under the
 // matrix), then -- with hgrad -- the site factors and the contraction of W = coef Sigma^-1 - LR LR' (LR: npad x ncol) with
 // dSigma/dtheta; the 7 p results (6 x p table, then the dense gradient's mean row) go to hgrad
@@ -4163,25 +4184,14 @@ static int grad_contract(cocons_fit *f, const double *theta, int rt, const doubl
     launch_grad_fill(f->dA, f->lda, 0, npad, npad, -1, s);
     launch_grad_syrk(f->dA, f->lda, npad, npad + rt, s);
     if (!hgrad) return 0;
-    ThetaVecs tv;
-    make_theta_vecs(theta, p, tv);
-    const ModeSel ms = select_mode(theta, p, f->smooth_limits, 0);
-    const int smooth_free = ms.smooth_kind == SMOOTH_LOGISTIC_SQRT && f->smooth_limits[1] != f->smooth_limits[0];
-    launch_grad_site(loc_args(f->n, p, f->dX, f->dlocs, G->site, npad, tv, ms.smooth_kind, f->smooth_limits), G->site, npad,
-                     smooth_free, s);
     GradArgs g;
-    memset(&g, 0, sizeof g);
-    g.n = f->n; g.pad0 = f->pad0; g.npad = npad; g.p = p;
-    g.S = f->dA; g.lds = f->lda;
+    const int mode = grad_pair_args(f, theta, g);
     g.AR = LR; g.ldar = npad; g.nr = ncol; g.coef = coef;
-    g.loc = f->dloc; g.stride = npad; g.site = G->site;
-    g.X = f->dX; g.ldx = f->n;
-    g.gr = ms.gr; g.nu_fixed = ms.nu_fixed; g.smooth_free = smooth_free;
     const size_t T = (size_t)npad / 64, ntile = T * (T + 1) / 2;
     g.part_row = G->scratch; g.part_col = g.part_row + ntile * 6 * 64; g.part_glob = g.part_col + ntile * 6 * 64;
     g.gsite = g.part_glob + ntile;
     g.out = G->out;
-    launch_grad_pairs(ms.mode, g, s);
+    launch_grad_pairs(mode, g, s);
     HIPCHK(hipMemcpyAsync(hgrad, G->out, (size_t)7 * p * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipGetLastError());
     return 0;
@@ -4375,6 +4385,82 @@ extern "C" int cocons_debug_sigma_inverse(cocons_fit *f, const double *theta, do
     HIPCHK_AT(who, hipStreamSynchronize(f->stream));
     for (size_t j = 0; j < n; ++j)                  // the square holds -Sigma^-1 below its diagonal, zeros above
         for (size_t i = 0; i < n; ++i) out[i + j * n] = i >= j ? -out[i + j * n] : 0.0;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Expected (Fisher) information of the dense model.  The gradient's bordered factorisation leaves -Sigma^-1 in
+// the leading square (grad_enqueue, full = false); everything else lives in buffers of this call: one tall buffer of ndir + 2
+// blocks of npad rows -- Sigma^-1 in full, the direction matrices Sigma_a, and the products, each of which lands in the block
+// the product before it has consumed --, the site weights and the traces' per-tile partial sums.
+struct FisherCall {
+    DevBuf<double> tall, dirs, w, part, sxpart, sx, out;
+    int ndir = 0;
+    size_t ldt = 0;
+};
+
+static int fisher_enqueue(cocons_fit *f, const double *theta, FisherCall &c, double *hinfo, double *hmean)
+{
+    const int npad = f->npad, p = f->p, ndir = c.ndir;
+    hipStream_t s = f->stream;
+    const std::vector<double> zero((size_t)p, 0.0);
+    if (int rc = grad_enqueue(f, theta, zero.data(), false, nullptr)) return rc;
+    double *Tb = c.tall;
+    launch_fisher_mirror(Tb, c.ldt, 0, f->dA, f->lda, 0, npad, 1, -1.0, s);
+    GradArgs g;
+    const int mode = grad_pair_args(f, theta, g);
+    launch_fisher_dirs(mode, g, ndir, c.dirs, c.w, Tb + npad, c.ldt, (size_t)npad, s);
+    HIPCHK(launch_fisher_products(Tb, c.ldt, npad, ndir, s));
+    launch_fisher_trace(Tb + 2 * (size_t)npad, c.ldt, (size_t)npad, npad, ndir, 0.5 * f->r, c.part, c.out, s);
+    HIPCHK(hipMemcpyAsync(hinfo, c.out, (size_t)ndir * ndir * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (hmean) {
+        double *dmean = c.out + (size_t)ndir * ndir;
+        launch_fisher_mean(Tb, c.ldt, f->n, f->pad0, npad, p, f->dX, f->n, (double)f->r, c.sxpart, c.sx, dmean, s);
+        HIPCHK(hipMemcpyAsync(hmean, dmean, (size_t)p * p * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int cocons_fisher_dense(cocons_fit *f, const double *theta, int ndir, const double *dirs, double *info,
+                                   double *info_mean)
+{
+    const char *who = "cocons_fisher_dense";
+    if (!f) return fail(-1, "%s: null fit handle", who);
+    if (!theta || !dirs || !info) return fail(-1, "%s: null argument", who);
+    if (ndir < 1 || ndir > 7 * COCONS_P_MAX) return fail(-1, "%s: ndir = %d is outside [1, %d]", who, ndir, 7 * COCONS_P_MAX);
+    FIT_ENTER(f);
+    if (int rc = grad_refuse(f, who)) return rc;
+    if (f->r < 1) return fail(-1, "%s: fit has no z", who);
+    const int npad = f->npad, p = f->p;
+    const size_t nd = (size_t)ndir * 6 * p;
+    for (size_t e = 0; e < nd; ++e)
+        if (!std::isfinite(dirs[e])) return fail(-1, "%s: direction %d has a non-finite entry", who, (int)(e / ((size_t)6 * p)));
+    FisherCall c;
+    c.ndir = ndir;
+    c.ldt = (size_t)(ndir + 2) * npad;
+    if (c.ldt * 64 * sizeof(double) > 0xffffffffull)       // (the product kernel's 32-bit byte offsets inside a tile)
+        return fail(-1, "%s: %d directions of order %d are beyond the product kernel's addressing", who, ndir, npad);
+    if (int rc = grad_prepare(f, who, f->r)) return rc;
+    const size_t counts[7] = {c.ldt * npad, nd, (size_t)ndir * 6 * npad, fisher_trace_scratch_doubles(npad, ndir),
+                              grad_sigma_r_scratch_doubles(npad, p), (size_t)npad * p, (size_t)ndir * ndir + (size_t)p * p};
+    DevBuf<double> *bufs[7] = {&c.tall, &c.dirs, &c.w, &c.part, &c.sxpart, &c.sx, &c.out};
+    size_t bytes = 0;
+    for (size_t k : counts) bytes += k * sizeof(double);
+    std::vector<double> hinfo((size_t)ndir * ndir), hmean((size_t)p * p);
+    StreamDrain drain{f->stream, false};       // (declared behind the buffers: the stream is idle before they are freed)
+    for (int k = 0; k < 7; ++k)
+        if (hipError_t e = bufs[k]->alloc(counts[k])) {
+            (void)hipGetLastError();
+            return fail(-100 - (int)e, "%s: the device cannot hold the %zu bytes of this call (%d + 2 matrices of order %d): %s",
+                        who, bytes, ndir, npad, hipGetErrorString(e));
+        }
+    HIPCHK_AT(who, upload_canon(c.dirs, dirs, nd, f->stream));
+    GradLayout layout(f, f->r);
+    const int st = run_op(f, who, [&]() -> int { return fisher_enqueue(f, theta, c, hinfo.data(), info_mean ? hmean.data() : nullptr); });
+    if (st) return st;                  // failing minor: nothing written
+    memcpy(info, hinfo.data(), hinfo.size() * sizeof(double));
+    if (info_mean) memcpy(info_mean, hmean.data(), hmean.size() * sizeof(double));
     return 0;
 }
 

@@ -9,6 +9,9 @@
 //   grad_pair_kernel     : W = r Sigma^-1 - A A' contracted with dSigma/d(site predictors) over the 64 x 64 lower tiles
 //   grad_reduce_kernel / grad_xt_kernel : fixed-order sums per site, then X' g and the mean gradient
 //
+//   fisher_*_kernel, dsigma_dirs_kernel : the expected information (cocons_fisher_dense): direction matrices from the same pair
+//                          partials, Sigma^-1 in full, the traces of the products
+//
 //   taper_grad_*_kernel : the taper fit's contraction over its CSR pattern (cocons_neg2loglik_grad_taper; selinv.hip gives S^-1)
 //
 // Every sum has a fixed order (no floating-point atomics): two calls give bit-identical gradients.
@@ -542,6 +545,236 @@ size_t grad_scratch_doubles(int npad)
 {
     const size_t T = (size_t)npad / GTS, ntile = T * (T + 1) / 2;
     return 2 * ntile * GFAM * GTS + ntile + (size_t)(GFAM + 1) * npad;
+}
+
+// ---------------------------------------------------------------------------
+// Expected (Fisher) information of the dense model (cocons_fisher_dense):
+//     I[a, b] = (r / 2) tr(Sigma^-1 Sigma_a Sigma^-1 Sigma_b),   Sigma_a = sum_{t,k} v_a[t, k] dSigma / dtheta[t, k].
+//   fisher_weight_kernel : per direction and family, the site weights w_a[f][i] = c_f sum_k X(i, k) v_a[f, k]
+//   dsigma_dirs_kernel   : the lower tiles of every Sigma_a from ONE evaluation of pair_partials per pair
+//   fisher_mirror_kernel : a lower triangle mirrored into a full symmetric matrix (Sigma_a in place; Sigma^-1 from the
+//                          gradient's -Sigma^-1, the sign folded in)
+//   (the products Sigma_a Sigma^-1 run on the trailing-update kernel, launch_fisher_products)
+//   fisher_trace_kernel / fisher_trace_sum_kernel : sum_ij G_a(i, j) G_b(j, i) per 64 x 64 tile, the transposed tile through
+//                          LDS; then the tiles' partial sums in a fixed order
+//   fisher_sx_kernel / fisher_xtsx_kernel : Sigma^-1 X and r X' (Sigma^-1 X), the mean block
+// The matrices live in ONE tall buffer of npad-row blocks with a common leading dimension: that is the panel shape the
+// trailing-update kernel multiplies row tiles of.
+__global__ void __launch_bounds__(256)
+fisher_weight_kernel(int n, int pad0, int npad, int p, const double *X, int ldx, const double *dirs, double *w)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, a = blockIdx.y;
+    if (i >= npad) return;
+    const bool in = i >= pad0 && i < n;
+    const double *v = dirs + (size_t)a * GFAM * p;
+    for (int f = 0; f < GFAM; ++f) {
+        double s = 0.0;
+        if (in)
+            for (int k = (f == TH_SCALE_ ? 1 : 0); k < p; ++k) s = fma(X[(size_t)i + (size_t)k * ldx], v[f * p + k], s);
+        w[((size_t)a * GFAM + f) * npad + i] = (f == TH_SCALE_ ? 2.0 : 1.0) * s;
+    }
+}
+
+// One workgroup per 64 x 64 lower tile, lane = row, each wave 16 columns (as grad_pair_kernel).  Entry (r, c), r >= c, of
+// direction a goes to D[a dstride + r + c ldd]: every entry of the lower tiles is written, the padding's with zeros.
+template <int MODE>
+__global__ void __launch_bounds__(256)
+dsigma_dirs_kernel(GradArgs g, int ndir, const double *dirs, const double *w, double *D, size_t ldd, size_t dstride)
+{
+    const int bi = blockIdx.x, bj = blockIdx.y;
+    if (bi < bj) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = bi * GTS + lane;
+    const bool rin = r >= g.pad0 && r < g.n;
+    for (int cc = 0; cc < GTS / 4; ++cc) {
+        const int c = bj * GTS + wave * (GTS / 4) + cc;
+        const bool cin = c >= g.pad0 && c < g.n;
+        const bool live = rin && cin && r >= c;
+        double da[GFAM] = {0, 0, 0, 0, 0, 0}, db[GFAM] = {0, 0, 0, 0, 0, 0}, dg = 0.0;
+        if (live) {
+            if (r == c) {                                   // the diagonal: exp(eta_sd) + nugget
+                da[TH_SD_] = g.site[3 * g.stride + r];
+                da[TH_NG_] = g.loc[12 * g.stride + r];
+            } else pair_partials<MODE>(g, c, r, da, db, dg);
+        }
+        if (r < c) continue;
+        for (int a = 0; a < ndir; ++a) {
+            double v = 0.0;
+            if (live) {
+                const double *wa = w + (size_t)a * GFAM * g.npad;
+                for (int f = 0; f < GFAM; ++f) v += da[f] * wa[(size_t)f * g.npad + c] + db[f] * wa[(size_t)f * g.npad + r];
+                v += dg * dirs[(size_t)a * GFAM * g.p + TH_SCALE_ * g.p];
+            }
+            D[(size_t)a * dstride + (size_t)r + (size_t)c * ldd] = v;
+        }
+    }
+}
+
+// Tile pair (bi, bj), bi >= bj, of matrix z: dst(bi, bj) = sign * the lower tile of src (its entries r >= c), dst(bj, bi)
+// its transpose through LDS.  dst == src (sign = 1) mirrors in place: a workgroup touches its own two tiles only.
+__global__ void __launch_bounds__(256)
+fisher_mirror_kernel(double *dst, size_t ldd, size_t dz, const double *src, size_t lds, size_t sz, double sign)
+{
+    const int bi = blockIdx.x, bj = blockIdx.y;
+    if (bi < bj) return;
+    __shared__ double t[GTS][GTS + 1];
+    dst += (size_t)blockIdx.z * dz;
+    src += (size_t)blockIdx.z * sz;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int cc = 0; cc < GTS / 4; ++cc) {
+        const int cl = wave * (GTS / 4) + cc;
+        const int r = bi * GTS + lane, c = bj * GTS + cl;
+        double v = 0.0;
+        if (r >= c) {
+            v = sign * src[(size_t)r + (size_t)c * lds];
+            dst[(size_t)r + (size_t)c * ldd] = v;
+        }
+        t[cl][lane] = v;
+    }
+    __syncthreads();
+    for (int cc = 0; cc < GTS / 4; ++cc) {
+        const int cl = wave * (GTS / 4) + cc;
+        const int r = bj * GTS + lane, c = bi * GTS + cl;
+        if (r < c) dst[(size_t)r + (size_t)c * ldd] = t[lane][cl];
+    }
+}
+
+// Workgroup (bi, bj, a): part[((a ndir + b) T + bj) T + bi] = sum over the tile of G_a(i, j) G_b(j, i) for every b >= a.
+// The tile of G_a stays in registers; tile (bj, bi) of each G_b goes through LDS so that both reads are coalesced.
+__global__ void __launch_bounds__(256)
+fisher_trace_kernel(const double *G, size_t ld, size_t dstride, int ndir, double *part)
+{
+    __shared__ double t[GTS][GTS + 1];
+    __shared__ double red[4];
+    const int bi = blockIdx.x, bj = blockIdx.y, a = blockIdx.z, T = gridDim.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const double *Ga = G + (size_t)a * dstride;
+    double mine[GTS / 4];
+    for (int cc = 0; cc < GTS / 4; ++cc)
+        mine[cc] = Ga[(size_t)(bi * GTS + lane) + (size_t)(bj * GTS + wave * (GTS / 4) + cc) * ld];
+    for (int b = a; b < ndir; ++b) {
+        const double *Gb = G + (size_t)b * dstride;
+        __syncthreads();
+        for (int cc = 0; cc < GTS / 4; ++cc) {
+            const int cl = wave * (GTS / 4) + cc;
+            t[cl][lane] = Gb[(size_t)(bj * GTS + lane) + (size_t)(bi * GTS + cl) * ld];
+        }
+        __syncthreads();
+        double s = 0.0;
+        for (int cc = 0; cc < GTS / 4; ++cc) s += mine[cc] * t[lane][wave * (GTS / 4) + cc];
+        s = wave_sum(s);
+        if (lane == 0) red[wave] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) part[(((size_t)a * ndir + b) * T + bj) * T + bi] = ((red[0] + red[1]) + red[2]) + red[3];
+    }
+}
+
+// info[a, b] = info[b, a] = coef * (the tiles' partial sums, in a fixed order).  One workgroup per pair a <= b.
+__global__ void __launch_bounds__(256)
+fisher_trace_sum_kernel(const double *part, size_t ntile, int ndir, double coef, double *info)
+{
+    __shared__ double red[256];
+    const int a = blockIdx.x / ndir, b = blockIdx.x % ndir;
+    if (a > b) return;
+    const double *pp = part + ((size_t)a * ndir + b) * ntile;
+    double s = 0.0;
+    for (size_t e = threadIdx.x; e < ntile; e += 256) s += pp[e];
+    s = block_sum256(s, red);
+    if (threadIdx.x == 0) {
+        info[(size_t)a * ndir + b] = coef * s;
+        info[(size_t)b * ndir + a] = coef * s;
+    }
+}
+
+// part[(chunk p + c) npad + i] = sum_{k in chunk, a caller's site} S(i, k) X(k, c): S the full symmetric Sigma^-1
+// (grad_sigma_r_sum_kernel adds the chunks in order)
+__global__ void __launch_bounds__(64)
+fisher_sx_kernel(const double *S, size_t lds, int n, int pad0, int npad, int p, const double *X, int ldx, double *part)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    const int chunk = (npad + GRAD_KSPLIT - 1) / GRAD_KSPLIT;
+    const int k0 = max(pad0, (int)blockIdx.y * chunk), k1 = min(n, ((int)blockIdx.y + 1) * chunk);
+    for (int c = 0; c < p; ++c) {
+        double s = 0.0;
+        for (int k = k0; k < k1; ++k) s = fma(S[(size_t)i + (size_t)k * lds], X[(size_t)k + (size_t)c * ldx], s);
+        part[((size_t)blockIdx.y * p + c) * npad + i] = s;
+    }
+}
+
+// out[k p + l] = out[l p + k] = coef sum_i X(i, k) SX(i, l), k <= l.  One workgroup per output.
+__global__ void __launch_bounds__(256)
+fisher_xtsx_kernel(int n, int pad0, int npad, int p, const double *X, int ldx, const double *SX, double coef, double *out)
+{
+    __shared__ double red[256];
+    const int k = blockIdx.x / p, l = blockIdx.x % p;
+    if (k > l) return;
+    double s = 0.0;
+    for (int i = pad0 + threadIdx.x; i < n; i += 256) s = fma(X[(size_t)i + (size_t)k * ldx], SX[(size_t)i + (size_t)l * npad], s);
+    s = block_sum256(s, red);
+    if (threadIdx.x == 0) {
+        out[k * p + l] = coef * s;
+        out[l * p + k] = coef * s;
+    }
+}
+
+void launch_fisher_mirror(double *dst, size_t ldd, size_t dz, const double *src, size_t lds, size_t sz, int npad, int count,
+                          double sign, hipStream_t s)
+{
+    const int T = npad / GTS;
+    hipLaunchKernelGGL(fisher_mirror_kernel, dim3(T, T, count), dim3(256), 0, s, dst, ldd, dz, src, lds, sz, sign);
+}
+
+void launch_fisher_dirs(int mode, const GradArgs &g, int ndir, const double *dirs, double *w, double *D, size_t ldd,
+                        size_t dstride, hipStream_t s)
+{
+    const int T = g.npad / GTS;
+    dim3 grid(T, T), blk(256);
+    hipLaunchKernelGGL(fisher_weight_kernel, dim3((g.npad + 255) / 256, ndir), blk, 0, s, g.n, g.pad0, g.npad, g.p, g.X, g.ldx,
+                       dirs, w);
+    switch (mode) {
+    case MODE_HALF: hipLaunchKernelGGL(dsigma_dirs_kernel<MODE_HALF>, grid, blk, 0, s, g, ndir, dirs, w, D, ldd, dstride); break;
+    case MODE_THREEHALF: hipLaunchKernelGGL(dsigma_dirs_kernel<MODE_THREEHALF>, grid, blk, 0, s, g, ndir, dirs, w, D, ldd, dstride); break;
+    case MODE_FIVEHALF: hipLaunchKernelGGL(dsigma_dirs_kernel<MODE_FIVEHALF>, grid, blk, 0, s, g, ndir, dirs, w, D, ldd, dstride); break;
+    default: hipLaunchKernelGGL(dsigma_dirs_kernel<MODE_GEOM>, grid, blk, 0, s, g, ndir, dirs, w, D, ldd, dstride); break;
+    }
+    launch_fisher_mirror(D, ldd, dstride, D, ldd, dstride, g.npad, ndir, 1.0, s);
+}
+
+// Block a + 2 of the tall buffer Tb (blocks of npad rows, leading dimension ldt) = -Sigma_a Sigma^-1 = -(Sigma^-1 Sigma_a)',
+// with Sigma^-1 in block 0 and Sigma_a in block a + 1, from the last direction down: a product lands in the block the one
+// before it has consumed (block ndir + 1 is the spare).  The trailing-update kernel forms C(I, J) -= sum_k P(I, k) P(J, k)
+// for row tiles of ONE panel buffer: I runs over the rows of Sigma_a, J over those of Sigma^-1, FISHER_KP columns a launch.
+constexpr int FISHER_KP = 512;
+hipError_t launch_fisher_products(double *Tb, size_t ldt, int npad, int ndir, hipStream_t s)
+{
+    const int nt = npad / TILE;
+    const size_t row = (size_t)npad * sizeof(double), pitch = ldt * sizeof(double);
+    hipError_t e = hipMemset2DAsync(Tb + (size_t)(ndir + 1) * npad, pitch, 0, row, npad, s);
+    for (int a = ndir - 1; a >= 0 && e == hipSuccess; --a) {
+        for (int k0 = 0; k0 < npad; k0 += FISHER_KP)
+            launch_update_from(Tb + npad, ldt, Tb + (size_t)k0 * ldt, ldt, min(FISHER_KP, npad - k0), (a + 1) * nt, (a + 2) * nt, 0,
+                               nt, false, s, 1, 1, 0);
+        if (a > 0) e = hipMemset2DAsync(Tb + (size_t)(a + 1) * npad, pitch, 0, row, npad, s);
+    }
+    return e;
+}
+
+size_t fisher_trace_scratch_doubles(int npad, int ndir) { return (size_t)ndir * ndir * (npad / GTS) * (npad / GTS); }
+
+void launch_fisher_trace(const double *G, size_t ld, size_t dstride, int npad, int ndir, double coef, double *part, double *info,
+                         hipStream_t s)
+{
+    const int T = npad / GTS;
+    hipLaunchKernelGGL(fisher_trace_kernel, dim3(T, T, ndir), dim3(256), 0, s, G, ld, dstride, ndir, part);
+    hipLaunchKernelGGL(fisher_trace_sum_kernel, dim3(ndir * ndir), dim3(256), 0, s, part, (size_t)T * T, ndir, coef, info);
+}
+
+void launch_fisher_mean(const double *S, size_t lds, int n, int pad0, int npad, int p, const double *X, int ldx, double coef,
+                        double *part, double *SX, double *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(fisher_sx_kernel, dim3(npad / 64, GRAD_KSPLIT), dim3(64), 0, s, S, lds, n, pad0, npad, p, X, ldx, part);
+    hipLaunchKernelGGL(grad_sigma_r_sum_kernel, dim3((npad + 255) / 256), dim3(256), 0, s, part, npad, p, SX);
+    hipLaunchKernelGGL(fisher_xtsx_kernel, dim3(p * p), dim3(256), 0, s, n, pad0, npad, p, X, ldx, SX, coef, out);
 }
 
 // ---------------------------------------------------------------------------

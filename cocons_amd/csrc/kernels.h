@@ -323,6 +323,26 @@ void launch_grad_pairs(int mode, const GradArgs &g, hipStream_t s);
 // out[i], out[n + i], out[2 n + i] = M, dM/du, dM/dnu of the gradient's device code
 void launch_matern_grad_points(int n, const double *nu, const double *u, double *out, hipStream_t s);
 
+// ---- expected (Fisher) information of the dense model (grad.hip) ---------------------------------------------
+// Matrices are blocks of npad rows in one tall buffer with a common leading dimension (the trailing-update kernel's panel shape).
+// tile pairs of `count` matrices (dz / sz elements apart): dst = sign * (the lower triangle of src, mirrored); dst may be src
+void launch_fisher_mirror(double *dst, size_t ldd, size_t dz, const double *src, size_t lds, size_t sz, int npad, int count,
+                          double sign, hipStream_t s);
+// Sigma_a = sum_tk dirs[a][t, k] dSigma/dtheta[t, k] for the ndir directions (device, ndir x 6 p in theta's table layout), in
+// full, at D + a dstride; g: the gradient's site and pair arguments (loc, site, X, gr, nu_fixed, smooth_free); w: ndir x 6 x npad
+void launch_fisher_dirs(int mode, const GradArgs &g, int ndir, const double *dirs, double *w, double *D, size_t ldd,
+                        size_t dstride, hipStream_t s);
+// block a + 2 of Tb = -(Sigma^-1 Sigma_a)' from Sigma^-1 in block 0 and Sigma_a in block a + 1 (ndir + 2 blocks; the
+// directions' blocks are consumed)
+hipError_t launch_fisher_products(double *Tb, size_t ldt, int npad, int ndir, hipStream_t s);
+// info[a, b] = coef sum_ij G_a(i, j) G_b(j, i) (ndir x ndir, symmetric to the bit), G_a at G + a dstride
+size_t fisher_trace_scratch_doubles(int npad, int ndir);
+void launch_fisher_trace(const double *G, size_t ld, size_t dstride, int npad, int ndir, double coef, double *part, double *info,
+                         hipStream_t s);
+// out (p x p) = coef X' S X over the caller's sites, S symmetric in full; part: grad_sigma_r_scratch_doubles(npad, p), SX: npad x p
+void launch_fisher_mean(const double *S, size_t lds, int n, int pad0, int npad, int p, const double *X, int ldx, double coef,
+                        double *part, double *SX, double *out, hipStream_t s);
+
 // ---- analytic gradient of the tapered -2 log-likelihood (selinv.hip, grad.hip) -------------------------------------------
 // Selected inverse on the tile envelope of a taper handle's factor.  L: the factorisation's buffer as it leaves it (leading
 // dimension ldl, the nr rows under the matrix hold (L^-1 R)'); Z: a buffer of the band's shape without rows under it

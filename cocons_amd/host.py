@@ -307,6 +307,18 @@ class CoconsFit:
                    "cocons_neg2loglik_grad_dense")
         return val.value, parts, gt, gm
 
+    def fisher_core(self, theta_list, dirs):
+        """Expected information of the dense model at `theta_list` (cocons_fisher_dense).  `dirs`: ndir directions in
+        table space, ndir x 6 x p (or ndir x 6p) in the order std.dev, scale, aniso, tilt, smooth, nugget.  Returns
+        (info ndir x ndir = (r / 2) tr(Sigma^-1 Sigma_a Sigma^-1 Sigma_b), info_mean p x p = r X' Sigma^-1 X)."""
+        T = theta_table(theta_list)
+        D = np.ascontiguousarray(np.asarray(dirs, dtype=np.float64).reshape(-1, 6 * self.p))
+        nd = D.shape[0]
+        info = np.zeros((nd, nd))
+        info_mean = np.zeros((self.p, self.p))
+        _lib.check(self._L.cocons_fisher_dense(self._h, _p(T), nd, _p(D), _p(info), _p(info_mean)), "cocons_fisher_dense")
+        return info, info_mean
+
     def neg2loglik_batch_core(self, theta_lists):
         """Independent evaluations pipelined on the GPU (cocons_neg2loglik_batch).  Returns
         (values, status) arrays; status k > 0 marks a Cholesky failure at minor k."""
@@ -774,6 +786,56 @@ def getHessian_dense(par, par_pos, locs, x_covariates, smooth_limits, z, n, lam,
         H = H + H.T
         H[np.diag_indices(P)] /= 2
         return H
+    finally:
+        if own:
+            f.close()
+
+
+def fisher_jacobian(par, par_pos):
+    """The optimiser's vector maps affinely onto the mean and the 6 x p table (getModelLists(type="diff")), so row a of the
+    Jacobian is getModelLists(par + e_a) - getModelLists(par), exactly.  Returns (J_table P x 6p, J_mean P x p)."""
+    par = np.asarray(par, dtype=np.float64).ravel()
+    base = getModelLists(par, par_pos, "diff")
+    T0, m0 = theta_table(base), np.asarray(base["mean"], dtype=np.float64)
+    Jt, Jm = np.zeros((par.size, T0.size)), np.zeros((par.size, m0.size))
+    for a in range(par.size):
+        e = par.copy()
+        e[a] += 1.0
+        tl = getModelLists(e, par_pos, "diff")
+        Jt[a] = (theta_table(tl) - T0).ravel()
+        Jm[a] = np.asarray(tl["mean"], dtype=np.float64) - m0
+    return Jt, Jm
+
+
+def fisher_to_par(info_table, info_mean, par, par_pos):
+    """An information matrix over the table's 6p entries (and the p x p mean block; the block between them is 0) in the
+    optimiser's coordinates: J_t I_table J_t' + J_m I_mean J_m', rows and columns in `par`'s order."""
+    Jt, Jm = fisher_jacobian(par, par_pos)
+    return Jt @ np.asarray(info_table, dtype=np.float64) @ Jt.T + Jm @ np.asarray(info_mean, dtype=np.float64) @ Jm.T
+
+
+def getFisher_dense(par, par_pos, locs, x_covariates, smooth_limits, z, n, fit=None):
+    """The P x P expected (Fisher) information of the dense model in the optimiser's coordinates, rows and columns in
+    `par`'s order, from ONE factorisation (cocons_fisher_dense) instead of getHessian_dense's 3 P (P + 1) / 2 evaluations.
+
+    What it is: the expected Hessian of the negative log-likelihood -l at the model, i.e. E[getHessian] in the reference's
+    own convention (0.5 (f11 - f01 - f10 + f00) / eps^2 is the Hessian of -l), positive semi-definite by construction, so
+    solve() of it gives non-negative variances.  What it is not: it contains no penalty (lambda plays no part), and it is
+    not the observed Hessian -- at the data actually drawn the two differ by a term of zero mean.
+
+    The Jacobian rows of `fisher_jacobian` go to the device as directions; the mean part is J_m (r X' Sigma^-1 X) J_m';
+    the block between mean and covariance parameters is 0.  A failing Cholesky raises CholeskyError."""
+    par = np.asarray(par, dtype=np.float64).ravel()
+    tl = getModelLists(par, par_pos, "diff")
+    Jt, Jm = fisher_jacobian(par, par_pos)
+    f, own = _with_fit(fit, locs, x_covariates, z, smooth_limits)
+    try:
+        cov = np.flatnonzero(np.any(Jt != 0, axis=1))       # (a pure mean parameter costs no product on the device)
+        sub, info_mean = f.fisher_core(tl, Jt[cov] if cov.size else Jt[:1])
+        info = Jm @ info_mean @ Jm.T
+        if cov.size:
+            info[np.ix_(cov, cov)] += sub
+        return info
     finally:
         if own:
             f.close()

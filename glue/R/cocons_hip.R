@@ -63,6 +63,30 @@ GetNeg2loglikelihood <- function(theta, par.pos, locs, x_covariates, smooth.limi
   list(value = res[[1]], table = res[[2]], mean = res[[3]])
 }
 
+# expected (Fisher) information of the dense model over theta (the optimiser's vector), P x P in theta's order, from one
+# factorisation: E[getHessian] at the model, without the penalty (INTEGRATION.md).  getModelLists(type = "diff") is affine, so
+# column a of the Jacobian is getModelLists(theta + e_a) - getModelLists(theta); the table parts go to the device as directions,
+# the mean parts give Jm' (r X' Sigma^-1 X) Jm.  NULL after a failing Cholesky under safe.
+.cocons.hip.fisher <- function(fit, theta, par.pos, safe = TRUE) {
+  aspects <- c("std.dev", "scale", "aniso", "tilt", "smooth", "nugget")
+  base <- cocons::getModelLists(theta = theta, par.pos = par.pos, type = "diff")
+  p <- length(base$mean)
+  flat <- function(tl) c(tl$mean, unlist(tl[aspects], use.names = FALSE))
+  J <- vapply(seq_along(theta), function(a) {
+    e <- theta
+    e[a] <- e[a] + 1
+    flat(cocons::getModelLists(theta = e, par.pos = par.pos, type = "diff")) - flat(base)
+  }, numeric(7 * p))
+  Jm <- J[seq_len(p), , drop = FALSE]
+  Jt <- J[-seq_len(p), , drop = FALSE]
+  cov <- which(colSums(Jt != 0) > 0)              # (a pure mean parameter costs no product on the device)
+  res <- .cocons.hip.result(.Call(`_cocons_hip_fisher`, fit, base[-1], Jt[, if (length(cov)) cov else 1L, drop = FALSE]), safe)
+  if (is.null(res)) return(NULL)
+  info <- crossprod(Jm, res[[2]] %*% Jm)
+  if (length(cov)) info[cov, cov] <- info[cov, cov] + res[[1]]
+  info
+}
+
 # derivative of sumsmoothlone (src/cocons_full.cpp:12-30) per element: sign(x) off the smooth branch, tanh(alpha x / 2) on it
 .cocons.hip.dsumsmoothlone <- function(x, lambda, alpha = 1e6) {
   lambda * ifelse(abs(x) > 1e-4, sign(x), tanh(alpha * x / 2))

@@ -229,6 +229,24 @@ int cocons_neg2loglik_grad_taper(cocons_fit *fit, const double *theta, const dou
                                  double *sum_logliks, double *parts,
                                  double *grad_theta, double *grad_quad, double *grad_mean);
 
+/* Expected (Fisher) information of the dense model at theta, from one factorisation:
+ *   info[a * ndir + b] = (r / 2) tr(Sigma^-1 Sigma_a Sigma^-1 Sigma_b),   Sigma_a = sum_{t,k} dirs[a][t * p + k] dSigma / dtheta[t * p + k],
+ *   info_mean[k * p + l] = r (X' Sigma^-1 X)[k, l]   (may be NULL; the block between mean and covariance parameters is 0),
+ * r the handle's number of realisations.  This is the expected Hessian of -log-likelihood (half the objective
+ * cocons_neg2loglik_dense returns) -- what getHessian (R/getFunctions.R:925-1034) estimates by second differences, without
+ * the penalty -- positive semi-definite by construction; it is not the observed Hessian.  dirs: ndir tables of 6 x p in
+ * theta's layout (row-major, ndir x 6 p), directions in table space under the conventions of grad_theta: scale k = 0 is the
+ * global range, scale k >= 1 enters the site predictor with the factor 2, coincident pairs take the first site's diagonal,
+ * pairs the reference rounds to 0 contribute 0.  The optimiser's vector maps linearly onto the table, so its P coordinates
+ * are P directions.  info is symmetric to the bit; every sum has a fixed order, so repeated calls agree bit for bit.
+ * 0, the failing minor k > 0, or < 0 with a message that starts with the entry's name; outputs are written on 0 only.
+ * Refused (-1) before any device work: null arguments, ndir outside [1, 7 * COCONS_P_MAX], non-finite entries of dirs,
+ * taper and sharded handles, a handle without z.  Memory: (ndir + 2) n_pad^2 doubles (n_pad = n rounded up to 128) and the
+ * traces' partial sums are allocated for the call and released before it returns; a device that cannot hold them gives
+ * < 0 with the bytes needed in the message.  The handle's matrix allocation is the one cocons_neg2loglik_grad_dense grows. */
+int cocons_fisher_dense(cocons_fit *fit, const double *theta, int ndir, const double *dirs,
+                        double *info, double *info_mean);
+
 /* Dense kriging core: replaces R/predict.R:136-183
  *   observed_cov <- cov_rns(...); cov_pred <- cov_rns_pred(...);
  *   inv_cov <- solve(observed_cov, t(cov_pred)); crossprod(resid, inv_cov);
