@@ -1,0 +1,599 @@
+// api_predict.hip -- C ABI, what is made of a factor: prediction and kriging (dense and taper), the marginal and
+// conditional simulations, cocons_chol_solve.
+#include "fit.hpp"
+
+// row row0 of out: the residual z[:, z_col] - X mean over the columns [0, ncols), then nrows_zero rows cleared.  out is in
+// the handle's layout (skew; a dense handle's is 0, the layout of cocons_sim_cond_dense's own buffer too)
+static void residual_row(cocons_fit *f, const double *mean, int z_col, double *out, size_t ld, int row0, int nrows_zero,
+                         int ncols)
+{
+    RhsArgs ra;
+    memset(&ra, 0, sizeof ra);
+    ra.n = f->n; ra.p = f->p; ra.X = f->dX; ra.ldx = f->n; ra.use_trend = 1;
+    for (int i = 0; i < f->p; ++i) ra.mean[i] = canon_nan(mean[i]);
+    ra.src = f->dz + (size_t)z_col * f->n; ra.lds = f->n;
+    ra.out = out; ra.ld = ld; ra.row0 = row0; ra.nrows = 1; ra.nrows_zero = nrows_zero;
+    ra.col0 = 0; ra.ncols_out = ncols;
+    ra.skew = f->skew; ra.npad = f->npad;
+    launch_rhs_rows(ra, f->stream);
+}
+
+// no right-hand sides: clear the rows under the matrix
+static void clear_border(cocons_fit *f)
+{
+    RhsArgs ra;
+    memset(&ra, 0, sizeof ra);
+    ra.n = f->n; ra.p = f->p; ra.X = f->dX; ra.ldx = f->n; ra.src = f->dX; ra.lds = f->n;
+    ra.out = f->dA; ra.ld = f->lda; ra.row0 = f->npad; ra.nrows = 0; ra.nrows_zero = f->rhs_act;
+    ra.col0 = 0; ra.ncols_out = f->npad;
+    ra.skew = f->skew; ra.npad = f->npad;
+    launch_rhs_rows(ra, f->stream);
+}
+
+// trend X %*% mean of the simulations on the host (O(n p)), as the reference does (R/sim.R:170), in the handle's order
+static std::vector<double> host_trend(const cocons_fit *f, const double *mean)
+{
+    const int n = f->n;
+    std::vector<double> tr(n, 0.0);
+    for (int j = 0; j < f->p; ++j)
+        for (int i = 0; i < n; ++i) tr[i] += f->h_X[(size_t)i + (size_t)j * n] * mean[j];
+    return tr;
+}
+
+// ---------------------------------------------------------------------------
+// the handle's buffers of the prediction entries, grown to m new locations
+static int pred_reserve(cocons_fit *f, int m)
+{
+    HIPCHK(f->dlocp.reserve((size_t)LOCP_FIELDS * m, f->stream, f->stream2));
+    HIPCHK(f->dXp.reserve((size_t)m * f->p, f->stream, f->stream2));
+    HIPCHK(f->dlocsp.reserve((size_t)m * 2, f->stream, f->stream2));
+    HIPCHK(f->dstoch.reserve((size_t)m, f->stream, f->stream2));
+    HIPCHK(f->dquad.reserve((size_t)m, f->stream, f->stream2));
+    HIPCHK(f->dred.reserve(row_reduce_scratch_doubles(f->n, m), f->stream, f->stream2));
+    return 0;
+}
+
+// kriging core: rows under the matrix = [ (z - X mean)' ; cov_rns_pred (m x n) ]
+extern "C" int cocons_predict_dense(cocons_fit *f, const double *theta, const double *mean, int z_col,
+                                    int m, const double *locs_pred, const double *X_pred,
+                                    double *stochastic, double *quadform)
+{
+    FIT_ENTER(f);
+    if (int rc = no_taper(f, "cocons_predict_dense")) return rc;
+    if (!theta || !mean || m <= 0 || !locs_pred || !X_pred || !stochastic || !quadform || z_col < 0 || z_col >= f->r)
+        return fail(-1, "cocons_predict_dense: bad argument");
+    const int p = f->p, n = f->n;
+    if (int rc = pred_reserve(f, m)) return rc;
+    if (int rc = fit_alloc_matrix(f, m + 1)) return rc;
+    hipStream_t s = f->stream;
+    HIPCHK_AT("cocons_predict_dense", upload_canon(f->dXp, X_pred, (size_t)m * p, s));
+    HIPCHK_AT("cocons_predict_dense", upload_canon(f->dlocsp, locs_pred, (size_t)m * 2, s));
+    ThetaVecs tv;
+    make_theta_vecs(theta, p, tv);
+    const ModeSel ms = select_mode(theta, p, f->smooth_limits, 2);
+    const ModeSel ms0 = select_mode(theta, p, f->smooth_limits, 0);
+    return run_op(f, "cocons_predict_dense", [&]() -> int {
+        assemble_sigma(f, theta, 0, 0, f->npad);
+        // row npad: residual of realization z_col (also clears padding rows and columns >= n); rows npad+1 .. npad+m:
+        // cross-covariance
+        residual_row(f, mean, z_col, f->dA, f->lda, f->npad, f->rhs_act - 1, f->npad);
+        launch_loc_params(loc_args(m, p, f->dXp, f->dlocsp, f->dlocp, m, tv, ms.smooth_kind, f->smooth_limits), s);
+        PairArgs pa;
+        memset(&pa, 0, sizeof pa);
+        pa.n = n; pa.m = m; pa.rows = f->dlocp; pa.stride_rows = m; pa.cols = f->dloc; pa.stride = f->npad;
+        pa.out = f->dA + f->npad + 1; pa.ld = f->lda; pa.nrows_out = m; pa.ncols_out = n;
+        pa.gr = ms.gr; pa.nu_fixed = 0.0;
+        // Sigma was assembled from dloc above (stream order); rebuild dloc only if cov_rns used a
+        // different smoothness vector (fixed-nu branch) than cov_rns_pred does: the observation-side SoA must use the
+        // pred-branch smoothness (always logistic+sqrt, :381)
+        if (ms0.smooth_kind != ms.smooth_kind)
+            launch_loc_params(loc_args(n, p, f->dX, f->dlocs, f->dloc, f->npad, tv, ms.smooth_kind, f->smooth_limits), s);
+        launch_pair_rect(MODE_GEOM, pa, s);
+        // (the dependency-driven schedule may take the head of this factorisation too -- round 6: the row reductions below read the
+        // factor from both buffers like the objectives' do; with m rows under the matrix every step is a long one)
+        FactorView pv = main_view(f);
+        pv.dag_ok = true;
+        if (int rc = factorize(f, pv, nullptr)) return rc;
+        launch_row_reduce(f->dA, f->lda, n, f->npad, f->npad + 1, m, f->dstoch, f->dquad, f->dred, s, 0, 0,
+                          f->dag_used ? f->dP : nullptr, f->dag_used ? 2 * TILE * f->dag_nsteps : 0);
+        HIPCHK_AT("cocons_predict_dense", hipMemcpyAsync(stochastic, f->dstoch, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT("cocons_predict_dense", hipMemcpyAsync(quadform, f->dquad, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+        return 0;
+    });
+}
+
+// ---------------------------------------------------------------------------
+// Kriging from a held factor: cocons_krige_prepare factors Sigma(theta) once (residual row of z_col as the one right-hand
+// side) and keeps the factor in the handle's KrigeState; cocons_krige_apply then predicts any number of new locations in
+// chunks of `rows` against it -- cross-covariance chunk (pair_rect), V = C L^-T with both reductions fused
+// (launch_krige_solve) -- with device memory independent of m.  Outputs as cocons_predict_dense's.
+static constexpr size_t KRIGE_CHUNK_BYTES = (size_t)1 << 30;      // max_rows = 0: the chunk buffers stay within 1 GiB
+static constexpr int KRIGE_ROWS_CAP = 16384;                       // ... and within 16384 rows
+
+static size_t krige_row_bytes(const cocons_fit *f)
+{
+    return ((size_t)f->npad + (size_t)f->p + 2 + LOCP_FIELDS + 2) * sizeof(double);     // C, Xp, lp, locp, st, qd
+}
+
+static int krige_rows(const cocons_fit *f, int max_rows)
+{
+    size_t r = max_rows > 0 ? (size_t)max_rows : std::min<size_t>(KRIGE_CHUNK_BYTES / krige_row_bytes(f), KRIGE_ROWS_CAP);
+    r = r / 64 * 64;                    // chunks of whole 64-row strips: a row's position in its strip never depends on the split
+    return (int)std::max<size_t>(r, 64);
+}
+
+static int krige_sharded(cocons_fit *f, const char *who)
+{
+    if (f->coll_kind && f->coll_world > 1) return fail(-1, "%s: not available on a sharded handle (world > 1)", who);
+    return 0;
+}
+
+extern "C" int cocons_krige_prepare(cocons_fit *f, const double *theta, const double *mean, int z_col, int max_rows)
+{
+    if (!f) return fail(-1, "cocons_krige_prepare: null fit handle");
+    FIT_ENTER(f);
+    if (int rc = no_taper(f, "cocons_krige_prepare")) return rc;
+    if (int rc = krige_sharded(f, "cocons_krige_prepare")) return rc;
+    if (!theta || !mean || z_col < 0 || z_col >= f->r || max_rows < 0) return fail(-1, "cocons_krige_prepare: bad argument");
+    f->krige.reset();                   // replaced -- and gone if this prepare fails
+    const int p = f->p, n = f->n, npad = f->npad, nt = f->nt;
+    std::unique_ptr<KrigeState> K(new KrigeState());
+    K->rows = krige_rows(f, max_rows);
+    K->theta.resize((size_t)6 * p);
+    for (int i = 0; i < 6 * p; ++i) K->theta[i] = canon_nan(theta[i]);
+    const size_t R = (size_t)K->rows, ntile = (size_t)nt * (nt + 1) / 2;
+    StreamDrain s{f->stream, false};
+    HIPCHK_AT("cocons_krige_prepare", K->L.alloc(ntile * TILE * TILE));
+    HIPCHK_AT("cocons_krige_prepare", K->Q.alloc((size_t)nt * 2048));
+    HIPCHK_AT("cocons_krige_prepare", K->w.alloc((size_t)npad));
+    HIPCHK_AT("cocons_krige_prepare", K->loc.alloc((size_t)LOCP_FIELDS * npad));
+    HIPCHK_AT("cocons_krige_prepare", K->C.alloc(R * npad));
+    HIPCHK_AT("cocons_krige_prepare", K->Xp.alloc(R * p));
+    HIPCHK_AT("cocons_krige_prepare", K->lp.alloc(R * 2));
+    HIPCHK_AT("cocons_krige_prepare", K->locp.alloc(R * LOCP_FIELDS));
+    HIPCHK_AT("cocons_krige_prepare", K->st.alloc(R));
+    HIPCHK_AT("cocons_krige_prepare", K->qd.alloc(R));
+    K->bytes = (long long)((ntile * TILE * TILE + (size_t)nt * 2048 + (size_t)npad * (1 + LOCP_FIELDS)) * sizeof(double) +
+                           R * krige_row_bytes(f));
+    // the padding and slot columns of a chunk are never written by the assembly: zero once
+    HIPCHK_AT("cocons_krige_prepare", hipMemsetAsync(K->C, 0, R * npad * sizeof(double), s));
+    const double *th = K->theta.data();
+    if (int rc = fit_alloc_matrix(f, 1)) return rc;
+    const int st = run_op(f, "cocons_krige_prepare", [&]() -> int {
+        f->nrhs_cur = 1;
+        assemble_sigma(f, th, 0, 0, npad);
+        // row npad: residual of realization z_col (the rows under it and the columns >= n cleared)
+        residual_row(f, mean, z_col, f->dA, f->lda, npad, f->rhs_act - 1, npad);
+        // the plain schedules (dag_ok = false): the factor lies whole in dA, with L^-1 r in row npad
+        if (int rc = factorize(f, main_view(f), nullptr)) return rc;
+        launch_krige_pack(f->dA, f->lda, nt, npad, f->pad0, n, K->L, K->Q, K->w, s);
+        return 0;
+    });
+    if (st) return st;                  // failing minor: no state (K's buffers are freed on the way out)
+    // observation-side SoA in the smoothness of cov_rns_pred (always logistic + sqrt, see cocons_predict_dense)
+    ThetaVecs tv;
+    make_theta_vecs(th, p, tv);
+    const ModeSel ms = select_mode(th, p, f->smooth_limits, 2);
+    launch_loc_params(loc_args(n, p, f->dX, f->dlocs, K->loc, npad, tv, ms.smooth_kind, f->smooth_limits), s);
+    HIPCHK_AT("cocons_krige_prepare", hipGetLastError());
+    HIPCHK_AT("cocons_krige_prepare", hipStreamSynchronize(s));
+    f->krige = std::move(K);
+    return 0;
+}
+
+extern "C" int cocons_krige_apply(cocons_fit *f, int m, const double *locs_pred, const double *X_pred,
+                                  double *stochastic, double *quadform)
+{
+    if (m < 0 || (m > 0 && (!locs_pred || !X_pred || !stochastic || !quadform)))
+        return fail(-1, "cocons_krige_apply: bad argument (m < 0 or a null pointer)");
+    if (!f) return fail(-1, "cocons_krige_apply: null fit handle");
+    FIT_ENTER(f);
+    if (int rc = no_taper(f, "cocons_krige_apply")) return rc;
+    if (int rc = krige_sharded(f, "cocons_krige_apply")) return rc;
+    KrigeState *K = f->krige.get();
+    if (!K) return fail(-1, "cocons_krige_apply: no kriging state on this handle (call cocons_krige_prepare first)");
+    const int p = f->p, rows = K->rows;
+    const double *th = K->theta.data();
+    ThetaVecs tv;
+    make_theta_vecs(th, p, tv);
+    const ModeSel ms = select_mode(th, p, f->smooth_limits, 2);
+    std::vector<double> hX((size_t)rows * p), hl((size_t)rows * 2);
+    StreamDrain s{f->stream, false};
+    for (int b = 0; b < m; b += rows) {
+        const int mc = std::min(rows, m - b);
+        // the chunk's rows of the caller's column-major m x p and m x 2 (drained below before the staging is reused)
+        for (int j = 0; j < p; ++j) memcpy(&hX[(size_t)j * mc], X_pred + b + (size_t)j * m, (size_t)mc * sizeof(double));
+        for (int j = 0; j < 2; ++j) memcpy(&hl[(size_t)j * mc], locs_pred + b + (size_t)j * m, (size_t)mc * sizeof(double));
+        HIPCHK_AT("cocons_krige_apply", upload_canon(K->Xp, hX.data(), (size_t)mc * p, s));
+        HIPCHK_AT("cocons_krige_apply", upload_canon(K->lp, hl.data(), (size_t)mc * 2, s));
+        launch_loc_params(loc_args(mc, p, K->Xp, K->lp, K->locp, rows, tv, ms.smooth_kind, f->smooth_limits), s);
+        // cross-covariance of the chunk with the caller's observations only: columns [pad0, n) in the handle's order
+        PairArgs pa;
+        memset(&pa, 0, sizeof pa);
+        pa.n = f->n_user; pa.m = mc; pa.rows = K->locp; pa.stride_rows = rows;
+        pa.cols = K->loc + f->pad0; pa.stride = f->npad;
+        pa.out = K->C + (size_t)f->pad0 * rows; pa.ld = rows; pa.nrows_out = mc; pa.ncols_out = f->n_user;
+        pa.gr = ms.gr; pa.nu_fixed = 0.0;
+        launch_pair_rect(MODE_GEOM, pa, s);
+        launch_krige_solve(K->L, K->Q, K->w, f->nt, K->C, rows, mc, f->pad0, f->n, K->st, K->qd, s);
+        HIPCHK_AT("cocons_krige_apply", hipMemcpyAsync(stochastic + b, K->st, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT("cocons_krige_apply", hipMemcpyAsync(quadform + b, K->qd, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT("cocons_krige_apply", hipGetLastError());
+        HIPCHK_AT("cocons_krige_apply", hipStreamSynchronize(s));
+    }
+    return 0;
+}
+
+extern "C" int cocons_krige_release(cocons_fit *f)
+{
+    if (!f) return fail(-1, "cocons_krige_release: null fit handle");
+    FIT_ENTER(f);
+    f->krige.reset();                   // (every entry point drains the main stream before it returns: nothing in flight uses it)
+    return 0;
+}
+
+// out4 = { prepared (0 / 1), device bytes held, rows per chunk, n }
+extern "C" int cocons_krige_info(cocons_fit *f, long long *out4)
+{
+    if (!f) return fail(-1, "cocons_krige_info: null fit handle");
+    if (!out4) return fail(-1, "cocons_krige_info: null argument");
+    FIT_ENTER(f);
+    const KrigeState *K = f->krige.get();
+    out4[0] = K ? 1 : 0;
+    out4[1] = K ? K->bytes : 0;
+    out4[2] = K ? K->rows : 0;
+    out4[3] = f->n_user;
+    return 0;
+}
+
+// Kriging core of the sparse branch of cocoPredict (R/predict.R:216-283) on a taper handle: S = taper o
+// cov_rns_taper(theta) as in the objective, C = pred_taper o cov_rns_taper_pred(theta) (m x n, its own pattern);
+// one bordered DENSE factorisation replaces  inv_cov <- spam::solve(S, t(C))  ("memory intensive", :244) and gives
+//   stochastic[i] = C[i,] S^-1 resid    (:252)      quadform[i] = C[i,] S^-1 C[i,]'    (:267)
+extern "C" int cocons_predict_taper(cocons_fit *f, const double *theta, const double *mean, int z_col, int m,
+                                    const double *locs_pred, const double *X_pred, int nnz_pred,
+                                    const int *colindices_pred, const int *rowpointers_pred,
+                                    const double *taper_entries_pred, double *stochastic, double *quadform)
+{
+    FIT_ENTER(f);
+    if (f->taper_nnz <= 0) return fail(-1, "cocons_predict_taper: not a taper fit");
+    if (!theta || !mean || m <= 0 || !locs_pred || !X_pred || !stochastic || !quadform || z_col < 0 || z_col >= f->r ||
+        nnz_pred < 0 || !rowpointers_pred || (nnz_pred > 0 && (!colindices_pred || !taper_entries_pred)))
+        return fail(-1, "cocons_predict_taper: bad argument");
+    const int p = f->p, n = f->n;
+    if (rowpointers_pred[0] != 1 || rowpointers_pred[m] != nnz_pred + 1)
+        return fail(-1, "cocons_predict_taper: rowpointers do not match nnz (1-based CSR expected)");
+    for (int w = 0; w < nnz_pred; ++w)
+        if (colindices_pred[w] < 1 || colindices_pred[w] > n) return fail(-1, "cocons_predict_taper: column index out of range");
+    if (int rc = pred_reserve(f, m)) return rc;
+    if (int rc = fit_alloc_matrix(f, m + 1)) return rc;
+    const size_t nz = nnz_pred > 0 ? (size_t)nnz_pred : 1;
+    DevBuf<int> dci, drp;
+    DevBuf<double> dtv;
+    StreamDrain s{f->stream, false};
+    HIPCHK_AT("cocons_predict_taper", dci.alloc(nz));
+    HIPCHK_AT("cocons_predict_taper", drp.alloc((size_t)m + 1));
+    HIPCHK_AT("cocons_predict_taper", dtv.alloc(nz));
+    HIPCHK_AT("cocons_predict_taper", upload_canon(f->dXp, X_pred, (size_t)m * p, s));
+    HIPCHK_AT("cocons_predict_taper", upload_canon(f->dlocsp, locs_pred, (size_t)m * 2, s));
+    HIPCHK_AT("cocons_predict_taper", hipMemcpyAsync(drp, rowpointers_pred, (size_t)(m + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+    if (nnz_pred > 0) {
+        std::vector<int> mapped(nnz_pred);          // the pattern's columns in the handle's order of the observations
+        for (int w = 0; w < nnz_pred; ++w) mapped[w] = f->taper_inv[colindices_pred[w] - 1] + 1;
+        HIPCHK_AT("cocons_predict_taper", hipMemcpy(dci, mapped.data(), (size_t)nnz_pred * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK_AT("cocons_predict_taper", upload_canon(dtv, taper_entries_pred, (size_t)nnz_pred, s));
+    }
+    // parameters as cocons_cov_rns_taper_pred prepares them: FULL scale vector, prediction-branch smoothness
+    ThetaVecs tv;
+    make_theta_vecs(theta, p, tv, true);
+    const ModeSel ms = select_mode(theta, p, f->smooth_limits, 2);
+    return run_op(f, "cocons_predict_taper", [&]() -> int {
+        if (int rc = assemble_sigma_taper(f, theta)) return rc;      // zeroes the whole buffer, border rows included
+        residual_row(f, mean, z_col, f->dA, f->lda, f->npad, f->rhs_act - 1, f->npad);
+        launch_loc_params(loc_args(m, p, f->dXp, f->dlocsp, f->dlocp, m, tv, ms.smooth_kind, f->smooth_limits), s);
+        // (the observation side after the entries of S were computed from it: stream order)
+        launch_loc_params(loc_args(n, p, f->dX, f->dlocs, f->dloc, f->npad, tv, ms.smooth_kind, f->smooth_limits), s);
+        launch_taper(MODE_GEOM, true, m, nnz_pred, dci, drp, f->dlocp, m, f->dloc, f->npad, 0.0, nullptr, s,
+                     dtv, f->dA, f->lda, f->npad + 1, f->skew, f->npad);
+        if (int rc = factorize(f, main_view(f), nullptr)) return rc;
+        launch_row_reduce(f->dA, f->lda, n, f->npad, f->npad + 1, m, f->dstoch, f->dquad, f->dred, s, f->skew, f->npad);
+        HIPCHK_AT("cocons_predict_taper", hipMemcpyAsync(stochastic, f->dstoch, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT("cocons_predict_taper", hipMemcpyAsync(quadform, f->dquad, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+        return 0;
+    });
+}
+
+// ---------------------------------------------------------------------------
+// Sparse branch of cocoSim (R/sim.R:177-217) on a taper handle: S = taper o cov_rns_taper(theta) assembled and factored as
+// the objective does (the band schedule of the handle's envelope), then Y = L E + trend by band_trmm_kernel and the rows
+// of Y gathered into the caller's order.  pos[i] = position of the caller's observation i in f's order.  Y in the handle's
+// order: (L E)[k, s] + (X mean)[k], k a position of f.
+extern "C" int cocons_fit_taper_order(cocons_fit *f, int *pivot_out)
+{
+    FIT_ENTER(f);
+    if (f->taper_nnz <= 0) return fail(-1, "cocons_fit_taper_order: not a taper fit");
+    if (!pivot_out) return fail(-1, "cocons_fit_taper_order: null argument");
+    const std::vector<int> &inv = f->taper_inv;
+    for (int i = 0; i < f->n; ++i) pivot_out[inv[i]] = i + 1;
+    return 0;
+}
+
+static int sim_taper_run(cocons_fit *f, const double *theta, const double *mean, int nsim, const double *iiderrors,
+                         const std::vector<int> &pos, double *out)
+{
+    const int n = f->n;
+    const size_t ne = (size_t)n * nsim;
+    const std::vector<double> tr = host_trend(f, mean);
+    DevBuf<double> dE, dY, dO, dtr;
+    DevBuf<int> dpos;
+    StreamDrain s{f->stream, false};
+    HIPCHK_AT("cocons_sim_taper", dE.alloc(ne));
+    HIPCHK_AT("cocons_sim_taper", dY.alloc(ne));
+    HIPCHK_AT("cocons_sim_taper", dO.alloc(ne));
+    HIPCHK_AT("cocons_sim_taper", dtr.alloc((size_t)n));
+    HIPCHK_AT("cocons_sim_taper", dpos.alloc((size_t)n));
+    HIPCHK_AT("cocons_sim_taper", upload_canon(dE, iiderrors, ne, s));
+    HIPCHK_AT("cocons_sim_taper", upload_canon(dtr, tr.data(), (size_t)n, s));
+    HIPCHK_AT("cocons_sim_taper", hipMemcpyAsync(dpos, pos.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    if (int rc = fit_alloc_matrix(f, 1)) return rc;
+    const int st = run_op(f, "cocons_sim_taper", [&]() -> int {
+        f->nrhs_cur = 0;
+        HIPCHK_AT("cocons_sim_taper", hipEventRecord(f->ev[4], s));
+        if (int rc = assemble_sigma_taper(f, theta)) return rc;
+        clear_border(f);
+        if (int rc = factorize(f, main_view(f), nullptr)) return rc;
+        HIPCHK_AT("cocons_sim_taper", hipEventRecord(f->ev[5], s));
+        launch_band_trmm(f->dA, f->lda, f->skew, f->npad, f->d_thi, f->nt, n, dE, n, nsim, dtr, dY, n, s);
+        HIPCHK_AT("cocons_sim_taper", hipEventRecord(f->ev[6], s));
+        launch_gather_rows(dY, n, dpos, n, nsim, dO, n, s);
+        HIPCHK_AT("cocons_sim_taper", hipEventRecord(f->ev[7], s));
+        HIPCHK_AT("cocons_sim_taper", hipMemcpyAsync(out, dO, ne * sizeof(double), hipMemcpyDeviceToHost, s));
+        return 0;
+    });
+    if (st == 0)
+        for (int q = 0; q < 3; ++q) HIPCHK_AT("cocons_sim_taper", hipEventElapsedTime(&f->sim_ms[q], f->ev[4 + q], f->ev[5 + q]));
+    return st;
+}
+
+extern "C" int cocons_sim_taper(cocons_fit *f, const double *theta, const double *mean, int nsim, const double *iiderrors,
+                                const int *pivot, double *out)
+{
+    FIT_ENTER(f);
+    if (f->taper_nnz <= 0) return fail(-1, "cocons_sim_taper: not a taper fit (cocons_sim_dense simulates on a dense handle)");
+    if (!theta || !mean || nsim <= 0 || !iiderrors || !out) return fail(-1, "cocons_sim_taper: bad argument");
+    const int n = f->n;
+    const std::vector<int> &inv = f->taper_inv;          // inv[caller index] = position in f's order
+    std::vector<int> tperm;                               // pivot route: twin position k <- position tperm[k] of f
+    bool own = true;
+    if (pivot) {
+        std::vector<char> seen(n, 0);
+        tperm.resize(n);
+        for (int k = 0; k < n; ++k) {
+            const int o = pivot[k] - 1;
+            if (o < 0 || o >= n || seen[o]) return fail(-1, "cocons_sim_taper: pivot is not a permutation of 1..n");
+            seen[o] = 1;
+            tperm[k] = inv[o];
+            if (tperm[k] != k) own = false;
+        }
+    }
+    std::vector<int> pos(n);
+    if (own) {                                            // the handle's own order: no twin
+        for (int i = 0; i < n; ++i) pos[i] = inv[i];
+        return sim_taper_run(f, theta, mean, nsim, iiderrors, pos, out);
+    }
+    // draw-equal route: the factor of S[pivot, pivot] -- a taper handle in that order, built once and kept while the callers
+    // pass the same pivot (the fill-reducing order of spam's chol: computed once per coco object)
+    if (!f->taper_twin || f->twin_perm != tperm) {
+        if (f->taper_twin) { cocons_fit_destroy(f->taper_twin); f->taper_twin = nullptr; }
+        f->krige.reset();                                       // (its buffers: the main stream is drained above)
+        f->twin_perm.clear();
+        cocons_fit *t = taper_create_ordered(n, f->p, f->r, f->h_locs.data(), f->h_X.data(), f->h_z.data(), f->smooth_limits,
+                                             f->device, (int)f->h_tci.size(), f->h_tci.data(), f->h_trp.data(),
+                                             f->h_tval.data(), tperm, true);
+        if (!t) {
+            const std::string why = g_err;
+            return fail(-4, "cocons_sim_taper: no taper handle in the given pivot order (%s); pivot = NULL simulates in the "
+                            "handle's own order (same distribution, another field for the same draws)", why.c_str());
+        }
+        f->taper_twin = t;
+        f->twin_perm = tperm;
+    }
+    for (int k = 0; k < n; ++k) pos[pivot[k] - 1] = k;
+    std::lock_guard<std::recursive_mutex> twin_guard(f->taper_twin->op_mu);
+    if (int rc = fit_check(f->taper_twin)) return rc;
+    return sim_taper_run(f->taper_twin, theta, mean, nsim, iiderrors, pos, out);
+}
+
+// (diagnostics) device times of the last successful cocons_sim_taper on the handle, in ms: assembly + factorisation,
+// band product, gather into the caller's order (the twin's, when that call took the pivot route); out4[3] = the 128 x 128
+// tiles of the envelope band_trmm_kernel reads per block of 64 draws
+extern "C" int cocons_debug_sim_taper_ms(cocons_fit *f, int twin, double *out4)
+{
+    FIT_ENTER(f);
+    if (!out4) return fail(-1, "cocons_debug_sim_taper_ms: null argument");
+    const cocons_fit *g = twin ? f->taper_twin : f;
+    if (!g) return fail(-1, "cocons_debug_sim_taper_ms: the handle has no twin");
+    if (g->taper_nnz <= 0) return fail(-1, "cocons_debug_sim_taper_ms: not a taper fit");
+    for (int q = 0; q < 3; ++q) out4[q] = g->sim_ms[q];
+    double tiles = 0;
+    if (g->taper_hi.empty()) tiles = 0.5 * g->nt * (g->nt + 1.0);
+    else for (int c = 0; c < g->nt; ++c) tiles += g->taper_hi[c] - c;
+    out4[3] = tiles;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// marginal simulation core: replaces R/sim.R:147-172
+//   covmat <- cov_rns[_classic](...); cholS <- chol(covmat); t(sweep(t(iiderrors) %*% cholS, 2, X %*% mean, "+"))
+extern "C" int cocons_sim_dense(cocons_fit *f, const double *theta, const double *mean, int classic,
+                                int nsim, const double *iiderrors, double *out)
+{
+    FIT_ENTER(f);
+    if (int rc = no_taper(f, "cocons_sim_dense")) return rc;
+    if (!theta || !mean || nsim <= 0 || !iiderrors || !out) return fail(-1, "cocons_sim_dense: bad argument");
+    if (f->sorted) {
+        // L E depends on the ORDER of the observations (the factor of a permuted matrix is not the
+        // permuted factor): the field for given draws is only reproduced in the caller's order
+        if (!f->unsorted) {
+            f->unsorted = fit_create_impl(f->n_user, f->p, f->r, 0, f->h_locs.data(), f->h_X.data(),
+                                          f->r > 0 ? f->h_z.data() : nullptr, nullptr, f->smooth_limits,
+                                          f->device, false);
+            if (!f->unsorted) return -1;
+        }
+        return cocons_sim_dense(f->unsorted, theta, mean, classic, nsim, iiderrors, out);
+    }
+    const int n = f->n;
+    if (int rc = fit_alloc_matrix(f, 1)) return rc;
+    const std::vector<double> tr = host_trend(f, mean);
+    DevBuf<double> dE, dY, dtr;
+    StreamDrain s{f->stream, false};
+    HIPCHK_AT("cocons_sim_dense", dE.alloc((size_t)n * nsim));
+    HIPCHK_AT("cocons_sim_dense", dY.alloc((size_t)n * nsim));
+    HIPCHK_AT("cocons_sim_dense", dtr.alloc((size_t)n));
+    HIPCHK_AT("cocons_sim_dense", upload_canon(dE, iiderrors, (size_t)n * nsim, s));
+    HIPCHK_AT("cocons_sim_dense", upload_canon(dtr, tr.data(), (size_t)n, s));
+    return run_op(f, "cocons_sim_dense", [&]() -> int {
+        f->nrhs_cur = 0;
+        assemble_sigma(f, theta, classic ? 1 : 0, 0, f->npad);
+        clear_border(f);
+        if (int rc = factorize(f, main_view(f), nullptr)) return rc;
+        launch_trmm_lower(f->dA, f->lda, n, dE, n, nsim, dtr, dY, n, s);
+        HIPCHK_AT("cocons_sim_dense", hipMemcpyAsync(out, dY, (size_t)n * nsim * sizeof(double), hipMemcpyDeviceToHost, s));
+        return 0;
+    });
+}
+
+// ---------------------------------------------------------------------------
+// conditional simulation core: replaces R/sim.R:84-127
+//   covmat, covmat_pred, covmat_unobs; L <- chol(covmat_unobs - covmat_pred solve(covmat) t(covmat_pred));
+//   t(sweep(t(iiderrors) %*% L, 2, systematic + stochastic, "+"))
+// One Cholesky of the JOINT covariance of (observed, new) locations: its lower-right block is
+// the factor of the Schur complement, and the kriging mean falls out of the border row, so the
+// LU solve, the m x n x m product and the second chol of the reference are all this one pass.
+extern "C" int cocons_sim_cond_dense(cocons_fit *f, const double *theta, const double *mean, int z_col,
+                                     int m, const double *locs_pred, const double *X_pred,
+                                     const double *locs_unobs, int nsim, const double *iiderrors, double *out)
+{
+    FIT_ENTER(f);
+    if (int rc = no_taper(f, "cocons_sim_cond_dense")) return rc;
+    if (!theta || !mean || m <= 0 || !locs_pred || !X_pred || !locs_unobs || nsim <= 0 || !iiderrors || !out ||
+        z_col < 0 || z_col >= f->r)
+        return fail(-1, "cocons_sim_cond_dense: bad argument");
+    const int n = f->n, p = f->p, npad = f->npad;
+    const int mpad = round_up(m, TILE), N = npad + mpad;
+    const size_t ldj = (size_t)N + TILE;
+    std::vector<double> mu(m), stv(m);
+    DevBuf<double> dJ, dXp, dlp, dlu, dlocp, dlocu, dE, dY, dmu, dst, dq, dred;
+    StreamDrain s{f->stream, false};
+    HIPCHK_AT("cocons_sim_cond_dense", dJ.alloc(ldj * (size_t)N));
+    HIPCHK_AT("cocons_sim_cond_dense", dXp.alloc((size_t)m * p));
+    HIPCHK_AT("cocons_sim_cond_dense", dlp.alloc((size_t)m * 2));
+    HIPCHK_AT("cocons_sim_cond_dense", dlu.alloc((size_t)m * 2));
+    HIPCHK_AT("cocons_sim_cond_dense", dlocp.alloc((size_t)LOCP_FIELDS * mpad));
+    HIPCHK_AT("cocons_sim_cond_dense", dlocu.alloc((size_t)LOCP_FIELDS * mpad));
+    HIPCHK_AT("cocons_sim_cond_dense", dE.alloc((size_t)m * nsim));
+    HIPCHK_AT("cocons_sim_cond_dense", dY.alloc((size_t)m * nsim));
+    HIPCHK_AT("cocons_sim_cond_dense", dmu.alloc((size_t)m));
+    HIPCHK_AT("cocons_sim_cond_dense", dst.alloc((size_t)m));
+    HIPCHK_AT("cocons_sim_cond_dense", dq.alloc((size_t)m));
+    HIPCHK_AT("cocons_sim_cond_dense", dred.alloc(row_reduce_scratch_doubles(n, m)));
+    HIPCHK_AT("cocons_sim_cond_dense", upload_canon(dXp, X_pred, (size_t)m * p, s));
+    HIPCHK_AT("cocons_sim_cond_dense", upload_canon(dlp, locs_pred, (size_t)m * 2, s));
+    HIPCHK_AT("cocons_sim_cond_dense", upload_canon(dlu, locs_unobs, (size_t)m * 2, s));
+    HIPCHK_AT("cocons_sim_cond_dense", upload_canon(dE, iiderrors, (size_t)m * nsim, s));
+    ThetaVecs tv;
+    make_theta_vecs(theta, p, tv);
+    const ModeSel ms0 = select_mode(theta, p, f->smooth_limits, 0);   // cov_rns semantics
+    const ModeSel msp = select_mode(theta, p, f->smooth_limits, 2);   // cov_rns_pred semantics
+    const int st = run_op(f, "cocons_sim_cond_dense", [&]() -> int {
+        f->nrhs_cur = 1;
+        // the observed side, then the new locations twice: with the coordinates handed to cov_rns (covmat_unobs) and with
+        // newlocs (cov_rns_pred, always logistic + sqrt)
+        launch_loc_params(loc_args(n, p, f->dX, f->dlocs, f->dloc, npad, tv, ms0.smooth_kind, f->smooth_limits), s);
+        launch_loc_params(loc_args(m, p, dXp, dlu, dlocu, mpad, tv, ms0.smooth_kind, f->smooth_limits), s);
+        launch_loc_params(loc_args(m, p, dXp, dlp, dlocp, mpad, tv, msp.smooth_kind, f->smooth_limits), s);
+        PairArgs pa;
+        // Sigma_oo  (rows/cols [0, npad))
+        memset(&pa, 0, sizeof pa);
+        pa.n = n; pa.m = n; pa.rows = f->dloc; pa.cols = f->dloc; pa.stride = npad; pa.stride_rows = npad;
+        pa.out = dJ; pa.ld = ldj; pa.nrows_out = npad; pa.ncols_out = npad; pa.gr = ms0.gr; pa.nu_fixed = ms0.nu_fixed;
+        launch_pair_sym(ms0.mode, false, pa, s);
+        // Sigma_uu  (rows/cols [npad, N))
+        memset(&pa, 0, sizeof pa);
+        pa.n = m; pa.m = m; pa.rows = dlocu; pa.cols = dlocu; pa.stride = mpad; pa.stride_rows = mpad;
+        pa.out = dJ + (size_t)npad + (size_t)npad * ldj; pa.ld = ldj; pa.nrows_out = mpad; pa.ncols_out = mpad;
+        pa.gr = ms0.gr; pa.nu_fixed = ms0.nu_fixed;
+        launch_pair_sym(ms0.mode, false, pa, s);
+        // cross block (rows [npad, N) x cols [0, npad)): observed side needs the pred-branch smoothness
+        if (ms0.smooth_kind != msp.smooth_kind)
+            launch_loc_params(loc_args(n, p, f->dX, f->dlocs, f->dloc, npad, tv, msp.smooth_kind, f->smooth_limits), s);
+        memset(&pa, 0, sizeof pa);
+        pa.n = n; pa.m = m; pa.rows = dlocp; pa.stride_rows = mpad; pa.cols = f->dloc; pa.stride = npad;
+        pa.out = dJ + npad; pa.ld = ldj; pa.nrows_out = mpad; pa.ncols_out = npad; pa.gr = msp.gr;
+        launch_pair_rect(MODE_GEOM, pa, s);
+        // border row N: residual of realization z_col over the observed columns, zero elsewhere
+        residual_row(f, mean, z_col, dJ, ldj, N, TILE - 1, N);
+        FactorView v;
+        v.A = dJ; v.lda = ldj; v.nt = N / TILE; v.mt = N / TILE + 1;
+        if (int rc = factorize(f, v, nullptr)) return rc;
+        // kriging mean: stochastic_i = sum_{c<n} J(npad+i, c) J(N, c);  tmp_mu = X_pred mean + stochastic
+        launch_row_reduce(dJ, ldj, n, N, npad, m, dst, dq, dred, s);
+        HIPCHK_AT("cocons_sim_cond_dense", hipMemcpyAsync(stv.data(), dst, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT("cocons_sim_cond_dense", hipStreamSynchronize(s));
+        for (int i = 0; i < m; ++i) {
+            double sys = 0;
+            for (int j = 0; j < p; ++j) sys += X_pred[(size_t)i + (size_t)j * m] * mean[j];
+            mu[i] = sys + stv[i];
+        }
+        HIPCHK_AT("cocons_sim_cond_dense", upload_canon(dmu, mu.data(), (size_t)m, s));
+        // fields = L_S E + tmp_mu with L_S = lower-right block of the joint factor
+        launch_trmm_lower(dJ + (size_t)npad + (size_t)npad * ldj, ldj, m, dE, m, nsim, dmu, dY, m, s);
+        HIPCHK_AT("cocons_sim_cond_dense", hipMemcpyAsync(out, dY, (size_t)m * nsim * sizeof(double), hipMemcpyDeviceToHost, s));
+        return 0;
+    });
+    return st > n ? n : st;    // a failure inside the Schur block is still "Cholesky error"
+}
+
+// ---------------------------------------------------------------------------
+extern "C" int cocons_chol_solve(int n, const double *Ain, int nrhs, const double *rhs,
+                                 double *L, double *Y, double *logdet_half)
+{
+    if (n <= 0 || !Ain || nrhs < 0 || (nrhs > 0 && !rhs)) return fail(-1, "cocons_chol_solve: bad argument");
+    // reuse the fit machinery with a dummy 1-column design
+    std::vector<double> locs((size_t)2 * n, 0.0), X((size_t)n, 1.0);
+    double sl[2] = {0.5, 0.5};
+    std::unique_ptr<cocons_fit, void (*)(cocons_fit *)> owner(
+        fit_create_impl(n, 1, 0, 0, locs.data(), X.data(), nullptr, nullptr, sl, -1, false), cocons_fit_destroy);   // caller's order,
+    cocons_fit *f = owner.get();                                                                                   // padding behind
+    if (!f) return -1;
+    f->engine_ok = false;     // one-shot handle whose input is uploaded once: plain schedule
+    if (int rc = fit_alloc_matrix(f, nrhs > 0 ? nrhs : 1)) return rc;
+    // identity everywhere in the padded square, zero rhs rows, then copy A and rhs^T in
+    std::vector<double> hostA(f->lda * (size_t)f->npad, 0.0);
+    for (int c = 0; c < f->npad; ++c) hostA[(size_t)c + (size_t)c * f->lda] = 1.0;
+    for (int c = 0; c < n; ++c) {
+        for (int r_ = c; r_ < n; ++r_) hostA[(size_t)r_ + (size_t)c * f->lda] = Ain[(size_t)r_ + (size_t)c * n];
+        for (int k = 0; k < nrhs; ++k) hostA[(size_t)(f->npad + k) + (size_t)c * f->lda] = rhs[(size_t)c + (size_t)k * n];
+    }
+    StreamDrain s{f->stream, false};
+    hipError_t e = upload_canon(f->dA, hostA.data(), hostA.size(), s);
+    if (e != hipSuccess) return fail(-100, "cocons_chol_solve: %s", hipGetErrorString(e));
+    if (int rc = reset_info(f)) return rc;
+    if (int rc = factorize(f, main_view(f), nullptr)) return rc;
+    launch_finalize(f->dA, f->lda, n, f->npad, 0, f->dout, s);
+    e = hipMemcpyAsync(hostA.data(), f->dA, hostA.size() * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(f->hout, f->dout, sizeof(double), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(-100, "cocons_chol_solve: %s", hipGetErrorString(e));
+    if (int rc = info_status(f)) return rc;
+    if (logdet_half) *logdet_half = f->hout[0];
+    if (L)
+        for (int c = 0; c < n; ++c)
+            for (int r_ = 0; r_ < n; ++r_)
+                L[(size_t)r_ + (size_t)c * n] = (r_ >= c) ? hostA[(size_t)r_ + (size_t)c * f->lda] : 0.0;
+    if (Y)
+        for (int k = 0; k < nrhs; ++k)
+            for (int c = 0; c < n; ++c) Y[(size_t)c + (size_t)k * n] = hostA[(size_t)(f->npad + k) + (size_t)c * f->lda];
+    return 0;
+}

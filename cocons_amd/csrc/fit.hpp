@@ -1,0 +1,473 @@
+// fit.hpp -- internal to the C ABI's translation units (api.hip, api_shard.hip, api_predict.hip, api_grad.hip): error reporting,
+// the owned device buffer, the fit handle with the states it owns, and the declarations of what api.hip -- the path of one
+// objective evaluation, the handle's life, the schedules -- offers the other three.  Not installed, not part of the contract
+// (include/cocons_hip.h is).  Everything declared here is hidden from the library's dynamic symbol table; a variable or a
+// function-local static lives in exactly one .hip file, never here.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <math.h>
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <unistd.h>
+#include <time.h>
+#include <rccl/rccl.h>         // ncclComm_t (members of the handle); the library is loaded on first use, api_shard.hip
+
+#include <algorithm>
+#include <limits>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "kernels.h"
+#include "../../include/cocons_hip_diag.h"
+#include "matern_device.hpp"   // PairMode, LOCP_FIELDS (host-visible enums)
+
+using namespace cocons;
+
+#pragma GCC visibility push(hidden)
+
+extern thread_local std::string g_err;      // the text cocons_last_error returns (api.hip)
+int fail(int code, const char *fmt, ...);
+
+#define HIPCHK(expr)                                                              \
+    do {                                                                          \
+        hipError_t e__ = (expr);                                                  \
+        if (e__ != hipSuccess) {                                                  \
+            char b__[512];                                                        \
+            snprintf(b__, sizeof b__, "%s failed: %s (%s:%d)", #expr,             \
+                     hipGetErrorString(e__), __FILE__, __LINE__);                 \
+            g_err = b__;                                                          \
+            return -100 - (int)e__;                                               \
+        }                                                                         \
+    } while (0)
+
+enum { ENGINE_ABORT = -5 };
+enum { TH_SD = 0, TH_SCALE = 1, TH_ANISO = 2, TH_TILT = 3, TH_SMOOTH = 4, TH_NUGGET = 5 };
+
+struct ModeSel {
+    int mode;          // PairMode
+    int smooth_kind;   // SmoothKind
+    double nu_fixed;
+    double gr;
+};
+
+// The mailboxes of the factorisation use the all-ones bit pattern as "not written yet" (chol.hip: the data is its own flag).
+// That pattern is a quiet NaN no arithmetic PRODUCES -- the hardware's own NaN is 0x7ff8000000000000 -- but NaN payloads
+// PROPAGATE, so an all-ones NaN in the caller's data or parameters could reach a factor block and be waited for until the bounded
+// wait gives up (a time-out and a repeat, never a wrong value).  Everything that enters the device is therefore canonicalised:
+// an all-ones NaN becomes the standard quiet NaN (R's NA_real_ and NaN are other patterns and pass unchanged).
+inline double canon_nan(double v)
+{
+    unsigned long long b;
+    memcpy(&b, &v, sizeof b);
+    return b == ~0ull ? std::numeric_limits<double>::quiet_NaN() : v;
+}
+
+hipError_t upload_canon(double *dst, const double *src, size_t count, hipStream_t s);
+
+// One owned device allocation and its element count: a local of a one-shot entry point (freed on every way out of it) or a
+// member of a handle or of one of its states (freed with it).  Empty: null with count 0 -- also after an allocation failed.
+// A buffer frees its memory only in the process that allocated it: a forked child that drops a handle abandons the
+// parent's device memory and makes no HIP call on a runtime it does not own (cocons_fit_destroy).
+template <class T> class DevBuf {
+    T *p_ = nullptr;
+    size_t n_ = 0;
+    pid_t pid_ = 0;
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_), n_(o.n_), pid_(o.pid_) { o.p_ = nullptr; o.n_ = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p_, o.p_); std::swap(n_, o.n_); std::swap(pid_, o.pid_); return *this; }
+    ~DevBuf() { reset(); }
+    void reset()
+    {
+        if (p_ && pid_ == getpid()) hipFree(p_);
+        p_ = nullptr; n_ = 0;
+    }
+    hipError_t alloc(size_t count)
+    {
+        reset();
+        hipError_t e = hipMalloc(&p_, count * sizeof(T));
+        if (e != hipSuccess) { p_ = nullptr; return e; }
+        n_ = count; pid_ = getpid();
+        return e;
+    }
+    // Hold at least (exact: exactly) count elements.  Nothing to do: no HIP call at all -- this sits on the path of every
+    // evaluation.  Otherwise: drain the handle's main stream s and its engine's stream s2 (may be null) -- work in flight may
+    // still use the old memory --, free, allocate and, with fill >= 0, set every byte to fill on s (not waited for).
+    // *grew (may be null): whether the buffer is a new allocation.
+    hipError_t reserve(size_t count, hipStream_t s, hipStream_t s2, int fill = -1, bool exact = false, bool *grew = nullptr)
+    {
+        if (grew) *grew = false;
+        if (exact ? n_ == count : n_ >= count) return hipSuccess;
+        hipError_t e = hipStreamSynchronize(s);
+        if (e == hipSuccess && s2) e = hipStreamSynchronize(s2);
+        if (e == hipSuccess) e = alloc(count);
+        if (e == hipSuccess && fill >= 0) e = hipMemsetAsync(p_, fill, count * sizeof(T), s);
+        if (grew) *grew = e == hipSuccess;
+        return e;
+    }
+    size_t count() const { return n_; }
+    T *get() const { return p_; }
+    operator T *() const { return p_; }
+};
+
+// Declared AFTER a function's DevBufs, so that its destructor -- draining the stream the buffers are used on -- runs before
+// theirs, on every way out.  own: the stream was created for this call and is destroyed as well.
+struct StreamDrain {
+    hipStream_t s;
+    bool own;
+    ~StreamDrain()
+    {
+        if (!s) return;
+        hipStreamSynchronize(s);
+        if (own) hipStreamDestroy(s);
+    }
+    operator hipStream_t() const { return s; }
+};
+
+// HIPCHK for the one-shot entry points: the message names the entry point, the code is -100 - hipError_t
+#define HIPCHK_AT(who, expr)                                                                        \
+    do {                                                                                            \
+        hipError_t e__ = (expr);                                                                    \
+        if (e__ != hipSuccess) return fail(-100 - (int)e__, "%s: %s", who, hipGetErrorString(e__)); \
+    } while (0)
+
+// theta -> kernel arguments (api.hip)
+void make_theta_vecs(const double *theta_in, int p, ThetaVecs &tv, bool full_scale = false);
+ModeSel select_mode(const double *theta, int p, const double *smooth_limits, int which);
+LocArgs loc_args(int n, int p, const double *X, const double *locs, double *out, size_t stride, const ThetaVecs &tv,
+                 int smooth_kind, const double *smooth_limits);
+inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// Kriging state of a dense handle (cocons_krige_prepare / _apply / _release).  Everything apply reads lives here, owned by
+// the state, so no other entry point on the handle -- predict growing dA, the batch slots, engine retries -- can touch it.
+struct KrigeState {
+    DevBuf<double> L;             // packed lower tiles of the factor: nt (nt + 1) / 2 tiles of 128 x 128 (kernels.h launch_krige_pack)
+    DevBuf<double> Q;             // nt x 2048: the triangular-solve operands of every diagonal tile
+    DevBuf<double> w;             // npad: L^-1 (z[:, z_col] - X mean), zero in the padding and slot columns
+    DevBuf<double> loc;           // LOCP_FIELDS x npad: observation-side SoA in the prediction branch's smoothness
+    DevBuf<double> C;             // rows x npad: one chunk of cross-covariance rows, solved in place
+    DevBuf<double> Xp, lp, locp;  // the chunk's X_pred (rows x p), locations (rows x 2) and SoA (LOCP_FIELDS x rows)
+    DevBuf<double> st, qd;        // rows: the chunk's outputs
+    std::vector<double> theta;    // 6 p: the prepared theta (canonicalised)
+    int rows = 0;                 // rows per chunk (a multiple of 64)
+    long long bytes = 0;          // device bytes held
+};
+
+// host-side plan of one evaluation's exchange: per block k the rows below it, dealt to their owners and packed
+struct ShardPlan {
+    int nt = 0, mt = 0, world = 0, group = 0;
+    std::vector<int> tlo;            // per block: first 64-row tile below the block
+    std::vector<int> ncols;          // per block: its columns (256, or 128 for a last block of one tile)
+    std::vector<long long> srows;    // per block: rows per slot S_k (64 x the largest number of tiles any rank owns below)
+    std::vector<int> pmap;           // nb x T64: element offset of 64-row tile ti in the gathered buffer of block k (-1: above)
+    std::vector<int> cnt;            // nb x world: tiles rank w owns below block k
+    size_t max_elems = 0;            // largest gathered buffer
+};
+
+// plan, buffers and events of the sharded evaluation on one handle (api_shard.hip)
+struct ShardState {
+    ShardPlan plan;
+    DevBuf<int> d_pmap;
+    DevBuf<double> lkk[2];
+    hipEvent_t ev_main_L = nullptr, ev_comm_L[2] = {nullptr, nullptr}, ev_main_X[2] = {nullptr, nullptr},
+               ev_comm_X[2] = {nullptr, nullptr};
+    hipEvent_t ev_main_U[2] = {nullptr, nullptr};    // main stream: the received L_kk in lkk[k & 1] has been unpacked (the buffer may be
+    bool unpacked[2] = {false, false};               // overwritten by the broadcast of L_(k+2)); unpacked[b]: recorded this evaluation
+};
+
+// Scratch of the dense, Profile and REML gradients and of cocons_fisher_dense (api_grad.hip)
+struct GradState {
+    DevBuf<double> scratch;       // grad_scratch_doubles(npad)
+    DevBuf<double> AR;            // npad x r: Sigma^-1 R
+    DevBuf<double> ARpart;        // its partial sums (grad_sigma_r_scratch_doubles)
+    DevBuf<double> site;          // GSITE_FIELDS x npad
+    DevBuf<double> out;           // 7 p: theta-table gradient, mean gradient
+    // Profile / REML gradients only (allocated by their first call, for a border of pcols = r + max(p, q) rows)
+    DevBuf<double> SX;            // npad x pcols: Sigma^-1 [Z | Xb]
+    DevBuf<double> SXpart;        // its partial sums
+    DevBuf<double> LR;            // npad x pcols: the low-rank block [U | sqrt(r) C]
+    DevBuf<double> gls;           // chol(Xb' Sigma^-1 Xb) and beta (grad_gls_doubles)
+    int pcols = 0;
+    long long bytes = 0;          // device bytes of the buffers above
+};
+
+// State of cocons_neg2loglik_grad_taper on a taper handle: the selected inverse goes to a second buffer of
+// the band's shape, the factor in dA is consumed by the sweep (every operation on the handle assembles its matrix anew).
+struct TaperGradState {
+    DevBuf<double> Z;             // S^-1 on the tile envelope: ldz x npad, ldz = skew * 128 (packed) or npad
+    DevBuf<double> AR;            // npad x r: S^-1 R
+    DevBuf<double> ent;           // 6 x nnz: per stored entry, the weighted partials (grad.hip taper_grad_entry_kernel)
+    DevBuf<double> site;          // GSITE_FIELDS x npad
+    DevBuf<double> gsite;         // 9 x npad
+    DevBuf<double> out;           // 9 p
+    DevBuf<int> tcp, tidx, trow;  // transposed index of the device pattern (built on the host, once)
+    size_t ldz = 0;
+    long long bytes = 0;          // device bytes of the buffers above
+};
+
+// ---------------------------------------------------------------------------
+// Every device buffer of the handle is a DevBuf member (freed with the handle, cocons_fit_destroy), every host container a
+// member by value; a feature that needs another buffer declares one.
+struct cocons_fit {
+    int n = 0, p = 0, r = 0, q = 0, device = 0;
+    pid_t pid = 0;
+    int npad = 0, nt = 0;    // padded order, tiles of 128
+    int rhs_cap = 0;         // rows reserved under the matrix (multiple of 128)
+    int rhs_act = 0;         // rows under the matrix the CURRENT operation uses (multiple of 128, <= rhs_cap)
+    size_t lda = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    DevBuf<double> dX, dlocs, dz, dxb;
+    DevBuf<double> dloc;     // LOCP_FIELDS x npad
+    DevBuf<double> dA;       // lda * npad doubles, or more once a gradient call has grown it (grad_prepare)
+    DevBuf<double> dinv;     // 2 x 8 x 256
+    DevBuf<double> dinfo_out;     // ONE allocation: the two info words, then the reductions
+    int *dinfo = nullptr;         // (view of dinfo_out)
+    double *dout = nullptr;       // reductions (view of dinfo_out)
+    double *hout = nullptr;       // pinned mirror (hinfo, hout, hinfo_init: one pinned allocation, freed through hinfo)
+    int *hinfo = nullptr, *hinfo_init = nullptr;
+    double smooth_limits[2] = {0, 0};
+    size_t out_cap = 0;
+    // predict scratch (pred_reserve)
+    DevBuf<double> dlocp, dXp, dlocsp, dstoch, dquad, dred;
+    // sharded state
+    int rank = 0, world = 1, nrhs_cur = 0;
+    int nslot = 0;                // > 0: the last nslot of the npad rows / columns are SLOTS (npad = n + nslot): columns with a huge
+                                  // diagonal and nothing else, rows that hold the right-hand sides of an evaluation (at most nslot
+                                  // of them) INSIDE the last tile of the matrix -- no tile row under the matrix (enqueue_eval)
+    int n_user = 0, pad0 = 0;     // n = pad0 + n_user: dense handles keep pad0 = npad - n_user placeholder observations IN FRONT
+                                  // of the caller's (their columns are made unit vectors before every factorisation,
+                                  // launch_front_identity), so that n == npad and no padding sits in the trailing matrix
+    DevBuf<double> xbuf[2];       // exchange buffers of the sharded evaluation (shard_prepare)
+    hipEvent_t ev[8] = {};
+    hipStream_t stream2 = nullptr;     // stream the resident diagonal-tile engine is launched on
+    hipEvent_t ev_eng = nullptr;  // orders the engine launch behind the reset of its flag words
+    DevBuf<unsigned> dflags;      // flags_cap words each: in[t], out[t], xr[t] (see launch_potrf_engine); 64: the alive word;
+                                  // flags_cap: tile counters of the trailing updates
+    int flags_cap = 0;            // (also the stride between in[], out[] and xr[]: not just dflags' count)
+    bool engine_ok = false;       // false: this handle never uses the resident engine (batch slots, band-limited taper fits)
+    bool engine_live = false;     // the engine of the NEXT factorize call is already launched (engine_start)
+    bool engine_used = false;     // the factorisation enqueued last runs on the engine schedule
+    int border_clean = -1;        // nr >= 0: the rows [nr, rhs_act) under the matrix are known to be exactly zero in every column
+                                  // (they were zeroed, and a SUCCESSFUL factorisation keeps zero rows zero): the next
+                                  // evaluation with the same nr does not zero them again (-1: unknown)
+    int border_pending = -1;      // what border_clean becomes when the operation in flight turns out to have succeeded
+    bool engine_active_last = false;   // the last COMPLETED operation ran on the engine schedule (cocons_fit_engine_state)
+    int engine_skip = 0;          // operations still to run on the plain schedule after a hand-off timed out (back-off)
+    int engine_fails = 0;         // consecutive time-outs (the back-off doubles with each, up to 64 operations)
+    int engine_retries = 0;       // time-outs in the life of the handle, each answered by one repeat on the plain schedule
+    int engine_last_abort = 0;    // abort word of the last time-out (who gave up: see info_status)
+    long long engine_ops = 0;     // operations enqueued on the engine schedule so far (the first one's gate is patient)
+    // dependency-driven schedule (factorize_dag): second buffer shaped like dA, tile inverses, task words, step table
+    DevBuf<double> dP;
+    DevBuf<double> dWt;           // one 128 x 128 tile per tile column
+    DevBuf<double> dpart;         // early halves of the split diagonal-block tiles (2 x 16 x 64 x 64 doubles)
+    DevBuf<unsigned> ddag;        // [queue (64 words)] [tdone] [pdone]
+    DevBuf<DagStepHost> ddag_steps; int dag_nsteps = 0; unsigned dag_ntasks = 0;
+    int dag_key[12] = {};         // (nt, mt, trim, kskip, lead, min_tiles, lead2, lead3, order, xcd, bw, bh) the step table was built for
+    DevBuf<unsigned> ddag_ftab;   // which tile every far tile task is (dag_build_steps' table), device copy
+    int dag_xcd_g = 0;            // chunk exponent of the XCD-aware deal the table was built for (0: one counter)
+    bool dag_have_ftab = false;   // the current step table comes with a far-tile table
+    size_t ddag_xcnt_off = 0;     // offset (words) of the XCDs' task counters inside ddag
+    DevBuf<unsigned long long> ddag_trace;   // diagnostics (cocons_debug_tune("dag_trace", 1)): 4 stamps per task, 5 words per
+    size_t dag_trace_tasks = 0;              // task + 8 per tile pair allocated
+    bool dag_next = false;        // the engine launched by engine_start is the DAG schedule's (publishes W and the second X)
+    int engine_pair_live = 0;     // 1: the engine launched for the next factorisation has a pair partner (it counts itself in alive[2])
+    size_t smb_off = 0, smb_elems = 0;   // inside dmbox: strip mailboxes, one per diagonal block (the panel launch's next-diagonal-block
+                                         // update), and xmb_off: the panel launch's exchange mailboxes, one per 64-row strip (split panel)
+    size_t xmb_off = 0, xmb_elems = 0;
+    DevBuf<double> dmbox;                // one mailbox per tile (mbox_reset): the engine's pair mode, the panel kernel and potrf_solve's
+                                         // followers read a tile's factor from there while it is being formed
+    bool follow_used = false, follow_off = false;   // the operation being enqueued used launch_potrf_follow; it timed out once on this handle: off
+    double enq_host_us = 0; long long enq_calls = 0;   // (diagnostics) host time spent enqueueing evaluations, calls: cocons_debug_host_enqueue
+    bool dag_used = false;        // the factorisation enqueued last ran the DAG schedule: its factor is split over dA and dP
+    double dag_flops = 0; int dag_events = 0;   // profile runs: update flops inside the DAG launch; 1 = the first event pair is that launch
+    // taper fit (cocons_fit_create_taper): the spam pattern (1-based CSR) with the taper's entries; the
+    // -2 log-likelihood is then that of the TAPERED covariance, evaluated through the dense factorisation
+    int taper_nnz = 0;            // > 0: taper fit
+    DevBuf<int> d_tci, d_trp;
+    DevBuf<double> d_tval;        // taper entries (constant)
+    std::vector<int> taper_hi;    // envelope of the (reordered) pattern per tile column: see FactorView::hi (empty: none)
+    DevBuf<int> d_thi; int taper_maxband = 0; // device copy of taper_hi and max_c (hi[c] - c)
+    int skew = 0;                 // > 0: the factorisation buffer is PACKED (kernels.h band_index): every tile column keeps
+                                  // `skew` (= taper_maxband) tile rows from its diagonal tile down plus the rows under the
+                                  // matrix -- O(n x bandwidth) doubles instead of n^2
+    std::vector<int> taper_inv;   // position of the caller's observation i in the handle's order (reverse Cuthill-McKee)
+    std::vector<int> h_trp, h_tci;     // host copy of the full (symmetric) pattern and taper entries in the handle's order:
+    std::vector<double> h_tval;        // what a twin in another order is built from (O(nnz))
+    cocons_fit *taper_twin = nullptr;  // lazily created taper handle in the order of the last pivot cocons_sim_taper was given
+    std::vector<int> twin_perm;   // that order: twin position k holds the observation at position twin_perm[k] of this handle
+    float sim_ms[3] = {0, 0, 0};  // last cocons_sim_taper: assembly + factorisation, band product, gather (device events)
+    // collectives of the natively sharded evaluation (see "native sharded evaluation" below)
+    int coll_kind = 0;            // 0 none, 1 RCCL communicator, 2 caller-provided transport
+    int coll_rank = 0, coll_world = 0;
+    ncclComm_t comm = nullptr;
+    bool comm_own = false;        // the communicator was created by cocons_fit_comm_init (destroy it with the fit)
+    cocons_bcast_fn cb_bcast = nullptr;
+    cocons_allreduce_fn cb_allreduce = nullptr;
+    cocons_allgather_fn cb_allgather = nullptr;
+    std::unique_ptr<ShardState> shard;   // plan, buffers and events of the sharded evaluation (row-block ownership)
+    void *cb_user = nullptr;
+    hipStream_t cstream = nullptr;     // stream the bulk exchange (all-gather of the solved rows) is issued on
+    hipStream_t cstream_l = nullptr;   // stream the 0.56 MB broadcasts of the factored diagonal blocks are issued on: the chain from one
+                                  // diagonal block to the next never queues behind an all-gather (== cstream when the
+                                  // broadcasts have no communicator of their own)
+    ncclComm_t comm_l = nullptr;  // RCCL: a second communicator over the same ranks (ncclCommSplit) for those broadcasts --
+                                  // operations of ONE communicator are serialised whatever stream they are given; null: comm
+    bool comm_l_own = false;
+    DevBuf<double> dcoll;         // device staging of the final all-reduce (RCCL)
+    double upd_flops = 0;         // algorithmic flops of the event-timed trailing updates (profile runs)
+    // host copies of the inputs + lazily created clones: the slots of cocons_neg2loglik_batch
+    std::vector<double> h_locs, h_X, h_z, h_xb;
+    std::vector<cocons_fit *> slots;
+    bool sorted = false;          // observations are stored in Morton order (see fit_create_impl)
+    cocons_fit *unsorted = nullptr;    // lazily created clone in the ORIGINAL order (marginal simulation)
+    std::recursive_mutex op_mu;   // held by every entry point for as long as it works on this handle (FIT_ENTER), and by another
+                                  // handle's stream self-test while it launches probe kernels on this handle's streams
+                                  // (engine_warm: try_lock under the registry's lock -- a busy handle is not probed, a probed one
+                                  // can neither be used nor destroyed until the probe is over)
+    std::unique_ptr<KrigeState> krige;   // kriging state (cocons_krige_prepare): one factor of Sigma(theta) held apart from dA
+    std::unique_ptr<GradState> grad;     // scratch of cocons_neg2loglik_grad_dense (allocated on first use)
+    std::unique_ptr<TaperGradState> tgrad;   // taper fit: state of cocons_neg2loglik_grad_taper (allocated on first use)
+};
+
+int fit_check(cocons_fit *f);
+
+// Every public entry point that works on a handle: validate it, then hold its operation lock until the call returns.
+// THREADING CONTRACT (include/cocons_hip.h): one handle serves one call at a time -- a second thread that enters with the
+// same handle waits here --; different handles may be used, created and destroyed from different threads concurrently.
+#define FIT_ENTER(f)                                                   \
+    if (int rc__ = fit_check(f)) return rc__;                          \
+    std::lock_guard<std::recursive_mutex> op_guard__((f)->op_mu)
+
+// the matrix a factorisation runs on: column tiles nt, row tiles mt (>= nt: rows under the square)
+struct FactorView {
+    double *A;
+    size_t lda;
+    int nt, mt;
+    const int *hi = nullptr;   // band-limited factorisation (taper handles): hi[c] = one past the last tile row of tile
+                               // column c that can be non-zero in the factor (envelope of the pattern); nullptr = dense
+    int skew = 0;              // > 0: A is a packed band buffer (kernels.h band_index) of `skew` tile rows per tile column
+    int trim = 0;              // 1: the last 64 of the mt * 128 rows hold nothing (the tile of right-hand sides has at most 64
+                               // rows in use): no kernel of the factorisation touches them
+    bool dag_ok = false;       // the caller reads the factor through launch_finalize(..., A2 = dP) only: the dependency-driven
+                               // schedule may be used (its factor is split over two buffers)
+};
+
+// Where the nrhs right-hand-side rows of an evaluation sit -- the ONE place that decides it (enqueue_eval_impl, the replay
+// diagnostic and cocons_debug_rhs_layout all ask here):
+//   slots   they ride in the slot rows of the matrix's last tile (the handle keeps nslot >= nrhs of them): no rows under it;
+//   border  otherwise in tile_rows = ceil(nrhs / 128) tile rows under the matrix (what fit_alloc_matrix makes of rhs_act),
+//           and trim says that the last 64 of those rows hold nothing: no kernel of the factorisation touches them.
+struct RhsLayout {
+    bool slots;
+    int tile_rows;
+    int trim;
+};
+
+// Schedule switches: read from the environment once per process, and settable afterwards through cocons_debug_tune (the
+// diagnostics header) so that variants can be timed in alternation inside ONE process on ONE device.
+struct Tunables {
+    int engine = 1;          // COCONS_ENGINE: 1 = diagonal blocks are factored by the resident engine beside the updates
+    int dag = 1;             // COCONS_DAG: 1 = the head of the factorisation under the dependency-driven schedule (one persistent
+                             // launch for its updates and panels, dag_kernel); 0 = the classic schedule throughout
+    // where a step's panel tasks sit in its list: `lead` far tiles, T1 (+ early halves), `lead2` far tiles, T2, `lead3` far
+    // tiles, T3 -- each group about where the chip gets to it when the engine publishes what it waits for (the chip draws ~32
+    // tasks per us; first tile out ~85 us into a step, strip (t+1, t) ~18 us later, second tile ~60 us after that), so that
+    // the workgroups that draw them neither wait with a slot in hand nor come late.  One block at 3600 (round 4's first
+    // form): -1.4 %; at 2400: -0.9 %; everything between (800 .. 2000, 400 .. 900, 1800 .. 2400) measures alike.
+    int dag_lead = 1600, dag_lead2 = 600, dag_lead3 = 1800;
+    int dag_min_tiles = 2000;  // COCONS_DAG_MIN_TILES: the DAG launch covers the leading steps of at least this many update tiles
+                             // (n = 10^4: 24 of the 39 steps, 94 % of the flops; below n ~ 4200 no step at all).  3000 until the
+                             // engine became a pair (round 5): with the shorter chain the break-even moved back, 1400 .. 2200
+                             // measure alike, +0.4 % over 3000)
+    int dag_xcd = 1;         // COCONS_DAG_XCD: 1 = XCD-aware task order of the persistent launch (round 6; chol.hip: dag_position) -- list
+                             // positions dealt to the XCDs in chunks of 32, the far tiles of a step dealt so that one XCD's tiles in
+                             // flight form one block of dag_bw x dag_bh tiles, a class that falls behind helped by the others: fetched
+                             // bytes per launch halve, +2 % evaluations/s at n = 10^4; 0 = one counter for all (rounds 4-5).
+                             // dag_order (COCONS_DAG_ORDER): 0 = far tiles column-major as in rounds 4-5
+    int dag_order = 1, dag_bw = 16, dag_bh = 16;
+    int dag_xcd_min_quota = 128;
+    int dag_xcc_quota = -1;  // workgroups of the DAG launch that take part on the engine's XCD (of the 255 that land there; 0: all;
+                             // -1: derived from the device, dag_xcc_quota() -- 208 on MI355X)
+    int engine_pair = 1;     // COCONS_ENGINE_PAIR: 1 = the engine is a PAIR of workgroups -- the second one follows the first tile's
+                             // factorisation column block by column block (strip solve, tile update) and factors the second tile
+                             // (chol.hip: engine_partner_loop); 0 = one workgroup does the four passes one behind the other
+    int panel_fused = 1;     // COCONS_PANEL_FUSED: 1 = the panel of a two-tile block of the engine schedule is ONE launch whose strips
+                             // follow the engine pair's tiles through their mailboxes (chol.hip: panel_pair_kernel); 0, or without
+                             // the pair: solve | in-panel update | solve, three launches
+    int panel_split = 32;    // COCONS_PANEL_SPLIT: a strip of the one-launch panel is TWO workgroups -- the first follows tile t (X0), the second
+                             // follows the first through an exchange mailbox (the in-panel product while X0 is being formed), then tile
+                             // t+1 -- in panels of at least this many 64-row strips (0: never, 1: always).  It pays where the panel stands
+                             // exposed behind a long update launch (n = 4096: +1.9 %, 6400: +1.5 %, 10^4: +0.6 %) and costs where the engine
+                             // is the bound anyway (always on: n = 2116 -4.3 %, n = 1024 -2.2 %); an update of 32 strips' trapezoid is ~30 us
+    int potrf_follow = 1;    // COCONS_POTRF_FOLLOW: 1 = a tile factorisation and the panel solve below it are ONE launch whose solve
+                             // workgroups follow the factorisation through a mailbox (chol.hip: potrf_follow_kernel; the plain and
+                             // the band-limited schedule); 0 = two launches
+    int dag_trace = 0;       // (diagnostics) time stamps per task, cocons_debug_dag_trace
+    int gate_sabotage = 0;   // (tests) the next N engine-schedule factorisations wait at the gate for a word nobody raises:
+                             // a genuine 5 ms time-out, abort code 0x600, to exercise the fall-back and its book-keeping
+    // (tests) a LATE HOST: the thread that enqueues a factorisation sleeps host_delay_us microseconds in front of the launches that
+    // raise the engine's input word in[host_delay_tile] (COCONS_DEBUG_HOST_DELAY_US / _TILE) -- what a host thread throttled in
+    // mid-enqueue looks like to the resident engine (round 5's recorded time-out 0x112) --, and
+    // engine_in_wait_ms > 0 puts the bound of the engine's input waits back to that many milliseconds (rounds 2-4: 100)
+    int host_delay_us = 0, host_delay_tile = -1, engine_in_wait_ms = 0;
+    bool init = false;
+};
+
+// What api.hip offers the other translation units (defined and described there) ...
+Tunables &tun();
+bool engine_enabled();
+int fit_alloc_matrix(cocons_fit *f, int rhs_rows);
+cocons_fit *fit_create_impl(int n, int p, int r, int q, const double *locs, const double *X, const double *z, const double *x_betas,
+                            const double *smooth_limits, int device, bool allow_sort, bool defer_matrix = false,
+                            bool want_engine = true, bool return_locked = false);
+cocons_fit *taper_create_ordered(int n, int p, int r, const double *locs, const double *X, const double *z,
+                                 const double *smooth_limits, int device, int nnz, const int *colindices, const int *rowpointers,
+                                 const double *taper_entries, const std::vector<int> &perm, bool check_fit);
+void assemble_sigma(cocons_fit *f, const double *theta, int which, int col0, int col1);
+int assemble_sigma_taper(cocons_fit *f, const double *theta);
+int no_taper(cocons_fit *f, const char *who);
+void assemble_rhs(cocons_fit *f, const double *mean, bool use_trend, const double *xb, int nxb, int col0, int col1,
+                  bool zero_rest = true, bool slots = false);
+FactorView main_view(cocons_fit *f);
+int flags_reset(cocons_fit *f, int nt);
+int mbox_reset(cocons_fit *f, int nt, bool engine_schedule = true);
+int factorize(cocons_fit *f, const FactorView &v, std::vector<hipEvent_t> *ev_upd);
+int reset_info(cocons_fit *f);
+int info_status(cocons_fit *f);
+bool engine_retry(cocons_fit *f, int st);
+void dense_collect(cocons_fit *f, double *sum_logliks, double *parts);
+int profile_tail(cocons_fit *f, int nxb, double n_eff, bool reml, double *sum_logliks, double *parts);
+// ... and what it calls in api_shard.hip: the sharded cocons_neg2loglik_dense, and cocons_fit_destroy's share
+int sharded_eval(cocons_fit *f, const double *theta, const double *mean, double *sum_logliks, double *parts);
+void shard_events_destroy(ShardState *S);
+void rccl_comm_destroy(ncclComm_t c);
+
+// One operation of a one-shot entry that factors on the handle: enqueue() puts everything of it but the info words on the
+// handle's stream (assembly, factorisation, the entry's own kernels and result copies; 0 or an error); it is run again after a
+// hand-off time-out.  0, a failing minor or an error.
+template <class F> int run_op(cocons_fit *f, const char *who, F &&enqueue)
+{
+    for (;;) {
+        if (int rc = reset_info(f)) return rc;
+        if (int rc = enqueue()) return rc;
+        HIPCHK_AT(who, hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, f->stream));
+        HIPCHK_AT(who, hipGetLastError());
+        HIPCHK_AT(who, hipStreamSynchronize(f->stream));
+        const int st = info_status(f);
+        if (!engine_retry(f, st)) return st;
+    }
+}
+
+constexpr double LOG_2PI = 1.8378770664093454835606594728112;
+
+#pragma GCC visibility pop

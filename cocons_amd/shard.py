@@ -17,7 +17,7 @@ solves and updates ITS rows of every column:
     all-reduce of {sum log diag, Gram of the rhs rows} (1 + r^2 doubles) and of the failing minor
 
 The schedule, the RCCL collectives (on a communication stream of their own) and the final all-reduce all live
-INSIDE the HIP library (`sharded_eval` in csrc/api.hip): once a fit has collectives, `cocons_neg2loglik_dense`
+INSIDE the HIP library (`sharded_eval` in csrc/api_shard.hip): once a fit has collectives, `cocons_neg2loglik_dense`
 on it is the sharded evaluation.  This module only wires a fit to its communicator:
 
   * `ShardedFit.init_rccl(dist)`    one process per GPU: rank 0 draws the RCCL unique id
@@ -225,7 +225,7 @@ class MultiFit:
 
 
 def sharded_neg2loglik_core(engine, theta_list, dist, rank, world, group=None, lookahead=True):
-    """The row-block sharded schedule over an abstract engine: the Python twin of `sharded_eval` in csrc/api.hip, run by
+    """The row-block sharded schedule over an abstract engine: the Python twin of `sharded_eval` in csrc/api_shard.hip, run by
     the CPU tests with a numpy engine.  Engine interface: begin / num_blocks / owner / factor_diag / diag_tensor /
     set_diag / solve / ahead / exchanges / pack / set_gathered / update / finish / make_tensor.
     Returns (sum_logliks, parts), identical on every rank; raises CholeskyError on every rank if any pivot failed.

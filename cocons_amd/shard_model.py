@@ -1,4 +1,4 @@
-"""Critical-path model of the row-block sharded evaluation (csrc/api.hip `sharded_eval`): what
+"""Critical-path model of the row-block sharded evaluation (csrc/api_shard.hip `sharded_eval`): what
 `bench.py --gpus N` prints beside its measurement.  Nothing here has been measured on a multi-GPU node -- the kernel
 times are single-GPU measurements of this repository (kernel traces of rounds 3-4), the link figures are assumptions
 stated below; the point of printing the prediction is that the first run on real hardware confirms or refutes it.

@@ -27,7 +27,7 @@ class NumpyShardEngine:
         return (self.nt + PT - 1) // PT
 
     def owner(self, b):
-        """(b div G) mod world: csrc/api.hip shard_owner."""
+        """(b div G) mod world: csrc/api_shard.hip shard_owner."""
         return (b // self.group) % self.world
 
     def _owner64(self, ti):

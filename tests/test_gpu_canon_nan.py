@@ -1,4 +1,4 @@
-"""An all-ones NaN in a caller's array is canonicalised before it reaches the device (api.hip: canon_nan, upload_canon).
+"""An all-ones NaN in a caller's array is canonicalised before it reaches the device (fit.hpp: canon_nan; api.hip: upload_canon).
 
 That bit pattern is the factorisation mailboxes' "not written yet" word: if it reached a factor block it would be waited on
 until the bounded wait ran out (an engine time-out and a repeat).  One small case per one-shot entry: the call returns in
