@@ -32,6 +32,7 @@ from .host import (  # noqa: F401
     cov_rns_taper_pred,
     getBetas_profile,
     getFisher_dense,
+    getFisher_reml,
     getHessian_dense,
     getModelLists,
     getModelLists_grad,

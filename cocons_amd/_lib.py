@@ -66,6 +66,7 @@ SIGNATURES = {
     "cocons_neg2loglik_reml_grad": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_dp]),
     "cocons_neg2loglik_grad_taper": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "cocons_fisher_dense": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_dp]),
+    "cocons_fisher_reml": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp]),
     "cocons_predict_dense": (c_int, [c_vp, c_dp, c_dp, c_int, c_int, c_dp, c_dp, c_dp, c_dp]),
     "cocons_sim_dense": (c_int, [c_vp, c_dp, c_dp, c_int, c_int, c_dp, c_dp]),
     "cocons_krige_prepare": (c_int, [c_vp, c_dp, c_dp, c_int, c_int]),

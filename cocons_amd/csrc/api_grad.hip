@@ -287,20 +287,30 @@ extern "C" int cocons_debug_sigma_inverse(cocons_fit *f, const double *theta, do
 // the leading square (grad_enqueue, full = false); everything else lives in buffers of this call: one tall buffer of ndir + 2
 // blocks of npad rows -- Sigma^-1 in full, the direction matrices Sigma_a, and the products, each of which lands in the block
 // the product before it has consumed --, the site weights and the traces' per-tile partial sums.
+// The information of the REML fit (cocons_fisher_reml) is the same operation on the REML gradient's border
+// [Z' ; X' ; I] (profile_grad_enqueue without the contraction), with the projector P = Sigma^-1 - C C' put where Sigma^-1 was
+// (launch_fisher_project) before the products run; it has no mean block.
 struct FisherCall {
     DevBuf<double> tall, dirs, w, part, sxpart, sx, out;
     int ndir = 0;
     size_t ldt = 0;
+    bool reml = false;
 };
 
 static int fisher_enqueue(cocons_fit *f, const double *theta, FisherCall &c, double *hinfo, double *hmean)
 {
     const int npad = f->npad, p = f->p, ndir = c.ndir;
     hipStream_t s = f->stream;
-    const std::vector<double> zero((size_t)p, 0.0);
-    if (int rc = grad_enqueue(f, theta, zero.data(), false, nullptr)) return rc;
+    if (c.reml) {
+        if (int rc = profile_grad_enqueue(f, theta, f->dX, p, true, nullptr)) return rc;
+    } else {
+        const std::vector<double> zero((size_t)p, 0.0);
+        if (int rc = grad_enqueue(f, theta, zero.data(), false, nullptr)) return rc;
+    }
     double *Tb = c.tall;
     launch_fisher_mirror(Tb, c.ldt, 0, f->dA, f->lda, 0, npad, 1, -1.0, s);
+    if (c.reml)         // (LR = [U | sqrt(r) C]: the factor sqrt(r) of the gradient's block goes out again)
+        launch_fisher_project(Tb, c.ldt, f->grad->LR + (size_t)f->r * npad, (size_t)npad, p, f->pad0, f->n, npad, 1.0 / f->r, s);
     GradArgs g;
     const int mode = grad_pair_args(f, theta, g);
     launch_fisher_dirs(mode, g, ndir, c.dirs, c.w, Tb + npad, c.ldt, (size_t)npad, s);
@@ -316,46 +326,68 @@ static int fisher_enqueue(cocons_fit *f, const double *theta, FisherCall &c, dou
     return 0;
 }
 
-extern "C" int cocons_fisher_dense(cocons_fit *f, const double *theta, int ndir, const double *dirs, double *info,
-                                   double *info_mean)
+// both entries; reml: the border is [Z' ; X' ; I] and info_mean is null
+static int fisher_entry(cocons_fit *f, const char *who, const double *theta, int ndir, const double *dirs, double *info,
+                        double *info_mean, bool reml)
 {
-    const char *who = "cocons_fisher_dense";
     if (!f) return fail(-1, "%s: null fit handle", who);
     if (!theta || !dirs || !info) return fail(-1, "%s: null argument", who);
     if (ndir < 1 || ndir > 7 * COCONS_P_MAX) return fail(-1, "%s: ndir = %d is outside [1, %d]", who, ndir, 7 * COCONS_P_MAX);
     FIT_ENTER(f);
     if (int rc = grad_refuse(f, who)) return rc;
     if (f->r < 1) return fail(-1, "%s: fit has no z", who);
-    const int npad = f->npad, p = f->p;
+    const int npad = f->npad, p = f->p, nb = reml ? f->r + p : f->r;
     const size_t nd = (size_t)ndir * 6 * p;
     for (size_t e = 0; e < nd; ++e)
         if (!std::isfinite(dirs[e])) return fail(-1, "%s: direction %d has a non-finite entry", who, (int)(e / ((size_t)6 * p)));
     FisherCall c;
     c.ndir = ndir;
     c.ldt = (size_t)(ndir + 2) * npad;
+    c.reml = reml;
     if (c.ldt * 64 * sizeof(double) > 0xffffffffull)       // (the product kernel's 32-bit byte offsets inside a tile)
         return fail(-1, "%s: %d directions of order %d are beyond the product kernel's addressing", who, ndir, npad);
-    if (int rc = grad_prepare(f, who, f->r)) return rc;
+    if (int rc = reml ? grad_prepare(f, who, nb, f->r + (f->q > p ? f->q : p)) : grad_prepare(f, who, nb)) return rc;
+    const bool mean = info_mean != nullptr;
     const size_t counts[7] = {c.ldt * npad, nd, (size_t)ndir * 6 * npad, fisher_trace_scratch_doubles(npad, ndir),
-                              grad_sigma_r_scratch_doubles(npad, p), (size_t)npad * p, (size_t)ndir * ndir + (size_t)p * p};
+                              reml ? 0 : grad_sigma_r_scratch_doubles(npad, p), reml ? 0 : (size_t)npad * p,
+                              (size_t)ndir * ndir + (reml ? 0 : (size_t)p * p)};
     DevBuf<double> *bufs[7] = {&c.tall, &c.dirs, &c.w, &c.part, &c.sxpart, &c.sx, &c.out};
     size_t bytes = 0;
     for (size_t k : counts) bytes += k * sizeof(double);
     std::vector<double> hinfo((size_t)ndir * ndir), hmean((size_t)p * p);
     StreamDrain drain{f->stream, false};       // (declared behind the buffers: the stream is idle before they are freed)
-    for (int k = 0; k < 7; ++k)
+    for (int k = 0; k < 7; ++k) {
+        if (!counts[k]) continue;
         if (hipError_t e = bufs[k]->alloc(counts[k])) {
             (void)hipGetLastError();
             return fail(-100 - (int)e, "%s: the device cannot hold the %zu bytes of this call (%d + 2 matrices of order %d): %s",
                         who, bytes, ndir, npad, hipGetErrorString(e));
         }
+    }
     HIPCHK_AT(who, upload_canon(c.dirs, dirs, nd, f->stream));
-    GradLayout layout(f, f->r);
-    const int st = run_op(f, who, [&]() -> int { return fisher_enqueue(f, theta, c, hinfo.data(), info_mean ? hmean.data() : nullptr); });
+    GradLayout layout(f, nb);
+    const int st = run_op(f, who, [&]() -> int { return fisher_enqueue(f, theta, c, hinfo.data(), mean ? hmean.data() : nullptr); });
     if (st) return st;                  // failing minor: nothing written
+    if (reml) {
+        // a failing pivot of W leaves C all zero (launch_grad_lowrank) and the result the ML information: the same Gram matrix,
+        // factored on the host in the device's order, says so (as the REML gradient's entry)
+        double val = 0.0;
+        if (profile_tail(f, p, 0.0, true, &val, nullptr)) return fail(-4, "%s: X' Sigma^-1 X is not positive definite", who);
+    }
     memcpy(info, hinfo.data(), hinfo.size() * sizeof(double));
-    if (info_mean) memcpy(info_mean, hmean.data(), hmean.size() * sizeof(double));
+    if (mean) memcpy(info_mean, hmean.data(), hmean.size() * sizeof(double));
     return 0;
+}
+
+extern "C" int cocons_fisher_dense(cocons_fit *f, const double *theta, int ndir, const double *dirs, double *info,
+                                   double *info_mean)
+{
+    return fisher_entry(f, "cocons_fisher_dense", theta, ndir, dirs, info, info_mean, false);
+}
+
+extern "C" int cocons_fisher_reml(cocons_fit *f, const double *theta, int ndir, const double *dirs, double *info)
+{
+    return fisher_entry(f, "cocons_fisher_reml", theta, ndir, dirs, info, nullptr, true);
 }
 
 // out4 = { bytes allocated for the matrix buffer dA, bytes of the DAG schedule's second buffer dP, bytes of the gradient's

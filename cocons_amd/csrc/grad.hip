@@ -554,6 +554,7 @@ size_t grad_scratch_doubles(int npad)
 //   dsigma_dirs_kernel   : the lower tiles of every Sigma_a from ONE evaluation of pair_partials per pair
 //   fisher_mirror_kernel : a lower triangle mirrored into a full symmetric matrix (Sigma_a in place; Sigma^-1 from the
 //                          gradient's -Sigma^-1, the sign folded in)
+//   fisher_project_kernel: (cocons_fisher_reml) Sigma^-1 -> P = Sigma^-1 - C C' in place, the rank-p downdate
 //   (the products Sigma_a Sigma^-1 run on the trailing-update kernel, launch_fisher_products)
 //   fisher_trace_kernel / fisher_trace_sum_kernel : sum_ij G_a(i, j) G_b(j, i) per 64 x 64 tile, the transposed tile through
 //                          LDS; then the tiles' partial sums in a fixed order
@@ -639,6 +640,34 @@ fisher_mirror_kernel(double *dst, size_t ldd, size_t dz, const double *src, size
     }
 }
 
+// The REML projector in place (cocons_fisher_reml): S(i, j) -= scale sum_k C(i, k) C(j, k) over every 64 x 64
+// tile of the full npad x npad matrix S = Sigma^-1, both triangles, C = Sigma^-1 X chol(X' Sigma^-1 X)^-T (npad x q, q <=
+// COCONS_P_MAX).  One streaming pass: lane = row, each wave 16 columns (as fisher_mirror_kernel), the tile's two 64-row strips
+// of C staged once in LDS, column by column (ci[k][lane]: one bank row per read; cj[k][c]: one address for the wave).  A row
+// outside the caller's sites [pad0, n) takes C as 0, so the padding keeps the bits it has.  The sum over k runs in order, and
+// entries (i, j) and (j, i) run the same products in the same order: P is symmetric to the bit where S is.
+__global__ void __launch_bounds__(256)
+fisher_project_kernel(double *S, size_t lds, const double *C, size_t ldc, int q, int pad0, int n, double scale)
+{
+    __shared__ double ci[COCONS_P_MAX][GTS], cj[COCONS_P_MAX][GTS];
+    const int bi = blockIdx.x, bj = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ri = bi * GTS + lane, rj = bj * GTS + lane;
+    for (int k = wave; k < q; k += 4) {
+        ci[k][lane] = (ri >= pad0 && ri < n) ? C[(size_t)ri + (size_t)k * ldc] : 0.0;
+        cj[k][lane] = (rj >= pad0 && rj < n) ? C[(size_t)rj + (size_t)k * ldc] : 0.0;
+    }
+    __syncthreads();
+    double acc[GTS / 4];
+    for (int cc = 0; cc < GTS / 4; ++cc) acc[cc] = 0.0;
+    for (int k = 0; k < q; ++k) {
+        const double a = ci[k][lane];
+        for (int cc = 0; cc < GTS / 4; ++cc) acc[cc] = fma(a, cj[k][wave * (GTS / 4) + cc], acc[cc]);
+    }
+    double *col = S + (size_t)ri + (size_t)(bj * GTS + wave * (GTS / 4)) * lds;
+    for (int cc = 0; cc < GTS / 4; ++cc) col[(size_t)cc * lds] -= scale * acc[cc];
+}
+
 // Workgroup (bi, bj, a): part[((a ndir + b) T + bj) T + bi] = sum over the tile of G_a(i, j) G_b(j, i) for every b >= a.
 // The tile of G_a stays in registers; tile (bj, bi) of each G_b goes through LDS so that both reads are coalesced.
 __global__ void __launch_bounds__(256)
@@ -722,6 +751,13 @@ void launch_fisher_mirror(double *dst, size_t ldd, size_t dz, const double *src,
 {
     const int T = npad / GTS;
     hipLaunchKernelGGL(fisher_mirror_kernel, dim3(T, T, count), dim3(256), 0, s, dst, ldd, dz, src, lds, sz, sign);
+}
+
+void launch_fisher_project(double *S, size_t lds, const double *C, size_t ldc, int q, int pad0, int n, int npad, double scale,
+                           hipStream_t s)
+{
+    const int T = npad / GTS;
+    hipLaunchKernelGGL(fisher_project_kernel, dim3(T, T), dim3(256), 0, s, S, lds, C, ldc, q, pad0, n, scale);
 }
 
 void launch_fisher_dirs(int mode, const GradArgs &g, int ndir, const double *dirs, double *w, double *D, size_t ldd,

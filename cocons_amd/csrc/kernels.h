@@ -328,6 +328,10 @@ void launch_matern_grad_points(int n, const double *nu, const double *u, double 
 // tile pairs of `count` matrices (dz / sz elements apart): dst = sign * (the lower triangle of src, mirrored); dst may be src
 void launch_fisher_mirror(double *dst, size_t ldd, size_t dz, const double *src, size_t lds, size_t sz, int npad, int count,
                           double sign, hipStream_t s);
+// (cocons_fisher_reml) S (npad x npad, symmetric in full) -= scale C C' in place, C npad x q (q <=
+// COCONS_P_MAX); rows of C outside the caller's sites [pad0, n) count as 0.  Fixed order, symmetric to the bit where S is.
+void launch_fisher_project(double *S, size_t lds, const double *C, size_t ldc, int q, int pad0, int n, int npad, double scale,
+                           hipStream_t s);
 // Sigma_a = sum_tk dirs[a][t, k] dSigma/dtheta[t, k] for the ndir directions (device, ndir x 6 p in theta's table layout), in
 // full, at D + a dstride; g: the gradient's site and pair arguments (loc, site, X, gr, nu_fixed, smooth_free); w: ndir x 6 x npad
 void launch_fisher_dirs(int mode, const GradArgs &g, int ndir, const double *dirs, double *w, double *D, size_t ldd,

@@ -319,6 +319,17 @@ class CoconsFit:
         _lib.check(self._L.cocons_fisher_dense(self._h, _p(T), nd, _p(D), _p(info), _p(info_mean)), "cocons_fisher_dense")
         return info, info_mean
 
+    def fisher_reml_core(self, theta_list, dirs):
+        """Expected information of the REML fit at `theta_list` (cocons_fisher_reml), `dirs` as for `fisher_core`:
+        info ndir x ndir = (r / 2) tr(P Sigma_a P Sigma_b), P = Sigma^-1 - Sigma^-1 X (X' Sigma^-1 X)^-1 X' Sigma^-1.
+        There is no mean block."""
+        T = theta_table(theta_list)
+        D = np.ascontiguousarray(np.asarray(dirs, dtype=np.float64).reshape(-1, 6 * self.p))
+        nd = D.shape[0]
+        info = np.zeros((nd, nd))
+        _lib.check(self._L.cocons_fisher_reml(self._h, _p(T), nd, _p(D), _p(info)), "cocons_fisher_reml")
+        return info
+
     def neg2loglik_batch_core(self, theta_lists):
         """Independent evaluations pipelined on the GPU (cocons_neg2loglik_batch).  Returns
         (values, status) arrays; status k > 0 marks a Cholesky failure at minor k."""
@@ -836,6 +847,27 @@ def getFisher_dense(par, par_pos, locs, x_covariates, smooth_limits, z, n, fit=N
         if cov.size:
             info[np.ix_(cov, cov)] += sub
         return info
+    finally:
+        if own:
+            f.close()
+
+
+def getFisher_reml(par, par_pos, locs, x_covariates, x_betas, smooth_limits, z, n, fit=None):
+    """The P x P expected information of the REML fit in the optimiser's coordinates, rows and columns in `par`'s order,
+    from ONE factorisation (cocons_fisher_reml): (r / 2) tr(P Sigma_a P Sigma_b) with the REML projector P, the expected
+    Hessian of half of what `GetNeg2loglikelihoodREML` returns, without the penalty.  The reference has no counterpart
+    (getHessian stops for reml objects); solve() of the result is the inv.hess of getCIs / getModHess.
+
+    `x_betas` is accepted and unused, as in `GetNeg2loglikelihoodREML`.  REML has no mean parameters: a free entry of
+    `par_pos["mean"]` raises ValueError.  A failing Cholesky raises CholeskyError."""
+    par = np.asarray(par, dtype=np.float64).ravel()
+    tl = getModelLists(par, par_pos, "diff")
+    Jt, Jm = fisher_jacobian(par, par_pos)
+    if np.any(Jm != 0):
+        raise ValueError("getFisher_reml: par_pos has a free mean entry; the REML objective has no mean parameters")
+    f, own = _with_fit(fit, locs, x_covariates, z, smooth_limits)
+    try:
+        return f.fisher_reml_core(tl, Jt)
     finally:
         if own:
             f.close()

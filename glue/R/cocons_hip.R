@@ -87,6 +87,24 @@ GetNeg2loglikelihood <- function(theta, par.pos, locs, x_covariates, smooth.limi
   info
 }
 
+# expected information of the REML fit over theta (cocons_fisher_reml), P x P in theta's order, from one factorisation:
+# (r / 2) tr(P Sigma_a P Sigma_b) with the REML projector P (INTEGRATION.md).  solve() of it is the inv.hess of getCIs /
+# getModHess for a reml object; the reference has no counterpart.  REML has no mean parameters: par.pos$mean holds no free
+# entry.  NULL after a failing Cholesky under safe.
+.cocons.hip.fisher_reml <- function(fit, theta, par.pos, safe = TRUE) {
+  aspects <- c("std.dev", "scale", "aniso", "tilt", "smooth", "nugget")
+  base <- cocons::getModelLists(theta = theta, par.pos = par.pos, type = "diff")
+  p <- length(base$mean)
+  flat <- function(tl) c(tl$mean, unlist(tl[aspects], use.names = FALSE))
+  J <- vapply(seq_along(theta), function(a) {
+    e <- theta
+    e[a] <- e[a] + 1
+    flat(cocons::getModelLists(theta = e, par.pos = par.pos, type = "diff")) - flat(base)
+  }, numeric(7 * p))
+  if (any(J[seq_len(p), ] != 0)) stop("par.pos has a free mean entry; the REML objective has no mean parameters")
+  .cocons.hip.result(.Call(`_cocons_hip_fisher_reml`, fit, base[-1], J[-seq_len(p), , drop = FALSE]), safe)
+}
+
 # derivative of sumsmoothlone (src/cocons_full.cpp:12-30) per element: sign(x) off the smooth branch, tanh(alpha x / 2) on it
 .cocons.hip.dsumsmoothlone <- function(x, lambda, alpha = 1e6) {
   lambda * ifelse(abs(x) > 1e-4, sign(x), tanh(alpha * x / 2))

@@ -419,6 +419,26 @@ SEXP _cocons_hip_fisher(SEXP fitp, SEXP theta, SEXP dirs)
     return out;
 }
 
+/* expected information of the REML fit (cocons_fisher_reml): dirs as for _cocons_hip_fisher; list(status, info ndir x ndir).
+ * There is no mean block. */
+SEXP _cocons_hip_fisher_reml(SEXP fitp, SEXP theta, SEXP dirs)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp);
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    if (!Rf_isReal(dirs) || !Rf_isMatrix(dirs) || Rf_nrows(dirs) != 6 * p)
+        Rf_error("dirs must be a double matrix with %d rows (one direction per column)", 6 * p);
+    const int nd = Rf_ncols(dirs);
+    SEXP info = PROTECT(Rf_allocMatrix(REALSXP, nd, nd));
+    for (R_xlen_t e = 0; e < XLENGTH(info); ++e) REAL(info)[e] = 0.0;
+    int rc = cocons_fisher_reml(f, T, nd, REAL(dirs), REAL(info));     /* (symmetric) */
+    hip_check(rc, "expected information (reml)");
+    SEXP out = status_value(rc, info);
+    UNPROTECT(1);
+    return out;
+}
+
 /* the same with its parts: list(status, c(sum_logliks, logdet_half, quad_1 .. quad_r)) -- what
  * GetNeg2loglikelihoodTaperProfile (R/neg2loglikelihood.R:98-106) is formed from on a taper handle */
 SEXP _cocons_hip_neg2loglik_parts(SEXP fitp, SEXP theta, SEXP mean)
@@ -808,6 +828,7 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_neg2loglik", (DL_FUNC)&_cocons_hip_neg2loglik, 3},
     {"_cocons_hip_neg2loglik_grad", (DL_FUNC)&_cocons_hip_neg2loglik_grad, 3},
     {"_cocons_hip_fisher", (DL_FUNC)&_cocons_hip_fisher, 3},
+    {"_cocons_hip_fisher_reml", (DL_FUNC)&_cocons_hip_fisher_reml, 3},
     {"_cocons_hip_neg2loglik_batch", (DL_FUNC)&_cocons_hip_neg2loglik_batch, 3},
     {"_cocons_hip_neg2loglik_profile", (DL_FUNC)&_cocons_hip_neg2loglik_profile, 2},
     {"_cocons_hip_neg2loglik_reml", (DL_FUNC)&_cocons_hip_neg2loglik_reml, 3},

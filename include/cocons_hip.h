@@ -247,6 +247,20 @@ int cocons_neg2loglik_grad_taper(cocons_fit *fit, const double *theta, const dou
 int cocons_fisher_dense(cocons_fit *fit, const double *theta, int ndir, const double *dirs,
                         double *info, double *info_mean);
 
+/* Expected information of the REML fit at theta, from one factorisation.  With X = x_covariates, the design
+ * cocons_neg2loglik_reml profiles out, V = Sigma^-1 X, W = X' V and P = Sigma^-1 - V W^-1 V' (R/neg2loglikelihood.R:273-278),
+ *   info[a * ndir + b] = (r / 2) tr(P Sigma_a P Sigma_b),   Sigma_a and dirs as for cocons_fisher_dense:
+ * the expected Hessian of the negative restricted log-likelihood (half the objective cocons_neg2loglik_reml returns), i.e.
+ * the Fisher information of the error contrasts K' z with K' X = 0.  Positive semi-definite by construction; no mean block
+ * (REML has no mean parameters) and no penalty.  The reference has no counterpart (R/getFunctions.R:930).  info is symmetric
+ * to the bit; every sum has a fixed order, so repeated calls agree bit for bit.  0, the failing minor k > 0 of Sigma, -4 when
+ * X' Sigma^-1 X is not positive definite, or < 0 with a message that starts with the entry's name; info is written on 0 only.
+ * Refused (-1) before any device work: null arguments, ndir outside [1, 7 * COCONS_P_MAX], non-finite entries of dirs, taper
+ * and sharded handles, a handle without z, sizes beyond the product kernel's addressing.  Memory as for cocons_fisher_dense:
+ * (ndir + 2) n_pad^2 doubles and the traces' partial sums belong to the call; the handle keeps what
+ * cocons_neg2loglik_reml_grad makes it keep.                                                                              */
+int cocons_fisher_reml(cocons_fit *fit, const double *theta, int ndir, const double *dirs, double *info);
+
 /* Dense kriging core: replaces R/predict.R:136-183
  *   observed_cov <- cov_rns(...); cov_pred <- cov_rns_pred(...);
  *   inv_cov <- solve(observed_cov, t(cov_pred)); crossprod(resid, inv_cov);
