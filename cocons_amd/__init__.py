@@ -19,6 +19,8 @@ from .host import (  # noqa: F401
     GetNeg2loglikelihoodREML_grad,
     GetNeg2loglikelihood_batch,
     GetNeg2loglikelihood_grad,
+    cocoCV_dense,
+    cocoCV_sparse,
     cocoPredict_dense,
     cocoPredict_dense_chunked,
     cocoPredict_sparse,
@@ -31,9 +33,11 @@ from .host import (  # noqa: F401
     cov_rns_taper,
     cov_rns_taper_pred,
     getBetas_profile,
+    getCRPS,
     getFisher_dense,
     getFisher_reml,
     getHessian_dense,
+    getLogScore,
     getModelLists,
     getModelLists_grad,
     getPen,

@@ -309,6 +309,8 @@ cocons_fit *fit_create_impl(int n, int p, int r, int q, const double *locs,
     }
     const int pad0 = f->pad0, nint = n + pad0;
     if (pad0 > 0) f->sorted = true;
+    f->obs_pos.resize(n);
+    for (int i = 0; i < n; ++i) f->obs_pos[perm[i]] = pad0 + i;
     auto permute_pad = [&](const double *src, int ncol, bool zero_pad) {
         std::vector<double> out((size_t)nint * ncol);
         for (int c = 0; c < ncol; ++c) {

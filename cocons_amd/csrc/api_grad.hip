@@ -15,30 +15,12 @@
 // from the view's lda), keeps the objective's value: a gradient call moves nothing else on the handle.
 // leading dimension of the gradient's layout with nb rows (residuals, or Z' and Xb') in front of the unit rows; while nb <= 128
 // it does not depend on nb
-static size_t grad_lda(const cocons_fit *f, int nb)
+size_t grad_lda(const cocons_fit *f, int nb)
 {
     return (size_t)f->npad + (size_t)round_up(nb > 0 ? nb : 1, TILE) + (size_t)f->npad;
 }
 
-// f->lda / f->rhs_act in the gradient's layout while one gradient operation runs, the objective's afterwards (every way
-// out); the rows under the matrix then hold nothing the objective may rely on (border_clean unknown)
-struct GradLayout {
-    cocons_fit *f;
-    size_t lda;
-    int rhs_act;
-    GradLayout(cocons_fit *f_, int nb) : f(f_), lda(f_->lda), rhs_act(f_->rhs_act)
-    {
-        f->lda = grad_lda(f, nb);
-        f->rhs_act = (int)(f->lda - (size_t)f->npad);
-        f->border_clean = -1; f->border_pending = -1;
-    }
-    ~GradLayout()
-    {
-        f->lda = lda; f->rhs_act = rhs_act;
-        f->border_clean = -1; f->border_pending = -1;
-    }
-};
-
+// (GradLayout, fit.hpp: f->lda / f->rhs_act in this layout while one gradient operation runs)
 static int grad_refuse(cocons_fit *f, const char *who)
 {
     if (int rc = no_taper(f, who)) return rc;
@@ -93,7 +75,7 @@ static int grad_contract(cocons_fit *f, const double *theta, int rt, const doubl
 
 // everything of one gradient operation on the handle's stream (run_op repeats it after a hand-off time-out); full = false
 // stops once -Sigma^-1 is in the leading square (cocons_debug_sigma_inverse)
-static int grad_enqueue(cocons_fit *f, const double *theta, const double *mean, bool full, double *hgrad)
+int grad_enqueue(cocons_fit *f, const double *theta, const double *mean, bool full, double *hgrad)
 {
     const int npad = f->npad, nr = f->r, rt = round_up(nr > 0 ? nr : 1, TILE), p = f->p;
     hipStream_t s = f->stream;
@@ -147,7 +129,7 @@ static int profile_grad_enqueue(cocons_fit *f, const double *theta, const double
 }
 
 // nb: rows in front of the unit rows (the dense gradient's r); pcols > 0: the Profile / REML buffers for that many columns
-static int grad_prepare(cocons_fit *f, const char *who, int nb, int pcols = 0)
+int grad_prepare(cocons_fit *f, const char *who, int nb, int pcols)
 {
     const int r1 = f->r > 0 ? f->r : 1;
     if (!f->grad) {
@@ -444,7 +426,7 @@ extern "C" int cocons_debug_matern(int n, const double *nu, const double *u, dou
 // factorisation with the residuals under the matrix, the log-determinant and quadratic forms (launch_finalize, as the
 // objective), then the selected inverse on the tile envelope with the back-substitution A = L^-T (L^-1 R) in the same
 // sweep (selinv.hip), and the contraction over the stored pattern (grad.hip).
-static int taper_grad_prepare(cocons_fit *f, const char *who)
+int taper_grad_prepare(cocons_fit *f, const char *who)
 {
     if (f->tgrad) return 0;
     std::unique_ptr<TaperGradState> G(new TaperGradState());
@@ -498,7 +480,7 @@ static int taper_grad_prepare(cocons_fit *f, const char *who)
 
 // everything of one operation on the handle's stream (run_op repeats it after a hand-off time-out); hgrad = null stops once
 // Z = S^-1 is complete (cocons_debug_taper_selinv)
-static int taper_grad_enqueue(cocons_fit *f, const double *theta, const double *mean, double *hgrad)
+int taper_grad_enqueue(cocons_fit *f, const double *theta, const double *mean, double *hgrad)
 {
     const int npad = f->npad, nr = f->r, p = f->p;
     hipStream_t s = f->stream;

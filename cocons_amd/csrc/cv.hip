@@ -1,0 +1,252 @@
+// cv.hip -- cross-validated predictions from the inverse covariance.
+//
+// With K = Sigma^-1 and U = K R, a held-out set B predicts as  R_B - E[R_B | R_A] = (K_BB)^-1 U_B  with covariance (K_BB)^-1.
+// The gradient's factorisation leaves -K in the lower triangle of the leading square and U in a buffer of its own; the kernels
+// here read them and write results in the handle's internal order:
+//   cv_loo_kernel     one observation per thread: var = 1 / K_ii, resid = U_i var
+//   cv_fold_kernel    one workgroup per fold of 2 .. 128 observations, the block in LDS: gather, C C' = K_BB, W = C^-1
+//                     (its transpose into the upper triangle the factor does not use), var_i = sum_j W_ji^2,
+//                     resid = W' (W U_B) -- every sum in a fixed order, no atomics
+//   cv_gather_kernel  a larger fold's bordered matrix [K_BB ; U_B' ; I] for the library's own factorisation
+//   cv_scatter_kernel its results back to the observations' positions
+//   cv_taper_kernel   leave-one-out from the diagonal of the selected inverse (taper handles)
+// The only atomic is the record of a failing fold (atomicMin of its label, as the factorisation's info word).
+#include "kernels.h"
+#include <atomic>
+
+namespace cocons {
+
+__global__ void __launch_bounds__(256)
+cv_loo_kernel(const double *S, size_t lds, const double *U, size_t ldu, int nr, const int *idx, const int *lab, int first,
+              int count, double *var, double *res, size_t ldr, int *fail)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    const int i = idx ? idx[t] : first + t;
+    const double k = -S[(size_t)i + (size_t)i * lds];
+    if (!(k > 0.0) || !isfinite(k)) atomicMin(fail, lab ? lab[t] : t);
+    const double v = 1.0 / k;
+    var[i] = v;
+    for (int c = 0; c < nr; ++c) res[(size_t)i + (size_t)c * ldr] = U[(size_t)i + (size_t)c * ldu] * v;
+}
+
+void launch_cv_loo(const double *S, size_t lds, const double *U, size_t ldu, int nr, const int *idx, const int *lab, int first,
+                   int count, double *var, double *res, size_t ldr, int *fail, hipStream_t s)
+{
+    if (count <= 0) return;
+    hipLaunchKernelGGL(cv_loo_kernel, dim3((count + 255) / 256), dim3(256), 0, s, S, lds, U, ldu, nr, idx, lab, first, count, var,
+                       res, ldr, fail);
+}
+
+// One workgroup of 256 threads per fold; BP = 16, 32, 64, 128 sizes the LDS (the arithmetic runs over the fold's own b and
+// does not depend on BP).  LDS: the block with an odd leading dimension BP + 1 (rows and columns both without bank conflicts),
+// the inverse pivots, and G = 256 / BP right-hand sides and intermediate vectors at a time.
+//   lower triangle  K_BB, then its factor C (the diagonal is not stored: dinv = 1 / C_jj)
+//   upper triangle  W' = C^-T: W(k, j), k > j, at (j, k); thread j forms column j of W by forward substitution and reads and
+//                   writes row j of the upper triangle only, so the inversion needs no barrier
+struct CvFoldArgs {
+    const double *S; size_t lds;
+    const double *U; size_t ldu; int nr;
+    const int *idx, *off, *flist, *lab;
+    double *var, *res; size_t ldr;
+    int *fail;
+};
+
+template <int BP> __global__ void __launch_bounds__(256)
+cv_fold_kernel(CvFoldArgs a)
+{
+    extern __shared__ double cv_lds[];
+    constexpr int LD = BP + 1, G = 256 / BP;
+    double *M = cv_lds, *dinv = M + (size_t)LD * BP, *ub = dinv + BP, *yb = ub + 256;
+    const int f = a.flist[blockIdx.x];
+    const int *pos = a.idx + a.off[f];
+    const int b = a.off[f + 1] - a.off[f];
+    const int tid = threadIdx.x, i = tid % BP, g = tid / BP;
+    if (b < 1 || b > BP) return;                       // (the host's size classes: never)
+    // gather: K(i, j) = -S(max, min); positions ascend inside a fold, so row >= column is the stored triangle
+    for (int e = tid; e < b * b; e += 256) {
+        const int rr = e % b, cc = e / b;
+        if (rr >= cc) M[rr + cc * LD] = -a.S[(size_t)pos[rr] + (size_t)pos[cc] * a.lds];
+    }
+    // C C' = K_BB, right-looking, column by column
+    bool bad = false;
+    for (int j = 0; j < b; ++j) {
+        __syncthreads();
+        double d = M[j + j * LD];
+        if (!(d > 0.0) || !isfinite(d)) { bad = true; d = 1.0; }
+        const double piv = sqrt(d);
+        if (tid == 0) dinv[j] = 1.0 / piv;
+        if (g == 0 && i > j && i < b) M[i + j * LD] /= piv;
+        __syncthreads();
+        if (i > j && i < b) {
+            const double lij = M[i + j * LD];
+            for (int c = j + 1 + g; c <= i; c += G) M[i + c * LD] -= lij * M[c + j * LD];
+        }
+    }
+    __syncthreads();
+    // W = C^-1: W(r, j) = -(sum_{k = r-1 .. j} C(r, k) W(k, j)) / C(r, r), W(j, j) = 1 / C(j, j)
+    if (tid < b) {
+        const int j = tid;
+        const double wjj = dinv[j];
+        for (int r = j + 1; r < b; ++r) {
+            double s = 0.0;
+            for (int k = r - 1; k > j; --k) s += M[r + k * LD] * M[j + k * LD];
+            s += M[r + j * LD] * wjj;
+            M[j + r * LD] = -s * dinv[r];
+        }
+        // var_j = sum_{k >= j} W(k, j)^2
+        double v = wjj * wjj;
+        for (int k = j + 1; k < b; ++k) v += M[j + k * LD] * M[j + k * LD];
+        a.var[pos[j]] = v;
+    }
+    // resid = W' (W U_B), G realisations at a time
+    for (int c0 = 0; c0 < a.nr; c0 += G) {
+        const int c = c0 + g;
+        const bool on = c < a.nr && i < b;
+        __syncthreads();
+        if (on) ub[g * BP + i] = a.U[(size_t)pos[i] + (size_t)c * a.ldu];
+        __syncthreads();
+        if (on) {
+            double y = 0.0;
+            for (int k = 0; k < i; ++k) y += M[k + i * LD] * ub[g * BP + k];      // W(i, k) at (k, i)
+            y += dinv[i] * ub[g * BP + i];
+            yb[g * BP + i] = y;
+        }
+        __syncthreads();
+        if (on) {
+            double e = dinv[i] * yb[g * BP + i];
+            for (int k = i + 1; k < b; ++k) e += M[i + k * LD] * yb[g * BP + k];  // W(k, i) at (i, k)
+            a.res[(size_t)pos[i] + (size_t)c * a.ldr] = e;
+        }
+    }
+    if (bad && tid == 0) atomicMin(a.fail, a.lab[f]);
+}
+
+template <int BP> static hipError_t cv_fold_launch(const CvFoldArgs &a, int nfolds, hipStream_t s)
+{
+    const size_t shm = ((size_t)(BP + 1) * BP + BP + 512) * sizeof(double);
+    // the attribute that allows more than 64 KB of dynamic LDS is per kernel and device: set once per device, not per launch
+    // (the mask is this class's own: a template's static)
+    static std::atomic<unsigned long long> attr_done{0};
+    if (shm > 64 * 1024) {
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        if (!(dev >= 0 && dev < 64 && ((attr_done.load(std::memory_order_relaxed) >> dev) & 1ull))) {
+            if (hipError_t e = hipFuncSetAttribute((const void *)cv_fold_kernel<BP>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                   (int)shm))
+                return e;
+            if (dev >= 0 && dev < 64) attr_done.fetch_or(1ull << dev, std::memory_order_relaxed);
+        }
+    }
+    hipLaunchKernelGGL(cv_fold_kernel<BP>, dim3(nfolds), dim3(256), shm, s, a);
+    return hipSuccess;
+}
+
+hipError_t launch_cv_folds(int cls, const double *S, size_t lds, const double *U, size_t ldu, int nr, const int *idx,
+                           const int *off, const int *flist, const int *lab, int nfolds, double *var, double *res, size_t ldr,
+                           int *fail, hipStream_t s)
+{
+    if (nfolds <= 0) return hipSuccess;
+    CvFoldArgs a{S, lds, U, ldu, nr, idx, off, flist, lab, var, res, ldr, fail};
+    switch (cls) {
+    case 16: return cv_fold_launch<16>(a, nfolds, s);
+    case 32: return cv_fold_launch<32>(a, nfolds, s);
+    case 64: return cv_fold_launch<64>(a, nfolds, s);
+    case 128: return cv_fold_launch<128>(a, nfolds, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+__global__ void __launch_bounds__(256)
+cv_gather_kernel(const double *S, size_t lds, const double *U, size_t ldu, int nr, const int *pos, int b, int bpad, int rt,
+                 double *out, size_t ldo)
+{
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= ldo * (size_t)bpad) return;
+    const int rr = (int)(e % ldo), c = (int)(e / ldo);
+    double v;
+    if (rr < bpad) {
+        if (rr < b && c < b) {
+            const int hi = rr >= c ? pos[rr] : pos[c], lo = rr >= c ? pos[c] : pos[rr];
+            v = -S[(size_t)hi + (size_t)lo * lds];
+        } else
+            v = rr == c ? 1.0 : 0.0;
+    } else if (rr < bpad + rt) {
+        const int k = rr - bpad;
+        v = (k < nr && c < b) ? U[(size_t)pos[c] + (size_t)k * ldu] : 0.0;
+    } else
+        v = rr - bpad - rt == c ? 1.0 : 0.0;
+    out[(size_t)rr + (size_t)c * ldo] = v;
+}
+
+void launch_cv_gather(const double *S, size_t lds, const double *U, size_t ldu, int nr, const int *pos, int b, int bpad, int rt,
+                      double *out, size_t ldo, hipStream_t s)
+{
+    hipLaunchKernelGGL(cv_gather_kernel, dim3((unsigned)((ldo * (size_t)bpad + 255) / 256)), dim3(256), 0, s, S, lds, U, ldu, nr, pos, b, bpad,
+                       rt, out, ldo);
+}
+
+__global__ void __launch_bounds__(256)
+cv_scatter_kernel(const int *pos, int b, int nr, const double *v, const double *r, double *var, double *res, size_t ldr)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= b) return;
+    const int o = pos[i];
+    var[o] = v[i];
+    for (int k = 0; k < nr; ++k) res[(size_t)o + (size_t)k * ldr] = r[(size_t)i + (size_t)k * b];
+}
+
+void launch_cv_scatter(const int *pos, int b, int nr, const double *v, const double *r, double *var, double *res, size_t ldr,
+                       hipStream_t s)
+{
+    if (b <= 0) return;
+    hipLaunchKernelGGL(cv_scatter_kernel, dim3((b + 255) / 256), dim3(256), 0, s, pos, b, nr, v, r, var, res, ldr);
+}
+
+__global__ void cv_info_take_kernel(int *info, int clean, int *keep, int *fail, int label)
+{
+    if (threadIdx.x || blockIdx.x) return;
+    const int v = *info;
+    if (keep) *keep = v;
+    else if (v != clean) atomicMin(fail, label);
+    *info = clean;
+}
+
+__global__ void cv_info_put_kernel(int *info, const int *keep)
+{
+    if (threadIdx.x || blockIdx.x) return;
+    *info = *keep;
+}
+
+void launch_cv_info_take(int *info, int clean, int *keep, int *fail, int label, hipStream_t s)
+{
+    hipLaunchKernelGGL(cv_info_take_kernel, dim3(1), dim3(64), 0, s, info, clean, keep, fail, label);
+}
+
+void launch_cv_info_put(int *info, const int *keep, hipStream_t s)
+{
+    hipLaunchKernelGGL(cv_info_put_kernel, dim3(1), dim3(64), 0, s, info, keep);
+}
+
+__global__ void __launch_bounds__(256)
+cv_taper_kernel(const double *Z, size_t ldz, int skew, int npad, int n, const double *U, size_t ldu, int nr, double *var,
+                double *res, size_t ldr, int *fail)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double k = Z[band_index(i, i, ldz, skew, npad)];
+    if (!(k > 0.0) || !isfinite(k)) atomicMin(fail, i);
+    const double v = 1.0 / k;
+    var[i] = v;
+    for (int c = 0; c < nr; ++c) res[(size_t)i + (size_t)c * ldr] = U[(size_t)i + (size_t)c * ldu] * v;
+}
+
+void launch_cv_taper(const double *Z, size_t ldz, int skew, int npad, int n, const double *U, size_t ldu, int nr, double *var,
+                     double *res, size_t ldr, int *fail, hipStream_t s)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(cv_taper_kernel, dim3((n + 255) / 256), dim3(256), 0, s, Z, ldz, skew, npad, n, U, ldu, nr, var, res, ldr,
+                       fail);
+}
+
+}  // namespace cocons

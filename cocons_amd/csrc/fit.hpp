@@ -1,4 +1,4 @@
-// fit.hpp -- internal to the C ABI's translation units (api.hip, api_shard.hip, api_predict.hip, api_grad.hip): error reporting,
+// fit.hpp -- internal to the C ABI's translation units (api.hip, api_shard.hip, api_predict.hip, api_grad.hip, api_cv.hip): error reporting,
 // the owned device buffer, the fit handle with the states it owns, and the declarations of what api.hip -- the path of one
 // objective evaluation, the handle's life, the schedules -- offers the other three.  Not installed, not part of the contract
 // (include/cocons_hip.h is).  Everything declared here is hidden from the library's dynamic symbol table; a variable or a
@@ -301,6 +301,9 @@ struct cocons_fit {
                                   // `skew` (= taper_maxband) tile rows from its diagonal tile down plus the rows under the
                                   // matrix -- O(n x bandwidth) doubles instead of n^2
     std::vector<int> taper_inv;   // position of the caller's observation i in the handle's order (reverse Cuthill-McKee)
+    std::vector<int> obs_pos;     // internal position (behind the front padding, in Morton order) of the caller's observation i,
+                                  // kept by every handle fit_create_impl makes (n ints); read by cocons_cv_dense, which maps labels
+                                  // in and results out through it (a taper handle's order on top of it is taper_inv)
     std::vector<int> h_trp, h_tci;     // host copy of the full (symmetric) pattern and taper entries in the handle's order:
     std::vector<double> h_tval;        // what a twin in another order is built from (O(nnz))
     cocons_fit *taper_twin = nullptr;  // lazily created taper handle in the order of the last pivot cocons_sim_taper was given
@@ -451,6 +454,34 @@ int profile_tail(cocons_fit *f, int nxb, double n_eff, bool reml, double *sum_lo
 int sharded_eval(cocons_fit *f, const double *theta, const double *mean, double *sum_logliks, double *parts);
 void shard_events_destroy(ShardState *S);
 void rccl_comm_destroy(ncclComm_t c);
+
+// ... what api_grad.hip offers api_cv.hip (defined and described there): one gradient operation up to -Sigma^-1 in the leading
+// square and Sigma^-1 R in grad->AR (grad_enqueue with full = false), S^-1 on the envelope and S^-1 R in tgrad->AR
+// (taper_grad_enqueue with hgrad = null), and the buffers and the layout they run in
+size_t grad_lda(const cocons_fit *f, int nb);
+int grad_prepare(cocons_fit *f, const char *who, int nb, int pcols = 0);
+int grad_enqueue(cocons_fit *f, const double *theta, const double *mean, bool full, double *hgrad);
+int taper_grad_prepare(cocons_fit *f, const char *who);
+int taper_grad_enqueue(cocons_fit *f, const double *theta, const double *mean, double *hgrad);
+
+// f->lda / f->rhs_act in the gradient's layout while one gradient operation runs, the objective's afterwards (every way
+// out); the rows under the matrix then hold nothing the objective may rely on (border_clean unknown)
+struct GradLayout {
+    cocons_fit *f;
+    size_t lda;
+    int rhs_act;
+    GradLayout(cocons_fit *f_, int nb) : f(f_), lda(f_->lda), rhs_act(f_->rhs_act)
+    {
+        f->lda = grad_lda(f, nb);
+        f->rhs_act = (int)(f->lda - (size_t)f->npad);
+        f->border_clean = -1; f->border_pending = -1;
+    }
+    ~GradLayout()
+    {
+        f->lda = lda; f->rhs_act = rhs_act;
+        f->border_clean = -1; f->border_pending = -1;
+    }
+};
 
 // One operation of a one-shot entry that factors on the handle: enqueue() puts everything of it but the info words on the
 // handle's stream (assembly, factorisation, the entry's own kernels and result copies; 0 or an error); it is run again after a

@@ -384,4 +384,33 @@ struct TaperGradArgs {
 };
 void launch_taper_grad(int mode, const TaperGradArgs &g, hipStream_t s);
 
+// ---- cross-validated predictions (cv.hip) ---------------------------------------------------------------------
+// S: -Sigma^-1 in the lower triangle (launch_grad_syrk), so K(i, j) = -S(max, min); U = Sigma^-1 R (npad x nr, ld ldu).  Results
+// go out in the handle's internal order: var[i], res[i + k ldr].  fail: one word, INT_MAX beforehand, atomicMin of the label of
+// a fold whose block has a pivot that is not positive and finite.
+constexpr int CV_SMALL_MAX = 128;  // largest fold the LDS kernel takes
+// closed form for single observations: positions idx[0 .. count) (idx = null: first + t); the label recorded on failure is
+// lab[t] (lab = null: t)
+void launch_cv_loo(const double *S, size_t lds, const double *U, size_t ldu, int nr, const int *idx, const int *lab, int first,
+                   int count, double *var, double *res, size_t ldr, int *fail, hipStream_t s);
+// folds of 2 .. CV_SMALL_MAX observations, one workgroup each: fold flist[g] holds the positions idx[off[f] .. off[f + 1]),
+// ascending; cls = 16, 32, 64 or 128 >= the largest of these folds sizes the LDS of the launch
+hipError_t launch_cv_folds(int cls, const double *S, size_t lds, const double *U, size_t ldu, int nr, const int *idx,
+                           const int *off, const int *flist, const int *lab, int nfolds, double *var, double *res, size_t ldr,
+                           int *fail, hipStream_t s);
+// a large fold's bordered matrix (ld ldo = 2 bpad + rt rows, bpad columns): K_BB identity-padded to bpad, under it rt rows with
+// U_B' (nr of them, the rest zero), then bpad unit rows
+void launch_cv_gather(const double *S, size_t lds, const double *U, size_t ldu, int nr, const int *pos, int b, int bpad, int rt,
+                      double *out, size_t ldo, hipStream_t s);
+// var[pos[i]] = v[i], res[pos[i] + k ldr] = r[i + k b]
+void launch_cv_scatter(const int *pos, int b, int nr, const double *v, const double *r, double *var, double *res, size_t ldr,
+                       hipStream_t s);
+// between the factorisations of one call: a failing minor in *info (anything but `clean`) is taken out -- into *keep when keep
+// is given (Sigma's own), else as atomicMin(*fail, label) -- and *info is `clean` again; put: *info = *keep
+void launch_cv_info_take(int *info, int clean, int *keep, int *fail, int label, hipStream_t s);
+void launch_cv_info_put(int *info, const int *keep, hipStream_t s);
+// taper handles: the diagonal of Z = S^-1 (band_index layout) and AR = S^-1 R
+void launch_cv_taper(const double *Z, size_t ldz, int skew, int npad, int n, const double *U, size_t ldu, int nr, double *var,
+                     double *res, size_t ldr, int *fail, hipStream_t s);
+
 }  // namespace cocons

@@ -330,6 +330,24 @@ class CoconsFit:
         _lib.check(self._L.cocons_fisher_reml(self._h, _p(T), nd, _p(D), _p(info)), "cocons_fisher_reml")
         return info
 
+    def cv_core(self, theta_list, fold=None):
+        """Cross-validated predictions from one factorisation (cocons_cv_dense).  `fold`: n integer labels in [0, nfold)
+        (None: leave-one-out).  Returns (resid n x r = z minus its prediction from the observations outside the fold,
+        var n = the predictive variance, nugget included)."""
+        T = theta_table(theta_list)
+        mean = np.ascontiguousarray(np.asarray(theta_list["mean"], dtype=np.float64))
+        resid = np.zeros((self.n, self.r), order="F")
+        var = np.zeros(self.n)
+        if fold is None:
+            nfold, fp = 0, None
+        else:
+            lab = np.ascontiguousarray(np.asarray(fold).ravel(), dtype=np.int32)
+            if lab.size != self.n:
+                raise ValueError("fold must have length n")
+            nfold, fp = (int(lab.max()) + 1 if lab.size and lab.max() >= 0 else 1), _ip(lab)
+        _lib.check(self._L.cocons_cv_dense(self._h, _p(T), _p(mean), nfold, fp, _p(resid), _p(var)), "cocons_cv_dense")
+        return resid, var
+
     def neg2loglik_batch_core(self, theta_lists):
         """Independent evaluations pipelined on the GPU (cocons_neg2loglik_batch).  Returns
         (values, status) arrays; status k > 0 marks a Cholesky failure at minor k."""
@@ -510,6 +528,16 @@ class CoconsTaperFit(CoconsFit):
                    "cocons_neg2loglik_grad_taper")
         return val.value, parts, gt, gq, gm
 
+    def cv_core(self, theta_list):
+        """Leave-one-out predictions of the tapered model from the selected inverse (cocons_cv_taper): (resid n x r, var n)
+        as `CoconsFit.cv_core` gives them."""
+        T = theta_table(theta_list)
+        mean = np.ascontiguousarray(np.asarray(theta_list["mean"], dtype=np.float64))
+        resid = np.zeros((self.n, self.r), order="F")
+        var = np.zeros(self.n)
+        _lib.check(self._L.cocons_cv_taper(self._h, _p(T), _p(mean), _p(resid), _p(var)), "cocons_cv_taper")
+        return resid, var
+
     def predict_core(self, theta_list, locs_pred, x_covariates_pred, pred_taper, z_col=0):
         """(stochastic, quadform) of the sparse branch of cocoPredict; pred_taper = (colindices, rowpointers,
         entries) of the m x n taper between prediction and observed locations (1-based CSR)."""
@@ -589,6 +617,56 @@ def cocoPredict_sparse(theta_list, locs, newlocs, X_std, X_pred_std, smooth_limi
     neg = unc < 1e-10
     unc[neg] = np.abs(unc[neg])                                                            # :269-271
     return {"systematic": systematic, "stochastic": st, "sd.pred": np.sqrt(unc)}
+
+
+def _cv_result(f, z, resid, var):
+    z = np.asarray(z, dtype=np.float64).reshape(f.n, -1)
+    return {"mean.pred": z - resid, "sd.pred": np.sqrt(var), "resid": resid}
+
+
+def cocoCV_dense(theta_list, locs, X_std, smooth_limits, z, fold=None, fit=None):
+    """Cross-validated predictions of the dense model at `theta_list` from ONE factorisation (cocons_cv_dense) instead of
+    one fit per fold.  `fold`: one label of any kind per observation (None: leave-one-out).  Returns `mean.pred` (n x r:
+    every observation predicted from the observations outside its fold), `sd.pred` (n, nugget included) and
+    `resid` = z - mean.pred -- what getLogScore / getCRPS take.  A failing Cholesky raises CholeskyError."""
+    lab = None if fold is None else np.unique(np.asarray(fold).ravel(), return_inverse=True)[1]
+    f, own = (fit, False) if fit is not None else (CoconsFit(locs, X_std, z, smooth_limits), True)
+    try:
+        resid, var = f.cv_core(theta_list, lab)
+        return _cv_result(f, z, resid, var)
+    finally:
+        if own:
+            f.close()
+
+
+def cocoCV_sparse(theta_list, locs, X_std, smooth_limits, z, ref_taper, fit=None):
+    """Leave-one-out predictions of the tapered model (cocons_cv_taper); `ref_taper` = (colindices, rowpointers, entries).
+    Returns what `cocoCV_dense` returns."""
+    f, own = (fit, False) if fit is not None else (CoconsTaperFit(locs, X_std, z, smooth_limits, *ref_taper), True)
+    try:
+        resid, var = f.cv_core(theta_list)
+        return _cv_result(f, z, resid, var)
+    finally:
+        if own:
+            f.close()
+
+
+def _pnorm(x):
+    from math import erf
+    return 0.5 * (1.0 + np.vectorize(erf)(np.asarray(x, dtype=np.float64) / np.sqrt(2.0)))
+
+
+def getLogScore(z_pred, mean_pred, sd_pred):
+    """R/getFunctions.R:100-104: the logarithmic score of Gaussian predictions, elementwise."""
+    z, m, s = (np.asarray(a, dtype=np.float64) for a in (z_pred, mean_pred, sd_pred))
+    return (np.log(2 * np.pi) + ((z - m) / s) ** 2) / 2 + np.log(s)
+
+
+def getCRPS(z_pred, mean_pred, sd_pred):
+    """R/getFunctions.R:117-124: the continuous ranked probability score of Gaussian predictions, elementwise."""
+    z, m, s = (np.asarray(a, dtype=np.float64) for a in (z_pred, mean_pred, sd_pred))
+    t = (m - z) / s
+    return s * (t * (2 * _pnorm(t) - 1) + 2 * np.exp(-0.5 * t * t) / np.sqrt(2 * np.pi) - 1 / np.sqrt(np.pi))
 
 
 def GetNeg2loglikelihoodTaper(theta, par_pos, ref_taper, locs, x_covariates, smooth_limits, z, n, lam, safe=True,

@@ -105,6 +105,24 @@ GetNeg2loglikelihood <- function(theta, par.pos, locs, x_covariates, smooth.limi
   .cocons.hip.result(.Call(`_cocons_hip_fisher_reml`, fit, base[-1], J[-seq_len(p), , drop = FALSE]), safe)
 }
 
+# cross-validated predictions at theta_list from ONE factorisation (cocons_cv_dense): every observation predicted from the
+# observations outside its fold.  fold: one label of any kind per observation (NULL: leave-one-out).  list(resid = z minus
+# its prediction, n x r; var = the predictive variance, nugget included); NULL after a failing Cholesky under safe.
+# INTEGRATION.md shows a cross-validated CRPS built on it.
+.cocons.hip.cv <- function(fit, theta_list, fold = NULL, safe = TRUE) {
+  if (!is.null(fold)) fold <- match(fold, unique(fold)) - 1L
+  res <- .cocons.hip.result(.Call(`_cocons_hip_cv`, fit, theta_list[-1], theta_list$mean, fold), safe)
+  if (is.null(res)) return(NULL)
+  list(resid = res[[1]], var = res[[2]])
+}
+
+# the same, leave-one-out, for the tapered model on a taper handle (cocons_cv_taper)
+.cocons.hip.cv.taper <- function(fit, theta_list, safe = TRUE) {
+  res <- .cocons.hip.result(.Call(`_cocons_hip_cv_taper`, fit, theta_list[-1], theta_list$mean), safe)
+  if (is.null(res)) return(NULL)
+  list(resid = res[[1]], var = res[[2]])
+}
+
 # derivative of sumsmoothlone (src/cocons_full.cpp:12-30) per element: sign(x) off the smooth branch, tanh(alpha x / 2) on it
 .cocons.hip.dsumsmoothlone <- function(x, lambda, alpha = 1e6) {
   lambda * ifelse(abs(x) > 1e-4, sign(x), tanh(alpha * x / 2))

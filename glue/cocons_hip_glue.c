@@ -439,6 +439,42 @@ SEXP _cocons_hip_fisher_reml(SEXP fitp, SEXP theta, SEXP dirs)
     return out;
 }
 
+/* cross-validated predictions (cocons_cv_dense / cocons_cv_taper): list(status, list(resid n x r, var n)).  fold: NULL
+ * (leave-one-out) or n integer labels from 0; the labels' count is the largest label + 1 */
+static SEXP cv_call(SEXP fitp, SEXP theta, SEXP mean, SEXP fold, int taper)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), n = fit_n(fitp), r = fit_r(fitp);
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    if (XLENGTH(mean) != p) Rf_error("theta$mean must have length %d", p);
+    int nfold = 0;
+    const int *lab = NULL;
+    if (!taper && !Rf_isNull(fold)) {
+        if (!Rf_isInteger(fold) || XLENGTH(fold) != (R_xlen_t)n) Rf_error("fold must be NULL or %d integer labels", n);
+        lab = INTEGER(fold);
+        for (int i = 0; i < n; ++i)
+            if (lab[i] + 1 > nfold) nfold = lab[i] + 1;
+        if (nfold < 1) nfold = 1;
+    }
+    SEXP resid = PROTECT(Rf_allocMatrix(REALSXP, n, r > 0 ? r : 1));
+    SEXP var = PROTECT(Rf_allocVector(REALSXP, n));
+    for (R_xlen_t e = 0; e < XLENGTH(resid); ++e) REAL(resid)[e] = 0.0;
+    for (R_xlen_t e = 0; e < XLENGTH(var); ++e) REAL(var)[e] = 0.0;
+    int rc = taper ? cocons_cv_taper(f, T, REAL(mean), REAL(resid), REAL(var))
+                   : cocons_cv_dense(f, T, REAL(mean), nfold, lab, REAL(resid), REAL(var));
+    hip_check(rc, taper ? "cross-validation (taper)" : "cross-validation");
+    SEXP res = PROTECT(Rf_allocVector(VECSXP, 2));
+    SET_VECTOR_ELT(res, 0, resid);
+    SET_VECTOR_ELT(res, 1, var);
+    SEXP out = status_value(rc, res);
+    UNPROTECT(3);
+    return out;
+}
+
+SEXP _cocons_hip_cv(SEXP fitp, SEXP theta, SEXP mean, SEXP fold) { return cv_call(fitp, theta, mean, fold, 0); }
+SEXP _cocons_hip_cv_taper(SEXP fitp, SEXP theta, SEXP mean) { return cv_call(fitp, theta, mean, R_NilValue, 1); }
+
 /* the same with its parts: list(status, c(sum_logliks, logdet_half, quad_1 .. quad_r)) -- what
  * GetNeg2loglikelihoodTaperProfile (R/neg2loglikelihood.R:98-106) is formed from on a taper handle */
 SEXP _cocons_hip_neg2loglik_parts(SEXP fitp, SEXP theta, SEXP mean)
@@ -829,6 +865,8 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_neg2loglik_grad", (DL_FUNC)&_cocons_hip_neg2loglik_grad, 3},
     {"_cocons_hip_fisher", (DL_FUNC)&_cocons_hip_fisher, 3},
     {"_cocons_hip_fisher_reml", (DL_FUNC)&_cocons_hip_fisher_reml, 3},
+    {"_cocons_hip_cv", (DL_FUNC)&_cocons_hip_cv, 4},
+    {"_cocons_hip_cv_taper", (DL_FUNC)&_cocons_hip_cv_taper, 3},
     {"_cocons_hip_neg2loglik_batch", (DL_FUNC)&_cocons_hip_neg2loglik_batch, 3},
     {"_cocons_hip_neg2loglik_profile", (DL_FUNC)&_cocons_hip_neg2loglik_profile, 2},
     {"_cocons_hip_neg2loglik_reml", (DL_FUNC)&_cocons_hip_neg2loglik_reml, 3},

@@ -261,6 +261,29 @@ int cocons_fisher_dense(cocons_fit *fit, const double *theta, int ndir, const do
  * cocons_neg2loglik_reml_grad makes it keep.                                                                              */
 int cocons_fisher_reml(cocons_fit *fit, const double *theta, int ndir, const double *dirs, double *info);
 
+/* Cross-validated predictions at theta from one factorisation.  With K = Sigma^-1, U = K (z - X mean) and B a
+ * held-out set of observations with complement A,
+ *   z_B - E[z_B | z_A] = (K_BB)^-1 U_B,   Cov(z_B | z_A) = (K_BB)^-1:
+ * every fold costs one block of K, gathered, factored and inverted, behind the one bordered factorisation of
+ * cocons_neg2loglik_grad_dense.  fold: n labels in [0, nfold) in the caller's observation order (labels nobody carries are
+ * allowed); fold = NULL with nfold = 0: leave-one-out.  resid (n x r, column-major, the caller's order):
+ *   resid[i + k n] = z[i, k] - E[z[i, k] | the observations outside i's fold];   var[i] (length n): the predictive variance
+ * of observation i (nugget included) given the observations outside its fold, the same for every realisation.
+ * Every sum has a fixed order: two calls agree bit for bit, and a fold's outputs depend only on which observations it holds.
+ * 0, the failing minor k > 0 of Sigma, -5 when a hold-out block of Sigma^-1 is not positive definite in floating point (the
+ * message names the fold), or < 0 with a message that starts with the entry's name; outputs are written on 0 only.
+ * Refused (-1) before any device work: null arguments, nfold < 0, fold and nfold that disagree, a label outside [0, nfold),
+ * a fold that holds all n observations, taper and sharded handles, a handle without z.  The handle keeps what
+ * cocons_neg2loglik_grad_dense makes it keep; everything else belongs to the call.                                        */
+int cocons_cv_dense(cocons_fit *fit, const double *theta, const double *mean,
+                    int nfold, const int *fold, double *resid, double *var);
+
+/* Leave-one-out for the tapered model S = T o C(theta) on a taper handle, from the selected inverse of
+ * cocons_neg2loglik_grad_taper: resid[i + k n] = (S^-1 R)[i, k] / (S^-1)_ii, var[i] = 1 / (S^-1)_ii.  Returns and contracts
+ * as cocons_cv_dense; refused (-1) for null arguments, dense and sharded handles and a handle without z.                   */
+int cocons_cv_taper(cocons_fit *fit, const double *theta, const double *mean,
+                    double *resid, double *var);
+
 /* Dense kriging core: replaces R/predict.R:136-183
  *   observed_cov <- cov_rns(...); cov_pred <- cov_rns_pred(...);
  *   inv_cov <- solve(observed_cov, t(cov_pred)); crossprod(resid, inv_cov);
