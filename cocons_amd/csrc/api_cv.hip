@@ -21,13 +21,6 @@ namespace {
 
 constexpr int INFO_CLEAN = 0x7f7f7f7f;      // reset_info's "no failing minor"
 
-struct FoldView {                           // pad0 = 0 while a fold's block is factored (every way out)
-    cocons_fit *f;
-    int pad0;
-    explicit FoldView(cocons_fit *f_) : f(f_), pad0(f_->pad0) { f->pad0 = 0; }
-    ~FoldView() { f->pad0 = pad0; }
-};
-
 // the folds of one call, in the handle's internal order
 struct CvPlan {
     std::vector<int> idx, off, lab;         // fold g (only labels somebody carries): positions idx[off[g] .. off[g + 1]), ascending

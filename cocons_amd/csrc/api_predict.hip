@@ -1,5 +1,5 @@
-// api_predict.hip -- C ABI, what is made of a factor: prediction and kriging (dense and taper), the marginal and
-// conditional simulations, cocons_chol_solve.
+// api_predict.hip -- C ABI, what is made of a factor: prediction and kriging (dense and taper), joint prediction from the
+// held factor, the marginal and conditional simulations, cocons_chol_solve.
 #include "fit.hpp"
 
 // row row0 of out: the residual z[:, z_col] - X mean over the columns [0, ncols), then nrows_zero rows cleared.  out is in
@@ -141,6 +141,8 @@ extern "C" int cocons_krige_prepare(cocons_fit *f, const double *theta, const do
     K->rows = krige_rows(f, max_rows);
     K->theta.resize((size_t)6 * p);
     for (int i = 0; i < 6 * p; ++i) K->theta[i] = canon_nan(theta[i]);
+    K->mean.resize((size_t)p);
+    for (int i = 0; i < p; ++i) K->mean[i] = canon_nan(mean[i]);
     const size_t R = (size_t)K->rows, ntile = (size_t)nt * (nt + 1) / 2;
     StreamDrain s{f->stream, false};
     HIPCHK_AT("cocons_krige_prepare", K->L.alloc(ntile * TILE * TILE));
@@ -243,6 +245,128 @@ extern "C" int cocons_krige_info(cocons_fit *f, long long *out4)
     out4[1] = K ? K->bytes : 0;
     out4[2] = K ? K->rows : 0;
     out4[3] = f->n_user;
+    return 0;
+}
+
+// Joint prediction from the held factor: the predictive covariance between the new locations and conditional draws,
+//   cov  = Sigma_uu - C Sigma^-1 C'                 (R/predict.R:136-183 gives its diagonal only)
+//   sims = L_S E + (X_pred mean + stochastic),  L_S L_S' = cov        (R/sim.R:84-127, cocons_sim_cond_dense's output)
+// against the theta, realisation and mean of cocons_krige_prepare.  With V = C L^-T as launch_krige_solve leaves it in a
+// buffer of the call, cov = Sigma_uu - V V': one symmetric product on the fp64 MFMA (launch_krige_schur) into a view of
+// the call that holds Sigma_uu (cov_rns semantics at locs_unobs, as cocons_sim_cond_dense's block), mirrored to the bit;
+// the draws then cost a factorisation of m, not of n + m.  The view does not start with the handle's observations
+// (FoldView), and it is factored on the schedules that leave the factor whole in it (dag_ok = false): no second buffer.
+// Device memory of the call: round_up(m, 64) x npad + round_up(m, 128)^2 doubles and the small arrays, all released on return.
+extern "C" int cocons_krige_joint(cocons_fit *f, int m, const double *locs_pred, const double *X_pred, const double *locs_unobs,
+                                  double *stochastic, double *cov, int nsim, const double *iiderrors, double *sims)
+{
+    const char *who = "cocons_krige_joint";
+    if (m < 1) return fail(-1, "%s: m = %d (at least one new location is needed)", who, m);
+    if (!locs_pred || !X_pred || !stochastic) return fail(-1, "%s: null locs_pred, X_pred or stochastic", who);
+    if (nsim < 0) return fail(-1, "%s: nsim = %d is negative", who, nsim);
+    if (nsim > 0 && (!iiderrors || !sims)) return fail(-1, "%s: nsim = %d with a null iiderrors or sims", who, nsim);
+    if (!f) return fail(-1, "%s: null fit handle", who);
+    FIT_ENTER(f);
+    if (int rc = no_taper(f, who)) return rc;
+    if (int rc = krige_sharded(f, who)) return rc;
+    const KrigeState *K = f->krige.get();
+    if (!K) return fail(-1, "%s: no kriging state on this handle (call cocons_krige_prepare first)", who);
+    const int p = f->p, npad = f->npad, pad0 = f->pad0;
+    if (m > INT_MAX - TILE) return fail(-1, "%s: m = %d is too large", who, m);
+    const int mv = round_up(m, 64), mpad = round_up(m, TILE);
+    const size_t ldv = (size_t)mv, lds = (size_t)mpad, ne = (size_t)m * (size_t)nsim;
+    const double *lu = locs_unobs ? locs_unobs : locs_pred;
+    const double *th = K->theta.data();
+    std::vector<double> stv((size_t)m), mu((size_t)m), hY(ne), hcov;
+    if (cov && nsim > 0) hcov.resize((size_t)m * m);     // the factorisation may still fail: cov goes home through a staging copy
+    double *cov_to = hcov.empty() ? cov : hcov.data();
+    int raw = 0x7f7f7f7f;                                // the view's own info word (minors counted from the view's first column)
+    DevBuf<double> dV, dS, dXp, dlp, dlu, dlocp, dlocu, dst, dq, dE, dY, dmu;
+    StreamDrain s{f->stream, false};
+    {
+        const size_t counts[12] = {ldv * npad, lds * mpad, (size_t)m * p, (size_t)m * 2, (size_t)m * 2, (size_t)LOCP_FIELDS * mv,
+                                   (size_t)LOCP_FIELDS * mpad, ldv, ldv, ne ? ne : 1, ne ? ne : 1, (size_t)m};
+        DevBuf<double> *bufs[12] = {&dV, &dS, &dXp, &dlp, &dlu, &dlocp, &dlocu, &dst, &dq, &dE, &dY, &dmu};
+        size_t total = 0;
+        for (int k = 0; k < 12; ++k) total += counts[k];
+        for (int k = 0; k < 12; ++k)
+            if (hipError_t e = bufs[k]->alloc(counts[k])) {
+                (void)hipGetLastError();
+                return fail(-100 - (int)e, "%s: the device cannot hold the %zu bytes of the call (m = %d new locations, n = %d): %s",
+                            who, total * sizeof(double), m, f->n_user, hipGetErrorString(e));
+            }
+    }
+    // rows >= m, the padding columns and the slot columns of V are never written by the assembly
+    HIPCHK_AT(who, hipMemsetAsync(dV, 0, ldv * npad * sizeof(double), s));
+    HIPCHK_AT(who, upload_canon(dXp, X_pred, (size_t)m * p, s));
+    HIPCHK_AT(who, upload_canon(dlp, locs_pred, (size_t)m * 2, s));
+    HIPCHK_AT(who, upload_canon(dlu, lu, (size_t)m * 2, s));
+    if (nsim > 0) HIPCHK_AT(who, upload_canon(dE, iiderrors, ne, s));
+    ThetaVecs tv;
+    make_theta_vecs(th, p, tv);
+    const ModeSel ms0 = select_mode(th, p, f->smooth_limits, 0);   // cov_rns semantics (Sigma_uu)
+    const ModeSel msp = select_mode(th, p, f->smooth_limits, 2);   // cov_rns_pred semantics (C)
+    auto enqueue = [&]() -> int {
+        launch_loc_params(loc_args(m, p, dXp, dlp, dlocp, ldv, tv, msp.smooth_kind, f->smooth_limits), s);
+        launch_loc_params(loc_args(m, p, dXp, dlu, dlocu, lds, tv, ms0.smooth_kind, f->smooth_limits), s);
+        PairArgs pa;
+        // C: the new locations against the caller's observations, columns [pad0, n) in the handle's order (cocons_krige_apply)
+        memset(&pa, 0, sizeof pa);
+        pa.n = f->n_user; pa.m = m; pa.rows = dlocp; pa.stride_rows = ldv;
+        pa.cols = K->loc + pad0; pa.stride = npad;
+        pa.out = dV + (size_t)pad0 * ldv; pa.ld = ldv; pa.nrows_out = m; pa.ncols_out = f->n_user;
+        pa.gr = msp.gr; pa.nu_fixed = 0.0;
+        launch_pair_rect(MODE_GEOM, pa, s);
+        launch_krige_solve(K->L, K->Q, K->w, f->nt, dV, ldv, m, pad0, f->n, dst, dq, s);
+        // Sigma_uu, identity in the rows and columns [m, mpad)
+        memset(&pa, 0, sizeof pa);
+        pa.n = m; pa.m = m; pa.rows = dlocu; pa.cols = dlocu; pa.stride = lds; pa.stride_rows = lds;
+        pa.out = dS; pa.ld = lds; pa.nrows_out = mpad; pa.ncols_out = mpad; pa.gr = ms0.gr; pa.nu_fixed = ms0.nu_fixed;
+        launch_pair_sym(ms0.mode, false, pa, s);
+        launch_krige_schur(dV, ldv, m, pad0, f->n, npad, dS, lds, s);
+        launch_sym_mirror(dS, lds, m, s);
+        HIPCHK_AT(who, hipMemcpyAsync(stv.data(), dst, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (cov)
+            HIPCHK_AT(who, hipMemcpy2DAsync(cov_to, (size_t)m * sizeof(double), dS, lds * sizeof(double), (size_t)m * sizeof(double),
+                                            (size_t)m, hipMemcpyDeviceToHost, s));
+        if (nsim == 0) return 0;
+        // tmp_mu = X_pred mean + stochastic on the host, as cocons_sim_cond_dense forms it
+        HIPCHK_AT(who, hipStreamSynchronize(s));
+        for (int i = 0; i < m; ++i) {
+            double sys = 0;
+            for (int j = 0; j < p; ++j) sys += X_pred[(size_t)i + (size_t)j * m] * K->mean[j];
+            mu[i] = sys + stv[i];
+        }
+        HIPCHK_AT(who, upload_canon(dmu, mu.data(), (size_t)m, s));
+        {
+            FoldView fv(f);
+            FactorView v;
+            v.A = dS; v.lda = lds; v.nt = mpad / TILE; v.mt = mpad / TILE;
+            if (int rc = factorize(f, v, nullptr)) return rc;
+        }
+        HIPCHK_AT(who, hipMemcpyAsync(&raw, f->dinfo, sizeof(int), hipMemcpyDeviceToHost, s));
+        launch_trmm_lower(dS, lds, m, dE, m, nsim, dmu, dY, m, s);
+        HIPCHK_AT(who, hipMemcpyAsync(hY.data(), dY, ne * sizeof(double), hipMemcpyDeviceToHost, s));
+        return 0;
+    };
+    if (nsim == 0) {                    // nothing is factored: no info words, nothing to repeat
+        if (int rc = enqueue()) return rc;
+        HIPCHK_AT(who, hipGetLastError());
+        HIPCHK_AT(who, hipStreamSynchronize(s));
+    } else {
+        f->nrhs_cur = 0;
+        const int st = run_op(f, who, enqueue);
+        if (st > 0)
+            return fail(-5, "%s: the predictive covariance is not positive definite (leading minor %d of %d not positive)", who,
+                        raw, m);
+        if (st < 0) {
+            const std::string why = g_err;
+            return why.compare(0, strlen(who), who) == 0 ? st : fail(st, "%s: %s", who, why.c_str());
+        }
+        memcpy(sims, hY.data(), ne * sizeof(double));
+        if (!hcov.empty()) memcpy(cov, hcov.data(), hcov.size() * sizeof(double));
+    }
+    memcpy(stochastic, stv.data(), (size_t)m * sizeof(double));
     return 0;
 }
 

@@ -3263,5 +3263,99 @@ void launch_krige_solve(const double *Lp, const double *Qp, const double *w, int
     }
 }
 
+// Predictive covariance from the solved chunk (cocons_krige_joint): S(I, J) -= V(I, :) V(J, :)' over the lower 128 x 128
+// tiles of S.  One workgroup per (64-row strip of tile row I, tile column J <= I): a wave 16 rows, all 128 columns of
+// the tile in eight accumulators, as krige_update_kernel.  Both operands are rows of the same V (column-major, ld ldv):
+// the strip's 64 x 32 slab and tile J's 128 x 32 slab of a K slice go through registers into LDS as 16 x 16 blocks in
+// lds_blk layout, 48 KiB together.  Rows >= m of either slab are read as zero (ldv may end before S's padding does).
+// K runs over the columns [k0, k1) in slices of 32, in 16-column blocks, in the MFMA's own order -- the same sequence for
+// every element of S, whatever m or the grid: no K split, no atomics, nothing between workgroups.  The strips inside a
+// diagonal tile form the whole 64 x 128 block, entries above the diagonal included (launch_sym_mirror overwrites them).
+constexpr int KS_KC = 32;
+__global__ void __launch_bounds__(256)
+krige_schur_kernel(const double *V, size_t ldv, int m, int k0, int k1, double *S, size_t lds)
+{
+    __shared__ double PS[64 * KS_KC];
+    __shared__ double QS[TILE * KS_KC];
+    const int strip = blockIdx.x, J = blockIdx.y;
+    if (2 * J > strip) return;                      // tile J lies right of the strip's diagonal tile
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r0 = 64 * strip, c0 = J * TILE, rs = r0 + 16 * wave;
+    d4 acc[8];
+#pragma unroll
+    for (int jb = 0; jb < 8; ++jb) acc[jb] = glb_blk(S, lds, rs, c0 + 16 * jb, lane);
+    for (int kc = k0; kc < k1; kc += KS_KC) {
+        double vq[TILE * KS_KC / 256], vp[64 * KS_KC / 256];
+#pragma unroll
+        for (int q = 0; q < TILE * KS_KC / 256; ++q) {
+            const int e = tid + 256 * q, j = e & (TILE - 1), k = e >> 7;
+            vq[q] = c0 + j < m ? V[(size_t)(c0 + j) + (size_t)(kc + k) * ldv] : 0.0;
+        }
+#pragma unroll
+        for (int q = 0; q < 64 * KS_KC / 256; ++q) {
+            const int e = tid + 256 * q, i = e & 63, k = e >> 6;
+            vp[q] = r0 + i < m ? V[(size_t)(r0 + i) + (size_t)(kc + k) * ldv] : 0.0;
+        }
+        __syncthreads();                  // every wave is done with the previous slice
+#pragma unroll
+        for (int q = 0; q < TILE * KS_KC / 256; ++q) {
+            const int e = tid + 256 * q, j = e & (TILE - 1), k = e >> 7;
+            QS[(((j >> 4) * (KS_KC / 16) + (k >> 4)) << 8) + ((k & 15) << 4) + (j & 15)] = vq[q];
+        }
+#pragma unroll
+        for (int q = 0; q < 64 * KS_KC / 256; ++q) {
+            const int e = tid + 256 * q, i = e & 63, k = e >> 6;
+            PS[(((i >> 4) * (KS_KC / 16) + (k >> 4)) << 8) + ((k & 15) << 4) + (i & 15)] = vp[q];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kb = 0; kb < KS_KC / 16; ++kb) {
+            const d4 NP = -lds_blk(PS + ((wave * (KS_KC / 16) + kb) << 8), lane);
+#pragma unroll
+            for (int jb = 0; jb < 8; ++jb) {
+                const d4 Q = lds_blk(QS + ((jb * (KS_KC / 16) + kb) << 8), lane);
+                blk_mma(acc[jb], NP, Q);
+            }
+        }
+    }
+#pragma unroll
+    for (int jb = 0; jb < 8; ++jb) glb_blk_store(S, lds, rs, c0 + 16 * jb, lane, acc[jb]);
+}
+
+void launch_krige_schur(const double *V, size_t ldv, int m, int c_lo, int c_hi, int npad, double *S, size_t lds, hipStream_t s)
+{
+    if (m <= 0 || c_hi <= c_lo) return;
+    const int mpad = (m + TILE - 1) / TILE * TILE;
+    hipLaunchKernelGGL(krige_schur_kernel, dim3((unsigned)(mpad / 64), (unsigned)(mpad / TILE)), dim3(256), 0, s, V, ldv, m,
+                       c_lo / TILE * TILE, npad, S, lds);
+}
+
+// S(j, i) = S(i, j) for i > j, i < n: the upper triangle becomes the mirror of the lower one, in 64 x 64 tiles through LDS
+__global__ void __launch_bounds__(256)
+sym_mirror_kernel(double *S, size_t lds, int n)
+{
+    __shared__ double T[64 * 65];
+    const int bi = blockIdx.x, bj = blockIdx.y;
+    if (bj > bi) return;
+    const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int cc = w; cc < 64; cc += 4) {
+        const int r = 64 * bi + l, c = 64 * bj + cc;
+        T[cc * 65 + l] = (r < n && c < n) ? S[(size_t)r + (size_t)c * lds] : 0.0;
+    }
+    __syncthreads();
+    // target (row 64 bj + l, column 64 bi + rr) = source (row 64 bi + rr, column 64 bj + l)
+    for (int rr = w; rr < 64; rr += 4) {
+        const int tr = 64 * bj + l, tc = 64 * bi + rr;
+        if (tr < tc && tc < n) S[(size_t)tr + (size_t)tc * lds] = T[l * 65 + rr];
+    }
+}
+
+void launch_sym_mirror(double *S, size_t lds, int n, hipStream_t s)
+{
+    if (n <= 0) return;
+    const unsigned t = (unsigned)((n + 63) / 64);
+    hipLaunchKernelGGL(sym_mirror_kernel, dim3(t, t), dim3(256), 0, s, S, lds, n);
+}
+
 }  // namespace cocons
 

@@ -157,6 +157,7 @@ struct KrigeState {
     DevBuf<double> Xp, lp, locp;  // the chunk's X_pred (rows x p), locations (rows x 2) and SoA (LOCP_FIELDS x rows)
     DevBuf<double> st, qd;        // rows: the chunk's outputs
     std::vector<double> theta;    // 6 p: the prepared theta (canonicalised)
+    std::vector<double> mean;     // p: the prepared mean (canonicalised; cocons_krige_joint's trend of the draws)
     int rows = 0;                 // rows per chunk (a multiple of 64)
     long long bytes = 0;          // device bytes held
 };
@@ -363,6 +364,15 @@ struct FactorView {
                                // rows in use): no kernel of the factorisation touches them
     bool dag_ok = false;       // the caller reads the factor through launch_finalize(..., A2 = dP) only: the dependency-driven
                                // schedule may be used (its factor is split over two buffers)
+};
+
+// pad0 = 0 while a view that does not start with the handle's observations is factored (every way out): factorize()'s
+// front-identity step belongs to the other kind (api_cv.hip: a fold's block; api_predict.hip: the predictive covariance)
+struct FoldView {
+    cocons_fit *f;
+    int pad0;
+    explicit FoldView(cocons_fit *f_) : f(f_), pad0(f_->pad0) { f->pad0 = 0; }
+    ~FoldView() { f->pad0 = pad0; }
 };
 
 // Where the nrhs right-hand-side rows of an evaluation sit -- the ONE place that decides it (enqueue_eval_impl, the replay

@@ -282,6 +282,13 @@ void launch_krige_pack(const double *A, size_t lda, int nt, int rowy, int c_lo, 
                        hipStream_t s);
 void launch_krige_solve(const double *Lp, const double *Qp, const double *w, int nt, double *C, size_t ldc, int rows,
                         int c_lo, int c_hi, double *stoch, double *quad, hipStream_t s);
+// schur: S(I, J) -= V(I, :) V(J, :)' over the lower 128 x 128 tiles of S (round_up(m, 128) rows and columns, column-major,
+// ld lds), V as launch_krige_solve leaves it (m rows, ld ldv >= round_up(m, 64), npad columns, zero outside [c_lo, c_hi));
+// rows >= m of V count as zero.  K runs from c_lo's tile to npad in one fixed order per element: bit-identical launches,
+// and the leading block of S does not depend on m.  The upper triangle of S's diagonal tiles is overwritten with values
+// nobody may read; launch_sym_mirror then makes the upper triangle of the leading n x n block the mirror of the lower one.
+void launch_krige_schur(const double *V, size_t ldv, int m, int c_lo, int c_hi, int npad, double *S, size_t lds, hipStream_t s);
+void launch_sym_mirror(double *S, size_t lds, int n, hipStream_t s);
 // out[i + s ldo] = Y[pos[i] + s ldy] for i < n, s < ncol
 void launch_gather_rows(const double *Y, int ldy, const int *pos, int n, int ncol, double *out, int ldo, hipStream_t s);
 

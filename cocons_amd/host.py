@@ -24,6 +24,12 @@ import numpy as np
 from . import _lib
 from ._lib import CholeskyError, c_dp
 
+
+class KrigeJointNotPositiveDefinite(_lib.CoconsHipError):
+    """cocons_krige_joint's -5: the predictive covariance is not positive definite in floating point (the message names
+    the failing minor); the reference's second `chol` fails there (R/sim.R:106)."""
+
+
 ASPECTS = ("mean", "std.dev", "scale", "aniso", "tilt", "smooth", "nugget")   # R/profile.R:5-7
 COV_ASPECTS = ASPECTS[1:]
 
@@ -424,6 +430,27 @@ class CoconsFit:
         st, qf = np.empty(m), np.empty(m)
         _lib.check(self._L.cocons_krige_apply(self._h, m, _p(lp), _p(Xp), _p(st), _p(qf)), "cocons_krige_apply")
         return st, qf
+
+    def krige_joint_core(self, locs_pred, x_covariates_pred, locs_unobs=None, iiderrors=None, cov=True):
+        """(stochastic, cov | None, sims | None) at the new locations against the prepared factor (cocons_krige_joint):
+        cov = Sigma_uu - C Sigma^-1 C' (m x m, symmetric to the bit; Sigma_uu at locs_unobs, default locs_pred), sims =
+        chol(cov) iiderrors + (X_pred mean + stochastic) for iiderrors m x nsim.  A predictive covariance that is not
+        positive definite in floating point (draws only) raises KrigeJointNotPositiveDefinite; nothing is returned then."""
+        lp, Xp = _f(locs_pred), _f(x_covariates_pred)
+        m = Xp.shape[0]
+        lu = None if locs_unobs is None else _f(np.asarray(locs_unobs, dtype=np.float64)[:, :2])
+        E = None if iiderrors is None else _f(np.asarray(iiderrors, dtype=np.float64).reshape(m, -1))
+        nsim = 0 if E is None else E.shape[1]
+        st = np.empty(m)
+        C = np.empty((m, m), order="F") if cov else None
+        Y = np.empty((m, nsim), order="F") if nsim > 0 else None
+        rc = self._L.cocons_krige_joint(self._h, m, _p(lp), _p(Xp), None if lu is None else _p(lu), _p(st),
+                                        None if C is None else _p(C), nsim, None if nsim == 0 else _p(E),
+                                        None if Y is None else _p(Y))
+        if rc == -5 and "not positive definite" in _lib.last_error():     # (-5 is also a hand-off time-out that was repeated in vain)
+            raise KrigeJointNotPositiveDefinite(_lib.last_error())
+        _lib.check(rc, "cocons_krige_joint")
+        return st, C, Y
 
     def krige_release(self):
         _lib.check(self._L.cocons_krige_release(self._h), "cocons_krige_release")
@@ -1086,6 +1113,27 @@ def cocoSim_cond_dense(theta_list, locs, newlocs, newdataset, X_std, X_pred_std,
             f.close()
 
 
+def cocoSim_cond_dense_held(theta_list, locs, newlocs, newdataset, X_std, X_pred_std, smooth_limits, z, iiderrors,
+                            fit=None):
+    """cocoSim_cond_dense from a held factor of Sigma(theta): prepare, one joint call (krige_joint_core: the predictive
+    covariance is formed from the factor, and only its own m x m Cholesky is taken), release.  Same arguments and output
+    as cocoSim_cond_dense; the handle's kriging state is released on return."""
+    f, own = _with_fit(fit, locs, X_std, z, smooth_limits)
+    try:
+        try:
+            f.krige_prepare(theta_list)
+            try:
+                return f.krige_joint_core(newlocs, X_pred_std, np.asarray(newdataset, dtype=np.float64), iiderrors,
+                                          cov=False)[2]
+            finally:
+                f.krige_release()
+        except (CholeskyError, KrigeJointNotPositiveDefinite):
+            raise RuntimeError("Cholesky error")
+    finally:
+        if own:
+            f.close()
+
+
 def cocoPredict_dense(theta_list, locs, newlocs, X_std, X_pred_std, smooth_limits, z, type="pred", fit=None):
     """Dense branch of cocoPredict, R/predict.R:136-187, from the point where the scaled
     design matrices and the adjusted theta list exist."""
@@ -1137,3 +1185,25 @@ def cocoPredict_dense_chunked(theta_list, locs, newlocs, X_std, X_pred_std, smoo
         if own:
             f.close()
     return _predict_outputs(theta_list, X_pred_std, st, qf, type)
+
+
+def cocoPredict_dense_joint(theta_list, locs, newlocs, X_std, X_pred_std, smooth_limits, z, fit=None):
+    """cocoPredict_dense with the predictive covariance BETWEEN the new locations: {"systematic", "stochastic", "sd.pred",
+    "cov.pred"}, cov.pred = Sigma_uu - C Sigma^-1 C' (m x m) from one held factor (krige_prepare, krige_joint_core,
+    release) and sd.pred the root of its diagonal with the reference's abs rule below 1e-10 (R/predict.R:175-177)."""
+    f, own = _with_fit(fit, locs, X_std, z, smooth_limits)
+    try:
+        f.krige_prepare(theta_list)
+        try:
+            st, cov, _ = f.krige_joint_core(newlocs, X_pred_std)
+        finally:
+            f.krige_release()
+    finally:
+        if own:
+            f.close()
+    Xp = np.asarray(X_pred_std, dtype=np.float64)
+    unc = np.diag(cov).copy()
+    neg = unc < 1e-10
+    unc[neg] = np.abs(unc[neg])
+    return {"systematic": Xp @ np.asarray(theta_list["mean"], dtype=np.float64), "stochastic": st, "sd.pred": np.sqrt(unc),
+            "cov.pred": cov}

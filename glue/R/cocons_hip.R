@@ -265,6 +265,17 @@ GetNeg2loglikelihoodREMLGrad <- function(theta, par.pos, locs, x_covariates, x_b
   res[[2]]
 }
 
+# joint prediction against the same held factor: the predictive covariance between the new locations (a joint interval, a
+# contrast, the variance of an areal mean) and, with iiderrors (m x nsim), cocoSim's conditional draws (R/sim.R:84-127)
+# without factoring the joint (n + m) matrix:
+#   kj <- .cocons.hip.krige.joint(fit, newlocs, X_pred_std, locs_unobs = as.matrix(newdataset)[, 1:2], iiderrors = E)
+#   kj$stochastic;  kj$cov  (m x m, or NULL with cov = FALSE);  kj$sims  (m x nsim, or NULL without iiderrors)
+.cocons.hip.krige.joint <- function(fit, newlocs, X_pred, locs_unobs = NULL, iiderrors = NULL, cov = TRUE) {
+  res <- .Call(`_cocons_hip_krige_joint`, fit, newlocs, X_pred, locs_unobs, iiderrors, as.logical(cov))
+  if (res[[1]] != 0L) stop("Cholesky error")
+  list(stochastic = res[[2]], cov = res[[3]], sims = res[[4]])
+}
+
 .cocons.hip.krige.release <- function(fit) invisible(.Call(`_cocons_hip_krige_release`, fit))
 
 # rows of cov2cor(cov_rns(...)) for plot(type = "correlations") (R/methods.R:161-165): tmp_cov[ww, ]

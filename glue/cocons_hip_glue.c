@@ -663,6 +663,35 @@ SEXP _cocons_hip_krige(SEXP fitp, SEXP locs_pred, SEXP X_pred)
     return out;
 }
 
+/* joint prediction against the held factor (R/predict.R:136-183 between the new locations, R/sim.R:84-127 from the held
+ * factor): locs_unobs m x 2 or NULL (= locs_pred), iiderrors m x nsim or NULL (no draws), want_cov.
+ * list(status, stochastic, cov m x m | NULL, sims m x nsim | NULL) -- status -5: the predictive covariance is not positive
+ * definite ("Cholesky error" in the R wrapper), nothing written */
+SEXP _cocons_hip_krige_joint(SEXP fitp, SEXP locs_pred, SEXP X_pred, SEXP locs_unobs, SEXP iiderrors, SEXP want_cov)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), m = Rf_nrows(X_pred);
+    if (Rf_ncols(X_pred) != p || Rf_nrows(locs_pred) != m || Rf_ncols(locs_pred) != 2)
+        Rf_error("prediction design / locations do not match the fit");
+    const int have_lu = !Rf_isNull(locs_unobs), have_e = !Rf_isNull(iiderrors), wc = Rf_asLogical(want_cov);
+    if (have_lu && (Rf_nrows(locs_unobs) != m || Rf_ncols(locs_unobs) != 2)) Rf_error("locs_unobs must be %d x 2", m);
+    if (have_e && Rf_nrows(iiderrors) != m) Rf_error("iiderrors must have %d rows", m);
+    const int nsim = have_e ? Rf_ncols(iiderrors) : 0;
+    SEXP res = PROTECT(Rf_allocVector(VECSXP, 4));
+    SEXP st = Rf_allocVector(REALSXP, m);
+    SET_VECTOR_ELT(res, 1, st);
+    SEXP cv = R_NilValue, sm = R_NilValue;
+    if (wc) { cv = Rf_allocMatrix(REALSXP, m, m); SET_VECTOR_ELT(res, 2, cv); }
+    if (nsim > 0) { sm = Rf_allocMatrix(REALSXP, m, nsim); SET_VECTOR_ELT(res, 3, sm); }
+    for (int i = 0; i < m; ++i) REAL(st)[i] = NA_REAL;
+    int rc = cocons_krige_joint(f, m, REAL(locs_pred), REAL(X_pred), have_lu ? REAL(locs_unobs) : NULL, REAL(st),
+                                wc ? REAL(cv) : NULL, nsim, nsim > 0 ? REAL(iiderrors) : NULL, nsim > 0 ? REAL(sm) : NULL);
+    if (rc != -5) hip_check(rc, "cocoPredict / cocoSim (krige joint)");
+    SET_VECTOR_ELT(res, 0, Rf_ScalarInteger(rc));
+    UNPROTECT(1);
+    return res;
+}
+
 SEXP _cocons_hip_krige_release(SEXP fitp)
 {
     hip_check(cocons_krige_release(fit_of(fitp)), "cocoPredict (krige release)");
@@ -877,6 +906,7 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_predict_taper", (DL_FUNC)&_cocons_hip_predict_taper, 9},
     {"_cocons_hip_krige_prepare", (DL_FUNC)&_cocons_hip_krige_prepare, 5},
     {"_cocons_hip_krige", (DL_FUNC)&_cocons_hip_krige, 3},
+    {"_cocons_hip_krige_joint", (DL_FUNC)&_cocons_hip_krige_joint, 6},
     {"_cocons_hip_krige_release", (DL_FUNC)&_cocons_hip_krige_release, 1},
     {"_cocons_hip_sim", (DL_FUNC)&_cocons_hip_sim, 5},
     {"_cocons_hip_sim_cond", (DL_FUNC)&_cocons_hip_sim_cond, 8},

@@ -115,6 +115,28 @@ int cocons_krige_apply(cocons_fit *fit, int m, const double *locs_pred, const do
 int cocons_krige_release(cocons_fit *fit);
 int cocons_krige_info(cocons_fit *fit, long long *out4);
 
+/* Joint prediction from the held factor, against the theta, realisation and mean of cocons_krige_prepare: what
+ * cocoPredict's dense branch (R/predict.R:136-183) gives per location, between the m new locations, and the conditional
+ * draws of cocoSim (R/sim.R:84-127) without the factorisation of the joint (n + m) x (n + m) matrix.
+ *   stochastic[i] = c_i' Sigma^-1 (z - X mean)            (the bits of cocons_krige_apply for the same rows)
+ *   cov  = Sigma_uu - C Sigma^-1 C'                       m x m column-major, full and symmetric to the bit; NULL: not wanted
+ *   sims = L_S E + (X_pred mean + stochastic)             m x nsim, L_S L_S' = cov, E = iiderrors (m x nsim); nsim = 0: no draws
+ * with C = cov_rns_pred(theta, locs, locs_pred, X, X_pred) and Sigma_uu = cov_rns(theta, locs_unobs, X_pred) -- nugget on
+ * the diagonal, the coincident-pair rule, as cocons_sim_cond_dense's block; locs_unobs = NULL: locs_pred.  With nsim = 0
+ * nothing is factored.  Repeated calls agree bit for bit, and the leading block of cov (and the leading entries of
+ * stochastic) for the first rows of a request do not depend on the rows behind them.
+ * The call takes round_up(m, 64) x npad + round_up(m, 128)^2 doubles of device memory and releases them before it returns;
+ * the kriging state is not touched.  Returns 0; -5 when the predictive covariance is not positive definite in floating
+ * point (nsim > 0 only; the message names the failing minor); -1 for m < 1, a null locs_pred, X_pred or stochastic,
+ * nsim < 0, nsim > 0 with a null iiderrors or sims, a null, taper or sharded handle, or no prepared state; < 0 otherwise
+ * (a failed allocation names the bytes needed).  The outputs are written on 0 only.                                     */
+int cocons_krige_joint(cocons_fit *fit, int m, const double *locs_pred, const double *X_pred,
+                       const double *locs_unobs,           /* m x 2, NULL = locs_pred */
+                       double *stochastic,                 /* m */
+                       double *cov,                        /* m x m column-major, may be NULL */
+                       int nsim, const double *iiderrors,  /* m x nsim, nsim = 0: no draws */
+                       double *sims);                      /* m x nsim */
+
 /* Kriging core of the sparse branch of cocoPredict (R/predict.R:216-283) on a taper handle: replaces
  * cov_rns_taper / cov_rns_taper_pred times their tapers, inv_cov <- spam::solve(taper_two, t(pred_taper)) (:244),
  * crossprod(resid, inv_cov) (:252) and rowSums(pred_taper * t(inv_cov)) (:267).  pred_taper's slots go in as they
