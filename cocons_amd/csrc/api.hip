@@ -674,8 +674,11 @@ int assemble_sigma_taper(cocons_fit *f, const double *theta)
     // full by the right-hand-side kernel), or the whole buffer when the factorisation is not band-limited
     if (f->d_thi) launch_band_zero(f->dA, f->lda, f->d_thi, f->nt, f->taper_maxband, f->stream, f->skew);
     else HIPCHK(hipMemsetAsync(f->dA, 0, f->lda * (size_t)f->npad * sizeof(double), f->stream));
-    launch_taper(ms.mode, false, f->n, f->taper_nnz, f->d_tci, f->d_trp, f->dloc, f->npad, f->dloc, f->npad,
-                 ms.nu_fixed, nullptr, f->stream, f->d_tval, f->dA, f->lda, 0, f->skew, f->npad);
+    TaperLaunch t;
+    t.mode = ms.mode; t.nrows = f->n; t.nnz = f->taper_nnz; t.ci = f->d_tci; t.rp = f->d_trp; t.nu_fixed = ms.nu_fixed;
+    t.rows = t.cols = f->dloc; t.stride_rows = t.stride = f->npad;
+    t.tapv = f->d_tval; t.A = f->dA; t.lda = f->lda; t.skew = f->skew; t.npad = f->npad;
+    launch_taper(t, f->stream);
     launch_pad_identity(f->dA, f->lda, f->n, f->npad, f->stream, f->skew);
     return 0;
 }
@@ -759,44 +762,36 @@ static int band_hi(const FactorView &v, int k)
     return h < v.nt ? h : v.nt;
 }
 
-static bool follow_on(cocons_fit *f)
-{
-    return tun().potrf_follow != 0 && !f->follow_off && f->dmbox != nullptr &&
-           f->smb_off >= ((size_t)f->nt + 2) * ENGINE_MBOX_DOUBLES;
-}
-
 // tile factorisation + the panel solve below it.  (ONE launch for the two -- the solve's workgroups fetch their rows, wait for
 // a word the factorising workgroup raises, take L and solve -- was built and measured in round 5: SLOWER, taper path 4.18 -> 4.57
 // ms, batch at n = 4096 1066 -> 1031 evaluations/s: the boundary between the two launches costs less than the write-through
 // factor and the serialised fetch of L behind the word; removed.)
 // (Round 5, later: ONE launch after all -- not behind a word but FOLLOWING the factorisation through the tile's mailbox, the way the
 // engine's partner does: potrf_follow_kernel.  The mailboxes are filled by mbox_reset at the start of the factorisation.)
-static void potrf_solve(cocons_fit *f, double *A, size_t lda, int tile, int r0, int r1, double *q, hipStream_t s, int br, int er)
+static void potrf_solve(cocons_fit *f, double *A, size_t lda, int tile, const RowRange &rows, double *q, hipStream_t s)
 {
-    if (follow_on(f) && ((size_t)tile + 1) * ENGINE_MBOX_DOUBLES <= f->smb_off) {
+    TrsmLaunch l;
+    l.A = A; l.lda = lda; l.c0 = tile * TILE; l.rows = rows; l.dinv = q;
+    if (tun().potrf_follow != 0 && !f->follow_off && tile_mbox(f, f->nt + 1) && (l.mbox = tile_mbox(f, tile)) != nullptr) {
         f->follow_used = true;
-        launch_potrf_follow(A, lda, tile * TILE, r0, r1, q, f->dinfo,
-                            f->dmbox + (size_t)tile * ENGINE_MBOX_DOUBLES, (unsigned *)(f->dinfo + 1), s, br, er);
+        l.info = f->dinfo; l.abort_word = handoff_words(f).abort;
+        launch_potrf_follow(l, s);
         return;
     }
     launch_potrf_tile(A, lda, tile * TILE, q, f->dinfo, s);
-    launch_trsm_tile(A, lda, tile * TILE, r0, r1, q, s, nullptr, nullptr, br, er);
+    launch_trsm_tile(l, s);
 }
 
 static void panel_ops(cocons_fit *f, const FactorView &v, int k, hipStream_t s)
 {
-    const int nt = v.nt, mt = v.mt;
-    double *A = v.A;
-    const size_t lda = v.lda;
     double *q0 = f->dinv, *q1 = f->dinv + 8 * 256;
     const int hb = band_hi(v, k);                       // rows [.., hb) of the band, then the rows under the matrix [nt, mt)
-    const int br = hb >= 0 ? hb * TILE : -1, er = nt * TILE;
-    const int r1 = mt * TILE - 64 * v.trim;
-    potrf_solve(f, A, lda, k, (k + 1) * TILE, r1, q0, s, br, er);
-    if (k + 1 < nt) {
-        launch_update(A, lda, k * TILE, TILE, k + 1, mt, k + 1, k + 2, true, s, nullptr, -1, nullptr, nullptr, nullptr, hb, nt,
-                      0, v.trim);
-        potrf_solve(f, A, lda, k + 1, (k + 2) * TILE, r1, q1, s, br, er);
+    potrf_solve(f, v.A, v.lda, k, v.panel_rows(k + 1, hb), q0, s);
+    if (k + 1 < v.nt) {
+        UpdateLaunch u = v.update(hb);
+        u.panel_in_c(k * TILE); u.K = TILE; u.ti0 = k + 1; u.ti1 = v.mt; u.tj0 = k + 1; u.tj1 = k + 2; u.lower_only = true;
+        launch_update(u, s);
+        potrf_solve(f, v.A, v.lda, k + 1, v.panel_rows(k + 2, hb), q1, s);
     }
 }
 
@@ -859,14 +854,6 @@ extern "C" int cocons_debug_tune(const char *name, int value)
 // moves the engine.  The quota keeps the launch below what fits in ANY placement: seven per CU on the XCD's other CUs, less
 // one CU's worth and one: (CUs per XCD - 1) x 7 - 9 = 208 for the 32 CUs per XCD of MI355X (the value of round 4's soak runs:
 // 0 time-outs in 40 000 evaluations), from hipDeviceProp instead of a constant; COCONS_DAG_XCC_QUOTA overrides.
-static int device_cus()
-{
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return cus;
-}
-
 static int dag_xcc_quota()
 {
     if (tun().dag_xcc_quota >= 0) return tun().dag_xcc_quota;
@@ -908,7 +895,6 @@ static void timed_update(cocons_fit *f, const FactorView &v, int k, int kw, int 
     const int hb = band_hi(v, k);                       // band-limited: tile columns and rows [t0, hb), plus the rows [nt, mt)
     if (hb >= 0 && hb < t1) t1 = hb;
     if (t1 <= t0) return;
-    unsigned *abort_word = sig ? (unsigned *)(f->dinfo + 1) : nullptr;   // engine schedule: see update_kernel
     hipEvent_t a = nullptr, b = nullptr;
     if (ev_upd) {
         hipEventCreate(&a); hipEventCreate(&b);
@@ -917,8 +903,11 @@ static void timed_update(cocons_fit *f, const FactorView &v, int k, int kw, int 
     // the first panel's leading columns are the unit vectors of the front padding (zero below the diagonal): they add
     // nothing to the trailing matrix, so the update starts behind them (whole 16-column chunks; bit-identical)
     const int kskip = (k == 0 && !v.hi) ? (f->pad0 / 16) * 16 : 0;
-    launch_update(v.A, v.lda, k * TILE + kskip, kw * TILE - kskip, t0, mt, t0, t1, true, s, sig, sig_tile, nullptr,
-                  abort_word, queue, hb, v.nt, 0, v.trim, skip_tiles > 0 ? 2 * t0 : 0, skip_tiles > 0 ? 2 * (t0 + skip_tiles) : 0);
+    UpdateLaunch u = v.update(hb);
+    u.panel_in_c(k * TILE + kskip); u.K = kw * TILE - kskip; u.ti0 = t0; u.ti1 = mt; u.tj0 = t0; u.tj1 = t1; u.lower_only = true;
+    u.sig = sig; u.sig_tile = sig_tile; u.queue = queue; u.abort_word = sig ? handoff_words(f).abort : nullptr;   // engine schedule: see update_kernel
+    if (skip_tiles > 0) { u.skip_lo = 2 * t0; u.skip_hi = 2 * (t0 + skip_tiles); }
+    launch_update(u, s);
     if (ev_upd) {
         hipEventRecord(b, s);
         ev_upd->push_back(a); ev_upd->push_back(b);
@@ -953,10 +942,10 @@ int flags_reset(cocons_fit *f, int nt)
 {
     if (f->flags_cap < nt) {
         const int cap = round_up(nt + 8, 64);
-        HIPCHK(f->dflags.reserve(4 * (size_t)cap + 64, f->stream, f->stream2));
+        HIPCHK(f->dflags.reserve(handoff_word_count(cap), f->stream, f->stream2));
         f->flags_cap = cap;
     }
-    HIPCHK(hipMemsetAsync(f->dflags, 0, (4 * (size_t)f->flags_cap + 64) * sizeof(unsigned), f->stream));
+    HIPCHK(hipMemsetAsync(f->dflags, 0, handoff_word_count(f->flags_cap) * sizeof(unsigned), f->stream));
     return 0;
 }
 
@@ -965,24 +954,13 @@ int flags_reset(cocons_fit *f, int nt)
 int mbox_reset(cocons_fit *f, int nt, bool engine_schedule)
 {
     // one allocation, one fill: the tiles' mailboxes | the strip mailboxes (0.5 MB per diagonal block) | the exchange mailboxes of
-    // the split panel (64 KB per 64-row strip of the matrix and the rows under it)
-    const size_t tiles = ((size_t)nt + 2) * ENGINE_MBOX_DOUBLES;
-    const bool panel = tun().panel_fused && tun().engine_pair;        // (the one-launch panel follows the pair's tiles)
-    const size_t smb = panel ? ((size_t)nt / 2 + 2) * PANEL_SMBOX_DOUBLES : 0;
-    const size_t xmb = panel && tun().panel_split ? (2 * ((size_t)nt + 2) + 4) * PANEL_XMBOX_DOUBLES : 0;
-    const size_t need = tiles + smb + xmb;
-    HIPCHK(f->dmbox.reserve(need, f->stream, f->stream2));
-    f->smb_off = tiles; f->smb_elems = smb;
-    f->xmb_off = tiles + smb; f->xmb_elems = xmb;
+    // the split panel (64 KB per 64-row strip); the one-launch panel follows the pair's tiles
+    const MboxLayout l = mbox_layout(nt, tun().panel_fused && tun().engine_pair, tun().panel_split != 0);
+    HIPCHK(f->dmbox.reserve(l.total(), f->stream, f->stream2));
+    f->mbox = l;
     // (the plain schedule uses the tiles' mailboxes only)
-    HIPCHK(hipMemsetAsync(f->dmbox, 0xff, (engine_schedule ? need : tiles) * sizeof(double), f->stream));
+    HIPCHK(hipMemsetAsync(f->dmbox, 0xff, (engine_schedule ? l.total() : l.tiles) * sizeof(double), f->stream));
     return 0;
-}
-
-// one tile counter per trailing update: see update_kernel's dynamic tile order
-static unsigned *tile_queue(cocons_fit *f, int k)
-{
-    return f->dflags + 3 * (size_t)f->flags_cap + 64 + k / 2;
 }
 
 // Warm-up of the engine's stream at handle creation: ONE launch of the engine kernel that raises its alive word and
@@ -1006,7 +984,7 @@ static int engine_warm(cocons_fit *f)
         std::vector<hipStream_t> losers;
         int ok = 0;
         for (int attempt = 0; attempt < 8; ++attempt) {
-            ok = streams_run_concurrently(f->stream2, f->stream, f->dflags + 3 * (size_t)f->flags_cap + 8);
+            ok = streams_run_concurrently(f->stream2, f->stream, handoff_words(f).selftest);
             if (ok != 0) break;
             losers.push_back(f->stream2);
             f->stream2 = nullptr;
@@ -1027,7 +1005,7 @@ static int engine_warm(cocons_fit *f)
         // probe is over (cocons_fit_destroy waits for the lock) --, and it leaves streams the library does not own alone
         // (cocons_fit_set_stream: a caller's stream may carry the caller's own work).  This handle is not in the registry yet and
         // not in anybody's hands: redrawing ITS streams is safe here, and nowhere later.
-        unsigned *words = f->dflags + 3 * (size_t)f->flags_cap + 8;
+        unsigned *words = handoff_words(f).selftest;
         for (int round = 0; ok == 1 && round < 8; ++round) {
             std::vector<cocons_fit *> others;
             {
@@ -1065,8 +1043,6 @@ static int engine_warm(cocons_fit *f)
             if (again == 0) {
                 // (the redrawn stream shares a queue with this handle's other stream: draw again next round -- the own pair
                 // is what must never share)
-                hipStream_t &other = clash == 1 ? f->stream2 : f->stream;
-                (void)other;
                 bool fixed = false;
                 for (int t2 = 0; t2 < 4 && !fixed; ++t2) {
                     losers.push_back(mine);
@@ -1083,14 +1059,14 @@ static int engine_warm(cocons_fit *f)
         for (hipStream_t l : losers) hipStreamDestroy(l);
         if (ok < 0) { (void)hipGetLastError(); return fail(-100, "engine_warm: stream self-test failed"); }
         if (ok == 0) { f->engine_ok = false; return 0; }
-        HIPCHK(hipMemsetAsync(f->dflags, 0, (4 * (size_t)f->flags_cap + 64) * sizeof(unsigned), f->stream));
+        HIPCHK(hipMemsetAsync(f->dflags, 0, handoff_word_count(f->flags_cap) * sizeof(unsigned), f->stream));
         HIPCHK(hipStreamSynchronize(f->stream));
     }
-    launch_potrf_engine(nullptr, 0, 0, 0, f->dinv, f->dinfo, f->dflags, f->dflags, f->dflags, (unsigned *)(f->dinfo + 1),
-                        f->dflags + 3 * (size_t)f->flags_cap, f->stream2);
-    if (tun().dag)         // the other instantiation of the engine (never dereferences its buffers when t0 >= nt)
-        launch_potrf_engine(nullptr, 0, 0, 0, f->dinv, f->dinfo, f->dflags, f->dflags, f->dflags, (unsigned *)(f->dinfo + 1),
-                            f->dflags + 3 * (size_t)f->flags_cap, f->stream2, f->dinv, f->dinv, 0);
+    const HandoffWords hw = handoff_words(f);
+    EngineLaunch e;
+    e.dinv = f->dinv; e.info = f->dinfo; e.in = e.out = e.xr = hw.in; e.abort_word = hw.abort; e.alive = hw.alive;
+    launch_potrf_engine_warmup(e, false, f->stream2);
+    if (tun().dag) launch_potrf_engine_warmup(e, true, f->stream2);        // the other instantiation of the engine
     HIPCHK(hipGetLastError());
     if (f->stream2) HIPCHK(hipStreamSynchronize(f->stream2));
     return 0;
@@ -1134,17 +1110,12 @@ static int dag_prepare(cocons_fit *f, const FactorView &v)
         HIPCHK(hipStreamSynchronize(f->stream));
         f->dag_nsteps = (int)steps.size(); f->dag_ntasks = ntasks;
         memcpy(f->dag_key, key, sizeof key);
-        const size_t T64 = 2 * (size_t)v.mt;
-        size_t words = 64 + T64 * (T64 + 1) / 2 + (steps.size() + 2) * T64 + steps.size() + 64 + 16 * (steps.size() + 2);
-        words = (words + 31) / 32 * 32;
-        f->ddag_xcnt_off = words;              // the XCDs' own task counters: eight cache lines behind everything else
-        words += 8 * 32;
-        HIPCHK(f->ddag.reserve(words, f->stream, f->stream2));
+        HIPCHK(f->ddag.reserve(dag_words(f, v.mt).total, f->stream, f->stream2));
     }
     HIPCHK(hipMemsetAsync(f->ddag, 0, f->ddag.count() * sizeof(unsigned), f->stream));
     // trace buffer: 4 stamps + one word of hw_where() pairs per task, 8 stamps per tile pair of the engine -- sized by BOTH
     // the task count and the tile count of THIS step table (a later table with fewer tasks and more tiles must not run past it)
-    const size_t trace_elems = (size_t)f->dag_ntasks * 5 + 8 * (size_t)(v.nt + 2);
+    const size_t trace_elems = dag_trace_words(f, v.nt).count;
     if (tun().dag_trace) HIPCHK(f->ddag_trace.reserve(trace_elems, f->stream, f->stream2));
     f->dag_trace_tasks = (tun().dag_trace && f->ddag_trace) ? f->dag_ntasks : 0;      // 0: the buffer does not describe this table
     if (f->dag_trace_tasks)
@@ -1170,11 +1141,10 @@ extern "C" long long cocons_debug_dag_trace(cocons_fit *f, int *nsteps_out, int 
     if (stamps_out) {
         if (!f->ddag_trace || f->dag_trace_tasks != f->dag_ntasks)
             return fail(-1, "cocons_debug_dag_trace: tracing was off (cocons_debug_tune(\"dag_trace\", 1))");
-        HIPCHK(hipMemcpyAsync(stamps_out, f->ddag_trace, (size_t)f->dag_ntasks * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                              f->stream));
+        const DagTraceWords tw = dag_trace_words(f, f->nt);
+        HIPCHK(hipMemcpyAsync(stamps_out, tw.tasks, (size_t)f->dag_ntasks * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream));
         if (engine_out)
-            HIPCHK(hipMemcpyAsync(engine_out, f->ddag_trace + 4 * (size_t)f->dag_ntasks, 8 * (size_t)(f->nt + 2) * sizeof(unsigned long long),
-                                  hipMemcpyDeviceToHost, f->stream));
+            HIPCHK(hipMemcpyAsync(engine_out, tw.engine, tw.engine_count * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream));
     }
     HIPCHK(hipStreamSynchronize(f->stream));
     return (long long)f->dag_ntasks;
@@ -1192,13 +1162,25 @@ extern "C" int cocons_debug_dag_words(cocons_fit *f, int count, unsigned *out)
     return 0;
 }
 
+// the persistent launch of view v on the handle's step table, task words and the hand-off words hw (no trace)
+static DagLaunch dag_launch(cocons_fit *f, const FactorView &v, const HandoffWords &hw, const unsigned *alive)
+{
+    const DagWords w = dag_words(f, v.mt);
+    DagLaunch d;
+    d.A = v.A; d.lda = v.lda; d.P = f->dP; d.Wt = f->dWt; d.steps = f->ddag_steps; d.nsteps = f->dag_nsteps; d.ntasks = f->dag_ntasks;
+    d.queue = w.queue; d.tdone = w.tdone; d.pdone = w.pdone; d.pstride = w.pstride; d.pall = w.pall; d.dcount = w.dcount; d.xcnt = w.xcnt;
+    d.partbuf = f->dpart; d.sig = hw.in; d.out = hw.out; d.xr = hw.xr; d.abort_word = hw.abort;
+    d.alive = alive; d.xcc_quota = dag_xcc_quota(); d.xcd_g = f->dag_xcd_g;
+    if (f->dag_have_ftab) d.ftab = f->ddag_ftab;
+    return d;
+}
+
 static int engine_start(cocons_fit *f, const FactorView &v)
 {
     if (f->engine_live) return 0;
     const int nt = v.nt;
     hipStream_t M = f->stream;
     if (int rc = flags_reset(f, nt)) return rc;
-    unsigned *in = f->dflags, *out = f->dflags + f->flags_cap, *xr = f->dflags + 2 * (size_t)f->flags_cap;
     f->dag_next = dag_wanted(f, v);
     if (f->dag_next) {
         if (int rc = dag_prepare(f, v)) return rc;
@@ -1209,14 +1191,16 @@ static int engine_start(cocons_fit *f, const FactorView &v)
         if (int rc = mbox_reset(f, nt > f->nt ? nt : f->nt)) return rc;
     HIPCHK(hipEventRecord(f->ev_eng, M));                    // (behind the resets of the flag and task words, and of W / P when new)
     HIPCHK(hipStreamWaitEvent(f->stream2, f->ev_eng, 0));
-    unsigned *alive_w = f->dflags + 3 * (size_t)f->flags_cap;
     // (from tile 0: the engine factors the first diagonal block too, its input words raised by the gate kernel -- band-limited
     // views, whose first block is not the engine's, never get the engine: fit_create_taper)
-    launch_potrf_engine(v.A, v.lda, 0, nt, f->dinv, f->dinfo, in, out, xr, (unsigned *)(f->dinfo + 1),
-                        alive_w, f->stream2, f->dag_next ? f->dWt : nullptr,
-                        f->dag_next ? f->dP : nullptr, f->dag_next ? 2 * f->dag_nsteps : 0,
-                        (f->dag_next && f->dag_trace_tasks) ? f->ddag_trace + 4 * (size_t)f->dag_ntasks : nullptr,
-                        f->engine_pair_live ? f->dmbox : nullptr, tun().engine_in_wait_ms);
+    const HandoffWords hw = handoff_words(f);
+    EngineLaunch e;
+    e.A = v.A; e.lda = v.lda; e.nt = nt; e.dinv = f->dinv; e.info = f->dinfo; e.in_wait_ms = tun().engine_in_wait_ms;
+    e.in = hw.in; e.out = hw.out; e.xr = hw.xr; e.abort_word = hw.abort; e.alive = hw.alive;
+    if (f->dag_next) { e.wbuf = f->dWt; e.pbuf = f->dP; e.dag_until = 2 * f->dag_nsteps; }
+    if (f->dag_next && f->dag_trace_tasks) e.trace = dag_trace_words(f, nt).engine;
+    if (f->engine_pair_live) e.mbox = f->dmbox;
+    launch_potrf_engine(e, f->stream2);
     f->engine_live = true;
     return 0;
 }
@@ -1266,10 +1250,15 @@ int factorize(cocons_fit *f, const FactorView &v, std::vector<hipEvent_t> *ev_up
                 double *q = f->dinv + (size_t)(k & 1) * 2048;
                 double *Ak = band_base(v.A, k, v.skew);
                 const int e0 = v.skew ? k + v.skew : nt, e1 = e0 + (mt - nt);      // tile rows under the matrix
-                potrf_solve(f, Ak, v.lda, k, (k + 1) * TILE, e1 * TILE - 64 * v.trim, q, M, hb * TILE, e0 * TILE);
-                if (k + 1 < nt)
-                    launch_update(v.A, v.lda, k * TILE, TILE, k + 1, mt, k + 1, hb < nt ? hb : nt, true, M, nullptr, -1,
-                                  nullptr, nullptr, nullptr, hb, nt, v.skew, v.trim);
+                RowRange rows;
+                rows.r0 = (k + 1) * TILE; rows.r1 = e1 * TILE - 64 * v.trim; rows.band_r1 = hb * TILE; rows.ext_r0 = e0 * TILE;
+                potrf_solve(f, Ak, v.lda, k, rows, q, M);
+                if (k + 1 < nt) {
+                    UpdateLaunch u = v.update(hb);
+                    u.panel_in_c(k * TILE); u.K = TILE; u.ti0 = k + 1; u.ti1 = mt; u.tj0 = k + 1; u.tj1 = hb < nt ? hb : nt; u.lower_only = true;
+                    u.skew = v.skew;
+                    launch_update(u, M);
+                }
             }
             return 0;
         }
@@ -1277,7 +1266,7 @@ int factorize(cocons_fit *f, const FactorView &v, std::vector<hipEvent_t> *ev_up
             panel_ops(f, v, k, M);
             if (k + 2 < nt) {
                 if (ev_upd) count_update_flops(f, 2, k + 2);
-                timed_update(f, v, k, 2, k + 2, nt, M, ev_upd, nullptr, -1, tile_queue(f, k));
+                timed_update(f, v, k, 2, k + 2, nt, M, ev_upd, nullptr, -1, handoff_words(f).tile_queue(k));
             }
         }
         return 0;
@@ -1285,15 +1274,13 @@ int factorize(cocons_fit *f, const FactorView &v, std::vector<hipEvent_t> *ev_up
     if (int rc = engine_start(f, v)) return rc;          // no-op when enqueue_eval started it before the assembly
     f->engine_live = false;
     f->engine_used = true;
-    unsigned *in = f->dflags, *out = f->dflags + f->flags_cap, *xr = f->dflags + 2 * (size_t)f->flags_cap;
-    unsigned *abort_word = (unsigned *)(f->dinfo + 1);
-    unsigned *alive = f->dflags + 3 * (size_t)f->flags_cap;
+    const HandoffWords hw = handoff_words(f);
+    unsigned *const in = hw.in, *const out = hw.out, *const xr = hw.xr, *const abort_word = hw.abort;
+    unsigned *alive = hw.alive;
     if (tun().gate_sabotage > 0) { --tun().gate_sabotage; alive += 1; }      // (tests: a word that stays zero)
-    // (the engine factors the first diagonal block too: the gate raises its input words)
-    launch_engine_gate(alive, abort_word, M, false, f->engine_ops++ == 0,
-                       f->engine_pair_live,       // (the pair partner counts itself)
-                       (tun().gate_sabotage == 0 && alive == f->dflags + 3 * (size_t)f->flags_cap) ? in : nullptr);
-    const int rend = mt * TILE - 64 * v.trim;         // one past the last row any panel kernel touches
+    // (the engine factors the first diagonal block too: the gate raises its input words; the pair partner counts itself)
+    launch_start_gate(alive, abort_word, f->engine_ops++ == 0, f->engine_pair_live,
+                      (tun().gate_sabotage == 0 && alive == hw.alive) ? in : nullptr, M);
     // the panel of the block at tile t (behind the engine's factorisation of it): one launch whose strips follow the pair's tiles
     // through their mailboxes, or three launches that wait for the tiles; returns the tiles of the NEXT diagonal block that the
     // launch has updated (the update launch behind it then leaves them alone)
@@ -1301,27 +1288,29 @@ int factorize(cocons_fit *f, const FactorView &v, std::vector<hipEvent_t> *ev_up
         const bool two = t + 1 < nt;                 // the block has a second tile
         const int r0 = two ? t + 2 : t + 1;          // first tile row below the diagonal block
         const int hb = band_hi(v, t);                // rows of block t's panel: [r0, hb) and the rows under the matrix
-        const int br = hb >= 0 ? hb * TILE : -1, er = nt * TILE;
+        const RowRange rows = v.panel_rows(r0, hb);
         if (two && hb < 0 && tun().panel_fused && f->engine_pair_live && f->dmbox != nullptr) {
             // the next diagonal block (tiles t + 2, t + 3), when there is one, is updated inside this launch
             const int next_tiles = t + 2 < nt ? (t + 3 < nt ? 2 : 1) : 0;
-            const bool dg = allow_diag && next_tiles > 0 && ((size_t)(t >> 1) + 1) * PANEL_SMBOX_DOUBLES <= f->smb_elems;
-            const int nstrips = (rend - r0 * TILE) / 64;
-            const bool sp = tun().panel_split > 0 && nstrips >= tun().panel_split &&
-                            (size_t)nstrips * PANEL_XMBOX_DOUBLES <= f->xmb_elems;
-            launch_panel_pair(v.A, v.lda, t * TILE, r0 * TILE, rend, xr + t, abort_word, M,
-                              f->dmbox + (size_t)t * ENGINE_MBOX_DOUBLES, f->dmbox + (size_t)(t + 1) * ENGINE_MBOX_DOUBLES,
-                              dg ? f->dmbox + f->smb_off + (size_t)(t >> 1) * PANEL_SMBOX_DOUBLES : nullptr,
-                              dg ? (next_tiles == 2 ? 10 : 3) : 0, in, t + 2, sp ? f->dmbox + f->xmb_off : nullptr);
-            return (dg && nstrips >= (next_tiles == 2 ? 4 : 2)) ? next_tiles : 0;
+            const int nstrips = (rows.r1 - rows.r0) / 64;
+            PanelLaunch p;
+            p.A = v.A; p.lda = v.lda; p.c0 = t * TILE; p.rows = rows; p.xr = xr + t; p.abort_word = abort_word;
+            p.mb0 = tile_mbox(f, t); p.mb1 = tile_mbox(f, t + 1); p.sig = in; p.sig_tile = t + 2;
+            if (allow_diag && next_tiles > 0) p.smb = strip_mbox(f, t >> 1);
+            if (p.smb) p.ndiag = next_tiles == 2 ? 10 : 3;
+            if (tun().panel_split > 0 && nstrips >= tun().panel_split) p.xmb = xchg_mbox(f, nstrips);
+            launch_panel_pair(p, M);
+            return (p.smb && nstrips >= (next_tiles == 2 ? 4 : 2)) ? next_tiles : 0;
         }
-        launch_trsm_tile(v.A, v.lda, t * TILE, r0 * TILE, rend, f->dinv + (size_t)(t & 1) * 2048, M,
-                         out + t, abort_word, br, er);
+        TrsmLaunch l;
+        l.A = v.A; l.lda = v.lda; l.c0 = t * TILE; l.rows = rows; l.dinv = f->dinv + (size_t)(t & 1) * 2048; l.wait_word = out + t; l.abort_word = abort_word;
+        launch_trsm_tile(l, M);
         if (two) {
-            launch_update(v.A, v.lda, t * TILE, TILE, r0, mt, t + 1, t + 2, false, M, nullptr, -1, xr + t, abort_word,
-                          nullptr, hb, nt, 0, v.trim);
-            launch_trsm_tile(v.A, v.lda, (t + 1) * TILE, r0 * TILE, rend,
-                             f->dinv + (size_t)((t + 1) & 1) * 2048, M, out + t + 1, abort_word, br, er);
+            UpdateLaunch u = v.update(hb);
+            u.panel_in_c(t * TILE); u.K = TILE; u.ti0 = r0; u.ti1 = mt; u.tj0 = t + 1; u.tj1 = t + 2; u.wait_word = xr + t; u.abort_word = abort_word;
+            launch_update(u, M);
+            l.c0 = (t + 1) * TILE; l.dinv = f->dinv + (size_t)((t + 1) & 1) * 2048; l.wait_word = out + t + 1;
+            launch_trsm_tile(l, M);
         }
         return 0;
     };
@@ -1336,10 +1325,6 @@ int factorize(cocons_fit *f, const FactorView &v, std::vector<hipEvent_t> *ev_up
         // update k are done, and the panels between them are tile tasks of the same launch (the engine publishes the tile
         // inverses they multiply with).  Behind the head a step is bound by its dependency chain, and there the classic
         // sequence below has the shorter one: it takes over with the panel behind the last DAG step.
-        const size_t T64 = 2 * (size_t)mt;
-        unsigned *queue = f->ddag, *tdone = f->ddag + 64, *pdone = tdone + T64 * (T64 + 1) / 2;
-        unsigned *pall = pdone + ((size_t)f->dag_nsteps + 2) * T64;
-        unsigned *dcount = pall + (size_t)f->dag_nsteps + 64;
         hipEvent_t ea = nullptr, eb = nullptr;
         if (ev_upd) {
             const double before = f->upd_flops;
@@ -1348,10 +1333,9 @@ int factorize(cocons_fit *f, const FactorView &v, std::vector<hipEvent_t> *ev_up
             hipEventCreate(&ea); hipEventCreate(&eb);
             hipEventRecord(ea, M);
         }
-        launch_dag(v.A, v.lda, f->dP, f->dWt, f->ddag_steps, f->dag_nsteps, f->dag_ntasks, queue, tdone,
-                   pdone, (int)T64, pall, f->dpart, dcount, in, out, xr, abort_word, M, f->dag_trace_tasks ? f->ddag_trace : nullptr,
-                   alive, dag_xcc_quota(), f->dag_trace_tasks ? (unsigned *)(f->ddag_trace + 4 * (size_t)f->dag_ntasks + 8 * (size_t)(v.nt + 2)) : nullptr,
-                   f->dag_have_ftab ? f->ddag_ftab : nullptr, f->dag_xcd_g, f->ddag + f->ddag_xcnt_off);
+        DagLaunch d = dag_launch(f, v, hw, alive);
+        if (f->dag_trace_tasks) { const DagTraceWords tw = dag_trace_words(f, nt); d.trace = tw.tasks; d.hw = tw.hw; }
+        launch_dag(d, M);
         if (ev_upd) { hipEventRecord(eb, M); ev_upd->push_back(ea); ev_upd->push_back(eb); f->dag_events = 1; }
         k_first = 2 * f->dag_nsteps;
     }
@@ -1367,13 +1351,13 @@ int factorize(cocons_fit *f, const FactorView &v, std::vector<hipEvent_t> *ev_up
         if (tun().host_delay_us > 0 && t + 2 == tun().host_delay_tile) usleep((useconds_t)tun().host_delay_us);
         if (k >= k_first) {                          // (the update with the last DAG step's panel was that launch's)
             if (ev_upd) count_update_flops(f, 2, t);
-            timed_update(f, v, k, 2, t, nt, M, ev_upd, in, t, tile_queue(f, k), diag_done);
+            timed_update(f, v, k, 2, t, nt, M, ev_upd, in, t, hw.tile_queue(k), diag_done);
         }
         diag_done = panel_for(t, k + 4 < nt);
     }
     // no rows under the matrix (right-hand sides in the slots of the last tile): nothing on the main stream has waited for
     // the engine's last tile yet -- what follows (the reductions) must
-    if (mt == nt) launch_engine_gate(out + (nt - 1), abort_word, M, true);
+    if (mt == nt) launch_last_tile_gate(out + (nt - 1), abort_word, M);
     return 0;
 }
 
@@ -1464,10 +1448,11 @@ static void debug_abort_report(cocons_fit *f)
     if (!f->dag_used || !f->ddag || cls < ABORT_DAG_FIRST || cls > ABORT_DAG_LAST) return;
     // a wait of the DAG launch: what it waited for (dag_wait's record) and what the word holds NOW
     unsigned rec[7] = {0, 0, 0, 0, 0, 0, 0}, now = 0, qn = 0;
-    hipMemcpyAsync(rec, f->ddag + 8, sizeof rec, hipMemcpyDeviceToHost, f->stream);
+    const DagWords W = dag_words(f, f->dag_key[1]);       // (the word indices of the record count from the task counter)
+    hipMemcpyAsync(rec, W.wait_record, sizeof rec, hipMemcpyDeviceToHost, f->stream);
     hipStreamSynchronize(f->stream);
-    if (rec[2] < f->ddag.count()) hipMemcpyAsync(&now, f->ddag + rec[2], sizeof now, hipMemcpyDeviceToHost, f->stream);
-    hipMemcpyAsync(&qn, f->ddag, sizeof qn, hipMemcpyDeviceToHost, f->stream);
+    if (rec[2] < f->ddag.count()) hipMemcpyAsync(&now, &W.queue[rec[2]], sizeof now, hipMemcpyDeviceToHost, f->stream);
+    hipMemcpyAsync(&qn, W.queue, sizeof qn, hipMemcpyDeviceToHost, f->stream);
     hipStreamSynchronize(f->stream);
     fprintf(stderr, "cocons: DAG wait: task %u (of %u, counter now %u) code 0x%x waited for word %u >= %u, saw %u, holds %u now; "
             "%.1f ms, %u polls\n", rec[0], f->dag_ntasks, qn, rec[1], rec[2], rec[3], rec[4], now, rec[5] * 1e-5, rec[6]);
@@ -1485,7 +1470,7 @@ static void debug_abort_report(cocons_fit *f)
             fwrite(rec, sizeof rec, 1, fp);
             std::vector<DagStepHost> sh((size_t)f->dag_nsteps);
             hipMemcpyAsync(sh.data(), f->ddag_steps, sh.size() * sizeof(DagStepHost), hipMemcpyDeviceToHost, f->stream);
-            std::vector<unsigned> w((size_t)f->ddag.count()), fl(4 * (size_t)f->flags_cap + 64);
+            std::vector<unsigned> w((size_t)f->ddag.count()), fl(handoff_word_count(f->flags_cap));
             hipMemcpyAsync(w.data(), f->ddag, w.size() * sizeof(unsigned), hipMemcpyDeviceToHost, f->stream);
             hipMemcpyAsync(fl.data(), f->dflags, fl.size() * sizeof(unsigned), hipMemcpyDeviceToHost, f->stream);
             hipStreamSynchronize(f->stream);
@@ -1493,7 +1478,7 @@ static void debug_abort_report(cocons_fit *f)
             fwrite(w.data(), sizeof(unsigned), w.size(), fp);
             fwrite(fl.data(), sizeof(unsigned), fl.size(), fp);
             if (ntr) {
-                std::vector<unsigned long long> st((size_t)f->dag_ntasks * 5 + 8 * (size_t)(f->nt + 2));
+                std::vector<unsigned long long> st(dag_trace_words(f, f->nt).count);
                 hipMemcpyAsync(st.data(), f->ddag_trace, st.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream);
                 hipStreamSynchronize(f->stream);
                 fwrite(st.data(), sizeof(unsigned long long), st.size(), fp);
@@ -1637,7 +1622,7 @@ void dense_collect(cocons_fit *f, double *sum_logliks, double *parts)
 static void slot_stream_apart(cocons_fit *f, cocons_fit *c)
 {
     if (!c->own_stream || !c->dflags) return;
-    unsigned *words = c->dflags + 3 * (size_t)c->flags_cap + 8;
+    unsigned *words = handoff_words(c).selftest;
     std::vector<hipStream_t> losers;
     for (int attempt = 0; attempt < 8; ++attempt) {
         bool clash = false;
@@ -1656,7 +1641,7 @@ static void slot_stream_apart(cocons_fit *f, cocons_fit *c)
     }
     for (hipStream_t l : losers) hipStreamDestroy(l);
     if (c->stream2 && streams_run_concurrently(c->stream2, c->stream, words) == 0) c->engine_ok = false;     // (its own pair again)
-    (void)hipMemsetAsync(c->dflags, 0, (4 * (size_t)c->flags_cap + 64) * sizeof(unsigned), c->stream);
+    (void)hipMemsetAsync(c->dflags, 0, handoff_word_count(c->flags_cap) * sizeof(unsigned), c->stream);
     (void)hipStreamSynchronize(c->stream);
 }
 
@@ -2046,10 +2031,11 @@ static int taper_common(bool pred, int n, int m, int p, const double *theta, con
         HIPCHK_AT("cov_rns_taper*", upload_canon(dXp, X_pred, (size_t)m * p, s));
         HIPCHK_AT("cov_rns_taper*", upload_canon(dlp, locs_pred, (size_t)m * 2, s));
         launch_loc_params(loc_args(m, p, dXp, dlp, dlocp, m, tv, ms.smooth_kind, smooth_limits), s);
-        launch_taper(MODE_GEOM, true, m, nnz, dci, drp, dlocp, m, dloc, n, 0.0, dout, s);
-    } else {
-        launch_taper(ms.mode, false, n, nnz, dci, drp, dloc, n, dloc, n, ms.nu_fixed, dout, s);
     }
+    TaperLaunch t;
+    t.mode = pred ? (int)MODE_GEOM : ms.mode; t.pred = pred; t.nrows = pred ? m : n; t.nnz = nnz; t.ci = dci; t.rp = drp; t.out = dout;
+    t.rows = pred ? dlocp : dloc; t.stride_rows = pred ? m : n; t.cols = dloc; t.stride = n; t.nu_fixed = pred ? 0.0 : ms.nu_fixed;
+    launch_taper(t, s);
     HIPCHK_AT("cov_rns_taper*", hipGetLastError());
     if (nnz > 0) HIPCHK_AT("cov_rns_taper*", hipMemcpyAsync(out, dout, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK_AT("cov_rns_taper*", hipStreamSynchronize(s));
@@ -2177,12 +2163,8 @@ static int dag_replay_run(cocons_fit *f, const FactorView &fv, bool slots, const
     }
     HIPCHK_AT("cocons_debug_dag_replay", dcmp.alloc(2));
     // (3) the launch, alone
-    const size_t T64 = 2 * (size_t)fv.mt;
-    unsigned *in = f->dflags, *outw = f->dflags + f->flags_cap, *xr = f->dflags + 2 * (size_t)f->flags_cap;
-    unsigned *abort_word = (unsigned *)(f->dinfo + 1);
-    unsigned *queue = f->ddag, *tdone = f->ddag + 64, *pdone = tdone + T64 * (T64 + 1) / 2;
-    unsigned *pall = pdone + ((size_t)f->dag_nsteps + 2) * T64;
-    unsigned *dcount = pall + (size_t)f->dag_nsteps + 64;
+    const HandoffWords hw = handoff_words(f);
+    const DagLaunch d = dag_launch(f, fv, hw, hw.alive);
     f->upd_flops = 0.0;
     f->nrhs_cur = nrhs;
     for (int s2 = 0; s2 < f->dag_nsteps; ++s2) count_update_flops(f, 2, 2 * s2 + 2);
@@ -2199,13 +2181,10 @@ static int dag_replay_run(cocons_fit *f, const FactorView &fv, bool slots, const
         HIPCHK_AT("cocons_debug_dag_replay", hipMemsetAsync(f->ddag, 0, f->ddag.count() * sizeof(unsigned), M));
         HIPCHK_AT("cocons_debug_dag_replay", hipMemsetD32Async((hipDeviceptr_t)f->dflags, 0x3fffffff, 3 * (size_t)f->flags_cap, M));   // in / out / xr: all raised
         // (as many workgroups take part as in a real evaluation: the engine and its partner are entered on XCD 0 by hand)
-        unsigned *alive_w = f->dflags + 3 * (size_t)f->flags_cap;
         static const unsigned pair_on_xcd0 = 2u;
-        HIPCHK_AT("cocons_debug_dag_replay", hipMemcpyAsync(alive_w + 16, &pair_on_xcd0, sizeof(unsigned), hipMemcpyHostToDevice, M));
+        HIPCHK_AT("cocons_debug_dag_replay", hipMemcpyAsync(hw.xcd_arrivals, &pair_on_xcd0, sizeof(unsigned), hipMemcpyHostToDevice, M));
         HIPCHK_AT("cocons_debug_dag_replay", hipEventRecord(ev.a, M));
-        launch_dag(fv.A, fv.lda, f->dP, f->dWt, f->ddag_steps, f->dag_nsteps, f->dag_ntasks, queue, tdone,
-                   pdone, (int)T64, pall, f->dpart, dcount, in, outw, xr, abort_word, M, nullptr, alive_w, dag_xcc_quota(), nullptr,
-                   f->dag_have_ftab ? f->ddag_ftab : nullptr, f->dag_xcd_g, f->ddag + f->ddag_xcnt_off);
+        launch_dag(d, M);
         HIPCHK_AT("cocons_debug_dag_replay", hipEventRecord(ev.b, M));
         HIPCHK_AT("cocons_debug_dag_replay", hipGetLastError());
         HIPCHK_AT("cocons_debug_dag_replay", hipStreamSynchronize(M));

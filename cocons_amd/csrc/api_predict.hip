@@ -417,8 +417,11 @@ extern "C" int cocons_predict_taper(cocons_fit *f, const double *theta, const do
         launch_loc_params(loc_args(m, p, f->dXp, f->dlocsp, f->dlocp, m, tv, ms.smooth_kind, f->smooth_limits), s);
         // (the observation side after the entries of S were computed from it: stream order)
         launch_loc_params(loc_args(n, p, f->dX, f->dlocs, f->dloc, f->npad, tv, ms.smooth_kind, f->smooth_limits), s);
-        launch_taper(MODE_GEOM, true, m, nnz_pred, dci, drp, f->dlocp, m, f->dloc, f->npad, 0.0, nullptr, s,
-                     dtv, f->dA, f->lda, f->npad + 1, f->skew, f->npad);
+        TaperLaunch t;
+        t.mode = MODE_GEOM; t.pred = true; t.nrows = m; t.nnz = nnz_pred; t.ci = dci; t.rp = drp;
+        t.rows = f->dlocp; t.stride_rows = m; t.cols = f->dloc; t.stride = f->npad;
+        t.tapv = dtv; t.A = f->dA; t.lda = f->lda; t.row0 = f->npad + 1; t.skew = f->skew; t.npad = f->npad;
+        launch_taper(t, s);
         if (int rc = factorize(f, main_view(f), nullptr)) return rc;
         launch_row_reduce(f->dA, f->lda, n, f->npad, f->npad + 1, m, f->dstoch, f->dquad, f->dred, s, f->skew, f->npad);
         HIPCHK_AT("cocons_predict_taper", hipMemcpyAsync(stochastic, f->dstoch, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));

@@ -252,23 +252,27 @@ static int shard_factor_diag(cocons_fit *f, int k)
         // the whole block in ONE launch of the diagonal-block engine (tile, strip solve, tile update, tile: what the four
         // launches below do, without their three boundaries -- this block is the chain every rank waits for, section 5): its
         // input words are raised beforehand, so it never waits, and it leaves behind the block of its second tile
-        unsigned *in = f->dflags, *out = f->dflags + f->flags_cap, *xr = f->dflags + 2 * (size_t)f->flags_cap;
-        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(in + t), 7, (size_t)w, s));
+        const HandoffWords hw = handoff_words(f);
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(hw.in + t), 7, (size_t)w, s));
+        EngineLaunch e;
+        e.A = A; e.lda = f->lda; e.t0 = t; e.nt = t + w; e.dinv = f->dinv; e.info = f->dinfo;
+        e.in = hw.in; e.out = hw.out; e.xr = hw.xr; e.abort_word = hw.abort; e.alive = hw.alive;
         // (pair mode: its two workgroups side by side -- the second tile's factorisation starts ~6 us behind the first's end
         // instead of behind the strip solve and the tile update: 78 -> ~56 us for the block)
-        const bool pair = w == 2 && tun().engine_pair && f->dmbox && f->smb_off >= ((size_t)f->nt + 2) * ENGINE_MBOX_DOUBLES;
-        launch_potrf_engine(A, f->lda, t, t + w, f->dinv, f->dinfo, in, out, xr, (unsigned *)(f->dinfo + 1),
-                            f->dflags + 3 * (size_t)f->flags_cap, s, nullptr, nullptr, 0, nullptr,
-                            pair ? f->dmbox : nullptr);
+        if (w == 2 && tun().engine_pair && tile_mbox(f, f->nt + 1)) e.mbox = tile_mbox(f, 0);
+        launch_potrf_engine(e, s);
     } else {
         launch_potrf_tile(A, f->lda, t * TILE, q0, f->dinfo, s);
         if (w == 2) {
-            launch_trsm_tile(A, f->lda, t * TILE, (t + 1) * TILE, (t + 2) * TILE, q0, s);
-            launch_update(A, f->lda, t * TILE, TILE, t + 1, t + 2, t + 1, t + 2, true, s);
+            TrsmLaunch l;
+            l.A = A; l.lda = f->lda; l.c0 = t * TILE; l.rows.r0 = (t + 1) * TILE; l.rows.r1 = (t + 2) * TILE; l.dinv = q0;
+            launch_trsm_tile(l, s);
+            UpdateLaunch u;
+            u.C = A; u.ldc = f->lda; u.panel_in_c(t * TILE); u.K = TILE; u.ti0 = u.tj0 = t + 1; u.ti1 = u.tj1 = t + 2; u.lower_only = true;
+            launch_update(u, s);
             launch_potrf_tile(A, f->lda, (t + 1) * TILE, q1, f->dinfo, s);
         }
     }
-    (void)q1;
     double *L = S->lkk[k & 1];
     HIPCHK(hipMemcpy2DAsync(L, (size_t)PT * TILE * sizeof(double), A + (size_t)t * TILE + (size_t)t * TILE * f->lda,
                             f->lda * sizeof(double), (size_t)w * TILE * sizeof(double), (size_t)w * TILE,
@@ -432,16 +436,24 @@ static int shard_step_pre(cocons_fit *f, int k, int nb)
     }
     if (tn >= mt) return 0;                                            // nothing below the block
     if (P.cnt[(size_t)k * W + rank] > 0) {
-        launch_trsm_tile(A, f->lda, t * TILE, tn * TILE, mt * TILE, f->dinv, s, nullptr, nullptr, -1, 0, W, rank, G);
+        TrsmLaunch l;
+        l.A = A; l.lda = f->lda; l.c0 = t * TILE; l.rows.r0 = tn * TILE; l.rows.r1 = mt * TILE; l.dinv = f->dinv; l.own_world = W; l.own_rank = rank; l.own_group = G;
+        launch_trsm_tile(l, s);
         if (w == 2) {
-            launch_update_from(A, f->lda, A + (size_t)t * TILE * f->lda, f->lda, TILE, tn, mt, t + 1, t + 2, false, s, G, W, rank);
-            launch_trsm_tile(A, f->lda, (t + 1) * TILE, tn * TILE, mt * TILE, f->dinv + 2048, s, nullptr, nullptr, -1, 0, W, rank, G);
+            UpdateLaunch u;
+            u.C = A; u.ldc = f->lda; u.P = A + (size_t)t * TILE * f->lda; u.ldp = f->lda;      // (kblk stays 0: a dense buffer)
+            u.K = TILE; u.ti0 = tn; u.ti1 = mt; u.tj0 = t + 1; u.tj1 = t + 2; u.group = G; u.world = W; u.rank = rank;
+            launch_update(u, s);
+            l.c0 = (t + 1) * TILE; l.dinv = f->dinv + 2048;
+            launch_trsm_tile(l, s);
         }
     }
     if (tn >= P.nt) return 0;                                          // last block: only right-hand-side rows below, no exchange
     if (k + 1 < nb && rank == shard_owner(k + 1, W)) {
         const int w1 = P.ncols[k + 1] / TILE;
-        launch_update(A, f->lda, t * TILE, w * TILE, tn, tn + w1, tn, tn + w1, true, s);     // own rows of X: local
+        UpdateLaunch u;                                                                      // own rows of X: local
+        u.C = A; u.ldc = f->lda; u.panel_in_c(t * TILE); u.K = w * TILE; u.ti0 = u.tj0 = tn; u.ti1 = u.tj1 = tn + w1; u.lower_only = true;
+        launch_update(u, s);
         if (int rc = shard_factor_diag(f, k + 1)) return rc;
     }
     const long long slot = (long long)P.srows[k] * P.ncols[k];
@@ -464,10 +476,11 @@ static int shard_step_post(cocons_fit *f, int k, int nb)
     if (P.cnt[(size_t)k * W + rank] > 0) {
         // (the owner of block k + 1 has updated that diagonal block with its own rows already: shard_step_pre)
         const bool ahead = k + 1 < nb && rank == shard_owner(k + 1, W);
-        const int skip_lo = ahead ? 2 * tn : 0, skip_hi = ahead ? 2 * (tn + P.ncols[k + 1] / TILE) : 0;
-        launch_update_from(f->dA, f->lda, f->xbuf[k & 1], (size_t)P.srows[k], w * TILE, tn, P.mt, tn, P.nt, true, f->stream,
-                           G, W, rank, nullptr, -1, nullptr, nullptr, nullptr, -1, 0, 0, 0, 0,
-                           S->d_pmap + (size_t)k * 2 * P.mt, skip_lo, skip_hi);
+        UpdateLaunch u;
+        u.C = f->dA; u.ldc = f->lda; u.P = f->xbuf[k & 1]; u.ldp = (size_t)P.srows[k]; u.K = w * TILE; u.ti0 = tn; u.ti1 = P.mt; u.tj0 = tn; u.tj1 = P.nt; u.lower_only = true;
+        u.group = G; u.world = W; u.rank = rank; u.pmap = S->d_pmap + (size_t)k * 2 * P.mt;
+        if (ahead) { u.skip_lo = 2 * tn; u.skip_hi = 2 * (tn + P.ncols[k + 1] / TILE); }
+        launch_update(u, f->stream);
     }
     HIPCHK(hipGetLastError());
     return 0;

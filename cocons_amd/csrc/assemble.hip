@@ -244,16 +244,16 @@ taper_kernel(TaperArgs a)
     else a.out[w] = v;
 }
 
-void launch_taper(int mode, bool pred, int nrows, int nnz, const int *ci, const int *rp, const double *rows,
-                  size_t stride_rows, const double *cols, size_t stride, double nu_fixed, double *out, hipStream_t s,
-                  const double *tapv, double *A, size_t lda, int row0, int skew, int npad)
+void launch_taper(const TaperLaunch &t, hipStream_t s)
 {
+    const int nnz = t.nnz, mode = t.mode;
+    const bool pred = t.pred;
     if (nnz <= 0) return;
     TaperArgs a;
-    a.skew = skew; a.npad = npad;
-    a.nrows = nrows; a.nnz = nnz; a.ci = ci; a.rp = rp; a.rows = rows; a.stride_rows = stride_rows;
-    a.cols = cols; a.stride = stride; a.nu_fixed = nu_fixed; a.out = out;
-    a.tapv = tapv; a.A = A; a.lda = lda; a.row0 = row0;
+    a.skew = t.skew; a.npad = t.npad;
+    a.nrows = t.nrows; a.nnz = nnz; a.ci = t.ci; a.rp = t.rp; a.rows = t.rows; a.stride_rows = t.stride_rows;
+    a.cols = t.cols; a.stride = t.stride; a.nu_fixed = t.nu_fixed; a.out = t.out;
+    a.tapv = t.tapv; a.A = t.A; a.lda = t.lda; a.row0 = t.row0;
     dim3 g((nnz + 255) / 256), b(256);
     if (pred) { hipLaunchKernelGGL((taper_kernel<MODE_GEOM, true>), g, b, 0, s, a); return; }
     switch (mode) {

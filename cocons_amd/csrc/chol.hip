@@ -2658,17 +2658,20 @@ int streams_run_concurrently(hipStream_t first, hipStream_t second, unsigned *wo
     return h[1] == 0 ? 1 : 0;
 }
 
-void launch_engine_gate(unsigned *alive, unsigned *abort_word, hipStream_t s, bool last_tile, bool patient, int nhelp,
-                        unsigned *raise_in)
+// the start-up gate (is the engine resident? 5 ms, code 0x600).  patient: that of a handle's FIRST engine-schedule operation -- 50 ms
+// instead of 5: whatever a first dispatch on a fresh stream may still cost the runtime (the warm-up launch of the handle has
+// paid what it can) must not be mistaken for "every CU is taken by someone else"
+void launch_start_gate(unsigned *alive, unsigned *abort_word, bool patient, int nhelp, unsigned *raise_in, hipStream_t s)
 {
-    // last_tile: not the start-up gate (is the engine resident? 5 ms, code 0x600) but the wait of the reductions for the
-    // engine's LAST diagonal tile when no panel kernel has waited for it (code 0x900, the hand-offs' 100 ms bound)
-    // patient: the start-up gate of a handle's FIRST engine-schedule operation -- 50 ms instead of 5: whatever a first
-    // dispatch on a fresh stream may still cost the runtime (the warm-up launch of the handle has paid what it can) must
-    // not be mistaken for "every CU is taken by someone else"
-    hipLaunchKernelGGL(engine_gate_kernel, dim3(1), dim3(64), 0, s, alive, abort_word, last_tile ? ABORT_LAST_TILE : ABORT_GATE,
-                       last_tile ? ENGINE_TIMEOUT_TICKS : (patient ? 10 * GATE_TIMEOUT_TICKS : GATE_TIMEOUT_TICKS),
-                       (unsigned)(last_tile || nhelp < 0 ? 0 : nhelp), last_tile ? nullptr : raise_in);
+    hipLaunchKernelGGL(engine_gate_kernel, dim3(1), dim3(64), 0, s, alive, abort_word, ABORT_GATE,
+                       patient ? 10 * GATE_TIMEOUT_TICKS : GATE_TIMEOUT_TICKS, (unsigned)(nhelp < 0 ? 0 : nhelp), raise_in);
+}
+
+// the wait of the reductions for the engine's LAST diagonal tile (its out[] word) when no panel kernel has waited for it (code
+// 0x900, the hand-offs' 100 ms bound)
+void launch_last_tile_gate(unsigned *out_word, unsigned *abort_word, hipStream_t s)
+{
+    hipLaunchKernelGGL(engine_gate_kernel, dim3(1), dim3(64), 0, s, out_word, abort_word, ABORT_LAST_TILE, ENGINE_TIMEOUT_TICKS, 0u, (unsigned *)nullptr);
 }
 
 // Dynamic LDS of the engine.  136 KB: the 128 KB LDS copy of X plus the flag word; leaves room for ONE update workgroup
@@ -2685,24 +2688,19 @@ static size_t engine_lds_bytes()
     return shm;
 }
 
-// t0 >= nt: the kernel is launched all the same, raises its alive word and leaves at once -- the WARM-UP launch of a
-// handle (api.hip): whatever the first dispatch of this kernel on this stream costs the runtime (queue set-up, code
-// object, LDS configuration) is paid there and not inside the bounded gate of the first engine-schedule operation.
-void launch_potrf_engine(double *A, size_t lda, int t0, int nt, double *dinv, int *info,
-                         unsigned *in, unsigned *out, unsigned *xr, unsigned *abort_word, unsigned *alive, hipStream_t s,
-                         double *wbuf, double *pbuf, int dag_until, unsigned long long *trace, double *mbox, int in_wait_ms)
+void launch_potrf_engine(const EngineLaunch &l, hipStream_t s)
 {
     EngineArgs e;
-    e.A = A; e.lda = lda; e.t0 = t0; e.nt = nt; e.dinv = dinv; e.info = info;
-    e.in = in; e.out = out; e.xr = xr; e.abort_word = abort_word; e.alive = alive;
-    e.wbuf = wbuf; e.pbuf = pbuf; e.dag_until = dag_until; e.trace = trace;
-    e.in_ticks = in_wait_ms > 0 ? 100000ull * (unsigned long long)in_wait_ms : HOST_PACED_TICKS;
+    e.A = l.A; e.lda = l.lda; e.t0 = l.t0; e.nt = l.nt; e.dinv = l.dinv; e.info = l.info;
+    e.in = l.in; e.out = l.out; e.xr = l.xr; e.abort_word = l.abort_word; e.alive = l.alive;
+    e.wbuf = l.wbuf; e.pbuf = l.pbuf; e.dag_until = l.dag_until; e.trace = l.trace;
+    e.in_ticks = l.in_wait_ms > 0 ? 100000ull * (unsigned long long)l.in_wait_ms : HOST_PACED_TICKS;
     // (mbox: pair mode -- the partner is workgroup 8: with the round robin over the eight XCDs, the next one on workgroup 0's XCD)
-    e.mbox = mbox;
-    e.partner = mbox ? 8 : 0;
+    e.mbox = l.mbox;
+    e.partner = l.mbox ? 8 : 0;
     const int grid = e.partner ? e.partner + 1 : 1;
     const size_t shm = engine_lds_bytes();
-    if (wbuf && pbuf) {
+    if (l.wbuf && l.pbuf) {
         static std::atomic<unsigned long long> attr_done{0};
         set_dynamic_lds_once((const void *)potrf_engine_kernel<true>, shm, attr_done);
         hipLaunchKernelGGL(potrf_engine_kernel<true>, dim3(grid), dim3(512), shm, s, e);
@@ -2713,46 +2711,49 @@ void launch_potrf_engine(double *A, size_t lda, int t0, int nt, double *dinv, in
     }
 }
 
-void launch_trsm_tile(double *A, size_t lda, int c0, int r0, int r1, const double *dinv, hipStream_t s,
-                      unsigned *wait_word, unsigned *abort_word, int band_r1, int ext_r0, int own_world, int own_rank,
-                      int own_group)
+// t0 >= nt: the kernel is launched all the same, raises its alive word and leaves at once -- the WARM-UP launch of a
+// handle (api.hip): whatever the first dispatch of this kernel on this stream costs the runtime (queue set-up, code
+// object, LDS configuration) is paid there and not inside the bounded gate of the first engine-schedule operation.
+void launch_potrf_engine_warmup(EngineLaunch e, bool dag, hipStream_t s)
 {
-    // rows [r0, r1), or -- band-limited -- [r0, band_r1) and [ext_r0, r1)
-    int nb1 = ((band_r1 >= 0 ? band_r1 : r1) - r0) / 64, nb2 = band_r1 >= 0 ? (r1 - ext_r0) / 64 : 0;
-    if (nb1 < 0) nb1 = 0;
-    if (nb2 < 0) nb2 = 0;
-    if (nb1 + nb2 <= 0) return;
-    hipLaunchKernelGGL(trsm_tile_kernel, dim3(nb1 + nb2), dim3(256), 0, s, A, lda, c0, r0, dinv, wait_word, abort_word,
-                       nb1, ext_r0, own_world, own_rank, own_group < 1 ? 1 : own_group);
+    e.A = nullptr; e.lda = 0; e.t0 = 0; e.nt = 0; e.dag_until = 0; e.trace = nullptr; e.mbox = nullptr; e.in_wait_ms = 0;
+    e.wbuf = e.pbuf = dag ? e.dinv : nullptr;      // (only which instantiation: never dereferenced when t0 >= nt)
+    launch_potrf_engine(e, s);
 }
 
-// rows like launch_trsm_tile: [r0, r1), or -- band-limited -- [r0, band_r1) and [ext_r0, r1); mbox: the tile's mailbox, filled
-// with the pattern ~0 by the caller
-void launch_potrf_follow(double *A, size_t lda, int c0, int r0, int r1, double *dinv, int *info, double *mbox,
-                         unsigned *abort_word, hipStream_t s, int band_r1, int ext_r0)
+void launch_trsm_tile(const TrsmLaunch &l, hipStream_t s)
 {
-    int nb1 = ((band_r1 >= 0 ? band_r1 : r1) - r0) / 64, nb2 = band_r1 >= 0 ? (r1 - ext_r0) / 64 : 0;
-    if (nb1 < 0) nb1 = 0;
-    if (nb2 < 0) nb2 = 0;
+    int nb1, nb2;
+    l.rows.strips(nb1, nb2);
+    if (nb1 + nb2 <= 0) return;
+    hipLaunchKernelGGL(trsm_tile_kernel, dim3(nb1 + nb2), dim3(256), 0, s, l.A, l.lda, l.c0, l.rows.r0, l.dinv, l.wait_word,
+                       l.abort_word, nb1, l.rows.ext_r0, l.own_world, l.own_rank, l.own_group < 1 ? 1 : l.own_group);
+}
+
+// mbox: the tile's mailbox, filled with the pattern ~0 by the caller
+void launch_potrf_follow(const TrsmLaunch &l, hipStream_t s)
+{
+    int nb1, nb2;
+    l.rows.strips(nb1, nb2);
     const int nstrips = nb1 + nb2;
     static std::atomic<unsigned long long> attr_done{0};
     const size_t shm = 76 * 1024;               // the tile's image and its Q operands (74 KB); a follower's two stages: 36 KB
     set_dynamic_lds_once((const void *)potrf_follow_kernel, shm, attr_done);
-    hipLaunchKernelGGL(potrf_follow_kernel, dim3(1 + (nstrips + 1) / 2), dim3(512), shm, s, A, lda, c0, dinv, info, mbox, r0, nb1,
-                       ext_r0, nstrips, abort_word);
+    hipLaunchKernelGGL(potrf_follow_kernel, dim3(1 + (nstrips + 1) / 2), dim3(512), shm, s, l.A, l.lda, l.c0, l.dinv, l.info, l.mbox,
+                       l.rows.r0, nb1, l.rows.ext_r0, nstrips, l.abort_word);
 }
 
-void launch_panel_pair(double *A, size_t lda, int c0, int r0, int r1, unsigned *xr, unsigned *abort_word, hipStream_t s,
-                       const double *mb0, const double *mb1, double *smb, int ndiag, unsigned *sig, int sig_tile, double *xmb)
+void launch_panel_pair(const PanelLaunch &l, hipStream_t s)
 {
-    const int nb = (r1 - r0) / 64;
+    const int nb = (l.rows.r1 - l.rows.r0) / 64;
     if (nb <= 0) return;
-    const bool split = xmb != nullptr;            // (two workgroups per strip: see the kernel)
+    const bool split = l.xmb != nullptr;          // (two workgroups per strip: see the kernel)
     // (ndiag = 10 or 3: the next diagonal block -- two tiles or one -- is updated by as many extra workgroups, which follow the
     // first 4 or 2 strips through the strip mailbox smb)
-    const bool diag = smb && ndiag > 0 && nb >= (ndiag == 10 ? 4 : 2);
-    hipLaunchKernelGGL(panel_pair_kernel, dim3((split ? 2 * nb : nb) + (diag ? ndiag : 0)), dim3(256), 0, s, A, lda, c0, r0,
-                       xr, abort_word, mb0, mb1, diag ? smb : nullptr, nb, diag ? (ndiag == 10 ? 4 : 2) : 0, sig, sig_tile, xmb);
+    const bool diag = l.smb && l.ndiag > 0 && nb >= (l.ndiag == 10 ? 4 : 2);
+    hipLaunchKernelGGL(panel_pair_kernel, dim3((split ? 2 * nb : nb) + (diag ? l.ndiag : 0)), dim3(256), 0, s, l.A, l.lda, l.c0,
+                       l.rows.r0, l.xr, l.abort_word, l.mb0, l.mb1, diag ? l.smb : nullptr, nb,
+                       diag ? (l.ndiag == 10 ? 4 : 2) : 0, l.sig, l.sig_tile, l.xmb);
 }
 
 // waves per workgroup of the trailing update (COCONS_UPD_WAVES: 4 or 8, see update_kernel's NW)
@@ -2763,17 +2764,25 @@ void set_update_w8_max_tiles(int ntiles) { upd_w8_max_tiles = ntiles < 0 ? 0 : n
 static int upd_c_wt = 0;
 void set_update_c_wt(int on) { upd_c_wt = on ? 1 : 0; }
 
-void launch_update_from(double *A, size_t lda, const double *P, size_t ldp, int K,
-                        int ti0, int ti1, int tj0, int tj1, bool lower_only, hipStream_t s,
-                        int ptiles, int world, int rank, unsigned *sig, int sig_tile,
-                        unsigned *wait_word, unsigned *abort_word, unsigned *queue, int band_hi, int ext0,
-                        int skew, int kblk, int trim64, const int *pmap, int skip_lo, int skip_hi)
+int device_cus()
+{
+    static const int cus = [] {
+        int dev = 0, n = 256;
+        (void)hipGetDevice(&dev);
+        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+        return n;
+    }();
+    return cus;
+}
+
+void launch_update(const UpdateLaunch &u, hipStream_t s)
 {
     // tile rows [ti0, ti1), or -- band-limited -- [ti0, band_hi) and [ext0, ti1)
-    const bool band = band_hi >= 0;
+    const int K = u.K, ti0 = u.ti0, ti1 = u.ti1, tj0 = u.tj0, tj1 = u.tj1, band_hi = u.band_hi, ext0 = u.ext0;
+    const bool band = band_hi >= 0, lower_only = u.lower_only;
     const int rows_band = (band ? band_hi : ti1) - ti0, rows_ext = band ? ti1 - ext0 : 0;
     if (rows_band + rows_ext <= 0 || rows_band < 0 || rows_ext < 0 || tj1 <= tj0 || K <= 0) return;
-    trim64 = trim64 ? 1 : 0;
+    const int trim64 = u.trim64 ? 1 : 0;
     const int rows64 = 2 * (rows_band + rows_ext) - trim64;        // 64-row tiles the launch covers
     if (rows64 <= 0) return;
     if (upd_waves < 0) { const char *e = getenv("COCONS_UPD_WAVES"); set_update_waves(e ? atoi(e) : 8); }
@@ -2781,13 +2790,12 @@ void launch_update_from(double *A, size_t lda, const double *P, size_t ldp, int 
     bool use_w8 = false;
     UpdArgs a;
     a.queue = nullptr; a.ntiles = 0;
-    a.skew = skew; a.kblk = kblk; a.c_wt = upd_c_wt;
+    a.skew = u.skew; a.kblk = u.kblk; a.c_wt = upd_c_wt;
     a.Hb = 2 * rows_band; a.ext0 = 2 * ext0;
-    a.C = A; a.ldc = lda; a.P = P; a.ldp = ldp; a.K = K;
+    a.C = u.C; a.ldc = u.ldc; a.P = u.P; a.ldp = u.ldp; a.K = K;
     a.lower_only = lower_only ? 1 : 0;
-    a.ptiles = ptiles < 1 ? 1 : ptiles; a.world = world; a.rank = rank; a.pmap = pmap; a.skip_lo = skip_lo; a.skip_hi = skip_hi;
-    a.sig = sig; a.sig_tile = sig_tile;
-    a.wait_word = wait_word; a.abort_word = abort_word;
+    a.ptiles = u.group < 1 ? 1 : u.group; a.world = u.world; a.rank = u.rank; a.pmap = u.pmap; a.skip_lo = u.skip_lo; a.skip_hi = u.skip_hi;
+    a.sig = u.sig; a.sig_tile = u.sig_tile; a.wait_word = u.wait_word; a.abort_word = u.abort_word;
     a.H = 0; a.W = 0;
     // 64 x 64 tiles throughout (the 128 x 128 shape measured 31 TFLOP/s against 50): tile indices in
     // units of 64 from here on
@@ -2800,30 +2808,24 @@ void launch_update_from(double *A, size_t lda, const double *P, size_t ldp, int 
             const long long H = rows64, W = 2LL * (tj1 - tj0);
             a.H = (int)H; a.W = (int)W;
             const long long total = W * H - W * (W - 1) / 2;
-            static int slots = 0;
-            if (!slots) {
-                int dev = 0, cus = 256;
-                hipGetDevice(&dev);
-                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-                slots = 8 * cus;
-            }
+            const int slots = resident_slots();
             grid = dim3((unsigned)total, 1);
-            if (queue && world == 1) {
+            if (u.queue && u.world == 1) {
                 // dynamic tile order: as many workgroups as the chip holds (8 per CU), tiles off *queue (zero now)
                 // (one CU's worth fewer: the engine owns a CU, and a workgroup that is not resident from the
                 // start would take its first, static tile late)
-                const bool w8 = upd_waves == 8 && K >= 2 * TILE && !skew &&
+                const bool w8 = upd_waves == 8 && K >= 2 * TILE && !u.skew &&
                                 (upd_w8_max_tiles == 0 || total <= upd_w8_max_tiles);
                 use_w8 = w8;
                 const int cap = w8 ? slots / 2 - 4 : slots - 8;       // resident workgroups: 4 or 8 per CU, one CU's worth fewer
                 if (total > cap + (w8 ? 4 : 8)) {
-                    a.queue = queue; a.ntiles = (unsigned)total;
+                    a.queue = u.queue; a.ntiles = (unsigned)total;
                     grid = dim3((unsigned)cap, 1);
                 }
             }
         }
     }
-    const bool trailing = (K > TILE) && world == 1;     // (the first trailing update has K = 256 - front padding: still role 0)
+    const bool trailing = (K > TILE) && u.world == 1;     // (the first trailing update has K = 256 - front padding: still role 0)
     if (trailing && use_w8 && a.lower_only) hipLaunchKernelGGL((update_kernel<64, 16, 0, 8>), grid, dim3(512), 0, s, a);
     else if (trailing) hipLaunchKernelGGL((update_kernel<64, 8, 0>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((update_kernel<64, 8, 1>), grid, dim3(256), 0, s, a);
@@ -2998,40 +3000,21 @@ unsigned dag_build_steps(int nt, int mt, int trim64, int kskip, int lead, int mi
     return base;
 }
 
-void launch_dag(double *A, size_t lda, double *P, const double *Wt, const DagStepHost *dsteps, int nsteps, unsigned ntasks,
-                unsigned *queue, unsigned *tdone, unsigned *pdone, int pstride, unsigned *pall, double *partbuf, unsigned *dcount,
-                unsigned *sig, unsigned *out, unsigned *xr, unsigned *abort_word, hipStream_t s, unsigned long long *trace,
-                const unsigned *alive, int xcc_quota, unsigned *hw, const unsigned *ftab, int xcd_g, unsigned *xcnt)
+void launch_dag(const DagLaunch &d, hipStream_t s)
 {
     static_assert(sizeof(DagStepHost) == sizeof(DagStep), "host and device step records");
-    if (nsteps <= 0 || ntasks == 0) return;
+    if (d.nsteps <= 0 || d.ntasks == 0) return;
     DagArgs a;
-    a.A = A; a.lda = lda; a.P = P; a.Wt = Wt;
-    a.steps = (const DagStep *)dsteps; a.nsteps = nsteps; a.ntasks = ntasks;
-    a.queue = queue; a.tdone = tdone; a.pdone = pdone; a.pstride = pstride; a.pall = pall;
-    a.partbuf = partbuf; a.dcount = dcount;
-    a.sig = sig; a.out = out; a.xr = xr; a.abort_word = abort_word; a.trace = trace; a.hw = trace ? hw : nullptr;
-    static int slots = 0;
-    if (!slots) {
-        int dev = 0, cus = 256;
-        hipGetDevice(&dev);
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        slots = 8 * cus;
-    }
-    const unsigned cap = (unsigned)(slots - 8);          // one CU's worth fewer: the engine owns a CU
-    a.alive = alive; a.xcc_quota = (alive && xcc_quota > 0) ? (unsigned)xcc_quota : 0u;
-    a.ftab = ftab; a.xcd_g = (ftab && xcnt && xcd_g > 0) ? (unsigned)xcd_g : 0u;
-    a.xcnt = xcnt;
-    hipLaunchKernelGGL(dag_kernel, dim3(ntasks < cap ? ntasks : cap), dim3(256), 0, s, a);
-}
-
-void launch_update(double *A, size_t lda, int k0, int K, int ti0, int ti1, int tj0, int tj1,
-                   bool lower_only, hipStream_t s, unsigned *sig, int sig_tile,
-                   unsigned *wait_word, unsigned *abort_word, unsigned *queue, int band_hi, int ext0,
-                   int skew, int trim64, int skip_lo, int skip_hi)
-{
-    launch_update_from(A, lda, A + (size_t)k0 * lda, lda, K, ti0, ti1, tj0, tj1, lower_only, s, 1, 1, 0, sig, sig_tile,
-                       wait_word, abort_word, queue, band_hi, ext0, skew, k0 / TILE, trim64, nullptr, skip_lo, skip_hi);
+    a.A = d.A; a.lda = d.lda; a.P = d.P; a.Wt = d.Wt;
+    a.steps = (const DagStep *)d.steps; a.nsteps = d.nsteps; a.ntasks = d.ntasks;
+    a.queue = d.queue; a.tdone = d.tdone; a.pdone = d.pdone; a.pstride = d.pstride; a.pall = d.pall;
+    a.partbuf = d.partbuf; a.dcount = d.dcount;
+    a.sig = d.sig; a.out = d.out; a.xr = d.xr; a.abort_word = d.abort_word; a.trace = d.trace; a.hw = d.trace ? d.hw : nullptr;
+    const unsigned cap = (unsigned)(resident_slots() - 8);          // one CU's worth fewer: the engine owns a CU
+    a.alive = d.alive; a.xcc_quota = (d.alive && d.xcc_quota > 0) ? (unsigned)d.xcc_quota : 0u;
+    a.ftab = d.ftab; a.xcd_g = (d.ftab && d.xcnt && d.xcd_g > 0) ? (unsigned)d.xcd_g : 0u;
+    a.xcnt = d.xcnt;
+    hipLaunchKernelGGL(dag_kernel, dim3(d.ntasks < cap ? d.ntasks : cap), dim3(256), 0, s, a);
 }
 
 void launch_finalize_cols(const double *A, size_t lda, int c0, int c1, int n, int row0, int nr,

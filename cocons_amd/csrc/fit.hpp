@@ -214,6 +214,12 @@ struct TaperGradState {
     long long bytes = 0;          // device bytes of the buffers above
 };
 
+// elements of the three parts of the mailbox buffer (dmbox; the accessors are below the handle)
+struct MboxLayout {
+    size_t tiles = 0, smb = 0, xmb = 0;
+    size_t total() const { return tiles + smb + xmb; }
+};
+
 // ---------------------------------------------------------------------------
 // Every device buffer of the handle is a DevBuf member (freed with the handle, cocons_fit_destroy), every host container a
 // member by value; a feature that needs another buffer declares one.
@@ -251,9 +257,8 @@ struct cocons_fit {
     hipEvent_t ev[8] = {};
     hipStream_t stream2 = nullptr;     // stream the resident diagonal-tile engine is launched on
     hipEvent_t ev_eng = nullptr;  // orders the engine launch behind the reset of its flag words
-    DevBuf<unsigned> dflags;      // flags_cap words each: in[t], out[t], xr[t] (see launch_potrf_engine); 64: the alive word;
-                                  // flags_cap: tile counters of the trailing updates
-    int flags_cap = 0;            // (also the stride between in[], out[] and xr[]: not just dflags' count)
+    DevBuf<unsigned> dflags;      // the hand-off words: handoff_words() below is their map
+    int flags_cap = 0;            // (the stride between in[], out[] and xr[]: not just dflags' count)
     bool engine_ok = false;       // false: this handle never uses the resident engine (batch slots, band-limited taper fits)
     bool engine_live = false;     // the engine of the NEXT factorize call is already launched (engine_start)
     bool engine_used = false;     // the factorisation enqueued last runs on the engine schedule
@@ -271,22 +276,19 @@ struct cocons_fit {
     DevBuf<double> dP;
     DevBuf<double> dWt;           // one 128 x 128 tile per tile column
     DevBuf<double> dpart;         // early halves of the split diagonal-block tiles (2 x 16 x 64 x 64 doubles)
-    DevBuf<unsigned> ddag;        // [queue (64 words)] [tdone] [pdone]
+    DevBuf<unsigned> ddag;        // the task words: dag_words() below is their map
     DevBuf<DagStepHost> ddag_steps; int dag_nsteps = 0; unsigned dag_ntasks = 0;
     int dag_key[12] = {};         // (nt, mt, trim, kskip, lead, min_tiles, lead2, lead3, order, xcd, bw, bh) the step table was built for
     DevBuf<unsigned> ddag_ftab;   // which tile every far tile task is (dag_build_steps' table), device copy
     int dag_xcd_g = 0;            // chunk exponent of the XCD-aware deal the table was built for (0: one counter)
     bool dag_have_ftab = false;   // the current step table comes with a far-tile table
-    size_t ddag_xcnt_off = 0;     // offset (words) of the XCDs' task counters inside ddag
-    DevBuf<unsigned long long> ddag_trace;   // diagnostics (cocons_debug_tune("dag_trace", 1)): 4 stamps per task, 5 words per
-    size_t dag_trace_tasks = 0;              // task + 8 per tile pair allocated
+    DevBuf<unsigned long long> ddag_trace;   // diagnostics (cocons_debug_tune("dag_trace", 1)): dag_trace_words() below
+    size_t dag_trace_tasks = 0;              // tasks the buffer describes (0: not this step table)
     bool dag_next = false;        // the engine launched by engine_start is the DAG schedule's (publishes W and the second X)
     int engine_pair_live = 0;     // 1: the engine launched for the next factorisation has a pair partner (it counts itself in alive[2])
-    size_t smb_off = 0, smb_elems = 0;   // inside dmbox: strip mailboxes, one per diagonal block (the panel launch's next-diagonal-block
-                                         // update), and xmb_off: the panel launch's exchange mailboxes, one per 64-row strip (split panel)
-    size_t xmb_off = 0, xmb_elems = 0;
+    MboxLayout mbox;                     // what dmbox holds (mbox_reset)
     DevBuf<double> dmbox;                // one mailbox per tile (mbox_reset): the engine's pair mode, the panel kernel and potrf_solve's
-                                         // followers read a tile's factor from there while it is being formed
+                                         // followers read a tile's factor from there while it is being formed; tile_mbox() .. below
     bool follow_used = false, follow_off = false;   // the operation being enqueued used launch_potrf_follow; it timed out once on this handle: off
     double enq_host_us = 0; long long enq_calls = 0;   // (diagnostics) host time spent enqueueing evaluations, calls: cocons_debug_host_enqueue
     bool dag_used = false;        // the factorisation enqueued last ran the DAG schedule: its factor is split over dA and dP
@@ -343,6 +345,93 @@ struct cocons_fit {
     std::unique_ptr<TaperGradState> tgrad;   // taper fit: state of cocons_neg2loglik_grad_taper (allocated on first use)
 };
 
+// ---- one map per region of device words (every offset in ONE place; the abort dump -- api.hip debug_abort_report, decoded by
+// tools/dag_abort.py --, cocons_debug_dag_words and the tests read these indices) ------------------------------------------
+// The hand-off words of a factorisation (dflags, zeroed by flags_reset): in[t], out[t], xr[t] (see EngineLaunch), flags_cap
+// words each; then 64 words -- the engine's alive word, at + 8 the two words of the stream self-test, at + 16 the
+// workgroups that took part per XCD --; then flags_cap tile counters of the trailing updates.  abort: the word behind the
+// info word (who gave up, kernels.h abort_code).
+struct HandoffWords {
+    unsigned *in, *out, *xr, *alive, *selftest, *xcd_arrivals, *abort, *queues;
+    unsigned *tile_queue(int k) const { return queues + k / 2; }   // of the update with block k's panel: update_kernel's dynamic tile order
+};
+inline size_t handoff_word_count(int cap) { return 4 * (size_t)cap + 64; }
+inline HandoffWords handoff_words(const cocons_fit *f)
+{
+    HandoffWords w;
+    const size_t cap = (size_t)f->flags_cap;
+    unsigned *b = f->dflags;
+    w.in = b; w.out = b + cap; w.xr = b + 2 * cap; w.alive = b + 3 * cap;
+    w.selftest = w.alive + 8; w.xcd_arrivals = w.alive + 16; w.queues = w.alive + 64;
+    w.abort = (unsigned *)(f->dinfo + 1);
+    return w;
+}
+
+// The task words of the persistent launch (ddag, DagLaunch) for the handle's step table and a view of mt tile rows: the task
+// counter, at + 8 the record of a wait that ran out (7 words), at + 64 tdone, then pdone (pstride words per panel), pall,
+// dcount and -- eight cache lines behind everything else -- the XCDs' own task counters; total: words in all.
+struct DagWords {
+    unsigned *queue, *wait_record, *tdone, *pdone, *pall, *dcount, *xcnt;
+    int pstride;
+    size_t total;
+};
+inline DagWords dag_words(const cocons_fit *f, int mt)
+{
+    DagWords w;
+    const size_t T64 = 2 * (size_t)mt, ns = (size_t)f->dag_nsteps;
+    const size_t tdone = 64, pdone = tdone + T64 * (T64 + 1) / 2, pall = pdone + (ns + 2) * T64, dcount = pall + ns + 64;
+    const size_t xcnt = (dcount + 16 * (ns + 2) + 31) / 32 * 32;
+    unsigned *b = f->ddag;
+    auto at = [b](size_t off) { return b ? b + off : nullptr; };      // (sized before it is allocated: dag_prepare)
+    w.queue = b; w.wait_record = at(8); w.tdone = at(tdone); w.pdone = at(pdone); w.pall = at(pall); w.dcount = at(dcount);
+    w.xcnt = at(xcnt);
+    w.pstride = (int)T64;
+    w.total = xcnt + 8 * 32;
+    return w;
+}
+
+// The trace buffer (ddag_trace) of a step table with the handle's task count on nt tile columns: 4 stamps per task, 8 stamps
+// per tile pair of the engine (room for nt + 2 tiles), then one word of hw_where() pairs per task
+struct DagTraceWords {
+    unsigned long long *tasks, *engine;
+    unsigned *hw;
+    size_t engine_count, count;      // elements of the engine's part, of everything
+};
+inline DagTraceWords dag_trace_words(const cocons_fit *f, int nt)
+{
+    DagTraceWords w;
+    unsigned long long *b = f->ddag_trace;
+    const size_t ntasks = f->dag_ntasks;
+    w.engine_count = 8 * (size_t)(nt + 2); w.count = 5 * ntasks + w.engine_count;
+    w.tasks = b; w.engine = b ? b + 4 * ntasks : nullptr; w.hw = b ? (unsigned *)(w.engine + w.engine_count) : nullptr;
+    return w;
+}
+
+// The mailboxes (dmbox, every byte 0xff = "not written yet", mbox_reset): one per tile for nt + 2 tiles | one strip mailbox per
+// diagonal block (the panel launch's next-diagonal-block update) | the exchange mailboxes of the split panel, one per 64-row
+// strip of the matrix and the rows under it.  The accessors return null when the buffer does not hold what is asked for.
+inline MboxLayout mbox_layout(int nt, bool panel, bool split)
+{
+    MboxLayout l;
+    l.tiles = ((size_t)nt + 2) * ENGINE_MBOX_DOUBLES;
+    l.smb = panel ? ((size_t)nt / 2 + 2) * PANEL_SMBOX_DOUBLES : 0;
+    l.xmb = panel && split ? (2 * ((size_t)nt + 2) + 4) * PANEL_XMBOX_DOUBLES : 0;
+    return l;
+}
+inline double *tile_mbox(const cocons_fit *f, int t)
+{
+    return f->dmbox && ((size_t)t + 1) * ENGINE_MBOX_DOUBLES <= f->mbox.tiles ? f->dmbox + (size_t)t * ENGINE_MBOX_DOUBLES : nullptr;
+}
+inline double *strip_mbox(const cocons_fit *f, int block)
+{
+    return f->dmbox && ((size_t)block + 1) * PANEL_SMBOX_DOUBLES <= f->mbox.smb
+               ? f->dmbox + f->mbox.tiles + (size_t)block * PANEL_SMBOX_DOUBLES : nullptr;
+}
+inline double *xchg_mbox(const cocons_fit *f, int nstrips)      // for a panel of nstrips 64-row strips
+{
+    return f->dmbox && (size_t)nstrips * PANEL_XMBOX_DOUBLES <= f->mbox.xmb ? f->dmbox + f->mbox.tiles + f->mbox.smb : nullptr;
+}
+
 int fit_check(cocons_fit *f);
 
 // Every public entry point that works on a handle: validate it, then hold its operation lock until the call returns.
@@ -364,6 +453,21 @@ struct FactorView {
                                // rows in use): no kernel of the factorisation touches them
     bool dag_ok = false;       // the caller reads the factor through launch_finalize(..., A2 = dP) only: the dependency-driven
                                // schedule may be used (its factor is split over two buffers)
+    // the rows of a panel from tile row t0 down to the last row any kernel touches; hb = one past the last band tile row of
+    // the panel's 256-column block (api.hip band_hi; -1: dense), behind which only the rows under the matrix follow
+    RowRange panel_rows(int t0, int hb) const
+    {
+        RowRange r;
+        r.r0 = t0 * TILE; r.r1 = mt * TILE - 64 * trim; r.band_r1 = hb >= 0 ? hb * TILE : -1; r.ext_r0 = nt * TILE;
+        return r;
+    }
+    // an update launch on this matrix with the same band limit and trim (dense indexing: skew stays 0)
+    UpdateLaunch update(int hb) const
+    {
+        UpdateLaunch u;
+        u.C = A; u.ldc = lda; u.band_hi = hb; u.ext0 = nt; u.trim64 = trim;
+        return u;
+    }
 };
 
 // pad0 = 0 while a view that does not start with the handle's observations is factored (every way out): factorize()'s

@@ -302,10 +302,13 @@ void launch_grad_lowrank(const double *fin, const double *SX, int npad, int r, i
 void launch_grad_syrk(double *A, size_t lda, int npad, int brow0, hipStream_t s)
 {
     const int nt = npad / TILE;
+    UpdateLaunch u;
+    u.C = A; u.ldc = lda; u.ldp = lda; u.lower_only = true;
     for (int t = 0; t < nt; t += 2) {
         const int kw = (t + 2 <= nt) ? 2 : 1;
-        const int t1 = t + kw;
-        launch_update_from(A, lda, A + brow0 + (size_t)t * TILE * lda, lda, kw * TILE, 0, t1, 0, t1, true, s, 1, 1, 0);
+        u.P = A + brow0 + (size_t)t * TILE * lda; u.K = kw * TILE;      // (rows brow0.. of C's own buffer: kblk stays 0, dense)
+        u.ti1 = u.tj1 = t + kw;
+        launch_update(u, s);
     }
 }
 
@@ -786,10 +789,14 @@ hipError_t launch_fisher_products(double *Tb, size_t ldt, int npad, int ndir, hi
     const int nt = npad / TILE;
     const size_t row = (size_t)npad * sizeof(double), pitch = ldt * sizeof(double);
     hipError_t e = hipMemset2DAsync(Tb + (size_t)(ndir + 1) * npad, pitch, 0, row, npad, s);
+    UpdateLaunch u;
+    u.C = Tb + npad; u.ldc = ldt; u.ldp = ldt; u.tj1 = nt;
     for (int a = ndir - 1; a >= 0 && e == hipSuccess; --a) {
-        for (int k0 = 0; k0 < npad; k0 += FISHER_KP)
-            launch_update_from(Tb + npad, ldt, Tb + (size_t)k0 * ldt, ldt, min(FISHER_KP, npad - k0), (a + 1) * nt, (a + 2) * nt, 0,
-                               nt, false, s, 1, 1, 0);
+        u.ti0 = (a + 1) * nt; u.ti1 = (a + 2) * nt;
+        for (int k0 = 0; k0 < npad; k0 += FISHER_KP) {
+            u.P = Tb + (size_t)k0 * ldt; u.K = min(FISHER_KP, npad - k0);      // (kblk stays 0: a dense buffer)
+            launch_update(u, s);
+        }
         if (a > 0) e = hipMemset2DAsync(Tb + (size_t)(a + 1) * npad, pitch, 0, row, npad, s);
     }
     return e;

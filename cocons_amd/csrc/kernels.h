@@ -74,17 +74,23 @@ void launch_loc_params(const LocArgs &a, hipStream_t s);
 void launch_pair_sym(int mode, bool mirror, const PairArgs &a, hipStream_t s);
 void launch_pair_rect(int mode, const PairArgs &a, hipStream_t s);
 void launch_rhs_rows(const RhsArgs &a, hipStream_t s);
-// entries of the sparse/taper covariance for a CSR pattern (1-based indices, device arrays)
-void launch_taper(int mode, bool pred, int nrows, int nnz, const int *ci, const int *rp, const double *rows,
-                  size_t stride_rows, const double *cols, size_t stride, double nu_fixed, double *out, hipStream_t s,
-                  const double *tapv = nullptr, double *A = nullptr, size_t lda = 0, int row0 = 0,    // A: dense target, see TaperArgs
-                  int skew = 0, int npad = 0);                                                       // packed band target (band_index)
-// rows idx[0..nidx) of the dense covariance (cor != 0: of cov2cor of it); out row b at out + b * n
+// entries of the sparse/taper covariance for a CSR pattern (1-based indices, device arrays): see TaperArgs (assemble.hip)
+struct TaperLaunch {
+    int mode = 0; bool pred = false;             // PairMode; pred: rows = prediction locations (always MODE_GEOM)
+    int nrows = 0, nnz = 0; const int *ci = nullptr, *rp = nullptr;
+    const double *rows = nullptr; size_t stride_rows = 0;   // SoA of the row side
+    const double *cols = nullptr; size_t stride = 0;        // SoA of the column side (observations)
+    double nu_fixed = 0.0; double *out = nullptr;           // out: one value per entry, unless A is given:
+    const double *tapv = nullptr; double *A = nullptr; size_t lda = 0; int row0 = 0;    // dense target, see TaperArgs
+    int skew = 0, npad = 0;                      // packed band target (band_index)
+};
+void launch_taper(const TaperLaunch &t, hipStream_t s);
 // zero the tiles inside the envelope (d_hi: device copy of FactorView::hi; max_band = max over c of hi[c] - c)
 void launch_band_zero(double *A, size_t lda, const int *d_hi, int nt, int max_band, hipStream_t s, int skew = 0);
 // identity on the padding diagonal of a taper handle's buffer
 void launch_front_identity(double *A, size_t lda, int pad0, int rows, hipStream_t s);   // columns [0, pad0): unit vectors
 void launch_pad_identity(double *A, size_t lda, int n, int npad, hipStream_t s, int skew = 0);
+// rows idx[0..nidx) of the dense covariance (cor != 0: of cov2cor of it); out row b at out + b * n
 void launch_cov_rows(int mode, int n, int nidx, const int *idx, const double *loc, size_t stride, double gr,
                      double nu_fixed, int cor, double *out, hipStream_t s);
 // out[i] = 2^(1-nu)/Gamma(nu) u^nu K_nu(u) by the device routine of the pair kernels (diagnostic)
@@ -113,10 +119,17 @@ inline double *band_base(double *A, int c, int skew) { return skew ? A - (ptrdif
 // its eight 16x16 diagonal blocks to dinv (8*256 doubles).  info: atomicMin of the
 // 1-based failing column (initialise to INT_MAX).
 void launch_potrf_tile(double *A, size_t lda, int c0, double *dinv, int *info, hipStream_t s);
-// launch_potrf_tile and launch_trsm_tile (rows as there) in ONE launch: the solve workgroups follow the factorisation through
-// the tile's mailbox (ENGINE_MBOX_DOUBLES doubles, every byte 0xff beforehand); bit-identical to the two launches
-void launch_potrf_follow(double *A, size_t lda, int c0, int r0, int r1, double *dinv, int *info, double *mbox,
-                         unsigned *abort_word, hipStream_t s, int band_r1 = -1, int ext_r0 = 0);
+// Rows [r0, r1) of a panel, or -- band_r1 >= 0, band-limited factorisation -- [r0, band_r1) and [ext_r0, r1); strips(): its
+// 64-row strips in the first stretch (the band) and in the second (the rows under the matrix)
+struct RowRange {
+    int r0 = 0, r1 = 0, band_r1 = -1, ext_r0 = 0;
+    void strips(int &nb1, int &nb2) const
+    {
+        nb1 = ((band_r1 >= 0 ? band_r1 : r1) - r0) / 64; nb2 = band_r1 >= 0 ? (r1 - ext_r0) / 64 : 0;
+        if (nb1 < 0) nb1 = 0;
+        if (nb2 < 0) nb2 = 0;
+    }
+};
 // Resident diagonal-BLOCK engine (one workgroup on a CU of its own) for the 256 x 256 diagonal blocks
 // starting at tile t0 (even): see potrf_engine_kernel.  Flag words, all zero at launch:
 //   in[t]    raised by the update kernels (launch_update's sig / sig_tile): 3 = tile (t,t) updated;
@@ -125,19 +138,20 @@ void launch_potrf_follow(double *A, size_t lda, int c0, int r0, int r1, double *
 //                     dinv + (tile & 1) * 2048) is published;
 //   xr[t]    raised to 1 when X = A(t+1,t) L(t)^-T is published.
 // abort_word: set by any party whose bounded wait ran out; everybody leaves when it is non-zero.
-//   alive    raised by the engine once it is resident; launch_engine_gate(alive, ...) holds a stream until then
-// t0 >= nt: a warm-up launch -- the kernel raises alive and leaves (first-dispatch costs paid outside any bounded wait)
+//   alive    raised by the engine once it is resident; launch_start_gate(alive, ...) holds a stream until then
 // wbuf, pbuf != NULL: the engine of the DAG schedule (launch_dag) -- it also publishes W = L^-1 of every diagonal tile t at
 // wbuf + t * 128 * 128 (zeroed once by the caller; complete before out[t]) and a second copy of X in pbuf (shaped like A)
-void launch_potrf_engine(double *A, size_t lda, int t0, int nt, double *dinv, int *info,
-                         unsigned *in, unsigned *out, unsigned *xr, unsigned *abort_word, unsigned *alive, hipStream_t s,
-                         double *wbuf = nullptr, double *pbuf = nullptr, int dag_until = 0,
-                         unsigned long long *trace = nullptr,
-                         double *mbox = nullptr,                         // pair mode (engine_partner_loop): the tiles' mailboxes
-                                                                         // (ENGINE_MBOX_DOUBLES each, index = tile), every byte 0xff at
-                                                                         // launch; a second workgroup takes the second tile of every block
-                         int in_wait_ms = 0);                            // > 0 (tests): bound of the engine's waits for its input words
-                                                                         // in milliseconds instead of the host-paced 3 s
+struct EngineLaunch {
+    double *A = nullptr; size_t lda = 0; int t0 = 0, nt = 0;
+    double *dinv = nullptr; int *info = nullptr; unsigned *in = nullptr, *out = nullptr, *xr = nullptr, *abort_word = nullptr, *alive = nullptr;
+    double *wbuf = nullptr, *pbuf = nullptr; int dag_until = 0; unsigned long long *trace = nullptr;
+    double *mbox = nullptr;    // pair mode (engine_partner_loop): the tiles' mailboxes (ENGINE_MBOX_DOUBLES each, index = tile), every
+                               // byte 0xff at launch; a second workgroup takes the second tile of every block
+    int in_wait_ms = 0;        // > 0 (tests): bound of the engine's waits for its input words in milliseconds, not the host-paced 3 s
+};
+void launch_potrf_engine(const EngineLaunch &e, hipStream_t s);
+// the WARM-UP launch (chol.hip): no tile at all, the kernel raises e.alive and leaves; e: dinv, info and the words; dag: which instantiation
+void launch_potrf_engine_warmup(EngineLaunch e, bool dag, hipStream_t s);
 // Abort codes of the bounded hand-off waits (the abort word behind the info word: who gave up).  CLASS in bits 8..11, an index
 // -- the tile or, for the persistent launch, the step -- in the low byte, masked so that no index can spill into another class
 // (until round 5 the engine's partner reported 0x700 + tile while the followers used the fixed codes 0x7d0 / 0x7e0 / 0x7f0: from
@@ -154,66 +168,73 @@ constexpr unsigned ABORT_ENGINE_IN0 = 0x100u, ABORT_ENGINE_IN1 = 0x200u, ABORT_P
 __host__ __device__ inline unsigned abort_code(unsigned cls, unsigned index) { return cls | (index & 0xffu); }
 inline unsigned abort_class(unsigned code) { return code & 0xf00u; }
 constexpr size_t ENGINE_MBOX_DOUBLES = 44 * 256;
+// the start-up gate holds the stream until the engine is resident (chol.hip; patient: a handle's first engine-schedule operation)
 // nhelp > 0: also waits until that many further workgroups of the engine's launch (the pair partner) are resident
 // raise_in != NULL: the gate also raises in[0] = 3, in[1] = 7 (the engine factors the first diagonal block too: launch_potrf_engine t0 = 0)
-void launch_engine_gate(unsigned *alive, unsigned *abort_word, hipStream_t s, bool last_tile = false, bool patient = false, int nhelp = 0,
-                        unsigned *raise_in = nullptr);
+void launch_start_gate(unsigned *alive, unsigned *abort_word, bool patient, int nhelp, unsigned *raise_in, hipStream_t s);
+void launch_last_tile_gate(unsigned *out_word, unsigned *abort_word, hipStream_t s);   // the reductions' wait for the engine's LAST tile
 void launch_raise_word(unsigned *word, hipStream_t s);      // *word = 1 (agent scope) by a one-lane kernel: "everything in front of me on this stream is done"
 // 1: a kernel on `first` and a kernel launched behind it on `second` overlap (the streams sit on different hardware queues);
 // 0: they run one after the other; -1: HIP error.  words: two device words; both streams idle.
 int streams_run_concurrently(hipStream_t first, hipStream_t second, unsigned *words);
-// rows [r0, r1) x cols [c0, c0+128):  X <- X * L(c0)^{-T}, L read from A(c0,c0).
+// rows x cols [c0, c0+128):  X <- X * L(c0)^{-T}, L read from A(c0,c0).
 // wait_word != NULL: the tile comes from the engine -- every workgroup first waits for *wait_word >= 1
-// band_r1 >= 0 (band-limited factorisation): rows [r0, band_r1) and [ext_r0, r1) instead of [r0, r1).
 // own_world > 1 (sharded evaluation): only the 64-row strips inside 256-row blocks b with (b / own_group) % own_world == own_rank
-void launch_trsm_tile(double *A, size_t lda, int c0, int r0, int r1, const double *dinv, hipStream_t s,
-                      unsigned *wait_word = nullptr, unsigned *abort_word = nullptr, int band_r1 = -1, int ext_r0 = 0,
-                      int own_world = 0, int own_rank = 0, int own_group = 1);
+struct TrsmLaunch {
+    double *A = nullptr; size_t lda = 0; int c0 = 0; RowRange rows;
+    double *dinv = nullptr; unsigned *wait_word = nullptr, *abort_word = nullptr;
+    int own_world = 0, own_rank = 0, own_group = 1;
+    int *info = nullptr; double *mbox = nullptr;      // launch_potrf_follow only
+};
+void launch_trsm_tile(const TrsmLaunch &l, hipStream_t s);
+// launch_potrf_tile (info) and launch_trsm_tile (dense, unsharded, no wait_word) in ONE launch: the solve workgroups follow the
+// factorisation through the tile's mailbox mbox (ENGINE_MBOX_DOUBLES doubles, every byte 0xff beforehand); bit-identical to the two
+void launch_potrf_follow(const TrsmLaunch &l, hipStream_t s);
 // The panel of a two-tile block of the engine schedule in one launch: rows [r0, r1) of the tile columns at c0 and c0 + 128,
-// X0 = B0 L(c0)^-T | B1 -= X0 X(t+1,t)^T | X1 = B1 L(c0+128)^-T (dense, unsharded).  The strips follow the two tiles through their
-// mailboxes mb0, mb1 (the engine's pair mode) and the in-panel product waits for xr.  Bit-identical to launch_trsm_tile |
-// launch_update (K = 128) | launch_trsm_tile.
-void launch_panel_pair(double *A, size_t lda, int c0, int r0, int r1, unsigned *xr, unsigned *abort_word, hipStream_t s,
-                       const double *mb0, const double *mb1,
-                       double *smb = nullptr, int ndiag = 0, unsigned *sig = nullptr, int sig_tile = 0,
-                       double *xmb = nullptr);   // split panel: exchange mailboxes, PANEL_XMBOX_DOUBLES per 64-row strip, every byte
-                                                 // 0xff (the second workgroup of a strip puts the pattern back as it reads)
+// X0 = B0 L(c0)^-T | B1 -= X0 X(t+1,t)^T | X1 = B1 L(c0+128)^-T (dense, unsharded: rows.band_r1 is not read).  The strips follow
+// the two tiles through their mailboxes mb0, mb1 (the engine's pair mode) and the in-panel product waits for xr.  Bit-identical
+// to launch_trsm_tile | launch_update (K = 128) | launch_trsm_tile.
+struct PanelLaunch {
+    double *A = nullptr; size_t lda = 0; int c0 = 0; RowRange rows;
+    unsigned *xr = nullptr, *abort_word = nullptr; const double *mb0 = nullptr, *mb1 = nullptr;
+    double *smb = nullptr; int ndiag = 0; unsigned *sig = nullptr; int sig_tile = 0;   // see PANEL_SMBOX_DOUBLES
+    double *xmb = nullptr;     // split panel: exchange mailboxes, PANEL_XMBOX_DOUBLES per 64-row strip, every byte 0xff (the second
+                               // workgroup of a strip puts the pattern back as it reads)
+};
+void launch_panel_pair(const PanelLaunch &l, hipStream_t s);
 constexpr size_t PANEL_XMBOX_DOUBLES = 8 * 4 * 256;
 // smb (PANEL_SMBOX_DOUBLES doubles, every byte 0xff beforehand) + ndiag = 10 or 3: the launch also updates the NEXT diagonal
 // block (two tiles or one) with this panel and raises sig[sig_tile] (+3) / sig[sig_tile + 1] (+7) like launch_update's tiles
 // inside the diagonal block do; the update launch that follows must leave those tiles alone (skip_lo / skip_hi)
 constexpr size_t PANEL_SMBOX_DOUBLES = 4 * 16 * 4 * 256;
-// C(i,j) -= sum_{k in [k0,k0+K)} A(i,k) A(j,k) for tiles with tile-row in [ti0,ti1),
-// tile-col in [tj0,tj1); lower_only keeps ti >= tj.  All tile indices in units of TILE.
-// sig / sig_tile: hand-off to the engine (sig = the in[] array, sig_tile = even tile of the diagonal block);
-// wait_word: an operand tile comes from the engine -- every workgroup first waits for *wait_word >= 1.
-// queue: a device word that is ZERO when the launch starts -- the launch then takes about as many workgroups
-// as the chip holds and they draw the tiles of the trapezoid from that counter (lower_only launches).
-void launch_update(double *A, size_t lda, int k0, int K, int ti0, int ti1, int tj0, int tj1,
-                   bool lower_only, hipStream_t s, unsigned *sig = nullptr, int sig_tile = -1,
-                   unsigned *wait_word = nullptr, unsigned *abort_word = nullptr, unsigned *queue = nullptr,
-                   int band_hi = -1, int ext0 = 0,       // band_hi >= 0: tile rows [ti0, band_hi) and [ext0, ti1)
-                   int skew = 0,           // packed band buffer (band_index; with band_hi / ext0): A is its unshifted base
-                   int trim64 = 0,         // 1: the last 64 rows of the row range hold nothing (a 128-row tile of right-hand
-                                           // sides of which at most 64 rows are used): they are not updated
-                   int skip_lo = 0, int skip_hi = 0);   // tiles with both 64-row and 64-column index in [skip_lo, skip_hi) are left
-                                                        // alone (the next diagonal block, when the panel's launch has updated it)
+// C(i,j) -= sum_{k < K} P(i,k) P(j,k) for tiles with tile-row in [ti0,ti1), tile-col in [tj0,tj1); lower_only keeps
+// ti >= tj.  All tile indices in units of TILE.
+struct UpdateLaunch {
+    double *C = nullptr; size_t ldc = 0;
+    const double *P = nullptr; size_t ldp = 0; int kblk = 0;   // the panel: element (row, k) at P[row + k * ldp]; packed band: tile column kblk
+    void panel_in_c(int k0) { P = C + (size_t)k0 * ldc; ldp = ldc; kblk = k0 / TILE; }   // ... = columns [k0, k0 + K) of C itself
+    int K = 0, ti0 = 0, ti1 = 0, tj0 = 0, tj1 = 0; bool lower_only = false;
+    int band_hi = -1, ext0 = 0;    // band_hi >= 0: tile rows [ti0, band_hi) and [ext0, ti1)
+    int skew = 0;                  // packed band buffer (band_index; with band_hi / ext0): C is its unshifted base
+    int trim64 = 0;                // 1: the last 64 rows of the row range hold nothing (a half-used tile of right-hand sides): not updated
+    int skip_lo = 0, skip_hi = 0;  // tiles with both 64-row and 64-column index in [skip_lo, skip_hi) are left alone (the next
+                                   // diagonal block, when the panel's launch or -- sharded -- its owner has updated it already)
+    unsigned *sig = nullptr; int sig_tile = -1;             // hand-off to the engine: its in[] array, even tile of the diagonal block
+    unsigned *wait_word = nullptr, *abort_word = nullptr;   // an operand tile comes from the engine: wait for *wait_word >= 1 first
+    unsigned *queue = nullptr;     // a device word, ZERO at launch: about as many workgroups as the chip holds then draw the tiles of
+                                   // the trapezoid from that counter (lower_only launches)
+    // sharded path, world > 1: only tiles whose ROW lies in a 256-row block b with (b / group) % world == rank; pmap (device, one
+    // int per 64-row tile, null = global row index): element offset of that tile's rows in the owner-packed panel P (api_shard.hip)
+    int group = 1, world = 1, rank = 0; const int *pmap = nullptr;
+};
+void launch_update(const UpdateLaunch &u, hipStream_t s);
 // waves per workgroup of the trailing-update kernel: 4 or 8 (512 threads, KC = 16: half the tile latency; default for
 // launches of at most set_update_w8_max_tiles tiles, 0 = every launch)
 void set_update_waves(int nw);
 void set_update_w8_max_tiles(int ntiles);
 void set_update_c_wt(int on);           // (experiment) every C tile through L2-bypassing loads and write-through stores
-// like launch_update but the (i,k) and (j,k) operands come from a separate panel buffer P, used by the sharded path:
-// world > 1: only the tiles whose ROW lies in a 256-row block b with (b / group) % world == rank are updated (row-block
-// ownership); pmap (device, one int per 64-row tile, may be null = global row index): element offset of that tile's rows in
-// P, whose columns are ldp apart -- the gathered panel is packed by owner (api.hip); [skip_lo, skip_hi): the tiles whose 64-row
-// AND 64-column index lie in that range -- a diagonal block its owner has updated ahead of the exchange -- are left out.
-void launch_update_from(double *A, size_t lda, const double *P, size_t ldp, int K,
-                        int ti0, int ti1, int tj0, int tj1, bool lower_only, hipStream_t s,
-                        int group, int world, int rank, unsigned *sig = nullptr, int sig_tile = -1,
-                        unsigned *wait_word = nullptr, unsigned *abort_word = nullptr, unsigned *queue = nullptr,
-                        int band_hi = -1, int ext0 = 0, int skew = 0, int kblk = 0, int trim64 = 0,
-                        const int *pmap = nullptr, int skip_lo = 0, int skip_hi = 0);
+int device_cus();                                           // CUs of the device (asked once per process)
+inline int resident_slots() { return 8 * device_cus(); }    // the chip holds 8 workgroups of the update and DAG kernels on each
 // sharded evaluation: the solved rows this rank owns of the 256-column panel at column col0 (ncols columns), gathered into
 // its slot of the owner-packed exchange buffer: for every 64-row tile ti in [ti_lo, ti_hi) with pmap[ti] inside the slot
 // [slot_lo, slot_hi): dst[pmap[ti] + rho + c * ldp] = A[(64 ti + rho) + (col0 + c) lda]
@@ -237,16 +258,20 @@ unsigned dag_build_steps(int nt, int mt, int trim64, int kskip, int lead, int mi
                          std::vector<unsigned> *ftab = nullptr,    // out: which tile every FAR tile task is (launch_dag's ftab; chol.hip:
                                                                    // dag_build_far_table) for tasks dealt to the XCDs in chunks of
                          int xcd_g = 0, int bw = 16, int bh = 16); // 2^xcd_g list positions (0: one counter), blocks of bw x bh tiles
-// dsteps: DEVICE copy of the table.  queue, tdone (2 mt (2 mt + 1) / 2 words), pdone ((nsteps + 1) * pstride words,
-// pstride >= 2 mt), pall (nsteps + 1 words): zero at launch.  sig / out / xr: the engine's words (launch_potrf_engine with wbuf = Wt, pbuf = P).
-void launch_dag(double *A, size_t lda, double *P, const double *Wt, const DagStepHost *dsteps, int nsteps, unsigned ntasks,
-                unsigned *queue, unsigned *tdone, unsigned *pdone, int pstride, unsigned *pall, double *partbuf, unsigned *dcount,
-                unsigned *sig, unsigned *out, unsigned *xr, unsigned *abort_word, hipStream_t s, unsigned long long *trace = nullptr,
-                const unsigned *alive = nullptr, int xcc_quota = 0, unsigned *hw = nullptr,
-                const unsigned *ftab = nullptr, int xcd_g = 0,      // DEVICE copy of dag_build_steps' far-tile table; chunk exponent
-                unsigned *xcnt = nullptr);                          // the XCDs' task counters: 8 x 32 words (a cache line each), zero at launch
-                // alive: the engine's alive word (1 + its XCD); xcc_quota: workgroups of the launch that take part on that XCD
-                // partbuf: 2 x 16 x 64 x 64 doubles; dcount: 16 words per step (+ 1 step), zero at launch
+// steps: DEVICE copy of the table.  queue, tdone (2 mt (2 mt + 1) / 2 words), pdone ((nsteps + 1) * pstride words,
+// pstride >= 2 mt), pall (nsteps + 1 words): zero at launch.  sig / out / xr: the engine's words (EngineLaunch with wbuf = Wt, pbuf = P).
+struct DagLaunch {
+    double *A = nullptr; size_t lda = 0; double *P = nullptr; const double *Wt = nullptr;
+    const DagStepHost *steps = nullptr; int nsteps = 0; unsigned ntasks = 0;
+    unsigned *queue = nullptr, *tdone = nullptr, *pdone = nullptr; int pstride = 0; unsigned *pall = nullptr;
+    double *partbuf = nullptr; unsigned *dcount = nullptr;   // 2 x 16 x 64 x 64 doubles; 16 words per step (+ 1 step), zero at launch
+    unsigned *sig = nullptr, *out = nullptr, *xr = nullptr, *abort_word = nullptr;
+    unsigned long long *trace = nullptr; unsigned *hw = nullptr;      // diagnostics (hw only with trace)
+    const unsigned *alive = nullptr; int xcc_quota = 0;   // the engine's alive word (1 + its XCD); workgroups that take part on that XCD
+    const unsigned *ftab = nullptr; int xcd_g = 0;        // DEVICE copy of dag_build_steps' far-tile table; chunk exponent
+    unsigned *xcnt = nullptr;              // the XCDs' task counters: 8 x 32 words (a cache line each), zero at launch
+};
+void launch_dag(const DagLaunch &d, hipStream_t s);
 
 // reductions: out[0] = sum_{i<n} log(A(i,i)); out[1 + a*nr + b] = sum_{c<n} A(row0+a,c) A(row0+b,c)
 void launch_finalize(const double *A, size_t lda, int n, int row0, int nr, double *out, hipStream_t s,
