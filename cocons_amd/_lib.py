@@ -75,6 +75,11 @@ SIGNATURES = {
     "cocons_krige_apply": (c_int, [c_vp, c_int, c_dp, c_dp, c_dp, c_dp]),
     "cocons_krige_release": (c_int, [c_vp]),
     "cocons_krige_info": (c_int, [c_vp, ctypes.POINTER(ctypes.c_longlong)]),
+    "cocons_krige_taper_prepare": (c_int, [c_vp, c_dp, c_dp, c_int, c_int]),
+    "cocons_krige_taper_apply": (c_int, [c_vp, c_int, c_dp, c_dp, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_dp,
+                                         c_dp, c_dp]),
+    "cocons_krige_taper_release": (c_int, [c_vp]),
+    "cocons_krige_taper_info": (c_int, [c_vp, ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_krige_joint": (c_int, [c_vp, c_int, c_dp, c_dp, c_dp, c_dp, c_dp, c_int, c_dp, c_dp]),
     "cocons_sim_taper": (c_int, [c_vp, c_dp, c_dp, c_int, c_dp, ctypes.POINTER(c_int), c_dp]),
     "cocons_fit_taper_order": (c_int, [c_vp, ctypes.POINTER(c_int)]),

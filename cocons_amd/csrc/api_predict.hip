@@ -431,6 +431,233 @@ extern "C" int cocons_predict_taper(cocons_fit *f, const double *theta, const do
 }
 
 // ---------------------------------------------------------------------------
+// Kriging from a held band factor: cocons_predict_taper in two parts.  cocons_krige_taper_prepare factors
+// S(theta) once with the residual row under it and copies the envelope's tiles, the solve operands and w = L^-1 r out of dA
+// into the handle's KrigeTaperState; cocons_krige_taper_apply then predicts any number of new locations in chunks against
+// it: the chunk's entries from the taper entry kernel, bucketed by tile column on the host, V = C L^-T through a ring of W
+// tile columns (launch_krige_band_solve).  No factorisation in apply, device memory independent of m.
+static constexpr int KRIGE_TAPER_ROWS_MAX = 1 << 20;               // a caller's max_rows beyond this is cut (slot offsets are ints)
+
+static int krige_taper_handle(cocons_fit *f, const char *who)
+{
+    if (f->taper_nnz <= 0) return fail(-1, "%s: not a taper fit (cocons_krige_prepare serves a dense handle)", who);
+    return krige_sharded(f, who);
+}
+
+static int krige_taper_W(const cocons_fit *f) { return f->taper_hi.empty() ? f->nt : f->taper_maxband; }
+
+static size_t krige_taper_row_bytes(const cocons_fit *f)
+{
+    return ((size_t)krige_taper_W(f) * TILE + (size_t)f->p + 2 + LOCP_FIELDS + 2) * sizeof(double);   // ring, Xp, lp, locp, st, qd
+}
+
+// the CSR staging holds at least `entries` entries; a new allocation only when it has to grow (the stream is idle then)
+static int krige_taper_stage(KrigeTaperState *K, size_t entries, const char *who)
+{
+    if (entries <= K->ecap) return 0;
+    HIPCHK_AT(who, K->ci.alloc(entries));
+    HIPCHK_AT(who, K->bdst.alloc(entries));
+    HIPCHK_AT(who, K->bsrc.alloc(entries));
+    HIPCHK_AT(who, K->tv.alloc(entries));
+    HIPCHK_AT(who, K->val.alloc(entries));
+    K->ecap = entries;
+    return 0;
+}
+
+extern "C" int cocons_krige_taper_prepare(cocons_fit *f, const double *theta, const double *mean, int z_col, int max_rows)
+{
+    const char *who = "cocons_krige_taper_prepare";
+    if (!f) return fail(-1, "%s: null fit handle", who);
+    FIT_ENTER(f);
+    if (int rc = krige_taper_handle(f, who)) return rc;
+    if (!theta || !mean || z_col < 0 || z_col >= f->r || max_rows < 0) return fail(-1, "%s: bad argument", who);
+    f->krige_taper.reset();             // replaced -- and gone if this prepare fails
+    const int p = f->p, n = f->n, npad = f->npad, nt = f->nt, W = krige_taper_W(f);
+    std::unique_ptr<KrigeTaperState> K(new KrigeTaperState());
+    {
+        size_t r = max_rows > 0 ? std::min<size_t>((size_t)max_rows, KRIGE_TAPER_ROWS_MAX)
+                                : std::min<size_t>(KRIGE_CHUNK_BYTES / krige_taper_row_bytes(f), KRIGE_ROWS_CAP);
+        K->rows = (int)std::max<size_t>(r / 64 * 64, 64);      // whole 64-row strips, as krige_rows
+    }
+    K->W = W;
+    K->theta.resize((size_t)6 * p);
+    for (int i = 0; i < 6 * p; ++i) K->theta[i] = canon_nan(theta[i]);
+    K->mean.resize((size_t)p);
+    for (int i = 0; i < p; ++i) K->mean[i] = canon_nan(mean[i]);
+    K->toff.assign((size_t)nt + 1, 0);
+    for (int c = 0; c < nt; ++c) {
+        const long long next = (long long)K->toff[c] + ((f->taper_hi.empty() ? nt : f->taper_hi[c]) - c);
+        if (next > INT_MAX) return fail(-1, "%s: the envelope holds too many tiles", who);
+        K->toff[c + 1] = (int)next;
+    }
+    const size_t R = (size_t)K->rows, ntile = (size_t)K->toff[nt];
+    // the staging starts at the densest row of the handle's own pattern for every row of a chunk
+    size_t dens = 1;
+    for (int i = 0; i < n; ++i) dens = std::max<size_t>(dens, (size_t)(f->h_trp[i + 1] - f->h_trp[i]));
+    StreamDrain s{f->stream, false};
+    HIPCHK_AT(who, K->L.alloc(ntile * TILE * TILE));
+    HIPCHK_AT(who, K->Q.alloc((size_t)nt * 2048));
+    HIPCHK_AT(who, K->w.alloc((size_t)npad));
+    HIPCHK_AT(who, K->loc.alloc((size_t)LOCP_FIELDS * npad));
+    HIPCHK_AT(who, K->ring.alloc(R * W * TILE));
+    HIPCHK_AT(who, K->Xp.alloc(R * p));
+    HIPCHK_AT(who, K->lp.alloc(R * 2));
+    HIPCHK_AT(who, K->locp.alloc(R * LOCP_FIELDS));
+    HIPCHK_AT(who, K->st.alloc(R));
+    HIPCHK_AT(who, K->qd.alloc(R));
+    HIPCHK_AT(who, K->d_toff.alloc((size_t)nt));
+    HIPCHK_AT(who, K->rp.alloc(R + 1));
+    if (int rc = krige_taper_stage(K.get(), R * dens, who)) return rc;
+    K->fixed_bytes = (long long)((ntile * TILE * TILE + (size_t)nt * 2048 + (size_t)npad * (1 + LOCP_FIELDS)) * sizeof(double) +
+                                 R * krige_taper_row_bytes(f) + ((size_t)nt + R + 1) * sizeof(int));
+    HIPCHK_AT(who, hipMemcpyAsync(K->d_toff, K->toff.data(), (size_t)nt * sizeof(int), hipMemcpyHostToDevice, s));
+    const double *th = K->theta.data();
+    if (int rc = fit_alloc_matrix(f, 1)) return rc;
+    const std::vector<int> full_hi((size_t)nt, nt);
+    struct PlainSchedule {              // the band schedule is a plain one: no resident engine while this prepare factors
+        cocons_fit *f; bool ok;
+        explicit PlainSchedule(cocons_fit *f_) : f(f_), ok(f_->engine_ok) { f->engine_ok = false; }
+        ~PlainSchedule() { f->engine_ok = ok; }
+    } plain(f);
+    const int st = run_op(f, who, [&]() -> int {
+        f->nrhs_cur = 1;
+        if (int rc = assemble_sigma_taper(f, th)) return rc;
+        residual_row(f, mean, z_col, f->dA, f->lda, npad, f->rhs_act - 1, npad);
+        // the band schedule, which leaves the factor whole in dA.  A handle without an envelope (COCONS_TAPER_BAND=0) takes it
+        // too, with hi[c] = nt: the same operations on every tile of the true band as under an envelope -- the tiles outside
+        // it only ever receive products with exact zeros -- so every layout prepares the same bits
+        FactorView v = main_view(f);
+        if (!v.hi) v.hi = full_hi.data();
+        if (int rc = factorize(f, v, nullptr)) return rc;
+        launch_krige_band_pack(f->dA, f->lda, f->skew, npad, n, f->d_thi, nt, W, K->d_toff, K->L, K->Q, K->w, s);
+        return 0;
+    });
+    if (st) return st;                  // failing minor: no state
+    // observation-side SoA as cocons_cov_rns_taper_pred prepares it: FULL scale vector, prediction-branch smoothness
+    ThetaVecs tv;
+    make_theta_vecs(th, p, tv, true);
+    const ModeSel ms = select_mode(th, p, f->smooth_limits, 2);
+    launch_loc_params(loc_args(n, p, f->dX, f->dlocs, K->loc, npad, tv, ms.smooth_kind, f->smooth_limits), s);
+    HIPCHK_AT(who, hipGetLastError());
+    HIPCHK_AT(who, hipStreamSynchronize(s));
+    f->krige_taper = std::move(K);
+    return 0;
+}
+
+extern "C" int cocons_krige_taper_apply(cocons_fit *f, int m, const double *locs_pred, const double *X_pred, int nnz_pred,
+                                        const int *colindices_pred, const int *rowpointers_pred,
+                                        const double *taper_entries_pred, double *stochastic, double *quadform)
+{
+    const char *who = "cocons_krige_taper_apply";
+    if (m < 0 || nnz_pred < 0 || (m > 0 && (!locs_pred || !X_pred || !rowpointers_pred || !stochastic || !quadform)) ||
+        (m > 0 && nnz_pred > 0 && (!colindices_pred || !taper_entries_pred)))
+        return fail(-1, "%s: bad argument (m < 0, nnz_pred < 0 or a null pointer)", who);
+    if (!f) return fail(-1, "%s: null fit handle", who);
+    FIT_ENTER(f);
+    if (int rc = krige_taper_handle(f, who)) return rc;
+    KrigeTaperState *K = f->krige_taper.get();
+    if (!K) return fail(-1, "%s: no kriging state on this handle (call cocons_krige_taper_prepare first)", who);
+    if (m == 0) return 0;
+    const int p = f->p, n = f->n, nt = f->nt, rows = K->rows, W = K->W;
+    // the whole pattern is checked before any device work: 1-based CSR, columns strictly increasing within a row
+    if (rowpointers_pred[0] != 1 || rowpointers_pred[m] != nnz_pred + 1)
+        return fail(-1, "%s: rowpointers do not match nnz (1-based CSR expected)", who);
+    for (int i = 0; i < m; ++i) {
+        const int a = rowpointers_pred[i], b = rowpointers_pred[i + 1];
+        if (b < a || a < 1 || b > nnz_pred + 1) return fail(-1, "%s: rowpointers decrease at row %d", who, i + 1);
+        for (int w = a - 1; w < b - 1; ++w) {
+            const int c = colindices_pred[w];
+            if (c < 1 || c > n) return fail(-1, "%s: column index out of range (row %d)", who, i + 1);
+            if (w > a - 1 && c <= colindices_pred[w - 1])
+                return fail(-1, "%s: column indices of row %d are not strictly increasing", who, i + 1);
+        }
+    }
+    const double *th = K->theta.data();
+    ThetaVecs tv;
+    make_theta_vecs(th, p, tv, true);
+    const ModeSel ms = select_mode(th, p, f->smooth_limits, 2);
+    std::vector<double> hX((size_t)rows * p), hl((size_t)rows * 2);
+    std::vector<int> hrp((size_t)rows + 1), hci, hdst, hsrc, boff((size_t)nt + 1), fill((size_t)nt);
+    StreamDrain s{f->stream, false};
+    for (int b = 0; b < m; b += rows) {
+        const int mc = std::min(rows, m - b);
+        const int e0 = rowpointers_pred[b] - 1, ne = rowpointers_pred[b + mc] - 1 - e0;
+        if (int rc = krige_taper_stage(K, (size_t)ne, who)) return rc;      // (the stream is idle: drained below per chunk)
+        for (int j = 0; j < p; ++j) memcpy(&hX[(size_t)j * mc], X_pred + b + (size_t)j * m, (size_t)mc * sizeof(double));
+        for (int j = 0; j < 2; ++j) memcpy(&hl[(size_t)j * mc], locs_pred + b + (size_t)j * m, (size_t)mc * sizeof(double));
+        // the chunk's pattern in the handle's order of the observations, and its entries bucketed by tile column (a counting
+        // sort over the chunk's entries: row by row, so a bucket keeps the rows' order)
+        hci.resize((size_t)ne); hdst.resize((size_t)ne); hsrc.resize((size_t)ne);
+        std::fill(boff.begin(), boff.end(), 0);
+        for (int i = 0; i <= mc; ++i) hrp[i] = rowpointers_pred[b + i] - e0;
+        for (int w = 0; w < ne; ++w) {
+            const int c = f->taper_inv[colindices_pred[e0 + w] - 1];
+            hci[w] = c + 1;
+            ++boff[c / TILE + 1];
+        }
+        for (int I = 0; I < nt; ++I) { boff[I + 1] += boff[I]; fill[I] = boff[I]; }
+        for (int i = 0; i < mc; ++i)
+            for (int w = hrp[i] - 1; w < hrp[i + 1] - 1; ++w) {
+                const int c = hci[w] - 1, k = fill[c / TILE]++;
+                hdst[k] = i + (c % TILE) * rows;
+                hsrc[k] = w;
+            }
+        HIPCHK_AT(who, upload_canon(K->Xp, hX.data(), (size_t)mc * p, s));
+        HIPCHK_AT(who, upload_canon(K->lp, hl.data(), (size_t)mc * 2, s));
+        HIPCHK_AT(who, hipMemcpyAsync(K->rp, hrp.data(), (size_t)(mc + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+        if (ne > 0) {
+            HIPCHK_AT(who, hipMemcpyAsync(K->ci, hci.data(), (size_t)ne * sizeof(int), hipMemcpyHostToDevice, s));
+            HIPCHK_AT(who, hipMemcpyAsync(K->bdst, hdst.data(), (size_t)ne * sizeof(int), hipMemcpyHostToDevice, s));
+            HIPCHK_AT(who, hipMemcpyAsync(K->bsrc, hsrc.data(), (size_t)ne * sizeof(int), hipMemcpyHostToDevice, s));
+            HIPCHK_AT(who, upload_canon(K->tv, taper_entries_pred + e0, (size_t)ne, s));
+        }
+        launch_loc_params(loc_args(mc, p, K->Xp, K->lp, K->locp, rows, tv, ms.smooth_kind, f->smooth_limits), s);
+        TaperLaunch t;
+        t.mode = MODE_GEOM; t.pred = true; t.nrows = mc; t.nnz = ne; t.ci = K->ci; t.rp = K->rp;
+        t.rows = K->locp; t.stride_rows = rows; t.cols = K->loc; t.stride = f->npad;
+        t.out = K->val;
+        launch_taper(t, s);
+        KrigeBandSolve a;
+        a.Lp = K->L; a.Qp = K->Q; a.w = K->w; a.toff = K->toff.data(); a.hi = f->taper_hi.empty() ? nullptr : f->taper_hi.data();
+        a.nt = nt; a.W = W; a.ring = K->ring; a.ldr = (size_t)rows; a.rows = mc;
+        a.boff = boff.data(); a.bdst = K->bdst; a.bsrc = K->bsrc; a.val = K->val; a.tapv = K->tv;
+        a.stoch = K->st; a.quad = K->qd;
+        HIPCHK_AT(who, launch_krige_band_solve(a, s));
+        HIPCHK_AT(who, hipMemcpyAsync(stochastic + b, K->st, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT(who, hipMemcpyAsync(quadform + b, K->qd, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT(who, hipGetLastError());
+        HIPCHK_AT(who, hipStreamSynchronize(s));
+    }
+    return 0;
+}
+
+extern "C" int cocons_krige_taper_release(cocons_fit *f)
+{
+    if (!f) return fail(-1, "cocons_krige_taper_release: null fit handle");
+    FIT_ENTER(f);
+    f->krige_taper.reset();             // (every entry point drains the main stream before it returns: nothing in flight uses it)
+    return 0;
+}
+
+// out6 = { prepared (0 / 1), device bytes held, rows per chunk, n, W (slots of the ring), nt (tile columns) }
+extern "C" int cocons_krige_taper_info(cocons_fit *f, long long *out6)
+{
+    const char *who = "cocons_krige_taper_info";
+    if (!f) return fail(-1, "%s: null fit handle", who);
+    if (!out6) return fail(-1, "%s: null argument", who);
+    FIT_ENTER(f);
+    if (int rc = krige_taper_handle(f, who)) return rc;
+    const KrigeTaperState *K = f->krige_taper.get();
+    out6[0] = K ? 1 : 0;
+    out6[1] = K ? K->bytes() : 0;
+    out6[2] = K ? K->rows : 0;
+    out6[3] = f->n;
+    out6[4] = krige_taper_W(f);
+    out6[5] = f->nt;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
 // Sparse branch of cocoSim (R/sim.R:177-217) on a taper handle: S = taper o cov_rns_taper(theta) assembled and factored as
 // the objective does (the band schedule of the handle's envelope), then Y = L E + trend by band_trmm_kernel and the rows
 // of Y gathered into the caller's order.  pos[i] = position of the caller's observation i in f's order.  Y in the handle's

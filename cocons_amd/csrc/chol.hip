@@ -3246,6 +3246,217 @@ void launch_krige_solve(const double *Lp, const double *Qp, const double *w, int
     }
 }
 
+// ---------------------------------------------------------------------------
+// Kriging from a held BAND factor (cocons_krige_taper_*): the same right-looking solve for a taper handle, whose factor
+// fills only the tile envelope J <= I < hi[J] and whose chunk C is sparse.  Tile I of the running right-hand side is
+// updated only by tile columns K with I < hi[K] <= K + W (W = max_J (hi[J] - J)), so at step J only the tile columns
+// J .. J + W - 1 are live: the chunk buffer is a RING of W slots of 128 columns (rows x W * 128, column-major, ld ldr),
+// tile column I in slot I mod W.  Per step J:
+//   load    tile column J + W - 1 (step 0: the first min(W, nt)) enters the slot tile J - 1 just left: the slot is zeroed
+//           and the chunk's entries of that tile column are scattered into it (krige_band_scatter_kernel; the host has
+//           bucketed them by tile column, so every stored entry is touched once)
+//   diag    V_J = R_J L_JJ^-T and the strip's partial reductions, as krige_diag_kernel
+//   update  R_I -= V_J L_IJ^T for J < I < hi[J], as krige_update_kernel
+// The factor is held packed per tile column: tile (I, J) at tile index toff[J] + (I - J), 128 x 128 column-major, the
+// strict upper triangle of the diagonal tiles zero; Qp and w as launch_krige_pack leaves them.  The padding columns
+// (>= n) of a slot are zero and the padding of the factor is the identity, so V is zero there without a mask.
+// Sum orders are those of the dense kernels: a row's outputs depend on the row's entries and its position modulo 64 only.
+
+// grid (W, nt): tile (J + blockIdx.x, J = blockIdx.y) of the factor in A (band_index layout) -> its packed place
+__global__ void __launch_bounds__(256)
+krige_band_pack_kernel(const double *A, size_t lda, int skew, int npad, const int *hi, int nt, const int *toff, double *Lp)
+{
+    const int J = blockIdx.y, I = J + (int)blockIdx.x;
+    if (I >= (hi ? hi[J] : nt)) return;
+    double *dst = Lp + (size_t)(toff[J] + (I - J)) * TILE * TILE;
+    for (int e = threadIdx.x; e < TILE * TILE; e += 256) {
+        const int r = e & (TILE - 1), c = e >> 7;
+        const double v = A[band_index(I * TILE + r, J * TILE + c, lda, skew, npad)];
+        dst[e] = (I == J && r < c) ? 0.0 : v;
+    }
+}
+
+// krige_qprep_kernel's arithmetic with the factor addressed through band_index; w = row `rowy`, zero from column n on
+__global__ void __launch_bounds__(256)
+krige_band_qprep_kernel(const double *A, size_t lda, int skew, int npad, int rowy, int n, double *Qp, double *w)
+{
+    const int J = blockIdx.x, tid = threadIdx.x;
+    if (tid < TILE) {
+        const int c = J * TILE + tid;
+        w[c] = c < n ? A[band_index(rowy, c, lda, skew, npad)] : 0.0;
+    }
+    for (int e = tid; e < 8 * 256; e += 256) {
+        const int jb = e >> 8, s = (e >> 6) & 3, lane = e & 63;
+        const int m = lane & 15, k = lane >> 4, c = m & 3;
+        double q = 0.0;
+        if ((m >> 2) == s && k <= c) {
+            const int d0 = J * TILE + 16 * jb + 4 * s;                                     // the 4 x 4 diagonal sub-block
+            auto L = [&](int i, int j) { return A[band_index(d0 + i, d0 + j, lda, skew, npad)]; };
+            const double l10 = L(1, 0), l20 = L(2, 0), l30 = L(3, 0), l21 = L(2, 1), l31 = L(3, 1), l32 = L(3, 2);
+            const double r0 = 1.0 / L(0, 0), r1 = 1.0 / L(1, 1), r2 = 1.0 / L(2, 2), r3 = 1.0 / L(3, 3);
+            const double m00 = r0, m11 = r1, m22 = r2, m33 = r3;
+            const double m10 = -(l10 * m00) * r1;
+            const double m21 = -(l21 * m11) * r2;
+            const double m32 = -(l32 * m22) * r3;
+            const double m20 = -fma(l21, m10, l20 * m00) * r2;
+            const double m31 = -fma(l32, m21, l31 * m11) * r3;
+            const double m30 = -fma(l32, m20, fma(l31, m10, l30 * m00)) * r3;
+            q = sel_lower4(c, k, m00, m10, m11, m20, m21, m22, m30, m31, m32, m33);
+        }
+        Qp[(size_t)J * 2048 + e] = q;
+    }
+}
+
+// entries [0, count) of one tile column's bucket: slot[dst[k]] = val[src[k]] * tapv[src[k]] (dst = row + column in the
+// tile * ldr; the pattern's columns are strictly increasing within a row, so no two entries share a destination)
+__global__ void __launch_bounds__(256)
+krige_band_scatter_kernel(double *slot, const int *dst, const int *src, int count, const double *val, const double *tapv)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= count) return;
+    const int w = src[k];
+    slot[dst[k]] = tapv[w] * val[w];
+}
+
+// V_J = R_J L_JJ^-T in the slot S (64 blockIdx.x .. + 63 of its rows, ld ldr), Lt = the packed diagonal tile, Qt / wt its
+// operands and the 128 entries of w; first: J == 0 (the sums start here).  LDS as krige_diag_kernel.
+__global__ void __launch_bounds__(256)
+krige_band_diag_kernel(const double *Lt, const double *Qt, const double *wt, double *S, size_t ldr, int first, double *stoch,
+                       double *quad)
+{
+    __shared__ double SL[36 * 256];
+    __shared__ double QS[8 * 256];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    fetch_factor_tile<false>(Lt, TILE, 0, Qt, SL, QS, tid);
+    const int rs = 64 * (int)blockIdx.x + 16 * wave;
+    d4 B[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) B[j] = glb_blk(S, ldr, rs, 16 * j, lane);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        d4 L = lds_blk(SL + (j * (j + 1) / 2 + j) * 256, lane);
+        double Q[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) Q[s] = QS[j * 256 + s * 64 + lane];
+        trsm16(B[j], L, Q);
+        d4 NX = -B[j];
+#pragma unroll
+        for (int jj = j + 1; jj < 8; ++jj) {
+            d4 Lb = lds_blk(SL + (jj * (jj + 1) / 2 + j) * 256, lane);
+            blk_mma(B[jj], NX, Lb);
+        }
+    }
+    // partial sums in (j, r) order, then the four column groups of a row in a fixed tree (krige_diag_kernel)
+    double sp = 0.0, qp = 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double v = B[j][r];
+            sp = fma(v, wt[16 * j + 4 * r + (lane >> 4)], sp);
+            qp = fma(v, v, qp);
+        }
+    sp += __shfl_xor(sp, 16);
+    qp += __shfl_xor(qp, 16);
+    sp += __shfl_xor(sp, 32);
+    qp += __shfl_xor(qp, 32);
+    if (lane < 16) {
+        const int i = rs + lane;
+        if (first) { stoch[i] = sp; quad[i] = qp; }
+        else { stoch[i] += sp; quad[i] += qp; }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) glb_blk_store(S, ldr, rs, 16 * j, lane, B[j]);
+}
+
+// R_I -= V_J L_IJ^T, I = J + 1 + blockIdx.y: Lcol = the packed tiles of tile column J (tile I at Lcol + (I - J) tiles), ring
+// slot I mod W updated from slot jslot = J mod W.  Registers and LDS as krige_update_kernel.
+__global__ void __launch_bounds__(256)
+krige_band_update_kernel(const double *Lcol, double *ring, size_t ldr, int jslot, int W)
+{
+    __shared__ double LS[TILE * KU_KC];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int d = 1 + (int)blockIdx.y, islot = jslot + d < W ? jslot + d : jslot + d - W;      // I = J + d, jslot = J mod W
+    const double *Lt = Lcol + (size_t)d * TILE * TILE;
+    const int cv = jslot * TILE, cr = islot * TILE;         // first ring columns of V_J and of R_I
+    const int rs = 64 * (int)blockIdx.x + 16 * wave;
+    d4 acc[8];
+#pragma unroll
+    for (int jb = 0; jb < 8; ++jb) acc[jb] = glb_blk(ring, ldr, rs, cr + 16 * jb, lane);
+    for (int kc = 0; kc < TILE / KU_KC; ++kc) {
+        double v[TILE * KU_KC / 256];
+#pragma unroll
+        for (int q = 0; q < TILE * KU_KC / 256; ++q) {
+            const int e = tid + 256 * q, j = e & (TILE - 1), k = e >> 7;
+            v[q] = Lt[(size_t)j + (size_t)(KU_KC * kc + k) * TILE];
+        }
+        __syncthreads();                  // every wave is done with the previous slice
+#pragma unroll
+        for (int q = 0; q < TILE * KU_KC / 256; ++q) {
+            const int e = tid + 256 * q, j = e & (TILE - 1), k = e >> 7;
+            LS[(((j >> 4) * (KU_KC / 16) + (k >> 4)) << 8) + ((k & 15) << 4) + (j & 15)] = v[q];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kb = 0; kb < KU_KC / 16; ++kb) {
+            const d4 NP = -glb_blk(ring, ldr, rs, cv + KU_KC * kc + 16 * kb, lane);
+#pragma unroll
+            for (int jb = 0; jb < 8; ++jb) {
+                const d4 Q = lds_blk(LS + ((jb * (KU_KC / 16) + kb) << 8), lane);
+                blk_mma(acc[jb], NP, Q);
+            }
+        }
+    }
+#pragma unroll
+    for (int jb = 0; jb < 8; ++jb) glb_blk_store(ring, ldr, rs, cr + 16 * jb, lane, acc[jb]);
+}
+
+void launch_krige_band_pack(const double *A, size_t lda, int skew, int npad, int n, const int *d_hi, int nt, int W,
+                            const int *d_toff, double *Lp, double *Qp, double *w, hipStream_t s)
+{
+    if (nt <= 0 || W <= 0) return;
+    hipLaunchKernelGGL(krige_band_pack_kernel, dim3((unsigned)W, (unsigned)nt), dim3(256), 0, s, A, lda, skew, npad, d_hi, nt,
+                       d_toff, Lp);
+    hipLaunchKernelGGL(krige_band_qprep_kernel, dim3(nt), dim3(256), 0, s, A, lda, skew, npad, npad, n, Qp, w);
+}
+
+hipError_t launch_krige_band_load(double *slot, size_t ldr, const int *dst, const int *src, int count, const double *val,
+                                  const double *tapv, hipStream_t s)
+{
+    hipError_t e = hipMemsetAsync(slot, 0, ldr * TILE * sizeof(double), s);
+    if (e != hipSuccess || count <= 0) return e;
+    hipLaunchKernelGGL(krige_band_scatter_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, slot, dst, src, count,
+                       val, tapv);
+    return hipSuccess;
+}
+
+hipError_t launch_krige_band_solve(const KrigeBandSolve &a, hipStream_t s)
+{
+    if (a.rows <= 0 || a.nt <= 0) return hipSuccess;
+    const unsigned strips = (unsigned)((a.rows + 63) / 64);
+    const int nt = a.nt, W = a.W;
+    auto load = [&](int I) {
+        const int k0 = a.boff[I], k1 = a.boff[I + 1];
+        return launch_krige_band_load(a.ring + (size_t)(I % W) * TILE * a.ldr, a.ldr, a.bdst + k0, a.bsrc + k0, k1 - k0, a.val,
+                                      a.tapv, s);
+    };
+    for (int I = 0; I < std::min(W, nt); ++I)
+        if (hipError_t e = load(I)) return e;
+    for (int J = 0; J < nt; ++J) {
+        if (J > 0 && J + W - 1 < nt)
+            if (hipError_t e = load(J + W - 1)) return e;
+        const double *Lcol = a.Lp + (size_t)a.toff[J] * TILE * TILE;
+        hipLaunchKernelGGL(krige_band_diag_kernel, dim3(strips), dim3(256), 0, s, Lcol, a.Qp + (size_t)J * 2048,
+                           a.w + (size_t)J * TILE, a.ring + (size_t)(J % W) * TILE * a.ldr, a.ldr, J == 0 ? 1 : 0, a.stoch, a.quad);
+        const int hj = a.hi ? a.hi[J] : nt;
+        if (hj - J - 1 > 0)
+            hipLaunchKernelGGL(krige_band_update_kernel, dim3(strips, (unsigned)(hj - J - 1)), dim3(256), 0, s, Lcol, a.ring, a.ldr,
+                               J % W, W);
+    }
+    return hipGetLastError();
+}
+
 // Predictive covariance from the solved chunk (cocons_krige_joint): S(I, J) -= V(I, :) V(J, :)' over the lower 128 x 128
 // tiles of S.  One workgroup per (64-row strip of tile row I, tile column J <= I): a wave 16 rows, all 128 columns of
 // the tile in eight accumulators, as krige_update_kernel.  Both operands are rows of the same V (column-major, ld ldv):

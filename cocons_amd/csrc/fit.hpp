@@ -162,6 +162,31 @@ struct KrigeState {
     long long bytes = 0;          // device bytes held
 };
 
+// Kriging state of a taper handle (cocons_krige_taper_prepare / _apply / _release): the band factor packed
+// per tile column and a ring of W tile columns for the chunk.  Owned by the state like KrigeState's buffers: no other entry
+// point reads or writes it.
+struct KrigeTaperState {
+    DevBuf<double> L;             // the envelope's lower tiles: tile (I, J) at toff[J] + (I - J) (kernels.h launch_krige_band_pack)
+    DevBuf<double> Q;             // nt x 2048
+    DevBuf<double> w;             // npad: L^-1 (z[:, z_col] - X mean), zero in the padding
+    DevBuf<double> loc;           // LOCP_FIELDS x npad: observation-side SoA in the prediction branch's parameters
+    DevBuf<double> ring;          // rows x W * 128: tile column I of the chunk's right-hand side in slot I mod W
+    DevBuf<double> Xp, lp, locp;  // the chunk's X_pred (rows x p), locations (rows x 2) and SoA (LOCP_FIELDS x rows)
+    DevBuf<double> st, qd;        // rows: the chunk's outputs
+    DevBuf<int> d_toff;           // nt: device copy of toff
+    // CSR staging of a chunk, ecap entries (grown to the densest chunk seen): mapped columns, the caller's taper values, the
+    // entries' covariance values, the buckets (destination in the slot, entry index), and the chunk's row pointers
+    DevBuf<int> ci, rp, bdst, bsrc;
+    DevBuf<double> tv, val;
+    size_t ecap = 0;
+    std::vector<int> toff;        // nt + 1: first packed tile of every tile column
+    std::vector<double> theta;    // 6 p: the prepared theta (canonicalised)
+    std::vector<double> mean;     // p
+    int rows = 0, W = 0;          // rows per chunk (a multiple of 64), slots of the ring
+    long long fixed_bytes = 0;    // device bytes of everything but the CSR staging
+    long long bytes() const { return fixed_bytes + (long long)(ecap * (3 * sizeof(int) + 2 * sizeof(double))); }
+};
+
 // host-side plan of one evaluation's exchange: per block k the rows below it, dealt to their owners and packed
 struct ShardPlan {
     int nt = 0, mt = 0, world = 0, group = 0;
@@ -341,6 +366,7 @@ struct cocons_fit {
                                   // (engine_warm: try_lock under the registry's lock -- a busy handle is not probed, a probed one
                                   // can neither be used nor destroyed until the probe is over)
     std::unique_ptr<KrigeState> krige;   // kriging state (cocons_krige_prepare): one factor of Sigma(theta) held apart from dA
+    std::unique_ptr<KrigeTaperState> krige_taper;   // taper fit: kriging state (cocons_krige_taper_prepare); clones and twins carry none
     std::unique_ptr<GradState> grad;     // scratch of cocons_neg2loglik_grad_dense (allocated on first use)
     std::unique_ptr<TaperGradState> tgrad;   // taper fit: state of cocons_neg2loglik_grad_taper (allocated on first use)
 };

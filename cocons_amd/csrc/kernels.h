@@ -307,6 +307,29 @@ void launch_krige_pack(const double *A, size_t lda, int nt, int rowy, int c_lo, 
                        hipStream_t s);
 void launch_krige_solve(const double *Lp, const double *Qp, const double *w, int nt, double *C, size_t ldc, int rows,
                         int c_lo, int c_hi, double *stoch, double *quad, hipStream_t s);
+// Kriging from a held band factor (cocons_krige_taper_*; chol.hip).  band_pack: the envelope's lower tiles of the factor in A
+// (band_index layout; d_hi: device copy of the envelope, null = hi[c] = nt; W = max_c (hi[c] - c)) into Lp, tile (I, J) at tile
+// index d_toff[J] + (I - J) (d_toff: device, nt ints), the operands of every diagonal tile into Qp (nt x 2048) and
+// w[c] = A(npad, c) for c < n, else 0 (npad doubles).
+void launch_krige_band_pack(const double *A, size_t lda, int skew, int npad, int n, const int *d_hi, int nt, int W,
+                            const int *d_toff, double *Lp, double *Qp, double *w, hipStream_t s);
+// load: one ring slot (128 columns of ldr rows) zeroed, then slot[dst[k]] = tapv[src[k]] * val[src[k]] for k < count
+// (dst = row + column in the tile * ldr, all different)
+hipError_t launch_krige_band_load(double *slot, size_t ldr, const int *dst, const int *src, int count, const double *val,
+                                  const double *tapv, hipStream_t s);
+// band_solve: V = C L^-T for the `rows` rows of a sparse chunk C through a ring of W slots (rows x W * 128 doubles, ld ldr >=
+// rows rounded up to 64), stoch[i] = V(i,:) w, quad[i] = V(i,:) V(i,:)'.  The chunk's entries are bucketed by tile column:
+// bucket I = the entries boff[I] .. boff[I + 1] of bdst / bsrc (device; boff, toff and hi are HOST arrays, hi null = nt).
+// Rows are independent and every sum order is fixed.
+struct KrigeBandSolve {
+    const double *Lp = nullptr, *Qp = nullptr, *w = nullptr;
+    const int *toff = nullptr, *hi = nullptr; int nt = 0, W = 0;
+    double *ring = nullptr; size_t ldr = 0; int rows = 0;
+    const int *boff = nullptr, *bdst = nullptr, *bsrc = nullptr;
+    const double *val = nullptr, *tapv = nullptr;
+    double *stoch = nullptr, *quad = nullptr;
+};
+hipError_t launch_krige_band_solve(const KrigeBandSolve &a, hipStream_t s);
 // schur: S(I, J) -= V(I, :) V(J, :)' over the lower 128 x 128 tiles of S (round_up(m, 128) rows and columns, column-major,
 // ld lds), V as launch_krige_solve leaves it (m rows, ld ldv >= round_up(m, 64), npad columns, zero outside [c_lo, c_hi));
 // rows >= m of V count as zero.  K runs from c_lo's tile to npad in one fixed order per element: bit-identical launches,

@@ -580,6 +580,38 @@ class CoconsTaperFit(CoconsFit):
                                                 _ip(ci), _ip(rp), _p(te), _p(st), _p(qf)), "cocons_predict_taper")
         return st, qf
 
+    def krige_taper_prepare(self, theta_list, z_col=0, max_rows=0):
+        """Factor the tapered S(theta) once and keep the band factor on the handle (cocons_krige_taper_prepare):
+        krige_taper_core then predicts at any number of new locations without factoring again.  max_rows: rows per
+        chunk (0: the library's default)."""
+        T = theta_table(theta_list)
+        mean = np.ascontiguousarray(np.asarray(theta_list["mean"], dtype=np.float64))
+        _lib.check(self._L.cocons_krige_taper_prepare(self._h, _p(T), _p(mean), int(z_col), int(max_rows)),
+                   "cocons_krige_taper_prepare")
+
+    def krige_taper_core(self, locs_pred, x_covariates_pred, pred_taper):
+        """(stochastic, quadform) at the new locations against the prepared band factor, as predict_core gives them;
+        pred_taper as predict_core takes it, its columns strictly increasing within a row."""
+        lp, Xp = _f(locs_pred), _f(x_covariates_pred)
+        m = Xp.shape[0]
+        ci = np.ascontiguousarray(np.asarray(pred_taper[0], dtype=np.int32))
+        rp = np.ascontiguousarray(np.asarray(pred_taper[1], dtype=np.int32))
+        te = np.ascontiguousarray(np.asarray(pred_taper[2], dtype=np.float64))
+        st, qf = np.empty(m), np.empty(m)
+        _lib.check(self._L.cocons_krige_taper_apply(self._h, m, _p(lp), _p(Xp), int(ci.size), _ip(ci), _ip(rp), _p(te),
+                                                    _p(st), _p(qf)), "cocons_krige_taper_apply")
+        return st, qf
+
+    def krige_taper_release(self):
+        _lib.check(self._L.cocons_krige_taper_release(self._h), "cocons_krige_taper_release")
+
+    def krige_taper_info(self):
+        """{prepared, bytes, rows, n, W, nt}: whether a state is held, its device bytes, rows per chunk, observations,
+        slots of the ring (tile columns of the band), tile columns of the factor."""
+        out = (ctypes.c_longlong * 6)()
+        _lib.check(self._L.cocons_krige_taper_info(self._h, out), "cocons_krige_taper_info")
+        return {"prepared": bool(out[0]), "bytes": int(out[1]), "rows": int(out[2]), "n": int(out[3]), "W": int(out[4]),
+                "nt": int(out[5])}
 
     def sim_core(self, theta_list, iiderrors, pivot=None):
         """Fields of the sparse branch of cocoSim (R/sim.R:177-217), n x nsim: (L_P E)[k] + (X mean) scattered to rows
@@ -634,6 +666,10 @@ def cocoPredict_sparse(theta_list, locs, newlocs, X_std, X_pred_std, smooth_limi
     finally:
         if own:
             f.close()
+    return _sparse_predict_tail(theta_list, X_pred_std, st, qf, type)
+
+
+def _sparse_predict_tail(theta_list, X_pred_std, st, qf, type):
     Xp = np.asarray(X_pred_std, dtype=np.float64)
     systematic = Xp @ np.asarray(theta_list["mean"], dtype=np.float64)                    # :247
     if type == "mean":
@@ -644,6 +680,24 @@ def cocoPredict_sparse(theta_list, locs, newlocs, X_std, X_pred_std, smooth_limi
     neg = unc < 1e-10
     unc[neg] = np.abs(unc[neg])                                                            # :269-271
     return {"systematic": systematic, "stochastic": st, "sd.pred": np.sqrt(unc)}
+
+
+def cocoPredict_sparse_chunked(theta_list, locs, newlocs, X_std, X_pred_std, smooth_limits, z, ref_taper, pred_taper,
+                               type="pred", fit=None, max_rows=0):
+    """cocoPredict_sparse from one held band factor: S(theta) is factored once (krige_taper_prepare) and the new
+    locations are predicted in chunks of max_rows rows (0: the library's default) through a ring of the band's tile
+    columns -- device memory does not grow with the number of new locations.  Returns what cocoPredict_sparse returns."""
+    f, own = (fit, False) if fit is not None else (CoconsTaperFit(locs, X_std, z, smooth_limits, *ref_taper), True)
+    try:
+        f.krige_taper_prepare(theta_list, max_rows=max_rows)
+        try:
+            st, qf = f.krige_taper_core(newlocs, X_pred_std, pred_taper)
+        finally:
+            f.krige_taper_release()
+    finally:
+        if own:
+            f.close()
+    return _sparse_predict_tail(theta_list, X_pred_std, st, qf, type)
 
 
 def _cv_result(f, z, resid, var):

@@ -378,6 +378,24 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
   res[[2]]
 }
 
+# the same core at any number of new locations from ONE factorisation of the tapered matrix (a map grid, a map in pieces):
+#   .cocons.hip.krige.taper.prepare(fit, theta_list)                     # S(theta) factored once, the band factor kept
+#   kr <- .cocons.hip.krige.taper(fit, newlocs, X_pred_std, pred_taper)  # as often as needed: chunked, memory independent of m
+#   .cocons.hip.krige.taper.release(fit)                                 # (or when the handle is closed)
+.cocons.hip.krige.taper.prepare <- function(fit, theta_list, z_col = 1L, max_rows = 0L) {
+  res <- .Call(`_cocons_hip_krige_taper_prepare`, fit, theta_list[-1], theta_list$mean, as.integer(z_col), as.integer(max_rows))
+  if (res[[1]] > 0L) stop("Cholesky error")
+  invisible(NULL)
+}
+
+.cocons.hip.krige.taper <- function(fit, newlocs, X_pred, pred_taper) {
+  res <- .Call(`_cocons_hip_krige_taper`, fit, newlocs, X_pred, pred_taper@colindices, pred_taper@rowpointers,
+               as.double(pred_taper@entries))
+  res[[2]]
+}
+
+.cocons.hip.krige.taper.release <- function(fit) invisible(.Call(`_cocons_hip_krige_taper_release`, fit))
+
 # sparse branch of cocoSim (R/sim.R:177-217): the lines from cov_rns_taper to the sweep (:193-216) become
 #   fields <- .cocons.hip.sim.taper(fit, theta_list, iiderrors, pivot)     # fit: cocons_hip_taper_fit(...)
 # pivot = spam::ordering(spam::chol(ref_taper)) gives the reference's fields to rounding (MMD depends only on the pattern:

@@ -855,6 +855,46 @@ SEXP _cocons_hip_predict_taper(SEXP fitp, SEXP theta, SEXP mean, SEXP z_col, SEX
     return out;
 }
 
+/* kriging from a held band factor on a taper handle: factor S(theta) once for realization z_col (1-based) and keep the band
+ * factor on the handle; max_rows = 0: the library's default chunk.  list(status, NULL) -- status > 0: the failing minor */
+SEXP _cocons_hip_krige_taper_prepare(SEXP fitp, SEXP theta, SEXP mean, SEXP z_col, SEXP max_rows)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp);
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    if (XLENGTH(mean) != p) Rf_error("theta$mean must have length %d", p);
+    int rc = cocons_krige_taper_prepare(f, T, REAL(mean), Rf_asInteger(z_col) - 1, Rf_asInteger(max_rows));
+    hip_check(rc, "cocoPredict (sparse, krige prepare)");
+    return status_value(rc, R_NilValue);
+}
+
+/* the sparse kriging core at new locations against the held band factor: list(status, cbind(stochastic, quadform));
+ * pred_taper's slots as _cocons_hip_predict_taper takes them */
+SEXP _cocons_hip_krige_taper(SEXP fitp, SEXP locs_pred, SEXP X_pred, SEXP colindices, SEXP rowpointers, SEXP entries)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), m = Rf_nrows(X_pred);
+    if (Rf_ncols(X_pred) != p || Rf_nrows(locs_pred) != m || Rf_ncols(locs_pred) != 2)
+        Rf_error("prediction design / locations do not match the fit");
+    if (!Rf_isInteger(colindices) || !Rf_isInteger(rowpointers) || XLENGTH(rowpointers) != (R_xlen_t)m + 1 ||
+        XLENGTH(entries) != XLENGTH(colindices))
+        Rf_error("pred_taper does not match the prediction locations");
+    SEXP v = PROTECT(Rf_allocMatrix(REALSXP, m, 2));
+    int rc = cocons_krige_taper_apply(f, m, REAL(locs_pred), REAL(X_pred), (int)XLENGTH(colindices), INTEGER(colindices),
+                                      INTEGER(rowpointers), REAL(entries), REAL(v), REAL(v) + m);
+    hip_check(rc, "cocoPredict (sparse, krige)");
+    SEXP out = status_value(rc, v);
+    UNPROTECT(1);
+    return out;
+}
+
+SEXP _cocons_hip_krige_taper_release(SEXP fitp)
+{
+    hip_check(cocons_krige_taper_release(fit_of(fitp)), "cocoPredict (sparse, krige release)");
+    return R_NilValue;
+}
+
 /* sparse branch of cocoSim (R/sim.R:177-217) on a taper handle: iiderrors n x nsim -> list(status, n x nsim fields).
  * pivot: R NULL (the handle's own order: same distribution, another field for the same draws) or an integer vector,
  * spam::ordering(spam::chol(ref_taper)) for the reference's fields to rounding */
@@ -908,6 +948,9 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_krige", (DL_FUNC)&_cocons_hip_krige, 3},
     {"_cocons_hip_krige_joint", (DL_FUNC)&_cocons_hip_krige_joint, 6},
     {"_cocons_hip_krige_release", (DL_FUNC)&_cocons_hip_krige_release, 1},
+    {"_cocons_hip_krige_taper_prepare", (DL_FUNC)&_cocons_hip_krige_taper_prepare, 5},
+    {"_cocons_hip_krige_taper", (DL_FUNC)&_cocons_hip_krige_taper, 6},
+    {"_cocons_hip_krige_taper_release", (DL_FUNC)&_cocons_hip_krige_taper_release, 1},
     {"_cocons_hip_sim", (DL_FUNC)&_cocons_hip_sim, 5},
     {"_cocons_hip_sim_cond", (DL_FUNC)&_cocons_hip_sim_cond, 8},
     {"_cocons_hip_sim_taper", (DL_FUNC)&_cocons_hip_sim_taper, 5},

@@ -147,6 +147,35 @@ int cocons_predict_taper(cocons_fit *fit, const double *theta, const double *mea
                          const int *rowpointers_pred, const double *taper_entries_pred,
                          double *stochastic, double *quadform);
 
+/* Kriging from a held BAND factor: cocons_predict_taper in two parts, for any number of new locations at one theta.
+ * cocons_krige_taper_prepare (taper handles, every buffer layout) assembles S(theta) as cocons_predict_taper does, factors it
+ * once with (z[:, z_col] - X mean)' as the one right-hand side and keeps, in buffers of its own on the handle: the lower
+ * 128 x 128 tiles of the factor's envelope packed per tile column, the solve's operands per diagonal tile, w = L^-1 r,
+ * the observation side of cov_rns_taper_pred and the chunk buffers.  It replaces any earlier state; on a non-positive
+ * pivot it returns the failing minor (> 0) and leaves no state.
+ * cocons_krige_taper_apply: for m >= 0 new locations it returns
+ *   stochastic[i] = c_i' S^-1 (z - X mean),  quadform[i] = c_i' S^-1 c_i            (the quantities of cocons_predict_taper)
+ * from the same inputs: locs_pred m x 2, X_pred m x p (column-major), and pred_taper's CSR slots, 1-based, columns =
+ * observations in the caller's order.  Chunks hold at most `max_rows` rows (rounded down to a multiple of 64, at least 64;
+ * 0: as many as keep the chunk buffers within 1 GiB, at most 16384).  A chunk's right-hand side lives in a ring of W tile
+ * columns (W = the widest tile column of the envelope), never in rows x n.  Apply does no factorisation.  Device memory
+ * held does not depend on m: the CSR staging of a chunk belongs to the state, is grown to the densest chunk seen and is
+ * counted in the reported bytes.  A row's outputs depend only on that row's data, the state and the row's position modulo
+ * 64 in the request -- not on max_rows, on m or on the other rows; repeats agree bit for bit (fixed sum order, no
+ * atomics).  A row without neighbours gives exactly 0.0 and 0.0.
+ * Refused with -1 and a message starting with the entry's name, before any device work and with the outputs untouched:
+ * null arguments or m < 0; a dense or sharded handle; no prepared state; rowpointers_pred[0] != 1, decreasing row
+ * pointers or rowpointers_pred[m] != nnz_pred + 1; a column outside [1, n]; column indices not strictly increasing
+ * within a row (spam's invariant; the scatter relies on it).
+ * No other entry point reads or writes the state; cocons_krige_taper_release and cocons_fit_destroy free it.
+ * cocons_krige_taper_info: out6 = {prepared, device bytes held, rows per chunk, n, W, nt (tile columns)}.               */
+int cocons_krige_taper_prepare(cocons_fit *fit, const double *theta, const double *mean, int z_col, int max_rows);
+int cocons_krige_taper_apply(cocons_fit *fit, int m, const double *locs_pred, const double *X_pred, int nnz_pred,
+                             const int *colindices_pred, const int *rowpointers_pred, const double *taper_entries_pred,
+                             double *stochastic, double *quadform);
+int cocons_krige_taper_release(cocons_fit *fit);
+int cocons_krige_taper_info(cocons_fit *fit, long long *out6);
+
 /* Sparse branch of cocoSim (R/sim.R:177-217) on a taper handle.  S = taper o cov_rns_taper(theta) (the handle's pattern
  * and taper entries), ordered by `pivot` (1-based permutation of 1..n, spam's `ordering(cholS)`; NULL = the handle's own
  * order, see cocons_fit_taper_order).  With L_P L_P' = S[pivot, pivot] and E = iiderrors (n x nsim, column-major, used
