@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include <atomic>
 #include <vector>
 #include "../../include/cocons_hip.h"
 
@@ -235,6 +236,15 @@ void set_update_w8_max_tiles(int ntiles);
 void set_update_c_wt(int on);           // (experiment) every C tile through L2-bypassing loads and write-through stores
 int device_cus();                                           // CUs of the device (asked once per process)
 inline int resident_slots() { return 8 * device_cus(); }    // the chip holds 8 workgroups of the update and DAG kernels on each
+// the attribute that allows more than 64 KB of dynamic LDS is per kernel and device: set once, not per launch
+inline void set_dynamic_lds_once(const void *kernel, size_t bytes, std::atomic<unsigned long long> &done_mask)
+{
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev >= 0 && dev < 64 && ((done_mask.load(std::memory_order_relaxed) >> dev) & 1ull)) return;
+    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (dev >= 0 && dev < 64) done_mask.fetch_or(1ull << dev, std::memory_order_relaxed);
+}
 // sharded evaluation: the solved rows this rank owns of the 256-column panel at column col0 (ncols columns), gathered into
 // its slot of the owner-packed exchange buffer: for every 64-row tile ti in [ti_lo, ti_hi) with pmap[ti] inside the slot
 // [slot_lo, slot_hi): dst[pmap[ti] + rho + c * ldp] = A[(64 ti + rho) + (col0 + c) lda]
@@ -273,6 +283,7 @@ struct DagLaunch {
 };
 void launch_dag(const DagLaunch &d, hipStream_t s);
 
+// ---- what is made of a finished factor (solve.hip): reductions, draws, kriging ---------------------------------------------
 // reductions: out[0] = sum_{i<n} log(A(i,i)); out[1 + a*nr + b] = sum_{c<n} A(row0+a,c) A(row0+b,c)
 void launch_finalize(const double *A, size_t lda, int n, int row0, int nr, double *out, hipStream_t s,
                      int skew = 0, int npad = 0,           // packed band source (band_index)
@@ -307,7 +318,7 @@ void launch_krige_pack(const double *A, size_t lda, int nt, int rowy, int c_lo, 
                        hipStream_t s);
 void launch_krige_solve(const double *Lp, const double *Qp, const double *w, int nt, double *C, size_t ldc, int rows,
                         int c_lo, int c_hi, double *stoch, double *quad, hipStream_t s);
-// Kriging from a held band factor (cocons_krige_taper_*; chol.hip).  band_pack: the envelope's lower tiles of the factor in A
+// Kriging from a held band factor (cocons_krige_taper_*).  band_pack: the envelope's lower tiles of the factor in A
 // (band_index layout; d_hi: device copy of the envelope, null = hi[c] = nt; W = max_c (hi[c] - c)) into Lp, tile (I, J) at tile
 // index d_toff[J] + (I - J) (d_toff: device, nt ints), the operands of every diagonal tile into Qp (nt x 2048) and
 // w[c] = A(npad, c) for c < n, else 0 (npad doubles).

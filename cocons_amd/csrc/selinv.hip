@@ -14,35 +14,16 @@
 //   selinv_diag_kernel : step J, Z_JJ (one wave per 16 x 16 block) and a_J (one wave per four columns)
 // Z goes to a second buffer of the band's shape; L is consumed (every operation on the handle assembles its matrix anew).
 // Two launches per tile column; every sum has a fixed order and nothing is accumulated atomically: repeated calls agree
-// bit for bit.  Blocks are held in the factorisation's register layout (chol.hip: reg r of lane l <-> (row l & 15,
+// bit for bit.  Blocks are held in the factorisation's register layout (tile_ops.hpp: reg r of lane l <-> (row l & 15,
 // column 4 r + (l >> 4))), in which blk_mma(acc, P, Q) is acc(i, j) += sum_k P(i, k) Q(j, k).
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include "kernels.h"
+#include "tile_ops.hpp"
 
 namespace cocons {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-#define MFMA64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
-
 namespace {
-
-__device__ __forceinline__ void blk_mma(d4 &acc, const d4 &P, const d4 &Q)
-{
-    acc = MFMA64(Q[0], P[0], acc);
-    acc = MFMA64(Q[1], P[1], acc);
-    acc = MFMA64(Q[2], P[2], acc);
-    acc = MFMA64(Q[3], P[3], acc);
-}
-
-// B(row, col) = T[r0 + row, c0 + col]
-__device__ __forceinline__ d4 blk_ld(const double *T, size_t ld, int r0, int c0, int lane)
-{
-    const double *p = T + (size_t)(r0 + (lane & 15)) + (size_t)(c0 + (lane >> 4)) * ld;
-    d4 v;
-    v[0] = p[0]; v[1] = p[4 * ld]; v[2] = p[8 * ld]; v[3] = p[12 * ld];
-    return v;
-}
 
 // B(row, col) = T[r0 + col, c0 + row]: the transpose of the 16 x 16 block at (r0, c0)
 __device__ __forceinline__ d4 blk_ld_t(const double *T, size_t ld, int r0, int c0, int lane)
@@ -51,12 +32,6 @@ __device__ __forceinline__ d4 blk_ld_t(const double *T, size_t ld, int r0, int c
     d4 v;
     v[0] = p[0]; v[1] = p[4]; v[2] = p[8]; v[3] = p[12];
     return v;
-}
-
-__device__ __forceinline__ void blk_st(double *T, size_t ld, int r0, int c0, int lane, const d4 &v)
-{
-    double *p = T + (size_t)(r0 + (lane & 15)) + (size_t)(c0 + (lane >> 4)) * ld;
-    p[0] = v[0]; p[4 * ld] = v[1]; p[8 * ld] = v[2]; p[12 * ld] = v[3];
 }
 
 __device__ __forceinline__ size_t tile_off(int I, int J, size_t ld, int skew, int npad)
@@ -109,7 +84,7 @@ selinv_g_kernel(SelinvArgs a)
     for (int rb = 0; rb < 2; ++rb)
         for (int cb = 0; cb < 8; ++cb) acc[rb][cb] = (d4){0.0, 0.0, 0.0, 0.0};
     for (int kb = 0; kb < 8; ++kb) {
-        const d4 P0 = blk_ld(X, ld, r0, kb * 16, lane), P1 = blk_ld(X, ld, r0 + 16, kb * 16, lane);
+        const d4 P0 = glb_blk(X, ld, r0, kb * 16, lane), P1 = glb_blk(X, ld, r0 + 16, kb * 16, lane);
 #pragma unroll
         for (int cb = 0; cb < 8; ++cb) {
             if (cb > kb) continue;                 // W is lower triangular: W(k, j) = 0 for k < j
@@ -119,7 +94,7 @@ selinv_g_kernel(SelinvArgs a)
         }
     }
     for (int rb = 0; rb < 2; ++rb)
-        for (int cb = 0; cb < 8; ++cb) blk_st(X, ld, r0 + 16 * rb, cb * 16, lane, acc[rb][cb]);
+        for (int cb = 0; cb < 8; ++cb) glb_blk_store(X, ld, r0 + 16 * rb, cb * 16, lane, acc[rb][cb]);
 }
 
 // Step J: Z_IJ = - sum_{J < K < hi} Zop(I, K) G_KJ for I = J + 1 + blockIdx.y.  blockIdx.x: the 64 x 64 quadrant of the
@@ -142,7 +117,7 @@ selinv_col_kernel(SelinvArgs a, int J, int hi)
         for (int kb = 0; kb < 8; ++kb) {
             d4 P[2], Q[2];
             for (int rb = 0; rb < 2; ++rb)
-                P[rb] = straight ? blk_ld(Zt, a.ldz, ro + 16 * rb, kb * 16, lane) : blk_ld_t(Zt, a.ldz, kb * 16, ro + 16 * rb, lane);
+                P[rb] = straight ? glb_blk(Zt, a.ldz, ro + 16 * rb, kb * 16, lane) : blk_ld_t(Zt, a.ldz, kb * 16, ro + 16 * rb, lane);
             for (int cb = 0; cb < 2; ++cb) Q[cb] = blk_ld_t(G, a.ldl, kb * 16, co + 16 * cb, lane);
             for (int rb = 0; rb < 2; ++rb)
                 for (int cb = 0; cb < 2; ++cb) blk_mma(acc[rb][cb], P[rb], Q[cb]);
@@ -150,7 +125,7 @@ selinv_col_kernel(SelinvArgs a, int J, int hi)
     }
     double *O = a.Z + tile_off(I, J, a.ldz, a.skew, a.npad);
     for (int rb = 0; rb < 2; ++rb)
-        for (int cb = 0; cb < 2; ++cb) blk_st(O, a.ldz, ro + 16 * rb, co + 16 * cb, lane, -acc[rb][cb]);
+        for (int cb = 0; cb < 2; ++cb) glb_blk_store(O, a.ldz, ro + 16 * rb, co + 16 * cb, lane, -acc[rb][cb]);
 }
 
 // Step J, behind selinv_col_kernel.  Workgroups 0 .. 15: Z_JJ = W' W - sum_K Z_KJ' G_KJ (W = L_JJ^-1), one wave per
@@ -193,9 +168,9 @@ selinv_diag_kernel(SelinvArgs a, int J, int hi)
                 const int row = lane & 15, col = 4 * r + (lane >> 4);
                 if (row < col) out[r] = t[col + 16 * row];
             }
-            blk_st(O, a.ldz, rb * 16, cb * 16, lane, out);
+            glb_blk_store(O, a.ldz, rb * 16, cb * 16, lane, out);
         } else {
-            blk_st(O, a.ldz, rb * 16, cb * 16, lane, out);
+            glb_blk_store(O, a.ldz, rb * 16, cb * 16, lane, out);
             double *q = O + (size_t)(cb * 16 + (lane >> 4)) + (size_t)(rb * 16 + (lane & 15)) * a.ldz;      // the transpose
             q[0] = out[0]; q[4] = out[1]; q[8] = out[2]; q[12] = out[3];
         }

@@ -1,7 +1,7 @@
 """The ring solve of cocons_krige_taper_apply in numpy, with a small tile edge: V = C L^-T for a sparse chunk C and a
 lower factor L that fills only the tile envelope J <= I < hi[J], right-looking over the tile columns with the running
 right-hand side held in a ring of W = max_J (hi[J] - J) tile columns (tile column I in slot I mod W).  The device code
-(chol.hip, launch_krige_band_solve) takes exactly these steps per tile column J: load, diag, update."""
+(solve.hip, launch_krige_band_solve) takes exactly these steps per tile column J: load, diag, update."""
 import numpy as np
 
 
