@@ -595,3 +595,225 @@ extern "C" int cocons_debug_taper_selinv(cocons_fit *f, const double *theta, dou
     if (bytes_out) *bytes_out = f->tgrad->bytes;
     return 0;
 }
+
+// ---------------------------------------------------------------------------
+// Expected (Fisher) information of a tapered fit on the band factor.  With S = T o C(theta) = L L' and
+// M_a = L^-1 S_a L^-T,  tr(S^-1 S_a S^-1 S_b) = <M_a, M_b>_F, and for probe rows e_k with sum_k e_k e_k' = c I
+//     sum_k (e_k' L^-1 S_a L^-T) . (e_k' L^-1 S_b L^-T) = c <M_a, M_b>_F:
+// the n unit vectors give it exactly, N random +-1 probes give Hutchinson's estimate.  One operation: the objective's assembly
+// and band factorisation (as cocons_krige_taper_prepare runs it: the same bits under every buffer layout), the factor packed
+// twice into buffers of the call -- its own tiles for the forward sweep, the flipped transpose for the backward one --, the
+// directions' entries on the pattern, then per chunk of probe rows: backward sweep, sparse product, forward sweep of every
+// direction's rows at once (with X' riding in the first chunk for the mean block), Gram partial sums per 64-row strip.
+// Nothing of it stays on the handle; the kriging and gradient states are neither read nor written.
+static constexpr size_t FISHER_TAPER_CHUNK_BYTES = (size_t)1 << 30;
+static constexpr int FISHER_TAPER_ROWS_CAP = 16384;
+
+struct FisherTaperCall {
+    DevBuf<double> Lp, Qp, Mp, Qb, E, U, Sd, wsite, site, dirs, zero, st, qd, seg, part, partm, out;
+    DevBuf<int> itab, pat, pos;        // itab: toff | toffb | hib (nt each); pat: frp (n + 1) | fci | fidx (full nnz each)
+    std::vector<int> toff, toffb, hi, hib;
+    size_t fnnz = 0;
+    int ndir = 0, nprobe = 0, c = 0, total = 0, W = 0;
+};
+
+static int fisher_taper_enqueue(cocons_fit *f, const double *theta, FisherTaperCall &c, const double *probes, double *hinfo,
+                                double *hmean)
+{
+    const int npad = f->npad, n = f->n, p = f->p, nt = f->nt, ndir = c.ndir;
+    hipStream_t s = f->stream;
+    const std::vector<double> zero((size_t)p, 0.0);
+    // 1. the factor
+    f->nrhs_cur = f->r;
+    if (int rc = fit_alloc_matrix(f, f->r)) return rc;
+    if (int rc = assemble_sigma_taper(f, theta)) return rc;
+    assemble_rhs(f, zero.data(), true, nullptr, 0, 0, npad, true, false);
+    FactorView v = main_view(f);
+    if (!v.hi) v.hi = c.hi.data();      // no envelope: the band schedule with hi[c] = nt (cocons_krige_taper_prepare's rule)
+    if (int rc = factorize(f, v, nullptr)) return rc;
+    const int *d_toff = c.itab, *d_toffb = c.itab + nt, *d_hib = c.itab + 2 * (size_t)nt;
+    launch_krige_band_pack(f->dA, f->lda, f->skew, npad, n, f->d_thi, nt, c.W, d_toff, c.Lp, c.Qp, c.st /* w: nobody reads it */, s);
+    launch_band_back_pack(f->dA, f->lda, f->skew, npad, d_hib, nt, c.W, d_toffb, c.Mp, c.Qb, s);
+    // 2. the directions' entries
+    ThetaVecs tv;
+    make_theta_vecs(theta, p, tv, true);
+    const ModeSel ms = select_mode(theta, p, f->smooth_limits, 0);
+    const int smooth_free = ms.smooth_kind == SMOOTH_LOGISTIC_SQRT && f->smooth_limits[1] != f->smooth_limits[0];
+    launch_grad_site(loc_args(n, p, f->dX, f->dlocs, c.site, npad, tv, ms.smooth_kind, f->smooth_limits), c.site, npad, smooth_free, s);
+    TaperDirsArgs d;
+    memset(&d, 0, sizeof d);
+    d.g.n = n; d.g.npad = npad; d.g.p = p; d.g.nnz = f->taper_nnz;
+    d.g.ci = f->d_tci; d.g.rp = f->d_trp; d.g.tapv = f->d_tval;
+    d.g.loc = f->dloc; d.g.stride = npad; d.g.site = c.site;
+    d.g.X = f->dX; d.g.ldx = n;
+    d.g.nu_fixed = ms.nu_fixed; d.g.smooth_free = smooth_free;
+    d.ndir = ndir; d.dirs = c.dirs; d.wsite = c.wsite; d.out = c.Sd;
+    launch_taper_dirs(ms.mode, d, s);
+    HIPCHK(hipGetLastError());
+    // 3 - 6. the chunks
+    const size_t ldu = (size_t)ndir * c.c + 64;
+    const int *frp = c.pat, *fci = c.pat + (n + 1), *fidx = fci + c.fnnz;
+    int strip0 = 0;
+    for (int g0 = 0; g0 < c.total; g0 += c.c) {
+        const int cc = std::min(c.c, c.total - g0), cs = round_up(cc, 64), nstrips = cs / 64;
+        const bool first = g0 == 0;
+        HIPCHK(hipMemsetAsync(c.E, 0, (size_t)c.c * npad * sizeof(double), s));
+        if (c.nprobe > 0) {
+            // the chunk's probes are staged in U, which the sparse product overwrites afterwards
+            HIPCHK(upload_canon(c.U, probes + (size_t)g0 * n, (size_t)cc * n, s));
+            launch_band_given_rows(c.E, (size_t)c.c, npad, c.U, n, c.pos, cc, s);
+        } else launch_band_unit_rows(c.E, (size_t)c.c, npad, g0, cc, s);
+        BandSweep b;
+        b.Lp = c.Mp; b.Qp = c.Qb; b.toff = c.toffb.data(); b.hi = c.hib.data(); b.nt = nt;
+        b.C = c.E; b.ldc = (size_t)c.c; b.rows = cs; b.zero = c.zero; b.st = c.st; b.qd = c.qd;
+        HIPCHK(launch_band_back_solve(b, s));
+        BandSpmm m;
+        m.Wf = c.E; m.ldw = (size_t)c.c; m.rows = cs; m.n = n; m.npad = npad; m.ndir = ndir;
+        m.frp = frp; m.fci = fci; m.fidx = fidx; m.Sd = c.Sd; m.nnz = (size_t)f->taper_nnz;
+        m.U = c.U; m.ldu = ldu; m.bstride = (size_t)cs;
+        launch_band_spmm_dirs(m, s);
+        const int urows = ndir * cs + (first && hmean ? 64 : 0);
+        if (first && hmean) launch_band_x_rows(c.U, ldu, ndir * cs, f->dX, n, p, npad, s);
+        BandSweep q;
+        q.Lp = c.Lp; q.Qp = c.Qp; q.toff = c.toff.data(); q.hi = c.hi.data(); q.nt = nt;
+        q.C = c.U; q.ldc = ldu; q.rows = urows; q.zero = c.zero; q.st = c.st; q.qd = c.qd;
+        HIPCHK(launch_band_sweep(q, s));
+        launch_band_gram(c.U, ldu, 0, (size_t)cs, 64, nstrips, npad, ndir, c.seg, c.part, strip0, s);
+        if (first && hmean) launch_band_gram(c.U, ldu, (size_t)ndir * cs, 1, 1, 1, npad, p, c.seg, c.partm, 0, s);
+        strip0 += nstrips;
+    }
+    const double weight = c.nprobe > 0 ? 0.5 * f->r / c.nprobe : 0.5 * f->r;
+    launch_band_gram_sum(c.part, strip0, ndir, weight, c.out, s);
+    HIPCHK(hipMemcpyAsync(hinfo, c.out, (size_t)ndir * ndir * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (hmean) {
+        double *dmean = c.out + (size_t)ndir * ndir;
+        launch_band_gram_sum(c.partm, 1, p, (double)f->r, dmean, s);
+        HIPCHK(hipMemcpyAsync(hmean, dmean, (size_t)p * p * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int cocons_fisher_taper(cocons_fit *f, const double *theta, int ndir, const double *dirs, int nprobe,
+                                   const double *probes, int max_rows, double *info, double *info_mean)
+{
+    const char *who = "cocons_fisher_taper";
+    if (!f) return fail(-1, "%s: null fit handle", who);
+    if (!theta || !dirs || !info) return fail(-1, "%s: null argument", who);
+    if (ndir < 1 || ndir > 7 * COCONS_P_MAX) return fail(-1, "%s: ndir = %d is outside [1, %d]", who, ndir, 7 * COCONS_P_MAX);
+    if (nprobe < 0) return fail(-1, "%s: nprobe = %d is negative", who, nprobe);
+    if (nprobe > 0 && !probes) return fail(-1, "%s: nprobe = %d without probes", who, nprobe);
+    if (nprobe == 0 && probes) return fail(-1, "%s: probes given with nprobe = 0 (exact mode takes none)", who);
+    if (max_rows < 0) return fail(-1, "%s: max_rows = %d is negative", who, max_rows);
+    FIT_ENTER(f);
+    if (f->taper_nnz <= 0) return fail(-1, "%s: not a taper fit (cocons_fisher_dense serves a dense handle)", who);
+    if (f->coll_kind) return fail(-1, "%s: not available on a sharded handle", who);
+    if (f->r < 1) return fail(-1, "%s: fit has no z", who);
+    const int npad = f->npad, n = f->n, p = f->p, nt = f->nt;
+    const size_t nd = (size_t)ndir * 6 * p;
+    for (size_t e = 0; e < nd; ++e)
+        if (!std::isfinite(dirs[e])) return fail(-1, "%s: direction %d has a non-finite entry", who, (int)(e / ((size_t)6 * p)));
+    for (size_t e = 0; e < (size_t)nprobe * n; ++e)
+        if (!std::isfinite(probes[e])) return fail(-1, "%s: probe %d has a non-finite entry", who, (int)(e / (size_t)n));
+    FisherTaperCall c;
+    c.ndir = ndir; c.nprobe = nprobe; c.total = nprobe > 0 ? nprobe : n;
+    {
+        size_t rows = std::min<size_t>(FISHER_TAPER_CHUNK_BYTES / ((size_t)(ndir + 1) * npad * sizeof(double)), FISHER_TAPER_ROWS_CAP);
+        rows = std::max<size_t>(rows / 64 * 64, 64);
+        if (max_rows > 0) rows = std::min<size_t>(rows, std::max<size_t>((size_t)max_rows / 64 * 64, 64));
+        c.c = (int)std::min<size_t>(rows, (size_t)round_up(c.total, 64));
+    }
+    // the envelope, its mirror (of M = F L' F: hib[J'] = nt - the first tile column that reaches tile row nt - 1 - J') and the
+    // packed tiles' offsets of both
+    c.hi = f->taper_hi.empty() ? std::vector<int>((size_t)nt, nt) : f->taper_hi;
+    c.W = f->taper_hi.empty() ? nt : f->taper_maxband;
+    c.hib.assign((size_t)nt, 0); c.toff.assign((size_t)nt + 1, 0); c.toffb.assign((size_t)nt + 1, 0);
+    for (int J = nt - 1, lo = nt - 1; J >= 0; --J) {
+        if (lo > J) lo = J;
+        while (lo > 0 && c.hi[lo - 1] > J) --lo;
+        c.hib[nt - 1 - J] = nt - lo;
+    }
+    for (int J = 0; J < nt; ++J) {
+        const long long a = (long long)c.toff[J] + (c.hi[J] - J), b = (long long)c.toffb[J] + (c.hib[J] - J);
+        if (a > INT_MAX || b > INT_MAX) return fail(-1, "%s: the envelope holds too many tiles", who);
+        c.toff[J + 1] = (int)a; c.toffb[J + 1] = (int)b;
+    }
+    if (c.toffb[nt] != c.toff[nt]) return fail(-1, "%s: the envelope is not monotone", who);
+    // the full symmetric pattern in the handle's order (0-based) and, per entry, the index of (max, min) among the lower
+    // entries as the device pattern numbers them (row by row)
+    const std::vector<int> &rp = f->h_trp, &ci = f->h_tci;
+    if (rp.size() != (size_t)n + 1) return fail(-1, "%s: the handle keeps no host copy of its pattern", who);
+    c.fnnz = ci.size();
+    std::vector<int> pat((size_t)n + 1 + 2 * c.fnnz);
+    {
+        int *frp = pat.data(), *fci = frp + (n + 1), *fidx = fci + c.fnnz;
+        std::vector<int> cur((size_t)n);
+        for (int i = 0; i < n; ++i) { frp[i] = rp[i] - 1; cur[i] = rp[i] - 1; }
+        frp[n] = rp[n] - 1;
+        int low = 0;
+        for (int i = 0; i < n; ++i)
+            for (int t = frp[i]; t < frp[i + 1]; ++t) {
+                fci[t] = ci[t] - 1;
+                if (fci[t] <= i) fidx[t] = low++;
+            }
+        if (low != f->taper_nnz) return fail(-1, "%s: the host copy of the pattern does not match the device's", who);
+        // the upper entry (j, i), i > j, is the lower entry (i, j): row i's entries in ascending column order meet the rows j
+        // in ascending order, so one cursor per row finds them
+        for (int j = 0; j < n; ++j)
+            for (int t = frp[j]; t < frp[j + 1]; ++t) {
+                const int i = fci[t];
+                if (i <= j) continue;
+                int u = cur[i];
+                if (u >= frp[i + 1] || fci[u] != j) {
+                    for (u = frp[i]; u < frp[i + 1] && fci[u] != j; ++u) {}
+                    if (u >= frp[i + 1]) return fail(-1, "%s: the handle's pattern is not symmetric", who);
+                } else cur[i] = u + 1;
+                fidx[t] = fidx[u];
+            }
+    }
+    const size_t ntile = (size_t)c.toff[nt], ldu = (size_t)ndir * c.c + 64, nnz = (size_t)f->taper_nnz;
+    const int total_strips = (c.total / c.c) * (c.c / 64) + (round_up(c.total % c.c, 64)) / 64;
+    const bool mean = info_mean != nullptr;
+    const size_t counts[17] = {ntile * TILE * TILE, (size_t)nt * 2048, ntile * TILE * TILE, (size_t)nt * 2048, (size_t)c.c * npad, ldu * npad,
+                               (size_t)ndir * nnz, (size_t)ndir * 4 * npad, (size_t)GSITE_FIELDS * npad, nd, (size_t)npad,
+                               std::max<size_t>(ldu, (size_t)npad), ldu,
+                               std::max(band_gram_scratch_doubles(c.c / 64, npad, ndir), band_gram_scratch_doubles(1, npad, p)),
+                               (size_t)total_strips * ndir * ndir, (size_t)p * p, (size_t)ndir * ndir + (size_t)p * p};
+    DevBuf<double> *bufs[17] = {&c.Lp, &c.Qp, &c.Mp, &c.Qb, &c.E, &c.U, &c.Sd, &c.wsite, &c.site, &c.dirs, &c.zero, &c.st, &c.qd,
+                                &c.seg, &c.part, &c.partm, &c.out};
+    size_t bytes = (3 * (size_t)nt + pat.size() + (size_t)n) * sizeof(int);
+    for (size_t k : counts) bytes += k * sizeof(double);
+    std::vector<double> hinfo((size_t)ndir * ndir), hmean((size_t)p * p);
+    StreamDrain drain{f->stream, false};       // (declared behind the buffers: the stream is idle before they are freed)
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 17 && e == hipSuccess; ++k) e = bufs[k]->alloc(counts[k]);
+    if (e == hipSuccess) e = c.itab.alloc(3 * (size_t)nt);
+    if (e == hipSuccess) e = c.pat.alloc(pat.size());
+    if (e == hipSuccess) e = c.pos.alloc((size_t)n);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(-100 - (int)e, "%s: the device cannot hold the %zu bytes of this call (%d directions, chunks of %d rows of %d): %s",
+                    who, bytes, ndir, c.c, npad, hipGetErrorString(e));
+    }
+    hipStream_t s = f->stream;
+    HIPCHK_AT(who, upload_canon(c.dirs, dirs, nd, s));
+    HIPCHK_AT(who, hipMemsetAsync(c.zero, 0, (size_t)npad * sizeof(double), s));
+    HIPCHK_AT(who, hipMemcpyAsync(c.itab, c.toff.data(), (size_t)nt * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK_AT(who, hipMemcpyAsync(c.itab + nt, c.toffb.data(), (size_t)nt * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK_AT(who, hipMemcpyAsync(c.itab + 2 * (size_t)nt, c.hib.data(), (size_t)nt * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK_AT(who, hipMemcpyAsync(c.pat, pat.data(), pat.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK_AT(who, hipMemcpyAsync(c.pos, f->taper_inv.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    struct PlainSchedule {              // the band schedule is a plain one: no resident engine while this call factors
+        cocons_fit *f; bool ok;
+        explicit PlainSchedule(cocons_fit *f_) : f(f_), ok(f_->engine_ok) { f->engine_ok = false; }
+        ~PlainSchedule() { f->engine_ok = ok; }
+    } plain(f);
+    const int st = run_op(f, who, [&]() -> int {
+        return fisher_taper_enqueue(f, theta, c, probes, hinfo.data(), mean ? hmean.data() : nullptr);
+    });
+    f->border_clean = -1; f->border_pending = -1;
+    if (st) return st;                  // failing minor: nothing written
+    memcpy(info, hinfo.data(), hinfo.size() * sizeof(double));
+    if (mean) memcpy(info_mean, hmean.data(), hmean.size() * sizeof(double));
+    return 0;
+}

@@ -977,4 +977,98 @@ void launch_taper_grad(int mode, const TaperGradArgs &g, hipStream_t s)
     hipLaunchKernelGGL(taper_grad_xt_kernel, dim3((2 * TG_FAM + 1) * g.p), blk, 0, s, g);
 }
 
+// ---------------------------------------------------------------------------
+// Expected information of a tapered fit (cocons_fisher_taper): the direction matrices on the pattern,
+//     S_a = T o sum_tk v_a[t, k] dC / dtheta[t, k],
+// from the three numbers per entry the gradient forms (C = P M, U = P u dM/du, E = P nu dM/dnu + U / 2) and the site weights
+// w_a[f][i] = sum_k X(i, k) v_a[f, k] (FULL scale vector: factor 1, k from 0).
+//   taper_dirs_weight_kernel : the weights of the four families that enter the taper model
+//   taper_dirs_entry_kernel  : one thread per stored (lower) entry, every direction from one evaluation of the pair
+__global__ void __launch_bounds__(256)
+taper_dirs_weight_kernel(TaperDirsArgs d)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, a = blockIdx.y;
+    if (i >= d.g.npad) return;
+    const int fam_row[TG_FAM] = {0, 1, 4, 5};      // std.dev, scale, smooth, nugget rows of the 6 x p table
+    const int p = d.g.p;
+    const double *v = d.dirs + (size_t)a * 6 * p;
+    for (int f = 0; f < TG_FAM; ++f) {
+        double s = 0.0;
+        if (i < d.g.n)
+            for (int k = 0; k < p; ++k) s = fma(d.g.X[(size_t)i + (size_t)k * d.g.ldx], v[fam_row[f] * p + k], s);
+        d.wsite[((size_t)a * TG_FAM + f) * d.g.npad + i] = s;
+    }
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256)
+taper_dirs_entry_kernel(TaperDirsArgs d)
+{
+    const double eps = 2.220446049250313e-16;
+    const TaperGradArgs &g = d.g;
+    const int w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= g.nnz) return;
+    int lo = 0, hi = g.n - 1;                 // largest ii with rp[ii] - 1 <= w (taper_grad_entry_kernel)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (g.rp[mid] - 1 <= w) lo = mid; else hi = mid - 1;
+    }
+    const int ii = lo, jj = g.ci[w] - 1;
+    const double *L = g.loc;
+    const size_t sl = g.stride, np = (size_t)g.npad, nz = (size_t)g.nnz;
+    const double t = g.tapv[w];
+    // value = t * (c_sd (w_sd,i + w_sd,j) + c_sci w_sc,i + c_scj w_sc,j + c_smi w_sm,i + c_smj w_sm,j + c_ng w_ng,i)
+    double c_sd = 0.0, c_sdj = 0.0, c_sci = 0.0, c_scj = 0.0, c_smi = 0.0, c_smj = 0.0, c_ng = 0.0;
+    bool own = ii == jj;
+    if (!own) {
+        double nu;
+        const double u = taper_u<MODE>(g, ii, jj, nu);
+        if (u <= eps) own = true;             // coincident: the row site's diagonal value
+        else if (!(u >= 706.0)) {             // (beyond: the reference's stand-in, derivatives round to 0)
+            double M, Mu, Mn = 0.0;
+            if (MODE == MODE_HALF) { M = exp(-u); Mu = -M; }
+            else if (MODE == MODE_THREEHALF) { const double e = exp(-u); M = (1.0 + u) * e; Mu = -u * e; }
+            else if (MODE == MODE_FIVEHALF) { const double e = exp(-u); M = (1.0 + u + u * u / 3.0) * e; Mu = -(u / 3.0) * (1.0 + u) * e; }
+            else {
+                matern_pair(nu, u, M, Mu);
+                if (g.smooth_free) Mn = matern_dnu(nu, u);
+            }
+            const double ri = L[2 * sl + ii], rj = L[2 * sl + jj];
+            const double P = (2 * sqrt(ri) * sqrt(rj)) / (ri + rj) * L[9 * sl + ii] * L[9 * sl + jj];
+            const double C = P * M, U = P * Mu * u;
+            const double phi_i = ri / (ri + rj), phi_j = rj / (ri + rj);
+            c_sd = 0.5 * C; c_sdj = 0.5 * C;
+            c_sci = C * (1.0 - 2.0 * phi_i) - U * phi_i;
+            c_scj = C * (1.0 - 2.0 * phi_j) - U * phi_j;
+            if (g.smooth_free) {
+                const double E = P * Mn * nu + 0.5 * U;
+                c_smi = E * g.site[2 * sl + ii];
+                c_smj = E * g.site[2 * sl + jj];
+            }
+        }
+    }
+    if (own) { c_sd = g.site[3 * sl + ii]; c_ng = L[12 * sl + ii]; }
+    for (int a = 0; a < d.ndir; ++a) {
+        const double *wa = d.wsite + (size_t)a * TG_FAM * np;
+        double v = c_sd * wa[TG_SD * np + ii] + c_sdj * wa[TG_SD * np + jj];
+        v += c_sci * wa[TG_SCALE * np + ii] + c_scj * wa[TG_SCALE * np + jj];
+        v += c_smi * wa[TG_SMOOTH * np + ii] + c_smj * wa[TG_SMOOTH * np + jj];
+        v += c_ng * wa[TG_NG * np + ii];
+        d.out[(size_t)a * nz + w] = t * v;
+    }
+}
+
+void launch_taper_dirs(int mode, const TaperDirsArgs &d, hipStream_t s)
+{
+    if (d.g.nnz <= 0 || d.g.n <= 0 || d.ndir <= 0) return;
+    hipLaunchKernelGGL(taper_dirs_weight_kernel, dim3((d.g.npad + 255) / 256, d.ndir), dim3(256), 0, s, d);
+    dim3 ge((d.g.nnz + 255) / 256), blk(256);
+    switch (mode) {
+    case MODE_HALF: hipLaunchKernelGGL(taper_dirs_entry_kernel<MODE_HALF>, ge, blk, 0, s, d); break;
+    case MODE_THREEHALF: hipLaunchKernelGGL(taper_dirs_entry_kernel<MODE_THREEHALF>, ge, blk, 0, s, d); break;
+    case MODE_FIVEHALF: hipLaunchKernelGGL(taper_dirs_entry_kernel<MODE_FIVEHALF>, ge, blk, 0, s, d); break;
+    default: hipLaunchKernelGGL(taper_dirs_entry_kernel<MODE_GEOM>, ge, blk, 0, s, d); break;
+    }
+}
+
 }  // namespace cocons

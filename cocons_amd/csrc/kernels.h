@@ -450,7 +450,62 @@ struct TaperGradArgs {
 };
 void launch_taper_grad(int mode, const TaperGradArgs &g, hipStream_t s);
 
-// ---- cross-validated predictions (cv.hip) ---------------------------------------------------------------------
+// ---- expected (Fisher) information of a tapered fit on the band factor (cocons_fisher_taper) -------------------
+// Direction entries (grad.hip): S_a = T o sum_tk v_a[t, k] dC/dtheta[t, k] on the device pattern (lower triangle, 1-based CSR),
+// out[a nnz + w] for the ndir directions (dirs: device, ndir x 6 p in theta's table layout); wsite: ndir x 4 x npad scratch
+// (the site weights of std.dev, scale, smooth, nugget).  The pair arithmetic is taper_grad_entry_kernel's.
+struct TaperDirsArgs {
+    TaperGradArgs g;               // n, npad, p, nnz, ci, rp, tapv, loc, stride, site, X, ldx, nu_fixed, smooth_free (the rest unused)
+    int ndir;
+    const double *dirs;
+    double *wsite, *out;
+};
+void launch_taper_dirs(int mode, const TaperDirsArgs &d, hipStream_t s);
+// Rows (probes, directions' vectors) live column-major with the row index fastest: rows x npad, ld a multiple of 64 -- the
+// layout of the kriging ring's slots, here at full width (tile column I in slot I).
+// back_pack: the operands of the BACKWARD solve W = E L^-1.  With F the flip of all npad indices, W F = (E F) (F L' F)^-T and
+// M = F L' F is lower triangular with L's envelope mirrored: the backward solve is the forward pair run on M with the rows'
+// columns flipped (column npad - 1 - c of the buffer holds column c).  Tile (I', J') of M, I' >= J', is the flipped transpose of
+// L's tile (nt - 1 - J', nt - 1 - I') and goes to tile index d_toffb[J'] + (I' - J') of Mp (d_hib: M's envelope; both device,
+// nt ints); Qb (nt x 2048) gets the operands of M's diagonal tiles.
+void launch_band_back_pack(const double *A, size_t lda, int skew, int npad, const int *d_hib, int nt, int W, const int *d_toffb,
+                           double *Mp, double *Qb, hipStream_t s);
+// V = C P^-T for the `rows` rows of a full-width buffer (rows a multiple of 64) on packed tiles P / operands Q as
+// launch_krige_band_pack or launch_band_back_pack leave them (toff, hi: HOST arrays of that factor); krige_band_diag_kernel and
+// krige_band_update_kernel with the identity ring, no loads.  zero: npad zeros; st, qd: `rows` doubles nobody reads.
+struct BandSweep {
+    const double *Lp = nullptr, *Qp = nullptr; const int *toff = nullptr, *hi = nullptr; int nt = 0;
+    double *C = nullptr; size_t ldc = 0; int rows = 0;
+    const double *zero = nullptr; double *st = nullptr, *qd = nullptr;
+};
+hipError_t launch_band_sweep(const BandSweep &a, hipStream_t s);
+inline hipError_t launch_band_back_solve(const BandSweep &a, hipStream_t s) { return launch_band_sweep(a, s); }   // (on back_pack's operands)
+// probe rows of a chunk into the flipped buffer E (rows x npad, zero beforehand): unit rows e_(g0 + k), k < count (exact mode) ...
+void launch_band_unit_rows(double *E, size_t lde, int npad, int g0, int count, hipStream_t s);
+// ... or the caller's probes: E[k, npad - 1 - pos[i]] = P[i + k n] for i < n, k < count (P: n x count, column-major)
+void launch_band_given_rows(double *E, size_t lde, int npad, const double *P, int n, const int *pos, int count, hipStream_t s);
+// rows [row0, row0 + 64) of U: X' (X: n x p column-major, p <= 64) in its first p rows, zero elsewhere and from column n on
+void launch_band_x_rows(double *U, size_t ldu, int row0, const double *X, int n, int p, int npad, hipStream_t s);
+// U_a[k, j] = sum_{i in row j of the FULL pattern} S_a[j, i] Wf[k, npad - 1 - i] for k < rows, every direction a at rows
+// a bstride + k of U (columns j >= n: zero).  frp / fci: the full symmetric pattern (0-based CSR), fidx: the index of
+// entry (max, min) in the lower-triangle order of Sd (ndir x nnz).  Sums in CSR index order.
+struct BandSpmm {
+    const double *Wf = nullptr; size_t ldw = 0; int rows = 0, n = 0, npad = 0, ndir = 0;
+    const int *frp = nullptr, *fci = nullptr, *fidx = nullptr; const double *Sd = nullptr; size_t nnz = 0;
+    double *U = nullptr; size_t ldu = 0, bstride = 0;
+};
+void launch_band_spmm_dirs(const BandSpmm &a, hipStream_t s);
+// Gram partial sums of solved rows: part[(strip0 + s) nd nd + a nd + b] = sum over the rows k < nrows (<= 64) of strip s and
+// all columns of Q[base + a bstride + 64 s + k, :] o Q[base + b bstride + 64 s + k, :] for a <= b < nd.  Fixed segments of
+// BAND_GRAM_SEG columns and a fixed tree inside the workgroup; seg: band_gram_scratch_doubles(nstrips, npad, nd) doubles.
+constexpr int BAND_GRAM_SEG = 1024;
+size_t band_gram_scratch_doubles(int nstrips, int npad, int nd);
+void launch_band_gram(const double *Q, size_t ld, size_t base, size_t bstride, int nrows, int nstrips, int npad, int nd,
+                      double *seg, double *part, int strip0, hipStream_t s);
+// out[a nd + b] = out[b nd + a] = weight * sum_{s < nstrips} part[s nd nd + a nd + b], in index order
+void launch_band_gram_sum(const double *part, int nstrips, int nd, double weight, double *out, hipStream_t s);
+
+// ---- cross-validated predictions (cv.hip)---------------------------------------------------------------------
 // S: -Sigma^-1 in the lower triangle (launch_grad_syrk), so K(i, j) = -S(max, min); U = Sigma^-1 R (npad x nr, ld ldu).  Results
 // go out in the handle's internal order: var[i], res[i + k ldr].  fail: one word, INT_MAX beforehand, atomicMin of the label of
 // a fold whose block has a pivot that is not positive and finite.

@@ -1,6 +1,7 @@
 // solve.hip -- the kernels that read a FINISHED factor (gfx950, fp64 MFMA): the reductions behind the likelihood and the
 // predictions (finalize, row_reduce), the draws Y = L E + trend (trmm_lower, band_trmm, gather_rows) and kriging from a held
-// factor, dense and band (krige_*, krige_band_*, krige_schur, sym_mirror).  No hand-offs, no mailboxes: nothing here changes
+// factor, dense and band (krige_*, krige_band_*, krige_schur, sym_mirror), and the band sweeps, sparse product and Gram sums of
+// the tapered fit's expected information (band_*).  No hand-offs, no mailboxes: nothing here changes
 // when a schedule of the factorisation (chol.hip) does.  Storage and the register "blk layout": chol.hip, tile_ops.hpp.
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -814,6 +815,253 @@ void launch_sym_mirror(double *S, size_t lds, int n, hipStream_t s)
     if (n <= 0) return;
     const unsigned t = (unsigned)((n + 63) / 64);
     hipLaunchKernelGGL(sym_mirror_kernel, dim3(t, t), dim3(256), 0, s, S, lds, n);
+}
+
+// ---------------------------------------------------------------------------
+// Expected information of a tapered fit on the band factor (cocons_fisher_taper).  Rows -- probes, then every
+// direction's vectors -- live in full-width buffers (rows x npad, column-major, the row index fastest): the kriging ring at
+// W = nt, tile column I in slot I.  Per chunk of probe rows E:
+//   back solve   W = E L^-1           the forward pair on the flipped transpose M = F L' F of the factor (band_back_pack),
+//                                     the rows' columns flipped: column npad - 1 - c of the buffer holds column c
+//   spmm         U_a = W S_a          band_spmm_dirs_kernel, every direction from one gather of W
+//   sweep        Q = U L^-T           the forward pair on the factor's own packed tiles (launch_band_sweep)
+//   gram         sum Q_a o Q_b        band_gram_kernel per 64-row strip and column segment, then fixed-order sums
+// No kernel here meets another row of a buffer, and every sum has one order: a row's contribution depends on its entries and its
+// position modulo 64 only.
+
+// grid (W, nt): tile (I' = J' + blockIdx.x, J' = blockIdx.y) of M = F L' F, element (r, c) = L's tile (nt - 1 - J', nt - 1 - I')
+// at (127 - c, 127 - r); the strict upper triangle of M's diagonal tiles zero
+__global__ void __launch_bounds__(256)
+band_back_pack_kernel(const double *A, size_t lda, int skew, int npad, const int *hib, int nt, const int *toffb, double *Mp)
+{
+    const int Jp = blockIdx.y, Ip = Jp + (int)blockIdx.x;
+    if (Ip >= hib[Jp]) return;
+    const int Lr = nt - 1 - Jp, Lc = nt - 1 - Ip;          // L's tile row and column
+    double *dst = Mp + (size_t)(toffb[Jp] + (Ip - Jp)) * TILE * TILE;
+    for (int e = threadIdx.x; e < TILE * TILE; e += 256) {
+        const int c = e & (TILE - 1), r = e >> 7;           // (source rows run fastest)
+        const double v = A[band_index(Lr * TILE + (TILE - 1 - c), Lc * TILE + (TILE - 1 - r), lda, skew, npad)];
+        dst[(size_t)r + (size_t)c * TILE] = (Ip == Jp && r < c) ? 0.0 : v;
+    }
+}
+
+// krige_band_qprep_kernel's arithmetic on the packed diagonal tiles of M (tile toffb[J'], ld 128)
+__global__ void __launch_bounds__(256)
+band_back_qprep_kernel(const double *Mp, const int *toffb, double *Qb)
+{
+    const int J = blockIdx.x, tid = threadIdx.x;
+    const double *D = Mp + (size_t)toffb[J] * TILE * TILE;
+    for (int e = tid; e < 8 * 256; e += 256) {
+        const int jb = e >> 8, s = (e >> 6) & 3, lane = e & 63;
+        const int m = lane & 15, k = lane >> 4, c = m & 3;
+        double q = 0.0;
+        if ((m >> 2) == s && k <= c) {
+            const int d0 = 16 * jb + 4 * s;                                                // the 4 x 4 diagonal sub-block
+            auto L = [&](int i, int j) { return D[(size_t)(d0 + i) + (size_t)(d0 + j) * TILE]; };
+            const double l10 = L(1, 0), l20 = L(2, 0), l30 = L(3, 0), l21 = L(2, 1), l31 = L(3, 1), l32 = L(3, 2);
+            const double r0 = 1.0 / L(0, 0), r1 = 1.0 / L(1, 1), r2 = 1.0 / L(2, 2), r3 = 1.0 / L(3, 3);
+            const double m00 = r0, m11 = r1, m22 = r2, m33 = r3;
+            const double m10 = -(l10 * m00) * r1;
+            const double m21 = -(l21 * m11) * r2;
+            const double m32 = -(l32 * m22) * r3;
+            const double m20 = -fma(l21, m10, l20 * m00) * r2;
+            const double m31 = -fma(l32, m21, l31 * m11) * r3;
+            const double m30 = -fma(l32, m20, fma(l31, m10, l30 * m00)) * r3;
+            q = sel_lower4(c, k, m00, m10, m11, m20, m21, m22, m30, m31, m32, m33);
+        }
+        Qb[(size_t)J * 2048 + e] = q;
+    }
+}
+
+void launch_band_back_pack(const double *A, size_t lda, int skew, int npad, const int *d_hib, int nt, int W, const int *d_toffb,
+                           double *Mp, double *Qb, hipStream_t s)
+{
+    if (nt <= 0 || W <= 0) return;
+    hipLaunchKernelGGL(band_back_pack_kernel, dim3((unsigned)W, (unsigned)nt), dim3(256), 0, s, A, lda, skew, npad, d_hib, nt,
+                       d_toffb, Mp);
+    hipLaunchKernelGGL(band_back_qprep_kernel, dim3(nt), dim3(256), 0, s, Mp, d_toffb, Qb);
+}
+
+hipError_t launch_band_sweep(const BandSweep &a, hipStream_t s)
+{
+    if (a.rows <= 0 || a.nt <= 0) return hipSuccess;
+    const unsigned strips = (unsigned)((a.rows + 63) / 64);
+    for (int J = 0; J < a.nt; ++J) {
+        const double *Lcol = a.Lp + (size_t)a.toff[J] * TILE * TILE;
+        hipLaunchKernelGGL(krige_band_diag_kernel, dim3(strips), dim3(256), 0, s, Lcol, a.Qp + (size_t)J * 2048, a.zero,
+                           a.C + (size_t)J * TILE * a.ldc, a.ldc, J == 0 ? 1 : 0, a.st, a.qd);
+        const int hj = a.hi ? a.hi[J] : a.nt;
+        if (hj - J - 1 > 0)
+            hipLaunchKernelGGL(krige_band_update_kernel, dim3(strips, (unsigned)(hj - J - 1)), dim3(256), 0, s, Lcol, a.C, a.ldc, J,
+                               a.nt);
+    }
+    return hipGetLastError();
+}
+
+__global__ void __launch_bounds__(256)
+band_unit_rows_kernel(double *E, size_t lde, int npad, int g0, int count)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k < count) E[(size_t)k + (size_t)(npad - 1 - (g0 + k)) * lde] = 1.0;
+}
+
+void launch_band_unit_rows(double *E, size_t lde, int npad, int g0, int count, hipStream_t s)
+{
+    if (count <= 0) return;
+    hipLaunchKernelGGL(band_unit_rows_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, E, lde, npad, g0, count);
+}
+
+__global__ void __launch_bounds__(256)
+band_given_rows_kernel(double *E, size_t lde, int npad, const double *P, int n, const int *pos)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
+    if (i < n) E[(size_t)k + (size_t)(npad - 1 - pos[i]) * lde] = P[(size_t)i + (size_t)k * n];
+}
+
+void launch_band_given_rows(double *E, size_t lde, int npad, const double *P, int n, const int *pos, int count, hipStream_t s)
+{
+    if (count <= 0 || n <= 0) return;
+    hipLaunchKernelGGL(band_given_rows_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)count), dim3(256), 0, s, E, lde, npad,
+                       P, n, pos);
+}
+
+__global__ void __launch_bounds__(256)
+band_x_rows_kernel(double *U, size_t ldu, int row0, const double *X, int n, int p, int npad)
+{
+    const int r = threadIdx.x & 63, j = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j < npad) U[(size_t)(row0 + r) + (size_t)j * ldu] = (r < p && j < n) ? X[(size_t)j + (size_t)r * n] : 0.0;
+}
+
+void launch_band_x_rows(double *U, size_t ldu, int row0, const double *X, int n, int p, int npad, hipStream_t s)
+{
+    hipLaunchKernelGGL(band_x_rows_kernel, dim3((unsigned)((npad + 3) / 4)), dim3(256), 0, s, U, ldu, row0, X, n, p, npad);
+}
+
+// One thread per (probe row k, site j): a wave shares j, so the pattern and the directions' entries are uniform loads and the
+// gather of W is one coalesced 512-byte row segment per entry, shared by the group's accumulators.
+constexpr int BAND_DG = 8;         // directions per register group (spmm) and per side of a group pair (gram)
+__global__ void __launch_bounds__(256)
+band_spmm_dirs_kernel(BandSpmm a)
+{
+    const int k = 64 * (int)blockIdx.y + (threadIdx.x & 63), j = 4 * (int)blockIdx.x + (threadIdx.x >> 6);
+    if (j >= a.npad) return;
+    const int t0 = j < a.n ? a.frp[j] : 0, t1 = j < a.n ? a.frp[j + 1] : 0;
+    for (int g0 = 0; g0 < a.ndir; g0 += BAND_DG) {
+        const int ng = a.ndir - g0 < BAND_DG ? a.ndir - g0 : BAND_DG;
+        double acc[BAND_DG];
+#pragma unroll
+        for (int x = 0; x < BAND_DG; ++x) acc[x] = 0.0;
+        for (int t = t0; t < t1; ++t) {
+            const double wv = a.Wf[(size_t)k + (size_t)(a.npad - 1 - a.fci[t]) * a.ldw];
+            const double *sd = a.Sd + (size_t)g0 * a.nnz + (size_t)a.fidx[t];
+#pragma unroll
+            for (int x = 0; x < BAND_DG; ++x)
+                if (x < ng) acc[x] = fma(sd[(size_t)x * a.nnz], wv, acc[x]);
+        }
+#pragma unroll
+        for (int x = 0; x < BAND_DG; ++x)
+            if (x < ng) a.U[(size_t)(g0 + x) * a.bstride + (size_t)k + (size_t)j * a.ldu] = acc[x];
+    }
+}
+
+void launch_band_spmm_dirs(const BandSpmm &a, hipStream_t s)
+{
+    if (a.rows <= 0 || a.npad <= 0 || a.ndir <= 0) return;
+    hipLaunchKernelGGL(band_spmm_dirs_kernel, dim3((unsigned)((a.npad + 3) / 4), (unsigned)((a.rows + 63) / 64)), dim3(256), 0, s, a);
+}
+
+// grid (strips, segments, group pairs ga <= gb): the thread of row k and column class tid / 64 runs over its columns of the
+// segment with BAND_DG x BAND_DG accumulators; then per accumulator a butterfly over the wave and the four waves in order
+__global__ void __launch_bounds__(256)
+band_gram_kernel(const double *Q, size_t ld, size_t base, size_t bstride, int nrows, int npad, int nd, int ngrp, double *seg)
+{
+    __shared__ double red[4][BAND_DG * BAND_DG];
+    int ga = 0, gb = (int)blockIdx.z;
+    while (gb >= ngrp - ga) { gb -= ngrp - ga; ++ga; }
+    gb += ga;
+    const int tid = threadIdx.x, k = tid & 63, wave = tid >> 6;
+    const int c0 = (int)blockIdx.y * BAND_GRAM_SEG, c1 = c0 + BAND_GRAM_SEG < npad ? c0 + BAND_GRAM_SEG : npad;
+    const int na = nd - ga * BAND_DG < BAND_DG ? nd - ga * BAND_DG : BAND_DG, nb = nd - gb * BAND_DG < BAND_DG ? nd - gb * BAND_DG : BAND_DG;
+    const double *qa = Q + base + (size_t)(ga * BAND_DG) * bstride + 64 * (size_t)blockIdx.x + k;
+    const double *qb = Q + base + (size_t)(gb * BAND_DG) * bstride + 64 * (size_t)blockIdx.x + k;
+    double acc[BAND_DG][BAND_DG];
+#pragma unroll
+    for (int x = 0; x < BAND_DG; ++x)
+#pragma unroll
+        for (int y = 0; y < BAND_DG; ++y) acc[x][y] = 0.0;
+    if (k < nrows)
+        for (int c = c0 + wave; c < c1; c += 4) {
+            double va[BAND_DG], vb[BAND_DG];
+#pragma unroll
+            for (int x = 0; x < BAND_DG; ++x) {
+                va[x] = x < na ? qa[(size_t)x * bstride + (size_t)c * ld] : 0.0;
+                vb[x] = x < nb ? qb[(size_t)x * bstride + (size_t)c * ld] : 0.0;
+            }
+#pragma unroll
+            for (int x = 0; x < BAND_DG; ++x)
+#pragma unroll
+                for (int y = 0; y < BAND_DG; ++y) acc[x][y] = fma(va[x], vb[y], acc[x][y]);
+        }
+#pragma unroll
+    for (int x = 0; x < BAND_DG; ++x)
+#pragma unroll
+        for (int y = 0; y < BAND_DG; ++y) {
+            double v = acc[x][y];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+            if (k == 0) red[wave][x * BAND_DG + y] = v;
+        }
+    __syncthreads();
+    if (tid < BAND_DG * BAND_DG) {
+        const int a = ga * BAND_DG + tid / BAND_DG, b = gb * BAND_DG + tid % BAND_DG;
+        if (a < nd && b < nd && a <= b)
+            seg[(((size_t)blockIdx.x * gridDim.y + blockIdx.y) * nd + a) * nd + b] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    }
+}
+
+// part[(strip0 + s) nd nd + e] = sum over the segments, in index order (entries a <= b; the others stay 0)
+__global__ void __launch_bounds__(256)
+band_gram_seg_kernel(const double *seg, int nseg, int nd, double *part, int strip0)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
+    if (e >= nd * nd) return;
+    double t = 0.0;
+    if (e / nd <= e % nd)
+        for (int g = 0; g < nseg; ++g) t += seg[((size_t)s * nseg + g) * nd * nd + e];
+    part[(size_t)(strip0 + s) * nd * nd + e] = t;
+}
+
+__global__ void __launch_bounds__(256)
+band_gram_sum_kernel(const double *part, int nstrips, int nd, double weight, double *out)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= nd * nd) return;
+    const int a = e / nd, b = e % nd;
+    if (a > b) return;
+    double t = 0.0;
+    for (int s = 0; s < nstrips; ++s) t += part[(size_t)s * nd * nd + e];
+    out[a * nd + b] = weight * t;
+    out[b * nd + a] = weight * t;
+}
+
+static inline int band_gram_segments(int npad) { return (npad + BAND_GRAM_SEG - 1) / BAND_GRAM_SEG; }
+size_t band_gram_scratch_doubles(int nstrips, int npad, int nd) { return (size_t)nstrips * band_gram_segments(npad) * nd * nd; }
+
+void launch_band_gram(const double *Q, size_t ld, size_t base, size_t bstride, int nrows, int nstrips, int npad, int nd,
+                      double *seg, double *part, int strip0, hipStream_t s)
+{
+    if (nstrips <= 0 || nd <= 0) return;
+    const int ngrp = (nd + BAND_DG - 1) / BAND_DG, nseg = band_gram_segments(npad);
+    hipLaunchKernelGGL(band_gram_kernel, dim3((unsigned)nstrips, (unsigned)nseg, (unsigned)(ngrp * (ngrp + 1) / 2)), dim3(256), 0, s,
+                       Q, ld, base, bstride, nrows, npad, nd, ngrp, seg);
+    hipLaunchKernelGGL(band_gram_seg_kernel, dim3((unsigned)((nd * nd + 255) / 256), (unsigned)nstrips), dim3(256), 0, s, seg, nseg,
+                       nd, part, strip0);
+}
+
+void launch_band_gram_sum(const double *part, int nstrips, int nd, double weight, double *out, hipStream_t s)
+{
+    if (nd <= 0) return;
+    hipLaunchKernelGGL(band_gram_sum_kernel, dim3((unsigned)((nd * nd + 255) / 256)), dim3(256), 0, s, part, nstrips, nd, weight, out);
 }
 
 }  // namespace cocons

@@ -105,6 +105,37 @@ GetNeg2loglikelihood <- function(theta, par.pos, locs, x_covariates, smooth.limi
   .cocons.hip.result(.Call(`_cocons_hip_fisher_reml`, fit, base[-1], J[-seq_len(p), , drop = FALSE]), safe)
 }
 
+# expected information of a tapered fit (type = "sparse") over theta (cocons_fisher_taper), P x P in theta's order, on the band
+# factor of one factorisation: (r / 2) tr(S^-1 S_a S^-1 S_b) with S = T o C(theta), a Gram matrix (symmetric, positive
+# semi-definite).  nprobe = 0: exact, O(P n^2 bandwidth); nprobe > 0: Hutchinson's estimate from that many random +-1 probes
+# over the n observations (set.seed() beforehand for a repeatable draw); the mean block is exact either way.  fit: a taper handle.  NULL after a
+# failing Cholesky under safe.  INTEGRATION.md has the details.
+.cocons.hip.fisher.taper <- function(fit, theta, par.pos, nprobe = 0L, n = NULL, max.rows = 0L, safe = TRUE) {
+  aspects <- c("std.dev", "scale", "aniso", "tilt", "smooth", "nugget")
+  base <- cocons::getModelLists(theta = theta, par.pos = par.pos, type = "diff")
+  p <- length(base$mean)
+  flat <- function(tl) c(tl$mean, unlist(tl[aspects], use.names = FALSE))
+  J <- vapply(seq_along(theta), function(a) {
+    e <- theta
+    e[a] <- e[a] + 1
+    flat(cocons::getModelLists(theta = e, par.pos = par.pos, type = "diff")) - flat(base)
+  }, numeric(7 * p))
+  Jm <- J[seq_len(p), , drop = FALSE]
+  Jt <- J[-seq_len(p), , drop = FALSE]
+  cov <- which(colSums(Jt != 0) > 0)
+  probes <- NULL
+  if (nprobe > 0) {
+    if (is.null(n)) stop("nprobe > 0 needs n, the number of observations of the fit")
+    probes <- matrix(sample(c(-1, 1), n * nprobe, replace = TRUE), n, nprobe)
+  }
+  res <- .cocons.hip.result(.Call(`_cocons_hip_fisher_taper`, fit, base[-1], Jt[, if (length(cov)) cov else 1L, drop = FALSE],
+                                  probes, as.integer(max.rows)), safe)
+  if (is.null(res)) return(NULL)
+  info <- crossprod(Jm, res[[2]] %*% Jm)
+  if (length(cov)) info[cov, cov] <- info[cov, cov] + res[[1]]
+  info
+}
+
 # cross-validated predictions at theta_list from ONE factorisation (cocons_cv_dense): every observation predicted from the
 # observations outside its fold.  fold: one label of any kind per observation (NULL: leave-one-out).  list(resid = z minus
 # its prediction, n x r; var = the predictive variance, nugget included); NULL after a failing Cholesky under safe.

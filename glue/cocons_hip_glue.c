@@ -439,6 +439,40 @@ SEXP _cocons_hip_fisher_reml(SEXP fitp, SEXP theta, SEXP dirs)
     return out;
 }
 
+/* expected information of a tapered fit on the band factor (cocons_fisher_taper): dirs as for _cocons_hip_fisher; probes NULL
+ * (exact: the n unit vectors) or an n x nprobe double matrix, one probe per column in the observations' order; max_rows the
+ * probe rows per chunk (0: the library's default); list(status, list(info ndir x ndir, info_mean p x p)) */
+SEXP _cocons_hip_fisher_taper(SEXP fitp, SEXP theta, SEXP dirs, SEXP probes, SEXP max_rows)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), n = fit_n(fitp);
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    if (!Rf_isReal(dirs) || !Rf_isMatrix(dirs) || Rf_nrows(dirs) != 6 * p)
+        Rf_error("dirs must be a double matrix with %d rows (one direction per column)", 6 * p);
+    const int nd = Rf_ncols(dirs);
+    int np = 0;
+    const double *pr = NULL;
+    if (!Rf_isNull(probes)) {
+        if (!Rf_isReal(probes) || !Rf_isMatrix(probes) || Rf_nrows(probes) != n || Rf_ncols(probes) < 1)
+            Rf_error("probes must be NULL or a double matrix with %d rows (one probe per column)", n);
+        np = Rf_ncols(probes);
+        pr = REAL(probes);
+    }
+    SEXP info = PROTECT(Rf_allocMatrix(REALSXP, nd, nd));
+    SEXP im = PROTECT(Rf_allocMatrix(REALSXP, p, p));
+    for (R_xlen_t e = 0; e < XLENGTH(info); ++e) REAL(info)[e] = 0.0;
+    for (R_xlen_t e = 0; e < XLENGTH(im); ++e) REAL(im)[e] = 0.0;
+    int rc = cocons_fisher_taper(f, T, nd, REAL(dirs), np, pr, Rf_asInteger(max_rows), REAL(info), REAL(im));   /* (both symmetric) */
+    hip_check(rc, "expected information (taper)");
+    SEXP res = PROTECT(Rf_allocVector(VECSXP, 2));
+    SET_VECTOR_ELT(res, 0, info);
+    SET_VECTOR_ELT(res, 1, im);
+    SEXP out = status_value(rc, res);
+    UNPROTECT(3);
+    return out;
+}
+
 /* cross-validated predictions (cocons_cv_dense / cocons_cv_taper): list(status, list(resid n x r, var n)).  fold: NULL
  * (leave-one-out) or n integer labels from 0; the labels' count is the largest label + 1 */
 static SEXP cv_call(SEXP fitp, SEXP theta, SEXP mean, SEXP fold, int taper)
@@ -934,6 +968,7 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_neg2loglik_grad", (DL_FUNC)&_cocons_hip_neg2loglik_grad, 3},
     {"_cocons_hip_fisher", (DL_FUNC)&_cocons_hip_fisher, 3},
     {"_cocons_hip_fisher_reml", (DL_FUNC)&_cocons_hip_fisher_reml, 3},
+    {"_cocons_hip_fisher_taper", (DL_FUNC)&_cocons_hip_fisher_taper, 5},
     {"_cocons_hip_cv", (DL_FUNC)&_cocons_hip_cv, 4},
     {"_cocons_hip_cv_taper", (DL_FUNC)&_cocons_hip_cv_taper, 3},
     {"_cocons_hip_neg2loglik_batch", (DL_FUNC)&_cocons_hip_neg2loglik_batch, 3},

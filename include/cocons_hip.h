@@ -312,6 +312,32 @@ int cocons_fisher_dense(cocons_fit *fit, const double *theta, int ndir, const do
  * cocons_neg2loglik_reml_grad makes it keep.                                                                              */
 int cocons_fisher_reml(cocons_fit *fit, const double *theta, int ndir, const double *dirs, double *info);
 
+/* Expected (Fisher) information of a tapered fit (a handle of cocons_fit_create_taper) at theta, exact or probed, on the band
+ * factor the handle's objective produces.  With S = T o C(theta) = L L' in place of Sigma,
+ *   info[a * ndir + b] = (r / 2) tr(S^-1 S_a S^-1 S_b),   S_a = T o sum_{t,k} dirs[a][t * p + k] dC / dtheta[t * p + k] (on the pattern),
+ *   info_mean[k * p + l] = r (X' S^-1 X)[k, l]   (may be NULL; exact in both modes),
+ * computed as the Gram matrix of the whitened rows e_k' L^-1 S_a L^-T over probe rows e_k:
+ *   nprobe = 0, probes = NULL   the n unit vectors, in chunks: exact.  Cost O(ndir n^2 bandwidth): meant for n up to ~10^4.
+ *   nprobe >= 1                 the caller's probes (n x nprobe, column-major; column k is probe k, its entry i belongs to the
+ *                               caller's observation i), used as given with the weight r / (2 nprobe): Hutchinson's estimator
+ *                               when E[e e'] = I (random +-1 entries), which is the caller's responsibility.
+ * Either way info is a Gram matrix: symmetric to the bit and positive semi-definite by construction; every sum has a fixed
+ * order, so the result is repeatable to the bit and does not depend on max_rows (probe rows per chunk, rounded as
+ * cocons_krige_taper_prepare rounds it; 0 = the largest multiple of 64 with (ndir + 1) rows n_pad doubles within 1 GiB, at
+ * most 16384) nor on the handle's buffer layout.  dirs as for cocons_fisher_dense (ndir tables of 6 x p), under the TAPER
+ * gradient's conventions: the full scale vector (rho_i = e^(2 eta_scale,i), no global range, factor 1), a coincident pair
+ * takes the diagonal value of the row site of the lower triangle, pairs the reference rounds to 0 contribute 0; the aniso and
+ * tilt rows do not enter the taper model, a direction with only those gives an exactly zero row and column.
+ * 0, the failing minor k > 0, or < 0 with a message that starts with the entry's name; outputs are written on 0 only.
+ * Refused (-1) before any device work: null fit, theta, dirs or info, ndir outside [1, 7 * COCONS_P_MAX], nprobe < 0,
+ * nprobe > 0 without probes or probes with nprobe = 0, max_rows < 0, non-finite entries of dirs or probes, a dense handle, a
+ * sharded handle, a handle without z.  Memory: two packed copies of the envelope's tiles, ndir values per stored entry and
+ * the chunk's (ndir + 1) rows n_pad doubles belong to the call and are released before it returns (a device that cannot
+ * hold them gives < 0 with the bytes needed in the message); the kriging and gradient states of the handle are neither read
+ * nor written. */
+int cocons_fisher_taper(cocons_fit *fit, const double *theta, int ndir, const double *dirs,
+                        int nprobe, const double *probes, int max_rows, double *info, double *info_mean);
+
 /* Cross-validated predictions at theta from one factorisation.  With K = Sigma^-1, U = K (z - X mean) and B a
  * held-out set of observations with complement A,
  *   z_B - E[z_B | z_A] = (K_BB)^-1 U_B,   Cov(z_B | z_A) = (K_BB)^-1:
