@@ -1,0 +1,204 @@
+"""tests/taper_envelope_cases.py (the cases and the restated envelope rule of tests/test_gpu_taper_envelopes.py) on the CPU:
+every case shows the shape it claims, the restated envelope holds the whole dense Cholesky factor in the order it was made
+for (and notices when it is one tile too tight), the inputs are conditioned like those the suite's tolerances were set at,
+the prediction sets hold the rows they promise, and the ring's load rule covers the case's (nt, W).  No GPU."""
+import functools
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import grad_taper_reference as GT  # noqa: E402
+import taper_envelope_cases as TE  # noqa: E402
+from krige_taper_reference import load_schedule  # noqa: E402
+
+COND_CAP = 1e5
+
+
+@functools.lru_cache(maxsize=None)
+def _matrix(name):
+    from cocons_amd.host import theta_table
+    p = TE.problem(name)
+    S, _ = GT.taper_matrix(theta_table(p.theta), p.locs, p.X, TE.SMOOTH_LIMITS, p.ref_taper)
+    S.setflags(write=False)
+    return S
+
+
+@functools.lru_cache(maxsize=None)
+def _envelope(name):
+    p = TE.problem(name)
+    order = TE.order_of(p)
+    return (order,) + TE.envelope_of(p.n, p.ref_taper[0], p.ref_taper[1], order)
+
+
+@functools.lru_cache(maxsize=None)
+def _factor(name):
+    """the dense factor of S in the handle's order, padded by the identity to whole tiles"""
+    p = TE.problem(name)
+    o = _envelope(name)[0] - 1
+    nt = (p.n + TE.TILE - 1) // TE.TILE
+    Sp = np.eye(nt * TE.TILE)
+    Sp[:p.n, :p.n] = _matrix(name)[np.ix_(o, o)]
+    return np.linalg.cholesky(Sp)
+
+
+def _tiles_outside(L, hi):
+    """tiles (I, J), I >= hi[J], of the lower factor that hold a non-zero"""
+    T = TE.TILE
+    return [(I, J) for J in range(len(hi)) for I in range(int(hi[J]), len(hi)) if np.any(L[I * T:(I + 1) * T, J * T:(J + 1) * T])]
+
+
+@pytest.mark.parametrize("name", TE.NAMES)
+def test_shape_conditioning_and_containment(name):
+    p = TE.problem(name)
+    order, nt, hi, W, packed = _envelope(name)
+    S = _matrix(name)
+    cond = float(np.linalg.cond(S))
+    print("%s: n %d nt %d W %d hi - c %s mirrored %s cond(S) %.3g"
+          % (name, p.n, nt, W, (hi - np.arange(nt)).tolist(), (TE.mirrored_envelope(hi) - np.arange(nt)).tolist(), cond))
+    TE.assert_shape(name, nt, hi, W, packed)
+    if not p.rcm:
+        assert np.array_equal(order, np.arange(1, p.n + 1))
+    else:
+        assert sorted(order.tolist()) == list(range(1, p.n + 1)) and not np.array_equal(order, np.arange(1, p.n + 1))
+    assert cond <= COND_CAP, cond
+    assert np.allclose(S, S.T, rtol=1e-14, atol=0) and np.all(np.isfinite(S))      # (the two orders of a product: last bit)
+    assert _tiles_outside(_factor(name), hi) == []
+    # the mirrored envelope holds the flipped factor in the same way
+    hib = TE.mirrored_envelope(hi)
+    assert np.sum(hib - np.arange(nt)) == np.sum(hi - np.arange(nt))          # the same tiles, seen from the other end
+    assert _tiles_outside(_factor(name)[::-1, ::-1].T, hib) == []
+
+
+def test_the_tables_that_are_pinned():
+    """clusters_caller: the exact envelope (a cluster of 300, one of 45 and one of 520 sites in this order, every one a
+    clique: tile rows 0 .. 2, 2 and 2 .. 6, then the scattered sites); the mirrored envelope of `clusters` is not the
+    envelope (the Fisher sweep's second table differs from its first); the stored zero of `lshape` sits where it should."""
+    _, nt, hi, W, _ = _envelope("clusters_caller")
+    assert hi.tolist() == [8, 8, 10, 10, 10, 10, 10, 10, 11, 11, 11] and W == 8
+    _, nt, hi, W, _ = _envelope("clusters")
+    assert not np.array_equal(TE.mirrored_envelope(hi), hi)
+    for name in ("chain", "hub_caller"):
+        hi = _envelope(name)[2]
+        assert np.array_equal(TE.mirrored_envelope(hi), hi)
+    p = TE.problem("lshape")
+    ci, rp, ent = p.ref_taper
+    row = 7 * 128 - 1                                   # (nt - 1) 128 - 1: the last row of tile row 6
+    assert ci[rp[row] - 1] == 1 and ent[rp[row] - 1] == 0.0 and ci[rp[0 + 1] - 2] == row + 1 and ent[rp[1] - 2] == 0.0
+    nt, raw = TE.raw_skyline(p.n, ci, rp, np.arange(1, p.n + 1))
+    assert raw[0] == 7
+    nt, raw = TE.raw_skyline(p.n, *TE.pattern(p.locs, p.delta)[:2], np.arange(1, p.n + 1))
+    assert np.all(raw - np.arange(nt) <= 3)                 # without the zero: a band of three tile rows
+    p = TE.problem("hub")
+    ci, rp, ent = p.ref_taper
+    near = int(np.sum(np.hypot(*(p.locs - p.locs[TE.HUB]).T) <= p.delta))
+    assert rp[TE.HUB + 1] - rp[TE.HUB] == p.n and np.sum(ent == 0.0) == 2 * (p.n - near) and 1 < near < 200
+    nt, raw = TE.raw_skyline(1153, *TE.problem("chain").ref_taper[:2], _envelope("chain")[0])
+    assert np.all(raw - np.arange(nt) <= 2)
+    nt, raw = TE.raw_skyline(577, *TE.problem("islands").ref_taper[:2], _envelope("islands")[0])
+    assert np.all(raw - np.arange(nt) == 1) and TE.problem("islands").ref_taper[0].size == 577
+
+
+@pytest.mark.parametrize("name", ["clusters", "clusters_caller", "hub_caller"])
+def test_containment_notices_an_envelope_one_tile_too_tight(name):
+    """Where the pattern (not the floor) decides a column and real entries fill it, a bound one tile lower lets the factor out."""
+    order, nt, hi, W, _ = _envelope(name)
+    p = TE.problem(name)
+    _, raw = TE.raw_skyline(p.n, p.ref_taper[0], p.ref_taper[1], order)
+    fl = TE.floor_envelope(nt)
+    decided = [c for c in range(nt) if raw[c] == hi[c] > fl[c]]
+    assert decided, (raw, hi, fl)
+    for c in decided:
+        tight = hi.copy()
+        tight[c] -= 1
+        out = _tiles_outside(_factor(name), tight)
+        assert out == [(int(hi[c]) - 1, c)], (c, out)
+
+
+@pytest.mark.parametrize("name", TE.NAMES)
+def test_prediction_sets(name):
+    p = TE.problem(name)
+    ci, rp, ent = p.pred_taper
+    dense, empty, on_top = p.special
+    assert p.lp.shape == (TE.M_PRED, 2) and rp.size == TE.M_PRED + 1 and rp[-1] == ci.size + 1
+    assert len({dense // 64, empty // 64, on_top // 64}) == 3
+    cnt = np.diff(rp)
+    assert cnt[empty] == 0
+    assert np.any(np.all(p.locs == p.lp[on_top], axis=1)) and 1.0 in ent[rp[on_top] - 1:rp[on_top + 1] - 1]
+    assert cnt[dense] >= (1 if name == "islands" else max(1, np.median(cnt)))      # next to the site with the most neighbours
+    for i in range(TE.M_PRED):
+        assert np.all(np.diff(ci[rp[i] - 1:rp[i + 1] - 1]) > 0)
+    if name.startswith("clusters"):
+        assert cnt[dense] >= 520                                # inside the largest cluster: all of it is in range
+        pos = np.empty(p.n, dtype=int)
+        pos[_envelope(name)[0] - 1] = np.arange(p.n)
+        tiles = np.unique(pos[ci[rp[dense] - 1:rp[dense + 1] - 1] - 1] // TE.TILE)
+        print("%s: the row inside the largest cluster has neighbours in tile columns %s" % (name, tiles.tolist()))
+        assert tiles.size >= 3
+    if name == "islands":
+        assert cnt.max() <= 3                                   # sites 0.032 apart at least, range 0.03
+
+
+@pytest.mark.parametrize("name", TE.NAMES)
+def test_patterns_are_what_the_library_accepts(name):
+    """1-based CSR, symmetric, diagonal stored with taper 1, columns ascending, entries in [0, 1]; stored zeros only where the
+    case has them"""
+    p = TE.problem(name)
+    ci, rp, ent = p.ref_taper
+    n = p.n
+    rows = np.repeat(np.arange(n), np.diff(rp))
+    A = np.full((n, n), -1.0)
+    A[rows, ci - 1] = ent
+    assert rp[0] == 1 and rp[-1] == ci.size + 1 and np.array_equal(A, A.T)
+    assert np.all(np.diag(A) == 1.0) and np.all(ent >= 0) and np.all(ent <= 1)
+    for i in range(n):
+        assert np.all(np.diff(ci[rp[i] - 1:rp[i + 1] - 1]) > 0)
+    zeros = int(np.sum(ent == 0.0))
+    assert (zeros > 0) == (name in ("hub", "hub_caller", "lshape")), zeros
+    if name == "islands":
+        assert ci.size == n
+
+
+@pytest.mark.parametrize("name", TE.NAMES)
+def test_ring_load_rule_at_the_cases_band(name):
+    """krige_taper_reference.load_schedule at the case's (nt, W): every tile column enters the ring once, into the slot the
+    tile column W places earlier has left, before the first step that updates it and within reach of it.  W = 6, 7 and 8 of
+    nt = 11, 8 and 11 do not divide nt: the ring wraps on a boundary of its own."""
+    _, nt, hi, W, packed = _envelope(name)
+    loads = load_schedule(nt, W)
+    assert sorted(I for _, I in loads) == list(range(nt))
+    at = dict((I, J) for J, I in loads)
+    for J, I in loads:
+        if J > 0:
+            assert I == J + W - 1 and I % W == (J - 1) % W
+    for J in range(nt):
+        for I in range(J + 1, int(hi[J])):
+            assert at[I] <= J and I <= J + W - 1
+    if name in ("clusters", "clusters_caller", "hub", "lshape"):
+        assert packed and nt % W != 0
+
+
+def test_theta_and_design_are_the_workloads():
+    from cocons_amd import workloads as wl
+    th = wl.theta_full(scale0=np.log(0.2))
+    mine = TE.theta_full()
+    assert list(mine) == list(th) and all(np.array_equal(mine[k], th[k]) for k in th if k != "mean")
+    assert TE.SMOOTH_LIMITS == wl.SMOOTH_LIMITS
+    locs = TE.problem("islands").locs
+    assert np.allclose(TE.design(locs), wl.design_from_locs(locs)["std.covs"], rtol=0, atol=1e-14)
+
+
+def test_restated_order_on_a_path_and_two_components():
+    """rcm_order by hand: a path 2 - 0 - 1 - 3 and an isolated vertex 4.  Components in (degree, index) order of their
+    least vertex: {4} first; the path starts at vertex 2 (degree 2 with its diagonal, the smaller index of the two ends), one
+    sweep ends in 3, the sweep from 3 gives 3 1 0 2; reversed: 2 0 1 3 4."""
+    edges = [(0, 1), (0, 2), (1, 3)]
+    stored = np.eye(5, dtype=bool)
+    for i, j in edges:
+        stored[i, j] = stored[j, i] = True
+    ci, rp, _ = TE._csr(stored, np.ones((5, 5)))
+    assert TE.rcm_order(5, ci, rp).tolist() == [3, 1, 2, 4, 5]
+    nt, hi, W, packed = TE.envelope_of(5, ci, rp, np.arange(1, 6))
+    assert (nt, hi.tolist(), W, packed) == (1, [1], 1, False)
