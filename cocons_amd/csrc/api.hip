@@ -151,7 +151,7 @@ int fit_alloc_matrix(cocons_fit *f, int rhs_rows)
 {
     int cap = rhs_rows_cap(rhs_rows);
     f->rhs_act = cap;        // a buffer grown by an earlier predict call must not slow later evaluations
-    f->border_clean = -1; f->border_pending = -1;      // every user of the rows under the matrix comes through here
+    border_unknown(f);      // every user of the rows under the matrix comes through here
     if (f->dA && cap <= f->rhs_cap) return 0;
     f->rhs_cap = cap;
     f->lda = (size_t)(f->skew > 0 ? f->skew * TILE : f->npad) + cap;
@@ -521,46 +521,18 @@ cocons_fit *taper_create_ordered(int n, int p, int r, const double *locs, const 
     cocons_fit *f = fit_create_impl(n, p, r, 0, pl.data(), pX.data(), pz.data(), nullptr, smooth_limits, device, false, true,
                                     true, true);       // (registered with its operation lock held: it is still being built)
     if (!f) return nullptr;
-    // envelope per tile column: row i of the factor is non-zero from its first stored column on
-    f->taper_hi.assign(f->nt, 0);
     f->taper_inv = inv;
     f->h_trp = prp;
     f->h_tci = pci;
     f->h_tval = pte;
-    {
-        std::vector<int> &hi = f->taper_hi;
-        for (int c = 0; c < f->nt; ++c) hi[c] = c + 1 < f->nt ? c + 1 : f->nt;
-        for (int i = 0; i < n; ++i) {
-            int first = i;
-            for (int w = prp[i] - 1; w < prp[i + 1] - 1; ++w) if (pci[w] - 1 < first) first = pci[w] - 1;
-            const int ti = i / TILE;
-            for (int c = first / TILE; c <= ti; ++c) if (hi[c] < ti + 1) hi[c] = ti + 1;
-        }
-        const char *e = getenv("COCONS_TAPER_BAND");
-        if (e && atoi(e) == 0) hi.clear();           // dense factorisation of the tapered matrix
-        if (!hi.empty()) {
-            // The schedule works on 256-column blocks and updates the square [t, hb) x [t, hb) with a block's panel:
-            // make the bound per block (both tile columns, at least the next diagonal block) and monotone, so that every
-            // tile an update touches lies inside the bound of its own column -- which is what gets zeroed.
-            std::vector<int> h2(f->nt);
-            int run = 0;
-            for (int c = 0; c < f->nt; ++c) {
-                const int k = c & ~1;
-                int hb = hi[k];
-                if (k + 1 < f->nt && hi[k + 1] > hb) hb = hi[k + 1];
-                const int need = k + 4 < f->nt ? k + 4 : f->nt;
-                if (hb < need) hb = need;
-                if (hb > f->nt) hb = f->nt;
-                if (hb > run) run = hb;
-                h2[c] = run;
-            }
-            hi = h2;
-            f->taper_maxband = 0;
-            for (int c = 0; c < f->nt; ++c) if (hi[c] - c > f->taper_maxband) f->taper_maxband = hi[c] - c;
-            // packed band storage unless switched off (COCONS_TAPER_PACKED=0: the dense n x n buffer, only its band used)
-            const char *pk = getenv("COCONS_TAPER_PACKED");
-            if (!(pk && atoi(pk) == 0) && f->taper_maxband < f->nt) f->skew = f->taper_maxband;
-        }
+    // the envelope per tile column (band_plan.hpp), unless switched off: dense factorisation of the tapered matrix
+    const char *e = getenv("COCONS_TAPER_BAND");
+    if (!(e && atoi(e) == 0)) {
+        BandEnvelope env = band_envelope(n, prp.data(), pci.data(), TILE);
+        f->taper_hi = std::move(env.hi); f->taper_maxband = env.maxband;
+        // packed band storage unless switched off (COCONS_TAPER_PACKED=0: the dense n x n buffer, only its band used)
+        const char *pk = getenv("COCONS_TAPER_PACKED");
+        if (!(pk && atoi(pk) == 0) && f->taper_maxband < f->nt) f->skew = f->taper_maxband;
     }
     if (check_fit) {
         const size_t bytes = ((size_t)(f->skew > 0 ? f->skew * TILE : f->npad) + (size_t)round_up(r + p, TILE)) *
@@ -589,8 +561,7 @@ cocons_fit *taper_create_ordered(int n, int p, int r, const double *locs, const 
         prp[n] = w2 + 1;
         nnz = w2;
     }
-    if (taper_pattern_to_device(f, nnz, pci.data(), prp.data(), pte.data(), f->taper_hi.empty() ? nullptr : f->taper_hi.data(),
-                                true) != 0) {
+    if (taper_pattern_to_device(f, nnz, pci.data(), prp.data(), pte.data(), envelope_or_null(f), true) != 0) {
         f->op_mu.unlock();
         cocons_fit_destroy(f);
         return nullptr;
@@ -726,7 +697,7 @@ FactorView main_view(cocons_fit *f)
 {
     FactorView v;
     v.A = f->dA; v.lda = f->lda; v.nt = f->nt; v.mt = f->nt + f->rhs_act / TILE;
-    v.hi = f->taper_hi.empty() ? nullptr : f->taper_hi.data();
+    v.hi = envelope_or_null(f);
     v.skew = f->skew;
     return v;
 }
@@ -2232,7 +2203,7 @@ extern "C" int cocons_debug_dag_replay(cocons_fit *f, const double *theta, const
     if (int prc = dag_prepare(f, fv)) return prc;
     if (f->dag_nsteps < 2) return fail(-1, "cocons_debug_dag_replay: problem too small for a DAG head");
     const int rc = dag_replay_run(f, fv, slots, theta, mean, reps, out);
-    f->border_clean = -1; f->border_pending = -1;        // (the buffer holds a half-done factorisation)
+    border_unknown(f);        // (the buffer holds a half-done factorisation)
     f->dag_used = false;
     return rc;
 }

@@ -161,12 +161,9 @@ extern "C" int cocons_cv_dense(cocons_fit *f, const double *theta, const double 
             const size_t counts[4] = {(2 * bpad + rt) * bpad, (size_t)plan.bmax * nr, (size_t)plan.bmax,
                                       row_reduce_scratch_doubles(plan.bmax, plan.bmax)};
             DevBuf<double> *bufs[4] = {&d.scratch, &d.tres, &d.tvar, &d.red};
-            for (int k = 0; k < 4; ++k)
-                if (hipError_t e = bufs[k]->alloc(counts[k])) {
-                    (void)hipGetLastError();
-                    return fail(-100 - (int)e, "%s: the device cannot hold the %zu bytes of the largest fold's matrix (%d observations): %s",
-                                who, (counts[0] + counts[1] + counts[2] + counts[3]) * sizeof(double), plan.bmax, hipGetErrorString(e));
-                }
+            if (hipError_t e = alloc_call_buffers(bufs, counts, 4))
+                return fail(-100 - (int)e, "%s: the device cannot hold the %zu bytes of the largest fold's matrix (%d observations): %s",
+                            who, (counts[0] + counts[1] + counts[2] + counts[3]) * sizeof(double), plan.bmax, hipGetErrorString(e));
         }
     }
     GradLayout layout(f, nr);
@@ -195,9 +192,7 @@ extern "C" int cocons_cv_taper(cocons_fit *f, const double *theta, const double 
     if (!f) return fail(-1, "%s: null fit handle", who);
     if (!theta || !mean || !resid || !var) return fail(-1, "%s: null argument", who);
     FIT_ENTER(f);
-    if (f->taper_nnz <= 0) return fail(-1, "%s: not a taper fit (cocons_cv_dense serves a dense handle)", who);
-    if (f->coll_kind) return fail(-1, "%s: not available on a sharded handle", who);
-    if (f->r < 1) return fail(-1, "%s: fit has no z", who);
+    if (int rc = taper_refuse(f, who, "cocons_cv_dense")) return rc;
     const int n = f->n, npad = f->npad, nr = f->r;
     if ((int)f->taper_inv.size() != n) return fail(-1, "%s: the handle keeps no order of its observations", who);
     if (int rc = taper_grad_prepare(f, who)) return rc;
@@ -221,7 +216,7 @@ extern "C" int cocons_cv_taper(cocons_fit *f, const double *theta, const double 
         HIPCHK(hipGetLastError());
         return 0;
     });
-    f->border_clean = -1; f->border_pending = -1;
+    border_unknown(f);
     if (st) return st;                  // failing minor: nothing written
     if (hfail != INFO_CLEAN) {
         int obs = -1;

@@ -28,18 +28,26 @@ static int grad_refuse(cocons_fit *f, const char *who)
     return 0;
 }
 
-// the site factors beside loc_params_kernel's SoA (launch_grad_site) and everything the pair partials read, into g (the rest
-// of it zero); the pair mode
+// The pair parameters of theta as every derivative reads them: the site factors beside loc_params_kernel's SoA go to `site`
+// (launch_grad_site, on the handle's stream); returns the pair mode with its fixed values, and whether the smoothness is free.
+// full_scale: the taper model's FULL scale vector (assemble_sigma_taper).
+static std::pair<ModeSel, int> grad_site_params(cocons_fit *f, const double *theta, bool full_scale, double *site)
+{
+    ThetaVecs tv;
+    make_theta_vecs(theta, f->p, tv, full_scale);
+    const ModeSel ms = select_mode(theta, f->p, f->smooth_limits, 0);
+    const int smooth_free = ms.smooth_kind == SMOOTH_LOGISTIC_SQRT && f->smooth_limits[1] != f->smooth_limits[0];
+    launch_grad_site(loc_args(f->n, f->p, f->dX, f->dlocs, site, f->npad, tv, ms.smooth_kind, f->smooth_limits), site, f->npad,
+                     smooth_free, f->stream);
+    return {ms, smooth_free};
+}
+
+// everything the dense pair partials read, into g (the rest of it zero); the pair mode
 static int grad_pair_args(cocons_fit *f, const double *theta, GradArgs &g)
 {
     const int npad = f->npad, p = f->p;
     GradState *G = f->grad.get();
-    ThetaVecs tv;
-    make_theta_vecs(theta, p, tv);
-    const ModeSel ms = select_mode(theta, p, f->smooth_limits, 0);
-    const int smooth_free = ms.smooth_kind == SMOOTH_LOGISTIC_SQRT && f->smooth_limits[1] != f->smooth_limits[0];
-    launch_grad_site(loc_args(f->n, p, f->dX, f->dlocs, G->site, npad, tv, ms.smooth_kind, f->smooth_limits), G->site, npad,
-                     smooth_free, f->stream);
+    const auto [ms, smooth_free] = grad_site_params(f, theta, false, G->site);
     memset(&g, 0, sizeof g);
     g.n = f->n; g.pad0 = f->pad0; g.npad = npad; g.p = p;
     g.S = f->dA; g.lds = f->lda;
@@ -164,7 +172,7 @@ int grad_prepare(cocons_fit *f, const char *who, int nb, int pcols)
     HIPCHK_AT(who, f->dA.reserve(need, f->stream, f->stream2, 0, false, &grew));
     if (grew) {
         HIPCHK_AT(who, hipStreamSynchronize(f->stream));
-        f->border_clean = -1; f->border_pending = -1;
+        border_unknown(f);
     }
     return 0;
 }
@@ -308,20 +316,33 @@ static int fisher_enqueue(cocons_fit *f, const double *theta, FisherCall &c, dou
     return 0;
 }
 
+// the checks of the arguments that every information entry makes, in two parts: the pointers and the number of directions
+// before the handle is entered, the directions' entries (ndir x 6 p, all finite) behind the handle's own checks
+static int fisher_check_args(const char *who, const cocons_fit *f, const double *theta, int ndir, const double *dirs, const double *info)
+{
+    if (!f) return fail(-1, "%s: null fit handle", who);
+    if (!theta || !dirs || !info) return fail(-1, "%s: null argument", who);
+    return ndir < 1 || ndir > 7 * COCONS_P_MAX ? fail(-1, "%s: ndir = %d is outside [1, %d]", who, ndir, 7 * COCONS_P_MAX) : 0;
+}
+
+static int fisher_check_dirs(const char *who, int ndir, const double *dirs, int p)
+{
+    for (size_t e = 0; e < (size_t)ndir * 6 * p; ++e)
+        if (!std::isfinite(dirs[e])) return fail(-1, "%s: direction %d has a non-finite entry", who, (int)(e / ((size_t)6 * p)));
+    return 0;
+}
+
 // both entries; reml: the border is [Z' ; X' ; I] and info_mean is null
 static int fisher_entry(cocons_fit *f, const char *who, const double *theta, int ndir, const double *dirs, double *info,
                         double *info_mean, bool reml)
 {
-    if (!f) return fail(-1, "%s: null fit handle", who);
-    if (!theta || !dirs || !info) return fail(-1, "%s: null argument", who);
-    if (ndir < 1 || ndir > 7 * COCONS_P_MAX) return fail(-1, "%s: ndir = %d is outside [1, %d]", who, ndir, 7 * COCONS_P_MAX);
+    if (int rc = fisher_check_args(who, f, theta, ndir, dirs, info)) return rc;
     FIT_ENTER(f);
     if (int rc = grad_refuse(f, who)) return rc;
     if (f->r < 1) return fail(-1, "%s: fit has no z", who);
     const int npad = f->npad, p = f->p, nb = reml ? f->r + p : f->r;
     const size_t nd = (size_t)ndir * 6 * p;
-    for (size_t e = 0; e < nd; ++e)
-        if (!std::isfinite(dirs[e])) return fail(-1, "%s: direction %d has a non-finite entry", who, (int)(e / ((size_t)6 * p)));
+    if (int rc = fisher_check_dirs(who, ndir, dirs, p)) return rc;
     FisherCall c;
     c.ndir = ndir;
     c.ldt = (size_t)(ndir + 2) * npad;
@@ -338,14 +359,9 @@ static int fisher_entry(cocons_fit *f, const char *who, const double *theta, int
     for (size_t k : counts) bytes += k * sizeof(double);
     std::vector<double> hinfo((size_t)ndir * ndir), hmean((size_t)p * p);
     StreamDrain drain{f->stream, false};       // (declared behind the buffers: the stream is idle before they are freed)
-    for (int k = 0; k < 7; ++k) {
-        if (!counts[k]) continue;
-        if (hipError_t e = bufs[k]->alloc(counts[k])) {
-            (void)hipGetLastError();
-            return fail(-100 - (int)e, "%s: the device cannot hold the %zu bytes of this call (%d + 2 matrices of order %d): %s",
-                        who, bytes, ndir, npad, hipGetErrorString(e));
-        }
-    }
+    if (hipError_t e = alloc_call_buffers(bufs, counts, 7))
+        return fail(-100 - (int)e, "%s: the device cannot hold the %zu bytes of this call (%d + 2 matrices of order %d): %s",
+                    who, bytes, ndir, npad, hipGetErrorString(e));
     HIPCHK_AT(who, upload_canon(c.dirs, dirs, nd, f->stream));
     GradLayout layout(f, nb);
     const int st = run_op(f, who, [&]() -> int { return fisher_enqueue(f, theta, c, hinfo.data(), mean ? hmean.data() : nullptr); });
@@ -497,15 +513,10 @@ int taper_grad_enqueue(cocons_fit *f, const double *theta, const double *mean, d
     sa.L = f->dA; sa.ldl = f->lda; sa.Z = G->Z; sa.ldz = G->ldz;
     sa.skew = f->skew; sa.npad = npad; sa.nt = f->nt;
     sa.d_hi = f->d_thi; sa.nr = nr; sa.AR = G->AR;
-    launch_selinv(sa, f->taper_hi.empty() ? nullptr : f->taper_hi.data(), f->taper_hi.empty() ? f->nt : f->taper_maxband, s);
+    launch_selinv(sa, envelope_or_null(f), band_W(f), s);
     HIPCHK(hipGetLastError());
     if (!hgrad) return 0;
-    ThetaVecs tv;
-    make_theta_vecs(theta, p, tv, true);
-    const ModeSel ms = select_mode(theta, p, f->smooth_limits, 0);
-    const int smooth_free = ms.smooth_kind == SMOOTH_LOGISTIC_SQRT && f->smooth_limits[1] != f->smooth_limits[0];
-    launch_grad_site(loc_args(f->n, p, f->dX, f->dlocs, G->site, npad, tv, ms.smooth_kind, f->smooth_limits), G->site, npad,
-                     smooth_free, s);
+    const auto [ms, smooth_free] = grad_site_params(f, theta, true, G->site);
     TaperGradArgs g;
     memset(&g, 0, sizeof g);
     g.n = f->n; g.npad = npad; g.p = p; g.nnz = f->taper_nnz; g.nr = nr;
@@ -522,9 +533,10 @@ int taper_grad_enqueue(cocons_fit *f, const double *theta, const double *mean, d
     return 0;
 }
 
-static int taper_grad_refuse(cocons_fit *f, const char *who)
+// what every entry of the tapered fit beside the objective asks of its handle; dense_entry: who serves a dense handle instead
+int taper_refuse(cocons_fit *f, const char *who, const char *dense_entry)
 {
-    if (f->taper_nnz <= 0) return fail(-1, "%s: not a taper fit (cocons_neg2loglik_grad_dense serves a dense handle)", who);
+    if (f->taper_nnz <= 0) return fail(-1, "%s: not a taper fit (%s serves a dense handle)", who, dense_entry);
     if (f->coll_kind) return fail(-1, "%s: not available on a sharded handle", who);
     if (f->r < 1) return fail(-1, "%s: fit has no z", who);
     return 0;
@@ -537,12 +549,12 @@ extern "C" int cocons_neg2loglik_grad_taper(cocons_fit *f, const double *theta, 
     if (!f) return fail(-1, "%s: null fit handle", who);
     if (!theta || !mean || !sum_logliks || !grad_theta || !grad_mean) return fail(-1, "%s: null argument", who);
     FIT_ENTER(f);
-    if (int rc = taper_grad_refuse(f, who)) return rc;
+    if (int rc = taper_refuse(f, who, "cocons_neg2loglik_grad_dense")) return rc;
     if (int rc = taper_grad_prepare(f, who)) return rc;
     const int p = f->p;
     std::vector<double> hg((size_t)9 * p);
     const int st = run_op(f, who, [&]() -> int { return taper_grad_enqueue(f, theta, mean, hg.data()); });
-    f->border_clean = -1; f->border_pending = -1;
+    border_unknown(f);
     if (st) return st;                  // failing minor: nothing written
     dense_collect(f, sum_logliks, parts);
     // device rows: part (log-determinant, quadratic form) x family (std.dev, scale, smooth, nugget); aniso and tilt do not
@@ -568,11 +580,11 @@ extern "C" int cocons_debug_taper_selinv(cocons_fit *f, const double *theta, dou
     if (!f) return fail(-1, "%s: null fit handle", who);
     if (!theta || !out_nnz) return fail(-1, "%s: null argument", who);
     FIT_ENTER(f);
-    if (int rc = taper_grad_refuse(f, who)) return rc;
+    if (int rc = taper_refuse(f, who, "cocons_neg2loglik_grad_dense")) return rc;
     if (int rc = taper_grad_prepare(f, who)) return rc;
     const std::vector<double> zero((size_t)f->p, 0.0);
     const int st = run_op(f, who, [&]() -> int { return taper_grad_enqueue(f, theta, zero.data(), nullptr); });
-    f->border_clean = -1; f->border_pending = -1;
+    border_unknown(f);
     if (st) return st;
     // the caller's entry w of row o is the entry at the same place of row taper_inv[o] of the handle's pattern
     const int n = f->n;
@@ -611,10 +623,10 @@ static constexpr int FISHER_TAPER_ROWS_CAP = 16384;
 
 struct FisherTaperCall {
     DevBuf<double> Lp, Qp, Mp, Qb, E, U, Sd, wsite, site, dirs, zero, st, qd, seg, part, partm, out;
-    DevBuf<int> itab, pat, pos;        // itab: toff | toffb | hib (nt each); pat: frp (n + 1) | fci | fidx (full nnz each)
-    std::vector<int> toff, toffb, hi, hib;
+    DevBuf<int> itab, pat, pos;        // itab: the plan's toff | toffb | hib (nt each); pat: frp (n + 1) | fci | fidx (full nnz each)
+    BandPlan plan;                     // the envelope, its mirror and the packed tiles' offsets of both (band_plan.hpp)
     size_t fnnz = 0;
-    int ndir = 0, nprobe = 0, c = 0, total = 0, W = 0;
+    int ndir = 0, nprobe = 0, c = 0, total = 0;
 };
 
 static int fisher_taper_enqueue(cocons_fit *f, const double *theta, FisherTaperCall &c, const double *probes, double *hinfo,
@@ -626,20 +638,13 @@ static int fisher_taper_enqueue(cocons_fit *f, const double *theta, FisherTaperC
     // 1. the factor
     f->nrhs_cur = f->r;
     if (int rc = fit_alloc_matrix(f, f->r)) return rc;
-    if (int rc = assemble_sigma_taper(f, theta)) return rc;
-    assemble_rhs(f, zero.data(), true, nullptr, 0, 0, npad, true, false);
-    FactorView v = main_view(f);
-    if (!v.hi) v.hi = c.hi.data();      // no envelope: the band schedule with hi[c] = nt (cocons_krige_taper_prepare's rule)
-    if (int rc = factorize(f, v, nullptr)) return rc;
+    if (int rc = factor_on_band_schedule(f, theta, c.plan, [&] { assemble_rhs(f, zero.data(), true, nullptr, 0, 0, npad, true, false); }))
+        return rc;
     const int *d_toff = c.itab, *d_toffb = c.itab + nt, *d_hib = c.itab + 2 * (size_t)nt;
-    launch_krige_band_pack(f->dA, f->lda, f->skew, npad, n, f->d_thi, nt, c.W, d_toff, c.Lp, c.Qp, c.st /* w: nobody reads it */, s);
-    launch_band_back_pack(f->dA, f->lda, f->skew, npad, d_hib, nt, c.W, d_toffb, c.Mp, c.Qb, s);
+    launch_krige_band_pack(f->dA, f->lda, f->skew, npad, n, f->d_thi, nt, c.plan.W, d_toff, c.Lp, c.Qp, c.st /* w: nobody reads it */, s);
+    launch_band_back_pack(f->dA, f->lda, f->skew, npad, d_hib, nt, c.plan.W, d_toffb, c.Mp, c.Qb, s);
     // 2. the directions' entries
-    ThetaVecs tv;
-    make_theta_vecs(theta, p, tv, true);
-    const ModeSel ms = select_mode(theta, p, f->smooth_limits, 0);
-    const int smooth_free = ms.smooth_kind == SMOOTH_LOGISTIC_SQRT && f->smooth_limits[1] != f->smooth_limits[0];
-    launch_grad_site(loc_args(n, p, f->dX, f->dlocs, c.site, npad, tv, ms.smooth_kind, f->smooth_limits), c.site, npad, smooth_free, s);
+    const auto [ms, smooth_free] = grad_site_params(f, theta, true, c.site);
     TaperDirsArgs d;
     memset(&d, 0, sizeof d);
     d.g.n = n; d.g.npad = npad; d.g.p = p; d.g.nnz = f->taper_nnz;
@@ -664,7 +669,7 @@ static int fisher_taper_enqueue(cocons_fit *f, const double *theta, FisherTaperC
             launch_band_given_rows(c.E, (size_t)c.c, npad, c.U, n, c.pos, cc, s);
         } else launch_band_unit_rows(c.E, (size_t)c.c, npad, g0, cc, s);
         BandSweep b;
-        b.Lp = c.Mp; b.Qp = c.Qb; b.toff = c.toffb.data(); b.hi = c.hib.data(); b.nt = nt;
+        b.Lp = c.Mp; b.Qp = c.Qb; b.toff = c.plan.toffb.data(); b.hi = c.plan.hib.data(); b.nt = nt;
         b.C = c.E; b.ldc = (size_t)c.c; b.rows = cs; b.zero = c.zero; b.st = c.st; b.qd = c.qd;
         HIPCHK(launch_band_back_solve(b, s));
         BandSpmm m;
@@ -675,7 +680,7 @@ static int fisher_taper_enqueue(cocons_fit *f, const double *theta, FisherTaperC
         const int urows = ndir * cs + (first && hmean ? 64 : 0);
         if (first && hmean) launch_band_x_rows(c.U, ldu, ndir * cs, f->dX, n, p, npad, s);
         BandSweep q;
-        q.Lp = c.Lp; q.Qp = c.Qp; q.toff = c.toff.data(); q.hi = c.hi.data(); q.nt = nt;
+        q.Lp = c.Lp; q.Qp = c.Qp; q.toff = c.plan.toff.data(); q.hi = c.plan.hi.data(); q.nt = nt;
         q.C = c.U; q.ldc = ldu; q.rows = urows; q.zero = c.zero; q.st = c.st; q.qd = c.qd;
         HIPCHK(launch_band_sweep(q, s));
         launch_band_gram(c.U, ldu, 0, (size_t)cs, 64, nstrips, npad, ndir, c.seg, c.part, strip0, s);
@@ -698,21 +703,16 @@ extern "C" int cocons_fisher_taper(cocons_fit *f, const double *theta, int ndir,
                                    const double *probes, int max_rows, double *info, double *info_mean)
 {
     const char *who = "cocons_fisher_taper";
-    if (!f) return fail(-1, "%s: null fit handle", who);
-    if (!theta || !dirs || !info) return fail(-1, "%s: null argument", who);
-    if (ndir < 1 || ndir > 7 * COCONS_P_MAX) return fail(-1, "%s: ndir = %d is outside [1, %d]", who, ndir, 7 * COCONS_P_MAX);
+    if (int rc = fisher_check_args(who, f, theta, ndir, dirs, info)) return rc;
     if (nprobe < 0) return fail(-1, "%s: nprobe = %d is negative", who, nprobe);
     if (nprobe > 0 && !probes) return fail(-1, "%s: nprobe = %d without probes", who, nprobe);
     if (nprobe == 0 && probes) return fail(-1, "%s: probes given with nprobe = 0 (exact mode takes none)", who);
     if (max_rows < 0) return fail(-1, "%s: max_rows = %d is negative", who, max_rows);
     FIT_ENTER(f);
-    if (f->taper_nnz <= 0) return fail(-1, "%s: not a taper fit (cocons_fisher_dense serves a dense handle)", who);
-    if (f->coll_kind) return fail(-1, "%s: not available on a sharded handle", who);
-    if (f->r < 1) return fail(-1, "%s: fit has no z", who);
+    if (int rc = taper_refuse(f, who, "cocons_fisher_dense")) return rc;
     const int npad = f->npad, n = f->n, p = f->p, nt = f->nt;
     const size_t nd = (size_t)ndir * 6 * p;
-    for (size_t e = 0; e < nd; ++e)
-        if (!std::isfinite(dirs[e])) return fail(-1, "%s: direction %d has a non-finite entry", who, (int)(e / ((size_t)6 * p)));
+    if (int rc = fisher_check_dirs(who, ndir, dirs, p)) return rc;
     for (size_t e = 0; e < (size_t)nprobe * n; ++e)
         if (!std::isfinite(probes[e])) return fail(-1, "%s: probe %d has a non-finite entry", who, (int)(e / (size_t)n));
     FisherTaperCall c;
@@ -723,22 +723,7 @@ extern "C" int cocons_fisher_taper(cocons_fit *f, const double *theta, int ndir,
         if (max_rows > 0) rows = std::min<size_t>(rows, std::max<size_t>((size_t)max_rows / 64 * 64, 64));
         c.c = (int)std::min<size_t>(rows, (size_t)round_up(c.total, 64));
     }
-    // the envelope, its mirror (of M = F L' F: hib[J'] = nt - the first tile column that reaches tile row nt - 1 - J') and the
-    // packed tiles' offsets of both
-    c.hi = f->taper_hi.empty() ? std::vector<int>((size_t)nt, nt) : f->taper_hi;
-    c.W = f->taper_hi.empty() ? nt : f->taper_maxband;
-    c.hib.assign((size_t)nt, 0); c.toff.assign((size_t)nt + 1, 0); c.toffb.assign((size_t)nt + 1, 0);
-    for (int J = nt - 1, lo = nt - 1; J >= 0; --J) {
-        if (lo > J) lo = J;
-        while (lo > 0 && c.hi[lo - 1] > J) --lo;
-        c.hib[nt - 1 - J] = nt - lo;
-    }
-    for (int J = 0; J < nt; ++J) {
-        const long long a = (long long)c.toff[J] + (c.hi[J] - J), b = (long long)c.toffb[J] + (c.hib[J] - J);
-        if (a > INT_MAX || b > INT_MAX) return fail(-1, "%s: the envelope holds too many tiles", who);
-        c.toff[J + 1] = (int)a; c.toffb[J + 1] = (int)b;
-    }
-    if (c.toffb[nt] != c.toff[nt]) return fail(-1, "%s: the envelope is not monotone", who);
+    if (const char *why = band_plan(nt, envelope_or_null(f), f->taper_maxband, c.plan)) return fail(-1, "%s: %s", who, why);
     // the full symmetric pattern in the handle's order (0-based) and, per entry, the index of (max, min) among the lower
     // entries as the device pattern numbers them (row by row)
     const std::vector<int> &rp = f->h_trp, &ci = f->h_tci;
@@ -771,7 +756,7 @@ extern "C" int cocons_fisher_taper(cocons_fit *f, const double *theta, int ndir,
                 fidx[t] = fidx[u];
             }
     }
-    const size_t ntile = (size_t)c.toff[nt], ldu = (size_t)ndir * c.c + 64, nnz = (size_t)f->taper_nnz;
+    const size_t ntile = (size_t)c.plan.toff[nt], ldu = (size_t)ndir * c.c + 64, nnz = (size_t)f->taper_nnz;
     const int total_strips = (c.total / c.c) * (c.c / 64) + (round_up(c.total % c.c, 64)) / 64;
     const bool mean = info_mean != nullptr;
     const size_t counts[17] = {ntile * TILE * TILE, (size_t)nt * 2048, ntile * TILE * TILE, (size_t)nt * 2048, (size_t)c.c * npad, ldu * npad,
@@ -785,8 +770,7 @@ extern "C" int cocons_fisher_taper(cocons_fit *f, const double *theta, int ndir,
     for (size_t k : counts) bytes += k * sizeof(double);
     std::vector<double> hinfo((size_t)ndir * ndir), hmean((size_t)p * p);
     StreamDrain drain{f->stream, false};       // (declared behind the buffers: the stream is idle before they are freed)
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 17 && e == hipSuccess; ++k) e = bufs[k]->alloc(counts[k]);
+    hipError_t e = alloc_call_buffers(bufs, counts, 17);
     if (e == hipSuccess) e = c.itab.alloc(3 * (size_t)nt);
     if (e == hipSuccess) e = c.pat.alloc(pat.size());
     if (e == hipSuccess) e = c.pos.alloc((size_t)n);
@@ -798,20 +782,15 @@ extern "C" int cocons_fisher_taper(cocons_fit *f, const double *theta, int ndir,
     hipStream_t s = f->stream;
     HIPCHK_AT(who, upload_canon(c.dirs, dirs, nd, s));
     HIPCHK_AT(who, hipMemsetAsync(c.zero, 0, (size_t)npad * sizeof(double), s));
-    HIPCHK_AT(who, hipMemcpyAsync(c.itab, c.toff.data(), (size_t)nt * sizeof(int), hipMemcpyHostToDevice, s));
-    HIPCHK_AT(who, hipMemcpyAsync(c.itab + nt, c.toffb.data(), (size_t)nt * sizeof(int), hipMemcpyHostToDevice, s));
-    HIPCHK_AT(who, hipMemcpyAsync(c.itab + 2 * (size_t)nt, c.hib.data(), (size_t)nt * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK_AT(who, hipMemcpyAsync(c.itab, c.plan.toff.data(), (size_t)nt * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK_AT(who, hipMemcpyAsync(c.itab + nt, c.plan.toffb.data(), (size_t)nt * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK_AT(who, hipMemcpyAsync(c.itab + 2 * (size_t)nt, c.plan.hib.data(), (size_t)nt * sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK_AT(who, hipMemcpyAsync(c.pat, pat.data(), pat.size() * sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK_AT(who, hipMemcpyAsync(c.pos, f->taper_inv.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
-    struct PlainSchedule {              // the band schedule is a plain one: no resident engine while this call factors
-        cocons_fit *f; bool ok;
-        explicit PlainSchedule(cocons_fit *f_) : f(f_), ok(f_->engine_ok) { f->engine_ok = false; }
-        ~PlainSchedule() { f->engine_ok = ok; }
-    } plain(f);
     const int st = run_op(f, who, [&]() -> int {
         return fisher_taper_enqueue(f, theta, c, probes, hinfo.data(), mean ? hmean.data() : nullptr);
     });
-    f->border_clean = -1; f->border_pending = -1;
+    border_unknown(f);
     if (st) return st;                  // failing minor: nothing written
     memcpy(info, hinfo.data(), hinfo.size() * sizeof(double));
     if (mean) memcpy(info_mean, hmean.data(), hmean.size() * sizeof(double));

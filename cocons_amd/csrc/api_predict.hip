@@ -289,12 +289,9 @@ extern "C" int cocons_krige_joint(cocons_fit *f, int m, const double *locs_pred,
         DevBuf<double> *bufs[12] = {&dV, &dS, &dXp, &dlp, &dlu, &dlocp, &dlocu, &dst, &dq, &dE, &dY, &dmu};
         size_t total = 0;
         for (int k = 0; k < 12; ++k) total += counts[k];
-        for (int k = 0; k < 12; ++k)
-            if (hipError_t e = bufs[k]->alloc(counts[k])) {
-                (void)hipGetLastError();
-                return fail(-100 - (int)e, "%s: the device cannot hold the %zu bytes of the call (m = %d new locations, n = %d): %s",
-                            who, total * sizeof(double), m, f->n_user, hipGetErrorString(e));
-            }
+        if (hipError_t e = alloc_call_buffers(bufs, counts, 12))      // (none of the counts is zero)
+            return fail(-100 - (int)e, "%s: the device cannot hold the %zu bytes of the call (m = %d new locations, n = %d): %s",
+                        who, total * sizeof(double), m, f->n_user, hipGetErrorString(e));
     }
     // rows >= m, the padding columns and the slot columns of V are never written by the assembly
     HIPCHK_AT(who, hipMemsetAsync(dV, 0, ldv * npad * sizeof(double), s));
@@ -444,11 +441,9 @@ static int krige_taper_handle(cocons_fit *f, const char *who)
     return krige_sharded(f, who);
 }
 
-static int krige_taper_W(const cocons_fit *f) { return f->taper_hi.empty() ? f->nt : f->taper_maxband; }
-
 static size_t krige_taper_row_bytes(const cocons_fit *f)
 {
-    return ((size_t)krige_taper_W(f) * TILE + (size_t)f->p + 2 + LOCP_FIELDS + 2) * sizeof(double);   // ring, Xp, lp, locp, st, qd
+    return ((size_t)band_W(f) * TILE + (size_t)f->p + 2 + LOCP_FIELDS + 2) * sizeof(double);   // ring, Xp, lp, locp, st, qd
 }
 
 // the CSR staging holds at least `entries` entries; a new allocation only when it has to grow (the stream is idle then)
@@ -472,25 +467,19 @@ extern "C" int cocons_krige_taper_prepare(cocons_fit *f, const double *theta, co
     if (int rc = krige_taper_handle(f, who)) return rc;
     if (!theta || !mean || z_col < 0 || z_col >= f->r || max_rows < 0) return fail(-1, "%s: bad argument", who);
     f->krige_taper.reset();             // replaced -- and gone if this prepare fails
-    const int p = f->p, n = f->n, npad = f->npad, nt = f->nt, W = krige_taper_W(f);
+    const int p = f->p, n = f->n, npad = f->npad, nt = f->nt;
     std::unique_ptr<KrigeTaperState> K(new KrigeTaperState());
     {
         size_t r = max_rows > 0 ? std::min<size_t>((size_t)max_rows, KRIGE_TAPER_ROWS_MAX)
                                 : std::min<size_t>(KRIGE_CHUNK_BYTES / krige_taper_row_bytes(f), KRIGE_ROWS_CAP);
         K->rows = (int)std::max<size_t>(r / 64 * 64, 64);      // whole 64-row strips, as krige_rows
     }
-    K->W = W;
     K->theta.resize((size_t)6 * p);
     for (int i = 0; i < 6 * p; ++i) K->theta[i] = canon_nan(theta[i]);
     K->mean.resize((size_t)p);
     for (int i = 0; i < p; ++i) K->mean[i] = canon_nan(mean[i]);
-    K->toff.assign((size_t)nt + 1, 0);
-    for (int c = 0; c < nt; ++c) {
-        const long long next = (long long)K->toff[c] + ((f->taper_hi.empty() ? nt : f->taper_hi[c]) - c);
-        if (next > INT_MAX) return fail(-1, "%s: the envelope holds too many tiles", who);
-        K->toff[c + 1] = (int)next;
-    }
-    const size_t R = (size_t)K->rows, ntile = (size_t)K->toff[nt];
+    if (const char *why = band_plan(nt, envelope_or_null(f), f->taper_maxband, K->plan)) return fail(-1, "%s: %s", who, why);
+    const size_t R = (size_t)K->rows, ntile = (size_t)K->plan.toff[nt];
     // the staging starts at the densest row of the handle's own pattern for every row of a chunk
     size_t dens = 1;
     for (int i = 0; i < n; ++i) dens = std::max<size_t>(dens, (size_t)(f->h_trp[i + 1] - f->h_trp[i]));
@@ -499,7 +488,7 @@ extern "C" int cocons_krige_taper_prepare(cocons_fit *f, const double *theta, co
     HIPCHK_AT(who, K->Q.alloc((size_t)nt * 2048));
     HIPCHK_AT(who, K->w.alloc((size_t)npad));
     HIPCHK_AT(who, K->loc.alloc((size_t)LOCP_FIELDS * npad));
-    HIPCHK_AT(who, K->ring.alloc(R * W * TILE));
+    HIPCHK_AT(who, K->ring.alloc(R * K->plan.W * TILE));
     HIPCHK_AT(who, K->Xp.alloc(R * p));
     HIPCHK_AT(who, K->lp.alloc(R * 2));
     HIPCHK_AT(who, K->locp.alloc(R * LOCP_FIELDS));
@@ -510,26 +499,15 @@ extern "C" int cocons_krige_taper_prepare(cocons_fit *f, const double *theta, co
     if (int rc = krige_taper_stage(K.get(), R * dens, who)) return rc;
     K->fixed_bytes = (long long)((ntile * TILE * TILE + (size_t)nt * 2048 + (size_t)npad * (1 + LOCP_FIELDS)) * sizeof(double) +
                                  R * krige_taper_row_bytes(f) + ((size_t)nt + R + 1) * sizeof(int));
-    HIPCHK_AT(who, hipMemcpyAsync(K->d_toff, K->toff.data(), (size_t)nt * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK_AT(who, hipMemcpyAsync(K->d_toff, K->plan.toff.data(), (size_t)nt * sizeof(int), hipMemcpyHostToDevice, s));
     const double *th = K->theta.data();
     if (int rc = fit_alloc_matrix(f, 1)) return rc;
-    const std::vector<int> full_hi((size_t)nt, nt);
-    struct PlainSchedule {              // the band schedule is a plain one: no resident engine while this prepare factors
-        cocons_fit *f; bool ok;
-        explicit PlainSchedule(cocons_fit *f_) : f(f_), ok(f_->engine_ok) { f->engine_ok = false; }
-        ~PlainSchedule() { f->engine_ok = ok; }
-    } plain(f);
     const int st = run_op(f, who, [&]() -> int {
         f->nrhs_cur = 1;
-        if (int rc = assemble_sigma_taper(f, th)) return rc;
-        residual_row(f, mean, z_col, f->dA, f->lda, npad, f->rhs_act - 1, npad);
-        // the band schedule, which leaves the factor whole in dA.  A handle without an envelope (COCONS_TAPER_BAND=0) takes it
-        // too, with hi[c] = nt: the same operations on every tile of the true band as under an envelope -- the tiles outside
-        // it only ever receive products with exact zeros -- so every layout prepares the same bits
-        FactorView v = main_view(f);
-        if (!v.hi) v.hi = full_hi.data();
-        if (int rc = factorize(f, v, nullptr)) return rc;
-        launch_krige_band_pack(f->dA, f->lda, f->skew, npad, n, f->d_thi, nt, W, K->d_toff, K->L, K->Q, K->w, s);
+        if (int rc = factor_on_band_schedule(f, th, K->plan, [&] {
+                residual_row(f, mean, z_col, f->dA, f->lda, npad, f->rhs_act - 1, npad);
+            })) return rc;
+        launch_krige_band_pack(f->dA, f->lda, f->skew, npad, n, f->d_thi, nt, K->plan.W, K->d_toff, K->L, K->Q, K->w, s);
         return 0;
     });
     if (st) return st;                  // failing minor: no state
@@ -558,7 +536,7 @@ extern "C" int cocons_krige_taper_apply(cocons_fit *f, int m, const double *locs
     KrigeTaperState *K = f->krige_taper.get();
     if (!K) return fail(-1, "%s: no kriging state on this handle (call cocons_krige_taper_prepare first)", who);
     if (m == 0) return 0;
-    const int p = f->p, n = f->n, nt = f->nt, rows = K->rows, W = K->W;
+    const int p = f->p, n = f->n, nt = f->nt, rows = K->rows, W = K->plan.W;
     // the whole pattern is checked before any device work: 1-based CSR, columns strictly increasing within a row
     if (rowpointers_pred[0] != 1 || rowpointers_pred[m] != nnz_pred + 1)
         return fail(-1, "%s: rowpointers do not match nnz (1-based CSR expected)", who);
@@ -618,7 +596,7 @@ extern "C" int cocons_krige_taper_apply(cocons_fit *f, int m, const double *locs
         t.out = K->val;
         launch_taper(t, s);
         KrigeBandSolve a;
-        a.Lp = K->L; a.Qp = K->Q; a.w = K->w; a.toff = K->toff.data(); a.hi = f->taper_hi.empty() ? nullptr : f->taper_hi.data();
+        a.Lp = K->L; a.Qp = K->Q; a.w = K->w; a.toff = K->plan.toff.data(); a.hi = envelope_or_null(f);
         a.nt = nt; a.W = W; a.ring = K->ring; a.ldr = (size_t)rows; a.rows = mc;
         a.boff = boff.data(); a.bdst = K->bdst; a.bsrc = K->bsrc; a.val = K->val; a.tapv = K->tv;
         a.stoch = K->st; a.quad = K->qd;
@@ -652,7 +630,7 @@ extern "C" int cocons_krige_taper_info(cocons_fit *f, long long *out6)
     out6[1] = K ? K->bytes() : 0;
     out6[2] = K ? K->rows : 0;
     out6[3] = f->n;
-    out6[4] = krige_taper_W(f);
+    out6[4] = band_W(f);
     out6[5] = f->nt;
     return 0;
 }

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "band_plan.hpp"       // the envelope rule and the packed layout of a band factor (host only)
 #include "../../include/cocons_hip_diag.h"
 #include "matern_device.hpp"   // PairMode, LOCP_FIELDS (host-visible enums)
 
@@ -166,23 +167,23 @@ struct KrigeState {
 // per tile column and a ring of W tile columns for the chunk.  Owned by the state like KrigeState's buffers: no other entry
 // point reads or writes it.
 struct KrigeTaperState {
-    DevBuf<double> L;             // the envelope's lower tiles: tile (I, J) at toff[J] + (I - J) (kernels.h launch_krige_band_pack)
+    DevBuf<double> L;             // the envelope's lower tiles: tile (I, J) at plan.toff[J] + (I - J) (kernels.h launch_krige_band_pack)
     DevBuf<double> Q;             // nt x 2048
     DevBuf<double> w;             // npad: L^-1 (z[:, z_col] - X mean), zero in the padding
     DevBuf<double> loc;           // LOCP_FIELDS x npad: observation-side SoA in the prediction branch's parameters
-    DevBuf<double> ring;          // rows x W * 128: tile column I of the chunk's right-hand side in slot I mod W
+    DevBuf<double> ring;          // rows x plan.W * 128: tile column I of the chunk's right-hand side in slot I mod W
     DevBuf<double> Xp, lp, locp;  // the chunk's X_pred (rows x p), locations (rows x 2) and SoA (LOCP_FIELDS x rows)
     DevBuf<double> st, qd;        // rows: the chunk's outputs
-    DevBuf<int> d_toff;           // nt: device copy of toff
+    DevBuf<int> d_toff;           // nt: device copy of plan.toff
     // CSR staging of a chunk, ecap entries (grown to the densest chunk seen): mapped columns, the caller's taper values, the
     // entries' covariance values, the buckets (destination in the slot, entry index), and the chunk's row pointers
     DevBuf<int> ci, rp, bdst, bsrc;
     DevBuf<double> tv, val;
     size_t ecap = 0;
-    std::vector<int> toff;        // nt + 1: first packed tile of every tile column
+    BandPlan plan;                // first packed tile of every tile column, slots of the ring (band_plan.hpp)
     std::vector<double> theta;    // 6 p: the prepared theta (canonicalised)
     std::vector<double> mean;     // p
-    int rows = 0, W = 0;          // rows per chunk (a multiple of 64), slots of the ring
+    int rows = 0;                 // rows per chunk (a multiple of 64)
     long long fixed_bytes = 0;    // device bytes of everything but the CSR staging
     long long bytes() const { return fixed_bytes + (long long)(ecap * (3 * sizeof(int) + 2 * sizeof(double))); }
 };
@@ -467,6 +468,22 @@ int fit_check(cocons_fit *f);
     if (int rc__ = fit_check(f)) return rc__;                          \
     std::lock_guard<std::recursive_mutex> op_guard__((f)->op_mu)
 
+// nothing under the matrix can be relied on: whoever wrote rows there that the objective does not know of says so
+inline void border_unknown(cocons_fit *f) { f->border_clean = -1; f->border_pending = -1; }
+
+// a taper handle's envelope as the launchers take it (null: none, they branch on it), and the tile rows a tile column reaches
+inline const int *envelope_or_null(const cocons_fit *f) { return f->taper_hi.empty() ? nullptr : f->taper_hi.data(); }
+inline int band_W(const cocons_fit *f) { return f->taper_hi.empty() ? f->nt : f->taper_maxband; }
+
+// Allocate the k buffers of one call (a count of zero: none) or say which allocation failed first -- the sticky error is
+// cleared, the caller reports how many bytes its call needs.
+inline hipError_t alloc_call_buffers(DevBuf<double> *const *bufs, const size_t *counts, int k)
+{
+    for (int i = 0; i < k; ++i)
+        if (hipError_t e = counts[i] ? bufs[i]->alloc(counts[i]) : hipSuccess) { (void)hipGetLastError(); return e; }
+    return hipSuccess;
+}
+
 // the matrix a factorisation runs on: column tiles nt, row tiles mt (>= nt: rows under the square)
 struct FactorView {
     double *A;
@@ -601,6 +618,7 @@ void rccl_comm_destroy(ncclComm_t c);
 size_t grad_lda(const cocons_fit *f, int nb);
 int grad_prepare(cocons_fit *f, const char *who, int nb, int pcols = 0);
 int grad_enqueue(cocons_fit *f, const double *theta, const double *mean, bool full, double *hgrad);
+int taper_refuse(cocons_fit *f, const char *who, const char *dense_entry);
 int taper_grad_prepare(cocons_fit *f, const char *who);
 int taper_grad_enqueue(cocons_fit *f, const double *theta, const double *mean, double *hgrad);
 
@@ -614,12 +632,12 @@ struct GradLayout {
     {
         f->lda = grad_lda(f, nb);
         f->rhs_act = (int)(f->lda - (size_t)f->npad);
-        f->border_clean = -1; f->border_pending = -1;
+        border_unknown(f);
     }
     ~GradLayout()
     {
         f->lda = lda; f->rhs_act = rhs_act;
-        f->border_clean = -1; f->border_pending = -1;
+        border_unknown(f);
     }
 };
 
@@ -637,6 +655,30 @@ template <class F> int run_op(cocons_fit *f, const char *who, F &&enqueue)
         const int st = info_status(f);
         if (!engine_retry(f, st)) return st;
     }
+}
+
+// the band schedule is a plain one: no resident engine while one of these is alive
+struct PlainSchedule {
+    cocons_fit *f; bool ok;
+    explicit PlainSchedule(cocons_fit *f_) : f(f_), ok(f_->engine_ok) { f->engine_ok = false; }
+    ~PlainSchedule() { f->engine_ok = ok; }
+};
+
+// S(theta) of a taper handle assembled, border_rows() -- the caller's rows under the matrix --, and the factorisation on the
+// band schedule, which leaves the factor whole in dA for the pack launches that follow (cocons_krige_taper_prepare,
+// cocons_fisher_taper).  A handle without an envelope (COCONS_TAPER_BAND=0) takes that schedule too, with the plan's
+// hi[c] = nt: the same operations on every tile of the true band as under an envelope -- the tiles outside it only ever
+// receive products with exact zeros -- so every layout prepares the same bits.
+// (Not for the selected inverse -- taper_grad_enqueue, i.e. the tapered gradient and cocons_cv_taper --: that path factors
+// main_view(f) as the objective does, on whatever schedule the handle has, and must stay so.)
+template <class F> int factor_on_band_schedule(cocons_fit *f, const double *theta, const BandPlan &pl, F &&border_rows)
+{
+    PlainSchedule plain(f);
+    if (int rc = assemble_sigma_taper(f, theta)) return rc;
+    border_rows();
+    FactorView v = main_view(f);
+    v.hi = pl.hi.data();                // (the handle's own envelope where it has one)
+    return factorize(f, v, nullptr);
 }
 
 constexpr double LOG_2PI = 1.8378770664093454835606594728112;

@@ -1,9 +1,12 @@
 """tests/taper_envelope_cases.py (the cases and the restated envelope rule of tests/test_gpu_taper_envelopes.py) on the CPU:
 every case shows the shape it claims, the restated envelope holds the whole dense Cholesky factor in the order it was made
 for (and notices when it is one tile too tight), the inputs are conditioned like those the suite's tolerances were set at,
-the prediction sets hold the rows they promise, and the ring's load rule covers the case's (nt, W).  No GPU."""
+the prediction sets hold the rows they promise, and the ring's load rule covers the case's (nt, W); and the library's own
+envelope rule and packed band layout (cocons_amd/csrc/band_plan.hpp, compiled into tests/band_plan_main.cpp by the host
+compiler) agree with the restatement integer for integer.  No GPU."""
 import functools
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -202,3 +205,77 @@ def test_restated_order_on_a_path_and_two_components():
     assert TE.rcm_order(5, ci, rp).tolist() == [3, 1, 2, 4, 5]
     nt, hi, W, packed = TE.envelope_of(5, ci, rp, np.arange(1, 6))
     assert (nt, hi.tolist(), W, packed) == (1, [1], 1, False)
+
+
+# --------------------------------------------------------------------------- the library's rule itself (band_plan.hpp)
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def band_plan_exe(tmp_path_factory):
+    """tests/band_plan_main.cpp over cocons_amd/csrc/band_plan.hpp, by the host compiler alone (a missing compiler fails)"""
+    exe = str(tmp_path_factory.mktemp("band_plan") / "band_plan_main")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "cocons_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "band_plan_main.cpp"), "-o", exe])
+    return exe
+
+
+def _run_band_plan(exe, path, text):
+    with open(path, "w") as fh:
+        fh.write(text)
+    out = {}
+    for line in subprocess.check_output([exe, str(path)]).decode().splitlines():
+        name, *vals = line.split()
+        out[name] = [int(v) for v in vals]
+    return out
+
+
+def _pattern_in_order(p, order):
+    """the case's full pattern as the handle keeps it: position i holds observation order[i], columns mapped likewise (within
+    a row in the caller's sequence, as the library leaves them)"""
+    ci, rp, _ = p.ref_taper
+    o = np.asarray(order) - 1
+    pos = np.empty(p.n, dtype=np.int64)
+    pos[o] = np.arange(p.n)
+    cnt = np.diff(rp)[o]
+    prp = np.concatenate([[1], 1 + np.cumsum(cnt)])
+    pci = np.concatenate([pos[ci[rp[r] - 1:rp[r + 1] - 1] - 1] + 1 for r in o])
+    return prp, pci
+
+
+def _prefix(reach):
+    return np.concatenate([[0], np.cumsum(reach)]).tolist()
+
+
+PINNED = {"clusters": ([5, 5, 6, 6, 10, 10, 10, 10, 11, 11, 11], [3, 7, 7, 7, 7, 9, 11, 11, 11, 11, 11]),
+          "hub_caller": ([8] * 8, [8] * 8)}
+
+
+@pytest.mark.parametrize("name", TE.NAMES)
+def test_library_rule_is_the_restated_rule(name, band_plan_exe, tmp_path):
+    p = TE.problem(name)
+    order, nt, hi, W, _ = _envelope(name)
+    prp, pci = _pattern_in_order(p, order)
+    got = _run_band_plan(band_plan_exe, tmp_path / "pattern.txt",
+                         "%d\n%s\n%s\n" % (p.n, " ".join(map(str, prp.tolist())), " ".join(map(str, pci.tolist()))))
+    hib = TE.mirrored_envelope(hi)
+    cols = np.arange(nt)
+    print("%s: hi %s hib %s" % (name, got["hi"], got["hib"]))
+    assert got["status"] == [0]
+    assert got["nt"] == [nt] and got["maxband"] == [W] and got["W"] == [W]
+    assert got["envelope"] == hi.tolist() and got["hi"] == hi.tolist()
+    assert got["hib"] == hib.tolist()
+    assert got["toff"] == _prefix(hi - cols) and got["toffb"] == _prefix(hib - cols)
+    assert len(got["toff"]) == nt + 1 and got["toff"][nt] == got["toffb"][nt]
+    if name in PINNED:
+        assert (got["hi"], got["hib"]) == PINNED[name]
+
+
+def test_library_plan_without_an_envelope(band_plan_exe, tmp_path):
+    """a handle without an envelope (COCONS_TAPER_BAND=0) on the tile columns of `clusters`: every column reaches the last
+    tile row, the ring holds all of them"""
+    nt = _envelope("clusters")[1]
+    got = _run_band_plan(band_plan_exe, tmp_path / "none.txt", "0 %d\n" % nt)
+    assert got["status"] == [0] and got["nt"] == [nt] and got["W"] == [nt] and got["envelope"] == []
+    assert got["hi"] == [nt] * nt and got["hib"] == [nt] * nt
+    assert got["toff"] == _prefix(nt - np.arange(nt)) and got["toffb"] == got["toff"]
