@@ -1,6 +1,6 @@
-// fit.hpp -- internal to the C ABI's translation units (api.hip, api_shard.hip, api_predict.hip, api_grad.hip, api_cv.hip): error reporting,
-// the owned device buffer, the fit handle with the states it owns, and the declarations of what api.hip -- the path of one
-// objective evaluation, the handle's life, the schedules -- offers the other three.  Not installed, not part of the contract
+// fit.hpp -- internal to the C ABI's translation units (api*.hip): error reporting, the owned device buffer, the fit handle
+// with the states it owns, and the declarations of what api.hip -- the path of one objective evaluation, the schedules -- and
+// api_handle.hip -- the handle's life -- offer the others.  Not installed, not part of the contract
 // (include/cocons_hip.h is).  Everything declared here is hidden from the library's dynamic symbol table; a variable or a
 // function-local static lives in exactly one .hip file, never here.
 #pragma once
@@ -372,7 +372,7 @@ struct cocons_fit {
     std::unique_ptr<TaperGradState> tgrad;   // taper fit: state of cocons_neg2loglik_grad_taper (allocated on first use)
 };
 
-// ---- one map per region of device words (every offset in ONE place; the abort dump -- api.hip debug_abort_report, decoded by
+// ---- one map per region of device words (every offset in ONE place; the abort dump -- api_diag.hip debug_abort_report, decoded by
 // tools/dag_abort.py --, cocons_debug_dag_words and the tests read these indices) ------------------------------------------
 // The hand-off words of a factorisation (dflags, zeroed by flags_reset): in[t], out[t], xr[t] (see EngineLaunch), flags_cap
 // words each; then 64 words -- the engine's alive word, at + 8 the two words of the stream self-test, at + 16 the
@@ -587,12 +587,6 @@ struct Tunables {
 Tunables &tun();
 bool engine_enabled();
 int fit_alloc_matrix(cocons_fit *f, int rhs_rows);
-cocons_fit *fit_create_impl(int n, int p, int r, int q, const double *locs, const double *X, const double *z, const double *x_betas,
-                            const double *smooth_limits, int device, bool allow_sort, bool defer_matrix = false,
-                            bool want_engine = true, bool return_locked = false);
-cocons_fit *taper_create_ordered(int n, int p, int r, const double *locs, const double *X, const double *z,
-                                 const double *smooth_limits, int device, int nnz, const int *colindices, const int *rowpointers,
-                                 const double *taper_entries, const std::vector<int> &perm, bool check_fit);
 void assemble_sigma(cocons_fit *f, const double *theta, int which, int col0, int col1);
 int assemble_sigma_taper(cocons_fit *f, const double *theta);
 int no_taper(cocons_fit *f, const char *who);
@@ -607,7 +601,26 @@ int info_status(cocons_fit *f);
 bool engine_retry(cocons_fit *f, int st);
 void dense_collect(cocons_fit *f, double *sum_logliks, double *parts);
 int profile_tail(cocons_fit *f, int nxb, double n_eff, bool reml, double *sum_logliks, double *parts);
-// ... and what it calls in api_shard.hip: the sharded cocons_neg2loglik_dense, and cocons_fit_destroy's share
+// ... the evaluation path's internals, offered to the diagnostics (api_diag.hip) only: what the replay and the profile run of
+// it, and the time-out report info_status asks api_diag.hip for under COCONS_DEBUG_ABORT
+RhsLayout rhs_layout(const cocons_fit *f, int nrhs);
+FactorView rhs_view(cocons_fit *f, const RhsLayout &l);
+void panel_ops(cocons_fit *f, const FactorView &v, int k, hipStream_t s);
+void count_update_flops(cocons_fit *f, int kw, int t0);
+int dag_prepare(cocons_fit *f, const FactorView &v);
+DagLaunch dag_launch(cocons_fit *f, const FactorView &v, const HandoffWords &hw, const unsigned *alive);
+int enqueue_eval(cocons_fit *f, const double *theta, const double *mean, bool use_trend, const double *xb, int nxb,
+                 std::vector<hipEvent_t> *ev_upd, bool stage_events);
+void debug_abort_report(cocons_fit *f);
+// ... what api_handle.hip offers: a handle over given data, a taper handle in a given order, a batch slot's clone
+cocons_fit *fit_create_impl(int n, int p, int r, int q, const double *locs, const double *X, const double *z, const double *x_betas,
+                            const double *smooth_limits, int device, bool allow_sort, bool defer_matrix = false,
+                            bool want_engine = true, bool return_locked = false);
+cocons_fit *taper_create_ordered(int n, int p, int r, const double *locs, const double *X, const double *z,
+                                 const double *smooth_limits, int device, int nnz, const int *colindices, const int *rowpointers,
+                                 const double *taper_entries, const std::vector<int> &perm, bool check_fit);
+cocons_fit *clone_for_slot(cocons_fit *f, bool want_engine);
+// ... and what they call in api_shard.hip: the sharded cocons_neg2loglik_dense, and cocons_fit_destroy's share
 int sharded_eval(cocons_fit *f, const double *theta, const double *mean, double *sum_logliks, double *parts);
 void shard_events_destroy(ShardState *S);
 void rccl_comm_destroy(ncclComm_t c);

@@ -73,14 +73,14 @@ def test_bad_arguments_return_error_codes_without_touching_the_gpu():
     dp = ctypes.POINTER(ctypes.c_double)
     a = np.zeros(8)
     p = a.ctypes.data_as(dp)
-    assert lib.cocons_cov_rns(0, 1, p, p, p, p, p) < 0
+    assert lib.cocons_cov_rns(0, 1, p, p, p, p, p) < 0                             # (api_cov.hip)
     assert "bad argument" in _lib.last_error()
     assert lib.cocons_cov_rns(4, 33, p, p, p, p, p) < 0            # p > COCONS_P_MAX
     assert lib.cocons_cov_rns_pred(4, 0, 1, p, p, p, p, p, p, p) < 0
     assert lib.cocons_chol_solve(0, p, 0, None, None, None, None) < 0
     assert _lib.last_error() == "cocons_chol_solve: bad argument"                  # (api_predict.hip)
-    assert not lib.cocons_fit_create(0, 1, 1, 0, p, p, p, None, p, 0)
-    assert lib.cocons_neg2loglik_dense(None, p, p, p, None) < 0
+    assert not lib.cocons_fit_create(0, 1, 1, 0, p, p, p, None, p, 0)              # (api_handle.hip)
+    assert lib.cocons_neg2loglik_dense(None, p, p, p, None) < 0                    # (api.hip)
     assert "null fit handle" in _lib.last_error()
     # an error raised in any translation unit of the library reaches the one cocons_last_error
     assert lib.cocons_krige_info(None, None) < 0                                   # (api_predict.hip)
@@ -90,7 +90,7 @@ def test_bad_arguments_return_error_codes_without_touching_the_gpu():
     assert lib.cocons_multi_neg2loglik_dense(None, p, p, p, None) < 0              # (api_shard.hip)
     assert _lib.last_error() == "cocons_multi_neg2loglik_dense: null argument"
     out5 = (ctypes.c_int * 5)()
-    assert lib.cocons_debug_rhs_layout(None, 0, out5) == -1           # (a diagnostic that makes no HIP call at all)
+    assert lib.cocons_debug_rhs_layout(None, 0, out5) == -1           # (api_diag.hip: a diagnostic that makes no HIP call at all)
     assert _lib.last_error().startswith("cocons_debug_rhs_layout:")
 
 

@@ -269,7 +269,7 @@ def test_late_host_is_waited_for_and_a_short_bound_records_0x112(oracle):
 def test_handles_created_used_and_destroyed_from_three_threads(record_property):
     """The threading contract of the boundary (include/cocons_hip.h): different handles may be created, used and destroyed from
     different threads at the same time.  A new handle's stream self-test launches probe kernels on the streams of OTHER live
-    handles (api.hip engine_warm) -- until round 5 without holding anything, so that a handle could be used or destroyed under
+    handles (api_handle.hip engine_warm) -- until round 5 without holding anything, so that a handle could be used or destroyed under
     the probe (the advisor's finding); now it takes the other handle's operation lock, and a busy handle is skipped.  Three
     threads churn through handles of engine-schedule size while each also evaluates on its own: every value must equal the
     single-threaded one and nothing may crash or hang.  (Hand-off time-outs are recorded, not forbidden: with this many live
@@ -316,7 +316,7 @@ def test_handles_created_used_and_destroyed_from_three_threads(record_property):
 
 def test_front_padding_n2115_all_entry_points_vs_oracle(oracle):
     """n = 45 x 47 = 2115 is not a multiple of 128: the handle keeps 61 placeholder observations IN FRONT of the caller's
-    (unit columns, api.hip fit_create_impl) instead of identity padding behind them.  Every entry point that runs on that
+    (unit columns, api_handle.hip fit_create_impl) instead of identity padding behind them.  Every entry point that runs on that
     layout, on the engine schedule, against the CPU restatement: -2 loglik (two realisations), Profile and REML with q = 3,
     the kriging core, and the status of a failing factorisation (reported in the caller's numbering)."""
     import cocons_amd as ca

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Offline look at the state a timed-out DAG launch left behind (COCONS_DEBUG_ABORT=1 COCONS_DEBUG_ABORT_DUMP=path writes
-path.N, see info_status in csrc/api.hip; with cocons_debug_tune("dag_trace", 1) the dump holds the stamps of every task).
+path.N, see debug_abort_report in csrc/api_diag.hip; with cocons_debug_tune("dag_trace", 1) the dump holds the stamps of every task).
 
     python tools/dag_abort.py gpurun_out/abort.bin.0
 """
