@@ -82,6 +82,10 @@ SIGNATURES = {
     "cocons_krige_taper_release": (c_int, [c_vp]),
     "cocons_krige_taper_info": (c_int, [c_vp, ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_krige_joint": (c_int, [c_vp, c_int, c_dp, c_dp, c_dp, c_dp, c_dp, c_int, c_dp, c_dp]),
+    "cocons_krige_taper_joint": (c_int, [c_vp, c_int, c_dp, c_dp, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_dp,
+                                         c_dp, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_dp,
+                                         c_dp, c_dp, c_int, c_dp, c_dp]),
+    "cocons_krige_taper_joint_bytes": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_sim_taper": (c_int, [c_vp, c_dp, c_dp, c_int, c_dp, ctypes.POINTER(c_int), c_dp]),
     "cocons_fit_taper_order": (c_int, [c_vp, ctypes.POINTER(c_int)]),
     "cocons_sim_cond_dense": (c_int, [c_vp, c_dp, c_dp, c_int, c_int, c_dp, c_dp, c_dp, c_int, c_dp, c_dp]),

@@ -459,6 +459,23 @@ static int krige_taper_stage(KrigeTaperState *K, size_t entries, const char *who
     return 0;
 }
 
+// a caller's m x ncols pattern: 1-based CSR, columns strictly increasing within a row (what: "" or which pattern of the call)
+static int krige_taper_csr_check(const char *who, const char *what, int m, int ncols, int nnz, const int *ci, const int *rp)
+{
+    if (rp[0] != 1 || rp[m] != nnz + 1) return fail(-1, "%s: %srowpointers do not match nnz (1-based CSR expected)", who, what);
+    for (int i = 0; i < m; ++i) {
+        const int a = rp[i], b = rp[i + 1];
+        if (b < a || a < 1 || b > nnz + 1) return fail(-1, "%s: %srowpointers decrease at row %d", who, what, i + 1);
+        for (int w = a - 1; w < b - 1; ++w) {
+            const int c = ci[w];
+            if (c < 1 || c > ncols) return fail(-1, "%s: %scolumn index out of range (row %d)", who, what, i + 1);
+            if (w > a - 1 && c <= ci[w - 1])
+                return fail(-1, "%s: %scolumn indices of row %d are not strictly increasing", who, what, i + 1);
+        }
+    }
+    return 0;
+}
+
 extern "C" int cocons_krige_taper_prepare(cocons_fit *f, const double *theta, const double *mean, int z_col, int max_rows)
 {
     const char *who = "cocons_krige_taper_prepare";
@@ -537,19 +554,8 @@ extern "C" int cocons_krige_taper_apply(cocons_fit *f, int m, const double *locs
     if (!K) return fail(-1, "%s: no kriging state on this handle (call cocons_krige_taper_prepare first)", who);
     if (m == 0) return 0;
     const int p = f->p, n = f->n, nt = f->nt, rows = K->rows, W = K->plan.W;
-    // the whole pattern is checked before any device work: 1-based CSR, columns strictly increasing within a row
-    if (rowpointers_pred[0] != 1 || rowpointers_pred[m] != nnz_pred + 1)
-        return fail(-1, "%s: rowpointers do not match nnz (1-based CSR expected)", who);
-    for (int i = 0; i < m; ++i) {
-        const int a = rowpointers_pred[i], b = rowpointers_pred[i + 1];
-        if (b < a || a < 1 || b > nnz_pred + 1) return fail(-1, "%s: rowpointers decrease at row %d", who, i + 1);
-        for (int w = a - 1; w < b - 1; ++w) {
-            const int c = colindices_pred[w];
-            if (c < 1 || c > n) return fail(-1, "%s: column index out of range (row %d)", who, i + 1);
-            if (w > a - 1 && c <= colindices_pred[w - 1])
-                return fail(-1, "%s: column indices of row %d are not strictly increasing", who, i + 1);
-        }
-    }
+    // the whole pattern is checked before any device work
+    if (int rc = krige_taper_csr_check(who, "", m, n, nnz_pred, colindices_pred, rowpointers_pred)) return rc;
     const double *th = K->theta.data();
     ThetaVecs tv;
     make_theta_vecs(th, p, tv, true);
@@ -632,6 +638,230 @@ extern "C" int cocons_krige_taper_info(cocons_fit *f, long long *out6)
     out6[3] = f->n;
     out6[4] = band_W(f);
     out6[5] = f->nt;
+    return 0;
+}
+
+// Joint prediction of a tapered fit from the held band factor: cocons_krige_joint's outputs,
+//   cov  = S_uu - C S^-1 C'         sims = L_S E + (X_pred mean + stochastic),  L_S L_S' = cov,
+// against the theta, realisation and mean of cocons_krige_taper_prepare.  C = pred_taper o cov_rns_taper_pred exactly as one
+// chunk of cocons_krige_taper_apply forms it; S_uu = taper_uu o cov_rns_taper at locs_unobs (the objective's entry kernel
+// straight into the lower triangle of the call's view S, identity on its padding).  V = C L^-T is never held as rows x n:
+// the ring solve runs with a ring depth - 1 slots deeper and S -= V_g V_g' leaves for S group by group of `depth` tile
+// columns while the window slides (launch_krige_band_solve).  Mirror, copy out; the draws are cocons_krige_joint's tail on
+// the plain schedule (a band handle has no resident engine, and every handle of a fit then draws the same bits).
+// Everything on the device belongs to the call; the kriging state is read only.
+static constexpr int KRIGE_JOINT_DEPTH = 8;                        // tile columns per Schur launch (measured)
+
+// COCONS_KRIGE_JOINT_DEPTH, read per call: 1 .. 16, or refused
+static int krige_joint_depth(const char *who, int *depth)
+{
+    *depth = KRIGE_JOINT_DEPTH;
+    const char *e = getenv("COCONS_KRIGE_JOINT_DEPTH");
+    if (!e || !*e) return 0;
+    char *end = nullptr;
+    const long v = strtol(e, &end, 10);
+    if (*end || v < 1 || v > 16) return fail(-1, "%s: COCONS_KRIGE_JOINT_DEPTH = \"%s\" (1 .. 16 expected)", who, e);
+    *depth = (int)v;
+    return 0;
+}
+
+// what every refusal of the two entries that needs no device work shares; K out
+static int krige_taper_joint_enter(cocons_fit *f, const char *who, int m, int *depth, const KrigeTaperState **K)
+{
+    if (int rc = krige_taper_handle(f, who)) return rc;
+    *K = f->krige_taper.get();
+    if (!*K) return fail(-1, "%s: no kriging state on this handle (call cocons_krige_taper_prepare first)", who);
+    if (m > KRIGE_TAPER_ROWS_MAX) return fail(-1, "%s: m = %d is too large (at most %d rows in one call)", who, m, KRIGE_TAPER_ROWS_MAX);
+    return krige_joint_depth(who, depth);
+}
+
+// doubles of the call's buffers but the CSR staging, in the order cocons_krige_taper_joint allocates them
+static void krige_taper_joint_counts(const cocons_fit *f, const KrigeTaperState *K, int m, int nsim, int depth, size_t counts[12])
+{
+    const size_t mv = (size_t)round_up(m, 64), mpad = (size_t)round_up(m, TILE), ne = (size_t)m * (size_t)nsim;
+    const size_t Wr = (size_t)std::min(K->plan.W + depth - 1, f->nt);
+    const size_t c[12] = {mv * Wr * TILE, mpad * mpad, (size_t)m * f->p, (size_t)m * 2, (size_t)m * 2, (size_t)LOCP_FIELDS * mv,
+                          (size_t)LOCP_FIELDS * mpad, mv, mv, ne ? ne : 1, ne ? ne : 1, (size_t)m};
+    memcpy(counts, c, sizeof c);
+}
+
+extern "C" int cocons_krige_taper_joint_bytes(cocons_fit *f, int m, int nsim, long long *bytes)
+{
+    const char *who = "cocons_krige_taper_joint_bytes";
+    if (m < 1) return fail(-1, "%s: m = %d (at least one new location is needed)", who, m);
+    if (nsim < 0) return fail(-1, "%s: nsim = %d is negative", who, nsim);
+    if (!bytes) return fail(-1, "%s: null argument", who);
+    if (!f) return fail(-1, "%s: null fit handle", who);
+    FIT_ENTER(f);
+    int depth = 0;
+    const KrigeTaperState *K = nullptr;
+    if (int rc = krige_taper_joint_enter(f, who, m, &depth, &K)) return rc;
+    size_t counts[12], total = 0;
+    krige_taper_joint_counts(f, K, m, nsim, depth, counts);
+    for (int k = 0; k < 12; ++k) total += counts[k];
+    *bytes = (long long)(total * sizeof(double) + 2 * ((size_t)m + 1) * sizeof(int));      // ... and the two row-pointer arrays
+    return 0;
+}
+
+extern "C" int cocons_krige_taper_joint(cocons_fit *f, int m, const double *locs_pred, const double *X_pred, int nnz_pred,
+                                        const int *colindices_pred, const int *rowpointers_pred,
+                                        const double *taper_entries_pred, const double *locs_unobs, int nnz_uu,
+                                        const int *colindices_uu, const int *rowpointers_uu, const double *taper_entries_uu,
+                                        double *stochastic, double *cov, int nsim, const double *iiderrors, double *sims)
+{
+    const char *who = "cocons_krige_taper_joint";
+    if (m < 1) return fail(-1, "%s: m = %d (at least one new location is needed)", who, m);
+    if (!locs_pred || !X_pred || !stochastic || !rowpointers_pred || !rowpointers_uu)
+        return fail(-1, "%s: null locs_pred, X_pred, stochastic or row pointers", who);
+    if (nnz_pred < 0 || (nnz_pred > 0 && (!colindices_pred || !taper_entries_pred)))
+        return fail(-1, "%s: nnz_pred = %d is negative, or comes with a null colindices_pred or taper_entries_pred", who, nnz_pred);
+    if (nnz_uu < 1 || !colindices_uu || !taper_entries_uu)
+        return fail(-1, "%s: nnz_uu = %d (every row holds its diagonal), or a null colindices_uu or taper_entries_uu", who, nnz_uu);
+    if (nsim < 0) return fail(-1, "%s: nsim = %d is negative", who, nsim);
+    if (nsim > 0 && (!iiderrors || !sims)) return fail(-1, "%s: nsim = %d with a null iiderrors or sims", who, nsim);
+    if (!f) return fail(-1, "%s: null fit handle", who);
+    FIT_ENTER(f);
+    int D = 0;
+    const KrigeTaperState *K = nullptr;
+    if (int rc = krige_taper_joint_enter(f, who, m, &D, &K)) return rc;
+    const int p = f->p, n = f->n, nt = f->nt, W = K->plan.W, Wr = std::min(W + D - 1, nt);
+    // both patterns are checked before any device work; a uu row holds its diagonal entry
+    if (int rc = krige_taper_csr_check(who, "pred pattern: ", m, n, nnz_pred, colindices_pred, rowpointers_pred)) return rc;
+    if (int rc = krige_taper_csr_check(who, "uu pattern: ", m, m, nnz_uu, colindices_uu, rowpointers_uu)) return rc;
+    for (int i = 0; i < m; ++i) {
+        const int *a = colindices_uu + rowpointers_uu[i] - 1, *b = colindices_uu + rowpointers_uu[i + 1] - 1;
+        if (!std::binary_search(a, b, i + 1)) return fail(-1, "%s: uu pattern: row %d does not hold its diagonal entry", who, i + 1);
+    }
+    const int mv = round_up(m, 64), mpad = round_up(m, TILE);
+    const size_t ldr = (size_t)mv, lds = (size_t)mpad, nsm = (size_t)m * (size_t)nsim;
+    const size_t ne = (size_t)nnz_pred, nu = (size_t)nnz_uu;
+    const double *lu = locs_unobs ? locs_unobs : locs_pred;
+    const double *th = K->theta.data();
+    // the pred pattern in the handle's order of the observations, bucketed by tile column (cocons_krige_taper_apply, one chunk)
+    std::vector<int> hci(ne), hdst(ne), hsrc(ne), boff((size_t)nt + 1, 0), fill((size_t)nt);
+    for (size_t w = 0; w < ne; ++w) {
+        const int c = f->taper_inv[colindices_pred[w] - 1];
+        hci[w] = c + 1;
+        ++boff[c / TILE + 1];
+    }
+    for (int I = 0; I < nt; ++I) { boff[I + 1] += boff[I]; fill[I] = boff[I]; }
+    for (int i = 0; i < m; ++i)
+        for (int w = rowpointers_pred[i] - 1; w < rowpointers_pred[i + 1] - 1; ++w) {
+            const int c = hci[w] - 1, k = fill[c / TILE]++;
+            hdst[k] = i + (c % TILE) * mv;
+            hsrc[k] = w;
+        }
+    std::vector<double> stv((size_t)m), mu((size_t)m), hY(nsm), hcov;
+    if (cov && nsim > 0) hcov.resize((size_t)m * m);     // the factorisation may still fail: cov goes home through a staging copy
+    double *cov_to = hcov.empty() ? cov : hcov.data();
+    int raw = 0x7f7f7f7f;                                // the view's own info word
+    DevBuf<double> dring, dS, dXp, dlp, dlu, dlocp, dlocu, dst, dq, dE, dY, dmu, dtvp, dval, dtvu;
+    DevBuf<int> dcip, drpp, dbdst, dbsrc, dciu, drpu;
+    StreamDrain s{f->stream, false};
+    {
+        size_t counts[15], total = 0;
+        krige_taper_joint_counts(f, K, m, nsim, D, counts);
+        counts[12] = ne ? ne : 1; counts[13] = ne ? ne : 1; counts[14] = nu;
+        DevBuf<double> *bufs[15] = {&dring, &dS, &dXp, &dlp, &dlu, &dlocp, &dlocu, &dst, &dq, &dE, &dY, &dmu, &dtvp, &dval, &dtvu};
+        const size_t icounts[6] = {ne ? ne : 1, (size_t)m + 1, ne ? ne : 1, ne ? ne : 1, nu, (size_t)m + 1};
+        DevBuf<int> *ibufs[6] = {&dcip, &drpp, &dbdst, &dbsrc, &dciu, &drpu};
+        for (int k = 0; k < 15; ++k) total += counts[k] * sizeof(double);
+        for (int k = 0; k < 6; ++k) total += icounts[k] * sizeof(int);
+        hipError_t e = alloc_call_buffers(bufs, counts, 15);
+        for (int k = 0; k < 6 && e == hipSuccess; ++k)
+            if ((e = ibufs[k]->alloc(icounts[k])) != hipSuccess) (void)hipGetLastError();
+        if (e != hipSuccess)
+            return fail(-100 - (int)e, "%s: the device cannot hold the %zu bytes of the call (m = %d new locations, %d ring slots, "
+                        "n = %d): %s", who, total, m, Wr, f->n, hipGetErrorString(e));
+    }
+    HIPCHK_AT(who, upload_canon(dXp, X_pred, (size_t)m * p, s));
+    HIPCHK_AT(who, upload_canon(dlp, locs_pred, (size_t)m * 2, s));
+    HIPCHK_AT(who, upload_canon(dlu, lu, (size_t)m * 2, s));
+    HIPCHK_AT(who, hipMemcpyAsync(drpp, rowpointers_pred, ((size_t)m + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK_AT(who, hipMemcpyAsync(drpu, rowpointers_uu, ((size_t)m + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK_AT(who, hipMemcpyAsync(dciu, colindices_uu, nu * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK_AT(who, upload_canon(dtvu, taper_entries_uu, nu, s));
+    if (ne > 0) {
+        HIPCHK_AT(who, hipMemcpyAsync(dcip, hci.data(), ne * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK_AT(who, hipMemcpyAsync(dbdst, hdst.data(), ne * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK_AT(who, hipMemcpyAsync(dbsrc, hsrc.data(), ne * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK_AT(who, upload_canon(dtvp, taper_entries_pred, ne, s));
+    }
+    if (nsim > 0) HIPCHK_AT(who, upload_canon(dE, iiderrors, nsm, s));
+    // C: prediction-branch parameters (cocons_krige_taper_apply); S_uu: those of cocons_cov_rns_taper (the objective's)
+    ThetaVecs tv;
+    make_theta_vecs(th, p, tv, true);
+    const ModeSel msp = select_mode(th, p, f->smooth_limits, 2);
+    const ModeSel ms0 = select_mode(th, p, f->smooth_limits, 0);
+    auto enqueue = [&]() -> int {
+        launch_loc_params(loc_args(m, p, dXp, dlp, dlocp, ldr, tv, msp.smooth_kind, f->smooth_limits), s);
+        launch_loc_params(loc_args(m, p, dXp, dlu, dlocu, lds, tv, ms0.smooth_kind, f->smooth_limits), s);
+        TaperLaunch t;
+        t.mode = MODE_GEOM; t.pred = true; t.nrows = m; t.nnz = nnz_pred; t.ci = dcip; t.rp = drpp;
+        t.rows = dlocp; t.stride_rows = ldr; t.cols = K->loc; t.stride = f->npad;
+        t.out = dval;
+        launch_taper(t, s);
+        // S_uu: the entries with column <= row times their taper value into the zeroed view, identity on [m, mpad)
+        HIPCHK_AT(who, hipMemsetAsync(dS, 0, lds * mpad * sizeof(double), s));
+        TaperLaunch u;
+        u.mode = ms0.mode; u.nrows = m; u.nnz = nnz_uu; u.ci = dciu; u.rp = drpu; u.nu_fixed = ms0.nu_fixed;
+        u.rows = u.cols = dlocu; u.stride_rows = u.stride = lds;
+        u.tapv = dtvu; u.A = dS; u.lda = lds;
+        launch_taper(u, s);
+        launch_pad_identity(dS, lds, m, mpad, s);
+        KrigeBandSolve a;
+        a.Lp = K->L; a.Qp = K->Q; a.w = K->w; a.toff = K->plan.toff.data(); a.hi = envelope_or_null(f);
+        a.nt = nt; a.W = W; a.ring = dring; a.ldr = ldr; a.rows = m;
+        a.boff = boff.data(); a.bdst = dbdst; a.bsrc = dbsrc; a.val = dval; a.tapv = dtvp;
+        a.stoch = dst; a.quad = dq;
+        a.Wr = Wr; a.depth = D; a.S = dS; a.lds = lds;
+        HIPCHK_AT(who, launch_krige_band_solve(a, s));
+        launch_sym_mirror(dS, lds, m, s);
+        HIPCHK_AT(who, hipMemcpyAsync(stv.data(), dst, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (cov)
+            HIPCHK_AT(who, hipMemcpy2DAsync(cov_to, (size_t)m * sizeof(double), dS, lds * sizeof(double), (size_t)m * sizeof(double),
+                                            (size_t)m, hipMemcpyDeviceToHost, s));
+        if (nsim == 0) return 0;
+        // tmp_mu = X_pred mean + stochastic on the host, then cocons_krige_joint's tail
+        HIPCHK_AT(who, hipStreamSynchronize(s));
+        for (int i = 0; i < m; ++i) {
+            double sys = 0;
+            for (int j = 0; j < p; ++j) sys += X_pred[(size_t)i + (size_t)j * m] * K->mean[j];
+            mu[i] = sys + stv[i];
+        }
+        HIPCHK_AT(who, upload_canon(dmu, mu.data(), (size_t)m, s));
+        {
+            // a dense view of the call, maybe of more tiles than the handle's nt: factorize() sizes the hand-off words and the
+            // mailboxes by the view (flags_reset, mbox_reset), dinv and dinfo do not depend on the order
+            PlainSchedule plain(f);
+            FoldView fv(f);
+            FactorView v;
+            v.A = dS; v.lda = lds; v.nt = mpad / TILE; v.mt = mpad / TILE;
+            if (int rc = factorize(f, v, nullptr)) return rc;
+        }
+        HIPCHK_AT(who, hipMemcpyAsync(&raw, f->dinfo, sizeof(int), hipMemcpyDeviceToHost, s));
+        launch_trmm_lower(dS, lds, m, dE, m, nsim, dmu, dY, m, s);
+        HIPCHK_AT(who, hipMemcpyAsync(hY.data(), dY, nsm * sizeof(double), hipMemcpyDeviceToHost, s));
+        return 0;
+    };
+    if (nsim == 0) {                    // nothing is factored: no info words, nothing to repeat
+        if (int rc = enqueue()) return rc;
+        HIPCHK_AT(who, hipGetLastError());
+        HIPCHK_AT(who, hipStreamSynchronize(s));
+    } else {
+        f->nrhs_cur = 0;
+        const int st = run_op(f, who, enqueue);
+        if (st > 0)
+            return fail(-5, "%s: the predictive covariance is not positive definite (leading minor %d of %d not positive)", who,
+                        raw, m);
+        if (st < 0) {
+            const std::string why = g_err;
+            return why.compare(0, strlen(who), who) == 0 ? st : fail(st, "%s: %s", who, why.c_str());
+        }
+        memcpy(sims, hY.data(), nsm * sizeof(double));
+        if (!hcov.empty()) memcpy(cov, hcov.data(), hcov.size() * sizeof(double));
+    }
+    memcpy(stochastic, stv.data(), (size_t)m * sizeof(double));
     return 0;
 }
 

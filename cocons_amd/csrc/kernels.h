@@ -332,6 +332,13 @@ hipError_t launch_krige_band_load(double *slot, size_t ldr, const int *dst, cons
 // rows rounded up to 64), stoch[i] = V(i,:) w, quad[i] = V(i,:) V(i,:)'.  The chunk's entries are bucketed by tile column:
 // bucket I = the entries boff[I] .. boff[I + 1] of bdst / bsrc (device; boff, toff and hi are HOST arrays, hi null = nt).
 // Rows are independent and every sum order is fixed.
+// Joint prediction (cocons_krige_taper_joint) sets the last three lines: the ring then has Wr = min(W + depth - 1, nt) slots
+// (tile column I in slot I mod Wr; the live window and the loads stay those of W), so a solved tile column survives
+// depth - 1 further steps, and behind the diag launch of the last tile column of every group of `depth` consecutive tile
+// columns (and of the last, possibly partial, group) one launch does S -= V_g V_g' over the lower tiles of S
+// (krige_band_schur_kernel; S: round_up(rows, 128) rows and columns, ld lds; ldr = round_up(rows, 64) exactly).  The slot
+// the load of step J takes over held tile J - depth, whose group ended at step <= J - 1.  Every element of S sees the
+// tile columns in ascending order whatever the depth: S does not depend on it to the bit.  Unset: the plain ring, no product.
 struct KrigeBandSolve {
     const double *Lp = nullptr, *Qp = nullptr, *w = nullptr;
     const int *toff = nullptr, *hi = nullptr; int nt = 0, W = 0;
@@ -339,6 +346,9 @@ struct KrigeBandSolve {
     const int *boff = nullptr, *bdst = nullptr, *bsrc = nullptr;
     const double *val = nullptr, *tapv = nullptr;
     double *stoch = nullptr, *quad = nullptr;
+    int Wr = 0;                    // slots of the ring (0: W)
+    int depth = 0;                 // tile columns per Schur launch (with S)
+    double *S = nullptr; size_t lds = 0;
 };
 hipError_t launch_krige_band_solve(const KrigeBandSolve &a, hipStream_t s);
 // schur: S(I, J) -= V(I, :) V(J, :)' over the lower 128 x 128 tiles of S (round_up(m, 128) rows and columns, column-major,

@@ -697,14 +697,20 @@ hipError_t launch_krige_band_load(double *slot, size_t ldr, const int *dst, cons
     return hipSuccess;
 }
 
+__global__ void __launch_bounds__(256)
+krige_band_schur_kernel(const double *ring, size_t ldr, int Wr, int t0, int t1, double *S, size_t lds);      // (below)
+
 hipError_t launch_krige_band_solve(const KrigeBandSolve &a, hipStream_t s)
 {
     if (a.rows <= 0 || a.nt <= 0) return hipSuccess;
     const unsigned strips = (unsigned)((a.rows + 63) / 64);
     const int nt = a.nt, W = a.W;
+    const int Wr = a.Wr > 0 ? a.Wr : W;                 // the ring's modulus; the live window stays W
+    const int D = a.S ? std::max(a.depth, 1) : 0;
+    const unsigned mpad = (unsigned)((a.rows + TILE - 1) / TILE * TILE);
     auto load = [&](int I) {
         const int k0 = a.boff[I], k1 = a.boff[I + 1];
-        return launch_krige_band_load(a.ring + (size_t)(I % W) * TILE * a.ldr, a.ldr, a.bdst + k0, a.bsrc + k0, k1 - k0, a.val,
+        return launch_krige_band_load(a.ring + (size_t)(I % Wr) * TILE * a.ldr, a.ldr, a.bdst + k0, a.bsrc + k0, k1 - k0, a.val,
                                       a.tapv, s);
     };
     for (int I = 0; I < std::min(W, nt); ++I)
@@ -714,11 +720,15 @@ hipError_t launch_krige_band_solve(const KrigeBandSolve &a, hipStream_t s)
             if (hipError_t e = load(J + W - 1)) return e;
         const double *Lcol = a.Lp + (size_t)a.toff[J] * TILE * TILE;
         hipLaunchKernelGGL(krige_band_diag_kernel, dim3(strips), dim3(256), 0, s, Lcol, a.Qp + (size_t)J * 2048,
-                           a.w + (size_t)J * TILE, a.ring + (size_t)(J % W) * TILE * a.ldr, a.ldr, J == 0 ? 1 : 0, a.stoch, a.quad);
+                           a.w + (size_t)J * TILE, a.ring + (size_t)(J % Wr) * TILE * a.ldr, a.ldr, J == 0 ? 1 : 0, a.stoch, a.quad);
+        // the group [J / D * D, J] is solved and still in the ring: its product leaves for S before a later load takes a slot
+        if (D && ((J + 1) % D == 0 || J + 1 == nt))
+            hipLaunchKernelGGL(krige_band_schur_kernel, dim3(mpad / 64, mpad / TILE), dim3(256), 0, s, a.ring, a.ldr, Wr,
+                               J / D * D, J + 1, a.S, a.lds);
         const int hj = a.hi ? a.hi[J] : nt;
         if (hj - J - 1 > 0)
             hipLaunchKernelGGL(krige_band_update_kernel, dim3(strips, (unsigned)(hj - J - 1)), dim3(256), 0, s, Lcol, a.ring, a.ldr,
-                               J % W, W);
+                               J % Wr, Wr);
     }
     return hipGetLastError();
 }
@@ -755,6 +765,66 @@ krige_schur_kernel(const double *V, size_t ldv, int m, int k0, int k1, double *S
         for (int q = 0; q < 64 * KS_KC / 256; ++q) {
             const int e = tid + 256 * q, i = e & 63, k = e >> 6;
             vp[q] = r0 + i < m ? V[(size_t)(r0 + i) + (size_t)(kc + k) * ldv] : 0.0;
+        }
+        __syncthreads();                  // every wave is done with the previous slice
+#pragma unroll
+        for (int q = 0; q < TILE * KS_KC / 256; ++q) {
+            const int e = tid + 256 * q, j = e & (TILE - 1), k = e >> 7;
+            QS[(((j >> 4) * (KS_KC / 16) + (k >> 4)) << 8) + ((k & 15) << 4) + (j & 15)] = vq[q];
+        }
+#pragma unroll
+        for (int q = 0; q < 64 * KS_KC / 256; ++q) {
+            const int e = tid + 256 * q, i = e & 63, k = e >> 6;
+            PS[(((i >> 4) * (KS_KC / 16) + (k >> 4)) << 8) + ((k & 15) << 4) + (i & 15)] = vp[q];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kb = 0; kb < KS_KC / 16; ++kb) {
+            const d4 NP = -lds_blk(PS + ((wave * (KS_KC / 16) + kb) << 8), lane);
+#pragma unroll
+            for (int jb = 0; jb < 8; ++jb) {
+                const d4 Q = lds_blk(QS + ((jb * (KS_KC / 16) + kb) << 8), lane);
+                blk_mma(acc[jb], NP, Q);
+            }
+        }
+    }
+#pragma unroll
+    for (int jb = 0; jb < 8; ++jb) glb_blk_store(S, lds, rs, c0 + 16 * jb, lane, acc[jb]);
+}
+
+// The same product with both operands read from the kriging ring of a band factor (cocons_krige_taper_joint): S(I, J) -=
+// sum over the tile columns t in [t0, t1) of V_t(I, :) V_t(J, :)', V_t the 128 solved columns at ring column (t mod Wr) * 128.
+// krige_schur_kernel's tile scheme, registers and LDS: per tile column the slices of 32, the 16-column blocks and the MFMA
+// order are its own, and the tile columns come in ascending order; the accumulators go back to S between launches, which is
+// exact -- every element of S sees ONE sequence over the columns whatever the grouping.  The ring has ldr = round_up(m, 64)
+// rows (those >= m exactly zero: a slot is zeroed before its entries arrive); rows >= ldr are read as zero.
+__global__ void __launch_bounds__(256)
+krige_band_schur_kernel(const double *ring, size_t ldr, int Wr, int t0, int t1, double *S, size_t lds)
+{
+    __shared__ double PS[64 * KS_KC];
+    __shared__ double QS[TILE * KS_KC];
+    const int strip = blockIdx.x, J = blockIdx.y;
+    if (2 * J > strip) return;                      // tile J lies right of the strip's diagonal tile
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r0 = 64 * strip, c0 = J * TILE, rs = r0 + 16 * wave;
+    const int mr = (int)ldr;
+    d4 acc[8];
+#pragma unroll
+    for (int jb = 0; jb < 8; ++jb) acc[jb] = glb_blk(S, lds, rs, c0 + 16 * jb, lane);
+    // one loop over the slices of every tile column of the group: slice s of tile column t at ring column (t mod Wr) 128 + 32 s
+    for (int sl = t0 * (TILE / KS_KC); sl < t1 * (TILE / KS_KC); ++sl) {
+        const int t = sl / (TILE / KS_KC), kc = (sl % (TILE / KS_KC)) * KS_KC;
+        const double *V = ring + (size_t)(t % Wr) * TILE * ldr;
+        double vq[TILE * KS_KC / 256], vp[64 * KS_KC / 256];
+#pragma unroll
+        for (int q = 0; q < TILE * KS_KC / 256; ++q) {
+            const int e = tid + 256 * q, j = e & (TILE - 1), k = e >> 7;
+            vq[q] = c0 + j < mr ? V[(size_t)(c0 + j) + (size_t)(kc + k) * ldr] : 0.0;
+        }
+#pragma unroll
+        for (int q = 0; q < 64 * KS_KC / 256; ++q) {
+            const int e = tid + 256 * q, i = e & 63, k = e >> 6;
+            vp[q] = r0 + i < mr ? V[(size_t)(r0 + i) + (size_t)(kc + k) * ldr] : 0.0;
         }
         __syncthreads();                  // every wave is done with the previous slice
 #pragma unroll

@@ -26,8 +26,8 @@ from ._lib import CholeskyError, c_dp
 
 
 class KrigeJointNotPositiveDefinite(_lib.CoconsHipError):
-    """cocons_krige_joint's -5: the predictive covariance is not positive definite in floating point (the message names
-    the failing minor); the reference's second `chol` fails there (R/sim.R:106)."""
+    """cocons_krige_joint's and cocons_krige_taper_joint's -5: the predictive covariance is not positive definite in floating
+    point (the message names the failing minor); the reference's second `chol` fails there (R/sim.R:106)."""
 
 
 ASPECTS = ("mean", "std.dev", "scale", "aniso", "tilt", "smooth", "nugget")   # R/profile.R:5-7
@@ -97,6 +97,12 @@ def cov_rns_pred(theta, locs, locs_pred, x_covariates, x_covariates_pred, smooth
 
 def _ip(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+
+
+def _csr(taper):
+    """(colindices int32, rowpointers int32, entries float64), contiguous, of a (colindices, rowpointers, entries) triple"""
+    return (np.ascontiguousarray(np.asarray(taper[0], dtype=np.int32)), np.ascontiguousarray(np.asarray(taper[1], dtype=np.int32)),
+            np.ascontiguousarray(np.asarray(taper[2], dtype=np.float64)))
 
 
 def cov_rns_taper(theta, locs, x_covariates, colindices, rowpointers, smooth_limits) -> np.ndarray:
@@ -634,6 +640,41 @@ class CoconsTaperFit(CoconsFit):
         return {"prepared": bool(out[0]), "bytes": int(out[1]), "rows": int(out[2]), "n": int(out[3]), "W": int(out[4]),
                 "nt": int(out[5])}
 
+    def krige_taper_joint_core(self, locs_pred, x_covariates_pred, pred_taper, uu_taper, locs_unobs=None, iiderrors=None,
+                               cov=True):
+        """(stochastic, cov | None, sims | None) at the new locations against the prepared band factor
+        (cocons_krige_taper_joint): cov = S_uu - C S^-1 C' (m x m, symmetric to the bit), S_uu = uu_taper o cov_rns_taper at
+        locs_unobs (default locs_pred); sims = chol(cov) iiderrors + (X_pred mean + stochastic) for iiderrors m x nsim.
+        pred_taper as krige_taper_core takes it; uu_taper = (colindices, rowpointers, entries) of the m x m taper between the
+        new locations (1-based CSR, every row with its diagonal; the entries with column <= row are read).  A predictive
+        covariance that is not positive definite in floating point (draws only) raises KrigeJointNotPositiveDefinite."""
+        lp, Xp = _f(locs_pred), _f(x_covariates_pred)
+        m = Xp.shape[0]
+        ci, rp, te = _csr(pred_taper)
+        cu, ru, tu = _csr(uu_taper)
+        lu = None if locs_unobs is None else _f(np.asarray(locs_unobs, dtype=np.float64)[:, :2])
+        E = None if iiderrors is None else _f(np.asarray(iiderrors, dtype=np.float64).reshape(m, -1))
+        nsim = 0 if E is None else E.shape[1]
+        st = np.empty(m)
+        C = np.empty((m, m), order="F") if cov else None
+        Y = np.empty((m, nsim), order="F") if nsim > 0 else None
+        rc = self._L.cocons_krige_taper_joint(self._h, m, _p(lp), _p(Xp), int(ci.size), _ip(ci), _ip(rp), _p(te),
+                                              None if lu is None else _p(lu), int(cu.size), _ip(cu), _ip(ru), _p(tu), _p(st),
+                                              None if C is None else _p(C), nsim, None if nsim == 0 else _p(E),
+                                              None if Y is None else _p(Y))
+        if rc == -5 and "not positive definite" in _lib.last_error():
+            raise KrigeJointNotPositiveDefinite(_lib.last_error())
+        _lib.check(rc, "cocons_krige_taper_joint")
+        return st, C, Y
+
+    def krige_taper_joint_bytes(self, m, nsim=0):
+        """Device bytes krige_taper_joint_core allocates for m new locations and nsim draws on this handle, the CSR staging
+        apart (cocons_krige_taper_joint_bytes): what a caller sizes m by."""
+        out = ctypes.c_longlong(0)
+        _lib.check(self._L.cocons_krige_taper_joint_bytes(self._h, int(m), int(nsim), ctypes.byref(out)),
+                   "cocons_krige_taper_joint_bytes")
+        return int(out.value)
+
     def sim_core(self, theta_list, iiderrors, pivot=None):
         """Fields of the sparse branch of cocoSim (R/sim.R:177-217), n x nsim: (L_P E)[k] + (X mean) scattered to rows
         pivot[k] - 1, L_P L_P' = S[pivot, pivot].  pivot = None: the handle's own order (same distribution, another field
@@ -719,6 +760,53 @@ def cocoPredict_sparse_chunked(theta_list, locs, newlocs, X_std, X_pred_std, smo
         if own:
             f.close()
     return _sparse_predict_tail(theta_list, X_pred_std, st, qf, type)
+
+
+def cocoPredict_sparse_joint(theta_list, locs, newlocs, X_std, X_pred_std, smooth_limits, z, ref_taper, pred_taper, uu_taper,
+                             fit=None):
+    """cocoPredict_sparse with the predictive covariance BETWEEN the new locations: {"systematic", "stochastic", "sd.pred",
+    "cov.pred"}, cov.pred = S_uu - C S^-1 C' (m x m) from one held band factor (krige_taper_prepare,
+    krige_taper_joint_core, release), S_uu = uu_taper o cov_rns_taper at the new locations, and sd.pred the root of its
+    diagonal with the reference's abs rule below 1e-10 (R/predict.R:269-271).  uu_taper = (colindices, rowpointers,
+    entries) of spam::nearest.dist(newlocs, delta, upper = NULL) with the taper applied."""
+    f, own = (fit, False) if fit is not None else (CoconsTaperFit(locs, X_std, z, smooth_limits, *ref_taper), True)
+    try:
+        f.krige_taper_prepare(theta_list)
+        try:
+            st, cov, _ = f.krige_taper_joint_core(newlocs, X_pred_std, pred_taper, uu_taper)
+        finally:
+            f.krige_taper_release()
+    finally:
+        if own:
+            f.close()
+    out = _sparse_predict_tail(theta_list, X_pred_std, st, np.zeros(len(st)), "mean")
+    unc = np.diag(cov).copy()
+    neg = unc < 1e-10
+    unc[neg] = np.abs(unc[neg])
+    out.update({"sd.pred": np.sqrt(unc), "cov.pred": cov})
+    return out
+
+
+def cocoSim_cond_sparse_held(theta_list, locs, newlocs, newdataset, X_std, X_pred_std, smooth_limits, z, ref_taper,
+                             pred_taper, uu_taper, iiderrors, fit=None):
+    """Conditional simulation (sim.type = "cond") of a tapered model, which the reference's cocoSim does not offer for
+    sparse objects (R/sim.R:177-217): cocoSim_cond_dense_held's draws from a held band factor -- prepare, one joint call
+    (krige_taper_joint_core: only the m x m Cholesky of the predictive covariance is taken), release.  `newdataset`
+    supplies the coordinates of S_uu (its first two columns), uu_taper its pattern and taper values.  Returns m x nsim."""
+    f, own = (fit, False) if fit is not None else (CoconsTaperFit(locs, X_std, z, smooth_limits, *ref_taper), True)
+    try:
+        try:
+            f.krige_taper_prepare(theta_list)
+            try:
+                return f.krige_taper_joint_core(newlocs, X_pred_std, pred_taper, uu_taper,
+                                                np.asarray(newdataset, dtype=np.float64), iiderrors, cov=False)[2]
+            finally:
+                f.krige_taper_release()
+        except (CholeskyError, KrigeJointNotPositiveDefinite):
+            raise RuntimeError("Cholesky error")
+    finally:
+        if own:
+            f.close()
 
 
 def _cv_result(f, z, resid, var):

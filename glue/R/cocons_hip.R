@@ -425,6 +425,22 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
   res[[2]]
 }
 
+# joint prediction against the same held band factor: the predictive covariance between the new locations and, with
+# iiderrors (m x nsim), conditional draws of the tapered model (the reference's cocoSim has no conditional branch for
+# sparse objects).  uu_taper: the taper between the new locations, spam::nearest.dist(newlocs, delta = delta, upper = NULL)
+# with the taper function applied (every row holds its diagonal; the entries with column <= row are read):
+#   kj <- .cocons.hip.krige.taper.joint(fit, newlocs, X_pred_std, pred_taper, uu_taper, iiderrors = E)
+#   kj$stochastic;  kj$cov  (m x m, or NULL with cov = FALSE);  kj$sims  (m x nsim, or NULL without iiderrors)
+.cocons.hip.krige.taper.joint <- function(fit, newlocs, X_pred, pred_taper, uu_taper, locs_unobs = NULL, iiderrors = NULL,
+                                          cov = TRUE) {
+  res <- .Call(`_cocons_hip_krige_taper_joint`, fit, newlocs, X_pred,
+               list(pred_taper@colindices, pred_taper@rowpointers, as.double(pred_taper@entries)),
+               list(uu_taper@colindices, uu_taper@rowpointers, as.double(uu_taper@entries)),
+               locs_unobs, iiderrors, as.logical(cov))
+  if (res[[1]] != 0L) stop("Cholesky error")
+  list(stochastic = res[[2]], cov = res[[3]], sims = res[[4]])
+}
+
 .cocons.hip.krige.taper.release <- function(fit) invisible(.Call(`_cocons_hip_krige_taper_release`, fit))
 
 # sparse branch of cocoSim (R/sim.R:177-217): the lines from cov_rns_taper to the sweep (:193-216) become

@@ -923,6 +923,52 @@ SEXP _cocons_hip_krige_taper(SEXP fitp, SEXP locs_pred, SEXP X_pred, SEXP colind
     return out;
 }
 
+/* one taper as list(colindices, rowpointers, entries) for m rows: its slots checked, its number of entries returned */
+static int taper_slots(SEXP taper, int m, const char *what, SEXP *ci, SEXP *rp, SEXP *en)
+{
+    if (XLENGTH(taper) != 3) Rf_error("%s must be list(colindices, rowpointers, entries)", what);
+    *ci = VECTOR_ELT(taper, 0); *rp = VECTOR_ELT(taper, 1); *en = VECTOR_ELT(taper, 2);
+    if (!Rf_isInteger(*ci) || !Rf_isInteger(*rp) || !Rf_isReal(*en) || XLENGTH(*rp) != (R_xlen_t)m + 1 ||
+        XLENGTH(*en) != XLENGTH(*ci))
+        Rf_error("%s does not match the prediction locations", what);
+    return (int)XLENGTH(*ci);
+}
+
+/* joint prediction against the held band factor: pred_taper (m x n) and uu_taper (m x m) as list(colindices, rowpointers,
+ * entries), locs_unobs m x 2 or NULL (= locs_pred), iiderrors m x nsim or NULL (no draws), want_cov.
+ * list(status, stochastic, cov m x m | NULL, sims m x nsim | NULL) as _cocons_hip_krige_joint -- status -5: the predictive
+ * covariance is not positive definite ("Cholesky error" in the R wrapper), nothing written */
+SEXP _cocons_hip_krige_taper_joint(SEXP fitp, SEXP locs_pred, SEXP X_pred, SEXP pred_taper, SEXP uu_taper, SEXP locs_unobs,
+                                   SEXP iiderrors, SEXP want_cov)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), m = Rf_nrows(X_pred);
+    if (Rf_ncols(X_pred) != p || Rf_nrows(locs_pred) != m || Rf_ncols(locs_pred) != 2)
+        Rf_error("prediction design / locations do not match the fit");
+    SEXP pci, prp, pen, uci, urp, uen;
+    const int nnz_pred = taper_slots(pred_taper, m, "pred_taper", &pci, &prp, &pen);
+    const int nnz_uu = taper_slots(uu_taper, m, "uu_taper", &uci, &urp, &uen);
+    const int have_lu = !Rf_isNull(locs_unobs), have_e = !Rf_isNull(iiderrors), wc = Rf_asLogical(want_cov);
+    if (have_lu && (Rf_nrows(locs_unobs) != m || Rf_ncols(locs_unobs) != 2)) Rf_error("locs_unobs must be %d x 2", m);
+    if (have_e && Rf_nrows(iiderrors) != m) Rf_error("iiderrors must have %d rows", m);
+    const int nsim = have_e ? Rf_ncols(iiderrors) : 0;
+    SEXP res = PROTECT(Rf_allocVector(VECSXP, 4));
+    SEXP st = Rf_allocVector(REALSXP, m);
+    SET_VECTOR_ELT(res, 1, st);
+    SEXP cv = R_NilValue, sm = R_NilValue;
+    if (wc) { cv = Rf_allocMatrix(REALSXP, m, m); SET_VECTOR_ELT(res, 2, cv); }
+    if (nsim > 0) { sm = Rf_allocMatrix(REALSXP, m, nsim); SET_VECTOR_ELT(res, 3, sm); }
+    for (int i = 0; i < m; ++i) REAL(st)[i] = NA_REAL;
+    int rc = cocons_krige_taper_joint(f, m, REAL(locs_pred), REAL(X_pred), nnz_pred, INTEGER(pci), INTEGER(prp), REAL(pen),
+                                      have_lu ? REAL(locs_unobs) : NULL, nnz_uu, INTEGER(uci), INTEGER(urp), REAL(uen),
+                                      REAL(st), wc ? REAL(cv) : NULL, nsim, nsim > 0 ? REAL(iiderrors) : NULL,
+                                      nsim > 0 ? REAL(sm) : NULL);
+    if (rc != -5) hip_check(rc, "cocoPredict / cocoSim (sparse, krige joint)");
+    SET_VECTOR_ELT(res, 0, Rf_ScalarInteger(rc));
+    UNPROTECT(1);
+    return res;
+}
+
 SEXP _cocons_hip_krige_taper_release(SEXP fitp)
 {
     hip_check(cocons_krige_taper_release(fit_of(fitp)), "cocoPredict (sparse, krige release)");
@@ -985,6 +1031,7 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_krige_release", (DL_FUNC)&_cocons_hip_krige_release, 1},
     {"_cocons_hip_krige_taper_prepare", (DL_FUNC)&_cocons_hip_krige_taper_prepare, 5},
     {"_cocons_hip_krige_taper", (DL_FUNC)&_cocons_hip_krige_taper, 6},
+    {"_cocons_hip_krige_taper_joint", (DL_FUNC)&_cocons_hip_krige_taper_joint, 8},
     {"_cocons_hip_krige_taper_release", (DL_FUNC)&_cocons_hip_krige_taper_release, 1},
     {"_cocons_hip_sim", (DL_FUNC)&_cocons_hip_sim, 5},
     {"_cocons_hip_sim_cond", (DL_FUNC)&_cocons_hip_sim_cond, 8},

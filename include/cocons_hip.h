@@ -176,6 +176,44 @@ int cocons_krige_taper_apply(cocons_fit *fit, int m, const double *locs_pred, co
 int cocons_krige_taper_release(cocons_fit *fit);
 int cocons_krige_taper_info(cocons_fit *fit, long long *out6);
 
+/* Joint prediction for a tapered fit from the held band factor, against the theta, realisation and mean of
+ * cocons_krige_taper_prepare: cocons_krige_joint's outputs for type = "sparse" (the reference's cocoSim has no
+ * conditional branch for sparse objects).
+ *   stochastic[i] = c_i' S^-1 (z - X mean)                (the bits of cocons_krige_taper_apply for the same rows)
+ *   cov  = S_uu - C S^-1 C'                               m x m column-major, full and symmetric to the bit; NULL: not wanted
+ *   sims = L_S E + (X_pred mean + stochastic)             m x nsim, L_S L_S' = cov, E = iiderrors (m x nsim); nsim = 0: no draws
+ * C = pred_taper o cov_rns_taper_pred(theta, ...) exactly as cocons_krige_taper_apply forms it (same CSR contract, same
+ * checks).  S_uu = taper_uu o cov_rns_taper(theta, locs_unobs, X_pred, uu pattern): the objective's entries, variance plus
+ * nugget on the diagonal, the kernel's own coincident-pair rule; locs_unobs = NULL: locs_pred.  The uu pattern is what
+ * spam::nearest.dist(newlocs, delta, upper = NULL) gives: m x m, 1-based CSR, columns strictly increasing within a row,
+ * every row with its diagonal entry.  Only entries with column <= row are read; the upper triangle is their mirror; outside
+ * the pattern S_uu is 0.
+ * All m rows are one chunk.  The solved rows V = C L^-T are never held as m x n: the ring of cocons_krige_taper_apply is
+ * D - 1 slots deeper (min(W + D - 1, nt) slots) and S -= V_g V_g' is accumulated per group of D tile columns while the
+ * window slides.  D: COCONS_KRIGE_JOINT_DEPTH, read per call, 1 .. 16 (default 8); cov does not depend on it to the bit.
+ * Repeats agree bit for bit, and the leading block of cov and the leading entries of stochastic for the first rows of a
+ * request do not depend on the rows behind them.  The draws factor cov on the plain schedule of the dense factorisation.
+ * Device memory: round_up(m, 64) x min(W + D - 1, nt) x 128 + round_up(m, 128)^2 doubles, small arrays and the CSR staging
+ * (28 bytes per pred entry, 12 per uu entry), all released before the call returns; the kriging state is read, never
+ * written.  cocons_krige_taper_joint_bytes: the device bytes the call allocates for (m, nsim) on this handle but the CSR
+ * staging, so that a caller can size m; it takes the same refusals.
+ * Returns 0; -5 when the predictive covariance is not positive definite in floating point (nsim > 0 only; the message names
+ * the failing minor); -1, with a message starting with the entry's name, before any device work and with the outputs
+ * untouched, for m < 1, a null locs_pred, X_pred, stochastic or row pointers, nsim < 0, nsim > 0 with a null iiderrors or
+ * sims, a null, dense or sharded handle, no prepared state, a malformed pattern (the checks of cocons_krige_taper_apply), a
+ * uu row without its diagonal, or a depth outside 1 .. 16; < 0 otherwise (a failed allocation names the bytes needed).
+ * The outputs are written on 0 only.                                                                                       */
+int cocons_krige_taper_joint(cocons_fit *fit, int m, const double *locs_pred, const double *X_pred,
+                             int nnz_pred, const int *colindices_pred, const int *rowpointers_pred,
+                             const double *taper_entries_pred,
+                             const double *locs_unobs,           /* m x 2, NULL = locs_pred */
+                             int nnz_uu, const int *colindices_uu, const int *rowpointers_uu, const double *taper_entries_uu,
+                             double *stochastic,                 /* m */
+                             double *cov,                        /* m x m column-major, may be NULL */
+                             int nsim, const double *iiderrors,  /* m x nsim, nsim = 0: no draws */
+                             double *sims);                      /* m x nsim */
+int cocons_krige_taper_joint_bytes(cocons_fit *fit, int m, int nsim, long long *bytes);
+
 /* Sparse branch of cocoSim (R/sim.R:177-217) on a taper handle.  S = taper o cov_rns_taper(theta) (the handle's pattern
  * and taper entries), ordered by `pivot` (1-based permutation of 1..n, spam's `ordering(cholS)`; NULL = the handle's own
  * order, see cocons_fit_taper_order).  With L_P L_P' = S[pivot, pivot] and E = iiderrors (n x nsim, column-major, used
