@@ -1,5 +1,8 @@
-// api_predict.hip -- C ABI, what is made of a factor: prediction and kriging (dense and taper), joint prediction from the
-// held factor, the marginal and conditional simulations, cocons_chol_solve.
+// api_predict.hip -- C ABI, what is made of a factor: the one-shot predictions (cocons_predict_dense / _taper), kriging from a
+// held factor -- prepare, apply in chunks and joint prediction (predictive covariance and draws), for dense handles and for the
+// band factor of tapered fits, over one set of shared helpers (KrigeHeld's allocation, krige_chunks, the argument builders,
+// krige_joint_tail; the bucket sort of a chunk's entries is band_plan.hpp's) --, the marginal and conditional simulations,
+// cocons_chol_solve.
 #include "fit.hpp"
 
 // row row0 of out: the residual z[:, z_col] - X mean over the columns [0, ncols), then nrows_zero rows cleared.  out is in
@@ -58,21 +61,22 @@ extern "C" int cocons_predict_dense(cocons_fit *f, const double *theta, const do
                                     int m, const double *locs_pred, const double *X_pred,
                                     double *stochastic, double *quadform)
 {
+    const char *who = "cocons_predict_dense";
     FIT_ENTER(f);
-    if (int rc = no_taper(f, "cocons_predict_dense")) return rc;
+    if (int rc = no_taper(f, who)) return rc;
     if (!theta || !mean || m <= 0 || !locs_pred || !X_pred || !stochastic || !quadform || z_col < 0 || z_col >= f->r)
-        return fail(-1, "cocons_predict_dense: bad argument");
+        return fail(-1, "%s: bad argument", who);
     const int p = f->p, n = f->n;
     if (int rc = pred_reserve(f, m)) return rc;
     if (int rc = fit_alloc_matrix(f, m + 1)) return rc;
     hipStream_t s = f->stream;
-    HIPCHK_AT("cocons_predict_dense", upload_canon(f->dXp, X_pred, (size_t)m * p, s));
-    HIPCHK_AT("cocons_predict_dense", upload_canon(f->dlocsp, locs_pred, (size_t)m * 2, s));
+    HIPCHK_AT(who, upload_canon(f->dXp, X_pred, (size_t)m * p, s));
+    HIPCHK_AT(who, upload_canon(f->dlocsp, locs_pred, (size_t)m * 2, s));
     ThetaVecs tv;
     make_theta_vecs(theta, p, tv);
     const ModeSel ms = select_mode(theta, p, f->smooth_limits, 2);
     const ModeSel ms0 = select_mode(theta, p, f->smooth_limits, 0);
-    return run_op(f, "cocons_predict_dense", [&]() -> int {
+    return run_op(f, who, [&]() -> int {
         assemble_sigma(f, theta, 0, 0, f->npad);
         // row npad: residual of realization z_col (also clears padding rows and columns >= n); rows npad+1 .. npad+m:
         // cross-covariance
@@ -96,8 +100,8 @@ extern "C" int cocons_predict_dense(cocons_fit *f, const double *theta, const do
         if (int rc = factorize(f, pv, nullptr)) return rc;
         launch_row_reduce(f->dA, f->lda, n, f->npad, f->npad + 1, m, f->dstoch, f->dquad, f->dred, s, 0, 0,
                           f->dag_used ? f->dP : nullptr, f->dag_used ? 2 * TILE * f->dag_nsteps : 0);
-        HIPCHK_AT("cocons_predict_dense", hipMemcpyAsync(stochastic, f->dstoch, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK_AT("cocons_predict_dense", hipMemcpyAsync(quadform, f->dquad, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT(who, hipMemcpyAsync(stochastic, f->dstoch, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT(who, hipMemcpyAsync(quadform, f->dquad, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
         return 0;
     });
 }
@@ -107,19 +111,109 @@ extern "C" int cocons_predict_dense(cocons_fit *f, const double *theta, const do
 // side) and keeps the factor in the handle's KrigeState; cocons_krige_apply then predicts any number of new locations in
 // chunks of `rows` against it -- cross-covariance chunk (pair_rect), V = C L^-T with both reductions fused
 // (launch_krige_solve) -- with device memory independent of m.  Outputs as cocons_predict_dense's.
+// What these entries share with the tapered ones further down stands here once, over KrigeHeld (fit.hpp: what both states hold).
 static constexpr size_t KRIGE_CHUNK_BYTES = (size_t)1 << 30;      // max_rows = 0: the chunk buffers stay within 1 GiB
 static constexpr int KRIGE_ROWS_CAP = 16384;                       // ... and within 16384 rows
 
-static size_t krige_row_bytes(const cocons_fit *f)
+// bytes of one chunk row: `wide` doubles in the state's own chunk buffer (C: npad, the ring: W * 128), then Xp, lp, locp, st, qd
+static size_t krige_row_bytes(const cocons_fit *f, size_t wide) { return (wide + (size_t)f->p + 2 + LOCP_FIELDS + 2) * sizeof(double); }
+
+// rows per chunk: a caller's max_rows, cut at user_cap where the entry has one (0: none), or what the two limits above
+// leave; whole 64-row strips (a row's position in its strip never depends on the split), one at least
+static int krige_rows(int max_rows, size_t row_bytes, size_t user_cap)
 {
-    return ((size_t)f->npad + (size_t)f->p + 2 + LOCP_FIELDS + 2) * sizeof(double);     // C, Xp, lp, locp, st, qd
+    size_t r = max_rows > 0 ? (size_t)max_rows : std::min<size_t>(KRIGE_CHUNK_BYTES / row_bytes, KRIGE_ROWS_CAP);
+    if (max_rows > 0 && user_cap) r = std::min(r, user_cap);
+    return (int)std::max<size_t>(r / 64 * 64, 64);
 }
 
-static int krige_rows(const cocons_fit *f, int max_rows)
+// theta and mean canonicalised into the state, and KrigeHeld's buffers for a factor of ntile packed tiles and chunks of K->rows
+// rows; *bytes: those buffers' and, at row_bytes a row, the chunk buffer's of the state itself, which the caller allocates
+static int krige_held_alloc(const cocons_fit *f, const char *who, KrigeHeld *K, const double *theta, const double *mean, size_t ntile,
+                            size_t row_bytes, long long *bytes)
 {
-    size_t r = max_rows > 0 ? (size_t)max_rows : std::min<size_t>(KRIGE_CHUNK_BYTES / krige_row_bytes(f), KRIGE_ROWS_CAP);
-    r = r / 64 * 64;                    // chunks of whole 64-row strips: a row's position in its strip never depends on the split
-    return (int)std::max<size_t>(r, 64);
+    const int p = f->p;
+    const size_t R = (size_t)K->rows, nt = (size_t)f->nt, npad = (size_t)f->npad;
+    K->theta.resize((size_t)6 * p);
+    for (int i = 0; i < 6 * p; ++i) K->theta[i] = canon_nan(theta[i]);
+    K->mean.resize((size_t)p);
+    for (int i = 0; i < p; ++i) K->mean[i] = canon_nan(mean[i]);
+    HIPCHK_AT(who, K->L.alloc(ntile * TILE * TILE));
+    HIPCHK_AT(who, K->Q.alloc(nt * 2048));
+    HIPCHK_AT(who, K->w.alloc(npad));
+    HIPCHK_AT(who, K->loc.alloc(LOCP_FIELDS * npad));
+    HIPCHK_AT(who, K->Xp.alloc(R * p));
+    HIPCHK_AT(who, K->lp.alloc(R * 2));
+    HIPCHK_AT(who, K->locp.alloc(R * LOCP_FIELDS));
+    HIPCHK_AT(who, K->st.alloc(R));
+    HIPCHK_AT(who, K->qd.alloc(R));
+    *bytes = (long long)((ntile * TILE * TILE + nt * 2048 + npad * (1 + LOCP_FIELDS)) * sizeof(double) + R * row_bytes);
+    return 0;
+}
+
+// the end of a prepare, behind the factor's pack launch: the observation-side SoA in the prediction branch's smoothness
+// (always logistic + sqrt, see cocons_predict_dense) -- full_scale: with the FULL scale vector, as cocons_cov_rns_taper_pred
+// prepares it --, and the stream drained
+static int krige_prepare_finish(cocons_fit *f, const char *who, KrigeHeld *K, bool full_scale)
+{
+    const double *th = K->theta.data();
+    ThetaVecs tv;
+    make_theta_vecs(th, f->p, tv, full_scale);
+    const ModeSel ms = select_mode(th, f->p, f->smooth_limits, 2);
+    launch_loc_params(loc_args(f->n, f->p, f->dX, f->dlocs, K->loc, f->npad, tv, ms.smooth_kind, f->smooth_limits), f->stream);
+    HIPCHK_AT(who, hipGetLastError());
+    HIPCHK_AT(who, hipStreamSynchronize(f->stream));
+    return 0;
+}
+
+static int krige_no_state(const char *who, const char *prepare)
+{
+    return fail(-1, "%s: no kriging state on this handle (call %s first)", who, prepare);
+}
+
+// The chunk loop of an apply call: rows [b, b + mc) of the caller's column-major X_pred (m x p) and locs_pred (m x 2) into the
+// state's staging, their SoA in the prediction branch's parameters (full_scale: as krige_prepare_finish), body(b, mc, global
+// range) -- the entry's own launches, which leave the chunk's outputs in K->st and K->qd --, those to the caller's rows, and
+// the stream drained before the staging, the host's and the state's, is used again.  before(b, mc) comes first: the entry's
+// host work on the chunk and its own uploads, so that every copy of a chunk goes ahead of its first launch, in one burst.
+template <class Before, class Body>
+static int krige_chunks(cocons_fit *f, KrigeHeld *K, const char *who, bool full_scale, int m, const double *locs_pred,
+                        const double *X_pred, double *stochastic, double *quadform, Before &&before, Body &&body)
+{
+    const int p = f->p, rows = K->rows;
+    ThetaVecs tv;
+    make_theta_vecs(K->theta.data(), p, tv, full_scale);
+    const ModeSel ms = select_mode(K->theta.data(), p, f->smooth_limits, 2);
+    std::vector<double> hX((size_t)rows * p), hl((size_t)rows * 2);
+    StreamDrain s{f->stream, false};
+    for (int b = 0; b < m; b += rows) {
+        const int mc = std::min(rows, m - b);
+        for (int j = 0; j < p; ++j) memcpy(&hX[(size_t)j * mc], X_pred + b + (size_t)j * m, (size_t)mc * sizeof(double));
+        for (int j = 0; j < 2; ++j) memcpy(&hl[(size_t)j * mc], locs_pred + b + (size_t)j * m, (size_t)mc * sizeof(double));
+        if (int rc = before(b, mc)) return rc;
+        HIPCHK_AT(who, upload_canon(K->Xp, hX.data(), (size_t)mc * p, s));
+        HIPCHK_AT(who, upload_canon(K->lp, hl.data(), (size_t)mc * 2, s));
+        launch_loc_params(loc_args(mc, p, K->Xp, K->lp, K->locp, rows, tv, ms.smooth_kind, f->smooth_limits), s);
+        if (int rc = body(b, mc, ms.gr)) return rc;
+        HIPCHK_AT(who, hipMemcpyAsync(stochastic + b, K->st, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT(who, hipMemcpyAsync(quadform + b, K->qd, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT(who, hipGetLastError());
+        HIPCHK_AT(who, hipStreamSynchronize(s));
+    }
+    return 0;
+}
+
+// the cross-covariance of m new locations (their SoA in `rows`, stride ld) with the caller's observations only -- columns
+// [pad0, n) in the handle's order -- into those columns of V (m x npad, leading dimension ld)
+static PairArgs krige_cross_args(const cocons_fit *f, const KrigeHeld *K, int m, const double *rows, double *V, size_t ld, double gr)
+{
+    PairArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.n = f->n_user; pa.m = m; pa.rows = rows; pa.stride_rows = ld;
+    pa.cols = K->loc + f->pad0; pa.stride = f->npad;
+    pa.out = V + (size_t)f->pad0 * ld; pa.ld = ld; pa.nrows_out = m; pa.ncols_out = f->n_user;
+    pa.gr = gr; pa.nu_fixed = 0.0;
+    return pa;
 }
 
 static int krige_sharded(cocons_fit *f, const char *who)
@@ -130,38 +224,26 @@ static int krige_sharded(cocons_fit *f, const char *who)
 
 extern "C" int cocons_krige_prepare(cocons_fit *f, const double *theta, const double *mean, int z_col, int max_rows)
 {
-    if (!f) return fail(-1, "cocons_krige_prepare: null fit handle");
+    const char *who = "cocons_krige_prepare";
+    if (!f) return fail(-1, "%s: null fit handle", who);
     FIT_ENTER(f);
-    if (int rc = no_taper(f, "cocons_krige_prepare")) return rc;
-    if (int rc = krige_sharded(f, "cocons_krige_prepare")) return rc;
-    if (!theta || !mean || z_col < 0 || z_col >= f->r || max_rows < 0) return fail(-1, "cocons_krige_prepare: bad argument");
+    if (int rc = no_taper(f, who)) return rc;
+    if (int rc = krige_sharded(f, who)) return rc;
+    if (!theta || !mean || z_col < 0 || z_col >= f->r || max_rows < 0) return fail(-1, "%s: bad argument", who);
     f->krige.reset();                   // replaced -- and gone if this prepare fails
-    const int p = f->p, n = f->n, npad = f->npad, nt = f->nt;
+    const int n = f->n, npad = f->npad, nt = f->nt;
     std::unique_ptr<KrigeState> K(new KrigeState());
-    K->rows = krige_rows(f, max_rows);
-    K->theta.resize((size_t)6 * p);
-    for (int i = 0; i < 6 * p; ++i) K->theta[i] = canon_nan(theta[i]);
-    K->mean.resize((size_t)p);
-    for (int i = 0; i < p; ++i) K->mean[i] = canon_nan(mean[i]);
-    const size_t R = (size_t)K->rows, ntile = (size_t)nt * (nt + 1) / 2;
+    const size_t row_bytes = krige_row_bytes(f, (size_t)npad), ntile = (size_t)nt * (nt + 1) / 2;
+    K->rows = krige_rows(max_rows, row_bytes, 0);
+    const size_t R = (size_t)K->rows;
     StreamDrain s{f->stream, false};
-    HIPCHK_AT("cocons_krige_prepare", K->L.alloc(ntile * TILE * TILE));
-    HIPCHK_AT("cocons_krige_prepare", K->Q.alloc((size_t)nt * 2048));
-    HIPCHK_AT("cocons_krige_prepare", K->w.alloc((size_t)npad));
-    HIPCHK_AT("cocons_krige_prepare", K->loc.alloc((size_t)LOCP_FIELDS * npad));
-    HIPCHK_AT("cocons_krige_prepare", K->C.alloc(R * npad));
-    HIPCHK_AT("cocons_krige_prepare", K->Xp.alloc(R * p));
-    HIPCHK_AT("cocons_krige_prepare", K->lp.alloc(R * 2));
-    HIPCHK_AT("cocons_krige_prepare", K->locp.alloc(R * LOCP_FIELDS));
-    HIPCHK_AT("cocons_krige_prepare", K->st.alloc(R));
-    HIPCHK_AT("cocons_krige_prepare", K->qd.alloc(R));
-    K->bytes = (long long)((ntile * TILE * TILE + (size_t)nt * 2048 + (size_t)npad * (1 + LOCP_FIELDS)) * sizeof(double) +
-                           R * krige_row_bytes(f));
+    if (int rc = krige_held_alloc(f, who, K.get(), theta, mean, ntile, row_bytes, &K->bytes)) return rc;
+    HIPCHK_AT(who, K->C.alloc(R * npad));
     // the padding and slot columns of a chunk are never written by the assembly: zero once
-    HIPCHK_AT("cocons_krige_prepare", hipMemsetAsync(K->C, 0, R * npad * sizeof(double), s));
+    HIPCHK_AT(who, hipMemsetAsync(K->C, 0, R * npad * sizeof(double), s));
     const double *th = K->theta.data();
     if (int rc = fit_alloc_matrix(f, 1)) return rc;
-    const int st = run_op(f, "cocons_krige_prepare", [&]() -> int {
+    const int st = run_op(f, who, [&]() -> int {
         f->nrhs_cur = 1;
         assemble_sigma(f, th, 0, 0, npad);
         // row npad: residual of realization z_col (the rows under it and the columns >= n cleared)
@@ -172,13 +254,7 @@ extern "C" int cocons_krige_prepare(cocons_fit *f, const double *theta, const do
         return 0;
     });
     if (st) return st;                  // failing minor: no state (K's buffers are freed on the way out)
-    // observation-side SoA in the smoothness of cov_rns_pred (always logistic + sqrt, see cocons_predict_dense)
-    ThetaVecs tv;
-    make_theta_vecs(th, p, tv);
-    const ModeSel ms = select_mode(th, p, f->smooth_limits, 2);
-    launch_loc_params(loc_args(n, p, f->dX, f->dlocs, K->loc, npad, tv, ms.smooth_kind, f->smooth_limits), s);
-    HIPCHK_AT("cocons_krige_prepare", hipGetLastError());
-    HIPCHK_AT("cocons_krige_prepare", hipStreamSynchronize(s));
+    if (int rc = krige_prepare_finish(f, who, K.get(), false)) return rc;
     f->krige = std::move(K);
     return 0;
 }
@@ -186,44 +262,22 @@ extern "C" int cocons_krige_prepare(cocons_fit *f, const double *theta, const do
 extern "C" int cocons_krige_apply(cocons_fit *f, int m, const double *locs_pred, const double *X_pred,
                                   double *stochastic, double *quadform)
 {
+    const char *who = "cocons_krige_apply";
     if (m < 0 || (m > 0 && (!locs_pred || !X_pred || !stochastic || !quadform)))
-        return fail(-1, "cocons_krige_apply: bad argument (m < 0 or a null pointer)");
-    if (!f) return fail(-1, "cocons_krige_apply: null fit handle");
+        return fail(-1, "%s: bad argument (m < 0 or a null pointer)", who);
+    if (!f) return fail(-1, "%s: null fit handle", who);
     FIT_ENTER(f);
-    if (int rc = no_taper(f, "cocons_krige_apply")) return rc;
-    if (int rc = krige_sharded(f, "cocons_krige_apply")) return rc;
+    if (int rc = no_taper(f, who)) return rc;
+    if (int rc = krige_sharded(f, who)) return rc;
     KrigeState *K = f->krige.get();
-    if (!K) return fail(-1, "cocons_krige_apply: no kriging state on this handle (call cocons_krige_prepare first)");
-    const int p = f->p, rows = K->rows;
-    const double *th = K->theta.data();
-    ThetaVecs tv;
-    make_theta_vecs(th, p, tv);
-    const ModeSel ms = select_mode(th, p, f->smooth_limits, 2);
-    std::vector<double> hX((size_t)rows * p), hl((size_t)rows * 2);
-    StreamDrain s{f->stream, false};
-    for (int b = 0; b < m; b += rows) {
-        const int mc = std::min(rows, m - b);
-        // the chunk's rows of the caller's column-major m x p and m x 2 (drained below before the staging is reused)
-        for (int j = 0; j < p; ++j) memcpy(&hX[(size_t)j * mc], X_pred + b + (size_t)j * m, (size_t)mc * sizeof(double));
-        for (int j = 0; j < 2; ++j) memcpy(&hl[(size_t)j * mc], locs_pred + b + (size_t)j * m, (size_t)mc * sizeof(double));
-        HIPCHK_AT("cocons_krige_apply", upload_canon(K->Xp, hX.data(), (size_t)mc * p, s));
-        HIPCHK_AT("cocons_krige_apply", upload_canon(K->lp, hl.data(), (size_t)mc * 2, s));
-        launch_loc_params(loc_args(mc, p, K->Xp, K->lp, K->locp, rows, tv, ms.smooth_kind, f->smooth_limits), s);
-        // cross-covariance of the chunk with the caller's observations only: columns [pad0, n) in the handle's order
-        PairArgs pa;
-        memset(&pa, 0, sizeof pa);
-        pa.n = f->n_user; pa.m = mc; pa.rows = K->locp; pa.stride_rows = rows;
-        pa.cols = K->loc + f->pad0; pa.stride = f->npad;
-        pa.out = K->C + (size_t)f->pad0 * rows; pa.ld = rows; pa.nrows_out = mc; pa.ncols_out = f->n_user;
-        pa.gr = ms.gr; pa.nu_fixed = 0.0;
-        launch_pair_rect(MODE_GEOM, pa, s);
-        launch_krige_solve(K->L, K->Q, K->w, f->nt, K->C, rows, mc, f->pad0, f->n, K->st, K->qd, s);
-        HIPCHK_AT("cocons_krige_apply", hipMemcpyAsync(stochastic + b, K->st, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK_AT("cocons_krige_apply", hipMemcpyAsync(quadform + b, K->qd, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK_AT("cocons_krige_apply", hipGetLastError());
-        HIPCHK_AT("cocons_krige_apply", hipStreamSynchronize(s));
-    }
-    return 0;
+    if (!K) return krige_no_state(who, "cocons_krige_prepare");
+    hipStream_t s = f->stream;
+    auto solve = [&](int, int mc, double gr) -> int {
+        launch_pair_rect(MODE_GEOM, krige_cross_args(f, K, mc, K->locp, K->C, (size_t)K->rows, gr), s);
+        launch_krige_solve(K->L, K->Q, K->w, f->nt, K->C, K->rows, mc, f->pad0, f->n, K->st, K->qd, s);
+        return 0;
+    };
+    return krige_chunks(f, K, who, false, m, locs_pred, X_pred, stochastic, quadform, [](int, int) { return 0; }, solve);
 }
 
 extern "C" int cocons_krige_release(cocons_fit *f)
@@ -248,14 +302,104 @@ extern "C" int cocons_krige_info(cocons_fit *f, long long *out4)
     return 0;
 }
 
+// mu[i] = X_pred[i, ] mean + stv[i]: tmp_mu of the conditional draws on the host, X_pred column-major m x p (this loop order
+// and this order of summation: the draws' bits depend on them)
+static void add_trend_to(double *mu, const double *X_pred, int m, int p, const double *mean, const double *stv)
+{
+    for (int i = 0; i < m; ++i) {
+        double sys = 0;
+        for (int j = 0; j < p; ++j) sys += X_pred[(size_t)i + (size_t)j * m] * mean[j];
+        mu[i] = sys + stv[i];
+    }
+}
+
+// doubles of the twelve buffers both joint entries allocate, in their order: `first` (V, or the ring) | S | Xp, lp, lu |
+// locp, locu | st, q | E, Y | mu.  None is zero.
+static void krige_joint_counts(const cocons_fit *f, int m, int nsim, size_t first, size_t counts[12])
+{
+    const size_t mv = (size_t)round_up(m, 64), mpad = (size_t)round_up(m, TILE), ne = (size_t)m * (size_t)nsim;
+    const size_t c[12] = {first, mpad * mpad, (size_t)m * f->p, (size_t)m * 2, (size_t)m * 2, (size_t)LOCP_FIELDS * mv,
+                          (size_t)LOCP_FIELDS * mpad, mv, mv, ne ? ne : 1, ne ? ne : 1, (size_t)m};
+    memcpy(counts, c, sizeof c);
+}
+
+// One joint call as krige_joint_tail takes it: the view S (round_up(m, 128) rows and columns, leading dimension lds), the
+// solve's stochastic in dst, the uploaded draws dE, room for the fields and their mean, and the caller's outputs.
+struct KrigeJointCall {
+    const char *who; int m, nsim; size_t lds;
+    double *dS, *dst, *dE, *dY, *dmu;
+    const double *X_pred, *mean;
+    double *stochastic, *cov, *sims;
+    bool plain;                      // the view is factored under PlainSchedule (a band handle: DESIGN.md 4p)
+};
+
+// What both joint entries do once head() has enqueued everything up to the mirrored predictive covariance in S: stochastic and
+// cov home; with draws, tmp_mu on the host, the factorisation of the view -- it does not start with the handle's observations
+// (FoldView), and the schedules with dag_ok = false leave the factor whole in it: no second buffer -- and sims = L_S E + tmp_mu.
+// Without draws nothing is factored: no info words, nothing to repeat.  The caller's outputs are written only once the whole
+// call has succeeded (cov through a staging copy).  The host ends of the copies are locals here: hence the drain of its own.
+template <class Head> static int krige_joint_tail(cocons_fit *f, const KrigeJointCall &c, Head &&head)
+{
+    const char *who = c.who;
+    const int m = c.m, nsim = c.nsim;
+    const size_t ne = (size_t)m * (size_t)nsim;
+    std::vector<double> stv((size_t)m), mu((size_t)m), hY(ne), hcov;
+    if (c.cov && nsim > 0) hcov.resize((size_t)m * m);
+    double *cov_to = hcov.empty() ? c.cov : hcov.data();
+    int raw = 0x7f7f7f7f;                                // the view's own info word (minors counted from the view's first column)
+    StreamDrain s{f->stream, false};
+    auto enqueue = [&]() -> int {
+        if (int rc = head()) return rc;
+        HIPCHK_AT(who, hipMemcpyAsync(stv.data(), c.dst, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (c.cov)
+            HIPCHK_AT(who, hipMemcpy2DAsync(cov_to, (size_t)m * sizeof(double), c.dS, c.lds * sizeof(double), (size_t)m * sizeof(double),
+                                            (size_t)m, hipMemcpyDeviceToHost, s));
+        if (nsim == 0) return 0;
+        HIPCHK_AT(who, hipStreamSynchronize(s));
+        add_trend_to(mu.data(), c.X_pred, m, f->p, c.mean, stv.data());
+        HIPCHK_AT(who, upload_canon(c.dmu, mu.data(), (size_t)m, s));
+        {
+            // a dense view of the call, maybe of more tiles than the handle's nt: factorize() sizes the hand-off words and the
+            // mailboxes by the view (flags_reset, mbox_reset), dinv and dinfo do not depend on the order
+            std::unique_ptr<PlainSchedule> plain(c.plain ? new PlainSchedule(f) : nullptr);
+            FoldView fv(f);
+            FactorView v;
+            v.A = c.dS; v.lda = c.lds; v.nt = (int)(c.lds / TILE); v.mt = v.nt;
+            if (int rc = factorize(f, v, nullptr)) return rc;
+        }
+        HIPCHK_AT(who, hipMemcpyAsync(&raw, f->dinfo, sizeof(int), hipMemcpyDeviceToHost, s));
+        launch_trmm_lower(c.dS, c.lds, m, c.dE, m, nsim, c.dmu, c.dY, m, s);
+        HIPCHK_AT(who, hipMemcpyAsync(hY.data(), c.dY, ne * sizeof(double), hipMemcpyDeviceToHost, s));
+        return 0;
+    };
+    if (nsim == 0) {
+        if (int rc = enqueue()) return rc;
+        HIPCHK_AT(who, hipGetLastError());
+        HIPCHK_AT(who, hipStreamSynchronize(s));
+    } else {
+        f->nrhs_cur = 0;
+        const int st = run_op(f, who, enqueue);
+        if (st > 0)
+            return fail(-5, "%s: the predictive covariance is not positive definite (leading minor %d of %d not positive)", who,
+                        raw, m);
+        if (st < 0) {
+            const std::string why = g_err;
+            return why.compare(0, strlen(who), who) == 0 ? st : fail(st, "%s: %s", who, why.c_str());
+        }
+        memcpy(c.sims, hY.data(), ne * sizeof(double));
+        if (!hcov.empty()) memcpy(c.cov, hcov.data(), hcov.size() * sizeof(double));
+    }
+    memcpy(c.stochastic, stv.data(), (size_t)m * sizeof(double));
+    return 0;
+}
+
 // Joint prediction from the held factor: the predictive covariance between the new locations and conditional draws,
 //   cov  = Sigma_uu - C Sigma^-1 C'                 (R/predict.R:136-183 gives its diagonal only)
 //   sims = L_S E + (X_pred mean + stochastic),  L_S L_S' = cov        (R/sim.R:84-127, cocons_sim_cond_dense's output)
 // against the theta, realisation and mean of cocons_krige_prepare.  With V = C L^-T as launch_krige_solve leaves it in a
 // buffer of the call, cov = Sigma_uu - V V': one symmetric product on the fp64 MFMA (launch_krige_schur) into a view of
 // the call that holds Sigma_uu (cov_rns semantics at locs_unobs, as cocons_sim_cond_dense's block), mirrored to the bit;
-// the draws then cost a factorisation of m, not of n + m.  The view does not start with the handle's observations
-// (FoldView), and it is factored on the schedules that leave the factor whole in it (dag_ok = false): no second buffer.
+// the draws then cost a factorisation of m, not of n + m (krige_joint_tail).
 // Device memory of the call: round_up(m, 64) x npad + round_up(m, 128)^2 doubles and the small arrays, all released on return.
 extern "C" int cocons_krige_joint(cocons_fit *f, int m, const double *locs_pred, const double *X_pred, const double *locs_unobs,
                                   double *stochastic, double *cov, int nsim, const double *iiderrors, double *sims)
@@ -270,26 +414,21 @@ extern "C" int cocons_krige_joint(cocons_fit *f, int m, const double *locs_pred,
     if (int rc = no_taper(f, who)) return rc;
     if (int rc = krige_sharded(f, who)) return rc;
     const KrigeState *K = f->krige.get();
-    if (!K) return fail(-1, "%s: no kriging state on this handle (call cocons_krige_prepare first)", who);
+    if (!K) return krige_no_state(who, "cocons_krige_prepare");
     const int p = f->p, npad = f->npad, pad0 = f->pad0;
     if (m > INT_MAX - TILE) return fail(-1, "%s: m = %d is too large", who, m);
     const int mv = round_up(m, 64), mpad = round_up(m, TILE);
     const size_t ldv = (size_t)mv, lds = (size_t)mpad, ne = (size_t)m * (size_t)nsim;
     const double *lu = locs_unobs ? locs_unobs : locs_pred;
     const double *th = K->theta.data();
-    std::vector<double> stv((size_t)m), mu((size_t)m), hY(ne), hcov;
-    if (cov && nsim > 0) hcov.resize((size_t)m * m);     // the factorisation may still fail: cov goes home through a staging copy
-    double *cov_to = hcov.empty() ? cov : hcov.data();
-    int raw = 0x7f7f7f7f;                                // the view's own info word (minors counted from the view's first column)
     DevBuf<double> dV, dS, dXp, dlp, dlu, dlocp, dlocu, dst, dq, dE, dY, dmu;
     StreamDrain s{f->stream, false};
     {
-        const size_t counts[12] = {ldv * npad, lds * mpad, (size_t)m * p, (size_t)m * 2, (size_t)m * 2, (size_t)LOCP_FIELDS * mv,
-                                   (size_t)LOCP_FIELDS * mpad, ldv, ldv, ne ? ne : 1, ne ? ne : 1, (size_t)m};
+        size_t counts[12], total = 0;
+        krige_joint_counts(f, m, nsim, ldv * npad, counts);
         DevBuf<double> *bufs[12] = {&dV, &dS, &dXp, &dlp, &dlu, &dlocp, &dlocu, &dst, &dq, &dE, &dY, &dmu};
-        size_t total = 0;
         for (int k = 0; k < 12; ++k) total += counts[k];
-        if (hipError_t e = alloc_call_buffers(bufs, counts, 12))      // (none of the counts is zero)
+        if (hipError_t e = alloc_call_buffers(bufs, counts, 12))
             return fail(-100 - (int)e, "%s: the device cannot hold the %zu bytes of the call (m = %d new locations, n = %d): %s",
                         who, total * sizeof(double), m, f->n_user, hipGetErrorString(e));
     }
@@ -303,68 +442,22 @@ extern "C" int cocons_krige_joint(cocons_fit *f, int m, const double *locs_pred,
     make_theta_vecs(th, p, tv);
     const ModeSel ms0 = select_mode(th, p, f->smooth_limits, 0);   // cov_rns semantics (Sigma_uu)
     const ModeSel msp = select_mode(th, p, f->smooth_limits, 2);   // cov_rns_pred semantics (C)
-    auto enqueue = [&]() -> int {
+    const KrigeJointCall call = {who, m, nsim, lds, dS, dst, dE, dY, dmu, X_pred, K->mean.data(), stochastic, cov, sims, false};
+    return krige_joint_tail(f, call, [&]() -> int {
         launch_loc_params(loc_args(m, p, dXp, dlp, dlocp, ldv, tv, msp.smooth_kind, f->smooth_limits), s);
         launch_loc_params(loc_args(m, p, dXp, dlu, dlocu, lds, tv, ms0.smooth_kind, f->smooth_limits), s);
-        PairArgs pa;
-        // C: the new locations against the caller's observations, columns [pad0, n) in the handle's order (cocons_krige_apply)
-        memset(&pa, 0, sizeof pa);
-        pa.n = f->n_user; pa.m = m; pa.rows = dlocp; pa.stride_rows = ldv;
-        pa.cols = K->loc + pad0; pa.stride = npad;
-        pa.out = dV + (size_t)pad0 * ldv; pa.ld = ldv; pa.nrows_out = m; pa.ncols_out = f->n_user;
-        pa.gr = msp.gr; pa.nu_fixed = 0.0;
-        launch_pair_rect(MODE_GEOM, pa, s);
+        launch_pair_rect(MODE_GEOM, krige_cross_args(f, K, m, dlocp, dV, ldv, msp.gr), s);
         launch_krige_solve(K->L, K->Q, K->w, f->nt, dV, ldv, m, pad0, f->n, dst, dq, s);
         // Sigma_uu, identity in the rows and columns [m, mpad)
+        PairArgs pa;
         memset(&pa, 0, sizeof pa);
         pa.n = m; pa.m = m; pa.rows = dlocu; pa.cols = dlocu; pa.stride = lds; pa.stride_rows = lds;
         pa.out = dS; pa.ld = lds; pa.nrows_out = mpad; pa.ncols_out = mpad; pa.gr = ms0.gr; pa.nu_fixed = ms0.nu_fixed;
         launch_pair_sym(ms0.mode, false, pa, s);
         launch_krige_schur(dV, ldv, m, pad0, f->n, npad, dS, lds, s);
         launch_sym_mirror(dS, lds, m, s);
-        HIPCHK_AT(who, hipMemcpyAsync(stv.data(), dst, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (cov)
-            HIPCHK_AT(who, hipMemcpy2DAsync(cov_to, (size_t)m * sizeof(double), dS, lds * sizeof(double), (size_t)m * sizeof(double),
-                                            (size_t)m, hipMemcpyDeviceToHost, s));
-        if (nsim == 0) return 0;
-        // tmp_mu = X_pred mean + stochastic on the host, as cocons_sim_cond_dense forms it
-        HIPCHK_AT(who, hipStreamSynchronize(s));
-        for (int i = 0; i < m; ++i) {
-            double sys = 0;
-            for (int j = 0; j < p; ++j) sys += X_pred[(size_t)i + (size_t)j * m] * K->mean[j];
-            mu[i] = sys + stv[i];
-        }
-        HIPCHK_AT(who, upload_canon(dmu, mu.data(), (size_t)m, s));
-        {
-            FoldView fv(f);
-            FactorView v;
-            v.A = dS; v.lda = lds; v.nt = mpad / TILE; v.mt = mpad / TILE;
-            if (int rc = factorize(f, v, nullptr)) return rc;
-        }
-        HIPCHK_AT(who, hipMemcpyAsync(&raw, f->dinfo, sizeof(int), hipMemcpyDeviceToHost, s));
-        launch_trmm_lower(dS, lds, m, dE, m, nsim, dmu, dY, m, s);
-        HIPCHK_AT(who, hipMemcpyAsync(hY.data(), dY, ne * sizeof(double), hipMemcpyDeviceToHost, s));
         return 0;
-    };
-    if (nsim == 0) {                    // nothing is factored: no info words, nothing to repeat
-        if (int rc = enqueue()) return rc;
-        HIPCHK_AT(who, hipGetLastError());
-        HIPCHK_AT(who, hipStreamSynchronize(s));
-    } else {
-        f->nrhs_cur = 0;
-        const int st = run_op(f, who, enqueue);
-        if (st > 0)
-            return fail(-5, "%s: the predictive covariance is not positive definite (leading minor %d of %d not positive)", who,
-                        raw, m);
-        if (st < 0) {
-            const std::string why = g_err;
-            return why.compare(0, strlen(who), who) == 0 ? st : fail(st, "%s: %s", who, why.c_str());
-        }
-        memcpy(sims, hY.data(), ne * sizeof(double));
-        if (!hcov.empty()) memcpy(cov, hcov.data(), hcov.size() * sizeof(double));
-    }
-    memcpy(stochastic, stv.data(), (size_t)m * sizeof(double));
-    return 0;
+    });
 }
 
 // Kriging core of the sparse branch of cocoPredict (R/predict.R:216-283) on a taper handle: S = taper o
@@ -376,39 +469,40 @@ extern "C" int cocons_predict_taper(cocons_fit *f, const double *theta, const do
                                     const int *colindices_pred, const int *rowpointers_pred,
                                     const double *taper_entries_pred, double *stochastic, double *quadform)
 {
+    const char *who = "cocons_predict_taper";
     FIT_ENTER(f);
-    if (f->taper_nnz <= 0) return fail(-1, "cocons_predict_taper: not a taper fit");
+    if (f->taper_nnz <= 0) return fail(-1, "%s: not a taper fit", who);
     if (!theta || !mean || m <= 0 || !locs_pred || !X_pred || !stochastic || !quadform || z_col < 0 || z_col >= f->r ||
         nnz_pred < 0 || !rowpointers_pred || (nnz_pred > 0 && (!colindices_pred || !taper_entries_pred)))
-        return fail(-1, "cocons_predict_taper: bad argument");
+        return fail(-1, "%s: bad argument", who);
     const int p = f->p, n = f->n;
     if (rowpointers_pred[0] != 1 || rowpointers_pred[m] != nnz_pred + 1)
-        return fail(-1, "cocons_predict_taper: rowpointers do not match nnz (1-based CSR expected)");
+        return fail(-1, "%s: rowpointers do not match nnz (1-based CSR expected)", who);
     for (int w = 0; w < nnz_pred; ++w)
-        if (colindices_pred[w] < 1 || colindices_pred[w] > n) return fail(-1, "cocons_predict_taper: column index out of range");
+        if (colindices_pred[w] < 1 || colindices_pred[w] > n) return fail(-1, "%s: column index out of range", who);
     if (int rc = pred_reserve(f, m)) return rc;
     if (int rc = fit_alloc_matrix(f, m + 1)) return rc;
     const size_t nz = nnz_pred > 0 ? (size_t)nnz_pred : 1;
     DevBuf<int> dci, drp;
     DevBuf<double> dtv;
     StreamDrain s{f->stream, false};
-    HIPCHK_AT("cocons_predict_taper", dci.alloc(nz));
-    HIPCHK_AT("cocons_predict_taper", drp.alloc((size_t)m + 1));
-    HIPCHK_AT("cocons_predict_taper", dtv.alloc(nz));
-    HIPCHK_AT("cocons_predict_taper", upload_canon(f->dXp, X_pred, (size_t)m * p, s));
-    HIPCHK_AT("cocons_predict_taper", upload_canon(f->dlocsp, locs_pred, (size_t)m * 2, s));
-    HIPCHK_AT("cocons_predict_taper", hipMemcpyAsync(drp, rowpointers_pred, (size_t)(m + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK_AT(who, dci.alloc(nz));
+    HIPCHK_AT(who, drp.alloc((size_t)m + 1));
+    HIPCHK_AT(who, dtv.alloc(nz));
+    HIPCHK_AT(who, upload_canon(f->dXp, X_pred, (size_t)m * p, s));
+    HIPCHK_AT(who, upload_canon(f->dlocsp, locs_pred, (size_t)m * 2, s));
+    HIPCHK_AT(who, hipMemcpyAsync(drp, rowpointers_pred, (size_t)(m + 1) * sizeof(int), hipMemcpyHostToDevice, s));
     if (nnz_pred > 0) {
         std::vector<int> mapped(nnz_pred);          // the pattern's columns in the handle's order of the observations
         for (int w = 0; w < nnz_pred; ++w) mapped[w] = f->taper_inv[colindices_pred[w] - 1] + 1;
-        HIPCHK_AT("cocons_predict_taper", hipMemcpy(dci, mapped.data(), (size_t)nnz_pred * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK_AT("cocons_predict_taper", upload_canon(dtv, taper_entries_pred, (size_t)nnz_pred, s));
+        HIPCHK_AT(who, hipMemcpy(dci, mapped.data(), (size_t)nnz_pred * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK_AT(who, upload_canon(dtv, taper_entries_pred, (size_t)nnz_pred, s));
     }
     // parameters as cocons_cov_rns_taper_pred prepares them: FULL scale vector, prediction-branch smoothness
     ThetaVecs tv;
     make_theta_vecs(theta, p, tv, true);
     const ModeSel ms = select_mode(theta, p, f->smooth_limits, 2);
-    return run_op(f, "cocons_predict_taper", [&]() -> int {
+    return run_op(f, who, [&]() -> int {
         if (int rc = assemble_sigma_taper(f, theta)) return rc;      // zeroes the whole buffer, border rows included
         residual_row(f, mean, z_col, f->dA, f->lda, f->npad, f->rhs_act - 1, f->npad);
         launch_loc_params(loc_args(m, p, f->dXp, f->dlocsp, f->dlocp, m, tv, ms.smooth_kind, f->smooth_limits), s);
@@ -421,8 +515,8 @@ extern "C" int cocons_predict_taper(cocons_fit *f, const double *theta, const do
         launch_taper(t, s);
         if (int rc = factorize(f, main_view(f), nullptr)) return rc;
         launch_row_reduce(f->dA, f->lda, n, f->npad, f->npad + 1, m, f->dstoch, f->dquad, f->dred, s, f->skew, f->npad);
-        HIPCHK_AT("cocons_predict_taper", hipMemcpyAsync(stochastic, f->dstoch, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK_AT("cocons_predict_taper", hipMemcpyAsync(quadform, f->dquad, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT(who, hipMemcpyAsync(stochastic, f->dstoch, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT(who, hipMemcpyAsync(quadform, f->dquad, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
         return 0;
     });
 }
@@ -439,11 +533,6 @@ static int krige_taper_handle(cocons_fit *f, const char *who)
 {
     if (f->taper_nnz <= 0) return fail(-1, "%s: not a taper fit (cocons_krige_prepare serves a dense handle)", who);
     return krige_sharded(f, who);
-}
-
-static size_t krige_taper_row_bytes(const cocons_fit *f)
-{
-    return ((size_t)band_W(f) * TILE + (size_t)f->p + 2 + LOCP_FIELDS + 2) * sizeof(double);   // ring, Xp, lp, locp, st, qd
 }
 
 // the CSR staging holds at least `entries` entries; a new allocation only when it has to grow (the stream is idle then)
@@ -476,6 +565,32 @@ static int krige_taper_csr_check(const char *who, const char *what, int m, int n
     return 0;
 }
 
+// the entries of a pred pattern (ci / rp on the device, columns in the handle's order) between nrows new locations -- their
+// SoA in `rows` -- and the observations, prediction branch, one value per entry into val
+static TaperLaunch krige_pred_taper(const cocons_fit *f, const KrigeHeld *K, int nrows, int nnz, const int *ci, const int *rp,
+                                    const double *rows, size_t stride_rows, double *val)
+{
+    TaperLaunch t;
+    t.mode = MODE_GEOM; t.pred = true; t.nrows = nrows; t.nnz = nnz; t.ci = ci; t.rp = rp;
+    t.rows = rows; t.stride_rows = stride_rows; t.cols = K->loc; t.stride = f->npad;
+    t.out = val;
+    return t;
+}
+
+// the ring solve of `rows` new locations against the held band factor: what apply and joint both set (boff on the host, the
+// other arrays on the device); the joint entry adds Wr, depth, S and lds
+static KrigeBandSolve krige_band_solve_args(const cocons_fit *f, const KrigeTaperState *K, double *ring, size_t ldr, int rows,
+                                            const int *boff, const int *bdst, const int *bsrc, const double *val,
+                                            const double *tapv, double *stoch, double *quad)
+{
+    KrigeBandSolve a;
+    a.Lp = K->L; a.Qp = K->Q; a.w = K->w; a.toff = K->plan.toff.data(); a.hi = envelope_or_null(f);
+    a.nt = f->nt; a.W = K->plan.W; a.ring = ring; a.ldr = ldr; a.rows = rows;
+    a.boff = boff; a.bdst = bdst; a.bsrc = bsrc; a.val = val; a.tapv = tapv;
+    a.stoch = stoch; a.quad = quad;
+    return a;
+}
+
 extern "C" int cocons_krige_taper_prepare(cocons_fit *f, const double *theta, const double *mean, int z_col, int max_rows)
 {
     const char *who = "cocons_krige_taper_prepare";
@@ -484,38 +599,22 @@ extern "C" int cocons_krige_taper_prepare(cocons_fit *f, const double *theta, co
     if (int rc = krige_taper_handle(f, who)) return rc;
     if (!theta || !mean || z_col < 0 || z_col >= f->r || max_rows < 0) return fail(-1, "%s: bad argument", who);
     f->krige_taper.reset();             // replaced -- and gone if this prepare fails
-    const int p = f->p, n = f->n, npad = f->npad, nt = f->nt;
+    const int n = f->n, npad = f->npad, nt = f->nt;
     std::unique_ptr<KrigeTaperState> K(new KrigeTaperState());
-    {
-        size_t r = max_rows > 0 ? std::min<size_t>((size_t)max_rows, KRIGE_TAPER_ROWS_MAX)
-                                : std::min<size_t>(KRIGE_CHUNK_BYTES / krige_taper_row_bytes(f), KRIGE_ROWS_CAP);
-        K->rows = (int)std::max<size_t>(r / 64 * 64, 64);      // whole 64-row strips, as krige_rows
-    }
-    K->theta.resize((size_t)6 * p);
-    for (int i = 0; i < 6 * p; ++i) K->theta[i] = canon_nan(theta[i]);
-    K->mean.resize((size_t)p);
-    for (int i = 0; i < p; ++i) K->mean[i] = canon_nan(mean[i]);
+    const size_t row_bytes = krige_row_bytes(f, (size_t)band_W(f) * TILE);
+    K->rows = krige_rows(max_rows, row_bytes, KRIGE_TAPER_ROWS_MAX);
     if (const char *why = band_plan(nt, envelope_or_null(f), f->taper_maxband, K->plan)) return fail(-1, "%s: %s", who, why);
     const size_t R = (size_t)K->rows, ntile = (size_t)K->plan.toff[nt];
     // the staging starts at the densest row of the handle's own pattern for every row of a chunk
     size_t dens = 1;
     for (int i = 0; i < n; ++i) dens = std::max<size_t>(dens, (size_t)(f->h_trp[i + 1] - f->h_trp[i]));
     StreamDrain s{f->stream, false};
-    HIPCHK_AT(who, K->L.alloc(ntile * TILE * TILE));
-    HIPCHK_AT(who, K->Q.alloc((size_t)nt * 2048));
-    HIPCHK_AT(who, K->w.alloc((size_t)npad));
-    HIPCHK_AT(who, K->loc.alloc((size_t)LOCP_FIELDS * npad));
+    if (int rc = krige_held_alloc(f, who, K.get(), theta, mean, ntile, row_bytes, &K->fixed_bytes)) return rc;
     HIPCHK_AT(who, K->ring.alloc(R * K->plan.W * TILE));
-    HIPCHK_AT(who, K->Xp.alloc(R * p));
-    HIPCHK_AT(who, K->lp.alloc(R * 2));
-    HIPCHK_AT(who, K->locp.alloc(R * LOCP_FIELDS));
-    HIPCHK_AT(who, K->st.alloc(R));
-    HIPCHK_AT(who, K->qd.alloc(R));
     HIPCHK_AT(who, K->d_toff.alloc((size_t)nt));
     HIPCHK_AT(who, K->rp.alloc(R + 1));
     if (int rc = krige_taper_stage(K.get(), R * dens, who)) return rc;
-    K->fixed_bytes = (long long)((ntile * TILE * TILE + (size_t)nt * 2048 + (size_t)npad * (1 + LOCP_FIELDS)) * sizeof(double) +
-                                 R * krige_taper_row_bytes(f) + ((size_t)nt + R + 1) * sizeof(int));
+    K->fixed_bytes += (long long)(((size_t)nt + R + 1) * sizeof(int));
     HIPCHK_AT(who, hipMemcpyAsync(K->d_toff, K->plan.toff.data(), (size_t)nt * sizeof(int), hipMemcpyHostToDevice, s));
     const double *th = K->theta.data();
     if (int rc = fit_alloc_matrix(f, 1)) return rc;
@@ -528,13 +627,7 @@ extern "C" int cocons_krige_taper_prepare(cocons_fit *f, const double *theta, co
         return 0;
     });
     if (st) return st;                  // failing minor: no state
-    // observation-side SoA as cocons_cov_rns_taper_pred prepares it: FULL scale vector, prediction-branch smoothness
-    ThetaVecs tv;
-    make_theta_vecs(th, p, tv, true);
-    const ModeSel ms = select_mode(th, p, f->smooth_limits, 2);
-    launch_loc_params(loc_args(n, p, f->dX, f->dlocs, K->loc, npad, tv, ms.smooth_kind, f->smooth_limits), s);
-    HIPCHK_AT(who, hipGetLastError());
-    HIPCHK_AT(who, hipStreamSynchronize(s));
+    if (int rc = krige_prepare_finish(f, who, K.get(), true)) return rc;
     f->krige_taper = std::move(K);
     return 0;
 }
@@ -551,43 +644,23 @@ extern "C" int cocons_krige_taper_apply(cocons_fit *f, int m, const double *locs
     FIT_ENTER(f);
     if (int rc = krige_taper_handle(f, who)) return rc;
     KrigeTaperState *K = f->krige_taper.get();
-    if (!K) return fail(-1, "%s: no kriging state on this handle (call cocons_krige_taper_prepare first)", who);
+    if (!K) return krige_no_state(who, "cocons_krige_taper_prepare");
     if (m == 0) return 0;
-    const int p = f->p, n = f->n, nt = f->nt, rows = K->rows, W = K->plan.W;
+    const int nt = f->nt, rows = K->rows;
     // the whole pattern is checked before any device work
-    if (int rc = krige_taper_csr_check(who, "", m, n, nnz_pred, colindices_pred, rowpointers_pred)) return rc;
-    const double *th = K->theta.data();
-    ThetaVecs tv;
-    make_theta_vecs(th, p, tv, true);
-    const ModeSel ms = select_mode(th, p, f->smooth_limits, 2);
-    std::vector<double> hX((size_t)rows * p), hl((size_t)rows * 2);
-    std::vector<int> hrp((size_t)rows + 1), hci, hdst, hsrc, boff((size_t)nt + 1), fill((size_t)nt);
-    StreamDrain s{f->stream, false};
-    for (int b = 0; b < m; b += rows) {
-        const int mc = std::min(rows, m - b);
+    if (int rc = krige_taper_csr_check(who, "", m, f->n, nnz_pred, colindices_pred, rowpointers_pred)) return rc;
+    // the CSR staging grows to the call's densest chunk before the first one is enqueued (the stream is idle)
+    size_t dens = 0;
+    for (int b = 0; b < m; b += rows) dens = std::max<size_t>(dens, (size_t)(rowpointers_pred[std::min(b + rows, m)] - rowpointers_pred[b]));
+    if (int rc = krige_taper_stage(K, dens, who)) return rc;
+    std::vector<int> hrp((size_t)rows + 1), hci, hdst, hsrc, boff;
+    hipStream_t s = f->stream;
+    // the chunk's pattern on its way to the staging: row pointers counted from its first entry, columns in the handle's order,
+    // buckets per tile column
+    auto pattern = [&](int b, int mc) -> int {
         const int e0 = rowpointers_pred[b] - 1, ne = rowpointers_pred[b + mc] - 1 - e0;
-        if (int rc = krige_taper_stage(K, (size_t)ne, who)) return rc;      // (the stream is idle: drained below per chunk)
-        for (int j = 0; j < p; ++j) memcpy(&hX[(size_t)j * mc], X_pred + b + (size_t)j * m, (size_t)mc * sizeof(double));
-        for (int j = 0; j < 2; ++j) memcpy(&hl[(size_t)j * mc], locs_pred + b + (size_t)j * m, (size_t)mc * sizeof(double));
-        // the chunk's pattern in the handle's order of the observations, and its entries bucketed by tile column (a counting
-        // sort over the chunk's entries: row by row, so a bucket keeps the rows' order)
-        hci.resize((size_t)ne); hdst.resize((size_t)ne); hsrc.resize((size_t)ne);
-        std::fill(boff.begin(), boff.end(), 0);
         for (int i = 0; i <= mc; ++i) hrp[i] = rowpointers_pred[b + i] - e0;
-        for (int w = 0; w < ne; ++w) {
-            const int c = f->taper_inv[colindices_pred[e0 + w] - 1];
-            hci[w] = c + 1;
-            ++boff[c / TILE + 1];
-        }
-        for (int I = 0; I < nt; ++I) { boff[I + 1] += boff[I]; fill[I] = boff[I]; }
-        for (int i = 0; i < mc; ++i)
-            for (int w = hrp[i] - 1; w < hrp[i + 1] - 1; ++w) {
-                const int c = hci[w] - 1, k = fill[c / TILE]++;
-                hdst[k] = i + (c % TILE) * rows;
-                hsrc[k] = w;
-            }
-        HIPCHK_AT(who, upload_canon(K->Xp, hX.data(), (size_t)mc * p, s));
-        HIPCHK_AT(who, upload_canon(K->lp, hl.data(), (size_t)mc * 2, s));
+        band_buckets<TILE>(nt, f->taper_inv.data(), colindices_pred, rowpointers_pred, b, mc, rows, hci, hdst, hsrc, boff);
         HIPCHK_AT(who, hipMemcpyAsync(K->rp, hrp.data(), (size_t)(mc + 1) * sizeof(int), hipMemcpyHostToDevice, s));
         if (ne > 0) {
             HIPCHK_AT(who, hipMemcpyAsync(K->ci, hci.data(), (size_t)ne * sizeof(int), hipMemcpyHostToDevice, s));
@@ -595,24 +668,15 @@ extern "C" int cocons_krige_taper_apply(cocons_fit *f, int m, const double *locs
             HIPCHK_AT(who, hipMemcpyAsync(K->bsrc, hsrc.data(), (size_t)ne * sizeof(int), hipMemcpyHostToDevice, s));
             HIPCHK_AT(who, upload_canon(K->tv, taper_entries_pred + e0, (size_t)ne, s));
         }
-        launch_loc_params(loc_args(mc, p, K->Xp, K->lp, K->locp, rows, tv, ms.smooth_kind, f->smooth_limits), s);
-        TaperLaunch t;
-        t.mode = MODE_GEOM; t.pred = true; t.nrows = mc; t.nnz = ne; t.ci = K->ci; t.rp = K->rp;
-        t.rows = K->locp; t.stride_rows = rows; t.cols = K->loc; t.stride = f->npad;
-        t.out = K->val;
-        launch_taper(t, s);
-        KrigeBandSolve a;
-        a.Lp = K->L; a.Qp = K->Q; a.w = K->w; a.toff = K->plan.toff.data(); a.hi = envelope_or_null(f);
-        a.nt = nt; a.W = W; a.ring = K->ring; a.ldr = (size_t)rows; a.rows = mc;
-        a.boff = boff.data(); a.bdst = K->bdst; a.bsrc = K->bsrc; a.val = K->val; a.tapv = K->tv;
-        a.stoch = K->st; a.quad = K->qd;
-        HIPCHK_AT(who, launch_krige_band_solve(a, s));
-        HIPCHK_AT(who, hipMemcpyAsync(stochastic + b, K->st, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK_AT(who, hipMemcpyAsync(quadform + b, K->qd, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK_AT(who, hipGetLastError());
-        HIPCHK_AT(who, hipStreamSynchronize(s));
-    }
-    return 0;
+        return 0;
+    };
+    return krige_chunks(f, K, who, true, m, locs_pred, X_pred, stochastic, quadform, pattern, [&](int b, int mc, double) -> int {
+        const int ne = rowpointers_pred[b + mc] - rowpointers_pred[b];
+        launch_taper(krige_pred_taper(f, K, mc, ne, K->ci, K->rp, K->locp, (size_t)rows, K->val), s);
+        HIPCHK_AT(who, launch_krige_band_solve(krige_band_solve_args(f, K, K->ring, (size_t)rows, mc, boff.data(), K->bdst, K->bsrc,
+                                                                     K->val, K->tv, K->st, K->qd), s));
+        return 0;
+    });
 }
 
 extern "C" int cocons_krige_taper_release(cocons_fit *f)
@@ -670,19 +734,15 @@ static int krige_taper_joint_enter(cocons_fit *f, const char *who, int m, int *d
 {
     if (int rc = krige_taper_handle(f, who)) return rc;
     *K = f->krige_taper.get();
-    if (!*K) return fail(-1, "%s: no kriging state on this handle (call cocons_krige_taper_prepare first)", who);
+    if (!*K) return krige_no_state(who, "cocons_krige_taper_prepare");
     if (m > KRIGE_TAPER_ROWS_MAX) return fail(-1, "%s: m = %d is too large (at most %d rows in one call)", who, m, KRIGE_TAPER_ROWS_MAX);
     return krige_joint_depth(who, depth);
 }
 
-// doubles of the call's buffers but the CSR staging, in the order cocons_krige_taper_joint allocates them
-static void krige_taper_joint_counts(const cocons_fit *f, const KrigeTaperState *K, int m, int nsim, int depth, size_t counts[12])
+// slots of the joint call's ring: depth - 1 more than the state's, all tile columns at most
+static int krige_joint_ring_slots(const cocons_fit *f, const KrigeTaperState *K, int depth)
 {
-    const size_t mv = (size_t)round_up(m, 64), mpad = (size_t)round_up(m, TILE), ne = (size_t)m * (size_t)nsim;
-    const size_t Wr = (size_t)std::min(K->plan.W + depth - 1, f->nt);
-    const size_t c[12] = {mv * Wr * TILE, mpad * mpad, (size_t)m * f->p, (size_t)m * 2, (size_t)m * 2, (size_t)LOCP_FIELDS * mv,
-                          (size_t)LOCP_FIELDS * mpad, mv, mv, ne ? ne : 1, ne ? ne : 1, (size_t)m};
-    memcpy(counts, c, sizeof c);
+    return std::min(K->plan.W + depth - 1, f->nt);
 }
 
 extern "C" int cocons_krige_taper_joint_bytes(cocons_fit *f, int m, int nsim, long long *bytes)
@@ -697,7 +757,7 @@ extern "C" int cocons_krige_taper_joint_bytes(cocons_fit *f, int m, int nsim, lo
     const KrigeTaperState *K = nullptr;
     if (int rc = krige_taper_joint_enter(f, who, m, &depth, &K)) return rc;
     size_t counts[12], total = 0;
-    krige_taper_joint_counts(f, K, m, nsim, depth, counts);
+    krige_joint_counts(f, m, nsim, (size_t)round_up(m, 64) * krige_joint_ring_slots(f, K, depth) * TILE, counts);
     for (int k = 0; k < 12; ++k) total += counts[k];
     *bytes = (long long)(total * sizeof(double) + 2 * ((size_t)m + 1) * sizeof(int));      // ... and the two row-pointer arrays
     return 0;
@@ -724,7 +784,7 @@ extern "C" int cocons_krige_taper_joint(cocons_fit *f, int m, const double *locs
     int D = 0;
     const KrigeTaperState *K = nullptr;
     if (int rc = krige_taper_joint_enter(f, who, m, &D, &K)) return rc;
-    const int p = f->p, n = f->n, nt = f->nt, W = K->plan.W, Wr = std::min(W + D - 1, nt);
+    const int p = f->p, n = f->n, nt = f->nt, Wr = krige_joint_ring_slots(f, K, D);
     // both patterns are checked before any device work; a uu row holds its diagonal entry
     if (int rc = krige_taper_csr_check(who, "pred pattern: ", m, n, nnz_pred, colindices_pred, rowpointers_pred)) return rc;
     if (int rc = krige_taper_csr_check(who, "uu pattern: ", m, m, nnz_uu, colindices_uu, rowpointers_uu)) return rc;
@@ -737,30 +797,15 @@ extern "C" int cocons_krige_taper_joint(cocons_fit *f, int m, const double *locs
     const size_t ne = (size_t)nnz_pred, nu = (size_t)nnz_uu;
     const double *lu = locs_unobs ? locs_unobs : locs_pred;
     const double *th = K->theta.data();
-    // the pred pattern in the handle's order of the observations, bucketed by tile column (cocons_krige_taper_apply, one chunk)
-    std::vector<int> hci(ne), hdst(ne), hsrc(ne), boff((size_t)nt + 1, 0), fill((size_t)nt);
-    for (size_t w = 0; w < ne; ++w) {
-        const int c = f->taper_inv[colindices_pred[w] - 1];
-        hci[w] = c + 1;
-        ++boff[c / TILE + 1];
-    }
-    for (int I = 0; I < nt; ++I) { boff[I + 1] += boff[I]; fill[I] = boff[I]; }
-    for (int i = 0; i < m; ++i)
-        for (int w = rowpointers_pred[i] - 1; w < rowpointers_pred[i + 1] - 1; ++w) {
-            const int c = hci[w] - 1, k = fill[c / TILE]++;
-            hdst[k] = i + (c % TILE) * mv;
-            hsrc[k] = w;
-        }
-    std::vector<double> stv((size_t)m), mu((size_t)m), hY(nsm), hcov;
-    if (cov && nsim > 0) hcov.resize((size_t)m * m);     // the factorisation may still fail: cov goes home through a staging copy
-    double *cov_to = hcov.empty() ? cov : hcov.data();
-    int raw = 0x7f7f7f7f;                                // the view's own info word
+    // the pred pattern as one chunk of cocons_krige_taper_apply, in slots of mv rows
+    std::vector<int> hci, hdst, hsrc, boff;
+    band_buckets<TILE>(nt, f->taper_inv.data(), colindices_pred, rowpointers_pred, 0, m, mv, hci, hdst, hsrc, boff);
     DevBuf<double> dring, dS, dXp, dlp, dlu, dlocp, dlocu, dst, dq, dE, dY, dmu, dtvp, dval, dtvu;
     DevBuf<int> dcip, drpp, dbdst, dbsrc, dciu, drpu;
     StreamDrain s{f->stream, false};
     {
         size_t counts[15], total = 0;
-        krige_taper_joint_counts(f, K, m, nsim, D, counts);
+        krige_joint_counts(f, m, nsim, ldr * Wr * TILE, counts);
         counts[12] = ne ? ne : 1; counts[13] = ne ? ne : 1; counts[14] = nu;
         DevBuf<double> *bufs[15] = {&dring, &dS, &dXp, &dlp, &dlu, &dlocp, &dlocu, &dst, &dq, &dE, &dY, &dmu, &dtvp, &dval, &dtvu};
         const size_t icounts[6] = {ne ? ne : 1, (size_t)m + 1, ne ? ne : 1, ne ? ne : 1, nu, (size_t)m + 1};
@@ -793,14 +838,11 @@ extern "C" int cocons_krige_taper_joint(cocons_fit *f, int m, const double *locs
     make_theta_vecs(th, p, tv, true);
     const ModeSel msp = select_mode(th, p, f->smooth_limits, 2);
     const ModeSel ms0 = select_mode(th, p, f->smooth_limits, 0);
-    auto enqueue = [&]() -> int {
+    const KrigeJointCall call = {who, m, nsim, lds, dS, dst, dE, dY, dmu, X_pred, K->mean.data(), stochastic, cov, sims, true};
+    return krige_joint_tail(f, call, [&]() -> int {
         launch_loc_params(loc_args(m, p, dXp, dlp, dlocp, ldr, tv, msp.smooth_kind, f->smooth_limits), s);
         launch_loc_params(loc_args(m, p, dXp, dlu, dlocu, lds, tv, ms0.smooth_kind, f->smooth_limits), s);
-        TaperLaunch t;
-        t.mode = MODE_GEOM; t.pred = true; t.nrows = m; t.nnz = nnz_pred; t.ci = dcip; t.rp = drpp;
-        t.rows = dlocp; t.stride_rows = ldr; t.cols = K->loc; t.stride = f->npad;
-        t.out = dval;
-        launch_taper(t, s);
+        launch_taper(krige_pred_taper(f, K, m, nnz_pred, dcip, drpp, dlocp, ldr, dval), s);
         // S_uu: the entries with column <= row times their taper value into the zeroed view, identity on [m, mpad)
         HIPCHK_AT(who, hipMemsetAsync(dS, 0, lds * mpad * sizeof(double), s));
         TaperLaunch u;
@@ -809,60 +851,12 @@ extern "C" int cocons_krige_taper_joint(cocons_fit *f, int m, const double *locs
         u.tapv = dtvu; u.A = dS; u.lda = lds;
         launch_taper(u, s);
         launch_pad_identity(dS, lds, m, mpad, s);
-        KrigeBandSolve a;
-        a.Lp = K->L; a.Qp = K->Q; a.w = K->w; a.toff = K->plan.toff.data(); a.hi = envelope_or_null(f);
-        a.nt = nt; a.W = W; a.ring = dring; a.ldr = ldr; a.rows = m;
-        a.boff = boff.data(); a.bdst = dbdst; a.bsrc = dbsrc; a.val = dval; a.tapv = dtvp;
-        a.stoch = dst; a.quad = dq;
+        KrigeBandSolve a = krige_band_solve_args(f, K, dring, ldr, m, boff.data(), dbdst, dbsrc, dval, dtvp, dst, dq);
         a.Wr = Wr; a.depth = D; a.S = dS; a.lds = lds;
         HIPCHK_AT(who, launch_krige_band_solve(a, s));
         launch_sym_mirror(dS, lds, m, s);
-        HIPCHK_AT(who, hipMemcpyAsync(stv.data(), dst, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (cov)
-            HIPCHK_AT(who, hipMemcpy2DAsync(cov_to, (size_t)m * sizeof(double), dS, lds * sizeof(double), (size_t)m * sizeof(double),
-                                            (size_t)m, hipMemcpyDeviceToHost, s));
-        if (nsim == 0) return 0;
-        // tmp_mu = X_pred mean + stochastic on the host, then cocons_krige_joint's tail
-        HIPCHK_AT(who, hipStreamSynchronize(s));
-        for (int i = 0; i < m; ++i) {
-            double sys = 0;
-            for (int j = 0; j < p; ++j) sys += X_pred[(size_t)i + (size_t)j * m] * K->mean[j];
-            mu[i] = sys + stv[i];
-        }
-        HIPCHK_AT(who, upload_canon(dmu, mu.data(), (size_t)m, s));
-        {
-            // a dense view of the call, maybe of more tiles than the handle's nt: factorize() sizes the hand-off words and the
-            // mailboxes by the view (flags_reset, mbox_reset), dinv and dinfo do not depend on the order
-            PlainSchedule plain(f);
-            FoldView fv(f);
-            FactorView v;
-            v.A = dS; v.lda = lds; v.nt = mpad / TILE; v.mt = mpad / TILE;
-            if (int rc = factorize(f, v, nullptr)) return rc;
-        }
-        HIPCHK_AT(who, hipMemcpyAsync(&raw, f->dinfo, sizeof(int), hipMemcpyDeviceToHost, s));
-        launch_trmm_lower(dS, lds, m, dE, m, nsim, dmu, dY, m, s);
-        HIPCHK_AT(who, hipMemcpyAsync(hY.data(), dY, nsm * sizeof(double), hipMemcpyDeviceToHost, s));
         return 0;
-    };
-    if (nsim == 0) {                    // nothing is factored: no info words, nothing to repeat
-        if (int rc = enqueue()) return rc;
-        HIPCHK_AT(who, hipGetLastError());
-        HIPCHK_AT(who, hipStreamSynchronize(s));
-    } else {
-        f->nrhs_cur = 0;
-        const int st = run_op(f, who, enqueue);
-        if (st > 0)
-            return fail(-5, "%s: the predictive covariance is not positive definite (leading minor %d of %d not positive)", who,
-                        raw, m);
-        if (st < 0) {
-            const std::string why = g_err;
-            return why.compare(0, strlen(who), who) == 0 ? st : fail(st, "%s: %s", who, why.c_str());
-        }
-        memcpy(sims, hY.data(), nsm * sizeof(double));
-        if (!hcov.empty()) memcpy(cov, hcov.data(), hcov.size() * sizeof(double));
-    }
-    memcpy(stochastic, stv.data(), (size_t)m * sizeof(double));
-    return 0;
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -1102,11 +1096,7 @@ extern "C" int cocons_sim_cond_dense(cocons_fit *f, const double *theta, const d
         launch_row_reduce(dJ, ldj, n, N, npad, m, dst, dq, dred, s);
         HIPCHK_AT("cocons_sim_cond_dense", hipMemcpyAsync(stv.data(), dst, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
         HIPCHK_AT("cocons_sim_cond_dense", hipStreamSynchronize(s));
-        for (int i = 0; i < m; ++i) {
-            double sys = 0;
-            for (int j = 0; j < p; ++j) sys += X_pred[(size_t)i + (size_t)j * m] * mean[j];
-            mu[i] = sys + stv[i];
-        }
+        add_trend_to(mu.data(), X_pred, m, p, mean, stv.data());
         HIPCHK_AT("cocons_sim_cond_dense", upload_canon(dmu, mu.data(), (size_t)m, s));
         // fields = L_S E + tmp_mu with L_S = lower-right block of the joint factor
         launch_trmm_lower(dJ + (size_t)npad + (size_t)npad * ldj, ldj, m, dE, m, nsim, dmu, dY, m, s);

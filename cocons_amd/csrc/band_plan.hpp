@@ -1,7 +1,8 @@
 // band_plan.hpp -- the host-side book-keeping of a taper handle's band factor, in ONE place: the envelope rule (which tiles of
 // the factor a pattern can fill) and the packed layout of the factor's tiles that every entry holding or sweeping a band factor
-// uses (tapered kriging, the tapered information).  Host only, standard headers only: tests/band_plan_main.cpp compiles it
-// with a plain C++17 compiler and holds it against the restatement in tests/taper_envelope_cases.py.
+// uses (tapered kriging, the tapered information), and the bucket sort by tile column that tapered kriging scatters a chunk's
+// entries into its ring by.  Host only, standard headers only: tests/band_plan_main.cpp compiles it with a plain C++17
+// compiler and tests/test_taper_envelope_cases.py holds it against restatements in numpy.
 #pragma once
 #include <climits>
 #include <vector>
@@ -67,6 +68,38 @@ inline const char *band_plan(int nt, const int *hi, int maxband, BandPlan &pl)
         pl.toff[J + 1] = (int)a; pl.toffb[J + 1] = (int)b;
     }
     return pl.toffb[nt] == pl.toff[nt] ? nullptr : "the envelope is not monotone";
+}
+
+// The entries of rows [row0, row0 + nrows) of a caller's pattern (ci / rp: its 1-based CSR, already checked) in the handle's
+// order of the columns -- inv[caller's column] = position --, bucketed by tile column for the ring solve of tapered kriging.
+// With e0 = rp[row0] - 1 the chunk's first entry and w counted from it:
+//   hci[w]              1-based position of entry w's column;
+//   boff[I], boff[I+1]  (nt + 1 entries) the bucket of tile column I in hdst / hsrc, which for its k-th place hold
+//   hsrc[k]             the entry w, and
+//   hdst[k]             where it goes in the tile column's slot: (row - row0) + (position % tile) * stride, stride the slot's
+//                       leading dimension (>= nrows).
+// A counting sort that walks the rows in order, so a bucket keeps the rows' order and, within a row, the caller's.  (The tile
+// edge is a template argument: two divisions per entry, which the compiler turns into shifts.)
+template <int tile>
+void band_buckets(int nt, const int *inv, const int *ci, const int *rp, int row0, int nrows, int stride,
+                  std::vector<int> &hci, std::vector<int> &hdst, std::vector<int> &hsrc, std::vector<int> &boff)
+{
+    const int e0 = rp[row0] - 1, ne = rp[row0 + nrows] - 1 - e0;
+    hci.resize((size_t)ne); hdst.resize((size_t)ne); hsrc.resize((size_t)ne);
+    boff.assign((size_t)nt + 1, 0);
+    for (int w = 0; w < ne; ++w) {
+        const int c = inv[ci[e0 + w] - 1];
+        hci[w] = c + 1;
+        ++boff[c / tile + 1];
+    }
+    std::vector<int> fill((size_t)nt);
+    for (int I = 0; I < nt; ++I) { boff[I + 1] += boff[I]; fill[I] = boff[I]; }
+    for (int i = 0; i < nrows; ++i)
+        for (int w = rp[row0 + i] - 1 - e0; w < rp[row0 + i + 1] - 1 - e0; ++w) {
+            const int c = hci[w] - 1, k = fill[c / tile]++;
+            hdst[k] = i + (c % tile) * stride;
+            hsrc[k] = w;
+        }
 }
 
 }  // namespace cocons

@@ -147,33 +147,33 @@ LocArgs loc_args(int n, int p, const double *X, const double *locs, double *out,
                  int smooth_kind, const double *smooth_limits);
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
-// Kriging state of a dense handle (cocons_krige_prepare / _apply / _release).  Everything apply reads lives here, owned by
-// the state, so no other entry point on the handle -- predict growing dA, the batch slots, engine retries -- can touch it.
-struct KrigeState {
-    DevBuf<double> L;             // packed lower tiles of the factor: nt (nt + 1) / 2 tiles of 128 x 128 (kernels.h launch_krige_pack)
+// What both kriging states hold (KrigeHeld): the packed factor with its solve operands, w, the observation-side SoA, the
+// staging and the outputs of one chunk of `rows` new locations, and the prepared theta and mean.  Every buffer is owned by the
+// state it is a member of, so no other entry point on the handle -- predict growing dA, the batch slots, engine retries --
+// can touch it; the joint entries read it only.
+struct KrigeHeld {
+    DevBuf<double> L;             // the factor's lower 128 x 128 tiles, packed (dense: all nt (nt + 1) / 2, kernels.h launch_krige_pack;
+                                  // taper: the envelope's, tile (I, J) at plan.toff[J] + (I - J), launch_krige_band_pack)
     DevBuf<double> Q;             // nt x 2048: the triangular-solve operands of every diagonal tile
     DevBuf<double> w;             // npad: L^-1 (z[:, z_col] - X mean), zero in the padding and slot columns
-    DevBuf<double> loc;           // LOCP_FIELDS x npad: observation-side SoA in the prediction branch's smoothness
-    DevBuf<double> C;             // rows x npad: one chunk of cross-covariance rows, solved in place
+    DevBuf<double> loc;           // LOCP_FIELDS x npad: observation-side SoA in the prediction branch's parameters
     DevBuf<double> Xp, lp, locp;  // the chunk's X_pred (rows x p), locations (rows x 2) and SoA (LOCP_FIELDS x rows)
     DevBuf<double> st, qd;        // rows: the chunk's outputs
     std::vector<double> theta;    // 6 p: the prepared theta (canonicalised)
-    std::vector<double> mean;     // p: the prepared mean (canonicalised; cocons_krige_joint's trend of the draws)
+    std::vector<double> mean;     // p: the prepared mean (canonicalised; the joint entries' trend of the draws)
     int rows = 0;                 // rows per chunk (a multiple of 64)
+};
+
+// Kriging state of a dense handle (cocons_krige_prepare / _apply / _release)
+struct KrigeState : KrigeHeld {
+    DevBuf<double> C;             // rows x npad: one chunk of cross-covariance rows, solved in place
     long long bytes = 0;          // device bytes held
 };
 
 // Kriging state of a taper handle (cocons_krige_taper_prepare / _apply / _release): the band factor packed
-// per tile column and a ring of W tile columns for the chunk.  Owned by the state like KrigeState's buffers: no other entry
-// point reads or writes it.
-struct KrigeTaperState {
-    DevBuf<double> L;             // the envelope's lower tiles: tile (I, J) at plan.toff[J] + (I - J) (kernels.h launch_krige_band_pack)
-    DevBuf<double> Q;             // nt x 2048
-    DevBuf<double> w;             // npad: L^-1 (z[:, z_col] - X mean), zero in the padding
-    DevBuf<double> loc;           // LOCP_FIELDS x npad: observation-side SoA in the prediction branch's parameters
+// per tile column and a ring of W tile columns for the chunk.
+struct KrigeTaperState : KrigeHeld {
     DevBuf<double> ring;          // rows x plan.W * 128: tile column I of the chunk's right-hand side in slot I mod W
-    DevBuf<double> Xp, lp, locp;  // the chunk's X_pred (rows x p), locations (rows x 2) and SoA (LOCP_FIELDS x rows)
-    DevBuf<double> st, qd;        // rows: the chunk's outputs
     DevBuf<int> d_toff;           // nt: device copy of plan.toff
     // CSR staging of a chunk, ecap entries (grown to the densest chunk seen): mapped columns, the caller's taper values, the
     // entries' covariance values, the buckets (destination in the slot, entry index), and the chunk's row pointers
@@ -181,9 +181,6 @@ struct KrigeTaperState {
     DevBuf<double> tv, val;
     size_t ecap = 0;
     BandPlan plan;                // first packed tile of every tile column, slots of the ring (band_plan.hpp)
-    std::vector<double> theta;    // 6 p: the prepared theta (canonicalised)
-    std::vector<double> mean;     // p
-    int rows = 0;                 // rows per chunk (a multiple of 64)
     long long fixed_bytes = 0;    // device bytes of everything but the CSR staging
     long long bytes() const { return fixed_bytes + (long long)(ecap * (3 * sizeof(int) + 2 * sizeof(double))); }
 };

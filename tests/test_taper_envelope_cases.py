@@ -3,7 +3,8 @@ every case shows the shape it claims, the restated envelope holds the whole dens
 for (and notices when it is one tile too tight), the inputs are conditioned like those the suite's tolerances were set at,
 the prediction sets hold the rows they promise, and the ring's load rule covers the case's (nt, W); and the library's own
 envelope rule and packed band layout (cocons_amd/csrc/band_plan.hpp, compiled into tests/band_plan_main.cpp by the host
-compiler) agree with the restatement integer for integer.  No GPU."""
+compiler) agree with the restatement integer for integer, and so does its bucket sort of a chunk's entries by tile column
+(band_buckets, what tapered kriging scatters a chunk into the ring by).  No GPU."""
 import functools
 import os
 import subprocess
@@ -279,3 +280,74 @@ def test_library_plan_without_an_envelope(band_plan_exe, tmp_path):
     assert got["status"] == [0] and got["nt"] == [nt] and got["W"] == [nt] and got["envelope"] == []
     assert got["hi"] == [nt] * nt and got["hib"] == [nt] * nt
     assert got["toff"] == _prefix(nt - np.arange(nt)) and got["toffb"] == got["toff"]
+
+
+# --------------------------------------------------------------------------- the bucket sort of tapered kriging (band_buckets)
+def _buckets(nt, inv, ci, rp, row0, nrows, stride):
+    """band_buckets restated: the entries of rows [row0, row0 + nrows) of the 1-based CSR (ci, rp), numbered from the chunk's
+    first entry; hci = 1-based position of an entry's column (inv[caller's column]); the entries stably sorted by the tile
+    column of that position (rows in order, a row's entries in the caller's order); hdst = row in the chunk + (position mod
+    128) * stride; boff = where each tile column's bucket starts, nt + 1 entries."""
+    ci, rp, inv = np.asarray(ci, dtype=np.int64), np.asarray(rp, dtype=np.int64), np.asarray(inv, dtype=np.int64)
+    e0, e1 = rp[row0] - 1, rp[row0 + nrows] - 1
+    pos = inv[ci[e0:e1] - 1]
+    row = np.repeat(np.arange(nrows), np.diff(rp[row0:row0 + nrows + 1]))
+    hsrc = np.argsort(pos // TE.TILE, kind="stable")
+    hdst = row[hsrc] + (pos[hsrc] % TE.TILE) * stride
+    boff = np.concatenate([[0], np.cumsum(np.bincount(pos // TE.TILE, minlength=nt))])
+    return {"hci": (pos + 1).tolist(), "hdst": hdst.tolist(), "hsrc": hsrc.tolist(), "boff": boff.tolist()}
+
+
+def _csr_rows(rows):
+    """1-based CSR of a list of rows, each a list of 1-based columns"""
+    rp = np.concatenate([[1], 1 + np.cumsum([len(r) for r in rows])]).astype(int)
+    return [c for r in rows for c in r], rp.tolist()
+
+
+def _bucket_cases():
+    rng = np.random.default_rng(5)
+    n = 300                                     # nt = 3 tile columns, the last one partial
+    ident = np.arange(n)
+    perm = rng.permutation(n)
+    inv128 = ident.copy()                       # caller's columns 1 and 2 at positions 127 and 128: the tile boundary in one row
+    inv128[[0, 127]], inv128[[1, 128]] = inv128[[127, 0]], inv128[[128, 1]]
+    rows = [sorted(rng.choice(n, size=k, replace=False) + 1) for k in rng.integers(1, 40, size=70)]
+    rows[9] = []                                # an empty row inside a chunk
+    rows[64], rows[65], rows[66] = [], [], []   # a chunk with no entries at all
+    rows[3] = [1, 2, 200]
+    m = len(rows)
+    return {
+        "nt1": (1, np.arange(100), [[5, 7], [], [1, 100]], 0, 3, 64),
+        "whole_identity": (3, ident, rows, 0, m, 128),
+        "empty_chunk": (3, perm, rows, 64, 3, 64),
+        "empty_row_inside": (3, perm, rows, 0, 64, 64),
+        "tile_boundary": (3, inv128, rows, 0, 64, 64),
+        "permuted": (3, perm, rows, 0, 64, 64),
+        "last_short_chunk": (3, perm, rows, 64, m - 64, 64),        # row0 > 0 and nrows = 6 < stride
+        "joint_m65": (3, perm, rows[:65], 0, 65, 128),               # stride = round_up(65, 64)
+    }
+
+
+@pytest.mark.parametrize("name", sorted(_bucket_cases()))
+def test_library_bucket_sort_is_the_restated_sort(name, band_plan_exe):
+    nt, inv, rows, row0, nrows, stride = _bucket_cases()[name]
+    ci, rp = _csr_rows(rows)
+    text = " ".join(map(str, [nt, len(inv)] + list(inv) + [len(rows)] + rp + ci + [row0, nrows, stride]))
+    got = {}
+    for line in subprocess.check_output([band_plan_exe, "buckets"], input=text.encode()).decode().splitlines():
+        key, *vals = line.split()
+        got[key] = [int(v) for v in vals]
+    want = _buckets(nt, inv, ci, rp, row0, nrows, stride)
+    ne = rp[row0 + nrows] - rp[row0]
+    print("%s: %d entries, boff %s" % (name, ne, got["boff"]))
+    assert got == want
+    # what the device relies on: every entry once, every destination inside the slot's rows [0, nrows) x 128 columns
+    assert sorted(got["hsrc"]) == list(range(ne)) and len(got["boff"]) == nt + 1 and got["boff"][-1] == ne
+    assert all(0 <= d % stride < max(nrows, 1) and d // stride < TE.TILE for d in got["hdst"])
+    if name == "empty_chunk":
+        assert ne == 0 and got["boff"] == [0] * (nt + 1)
+    if name == "tile_boundary":
+        k127, k128 = rp[3] - 1, rp[3]                                       # row 3's first two entries: positions 127 and 128
+        assert (got["hci"][k127], got["hci"][k128]) == (128, 129)
+        assert got["hsrc"].index(k127) < got["boff"][1] <= got["hsrc"].index(k128)
+        assert got["hdst"][got["hsrc"].index(k127)] == 3 + 127 * stride and got["hdst"][got["hsrc"].index(k128)] == 3
