@@ -106,7 +106,8 @@ extern "C" int cocons_cv_dense(cocons_fit *f, const double *theta, const double 
     if (f->r < 1) return fail(-1, "%s: fit has no z", who);
     const int n = f->n_user, npad = f->npad, nr = f->r;
     if ((int)f->obs_pos.size() != n) return fail(-1, "%s: the handle keeps no order of its observations", who);
-    if (!fold && n == 1) return fail(-1, "%s: fold 0 holds all 1 observations", who);
+    // (leave-one-out of a single observation is answered, as cocons_cv_taper answers it: nothing is left to predict from, and
+    // (K_11)^-1 U_1 and (K_11)^-1 are the residual and Sigma_11)
     CvPlan plan;
     if (fold) {
         std::vector<int> cnt((size_t)nfold, 0);

@@ -371,6 +371,10 @@ static int fisher_entry(cocons_fit *f, const char *who, const double *theta, int
         // factored on the host in the device's order, says so (as the REML gradient's entry)
         double val = 0.0;
         if (profile_tail(f, p, 0.0, true, &val, nullptr)) return fail(-4, "%s: X' Sigma^-1 X is not positive definite", who);
+        // n = p with W positive definite: no error contrasts, P = 0 and the information is the zero matrix -- in floating point
+        // the projector keeps the rounding error of Sigma^-1 - C C', whose square (1e-32) would come back instead
+        if (f->n_user <= p)
+            for (double &x : hinfo) x = 0.0;
     }
     memcpy(info, hinfo.data(), hinfo.size() * sizeof(double));
     if (mean) memcpy(info_mean, hmean.data(), hmean.size() * sizeof(double));

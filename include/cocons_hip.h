@@ -342,7 +342,8 @@ int cocons_fisher_dense(cocons_fit *fit, const double *theta, int ndir, const do
  * the expected Hessian of the negative restricted log-likelihood (half the objective cocons_neg2loglik_reml returns), i.e.
  * the Fisher information of the error contrasts K' z with K' X = 0.  Positive semi-definite by construction; no mean block
  * (REML has no mean parameters) and no penalty.  The reference has no counterpart (R/getFunctions.R:930).  info is symmetric
- * to the bit; every sum has a fixed order, so repeated calls agree bit for bit.  0, the failing minor k > 0 of Sigma, -4 when
+ * to the bit; every sum has a fixed order, so repeated calls agree bit for bit.  With n = p observations there are no error
+ * contrasts: info is the zero matrix, exactly.  0, the failing minor k > 0 of Sigma, -4 when
  * X' Sigma^-1 X is not positive definite, or < 0 with a message that starts with the entry's name; info is written on 0 only.
  * Refused (-1) before any device work: null arguments, ndir outside [1, 7 * COCONS_P_MAX], non-finite entries of dirs, taper
  * and sharded handles, a handle without z, sizes beyond the product kernel's addressing.  Memory as for cocons_fisher_dense:
@@ -388,7 +389,8 @@ int cocons_fisher_taper(cocons_fit *fit, const double *theta, int ndir, const do
  * 0, the failing minor k > 0 of Sigma, -5 when a hold-out block of Sigma^-1 is not positive definite in floating point (the
  * message names the fold), or < 0 with a message that starts with the entry's name; outputs are written on 0 only.
  * Refused (-1) before any device work: null arguments, nfold < 0, fold and nfold that disagree, a label outside [0, nfold),
- * a fold that holds all n observations, taper and sharded handles, a handle without z.  The handle keeps what
+ * a fold that holds all n observations, taper and sharded handles, a handle without z.  (Leave-one-out of n = 1 is answered:
+ * nothing is left to predict from, resid is z - X mean and var is Sigma_11.)  The handle keeps what
  * cocons_neg2loglik_grad_dense makes it keep; everything else belongs to the call.                                        */
 int cocons_cv_dense(cocons_fit *fit, const double *theta, const double *mean,
                     int nfold, const int *fold, double *resid, double *var);
