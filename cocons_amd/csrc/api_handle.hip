@@ -452,6 +452,49 @@ extern "C" int cocons_fit_same_data(cocons_fit *f, int n, int p, int r, int q, c
 
 extern "C" void *cocons_fit_stream(cocons_fit *f) { return f ? (void *)f->stream : nullptr; }
 
+static bool redraw_stream(hipStream_t &s, std::vector<hipStream_t> &losers);
+
+// The handle's own pair again, for a main stream the caller has just installed: engine_warm proved at creation that the engine's
+// stream runs beside the main stream the library had drawn, which says nothing about this one (a caller's stream that shares
+// the engine stream's hardware queue makes every engine-schedule operation run into its bounded wait: correct values from the
+// repeat on the plain schedule, 100 ms lost each time).  Only stream2 -- the library's own -- is redrawn, up to engine_warm's 8
+// attempts; no clash-free draw, or the NULL stream (never probed): the handle takes the plain schedule until another stream is
+// installed.  The caller is inside cocons_fit_set_stream and both streams are idle: the one place where the library launches its
+// probe pair on a caller's stream.
+static int own_pair_again(cocons_fit *f)
+{
+    if (f->engine_pair_lost) { f->engine_ok = true; f->engine_pair_lost = false; }
+    if (!engine_enabled() || f->nt <= 4 || !f->engine_ok || !f->stream2 || !f->dflags) return 0;
+    if (!f->stream) { f->engine_ok = false; f->engine_pair_lost = true; return 0; }
+    HIPCHK(hipStreamSynchronize(f->stream));
+    unsigned *words = handoff_words(f).selftest;
+    std::vector<hipStream_t> losers;
+    int ok = 0;
+    for (int attempt = 0; attempt < 8; ++attempt) {
+        ok = streams_run_concurrently(f->stream2, f->stream, words);
+        if (ok != 0) break;
+        if (!redraw_stream(f->stream2, losers)) { ok = -1; break; }
+    }
+    const bool redrawn = !losers.empty();
+    for (hipStream_t l : losers) hipStreamDestroy(l);
+    if (ok < 0) { (void)hipGetLastError(); return fail(-100, "cocons_fit_set_stream: stream self-test failed"); }
+    if (ok == 0) { f->engine_ok = false; f->engine_pair_lost = true; return 0; }
+    HIPCHK(hipMemsetAsync(f->dflags, 0, handoff_word_count(f->flags_cap) * sizeof(unsigned), f->stream));
+    HIPCHK(hipStreamSynchronize(f->stream));
+    if (redrawn) {
+        // (the first dispatch of the engine kernel on a fresh stream is paid here, as at creation: engine_warm)
+        const HandoffWords hw = handoff_words(f);
+        EngineLaunch e;
+        e.dinv = f->dinv; e.info = f->dinfo; e.in = e.out = e.xr = hw.in; e.abort_word = hw.abort; e.alive = hw.alive;
+        launch_potrf_engine_warmup(e, false, f->stream2);
+        if (tun().dag) launch_potrf_engine_warmup(e, true, f->stream2);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(f->stream2));
+        f->engine_ops = 0;        // (the next engine-schedule operation is the first on this stream: its gate is patient)
+    }
+    return 0;
+}
+
 extern "C" int cocons_fit_set_stream(cocons_fit *f, void *stream)
 {
     FIT_ENTER(f);
@@ -461,7 +504,7 @@ extern "C" int cocons_fit_set_stream(cocons_fit *f, void *stream)
     if (f->stream2) HIPCHK(hipStreamSynchronize(f->stream2));
     if (f->own_stream) { HIPCHK(hipStreamDestroy(f->stream)); f->own_stream = false; }
     f->stream = (hipStream_t)stream;
-    return 0;
+    return own_pair_again(f);
 }
 
 extern "C" int cocons_fit_sync(cocons_fit *f)
@@ -603,6 +646,7 @@ static void slot_stream_apart(cocons_fit *f, cocons_fit *c)
         std::vector<cocons_fit *> peers{f};
         for (cocons_fit *o : f->slots) if (o != c) peers.push_back(o);
         for (cocons_fit *o : peers) {
+            if (!o->own_stream) continue;      // (a caller's stream is never probed for another handle's sake: engine_warm likewise)
             if (hipStreamQuery(o->stream) != hipSuccess) { (void)hipGetLastError(); continue; }      // (busy: not probed)
             const int r = streams_run_concurrently(o->stream, c->stream, words);
             if (r == 0) { clash = true; break; }

@@ -283,6 +283,8 @@ struct cocons_fit {
     DevBuf<unsigned> dflags;      // the hand-off words: handoff_words() below is their map
     int flags_cap = 0;            // (the stride between in[], out[] and xr[]: not just dflags' count)
     bool engine_ok = false;       // false: this handle never uses the resident engine (batch slots, band-limited taper fits)
+    bool engine_pair_lost = false;     // engine_ok went false in cocons_fit_set_stream (the caller's stream shares the engine stream's
+                                  // hardware queue, or is the NULL stream): the next stream installed is tested afresh
     bool engine_live = false;     // the engine of the NEXT factorize call is already launched (engine_start)
     bool engine_used = false;     // the factorisation enqueued last runs on the engine schedule
     int border_clean = -1;        // nr >= 0: the rows [nr, rhs_act) under the matrix are known to be exactly zero in every column

@@ -504,6 +504,19 @@ class CoconsFit:
         _lib.check(self._L.cocons_fit_engine_state(self._h, out), "cocons_fit_engine_state")
         return {"active": bool(out[0]), "retries": int(out[1]), "last_abort": int(out[2])}
 
+    def stream(self):
+        """The hipStream_t the handle launches on, as an integer (0: the NULL stream) -- cocons_fit_stream."""
+        return int(self._L.cocons_fit_stream(self._h) or 0)
+
+    def set_stream(self, stream):
+        """Launch on the caller's stream from now on (a hipStream_t as an integer, e.g. torch.cuda.Stream().cuda_stream;
+        None or 0: the NULL stream) -- cocons_fit_set_stream."""
+        _lib.check(self._L.cocons_fit_set_stream(self._h, ctypes.c_void_p(int(stream or 0) or None)), "cocons_fit_set_stream")
+
+    def sync(self):
+        """Wait for everything the handle has enqueued on its stream -- cocons_fit_sync."""
+        _lib.check(self._L.cocons_fit_sync(self._h), "cocons_fit_sync")
+
     def profile_stages(self, theta_list, reps=3):
         """Stage timings (ms) from HIP events on the fit's stream; see cocons_fit_profile."""
         T = theta_table(theta_list)

@@ -24,7 +24,8 @@
  *     entry point holds the handle's operation lock); DIFFERENT handles may be created, used and destroyed from
  *     different threads concurrently, the stateless entry points likewise; cocons_last_error() is per thread.
  *     A handle must not be destroyed while another thread is inside a call on it, and a stream installed with
- *     cocons_fit_set_stream is the caller's: the library never launches its own probe kernels on it.
+ *     cocons_fit_set_stream is the caller's: the creation of ANOTHER handle or of a batch slot never launches the
+ *     library's probe kernels on it.  (The one exception is cocons_fit_set_stream itself, see there.)
  */
 #ifndef COCONS_HIP_H
 #define COCONS_HIP_H
@@ -549,7 +550,13 @@ int cocons_fit_same_data(cocons_fit *fit, int n, int p, int r, int q, const doub
 /* HIP stream the fit launches on (hipStream_t as void*), so the caller can order
  * collectives against it. */
 void *cocons_fit_stream(cocons_fit *fit);
-/* launch on a caller-owned stream instead (hipStream_t as void*; NULL = default stream) */
+/* launch on a caller-owned stream instead (hipStream_t as void*; NULL = default stream).  The call waits until the
+ * handle's streams AND the new stream are idle.  A handle that uses the resident diagonal-block engine then tests, inside
+ * this call, that its engine stream runs beside the new stream (two one-lane probe kernels, one of them on the caller's
+ * stream); on a clash the library redraws its OWN engine stream, and when no draw is clash-free the handle takes the
+ * plain schedule (same values to 1e-12, cocons_fit_engine_state reports active = 0) until another stream is installed.
+ * The NULL stream is never probed: a handle on it takes the plain schedule.  Results are bit-identical to those on the
+ * handle's own stream whenever the schedule is the same.                                                              */
 int cocons_fit_set_stream(cocons_fit *fit, void *stream);
 int cocons_fit_sync(cocons_fit *fit);
 
