@@ -70,6 +70,8 @@ SIGNATURES = {
     "cocons_fisher_taper": (c_int, [c_vp, c_dp, c_int, c_dp, c_int, c_dp, c_int, c_dp, c_dp]),
     "cocons_cv_dense": (c_int, [c_vp, c_dp, c_dp, c_int, ctypes.POINTER(c_int), c_dp, c_dp]),
     "cocons_cv_taper": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp]),
+    "cocons_cv_taper_folds": (c_int, [c_vp, c_dp, c_dp, c_int, ctypes.POINTER(c_int), c_int, c_dp, c_dp,
+                                      ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_predict_dense": (c_int, [c_vp, c_dp, c_dp, c_int, c_int, c_dp, c_dp, c_dp, c_dp]),
     "cocons_sim_dense": (c_int, [c_vp, c_dp, c_dp, c_int, c_int, c_dp, c_dp]),
     "cocons_krige_prepare": (c_int, [c_vp, c_dp, c_dp, c_int, c_int]),

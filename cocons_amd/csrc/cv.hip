@@ -9,7 +9,10 @@
 //                     resid = W' (W U_B) -- every sum in a fixed order, no atomics
 //   cv_gather_kernel  a larger fold's bordered matrix [K_BB ; U_B' ; I] for the library's own factorisation
 //   cv_scatter_kernel its results back to the observations' positions
-//   cv_taper_kernel   leave-one-out from the diagonal of the selected inverse (taper handles)
+//   cv_taper_kernel   leave-one-out from the diagonal of the selected inverse (taper handles), all observations or a list
+//   cv_border_kernel  a larger fold's bordered matrix without its top block [0 (+ I on the padding) ; U_B' ; I]: the Gram
+//                     product of cocons_cv_taper_folds adds K_BB = V V' into the top (solve.hip krige_band_gram_kernel)
+// Taper handles by folds: cv_fold_kernel reads a fold's K_BB from a block of its own (base, + sign) instead of -S.
 // The only atomic is the record of a failing fold (atomicMin of its label, as the factorisation's info word).
 #include "kernels.h"
 #include <atomic>
@@ -50,6 +53,7 @@ struct CvFoldArgs {
     const int *idx, *off, *flist, *lab;
     double *var, *res; size_t ldr;
     int *fail;
+    const long long *base;      // non-null: K_BB of fold f is the b x b block at S + base[f], ld lds (lower triangle), as it is
 };
 
 template <int BP> __global__ void __launch_bounds__(256)
@@ -66,7 +70,9 @@ cv_fold_kernel(CvFoldArgs a)
     // gather: K(i, j) = -S(max, min); positions ascend inside a fold, so row >= column is the stored triangle
     for (int e = tid; e < b * b; e += 256) {
         const int rr = e % b, cc = e / b;
-        if (rr >= cc) M[rr + cc * LD] = -a.S[(size_t)pos[rr] + (size_t)pos[cc] * a.lds];
+        if (rr >= cc)
+            M[rr + cc * LD] = a.base ? a.S[(size_t)a.base[f] + (size_t)rr + (size_t)cc * a.lds]
+                                     : -a.S[(size_t)pos[rr] + (size_t)pos[cc] * a.lds];
     }
     // C C' = K_BB, right-looking, column by column
     bool bad = false;
@@ -147,7 +153,15 @@ hipError_t launch_cv_folds(int cls, const double *S, size_t lds, const double *U
                            int *fail, hipStream_t s)
 {
     if (nfolds <= 0) return hipSuccess;
-    CvFoldArgs a{S, lds, U, ldu, nr, idx, off, flist, lab, var, res, ldr, fail};
+    return launch_cv_folds_at(cls, S, lds, nullptr, U, ldu, nr, idx, off, flist, lab, nfolds, var, res, ldr, fail, s);
+}
+
+hipError_t launch_cv_folds_at(int cls, const double *S, size_t lds, const long long *base, const double *U, size_t ldu, int nr,
+                              const int *idx, const int *off, const int *flist, const int *lab, int nfolds, double *var,
+                              double *res, size_t ldr, int *fail, hipStream_t s)
+{
+    if (nfolds <= 0) return hipSuccess;
+    CvFoldArgs a{S, lds, U, ldu, nr, idx, off, flist, lab, var, res, ldr, fail, base};
     switch (cls) {
     case 16: return cv_fold_launch<16>(a, nfolds, s);
     case 32: return cv_fold_launch<32>(a, nfolds, s);
@@ -203,6 +217,30 @@ void launch_cv_scatter(const int *pos, int b, int nr, const double *v, const dou
     hipLaunchKernelGGL(cv_scatter_kernel, dim3((b + 255) / 256), dim3(256), 0, s, pos, b, nr, v, r, var, res, ldr);
 }
 
+__global__ void __launch_bounds__(256)
+cv_border_kernel(const double *U, size_t ldu, int nr, const int *pos, int b, int bpad, int rt, double *out, size_t ldo)
+{
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= ldo * (size_t)bpad) return;
+    const int rr = (int)(e % ldo), c = (int)(e / ldo);
+    double v;
+    if (rr < bpad)
+        v = (rr == c && rr >= b) ? 1.0 : 0.0;
+    else if (rr < bpad + rt) {
+        const int k = rr - bpad;
+        v = (k < nr && c < b) ? U[(size_t)pos[c] + (size_t)k * ldu] : 0.0;
+    } else
+        v = rr - bpad - rt == c ? 1.0 : 0.0;
+    out[(size_t)rr + (size_t)c * ldo] = v;
+}
+
+void launch_cv_border(const double *U, size_t ldu, int nr, const int *pos, int b, int bpad, int rt, double *out, size_t ldo,
+                      hipStream_t s)
+{
+    hipLaunchKernelGGL(cv_border_kernel, dim3((unsigned)((ldo * (size_t)bpad + 255) / 256)), dim3(256), 0, s, U, ldu, nr, pos, b,
+                       bpad, rt, out, ldo);
+}
+
 __global__ void cv_info_take_kernel(int *info, int clean, int *keep, int *fail, int label)
 {
     if (threadIdx.x || blockIdx.x) return;
@@ -230,12 +268,13 @@ void launch_cv_info_put(int *info, const int *keep, hipStream_t s)
 
 __global__ void __launch_bounds__(256)
 cv_taper_kernel(const double *Z, size_t ldz, int skew, int npad, int n, const double *U, size_t ldu, int nr, double *var,
-                double *res, size_t ldr, int *fail)
+                double *res, size_t ldr, int *fail, const int *idx, const int *lab)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const int i = idx ? idx[t] : t;
     const double k = Z[band_index(i, i, ldz, skew, npad)];
-    if (!(k > 0.0) || !isfinite(k)) atomicMin(fail, i);
+    if (!(k > 0.0) || !isfinite(k)) atomicMin(fail, lab ? lab[t] : i);
     const double v = 1.0 / k;
     var[i] = v;
     for (int c = 0; c < nr; ++c) res[(size_t)i + (size_t)c * ldr] = U[(size_t)i + (size_t)c * ldu] * v;
@@ -246,7 +285,15 @@ void launch_cv_taper(const double *Z, size_t ldz, int skew, int npad, int n, con
 {
     if (n <= 0) return;
     hipLaunchKernelGGL(cv_taper_kernel, dim3((n + 255) / 256), dim3(256), 0, s, Z, ldz, skew, npad, n, U, ldu, nr, var, res, ldr,
-                       fail);
+                       fail, (const int *)nullptr, (const int *)nullptr);
+}
+
+void launch_cv_taper_list(const double *Z, size_t ldz, int skew, int npad, const int *idx, const int *lab, int count,
+                          const double *U, size_t ldu, int nr, double *var, double *res, size_t ldr, int *fail, hipStream_t s)
+{
+    if (count <= 0) return;
+    hipLaunchKernelGGL(cv_taper_kernel, dim3((count + 255) / 256), dim3(256), 0, s, Z, ldz, skew, npad, count, U, ldu, nr, var,
+                       res, ldr, fail, idx, lab);
 }
 
 }  // namespace cocons

@@ -339,6 +339,9 @@ hipError_t launch_krige_band_load(double *slot, size_t ldr, const int *dst, cons
 // (krige_band_schur_kernel; S: round_up(rows, 128) rows and columns, ld lds; ldr = round_up(rows, 64) exactly).  The slot
 // the load of step J takes over held tile J - depth, whose group ended at step <= J - 1.  Every element of S sees the
 // tile columns in ascending order whatever the depth: S does not depend on it to the bit.  Unset: the plain ring, no product.
+// One 64 x 128 block of a fold-aware Gram product: ring rows [row0, row0 + 64) against ring rows [col0, col0 + 128) -- both
+// inside one fold, or one 128-row tile of packed small folds -- added to the block at blocks + dst, leading dimension ld.
+struct KrigeGramTask { int row0, col0, ld, pad; long long dst; };
 struct KrigeBandSolve {
     const double *Lp = nullptr, *Qp = nullptr, *w = nullptr;
     const int *toff = nullptr, *hi = nullptr; int nt = 0, W = 0;
@@ -349,6 +352,11 @@ struct KrigeBandSolve {
     int Wr = 0;                    // slots of the ring (0: W)
     int depth = 0;                 // tile columns per Schur launch (with S)
     double *S = nullptr; size_t lds = 0;
+    // cross-validation by folds (cocons_cv_taper_folds) sets these in place of S: the product of every group goes to the
+    // blocks of `tasks` (device, ntasks of them) inside `blocks` instead of one dense S -- D += V_g(strip, :) V_g(tile, :)'
+    // (krige_band_gram_kernel), nothing between rows of different tasks' tiles; Wr and depth as with S
+    const KrigeGramTask *tasks = nullptr; int ntasks = 0;
+    double *blocks = nullptr;
 };
 hipError_t launch_krige_band_solve(const KrigeBandSolve &a, hipStream_t s);
 // schur: S(I, J) -= V(I, :) V(J, :)' over the lower 128 x 128 tiles of S (round_up(m, 128) rows and columns, column-major,
@@ -529,10 +537,19 @@ void launch_cv_loo(const double *S, size_t lds, const double *U, size_t ldu, int
 hipError_t launch_cv_folds(int cls, const double *S, size_t lds, const double *U, size_t ldu, int nr, const int *idx,
                            const int *off, const int *flist, const int *lab, int nfolds, double *var, double *res, size_t ldr,
                            int *fail, hipStream_t s);
+// the same with K_BB of fold f read as it is from the b x b block at S + base[f], leading dimension lds (lower triangle): the
+// blocks the fold-aware Gram product of cocons_cv_taper_folds leaves (base: device, indexed by fold)
+hipError_t launch_cv_folds_at(int cls, const double *S, size_t lds, const long long *base, const double *U, size_t ldu, int nr,
+                              const int *idx, const int *off, const int *flist, const int *lab, int nfolds, double *var,
+                              double *res, size_t ldr, int *fail, hipStream_t s);
 // a large fold's bordered matrix (ld ldo = 2 bpad + rt rows, bpad columns): K_BB identity-padded to bpad, under it rt rows with
 // U_B' (nr of them, the rest zero), then bpad unit rows
 void launch_cv_gather(const double *S, size_t lds, const double *U, size_t ldu, int nr, const int *pos, int b, int bpad, int rt,
                       double *out, size_t ldo, hipStream_t s);
+// launch_cv_gather's matrix without K_BB: the top block zero with ones on the padding's diagonal [b, bpad) -- the Gram product
+// adds K_BB into it --, U_B' and the unit rows as there
+void launch_cv_border(const double *U, size_t ldu, int nr, const int *pos, int b, int bpad, int rt, double *out, size_t ldo,
+                      hipStream_t s);
 // var[pos[i]] = v[i], res[pos[i] + k ldr] = r[i + k b]
 void launch_cv_scatter(const int *pos, int b, int nr, const double *v, const double *r, double *var, double *res, size_t ldr,
                        hipStream_t s);
@@ -543,5 +560,8 @@ void launch_cv_info_put(int *info, const int *keep, hipStream_t s);
 // taper handles: the diagonal of Z = S^-1 (band_index layout) and AR = S^-1 R
 void launch_cv_taper(const double *Z, size_t ldz, int skew, int npad, int n, const double *U, size_t ldu, int nr, double *var,
                      double *res, size_t ldr, int *fail, hipStream_t s);
+// the same closed form for the `count` positions idx[t] only; the label recorded on failure is lab[t]
+void launch_cv_taper_list(const double *Z, size_t ldz, int skew, int npad, const int *idx, const int *lab, int count,
+                          const double *U, size_t ldu, int nr, double *var, double *res, size_t ldr, int *fail, hipStream_t s);
 
 }  // namespace cocons

@@ -1,6 +1,7 @@
 // solve.hip -- the kernels that read a FINISHED factor (gfx950, fp64 MFMA): the reductions behind the likelihood and the
 // predictions (finalize, row_reduce), the draws Y = L E + trend (trmm_lower, band_trmm, gather_rows) and kriging from a held
-// factor, dense and band (krige_*, krige_band_*, krige_schur, sym_mirror), and the band sweeps, sparse product and Gram sums of
+// factor, dense and band (krige_*, krige_band_*, krige_schur, sym_mirror; krige_band_gram: the folds' K_BB = V V' of
+// cocons_cv_taper_folds), and the band sweeps, sparse product and Gram sums of
 // the tapered fit's expected information (band_*).  No hand-offs, no mailboxes: nothing here changes
 // when a schedule of the factorisation (chol.hip) does.  Storage and the register "blk layout": chol.hip, tile_ops.hpp.
 #include <hip/hip_runtime.h>
@@ -699,6 +700,8 @@ hipError_t launch_krige_band_load(double *slot, size_t ldr, const int *dst, cons
 
 __global__ void __launch_bounds__(256)
 krige_band_schur_kernel(const double *ring, size_t ldr, int Wr, int t0, int t1, double *S, size_t lds);      // (below)
+__global__ void __launch_bounds__(256)
+krige_band_gram_kernel(const double *ring, size_t ldr, int Wr, int t0, int t1, const KrigeGramTask *tasks, double *blocks);
 
 hipError_t launch_krige_band_solve(const KrigeBandSolve &a, hipStream_t s)
 {
@@ -706,7 +709,7 @@ hipError_t launch_krige_band_solve(const KrigeBandSolve &a, hipStream_t s)
     const unsigned strips = (unsigned)((a.rows + 63) / 64);
     const int nt = a.nt, W = a.W;
     const int Wr = a.Wr > 0 ? a.Wr : W;                 // the ring's modulus; the live window stays W
-    const int D = a.S ? std::max(a.depth, 1) : 0;
+    const int D = (a.S || a.tasks) ? std::max(a.depth, 1) : 0;
     const unsigned mpad = (unsigned)((a.rows + TILE - 1) / TILE * TILE);
     auto load = [&](int I) {
         const int k0 = a.boff[I], k1 = a.boff[I + 1];
@@ -722,9 +725,15 @@ hipError_t launch_krige_band_solve(const KrigeBandSolve &a, hipStream_t s)
         hipLaunchKernelGGL(krige_band_diag_kernel, dim3(strips), dim3(256), 0, s, Lcol, a.Qp + (size_t)J * 2048,
                            a.w + (size_t)J * TILE, a.ring + (size_t)(J % Wr) * TILE * a.ldr, a.ldr, J == 0 ? 1 : 0, a.stoch, a.quad);
         // the group [J / D * D, J] is solved and still in the ring: its product leaves for S before a later load takes a slot
-        if (D && ((J + 1) % D == 0 || J + 1 == nt))
-            hipLaunchKernelGGL(krige_band_schur_kernel, dim3(mpad / 64, mpad / TILE), dim3(256), 0, s, a.ring, a.ldr, Wr,
-                               J / D * D, J + 1, a.S, a.lds);
+        if (D && ((J + 1) % D == 0 || J + 1 == nt)) {
+            if (a.tasks) {
+                if (a.ntasks > 0)
+                    hipLaunchKernelGGL(krige_band_gram_kernel, dim3((unsigned)a.ntasks), dim3(256), 0, s, a.ring, a.ldr, Wr,
+                                       J / D * D, J + 1, a.tasks, a.blocks);
+            } else
+                hipLaunchKernelGGL(krige_band_schur_kernel, dim3(mpad / 64, mpad / TILE), dim3(256), 0, s, a.ring, a.ldr, Wr,
+                                   J / D * D, J + 1, a.S, a.lds);
+        }
         const int hj = a.hi ? a.hi[J] : nt;
         if (hj - J - 1 > 0)
             hipLaunchKernelGGL(krige_band_update_kernel, dim3(strips, (unsigned)(hj - J - 1)), dim3(256), 0, s, Lcol, a.ring, a.ldr,
@@ -850,6 +859,66 @@ krige_band_schur_kernel(const double *ring, size_t ldr, int Wr, int t0, int t1, 
     }
 #pragma unroll
     for (int jb = 0; jb < 8; ++jb) glb_blk_store(S, lds, rs, c0 + 16 * jb, lane, acc[jb]);
+}
+
+// The fold-aware Gram product of cross-validation by folds (cocons_cv_taper_folds): D += V_t(strip, :) V_t(tile, :)' over the
+// tile columns t in [t0, t1), one workgroup per task -- a 64-row strip of the ring against a 128-row tile of the ring, both
+// inside one fold (or one tile of packed small folds), into the task's own block.  krige_band_schur_kernel's slab staging,
+// K order and accumulators-through-memory between groups: every element sees ONE summation sequence whatever the grouping,
+// the chunk or the other tasks.  The sign is the only difference (K_BB = V V' is added), the operands are read with the
+// same guard (ring rows >= ldr count as zero).
+__global__ void __launch_bounds__(256)
+krige_band_gram_kernel(const double *ring, size_t ldr, int Wr, int t0, int t1, const KrigeGramTask *tasks, double *blocks)
+{
+    __shared__ double PS[64 * KS_KC];
+    __shared__ double QS[TILE * KS_KC];
+    const KrigeGramTask tk = tasks[blockIdx.x];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r0 = tk.row0, c0 = tk.col0;
+    const int mr = (int)ldr;
+    double *D = blocks + tk.dst;
+    const size_t ldd = (size_t)tk.ld;
+    d4 acc[8];
+#pragma unroll
+    for (int jb = 0; jb < 8; ++jb) acc[jb] = glb_blk(D, ldd, 16 * wave, 16 * jb, lane);
+    for (int sl = t0 * (TILE / KS_KC); sl < t1 * (TILE / KS_KC); ++sl) {
+        const int t = sl / (TILE / KS_KC), kc = (sl % (TILE / KS_KC)) * KS_KC;
+        const double *V = ring + (size_t)(t % Wr) * TILE * ldr;
+        double vq[TILE * KS_KC / 256], vp[64 * KS_KC / 256];
+#pragma unroll
+        for (int q = 0; q < TILE * KS_KC / 256; ++q) {
+            const int e = tid + 256 * q, j = e & (TILE - 1), k = e >> 7;
+            vq[q] = c0 + j < mr ? V[(size_t)(c0 + j) + (size_t)(kc + k) * ldr] : 0.0;
+        }
+#pragma unroll
+        for (int q = 0; q < 64 * KS_KC / 256; ++q) {
+            const int e = tid + 256 * q, i = e & 63, k = e >> 6;
+            vp[q] = r0 + i < mr ? V[(size_t)(r0 + i) + (size_t)(kc + k) * ldr] : 0.0;
+        }
+        __syncthreads();                  // every wave is done with the previous slice
+#pragma unroll
+        for (int q = 0; q < TILE * KS_KC / 256; ++q) {
+            const int e = tid + 256 * q, j = e & (TILE - 1), k = e >> 7;
+            QS[(((j >> 4) * (KS_KC / 16) + (k >> 4)) << 8) + ((k & 15) << 4) + (j & 15)] = vq[q];
+        }
+#pragma unroll
+        for (int q = 0; q < 64 * KS_KC / 256; ++q) {
+            const int e = tid + 256 * q, i = e & 63, k = e >> 6;
+            PS[(((i >> 4) * (KS_KC / 16) + (k >> 4)) << 8) + ((k & 15) << 4) + (i & 15)] = vp[q];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kb = 0; kb < KS_KC / 16; ++kb) {
+            const d4 P = lds_blk(PS + ((wave * (KS_KC / 16) + kb) << 8), lane);
+#pragma unroll
+            for (int jb = 0; jb < 8; ++jb) {
+                const d4 Q = lds_blk(QS + ((jb * (KS_KC / 16) + kb) << 8), lane);
+                blk_mma(acc[jb], P, Q);
+            }
+        }
+    }
+#pragma unroll
+    for (int jb = 0; jb < 8; ++jb) glb_blk_store(D, ldd, 16 * wave, 16 * jb, lane, acc[jb]);
 }
 
 void launch_krige_schur(const double *V, size_t ldv, int m, int c_lo, int c_hi, int npad, double *S, size_t lds, hipStream_t s)

@@ -595,14 +595,27 @@ class CoconsTaperFit(CoconsFit):
                                                int(max_rows), _p(info), _p(info_mean)), "cocons_fisher_taper")
         return info, info_mean
 
-    def cv_core(self, theta_list):
-        """Leave-one-out predictions of the tapered model from the selected inverse (cocons_cv_taper): (resid n x r, var n)
-        as `CoconsFit.cv_core` gives them."""
+    def cv_core(self, theta_list, fold=None, max_rows=0):
+        """Cross-validated predictions of the tapered model: (resid n x r, var n) as `CoconsFit.cv_core` gives them.
+        `fold` = None: leave-one-out from the selected inverse (cocons_cv_taper).  `fold`: n integer labels in [0, nfold) --
+        every fold from the one held band factor (cocons_cv_taper_folds), in chunks of `max_rows` rows of the band solve
+        (0: the library's choice); `last_cv_stats` then holds the call's five counts (folds of one observation, of 2 .. 128,
+        larger, chunks run, device bytes of the call)."""
         T = theta_table(theta_list)
         mean = np.ascontiguousarray(np.asarray(theta_list["mean"], dtype=np.float64))
         resid = np.zeros((self.n, self.r), order="F")
         var = np.zeros(self.n)
-        _lib.check(self._L.cocons_cv_taper(self._h, _p(T), _p(mean), _p(resid), _p(var)), "cocons_cv_taper")
+        if fold is None:
+            _lib.check(self._L.cocons_cv_taper(self._h, _p(T), _p(mean), _p(resid), _p(var)), "cocons_cv_taper")
+            return resid, var
+        lab = np.ascontiguousarray(np.asarray(fold).ravel(), dtype=np.int32)
+        if lab.size != self.n:
+            raise ValueError("fold must have length n")
+        nfold = int(lab.max()) + 1 if lab.size and lab.max() >= 0 else 1
+        stats = (ctypes.c_longlong * 5)()
+        _lib.check(self._L.cocons_cv_taper_folds(self._h, _p(T), _p(mean), nfold, _ip(lab), int(max_rows), _p(resid), _p(var),
+                                                 stats), "cocons_cv_taper_folds")
+        self.last_cv_stats = [int(v) for v in stats]
         return resid, var
 
     def predict_core(self, theta_list, locs_pred, x_covariates_pred, pred_taper, z_col=0):
@@ -842,12 +855,14 @@ def cocoCV_dense(theta_list, locs, X_std, smooth_limits, z, fold=None, fit=None)
             f.close()
 
 
-def cocoCV_sparse(theta_list, locs, X_std, smooth_limits, z, ref_taper, fit=None):
-    """Leave-one-out predictions of the tapered model (cocons_cv_taper); `ref_taper` = (colindices, rowpointers, entries).
-    Returns what `cocoCV_dense` returns."""
+def cocoCV_sparse(theta_list, locs, X_std, smooth_limits, z, ref_taper, fit=None, fold=None):
+    """Cross-validated predictions of the tapered model; `ref_taper` = (colindices, rowpointers, entries).  `fold`: one label
+    of any kind per observation, every fold from the one held band factor (cocons_cv_taper_folds); None: leave-one-out
+    (cocons_cv_taper).  Returns what `cocoCV_dense` returns."""
+    lab = None if fold is None else np.unique(np.asarray(fold).ravel(), return_inverse=True)[1]
     f, own = (fit, False) if fit is not None else (CoconsTaperFit(locs, X_std, z, smooth_limits, *ref_taper), True)
     try:
-        resid, var = f.cv_core(theta_list)
+        resid, var = f.cv_core(theta_list, lab)
         return _cv_result(f, z, resid, var)
     finally:
         if own:

@@ -154,6 +154,17 @@ GetNeg2loglikelihood <- function(theta, par.pos, locs, x_covariates, smooth.limi
   list(resid = res[[1]], var = res[[2]])
 }
 
+# the same by folds on a taper handle, every fold from the one held band factor (cocons_cv_taper_folds).  fold: one label of
+# any kind per observation, normalised as .cocons.hip.cv does (NULL: leave-one-out); max_rows: rows per chunk of the band
+# solve (0: the library's choice)
+.cocons.hip.cv.taper.folds <- function(fit, theta_list, fold, max_rows = 0L, safe = TRUE) {
+  if (!is.null(fold)) fold <- match(fold, unique(fold)) - 1L
+  res <- .cocons.hip.result(.Call(`_cocons_hip_cv_taper_folds`, fit, theta_list[-1], theta_list$mean, fold,
+                                  as.integer(max_rows)), safe)
+  if (is.null(res)) return(NULL)
+  list(resid = res[[1]], var = res[[2]])
+}
+
 # derivative of sumsmoothlone (src/cocons_full.cpp:12-30) per element: sign(x) off the smooth branch, tanh(alpha x / 2) on it
 .cocons.hip.dsumsmoothlone <- function(x, lambda, alpha = 1e6) {
   lambda * ifelse(abs(x) > 1e-4, sign(x), tanh(alpha * x / 2))

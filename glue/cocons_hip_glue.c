@@ -473,9 +473,10 @@ SEXP _cocons_hip_fisher_taper(SEXP fitp, SEXP theta, SEXP dirs, SEXP probes, SEX
     return out;
 }
 
-/* cross-validated predictions (cocons_cv_dense / cocons_cv_taper): list(status, list(resid n x r, var n)).  fold: NULL
- * (leave-one-out) or n integer labels from 0; the labels' count is the largest label + 1 */
-static SEXP cv_call(SEXP fitp, SEXP theta, SEXP mean, SEXP fold, int taper)
+/* cross-validated predictions (cocons_cv_dense / cocons_cv_taper / cocons_cv_taper_folds): list(status, list(resid n x r,
+ * var n)).  fold: NULL (leave-one-out) or n integer labels from 0; the labels' count is the largest label + 1.  taper: 0 a
+ * dense handle, 1 leave-one-out on a taper handle, 2 folds on a taper handle (max_rows: rows per chunk of its band solve) */
+static SEXP cv_call(SEXP fitp, SEXP theta, SEXP mean, SEXP fold, int taper, int max_rows)
 {
     cocons_fit *f = fit_of(fitp);
     const int p = fit_p(fitp), n = fit_n(fitp), r = fit_r(fitp);
@@ -484,7 +485,7 @@ static SEXP cv_call(SEXP fitp, SEXP theta, SEXP mean, SEXP fold, int taper)
     if (XLENGTH(mean) != p) Rf_error("theta$mean must have length %d", p);
     int nfold = 0;
     const int *lab = NULL;
-    if (!taper && !Rf_isNull(fold)) {
+    if (taper != 1 && !Rf_isNull(fold)) {
         if (!Rf_isInteger(fold) || XLENGTH(fold) != (R_xlen_t)n) Rf_error("fold must be NULL or %d integer labels", n);
         lab = INTEGER(fold);
         for (int i = 0; i < n; ++i)
@@ -495,8 +496,9 @@ static SEXP cv_call(SEXP fitp, SEXP theta, SEXP mean, SEXP fold, int taper)
     SEXP var = PROTECT(Rf_allocVector(REALSXP, n));
     for (R_xlen_t e = 0; e < XLENGTH(resid); ++e) REAL(resid)[e] = 0.0;
     for (R_xlen_t e = 0; e < XLENGTH(var); ++e) REAL(var)[e] = 0.0;
-    int rc = taper ? cocons_cv_taper(f, T, REAL(mean), REAL(resid), REAL(var))
-                   : cocons_cv_dense(f, T, REAL(mean), nfold, lab, REAL(resid), REAL(var));
+    int rc = taper == 2 ? cocons_cv_taper_folds(f, T, REAL(mean), nfold, lab, max_rows, REAL(resid), REAL(var), NULL)
+             : taper ? cocons_cv_taper(f, T, REAL(mean), REAL(resid), REAL(var))
+                     : cocons_cv_dense(f, T, REAL(mean), nfold, lab, REAL(resid), REAL(var));
     hip_check(rc, taper ? "cross-validation (taper)" : "cross-validation");
     SEXP res = PROTECT(Rf_allocVector(VECSXP, 2));
     SET_VECTOR_ELT(res, 0, resid);
@@ -506,8 +508,14 @@ static SEXP cv_call(SEXP fitp, SEXP theta, SEXP mean, SEXP fold, int taper)
     return out;
 }
 
-SEXP _cocons_hip_cv(SEXP fitp, SEXP theta, SEXP mean, SEXP fold) { return cv_call(fitp, theta, mean, fold, 0); }
-SEXP _cocons_hip_cv_taper(SEXP fitp, SEXP theta, SEXP mean) { return cv_call(fitp, theta, mean, R_NilValue, 1); }
+SEXP _cocons_hip_cv(SEXP fitp, SEXP theta, SEXP mean, SEXP fold) { return cv_call(fitp, theta, mean, fold, 0, 0); }
+SEXP _cocons_hip_cv_taper(SEXP fitp, SEXP theta, SEXP mean) { return cv_call(fitp, theta, mean, R_NilValue, 1, 0); }
+SEXP _cocons_hip_cv_taper_folds(SEXP fitp, SEXP theta, SEXP mean, SEXP fold, SEXP max_rows)
+{
+    const int mr = Rf_asInteger(max_rows);
+    if (mr < 0) Rf_error(      /* (NA_integer_ is negative) */"max_rows must be a non-negative integer");
+    return cv_call(fitp, theta, mean, fold, 2, mr);
+}
 
 /* the same with its parts: list(status, c(sum_logliks, logdet_half, quad_1 .. quad_r)) -- what
  * GetNeg2loglikelihoodTaperProfile (R/neg2loglikelihood.R:98-106) is formed from on a taper handle */
@@ -1017,6 +1025,7 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_fisher_taper", (DL_FUNC)&_cocons_hip_fisher_taper, 5},
     {"_cocons_hip_cv", (DL_FUNC)&_cocons_hip_cv, 4},
     {"_cocons_hip_cv_taper", (DL_FUNC)&_cocons_hip_cv_taper, 3},
+    {"_cocons_hip_cv_taper_folds", (DL_FUNC)&_cocons_hip_cv_taper_folds, 5},
     {"_cocons_hip_neg2loglik_batch", (DL_FUNC)&_cocons_hip_neg2loglik_batch, 3},
     {"_cocons_hip_neg2loglik_profile", (DL_FUNC)&_cocons_hip_neg2loglik_profile, 2},
     {"_cocons_hip_neg2loglik_reml", (DL_FUNC)&_cocons_hip_neg2loglik_reml, 3},

@@ -402,6 +402,27 @@ int cocons_cv_dense(cocons_fit *fit, const double *theta, const double *mean,
 int cocons_cv_taper(cocons_fit *fit, const double *theta, const double *mean,
                     double *resid, double *var);
 
+/* Cross-validation by folds for the tapered model, from ONE selected inverse and one more band factorisation (DESIGN.md 4l,
+ * continued) instead of a refit per fold.  fold, nfold, resid, var, the return codes, the -5 message naming the fold and
+ * "outputs are written on 0 only" are cocons_cv_dense's, for S = T o C(theta) on a taper handle; fold = NULL with nfold = 0
+ * is leave-one-out and returns the bits of cocons_cv_taper.  Observations alone in their fold take cocons_cv_taper's closed
+ * form (its bits).  A fold B of two or more costs K_BB = V V' with V = E_B' L^-T: its observations go through the
+ * sliding-window band solve of cocons_krige_taper_apply as unit rows, in chunks of whole 128-row tiles (folds of up to 128
+ * packed into tiles, a larger fold from a tile boundary on), and the product is accumulated fold by fold while the window
+ * slides -- nothing is formed between different folds.  max_rows: rows per chunk, rounded up to 128; 0 = as many as keep the
+ * ring and the blocks of a chunk within 1 GiB, at most 16384 (a fold larger than that gets a chunk of its own size).
+ * Every sum has a fixed order: two calls agree bit for bit, and a fold's outputs depend only on which observations it holds
+ * -- not on the labels, on how the other observations are grouped, on max_rows or on the depth of the Gram product's groups
+ * (COCONS_CV_GRAM_DEPTH, 1 .. 16, default 8).
+ * stats5 (may be NULL, written on 0): folds of one observation, folds of 2 .. 128, larger folds, chunks run, device bytes
+ * allocated by the call (released before it returns; a device that cannot hold them gives < 0 with the bytes needed in the
+ * message).  Refused (-1) before any device work: null arguments, nfold < 0, fold and nfold that disagree, a label outside
+ * [0, nfold), a fold that holds all n observations, max_rows < 0, dense and sharded handles, a handle without z.
+ * The handle keeps what cocons_neg2loglik_grad_taper makes it keep; a prepared kriging state is neither read nor written. */
+int cocons_cv_taper_folds(cocons_fit *fit, const double *theta, const double *mean,
+                          int nfold, const int *fold, int max_rows,
+                          double *resid, double *var, long long *stats5);
+
 /* Dense kriging core: replaces R/predict.R:136-183
  *   observed_cov <- cov_rns(...); cov_pred <- cov_rns_pred(...);
  *   inv_cov <- solve(observed_cov, t(cov_pred)); crossprod(resid, inv_cov);
