@@ -56,6 +56,9 @@ SIGNATURES = {
                                      ctypes.POINTER(c_int), c_dp, c_dp, c_dp]),
     "cocons_fit_create_taper": (c_vp, [c_int, c_int, c_int, c_dp, c_dp, c_dp, c_dp, c_int, c_int,
                                        ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_dp]),
+    "cocons_taper_pattern": (c_int, [c_int, c_dp, c_int, c_dp, ctypes.c_double, c_int, c_int, ctypes.c_longlong,
+                                     ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_dp]),
+    "cocons_fit_create_taper_delta": (c_vp, [c_int, c_int, c_int, c_dp, c_dp, c_dp, c_dp, c_int, ctypes.c_double, c_int]),
     "cocons_fit_destroy": (None, [c_vp]),
     "cocons_neg2loglik_dense": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp]),
     "cocons_neg2loglik_grad_dense": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
@@ -81,6 +84,8 @@ SIGNATURES = {
     "cocons_krige_taper_prepare": (c_int, [c_vp, c_dp, c_dp, c_int, c_int]),
     "cocons_krige_taper_apply": (c_int, [c_vp, c_int, c_dp, c_dp, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_dp,
                                          c_dp, c_dp]),
+    "cocons_krige_taper_apply_delta": (c_int, [c_vp, c_int, c_dp, c_dp, ctypes.c_double, c_int, c_dp, c_dp,
+                                               ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_krige_taper_release": (c_int, [c_vp]),
     "cocons_krige_taper_info": (c_int, [c_vp, ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_krige_joint": (c_int, [c_vp, c_int, c_dp, c_dp, c_dp, c_dp, c_dp, c_int, c_dp, c_dp]),
@@ -122,6 +127,7 @@ DIAG_SIGNATURES = {
     "cocons_debug_sigma_inverse": (c_int, [c_vp, c_dp, c_dp]),
     "cocons_debug_fit_memory": (c_int, [c_vp, ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_debug_rhs_layout": (c_int, [c_vp, c_int, ctypes.POINTER(c_int)]),
+    "cocons_debug_pattern_cells": (c_int, [c_int, c_dp, ctypes.c_double, c_int, c_dp, c_dp, ctypes.POINTER(c_int)]),
     "cocons_debug_taper_selinv": (c_int, [c_vp, c_dp, c_dp, ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_debug_tune": (c_int, [ctypes.c_char_p, c_int]),
     "cocons_debug_dag_replay": (c_int, [c_vp, c_dp, c_dp, c_int, c_dp]),

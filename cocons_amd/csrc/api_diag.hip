@@ -15,6 +15,23 @@ extern "C" int cocons_debug_host_enqueue(cocons_fit *f, double *out)
 }
 
 // (diagnostics, no HIP call) where an operation with r + nxb right-hand sides puts them on this handle: rhs_layout itself
+// the pattern builder's grid and the clamped cells of given points, from pattern_grid.hpp as the kernels use it (host only)
+extern "C" int cocons_debug_pattern_cells(int n, const double *locs, double delta, int m, const double *pts, double *geom5, int *cells)
+{
+    const char *who = "cocons_debug_pattern_cells";
+    if (!locs || !geom5 || n < 1 || m < 0 || (m > 0 && (!pts || !cells))) return fail(-1, "%s: bad argument", who);
+    if (!std::isfinite(delta) || delta <= 0.0) return fail(-1, "%s: delta must be finite and > 0", who);
+    for (size_t i = 0; i < (size_t)2 * n; ++i)
+        if (!std::isfinite(locs[i])) return fail(-1, "%s: a target coordinate is not finite", who);
+    const PatternGrid g = pattern_grid_make(n, locs, locs + n, delta);
+    geom5[0] = g.x0; geom5[1] = g.y0; geom5[2] = g.edge; geom5[3] = g.nx; geom5[4] = g.ny;
+    for (int i = 0; i < m; ++i) {
+        cells[2 * i] = pattern_cell_x(g, pts[i]);
+        cells[2 * i + 1] = pattern_cell_y(g, pts[i + (size_t)m]);
+    }
+    return 0;
+}
+
 extern "C" int cocons_debug_rhs_layout(cocons_fit *f, int nxb, int *out5)
 {
     if (!f || !out5 || nxb < 0) return fail(-1, "cocons_debug_rhs_layout: bad argument");

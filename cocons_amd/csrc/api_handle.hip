@@ -325,6 +325,121 @@ extern "C" cocons_fit *cocons_fit_create_taper(int n, int p, int r, const double
                                 false);
 }
 
+// ---------------------------------------------------------------------------
+// Taper patterns from delta: what the entries that take (delta, kind) share, and the stateless builder.
+int pattern_check_delta(const char *who, double delta, int kind)
+{
+    if (!std::isfinite(delta) || delta <= 0.0) return fail(-1, "%s: delta must be finite and > 0", who);
+    if (kind < COCONS_TAPER_WEND1 || kind > COCONS_TAPER_SPH)
+        return fail(-1, "%s: kind = %d is no taper (1 = wend1, 2 = wend2, 3 = sph)", who, kind);
+    return 0;
+}
+
+int pattern_check_finite(const char *who, const char *what, size_t npts, const double *pts)
+{
+    for (size_t i = 0; i < 2 * npts; ++i)
+        if (!std::isfinite(pts[i])) return fail(-1, "%s: a coordinate of %s is not finite (point %zu)", who, what, i % npts + 1);
+    return 0;
+}
+
+int pattern_grid_build(const char *who, PatternGridBufs &G, int n, const double *hx, const double *hy, const double *dx,
+                       const double *dy, double delta, hipStream_t s)
+{
+    G.t.g = pattern_grid_make(n, hx, hy, delta);
+    G.t.n = n; G.t.x = dx; G.t.y = dy;
+    G.delta = delta;
+    const size_t ncell = pattern_cells(G.t.g);
+    HIPCHK_AT(who, G.cstart.alloc(ncell + 1));
+    HIPCHK_AT(who, G.cursor.alloc(ncell + 1));
+    HIPCHK_AT(who, G.sidx.alloc((size_t)n));
+    HIPCHK_AT(who, G.sxy.alloc((size_t)2 * n));
+    G.t.cstart = G.cstart; G.t.sidx = G.sidx; G.t.sx = G.sxy; G.t.sy = G.sxy + n;
+    G.bytes = (long long)((2 * (ncell + 1) + (size_t)n) * sizeof(int) + (size_t)2 * n * sizeof(double));
+    HIPCHK_AT(who, launch_pattern_bin(G.t, G.cursor, s));
+    return 0;
+}
+
+// cocons_taper_pattern under the name of the entry that asks (who)
+static int taper_pattern_impl(const char *who, int n, const double *locs, int m, const double *locs_query, double delta, int kind,
+                              int device, long long cap, long long *nnz, int *rowpointers, int *colindices, double *entries)
+{
+    if (!locs || !nnz || !rowpointers || (colindices && !entries)) return fail(-1, "%s: null argument", who);
+    if (n < 1) return fail(-1, "%s: n = %d (at least one point expected)", who, n);
+    if (locs_query && m < 1) return fail(-1, "%s: m = %d with a query set (at least one query expected)", who, m);
+    if (int rc = pattern_check_delta(who, delta, kind)) return rc;
+    if (int rc = pattern_check_finite(who, "locs", (size_t)n, locs)) return rc;
+    if (locs_query)
+        if (int rc = pattern_check_finite(who, "locs_query", (size_t)m, locs_query)) return rc;
+    const int rows = locs_query ? m : n;
+    HIPCHK_AT(who, hipSetDevice(device < 0 ? 0 : device));
+    DevBuf<double> dl, dq, dent;
+    DevBuf<int> drp, dci;
+    DevBuf<long long> dtot;
+    PatternGridBufs G;
+    StreamDrain s{nullptr, true};     // own non-blocking stream (the library never launches on the NULL stream)
+    HIPCHK_AT(who, hipStreamCreateWithFlags(&s.s, hipStreamNonBlocking));
+    HIPCHK_AT(who, dl.alloc((size_t)2 * n));
+    HIPCHK_AT(who, drp.alloc((size_t)rows + 1));
+    HIPCHK_AT(who, dtot.alloc(1));
+    HIPCHK_AT(who, upload_canon(dl, locs, (size_t)2 * n, s));
+    const double *qx = dl, *qy = dl + n;
+    if (locs_query) {
+        HIPCHK_AT(who, dq.alloc((size_t)2 * m));
+        HIPCHK_AT(who, upload_canon(dq, locs_query, (size_t)2 * m, s));
+        qx = dq; qy = dq + m;
+    }
+    if (int rc = pattern_grid_build(who, G, n, locs, locs + n, dl, dl + n, delta, s)) return rc;
+    HIPCHK_AT(who, launch_pattern_count(G.t, rows, qx, qy, delta, drp, nullptr, 0, s));
+    HIPCHK_AT(who, launch_scan_exclusive(drp, drp, rows, 1, dtot, s));
+    long long total = 0;
+    HIPCHK_AT(who, hipMemcpyAsync(&total, dtot, sizeof total, hipMemcpyDeviceToHost, s));
+    HIPCHK_AT(who, hipStreamSynchronize(s));
+    if (total > (long long)INT_MAX - 1)
+        return fail(-1, "%s: the pattern holds %lld entries, more than an int counts (INT_MAX - 1 at most)", who, total);
+    if (!colindices) {                // the count call
+        HIPCHK_AT(who, hipMemcpyAsync(rowpointers, drp, ((size_t)rows + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT(who, hipStreamSynchronize(s));
+        *nnz = total;
+        return 0;
+    }
+    if (cap < total) return fail(-1, "%s: cap = %lld is too small, the pattern holds nnz = %lld entries", who, cap, total);
+    const size_t nz = total > 0 ? (size_t)total : 1;
+    HIPCHK_AT(who, dci.alloc(nz));
+    HIPCHK_AT(who, dent.alloc(nz));
+    HIPCHK_AT(who, launch_pattern_fill(G.t, rows, qx, qy, delta, kind, drp, dci, dent, s));
+    HIPCHK_AT(who, hipMemcpyAsync(rowpointers, drp, ((size_t)rows + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (total > 0) {
+        HIPCHK_AT(who, hipMemcpyAsync(colindices, dci, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT(who, hipMemcpyAsync(entries, dent, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK_AT(who, hipStreamSynchronize(s));
+    *nnz = total;
+    return 0;
+}
+
+extern "C" int cocons_taper_pattern(int n, const double *locs, int m, const double *locs_query, double delta, int kind, int device,
+                                    long long cap, long long *nnz, int *rowpointers, int *colindices, double *entries)
+{
+    return taper_pattern_impl("cocons_taper_pattern", n, locs, m, locs_query, delta, kind, device, cap, nnz, rowpointers, colindices,
+                              entries);
+}
+
+extern "C" cocons_fit *cocons_fit_create_taper_delta(int n, int p, int r, const double *locs, const double *X, const double *z,
+                                                     const double *smooth_limits, int device, double delta, int kind)
+{
+    const char *who = "cocons_fit_create_taper_delta";
+    if (!locs || !X || !z || !smooth_limits) { fail(-1, "%s: null argument", who); return nullptr; }
+    if (n < 1) { fail(-1, "%s: n = %d (at least one point expected)", who, n); return nullptr; }
+    // the self pattern by the builder (count, then fill), and the handle as cocons_fit_create_taper makes it from the arrays
+    std::vector<int> rp((size_t)n + 1), ci;
+    std::vector<double> ent;
+    long long nnz = 0;
+    if (taper_pattern_impl(who, n, locs, n, nullptr, delta, kind, device, 0, &nnz, rp.data(), nullptr, nullptr)) return nullptr;
+    ci.resize((size_t)nnz); ent.resize((size_t)nnz);
+    if (taper_pattern_impl(who, n, locs, n, nullptr, delta, kind, device, nnz, &nnz, rp.data(), ci.data(), ent.data())) return nullptr;
+    return cocons_fit_create_taper(n, p, r, locs, X, z, smooth_limits, device, (int)nnz, ci.data(), rp.data(), ent.data());
+}
+
 // Device copies of a taper handle's pattern (lower triangle, nnz entries), taper entries and envelope (hi may be null: none):
 // from host vectors (taper_create_ordered) or device to device from another handle (clone_for_slot) on f's stream, drained.
 static int taper_pattern_to_device(cocons_fit *f, size_t nnz, const int *ci, const int *rp, const double *val, const int *hi,

@@ -174,8 +174,9 @@ static int krige_no_state(const char *who, const char *prepare)
 // The chunk loop of an apply call: rows [b, b + mc) of the caller's column-major X_pred (m x p) and locs_pred (m x 2) into the
 // state's staging, their SoA in the prediction branch's parameters (full_scale: as krige_prepare_finish), body(b, mc, global
 // range) -- the entry's own launches, which leave the chunk's outputs in K->st and K->qd --, those to the caller's rows, and
-// the stream drained before the staging, the host's and the state's, is used again.  before(b, mc) comes first: the entry's
-// host work on the chunk and its own uploads, so that every copy of a chunk goes ahead of its first launch, in one burst.
+// the stream drained before the staging, the host's and the state's, is used again.  before(b, mc) comes behind the uploads
+// of the chunk's rows (K->Xp, K->lp) and ahead of every launch of the loop: the entry's step that makes the chunk's pattern --
+// host work and uploads of its own (cocons_krige_taper_apply), or the search on the device from K->lp (..._apply_delta).
 template <class Before, class Body>
 static int krige_chunks(cocons_fit *f, KrigeHeld *K, const char *who, bool full_scale, int m, const double *locs_pred,
                         const double *X_pred, double *stochastic, double *quadform, Before &&before, Body &&body)
@@ -190,9 +191,9 @@ static int krige_chunks(cocons_fit *f, KrigeHeld *K, const char *who, bool full_
         const int mc = std::min(rows, m - b);
         for (int j = 0; j < p; ++j) memcpy(&hX[(size_t)j * mc], X_pred + b + (size_t)j * m, (size_t)mc * sizeof(double));
         for (int j = 0; j < 2; ++j) memcpy(&hl[(size_t)j * mc], locs_pred + b + (size_t)j * m, (size_t)mc * sizeof(double));
-        if (int rc = before(b, mc)) return rc;
         HIPCHK_AT(who, upload_canon(K->Xp, hX.data(), (size_t)mc * p, s));
         HIPCHK_AT(who, upload_canon(K->lp, hl.data(), (size_t)mc * 2, s));
+        if (int rc = before(b, mc)) return rc;
         launch_loc_params(loc_args(mc, p, K->Xp, K->lp, K->locp, rows, tv, ms.smooth_kind, f->smooth_limits), s);
         if (int rc = body(b, mc, ms.gr)) return rc;
         HIPCHK_AT(who, hipMemcpyAsync(stochastic + b, K->st, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -677,6 +678,77 @@ extern "C" int cocons_krige_taper_apply(cocons_fit *f, int m, const double *locs
                                                                      K->val, K->tv, K->st, K->qd), s));
         return 0;
     });
+}
+
+// cocons_krige_taper_apply with the pattern found on the device: per chunk, from its locations in K->lp and the
+// grid over the observations in the handle's order (f->dlocs: no taper_inv), the count pass with the histogram of the tile
+// columns, both scans, the nt + 1 bucket offsets to the host -- the one wait of the step, and what says how many entries the
+// chunk holds --, then columns, taper values and buckets straight into the staging.
+extern "C" int cocons_krige_taper_apply_delta(cocons_fit *f, int m, const double *locs_pred, const double *X_pred, double delta,
+                                              int kind, double *stochastic, double *quadform, long long *nnz_out)
+{
+    const char *who = "cocons_krige_taper_apply_delta";
+    if (m < 0 || (m > 0 && (!locs_pred || !X_pred || !stochastic || !quadform)))
+        return fail(-1, "%s: bad argument (m < 0 or a null pointer)", who);
+    if (int rc = pattern_check_delta(who, delta, kind)) return rc;
+    if (m > 0)
+        if (int rc = pattern_check_finite(who, "locs_pred", (size_t)m, locs_pred)) return rc;
+    if (!f) return fail(-1, "%s: null fit handle", who);
+    FIT_ENTER(f);
+    if (int rc = krige_taper_handle(f, who)) return rc;
+    KrigeTaperState *K = f->krige_taper.get();
+    if (!K) return krige_no_state(who, "cocons_krige_taper_prepare");
+    if (m == 0) { if (nnz_out) *nnz_out = 0; return 0; }
+    const int nt = f->nt, n = f->n, rows = K->rows;
+    hipStream_t s = f->stream;
+    // the grid over the observations: made by the first call on this state, and again for another delta
+    if (!K->grid || K->grid->delta != delta) {
+        HIPCHK_AT(who, hipStreamSynchronize(s));
+        K->grid.reset(new PatternGridBufs());
+        HIPCHK_AT(who, K->bwork.alloc((size_t)3 * (nt + 1)));
+        if (int rc = pattern_grid_build(who, *K->grid, n, f->h_locs.data(), f->h_locs.data() + n, f->dlocs, f->dlocs + n, delta, s)) {
+            hipStreamSynchronize(s);
+            K->grid.reset();
+            return rc;
+        }
+    }
+    const PatternTargets &T = K->grid->t;
+    int *hist = K->bwork, *d_boff = hist + (nt + 1), *cursor = d_boff + (nt + 1);
+    std::vector<int> boff((size_t)nt + 1);
+    long long total = 0;
+    int ne = 0;
+    auto pattern = [&](int, int mc) -> int {
+        const double *qx = K->lp, *qy = K->lp + mc;
+        HIPCHK_AT(who, hipMemsetAsync(hist, 0, ((size_t)nt + 1) * sizeof(int), s));
+        HIPCHK_AT(who, launch_pattern_count(T, mc, qx, qy, delta, K->rp, hist, TILE, s));
+        HIPCHK_AT(who, launch_scan_exclusive(K->rp, K->rp, mc, 1, nullptr, s));
+        HIPCHK_AT(who, launch_scan_exclusive(hist, d_boff, nt, 0, nullptr, s));
+        HIPCHK_AT(who, hipMemcpyAsync(boff.data(), d_boff, ((size_t)nt + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT(who, hipStreamSynchronize(s));
+        // (a bucket holds at most rows x 128 entries, so the differences are exact even where the offsets wrapped)
+        long long cnt = 0;
+        for (int I = 0; I < nt; ++I) cnt += (long long)(unsigned)(boff[I + 1] - boff[I]);
+        if (cnt > INT_MAX)
+            return fail(-1, "%s: a chunk of %d rows holds %lld entries, more than an int counts (prepare with a smaller max_rows)",
+                        who, mc, cnt);
+        ne = (int)cnt;
+        total += cnt;
+        if (int rc = krige_taper_stage(K, (size_t)ne, who)) return rc;      // (the stream is idle)
+        if (ne > 0) {
+            HIPCHK_AT(who, launch_pattern_fill(T, mc, qx, qy, delta, kind, K->rp, K->ci, K->tv, s));
+            HIPCHK_AT(who, hipMemcpyAsync(cursor, d_boff, (size_t)nt * sizeof(int), hipMemcpyDeviceToDevice, s));
+            HIPCHK_AT(who, launch_pattern_buckets(mc, K->rp, K->ci, TILE, rows, cursor, K->bdst, K->bsrc, s));
+        }
+        return 0;
+    };
+    const int rc = krige_chunks(f, K, who, true, m, locs_pred, X_pred, stochastic, quadform, pattern, [&](int, int mc, double) -> int {
+        launch_taper(krige_pred_taper(f, K, mc, ne, K->ci, K->rp, K->locp, (size_t)rows, K->val), s);
+        HIPCHK_AT(who, launch_krige_band_solve(krige_band_solve_args(f, K, K->ring, (size_t)rows, mc, boff.data(), K->bdst, K->bsrc,
+                                                                     K->val, K->tv, K->st, K->qd), s));
+        return 0;
+    });
+    if (rc == 0 && nnz_out) *nnz_out = total;
+    return rc;
 }
 
 extern "C" int cocons_krige_taper_release(cocons_fit *f)

@@ -170,6 +170,16 @@ struct KrigeState : KrigeHeld {
     long long bytes = 0;          // device bytes held
 };
 
+// The binned targets of a pattern search (pattern.hip), owned: the grid for `delta` over n points whose
+// coordinates (t.x, t.y) belong to somebody else, the cell-sorted list and the binning's scratch.
+struct PatternGridBufs {
+    PatternTargets t;
+    double delta = 0.0;
+    DevBuf<int> cstart, sidx, cursor;
+    DevBuf<double> sxy;
+    long long bytes = 0;          // device bytes of the buffers above
+};
+
 // Kriging state of a taper handle (cocons_krige_taper_prepare / _apply / _release): the band factor packed
 // per tile column and a ring of W tile columns for the chunk.
 struct KrigeTaperState : KrigeHeld {
@@ -182,7 +192,15 @@ struct KrigeTaperState : KrigeHeld {
     size_t ecap = 0;
     BandPlan plan;                // first packed tile of every tile column, slots of the ring (band_plan.hpp)
     long long fixed_bytes = 0;    // device bytes of everything but the CSR staging
-    long long bytes() const { return fixed_bytes + (long long)(ecap * (3 * sizeof(int) + 2 * sizeof(double))); }
+    // cocons_krige_taper_apply_delta, made by its first call: the grid over the observations in the handle's
+    // order, and the bucket histogram, offsets and cursors of a chunk (3 x (nt + 1) ints)
+    std::unique_ptr<PatternGridBufs> grid;
+    DevBuf<int> bwork;
+    long long bytes() const
+    {
+        return fixed_bytes + (long long)(ecap * (3 * sizeof(int) + 2 * sizeof(double))) +
+               (grid ? grid->bytes + (long long)(bwork.count() * sizeof(int)) : 0);
+    }
 };
 
 // host-side plan of one evaluation's exchange: per block k the rows below it, dealt to their owners and packed
@@ -619,6 +637,13 @@ cocons_fit *taper_create_ordered(int n, int p, int r, const double *locs, const 
                                  const double *smooth_limits, int device, int nnz, const int *colindices, const int *rowpointers,
                                  const double *taper_entries, const std::vector<int> &perm, bool check_fit);
 cocons_fit *clone_for_slot(cocons_fit *f, bool want_engine);
+// ... the builder of taper patterns: the refusals every entry that takes (delta, kind) and coordinates shares
+// (npts points, column-major npts x 2), and the grid over n targets -- hx, hy: their coordinates on the host (the box), dx,
+// dy: on the device -- binned on s (not waited for)
+int pattern_check_delta(const char *who, double delta, int kind);
+int pattern_check_finite(const char *who, const char *what, size_t npts, const double *pts);
+int pattern_grid_build(const char *who, PatternGridBufs &G, int n, const double *hx, const double *hy, const double *dx,
+                       const double *dy, double delta, hipStream_t s);
 // ... and what they call in api_shard.hip: the sharded cocons_neg2loglik_dense, and cocons_fit_destroy's share
 int sharded_eval(cocons_fit *f, const double *theta, const double *mean, double *sum_logliks, double *parts);
 void shard_events_destroy(ShardState *S);

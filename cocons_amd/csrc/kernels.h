@@ -5,6 +5,7 @@
 #include <atomic>
 #include <vector>
 #include "../../include/cocons_hip.h"
+#include "pattern_grid.hpp"
 
 namespace cocons {
 
@@ -368,6 +369,52 @@ void launch_krige_schur(const double *V, size_t ldv, int m, int c_lo, int c_hi, 
 void launch_sym_mirror(double *S, size_t lds, int n, hipStream_t s);
 // out[i + s ldo] = Y[pos[i] + s ldy] for i < n, s < ncol
 void launch_gather_rows(const double *Y, int ldy, const int *pos, int n, int ncol, double *out, int ldo, hipStream_t s);
+
+// ---- taper patterns from delta (pattern.hip) -----------------------------------------------------------------
+// The taper of an entry at distance d, h = d / delta in [0, 1] -- spam's cov.wend1, cov.wend2 and cov.sph with
+// theta = c(delta, 1) --, by plain products:
+//   COCONS_TAPER_WEND1   (1 - h)^4 (4 h + 1)
+//   COCONS_TAPER_WEND2   (1 - h)^6 (35 h^2 + 18 h + 3) / 3
+//   COCONS_TAPER_SPH     1 - 1.5 h + 0.5 h^3
+__host__ __device__ inline double pattern_taper_value(int kind, double h)
+{
+    const double u = 1.0 - h, u2 = u * u;
+    if (kind == COCONS_TAPER_WEND1) return (u2 * u2) * (4.0 * h + 1.0);
+    if (kind == COCONS_TAPER_WEND2) return ((u2 * u2) * u2) * (((35.0 * h) * h + 18.0 * h) + 3.0) / 3.0;
+    return (1.0 - 1.5 * h) + (0.5 * h) * (h * h);
+}
+// The targets of a search, binned (launch_pattern_bin): the grid, the points (x, y: n each), and the cell-sorted list --
+// cstart (nx ny + 1: first place of every cell), sidx (n: the point at every place) and its coordinates sx, sy.
+struct PatternTargets {
+    PatternGrid g;
+    int n = 0;
+    const double *x = nullptr, *y = nullptr;
+    int *cstart = nullptr, *sidx = nullptr;
+    double *sx = nullptr, *sy = nullptr;
+};
+inline size_t pattern_cells(const PatternGrid &g) { return (size_t)g.nx * (size_t)g.ny; }
+// out[i] = base + in[0] + .. + in[i - 1] for i <= n (n + 1 outputs; out may be in), *total (device, may be null) = the sum in
+// 64 bits -- the outputs are ints and mean nothing when it passes INT_MAX.  One workgroup, a fixed order.
+hipError_t launch_scan_exclusive(const int *in, int *out, int n, int base, long long *total, hipStream_t s);
+// bin: histogram of the targets' cells, scan, fill of the cell-sorted list.  cursor: nx ny + 1 ints of scratch.  The order
+// inside a cell is whatever the atomics give; nothing that leaves the builder depends on it.
+hipError_t launch_pattern_bin(const PatternTargets &t, int *cursor, hipStream_t s);
+// count: rowcnt[i] = targets within delta of query i (m queries qx, qy), one wave per row.  hist (may be null): nbucket ints,
+// zero beforehand; every accepted pair adds one to hist[target / tile].
+hipError_t launch_pattern_count(const PatternTargets &t, int m, const double *qx, const double *qy, double delta, int *rowcnt,
+                                int *hist, int tile, hipStream_t s);
+// fill: for the 1-based row pointers rp of those counts, ci = the accepted targets of every row, 1-based and ascending, and
+// ent = their taper values (kind: COCONS_TAPER_*).  Rows of up to PATTERN_SORT_LDS entries are sorted in LDS, longer ones by
+// ranks in global memory.
+constexpr int PATTERN_SORT_LDS = 512;
+hipError_t launch_pattern_fill(const PatternTargets &t, int m, const double *qx, const double *qy, double delta, int kind,
+                               const int *rp, int *ci, double *ent, hipStream_t s);
+// buckets: band_buckets (band_plan.hpp) on the device for a chunk whose columns are already in the handle's order: entry w
+// (row i, 1-based column c + 1) takes a place k of bucket c / tile -- cursor[c / tile]++, cursor starting as a copy of the
+// bucket offsets --, bdst[k] = i + (c % tile) * stride, bsrc[k] = w.  Places inside a bucket are dealt by atomics; the ring
+// load is a scatter to distinct addresses and does not see their order.
+hipError_t launch_pattern_buckets(int m, const int *rp, const int *ci, int tile, int stride, int *cursor, int *bdst, int *bsrc,
+                                  hipStream_t s);
 
 // ---- analytic gradient of the dense -2 log-likelihood (grad.hip) ----------------------------------------------------------
 constexpr int GSITE_FIELDS = 4;    // launch_grad_site: dtilt/deta, cot(tilt), dlog(nu_ij)/deta_smooth, exp(eta_sd)

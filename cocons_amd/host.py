@@ -528,6 +528,40 @@ class CoconsFit:
                 "update_flops": ms[7], "dag_ms": ms[8], "dag_flops": ms[9]}
 
 
+TAPER_KINDS = {"wend1": 1, "wend2": 2, "sph": 3}
+
+
+def _taper_kind(kind) -> int:
+    if isinstance(kind, str):
+        if kind not in TAPER_KINDS:
+            raise ValueError("kind must be one of %s" % sorted(TAPER_KINDS))
+        return TAPER_KINDS[kind]
+    return int(kind)
+
+
+def taper_pattern(locs, delta, kind="wend1", newlocs=None, device=0):
+    """(colindices, rowpointers, entries) of the taper between `newlocs` (default: locs themselves) and locs, found on the
+    device (cocons_taper_pattern): spam's nearest.dist(newlocs, locs, delta) -- every pair with d <= delta, zero distances
+    and the diagonal stored, 1-based CSR with ascending columns -- with cov.wend1 / cov.wend2 / cov.sph at
+    theta = c(delta, 1) as entries.  One count call, then the fill call."""
+    L = _lib.load()
+    locs = _f(locs)
+    n = locs.shape[0]
+    q = None if newlocs is None else _f(newlocs)
+    m = n if q is None else q.shape[0]
+    k = _taper_kind(kind)
+    nnz = ctypes.c_longlong(0)
+    rp = np.zeros(m + 1, dtype=np.int32)
+    qp = None if q is None else _p(q)
+    _lib.check(L.cocons_taper_pattern(n, _p(locs), m, qp, float(delta), k, int(device), 0, ctypes.byref(nnz), _ip(rp), None,
+                                      None), "cocons_taper_pattern")
+    ci = np.zeros(max(int(nnz.value), 1), dtype=np.int32)
+    ent = np.zeros(max(int(nnz.value), 1))
+    _lib.check(L.cocons_taper_pattern(n, _p(locs), m, qp, float(delta), k, int(device), int(nnz.value), ctypes.byref(nnz),
+                                      _ip(rp), _ip(ci), _p(ent)), "cocons_taper_pattern")
+    return ci[:nnz.value], rp, ent[:nnz.value]
+
+
 class CoconsTaperFit(CoconsFit):
     """Handle of an optimisation of GetNeg2loglikelihoodTaper: (locs, x_covariates, z, smooth.limits) plus the
     spam pattern of `ref_taper` (colindices / rowpointers, 1-based, symmetric, diagonal stored) and its entries.
@@ -556,6 +590,28 @@ class CoconsTaperFit(CoconsFit):
                                             int(device), int(ci.size), _ip(ci), _ip(rp), _p(te))
         if not self._h:
             raise _lib.CoconsHipError("cocons_fit_create_taper failed: " + _lib.last_error())
+
+    @classmethod
+    def from_delta(cls, locs, x_covariates, z, smooth_limits, delta, kind="wend1", device=-1):
+        """The handle of the taper `kind` with range `delta`: the library finds the pattern and its entries itself
+        (cocons_fit_create_taper_delta), then builds what __init__ builds from them."""
+        self = cls.__new__(cls)
+        L = _lib.load()
+        self._L = L
+        locs, X = _f(locs), _f(x_covariates)
+        self.n, self.p = X.shape
+        if locs.shape != (self.n, 2):
+            raise ValueError("locs must be n x 2")
+        z = _f(np.asarray(z, dtype=np.float64).reshape(self.n, -1))
+        self.r = z.shape[1]
+        self.q = 0
+        self.smooth_limits = np.asarray(smooth_limits, dtype=np.float64).copy()
+        self.x_covariates = X
+        self._h = L.cocons_fit_create_taper_delta(self.n, self.p, self.r, _p(locs), _p(X), _p(z), _p(self.smooth_limits),
+                                                  int(device), float(delta), _taper_kind(kind))
+        if not self._h:
+            raise _lib.CoconsHipError("cocons_fit_create_taper_delta failed: " + _lib.last_error())
+        return self
 
     def neg2loglik_grad_core(self, theta_list):
         """The value of `neg2loglik_core` on this handle and its analytic gradient (cocons_neg2loglik_grad_taper): returns
@@ -653,6 +709,19 @@ class CoconsTaperFit(CoconsFit):
         st, qf = np.empty(m), np.empty(m)
         _lib.check(self._L.cocons_krige_taper_apply(self._h, m, _p(lp), _p(Xp), int(ci.size), _ip(ci), _ip(rp), _p(te),
                                                     _p(st), _p(qf)), "cocons_krige_taper_apply")
+        return st, qf
+
+    def krige_taper_core_delta(self, locs_pred, x_covariates_pred, delta, kind="wend1"):
+        """krige_taper_core without a pattern: the neighbours within `delta` and the taper `kind` are found per chunk on the
+        device (cocons_krige_taper_apply_delta).  `last_pattern_nnz` then holds the entries the call's pattern had."""
+        lp, Xp = _f(locs_pred), _f(x_covariates_pred)
+        m = Xp.shape[0]
+        st, qf = np.empty(m), np.empty(m)
+        nnz = ctypes.c_longlong(0)
+        _lib.check(self._L.cocons_krige_taper_apply_delta(self._h, m, _p(lp), _p(Xp), float(delta), _taper_kind(kind),
+                                                          _p(st), _p(qf), ctypes.byref(nnz)),
+                   "cocons_krige_taper_apply_delta")
+        self.last_pattern_nnz = int(nnz.value)
         return st, qf
 
     def krige_taper_release(self):
@@ -780,6 +849,23 @@ def cocoPredict_sparse_chunked(theta_list, locs, newlocs, X_std, X_pred_std, smo
         f.krige_taper_prepare(theta_list, max_rows=max_rows)
         try:
             st, qf = f.krige_taper_core(newlocs, X_pred_std, pred_taper)
+        finally:
+            f.krige_taper_release()
+    finally:
+        if own:
+            f.close()
+    return _sparse_predict_tail(theta_list, X_pred_std, st, qf, type)
+
+
+def cocoPredict_sparse_delta(theta_list, locs, newlocs, X_std, X_pred_std, smooth_limits, z, ref_taper, delta, kind="wend1",
+                             type="pred", fit=None, max_rows=0):
+    """cocoPredict_sparse_chunked without pred_taper: the library finds the neighbours of the new locations within `delta`
+    and evaluates the taper `kind` itself."""
+    f, own = (fit, False) if fit is not None else (CoconsTaperFit(locs, X_std, z, smooth_limits, *ref_taper), True)
+    try:
+        f.krige_taper_prepare(theta_list, max_rows=max_rows)
+        try:
+            st, qf = f.krige_taper_core_delta(newlocs, X_pred_std, delta, kind)
         finally:
             f.krige_taper_release()
     finally:

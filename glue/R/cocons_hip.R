@@ -436,6 +436,26 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
   res[[2]]
 }
 
+# the taper itself from delta, found on the device: the slots of spam::nearest.dist(newlocs, locs, delta) (newlocs = NULL:
+# nearest.dist(locs, delta = delta, upper = NULL)) with cov.wend1 / cov.wend2 / cov.sph at theta = c(delta, 1) as entries
+#   tp <- .cocons.hip.taper.pattern(locs, delta, "wend1")   # list(colindices, rowpointers, entries), 1-based
+.cocons.hip.taper.kind <- function(kind) {
+  k <- match(kind, c("wend1", "wend2", "sph"))
+  if (is.na(k)) stop("kind must be one of wend1, wend2, sph")
+  as.integer(k)
+}
+
+.cocons.hip.taper.pattern <- function(locs, delta, kind = "wend1", newlocs = NULL, device = 0L) {
+  res <- .Call(`_cocons_hip_taper_pattern`, locs, newlocs, as.double(delta), .cocons.hip.taper.kind(kind), as.integer(device))
+  list(colindices = res[[1]], rowpointers = res[[2]], entries = res[[3]])
+}
+
+# .cocons.hip.krige.taper without pred_taper: neighbours and taper values come from delta, chunk by chunk on the device
+.cocons.hip.krige.taper.delta <- function(fit, newlocs, X_pred, delta, kind = "wend1") {
+  res <- .Call(`_cocons_hip_krige_taper_delta`, fit, newlocs, X_pred, as.double(delta), .cocons.hip.taper.kind(kind))
+  res[[2]]
+}
+
 # joint prediction against the same held band factor: the predictive covariance between the new locations and, with
 # iiderrors (m x nsim), conditional draws of the tapered model (the reference's cocoSim has no conditional branch for
 # sparse objects).  uu_taper: the taper between the new locations, spam::nearest.dist(newlocs, delta = delta, upper = NULL)

@@ -931,6 +931,51 @@ SEXP _cocons_hip_krige_taper(SEXP fitp, SEXP locs_pred, SEXP X_pred, SEXP colind
     return out;
 }
 
+/* the taper between newlocs (m x 2, or NULL: locs themselves) and locs (n x 2) from delta, found on the device: what
+ * spam::nearest.dist(newlocs, locs, delta) and cov.wend1 / cov.wend2 / cov.sph (kind 1 / 2 / 3, theta = c(delta, 1)) give.
+ * list(colindices, rowpointers, entries) -- the three slots of the spam object, 1-based */
+SEXP _cocons_hip_taper_pattern(SEXP locs, SEXP newlocs, SEXP delta, SEXP kind, SEXP device)
+{
+    if (!Rf_isReal(locs) || Rf_ncols(locs) != 2) Rf_error("locs must be a double matrix with 2 columns");
+    const int n = Rf_nrows(locs), self = Rf_isNull(newlocs);
+    if (!self && (!Rf_isReal(newlocs) || Rf_ncols(newlocs) != 2)) Rf_error("newlocs must be a double matrix with 2 columns");
+    const int m = self ? n : Rf_nrows(newlocs);
+    const double *q = self ? NULL : REAL(newlocs);
+    const double d = Rf_asReal(delta);
+    const int k = Rf_asInteger(kind), dev = Rf_asInteger(device);
+    long long nnz = 0;
+    SEXP rp = PROTECT(Rf_allocVector(INTSXP, (R_xlen_t)m + 1));
+    hip_check(cocons_taper_pattern(n, REAL(locs), m, q, d, k, dev, 0, &nnz, INTEGER(rp), NULL, NULL), "taper pattern (count)");
+    SEXP ci = PROTECT(Rf_allocVector(INTSXP, (R_xlen_t)nnz));
+    SEXP en = PROTECT(Rf_allocVector(REALSXP, (R_xlen_t)nnz));
+    /* (zero-length vectors still have a data pointer the library may be given) */
+    hip_check(cocons_taper_pattern(n, REAL(locs), m, q, d, k, dev, nnz, &nnz, INTEGER(rp), INTEGER(ci), REAL(en)),
+              "taper pattern");
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 3));
+    SET_VECTOR_ELT(out, 0, ci);
+    SET_VECTOR_ELT(out, 1, rp);
+    SET_VECTOR_ELT(out, 2, en);
+    UNPROTECT(4);
+    return out;
+}
+
+/* _cocons_hip_krige_taper without pred_taper: the neighbours of the new locations within delta and the taper `kind` are found
+ * on the device, chunk by chunk.  list(status, cbind(stochastic, quadform)) */
+SEXP _cocons_hip_krige_taper_delta(SEXP fitp, SEXP locs_pred, SEXP X_pred, SEXP delta, SEXP kind)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), m = Rf_nrows(X_pred);
+    if (Rf_ncols(X_pred) != p || Rf_nrows(locs_pred) != m || Rf_ncols(locs_pred) != 2)
+        Rf_error("prediction design / locations do not match the fit");
+    SEXP v = PROTECT(Rf_allocMatrix(REALSXP, m, 2));
+    int rc = cocons_krige_taper_apply_delta(f, m, REAL(locs_pred), REAL(X_pred), Rf_asReal(delta), Rf_asInteger(kind), REAL(v),
+                                            REAL(v) + m, NULL);
+    hip_check(rc, "cocoPredict (sparse, krige from delta)");
+    SEXP out = status_value(rc, v);
+    UNPROTECT(1);
+    return out;
+}
+
 /* one taper as list(colindices, rowpointers, entries) for m rows: its slots checked, its number of entries returned */
 static int taper_slots(SEXP taper, int m, const char *what, SEXP *ci, SEXP *rp, SEXP *en)
 {
@@ -1041,6 +1086,8 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_krige_taper_prepare", (DL_FUNC)&_cocons_hip_krige_taper_prepare, 5},
     {"_cocons_hip_krige_taper", (DL_FUNC)&_cocons_hip_krige_taper, 6},
     {"_cocons_hip_krige_taper_joint", (DL_FUNC)&_cocons_hip_krige_taper_joint, 8},
+    {"_cocons_hip_taper_pattern", (DL_FUNC)&_cocons_hip_taper_pattern, 5},
+    {"_cocons_hip_krige_taper_delta", (DL_FUNC)&_cocons_hip_krige_taper_delta, 5},
     {"_cocons_hip_krige_taper_release", (DL_FUNC)&_cocons_hip_krige_taper_release, 1},
     {"_cocons_hip_sim", (DL_FUNC)&_cocons_hip_sim, 5},
     {"_cocons_hip_sim_cond", (DL_FUNC)&_cocons_hip_sim_cond, 8},

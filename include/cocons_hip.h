@@ -98,6 +98,34 @@ cocons_fit *cocons_fit_create_taper(int n, int p, int r, const double *locs, con
                                     const double *smooth_limits, int device, int nnz, const int *colindices,
                                     const int *rowpointers, const double *taper_entries);
 
+/* ---- taper patterns from delta: neighbour search and taper values on the device -----------------------------------
+ * What spam::nearest.dist and the taper function build in R (R/predict.R:219-235, R/optim.R:377, R/sim.R:194).  The taper of a
+ * pair at distance d, with h = d / delta -- spam's cov.wend1, cov.wend2 and cov.sph with theta = c(delta, 1):          */
+#define COCONS_TAPER_WEND1 1   /* (1 - h)^4 (4 h + 1)                    */
+#define COCONS_TAPER_WEND2 2   /* (1 - h)^6 (35 h^2 + 18 h + 3) / 3      */
+#define COCONS_TAPER_SPH   3   /* 1 - 1.5 h + 0.5 h^3                    */
+
+/* cocons_taper_pattern: every pair of a query point (locs_query, m x 2; NULL: the n points of locs themselves, m is then
+ * ignored) and a point of locs (n x 2, both column-major) with d = sqrt(dx dx + dy dy) <= delta in fp64, as spam stores it:
+ * 1-based CSR, rows = queries, columns = indices into locs, strictly increasing within a row, `entries` the taper `kind` of
+ * every pair.  Pairs at d = 0 are stored (the diagonal of the self pattern, coincident points).  Stateless: host buffers in
+ * and out, device memory of the call only.  The arrays are a function of the inputs alone (two calls agree bit for bit), and
+ * the self pattern with its entries is symmetric to the bit.
+ * colindices == NULL: the count call -- *nnz and rowpointers (rows + 1) are written, entries is not read.  Otherwise `cap`
+ * (the room in colindices / entries) must be >= the pattern's nnz: if it is not, -1, the message names the nnz needed and
+ * nothing is written.  A pattern of more than INT_MAX - 1 entries is refused, naming the count.
+ * -1, with a message starting with the entry's name, before any device work and with the outputs untouched: a null locs, nnz
+ * or rowpointers, a null entries with colindices given, n < 1, m < 1 with a query set, delta not finite or <= 0, kind
+ * outside 1 .. 3, a coordinate that is not finite.                                                                    */
+int cocons_taper_pattern(int n, const double *locs, int m, const double *locs_query /* NULL: self */, double delta, int kind,
+                         int device, long long cap, long long *nnz, int *rowpointers, int *colindices, double *entries);
+
+/* cocons_fit_create_taper from delta: the self pattern of locs and its taper entries by cocons_taper_pattern's builder, then
+ * the handle exactly as cocons_fit_create_taper makes it from those arrays (the same code).  Refusals as above (null
+ * pointers, n < 1, delta, kind, coordinates), then cocons_fit_create_taper's.  NULL + cocons_last_error() on failure.   */
+cocons_fit *cocons_fit_create_taper_delta(int n, int p, int r, const double *locs, const double *X, const double *z,
+                                          const double *smooth_limits, int device, double delta, int kind);
+
 /* Kriging from a held factor: cocoPredict (R/predict.R:136-183) at any number of new locations for one theta.
  * cocons_krige_prepare assembles Sigma(theta), factors it once with (z[:, z_col] - X mean)' as the one right-hand side and
  * keeps, in buffers of its own on the handle: the lower factor in packed 128 x 128 tiles (nt (nt + 1) / 2 of them, not the
@@ -176,6 +204,21 @@ int cocons_krige_taper_apply(cocons_fit *fit, int m, const double *locs_pred, co
                              double *stochastic, double *quadform);
 int cocons_krige_taper_release(cocons_fit *fit);
 int cocons_krige_taper_info(cocons_fit *fit, long long *out6);
+
+/* cocons_krige_taper_apply without a pattern from the caller: pred_taper is what nearest.dist(locs_pred, locs, delta) and the
+ * taper `kind` (COCONS_TAPER_*) give, found per chunk on the device against the observations in the handle's own order --
+ * neighbour search, taper values and the buckets per tile column land straight in the state's CSR staging; the nt + 1 bucket
+ * offsets are the only thing that comes back to the host, and no per-entry data crosses to the device.  Outputs, chunking
+ * and guarantees are cocons_krige_taper_apply's (independence of max_rows bit for bit, exactly 0.0 and 0.0 for a row without
+ * neighbours), and so are the bits for the pattern cocons_taper_pattern(locs, locs_pred) exports.  *nnz_out (may be NULL):
+ * the pattern's entries over all m rows.  The grid over the observations is built by the first such call on a prepared
+ * state, belongs to the state (counted in cocons_krige_taper_info's bytes, dropped with it); the staging grows, with the
+ * stream drained, when a chunk needs more entries than it holds.
+ * -1, with a message starting with the entry's name, before any device work and with the outputs untouched: m < 0, a null
+ * pointer, delta not finite or <= 0, kind outside 1 .. 3, a coordinate of locs_pred that is not finite, a null, dense or
+ * sharded handle, no prepared state.                                                                                       */
+int cocons_krige_taper_apply_delta(cocons_fit *fit, int m, const double *locs_pred, const double *X_pred, double delta, int kind,
+                                   double *stochastic, double *quadform, long long *nnz_out /* may be NULL */);
 
 /* Joint prediction for a tapered fit from the held band factor, against the theta, realisation and mean of
  * cocons_krige_taper_prepare: cocons_krige_joint's outputs for type = "sparse" (the reference's cocoSim has no

@@ -38,6 +38,13 @@ int cocons_debug_fit_memory(struct cocons_fit *fit, long long *out4);
  * call.  0, or -1 on a null argument or nxb < 0.                                                                          */
 int cocons_debug_rhs_layout(struct cocons_fit *fit, int nxb, int *out5);
 
+/* The grid of the taper-pattern builder (cocons_taper_pattern, cocons_krige_taper_apply_delta) for n targets (locs, n x 2
+ * column-major) and delta, and the clamped cell of each of m points (pts, m x 2 column-major), both from the header the
+ * kernels use: geom5 = { origin x, origin y, cell edge, cells along x, cells along y }, cells = m pairs (cx, cy), each
+ * coordinate in [-1, count] (-1 and count: outside the targets' box on that side).  Host only: no HIP call.  0, or -1 on a
+ * null argument, n < 1, m < 0, a delta that is not finite or <= 0, or a target coordinate that is not finite.            */
+int cocons_debug_pattern_cells(int n, const double *locs, double delta, int m, const double *pts, double *geom5, int *cells);
+
 /* Diagnostics of cocons_neg2loglik_grad_taper: (S(theta)^-1)_ij at every stored entry of the pattern the taper handle was
  * created with, in the caller's CSR order (out_nnz: one double per entry of that pattern), by the gradient's selected
  * inverse; bytes_out (may be NULL): the device bytes the gradient holds on the handle.  0, a failing minor k > 0, or < 0. */
