@@ -21,6 +21,22 @@ envelope does -- the only way to shape an envelope without touching the matrix.
   hub              900 uniform sites; site HUB is joined to all others by stored zeros; the library's order.
   hub_caller       the same in the caller's order: every column reaches the last tile row, W = nt, unpacked buffer.
   lshape           897 sites sorted by x and ONE stored zero at row (nt - 1) 128 - 1, column 0; the caller's order.
+
+Bands wider than eight tile rows (tests/golden/WIDE_BANDS_REPORT.md).  These three have a theta of their own (wide_theta: a
+longer range and a nugget as large as the variance keep cond(S) at about 500 and the far tiles of the factor audible); the flat ones use
+the spherical taper (1 - h)^2 (1 + h / 2), ten times Wendland-1 near h = 0.8, evaluated in the order of operations of the
+device's own pattern search so that a handle made from delta alone holds the same doubles.  tests/
+test_taper_envelope_cases.py asserts for each that zeroing every tile (I, J), I - J >= 8, of the dense factor moves the
+quadratic form and the kriging prediction far above the suite's tolerances: without that a wide case tests nothing.
+
+  flat9            1665 = 13 x 128 + 1 sites on a strip, sorted by x, delta = 0.6, r = 2; the caller's order.  A flat band:
+                   raw reach 9, W = 10 by the two-column block rule (the tiles at distance W - 1 exist in even columns only
+                   and are structurally zero), six columns at reach W or W - 1.
+  flat10_long      2433 = 19 x 128 + 1 sites on the same strip, delta = 0.37; the caller's order.  W = 10 of nt = 20: the ring
+                   wraps twice.  Only the entries whose reference is S and one factorisation run on it.
+  tall             a clique of 1300 sites in a disc of diameter 0.28 < delta = 0.3 first, then 569 scattered sites by x; the
+                   caller's order.  Column 0 is twelve tile rows tall, the scattered columns stay at the floor.
+  tall_rcm         the same observations in the library's order (W = 11, the clique behind the scattered sites).
 """
 from __future__ import annotations
 
@@ -158,6 +174,47 @@ def _distances(a, b):
     return np.hypot(a[:, None, 0] - b[None, :, 0], a[:, None, 1] - b[None, :, 1])
 
 
+def wide_theta():
+    """theta of the cases wider than eight tile rows: range intercept log 0.6, nugget intercept log 1 (cond(S) about 500:
+    with theta_full's they stand at 2.5e4 .. 4.8e4, and at log 0.45 / log 0.1, cond(S) 4e3, the two routes of the sparse
+    prediction still differed by more than the bound the suite holds them to)"""
+    th = theta_full()
+    th["scale"] = np.array([np.log(0.6), 0.2, 0.1])
+    th["nugget"] = np.array([np.log(1.0), 0.0, 0.0])
+    return th
+
+
+def _spherical(d, delta):
+    """(1 - h)^2 (1 + h / 2) = 1 - 1.5 h + 0.5 h^3, in the device's order of operations"""
+    h = np.minimum(d / delta, 1.0)
+    return (1.0 - 1.5 * h) + (0.5 * h) * (h * h)
+
+
+def _wendland1_device(d, delta):
+    """_wendland1 in the device's order of operations"""
+    h = np.minimum(d / delta, 1.0)
+    u2 = (1.0 - h) * (1.0 - h)
+    return (u2 * u2) * (4.0 * h + 1.0)
+
+
+def _distances_device(a, b):
+    """sqrt(dx dx + dy dy), as the device's pattern search forms a distance (hypot may differ in the last bit)"""
+    dx, dy = a[:, None, 0] - b[None, :, 0], a[:, None, 1] - b[None, :, 1]
+    return np.sqrt(dx * dx + dy * dy)
+
+
+# kind: the name the library knows the case's taper by (CoconsTaperFit.from_delta, krige_taper_core_delta); the cases not
+# listed are Wendland-1 through hypot, as they always were
+KIND_OF = {"flat9": "sph", "flat10_long": "sph", "tall": "wend1"}
+_TAPER_OF = {"sph": _spherical, "wend1": _wendland1_device}
+
+
+def device_pattern(a, b, delta, kind):
+    """(colindices, rowpointers, entries) of rows a against columns b as the library's own search states them: d <= delta"""
+    d = _distances_device(a, b)
+    return _csr(d <= delta, _TAPER_OF[kind](d, delta))
+
+
 def _csr(stored, values):
     """1-based CSR of the entries marked in `stored`, columns ascending"""
     rows, cols = np.nonzero(stored)
@@ -188,9 +245,15 @@ Problem = namedtuple("Problem", "name n delta rcm locs X theta z ref_taper lp Xp
 Case = namedtuple("Case", "name rcm r base")
 CASES = [Case("clusters", True, 2, "clusters"), Case("clusters_caller", False, 2, "clusters"),
          Case("islands", True, 1, "islands"), Case("chain", True, 1, "chain"), Case("hub", True, 1, "hub"),
-         Case("hub_caller", False, 1, "hub"), Case("lshape", False, 1, "lshape")]
+         Case("hub_caller", False, 1, "hub"), Case("lshape", False, 1, "lshape"),
+         Case("flat9", False, 2, "flat9"), Case("flat10_long", False, 1, "flat10_long"), Case("tall", False, 1, "tall"),
+         Case("tall_rcm", True, 1, "tall")]
 BY_NAME = {c.name: c for c in CASES}
 NAMES = [c.name for c in CASES]
+WIDE = ["flat9", "flat10_long", "tall", "tall_rcm"]          # bands wider than eight tile rows
+FLAT = ["flat9", "flat10_long"]
+FAR = 8                                                      # tiles (I, J), I - J >= FAR: what no narrower case has
+TALL_CLIQUE = 1300
 HUB = 450            # the hub's index in `hub` / `hub_caller`: neither first nor last
 
 
@@ -251,7 +314,23 @@ def _sites(name):
         locs = locs[np.argsort(locs[:, 0], kind="stable")]
         nt = (897 + TILE - 1) // TILE
         return locs, 0.15, (((nt - 1) * TILE - 1, 0),)
+    if name in ("flat9", "flat10_long"):
+        n, delta = (1665, 0.6) if name == "flat9" else (2433, 0.37)
+        rng = np.random.default_rng(n)
+        x = np.sort(rng.uniform(0, 1, n))
+        return np.column_stack([x, rng.uniform(0, 0.3, n)]), delta, ()
+    if name == "tall":
+        rng = np.random.default_rng(1869)
+        rad = 0.14 * np.sqrt(rng.uniform(0, 1, TALL_CLIQUE))
+        ang = rng.uniform(0, 2 * np.pi, TALL_CLIQUE)
+        clique = np.column_stack([0.5 + rad * np.cos(ang), 0.5 + rad * np.sin(ang)])
+        rest = rng.uniform(0, 3, size=(569, 2))
+        return np.concatenate([clique, rest[np.argsort(rest[:, 0], kind="stable")]]), 0.3, ()
     raise KeyError(name)
+
+
+# the box the prediction rows are drawn in, where it is not the unit square
+_PRED_BOX = {"flat9": (1.0, 0.3), "flat10_long": (1.0, 0.3)}
 
 
 @functools.lru_cache(maxsize=None)
@@ -268,8 +347,13 @@ def problem(name):
         far = _distances(b.locs, b.locs)[brow, ci - 1] > b.delta
         zeros = tuple(zip(where[brow[far]].tolist(), where[ci[far] - 1].tolist()))
         locs = b.locs[perm]
+        if c.base in KIND_OF:
+            assert not zeros
+            tapers = device_pattern(locs, locs, b.delta, KIND_OF[c.base]), device_pattern(b.lp, locs, b.delta, KIND_OF[c.base])
+        else:
+            tapers = pattern(locs, b.delta, zeros), pred_pattern(b.lp, locs, b.delta)
         out = Problem(name, b.n, b.delta, c.rcm, locs, np.asfortranarray(b.X[perm]), b.theta, np.asfortranarray(b.z[perm]),
-                      pattern(locs, b.delta, zeros), b.lp, b.Xp, pred_pattern(b.lp, locs, b.delta), b.special, c.base, perm)
+                      tapers[0], b.lp, b.Xp, tapers[1], b.special, c.base, perm)
         for a in (out.locs, out.X, out.z, perm) + out.ref_taper + out.pred_taper:
             a.setflags(write=False)
         return out
@@ -278,17 +362,19 @@ def problem(name):
     rng = np.random.default_rng(7000 + n)
     X = design(locs)
     z = np.asfortranarray(rng.standard_normal((n, c.r)))
-    ref_taper = pattern(locs, delta, zeros)
-    deg = np.diff(pattern(locs, delta)[1])
+    kind = KIND_OF.get(name)
+    ref_taper = device_pattern(locs, locs, delta, kind) if kind else pattern(locs, delta, zeros)
+    deg = np.diff(ref_taper[1] if kind else pattern(locs, delta)[1])
     busiest = int(np.argmax(deg))
-    lp = rng.uniform(0, 1, size=(M_PRED, 2))
+    lp = rng.uniform(0, 1, size=(M_PRED, 2)) * np.array(_PRED_BOX.get(name, (1.0, 1.0)))
     special = (70, 4, 133)                                    # rows of three different 64-row chunks
     lp[special[0]] = locs[busiest] + np.array([0.002, -0.001])
     lp[special[1]] = np.array([4.0, 4.0])
     lp[special[2]] = locs[(3 * n) // 7]
     Xp = np.asfortranarray(np.column_stack([np.ones(M_PRED), rng.standard_normal(M_PRED), rng.standard_normal(M_PRED)]))
-    pred_taper = pred_pattern(lp, locs, delta)
-    out = Problem(name, n, delta, c.rcm, locs, X, theta_full(), z, ref_taper, lp, Xp, pred_taper, special, name, np.arange(n))
+    pred_taper = device_pattern(lp, locs, delta, kind) if kind else pred_pattern(lp, locs, delta)
+    theta = wide_theta() if name in WIDE else theta_full()
+    out = Problem(name, n, delta, c.rcm, locs, X, theta, z, ref_taper, lp, Xp, pred_taper, special, name, np.arange(n))
     for a in (locs, X, z, lp, Xp, out.perm) + ref_taper + pred_taper + tuple(out.theta.values()):
         a.setflags(write=False)
     return out
@@ -341,5 +427,15 @@ def assert_shape(name, nt, hi, W, packed):
         assert nt == 8 and not packed and W == nt and np.all(hi == nt), reach
     elif name == "lshape":
         assert nt == 8 and packed and W == nt - 1 and hi[0] == nt - 1, reach     # the last tile row is outside column 0
+    elif name == "flat9":
+        assert nt == 14 and packed and W >= 9, (nt, W)
+        assert np.sum(reach >= W - 1) >= 6, reach
+    elif name == "flat10_long":
+        assert nt == 20 and packed and W >= 10 and nt >= 2 * W, (nt, W)            # the ring wraps twice
+        assert np.sum(reach >= W - 1) >= 8, reach
+    elif name in ("tall", "tall_rcm"):
+        assert nt == 15 and packed and W >= 11, (nt, W)
+        assert sum(hi[c] == fl[c] for c in inner) >= 2, reach
+        assert not np.array_equal(mirrored_envelope(hi), hi), reach
     else:
         raise KeyError(name)

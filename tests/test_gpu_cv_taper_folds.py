@@ -150,15 +150,47 @@ def test_packed_band_buffer_and_several_gram_groups():
         fit.close()
 
 
+@functools.lru_cache(maxsize=None)
+def _wide_dense(base):
+    """(S, R) of a case wider than eight tile rows: the lines of _dense, 9 s and more at these sizes, so computed once for
+    this file and tests/test_gpu_taper_envelopes.py"""
+    from test_gpu_taper_envelopes import _ref_matrix
+    return _ref_matrix(base)
+
+
+@functools.lru_cache(maxsize=None)
+def _wide_brute(base, layout):
+    """cv_brute on the layout `layout` of _wide_layouts (or on the 10 random folds of test_irregular_envelopes)"""
+    p = TE.problem(base)
+    lab = np.random.default_rng(17).permutation(p.n) % 10 if layout == "irregular" else _wide_layouts(base)[layout]
+    return CV.cv_brute(*_wide_dense(base), lab)
+
+
+@functools.lru_cache(maxsize=None)
+def _wide_layouts(base):
+    """CV.layouts without leave-one-out: 10 random folds, the spatial blocks, 2 folds -- 28 folds at most, each one Cholesky
+    of order n - |fold| for brute force (leave-one-out, n folds, is tests/test_gpu_taper_envelopes.py's, with a stride)"""
+    out = CV.layouts(TE.problem(base).locs)
+    del out["loo"]
+    assert sum(np.unique(lab).size for lab in out.values()) <= 64
+    return out
+
+
 @pytest.mark.parametrize("name,depth", [("clusters", None), ("chain", None), ("chain", "1"), ("hub_caller", None),
-                                        ("islands", None)])
+                                        ("islands", None), ("flat9", None), ("flat9", "1"), ("flat9", "3"), ("tall", None),
+                                        ("tall", "3"), ("tall_rcm", "1"), ("flat10_long", None), ("flat10_long", "3")])
 def test_irregular_envelopes(monkeypatch, name, depth):
     """10 random folds on the envelopes of tests/taper_envelope_cases.py: clusters (n = 1281, a ragged envelope), chain (W = 4 of
     10; at Gram depth 1 the ring has W slots and wraps), hub_caller (W = nt, unpacked), islands (S diagonal: resid = R and
-    var = diag S)"""
+    var = diag S); and on the bands wider than eight tile rows, flat9, tall and tall_rcm (W = 10, 12, 11 of nt = 14, 15, 15)
+    and flat10_long (W = 10 of 20): at the default depth of 8 only flat10_long's ring of W + 7 slots is shorter than nt; at
+    depth 3 every one wraps at W + 2, a modulus that is not W, and at depth 1 at W itself"""
     from test_gpu_taper_envelopes import _assert_shape, _fit
     p = TE.problem(name)
-    S, R = _dense(p.theta, p.locs, p.X, p.z, p.ref_taper, TE.SMOOTH_LIMITS)
+    if name in TE.WIDE:
+        S, R = _wide_dense(p.base)
+    else:
+        S, R = _dense(p.theta, p.locs, p.X, p.z, p.ref_taper, TE.SMOOTH_LIMITS)
     lab = np.random.default_rng(17).permutation(p.n) % 10
     fit = _fit(monkeypatch, p)
     try:
@@ -167,12 +199,36 @@ def test_irregular_envelopes(monkeypatch, name, depth):
             assert (W, nt) == (4, 10)
         if depth:
             monkeypatch.setenv("COCONS_CV_GRAM_DEPTH", depth)
+        if name in TE.WIDE:
+            assert W > 8
+            if depth or name == "flat10_long":
+                assert W + int(depth or 8) - 1 < nt, (W, nt, depth)          # a ring shorter than the matrix: it wraps
         got = fit.cv_core(p.theta, lab)
     finally:
         fit.close()
-    _check("%s depth %s" % (name, depth or "default"), got, CV.cv_brute(S, R, lab))
+    ref = _wide_brute(p.base, "irregular") if name in TE.WIDE else CV.cv_brute(S, R, lab)
+    _check("%s depth %s" % (name, depth or "default"), got, ref)
     if name == "islands":
         _check("islands: resid = R, var = diag S", got, (R, np.diag(S).copy()))
+
+
+@pytest.mark.parametrize("name", ["flat9", "tall"])
+def test_layouts_on_wide_bands(monkeypatch, name):
+    """the layouts of CV.layouts but leave-one-out (_wide_layouts) on flat9 and tall against brute force, at BOUND; the spatial
+    blocks put whole tile columns of the caller's order into one fold (flat9: sorted by x; tall: the clique is one block or
+    two), so large folds span the wide part of the band"""
+    from test_gpu_taper_envelopes import _assert_shape, _fit
+    p = TE.problem(name)
+    fit = _fit(monkeypatch, p)
+    try:
+        _, nt, _, W = _assert_shape(fit, p)
+        for layout, lab in _wide_layouts(p.base).items():
+            got = fit.cv_core(p.theta, lab)
+            sizes = np.bincount(lab)
+            _check("%s (nt %d, W %d) %s, %d folds of %d .. %d" % (name, nt, W, layout, (sizes > 0).sum(), sizes[sizes > 0].min(),
+                                                                sizes.max()), got, _wide_brute(p.base, layout))
+    finally:
+        fit.close()
 
 
 @pytest.mark.parametrize("together", [True, False])

@@ -1,7 +1,12 @@
 """Every entry of a tapered fit on band envelopes that are NOT flat -- wide in one place and at the floor in another (three
 clusters among scattered sites), a clique laid out by the caller (columns eight tiles tall), a diagonal matrix, a chain, a
 hub of stored zeros (W = nt - 1 packed, W = nt unpacked) and one stored zero far from the diagonal (the widest skew that
-still packs) -- tests/taper_envelope_cases.py, seven named cases.
+still packs) -- tests/taper_envelope_cases.py, seven named cases -- and on bands wider than eight tile rows: two flat bands of
+W = 10 (flat9; flat10_long, twenty tile columns, the ring wraps twice) and a clique of 1300 sites laid out first (tall: column
+0 twelve tile rows tall; tall_rcm, the library's order).  tests/test_taper_envelope_cases.py shows on the CPU that the far
+tiles of those four matter to the answers held here; tests/golden/WIDE_BANDS_REPORT.md has the measured gaps.  flat10_long's
+numpy references are expensive, so it runs the entries whose reference is S and one factorisation (no gradient, selected
+inverse or exact Fisher information).
 
 Every case ASSERTS the envelope it claims from what the handle reports: nt and W of krige_taper_info() equal the restated
 rule (taper_envelope_cases.envelope_of) applied to the order the handle reports, the case's shape property holds for that
@@ -23,20 +28,25 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import cv_reference as CV  # noqa: E402
 import fisher_taper_reference as FT  # noqa: E402
 import grad_taper_reference as GT  # noqa: E402
+import krige_taper_joint_reference as KJ  # noqa: E402
 import taper_envelope_cases as TE  # noqa: E402
 from test_gpu_cv_taper import BOUND as CV_BOUND  # noqa: E402
 from test_gpu_fisher_taper import TOL as FISHER_TOL  # noqa: E402
 from test_gpu_grad_taper import _fit_memory, _inf, _selinv  # noqa: E402
 from test_gpu_krige_taper import ROUTE_TOL  # noqa: E402
+from test_gpu_krige_taper_joint import TOL_COV, TOL_SIMS, TOL_STOCHASTIC  # noqa: E402
 from test_gpu_parity import N2LL_RTOL  # noqa: E402
 from test_gpu_sim_taper import TOL as SIM_TOL  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 SL = TE.SMOOTH_LIMITS
-ENTRIES = ["clusters", "clusters_caller", "hub", "hub_caller", "lshape", "islands"]
+LONG = "flat10_long"                  # no gradient, selected inverse or exact Fisher information (module docstring)
+ENTRIES = ["clusters", "clusters_caller", "hub", "hub_caller", "lshape", "islands", "flat9", "tall", "tall_rcm"]
 WITH_CHAIN = ENTRIES + ["chain"]
-LAYOUTS = ["clusters", "hub", "lshape"]
+LAYOUTS = ["clusters", "hub", "lshape", "flat9", "tall", LONG]
+WIDE = ["flat9", LONG, "tall", "tall_rcm"]
+BRUTE_FOLDS = 64                      # leave-one-out by brute force above n = 1500: about this many refits
 LAM = (0.1, 0.2, 0.3)                 # the penalty of test_taper_objective_vs_oracle
 
 # The bound between the two device routes of the sparse prediction, ROUTE_TOL = 4 x 1.912e-14, is four times the worst
@@ -115,6 +125,35 @@ def _ref_grad(base):
 
 
 @functools.lru_cache(maxsize=None)
+def _ref_matrix(base):
+    """(S of tests/grad_taper_reference.py, the lower triangle mirrored as the library reads it; R = z - X mean)"""
+    from cocons_amd.host import theta_table
+    p = TE.problem(base)
+    S, _ = GT.taper_matrix(theta_table(p.theta), p.locs, p.X, SL, p.ref_taper)
+    out = (np.tril(S) + np.tril(S, -1).T, p.z - (p.X @ p.theta["mean"])[:, None])
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _ref_value(base):
+    """(f, parts) as grad_taper_reference.neg2loglik_taper_grad states them.  flat10_long: from S and one factorisation, the
+    lines of that function that give f and parts, without its gradient (20 s at n = 2433)."""
+    if base != LONG:
+        return _ref_grad(base)[:2]
+    from scipy import linalg
+    p = TE.problem(base)
+    S, R = _ref_matrix(base)
+    cf = linalg.cho_factor(S, lower=True)
+    half_logdet = float(np.sum(np.log(np.diag(cf[0]))))
+    quads = np.sum(R * linalg.cho_solve(cf, R), axis=0)
+    parts = np.concatenate([[half_logdet], quads])
+    parts.setflags(write=False)
+    return R.shape[1] * (p.n * np.log(2 * np.pi) + 2 * half_logdet) + float(np.sum(quads)), parts
+
+
+@functools.lru_cache(maxsize=None)
 def _ref_oracle_values(base):
     """the oracle's objective with the penalty, its Profile form, and the plain value at the shifted theta"""
     from oracle import oracle as O
@@ -141,34 +180,42 @@ def _oracle_matrix(name):
 
 @functools.lru_cache(maxsize=None)
 def _ref_fisher(base):
-    """(I at r = 1, X' S^-1 X) for the standard directions: tests/fisher_taper_reference.py"""
+    """(I at r = 1, X' S^-1 X) for the standard directions: tests/fisher_taper_reference.py; for the wide cases also S and
+    the direction matrices themselves (what the probe mode's numpy sweep runs on)"""
     from cocons_amd.host import theta_table
     p = TE.problem(base)
     S, Sa = FT.direction_matrices(theta_table(p.theta), p.locs, p.X, SL, p.ref_taper, FT.standard_directions(3))
-    out = (FT.info_whiten(S, Sa, 1), FT.info_mean(S, p.X, 1))
+    out = (FT.info_whiten(S, Sa, 1), FT.info_mean(S, p.X, 1)) + ((S, Sa) if base in WIDE else ())
     for a in out:
         a.setflags(write=False)
     return out
 
 
+def _brute_stride(base):
+    """every 4th observation, every 8th above n = 1000; above n = 1500, where one refit costs a second, the stride that
+    leaves about BRUTE_FOLDS refits (27 at n = 1665: 62 of them; 30 at n = 1869: 63); flat10_long: no refit at all (0)"""
+    n = TE.problem(base).n
+    if base == LONG:
+        return 0
+    return -(-n // BRUTE_FOLDS) if n > 1500 else (8 if n > 1000 else 4)
+
+
 @functools.lru_cache(maxsize=None)
 def _ref_cv(base):
-    """(e, var of cv_reference.cv_kroute for every observation; idx, e, var of cv_reference.cv_brute for every 8th (n > 1000)
-    or 4th observation) on the dense S of grad_taper_reference, as test_gpu_cv_taper._reference.  Brute force is one Cholesky
+    """(e, var of cv_reference.cv_kroute for every observation; idx, e, var of cv_reference.cv_brute for every
+    _brute_stride-th observation) on the dense S of grad_taper_reference, as test_gpu_cv_taper._reference.  Brute force is one Cholesky
     of order n - 1 per observation it predicts -- 19 s for the 1281 of clusters -- so it predicts a stride of them: each of
     these is a fold of its own, all the others share one fold whose result is dropped, and cv_brute's answer for a fold of
     one is the leave-one-out prediction whatever the other folds are.  The stride runs over the caller's order, which the
     handle's order scatters over every tile column.  Every observation is held to the route through the dense inverse, which
     test_leave_one_out_vs_reference uses above n = 700 and tests/test_cv_reference.py pins to brute force."""
-    from cocons_amd.host import theta_table
     p = TE.problem(base)
-    S, _ = GT.taper_matrix(theta_table(p.theta), p.locs, p.X, SL, p.ref_taper)
-    S = np.tril(S) + np.tril(S, -1).T
-    R = p.z - (p.X @ p.theta["mean"])[:, None]
-    idx = np.arange(0, p.n, 8 if p.n > 1000 else 4)
+    S, R = _ref_matrix(base)
+    stride = _brute_stride(base)
+    idx = np.arange(0, p.n, stride) if stride else np.zeros(0, dtype=int)
     lab = np.full(p.n, -1)
     lab[idx] = idx
-    eb, vb = CV.cv_brute(S, R, lab)
+    eb, vb = CV.cv_brute(S, R, lab) if idx.size else (np.zeros((0, 1)), np.zeros(0))
     out = CV.cv_kroute(S, R, np.arange(p.n)) + (idx, eb[idx], vb[idx])
     for a in out:
         a.setflags(write=False)
@@ -226,7 +273,7 @@ def test_shape_reported_by_the_handle(monkeypatch, name):
 
 
 # --------------------------------------------------------------------------- entries
-@pytest.mark.parametrize("name", WITH_CHAIN)
+@pytest.mark.parametrize("name", WITH_CHAIN + [LONG])
 def test_value_and_parts(monkeypatch, name):
     """GetNeg2loglikelihoodTaper and its Profile form against the oracle (1e-8: test_taper_objective_vs_oracle); value and
     parts of neg2loglik_core against tests/grad_taper_reference.py (value 1e-9: test_value_and_gradient_vs_reference; every
@@ -235,7 +282,7 @@ def test_value_and_parts(monkeypatch, name):
     import cocons_amd as ca
     p = TE.problem(name)
     want, wantp, want2 = _ref_oracle_values(p.base)
-    f, rparts = _ref_grad(p.base)[:2]
+    f, rparts = _ref_value(p.base)
     tv, pp = _theta_vector(p.theta)
     fit = _fit(monkeypatch, p)
     try:
@@ -320,7 +367,7 @@ def test_fisher_exact_mode(monkeypatch, name):
     the same bits.  clusters: the mirrored envelope of the flipped factor is not the envelope, so the sweep's second set of
     tables differs from its first."""
     p = TE.problem(name)
-    R, Rm = _ref_fisher(p.base)
+    R, Rm = _ref_fisher(p.base)[:2]
     r = p.z.shape[1]
     dirs = FT.standard_directions(3)
     fit = _fit(monkeypatch, p)
@@ -343,10 +390,11 @@ def test_fisher_exact_mode(monkeypatch, name):
     assert np.array_equal(info0, info) and np.array_equal(info_mean0, info_mean), "the chunk size changed the bits"
 
 
-@pytest.mark.parametrize("name", ENTRIES)
+@pytest.mark.parametrize("name", ENTRIES + [LONG])
 def test_leave_one_out(monkeypatch, name):
-    """cv_core against cv_reference.cv_brute at every 8th or 4th observation and against cv_reference.cv_kroute at every one
-    (_ref_cv): gap_e and gap_v within 1e-8 (test_leave_one_out_vs_reference); two calls give the same bits."""
+    """cv_core against cv_reference.cv_brute at every 8th or 4th observation (the wide cases: _brute_stride; flat10_long: none)
+    and against cv_reference.cv_kroute at every one (_ref_cv): gap_e and gap_v within 1e-8
+    (test_leave_one_out_vs_reference); two calls give the same bits."""
     p = TE.problem(name)
     e, var, idx, eb, vb = _ref_cv(p.base)
     where = np.empty(p.n, dtype=int)
@@ -360,8 +408,9 @@ def test_leave_one_out(monkeypatch, name):
         fit.close()
     assert got[0].shape == p.z.shape and got[1].shape == (p.n,)
     ge, gv = CV.gaps(got[0], got[1], e[p.perm], var[p.perm])
-    be, bv = CV.gaps(got[0][where[idx]], got[1][where[idx]], eb, vb)
-    re, rv = CV.gaps(e[idx], var[idx], eb, vb)
+    assert idx.size or name == LONG
+    be, bv = CV.gaps(got[0][where[idx]], got[1][where[idx]], eb, vb) if idx.size else (0.0, 0.0)
+    re, rv = CV.gaps(e[idx], var[idx], eb, vb) if idx.size else (0.0, 0.0)
     print("%s: leave-one-out gap_e %.2e gap_v %.2e at all %d observations (dense inverse), %.2e %.2e at %d of them (brute "
           "force; the two references there: %.2e %.2e); var %.3g .. %.3g" % (name, ge, gv, p.n, be, bv, idx.size, re, rv,
                                                                           var.min(), var.max()))
@@ -370,7 +419,7 @@ def test_leave_one_out(monkeypatch, name):
     assert _same(got, again)
 
 
-@pytest.mark.parametrize("name", ENTRIES)
+@pytest.mark.parametrize("name", ENTRIES + [LONG])
 def test_prediction(monkeypatch, name):
     """predict_core against the oracle's cocoPredict_sparse at the bounds of test_taper_predict_vs_oracle; the row without
     neighbours gives a stochastic part of exactly 0; the objective's bits survive the prediction's larger border."""
@@ -389,13 +438,15 @@ def test_prediction(monkeypatch, name):
     assert v1[0] == v0[0] and np.array_equal(v1[1], v0[1])
 
 
-@pytest.mark.parametrize("name", WITH_CHAIN)
+@pytest.mark.parametrize("name", WITH_CHAIN + [LONG])
 def test_held_factor_kriging(monkeypatch, name):
     """krige_taper_prepare(max_rows = 64), krige_taper_core on the 200 rows (four chunks, the last one of 8 rows): against
     predict_core on the same handle (4 x 1.912e-14 of the largest value: test_matches_the_one_shot_route; clusters_caller:
     1.656e-12, ten times the one-shot route's own distance from a long-double solve, see ROUTE_TOL_OF) and against the
     oracle (test_chunked_predict_vs_oracle); one chunk gives the same bits; so do the three whole 64-row blocks permuted.
-    W = 6, 7 and 8 do not divide nt = 11 and 8: the ring wraps where no other test has it wrap."""
+    W = 6, 7 and 8 do not divide nt = 11 and 8: the ring wraps where no other test has it wrap.  The wide cases (W = 10, 11
+    and 12 of nt = 14, 15 and 20) keep ROUTE_TOL: an update step there has up to W (W + 1) / 2 = 78 tiles, and the slot of
+    tile column I is I mod W with W > 8."""
     from test_gpu_krige_taper import _err
     p = TE.problem(name)
     want = _ref_predict(name)
@@ -422,11 +473,15 @@ def test_held_factor_kriging(monkeypatch, name):
     assert np.array_equal(moved[0], got[0][idx]) and np.array_equal(moved[1], got[1][idx]), "blocks of rows permuted"
 
 
-@pytest.mark.parametrize("name", ENTRIES)
+PIVOTED = ("clusters", "flat9", "tall")
+
+
+@pytest.mark.parametrize("name", ENTRIES + [LONG])
 def test_simulation(monkeypatch, name):
     """sim_core in the handle's own order with 65 draws (one more than a pass of band_trmm_kernel) against
-    numpy.linalg.cholesky(S[order][:, order]) @ E + trend: 1e-10 of the largest value (test_fast_route_own_order).  clusters:
-    also a pivot that is neither the handle's order nor the identity (test_draw_equal_route_pivot, the same bound)."""
+    numpy.linalg.cholesky(S[order][:, order]) @ E + trend: 1e-10 of the largest value (test_fast_route_own_order).  clusters,
+    flat9 and tall: also a pivot that is neither the handle's order nor the identity (test_draw_equal_route_pivot, the same
+    bound) -- the twin handle in the pivot's order has an envelope of its own (a random order: no band at all)."""
     from test_gpu_sim_taper import _want
     p = TE.problem(name)
     S = _oracle_matrix(name)
@@ -438,7 +493,7 @@ def test_simulation(monkeypatch, name):
         order = _assert_shape(fit, p)[0]
         got = fit.sim_core(p.theta, E)
         again = fit.sim_core(p.theta, E)
-        if name == "clusters":
+        if name in PIVOTED:
             piv = (rng.permutation(p.n) + 1).astype(np.int32)
             assert not np.array_equal(piv, order) and not np.array_equal(piv, np.arange(1, p.n + 1))
             got_piv = fit.sim_core(p.theta, E, pivot=piv)
@@ -450,7 +505,7 @@ def test_simulation(monkeypatch, name):
     print("%s: 65 draws in the handle's order %.2e" % (name, e))
     assert got.shape == (p.n, 65) and e <= SIM_TOL
     assert np.array_equal(got, again)
-    if name == "clusters":
+    if name in PIVOTED:
         want_piv = _want(S, piv, E, trend)
         e = _inf(got_piv - want_piv) / _inf(want_piv)
         print("%s: 65 draws with a caller's pivot %.2e" % (name, e))
@@ -463,7 +518,8 @@ def test_simulation(monkeypatch, name):
 def test_buffer_layouts(monkeypatch, name):
     """COCONS_TAPER_PACKED=0 (the dense buffer, its band used) gives the packed default's bits in value, parts, gradient,
     prediction and kriging (test_taper_packed_band_buffer_equals_dense_buffer and test_buffer_layouts_give_the_same_bits claim
-    it at W = 5; here W = 6 and W = nt - 1).  COCONS_TAPER_BAND=0 (no envelope: another schedule) agrees in value (1e-12), parts
+    it at W = 5; here W = 6, W = nt - 1 and, on flat9, tall and flat10_long, W = 10 and 12: a leading dimension of (W + 1) 128 =
+1408 and 1664 rows).  COCONS_TAPER_BAND=0 (no envelope: another schedule) agrees in value (1e-12), parts
     (1e-12 of the largest) and gradient (1e-10 of the largest component of grad_theta), the bounds of
     test_buffer_layouts_and_orders_agree and test_value_and_gradient_vs_reference."""
     p = TE.problem(name)
@@ -500,8 +556,17 @@ def test_recovery_on_a_wide_envelope(monkeypatch):
     """clusters: a NaN theta and a theta whose matrix is not positive definite (the -Inf variance of
     test_taper_handle_recovers_after_failed_evaluation) each poison every tile the factorisation touches; the first theta
     afterwards gives the first call's bits, value and gradient: nothing is left in a column taller than the floor."""
+    _recovery(monkeypatch, "clusters")
+
+
+def test_recovery_on_a_tall_envelope(monkeypatch):
+    """the same on tall: column 0 is twelve tile rows tall, and every one of them is poisoned and must come back clean"""
+    _recovery(monkeypatch, "tall")
+
+
+def _recovery(monkeypatch, name):
     import cocons_amd as ca
-    p = TE.problem("clusters")
+    p = TE.problem(name)
     nan, npd = _bad_thetas(p.theta)
     tv, pp = _theta_vector(p.theta)
     tv_nan = tv.copy()
@@ -526,6 +591,220 @@ def test_recovery_on_a_wide_envelope(monkeypatch):
         assert again[0] == first[0] and np.array_equal(again[1], first[1])
     finally:
         fit.close()
-    f = _ref_grad("clusters")[0]
-    print("clusters: value after two poisoned evaluations %.2e against the numpy statement" % (abs(first[0] - f) / abs(f)))
+    f = _ref_grad(p.base)[0]
+    print("%s: value after two poisoned evaluations %.2e against the numpy statement" % (name, abs(first[0] - f) / abs(f)))
     assert abs(first[0] - f) <= 1e-9 * abs(f)
+
+
+# --------------------------------------------------------------------------- what the wide cases are the first to meet
+@functools.lru_cache(maxsize=None)
+def _uu(base):
+    """the case's taper among its own prediction rows (the row without a neighbour holds its diagonal alone)"""
+    p = TE.problem(base)
+    out = TE.device_pattern(p.lp, p.lp, p.delta, TE.KIND_OF[base])
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def _dense(pattern, entries, nrow, ncol):
+    ci, rp = np.asarray(pattern[0]), np.asarray(pattern[1])
+    A = np.zeros((nrow, ncol))
+    A[np.repeat(np.arange(nrow), np.diff(rp)), ci - 1] = entries
+    return A
+
+
+@functools.lru_cache(maxsize=None)
+def _ref_joint(base):
+    """The dense numpy statement of test_gpu_krige_taper_joint._reference on the case: (stochastic, S_uu, cov, mu, C); S_uu from
+    the lower triangle of the uu pattern, mirrored; C the m x n cross-covariances on the prediction pattern."""
+    from oracle import oracle as O
+    O.build()
+    p = TE.problem(base)
+    uu, pt, th, m = _uu(base), p.pred_taper, p.theta, TE.M_PRED
+    S = _oracle_matrix(base)
+    C = _dense(pt, np.asarray(pt[2]) * O.cov_rns_taper_pred(th, p.locs, p.lp, p.X, p.Xp, pt[0], pt[1], SL), m, p.n)
+    Su = np.tril(_dense(uu, np.asarray(uu[2]) * O.cov_rns_taper(th, p.lp, p.Xp, uu[0], uu[1], SL), m, m))
+    Su = Su + np.tril(Su, -1).T
+    SiCt = np.linalg.solve(S, C.T)
+    st = (p.z[:, 0] - p.X @ th["mean"]) @ SiCt
+    cov = Su - C @ SiCt
+    out = (st, Su, (cov + cov.T) / 2, p.Xp @ th["mean"] + st, C)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def _ring_schur(name, order, hi, W, depth):
+    """tests/krige_taper_joint_reference.py (the ring of min(W + depth - 1, nt) slots, tile column I in slot I mod that) at the
+    tile edge 128 on the dense numpy factor in the handle's order: S_uu - sum_g V_g V_g'"""
+    p = TE.problem(name)
+    assert np.array_equal(p.perm, np.arange(p.n))
+    _, Su, _, _, C = _ref_joint(p.base)
+    o = np.asarray(order) - 1
+    nt = len(hi)
+    Sp = np.eye(nt * TE.TILE)
+    Sp[:p.n, :p.n] = _oracle_matrix(p.base)[np.ix_(o, o)]
+    L = np.linalg.cholesky(Sp)
+    stored = _dense(p.pred_taper, 1.0, TE.M_PRED, p.n)[:, o] != 0
+    Co = C[:, o]
+    rows_ci = [np.nonzero(stored[i])[0] for i in range(TE.M_PRED)]
+    rows_val = [Co[i, rows_ci[i]] for i in range(TE.M_PRED)]
+    return KJ.ring_schur(L, [int(h) for h in hi], TE.TILE, W, depth, rows_ci, rows_val, Su)[0]
+
+
+@pytest.mark.parametrize("name", WIDE)
+def test_joint_prediction(monkeypatch, name):
+    """krige_taper_joint on the 200 prediction rows against the dense numpy statement of test_gpu_krige_taper_joint._reference
+    at that file's bounds (TOL_COV, TOL_SIMS, TOL_STOCHASTIC; above 1e-10 a defect) and against the ring solve of tests/
+    krige_taper_joint_reference.py on the numpy factor (TOL_COV): the covariance on all rows; covariance and three draws on
+    the 199 rows off the observation (with the row on top of an observation the predictive covariance is singular, tests/
+    golden/SIZES_REPORT.md: no draw is defined there).  The stochastic part has the bits of krige_taper_core
+    (test_same_bits_as_apply); the covariance is symmetric to the bit; ring depths 1 and 3 (W and W + 2 slots: both wrap, the
+    second at a modulus that is not W) give the default's bits."""
+    from test_gpu_krige_taper_joint import _default_depth, _eq
+    from taper_size_cases import sub_pattern
+    p = TE.problem(name)
+    uu = _uu(p.base)
+    st_ref, Su, cov_ref, mu, _ = _ref_joint(p.base)
+    rows = np.delete(np.arange(TE.M_PRED), p.special[2])
+    sub_ref = cov_ref[np.ix_(rows, rows)]
+    ev = np.linalg.eigvalsh(sub_ref)
+    assert ev.min() > 0
+    E = np.random.default_rng(70 + p.n).standard_normal((TE.M_PRED, 3))
+    monkeypatch.delenv("COCONS_KRIGE_JOINT_DEPTH", raising=False)
+    fit = _fit(monkeypatch, p)
+    try:
+        order, nt, hi, W = _assert_shape(fit, p)
+        fit.krige_taper_prepare(p.theta)
+        depth = _default_depth(fit, TE.M_PRED, monkeypatch)
+        st0, qf0 = fit.krige_taper_core(p.lp, p.Xp, p.pred_taper)
+        st, cov, none = fit.krige_taper_joint_core(p.lp, p.Xp, p.pred_taper, uu)
+        sub = (p.lp[rows], p.Xp[rows], TE.take_rows(p.pred_taper, rows), sub_pattern(uu, rows))
+        drawn = fit.krige_taper_joint_core(*sub, iiderrors=E[rows])
+        depths = {}
+        for d in ("1", "3"):
+            monkeypatch.setenv("COCONS_KRIGE_JOINT_DEPTH", d)
+            depths[d] = fit.krige_taper_joint_core(p.lp, p.Xp, p.pred_taper, uu)
+        monkeypatch.delenv("COCONS_KRIGE_JOINT_DEPTH")
+    finally:
+        fit.close()
+    assert none is None and W + 3 - 1 < nt, (W, nt)
+    top = float(np.max(np.diag(cov_ref)))
+    want = np.linalg.cholesky(sub_ref) @ E[rows] + mu[rows, None]
+    e_cov = _inf(cov - cov_ref) / top
+    e_ring = _inf(cov - _ring_schur(name, order, hi, W, 3)) / top
+    e_sub = _inf(drawn[1] - sub_ref) / float(np.max(np.diag(sub_ref)))
+    e_sims = _inf(drawn[2] - want) / _inf(want)
+    e_st = _inf(st - st_ref) / _inf(st_ref)
+    e_qf = _inf((np.diag(Su) - np.diag(cov)) - qf0) / top
+    print("%s (nt %d, W %d, default depth %d): joint prediction cov %.3e (ring solve in numpy %.3e; 199 rows %.3e) sims %.3e "
+          "stochastic %.3e diag against quadform %.3e (eigenvalues %.3e .. %.3e)"
+          % (name, nt, W, depth, e_cov, e_ring, e_sub, e_sims, e_st, e_qf, ev.min(), ev.max()))
+    assert np.array_equal(st, st0), "the stochastic part is krige_taper_core's"
+    assert np.array_equal(drawn[0], st0[rows])
+    assert np.array_equal(cov, cov.T) and np.array_equal(drawn[1], drawn[1].T)
+    for d, b in depths.items():
+        assert _eq(b, (st, cov, None)), "depth " + d
+    assert st[p.special[1]] == 0.0 and np.count_nonzero(cov[p.special[1]]) == 1 and cov[p.special[1], p.special[1]] > 0
+    assert max(e_cov, e_ring, e_sub, e_sims, e_st) <= 1e-10, "a defect, not a bound"
+    assert e_cov <= TOL_COV and e_sub <= TOL_COV and e_sims <= TOL_SIMS and e_st <= TOL_STOCHASTIC, (e_cov, e_sub, e_sims, e_st)
+    assert e_ring <= TOL_COV and e_qf <= TOL_COV, (e_ring, e_qf)
+
+
+@pytest.mark.parametrize("name", TE.FLAT)
+def test_device_pattern(monkeypatch, name):
+    """The flat cases have no stored zero: their pattern is a function of delta.  CoconsTaperFit.from_delta reports the order,
+    nt and W of the handle built from ref_taper and gives the bits of its value (test_create_taper_delta); the exported
+    patterns are ref_taper and pred_taper, entries included (tests/test_gpu_pattern.py allows 16 x 2^-52 and measures 0; the
+    cases' entries are evaluated in the device's order of operations); krige_taper_core_delta gives the bits of krige_taper_core
+    fed the exported pattern (test_apply_delta_equals_apply_bit_for_bit), in chunks of 64 rows and in one."""
+    import cocons_amd as ca
+    p = TE.problem(name)
+    kind = TE.KIND_OF[p.base]
+    fit = _fit(monkeypatch, p)
+    other = None
+    try:
+        order, nt, hi, W = _assert_shape(fit, p)
+        other = ca.CoconsTaperFit.from_delta(p.locs, p.X, p.z, SL, p.delta, kind)
+        info = other.krige_taper_info()
+        assert np.array_equal(other.order(), order) and (info["nt"], info["W"]) == (nt, W), info
+        v, va = fit.neg2loglik_core(p.theta), other.neg2loglik_core(p.theta)
+        own = ca.taper_pattern(p.locs, p.delta, kind)
+        exported = ca.taper_pattern(p.locs, p.delta, kind, newlocs=p.lp)
+        dev = max(_inf(own[2] / p.ref_taper[2] - 1), _inf(exported[2] / p.pred_taper[2] - 1))
+        print("%s (%s, delta %g, nt %d, W %d): %d + %d entries from the device, largest deviation from the case's %.3e"
+              % (name, kind, p.delta, nt, W, own[0].size, exported[0].size, dev))
+        got = {}
+        for max_rows in (64, 0):
+            fit.krige_taper_prepare(p.theta, max_rows=max_rows)
+            got[max_rows] = (fit.krige_taper_core(p.lp, p.Xp, exported), fit.krige_taper_core_delta(p.lp, p.Xp, p.delta, kind),
+                             fit.krige_taper_core(p.lp, p.Xp, p.pred_taper))
+            assert fit.last_pattern_nnz == exported[0].size
+    finally:
+        fit.close()
+        if other is not None:
+            other.close()
+    for mine, theirs in ((p.ref_taper, own), (p.pred_taper, exported)):
+        assert np.array_equal(mine[0], theirs[0]) and np.array_equal(mine[1], theirs[1])
+        assert np.array_equal(mine[2], theirs[2]), dev
+    assert va[0] == v[0] and np.array_equal(va[1], v[1]), "from_delta: the value's bits"
+    for max_rows, (fed, from_delta, mine) in got.items():
+        assert _same(from_delta, fed), "krige_taper_core_delta, max_rows %d" % max_rows
+        assert _same(mine, fed)
+    assert _same(got[0][1], got[64][1])
+    empty = np.nonzero(np.diff(p.pred_taper[1]) == 0)[0]
+    assert p.special[1] in empty and np.all(got[64][1][0][empty] == 0.0) and np.all(got[64][1][1][empty] == 0.0)
+
+
+PROBED = ["flat9", "tall"]            # (the numpy sweep costs 20 s a call at these sizes)
+
+
+@pytest.mark.parametrize("nprobe", [64, 100])
+@pytest.mark.parametrize("name", PROBED)
+def test_fisher_probe_mode(monkeypatch, name, nprobe):
+    """random +-1 probes through the handle's own order against the same probes through fisher_taper_reference.band_fisher with
+    the handle's pivot: FISHER_TOL, info_mean 1e-10 (test_probe_mode_against_the_numpy_sweep, test_gpu_taper_sizes.
+    test_fisher_probe_mode); 100 probes leave the second strip partly filled"""
+    p = TE.problem(name)
+    assert np.array_equal(p.perm, np.arange(p.n))
+    _, Rm, S, Sa = _ref_fisher(p.base)
+    r = p.z.shape[1]
+    dirs = FT.standard_directions(3)
+    P = np.random.default_rng(nprobe + p.n).integers(0, 2, size=(p.n, nprobe)) * 2.0 - 1.0
+    fit = _fit(monkeypatch, p)
+    try:
+        pivot, nt, hi, W = _assert_shape(fit, p)
+        info, info_mean = fit.fisher_core(p.theta, dirs, probes=P)
+    finally:
+        fit.close()
+    want, _, rhi, rW = FT.band_fisher(S, Sa, P, pivot, r=r, X=p.X)
+    gap = FT.metric(info, want)
+    gm = _inf(info_mean - r * Rm) / _inf(r * Rm)
+    print("%s (nt %d, W %d; the numpy factor fills W %d): %d probes, gap to the numpy sweep %.2e info_mean %.2e"
+          % (name, nt, W, rW, nprobe, gap, gm))
+    assert rW <= W and np.all(np.asarray(rhi) <= hi)
+    assert gap <= FISHER_TOL
+    assert gm <= 1e-10
+    assert np.array_equal(info, info.T)
+
+
+@pytest.mark.parametrize("name", ["flat9", "tall"])
+def test_fisher_orthogonal_probes_equal_the_exact_mode(monkeypatch, name):
+    """sqrt(n) Q, Q orthogonal, nprobe = n: sum_k e_k e_k' = n I, so the probe mode must give the exact mode's information
+    (FISHER_TOL, info_mean to the bit: test_orthogonal_probes_equal_the_exact_mode)"""
+    from scipy import linalg
+    p = TE.problem(name)
+    dirs = FT.standard_directions(3)
+    Q = linalg.qr(np.random.default_rng(2 + p.n).standard_normal((p.n, p.n)))[0]
+    fit = _fit(monkeypatch, p)
+    try:
+        _assert_shape(fit, p)
+        exact, em = fit.fisher_core(p.theta, dirs)
+        got, gm = fit.fisher_core(p.theta, dirs, probes=np.sqrt(p.n) * Q)
+    finally:
+        fit.close()
+    gap = FT.metric(got, exact)
+    print("%s: %d orthogonal probes against the exact mode %.2e" % (name, p.n, gap))
+    assert gap <= FISHER_TOL
+    assert np.array_equal(gm, em)

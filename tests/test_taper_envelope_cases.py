@@ -4,7 +4,10 @@ for (and notices when it is one tile too tight), the inputs are conditioned like
 the prediction sets hold the rows they promise, and the ring's load rule covers the case's (nt, W); and the library's own
 envelope rule and packed band layout (cocons_amd/csrc/band_plan.hpp, compiled into tests/band_plan_main.cpp by the host
 compiler) agree with the restatement integer for integer, and so does its bucket sort of a chunk's entries by tile column
-(band_buckets, what tapered kriging scatters a chunk into the ring by).  No GPU."""
+(band_buckets, what tapered kriging scatters a chunk into the ring by).  The cases wider than eight tile rows (TE.WIDE) must
+also show that their far tiles matter: the factor with every tile (I, J), I - J >= 8, set to zero gives another quadratic
+form and another kriging prediction, by a hundred times the suite's tolerances at least; and the tiles the two-column block
+rule adds to a flat band are shown to be exactly zero, so nobody counts them as coverage.  No GPU."""
 import functools
 import os
 import subprocess
@@ -19,12 +22,17 @@ import taper_envelope_cases as TE  # noqa: E402
 from krige_taper_reference import load_schedule  # noqa: E402
 
 COND_CAP = 1e5
+COND_CAP_WIDE = 1e3               # the wide cases keep ROUTE_TOL by staying well conditioned
+QUAD_MOVES = 100 * 1e-8           # 100 x N2LL_RTOL (tests/test_gpu_parity.py)
+KRIGE_MOVES = 100 * 1e-10         # 100 x the stochastic bound of test_taper_predict_vs_oracle
 
 
 @functools.lru_cache(maxsize=None)
 def _matrix(name):
     from cocons_amd.host import theta_table
     p = TE.problem(name)
+    if p.base != name and np.array_equal(p.perm, np.arange(p.n)) and np.array_equal(p.ref_taper[2], TE.problem(p.base).ref_taper[2]):
+        return _matrix(p.base)                                  # the same observations and pattern in another handle order
     S, _ = GT.taper_matrix(theta_table(p.theta), p.locs, p.X, TE.SMOOTH_LIMITS, p.ref_taper)
     S.setflags(write=False)
     return S
@@ -67,7 +75,7 @@ def test_shape_conditioning_and_containment(name):
         assert np.array_equal(order, np.arange(1, p.n + 1))
     else:
         assert sorted(order.tolist()) == list(range(1, p.n + 1)) and not np.array_equal(order, np.arange(1, p.n + 1))
-    assert cond <= COND_CAP, cond
+    assert cond <= (COND_CAP_WIDE if name in TE.WIDE else COND_CAP), cond
     assert np.allclose(S, S.T, rtol=1e-14, atol=0) and np.all(np.isfinite(S))      # (the two orders of a product: last bit)
     assert _tiles_outside(_factor(name), hi) == []
     # the mirrored envelope holds the flipped factor in the same way
@@ -119,6 +127,99 @@ def test_containment_notices_an_envelope_one_tile_too_tight(name):
         tight[c] -= 1
         out = _tiles_outside(_factor(name), tight)
         assert out == [(int(hi[c]) - 1, c)], (c, out)
+
+
+def _zero_far_tiles(L, cut):
+    """(L with every tile (I, J), I - J >= cut, set to zero; the largest entry that went)"""
+    T = TE.TILE
+    nt = L.shape[0] // T
+    out, gone = L.copy(), 0.0
+    for J in range(nt):
+        for I in range(J + cut, nt):
+            blk = out[I * T:(I + 1) * T, J * T:(J + 1) * T]
+            gone = max(gone, float(np.abs(blk).max()))
+            blk[:] = 0.0
+    return out, gone
+
+
+@pytest.mark.parametrize("name", TE.WIDE)
+def test_far_tiles_matter(name):
+    """The condition every wide case must meet before it may claim to test anything (a condition on the inputs, not a
+    measurement of the library): with the tiles (I, J), I - J >= 8, of the dense numpy factor set to zero -- the tiles no case
+    of W <= 8 has -- the quadratic form |L^-1 (z - X beta)|^2 moves by 1e-6 of itself at least (100 x N2LL_RTOL) and the
+    stochastic part of the kriging prediction at the case's 200 rows by 1e-8 of its largest value (100 x the bound of
+    test_taper_predict_vs_oracle).  The cross-covariances are the CPU oracle's."""
+    from scipy.linalg import solve_triangular
+    from oracle import oracle as O
+    O.build()
+    p = TE.problem(name)
+    order, nt, hi, W, _ = _envelope(name)
+    o = order - 1
+    L = _factor(name)
+    Lz, gone = _zero_far_tiles(L, TE.FAR)
+    ci, rp, ent = p.pred_taper
+    C = np.zeros((TE.M_PRED, nt * TE.TILE))
+    Cn = np.zeros((TE.M_PRED, p.n))
+    Cn[np.repeat(np.arange(TE.M_PRED), np.diff(rp)), ci - 1] = ent * O.cov_rns_taper_pred(p.theta, p.locs, p.lp, p.X, p.Xp, ci, rp,
+                                                                                            TE.SMOOTH_LIMITS)
+    C[:, :p.n] = Cn[:, o]
+    worst_q, worst_s = np.inf, np.inf
+    for col in range(p.z.shape[1]):
+        res = np.zeros(nt * TE.TILE)
+        res[:p.n] = (p.z[:, col] - p.X @ p.theta["mean"])[o]
+        y, yz = solve_triangular(L, res, lower=True), solve_triangular(Lz, res, lower=True)
+        st = solve_triangular(L, C.T, lower=True).T @ y
+        stz = solve_triangular(Lz, C.T, lower=True).T @ yz
+        worst_q = min(worst_q, abs(y @ y - yz @ yz) / (y @ y))
+        worst_s = min(worst_s, float(np.max(np.abs(st - stz)) / np.max(np.abs(st))))
+    print("%s: W %d, largest entry of the tiles at distance >= %d: %.3e of max |L| = %.3g; zeroing them moves the quadratic form "
+          "by %.3e of itself and the stochastic part by %.3e of its largest value" % (name, W, TE.FAR, gone / np.abs(L).max(),
+                                                                                 np.abs(L).max(), worst_q, worst_s))
+    assert W > TE.FAR and gone > 0
+    assert worst_q >= QUAD_MOVES, worst_q
+    assert worst_s >= KRIGE_MOVES, worst_s
+
+
+@pytest.mark.parametrize("name", TE.FLAT)
+def test_block_rule_tiles_of_a_flat_band_are_zero(name):
+    """A flat band's raw skyline reaches W - 1 tile rows; the two-column block rule gives the even column of a block the
+    bound of the odd one, so the tiles at distance W - 1 exist in even columns alone, and the true factor has nothing in them.
+    They are storage the schedule walks over, not coverage: the outermost tiles with anything in them are at distance W - 2."""
+    p = TE.problem(name)
+    order, nt, hi, W, _ = _envelope(name)
+    _, raw = TE.raw_skyline(p.n, p.ref_taper[0], p.ref_taper[1], order)
+    L = _factor(name)
+    T = TE.TILE
+    outer = [c for c in range(nt) if hi[c] - c == W]
+    assert outer and all(c % 2 == 0 for c in outer), outer
+    assert np.max(raw - np.arange(nt)) == W - 1
+    for c in outer:
+        I = c + W - 1
+        assert not np.any(L[I * T:(I + 1) * T, c * T:(c + 1) * T]), c
+    full = [c for c in range(nt) if hi[c] - c >= W - 1]
+    live = [c for c in full if np.any(L[(c + W - 2) * T:(c + W - 1) * T, c * T:(c + 1) * T])]
+    print("%s: W %d; columns at reach W %s, all empty at distance W - 1; %d of %d columns at reach >= W - 1 hold entries at "
+          "distance W - 2" % (name, W, outer, len(live), len(full)))
+    assert len(live) >= 6 and set(outer) <= set(live), (live, full)
+
+
+@pytest.mark.parametrize("name", TE.WIDE)
+def test_wide_patterns_are_a_function_of_delta(name):
+    """No stored zero, every pair within delta stored, and no pair within 1e-12 delta of delta: the device's own neighbour
+    search (CoconsTaperFit.from_delta, krige_taper_core_delta) must find exactly this pattern, and -- the entries being
+    evaluated in its order of operations -- these doubles."""
+    p = TE.problem(name)
+    kind = TE.KIND_OF[p.base]
+    for rows, pt in ((p.locs, p.ref_taper), (p.lp, p.pred_taper)):
+        d = TE._distances_device(rows, p.locs)
+        assert not np.any(np.abs(d - p.delta) <= 1e-12 * p.delta)
+        ci, rp, ent = pt
+        stored = np.zeros(d.shape, dtype=bool)
+        stored[np.repeat(np.arange(d.shape[0]), np.diff(rp)), ci - 1] = True
+        assert np.array_equal(stored, d <= p.delta) and np.all(ent > 0)
+        h = d[stored] / p.delta
+        want = (1 - h) ** 2 * (1 + h / 2) if kind == "sph" else (1 - h) ** 4 * (4 * h + 1)
+        assert np.allclose(ent, want, rtol=0, atol=4e-16)
 
 
 @pytest.mark.parametrize("name", TE.NAMES)
@@ -192,6 +293,12 @@ def test_theta_and_design_are_the_workloads():
     assert TE.SMOOTH_LIMITS == wl.SMOOTH_LIMITS
     locs = TE.problem("islands").locs
     assert np.allclose(TE.design(locs), wl.design_from_locs(locs)["std.covs"], rtol=0, atol=1e-14)
+    wide = TE.wide_theta()
+    assert list(wide) == list(mine)
+    for k in mine:
+        same = np.array_equal(wide[k], mine[k])
+        assert same == (k not in ("scale", "nugget")) and np.array_equal(wide[k][1:], mine[k][1:])
+    assert all(TE.problem(name).theta["scale"][0] == np.log(0.6) for name in TE.WIDE)
 
 
 def test_restated_order_on_a_path_and_two_components():
