@@ -458,7 +458,14 @@ __device__ __forceinline__ double pair_value_idx(const double *base_a, size_t sa
     // stage 2: amplitude (fields reloaded, see above)
     asm volatile("" : "+v"(oa), "+v"(ob));
     // (1 / det is formed again rather than kept across the Bessel call: one more live value there spills)
-    double amp = sqrt_pos(FA(8) * FB(8) * fast_rcp(det));      // sqrt(dets_i sin t_i dets_j sin t_j / det), field 8 = dets sin t
+    const double pw = FA(8) * FB(8);
+    const double w = pw * fast_rcp(det);
+    double amp = sqrt_pos(w);                                   // sqrt(dets_i sin t_i dets_j sin t_j / det), field 8 = dets sin t
+    // Link functions near overflow put dets sin t and det near opposite ends of the exponent range: the quotient under ONE root
+    // then underflows (or overflows) where the reference's two roots, sqrt(.) / sqrt(det_ij) (src/cocons_full.cpp:296-297), stay
+    // finite -- the entry came out 0 where the reference has 1.8e-180.  Such a pair takes two roots as well; nothing else does.
+    // (w outside 2^-900 .. 2^900, negative or NaN, read off its sign and exponent bits: three 32-bit operations)
+    if (((unsigned)__double2hiint(w) >> 20) - 123u > 1800u) amp = sqrt_pos(pw) * sqrt_pos(fast_rcp(det));
     return m * FA(9) * FB(9) * amp;
 #undef FA
 #undef FB

@@ -9,13 +9,12 @@
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load
  * this library; the product path (cocons_amd/) never links or imports it.
  *
- * PARITY UNPINNED w.r.t. the reference binary: the reference cannot be built
- * here (needs Rcpp.h, R.h and Boost headers, none installed) and its own test
- * script holds no numeric golden vector for cov_rns* or -2loglik
- * (tests/coco_test.R asserts shapes / eigenvalues>0 / non-NA only).  The oracle
- * is therefore pinned by (a) closed-form Matern identities, (b) 40-digit mpmath
- * evaluations committed under tests/golden/, (c) cross-branch identities
- * between cov_rns / cov_rns_classic / cov_rns_pred.
+ * PINNED to the reference's compiled code: oracle/ref_wrap.cpp compiles the three reference files unmodified
+ * behind the stand-in headers of oracle/ref_shim/ (make ref -> oracle/_ref/, never committed), and
+ * tests/test_reference_pin.py requires this file's outputs to equal that library's bit for bit on the case
+ * matrix of tests/reference_cases.py and on random cases.  Outside that pin: K_nu below (the stand-in Boost
+ * header forwards to it), pinned by (a) closed-form Matern identities and (b) 40-digit mpmath evaluations
+ * committed under tests/golden/, which also pin the mathematics of the whole path.
  *
  * Third-party arithmetic on the path that is NOT under /root/reference:
  *   - boost::math::cyl_bessel_k  (BH headers, version unpinned, DESCRIPTION:25;
@@ -234,8 +233,14 @@ static inline double pair_geometry(const locvec_t *vi, int ii, const locvec_t *v
     double s12 = kahan(vi->rd[ii] * vi->an[ii], cos(vi->tilt[ii]),
                        -1 * vj->rd[jj] * vj->an[jj], cos(vj->tilt[jj])) * 0.5;
     double det = kahan(s11, s22, s12, s12);
-    double u = sqrt(8 * smtns / (global_range * det)) *
-               sqrt(fma(kahan(s22, dx * dx, -s11, dy * dy), 1, -2 * s12 * dx * dy));
+    /* The reference writes sqrt(8 nu / (range det)) * sqrt(Q); the factors stand the other way round here.  The
+     * product is commutative in every bit except one: when BOTH factors are NaN (overflowing links), x86 hands on
+     * the first machine operand's NaN, sign included, and gcc puts sqrt(Q) first in the reference's general,
+     * 1.5, 2.5, classic and prediction loops.  Written this way the oracle returns the compiled reference's bits
+     * there, NaN signs included (tests/test_reference_pin.py); in the reference's 0.5 loop gcc chose the other
+     * order, so under nu = 0.5 the two agree on where NaN lands but not on its sign (REFERENCE_PIN_REPORT.md). */
+    double u = sqrt(fma(kahan(s22, dx * dx, -s11, dy * dy), 1, -2 * s12 * dx * dy)) *
+               sqrt(8 * smtns / (global_range * det));
     *det_out = det;
     return u;
 }

@@ -7,7 +7,8 @@ restated in numpy.  Cholesky / triangular solves go through scipy's LAPACK
 (`dpotrf`, `dtrtrs`) -- the same LAPACK routines `base::chol` / `forwardsolve`
 dispatch to (R's LAPACK is not vendored in the reference; version unpinned).
 
-PARITY UNPINNED w.r.t. the reference binary (see the C file's header).  Only
+The C oracle is pinned to the reference's compiled code (oracle/reference.py, tests/test_reference_pin.py); the
+closures restated here need R and are not.  Only
 tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this
 module.
 """
