@@ -59,6 +59,11 @@ SIGNATURES = {
     "cocons_taper_pattern": (c_int, [c_int, c_dp, c_int, c_dp, ctypes.c_double, c_int, c_int, ctypes.c_longlong,
                                      ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_dp]),
     "cocons_fit_create_taper_delta": (c_vp, [c_int, c_int, c_int, c_dp, c_dp, c_dp, c_dp, c_int, ctypes.c_double, c_int]),
+    "cocons_fit_create_vecchia": (c_vp, [c_int, c_int, c_int, c_dp, c_dp, c_dp, c_dp, c_int, c_int, ctypes.POINTER(c_int)]),
+    "cocons_neg2loglik_vecchia": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp]),
+    "cocons_vecchia_whiten": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_dp]),
+    "cocons_vecchia_predict": (c_int, [c_vp, c_dp, c_dp, c_int, c_int, c_dp, c_dp, c_int, ctypes.POINTER(c_int), c_dp, c_dp]),
+    "cocons_vecchia_info": (c_int, [c_vp, ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_fit_destroy": (None, [c_vp]),
     "cocons_neg2loglik_dense": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp]),
     "cocons_neg2loglik_grad_dense": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),

@@ -337,7 +337,7 @@ static int fisher_entry(cocons_fit *f, const char *who, const double *theta, int
                         double *info_mean, bool reml)
 {
     if (int rc = fisher_check_args(who, f, theta, ndir, dirs, info)) return rc;
-    FIT_ENTER(f);
+    FIT_ENTER_AS(f, who);
     if (int rc = grad_refuse(f, who)) return rc;
     if (f->r < 1) return fail(-1, "%s: fit has no z", who);
     const int npad = f->npad, p = f->p, nb = reml ? f->r + p : f->r;

@@ -554,7 +554,7 @@ cocons_fit *taper_create_ordered(int n, int p, int r, const double *locs, const 
 extern "C" int cocons_fit_same_data(cocons_fit *f, int n, int p, int r, int q, const double *locs, const double *X,
                                     const double *z, const double *x_betas, const double *smooth_limits)
 {
-    if (!f || !locs || !X || !smooth_limits || f->taper_nnz > 0) return 0;
+    if (!f || !locs || !X || !smooth_limits || f->taper_nnz > 0 || f->vecchia) return 0;
     if (f->n_user != n || f->p != p || f->r != r || f->q != q) return 0;
     if (f->smooth_limits[0] != smooth_limits[0] || f->smooth_limits[1] != smooth_limits[1]) return 0;
     if (memcmp(f->h_locs.data(), locs, (size_t)2 * n * sizeof(double)) != 0) return 0;
@@ -612,7 +612,7 @@ static int own_pair_again(cocons_fit *f)
 
 extern "C" int cocons_fit_set_stream(cocons_fit *f, void *stream)
 {
-    FIT_ENTER(f);
+    FIT_ENTER_ANY(f);
     // both streams idle before the swap: no event wait of the panel stream may refer to work on a
     // stream that is about to be destroyed
     HIPCHK(hipStreamSynchronize(f->stream));
@@ -624,7 +624,7 @@ extern "C" int cocons_fit_set_stream(cocons_fit *f, void *stream)
 
 extern "C" int cocons_fit_sync(cocons_fit *f)
 {
-    FIT_ENTER(f);
+    FIT_ENTER_ANY(f);
     HIPCHK(hipStreamSynchronize(f->stream));
     return 0;
 }

@@ -1,0 +1,257 @@
+// api_vecchia.hip -- C ABI of the Vecchia approximation: the third kind of handle -- data, a neighbour table and
+// O(n (m + 16)) bytes of scratch, never an n x n buffer -- and the three entries on it: the -2 log-likelihood, the whitening of
+// given columns, and local kriging.  One evaluation is: the location parameters for theta (loc_params_kernel, then their
+// transpose to one record per location), the right-hand sides, ONE launch of vecchia_block_kernel with a wavefront per
+// observation, and -- for the value -- the totals as a tree of fixed shape.  Nothing here factors through api.hip.
+#include "fit.hpp"
+
+int vecchia_refuse(const char *who)
+{
+    return fail(-1, "%s: not available on a Vecchia fit (cocons_neg2loglik_vecchia, cocons_vecchia_whiten and "
+                    "cocons_vecchia_predict are)", who);
+}
+
+static int vecchia_only(cocons_fit *f, const char *who)
+{
+    if (!f->vecchia) return fail(-1, "%s: not a Vecchia fit (cocons_fit_create_vecchia makes one)", who);
+    return 0;
+}
+
+// Row i of a neighbour table (rows x m column-major, 1-based, 0 = none) into row i of the device layout: 0-based, ascending,
+// -1 behind the last.  limit: the largest index row i may name.  0, or the first offence: 1 = out of range, 2 = twice.
+static int vecchia_row(const int *nn, size_t rows, int m, size_t i, int limit, int *out)
+{
+    int k = 0;
+    for (int j = 0; j < m; ++j) {
+        const int v = nn[i + (size_t)j * rows];
+        if (v < 0 || v > limit) return 1;
+        if (v > 0) out[k++] = v - 1;
+    }
+    std::sort(out, out + k);
+    for (int j = 1; j < k; ++j) if (out[j] == out[j - 1]) return 2;
+    for (int j = k; j < m; ++j) out[j] = -1;
+    return 0;
+}
+
+static const char *const vecchia_offence[] = {"", "names an index outside its range", "names an index twice"};
+
+extern "C" cocons_fit *cocons_fit_create_vecchia(int n, int p, int r, const double *locs, const double *X, const double *z,
+                                                 const double *smooth_limits, int device, int m, const int *nn)
+{
+    const char *who = "cocons_fit_create_vecchia";
+    if (!locs || !X || !z || !smooth_limits || !nn) { fail(-1, "%s: null argument", who); return nullptr; }
+    if (n < 1) { fail(-1, "%s: n = %d (at least one observation expected)", who, n); return nullptr; }
+    if (p < 1 || p > COCONS_P_MAX || r < 1) { fail(-1, "%s: bad argument (p = %d, r = %d)", who, p, r); return nullptr; }
+    if (m < 1 || m > VECCHIA_M_MAX) { fail(-1, "%s: m = %d is outside 1 .. %d", who, m, VECCHIA_M_MAX); return nullptr; }
+    if (pattern_check_finite(who, "locs", (size_t)n, locs)) return nullptr;
+    std::vector<int> tab((size_t)n * m);
+    for (int i = 0; i < n; ++i)
+        if (int bad = vecchia_row(nn, (size_t)n, m, (size_t)i, i, &tab[(size_t)i * m])) {
+            fail(-1, "%s: row %d of nn %s (1-based indices in 1 .. row - 1, 0 = none)", who, i + 1, vecchia_offence[bad]);
+            return nullptr;
+        }
+    // the caller's order is the Vecchia order and the handle keeps it (no Morton sort, no padding in front): neighbour
+    // indices and outputs need no mapping, and COCONS_SPATIAL_SORT cannot reach a bit of any output
+    cocons_fit *f = fit_create_impl(n, p, r, 0, locs, X, z, nullptr, smooth_limits, device, false, true, false, true);
+    if (!f) return nullptr;
+    auto drop = [&](hipError_t e) {
+        fail(-100 - (int)e, "%s: %s", who, hipGetErrorString(e));
+        (void)hipGetLastError();
+        f->op_mu.unlock();
+        cocons_fit_destroy(f);
+        return (cocons_fit *)nullptr;
+    };
+    f->vecchia.reset(new VecchiaState());
+    VecchiaState *V = f->vecchia.get();
+    V->m = m;
+    if (hipError_t e = V->nbr.alloc(tab.size())) return drop(e);
+    if (hipError_t e = V->aos.alloc((size_t)VECCHIA_REC * n)) return drop(e);
+    if (hipError_t e = V->B.alloc((size_t)n * r)) return drop(e);
+    if (hipError_t e = V->W.alloc((size_t)n * (1 + r))) return drop(e);
+    if (hipError_t e = V->part.alloc(vecchia_sum_scratch_doubles(n, 1 + r))) return drop(e);
+    if (hipError_t e = hipMemcpyAsync(V->nbr, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, f->stream)) return drop(e);
+    if (hipError_t e = hipStreamSynchronize(f->stream)) return drop(e);
+    f->op_mu.unlock();
+    return f;
+}
+
+// out4 = {n, m, device bytes the handle holds, rows per chunk of cocons_vecchia_predict}
+static constexpr int VECCHIA_PRED_ROWS = 16384;
+
+extern "C" int cocons_vecchia_info(cocons_fit *f, long long *out4)
+{
+    const char *who = "cocons_vecchia_info";
+    if (!f) return fail(-1, "%s: null fit handle", who);
+    if (!out4) return fail(-1, "%s: null argument", who);
+    FIT_ENTER_ANY(f);
+    if (int rc = vecchia_only(f, who)) return rc;
+    out4[0] = f->n; out4[1] = f->vecchia->m;
+    out4[2] = f->vecchia->bytes() +
+              (long long)((f->dX.count() + f->dlocs.count() + f->dz.count() + f->dloc.count() + f->dinv.count() +
+                           f->dinfo_out.count()) * sizeof(double));
+    out4[3] = VECCHIA_PRED_ROWS;
+    return 0;
+}
+
+// the observations' records for theta in the parameters of cov_rns (which = 0) or of cov_rns_pred's branch (which = 2)
+static ModeSel vecchia_records(cocons_fit *f, const double *theta, int which, double *aos)
+{
+    ThetaVecs tv;
+    make_theta_vecs(theta, f->p, tv);
+    const ModeSel ms = select_mode(theta, f->p, f->smooth_limits, which);
+    launch_loc_params(loc_args(f->n, f->p, f->dX, f->dlocs, f->dloc, f->npad, tv, ms.smooth_kind, f->smooth_limits), f->stream);
+    launch_vecchia_aos(f->dloc, f->npad, f->n, aos, f->stream);
+    return ms;
+}
+
+// the info words home and the stream drained; 0, or the smallest 1-based row whose block has a pivot that is not positive
+static int vecchia_status(cocons_fit *f, const char *who)
+{
+    HIPCHK_AT(who, hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, f->stream));
+    HIPCHK_AT(who, hipGetLastError());
+    HIPCHK_AT(who, hipStreamSynchronize(f->stream));
+    if (f->hinfo[0] == 0x7f7f7f7f) return 0;
+    g_err = "a conditional variance is not positive";
+    return f->hinfo[0];
+}
+
+// the likelihood launch over all n observations for nb right-hand sides in V->B: log d and the whitened columns into V->W
+static void vecchia_blocks(cocons_fit *f, const ModeSel &ms, int nb)
+{
+    VecchiaState *V = f->vecchia.get();
+    VecchiaArgs a;
+    a.rows = f->n; a.m = V->m; a.kb = V->m + 1; a.nbr = V->nbr; a.aosK = V->aos;
+    a.gr = ms.gr; a.nu_fixed = ms.nu_fixed;
+    a.B = V->B; a.ldb = (size_t)f->n; a.nb = nb;
+    a.logd = V->W; a.Y = V->W + f->n; a.ldy = (size_t)f->n;
+    a.fail = f->dinfo;
+    launch_vecchia_blocks(ms.mode, false, a, f->stream);
+}
+
+extern "C" int cocons_neg2loglik_vecchia(cocons_fit *f, const double *theta, const double *mean, double *value, double *parts)
+{
+    const char *who = "cocons_neg2loglik_vecchia";
+    if (!f) return fail(-1, "%s: null fit handle", who);
+    if (!theta || !mean || !value) return fail(-1, "%s: null argument", who);
+    FIT_ENTER_ANY(f);
+    if (int rc = vecchia_only(f, who)) return rc;
+    VecchiaState *V = f->vecchia.get();
+    const int n = f->n, r = f->r;
+    double hmean[COCONS_P_MAX];
+    for (int i = 0; i < f->p; ++i) hmean[i] = canon_nan(mean[i]);
+    if (int rc = reset_info(f)) return rc;
+    const ModeSel ms = vecchia_records(f, theta, 0, V->aos);
+    launch_vecchia_resid(n, f->p, f->dX, n, hmean, f->dz, n, 0, r, V->B, (size_t)n, f->stream);
+    vecchia_blocks(f, ms, r);
+    launch_vecchia_sums(V->W, (size_t)n, n, 1 + r, V->part, f->dout, f->stream);
+    HIPCHK_AT(who, hipMemcpyAsync(f->hout, f->dout, (size_t)(1 + r) * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    if (int st = vecchia_status(f, who)) return st;
+    double total = 0.0;
+    for (int k = 0; k < r; ++k) total += n * LOG_2PI + 2 * f->hout[0] + f->hout[1 + k];
+    if (parts) for (int k = 0; k <= r; ++k) parts[k] = f->hout[k];
+    *value = total;
+    return 0;
+}
+
+extern "C" int cocons_vecchia_whiten(cocons_fit *f, const double *theta, int c, const double *B, double *out, double *logd)
+{
+    const char *who = "cocons_vecchia_whiten";
+    if (!f) return fail(-1, "%s: null fit handle", who);
+    if (!theta || !B || !out) return fail(-1, "%s: null argument", who);
+    if (c < 1) return fail(-1, "%s: c = %d (at least one column expected)", who, c);
+    FIT_ENTER_ANY(f);
+    if (int rc = vecchia_only(f, who)) return rc;
+    VecchiaState *V = f->vecchia.get();
+    const size_t n = (size_t)f->n;
+    HIPCHK_AT(who, V->B.reserve(n * c, f->stream, nullptr));
+    HIPCHK_AT(who, V->W.reserve(n * (1 + c), f->stream, nullptr));
+    if (int rc = reset_info(f)) return rc;
+    HIPCHK_AT(who, upload_canon(V->B, B, n * c, f->stream));
+    const ModeSel ms = vecchia_records(f, theta, 0, V->aos);
+    vecchia_blocks(f, ms, c);
+    // (into staging of the call: the caller's arrays stay untouched when a block fails)
+    std::vector<double> h(n * (1 + c));
+    HIPCHK_AT(who, hipMemcpyAsync(h.data(), V->W, h.size() * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    if (int st = vecchia_status(f, who)) return st;
+    if (logd) memcpy(logd, h.data(), n * sizeof(double));
+    memcpy(out, h.data() + n, n * c * sizeof(double));
+    return 0;
+}
+
+extern "C" int cocons_vecchia_predict(cocons_fit *f, const double *theta, const double *mean, int z_col, int mp,
+                                      const double *locs_pred, const double *X_pred, int m_pred, const int *nn_pred,
+                                      double *stochastic, double *quadform)
+{
+    const char *who = "cocons_vecchia_predict";
+    if (!f) return fail(-1, "%s: null fit handle", who);
+    if (!theta || !mean) return fail(-1, "%s: null argument", who);
+    if (mp < 0 || (mp > 0 && (!locs_pred || !X_pred || !nn_pred || !stochastic || !quadform)))
+        return fail(-1, "%s: bad argument (mp < 0 or a null pointer)", who);
+    if (m_pred < 1 || m_pred > VECCHIA_M_MAX) return fail(-1, "%s: m_pred = %d is outside 1 .. %d", who, m_pred, VECCHIA_M_MAX);
+    if (mp > 0)
+        if (int rc = pattern_check_finite(who, "locs_pred", (size_t)mp, locs_pred)) return rc;
+    FIT_ENTER_ANY(f);
+    if (int rc = vecchia_only(f, who)) return rc;
+    if (z_col < 0 || z_col >= f->r) return fail(-1, "%s: z_col = %d is outside 0 .. %d", who, z_col, f->r - 1);
+    VecchiaState *V = f->vecchia.get();
+    const int n = f->n, p = f->p, rows = VECCHIA_PRED_ROWS;
+    std::vector<int> tab((size_t)mp * m_pred);
+    for (int i = 0; i < mp; ++i)
+        if (int bad = vecchia_row(nn_pred, (size_t)mp, m_pred, (size_t)i, n, &tab[(size_t)i * m_pred]))
+            return fail(-1, "%s: row %d of nn_pred %s (1-based indices in 1 .. n, 0 = none)", who, i + 1, vecchia_offence[bad]);
+    if (mp == 0) return 0;
+    double hmean[COCONS_P_MAX];
+    for (int i = 0; i < p; ++i) hmean[i] = canon_nan(mean[i]);
+    // the chunk's buffers: locals of the call (device memory does not grow with mp)
+    DevBuf<double> dXp, dlp, dsoa, drec, dst, dqd;
+    DevBuf<int> dnb;
+    HIPCHK_AT(who, dXp.alloc((size_t)rows * p));
+    HIPCHK_AT(who, dlp.alloc((size_t)rows * 2));
+    HIPCHK_AT(who, dsoa.alloc((size_t)rows * LOCP_FIELDS));
+    HIPCHK_AT(who, drec.alloc((size_t)rows * VECCHIA_REC));
+    HIPCHK_AT(who, dst.alloc((size_t)rows));
+    HIPCHK_AT(who, dqd.alloc((size_t)rows));
+    HIPCHK_AT(who, dnb.alloc((size_t)rows * m_pred));
+    StreamDrain s{f->stream, false};
+    if (int rc = reset_info(f)) return rc;
+    // K from cov_rns's records; c from the prediction branch's (always logistic + sqrt, see cocons_predict_dense): a second
+    // set of records only where the two differ (a fixed smoothness)
+    const ModeSel ms2 = select_mode(theta, p, f->smooth_limits, 2);
+    const double *aosC = V->aos;
+    if (select_mode(theta, p, f->smooth_limits, 0).smooth_kind != ms2.smooth_kind) {
+        HIPCHK_AT(who, V->aos2.reserve((size_t)VECCHIA_REC * n, f->stream, nullptr));
+        vecchia_records(f, theta, 2, V->aos2);
+        aosC = V->aos2;
+    }
+    const ModeSel ms = vecchia_records(f, theta, 0, V->aos);
+    launch_vecchia_resid(n, p, f->dX, n, hmean, f->dz, n, z_col, 1, V->B, (size_t)n, s);
+    ThetaVecs tv;
+    make_theta_vecs(theta, p, tv);
+    std::vector<double> hX((size_t)rows * p), hl((size_t)rows * 2), hst((size_t)mp), hqd((size_t)mp);
+    for (int b = 0; b < mp; b += rows) {
+        const int mc = std::min(rows, mp - b);
+        for (int j = 0; j < p; ++j) memcpy(&hX[(size_t)j * mc], X_pred + b + (size_t)j * mp, (size_t)mc * sizeof(double));
+        for (int j = 0; j < 2; ++j) memcpy(&hl[(size_t)j * mc], locs_pred + b + (size_t)j * mp, (size_t)mc * sizeof(double));
+        HIPCHK_AT(who, upload_canon(dXp, hX.data(), (size_t)mc * p, s));
+        HIPCHK_AT(who, upload_canon(dlp, hl.data(), (size_t)mc * 2, s));
+        HIPCHK_AT(who, hipMemcpyAsync(dnb, &tab[(size_t)b * m_pred], (size_t)mc * m_pred * sizeof(int), hipMemcpyHostToDevice, s));
+        launch_loc_params(loc_args(mc, p, dXp, dlp, dsoa, rows, tv, ms2.smooth_kind, f->smooth_limits), s);
+        launch_vecchia_aos(dsoa, rows, mc, drec, s);
+        VecchiaArgs a;
+        a.rows = mc; a.m = m_pred; a.kb = m_pred + 1; a.nbr = dnb;
+        a.aosK = V->aos; a.aosC = aosC; a.aosP = drec;
+        a.gr = ms.gr; a.nu_fixed = ms.nu_fixed;
+        a.B = V->B; a.ldb = (size_t)n; a.nb = 1;
+        a.stoch = dst; a.quad = dqd;
+        a.fail = f->dinfo; a.row0 = b;
+        launch_vecchia_blocks(ms.mode, true, a, s);
+        HIPCHK_AT(who, hipMemcpyAsync(&hst[b], dst, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT(who, hipMemcpyAsync(&hqd[b], dqd, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK_AT(who, hipGetLastError());
+        HIPCHK_AT(who, hipStreamSynchronize(s));         // the staging is used again
+    }
+    if (int st = vecchia_status(f, who)) return st;
+    memcpy(stochastic, hst.data(), (size_t)mp * sizeof(double));
+    memcpy(quadform, hqd.data(), (size_t)mp * sizeof(double));
+    return 0;
+}

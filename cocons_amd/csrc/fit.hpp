@@ -255,6 +255,23 @@ struct TaperGradState {
     long long bytes = 0;          // device bytes of the buffers above
 };
 
+// What makes a handle a Vecchia handle (cocons_fit_create_vecchia, api_vecchia.hip): the neighbour table and the
+// scratch of one evaluation, O(n (m + r + 16)) bytes.  Such a handle has no factorisation buffer at all.
+struct VecchiaState {
+    int m = 0;                    // columns of the table
+    DevBuf<int> nbr;              // n x m, row after row: 0-based neighbours ascending, -1 behind them (kernels.h VecchiaArgs)
+    DevBuf<double> aos, aos2;     // VECCHIA_REC x n: the observations' records for this theta (aos2: in the prediction branch's
+                                  // parameters, made by the first prediction whose theta needs it)
+    DevBuf<double> B;             // n x c: the right-hand sides (the residuals, or cocons_vecchia_whiten's columns)
+    DevBuf<double> W;             // n x (1 + c): log d, then the whitened columns
+    DevBuf<double> part;          // first-stage sums of the totals
+    long long bytes() const
+    {
+        return (long long)(nbr.count() * sizeof(int) +
+                           (aos.count() + aos2.count() + B.count() + W.count() + part.count()) * sizeof(double));
+    }
+};
+
 // elements of the three parts of the mailbox buffer (dmbox; the accessors are below the handle)
 struct MboxLayout {
     size_t tiles = 0, smb = 0, xmb = 0;
@@ -387,6 +404,7 @@ struct cocons_fit {
     std::unique_ptr<KrigeTaperState> krige_taper;   // taper fit: kriging state (cocons_krige_taper_prepare); clones and twins carry none
     std::unique_ptr<GradState> grad;     // scratch of cocons_neg2loglik_grad_dense (allocated on first use)
     std::unique_ptr<TaperGradState> tgrad;   // taper fit: state of cocons_neg2loglik_grad_taper (allocated on first use)
+    std::unique_ptr<VecchiaState> vecchia;   // non-null: a Vecchia handle (cocons_fit_create_vecchia) -- the third kind
 };
 
 // ---- one map per region of device words (every offset in ONE place; the abort dump -- api_diag.hip debug_abort_report, decoded by
@@ -481,9 +499,17 @@ int fit_check(cocons_fit *f);
 // Every public entry point that works on a handle: validate it, then hold its operation lock until the call returns.
 // THREADING CONTRACT (include/cocons_hip.h): one handle serves one call at a time -- a second thread that enters with the
 // same handle waits here --; different handles may be used, created and destroyed from different threads concurrently.
-#define FIT_ENTER(f)                                                   \
+// FIT_ENTER: the entries of the dense and taper families -- they refuse a Vecchia handle, which has no factorisation buffer,
+// under their own name.  FIT_ENTER_ANY: the entries that serve every kind (streams, the Vecchia entries themselves).
+int vecchia_refuse(const char *who);
+#define FIT_ENTER_ANY(f)                                               \
     if (int rc__ = fit_check(f)) return rc__;                          \
     std::lock_guard<std::recursive_mutex> op_guard__((f)->op_mu)
+#define FIT_ENTER_AS(f, who)                                           \
+    if (int rc__ = fit_check(f)) return rc__;                          \
+    if ((f)->vecchia) return vecchia_refuse(who);                      \
+    std::lock_guard<std::recursive_mutex> op_guard__((f)->op_mu)
+#define FIT_ENTER(f) FIT_ENTER_AS(f, __func__)      /* (in an entry's own body: __func__ is its name) */
 
 // nothing under the matrix can be relied on: whoever wrote rows there that the objective does not know of says so
 inline void border_unknown(cocons_fit *f) { f->border_clean = -1; f->border_pending = -1; }

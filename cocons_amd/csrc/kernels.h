@@ -611,4 +611,39 @@ void launch_cv_taper(const double *Z, size_t ldz, int skew, int npad, int n, con
 void launch_cv_taper_list(const double *Z, size_t ldz, int skew, int npad, const int *idx, const int *lab, int count,
                           const double *U, size_t ldu, int nr, double *var, double *res, size_t ldr, int *fail, hipStream_t s);
 
+// ---- Vecchia approximation: one small block per observation (vecchia.hip) -------------------------------------
+constexpr int VECCHIA_M_MAX = 63;      // neighbours per row: a block of m + 1 rows never exceeds one wavefront
+constexpr int VECCHIA_REC = 16;        // doubles per location record: the LOCP_FIELDS parameters padded to one 128-byte line
+constexpr int VECCHIA_G = 4;           // right-hand sides carried through one forward substitution
+constexpr int VECCHIA_SUM_SEG = 4096;  // elements per first-stage segment of the totals
+// aos[i * VECCHIA_REC + f] = soa[i + f * stride] for the n locations of loc_params_kernel's SoA, f < LOCP_FIELDS; the rest 0
+void launch_vecchia_aos(const double *soa, size_t stride, int n, double *aos, hipStream_t s);
+// out[i + k ldo] = z[i + (col0 + k) ldz] - (X mean)[i] for i < n, k < ncol (mean: p doubles on the host)
+void launch_vecchia_resid(int n, int p, const double *X, int ldx, const double *mean, const double *z, int ldz, int col0,
+                          int ncol, double *out, size_t ldo, hipStream_t s);
+// One block per row.  nbr: rows x m, row after row, the 0-based locations a row is conditioned on in ascending order and -1
+// in the places behind them.  Likelihood (pred = false): row i is observation i, its block the neighbours' and its own
+// rows of Sigma(theta) from the records aosK; with K = C C', logd[i] = log C(k, k) (logd may be null) and
+// Y[i + c ldy] = the last component of C^-1 B[(neighbours, i), c] for the nb columns of B (locations x nb, ld ldb).
+// Prediction (pred = true): row i is prediction site i of the chunk (records aosP, prediction branch), K the neighbours'
+// block from aosK, c the cross-covariance by cov_rns_pred's rule from aosC (the observations in the prediction branch's
+// parameters; may be aosK); stoch[i] = c' K^-1 B[neighbours, 0], quad[i] = c' K^-1 c; a row without neighbours gives 0, 0.
+// A pivot that is not positive and finite: atomicMin(*fail, row0 + i + 1), nothing written for that row.
+struct VecchiaArgs {
+    int rows = 0, m = 0, kb = 0;       // kb = m + 1: what the launch's LDS is sized by
+    const int *nbr = nullptr;
+    const double *aosK = nullptr, *aosC = nullptr, *aosP = nullptr;
+    double gr = 0.0, nu_fixed = 0.0;
+    const double *B = nullptr; size_t ldb = 0; int nb = 0;
+    double *Y = nullptr; size_t ldy = 0;
+    double *logd = nullptr, *stoch = nullptr, *quad = nullptr;
+    int *fail = nullptr; int row0 = 0;
+};
+size_t vecchia_lds_bytes(int m, bool pred);
+void launch_vecchia_blocks(int mode, bool pred, const VecchiaArgs &a, hipStream_t s);
+// out[q] = sum_i v[i + q ldv] (q = 0) or of its squares (q >= 1) over i < n, for q < ncol: a tree of fixed shape over values in
+// memory; part: vecchia_sum_scratch_doubles(n, ncol) doubles
+size_t vecchia_sum_scratch_doubles(int n, int ncol);
+void launch_vecchia_sums(const double *v, size_t ldv, int n, int ncol, double *part, double *out, hipStream_t s);
+
 }  // namespace cocons

@@ -1517,3 +1517,228 @@ def cocoPredict_dense_joint(theta_list, locs, newlocs, X_std, X_pred_std, smooth
     unc[neg] = np.abs(unc[neg])
     return {"systematic": Xp @ np.asarray(theta_list["mean"], dtype=np.float64), "stochastic": st, "sd.pred": np.sqrt(unc),
             "cov.pred": cov}
+
+
+# --------------------------------------------------------------------------- #
+# Vecchia approximation: the model's own likelihood from n small blocks, O(n m) memory
+# --------------------------------------------------------------------------- #
+def _nn_table(nn, rows):
+    nn = np.asarray(nn, dtype=np.int32)
+    if nn.ndim != 2:
+        nn = nn.reshape(rows, -1)
+    if nn.shape[0] != rows:
+        raise ValueError("the neighbour table must have one row per location")
+    return np.asfortranarray(nn), int(nn.shape[1])
+
+
+def vecchia_neighbours(locs, m) -> np.ndarray:
+    """The exact m nearest EARLIER observations of every row of locs (n x 2), in the order the rows come in (the Vecchia
+    order: choosing it -- maxmin, random, by coordinate -- stays with the caller): n x m int32 in Fortran order, 1-based,
+    nearest first, ties broken by index, zero-padded where a row has fewer than m predecessors.  The first rows by brute
+    force; the rows [b / 2, b) of every doubling block from a k-d tree over the first b points, queried with a doubling k
+    until m earlier points are found and every point tied with the last of them has been seen."""
+    from scipy.spatial import cKDTree
+    locs = np.ascontiguousarray(np.asarray(locs, dtype=np.float64))
+    n, m = locs.shape[0], int(m)
+    if m < 1:
+        raise ValueError("m must be at least 1")
+    nn = np.zeros((n, m), dtype=np.int32, order="F")
+
+    def dist(rows, idx):
+        return np.hypot(locs[idx, 0] - locs[rows, 0][:, None], locs[idx, 1] - locs[rows, 1][:, None])
+
+    head = min(n, max(2 * m + 1, 64))
+    for i in range(1, head):
+        o = np.lexsort((np.arange(i), dist(np.array([i]), np.arange(i)[None, :])[0]))[:m]
+        nn[i, :o.size] = o + 1
+    lo = head
+    while lo < n:
+        hi = min(n, 2 * lo)
+        tree = cKDTree(locs[:hi])
+        for b0 in range(lo, hi, 65536):
+            todo = np.arange(b0, min(hi, b0 + 65536))
+            k = min(hi, 2 * m + 2)
+            while todo.size:
+                idx = np.asarray(tree.query(locs[todo], k=k)[1]).reshape(todo.size, -1)
+                d = dist(todo, idx)
+                earlier = idx < todo[:, None]
+                dm = np.where(earlier, d, np.inf)
+                order = np.lexsort((idx, dm), axis=1)[:, :m]
+                far = np.take_along_axis(dm, order[:, -1:], axis=1)[:, 0]      # the m-th earlier point (inf: fewer than m)
+                done = np.isfinite(far) & ((k == hi) | (np.max(d, axis=1) > far))
+                nn[todo[done], :] = np.take_along_axis(idx, order, axis=1)[done] + 1
+                todo = todo[~done]
+                k = min(hi, 2 * k)
+        lo = hi
+    return nn
+
+
+def vecchia_neighbours_pred(locs, newlocs, m) -> np.ndarray:
+    """The m nearest observations of every new location (plain kNN): mp x m int32 in Fortran order, 1-based, zero-padded
+    when there are fewer than m observations."""
+    from scipy.spatial import cKDTree
+    locs = np.ascontiguousarray(np.asarray(locs, dtype=np.float64))
+    new = np.ascontiguousarray(np.asarray(newlocs, dtype=np.float64))
+    n, m = locs.shape[0], int(m)
+    k = min(n, m)
+    _, idx = cKDTree(locs).query(new, k=k)
+    nn = np.zeros((new.shape[0], m), dtype=np.int32, order="F")
+    nn[:, :k] = np.asarray(idx).reshape(new.shape[0], k) + 1
+    return nn
+
+
+class CoconsVecchiaFit:
+    """Handle of a Vecchia fit (cocons_fit_create_vecchia): (locs, x_covariates, z, smooth.limits) and the neighbour table
+    `nn` (n x m, 1-based indices of EARLIER rows, 0 = none; `vecchia_neighbours` makes one).  The rows' order is the Vecchia
+    order.  No n x n buffer exists; the library refuses this handle everywhere but in the three cores below."""
+
+    def __init__(self, locs, x_covariates, z, smooth_limits, nn, device=-1):
+        L = _lib.load()
+        self._L = L
+        locs, X = _f(locs), _f(x_covariates)
+        self.n, self.p = X.shape
+        if locs.shape != (self.n, 2):
+            raise ValueError("locs must be n x 2")
+        z = _f(np.asarray(z, dtype=np.float64).reshape(self.n, -1))
+        self.r = z.shape[1]
+        self.smooth_limits = np.asarray(smooth_limits, dtype=np.float64).copy()
+        self.x_covariates = X
+        nn, self.m = _nn_table(nn, self.n)
+        self._h = L.cocons_fit_create_vecchia(self.n, self.p, self.r, _p(locs), _p(X), _p(z), _p(self.smooth_limits),
+                                              int(device), self.m, _ip(nn))
+        if not self._h:
+            raise _lib.CoconsHipError("cocons_fit_create_vecchia failed: " + _lib.last_error())
+
+    close = CoconsFit.close
+    __del__ = CoconsFit.__del__
+
+    def neg2loglik_core(self, theta_list):
+        """(value, parts): parts[0] = sum_i log d_i, parts[1 + k] = sum_i y_ik^2, value = sum_k [n log 2 pi + 2 parts[0] +
+        parts[1 + k]].  CholeskyError(i): the block of row i has a conditional variance that is not positive."""
+        T = theta_table(theta_list)
+        mean = np.ascontiguousarray(np.asarray(theta_list["mean"], dtype=np.float64))
+        val = ctypes.c_double(0.0)
+        parts = np.zeros(1 + self.r)
+        _lib.check(self._L.cocons_neg2loglik_vecchia(self._h, _p(T), _p(mean), ctypes.byref(val), _p(parts)),
+                   "cocons_neg2loglik_vecchia")
+        return val.value, parts
+
+    def whiten_core(self, theta_list, B):
+        """(U B, log d) for the columns of B (n x c, the caller's order): U'U is the approximation's Sigma^-1."""
+        T = theta_table(theta_list)
+        B = _f(np.asarray(B, dtype=np.float64).reshape(self.n, -1))
+        out, logd = np.zeros(B.shape, order="F"), np.zeros(self.n)
+        _lib.check(self._L.cocons_vecchia_whiten(self._h, _p(T), int(B.shape[1]), _p(B), _p(out), _p(logd)),
+                   "cocons_vecchia_whiten")
+        return out, logd
+
+    def predict_core(self, theta_list, locs_pred, x_covariates_pred, nn_pred, z_col=0):
+        """Local kriging: (stochastic, quadform) of cocons_vecchia_predict for the neighbour table nn_pred (mp x m_pred,
+        1-based indices into the observations, 0 = none; `vecchia_neighbours_pred` makes one)."""
+        T = theta_table(theta_list)
+        mean = np.ascontiguousarray(np.asarray(theta_list["mean"], dtype=np.float64))
+        lp, Xp = _f(locs_pred), _f(x_covariates_pred)
+        mp = lp.shape[0]
+        nnp, m_pred = _nn_table(nn_pred, mp)
+        st, qf = np.zeros(mp), np.zeros(mp)
+        _lib.check(self._L.cocons_vecchia_predict(self._h, _p(T), _p(mean), int(z_col), mp, _p(lp), _p(Xp), m_pred, _ip(nnp),
+                                                  _p(st), _p(qf)), "cocons_vecchia_predict")
+        return st, qf
+
+    def info(self):
+        """{"n", "m", "bytes": device bytes the handle holds, "rows": rows per chunk of predict_core}"""
+        out = (ctypes.c_longlong * 4)()
+        _lib.check(self._L.cocons_vecchia_info(self._h, out), "cocons_vecchia_info")
+        return {"n": int(out[0]), "m": int(out[1]), "bytes": int(out[2]), "rows": int(out[3])}
+
+
+def _with_vecchia_fit(fit, locs, x_covariates, z, smooth_limits, nn):
+    if fit is not None:
+        return fit, False
+    return CoconsVecchiaFit(locs, x_covariates, z, smooth_limits, nn), True
+
+
+def GetNeg2loglikelihoodVecchia(theta, par_pos, nn, locs, x_covariates, smooth_limits, z, n, lam, safe=True, fit=None):
+    """GetNeg2loglikelihood (R/neg2loglikelihood.R:183-222) with the Vecchia approximation of the likelihood for the neighbour
+    table `nn`; `fit` (optional) a CoconsVecchiaFit built once from the same data and table."""
+    tl = getModelLists(theta, par_pos, "diff")
+    f, own = _with_vecchia_fit(fit, locs, x_covariates, z, smooth_limits, nn)
+    try:
+        try:
+            val, _ = f.neg2loglik_core(tl)
+        except CholeskyError:
+            if safe:
+                return 1e6                                  # :202-206
+            raise RuntimeError("Cholesky error")
+        return val + getPen(n * f.r, lam, tl, smooth_limits)
+    finally:
+        if own:
+            f.close()
+
+
+def _vecchia_gls(f, tl, z, x_betas):
+    """One whitening of [z | x_betas]: (sum log d, W = Xb' U'U Xb, the r quadratic forms z_k' P z_k with
+    P = U'U - U'U Xb W^-1 Xb' U'U)."""
+    z = np.asarray(z, dtype=np.float64).reshape(f.n, -1)
+    xb = np.asarray(x_betas, dtype=np.float64).reshape(f.n, -1)
+    UB, logd = f.whiten_core(tl, np.hstack([z, xb]))
+    Uz, UX = UB[:, :z.shape[1]], UB[:, z.shape[1]:]
+    W = UX.T @ UX
+    g = UX.T @ Uz
+    quad = np.sum(Uz * Uz, axis=0) - np.sum(g * np.linalg.solve(W, g), axis=0)
+    return float(np.sum(logd)), W, quad
+
+
+def GetNeg2loglikelihoodVecchiaProfile(theta, par_pos, nn, locs, x_covariates, smooth_limits, z, n, x_betas, lam,
+                                       safe=True, fit=None):
+    """R/neg2loglikelihood.R:127-165 with Sigma^-1 replaced by U'U."""
+    tl = getModelLists(theta, par_pos, "diff")
+    f, own = _with_vecchia_fit(fit, locs, x_covariates, z, smooth_limits, nn)
+    try:
+        try:
+            logdet, _, quad = _vecchia_gls(f, tl, z, x_betas)
+        except CholeskyError:
+            if safe:
+                return 1e6
+            raise RuntimeError("Cholesky error")
+        return float(np.sum(n * np.log(2 * np.pi) + 2 * logdet + quad)) + getPen(n * f.r, lam, tl, smooth_limits)
+    finally:
+        if own:
+            f.close()
+
+
+def GetNeg2loglikelihoodVecchiaREML(theta, par_pos, nn, locs, x_covariates, x_betas, smooth_limits, z, n, lam,
+                                    safe=True, fit=None):
+    """R/neg2loglikelihood.R:241-291 with Sigma^-1 replaced by U'U (x_betas is accepted and, as in the reference, unused:
+    the restricted likelihood projects out x_covariates)."""
+    tl = getModelLists(theta, par_pos, "diff")
+    f, own = _with_vecchia_fit(fit, locs, x_covariates, z, smooth_limits, nn)
+    try:
+        X = np.asarray(x_covariates, dtype=np.float64)
+        rank = int(np.linalg.matrix_rank(X))                # qr(x)$rank, :270
+        try:
+            logdet, W, quad = _vecchia_gls(f, tl, z, X)
+        except CholeskyError:
+            if safe:
+                return 1e6
+            raise RuntimeError("Cholesky error")
+        logdet_w = float(np.sum(np.log(np.diag(np.linalg.cholesky(W)))))
+        return (float(np.sum((n - rank) * np.log(2 * np.pi) + 2 * logdet + 2 * logdet_w + quad))
+                + getPen((n - rank) * f.r, lam, tl, smooth_limits))
+    finally:
+        if own:
+            f.close()
+
+
+def cocoPredict_vecchia(theta_list, locs, newlocs, X_std, X_pred_std, smooth_limits, z, nn_pred, type="pred", fit=None):
+    """cocoPredict (R/predict.R:136-183) by local kriging: every new location is predicted from the observations its row of
+    nn_pred names.  `fit` (optional) a CoconsVecchiaFit over the same data (its own table is not used here); without one a
+    handle with a one-column table is made for the call."""
+    f, own = (fit, False) if fit is not None else (
+        CoconsVecchiaFit(locs, X_std, z, smooth_limits, np.zeros((np.asarray(X_std).shape[0], 1), dtype=np.int32)), True)
+    try:
+        st, qf = f.predict_core(theta_list, newlocs, X_pred_std, nn_pred)
+    finally:
+        if own:
+            f.close()
+    return _predict_outputs(theta_list, X_pred_std, st, qf, type)

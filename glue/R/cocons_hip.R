@@ -484,3 +484,33 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
   if (res[[1]] > 0L) stop("Cholesky error")
   res[[2]]
 }
+
+# Vecchia approximation of the model's own likelihood (DESIGN.md 4r): n small blocks instead of one factorisation, O(n m)
+# memory, for n up to 10^6.  nn is the n x m matrix of neighbours -- row i names the EARLIER rows (1-based, 0 = none) that
+# observation i is conditioned on; the rows' order (maxmin, random, by coordinate) and the neighbour search stay with the caller
+# (GpGp::order_maxmin and GpGp::find_ordered_nn give both: nn <- find_ordered_nn(locs[ord, ], m)[, -1]; nn[is.na(nn)] <- 0):
+#   fit <- .cocons.hip.vecchia.create(locs[ord, ], x_covariates[ord, ], z[ord, , drop = FALSE], smooth.limits, nn)
+#   optim(..., fn = function(theta) .cocons.hip.vecchia.neg2loglik(fit, theta, par.pos, smooth.limits, n, r, lambda))
+.cocons.hip.vecchia.create <- function(locs, x_covariates, z, smooth.limits, nn, device = -1L) {
+  storage.mode(nn) <- "integer"
+  .Call(`_cocons_hip_vecchia_create`, as.matrix(locs), as.matrix(x_covariates), as.matrix(z), as.double(smooth.limits),
+        as.integer(device), nn)
+}
+
+# GetNeg2loglikelihood with the Vecchia value in place of the dense one: 1e+06 on a failing block under safe (:202-206)
+.cocons.hip.vecchia.neg2loglik <- function(fit, theta, par.pos, smooth.limits, n, r, lambda, safe = TRUE) {
+  theta_list <- getModelLists(theta = theta, par.pos = par.pos, type = "diff")
+  v <- .cocons.hip.result(.Call(`_cocons_hip_vecchia_neg2loglik`, fit, theta_list[-1], theta_list$mean), safe)
+  if (is.null(v)) return(1e+06)
+  v[1] + .cocons.getPen(n * r, lambda, theta_list, smooth.limits)
+}
+
+# local kriging: cbind(stochastic, quadform) for the new locations, each from the observations its row of nn_pred names
+# (1-based, 0 = none) -- the two columns cocoPredict's dense branch takes from its solve (R/predict.R:165-173)
+.cocons.hip.vecchia.predict <- function(fit, theta_list, newlocs, X_pred, nn_pred, z_col = 1L) {
+  storage.mode(nn_pred) <- "integer"
+  res <- .Call(`_cocons_hip_vecchia_predict`, fit, theta_list, as.integer(z_col), as.matrix(newlocs), as.matrix(X_pred),
+               nn_pred)
+  if (res[[1]] > 0L) stop("Cholesky error")
+  res[[2]]
+}

@@ -345,6 +345,27 @@ SEXP _cocons_hip_fit_create_taper(SEXP locs, SEXP X, SEXP z, SEXP smooth_limits,
     return ptr;
 }
 
+/* Vecchia handle (cocons_fit_create_vecchia): nn is the n x m neighbour matrix, 1-based indices of EARLIER rows, 0 = none
+ * (integer, or double after arithmetic); the rows' order is the Vecchia order */
+SEXP _cocons_hip_vecchia_create(SEXP locs, SEXP X, SEXP z, SEXP smooth_limits, SEXP device, SEXP nn)
+{
+    const int n = Rf_nrows(X), p = Rf_ncols(X);
+    const int r = Rf_isMatrix(z) ? Rf_ncols(z) : 1;
+    if (Rf_nrows(locs) != n || Rf_ncols(locs) != 2) Rf_error("locs must be n x 2");
+    if (!Rf_isMatrix(nn) || Rf_nrows(nn) != n) Rf_error("nn must be a matrix with one row per observation (n = %d)", n);
+    R_xlen_t len = 0;
+    const int *tab = as_int_copy(nn, &len);
+    cocons_fit *f = cocons_fit_create_vecchia(n, p, r, REAL(locs), REAL(X), REAL(z), REAL(smooth_limits), Rf_asInteger(device),
+                                              Rf_ncols(nn), tab);
+    if (!f) Rf_error("%s", cocons_last_error());
+    SEXP tag = PROTECT(Rf_allocVector(INTSXP, 4));
+    INTEGER(tag)[0] = n; INTEGER(tag)[1] = p; INTEGER(tag)[2] = r; INTEGER(tag)[3] = 0;
+    SEXP ptr = PROTECT(R_MakeExternalPtr(f, tag, R_NilValue));
+    R_RegisterCFinalizerEx(ptr, fit_finalizer, TRUE);
+    UNPROTECT(2);
+    return ptr;
+}
+
 SEXP _cocons_hip_fit_close(SEXP ptr)
 {
     fit_finalizer(ptr);
@@ -897,6 +918,48 @@ SEXP _cocons_hip_predict_taper(SEXP fitp, SEXP theta, SEXP mean, SEXP z_col, SEX
     return out;
 }
 
+/* Vecchia -2 log-likelihood (cocons_neg2loglik_vecchia): list(status, c(value, sum log d, the r sums of squares));
+ * status > 0: the first row whose block has a conditional variance that is not positive */
+SEXP _cocons_hip_vecchia_neg2loglik(SEXP fitp, SEXP theta, SEXP mean)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), r = fit_r(fitp);
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    if (XLENGTH(mean) != p) Rf_error("theta$mean must have length %d", p);
+    SEXP v = PROTECT(Rf_allocVector(REALSXP, 2 + r));
+    for (int i = 0; i < 2 + r; ++i) REAL(v)[i] = NA_REAL;
+    int rc = cocons_neg2loglik_vecchia(f, T, REAL(mean), REAL(v), REAL(v) + 1);
+    hip_check(rc, "GetNeg2loglikelihoodVecchia");
+    SEXP out = status_value(rc, v);
+    UNPROTECT(1);
+    return out;
+}
+
+/* local kriging on a Vecchia handle (cocons_vecchia_predict): list(status, cbind(stochastic, quadform)); theta is the WHOLE
+ * theta_list (its `mean` element is read by name like the others); nn_pred is the mp x m_pred matrix of 1-based indices
+ * into the observations, 0 = none; z_col 1-based */
+SEXP _cocons_hip_vecchia_predict(SEXP fitp, SEXP theta, SEXP z_col, SEXP locs_pred, SEXP X_pred, SEXP nn_pred)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), m = Rf_nrows(X_pred);
+    if (Rf_ncols(X_pred) != p || Rf_nrows(locs_pred) != m) Rf_error("prediction design / locations do not match the fit");
+    if (!Rf_isMatrix(nn_pred) || Rf_nrows(nn_pred) != m) Rf_error("nn_pred must be a matrix with one row per new location");
+    SEXP mean = list_get(theta, "mean");
+    if (!Rf_isReal(mean) || XLENGTH(mean) != p) Rf_error("theta$mean must be a double vector of length %d", p);
+    R_xlen_t len = 0;
+    const int *tab = as_int_copy(nn_pred, &len);
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    SEXP v = PROTECT(Rf_allocMatrix(REALSXP, m, 2));
+    int rc = cocons_vecchia_predict(f, T, REAL(mean), Rf_asInteger(z_col) - 1, m, REAL(locs_pred), REAL(X_pred),
+                                    Rf_ncols(nn_pred), tab, REAL(v), REAL(v) + m);
+    hip_check(rc, "cocoPredict (Vecchia)");
+    SEXP out = status_value(rc, v);
+    UNPROTECT(1);
+    return out;
+}
+
 /* kriging from a held band factor on a taper handle: factor S(theta) once for realization z_col (1-based) and keep the band
  * factor on the handle; max_rows = 0: the library's default chunk.  list(status, NULL) -- status > 0: the failing minor */
 SEXP _cocons_hip_krige_taper_prepare(SEXP fitp, SEXP theta, SEXP mean, SEXP z_col, SEXP max_rows)
@@ -1061,6 +1124,9 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_fit_cached", (DL_FUNC)&_cocons_hip_fit_cached, 6},
     {"_cocons_hip_cache_clear", (DL_FUNC)&_cocons_hip_cache_clear, 0},
     {"_cocons_hip_fit_create_taper", (DL_FUNC)&_cocons_hip_fit_create_taper, 8},
+    {"_cocons_hip_vecchia_create", (DL_FUNC)&_cocons_hip_vecchia_create, 6},
+    {"_cocons_hip_vecchia_neg2loglik", (DL_FUNC)&_cocons_hip_vecchia_neg2loglik, 3},
+    {"_cocons_hip_vecchia_predict", (DL_FUNC)&_cocons_hip_vecchia_predict, 6},
     {"_cocons_hip_fit_close", (DL_FUNC)&_cocons_hip_fit_close, 1},
     {"_cocons_hip_neg2loglik_parts", (DL_FUNC)&_cocons_hip_neg2loglik_parts, 3},
     {"_cocons_hip_neg2loglik", (DL_FUNC)&_cocons_hip_neg2loglik, 3},

@@ -273,6 +273,53 @@ int cocons_sim_taper(cocons_fit *fit, const double *theta, const double *mean, i
 /* the handle's own order (RCM unless COCONS_TAPER_RCM=0): pivot_out[k] = 1-based caller index at position k */
 int cocons_fit_taper_order(cocons_fit *fit, int *pivot_out);
 
+/* ---- Vecchia approximation: the model's own likelihood from n small blocks -----------------------------
+ * What GpGp computes, on the reference's covariance: every observation is conditioned on at most m earlier ones, so
+ *   -2 l(theta) ~ sum_k sum_i [ log 2 pi + 2 log d_i + y_ik^2 ],
+ * d_i the conditional standard deviation of observation i given its neighbours and y_ik its whitened residual.  It is exact
+ * when every observation names all its predecessors, approximates the likelihood of Sigma(theta) itself (not of a tapered
+ * covariance), and needs O(n m) memory: the handle holds the data, the table and O(n (m + r + 16)) bytes of scratch, never
+ * an n x n buffer.  The caller's order of the observations is the Vecchia order (maxmin, random, by coordinate: the caller's
+ * choice), and the handle keeps it.
+ * cocons_fit_create_vecchia: locs, X, z, smooth_limits as for cocons_fit_create (r >= 1); nn is n x m column-major, row i
+ * (1-based) listing the observations that observation i is conditioned on as 1-based indices in 1 .. i - 1, 0 = none -- zeros
+ * anywhere in a row, a row of zeros is an independent observation.  NULL + cocons_last_error(), which names the entry and the
+ * first offending row, before any device work: a null pointer, n < 1, m outside 1 .. 63, an index >= its row or < 0, an index
+ * twice in a row, a coordinate that is not finite.  This is a third kind of handle: every fit entry above and below refuses
+ * it with a message (cocons_fit_destroy, cocons_fit_stream, cocons_fit_set_stream and cocons_fit_sync serve it), and the
+ * entries here refuse every other kind.
+ * Block of observation i with neighbours j_1 < .. < j_k: K = Sigma(theta)[(j_1 .. j_k, i), (j_1 .. j_k, i)] -- the diagonal and
+ * the pair values of cocons_cov_rns for this theta, closed forms at nu = 1/2, 3/2, 5/2 included, a pair evaluated with the
+ * observation that comes earlier in the caller's order on the reference's `ii` side -- factored K = C C' in that order of
+ * rows.  Every sum has a fixed order: an observation's outputs depend on its own block alone (not on n, on the other rows,
+ * or on COCONS_SPATIAL_SORT), the totals are a tree of fixed shape over the per-observation terms, and repeated calls
+ * agree bit for bit.  A pivot of any block that is not positive and finite: the entry returns the smallest 1-based index i
+ * of such a block (a row of nn_pred for cocons_vecchia_predict) and writes no output; the handle stays usable.
+ * Returns: 0, such an index > 0, or < 0 with cocons_last_error().                                                      */
+cocons_fit *cocons_fit_create_vecchia(int n, int p, int r, const double *locs, const double *X, const double *z,
+                                      const double *smooth_limits, int device, int m, const int *nn);
+/* theta (6 x p table) and mean (p) as for cocons_neg2loglik_dense.  parts (1 + r doubles, may be NULL): parts[0] =
+ * sum_i log d_i, parts[1 + k] = sum_i y_ik^2 with y_k the whitened z_k - X mean; *value = sum_k [ n log 2 pi +
+ * 2 parts[0] + parts[1 + k] ].                                                                                         */
+int cocons_neg2loglik_vecchia(cocons_fit *fit, const double *theta, const double *mean, double *value, double *parts);
+/* U B for c >= 1 columns: B and out n x c column-major in the caller's order, out[i, :] = the last component of
+ * C_i^-1 B[(neighbours of i, i), :]; logd[i] = log d_i (may be NULL).  U'U approximates Sigma^-1: the building block of the
+ * forms with covariates in the mean (Profile, REML, GLS), which the caller finishes in O(n c^2).                        */
+int cocons_vecchia_whiten(cocons_fit *fit, const double *theta, int c, const double *B, double *out, double *logd);
+/* Local kriging at mp >= 0 new locations (locs_pred mp x 2, X_pred mp x p, column-major): nn_pred is mp x m_pred
+ * column-major, 1-based indices into the observations, 0 = none, m_pred in 1 .. 63.  For row i with K its neighbours' block
+ * (as above) and c the cross-covariance to them by cocons_cov_rns_pred's rule (an exact coordinate match gives the
+ * prediction side's diagonal value; the new site is never part of the factored block, so a site on top of an observation is
+ * well posed):  stochastic[i] = c' K^-1 (z[nb, z_col] - X[nb] mean),  quadform[i] = c' K^-1 c  -- the two outputs of
+ * cocons_predict_dense, for the same host tail.  A row without neighbours gives 0 and 0.  Rows are processed in chunks of
+ * 16384 with buffers of the call (device memory does not grow with mp); a row's outputs depend neither on the chunking nor
+ * on the other rows, bit for bit.  Refusals (< 0) as for the table of the handle, and a coordinate that is not finite.    */
+int cocons_vecchia_predict(cocons_fit *fit, const double *theta, const double *mean, int z_col, int mp,
+                           const double *locs_pred, const double *X_pred, int m_pred, const int *nn_pred,
+                           double *stochastic, double *quadform);
+/* out4 = {n, m, device bytes the handle holds (data, table, scratch), rows per chunk of cocons_vecchia_predict} */
+int cocons_vecchia_info(cocons_fit *fit, long long *out4);
+
 /* ---- fit handle: everything that is constant over an optimisation -------------
  * Created once per cocoOptim / getHessian call from the arguments the reference
  * passes unchanged to every GetNeg2loglikelihood* evaluation
