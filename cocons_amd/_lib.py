@@ -62,6 +62,7 @@ SIGNATURES = {
     "cocons_fit_create_vecchia": (c_vp, [c_int, c_int, c_int, c_dp, c_dp, c_dp, c_dp, c_int, c_int, ctypes.POINTER(c_int)]),
     "cocons_neg2loglik_vecchia": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp]),
     "cocons_vecchia_whiten": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_dp]),
+    "cocons_neg2loglik_grad_vecchia": (c_int, [c_vp, c_dp, c_dp, c_int, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "cocons_vecchia_predict": (c_int, [c_vp, c_dp, c_dp, c_int, c_int, c_dp, c_dp, c_int, ctypes.POINTER(c_int), c_dp, c_dp]),
     "cocons_vecchia_info": (c_int, [c_vp, ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_fit_destroy": (None, [c_vp]),

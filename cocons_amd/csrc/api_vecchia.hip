@@ -1,14 +1,14 @@
 // api_vecchia.hip -- C ABI of the Vecchia approximation: the third kind of handle -- data, a neighbour table and
-// O(n (m + 16)) bytes of scratch, never an n x n buffer -- and the three entries on it: the -2 log-likelihood, the whitening of
-// given columns, and local kriging.  One evaluation is: the location parameters for theta (loc_params_kernel, then their
+// O(n (m + 16)) bytes of scratch, never an n x n buffer -- and the entries on it: the -2 log-likelihood, its analytic gradient
+// (DESIGN.md 4s), the whitening of given columns, and local kriging.  One evaluation is: the location parameters for theta (loc_params_kernel, then their
 // transpose to one record per location), the right-hand sides, ONE launch of vecchia_block_kernel with a wavefront per
 // observation, and -- for the value -- the totals as a tree of fixed shape.  Nothing here factors through api.hip.
 #include "fit.hpp"
 
 int vecchia_refuse(const char *who)
 {
-    return fail(-1, "%s: not available on a Vecchia fit (cocons_neg2loglik_vecchia, cocons_vecchia_whiten and "
-                    "cocons_vecchia_predict are)", who);
+    return fail(-1, "%s: not available on a Vecchia fit (cocons_neg2loglik_vecchia, cocons_neg2loglik_grad_vecchia, "
+                    "cocons_vecchia_whiten and cocons_vecchia_predict are)", who);
 }
 
 static int vecchia_only(cocons_fit *f, const char *who)
@@ -150,6 +150,84 @@ extern "C" int cocons_neg2loglik_vecchia(cocons_fit *f, const double *theta, con
     for (int k = 0; k < r; ++k) total += n * LOG_2PI + 2 * f->hout[0] + f->hout[1 + k];
     if (parts) for (int k = 0; k <= r; ++k) parts[k] = f->hout[k];
     *value = total;
+    return 0;
+}
+
+// Value and gradient from one launch per chunk of VECCHIA_GRAD_CHUNK observations.  The value's totals are
+// launch_vecchia_sums over log d and the whitened columns of all n rows -- the value entry's tree over the value kernel's
+// numbers --, the gradient's the same tree over the per-observation records, its first stage run chunk by chunk.
+extern "C" int cocons_neg2loglik_grad_vecchia(cocons_fit *f, const double *theta, const double *mean, int c, const double *B,
+                                              double *sum_logliks, double *parts, double *grad_theta, double *grad_quad,
+                                              double *grad_mean)
+{
+    const char *who = "cocons_neg2loglik_grad_vecchia";
+    if (!f) return fail(-1, "%s: null fit handle", who);
+    if (!theta || !sum_logliks || !grad_theta || (!B && (!mean || !grad_mean))) return fail(-1, "%s: null argument", who);
+    if (B && (mean || grad_mean))
+        return fail(-1, "%s: B is given, so mean and grad_mean must be NULL (the columns are used as they are)", who);
+    if (B && c < 1) return fail(-1, "%s: c = %d (at least one column expected)", who, c);
+    FIT_ENTER_ANY(f);
+    if (int rc = vecchia_only(f, who)) return rc;
+    VecchiaState *V = f->vecchia.get();
+    const int n = f->n, p = f->p, nc = B ? c : f->r, ncol = vecchia_rec_cols(p);
+    const int nseg = (n + VECCHIA_SUM_SEG - 1) / VECCHIA_SUM_SEG, chunk = std::min(n, VECCHIA_GRAD_CHUNK);
+    hipStream_t s = f->stream;
+    HIPCHK_AT(who, V->B.reserve((size_t)n * nc, s, nullptr));
+    HIPCHK_AT(who, V->W.reserve((size_t)n * (1 + nc), s, nullptr));
+    HIPCHK_AT(who, V->part.reserve(vecchia_sum_scratch_doubles(n, 1 + nc), s, nullptr));
+    HIPCHK_AT(who, V->gsite.reserve((size_t)GSITE_FIELDS * f->npad, s, nullptr));
+    HIPCHK_AT(who, V->gaos.reserve((size_t)VECCHIA_GSITE_REC * n, s, nullptr));
+    HIPCHK_AT(who, V->grec.reserve((size_t)chunk * ncol, s, nullptr));
+    HIPCHK_AT(who, V->gpart.reserve((size_t)nseg * ncol, s, nullptr));
+    HIPCHK_AT(who, V->gout.reserve((size_t)(1 + nc) + ncol, s, nullptr));
+    double hmean[COCONS_P_MAX];
+    if (!B) for (int i = 0; i < p; ++i) hmean[i] = canon_nan(mean[i]);
+    if (int rc = reset_info(f)) return rc;
+    if (B) HIPCHK_AT(who, upload_canon(V->B, B, (size_t)n * nc, s));
+    const ModeSel ms = vecchia_records(f, theta, 0, V->aos);
+    if (!B) launch_vecchia_resid(n, p, f->dX, n, hmean, f->dz, n, 0, nc, V->B, (size_t)n, s);
+    // the site derivatives beside the records (grad_site_kernel, as every other gradient here forms them)
+    ThetaVecs tv;
+    make_theta_vecs(theta, p, tv);
+    const int smooth_free = ms.smooth_kind == SMOOTH_LOGISTIC_SQRT && f->smooth_limits[1] != f->smooth_limits[0];
+    launch_grad_site(loc_args(n, p, f->dX, f->dlocs, V->gsite, f->npad, tv, ms.smooth_kind, f->smooth_limits), V->gsite,
+                     f->npad, smooth_free, s);
+    launch_vecchia_site_rec(V->gsite, f->npad, n, V->gaos, s);
+    VecchiaArgs a;
+    a.m = V->m; a.kb = V->m + 1; a.nbr = V->nbr; a.aosK = V->aos; a.aosG = V->gaos;
+    a.gr = ms.gr; a.nu_fixed = ms.nu_fixed; a.smooth_free = smooth_free;
+    a.B = V->B; a.ldb = (size_t)n; a.nb = nc;
+    a.logd = V->W; a.Y = V->W + n; a.ldy = (size_t)n;
+    a.X = f->dX; a.ldx = n; a.p = p;
+    a.rec = V->grec; a.ldr = (size_t)chunk;
+    a.fail = f->dinfo;
+    for (int r0 = 0; r0 < n; r0 += chunk) {
+        a.rows = std::min(chunk, n - r0); a.obs0 = r0; a.row0 = r0;
+        launch_vecchia_grad_blocks(ms.mode, a, s);
+        launch_vecchia_chunk_sums(V->grec, (size_t)chunk, a.rows, ncol, V->gpart, r0 / VECCHIA_SUM_SEG, nseg, s);
+    }
+    launch_vecchia_sums(V->W, (size_t)n, n, 1 + nc, V->part, V->gout, s);
+    launch_vecchia_final_sums(V->gpart, nseg, ncol, V->gout + (1 + nc), s);
+    std::vector<double> h((size_t)(1 + nc) + ncol);
+    HIPCHK_AT(who, hipMemcpyAsync(h.data(), V->gout, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (int st = vecchia_status(f, who)) return st;
+    double total = 0.0;
+    for (int k = 0; k < nc; ++k) total += n * LOG_2PI + 2 * h[0] + h[1 + k];
+    if (parts) for (int k = 0; k <= nc; ++k) parts[k] = h[k];
+    *sum_logliks = total;
+    // the table in cocons_neg2loglik_grad_dense's conventions: scale[0] takes the global-range sum, scale[k >= 1] the factor 2
+    const double *g = h.data() + (1 + nc);
+    for (int t = 0; t < 6; ++t)
+        for (int k = 0; k < p; ++k) {
+            double lg = g[t * p + k], qd = g[6 * p + t * p + k];
+            if (t == TH_SCALE) {
+                if (k == 0) { lg = g[12 * p]; qd = g[12 * p + 1]; }
+                else { lg = 2.0 * lg; qd = 2.0 * qd; }
+            }
+            grad_theta[t * p + k] = lg + qd;
+            if (grad_quad) grad_quad[t * p + k] = qd;
+        }
+    if (grad_mean) for (int k = 0; k < p; ++k) grad_mean[k] = -2.0 * g[12 * p + 2 + k];
     return 0;
 }
 

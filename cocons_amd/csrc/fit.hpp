@@ -265,10 +265,17 @@ struct VecchiaState {
     DevBuf<double> B;             // n x c: the right-hand sides (the residuals, or cocons_vecchia_whiten's columns)
     DevBuf<double> W;             // n x (1 + c): log d, then the whitened columns
     DevBuf<double> part;          // first-stage sums of the totals
+    // cocons_neg2loglik_grad_vecchia, allocated by its first call: O(n) with a small constant, plus one chunk
+    DevBuf<double> gsite;         // GSITE_FIELDS x npad: launch_grad_site's SoA
+    DevBuf<double> gaos;          // VECCHIA_GSITE_REC x n: the same as one record per location
+    DevBuf<double> grec;          // VECCHIA_GRAD_CHUNK x vecchia_rec_cols(p): the per-observation records of one chunk
+    DevBuf<double> gpart;         // their first-stage sums, all segments of n
+    DevBuf<double> gout;          // the totals: 1 + c of the value, then vecchia_rec_cols(p)
     long long bytes() const
     {
         return (long long)(nbr.count() * sizeof(int) +
-                           (aos.count() + aos2.count() + B.count() + W.count() + part.count()) * sizeof(double));
+                           (aos.count() + aos2.count() + B.count() + W.count() + part.count() + gsite.count() + gaos.count() +
+                            grec.count() + gpart.count() + gout.count()) * sizeof(double));
     }
 };
 

@@ -638,9 +638,31 @@ struct VecchiaArgs {
     double *Y = nullptr; size_t ldy = 0;
     double *logd = nullptr, *stoch = nullptr, *quad = nullptr;
     int *fail = nullptr; int row0 = 0;
+    // the gradient launch only (launch_vecchia_grad_blocks): block b of the launch is observation obs0 + b
+    int obs0 = 0;
+    const double *aosG = nullptr;      // launch_vecchia_site_rec's records
+    int smooth_free = 0;
+    const double *X = nullptr; int ldx = 0, p = 0;
+    double *rec = nullptr; size_t ldr = 0;     // the per-observation records, column q of block b at rec[q ldr + b]
 };
 size_t vecchia_lds_bytes(int m, bool pred);
 void launch_vecchia_blocks(int mode, bool pred, const VecchiaArgs &a, hipStream_t s);
+// The gradient variant of the likelihood launch: logd and Y as there (the same code), and per observation the record of
+// vecchia_rec_cols(p) doubles -- with q = f p + k for family f and column k of X: [q] the log-determinant's share of the
+// site sums contracted with X, [6 p + q] the quadratic forms' share, [12 p] and [12 p + 1] the two shares of the global-range
+// sum, [12 p + 2 + k] = (sum_c y_c) sum_rows s[row] X[site(row), k] (the mean gradient without its factor -2).
+constexpr int VECCHIA_GSITE_REC = 4;   // doubles per location of launch_vecchia_site_rec: GSITE_FIELDS
+constexpr int VECCHIA_GRAD_CHUNK = 8 * VECCHIA_SUM_SEG;     // observations per gradient launch (a multiple of VECCHIA_SUM_SEG)
+inline int vecchia_rec_cols(int p) { return 13 * p + 2; }
+// rec[i * VECCHIA_GSITE_REC + f] = soa[i + f * stride] for the n locations of launch_grad_site's SoA
+void launch_vecchia_site_rec(const double *soa, size_t stride, int n, double *rec, hipStream_t s);
+size_t vecchia_grad_lds_bytes(int m);
+void launch_vecchia_grad_blocks(int mode, const VecchiaArgs &a, hipStream_t s);
+// launch_vecchia_sums in two steps for values that arrive in chunks: the first stage over the `rows` values of a chunk that
+// starts at segment seg0 of nseg (plain sums in every column), then the second stage over all nseg segments.  The totals are
+// the tree launch_vecchia_sums would form over all the values at once, whatever the chunk.
+void launch_vecchia_chunk_sums(const double *v, size_t ldv, int rows, int ncol, double *part, int seg0, int nseg, hipStream_t s);
+void launch_vecchia_final_sums(const double *part, int nseg, int ncol, double *out, hipStream_t s);
 // out[q] = sum_i v[i + q ldv] (q = 0) or of its squares (q >= 1) over i < n, for q < ncol: a tree of fixed shape over values in
 // memory; part: vecchia_sum_scratch_doubles(n, ncol) doubles
 size_t vecchia_sum_scratch_doubles(int n, int ncol);

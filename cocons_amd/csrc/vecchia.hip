@@ -9,6 +9,9 @@
 //                           there column by column with lane = row, and the right-hand sides carried through the forward
 //                           substitution in registers.  PRED: the last row is a prediction site (cov_rns_pred's rule) and stays
 //                           out of the factored block.
+//                           GRAD: the same gather, pair loop, factorisation and substitution, then the block's
+//                           share of the gradient: two backward solves, the pair partials contracted with the block's weights,
+//                           per-site sums in one fixed order, and one record per observation.
 //   vecchia_sum_kernel    : the totals over the per-observation terms, as a two-stage tree of fixed shape.
 //
 // Every sum of a block runs in ascending row order of the block, which the host makes the ascending order of the caller's
@@ -19,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 #include "matern_device.hpp"
+#include "grad_pair.hpp"
 
 namespace cocons {
 
@@ -44,6 +48,24 @@ void launch_vecchia_aos(const double *soa, size_t stride, int n, double *aos, hi
 {
     if (n <= 0) return;
     hipLaunchKernelGGL(vecchia_aos_kernel, dim3((n + 63) / 64), dim3(256), 0, s, soa, stride, n, aos);
+}
+
+// the four site derivatives of grad_site_kernel as one 32-byte record per location: what the gradient launch gathers beside
+// the parameters' records
+__global__ void __launch_bounds__(256)
+vecchia_site_rec_kernel(const double *soa, size_t stride, int n, double *rec)
+{
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)n * VECCHIA_GSITE_REC) return;
+    const size_t i = e / VECCHIA_GSITE_REC, f = e % VECCHIA_GSITE_REC;
+    rec[e] = soa[f * stride + i];
+}
+
+void launch_vecchia_site_rec(const double *soa, size_t stride, int n, double *rec, hipStream_t s)
+{
+    if (n <= 0) return;
+    const size_t total = (size_t)n * VECCHIA_GSITE_REC;
+    hipLaunchKernelGGL(vecchia_site_rec_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, soa, stride, n, rec);
 }
 
 // out[i + k ldo] = z[i + (col0 + k) ldz] - (X mean)[i]; the trend as rhs_rows_kernel forms it (a plain dot product, i ascending)
@@ -84,16 +106,42 @@ __device__ __forceinline__ int tri_at(int r, int c) { return r * (r + 1) / 2 + c
 //   par2  LOCP_FIELDS x kb   PRED only: the same rows in the prediction branch's parameters, the prediction site last;
 //   tri   kb (kb + 1) / 2    the block, then its factor (the pivots stay in registers: lane r keeps C(r, r));
 //   nb    kb ints            the rows' locations.
-template <int MODE, bool PRED>
+// GRAD (vecchia_grad_lds_bytes) keeps tri at VECCHIA_STG doubles or more -- once s and h are known the factor is dead and the
+// pair walk stages its contributions there -- and puts VECCHIA_GX x kb doubles between tri and nb:
+//   sp    GSITE_FIELDS x kb  the rows' site derivatives (grad_site_kernel's fields) as an SoA of stride kb;
+//   sv, hv  kb each          s = L^-T e_last and h = L^-T v;
+//   gs    2 GFAM x kb        the rows' site sums: the log-determinant's share per family, then the quadratic forms'.
+constexpr int VECCHIA_STG = 4 * GFAM * 64;              // a pass of 64 pairs: (ii side, jj side) x (two shares) x GFAM
+constexpr int VECCHIA_GX = GSITE_FIELDS + 2 + 2 * GFAM;
+
+// pair t = r (r - 1) / 2 + c of the packed strict lower triangle, r > c
+__device__ __forceinline__ void tri_pair(int t, int &r, int &c)
+{
+    r = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)t)) * 0.5f);
+    while (r * (r - 1) / 2 > t) --r;
+    while ((r + 1) * r / 2 <= t) ++r;
+    c = t - r * (r - 1) / 2;
+}
+
+__device__ __forceinline__ double vecchia_wave_sum(double v)
+{
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+template <int MODE, bool PRED, bool GRAD>
 __global__ void __launch_bounds__(64)
 vecchia_block_kernel(VecchiaArgs a)
 {
+    static_assert(!(PRED && GRAD), "the gradient is the likelihood launch's");
     extern __shared__ double vecchia_lds[];
-    const int lane = threadIdx.x, row = blockIdx.x, kb = a.kb;
+    const int lane = threadIdx.x, row = (GRAD ? a.obs0 : 0) + blockIdx.x, kb = a.kb;
     double *par = vecchia_lds;
     double *par2 = par + (PRED ? LOCP_FIELDS * kb : 0);
     double *tri = par2 + LOCP_FIELDS * kb;
-    int *nb = (int *)(tri + kb * (kb + 1) / 2);
+    const int ntri = kb * (kb + 1) / 2;
+    double *gx = tri + ((GRAD && ntri < VECCHIA_STG) ? VECCHIA_STG : ntri);
+    int *nb = (int *)(gx + (GRAD ? VECCHIA_GX * kb : 0));
 
     // the row's neighbours: ascending, the free places (-1) behind them
     const int mine = lane < a.m ? a.nbr[(size_t)row * a.m + lane] : -1;
@@ -110,16 +158,19 @@ vecchia_block_kernel(VecchiaArgs a)
         else if (r < k) { par[f * kb + r] = a.aosK[at]; par2[f * kb + r] = a.aosC[at]; }
         else { par[f * kb + r] = 0.0; par2[f * kb + r] = a.aosP[at]; }
     }
+    if (GRAD)
+        for (int e = lane; e < nrows * VECCHIA_GSITE_REC; e += 64) {
+            const int r = e / VECCHIA_GSITE_REC, f = e % VECCHIA_GSITE_REC;
+            gx[f * kb + r] = a.aosG[(size_t)nb[r] * VECCHIA_GSITE_REC + f];
+        }
     __syncthreads();
     // the block: pair t = r (r - 1) / 2 + c is (r, c), r > c, evaluated with the EARLIER row on the `ii` side (the reference's
     // orientation, which the u <= eps rule sees); PRED, last row: the prediction site on the `ii` side, exact coordinate
     // matches give its own diagonal value (cov_rns_pred)
     const int npairs = nrows * (nrows - 1) / 2;
     for (int t = lane; t < npairs; t += 64) {
-        int r = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)t)) * 0.5f);
-        while (r * (r - 1) / 2 > t) --r;
-        while ((r + 1) * r / 2 <= t) ++r;
-        const int c = t - r * (r - 1) / 2;
+        int r, c;
+        tri_pair(t, r, c);
         double v;
         if (PRED && r == k) v = pair_value_idx<MODE_GEOM>(par2, (size_t)kb, r, par2, (size_t)kb, c, a.gr, 0.0, true);
         else v = pair_value_idx<MODE>(par, (size_t)kb, c, par, (size_t)kb, r, a.gr, a.nu_fixed, false);
@@ -144,13 +195,15 @@ vecchia_block_kernel(VecchiaArgs a)
             for (int c = j + 1; c <= lane; ++c) tri[myrow + c] -= lrj * tri[tri_at(c, j)];
     }
     if (bad) {
-        if (lane == 0) atomicMin(a.fail, a.row0 + row + 1);
+        if (lane == 0) atomicMin(a.fail, a.row0 + (int)blockIdx.x + 1);
         return;
     }
     __syncthreads();
     // forward substitution over the neighbours' rows, VECCHIA_G right-hand sides at a time; lane k ends with
-    // b_k - sum_j C(k, j) y_j, j ascending
+    // b_k - sum_j C(k, j) y_j, j ascending.  GRAD: every lane j ends with the numerator of w_c[j] (the steps from j on
+    // leave it alone), so v = sum_c y_c w_c, sum_c y_c^2 and sum_c y_c are formed on the way, the columns ascending
     const int site = lane < nrows ? nb[lane] : 0;
+    double vacc = 0.0, ysq = 0.0, ysum = 0.0;
     for (int c0 = 0; c0 < a.nb; c0 += VECCHIA_G) {
         double b[VECCHIA_G];
 #pragma unroll
@@ -172,6 +225,17 @@ vecchia_block_kernel(VecchiaArgs a)
                 else a.Y[(size_t)row + (size_t)(c0 + g) * a.ldy] = b[g] / piv_mine;
             }
         }
+        if (GRAD) {
+#pragma unroll
+            for (int g = 0; g < VECCHIA_G; ++g) {
+                if (c0 + g >= a.nb) break;
+                const double w = b[g] / piv_mine;                     // lane k: the whitened value, as stored above
+                const double y = __shfl(w, k);
+                if (lane < k) vacc += y * w;
+                ysq += y * y;
+                ysum += y;
+            }
+        }
     }
     if (lane == k) {
         if (PRED) {
@@ -179,6 +243,112 @@ vecchia_block_kernel(VecchiaArgs a)
             for (int j = 0; j < k; ++j) { const double v = tri[myrow + j]; q += v * v; }
             a.quad[row] = q;
         } else if (a.logd) a.logd[row] = log(piv_mine);
+    }
+    if constexpr (GRAD) {
+        // The block's term f = nb 2 log d + sum_c y_c^2 has the derivative <W, dC> with W_log = nb s s' and
+        // W_quad = -(sum_c y_c^2) s s' - (h s' + s h'), s = L^-T e_last, h = L^-T v.
+        double *sp = gx, *sv = sp + GSITE_FIELDS * kb, *hv = sv + kb, *gs = hv + kb;
+        // the two backward solves, one column of L' (a row of the packed factor) per step; lane j ends with component j
+        double rs = lane == k ? 1.0 : 0.0, rh = lane < k ? vacc : 0.0, s_mine = 0.0, h_mine = 0.0;
+        for (int j = k; j >= 0; --j) {
+            const double xs = __shfl(rs / piv_mine, j), xh = __shfl(rh / piv_mine, j);
+            if (lane == j) { s_mine = xs; h_mine = xh; }
+            if (lane < j) {
+                const double l = tri[tri_at(j, 0) + lane];
+                rs -= l * xs;
+                rh -= l * xh;
+            }
+        }
+        __syncthreads();                   // the factor is dead from here on: tri is the staging of the pair walk
+        if (lane < nrows) { sv[lane] = s_mine; hv[lane] = h_mine; }
+        const double cn = (double)a.nb;
+        auto w_log = [&](double sa, double sb) { return cn * (sa * sb); };
+        auto w_quad = [&](double sa, double ha, double sb, double hb) { return 0.0 - ysq * (sa * sb) - (ha * sb + sa * hb); };
+        // a row's site sums in registers: the diagonal first -- W_aa (exp(eta_sd), nugget) --, then its pairs pass by pass
+        double acc[2 * GFAM];
+#pragma unroll
+        for (int f = 0; f < 2 * GFAM; ++f) acc[f] = 0.0;
+        if (lane < nrows) {
+            const double wl = w_log(s_mine, s_mine), wq = w_quad(s_mine, h_mine, s_mine, h_mine);
+            const double dsd = sp[3 * kb + lane], dng = par[12 * kb + lane];
+            acc[TH_SD_] = wl * dsd; acc[TH_NG_] = wl * dng;
+            acc[GFAM + TH_SD_] = wq * dsd; acc[GFAM + TH_NG_] = wq * dng;
+        }
+        __syncthreads();
+        // The pair walk: 64 pairs a pass, one per lane (the order of the assembly above), each pair's partials evaluated once
+        // and weighted with 2 W_log and 2 W_quad into the staging; then lane = row a adds what the pass holds for its site --
+        // its pairs (a, c), c < a ascending (the jj side), then its pairs (r, a), r > a ascending (the ii side).  A site's sum
+        // is therefore formed in one order that is a function of the block alone.
+        double *stg = tri;
+        double glob_l = 0.0, glob_q = 0.0;
+        for (int t0 = 0; t0 < npairs; t0 += 64) {
+            const int t = t0 + lane;
+            double da[GFAM], db[GFAM], dg = 0.0, w2l = 0.0, w2q = 0.0;
+#pragma unroll
+            for (int f = 0; f < GFAM; ++f) { da[f] = 0.0; db[f] = 0.0; }
+            if (t < npairs) {
+                int r, c;
+                tri_pair(t, r, c);
+                pair_partials<MODE>(par, (size_t)kb, sp, (size_t)kb, a.gr, a.nu_fixed, a.smooth_free, c, r, da, db, dg);
+                const double sa = sv[r], ha = hv[r], sb = sv[c], hb = hv[c];
+                w2l = 2.0 * w_log(sa, sb);
+                w2q = 2.0 * w_quad(sa, ha, sb, hb);
+                glob_l += w2l * dg;
+                glob_q += w2q * dg;
+            }
+#pragma unroll
+            for (int f = 0; f < GFAM; ++f) {
+                stg[(0 * GFAM + f) * 64 + lane] = w2l * da[f];
+                stg[(1 * GFAM + f) * 64 + lane] = w2q * da[f];
+                stg[(2 * GFAM + f) * 64 + lane] = w2l * db[f];
+                stg[(3 * GFAM + f) * 64 + lane] = w2q * db[f];
+            }
+            __syncthreads();
+            if (lane < nrows) {
+                const int tend = min(t0 + 64, npairs), mine0 = lane * (lane - 1) / 2;
+                for (int u = max(t0, mine0); u < min(tend, mine0 + lane); ++u) {
+#pragma unroll
+                    for (int f = 0; f < GFAM; ++f) {
+                        acc[f] += stg[(2 * GFAM + f) * 64 + (u - t0)];
+                        acc[GFAM + f] += stg[(3 * GFAM + f) * 64 + (u - t0)];
+                    }
+                }
+                int r_lo, r_hi, c_;
+                tri_pair(t0, r_lo, c_);
+                tri_pair(tend - 1, r_hi, c_);
+                for (int r = max(r_lo, lane + 1); r <= r_hi; ++r) {
+                    const int u = r * (r - 1) / 2 + lane;
+                    if (u < t0 || u >= tend) continue;
+#pragma unroll
+                    for (int f = 0; f < GFAM; ++f) {
+                        acc[f] += stg[(0 * GFAM + f) * 64 + (u - t0)];
+                        acc[GFAM + f] += stg[(1 * GFAM + f) * 64 + (u - t0)];
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        if (lane < nrows) {
+#pragma unroll
+            for (int f = 0; f < 2 * GFAM; ++f) gs[f * kb + lane] = acc[f];
+        }
+        glob_l = vecchia_wave_sum(glob_l);
+        glob_q = vecchia_wave_sum(glob_q);
+        __syncthreads();
+        // the record: the site sums contracted with X over the block's rows, ascending
+        const int p = a.p, b = blockIdx.x;
+        for (int o = lane; o < (2 * GFAM + 1) * p; o += 64) {
+            const int q = o / p, kx = o % p;
+            const double *g = q < 2 * GFAM ? gs + q * kb : sv;
+            double s = 0.0;
+            for (int rr = 0; rr < nrows; ++rr) s += g[rr] * a.X[(size_t)nb[rr] + (size_t)kx * a.ldx];
+            if (q < 2 * GFAM) a.rec[(size_t)o * a.ldr + b] = s;
+            else a.rec[(size_t)(2 * GFAM * p + 2 + kx) * a.ldr + b] = ysum * s;
+        }
+        if (lane == 0) {
+            a.rec[(size_t)(2 * GFAM * p) * a.ldr + b] = glob_l;
+            a.rec[(size_t)(2 * GFAM * p + 1) * a.ldr + b] = glob_q;
+        }
     }
 }
 
@@ -193,10 +363,30 @@ template <bool PRED> static void vecchia_launch(int mode, const VecchiaArgs &a, 
     const size_t shm = vecchia_lds_bytes(a.m, PRED);          // m <= 63: at most 31 KB, no attribute needed
     const dim3 grid((unsigned)a.rows), block(64);
     switch (mode) {
-    case MODE_HALF: hipLaunchKernelGGL((vecchia_block_kernel<MODE_HALF, PRED>), grid, block, shm, s, a); break;
-    case MODE_THREEHALF: hipLaunchKernelGGL((vecchia_block_kernel<MODE_THREEHALF, PRED>), grid, block, shm, s, a); break;
-    case MODE_FIVEHALF: hipLaunchKernelGGL((vecchia_block_kernel<MODE_FIVEHALF, PRED>), grid, block, shm, s, a); break;
-    default: hipLaunchKernelGGL((vecchia_block_kernel<MODE_GEOM, PRED>), grid, block, shm, s, a); break;
+    case MODE_HALF: hipLaunchKernelGGL((vecchia_block_kernel<MODE_HALF, PRED, false>), grid, block, shm, s, a); break;
+    case MODE_THREEHALF: hipLaunchKernelGGL((vecchia_block_kernel<MODE_THREEHALF, PRED, false>), grid, block, shm, s, a); break;
+    case MODE_FIVEHALF: hipLaunchKernelGGL((vecchia_block_kernel<MODE_FIVEHALF, PRED, false>), grid, block, shm, s, a); break;
+    default: hipLaunchKernelGGL((vecchia_block_kernel<MODE_GEOM, PRED, false>), grid, block, shm, s, a); break;
+    }
+}
+
+size_t vecchia_grad_lds_bytes(int m)
+{
+    const size_t kb = (size_t)m + 1, ntri = kb * (kb + 1) / 2;
+    return (LOCP_FIELDS * kb + (ntri < (size_t)VECCHIA_STG ? (size_t)VECCHIA_STG : ntri) + VECCHIA_GX * kb) * sizeof(double) +
+           kb * sizeof(int);
+}
+
+void launch_vecchia_grad_blocks(int mode, const VecchiaArgs &a, hipStream_t s)
+{
+    if (a.rows <= 0) return;
+    const size_t shm = vecchia_grad_lds_bytes(a.m);           // m <= 63: at most 32 KB, no attribute needed
+    const dim3 grid((unsigned)a.rows), block(64);
+    switch (mode) {
+    case MODE_HALF: hipLaunchKernelGGL((vecchia_block_kernel<MODE_HALF, false, true>), grid, block, shm, s, a); break;
+    case MODE_THREEHALF: hipLaunchKernelGGL((vecchia_block_kernel<MODE_THREEHALF, false, true>), grid, block, shm, s, a); break;
+    case MODE_FIVEHALF: hipLaunchKernelGGL((vecchia_block_kernel<MODE_FIVEHALF, false, true>), grid, block, shm, s, a); break;
+    default: hipLaunchKernelGGL((vecchia_block_kernel<MODE_GEOM, false, true>), grid, block, shm, s, a); break;
     }
 }
 
@@ -224,7 +414,7 @@ __device__ __forceinline__ double vecchia_tree(double acc, double *red)
 }
 
 __global__ void __launch_bounds__(256)
-vecchia_sum_kernel(const double *v, size_t ldv, int n, double *part)
+vecchia_sum_kernel(const double *v, size_t ldv, int n, double *part, int squares, int seg0, int nseg)
 {
     __shared__ double red[256];
     const int seg = blockIdx.x, q = blockIdx.y, t = threadIdx.x;
@@ -232,10 +422,10 @@ vecchia_sum_kernel(const double *v, size_t ldv, int n, double *part)
     double acc = 0.0;
     for (int s = 0; s < VECCHIA_SUM_SEG / 256; ++s) {
         const size_t i = (size_t)seg * VECCHIA_SUM_SEG + (size_t)s * 256 + t;
-        if (i < (size_t)n) { const double x = col[i]; acc += q > 0 ? x * x : x; }
+        if (i < (size_t)n) { const double x = col[i]; acc += (squares && q > 0) ? x * x : x; }
     }
     const double total = vecchia_tree(acc, red);
-    if (t == 0) part[(size_t)q * gridDim.x + seg] = total;
+    if (t == 0) part[(size_t)q * nseg + seg0 + seg] = total;
 }
 
 __global__ void __launch_bounds__(256)
@@ -254,7 +444,19 @@ size_t vecchia_sum_scratch_doubles(int n, int ncol) { return (size_t)((n + VECCH
 void launch_vecchia_sums(const double *v, size_t ldv, int n, int ncol, double *part, double *out, hipStream_t s)
 {
     const int nseg = (n + VECCHIA_SUM_SEG - 1) / VECCHIA_SUM_SEG;
-    hipLaunchKernelGGL(vecchia_sum_kernel, dim3(nseg, ncol), dim3(256), 0, s, v, ldv, n, part);
+    hipLaunchKernelGGL(vecchia_sum_kernel, dim3(nseg, ncol), dim3(256), 0, s, v, ldv, n, part, 1, 0, nseg);
+    hipLaunchKernelGGL(vecchia_sum_final_kernel, dim3(ncol), dim3(256), 0, s, part, nseg, out);
+}
+
+void launch_vecchia_chunk_sums(const double *v, size_t ldv, int rows, int ncol, double *part, int seg0, int nseg, hipStream_t s)
+{
+    if (rows <= 0) return;
+    const int segs = (rows + VECCHIA_SUM_SEG - 1) / VECCHIA_SUM_SEG;
+    hipLaunchKernelGGL(vecchia_sum_kernel, dim3(segs, ncol), dim3(256), 0, s, v, ldv, rows, part, 0, seg0, nseg);
+}
+
+void launch_vecchia_final_sums(const double *part, int nseg, int ncol, double *out, hipStream_t s)
+{
     hipLaunchKernelGGL(vecchia_sum_final_kernel, dim3(ncol), dim3(256), 0, s, part, nseg, out);
 }
 

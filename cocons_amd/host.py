@@ -1590,7 +1590,7 @@ def vecchia_neighbours_pred(locs, newlocs, m) -> np.ndarray:
 class CoconsVecchiaFit:
     """Handle of a Vecchia fit (cocons_fit_create_vecchia): (locs, x_covariates, z, smooth.limits) and the neighbour table
     `nn` (n x m, 1-based indices of EARLIER rows, 0 = none; `vecchia_neighbours` makes one).  The rows' order is the Vecchia
-    order.  No n x n buffer exists; the library refuses this handle everywhere but in the three cores below."""
+    order.  No n x n buffer exists; the library refuses this handle everywhere but in the cores below."""
 
     def __init__(self, locs, x_covariates, z, smooth_limits, nn, device=-1):
         L = _lib.load()
@@ -1622,6 +1622,28 @@ class CoconsVecchiaFit:
         _lib.check(self._L.cocons_neg2loglik_vecchia(self._h, _p(T), _p(mean), ctypes.byref(val), _p(parts)),
                    "cocons_neg2loglik_vecchia")
         return val.value, parts
+
+    def neg2loglik_grad_core(self, theta_list, B=None):
+        """(value, parts, grad_table, grad_quad, grad_mean) of cocons_neg2loglik_grad_vecchia: value and parts are
+        neg2loglik_core's to the bit, grad_table the 6 x p table of the whole value in the conventions of the dense
+        gradient, grad_quad the quadratic forms' share of it (the log-determinant's is grad_table - grad_quad), grad_mean p
+        doubles.  With B (n x c, the caller's order) the columns are used as given -- the forms with the mean profiled out
+        --, parts has 1 + c entries and grad_mean is None."""
+        T = theta_table(theta_list)
+        val = ctypes.c_double(0.0)
+        gt, gq = np.zeros((6, self.p)), np.zeros((6, self.p))
+        if B is None:
+            mean = np.ascontiguousarray(np.asarray(theta_list["mean"], dtype=np.float64))
+            parts, gm = np.zeros(1 + self.r), np.zeros(self.p)
+            st = self._L.cocons_neg2loglik_grad_vecchia(self._h, _p(T), _p(mean), 0, None, ctypes.byref(val), _p(parts),
+                                                        _p(gt), _p(gq), _p(gm))
+        else:
+            B = _f(np.asarray(B, dtype=np.float64).reshape(self.n, -1))
+            parts, gm = np.zeros(1 + B.shape[1]), None
+            st = self._L.cocons_neg2loglik_grad_vecchia(self._h, _p(T), None, int(B.shape[1]), _p(B), ctypes.byref(val),
+                                                        _p(parts), _p(gt), _p(gq), None)
+        _lib.check(st, "cocons_neg2loglik_grad_vecchia")
+        return val.value, parts, gt, gq, gm
 
     def whiten_core(self, theta_list, B):
         """(U B, log d) for the columns of B (n x c, the caller's order): U'U is the approximation's Sigma^-1."""
@@ -1725,6 +1747,102 @@ def GetNeg2loglikelihoodVecchiaREML(theta, par_pos, nn, locs, x_covariates, x_be
         logdet_w = float(np.sum(np.log(np.diag(np.linalg.cholesky(W)))))
         return (float(np.sum((n - rank) * np.log(2 * np.pi) + 2 * logdet + 2 * logdet_w + quad))
                 + getPen((n - rank) * f.r, lam, tl, smooth_limits))
+    finally:
+        if own:
+            f.close()
+
+
+def GetNeg2loglikelihoodVecchia_grad(theta, par_pos, nn, locs, x_covariates, smooth_limits, z, n, lam, safe=True, fit=None):
+    """`GetNeg2loglikelihoodVecchia` and its gradient over the optimiser's vector `theta` in one call: (value, gradient).
+    The value is that function's to the bit; the gradient is cocons_neg2loglik_grad_vecchia's plus the penalty's, carried
+    through getModelLists(type="diff") as GetNeg2loglikelihood_grad does.  A failing block gives (1e6, zeros) under `safe`."""
+    tl = getModelLists(theta, par_pos, "diff")
+    f, own = _with_vecchia_fit(fit, locs, x_covariates, z, smooth_limits, nn)
+    try:
+        try:
+            val, _, gt, _, gm = f.neg2loglik_grad_core(tl)
+        except CholeskyError:
+            if safe:
+                return 1e6, np.zeros(np.asarray(theta).size)
+            raise RuntimeError("Cholesky error")
+        N = n * f.r
+        g = getPen_grad(N, lam, tl, smooth_limits)
+        g["mean"] = g["mean"] + gm
+        for t, k in enumerate(COV_ASPECTS):
+            g[k] = g[k] + gt[t]
+        return val + getPen(N, lam, tl, smooth_limits), getModelLists_grad(g, par_pos)
+    finally:
+        if own:
+            f.close()
+
+
+def _vecchia_gls_resid(f, tl, z, x_betas):
+    """One whitening of [z | x_betas]: (W = Xb' U'U Xb, the residual columns z_k - Xb beta_k at the GLS estimate)."""
+    z = np.asarray(z, dtype=np.float64).reshape(f.n, -1)
+    xb = np.asarray(x_betas, dtype=np.float64).reshape(f.n, -1)
+    UB, _ = f.whiten_core(tl, np.hstack([z, xb]))
+    Uz, UX = UB[:, :z.shape[1]], UB[:, z.shape[1]:]
+    W = UX.T @ UX
+    return W, z - xb @ np.linalg.solve(W, UX.T @ Uz)
+
+
+def _vecchia_table_result(theta, par_pos, tl, val, gt, N, lam, smooth_limits):
+    g = getPen_grad(N, lam, tl, smooth_limits)
+    for t, k in enumerate(COV_ASPECTS):
+        g[k] = g[k] + gt[t]
+    return val + getPen(N, lam, tl, smooth_limits), getModelLists_grad(g, par_pos)
+
+
+def GetNeg2loglikelihoodVecchiaProfile_grad(theta, par_pos, nn, locs, x_covariates, smooth_limits, z, n, x_betas, lam,
+                                            safe=True, fit=None):
+    """`GetNeg2loglikelihoodVecchiaProfile` and its gradient over the optimiser's vector: (value, gradient).  One whitening
+    gives beta-hat; the gradient entry then runs on the columns z_k - Xb beta-hat_k.  By the envelope theorem the gradient
+    at fixed beta-hat is the gradient of the profiled value (the mean is profiled out: `par_pos["mean"]` holds no free entry)."""
+    tl = getModelLists(theta, par_pos, "diff")
+    f, own = _with_vecchia_fit(fit, locs, x_covariates, z, smooth_limits, nn)
+    try:
+        try:
+            _, E = _vecchia_gls_resid(f, tl, z, x_betas)
+            val, _, gt, _, _ = f.neg2loglik_grad_core(tl, B=E)
+        except CholeskyError:
+            if safe:
+                return 1e6, np.zeros(np.asarray(theta).size)
+            raise RuntimeError("Cholesky error")
+        return _vecchia_table_result(theta, par_pos, tl, val, gt, n * f.r, lam, smooth_limits)
+    finally:
+        if own:
+            f.close()
+
+
+def GetNeg2loglikelihoodVecchiaREML_grad(theta, par_pos, nn, locs, x_covariates, x_betas, smooth_limits, z, n, lam,
+                                         safe=True, fit=None):
+    """`GetNeg2loglikelihoodVecchiaREML` and its gradient over the optimiser's vector: (value, gradient).  Beside the
+    residual columns the restricted likelihood has log|X' U'U X|, whose derivative is sum_j d||U v_j||^2 at fixed
+    V = X chol(X' U'U X)^-T: the gradient entry runs on B = [residual columns | sqrt(r) V]; the log-determinant's share
+    (grad_theta - grad_quad) is scaled from B's columns to the r realisations, the quadratic forms' share taken as it is.
+    x_betas is accepted and unused, as there.  A rank-deficient x_covariates is refused (ValueError)."""
+    tl = getModelLists(theta, par_pos, "diff")
+    f, own = _with_vecchia_fit(fit, locs, x_covariates, z, smooth_limits, nn)
+    try:
+        X = np.asarray(x_covariates, dtype=np.float64)
+        rank = int(np.linalg.matrix_rank(X))
+        if rank < X.shape[1]:
+            raise ValueError("GetNeg2loglikelihoodVecchiaREML_grad: x_covariates has rank %d < %d columns "
+                             "(X' U'U X has no Cholesky factor)" % (rank, X.shape[1]))
+        r = f.r
+        try:
+            W, E = _vecchia_gls_resid(f, tl, z, X)
+            Lw = np.linalg.cholesky(W)
+            V = np.linalg.solve(Lw, X.T).T
+            _, parts, gt, gq, _ = f.neg2loglik_grad_core(tl, B=np.hstack([E, np.sqrt(r) * V]))
+        except CholeskyError:
+            if safe:
+                return 1e6, np.zeros(np.asarray(theta).size)
+            raise RuntimeError("Cholesky error")
+        logdet_w = float(np.sum(np.log(np.diag(Lw))))
+        val = float(np.sum((n - rank) * np.log(2 * np.pi) + 2 * parts[0] + 2 * logdet_w + parts[1:1 + r]))
+        table = (gt - gq) * (r / (r + X.shape[1])) + gq
+        return _vecchia_table_result(theta, par_pos, tl, val, table, (n - rank) * r, lam, smooth_limits)
     finally:
         if own:
             f.close()

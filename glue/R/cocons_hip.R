@@ -505,6 +505,15 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
   v[1] + .cocons.getPen(n * r, lambda, theta_list, smooth.limits)
 }
 
+# value and analytic gradient of the Vecchia -2 log-likelihood core (no penalty; DESIGN.md 4s): list(value, table = 6 x p
+# gradient over std.dev, scale, aniso, tilt, smooth, nugget, quad = the quadratic forms' share of it, mean = gradient over
+# theta$mean); NULL after a failing block under safe.  The gr = of an optimiser is built on it as on .cocons.hip.neg2loglik.grad
+.cocons.hip.vecchia.neg2loglik.grad <- function(fit, theta_list, safe = TRUE) {
+  res <- .cocons.hip.result(.Call(`_cocons_hip_vecchia_neg2loglik_grad`, fit, theta_list[-1], theta_list$mean), safe)
+  if (is.null(res)) return(NULL)
+  list(value = res[[1]], table = res[[2]], quad = res[[3]], mean = res[[4]])
+}
+
 # local kriging: cbind(stochastic, quadform) for the new locations, each from the observations its row of nn_pred names
 # (1-based, 0 = none) -- the two columns cocoPredict's dense branch takes from its solve (R/predict.R:165-173)
 .cocons.hip.vecchia.predict <- function(fit, theta_list, newlocs, X_pred, nn_pred, z_col = 1L) {

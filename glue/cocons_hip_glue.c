@@ -936,6 +936,37 @@ SEXP _cocons_hip_vecchia_neg2loglik(SEXP fitp, SEXP theta, SEXP mean)
     return out;
 }
 
+/* Vecchia value and analytic gradient (cocons_neg2loglik_grad_vecchia, the columns z - X mean): list(status, list(value,
+ * grad_table 6 x p, grad_quad 6 x p, grad_mean p)), the tables' rows in the order std.dev, scale, aniso, tilt, smooth,
+ * nugget; grad_quad is the quadratic forms' share of grad_table.  status > 0: the first failing row, the gradients zero */
+SEXP _cocons_hip_vecchia_neg2loglik_grad(SEXP fitp, SEXP theta, SEXP mean)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp);
+    double T[6 * COCONS_P_MAX], G[6 * COCONS_P_MAX] = {0}, Q[6 * COCONS_P_MAX] = {0}, val = NA_REAL;
+    theta_table(theta, p, T);
+    if (XLENGTH(mean) != p) Rf_error("theta$mean must have length %d", p);
+    SEXP gt = PROTECT(Rf_allocMatrix(REALSXP, 6, p));
+    SEXP gq = PROTECT(Rf_allocMatrix(REALSXP, 6, p));
+    SEXP gm = PROTECT(Rf_allocVector(REALSXP, p));
+    for (int k = 0; k < p; ++k) REAL(gm)[k] = 0.0;
+    int rc = cocons_neg2loglik_grad_vecchia(f, T, REAL(mean), 0, NULL, &val, NULL, G, Q, REAL(gm));
+    hip_check(rc, "GetNeg2loglikelihoodVecchia (gradient)");
+    for (int t = 0; t < 6; ++t)         /* (a failing block writes nothing: G and Q stay zero) */
+        for (int k = 0; k < p; ++k) {
+            REAL(gt)[t + 6 * k] = G[t * p + k];
+            REAL(gq)[t + 6 * k] = Q[t * p + k];
+        }
+    SEXP res = PROTECT(Rf_allocVector(VECSXP, 4));
+    SET_VECTOR_ELT(res, 0, Rf_ScalarReal(val));
+    SET_VECTOR_ELT(res, 1, gt);
+    SET_VECTOR_ELT(res, 2, gq);
+    SET_VECTOR_ELT(res, 3, gm);
+    SEXP out = status_value(rc, res);
+    UNPROTECT(4);
+    return out;
+}
+
 /* local kriging on a Vecchia handle (cocons_vecchia_predict): list(status, cbind(stochastic, quadform)); theta is the WHOLE
  * theta_list (its `mean` element is read by name like the others); nn_pred is the mp x m_pred matrix of 1-based indices
  * into the observations, 0 = none; z_col 1-based */
@@ -1126,6 +1157,7 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_fit_create_taper", (DL_FUNC)&_cocons_hip_fit_create_taper, 8},
     {"_cocons_hip_vecchia_create", (DL_FUNC)&_cocons_hip_vecchia_create, 6},
     {"_cocons_hip_vecchia_neg2loglik", (DL_FUNC)&_cocons_hip_vecchia_neg2loglik, 3},
+    {"_cocons_hip_vecchia_neg2loglik_grad", (DL_FUNC)&_cocons_hip_vecchia_neg2loglik_grad, 3},
     {"_cocons_hip_vecchia_predict", (DL_FUNC)&_cocons_hip_vecchia_predict, 6},
     {"_cocons_hip_fit_close", (DL_FUNC)&_cocons_hip_fit_close, 1},
     {"_cocons_hip_neg2loglik_parts", (DL_FUNC)&_cocons_hip_neg2loglik_parts, 3},

@@ -306,6 +306,22 @@ int cocons_neg2loglik_vecchia(cocons_fit *fit, const double *theta, const double
  * C_i^-1 B[(neighbours of i, i), :]; logd[i] = log d_i (may be NULL).  U'U approximates Sigma^-1: the building block of the
  * forms with covariates in the mean (Profile, REML, GLS), which the caller finishes in O(n c^2).                        */
 int cocons_vecchia_whiten(cocons_fit *fit, const double *theta, int c, const double *B, double *out, double *logd);
+/* The Vecchia -2 log-likelihood and its analytic gradient in one call: per block two backward solves on the
+ * factor the value needs anyway, then the pair partials of the dense gradient contracted with the block's weights.
+ * B == NULL: the columns are z - X mean (c is ignored, it is r); sum_logliks and parts (1 + r doubles, may be NULL) are what
+ * cocons_neg2loglik_vecchia returns, to the bit; grad_theta is the 6 x p table in theta's layout with the conventions of
+ * cocons_neg2loglik_grad_dense (scale[0] takes the global-range sum, scale[k >= 1] carries the factor 2); grad_quad (may be
+ * NULL) the same table for the quadratic forms alone, so that the log-determinant's share is grad_theta - grad_quad (as
+ * cocons_neg2loglik_grad_taper); grad_mean p doubles.
+ * B != NULL: n x c column-major, c >= 1, in the caller's order, used as given -- the forms with the mean profiled out
+ * (Profile, REML).  mean and grad_mean must be NULL.  value = sum_k [ n log 2 pi + 2 parts[0] + parts[1 + k] ] over the c
+ * columns, parts has 1 + c doubles.
+ * Every sum has a fixed order: repeated calls agree bit for bit, and nothing depends on the other rows of n or on the
+ * chunks the rows run in.  The first call allocates O(n) doubles plus one chunk of records, kept on the handle and counted by
+ * cocons_vecchia_info.  Returns and refusals as the other Vecchia entries; outputs are written on 0 only.                 */
+int cocons_neg2loglik_grad_vecchia(cocons_fit *fit, const double *theta, const double *mean, int c, const double *B,
+                                   double *sum_logliks, double *parts,
+                                   double *grad_theta, double *grad_quad, double *grad_mean);
 /* Local kriging at mp >= 0 new locations (locs_pred mp x 2, X_pred mp x p, column-major): nn_pred is mp x m_pred
  * column-major, 1-based indices into the observations, 0 = none, m_pred in 1 .. 63.  For row i with K its neighbours' block
  * (as above) and c the cross-covariance to them by cocons_cov_rns_pred's rule (an exact coordinate match gives the
