@@ -318,14 +318,14 @@ static int fisher_enqueue(cocons_fit *f, const double *theta, FisherCall &c, dou
 
 // the checks of the arguments that every information entry makes, in two parts: the pointers and the number of directions
 // before the handle is entered, the directions' entries (ndir x 6 p, all finite) behind the handle's own checks
-static int fisher_check_args(const char *who, const cocons_fit *f, const double *theta, int ndir, const double *dirs, const double *info)
+int fisher_check_args(const char *who, const cocons_fit *f, const double *theta, int ndir, const double *dirs, const double *info)
 {
     if (!f) return fail(-1, "%s: null fit handle", who);
     if (!theta || !dirs || !info) return fail(-1, "%s: null argument", who);
     return ndir < 1 || ndir > 7 * COCONS_P_MAX ? fail(-1, "%s: ndir = %d is outside [1, %d]", who, ndir, 7 * COCONS_P_MAX) : 0;
 }
 
-static int fisher_check_dirs(const char *who, int ndir, const double *dirs, int p)
+int fisher_check_dirs(const char *who, int ndir, const double *dirs, int p)
 {
     for (size_t e = 0; e < (size_t)ndir * 6 * p; ++e)
         if (!std::isfinite(dirs[e])) return fail(-1, "%s: direction %d has a non-finite entry", who, (int)(e / ((size_t)6 * p)));

@@ -1,6 +1,6 @@
 // api_vecchia.hip -- C ABI of the Vecchia approximation: the third kind of handle -- data, a neighbour table and
 // O(n (m + 16)) bytes of scratch, never an n x n buffer -- and the entries on it: the -2 log-likelihood, its analytic gradient
-// (DESIGN.md 4s), the whitening of given columns, and local kriging.  One evaluation is: the location parameters for theta (loc_params_kernel, then their
+// (DESIGN.md 4s), its expected information, the whitening of given columns, and local kriging.  One evaluation is: the location parameters for theta (loc_params_kernel, then their
 // transpose to one record per location), the right-hand sides, ONE launch of vecchia_block_kernel with a wavefront per
 // observation, and -- for the value -- the totals as a tree of fixed shape.  Nothing here factors through api.hip.
 #include "fit.hpp"
@@ -8,7 +8,7 @@
 int vecchia_refuse(const char *who)
 {
     return fail(-1, "%s: not available on a Vecchia fit (cocons_neg2loglik_vecchia, cocons_neg2loglik_grad_vecchia, "
-                    "cocons_vecchia_whiten and cocons_vecchia_predict are)", who);
+                    "cocons_fisher_vecchia, cocons_vecchia_whiten and cocons_vecchia_predict are)", who);
 }
 
 static int vecchia_only(cocons_fit *f, const char *who)
@@ -228,6 +228,72 @@ extern "C" int cocons_neg2loglik_grad_vecchia(cocons_fit *f, const double *theta
             if (grad_quad) grad_quad[t * p + k] = qd;
         }
     if (grad_mean) for (int k = 0; k < p; ++k) grad_mean[k] = -2.0 * g[12 * p + 2 + k];
+    return 0;
+}
+
+// Expected information of the Vecchia likelihood: one launch per chunk of vecchia_fisher_chunk observations,
+// one record per observation, and the totals through the gradient's two-stage tree -- a function of n alone, whatever the chunk.
+extern "C" int cocons_fisher_vecchia(cocons_fit *f, const double *theta, int ndir, const double *dirs, double *info,
+                                     double *info_mean)
+{
+    const char *who = "cocons_fisher_vecchia";
+    if (int rc = fisher_check_args(who, f, theta, ndir, dirs, info)) return rc;
+    FIT_ENTER_ANY(f);
+    if (int rc = vecchia_only(f, who)) return rc;
+    VecchiaState *V = f->vecchia.get();
+    const int n = f->n, p = f->p, ncol = vecchia_fisher_cols(ndir, p), ng = ndir * (ndir + 1) / 2;
+    if (int rc = fisher_check_dirs(who, ndir, dirs, p)) return rc;
+    const int nseg = (n + VECCHIA_SUM_SEG - 1) / VECCHIA_SUM_SEG, chunk = std::min(n, vecchia_fisher_chunk(ndir, p));
+    const int gd = vecchia_fisher_group(V->m, ndir);
+    if (vecchia_fisher_lds_bytes(V->m, ndir, gd) > VECCHIA_FISHER_LDS_MAX)
+        return fail(-1, "%s: %d directions at m = %d need %zu bytes of LDS a workgroup (%zu at most)", who, ndir, V->m,
+                    vecchia_fisher_lds_bytes(V->m, ndir, gd), VECCHIA_FISHER_LDS_MAX);
+    hipStream_t s = f->stream;
+    const size_t nd = (size_t)ndir * 6 * p;
+    const size_t counts[6] = {(size_t)GSITE_FIELDS * f->npad, (size_t)VECCHIA_GSITE_REC * n, nd, (size_t)chunk * ncol,
+                              (size_t)nseg * ncol, (size_t)ncol};
+    DevBuf<double> *bufs[6] = {&V->gsite, &V->gaos, &V->fdirs, &V->frec, &V->fpart, &V->fout};
+    size_t bytes = 0;
+    for (int b = 0; b < 6; ++b) bytes += std::max(counts[b], bufs[b]->count()) * sizeof(double);
+    for (int b = 0; b < 6; ++b)
+        if (hipError_t e = bufs[b]->reserve(counts[b], s, nullptr)) {
+            (void)hipGetLastError();
+            return fail(-100 - (int)e, "%s: the device cannot hold the %zu bytes of this call's scratch (%d directions, chunks of "
+                                       "%d rows): %s", who, bytes, ndir, chunk, hipGetErrorString(e));
+        }
+    if (int rc = reset_info(f)) return rc;
+    HIPCHK_AT(who, upload_canon(V->fdirs, dirs, nd, s));
+    const ModeSel ms = vecchia_records(f, theta, 0, V->aos);
+    ThetaVecs tv;
+    make_theta_vecs(theta, p, tv);
+    const int smooth_free = ms.smooth_kind == SMOOTH_LOGISTIC_SQRT && f->smooth_limits[1] != f->smooth_limits[0];
+    launch_grad_site(loc_args(n, p, f->dX, f->dlocs, V->gsite, f->npad, tv, ms.smooth_kind, f->smooth_limits), V->gsite,
+                     f->npad, smooth_free, s);
+    launch_vecchia_site_rec(V->gsite, f->npad, n, V->gaos, s);
+    VecchiaArgs a;
+    a.m = V->m; a.kb = V->m + 1; a.nbr = V->nbr; a.aosK = V->aos; a.aosG = V->gaos;
+    a.gr = ms.gr; a.nu_fixed = ms.nu_fixed; a.smooth_free = smooth_free;
+    a.nb = 0;                                   // no right-hand sides, no log d
+    a.X = f->dX; a.ldx = n; a.p = p;
+    a.ndir = ndir; a.gd = gd; a.dirs = V->fdirs;
+    a.rec = V->frec; a.ldr = (size_t)chunk;
+    a.fail = f->dinfo;
+    for (int r0 = 0; r0 < n; r0 += chunk) {
+        a.rows = std::min(chunk, n - r0); a.obs0 = r0; a.row0 = r0;
+        launch_vecchia_fisher_blocks(ms.mode, a, s);
+        launch_vecchia_chunk_sums(V->frec, (size_t)chunk, a.rows, ncol, V->fpart, r0 / VECCHIA_SUM_SEG, nseg, s);
+    }
+    launch_vecchia_final_sums(V->fpart, nseg, ncol, V->fout, s);
+    std::vector<double> h((size_t)ncol);
+    HIPCHK_AT(who, hipMemcpyAsync(h.data(), V->fout, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (int st = vecchia_status(f, who)) return st;
+    // mirrored from the lower triangles: symmetric to the bit
+    const double r = (double)f->r;
+    for (int a_ = 0; a_ < ndir; ++a_)
+        for (int b = 0; b <= a_; ++b) info[a_ * ndir + b] = info[b * ndir + a_] = r * h[(size_t)a_ * (a_ + 1) / 2 + b];
+    if (info_mean)
+        for (int k = 0; k < p; ++k)
+            for (int l = 0; l <= k; ++l) info_mean[k * p + l] = info_mean[l * p + k] = r * h[(size_t)ng + k * (k + 1) / 2 + l];
     return 0;
 }
 

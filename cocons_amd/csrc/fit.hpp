@@ -271,11 +271,17 @@ struct VecchiaState {
     DevBuf<double> grec;          // VECCHIA_GRAD_CHUNK x vecchia_rec_cols(p): the per-observation records of one chunk
     DevBuf<double> gpart;         // their first-stage sums, all segments of n
     DevBuf<double> gout;          // the totals: 1 + c of the value, then vecchia_rec_cols(p)
+    // cocons_fisher_vecchia, allocated by its first call (gsite and gaos above are shared with the gradient)
+    DevBuf<double> fdirs;         // ndir x 6 p: the directions
+    DevBuf<double> frec;          // vecchia_fisher_chunk x vecchia_fisher_cols: the per-observation records of one chunk
+    DevBuf<double> fpart;         // their first-stage sums, all segments of n
+    DevBuf<double> fout;          // the totals: vecchia_fisher_cols
     long long bytes() const
     {
         return (long long)(nbr.count() * sizeof(int) +
                            (aos.count() + aos2.count() + B.count() + W.count() + part.count() + gsite.count() + gaos.count() +
-                            grec.count() + gpart.count() + gout.count()) * sizeof(double));
+                            grec.count() + gpart.count() + gout.count() + fdirs.count() + frec.count() + fpart.count() +
+                            fout.count()) * sizeof(double));
     }
 };
 
@@ -647,6 +653,10 @@ int flags_reset(cocons_fit *f, int nt);
 int mbox_reset(cocons_fit *f, int nt, bool engine_schedule = true);
 int factorize(cocons_fit *f, const FactorView &v, std::vector<hipEvent_t> *ev_upd);
 int reset_info(cocons_fit *f);
+// the checks every information entry makes of its arguments (api_grad.hip): the pointers and the number of directions before
+// the handle is entered, the directions' entries (ndir x 6 p, all finite) behind the handle's own checks
+int fisher_check_args(const char *who, const cocons_fit *f, const double *theta, int ndir, const double *dirs, const double *info);
+int fisher_check_dirs(const char *who, int ndir, const double *dirs, int p);
 int info_status(cocons_fit *f);
 bool engine_retry(cocons_fit *f, int st);
 void dense_collect(cocons_fit *f, double *sum_logliks, double *parts);

@@ -644,6 +644,9 @@ struct VecchiaArgs {
     int smooth_free = 0;
     const double *X = nullptr; int ldx = 0, p = 0;
     double *rec = nullptr; size_t ldr = 0;     // the per-observation records, column q of block b at rec[q ldr + b]
+    // the information launch only (launch_vecchia_fisher_blocks); it uses obs0, aosG, smooth_free, X and rec too
+    int ndir = 0, gd = 0;              // directions, and how many of them one pair walk serves (vecchia_fisher_group)
+    const double *dirs = nullptr;      // ndir tables of 6 x p on the device
 };
 size_t vecchia_lds_bytes(int m, bool pred);
 void launch_vecchia_blocks(int mode, bool pred, const VecchiaArgs &a, hipStream_t s);
@@ -658,6 +661,23 @@ inline int vecchia_rec_cols(int p) { return 13 * p + 2; }
 void launch_vecchia_site_rec(const double *soa, size_t stride, int n, double *rec, hipStream_t s);
 size_t vecchia_grad_lds_bytes(int m);
 void launch_vecchia_grad_blocks(int mode, const VecchiaArgs &a, hipStream_t s);
+// The information variant of the likelihood launch (no right-hand sides, logd null): per observation the record of
+// vecchia_fisher_cols(ndir, p) doubles -- the lower triangle of the block's Gram over the directions, entry a (a + 1) / 2 + b
+// for b <= a, then that of u u' with u = sum_rows s[row] X[site(row), .].  The dynamic LDS grows with m, ndir and the group
+// gd = vecchia_fisher_group(m, ndir) <= VECCHIA_FD, the largest that keeps it within VECCHIA_FISHER_LDS_MAX.
+constexpr int VECCHIA_FD = 16;         // directions per pair walk at most (a multiple of VECCHIA_G)
+constexpr size_t VECCHIA_FISHER_LDS_MAX = 160 * 1024;
+constexpr size_t VECCHIA_FISHER_CHUNK_BYTES = (size_t)16 << 20;   // a chunk's records: this many bytes, or one segment's
+inline int vecchia_fisher_cols(int ndir, int p) { return ndir * (ndir + 1) / 2 + p * (p + 1) / 2; }
+// observations per information launch: a multiple of VECCHIA_SUM_SEG, at most VECCHIA_GRAD_CHUNK
+inline int vecchia_fisher_chunk(int ndir, int p)
+{
+    const size_t segs = VECCHIA_FISHER_CHUNK_BYTES / ((size_t)vecchia_fisher_cols(ndir, p) * sizeof(double) * VECCHIA_SUM_SEG);
+    return VECCHIA_SUM_SEG * (int)(segs < 1 ? 1 : segs > VECCHIA_GRAD_CHUNK / VECCHIA_SUM_SEG ? VECCHIA_GRAD_CHUNK / VECCHIA_SUM_SEG : segs);
+}
+size_t vecchia_fisher_lds_bytes(int m, int ndir, int gd);
+int vecchia_fisher_group(int m, int ndir);
+void launch_vecchia_fisher_blocks(int mode, const VecchiaArgs &a, hipStream_t s);
 // launch_vecchia_sums in two steps for values that arrive in chunks: the first stage over the `rows` values of a chunk that
 // starts at segment seg0 of nseg (plain sums in every column), then the second stage over all nseg segments.  The totals are
 // the tree launch_vecchia_sums would form over all the values at once, whatever the chunk.

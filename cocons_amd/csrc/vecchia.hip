@@ -12,6 +12,9 @@
 //                           GRAD: the same gather, pair loop, factorisation and substitution, then the block's
 //                           share of the gradient: two backward solves, the pair partials contracted with the block's weights,
 //                           per-site sums in one fixed order, and one record per observation.
+//                           FISH: the same gather, pair loop, factorisation and backward solve for s, then the
+//                           block's share of the expected information: C_a s per direction from the pair partials, forward
+//                           solves against the factor that is still in LDS, and the Gram of the results as one record.
 //   vecchia_sum_kernel    : the totals over the per-observation terms, as a two-stage tree of fixed shape.
 //
 // Every sum of a block runs in ascending row order of the block, which the host makes the ascending order of the caller's
@@ -20,6 +23,7 @@
 //
 // Compile with -ffp-contract=off (see matern_device.hpp).
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include "kernels.h"
 #include "matern_device.hpp"
 #include "grad_pair.hpp"
@@ -113,6 +117,11 @@ __device__ __forceinline__ int tri_at(int r, int c) { return r * (r + 1) / 2 + c
 //   gs    2 GFAM x kb        the rows' site sums: the log-determinant's share per family, then the quadratic forms'.
 constexpr int VECCHIA_STG = 4 * GFAM * 64;              // a pass of 64 pairs: (ii side, jj side) x (two shares) x GFAM
 constexpr int VECCHIA_GX = GSITE_FIELDS + 2 + 2 * GFAM;
+// FISH (vecchia_fisher_lds_bytes) keeps the factor in tri and puts behind sp, sv, hv, for groups of gd <= VECCHIA_FD directions:
+//   wts   gd x GFAM x kb     the rows' site weights w_a[f][row] of the group's directions;
+//   stg   gd x 64            a pass of 64 pairs: the entry of C_a per direction (then, once, the p sums u of the mean block);
+//   gall  ndir x kb          g_a = L^-1 (C_a s) of every direction, what the Gram is formed of.
+constexpr int VECCHIA_FX = GSITE_FIELDS + 2;
 
 // pair t = r (r - 1) / 2 + c of the packed strict lower triangle, r > c
 __device__ __forceinline__ void tri_pair(int t, int &r, int &c)
@@ -123,25 +132,41 @@ __device__ __forceinline__ void tri_pair(int t, int &r, int &c)
     c = t - r * (r - 1) / 2;
 }
 
+// Forward substitution over the neighbours' rows for VECCHIA_G right-hand sides in registers, lane = row: lane r ends with
+// b_r - sum_{j < r} C(r, j) y_j, j ascending (the numerator of y_r: the steps from r on leave it alone).
+__device__ __forceinline__ void vecchia_forward(double (&b)[VECCHIA_G], const double *tri, int myrow, double piv_mine, int lane,
+                                                int k, int nrows)
+{
+    for (int j = 0; j < k; ++j) {
+        const double l = (lane > j && lane < nrows) ? tri[myrow + j] : 0.0;
+#pragma unroll
+        for (int g = 0; g < VECCHIA_G; ++g) {
+            const double yj = __shfl(lane == j ? b[g] / piv_mine : 0.0, j);
+            b[g] -= l * yj;
+        }
+    }
+}
+
 __device__ __forceinline__ double vecchia_wave_sum(double v)
 {
     for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
 
-template <int MODE, bool PRED, bool GRAD>
+template <int MODE, bool PRED, bool GRAD, bool FISH = false>
 __global__ void __launch_bounds__(64)
 vecchia_block_kernel(VecchiaArgs a)
 {
-    static_assert(!(PRED && GRAD), "the gradient is the likelihood launch's");
+    static_assert(!(PRED && (GRAD || FISH)) && !(GRAD && FISH), "the gradient and the information are the likelihood launch's");
+    constexpr bool DER = GRAD || FISH;             // the launches that gather the site derivatives and solve for s
     extern __shared__ double vecchia_lds[];
-    const int lane = threadIdx.x, row = (GRAD ? a.obs0 : 0) + blockIdx.x, kb = a.kb;
+    const int lane = threadIdx.x, row = (DER ? a.obs0 : 0) + blockIdx.x, kb = a.kb;
     double *par = vecchia_lds;
     double *par2 = par + (PRED ? LOCP_FIELDS * kb : 0);
     double *tri = par2 + LOCP_FIELDS * kb;
     const int ntri = kb * (kb + 1) / 2;
     double *gx = tri + ((GRAD && ntri < VECCHIA_STG) ? VECCHIA_STG : ntri);
-    int *nb = (int *)(gx + (GRAD ? VECCHIA_GX * kb : 0));
+    int *nb = (int *)(gx + (GRAD ? VECCHIA_GX * kb : FISH ? VECCHIA_FX * kb + a.gd * (GFAM * kb + 64) + a.ndir * kb : 0));
 
     // the row's neighbours: ascending, the free places (-1) behind them
     const int mine = lane < a.m ? a.nbr[(size_t)row * a.m + lane] : -1;
@@ -158,7 +183,7 @@ vecchia_block_kernel(VecchiaArgs a)
         else if (r < k) { par[f * kb + r] = a.aosK[at]; par2[f * kb + r] = a.aosC[at]; }
         else { par[f * kb + r] = 0.0; par2[f * kb + r] = a.aosP[at]; }
     }
-    if (GRAD)
+    if (DER)
         for (int e = lane; e < nrows * VECCHIA_GSITE_REC; e += 64) {
             const int r = e / VECCHIA_GSITE_REC, f = e % VECCHIA_GSITE_REC;
             gx[f * kb + r] = a.aosG[(size_t)nb[r] * VECCHIA_GSITE_REC + f];
@@ -209,14 +234,7 @@ vecchia_block_kernel(VecchiaArgs a)
 #pragma unroll
         for (int g = 0; g < VECCHIA_G; ++g)
             b[g] = (lane < nrows && c0 + g < a.nb && !(PRED && lane == k)) ? a.B[(size_t)site + (size_t)(c0 + g) * a.ldb] : 0.0;
-        for (int j = 0; j < k; ++j) {
-            const double l = (lane > j && lane < nrows) ? tri[myrow + j] : 0.0;
-#pragma unroll
-            for (int g = 0; g < VECCHIA_G; ++g) {
-                const double yj = __shfl(lane == j ? b[g] / piv_mine : 0.0, j);
-                b[g] -= l * yj;
-            }
-        }
+        vecchia_forward(b, tri, myrow, piv_mine, lane, k, nrows);
         if (lane == k) {
 #pragma unroll
             for (int g = 0; g < VECCHIA_G; ++g) {
@@ -244,12 +262,14 @@ vecchia_block_kernel(VecchiaArgs a)
             a.quad[row] = q;
         } else if (a.logd) a.logd[row] = log(piv_mine);
     }
-    if constexpr (GRAD) {
-        // The block's term f = nb 2 log d + sum_c y_c^2 has the derivative <W, dC> with W_log = nb s s' and
-        // W_quad = -(sum_c y_c^2) s s' - (h s' + s h'), s = L^-T e_last, h = L^-T v.
-        double *sp = gx, *sv = sp + GSITE_FIELDS * kb, *hv = sv + kb, *gs = hv + kb;
+    // The block's term f = nb 2 log d + sum_c y_c^2 has the derivative <W, dC> with W_log = nb s s' and
+    // W_quad = -(sum_c y_c^2) s s' - (h s' + s h'), s = L^-T e_last, h = L^-T v.  FISH has no right-hand
+    // sides (h = 0) and uses s alone.
+    [[maybe_unused]] double *sp = gx, *sv = sp + GSITE_FIELDS * kb, *hv = sv + kb;
+    [[maybe_unused]] double s_mine = 0.0, h_mine = 0.0;
+    if constexpr (DER) {
         // the two backward solves, one column of L' (a row of the packed factor) per step; lane j ends with component j
-        double rs = lane == k ? 1.0 : 0.0, rh = lane < k ? vacc : 0.0, s_mine = 0.0, h_mine = 0.0;
+        double rs = lane == k ? 1.0 : 0.0, rh = lane < k ? vacc : 0.0;
         for (int j = k; j >= 0; --j) {
             const double xs = __shfl(rs / piv_mine, j), xh = __shfl(rh / piv_mine, j);
             if (lane == j) { s_mine = xs; h_mine = xh; }
@@ -259,8 +279,11 @@ vecchia_block_kernel(VecchiaArgs a)
                 rh -= l * xh;
             }
         }
-        __syncthreads();                   // the factor is dead from here on: tri is the staging of the pair walk
+        __syncthreads();                   // GRAD: the factor is dead from here on, tri is the staging of the pair walk
         if (lane < nrows) { sv[lane] = s_mine; hv[lane] = h_mine; }
+    }
+    if constexpr (GRAD) {
+        double *gs = hv + kb;
         const double cn = (double)a.nb;
         auto w_log = [&](double sa, double sb) { return cn * (sa * sb); };
         auto w_quad = [&](double sa, double ha, double sb, double hb) { return 0.0 - ysq * (sa * sb) - (ha * sb + sa * hb); };
@@ -350,6 +373,118 @@ vecchia_block_kernel(VecchiaArgs a)
             a.rec[(size_t)(2 * GFAM * p + 1) * a.ldr + b] = glob_q;
         }
     }
+    if constexpr (FISH) {
+        // The block's share of the expected information: with q_a = C_a s and g_a = L^-1 q_a,
+        // sum_{j < k} g_a[j] g_b[j] + g_a[k] g_b[k] / 2.  Directions in groups of a.gd, so that the weights fit the LDS.
+        const int p = a.p, ndir = a.ndir, b = blockIdx.x;
+        double *wts = hv + kb, *stg = wts + a.gd * GFAM * kb, *gall = stg + a.gd * 64;
+        for (int d0 = 0; d0 < ndir; d0 += a.gd) {
+            const int gd = min(a.gd, ndir - d0);
+            __syncthreads();               // sv is written; the previous group's walk has left wts and stg
+            // the site weights of the group's directions: w_a[f][row] = c_f sum_k X[site(row), k] dirs[a][f, k], k ascending;
+            // scale: c = 2 over k >= 1 (k = 0 is the global range)
+            for (int e = lane; e < gd * GFAM * nrows; e += 64) {
+                const int rr = e % nrows, f = (e / nrows) % GFAM, d = e / (nrows * GFAM);
+                const double *v = a.dirs + ((size_t)(d0 + d) * GFAM + f) * p;
+                double w = 0.0;
+                for (int kx = (f == TH_SCALE_ ? 1 : 0); kx < p; ++kx) w += a.X[(size_t)nb[rr] + (size_t)kx * a.ldx] * v[kx];
+                wts[(d * GFAM + f) * kb + rr] = f == TH_SCALE_ ? 2.0 * w : w;
+            }
+            __syncthreads();
+            // q_a[row] in registers: the diagonal first, then the row's pairs pass by pass (the gradient walk's order)
+            double qa[VECCHIA_FD];
+#pragma unroll
+            for (int d = 0; d < VECCHIA_FD; ++d) qa[d] = 0.0;
+            if (lane < nrows) {
+                const double dsd = sp[3 * kb + lane], dng = par[12 * kb + lane];
+#pragma unroll
+                for (int d = 0; d < VECCHIA_FD; ++d)
+                    if (d < gd)
+                        qa[d] = (dsd * wts[(d * GFAM + TH_SD_) * kb + lane] + dng * wts[(d * GFAM + TH_NG_) * kb + lane]) * s_mine;
+            }
+            for (int t0 = 0; t0 < npairs; t0 += 64) {
+                const int t = t0 + lane;
+                double da[GFAM], db[GFAM], dg = 0.0;
+                int r = 0, c = 0;
+#pragma unroll
+                for (int f = 0; f < GFAM; ++f) { da[f] = 0.0; db[f] = 0.0; }
+                if (t < npairs) {
+                    tri_pair(t, r, c);
+                    pair_partials<MODE>(par, (size_t)kb, sp, (size_t)kb, a.gr, a.nu_fixed, a.smooth_free, c, r, da, db, dg);
+                }
+                for (int d = 0; d < gd; ++d) {
+                    double e = 0.0;
+                    if (t < npairs) {
+                        const double *w = wts + d * GFAM * kb;
+                        e = dg * a.dirs[((size_t)(d0 + d) * GFAM + TH_SCALE_) * p];
+#pragma unroll
+                        for (int f = 0; f < GFAM; ++f) {
+                            e += da[f] * w[f * kb + c];
+                            e += db[f] * w[f * kb + r];
+                        }
+                    }
+                    stg[d * 64 + lane] = e;
+                }
+                __syncthreads();
+                if (lane < nrows) {
+                    const int tend = min(t0 + 64, npairs), mine0 = lane * (lane - 1) / 2;
+                    for (int u = max(t0, mine0); u < min(tend, mine0 + lane); ++u) {
+                        const double so = sv[u - mine0];
+#pragma unroll
+                        for (int d = 0; d < VECCHIA_FD; ++d)
+                            if (d < gd) qa[d] += stg[d * 64 + (u - t0)] * so;
+                    }
+                    int r_lo, r_hi, c_;
+                    tri_pair(t0, r_lo, c_);
+                    tri_pair(tend - 1, r_hi, c_);
+                    for (int rr = max(r_lo, lane + 1); rr <= r_hi; ++rr) {
+                        const int u = rr * (rr - 1) / 2 + lane;
+                        if (u < t0 || u >= tend) continue;
+                        const double so = sv[rr];
+#pragma unroll
+                        for (int d = 0; d < VECCHIA_FD; ++d)
+                            if (d < gd) qa[d] += stg[d * 64 + (u - t0)] * so;
+                    }
+                }
+                __syncthreads();
+            }
+            // g_a = L^-1 q_a: the likelihood's substitution with q as the right-hand sides; every lane keeps its component
+#pragma unroll
+            for (int c0 = 0; c0 < VECCHIA_FD; c0 += VECCHIA_G) {
+                if (c0 >= gd) break;
+                double bb[VECCHIA_G];
+#pragma unroll
+                for (int g = 0; g < VECCHIA_G; ++g) bb[g] = qa[c0 + g];
+                vecchia_forward(bb, tri, myrow, piv_mine, lane, k, nrows);
+#pragma unroll
+                for (int g = 0; g < VECCHIA_G; ++g)
+                    if (c0 + g < gd && lane < nrows) gall[(d0 + c0 + g) * kb + lane] = bb[g] / piv_mine;
+            }
+        }
+        // u = sum_rows s[row] X[site(row), .], the rows ascending (the mean gradient's sum)
+        if (lane < p) {
+            double s = 0.0;
+            for (int rr = 0; rr < nrows; ++rr) s += sv[rr] * a.X[(size_t)nb[rr] + (size_t)lane * a.ldx];
+            stg[lane] = s;
+        }
+        __syncthreads();
+        // the record: the lower triangle of the Gram, entry o = a (a + 1) / 2 + b, then that of u u'
+        const int ng = ndir * (ndir + 1) / 2;
+        for (int o = lane; o < ng; o += 64) {
+            int ra, cb;
+            tri_pair(o, ra, cb);           // (the strict triangle's numbering of (a + 1, b))
+            const double *ga = gall + (ra - 1) * kb, *gb = gall + cb * kb;
+            double s = 0.0;
+            for (int j = 0; j < k; ++j) s += ga[j] * gb[j];
+            s += 0.5 * (ga[k] * gb[k]);
+            a.rec[(size_t)o * a.ldr + b] = s;
+        }
+        for (int o = lane; o < p * (p + 1) / 2; o += 64) {
+            int ra, cb;
+            tri_pair(o, ra, cb);
+            a.rec[(size_t)(ng + o) * a.ldr + b] = stg[ra - 1] * stg[cb];
+        }
+    }
 }
 
 size_t vecchia_lds_bytes(int m, bool pred)
@@ -387,6 +522,40 @@ void launch_vecchia_grad_blocks(int mode, const VecchiaArgs &a, hipStream_t s)
     case MODE_THREEHALF: hipLaunchKernelGGL((vecchia_block_kernel<MODE_THREEHALF, false, true>), grid, block, shm, s, a); break;
     case MODE_FIVEHALF: hipLaunchKernelGGL((vecchia_block_kernel<MODE_FIVEHALF, false, true>), grid, block, shm, s, a); break;
     default: hipLaunchKernelGGL((vecchia_block_kernel<MODE_GEOM, false, true>), grid, block, shm, s, a); break;
+    }
+}
+
+size_t vecchia_fisher_lds_bytes(int m, int ndir, int gd)
+{
+    const size_t kb = (size_t)m + 1;
+    return (LOCP_FIELDS * kb + kb * (kb + 1) / 2 + VECCHIA_FX * kb + (size_t)gd * (GFAM * kb + 64) + (size_t)ndir * kb) *
+               sizeof(double) + kb * sizeof(int);
+}
+
+int vecchia_fisher_group(int m, int ndir)
+{
+    int gd = VECCHIA_FD;
+    while (gd > VECCHIA_G && vecchia_fisher_lds_bytes(m, ndir, gd) > VECCHIA_FISHER_LDS_MAX) gd /= 2;
+    return std::min(gd, std::max(ndir, 1));
+}
+
+template <int MODE> static void vecchia_fisher_launch(const VecchiaArgs &a, size_t shm, hipStream_t s)
+{
+    static std::atomic<unsigned long long> attr_done{0};
+    if (shm > 64 * 1024)
+        set_dynamic_lds_once((const void *)vecchia_block_kernel<MODE, false, false, true>, VECCHIA_FISHER_LDS_MAX, attr_done);
+    hipLaunchKernelGGL((vecchia_block_kernel<MODE, false, false, true>), dim3((unsigned)a.rows), dim3(64), shm, s, a);
+}
+
+void launch_vecchia_fisher_blocks(int mode, const VecchiaArgs &a, hipStream_t s)
+{
+    if (a.rows <= 0) return;
+    const size_t shm = vecchia_fisher_lds_bytes(a.m, a.ndir, a.gd);
+    switch (mode) {
+    case MODE_HALF: vecchia_fisher_launch<MODE_HALF>(a, shm, s); break;
+    case MODE_THREEHALF: vecchia_fisher_launch<MODE_THREEHALF>(a, shm, s); break;
+    case MODE_FIVEHALF: vecchia_fisher_launch<MODE_FIVEHALF>(a, shm, s); break;
+    default: vecchia_fisher_launch<MODE_GEOM>(a, shm, s); break;
     }
 }
 

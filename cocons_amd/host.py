@@ -1645,6 +1645,19 @@ class CoconsVecchiaFit:
         _lib.check(st, "cocons_neg2loglik_grad_vecchia")
         return val.value, parts, gt, gq, gm
 
+    def fisher_core(self, theta_list, dirs):
+        """Expected information of the Vecchia likelihood at `theta_list` (cocons_fisher_vecchia), `dirs` as for
+        `CoconsFit.fisher_core` (ndir x 6 x p or ndir x 6p).  Returns (info ndir x ndir, info_mean p x p): the sums over the
+        n blocks of the block's information minus that of its neighbours alone, and r (U X)'(U X) with U the whitening.
+        Both are Gram matrices, symmetric to the bit; with every predecessor in the table they are the dense ones."""
+        T = theta_table(theta_list)
+        D = np.ascontiguousarray(np.asarray(dirs, dtype=np.float64).reshape(-1, 6 * self.p))
+        nd = D.shape[0]
+        info = np.zeros((nd, nd))
+        info_mean = np.zeros((self.p, self.p))
+        _lib.check(self._L.cocons_fisher_vecchia(self._h, _p(T), nd, _p(D), _p(info), _p(info_mean)), "cocons_fisher_vecchia")
+        return info, info_mean
+
     def whiten_core(self, theta_list, B):
         """(U B, log d) for the columns of B (n x c, the caller's order): U'U is the approximation's Sigma^-1."""
         T = theta_table(theta_list)
@@ -1771,6 +1784,30 @@ def GetNeg2loglikelihoodVecchia_grad(theta, par_pos, nn, locs, x_covariates, smo
         for t, k in enumerate(COV_ASPECTS):
             g[k] = g[k] + gt[t]
         return val + getPen(N, lam, tl, smooth_limits), getModelLists_grad(g, par_pos)
+    finally:
+        if own:
+            f.close()
+
+
+def getFisher_vecchia(par, par_pos, locs, x_covariates, smooth_limits, z, n, nn, fit=None):
+    """The P x P expected information of the Vecchia fit for the neighbour table `nn` in the optimiser's coordinates, rows
+    and columns in `par`'s order, from ONE pass over the n blocks (cocons_fisher_vecchia): the expectation under the model of
+    the Hessian of half of `GetNeg2loglikelihoodVecchia` without its penalty -- what GpGp returns as `info`.  It goes
+    through `fisher_jacobian` as `getFisher_dense` does: the covariance block from the Jacobian's rows as directions, then
+    J_m info_mean J_m' for the mean; the block between them is 0.  A Gram matrix, so solve() of it gives non-negative
+    variances.  It is not the observed Hessian and not the Godambe (sandwich) information of the composite likelihood.
+    A failing block raises CholeskyError."""
+    par = np.asarray(par, dtype=np.float64).ravel()
+    tl = getModelLists(par, par_pos, "diff")
+    Jt, Jm = fisher_jacobian(par, par_pos)
+    f, own = _with_vecchia_fit(fit, locs, x_covariates, z, smooth_limits, nn)
+    try:
+        cov = np.flatnonzero(np.any(Jt != 0, axis=1))       # (a pure mean parameter costs no direction on the device)
+        sub, info_mean = f.fisher_core(tl, Jt[cov] if cov.size else Jt[:1])
+        info = Jm @ info_mean @ Jm.T
+        if cov.size:
+            info[np.ix_(cov, cov)] += sub
+        return info
     finally:
         if own:
             f.close()

@@ -514,6 +514,31 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
   list(value = res[[1]], table = res[[2]], quad = res[[3]], mean = res[[4]])
 }
 
+# expected information of the Vecchia fit over theta (cocons_fisher_vecchia; DESIGN.md 4t), P x P in theta's order, from one
+# pass over the n blocks: the expectation at the model of the Hessian of half of the Vecchia -2 log-likelihood, without the
+# penalty -- what GpGp calls info.  Not the observed Hessian, not the Godambe (sandwich) information.  The Jacobian as in
+# .cocons.hip.fisher; NULL after a failing block under safe.
+.cocons.hip.vecchia.fisher <- function(fit, theta, par.pos, safe = TRUE) {
+  aspects <- c("std.dev", "scale", "aniso", "tilt", "smooth", "nugget")
+  base <- cocons::getModelLists(theta = theta, par.pos = par.pos, type = "diff")
+  p <- length(base$mean)
+  flat <- function(tl) c(tl$mean, unlist(tl[aspects], use.names = FALSE))
+  J <- vapply(seq_along(theta), function(a) {
+    e <- theta
+    e[a] <- e[a] + 1
+    flat(cocons::getModelLists(theta = e, par.pos = par.pos, type = "diff")) - flat(base)
+  }, numeric(7 * p))
+  Jm <- J[seq_len(p), , drop = FALSE]
+  Jt <- J[-seq_len(p), , drop = FALSE]
+  cov <- which(colSums(Jt != 0) > 0)
+  res <- .cocons.hip.result(.Call(`_cocons_hip_vecchia_fisher`, fit, base[-1], Jt[, if (length(cov)) cov else 1L, drop = FALSE]),
+                            safe)
+  if (is.null(res)) return(NULL)
+  info <- crossprod(Jm, res[[2]] %*% Jm)
+  if (length(cov)) info[cov, cov] <- info[cov, cov] + res[[1]]
+  info
+}
+
 # local kriging: cbind(stochastic, quadform) for the new locations, each from the observations its row of nn_pred names
 # (1-based, 0 = none) -- the two columns cocoPredict's dense branch takes from its solve (R/predict.R:165-173)
 .cocons.hip.vecchia.predict <- function(fit, theta_list, newlocs, X_pred, nn_pred, z_col = 1L) {

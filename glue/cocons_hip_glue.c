@@ -967,6 +967,31 @@ SEXP _cocons_hip_vecchia_neg2loglik_grad(SEXP fitp, SEXP theta, SEXP mean)
     return out;
 }
 
+/* expected information of a Vecchia fit (cocons_fisher_vecchia): dirs as for _cocons_hip_fisher; list(status, list(info
+ * ndir x ndir, info_mean p x p)); a failing block is a status */
+SEXP _cocons_hip_vecchia_fisher(SEXP fitp, SEXP theta, SEXP dirs)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp);
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    if (!Rf_isReal(dirs) || !Rf_isMatrix(dirs) || Rf_nrows(dirs) != 6 * p)
+        Rf_error("dirs must be a double matrix with %d rows (one direction per column)", 6 * p);
+    const int nd = Rf_ncols(dirs);
+    SEXP info = PROTECT(Rf_allocMatrix(REALSXP, nd, nd));
+    SEXP im = PROTECT(Rf_allocMatrix(REALSXP, p, p));
+    for (R_xlen_t e = 0; e < XLENGTH(info); ++e) REAL(info)[e] = 0.0;
+    for (R_xlen_t e = 0; e < XLENGTH(im); ++e) REAL(im)[e] = 0.0;
+    int rc = cocons_fisher_vecchia(f, T, nd, REAL(dirs), REAL(info), REAL(im));     /* (both outputs are symmetric) */
+    hip_check(rc, "expected information of the Vecchia fit");
+    SEXP res = PROTECT(Rf_allocVector(VECSXP, 2));
+    SET_VECTOR_ELT(res, 0, info);
+    SET_VECTOR_ELT(res, 1, im);
+    SEXP out = status_value(rc, res);
+    UNPROTECT(3);
+    return out;
+}
+
 /* local kriging on a Vecchia handle (cocons_vecchia_predict): list(status, cbind(stochastic, quadform)); theta is the WHOLE
  * theta_list (its `mean` element is read by name like the others); nn_pred is the mp x m_pred matrix of 1-based indices
  * into the observations, 0 = none; z_col 1-based */
@@ -1159,6 +1184,7 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_vecchia_neg2loglik", (DL_FUNC)&_cocons_hip_vecchia_neg2loglik, 3},
     {"_cocons_hip_vecchia_neg2loglik_grad", (DL_FUNC)&_cocons_hip_vecchia_neg2loglik_grad, 3},
     {"_cocons_hip_vecchia_predict", (DL_FUNC)&_cocons_hip_vecchia_predict, 6},
+    {"_cocons_hip_vecchia_fisher", (DL_FUNC)&_cocons_hip_vecchia_fisher, 3},
     {"_cocons_hip_fit_close", (DL_FUNC)&_cocons_hip_fit_close, 1},
     {"_cocons_hip_neg2loglik_parts", (DL_FUNC)&_cocons_hip_neg2loglik_parts, 3},
     {"_cocons_hip_neg2loglik", (DL_FUNC)&_cocons_hip_neg2loglik, 3},

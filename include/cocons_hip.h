@@ -322,6 +322,26 @@ int cocons_vecchia_whiten(cocons_fit *fit, const double *theta, int c, const dou
 int cocons_neg2loglik_grad_vecchia(cocons_fit *fit, const double *theta, const double *mean, int c, const double *B,
                                    double *sum_logliks, double *parts,
                                    double *grad_theta, double *grad_quad, double *grad_mean);
+/* Expected information of the Vecchia likelihood over ndir directions of the table, dirs as for
+ * cocons_fisher_dense: ndir tables of 6 x p, ndir in 1 .. 7 * COCONS_P_MAX, under the dense conventions (scale k = 0 is the
+ * global range, scale k >= 1 carries the factor 2, a coincident pair takes the earlier row's diagonal partials, a pair with
+ * u >= 706 contributes 0).  For observation i with its block C = L L' (neighbours, then i; l the last row), C_a the same
+ * block of Sigma_a = sum_tk dirs[a][t p + k] dSigma / dtheta[t p + k], s = L^-T e_l and g_a = L^-1 (C_a s):
+ *   info[a * ndir + b] = r sum_i ( sum_{j < l} g_a[j] g_b[j] + g_a[l] g_b[l] / 2 ),
+ *   info_mean[k * p + l] = r sum_i u_i[k] u_i[l],  u_i = sum_rows s[row] X[site(row), .]        (p x p, may be NULL).
+ * The block's term is (1 / 2) [ tr(C^-1 C_a C^-1 C_b) - tr(C_NN^-1 C_a,NN C_NN^-1 C_b,NN) ], the information of the block less
+ * that of its neighbours alone: the expectation under Sigma(theta) of the Hessian of half of cocons_neg2loglik_vecchia,
+ * without a penalty.  It is a Gram matrix -- symmetric to the bit (mirrored from its lower triangle) and positive
+ * semi-definite --, the block between mean and covariance parameters is 0, and with every predecessor in the table it is
+ * cocons_fisher_dense's.  It is NOT the observed Hessian, and NOT the Godambe (sandwich) information of the composite
+ * likelihood: only the sensitivity matrix is formed.
+ * Every sum has a fixed order: repeated calls agree bit for bit, and nothing depends on the other rows of n or on the chunks
+ * the rows run in.  The first call allocates O(n) doubles plus one chunk of records (at most 16 MiB, or 4096 records), kept
+ * on the handle and counted by cocons_vecchia_info; a device that cannot hold them gives < 0 with the bytes in the message.
+ * Refused (-1) before any device work: null fit, theta, dirs or info, ndir out of range, non-finite dirs, any other kind of
+ * handle.  A failing block returns the smallest 1-based row; outputs are written on 0 only.                              */
+int cocons_fisher_vecchia(cocons_fit *fit, const double *theta, int ndir, const double *dirs,
+                          double *info, double *info_mean);
 /* Local kriging at mp >= 0 new locations (locs_pred mp x 2, X_pred mp x p, column-major): nn_pred is mp x m_pred
  * column-major, 1-based indices into the observations, 0 = none, m_pred in 1 .. 63.  For row i with K its neighbours' block
  * (as above) and c the cross-covariance to them by cocons_cov_rns_pred's rule (an exact coordinate match gives the
