@@ -65,6 +65,9 @@ SIGNATURES = {
     "cocons_neg2loglik_grad_vecchia": (c_int, [c_vp, c_dp, c_dp, c_int, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "cocons_vecchia_predict": (c_int, [c_vp, c_dp, c_dp, c_int, c_int, c_dp, c_dp, c_int, ctypes.POINTER(c_int), c_dp, c_dp]),
     "cocons_vecchia_info": (c_int, [c_vp, ctypes.POINTER(ctypes.c_longlong)]),
+    "cocons_vecchia_neighbours": (c_int, [c_int, c_dp, c_int, c_dp, c_int, c_int, ctypes.POINTER(c_int)]),
+    "cocons_fit_create_vecchia_knn": (c_vp, [c_int, c_int, c_int, c_dp, c_dp, c_dp, c_dp, c_int, c_int]),
+    "cocons_vecchia_predict_knn": (c_int, [c_vp, c_dp, c_dp, c_int, c_int, c_dp, c_dp, c_int, c_dp, c_dp]),
     "cocons_fit_destroy": (None, [c_vp]),
     "cocons_neg2loglik_dense": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp]),
     "cocons_neg2loglik_grad_dense": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
@@ -135,6 +138,9 @@ DIAG_SIGNATURES = {
     "cocons_debug_fit_memory": (c_int, [c_vp, ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_debug_rhs_layout": (c_int, [c_vp, c_int, ctypes.POINTER(c_int)]),
     "cocons_debug_pattern_cells": (c_int, [c_int, c_dp, ctypes.c_double, c_int, c_dp, c_dp, ctypes.POINTER(c_int)]),
+    "cocons_debug_knn_plan": (c_int, [c_int, c_dp, c_int, c_int, c_dp, c_int, ctypes.POINTER(c_int), c_dp, ctypes.POINTER(c_int),
+                                      c_dp]),
+    "cocons_debug_knn_phases": (c_int, [c_int, c_dp, c_int, c_int, c_dp]),
     "cocons_debug_taper_selinv": (c_int, [c_vp, c_dp, c_dp, ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_debug_tune": (c_int, [ctypes.c_char_p, c_int]),
     "cocons_debug_dag_replay": (c_int, [c_vp, c_dp, c_dp, c_int, c_dp]),

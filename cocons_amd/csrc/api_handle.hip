@@ -342,21 +342,33 @@ int pattern_check_finite(const char *who, const char *what, size_t npts, const d
     return 0;
 }
 
+int pattern_grid_alloc(const char *who, PatternGridBufs &G, size_t pts, size_t cells)
+{
+    HIPCHK_AT(who, G.cstart.alloc(cells + 1));
+    HIPCHK_AT(who, G.cursor.alloc(cells + 1));
+    HIPCHK_AT(who, G.sidx.alloc(pts));
+    HIPCHK_AT(who, G.sxy.alloc(2 * pts));
+    G.bytes = (long long)((2 * (cells + 1) + pts) * sizeof(int) + 2 * pts * sizeof(double));
+    return 0;
+}
+
+int pattern_grid_bin(const char *who, PatternGridBufs &G, const PatternGrid &g, int cnt, const double *dx, const double *dy,
+                     hipStream_t s)
+{
+    G.t.g = g;
+    G.t.n = cnt; G.t.x = dx; G.t.y = dy;
+    G.t.cstart = G.cstart; G.t.sidx = G.sidx; G.t.sx = G.sxy; G.t.sy = G.sxy + cnt;
+    HIPCHK_AT(who, launch_pattern_bin(G.t, G.cursor, s));
+    return 0;
+}
+
 int pattern_grid_build(const char *who, PatternGridBufs &G, int n, const double *hx, const double *hy, const double *dx,
                        const double *dy, double delta, hipStream_t s)
 {
-    G.t.g = pattern_grid_make(n, hx, hy, delta);
-    G.t.n = n; G.t.x = dx; G.t.y = dy;
+    const PatternGrid g = pattern_grid_make(n, hx, hy, delta);
     G.delta = delta;
-    const size_t ncell = pattern_cells(G.t.g);
-    HIPCHK_AT(who, G.cstart.alloc(ncell + 1));
-    HIPCHK_AT(who, G.cursor.alloc(ncell + 1));
-    HIPCHK_AT(who, G.sidx.alloc((size_t)n));
-    HIPCHK_AT(who, G.sxy.alloc((size_t)2 * n));
-    G.t.cstart = G.cstart; G.t.sidx = G.sidx; G.t.sx = G.sxy; G.t.sy = G.sxy + n;
-    G.bytes = (long long)((2 * (ncell + 1) + (size_t)n) * sizeof(int) + (size_t)2 * n * sizeof(double));
-    HIPCHK_AT(who, launch_pattern_bin(G.t, G.cursor, s));
-    return 0;
+    if (int rc = pattern_grid_alloc(who, G, (size_t)n, pattern_cells(g))) return rc;
+    return pattern_grid_bin(who, G, g, n, dx, dy, s);
 }
 
 // cocons_taper_pattern under the name of the entry that asks (who)

@@ -35,21 +35,24 @@ static int vecchia_row(const int *nn, size_t rows, int m, size_t i, int limit, i
 
 static const char *const vecchia_offence[] = {"", "names an index outside its range", "names an index twice"};
 
-extern "C" cocons_fit *cocons_fit_create_vecchia(int n, int p, int r, const double *locs, const double *X, const double *z,
-                                                 const double *smooth_limits, int device, int m, const int *nn)
+cocons_fit *vecchia_create_impl(const char *who, int n, int p, int r, const double *locs, const double *X, const double *z,
+                                const double *smooth_limits, int device, int m, const int *nn, bool search)
 {
-    const char *who = "cocons_fit_create_vecchia";
-    if (!locs || !X || !z || !smooth_limits || !nn) { fail(-1, "%s: null argument", who); return nullptr; }
+    if (!locs || !X || !z || !smooth_limits || (!search && !nn)) { fail(-1, "%s: null argument", who); return nullptr; }
     if (n < 1) { fail(-1, "%s: n = %d (at least one observation expected)", who, n); return nullptr; }
     if (p < 1 || p > COCONS_P_MAX || r < 1) { fail(-1, "%s: bad argument (p = %d, r = %d)", who, p, r); return nullptr; }
     if (m < 1 || m > VECCHIA_M_MAX) { fail(-1, "%s: m = %d is outside 1 .. %d", who, m, VECCHIA_M_MAX); return nullptr; }
     if (pattern_check_finite(who, "locs", (size_t)n, locs)) return nullptr;
-    std::vector<int> tab((size_t)n * m);
-    for (int i = 0; i < n; ++i)
-        if (int bad = vecchia_row(nn, (size_t)n, m, (size_t)i, i, &tab[(size_t)i * m])) {
-            fail(-1, "%s: row %d of nn %s (1-based indices in 1 .. row - 1, 0 = none)", who, i + 1, vecchia_offence[bad]);
-            return nullptr;
-        }
+    // a table that comes in is put into the device layout here, before any device work; search: there is none
+    std::vector<int> tab;
+    if (!search) {
+        tab.resize((size_t)n * m);
+        for (int i = 0; i < n; ++i)
+            if (int bad = vecchia_row(nn, (size_t)n, m, (size_t)i, i, &tab[(size_t)i * m])) {
+                fail(-1, "%s: row %d of nn %s (1-based indices in 1 .. row - 1, 0 = none)", who, i + 1, vecchia_offence[bad]);
+                return nullptr;
+            }
+    }
     // the caller's order is the Vecchia order and the handle keeps it (no Morton sort, no padding in front): neighbour
     // indices and outputs need no mapping, and COCONS_SPATIAL_SORT cannot reach a bit of any output
     cocons_fit *f = fit_create_impl(n, p, r, 0, locs, X, z, nullptr, smooth_limits, device, false, true, false, true);
@@ -64,15 +67,31 @@ extern "C" cocons_fit *cocons_fit_create_vecchia(int n, int p, int r, const doub
     f->vecchia.reset(new VecchiaState());
     VecchiaState *V = f->vecchia.get();
     V->m = m;
-    if (hipError_t e = V->nbr.alloc(tab.size())) return drop(e);
+    if (hipError_t e = V->nbr.alloc((size_t)n * m)) return drop(e);
     if (hipError_t e = V->aos.alloc((size_t)VECCHIA_REC * n)) return drop(e);
     if (hipError_t e = V->B.alloc((size_t)n * r)) return drop(e);
     if (hipError_t e = V->W.alloc((size_t)n * (1 + r))) return drop(e);
     if (hipError_t e = V->part.alloc(vecchia_sum_scratch_doubles(n, 1 + r))) return drop(e);
-    if (hipError_t e = hipMemcpyAsync(V->nbr, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, f->stream)) return drop(e);
-    if (hipError_t e = hipStreamSynchronize(f->stream)) return drop(e);
+    if (search) {
+        // the table straight into V->nbr: it never exists on the host
+        if (knn_self_search(who, n, locs, locs + n, f->dlocs, f->dlocs + n, m, nullptr, V->nbr, f->stream)) {
+            (void)hipGetLastError();
+            f->op_mu.unlock();
+            cocons_fit_destroy(f);
+            return nullptr;
+        }
+    } else {
+        if (hipError_t e = hipMemcpyAsync(V->nbr, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, f->stream)) return drop(e);
+        if (hipError_t e = hipStreamSynchronize(f->stream)) return drop(e);
+    }
     f->op_mu.unlock();
     return f;
+}
+
+extern "C" cocons_fit *cocons_fit_create_vecchia(int n, int p, int r, const double *locs, const double *X, const double *z,
+                                                 const double *smooth_limits, int device, int m, const int *nn)
+{
+    return vecchia_create_impl("cocons_fit_create_vecchia", n, p, r, locs, X, z, smooth_limits, device, m, nn, false);
 }
 
 // out4 = {n, m, device bytes the handle holds, rows per chunk of cocons_vecchia_predict}
@@ -322,14 +341,15 @@ extern "C" int cocons_vecchia_whiten(cocons_fit *f, const double *theta, int c, 
     return 0;
 }
 
-extern "C" int cocons_vecchia_predict(cocons_fit *f, const double *theta, const double *mean, int z_col, int mp,
-                                      const double *locs_pred, const double *X_pred, int m_pred, const int *nn_pred,
-                                      double *stochastic, double *quadform)
+// cocons_vecchia_predict, or with search (cocons_vecchia_predict_knn) the same with every chunk's table found on
+// the device: the neighbours land ascending in the chunk's table buffer, no table is uploaded and none is sorted on the host
+int vecchia_predict_impl(const char *who, cocons_fit *f, const double *theta, const double *mean, int z_col, int mp,
+                         const double *locs_pred, const double *X_pred, int m_pred, const int *nn_pred, bool search,
+                         double *stochastic, double *quadform)
 {
-    const char *who = "cocons_vecchia_predict";
     if (!f) return fail(-1, "%s: null fit handle", who);
     if (!theta || !mean) return fail(-1, "%s: null argument", who);
-    if (mp < 0 || (mp > 0 && (!locs_pred || !X_pred || !nn_pred || !stochastic || !quadform)))
+    if (mp < 0 || (mp > 0 && (!locs_pred || !X_pred || (!search && !nn_pred) || !stochastic || !quadform)))
         return fail(-1, "%s: bad argument (mp < 0 or a null pointer)", who);
     if (m_pred < 1 || m_pred > VECCHIA_M_MAX) return fail(-1, "%s: m_pred = %d is outside 1 .. %d", who, m_pred, VECCHIA_M_MAX);
     if (mp > 0)
@@ -339,10 +359,13 @@ extern "C" int cocons_vecchia_predict(cocons_fit *f, const double *theta, const 
     if (z_col < 0 || z_col >= f->r) return fail(-1, "%s: z_col = %d is outside 0 .. %d", who, z_col, f->r - 1);
     VecchiaState *V = f->vecchia.get();
     const int n = f->n, p = f->p, rows = VECCHIA_PRED_ROWS;
-    std::vector<int> tab((size_t)mp * m_pred);
-    for (int i = 0; i < mp; ++i)
-        if (int bad = vecchia_row(nn_pred, (size_t)mp, m_pred, (size_t)i, n, &tab[(size_t)i * m_pred]))
-            return fail(-1, "%s: row %d of nn_pred %s (1-based indices in 1 .. n, 0 = none)", who, i + 1, vecchia_offence[bad]);
+    std::vector<int> tab;
+    if (!search) {
+        tab.resize((size_t)mp * m_pred);
+        for (int i = 0; i < mp; ++i)
+            if (int bad = vecchia_row(nn_pred, (size_t)mp, m_pred, (size_t)i, n, &tab[(size_t)i * m_pred]))
+                return fail(-1, "%s: row %d of nn_pred %s (1-based indices in 1 .. n, 0 = none)", who, i + 1, vecchia_offence[bad]);
+    }
     if (mp == 0) return 0;
     double hmean[COCONS_P_MAX];
     for (int i = 0; i < p; ++i) hmean[i] = canon_nan(mean[i]);
@@ -358,6 +381,15 @@ extern "C" int cocons_vecchia_predict(cocons_fit *f, const double *theta, const 
     HIPCHK_AT(who, dnb.alloc((size_t)rows * m_pred));
     StreamDrain s{f->stream, false};
     if (int rc = reset_info(f)) return rc;
+    if (search && !V->knn) {
+        // the grid over the observations: the handle's from here on (counted by cocons_vecchia_info, freed with it)
+        V->knn.reset(new PatternGridBufs());
+        if (int rc = knn_grid_build(who, *V->knn, n, f->h_locs.data(), f->h_locs.data() + n, f->dlocs, f->dlocs + n, s)) {
+            (void)hipStreamSynchronize(s);
+            V->knn.reset();
+            return rc;
+        }
+    }
     // K from cov_rns's records; c from the prediction branch's (always logistic + sqrt, see cocons_predict_dense): a second
     // set of records only where the two differ (a fixed smoothness)
     const ModeSel ms2 = select_mode(theta, p, f->smooth_limits, 2);
@@ -378,7 +410,13 @@ extern "C" int cocons_vecchia_predict(cocons_fit *f, const double *theta, const 
         for (int j = 0; j < 2; ++j) memcpy(&hl[(size_t)j * mc], locs_pred + b + (size_t)j * mp, (size_t)mc * sizeof(double));
         HIPCHK_AT(who, upload_canon(dXp, hX.data(), (size_t)mc * p, s));
         HIPCHK_AT(who, upload_canon(dlp, hl.data(), (size_t)mc * 2, s));
-        HIPCHK_AT(who, hipMemcpyAsync(dnb, &tab[(size_t)b * m_pred], (size_t)mc * m_pred * sizeof(int), hipMemcpyHostToDevice, s));
+        if (search) {
+            KnnArgs k;
+            k.t = V->knn->t; k.qx = dlp; k.qy = dlp + mc; k.m = m_pred; k.tab = dnb;
+            HIPCHK_AT(who, launch_knn_query(k, mc, s));
+        } else {
+            HIPCHK_AT(who, hipMemcpyAsync(dnb, &tab[(size_t)b * m_pred], (size_t)mc * m_pred * sizeof(int), hipMemcpyHostToDevice, s));
+        }
         launch_loc_params(loc_args(mc, p, dXp, dlp, dsoa, rows, tv, ms2.smooth_kind, f->smooth_limits), s);
         launch_vecchia_aos(dsoa, rows, mc, drec, s);
         VecchiaArgs a;
@@ -398,4 +436,12 @@ extern "C" int cocons_vecchia_predict(cocons_fit *f, const double *theta, const 
     memcpy(stochastic, hst.data(), (size_t)mp * sizeof(double));
     memcpy(quadform, hqd.data(), (size_t)mp * sizeof(double));
     return 0;
+}
+
+extern "C" int cocons_vecchia_predict(cocons_fit *f, const double *theta, const double *mean, int z_col, int mp,
+                                      const double *locs_pred, const double *X_pred, int m_pred, const int *nn_pred,
+                                      double *stochastic, double *quadform)
+{
+    return vecchia_predict_impl("cocons_vecchia_predict", f, theta, mean, z_col, mp, locs_pred, X_pred, m_pred, nn_pred, false,
+                                stochastic, quadform);
 }

@@ -276,9 +276,12 @@ struct VecchiaState {
     DevBuf<double> frec;          // vecchia_fisher_chunk x vecchia_fisher_cols: the per-observation records of one chunk
     DevBuf<double> fpart;         // their first-stage sums, all segments of n
     DevBuf<double> fout;          // the totals: vecchia_fisher_cols
+    // cocons_vecchia_predict_knn, made by its first call: the grid over the observations
+    std::unique_ptr<PatternGridBufs> knn;
     long long bytes() const
     {
-        return (long long)(nbr.count() * sizeof(int) +
+        return (knn ? knn->bytes : 0) +
+               (long long)(nbr.count() * sizeof(int) +
                            (aos.count() + aos2.count() + B.count() + W.count() + part.count() + gsite.count() + gaos.count() +
                             grec.count() + gpart.count() + gout.count() + fdirs.count() + frec.count() + fpart.count() +
                             fout.count()) * sizeof(double));
@@ -687,6 +690,28 @@ int pattern_check_delta(const char *who, double delta, int kind);
 int pattern_check_finite(const char *who, const char *what, size_t npts, const double *pts);
 int pattern_grid_build(const char *who, PatternGridBufs &G, int n, const double *hx, const double *hy, const double *dx,
                        const double *dy, double delta, hipStream_t s);
+// ... its two halves, for grids whose geometry is made elsewhere (the neighbour search's levels): buffers for grids of up to
+// pts points and cells cells, and the first cnt points (dx, dy) binned on the grid g into them on s (not waited for)
+int pattern_grid_alloc(const char *who, PatternGridBufs &G, size_t pts, size_t cells);
+int pattern_grid_bin(const char *who, PatternGridBufs &G, const PatternGrid &g, int cnt, const double *dx, const double *dy,
+                     hipStream_t s);
+// ... the Vecchia neighbour search (api_knn.hip): the grid over n points for plain kNN, binned on s (not waited
+// for), and the ordered self search of n points on s (drained) into d_nn (n x m column-major, 1-based, nearest first; may be
+// null) and d_tab (the layout of VecchiaState::nbr; may be null); phases (may be null: no events are made): the device time
+// of the binning and of the query launches, by events on s.  And what api_vecchia.hip offers it: the handle and the
+// prediction under the name of the entry that asks, search = true: no table comes in, the neighbours are found on the device
+struct KnnPhases {
+    double build_ms = 0.0, query_ms = 0.0;
+};
+int knn_grid_build(const char *who, PatternGridBufs &G, int n, const double *hx, const double *hy, const double *dx,
+                   const double *dy, hipStream_t s);
+int knn_self_search(const char *who, int n, const double *hx, const double *hy, const double *dx, const double *dy, int m,
+                    int *d_nn, int *d_tab, hipStream_t s, KnnPhases *phases = nullptr);
+cocons_fit *vecchia_create_impl(const char *who, int n, int p, int r, const double *locs, const double *X, const double *z,
+                                const double *smooth_limits, int device, int m, const int *nn, bool search);
+int vecchia_predict_impl(const char *who, cocons_fit *f, const double *theta, const double *mean, int z_col, int mp,
+                         const double *locs_pred, const double *X_pred, int m_pred, const int *nn_pred, bool search,
+                         double *stochastic, double *quadform);
 // ... and what they call in api_shard.hip: the sharded cocons_neg2loglik_dense, and cocons_fit_destroy's share
 int sharded_eval(cocons_fit *f, const double *theta, const double *mean, double *sum_logliks, double *parts);
 void shard_events_destroy(ShardState *S);

@@ -416,6 +416,23 @@ hipError_t launch_pattern_fill(const PatternTargets &t, int m, const double *qx,
 hipError_t launch_pattern_buckets(int m, const int *rp, const int *ci, int tile, int stride, int *cursor, int *bdst, int *bsrc,
                                   hipStream_t s);
 
+// ---- Vecchia neighbour search (knn.hip) ---------------------------------------------------------------------
+// One wave per query row: block b of the launch is query q = row0 + b at (qx[q], qy[q]).  Its neighbours are the m candidates
+// with the smallest key (d2, index), d2 = fl(fl(dx dx) + fl(dy dy)) -- no square root, ties to the lower index.  The
+// candidates are the points of t (binned: launch_pattern_bin) with an index below q (ordered) or all of them; brute: t is not
+// binned and the wave scans t.x, t.y[0 .. min(q, t.n)) as they lie (the head of the ordered search).
+// nn (may be null): nn[q + j ldn] = the j-th nearest + 1, 0 behind the last.  tab (may be null): tab[q m + j] = the same
+// neighbours 0-based and ascending by index, -1 behind the last -- the layout VecchiaArgs::nbr reads.
+struct KnnArgs {
+    PatternTargets t;
+    const double *qx = nullptr, *qy = nullptr;
+    int row0 = 0, m = 0;
+    int ordered = 0, brute = 0;
+    int *nn = nullptr; size_t ldn = 0;
+    int *tab = nullptr;
+};
+hipError_t launch_knn_query(const KnnArgs &a, int rows, hipStream_t s);
+
 // ---- analytic gradient of the dense -2 log-likelihood (grad.hip) ----------------------------------------------------------
 constexpr int GSITE_FIELDS = 4;    // launch_grad_site: dtilt/deta, cot(tilt), dlog(nu_ij)/deta_smooth, exp(eta_sd)
 struct GradArgs {

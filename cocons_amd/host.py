@@ -1404,10 +1404,48 @@ def vecchia_neighbours_pred(locs, newlocs, m) -> np.ndarray:
     return nn
 
 
+def _neighbours_device(locs, newlocs, m, device):
+    L = _lib.load()
+    locs = _f(locs)
+    n = locs.shape[0]
+    q = None if newlocs is None else _f(newlocs)
+    rows = n if q is None else q.shape[0]
+    nn = np.zeros((rows, int(m)), dtype=np.int32, order="F")
+    _lib.check(L.cocons_vecchia_neighbours(n, _p(locs), 0 if q is None else rows, None if q is None else _p(q), int(m),
+                                           int(device), _ip(nn)), "cocons_vecchia_neighbours")
+    return nn
+
+
+def vecchia_neighbours_device(locs, m, device=0) -> np.ndarray:
+    """`vecchia_neighbours` found on the device (cocons_vecchia_neighbours): n x m int32 in Fortran order,
+    1-based, nearest first, zero-padded.  The rule is the key (d2, index) with d2 = dx dx + dy dy in fp64, no square root,
+    ties to the lower index; `vecchia_neighbours` ranks by np.hypot, which rounds near-ties differently, so the two tables
+    may differ in rows that hold such ties (a regular lattice with an inexact spacing)."""
+    return _neighbours_device(locs, None, m, device)
+
+
+def vecchia_neighbours_pred_device(locs, newlocs, m, device=0) -> np.ndarray:
+    """`vecchia_neighbours_pred` found on the device, by the rule of `vecchia_neighbours_device`: mp x m int32 in Fortran
+    order, 1-based, nearest first, zero-padded when there are fewer than m observations."""
+    return _neighbours_device(locs, newlocs, m, device)
+
+
 class CoconsVecchiaFit(_Handle):
     """Handle of a Vecchia fit (cocons_fit_create_vecchia): (locs, x_covariates, z, smooth.limits) and the neighbour table
     `nn` (n x m, 1-based indices of EARLIER rows, 0 = none; `vecchia_neighbours` makes one).  The rows' order is the Vecchia
     order.  No n x n buffer exists; the library refuses this handle everywhere but in the cores below."""
+
+    @classmethod
+    def from_knn(cls, locs, x_covariates, z, smooth_limits, m, device=-1):
+        """The handle of the table `vecchia_neighbours_device(locs, m)`: the library searches it on the device and keeps it
+        there (cocons_fit_create_vecchia_knn); every core below gives the bits of the handle made from that table."""
+        self = cls.__new__(cls)
+        locs, X, z = self._adopt(locs, x_covariates, z, smooth_limits)
+        self.m = int(m)
+        self._created(self._L.cocons_fit_create_vecchia_knn(self.n, self.p, self.r, _p(locs), _p(X), _p(z),
+                                                            _p(self.smooth_limits), int(device), self.m),
+                      "cocons_fit_create_vecchia_knn")
+        return self
 
     def __init__(self, locs, x_covariates, z, smooth_limits, nn, device=-1):
         locs, X, z = self._adopt(locs, x_covariates, z, smooth_limits)
@@ -1479,6 +1517,18 @@ class CoconsVecchiaFit(_Handle):
         st, qf = np.zeros(mp), np.zeros(mp)
         _lib.check(self._L.cocons_vecchia_predict(self._h, _p(T), _p(mean), int(z_col), mp, _p(lp), _p(Xp), m_pred, _ip(nnp),
                                                   _p(st), _p(qf)), "cocons_vecchia_predict")
+        return st, qf
+
+    def predict_knn_core(self, theta_list, locs_pred, x_covariates_pred, m_pred, z_col=0):
+        """`predict_core` with the table `vecchia_neighbours_pred_device(locs, locs_pred, m_pred)`, to the bit
+        (cocons_vecchia_predict_knn): the neighbours are found on the device chunk by chunk.  The first call builds the grid
+        over the observations, which the handle keeps (`info()["bytes"]` counts it)."""
+        T, mean = _table_mean(theta_list)
+        lp, Xp = _f(locs_pred), _f(x_covariates_pred)
+        mp = lp.shape[0]
+        st, qf = np.zeros(mp), np.zeros(mp)
+        _lib.check(self._L.cocons_vecchia_predict_knn(self._h, _p(T), _p(mean), int(z_col), mp, _p(lp), _p(Xp), int(m_pred),
+                                                      _p(st), _p(qf)), "cocons_vecchia_predict_knn")
         return st, qf
 
     def info(self):
@@ -1618,4 +1668,17 @@ def cocoPredict_vecchia(theta_list, locs, newlocs, X_std, X_pred_std, smooth_lim
 
     with _borrowed(fit, one_column) as f:
         st, qf = f.predict_core(theta_list, newlocs, X_pred_std, nn_pred)
+    return _predict_outputs(theta_list, X_pred_std, st, qf, type)
+
+
+def cocoPredict_vecchia_knn(theta_list, locs, newlocs, X_std, X_pred_std, smooth_limits, z, m_pred, type="pred", fit=None):
+    """`cocoPredict_vecchia` without nn_pred: every new location is predicted from its m_pred nearest observations, found on
+    the device (cocons_vecchia_predict_knn).  `fit` as there."""
+    def one_column():
+        # a handle for the data alone: prediction never reads the handle's own table, so an all-zero column (every
+        # observation independent) stands in for one, as in cocoPredict_vecchia
+        return CoconsVecchiaFit(locs, X_std, z, smooth_limits, np.zeros((np.asarray(X_std).shape[0], 1), dtype=np.int32))
+
+    with _borrowed(fit, one_column) as f:
+        st, qf = f.predict_knn_core(theta_list, newlocs, X_pred_std, m_pred)
     return _predict_outputs(theta_list, X_pred_std, st, qf, type)

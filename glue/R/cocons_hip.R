@@ -548,3 +548,29 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
   if (res[[1]] > 0L) stop("Cholesky error")
   res[[2]]
 }
+
+# the neighbour search on the device (DESIGN.md 4u): no table from another package is needed.  The rule is the key
+# (d2, index) with d2 = dx * dx + dy * dy in double, no square root, ties to the lower index; rows list the nearest first and are
+# zero-padded, so the table for m is the first m columns of the table for any larger m.
+#   nn <- .cocons.hip.vecchia.neighbours(locs[ord, ], m)                 # row i: the m nearest EARLIER rows
+#   nn_pred <- .cocons.hip.vecchia.neighbours(locs[ord, ], m, newlocs)   # row i: the m nearest observations of newlocs[i, ]
+.cocons.hip.vecchia.neighbours <- function(locs, m, newlocs = NULL, device = 0L) {
+  if (!is.null(newlocs)) newlocs <- as.matrix(newlocs)
+  .Call(`_cocons_hip_vecchia_neighbours`, as.matrix(locs), newlocs, as.integer(m), as.integer(device))
+}
+
+# .cocons.hip.vecchia.create without nn: the table of .cocons.hip.vecchia.neighbours(locs, m) is searched on the device and
+# stays there; every entry on the handle gives the bits of the handle made from that table
+.cocons.hip.vecchia.create.knn <- function(locs, x_covariates, z, smooth.limits, m, device = -1L) {
+  .Call(`_cocons_hip_vecchia_create_knn`, as.matrix(locs), as.matrix(x_covariates), as.matrix(z), as.double(smooth.limits),
+        as.integer(device), as.integer(m))
+}
+
+# .cocons.hip.vecchia.predict without nn_pred: every new location is predicted from its m_pred nearest observations, found
+# on the device chunk by chunk
+.cocons.hip.vecchia.predict.knn <- function(fit, theta_list, newlocs, X_pred, m_pred, z_col = 1L) {
+  res <- .Call(`_cocons_hip_vecchia_predict_knn`, fit, theta_list, as.integer(z_col), as.matrix(newlocs), as.matrix(X_pred),
+               as.integer(m_pred))
+  if (res[[1]] > 0L) stop("Cholesky error")
+  res[[2]]
+}

@@ -366,6 +366,24 @@ SEXP _cocons_hip_vecchia_create(SEXP locs, SEXP X, SEXP z, SEXP smooth_limits, S
     return ptr;
 }
 
+/* Vecchia handle whose table the library searches on the device (cocons_fit_create_vecchia_knn): the m nearest EARLIER rows
+ * of every row in the rows' order, which is the Vecchia order */
+SEXP _cocons_hip_vecchia_create_knn(SEXP locs, SEXP X, SEXP z, SEXP smooth_limits, SEXP device, SEXP m)
+{
+    const int n = Rf_nrows(X), p = Rf_ncols(X);
+    const int r = Rf_isMatrix(z) ? Rf_ncols(z) : 1;
+    if (Rf_nrows(locs) != n || Rf_ncols(locs) != 2) Rf_error("locs must be n x 2");
+    cocons_fit *f = cocons_fit_create_vecchia_knn(n, p, r, REAL(locs), REAL(X), REAL(z), REAL(smooth_limits),
+                                                  Rf_asInteger(device), Rf_asInteger(m));
+    if (!f) Rf_error("%s", cocons_last_error());
+    SEXP tag = PROTECT(Rf_allocVector(INTSXP, 4));
+    INTEGER(tag)[0] = n; INTEGER(tag)[1] = p; INTEGER(tag)[2] = r; INTEGER(tag)[3] = 0;
+    SEXP ptr = PROTECT(R_MakeExternalPtr(f, tag, R_NilValue));
+    R_RegisterCFinalizerEx(ptr, fit_finalizer, TRUE);
+    UNPROTECT(2);
+    return ptr;
+}
+
 SEXP _cocons_hip_fit_close(SEXP ptr)
 {
     fit_finalizer(ptr);
@@ -1016,6 +1034,44 @@ SEXP _cocons_hip_vecchia_predict(SEXP fitp, SEXP theta, SEXP z_col, SEXP locs_pr
     return out;
 }
 
+/* _cocons_hip_vecchia_predict without nn_pred: the m_pred nearest observations of every new location are found on the
+ * device, chunk by chunk (cocons_vecchia_predict_knn).  list(status, cbind(stochastic, quadform)) */
+SEXP _cocons_hip_vecchia_predict_knn(SEXP fitp, SEXP theta, SEXP z_col, SEXP locs_pred, SEXP X_pred, SEXP m_pred)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), m = Rf_nrows(X_pred);
+    if (Rf_ncols(X_pred) != p || Rf_nrows(locs_pred) != m || Rf_ncols(locs_pred) != 2)
+        Rf_error("prediction design / locations do not match the fit");
+    SEXP mean = list_get(theta, "mean");
+    if (!Rf_isReal(mean) || XLENGTH(mean) != p) Rf_error("theta$mean must be a double vector of length %d", p);
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    SEXP v = PROTECT(Rf_allocMatrix(REALSXP, m, 2));
+    int rc = cocons_vecchia_predict_knn(f, T, REAL(mean), Rf_asInteger(z_col) - 1, m, REAL(locs_pred), REAL(X_pred),
+                                        Rf_asInteger(m_pred), REAL(v), REAL(v) + m);
+    hip_check(rc, "cocoPredict (Vecchia, neighbours on the device)");
+    SEXP out = status_value(rc, v);
+    UNPROTECT(1);
+    return out;
+}
+
+/* the Vecchia neighbour table found on the device (cocons_vecchia_neighbours): newlocs NULL -- row i names the m nearest
+ * EARLIER rows of locs (n x 2) in the rows' order; otherwise row i names the m nearest rows of locs to new location i.
+ * An integer matrix, 1-based, nearest first, 0 = none */
+SEXP _cocons_hip_vecchia_neighbours(SEXP locs, SEXP newlocs, SEXP m, SEXP device)
+{
+    if (!Rf_isReal(locs) || Rf_ncols(locs) != 2) Rf_error("locs must be a double matrix with 2 columns");
+    const int n = Rf_nrows(locs), self = Rf_isNull(newlocs);
+    if (!self && (!Rf_isReal(newlocs) || Rf_ncols(newlocs) != 2)) Rf_error("newlocs must be a double matrix with 2 columns");
+    const int rows = self ? n : Rf_nrows(newlocs), k = Rf_asInteger(m);
+    if (k < 1 || k > 63) Rf_error("cocons_vecchia_neighbours: m = %d is outside 1 .. 63", k);
+    SEXP nn = PROTECT(Rf_allocMatrix(INTSXP, rows, k));
+    hip_check(cocons_vecchia_neighbours(n, REAL(locs), self ? 0 : rows, self ? NULL : REAL(newlocs), k, Rf_asInteger(device),
+                                        INTEGER(nn)), "Vecchia neighbours");
+    UNPROTECT(1);
+    return nn;
+}
+
 /* kriging from a held band factor on a taper handle: factor S(theta) once for realization z_col (1-based) and keep the band
  * factor on the handle; max_rows = 0: the library's default chunk.  list(status, NULL) -- status > 0: the failing minor */
 SEXP _cocons_hip_krige_taper_prepare(SEXP fitp, SEXP theta, SEXP mean, SEXP z_col, SEXP max_rows)
@@ -1185,6 +1241,9 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_vecchia_neg2loglik_grad", (DL_FUNC)&_cocons_hip_vecchia_neg2loglik_grad, 3},
     {"_cocons_hip_vecchia_predict", (DL_FUNC)&_cocons_hip_vecchia_predict, 6},
     {"_cocons_hip_vecchia_fisher", (DL_FUNC)&_cocons_hip_vecchia_fisher, 3},
+    {"_cocons_hip_vecchia_neighbours", (DL_FUNC)&_cocons_hip_vecchia_neighbours, 4},
+    {"_cocons_hip_vecchia_create_knn", (DL_FUNC)&_cocons_hip_vecchia_create_knn, 6},
+    {"_cocons_hip_vecchia_predict_knn", (DL_FUNC)&_cocons_hip_vecchia_predict_knn, 6},
     {"_cocons_hip_fit_close", (DL_FUNC)&_cocons_hip_fit_close, 1},
     {"_cocons_hip_neg2loglik_parts", (DL_FUNC)&_cocons_hip_neg2loglik_parts, 3},
     {"_cocons_hip_neg2loglik", (DL_FUNC)&_cocons_hip_neg2loglik, 3},

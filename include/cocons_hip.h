@@ -356,6 +356,37 @@ int cocons_vecchia_predict(cocons_fit *fit, const double *theta, const double *m
 /* out4 = {n, m, device bytes the handle holds (data, table, scratch), rows per chunk of cocons_vecchia_predict} */
 int cocons_vecchia_info(cocons_fit *fit, long long *out4);
 
+/* ---- Vecchia neighbour search on the device ---------------------
+ * The rule, here and in every reference: the neighbours of a query q among a set of candidates are the m candidates with the
+ * smallest key (d2, index), d2 = fl(fl(dx dx) + fl(dy dy)) with dx = x_c - x_q, dy = y_c - y_q in fp64, no contraction, no
+ * square root; ties go to the lower index.  Rows list the nearest first and are zero-padded, so the table for m is the first
+ * m columns of the table for any m' > m.  (np.hypot and sqrt round near-ties differently: a table from another rule may
+ * differ in such rows.)  The outputs are a function of the inputs, bit for bit, run to run.
+ *
+ * cocons_vecchia_neighbours: stateless -- host buffers in and out, device memory of the call only.  locs n x 2 column-major.
+ * locs_query == NULL: the ordered self search; rows = n, row i (1-based) names the m nearest among rows 1 .. i - 1 in the
+ * caller's order, so row 1 is all zeros (mq is ignored).  Otherwise plain kNN: rows = mq >= 0, row i names the m nearest of
+ * the n points to query i (locs_query mq x 2 column-major).  nn: rows x m column-major, 1-based, nearest first, 0 = none.
+ * Refused (-1) before any HIP call, nn untouched, with a message that starts with the entry's name: null locs or nn, n < 1,
+ * mq < 0 with a query set, m outside 1 .. 63, a coordinate that is not finite.  An adversarial order (early rows all in one
+ * corner) or a query far from the points is slower, never wrong.                                                          */
+int cocons_vecchia_neighbours(int n, const double *locs, int mq, const double *locs_query /* NULL: ordered self search */,
+                              int m, int device, int *nn /* rows x m column-major, 1-based, nearest first, 0 = none */);
+/* cocons_fit_create_vecchia with the table cocons_vecchia_neighbours(n, locs, 0, NULL, m, ..) returns: the same handle, the
+ * same bits from every Vecchia entry.  The table is searched on the device and written straight into the handle; it never
+ * exists on the host.  Refusals as cocons_fit_create_vecchia's, under this entry's name.                                  */
+cocons_fit *cocons_fit_create_vecchia_knn(int n, int p, int r, const double *locs, const double *X, const double *z,
+                                          const double *smooth_limits, int device, int m);
+/* cocons_vecchia_predict with the table cocons_vecchia_neighbours(n, locs, mp, locs_pred, m_pred, ..) returns, to the bit:
+ * per chunk of 16384 rows the neighbours are found on the device and land in the chunk's table buffer -- no table upload, no
+ * host sort.  A row's outputs depend neither on the chunking nor on the other rows.  The grid over the observations is built
+ * by the first such call and belongs to the handle: counted by cocons_vecchia_info from then on, freed with the handle.
+ * Refusals as cocons_vecchia_predict's, before any device work and with the outputs untouched; a failing block returns its
+ * 1-based row.                                                                                                          */
+int cocons_vecchia_predict_knn(cocons_fit *fit, const double *theta, const double *mean, int z_col, int mp,
+                               const double *locs_pred, const double *X_pred, int m_pred,
+                               double *stochastic, double *quadform);
+
 /* ---- fit handle: everything that is constant over an optimisation -------------
  * Created once per cocoOptim / getHessian call from the arguments the reference
  * passes unchanged to every GetNeg2loglikelihood* evaluation

@@ -45,6 +45,24 @@ int cocons_debug_rhs_layout(struct cocons_fit *fit, int nxb, int *out5);
  * null argument, n < 1, m < 0, a delta that is not finite or <= 0, or a target coordinate that is not finite.            */
 int cocons_debug_pattern_cells(int n, const double *locs, double delta, int m, const double *pts, double *geom5, int *cells);
 
+/* The plan of the Vecchia neighbour search (cocons_vecchia_neighbours) for n points (locs, n x 2 column-major),
+ * from the header the kernels use: plan = { head (rows searched by brute force), L (levels), then L pairs (lo, hi): rows
+ * [lo, hi) search the grid over the first hi points } -- room for 2 + 2 * 32 ints; geom5 = L + 1 records { origin x,
+ * origin y, cell edge, cells along x, cells along y }, one per level and a last one for the grid over all n points that plain
+ * kNN searches (room for 5 * 33 doubles).  For the grid `level` in 0 .. L: cells = m pairs (cx, cy), the clamped cells of the
+ * m points pts (m x 2 column-major), each coordinate in [-1, count]; bounds[r], r = 0 .. rmax (rmax = -1: none), the lower
+ * bound on the d2 of anything outside the (2 r + 1)^2 block of cells around a query's clamped cell, at which the ring walk
+ * stops.  Host only: no HIP call.  0, or -1 with the outputs untouched on a null argument, n < 1, m < 0, rmax < -1, a level
+ * outside 0 .. L, or a coordinate of locs that is not finite.                                                              */
+int cocons_debug_knn_plan(int n, const double *locs, int level, int m, const double *pts, int rmax, int *plan, double *geom5,
+                          int *cells, double *bounds);
+
+/* The two phases of the ordered self search of cocons_vecchia_neighbours(n, locs, 0, NULL, m, device, ..), timed by events on
+ * the search's stream: ms2 = { device milliseconds of binning the levels, device milliseconds of the query launches (the
+ * head's included) }.  The search runs as it does there, its table stays on the device and is dropped.  For
+ * tools/vecchia_knn_timing.py.  0, or < 0 with the refusals of cocons_vecchia_neighbours under this entry's name.        */
+int cocons_debug_knn_phases(int n, const double *locs, int m, int device, double *ms2);
+
 /* Diagnostics of cocons_neg2loglik_grad_taper: (S(theta)^-1)_ij at every stored entry of the pattern the taper handle was
  * created with, in the caller's CSR order (out_nnz: one double per entry of that pattern), by the gradient's selected
  * inverse; bytes_out (may be NULL): the device bytes the gradient holds on the handle.  0, a failing minor k > 0, or < 0. */
