@@ -11,7 +11,7 @@ int vecchia_refuse(const char *who)
                     "cocons_fisher_vecchia, cocons_vecchia_whiten and cocons_vecchia_predict are)", who);
 }
 
-static int vecchia_only(cocons_fit *f, const char *who)
+int vecchia_only(cocons_fit *f, const char *who)
 {
     if (!f->vecchia) return fail(-1, "%s: not a Vecchia fit (cocons_fit_create_vecchia makes one)", who);
     return 0;
@@ -113,7 +113,7 @@ extern "C" int cocons_vecchia_info(cocons_fit *f, long long *out4)
 }
 
 // the observations' records for theta in the parameters of cov_rns (which = 0) or of cov_rns_pred's branch (which = 2)
-static ModeSel vecchia_records(cocons_fit *f, const double *theta, int which, double *aos)
+ModeSel vecchia_records(cocons_fit *f, const double *theta, int which, double *aos)
 {
     ThetaVecs tv;
     make_theta_vecs(theta, f->p, tv);
@@ -124,7 +124,7 @@ static ModeSel vecchia_records(cocons_fit *f, const double *theta, int which, do
 }
 
 // the info words home and the stream drained; 0, or the smallest 1-based row whose block has a pivot that is not positive
-static int vecchia_status(cocons_fit *f, const char *who)
+int vecchia_status(cocons_fit *f, const char *who)
 {
     HIPCHK_AT(who, hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, f->stream));
     HIPCHK_AT(who, hipGetLastError());

@@ -255,6 +255,22 @@ struct TaperGradState {
     long long bytes = 0;          // device bytes of the buffers above
 };
 
+// U^-1 of a Vecchia fit (api_vecchia_sim.hip): the level schedule of (table, n_fixed) -- the last one asked for --
+// and the coefficients of one call, n (m + 1) doubles of scratch.
+struct VecchiaSimState {
+    int n_fixed = -1;             // what the schedule below was made for; -1: none yet
+    DevBuf<int> level;            // n: the rows' levels (0: a fixed row)
+    DevBuf<int> order;            // n - n_fixed: the rows by level
+    DevBuf<int> off;              // depth + 1 offsets into order (allocated n + 2: the counts are formed in it)
+    DevBuf<int> word;             // {changed, depth}
+    std::vector<int> hoff;        // off on the host: what the launches are planned from
+    int widest = 0;               // rows of the largest level
+    DevBuf<double> coef;          // n x (m + 1): the rows' s for this theta
+    int depth() const { return hoff.empty() ? 0 : (int)hoff.size() - 1; }
+    long long schedule_bytes() const { return (long long)((level.count() + order.count() + off.count() + word.count()) * sizeof(int)); }
+    long long bytes() const { return schedule_bytes() + (long long)(coef.count() * sizeof(double)); }
+};
+
 // What makes a handle a Vecchia handle (cocons_fit_create_vecchia, api_vecchia.hip): the neighbour table and the
 // scratch of one evaluation, O(n (m + r + 16)) bytes.  Such a handle has no factorisation buffer at all.
 struct VecchiaState {
@@ -278,9 +294,11 @@ struct VecchiaState {
     DevBuf<double> fout;          // the totals: vecchia_fisher_cols
     // cocons_vecchia_predict_knn, made by its first call: the grid over the observations
     std::unique_ptr<PatternGridBufs> knn;
+    // cocons_vecchia_unwhiten, cocons_sim_vecchia, cocons_vecchia_schedule, made by their first call
+    std::unique_ptr<VecchiaSimState> sim;
     long long bytes() const
     {
-        return (knn ? knn->bytes : 0) +
+        return (knn ? knn->bytes : 0) + (sim ? sim->bytes() : 0) +
                (long long)(nbr.count() * sizeof(int) +
                            (aos.count() + aos2.count() + B.count() + W.count() + part.count() + gsite.count() + gaos.count() +
                             grec.count() + gpart.count() + gout.count() + fdirs.count() + frec.count() + fpart.count() +
@@ -712,6 +730,12 @@ cocons_fit *vecchia_create_impl(const char *who, int n, int p, int r, const doub
 int vecchia_predict_impl(const char *who, cocons_fit *f, const double *theta, const double *mean, int z_col, int mp,
                          const double *locs_pred, const double *X_pred, int m_pred, const int *nn_pred, bool search,
                          double *stochastic, double *quadform);
+// ... and what api_vecchia.hip offers api_vecchia_sim.hip: the refusal of the other kinds of handle, the
+// observations' records for theta (which = 0: cov_rns's parameters) and the info words home with the stream drained (0, or the
+// smallest 1-based row whose block failed)
+int vecchia_only(cocons_fit *f, const char *who);
+ModeSel vecchia_records(cocons_fit *f, const double *theta, int which, double *aos);
+int vecchia_status(cocons_fit *f, const char *who);
 // ... and what they call in api_shard.hip: the sharded cocons_neg2loglik_dense, and cocons_fit_destroy's share
 int sharded_eval(cocons_fit *f, const double *theta, const double *mean, double *sum_logliks, double *parts);
 void shard_events_destroy(ShardState *S);

@@ -705,4 +705,40 @@ void launch_vecchia_final_sums(const double *part, int nseg, int ncol, double *o
 size_t vecchia_sum_scratch_doubles(int n, int ncol);
 void launch_vecchia_sums(const double *v, size_t ldv, int n, int ncol, double *part, double *out, hipStream_t s);
 
+// ---- U^-1 of a Vecchia fit: coefficients, levels and the level solve (vecchia_sim.hip) -------------------------
+constexpr int VECCHIA_SIM_FUSE_ITEMS = 256;     // a level of at most this many (row, column) pairs may join a fused run
+constexpr int VECCHIA_SIM_FUSE_THREADS = 256;   // the one workgroup of a fused run
+constexpr int VECCHIA_SIM_FUSE_LEVELS = 2048;   // levels one fused launch walks at most: a chain-shaped table becomes many
+                                                // short launches, never one long-running kernel
+constexpr int VECCHIA_SIM_SWEEPS = 8;           // relaxation sweeps between two looks at the "changed" word
+// The likelihood launch's gather, pair loop and factorisation, then s = C^-T e_last, for the observations a.obs0 ..
+// a.obs0 + a.rows - 1 (uses m, kb, nbr, aosK, gr, nu_fixed, fail).  a.rec: n records of kb = m + 1 doubles, row i at
+// rec[i kb ..]: place t < k holds s_t of the neighbour at place t of nbr's row, places k .. m - 1 hold 0, place m holds s_last.
+// A pivot that is not positive and finite: atomicMin(*fail, row + 1), nothing written for that row.
+void launch_vecchia_coefs(int mode, const VecchiaArgs &a, hipStream_t s);
+// One relaxation sweep of level[i] = 1 + max_t level[nbr[i m + t]] (1 without neighbours) over the rows n_fixed .. n - 1, in
+// place; *changed = 1 where a row's level grew.  level starts as zeros and level[i < n_fixed] stays 0.
+void launch_vecchia_level_sweep(const int *nbr, int m, int n, int n_fixed, int *level, int *changed, hipStream_t s);
+// count[l - 1] = rows of level l, *depth = the largest level (both zeroed by the caller); then, cursor holding the levels'
+// offsets, order[..] = the rows n_fixed .. n - 1 by level (cursor ends as the offsets of the next levels)
+void launch_vecchia_level_count(const int *level, int n, int n_fixed, int *count, int *depth, hipStream_t s);
+void launch_vecchia_level_scatter(const int *level, int n, int n_fixed, int *cursor, int *order, hipStream_t s);
+// x[row + q ldx] = (W[(row - w_row0) + q ldw] - sum_t coef[row (m + 1) + t] x[nbr[row m + t] + q ldx]) / coef[row (m + 1) + m],
+// t ascending over the row's neighbours, for q < c.  off: depth + 1 offsets into order, level l (0-based) = order[off[l] ..
+// off[l + 1]).
+struct VecchiaSimArgs {
+    const int *nbr = nullptr; int m = 0;
+    const double *coef = nullptr;
+    const int *order = nullptr, *off = nullptr;
+    const double *W = nullptr; size_t ldw = 0; int w_row0 = 0;
+    double *x = nullptr; size_t ldx = 0;
+    int c = 0;
+};
+void launch_vecchia_sim_level(const VecchiaSimArgs &a, int begin, int rows, hipStream_t s);   // one level, the whole chip
+void launch_vecchia_sim_fused(const VecchiaSimArgs &a, int lv0, int lv1, hipStream_t s);      // levels lv0 .. lv1 - 1, one workgroup
+// cocons_sim_vecchia's ends.  fixed: x[i + q ldx] = z[i] - X_i mean for i < n_fixed, q < c.  Otherwise:
+// out[(i - n_fixed) + q ldo] = X_i mean + x[i + q ldx] for n_fixed <= i < n.  The trend as launch_vecchia_resid forms it.
+void launch_vecchia_sim_ends(bool fixed, int n, int p, int n_fixed, int c, const double *X, int ldx_design, const double *mean,
+                             const double *z, double *x, size_t ldx, double *out, size_t ldo, hipStream_t s);
+
 }  // namespace cocons

@@ -27,6 +27,7 @@
 #include "kernels.h"
 #include "matern_device.hpp"
 #include "grad_pair.hpp"
+#include "vecchia_tri.hpp"
 
 namespace cocons {
 
@@ -102,9 +103,6 @@ void launch_vecchia_resid(int n, int p, const double *X, int ldx, const double *
 }
 
 // ---------------------------------------------------------------------------
-// element (r, c), r >= c, of the packed lower triangle (row after row)
-__device__ __forceinline__ int tri_at(int r, int c) { return r * (r + 1) / 2 + c; }
-
 // Dynamic LDS, sized by kb = m + 1 rows (vecchia_lds_bytes):
 //   par   LOCP_FIELDS x kb   the block's parameters as an SoA of stride kb -- what pair_value_idx reads;
 //   par2  LOCP_FIELDS x kb   PRED only: the same rows in the prediction branch's parameters, the prediction site last;
@@ -122,15 +120,6 @@ constexpr int VECCHIA_GX = GSITE_FIELDS + 2 + 2 * GFAM;
 //   stg   gd x 64            a pass of 64 pairs: the entry of C_a per direction (then, once, the p sums u of the mean block);
 //   gall  ndir x kb          g_a = L^-1 (C_a s) of every direction, what the Gram is formed of.
 constexpr int VECCHIA_FX = GSITE_FIELDS + 2;
-
-// pair t = r (r - 1) / 2 + c of the packed strict lower triangle, r > c
-__device__ __forceinline__ void tri_pair(int t, int &r, int &c)
-{
-    r = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)t)) * 0.5f);
-    while (r * (r - 1) / 2 > t) --r;
-    while ((r + 1) * r / 2 <= t) ++r;
-    c = t - r * (r - 1) / 2;
-}
 
 // Forward substitution over the neighbours' rows for VECCHIA_G right-hand sides in registers, lane = row: lane r ends with
 // b_r - sum_{j < r} C(r, j) y_j, j ascending (the numerator of y_r: the steps from r on leave it alone).

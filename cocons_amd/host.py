@@ -1531,6 +1531,36 @@ class CoconsVecchiaFit(_Handle):
                                                       _p(st), _p(qf)), "cocons_vecchia_predict_knn")
         return st, qf
 
+    def unwhiten_core(self, theta_list, W):
+        """U^-1 W for the columns of W (n x c, the caller's order): the inverse of `whiten_core` for the same theta
+        (cocons_vecchia_unwhiten).  With N(0, 1) columns the result has the Vecchia model's covariance."""
+        T = theta_table(theta_list)
+        W = _f(np.asarray(W, dtype=np.float64).reshape(self.n, -1))
+        out = np.zeros(W.shape, order="F")
+        _lib.check(self._L.cocons_vecchia_unwhiten(self._h, _p(T), int(W.shape[1]), _p(W), _p(out)), "cocons_vecchia_unwhiten")
+        return out
+
+    def sim_core(self, theta_list, iiderrors, n_fixed=0, z_col=0):
+        """cocons_sim_vecchia.  n_fixed = 0: X mean + U^-1 E, n x nsim.  1 <= n_fixed < n: the first n_fixed rows are data
+        (z[:, z_col] - X mean) and the rows behind them run the recursion; E and the result are (n - n_fixed) x nsim -- the
+        joint conditional mean at the later rows for E = 0, a conditional draw for N(0, 1) numbers."""
+        rows = self.n - int(n_fixed)
+        E = _f(np.asarray(iiderrors, dtype=np.float64).reshape(max(rows, 1), -1))
+        T, mean = _table_mean(theta_list)
+        out = np.zeros(E.shape, order="F")
+        _lib.check(self._L.cocons_sim_vecchia(self._h, _p(T), _p(mean), int(n_fixed), int(z_col), int(E.shape[1]), _p(E),
+                                              _p(out)), "cocons_sim_vecchia")
+        return out
+
+    def schedule(self, n_fixed=0):
+        """The level schedule of (table, n_fixed) that `unwhiten_core` and `sim_core` run on (cocons_vecchia_schedule):
+        {"levels": n int32 (0: a fixed row), "depth", "widest": rows of the largest level, "launches": of one solve under the
+        current COCONS_VECCHIA_SIM_FUSE, "bytes": device bytes of the schedule and of a solve's coefficients}"""
+        levels = np.zeros(self.n, dtype=np.int32)
+        out = (ctypes.c_longlong * 4)()
+        _lib.check(self._L.cocons_vecchia_schedule(self._h, int(n_fixed), _ip(levels), out), "cocons_vecchia_schedule")
+        return {"levels": levels, "depth": int(out[0]), "widest": int(out[1]), "launches": int(out[2]), "bytes": int(out[3])}
+
     def info(self):
         """{"n", "m", "bytes": device bytes the handle holds, "rows": rows per chunk of predict_core}"""
         out = (ctypes.c_longlong * 4)()
@@ -1682,3 +1712,40 @@ def cocoPredict_vecchia_knn(theta_list, locs, newlocs, X_std, X_pred_std, smooth
     with _borrowed(fit, one_column) as f:
         st, qf = f.predict_knn_core(theta_list, newlocs, X_pred_std, m_pred)
     return _predict_outputs(theta_list, X_pred_std, st, qf, type)
+
+
+def cocoSim_vecchia(theta_list, locs, X_std, smooth_limits, iiderrors, nn=None, m=None, fit=None):
+    """Marginal branch of cocoSim (R/sim.R:147-172) for the Vecchia model: X mean + U^-1 E, n x nsim, E = `iiderrors` the
+    n x nsim matrix of N(0, 1) draws, used as given.  The rows' order is the Vecchia order.  The table is `nn`, or with `m`
+    the m nearest earlier rows found on the device (`CoconsVecchiaFit.from_knn`); `fit` (optional) a CoconsVecchiaFit over
+    (locs, X_std) with the table to draw from.  With every predecessor in the table the fields are `cocoSim_dense`'s of
+    type "diff"."""
+    n = np.asarray(X_std).shape[0]
+    if fit is None and (nn is None) == (m is None):
+        raise ValueError("cocoSim_vecchia: give a neighbour table nn, a number of neighbours m, or a fit")
+
+    def make():
+        if nn is not None:
+            return CoconsVecchiaFit(locs, X_std, np.zeros(n), smooth_limits, nn)
+        return CoconsVecchiaFit.from_knn(locs, X_std, np.zeros(n), smooth_limits, m)
+
+    with _borrowed(fit, make) as f, _chol_error():
+        return f.sim_core(theta_list, np.asarray(iiderrors, dtype=np.float64).reshape(n, -1))
+
+
+def cocoSim_cond_vecchia(theta_list, locs, newlocs, X_std, X_pred_std, smooth_limits, z, iiderrors, m, fit=None):
+    """Conditional branch of cocoSim (sim.type = "cond") for the Vecchia model: the joint handle over (observations, then new
+    locations) with the m nearest earlier rows of every row, found on the device -- a new location is conditioned on
+    observations and on the new locations in front of it --, the observations fixed at z (its first column) and the
+    recursion run over the new rows: mp x nsim, X_pred mean + x.  `iiderrors` (mp x nsim) = 0 gives the joint conditional mean
+    of the model.  `fit` (optional): such a joint handle, made once."""
+    X, Xp = np.asarray(X_std, dtype=np.float64), np.asarray(X_pred_std, dtype=np.float64)
+    n, mp = X.shape[0], Xp.shape[0]
+
+    def make():
+        zz = np.asarray(z, dtype=np.float64).reshape(n, -1)
+        return CoconsVecchiaFit.from_knn(np.vstack([np.asarray(locs, dtype=np.float64), np.asarray(newlocs, dtype=np.float64)]),
+                                         np.vstack([X, Xp]), np.vstack([zz, np.zeros((mp, zz.shape[1]))]), smooth_limits, m)
+
+    with _borrowed(fit, make) as f, _chol_error():
+        return f.sim_core(theta_list, np.asarray(iiderrors, dtype=np.float64).reshape(mp, -1), n_fixed=n)

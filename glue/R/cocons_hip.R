@@ -574,3 +574,32 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
   if (res[[1]] > 0L) stop("Cholesky error")
   res[[2]]
 }
+
+# U^-1 on a Vecchia handle (DESIGN.md 4v): the inverse of the whitening, solved level by level on the device.
+# .cocons.hip.vecchia.unwhiten: U^-1 W for the n x c matrix W -- with N(0, 1) columns, fields with the Vecchia model's
+# covariance and mean zero, in the rows' (Vecchia) order
+.cocons.hip.vecchia.unwhiten <- function(fit, theta_list, W) {
+  W <- as.matrix(W)
+  storage.mode(W) <- "double"
+  res <- .Call(`_cocons_hip_vecchia_unwhiten`, fit, theta_list[names(theta_list) != "mean"], W)
+  if (res[[1]] > 0L) stop("Cholesky error")
+  res[[2]]
+}
+
+# cocoSim for a Vecchia handle.  n_fixed = 0: X mean + U^-1 iiderrors, the marginal branch (R/sim.R:147-172).  n_fixed >= 1:
+# the first n_fixed rows are data (z[, z_col]) and the rows behind them are drawn given them (sim.type = "cond"); the handle
+# is made over rbind(locs, newlocs), rbind(X, X_pred) and rbind(z, anything); iiderrors is (n - n_fixed) x nsim, all zero for
+# the joint conditional mean
+.cocons.hip.vecchia.sim <- function(fit, theta_list, iiderrors, n_fixed = 0L, z_col = 1L) {
+  iiderrors <- as.matrix(iiderrors)
+  storage.mode(iiderrors) <- "double"
+  res <- .Call(`_cocons_hip_vecchia_sim`, fit, theta_list, as.integer(n_fixed), as.integer(z_col), iiderrors)
+  if (res[[1]] > 0L) stop("Cholesky error")
+  res[[2]]
+}
+
+# the schedule the two run on: list(levels, info = c(depth, widest level, launches of one solve, device bytes))
+.cocons.hip.vecchia.schedule <- function(fit, n_fixed = 0L) {
+  res <- .Call(`_cocons_hip_vecchia_schedule`, fit, as.integer(n_fixed))
+  list(levels = res[[1]], info = res[[2]])
+}

@@ -1072,6 +1072,68 @@ SEXP _cocons_hip_vecchia_neighbours(SEXP locs, SEXP newlocs, SEXP m, SEXP device
     return nn;
 }
 
+/* U^-1 W on a Vecchia handle (cocons_vecchia_unwhiten): W is n x c; list(status, the n x c result); theta without `mean` */
+SEXP _cocons_hip_vecchia_unwhiten(SEXP fitp, SEXP theta, SEXP W)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), n = fit_n(fitp);
+    if (!Rf_isReal(W) || !Rf_isMatrix(W) || Rf_nrows(W) != n) Rf_error("W must be a double matrix with %d rows", n);
+    const int c = Rf_ncols(W);
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    SEXP v = PROTECT(Rf_allocMatrix(REALSXP, n, c));
+    for (R_xlen_t e = 0; e < XLENGTH(v); ++e) REAL(v)[e] = NA_REAL;
+    int rc = cocons_vecchia_unwhiten(f, T, c, REAL(W), REAL(v));
+    hip_check(rc, "cocoSim (Vecchia, unwhiten)");
+    SEXP out = status_value(rc, v);
+    UNPROTECT(1);
+    return out;
+}
+
+/* fields and conditional draws of the Vecchia model (cocons_sim_vecchia): theta is the WHOLE theta_list (`mean` read by name),
+ * n_fixed the number of leading rows held at z[, z_col] (z_col 1-based), iiderrors (n - n_fixed) x nsim;
+ * list(status, the (n - n_fixed) x nsim result) */
+SEXP _cocons_hip_vecchia_sim(SEXP fitp, SEXP theta, SEXP n_fixed, SEXP z_col, SEXP iiderrors)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), n = fit_n(fitp), nf = Rf_asInteger(n_fixed);
+    if (nf < 0 || nf >= n) Rf_error("cocons_sim_vecchia: n_fixed = %d is outside 0 .. %d", nf, n - 1);
+    if (!Rf_isReal(iiderrors) || !Rf_isMatrix(iiderrors) || Rf_nrows(iiderrors) != n - nf)
+        Rf_error("iiderrors must be a double matrix with %d rows", n - nf);
+    const int nsim = Rf_ncols(iiderrors);
+    SEXP mean = list_get(theta, "mean");
+    if (!Rf_isReal(mean) || XLENGTH(mean) != p) Rf_error("theta$mean must be a double vector of length %d", p);
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    SEXP v = PROTECT(Rf_allocMatrix(REALSXP, n - nf, nsim));
+    for (R_xlen_t e = 0; e < XLENGTH(v); ++e) REAL(v)[e] = NA_REAL;
+    int rc = cocons_sim_vecchia(f, T, REAL(mean), nf, Rf_asInteger(z_col) - 1, nsim, REAL(iiderrors), REAL(v));
+    hip_check(rc, "cocoSim (Vecchia)");
+    SEXP out = status_value(rc, v);
+    UNPROTECT(1);
+    return out;
+}
+
+/* the level schedule of (table, n_fixed) (cocons_vecchia_schedule): list(levels = n integers, info = c(depth, rows of the
+ * largest level, launches of one solve, device bytes)) */
+SEXP _cocons_hip_vecchia_schedule(SEXP fitp, SEXP n_fixed)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int n = fit_n(fitp), nf = Rf_asInteger(n_fixed);
+    if (nf < 0 || nf >= n) Rf_error("cocons_vecchia_schedule: n_fixed = %d is outside 0 .. %d", nf, n - 1);
+    long long o4[4] = {0, 0, 0, 0};
+    SEXP lv = PROTECT(Rf_allocVector(INTSXP, n));
+    for (int i = 0; i < n; ++i) INTEGER(lv)[i] = 0;
+    hip_check(cocons_vecchia_schedule(f, nf, INTEGER(lv), o4), "Vecchia schedule");
+    SEXP info = PROTECT(Rf_allocVector(REALSXP, 4));
+    for (int i = 0; i < 4; ++i) REAL(info)[i] = (double)o4[i];
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 2));
+    SET_VECTOR_ELT(out, 0, lv);
+    SET_VECTOR_ELT(out, 1, info);
+    UNPROTECT(3);
+    return out;
+}
+
 /* kriging from a held band factor on a taper handle: factor S(theta) once for realization z_col (1-based) and keep the band
  * factor on the handle; max_rows = 0: the library's default chunk.  list(status, NULL) -- status > 0: the failing minor */
 SEXP _cocons_hip_krige_taper_prepare(SEXP fitp, SEXP theta, SEXP mean, SEXP z_col, SEXP max_rows)
@@ -1244,6 +1306,9 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_vecchia_neighbours", (DL_FUNC)&_cocons_hip_vecchia_neighbours, 4},
     {"_cocons_hip_vecchia_create_knn", (DL_FUNC)&_cocons_hip_vecchia_create_knn, 6},
     {"_cocons_hip_vecchia_predict_knn", (DL_FUNC)&_cocons_hip_vecchia_predict_knn, 6},
+    {"_cocons_hip_vecchia_unwhiten", (DL_FUNC)&_cocons_hip_vecchia_unwhiten, 3},
+    {"_cocons_hip_vecchia_sim", (DL_FUNC)&_cocons_hip_vecchia_sim, 5},
+    {"_cocons_hip_vecchia_schedule", (DL_FUNC)&_cocons_hip_vecchia_schedule, 2},
     {"_cocons_hip_fit_close", (DL_FUNC)&_cocons_hip_fit_close, 1},
     {"_cocons_hip_neg2loglik_parts", (DL_FUNC)&_cocons_hip_neg2loglik_parts, 3},
     {"_cocons_hip_neg2loglik", (DL_FUNC)&_cocons_hip_neg2loglik, 3},

@@ -387,6 +387,36 @@ int cocons_vecchia_predict_knn(cocons_fit *fit, const double *theta, const doubl
                                const double *locs_pred, const double *X_pred, int m_pred,
                                double *stochastic, double *quadform);
 
+/* ---- U^-1 on a Vecchia fit: fields and conditional draws of the Vecchia model -----------------------------
+ * Observation i has the neighbours j_1 < .. < j_k, all earlier rows, and the block K = C C' with its rows in the order
+ * (j_1 .. j_k, i), exactly as cocons_neg2loglik_vecchia builds it.  With s = C^-T e_last (the vector the gradient and the
+ * information solve for) the whitening is y_i = sum_t s_t b_{j_t} + s_last b_i, and its inverse the recursion, in ascending i,
+ *     x_i = ( w_i - sum_{t = 1 .. k} s_t x_{j_t} ) / s_last,
+ * the sum over t ascending in one thread, no contraction.  x = U^-1 w has the covariance (U'U)^-1, the Vecchia model's Sigma;
+ * with every predecessor in the table U^-1 is the lower Cholesky factor of Sigma(theta).  A row's result is a function of its
+ * own coefficients and of its neighbours' results alone: it does not depend on the number of columns, on how the rows are
+ * spread over launches (COCONS_VECCHIA_SIM_FUSE=0: one launch per level, no fused runs of small levels) or on the run.
+ * The rows are solved level by level: level(i) = 0 for the rows i <= n_fixed, otherwise 1 + the largest level among the row's
+ * neighbours (1 without neighbours).  The levels are computed on the device from the handle's table; the handle keeps the
+ * schedule of the last n_fixed and n (m + 1) doubles of coefficients, recomputed per call; cocons_vecchia_info counts both.
+ * Refused (-1) before any device work, outputs untouched, with a message that starts with the entry's name: a null argument,
+ * c < 1, nsim < 1, n_fixed outside 0 .. n - 1, z_col outside the realisations, a handle that is not a Vecchia handle.  A
+ * failing block returns its smallest 1-based row; nothing is written and the solve is not launched.  Outputs are written on
+ * 0 only.
+ * cocons_vecchia_unwhiten: out = U^-1 W, W and out n x c column-major in the caller's order: the inverse of
+ * cocons_vecchia_whiten for the same theta.                                                                              */
+int cocons_vecchia_unwhiten(cocons_fit *fit, const double *theta, int c, const double *W, double *out);
+/* n_fixed = 0: out (n x nsim) = X mean + U^-1 E, cocoSim's marginal branch for a Vecchia handle; E = iiderrors (n x nsim) is
+ * used as given.  1 <= n_fixed < n: the rows 1 .. n_fixed are data, x_i = z[i, z_col] - X_i mean, and the rows behind them run
+ * the recursion; E and out are (n - n_fixed) x nsim and out_i = X_i mean + x_i.  With E = 0 that is the joint conditional mean
+ * of the Vecchia model at the later rows, with N(0, 1) numbers a conditional draw.  The handle is made over (observations,
+ * then new locations) with any z in the new rows: they are not read.                                                      */
+int cocons_sim_vecchia(cocons_fit *fit, const double *theta, const double *mean, int n_fixed, int z_col,
+                       int nsim, const double *iiderrors, double *out);
+/* The schedule of (table, n_fixed): levels (n ints, may be NULL) and out4 = {depth, rows of the largest level, launches of one
+ * solve of one column under the current COCONS_VECCHIA_SIM_FUSE, device bytes of the schedule and of the coefficients of a solve}.       */
+int cocons_vecchia_schedule(cocons_fit *fit, int n_fixed, int *levels /* n, may be NULL */, long long *out4);
+
 /* ---- fit handle: everything that is constant over an optimisation -------------
  * Created once per cocoOptim / getHessian call from the arguments the reference
  * passes unchanged to every GetNeg2loglikelihood* evaluation

@@ -63,6 +63,13 @@ int cocons_debug_knn_plan(int n, const double *locs, int level, int m, const dou
  * tools/vecchia_knn_timing.py.  0, or < 0 with the refusals of cocons_vecchia_neighbours under this entry's name.        */
 int cocons_debug_knn_phases(int n, const double *locs, int m, int device, double *ms2);
 
+/* cocons_vecchia_unwhiten(fit, theta, c, W, out) with its three phases timed by events on the handle's stream: ms3 = { the
+ * records and the coefficient launch with the status word's way home, the schedule (0 when the handle holds it already), the
+ * upload of W and the solve's launches }, device milliseconds.  For tools/vecchia_sim_timing.py.  Returns and refusals as
+ * cocons_vecchia_unwhiten's, under this entry's name.                                                                    */
+int cocons_debug_vecchia_sim_phases(struct cocons_fit *fit, const double *theta, int c, const double *W, double *out,
+                                    double *ms3);
+
 /* Diagnostics of cocons_neg2loglik_grad_taper: (S(theta)^-1)_ij at every stored entry of the pattern the taper handle was
  * created with, in the caller's CSR order (out_nnz: one double per entry of that pattern), by the gradient's selected
  * inverse; bytes_out (may be NULL): the device bytes the gradient holds on the handle.  0, a failing minor k > 0, or < 0. */
