@@ -433,6 +433,54 @@ struct KnnArgs {
 };
 hipError_t launch_knn_query(const KnnArgs &a, int rows, hipStream_t s);
 
+// ---- maxmin ordering by scale-halving nets (order.hip; the rule: order_plan.hpp) -------------------------------
+// The points live in LABEL order (px, py, orig: the caller's index), so a lower index is a higher priority.  state[p], by
+// label: ORDER_FREE (not ordered, undecided at this level), ORDER_DONE (ordered), ORDER_DROPPED (conflicts with an ordered
+// point at this level), ORDER_NEW (the dense schedule: taken in this round, ORDER_DONE after its check kernel).  rem: the R
+// labels not ordered before this level, ascending.  A state only ever leaves ORDER_FREE inside a level, so a stale read
+// means "undecided" and costs a round, never a bit.
+enum : int { ORDER_FREE = 0, ORDER_DONE = 1, ORDER_DROPPED = 2, ORDER_NEW = 3 };
+struct OrderArgs {
+    int n = 0;
+    const double *px = nullptr, *py = nullptr;
+    const int *orig = nullptr;
+    int *state = nullptr;
+    const int *rem = nullptr;
+    int R = 0;
+    double e = 0.0;                     // e_k: two points conflict iff d2 < e
+    // the dense schedule: the level's grid, S (one ordered label per cell, -1: none), the champions (all ones: none) and
+    // every rem entry's cell
+    PatternGrid g;
+    int *S = nullptr;
+    unsigned *champ = nullptr;
+    int *cellof = nullptr;
+    // the binned schedule: all n points (label order) on a grid whose edge exceeds l_k
+    PatternTargets t;
+    unsigned *counter = nullptr;        // += the points still undecided after the round
+};
+// relabel: px, py, orig, state from the caller's x, y; rem = every label but first's, ascending; order[0], olab[0]: level 0
+hipError_t launch_order_relabel(int n, const double *x, const double *y, int first, double *px, double *py, int *orig, int *state,
+                                int *rem, int *order, int *olab, hipStream_t s);
+// dense level: S[cell] = label for the `done` ordered labels olab (S is all -1 beforehand)
+hipError_t launch_order_dense_seed(const OrderArgs &a, const int *olab, int done, hipStream_t s);
+// dense round, three launches: (a) champ[cell] = min of the undecided labels; (b) a champion below the champions of the 24
+// surrounding cells is taken (ORDER_NEW, S[cell] = label); (c) check: ORDER_NEW -> ORDER_DONE, the champions of the cells
+// touched are cleared, every undecided point looks for a conflict in the 5 x 5 block of S and counts itself if it finds none.
+// first: the level's opening check (cellof is computed, champ is all ones already)
+hipError_t launch_order_dense_champions(const OrderArgs &a, hipStream_t s);
+hipError_t launch_order_dense_take(const OrderArgs &a, hipStream_t s);
+hipError_t launch_order_dense_check(const OrderArgs &a, bool first, hipStream_t s);
+// binned round, one launch: every undecided point scans the 3 x 3 block; a conflict with an ordered point drops it, else with
+// no undecided conflicting point of a lower label it is taken (ORDER_DONE), else it waits and counts itself
+hipError_t launch_order_binned_round(const OrderArgs &a, hipStream_t s);
+// the end of a level, three launches: cnt[b] = the ordered among places [256 b, 256 b + 256) of rem, first = its exclusive
+// scan (launch_scan_exclusive; *total: their number), then order[base + rank] = orig + 1 and olab[..] = label for the
+// ordered, rem2[j - rank] = label with the state back to ORDER_FREE for the others.  cnt, first: R / 256 + 2 ints
+hipError_t launch_order_emit(const OrderArgs &a, int *cnt, int *first, long long *total, int base, int *order, int *olab,
+                             int *rem2, hipStream_t s);
+// the rest: order[base + j] = orig[rem[j]] + 1
+hipError_t launch_order_rest(const OrderArgs &a, int base, int *order, hipStream_t s);
+
 // ---- analytic gradient of the dense -2 log-likelihood (grad.hip) ----------------------------------------------------------
 constexpr int GSITE_FIELDS = 4;    // launch_grad_site: dtilt/deta, cot(tilt), dlog(nu_ij)/deta_smooth, exp(eta_sd)
 struct GradArgs {

@@ -1430,6 +1430,104 @@ def vecchia_neighbours_pred_device(locs, newlocs, m, device=0) -> np.ndarray:
     return _neighbours_device(locs, newlocs, m, device)
 
 
+_ORDER_LEVELS = 64
+_ORDER_MIX = (0x9E3779B1, 0x85EBCA6B, 0xC2B2AE35)
+
+
+def _order_labels(n) -> np.ndarray:
+    """label(i) for i = 0 .. n - 1 (include/cocons_hip.h, the rule's step 1): three multiply-xorshift rounds on b-bit
+    words, walked until the word is below n."""
+    b = max(1, int(n - 1).bit_length())
+    mask, s = np.uint64((1 << b) - 1), np.uint64((b + 1) // 2)
+
+    def mix(v):
+        for c in _ORDER_MIX:
+            v = (v * np.uint64(c)) & mask
+            v = v ^ (v >> s)
+        return v
+
+    v = mix(np.arange(n, dtype=np.uint64))
+    while True:
+        out = v >= np.uint64(n)
+        if not out.any():
+            return v.astype(np.int64)
+        v[out] = mix(v[out])
+
+
+def vecchia_order(locs, levels=False):
+    """The maxmin ordering by scale-halving nets on the host: the rule of include/cocons_hip.h in numpy, with
+    a k-d tree that only proposes candidates -- every decision is the rule's d2 = dx dx + dy dy < e_k.  Returns the order
+    (n int32, 1-based: order[t] is the row at position t + 1), with levels=True also the level counts
+    [level 0, levels 1 .. K, the rest].  `vecchia_order_device` returns the same bits."""
+    from scipy.spatial import cKDTree
+    locs = np.ascontiguousarray(np.asarray(locs, dtype=np.float64))
+    n = locs.shape[0]
+    if n < 1 or locs.shape != (n, 2) or not np.all(np.isfinite(locs)):
+        raise ValueError("locs must be n x 2, n >= 1, finite")
+    lab = _order_labels(n)
+    P = np.empty_like(locs)
+    P[lab] = locs                                   # the points in label order: a lower index is a higher priority
+    orig = np.empty(n, dtype=np.int64)
+    orig[lab] = np.arange(n)
+    x0, y0 = locs.min(axis=0)
+    x1, y1 = locs.max(axis=0)
+    L = max(x1 - x0, y1 - y0)
+    c = np.array([x0 + 0.5 * (x1 - x0), y0 + 0.5 * (y1 - y0)])
+
+    def d2(a, b):
+        dx, dy = a[..., 0] - b[..., 0], a[..., 1] - b[..., 1]
+        return dx * dx + dy * dy
+
+    first = int(np.argmin(d2(locs, c)))             # argmin: the first of equal keys, the lower caller's index
+    done = [np.array([lab[first]])]
+    counts = [1]
+    rem = np.delete(np.arange(n), lab[first])
+    for k in range(1, _ORDER_LEVELS + 1):
+        if rem.size == 0:
+            break
+        ell = math.ldexp(L, 1 - k)
+        e, r = ell * ell, ell * (1.0 + 1e-9)
+        taken = []
+        if r > 0.0:
+            tree = cKDTree(P[rem])
+            alive = np.ones(rem.size, dtype=bool)
+            S = np.concatenate(done)
+            hits = tree.query_ball_point(P[S], r)
+            src = np.repeat(np.arange(S.size), [len(h) for h in hits])
+            if src.size:
+                dst = np.concatenate([np.asarray(h, dtype=np.int64) for h in hits if len(h)])
+                alive[dst[d2(P[S[src]], P[rem[dst]]) < e]] = False
+            for j in np.flatnonzero(alive):         # ascending label; alive shrinks while the walk goes on
+                if not alive[j]:
+                    continue
+                taken.append(j)
+                near = np.asarray(tree.query_ball_point(P[rem[j]], r), dtype=np.int64)
+                alive[near[d2(P[rem[near]], P[rem[j]]) < e]] = False
+                alive[j] = False
+            taken = np.asarray(taken, dtype=np.int64)
+        else:
+            taken = np.arange(rem.size)             # e_k = 0: nothing conflicts
+        done.append(rem[taken])
+        counts.append(int(taken.size))
+        rem = np.delete(rem, taken)
+    done.append(rem)
+    counts.append(int(rem.size))
+    order = (orig[np.concatenate(done)] + 1).astype(np.int32)
+    return (order, np.asarray(counts, dtype=np.int32)) if levels else order
+
+
+def vecchia_order_device(locs, device=0, levels=False):
+    """`vecchia_order` on the device (cocons_vecchia_order): the same bits.  levels=True: (order, counts) with
+    counts = [level 0, levels 1 .. K, the rest]."""
+    L = _lib.load()
+    locs = _f(locs)
+    n = locs.shape[0]
+    order = np.zeros(n, dtype=np.int32)
+    counts = np.zeros(_ORDER_LEVELS + 3, dtype=np.int32)
+    _lib.check(L.cocons_vecchia_order(n, _p(locs), int(device), _ip(order), _ip(counts)), "cocons_vecchia_order")
+    return (order, counts[1:1 + counts[0]].copy()) if levels else order
+
+
 class CoconsVecchiaFit(_Handle):
     """Handle of a Vecchia fit (cocons_fit_create_vecchia): (locs, x_covariates, z, smooth.limits) and the neighbour table
     `nn` (n x m, 1-based indices of EARLIER rows, 0 = none; `vecchia_neighbours` makes one).  The rows' order is the Vecchia
@@ -1446,6 +1544,33 @@ class CoconsVecchiaFit(_Handle):
                                                             _p(self.smooth_limits), int(device), self.m),
                       "cocons_fit_create_vecchia_knn")
         return self
+
+    @classmethod
+    def from_maxmin(cls, locs, x_covariates, z, smooth_limits, m, device=-1):
+        """`from_knn` on the rows in the maxmin order of `vecchia_order_device(locs)`: the order is found on the device, the
+        data is permuted on the host, and every core gives the bits of `from_knn` on the permuted arrays.  The handle's rows
+        are the PERMUTED ones: `maxmin_order` (n int32, 1-based) says which of the caller's rows stands where, `to_maxmin`
+        carries per-row arrays of the caller (B of whiten_core, iiderrors, W) into the handle's order and `from_maxmin_order`
+        carries per-row outputs (whitened columns, simulated fields) back."""
+        locs = _f(locs)
+        order = vecchia_order_device(locs, device=max(int(device), 0))
+        o = order.astype(np.int64) - 1
+        X = _f(x_covariates)
+        z = np.asarray(z, dtype=np.float64).reshape(locs.shape[0], -1)
+        self = cls.from_knn(locs[o], X[o], z[o], smooth_limits, m, device=device)
+        self.maxmin_order = order
+        return self
+
+    def to_maxmin(self, rows):
+        """A per-row array in the caller's order (n or n x c) in the handle's order (`from_maxmin`)"""
+        return np.asarray(rows)[self.maxmin_order.astype(np.int64) - 1]
+
+    def from_maxmin_order(self, rows):
+        """A per-row array in the handle's order (n or n x c) in the caller's order: the inverse of `to_maxmin`"""
+        rows = np.asarray(rows)
+        out = np.empty_like(rows)
+        out[self.maxmin_order.astype(np.int64) - 1] = rows
+        return out
 
     def __init__(self, locs, x_covariates, z, smooth_limits, nn, device=-1):
         locs, X, z = self._adopt(locs, x_covariates, z, smooth_limits)

@@ -488,7 +488,7 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
 # Vecchia approximation of the model's own likelihood (DESIGN.md 4r): n small blocks instead of one factorisation, O(n m)
 # memory, for n up to 10^6.  nn is the n x m matrix of neighbours -- row i names the EARLIER rows (1-based, 0 = none) that
 # observation i is conditioned on; the rows' order (maxmin, random, by coordinate) and the neighbour search stay with the caller
-# (GpGp::order_maxmin and GpGp::find_ordered_nn give both: nn <- find_ordered_nn(locs[ord, ], m)[, -1]; nn[is.na(nn)] <- 0):
+# (.cocons.hip.vecchia.order and .cocons.hip.vecchia.neighbours below, or GpGp::order_maxmin and GpGp::find_ordered_nn, give both: nn <- find_ordered_nn(locs[ord, ], m)[, -1]; nn[is.na(nn)] <- 0):
 #   fit <- .cocons.hip.vecchia.create(locs[ord, ], x_covariates[ord, ], z[ord, , drop = FALSE], smooth.limits, nn)
 #   optim(..., fn = function(theta) .cocons.hip.vecchia.neg2loglik(fit, theta, par.pos, smooth.limits, n, r, lambda))
 .cocons.hip.vecchia.create <- function(locs, x_covariates, z, smooth.limits, nn, device = -1L) {
@@ -557,6 +557,13 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
 .cocons.hip.vecchia.neighbours <- function(locs, m, newlocs = NULL, device = 0L) {
   if (!is.null(newlocs)) newlocs <- as.matrix(newlocs)
   .Call(`_cocons_hip_vecchia_neighbours`, as.matrix(locs), newlocs, as.integer(m), as.integer(device))
+}
+
+# the maxmin order on the device (DESIGN.md 4w): coarse to fine by nets whose radius halves from level to level, every point
+# at least half as far from its predecessors as the farthest remaining point; a function of locs alone, no seed.
+#   ord <- .cocons.hip.vecchia.order(locs)        # ord[t]: the row at position t
+.cocons.hip.vecchia.order <- function(locs, device = 0L) {
+  .Call(`_cocons_hip_vecchia_order`, as.matrix(locs), as.integer(device))
 }
 
 # .cocons.hip.vecchia.create without nn: the table of .cocons.hip.vecchia.neighbours(locs, m) is searched on the device and

@@ -1072,6 +1072,18 @@ SEXP _cocons_hip_vecchia_neighbours(SEXP locs, SEXP newlocs, SEXP m, SEXP device
     return nn;
 }
 
+/* the maxmin order of the rows of locs (n x 2) found on the device (cocons_vecchia_order): an integer vector, 1-based,
+ * ord[t] the row at position t */
+SEXP _cocons_hip_vecchia_order(SEXP locs, SEXP device)
+{
+    if (!Rf_isReal(locs) || Rf_ncols(locs) != 2) Rf_error("locs must be a double matrix with 2 columns");
+    const int n = Rf_nrows(locs);
+    SEXP ord = PROTECT(Rf_allocVector(INTSXP, n));
+    hip_check(cocons_vecchia_order(n, REAL(locs), Rf_asInteger(device), INTEGER(ord), NULL), "Vecchia order");
+    UNPROTECT(1);
+    return ord;
+}
+
 /* U^-1 W on a Vecchia handle (cocons_vecchia_unwhiten): W is n x c; list(status, the n x c result); theta without `mean` */
 SEXP _cocons_hip_vecchia_unwhiten(SEXP fitp, SEXP theta, SEXP W)
 {
@@ -1304,6 +1316,7 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_vecchia_predict", (DL_FUNC)&_cocons_hip_vecchia_predict, 6},
     {"_cocons_hip_vecchia_fisher", (DL_FUNC)&_cocons_hip_vecchia_fisher, 3},
     {"_cocons_hip_vecchia_neighbours", (DL_FUNC)&_cocons_hip_vecchia_neighbours, 4},
+    {"_cocons_hip_vecchia_order", (DL_FUNC)&_cocons_hip_vecchia_order, 2},
     {"_cocons_hip_vecchia_create_knn", (DL_FUNC)&_cocons_hip_vecchia_create_knn, 6},
     {"_cocons_hip_vecchia_predict_knn", (DL_FUNC)&_cocons_hip_vecchia_predict_knn, 6},
     {"_cocons_hip_vecchia_unwhiten", (DL_FUNC)&_cocons_hip_vecchia_unwhiten, 3},

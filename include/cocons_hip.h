@@ -387,6 +387,35 @@ int cocons_vecchia_predict_knn(cocons_fit *fit, const double *theta, const doubl
                                const double *locs_pred, const double *X_pred, int m_pred,
                                double *stochastic, double *quadform);
 
+/* ---- Maxmin ordering on the device: scale-halving nets ------------------------------------------------------
+ * The order of the observations a Vecchia fit wants: coarse to fine, every point at least half as far from its predecessors
+ * as the farthest remaining point is.  The rule, here and in every reference (d2 as above: fl(fl(dx dx) + fl(dy dy)), fp64,
+ * no contraction, no square root):
+ *  1. Labels, a fixed pseudo-random bijection of the caller's indices 0 .. n - 1 onto 0 .. n - 1: with b the smallest integer
+ *     >= 1 with 2^b >= n, mask = 2^b - 1 and s = (b + 1) / 2 (integer division), mix(v) is three rounds of
+ *     v = (v C_j) & mask; v ^= v >> s, the product in 64 bits, C = 0x9E3779B1, 0x85EBCA6B, 0xC2B2AE35; label(i) is the
+ *     first of mix(i), mix(mix(i)), .. that is below n.  No seed, nothing random at run time.  A lower label is a higher
+ *     priority.
+ *  2. Level 0 is one point: the smallest key (d2(point, c), caller's index), c = (x0 + 0.5 (x1 - x0), y0 + 0.5 (y1 - y0)) the
+ *     centre of the bounding box [x0, x1] x [y0, y1].
+ *  3. Levels k = 1 .. 64: L = max(x1 - x0, y1 - y0), l_k = ldexp(L, 1 - k), e_k = fl(l_k l_k).  Two points conflict at level
+ *     k iff d2 < e_k (strict).  Walk the points not yet ordered in ascending label and take a point iff it conflicts with
+ *     nothing taken so far, at this level or any earlier one.  Inside a level the points stand in ascending label.  A level
+ *     may be empty; the levels stop once every point is ordered.
+ *  4. The rest: what is unordered after level 64 follows in ascending label (coincident points, pairs closer than L 2^-63).
+ * Consequences: order is a permutation; for every position t >= 2 outside the rest, with m_t the smallest d2 from the point at
+ * t to the points before it and M_t the largest such minimum over the points at or behind t, M_t < 4 m_t (e_(k-1) = 4 e_k
+ * exactly while e_k is a normal number); the output is a function of the inputs alone, bit for bit, run to run.
+ *
+ * cocons_vecchia_order: stateless -- host buffers in and out, device memory of the call only.  locs n x 2 column-major.
+ * order: n ints, 1-based: order[t] is the caller's row at position t + 1.  level_counts (may be NULL; room for 67 ints):
+ * [0] = K + 2, the number of records that follow; then the size of level 0 (1), of the levels 1 .. K -- K the last level that
+ * was walked, 0 for n = 1 --, and of the rest.
+ * Refused (-1) before any HIP call, the outputs untouched, with a message that starts with the entry's name: null locs or
+ * order, n < 1, a coordinate that is not finite, and a bounding box whose longer side exceeds 2^511 (d2 and e_1 must not
+ * overflow).  Clustered or near-coincident points cost more rounds and larger cells, never a different bit.                */
+int cocons_vecchia_order(int n, const double *locs, int device, int *order, int *level_counts /* may be NULL: 67 ints */);
+
 /* ---- U^-1 on a Vecchia fit: fields and conditional draws of the Vecchia model -----------------------------
  * Observation i has the neighbours j_1 < .. < j_k, all earlier rows, and the block K = C C' with its rows in the order
  * (j_1 .. j_k, i), exactly as cocons_neg2loglik_vecchia builds it.  With s = C^-T e_last (the vector the gradient and the

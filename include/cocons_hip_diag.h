@@ -63,6 +63,22 @@ int cocons_debug_knn_plan(int n, const double *locs, int level, int m, const dou
  * tools/vecchia_knn_timing.py.  0, or < 0 with the refusals of cocons_vecchia_neighbours under this entry's name.        */
 int cocons_debug_knn_phases(int n, const double *locs, int m, int device, double *ms2);
 
+/* The plan of the maxmin ordering (cocons_vecchia_order) for n points (locs, n x 2 column-major), from the
+ * header the kernels use: labels[i] = label(i) for i = 0 .. n - 1; geom3 = { centre x, centre y, L }; levels2 = 64 pairs
+ * (l_k, e_k), k = 1 .. 64.  Host only: no HIP call.  0, or -1 with the outputs untouched on a null argument, n < 1, a
+ * coordinate that is not finite or a span above 2^511.                                                                   */
+int cocons_debug_order_plan(int n, const double *locs, int *labels, double *geom3, double *levels2);
+
+/* cocons_vecchia_order(n, locs, device, order, level_counts) with its phases timed by events on the call's stream and its
+ * work counted: ms4 = device milliseconds of { the upload and the relabelling, the dense levels' rounds, the binned levels'
+ * binning and rounds, the levels' ends (counts, scan, scatter, the count's way home) }; stats5 = { levels walked, of them on
+ * the dense grid, rounds, kernel launches, host reads of a counter }.  binned_from = 0: the schedule as it is there; k in
+ * 1 .. 64: the binned schedule from level k on, whatever the plan says (the bits do not depend on it).  order and
+ * level_counts may be NULL.  For tools/vecchia_order_timing.py and the tests.  0, or < 0 with the refusals of
+ * cocons_vecchia_order under this entry's name.                                                                          */
+int cocons_debug_order_phases(int n, const double *locs, int device, int binned_from, int *order, int *level_counts,
+                              double *ms4, long long *stats5);
+
 /* cocons_vecchia_unwhiten(fit, theta, c, W, out) with its three phases timed by events on the handle's stream: ms3 = { the
  * records and the coefficient launch with the status word's way home, the schedule (0 when the handle holds it already), the
  * upload of W and the solve's launches }, device milliseconds.  For tools/vecchia_sim_timing.py.  Returns and refusals as
