@@ -72,6 +72,10 @@ SIGNATURES = {
     "cocons_vecchia_unwhiten": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp]),
     "cocons_sim_vecchia": (c_int, [c_vp, c_dp, c_dp, c_int, c_int, c_int, c_dp, c_dp]),
     "cocons_vecchia_schedule": (c_int, [c_vp, c_int, ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_longlong)]),
+    "cocons_vecchia_transpose": (c_int, [c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_longlong)]),
+    "cocons_vecchia_whiten_t": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_dp]),
+    "cocons_cv_vecchia": (c_int, [c_vp, c_dp, c_dp, c_int, ctypes.POINTER(c_int), c_dp, c_dp,
+                                  ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_fit_destroy": (None, [c_vp]),
     "cocons_neg2loglik_dense": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp]),
     "cocons_neg2loglik_grad_dense": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
@@ -149,6 +153,7 @@ DIAG_SIGNATURES = {
     "cocons_debug_order_phases": (c_int, [c_int, c_dp, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_dp,
                                           ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_debug_vecchia_sim_phases": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_dp]),
+    "cocons_debug_vecchia_transpose_phases": (c_int, [c_vp, c_dp]),
     "cocons_debug_taper_selinv": (c_int, [c_vp, c_dp, c_dp, ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_debug_tune": (c_int, [ctypes.c_char_p, c_int]),
     "cocons_debug_dag_replay": (c_int, [c_vp, c_dp, c_dp, c_int, c_dp]),

@@ -108,7 +108,7 @@ static int sim_schedule(cocons_fit *f, const char *who, int n_fixed)
 
 // The coefficients of the rows n_fixed .. n - 1 for theta into S->coef and the status word home: 0, the smallest failing
 // 1-based row, or < 0
-static int sim_coefs(cocons_fit *f, const char *who, const double *theta, int n_fixed)
+int vecchia_sim_coefs(cocons_fit *f, const char *who, const double *theta, int n_fixed)
 {
     VecchiaState *V = f->vecchia.get();
     if (!V->sim) V->sim.reset(new VecchiaSimState());
@@ -153,7 +153,7 @@ static int sim_impl(const char *who, cocons_fit *f, const double *theta, const d
     double hmean[COCONS_P_MAX] = {};
     if (mean) for (int i = 0; i < f->p; ++i) hmean[i] = canon_nan(mean[i]);
     marks.mark(0);
-    if (int st = sim_coefs(f, who, theta, n_fixed)) return st;
+    if (int st = vecchia_sim_coefs(f, who, theta, n_fixed)) return st;
     marks.mark(1);
     marks.mark(2);
     if (int rc = sim_schedule(f, who, n_fixed)) return rc;

@@ -15,6 +15,7 @@
 // Taper handles by folds: cv_fold_kernel reads a fold's K_BB from a block of its own (base, + sign) instead of -S.
 // The only atomic is the record of a failing fold (atomicMin of its label, as the factorisation's info word).
 #include "kernels.h"
+#include "cv_fold_tail.hpp"
 #include <atomic>
 
 namespace cocons {
@@ -60,12 +61,12 @@ template <int BP> __global__ void __launch_bounds__(256)
 cv_fold_kernel(CvFoldArgs a)
 {
     extern __shared__ double cv_lds[];
-    constexpr int LD = BP + 1, G = 256 / BP;
+    constexpr int LD = BP + 1;
     double *M = cv_lds, *dinv = M + (size_t)LD * BP, *ub = dinv + BP, *yb = ub + 256;
     const int f = a.flist[blockIdx.x];
     const int *pos = a.idx + a.off[f];
     const int b = a.off[f + 1] - a.off[f];
-    const int tid = threadIdx.x, i = tid % BP, g = tid / BP;
+    const int tid = threadIdx.x;
     if (b < 1 || b > BP) return;                       // (the host's size classes: never)
     // gather: K(i, j) = -S(max, min); positions ascend inside a fold, so row >= column is the stored triangle
     for (int e = tid; e < b * b; e += 256) {
@@ -74,57 +75,7 @@ cv_fold_kernel(CvFoldArgs a)
             M[rr + cc * LD] = a.base ? a.S[(size_t)a.base[f] + (size_t)rr + (size_t)cc * a.lds]
                                      : -a.S[(size_t)pos[rr] + (size_t)pos[cc] * a.lds];
     }
-    // C C' = K_BB, right-looking, column by column
-    bool bad = false;
-    for (int j = 0; j < b; ++j) {
-        __syncthreads();
-        double d = M[j + j * LD];
-        if (!(d > 0.0) || !isfinite(d)) { bad = true; d = 1.0; }
-        const double piv = sqrt(d);
-        if (tid == 0) dinv[j] = 1.0 / piv;
-        if (g == 0 && i > j && i < b) M[i + j * LD] /= piv;
-        __syncthreads();
-        if (i > j && i < b) {
-            const double lij = M[i + j * LD];
-            for (int c = j + 1 + g; c <= i; c += G) M[i + c * LD] -= lij * M[c + j * LD];
-        }
-    }
-    __syncthreads();
-    // W = C^-1: W(r, j) = -(sum_{k = r-1 .. j} C(r, k) W(k, j)) / C(r, r), W(j, j) = 1 / C(j, j)
-    if (tid < b) {
-        const int j = tid;
-        const double wjj = dinv[j];
-        for (int r = j + 1; r < b; ++r) {
-            double s = 0.0;
-            for (int k = r - 1; k > j; --k) s += M[r + k * LD] * M[j + k * LD];
-            s += M[r + j * LD] * wjj;
-            M[j + r * LD] = -s * dinv[r];
-        }
-        // var_j = sum_{k >= j} W(k, j)^2
-        double v = wjj * wjj;
-        for (int k = j + 1; k < b; ++k) v += M[j + k * LD] * M[j + k * LD];
-        a.var[pos[j]] = v;
-    }
-    // resid = W' (W U_B), G realisations at a time
-    for (int c0 = 0; c0 < a.nr; c0 += G) {
-        const int c = c0 + g;
-        const bool on = c < a.nr && i < b;
-        __syncthreads();
-        if (on) ub[g * BP + i] = a.U[(size_t)pos[i] + (size_t)c * a.ldu];
-        __syncthreads();
-        if (on) {
-            double y = 0.0;
-            for (int k = 0; k < i; ++k) y += M[k + i * LD] * ub[g * BP + k];      // W(i, k) at (k, i)
-            y += dinv[i] * ub[g * BP + i];
-            yb[g * BP + i] = y;
-        }
-        __syncthreads();
-        if (on) {
-            double e = dinv[i] * yb[g * BP + i];
-            for (int k = i + 1; k < b; ++k) e += M[i + k * LD] * yb[g * BP + k];  // W(k, i) at (i, k)
-            a.res[(size_t)pos[i] + (size_t)c * a.ldr] = e;
-        }
-    }
+    const bool bad = cv_fold_tail<BP>(M, dinv, ub, yb, b, pos, a.U, a.ldu, a.nr, a.var, a.res, a.ldr);
     if (bad && tid == 0) atomicMin(a.fail, a.lab[f]);
 }
 

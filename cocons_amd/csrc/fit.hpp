@@ -271,6 +271,17 @@ struct VecchiaSimState {
     long long bytes() const { return schedule_bytes() + (long long)(coef.count() * sizeof(double)); }
 };
 
+// U' of a Vecchia fit (api_vecchia_cv.hip): the transposed lists of the table -- a function of the table alone,
+// built by the first call that needs them and kept for the handle's life.
+struct VecchiaCvState {
+    bool built = false;
+    DevBuf<int> ptr;              // n + 1 offsets: list(j) = rows[ptr[j] .. ptr[j + 1])
+    DevBuf<int> rows;             // entries: the rows that name j, ascending (0-based)
+    DevBuf<unsigned char> place;  // entries: the place of j in that row of the table
+    long long entries = 0, longest = 0, unnamed = 0;
+    long long bytes() const { return (long long)((ptr.count() + rows.count()) * sizeof(int) + place.count()); }
+};
+
 // What makes a handle a Vecchia handle (cocons_fit_create_vecchia, api_vecchia.hip): the neighbour table and the
 // scratch of one evaluation, O(n (m + r + 16)) bytes.  Such a handle has no factorisation buffer at all.
 struct VecchiaState {
@@ -296,9 +307,11 @@ struct VecchiaState {
     std::unique_ptr<PatternGridBufs> knn;
     // cocons_vecchia_unwhiten, cocons_sim_vecchia, cocons_vecchia_schedule, made by their first call
     std::unique_ptr<VecchiaSimState> sim;
+    // cocons_vecchia_transpose, cocons_vecchia_whiten_t, cocons_cv_vecchia, made by their first call
+    std::unique_ptr<VecchiaCvState> cv;
     long long bytes() const
     {
-        return (knn ? knn->bytes : 0) + (sim ? sim->bytes() : 0) +
+        return (knn ? knn->bytes : 0) + (sim ? sim->bytes() : 0) + (cv ? cv->bytes() : 0) +
                (long long)(nbr.count() * sizeof(int) +
                            (aos.count() + aos2.count() + B.count() + W.count() + part.count() + gsite.count() + gaos.count() +
                             grec.count() + gpart.count() + gout.count() + fdirs.count() + frec.count() + fpart.count() +
@@ -736,6 +749,9 @@ int vecchia_predict_impl(const char *who, cocons_fit *f, const double *theta, co
 int vecchia_only(cocons_fit *f, const char *who);
 ModeSel vecchia_records(cocons_fit *f, const double *theta, int which, double *aos);
 int vecchia_status(cocons_fit *f, const char *who);
+// ... and what api_vecchia_sim.hip offers api_vecchia_cv.hip: the coefficients of the rows n_fixed .. n - 1 for
+// theta into the handle's sim->coef and the status word home: 0, the smallest failing 1-based row, or < 0
+int vecchia_sim_coefs(cocons_fit *f, const char *who, const double *theta, int n_fixed);
 // ... and what they call in api_shard.hip: the sharded cocons_neg2loglik_dense, and cocons_fit_destroy's share
 int sharded_eval(cocons_fit *f, const double *theta, const double *mean, double *sum_logliks, double *parts);
 void shard_events_destroy(ShardState *S);

@@ -789,4 +789,44 @@ void launch_vecchia_sim_fused(const VecchiaSimArgs &a, int lv0, int lv1, hipStre
 void launch_vecchia_sim_ends(bool fixed, int n, int p, int n_fixed, int c, const double *X, int ldx_design, const double *mean,
                              const double *z, double *x, size_t ldx, double *out, size_t ldo, hipStream_t s);
 
+// ---- U' of a Vecchia fit and cross-validation from Q = U'U (vecchia_cv.hip) -------------------------------------
+// The transposed lists: list(j) = the rows k > j whose table row names j, ascending, at rows[ptr[j] .. ptr[j + 1]) (0-based);
+// place[e] = the place of j in row rows[e] of the table, so that U(k, j) = coef[k (m + 1) + place[e]].
+constexpr int VECCHIA_T_WAVE = 64;      // a list of at most this many rows is sorted by one wavefront in registers
+constexpr int VECCHIA_T_LDS = 4096;     // ... of at most this many by one workgroup in LDS; a longer one in memory (bitonic)
+constexpr int VECCHIA_T_SCAN = 1024;    // counts per workgroup of the scan's first stage
+// cnt[j] += 1 for every entry of the table that names j (cnt zeroed by the caller; integer atomics)
+void launch_vecchia_t_count(const int *nbr, int m, int n, int *cnt, hipStream_t s);
+// ptr[0 .. n] = the exclusive prefix sums of cnt[0 .. n) in three launches (bsum: (n + VECCHIA_T_SCAN - 1) / VECCHIA_T_SCAN
+// ints); the last one also leaves stat = {longest list, columns nobody names, lists of VECCHIA_T_WAVE + 1 .. VECCHIA_T_LDS
+// rows, longer lists} (zeroed by the caller) with those lists' columns in mid and big (any order), and cnt zeroed again
+void launch_vecchia_t_scan(int *cnt, int n, int *ptr, int *bsum, int *stat, int *mid, int *big, hipStream_t s);
+// rows[ptr[j] + cursor[j]++] = i for every entry of row i that names j (cursor zeroed: the order inside a list is the atomics')
+void launch_vecchia_t_fill(const int *nbr, int m, int n, const int *ptr, int *cursor, int *rows, hipStream_t s);
+// every list ascending: one wavefront per column for the short ones, then nmid and nbig workgroups for the listed columns
+void launch_vecchia_t_sort(int n, const int *ptr, int *rows, const int *mid, int nmid, const int *big, int nbig, hipStream_t s);
+// place[e] for every entry (a binary search of row i in the sorted list of the column it names)
+void launch_vecchia_t_place(const int *nbr, int m, int n, const int *ptr, const int *rows, unsigned char *place, hipStream_t s);
+struct VecchiaTArgs {
+    int n = 0, m = 0;
+    const int *nbr = nullptr, *ptr = nullptr, *rows = nullptr;
+    const unsigned char *place = nullptr;
+    const double *coef = nullptr;        // launch_vecchia_coefs' records
+};
+// Y[i + q ldy] = sum_t coef[i (m + 1) + t] B[nbr[i m + t] + q ldb] + coef[i (m + 1) + m] B[i + q ldb], t ascending, one thread
+void launch_vecchia_umul(const VecchiaTArgs &a, int c, const double *B, size_t ldb, double *Y, size_t ldy, hipStream_t s);
+// out[j + q ldo] = (U'W)(j, q) for q < c and qdiag[j] = (U'U)(j, j) (qdiag may be null): one wavefront per column j; lane l
+// sums the entries l, l + 64, .. of list(j) in ascending order -- lane 0 starts from the own row's term --, then the 64
+// partial sums meet in a butterfly of fixed shape.  A column's result does not depend on c.
+void launch_vecchia_ut(const VecchiaTArgs &a, int c, const double *W, size_t ldw, double *out, size_t ldo, double *qdiag,
+                       hipStream_t s);
+// observations alone in their fold: var = 1 / qdiag, resid = uty var; idx, lab null: the observations 0 .. count - 1
+void launch_vecchia_cv_single(const double *qdiag, const double *uty, size_t ldu, int nr, const int *idx, const int *lab,
+                              int count, double *var, double *res, size_t ldr, int *fail, hipStream_t s);
+// folds of 2 .. CV_SMALL_MAX observations, one workgroup each (launch_cv_folds' plan and size classes): Q_BB built in LDS
+// from the rows of U -- inv[i] = where observation i stands in idx --, then cv_fold_tail with U_B = uty
+hipError_t launch_vecchia_cv_folds(int cls, const VecchiaTArgs &a, const int *inv, const double *uty, size_t ldu, int nr,
+                                   const int *idx, const int *off, const int *flist, const int *lab, int nfolds, double *var,
+                                   double *res, size_t ldr, int *fail, hipStream_t s);
+
 }  // namespace cocons

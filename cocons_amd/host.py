@@ -1686,6 +1686,45 @@ class CoconsVecchiaFit(_Handle):
         _lib.check(self._L.cocons_vecchia_schedule(self._h, int(n_fixed), _ip(levels), out), "cocons_vecchia_schedule")
         return {"levels": levels, "depth": int(out[0]), "widest": int(out[1]), "launches": int(out[2]), "bytes": int(out[3])}
 
+    def transpose(self):
+        """The transposed lists of the handle's table (cocons_vecchia_transpose): {"ptr": n + 1 int32 0-based
+        offsets, "rows": the 1-based rows that name column j at rows[ptr[j]:ptr[j + 1]], ascending, "entries", "longest":
+        the longest list, "bytes": device bytes of the lists, "unnamed": columns nobody names}.  Built by the first call that
+        needs them and kept by the handle (`info()["bytes"]` counts them)."""
+        out = (ctypes.c_longlong * 4)()
+        _lib.check(self._L.cocons_vecchia_transpose(self._h, None, None, out), "cocons_vecchia_transpose")
+        ptr = np.zeros(self.n + 1, dtype=np.int32)
+        rows = np.zeros(int(out[0]), dtype=np.int32)
+        _lib.check(self._L.cocons_vecchia_transpose(self._h, _ip(ptr), _ip(rows) if rows.size else None, out),
+                   "cocons_vecchia_transpose")
+        return {"ptr": ptr, "rows": rows, "entries": int(out[0]), "longest": int(out[1]), "bytes": int(out[2]),
+                "unnamed": int(out[3])}
+
+    def whiten_t_core(self, theta_list, W):
+        """(U'W, diag(U'U)) for the columns of W (n x c, the caller's order): the transpose of `whiten_core`'s U, applied
+        through the transposed lists in a fixed order (cocons_vecchia_whiten_t).  A column's result does not depend on c."""
+        T = theta_table(theta_list)
+        W = _f(np.asarray(W, dtype=np.float64).reshape(self.n, -1))
+        out, qd = np.zeros(W.shape, order="F"), np.zeros(self.n)
+        _lib.check(self._L.cocons_vecchia_whiten_t(self._h, _p(T), int(W.shape[1]), _p(W), _p(out), _p(qd)),
+                   "cocons_vecchia_whiten_t")
+        return out, qd
+
+    def cv_core(self, theta_list, fold=None, stats=False):
+        """Cross-validated predictions of the Vecchia model from Q = U'U (cocons_cv_vecchia).  `fold`: n integer labels in
+        [0, nfold), every fold of at most 128 observations (None: leave-one-out).  Returns (resid n x r, var n) as
+        `CoconsFit.cv_core`; with `stats` also {"singles", "folds", "entries", "bytes": device bytes of the call}."""
+        T, mean = _table_mean(theta_list)
+        resid = np.zeros((self.n, self.r), order="F")
+        var = np.zeros(self.n)
+        nfold, lab = (0, None) if fold is None else _fold_labels(fold, self.n)
+        st = (ctypes.c_longlong * 4)()
+        _lib.check(self._L.cocons_cv_vecchia(self._h, _p(T), _p(mean), nfold, None if lab is None else _ip(lab), _p(resid),
+                                             _p(var), st), "cocons_cv_vecchia")
+        if stats:
+            return resid, var, {"singles": int(st[0]), "folds": int(st[1]), "entries": int(st[2]), "bytes": int(st[3])}
+        return resid, var
+
     def info(self):
         """{"n", "m", "bytes": device bytes the handle holds, "rows": rows per chunk of predict_core}"""
         out = (ctypes.c_longlong * 4)()
@@ -1856,6 +1895,25 @@ def cocoSim_vecchia(theta_list, locs, X_std, smooth_limits, iiderrors, nn=None, 
 
     with _borrowed(fit, make) as f, _chol_error():
         return f.sim_core(theta_list, np.asarray(iiderrors, dtype=np.float64).reshape(n, -1))
+
+
+def cocoCV_vecchia(theta_list, locs, X_std, smooth_limits, z, nn=None, m=None, fold=None, fit=None):
+    """Cross-validated predictions of the Vecchia model at `theta_list` from its precision U'U (cocons_cv_vecchia): no refit
+    and no n x n matrix.  `fold`: one label of any kind per observation, every fold of at most 128 observations (None:
+    leave-one-out).  The table is `nn`, or with `m` the m nearest earlier rows found on the device; `fit` (optional) a
+    CoconsVecchiaFit over the same data.  Returns what `cocoCV_dense` returns; with every predecessor in the table, its
+    numbers.  A failing block raises CholeskyError."""
+    if fit is None and (nn is None) == (m is None):
+        raise ValueError("cocoCV_vecchia: give a neighbour table nn, a number of neighbours m, or a fit")
+    lab = None if fold is None else np.unique(np.asarray(fold).ravel(), return_inverse=True)[1]
+
+    def make():
+        if nn is not None:
+            return CoconsVecchiaFit(locs, X_std, z, smooth_limits, nn)
+        return CoconsVecchiaFit.from_knn(locs, X_std, z, smooth_limits, m)
+
+    with _borrowed(fit, make) as f:
+        return _cv_result(f, z, *f.cv_core(theta_list, lab))
 
 
 def cocoSim_cond_vecchia(theta_list, locs, newlocs, X_std, X_pred_std, smooth_limits, z, iiderrors, m, fit=None):

@@ -610,3 +610,30 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
   res <- .Call(`_cocons_hip_vecchia_schedule`, fit, as.integer(n_fixed))
   list(levels = res[[1]], info = res[[2]])
 }
+
+# U' and cross-validation on a Vecchia handle (DESIGN.md 4x): the model's precision is U'U, applied through the transposed
+# lists of the table ("which rows name me"), which the handle builds once on the device.
+# .cocons.hip.vecchia.transpose: list(ptr, rows, info = c(entries, longest list, device bytes, columns nobody names)) -- the
+# rows that name column j are rows[(ptr[j] + 1):ptr[j + 1]], ascending
+.cocons.hip.vecchia.transpose <- function(fit) {
+  res <- .Call(`_cocons_hip_vecchia_transpose`, fit)
+  list(ptr = res[[1]], rows = res[[2]], info = res[[3]])
+}
+
+# U'W for the n x c matrix W and diag(U'U): list(out, qdiag)
+.cocons.hip.vecchia.whiten.t <- function(fit, theta_list, W) {
+  W <- as.matrix(W)
+  storage.mode(W) <- "double"
+  res <- .Call(`_cocons_hip_vecchia_whiten_t`, fit, theta_list[names(theta_list) != "mean"], W)
+  if (res[[1]] > 0L) stop("Cholesky error")
+  list(out = res[[2]][[1]], qdiag = res[[2]][[2]])
+}
+
+# cross-validated predictions of the Vecchia model (cocons_cv_vecchia): what .cocons.hip.cv returns, from U'U -- no refit and
+# no n x n matrix.  fold: one label of any kind per observation, every fold of at most 128 observations (NULL: leave-one-out)
+.cocons.hip.vecchia.cv <- function(fit, theta_list, fold = NULL, safe = TRUE) {
+  if (!is.null(fold)) fold <- match(fold, unique(fold)) - 1L
+  res <- .cocons.hip.result(.Call(`_cocons_hip_vecchia_cv`, fit, theta_list, fold), safe)
+  if (is.null(res)) return(NULL)
+  list(resid = res[[1]], var = res[[2]], stats = res[[3]])
+}

@@ -1146,6 +1146,92 @@ SEXP _cocons_hip_vecchia_schedule(SEXP fitp, SEXP n_fixed)
     return out;
 }
 
+/* the transposed lists of a Vecchia handle's table (cocons_vecchia_transpose): list(ptr = n + 1 integers, 0-based offsets,
+ * rows = the 1-based rows that name column j at rows[ptr[j] + 1 .. ptr[j + 1]], ascending, info = c(entries, longest list,
+ * device bytes of the lists, columns nobody names)) */
+SEXP _cocons_hip_vecchia_transpose(SEXP fitp)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int n = fit_n(fitp);
+    long long o4[4] = {0, 0, 0, 0};
+    hip_check(cocons_vecchia_transpose(f, NULL, NULL, o4), "Vecchia transpose");
+    SEXP ptr = PROTECT(Rf_allocVector(INTSXP, (R_xlen_t)n + 1));
+    SEXP rows = PROTECT(Rf_allocVector(INTSXP, (R_xlen_t)o4[0]));
+    for (R_xlen_t e = 0; e < XLENGTH(ptr); ++e) INTEGER(ptr)[e] = 0;
+    for (R_xlen_t e = 0; e < XLENGTH(rows); ++e) INTEGER(rows)[e] = 0;
+    hip_check(cocons_vecchia_transpose(f, INTEGER(ptr), o4[0] > 0 ? INTEGER(rows) : NULL, o4), "Vecchia transpose");
+    SEXP info = PROTECT(Rf_allocVector(REALSXP, 4));
+    for (int i = 0; i < 4; ++i) REAL(info)[i] = (double)o4[i];
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 3));
+    SET_VECTOR_ELT(out, 0, ptr);
+    SET_VECTOR_ELT(out, 1, rows);
+    SET_VECTOR_ELT(out, 2, info);
+    UNPROTECT(4);
+    return out;
+}
+
+/* U'W and diag(U'U) on a Vecchia handle (cocons_vecchia_whiten_t): W is n x c; list(status, list(the n x c result, the n
+ * diagonal entries)); theta without `mean` */
+SEXP _cocons_hip_vecchia_whiten_t(SEXP fitp, SEXP theta, SEXP W)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), n = fit_n(fitp);
+    if (!Rf_isReal(W) || !Rf_isMatrix(W) || Rf_nrows(W) != n) Rf_error("W must be a double matrix with %d rows", n);
+    const int c = Rf_ncols(W);
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    SEXP v = PROTECT(Rf_allocMatrix(REALSXP, n, c));
+    SEXP q = PROTECT(Rf_allocVector(REALSXP, n));
+    for (R_xlen_t e = 0; e < XLENGTH(v); ++e) REAL(v)[e] = NA_REAL;
+    for (R_xlen_t e = 0; e < XLENGTH(q); ++e) REAL(q)[e] = NA_REAL;
+    int rc = cocons_vecchia_whiten_t(f, T, c, REAL(W), REAL(v), REAL(q));
+    hip_check(rc, "Vecchia whiten (transposed)");
+    SEXP res = PROTECT(Rf_allocVector(VECSXP, 2));
+    SET_VECTOR_ELT(res, 0, v);
+    SET_VECTOR_ELT(res, 1, q);
+    SEXP out = status_value(rc, res);
+    UNPROTECT(3);
+    return out;
+}
+
+/* cross-validated predictions of the Vecchia model (cocons_cv_vecchia): theta is the WHOLE theta_list (`mean` read by name),
+ * fold NULL (leave-one-out) or n integer labels from 0; list(status, list(resid n x r, var n, stats = c(folds of one, folds
+ * of 2 .. 128, entries, device bytes of the call))) */
+SEXP _cocons_hip_vecchia_cv(SEXP fitp, SEXP theta, SEXP fold)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), n = fit_n(fitp), r = fit_r(fitp);
+    int nfold = 0;
+    const int *lab = NULL;
+    if (!Rf_isNull(fold)) {
+        if (!Rf_isInteger(fold) || XLENGTH(fold) != (R_xlen_t)n) Rf_error("fold must be NULL or %d integer labels", n);
+        lab = INTEGER(fold);
+        for (int i = 0; i < n; ++i)
+            if (lab[i] + 1 > nfold) nfold = lab[i] + 1;
+        if (nfold < 1) nfold = 1;
+    }
+    SEXP mean = list_get(theta, "mean");
+    if (!Rf_isReal(mean) || XLENGTH(mean) != p) Rf_error("theta$mean must be a double vector of length %d", p);
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    long long s4[4] = {0, 0, 0, 0};
+    SEXP resid = PROTECT(Rf_allocMatrix(REALSXP, n, r > 0 ? r : 1));
+    SEXP var = PROTECT(Rf_allocVector(REALSXP, n));
+    for (R_xlen_t e = 0; e < XLENGTH(resid); ++e) REAL(resid)[e] = NA_REAL;
+    for (R_xlen_t e = 0; e < XLENGTH(var); ++e) REAL(var)[e] = NA_REAL;
+    int rc = cocons_cv_vecchia(f, T, REAL(mean), nfold, lab, REAL(resid), REAL(var), s4);
+    hip_check(rc, "cross-validation (Vecchia)");
+    SEXP stats = PROTECT(Rf_allocVector(REALSXP, 4));
+    for (int i = 0; i < 4; ++i) REAL(stats)[i] = (double)s4[i];
+    SEXP res = PROTECT(Rf_allocVector(VECSXP, 3));
+    SET_VECTOR_ELT(res, 0, resid);
+    SET_VECTOR_ELT(res, 1, var);
+    SET_VECTOR_ELT(res, 2, stats);
+    SEXP out = status_value(rc, res);
+    UNPROTECT(4);
+    return out;
+}
+
 /* kriging from a held band factor on a taper handle: factor S(theta) once for realization z_col (1-based) and keep the band
  * factor on the handle; max_rows = 0: the library's default chunk.  list(status, NULL) -- status > 0: the failing minor */
 SEXP _cocons_hip_krige_taper_prepare(SEXP fitp, SEXP theta, SEXP mean, SEXP z_col, SEXP max_rows)
@@ -1322,6 +1408,9 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_vecchia_unwhiten", (DL_FUNC)&_cocons_hip_vecchia_unwhiten, 3},
     {"_cocons_hip_vecchia_sim", (DL_FUNC)&_cocons_hip_vecchia_sim, 5},
     {"_cocons_hip_vecchia_schedule", (DL_FUNC)&_cocons_hip_vecchia_schedule, 2},
+    {"_cocons_hip_vecchia_transpose", (DL_FUNC)&_cocons_hip_vecchia_transpose, 1},
+    {"_cocons_hip_vecchia_whiten_t", (DL_FUNC)&_cocons_hip_vecchia_whiten_t, 3},
+    {"_cocons_hip_vecchia_cv", (DL_FUNC)&_cocons_hip_vecchia_cv, 3},
     {"_cocons_hip_fit_close", (DL_FUNC)&_cocons_hip_fit_close, 1},
     {"_cocons_hip_neg2loglik_parts", (DL_FUNC)&_cocons_hip_neg2loglik_parts, 3},
     {"_cocons_hip_neg2loglik", (DL_FUNC)&_cocons_hip_neg2loglik, 3},

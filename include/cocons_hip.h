@@ -446,6 +446,54 @@ int cocons_sim_vecchia(cocons_fit *fit, const double *theta, const double *mean,
  * solve of one column under the current COCONS_VECCHIA_SIM_FUSE, device bytes of the schedule and of the coefficients of a solve}.       */
 int cocons_vecchia_schedule(cocons_fit *fit, int n_fixed, int *levels /* n, may be NULL */, long long *out4);
 
+/* ---- U' on a Vecchia fit and cross-validation from Q = U'U -------------------------------------------------
+ * The Vecchia model's precision is Q = U'U, U the sparse whitening above.  For a held-out set B with complement A and
+ * R = z - X mean, the identities of cocons_cv_dense hold with K = Q:
+ *     R_B - E[R_B | R_A] = (Q_BB)^-1 (Q R)_B,      Cov(R_B | R_A) = (Q_BB)^-1.
+ * Q is never formed.  Definitions every entry below follows:
+ *   Coefficients.  Row i of U holds s = C^-T e_last of the row's block: U(i, j_t) = s_t for the neighbour at place t of the
+ *     handle's ascending table, U(i, i) = s_last.
+ *   Transposed lists.  list(j) = the rows k (all > j) whose table row names j, in ascending k; a row names an index at most
+ *     once, so k is unique within a list.  entries = the number of non-zero table entries.  The lists are a function of the
+ *     table alone: built once per handle on the device by the first call that needs them, kept on the handle, counted by
+ *     cocons_vecchia_info and freed with the handle.
+ *   y = U b is formed from the rows' coefficients: y_i = sum_t s_t b_{j_t} + s_last b_i, t ascending, one thread, no
+ *     contraction -- the formula of cocons_vecchia_unwhiten's text.  It need not be cocons_vecchia_whiten's bits, which come
+ *     from a forward substitution through the block's factor.
+ *   (U'w)_j = s_last(j) w_j + sum_{k in list(j)} U(k, j) w_k,     Q_jj = s_last(j)^2 + sum_{k in list(j)} U(k, j)^2.
+ *     The order of summation is a fixed function of the list alone: one wavefront serves a column, lane l sums the entries
+ *     l, l + 64, .. of the list in ascending order -- lane 0 starts from the own row's term --, and the 64 partial sums meet
+ *     in a butterfly of fixed shape.  No floating-point atomics anywhere.
+ *   Fold block.  For a fold B with members ascending, Q_BB[a, b] = sum_k U(k, a) U(k, b) over the rows k that hold both
+ *     columns, in ascending k, the own row of the later index first.
+ * Determinism: repeated calls agree to the bit; a fold's outputs depend on its members alone -- not on the labels, not on how
+ * the other observations are grouped; a fold of one returns leave-one-out's bits; the outputs of cocons_vecchia_whiten_t do
+ * not depend on c; no other Vecchia entry returns other bits before or after these calls, in any order.
+ *
+ * cocons_vecchia_transpose: ptr (n + 1 ints, may be NULL) the 0-based offsets of the lists, rows (entries ints, may be NULL)
+ * the 1-based rows, ascending inside a list; out4 = {entries, longest list, device bytes of the lists, columns nobody names}.
+ * A call with both NULL sizes the buffers.                                                                                */
+int cocons_vecchia_transpose(cocons_fit *fit, int *ptr /* n + 1, may be NULL */, int *rows /* entries, may be NULL */,
+                             long long *out4);
+/* out (n x c) = U'W for W n x c column-major in the caller's order, qdiag (n, may be NULL) = diag(U'U).  Refused (-1) before
+ * any device work, outputs untouched, the entry's name in front: a null argument, c < 1, a handle that is not a Vecchia
+ * handle.  A failing block returns its smallest 1-based row and nothing is written.                                       */
+int cocons_vecchia_whiten_t(cocons_fit *fit, const double *theta, int c, const double *W, double *out /* n x c: U'W */,
+                            double *qdiag /* n: diag(U'U), may be NULL */);
+/* Cross-validated predictions of the Vecchia model: fold, nfold, resid (n x r), var (n), the return codes and "outputs are
+ * written on 0 only" as cocons_cv_dense; fold = NULL with nfold = 0 is leave-one-out; labels nobody carries are allowed;
+ * R = z - X mean as cocons_neg2loglik_vecchia forms it.  An observation alone in its fold: var = 1 / Q_jj, resid =
+ * (U'U R)_j var.  A fold of 2 .. 128 observations: one workgroup builds Q_BB in LDS and runs cocons_cv_dense's block
+ * arithmetic on it.  stats4 (may be NULL) = {folds of one, folds of 2 .. 128, entries, device bytes the call allocated}.
+ * Returns 0, the smallest failing 1-based block row (nothing written), -5 when a Q_BB is not positive definite in floating
+ * point (the message names the fold), < 0 with cocons_last_error() otherwise.  Refused (-1) before any device work, outputs
+ * untouched, the entry's name in front: a null argument, nfold < 0, fold and nfold that disagree, a label outside
+ * [0, nfold), a fold that holds all n observations (leave-one-out at n = 1 is answered: resid = z - X mean, var = Sigma_11),
+ * a fold of more than 128 observations -- a larger Q_BB is a sparse system of its own; a handle over the complement and
+ * cocons_vecchia_predict_knn is the route for such folds --, a handle that is not a Vecchia handle.                       */
+int cocons_cv_vecchia(cocons_fit *fit, const double *theta, const double *mean, int nfold, const int *fold,
+                      double *resid /* n x r */, double *var /* n */, long long *stats4 /* may be NULL */);
+
 /* ---- fit handle: everything that is constant over an optimisation -------------
  * Created once per cocoOptim / getHessian call from the arguments the reference
  * passes unchanged to every GetNeg2loglikelihood* evaluation

@@ -86,6 +86,11 @@ int cocons_debug_order_phases(int n, const double *locs, int device, int binned_
 int cocons_debug_vecchia_sim_phases(struct cocons_fit *fit, const double *theta, int c, const double *W, double *out,
                                     double *ms3);
 
+/* The transposed lists of a Vecchia handle's table (cocons_vecchia_transpose) built anew, whether the handle holds them or
+ * not, with the build's phases timed by events on the handle's stream: ms4 = { in-degree counts, the scan, the fill, the
+ * sorts and the places }, device milliseconds.  For tools/vecchia_cv_timing.py.                                          */
+int cocons_debug_vecchia_transpose_phases(struct cocons_fit *fit, double *ms4);
+
 /* Diagnostics of cocons_neg2loglik_grad_taper: (S(theta)^-1)_ij at every stored entry of the pattern the taper handle was
  * created with, in the caller's CSR order (out_nnz: one double per entry of that pattern), by the gradient's selected
  * inverse; bytes_out (may be NULL): the device bytes the gradient holds on the handle.  0, a failing minor k > 0, or < 0. */
