@@ -74,6 +74,16 @@ SIGNATURES = {
     "cocons_vecchia_schedule": (c_int, [c_vp, c_int, ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_vecchia_transpose": (c_int, [c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_vecchia_whiten_t": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_dp]),
+    "cocons_vecchia_group": (c_int, [c_int, c_int, ctypes.POINTER(c_int), c_int, ctypes.POINTER(c_int),
+                                     ctypes.POINTER(ctypes.c_longlong)]),
+    "cocons_vecchia_group_table": (c_int, [c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int,
+                                           ctypes.POINTER(c_int)]),
+    "cocons_vecchia_set_groups": (c_int, [c_vp, ctypes.POINTER(c_int)]),
+    "cocons_vecchia_groups_info": (c_int, [c_vp, ctypes.POINTER(ctypes.c_longlong)]),
+    "cocons_fit_create_vecchia_grouped": (c_vp, [c_int, c_int, c_int, c_dp, c_dp, c_dp, c_dp, c_int, c_int, ctypes.POINTER(c_int),
+                                                 c_int]),
+    "cocons_neg2loglik_vecchia_grouped": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp]),
+    "cocons_vecchia_whiten_grouped": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_dp]),
     "cocons_cv_vecchia": (c_int, [c_vp, c_dp, c_dp, c_int, ctypes.POINTER(c_int), c_dp, c_dp,
                                   ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_fit_destroy": (None, [c_vp]),

@@ -282,6 +282,22 @@ struct VecchiaCvState {
     long long bytes() const { return (long long)((ptr.count() + rows.count()) * sizeof(int) + place.count()); }
 };
 
+// Grouped blocks of a Vecchia fit (api_vecchia_group.hip): the plan of cocons_vecchia_set_groups on the device --
+// group_plan.hpp's GroupPlan --, replaced by a second call.
+struct VecchiaGroupState {
+    DevBuf<int> off;              // blocks + 1 offsets into rows
+    DevBuf<int> rows;             // every block's rows, ascending (0-based)
+    DevBuf<int> order;            // the blocks largest first: the sequence a launch deals them in
+    DevBuf<unsigned long long> mask;   // per block: bit p = the row at position p is a member
+    int blocks = 0, maxrows = 0;
+    bool by_size = true;          // deal the blocks in `order` (COCONS_VECCHIA_GROUP_ORDER=0: by block id)
+    long long sum_rows = 0, pairs = 0;
+    long long bytes() const
+    {
+        return (long long)((off.count() + rows.count() + order.count()) * sizeof(int) + mask.count() * sizeof(unsigned long long));
+    }
+};
+
 // What makes a handle a Vecchia handle (cocons_fit_create_vecchia, api_vecchia.hip): the neighbour table and the
 // scratch of one evaluation, O(n (m + r + 16)) bytes.  Such a handle has no factorisation buffer at all.
 struct VecchiaState {
@@ -309,9 +325,11 @@ struct VecchiaState {
     std::unique_ptr<VecchiaSimState> sim;
     // cocons_vecchia_transpose, cocons_vecchia_whiten_t, cocons_cv_vecchia, made by their first call
     std::unique_ptr<VecchiaCvState> cv;
+    // cocons_vecchia_set_groups: the plan of the grouped value and whitening
+    std::unique_ptr<VecchiaGroupState> grp;
     long long bytes() const
     {
-        return (knn ? knn->bytes : 0) + (sim ? sim->bytes() : 0) + (cv ? cv->bytes() : 0) +
+        return (knn ? knn->bytes : 0) + (sim ? sim->bytes() : 0) + (cv ? cv->bytes() : 0) + (grp ? grp->bytes() : 0) +
                (long long)(nbr.count() * sizeof(int) +
                            (aos.count() + aos2.count() + B.count() + W.count() + part.count() + gsite.count() + gaos.count() +
                             grec.count() + gpart.count() + gout.count() + fdirs.count() + frec.count() + fpart.count() +

@@ -753,6 +753,27 @@ void launch_vecchia_final_sums(const double *part, int nseg, int ncol, double *o
 size_t vecchia_sum_scratch_doubles(int n, int ncol);
 void launch_vecchia_sums(const double *v, size_t ldv, int n, int ncol, double *part, double *out, hipStream_t s);
 
+// ---- grouped Vecchia blocks: one factorisation for a group of rows (vecchia_group.hip) -------------------------
+// The plan of group_plan.hpp on the device: block b holds the rows rows[off[b] .. off[b + 1]) (at most 64 and at most kb,
+// 0-based, ascending), bit p of mask[b] says whether the row at position p is a member; workgroup w of the launch takes block
+// order[w] (order null: block w).  Every member i gets logd[i] (logd may be null) and Y[i + c ldy] for the nb columns of B as
+// launch_vecchia_blocks gives them on the table whose row i is the block's rows in front of i -- the same bits.  A pivot that
+// is not positive and finite at position q: atomicMin(*fail, row + 1) for the first member at a position >= q, nothing written
+// for the block.
+constexpr int VECCHIA_GROUP_THREADS = 256;     // threads of a block's workgroup: the first 64 are its rows, all evaluate pairs
+struct VecchiaGroupArgs {
+    int blocks = 0, kb = 0;            // kb: the plan's largest block, what the launch's LDS is sized by
+    const int *off = nullptr, *rows = nullptr, *order = nullptr;
+    const unsigned long long *mask = nullptr;
+    const double *aosK = nullptr;
+    double gr = 0.0, nu_fixed = 0.0;
+    const double *B = nullptr; size_t ldb = 0; int nb = 0;
+    double *Y = nullptr; size_t ldy = 0;
+    double *logd = nullptr;
+    int *fail = nullptr;
+};
+void launch_vecchia_group_blocks(int mode, const VecchiaGroupArgs &a, hipStream_t s);
+
 // ---- U^-1 of a Vecchia fit: coefficients, levels and the level solve (vecchia_sim.hip) -------------------------
 constexpr int VECCHIA_SIM_FUSE_ITEMS = 256;     // a level of at most this many (row, column) pairs may join a fused run
 constexpr int VECCHIA_SIM_FUSE_THREADS = 256;   // the one workgroup of a fused run

@@ -320,8 +320,9 @@ def _tapered(fit, locs, x_covariates, z, smooth_limits, ref_taper):
     return _borrowed(fit, lambda: CoconsTaperFit(locs, x_covariates, z, smooth_limits, *ref_taper))
 
 
-def _vecchia(fit, locs, x_covariates, z, smooth_limits, nn):
-    return _borrowed(fit, lambda: CoconsVecchiaFit(locs, x_covariates, z, smooth_limits, nn))
+def _vecchia(fit, locs, x_covariates, z, smooth_limits, nn, grouped=False):
+    make = CoconsVecchiaFit.from_groups if grouped else CoconsVecchiaFit
+    return _borrowed(fit, lambda: make(locs, x_covariates, z, smooth_limits, nn))
 
 
 @contextlib.contextmanager
@@ -1528,6 +1529,43 @@ def vecchia_order_device(locs, device=0, levels=False):
     return (order, counts[1:1 + counts[0]].copy()) if levels else order
 
 
+def vecchia_group(nn, max_rows=64, stats=False):
+    """The greedy grouping of the rows of the neighbour table `nn` (cocons_vecchia_group; Guinness 2018): n
+    int32 block ids, 0-based, numbered by their smallest member.  Rows are visited in ascending order; for each neighbour j of
+    row i, in the order the row lists them, the blocks of i and j are merged when the union u of their row sets S (members and
+    all their neighbours) has u <= max_rows and u^2 < |S(A)|^2 + |S(B)|^2.  With `stats` also {"blocks", "rows": the sum of
+    |S|, "pairs": what the grouped schedule evaluates, "pairs_ungrouped": what the ungrouped schedule evaluates on nn}.  The
+    rule runs on the host; nothing here needs a device."""
+    L = _lib.load()
+    nn = np.asarray(nn)
+    nn, m = _nn_table(nn, nn.shape[0])
+    group = np.zeros(nn.shape[0], dtype=np.int32)
+    out = (ctypes.c_longlong * 4)()
+    _lib.check(L.cocons_vecchia_group(nn.shape[0], m, _ip(nn), int(max_rows), _ip(group), out), "cocons_vecchia_group")
+    if stats:
+        return group, {"blocks": int(out[0]), "rows": int(out[1]), "pairs": int(out[2]), "pairs_ungrouped": int(out[3])}
+    return group
+
+
+def vecchia_group_table(nn, group, m_out=None) -> np.ndarray:
+    """The expanded table of ANY partition `group` of nn's rows (cocons_vecchia_group_table): row i names every earlier row of
+    S(block(i)) -- its own neighbours and those of the block's other members --, n x m_out int32 in Fortran order, 1-based,
+    ascending, zero padded; m_out None: the longest expanded row (at least 1).  The grouped model is the ordinary Vecchia
+    model on this table."""
+    L = _lib.load()
+    nn = np.asarray(nn)
+    nn, m = _nn_table(nn, nn.shape[0])
+    n = nn.shape[0]
+    group = np.ascontiguousarray(np.asarray(group, dtype=np.int32).reshape(n))
+    if m_out is None:
+        m_out = L.cocons_vecchia_group_table(n, m, _ip(nn), _ip(group), 0, None)
+        _lib.check(min(m_out, 0), "cocons_vecchia_group_table")
+        m_out = max(m_out, 1)
+    out = np.zeros((n, int(m_out)), dtype=np.int32, order="F")
+    _lib.check(L.cocons_vecchia_group_table(n, m, _ip(nn), _ip(group), int(m_out), _ip(out)), "cocons_vecchia_group_table")
+    return out
+
+
 class CoconsVecchiaFit(_Handle):
     """Handle of a Vecchia fit (cocons_fit_create_vecchia): (locs, x_covariates, z, smooth.limits) and the neighbour table
     `nn` (n x m, 1-based indices of EARLIER rows, 0 = none; `vecchia_neighbours` makes one).  The rows' order is the Vecchia
@@ -1561,6 +1599,34 @@ class CoconsVecchiaFit(_Handle):
         self.maxmin_order = order
         return self
 
+    @classmethod
+    def from_groups(cls, locs, x_covariates, z, smooth_limits, nn, max_rows=64, device=-1):
+        """The handle of the grouped model of the table `nn` (cocons_fit_create_vecchia_grouped): the greedy
+        groups of `vecchia_group(nn, max_rows)`, the handle of `vecchia_group_table(nn, groups)` and `set_groups(groups)` in
+        one call.  Every core serves the model of the expanded table; `neg2loglik_core(theta, grouped=True)` and
+        `whiten_grouped_core` run the grouped schedule."""
+        self = cls.__new__(cls)
+        locs, X, z = self._adopt(locs, x_covariates, z, smooth_limits)
+        nn, m = _nn_table(nn, self.n)
+        self._created(self._L.cocons_fit_create_vecchia_grouped(self.n, self.p, self.r, _p(locs), _p(X), _p(z),
+                                                                _p(self.smooth_limits), int(device), m, _ip(nn),
+                                                                int(max_rows)), "cocons_fit_create_vecchia_grouped")
+        self.m = self.info()["m"]
+        return self
+
+    def set_groups(self, group):
+        """Attach the plan of the partition `group` (n block labels) to the handle (cocons_vecchia_set_groups).  The handle's
+        table must be closed under it -- `vecchia_group_table` makes such a table --; a second call replaces the plan.
+        Returns {"blocks", "maxrows", "rows", "pairs", "bytes"} of the plan."""
+        group = np.ascontiguousarray(np.asarray(group, dtype=np.int32).reshape(self.n))
+        _lib.check(self._L.cocons_vecchia_set_groups(self._h, _ip(group)), "cocons_vecchia_set_groups")
+        return self.groups_info()
+
+    def groups_info(self):
+        out = (ctypes.c_longlong * 5)()
+        _lib.check(self._L.cocons_vecchia_groups_info(self._h, out), "cocons_vecchia_groups_info")
+        return {"blocks": int(out[0]), "maxrows": int(out[1]), "rows": int(out[2]), "pairs": int(out[3]), "bytes": int(out[4])}
+
     def to_maxmin(self, rows):
         """A per-row array in the caller's order (n or n x c) in the handle's order (`from_maxmin`)"""
         return np.asarray(rows)[self.maxmin_order.astype(np.int64) - 1]
@@ -1578,14 +1644,15 @@ class CoconsVecchiaFit(_Handle):
         self._created(self._L.cocons_fit_create_vecchia(self.n, self.p, self.r, _p(locs), _p(X), _p(z), _p(self.smooth_limits),
                                                         int(device), self.m, _ip(nn)), "cocons_fit_create_vecchia")
 
-    def neg2loglik_core(self, theta_list):
+    def neg2loglik_core(self, theta_list, grouped=False):
         """(value, parts): parts[0] = sum_i log d_i, parts[1 + k] = sum_i y_ik^2, value = sum_k [n log 2 pi + 2 parts[0] +
-        parts[1 + k]].  CholeskyError(i): the block of row i has a conditional variance that is not positive."""
+        parts[1 + k]].  CholeskyError(i): the block of row i has a conditional variance that is not positive.  `grouped`:
+        on the plan of `set_groups`, one factorisation per block (cocons_neg2loglik_vecchia_grouped) -- the same bits."""
         T, mean = _table_mean(theta_list)
         val = ctypes.c_double(0.0)
         parts = np.zeros(1 + self.r)
-        _lib.check(self._L.cocons_neg2loglik_vecchia(self._h, _p(T), _p(mean), ctypes.byref(val), _p(parts)),
-                   "cocons_neg2loglik_vecchia")
+        entry = "cocons_neg2loglik_vecchia_grouped" if grouped else "cocons_neg2loglik_vecchia"
+        _lib.check(getattr(self._L, entry)(self._h, _p(T), _p(mean), ctypes.byref(val), _p(parts)), entry)
         return val.value, parts
 
     def neg2loglik_grad_core(self, theta_list, B=None):
@@ -1623,14 +1690,21 @@ class CoconsVecchiaFit(_Handle):
         _lib.check(self._L.cocons_fisher_vecchia(self._h, _p(T), nd, _p(D), _p(info), _p(info_mean)), "cocons_fisher_vecchia")
         return info, info_mean
 
-    def whiten_core(self, theta_list, B):
-        """(U B, log d) for the columns of B (n x c, the caller's order): U'U is the approximation's Sigma^-1."""
+    def _whiten(self, theta_list, B, entry):
         T = theta_table(theta_list)
         B = _f(np.asarray(B, dtype=np.float64).reshape(self.n, -1))
         out, logd = np.zeros(B.shape, order="F"), np.zeros(self.n)
-        _lib.check(self._L.cocons_vecchia_whiten(self._h, _p(T), int(B.shape[1]), _p(B), _p(out), _p(logd)),
-                   "cocons_vecchia_whiten")
+        _lib.check(getattr(self._L, entry)(self._h, _p(T), int(B.shape[1]), _p(B), _p(out), _p(logd)), entry)
         return out, logd
+
+    def whiten_core(self, theta_list, B):
+        """(U B, log d) for the columns of B (n x c, the caller's order): U'U is the approximation's Sigma^-1."""
+        return self._whiten(theta_list, B, "cocons_vecchia_whiten")
+
+    def whiten_grouped_core(self, theta_list, B):
+        """`whiten_core` on the plan of `set_groups`, one factorisation per block (cocons_vecchia_whiten_grouped): the same
+        bits.  (A method of its own: `whiten_core`'s signature is part of the layer's contract.)"""
+        return self._whiten(theta_list, B, "cocons_vecchia_whiten_grouped")
 
     def predict_core(self, theta_list, locs_pred, x_covariates_pred, nn_pred, z_col=0):
         """Local kriging: (stochastic, quadform) of cocons_vecchia_predict for the neighbour table nn_pred (mp x m_pred,
@@ -1732,19 +1806,21 @@ class CoconsVecchiaFit(_Handle):
         return {"n": int(out[0]), "m": int(out[1]), "bytes": int(out[2]), "rows": int(out[3])}
 
 
-def GetNeg2loglikelihoodVecchia(theta, par_pos, nn, locs, x_covariates, smooth_limits, z, n, lam, safe=True, fit=None):
+def GetNeg2loglikelihoodVecchia(theta, par_pos, nn, locs, x_covariates, smooth_limits, z, n, lam, safe=True, fit=None,
+                                grouped=False):
     """GetNeg2loglikelihood (R/neg2loglikelihood.R:183-222) with the Vecchia approximation of the likelihood for the neighbour
-    table `nn`; `fit` (optional) a CoconsVecchiaFit built once from the same data and table."""
-    return _objective(theta, par_pos, lam, smooth_limits, safe, _vecchia(fit, locs, x_covariates, z, smooth_limits, nn),
-                      lambda f, tl: f.neg2loglik_core(tl)[0], n)
+    table `nn`; `fit` (optional) a CoconsVecchiaFit built once from the same data and table.  `grouped`: the grouped model of
+    `nn` on the grouped schedule (`fit` then a handle of `CoconsVecchiaFit.from_groups` or one with a plan)."""
+    return _objective(theta, par_pos, lam, smooth_limits, safe, _vecchia(fit, locs, x_covariates, z, smooth_limits, nn, grouped),
+                      lambda f, tl: f.neg2loglik_core(tl, grouped=grouped)[0], n)
 
 
-def _vecchia_gls(f, tl, z, x_betas):
+def _vecchia_gls(f, tl, z, x_betas, grouped=False):
     """One whitening of [z | x_betas]: (sum log d, W = Xb' U'U Xb, the r quadratic forms z_k' P z_k with
     P = U'U - U'U Xb W^-1 Xb' U'U)."""
     z = np.asarray(z, dtype=np.float64).reshape(f.n, -1)
     xb = np.asarray(x_betas, dtype=np.float64).reshape(f.n, -1)
-    UB, logd = f.whiten_core(tl, np.hstack([z, xb]))
+    UB, logd = (f.whiten_grouped_core if grouped else f.whiten_core)(tl, np.hstack([z, xb]))
     Uz, UX = UB[:, :z.shape[1]], UB[:, z.shape[1]:]
     W = UX.T @ UX
     g = UX.T @ Uz
@@ -1753,29 +1829,29 @@ def _vecchia_gls(f, tl, z, x_betas):
 
 
 def GetNeg2loglikelihoodVecchiaProfile(theta, par_pos, nn, locs, x_covariates, smooth_limits, z, n, x_betas, lam,
-                                       safe=True, fit=None):
-    """R/neg2loglikelihood.R:127-165 with Sigma^-1 replaced by U'U."""
+                                       safe=True, fit=None, grouped=False):
+    """R/neg2loglikelihood.R:127-165 with Sigma^-1 replaced by U'U; `grouped` as in GetNeg2loglikelihoodVecchia."""
     def core(f, tl):
-        logdet, _, quad = _vecchia_gls(f, tl, z, x_betas)
+        logdet, _, quad = _vecchia_gls(f, tl, z, x_betas, grouped)
         return float(np.sum(n * np.log(2 * np.pi) + 2 * logdet + quad))
 
-    return _objective(theta, par_pos, lam, smooth_limits, safe, _vecchia(fit, locs, x_covariates, z, smooth_limits, nn),
+    return _objective(theta, par_pos, lam, smooth_limits, safe, _vecchia(fit, locs, x_covariates, z, smooth_limits, nn, grouped),
                       core, n)
 
 
 def GetNeg2loglikelihoodVecchiaREML(theta, par_pos, nn, locs, x_covariates, x_betas, smooth_limits, z, n, lam,
-                                    safe=True, fit=None):
+                                    safe=True, fit=None, grouped=False):
     """R/neg2loglikelihood.R:241-291 with Sigma^-1 replaced by U'U (x_betas is accepted and, as in the reference, unused:
-    the restricted likelihood projects out x_covariates)."""
+    the restricted likelihood projects out x_covariates); `grouped` as in GetNeg2loglikelihoodVecchia."""
     X = np.asarray(x_covariates, dtype=np.float64)
     rank = int(np.linalg.matrix_rank(X))                    # qr(x)$rank, :270
 
     def core(f, tl):
-        logdet, W, quad = _vecchia_gls(f, tl, z, X)
+        logdet, W, quad = _vecchia_gls(f, tl, z, X, grouped)
         logdet_w = float(np.sum(np.log(np.diag(np.linalg.cholesky(W)))))
         return float(np.sum((n - rank) * np.log(2 * np.pi) + 2 * logdet + 2 * logdet_w + quad))
 
-    return _objective(theta, par_pos, lam, smooth_limits, safe, _vecchia(fit, locs, x_covariates, z, smooth_limits, nn),
+    return _objective(theta, par_pos, lam, smooth_limits, safe, _vecchia(fit, locs, x_covariates, z, smooth_limits, nn, grouped),
                       core, n - rank)
 
 

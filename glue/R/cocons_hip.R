@@ -629,6 +629,49 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
   list(out = res[[2]][[1]], qdiag = res[[2]][[2]])
 }
 
+# Grouped Vecchia blocks (DESIGN.md 4y; Guinness 2018, GpGp's group_obs): rows with overlapping neighbour sets share one block,
+# which is assembled and factored once.  Every member then conditions on a superset of its own neighbours: the grouped model is
+# the Vecchia model of the EXPANDED table, and the grouped entries return the bits of the ungrouped ones on that table's handle.
+#   g <- .cocons.hip.vecchia.group(nn)                                   # greedy groups of the table (on the host)
+#   wide <- .cocons.hip.vecchia.group.table(nn, g$group)                 # row i: every earlier row of its block
+#   fit <- .cocons.hip.vecchia.create(locs, x_covariates, z, smooth.limits, wide)
+#   .cocons.hip.vecchia.set.groups(fit, g$group)
+#   optim(..., fn = function(theta) .cocons.hip.vecchia.neg2loglik.grouped(fit, theta, par.pos, smooth.limits, n, r, lambda))
+# .cocons.hip.vecchia.group: list(group = block ids from 0, numbered by their smallest member, info = c(blocks, rows over the
+# blocks, pairs of the grouped schedule, pairs of the ungrouped schedule on nn)); max_rows in 2 .. 64 caps the rows of a block
+.cocons.hip.vecchia.group <- function(nn, max_rows = 64L) {
+  res <- .Call(`_cocons_hip_vecchia_group`, as.matrix(nn), as.integer(max_rows))
+  list(group = res[[1]], info = res[[2]])
+}
+
+# the expanded table of ANY partition of nn's rows (labels in 0 .. n - 1): an integer matrix, 1-based, ascending, 0 = none
+.cocons.hip.vecchia.group.table <- function(nn, group) {
+  .Call(`_cocons_hip_vecchia_group_table`, as.matrix(nn), as.integer(group))
+}
+
+# attach the plan of a partition to a Vecchia handle whose table is closed under it (the library checks and names the first
+# row that is not): c(blocks, rows of the largest block, rows over the blocks, pairs, device bytes of the plan)
+.cocons.hip.vecchia.set.groups <- function(fit, group) {
+  .Call(`_cocons_hip_vecchia_set_groups`, fit, as.integer(group))
+}
+
+# .cocons.hip.vecchia.neg2loglik on the grouped schedule: the same value to the bit, one factorisation per block
+.cocons.hip.vecchia.neg2loglik.grouped <- function(fit, theta, par.pos, smooth.limits, n, r, lambda, safe = TRUE) {
+  theta_list <- getModelLists(theta = theta, par.pos = par.pos, type = "diff")
+  v <- .cocons.hip.result(.Call(`_cocons_hip_vecchia_neg2loglik_grouped`, fit, theta_list[-1], theta_list$mean), safe)
+  if (is.null(v)) return(1e+06)
+  v[1] + .cocons.getPen(n * r, lambda, theta_list, smooth.limits)
+}
+
+# U W for the n x c matrix W and log d on the grouped schedule: list(out, logd)
+.cocons.hip.vecchia.whiten.grouped <- function(fit, theta_list, W) {
+  W <- as.matrix(W)
+  storage.mode(W) <- "double"
+  res <- .Call(`_cocons_hip_vecchia_whiten_grouped`, fit, theta_list[names(theta_list) != "mean"], W)
+  if (res[[1]] > 0L) stop("Cholesky error")
+  list(out = res[[2]][[1]], logd = res[[2]][[2]])
+}
+
 # cross-validated predictions of the Vecchia model (cocons_cv_vecchia): what .cocons.hip.cv returns, from U'U -- no refit and
 # no n x n matrix.  fold: one label of any kind per observation, every fold of at most 128 observations (NULL: leave-one-out)
 .cocons.hip.vecchia.cv <- function(fit, theta_list, fold = NULL, safe = TRUE) {

@@ -1194,6 +1194,104 @@ SEXP _cocons_hip_vecchia_whiten_t(SEXP fitp, SEXP theta, SEXP W)
     return out;
 }
 
+/* grouped Vecchia blocks.  The greedy groups of the n x m neighbour matrix nn (cocons_vecchia_group; integer, or
+ * double after arithmetic): list(group = n integer block ids from 0, info = c(blocks, rows over the blocks, pairs of the
+ * grouped schedule, pairs of the ungrouped schedule on nn)) */
+SEXP _cocons_hip_vecchia_group(SEXP nn, SEXP max_rows)
+{
+    if (!Rf_isMatrix(nn) || Rf_nrows(nn) < 1) Rf_error("nn must be a matrix with one row per observation");
+    const int n = Rf_nrows(nn);
+    R_xlen_t len = 0;
+    const int *tab = as_int_copy(nn, &len);
+    long long o4[4] = {0, 0, 0, 0};
+    SEXP group = PROTECT(Rf_allocVector(INTSXP, n));
+    for (int i = 0; i < n; ++i) INTEGER(group)[i] = 0;
+    hip_check(cocons_vecchia_group(n, Rf_ncols(nn), tab, Rf_asInteger(max_rows), INTEGER(group), o4), "Vecchia groups");
+    SEXP info = PROTECT(Rf_allocVector(REALSXP, 4));
+    for (int i = 0; i < 4; ++i) REAL(info)[i] = (double)o4[i];
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 2));
+    SET_VECTOR_ELT(out, 0, group);
+    SET_VECTOR_ELT(out, 1, info);
+    UNPROTECT(3);
+    return out;
+}
+
+/* the expanded table of any partition of nn's rows (cocons_vecchia_group_table): group holds n integer labels in 0 .. n - 1;
+ * an integer matrix of as many columns as the longest expanded row (at least one), 1-based, ascending, 0 = none */
+SEXP _cocons_hip_vecchia_group_table(SEXP nn, SEXP group)
+{
+    if (!Rf_isMatrix(nn) || Rf_nrows(nn) < 1) Rf_error("nn must be a matrix with one row per observation");
+    const int n = Rf_nrows(nn);
+    if (!Rf_isInteger(group) || XLENGTH(group) != (R_xlen_t)n) Rf_error("group must be %d integer labels", n);
+    R_xlen_t len = 0;
+    const int *tab = as_int_copy(nn, &len);
+    int longest = cocons_vecchia_group_table(n, Rf_ncols(nn), tab, INTEGER(group), 0, NULL);
+    if (longest < 0) Rf_error("%s", cocons_last_error());
+    if (longest < 1) longest = 1;
+    SEXP wide = PROTECT(Rf_allocMatrix(INTSXP, n, longest));
+    for (R_xlen_t e = 0; e < XLENGTH(wide); ++e) INTEGER(wide)[e] = 0;
+    hip_check(cocons_vecchia_group_table(n, Rf_ncols(nn), tab, INTEGER(group), longest, INTEGER(wide)), "Vecchia group table");
+    UNPROTECT(1);
+    return wide;
+}
+
+/* the plan of a partition on a Vecchia handle whose table is closed under it (cocons_vecchia_set_groups): c(blocks, rows of
+ * the largest block, rows over the blocks, pairs, device bytes of the plan) */
+SEXP _cocons_hip_vecchia_set_groups(SEXP fitp, SEXP group)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int n = fit_n(fitp);
+    if (!Rf_isInteger(group) || XLENGTH(group) != (R_xlen_t)n) Rf_error("group must be %d integer labels", n);
+    long long o5[5] = {0, 0, 0, 0, 0};
+    hip_check(cocons_vecchia_set_groups(f, INTEGER(group)), "Vecchia groups");
+    hip_check(cocons_vecchia_groups_info(f, o5), "Vecchia groups");
+    SEXP info = PROTECT(Rf_allocVector(REALSXP, 5));
+    for (int i = 0; i < 5; ++i) REAL(info)[i] = (double)o5[i];
+    UNPROTECT(1);
+    return info;
+}
+
+/* _cocons_hip_vecchia_neg2loglik on the grouped schedule (cocons_neg2loglik_vecchia_grouped): the same list, the same bits */
+SEXP _cocons_hip_vecchia_neg2loglik_grouped(SEXP fitp, SEXP theta, SEXP mean)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), r = fit_r(fitp);
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    if (XLENGTH(mean) != p) Rf_error("theta$mean must have length %d", p);
+    SEXP v = PROTECT(Rf_allocVector(REALSXP, 2 + r));
+    for (int i = 0; i < 2 + r; ++i) REAL(v)[i] = NA_REAL;
+    int rc = cocons_neg2loglik_vecchia_grouped(f, T, REAL(mean), REAL(v), REAL(v) + 1);
+    hip_check(rc, "GetNeg2loglikelihoodVecchia (grouped)");
+    SEXP out = status_value(rc, v);
+    UNPROTECT(1);
+    return out;
+}
+
+/* U W and log d on the grouped schedule (cocons_vecchia_whiten_grouped): W is n x c; list(status, list(the n x c result, the
+ * n values log d)); theta without `mean` */
+SEXP _cocons_hip_vecchia_whiten_grouped(SEXP fitp, SEXP theta, SEXP W)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), n = fit_n(fitp);
+    if (!Rf_isReal(W) || !Rf_isMatrix(W) || Rf_nrows(W) != n) Rf_error("W must be a double matrix with %d rows", n);
+    const int c = Rf_ncols(W);
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    SEXP v = PROTECT(Rf_allocMatrix(REALSXP, n, c));
+    SEXP q = PROTECT(Rf_allocVector(REALSXP, n));
+    for (R_xlen_t e = 0; e < XLENGTH(v); ++e) REAL(v)[e] = NA_REAL;
+    for (R_xlen_t e = 0; e < XLENGTH(q); ++e) REAL(q)[e] = NA_REAL;
+    int rc = cocons_vecchia_whiten_grouped(f, T, c, REAL(W), REAL(v), REAL(q));
+    hip_check(rc, "Vecchia whiten (grouped)");
+    SEXP res = PROTECT(Rf_allocVector(VECSXP, 2));
+    SET_VECTOR_ELT(res, 0, v);
+    SET_VECTOR_ELT(res, 1, q);
+    SEXP out = status_value(rc, res);
+    UNPROTECT(3);
+    return out;
+}
+
 /* cross-validated predictions of the Vecchia model (cocons_cv_vecchia): theta is the WHOLE theta_list (`mean` read by name),
  * fold NULL (leave-one-out) or n integer labels from 0; list(status, list(resid n x r, var n, stats = c(folds of one, folds
  * of 2 .. 128, entries, device bytes of the call))) */
@@ -1411,6 +1509,11 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_vecchia_transpose", (DL_FUNC)&_cocons_hip_vecchia_transpose, 1},
     {"_cocons_hip_vecchia_whiten_t", (DL_FUNC)&_cocons_hip_vecchia_whiten_t, 3},
     {"_cocons_hip_vecchia_cv", (DL_FUNC)&_cocons_hip_vecchia_cv, 3},
+    {"_cocons_hip_vecchia_group", (DL_FUNC)&_cocons_hip_vecchia_group, 2},
+    {"_cocons_hip_vecchia_group_table", (DL_FUNC)&_cocons_hip_vecchia_group_table, 2},
+    {"_cocons_hip_vecchia_set_groups", (DL_FUNC)&_cocons_hip_vecchia_set_groups, 2},
+    {"_cocons_hip_vecchia_neg2loglik_grouped", (DL_FUNC)&_cocons_hip_vecchia_neg2loglik_grouped, 3},
+    {"_cocons_hip_vecchia_whiten_grouped", (DL_FUNC)&_cocons_hip_vecchia_whiten_grouped, 3},
     {"_cocons_hip_fit_close", (DL_FUNC)&_cocons_hip_fit_close, 1},
     {"_cocons_hip_neg2loglik_parts", (DL_FUNC)&_cocons_hip_neg2loglik_parts, 3},
     {"_cocons_hip_neg2loglik", (DL_FUNC)&_cocons_hip_neg2loglik, 3},

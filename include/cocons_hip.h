@@ -494,6 +494,47 @@ int cocons_vecchia_whiten_t(cocons_fit *fit, const double *theta, int c, const d
 int cocons_cv_vecchia(cocons_fit *fit, const double *theta, const double *mean, int nfold, const int *fold,
                       double *resid /* n x r */, double *var /* n */, long long *stats4 /* may be NULL */);
 
+/* ---- grouped Vecchia blocks: one factorisation for a group of rows ------------------------------------------
+ * A block B is a set of member rows; S(B) is the union of its members and all their table neighbours, at most 64 rows.  The
+ * member at position p of S(B) (ascending) conditions on the positions 0 .. p - 1: a superset of its own neighbours.  The
+ * grouped model is therefore an ordinary Vecchia model on the EXPANDED table (m <= 63), and a handle made from that table
+ * serves every Vecchia entry; the grouped entries below assemble and factor each block once and return the bits of the
+ * ungrouped entries on the same handle.
+ *
+ * cocons_vecchia_group: the greedy rule on the host (Guinness 2018; GpGp's group_obs).  nn: n x m column-major, 1-based,
+ * 0 = none, earlier rows only, m in 1 .. 63 (cocons_fit_create_vecchia's rules, checked); max_rows in 2 .. 64.  Every row
+ * starts as a block of its own; the rows are visited in ascending order and, for each neighbour j of row i in the order the
+ * row lists them (zeros skipped), the blocks A of i and B of j are merged when A != B, u = |S(A) u S(B)| <= max_rows and
+ * u^2 < |S(A)|^2 + |S(B)|^2 -- integers only.  group[n]: 0-based block ids, numbered by their smallest member, ascending.
+ * out4 (may be NULL) = {blocks, sum of |S| over the blocks, sum of |S| (|S| - 1) / 2 (the pairs the grouped schedule
+ * evaluates), sum over the rows of (k + 1) k / 2 for k neighbours (the pairs of the ungrouped schedule on nn)}.             */
+int cocons_vecchia_group(int n, int m, const int *nn, int max_rows, int *group, long long *out4);
+/* The expanded table of ANY partition `group` (labels in 0 .. n - 1) of nn's rows: nn_out is n x m_out column-major, 1-based,
+ * ascending, zero padded.  m_out = 0 with nn_out = NULL asks for the longest expanded row alone, which is returned (>= 0);
+ * otherwise 0.  Refused (-1, the entry's name in front): a table that breaks the rules, a block with |S| > 64 (its smallest
+ * member is named), m_out smaller than the longest expanded row or outside 1 .. 63.                                        */
+int cocons_vecchia_group_table(int n, int m, const int *nn, const int *group, int m_out, int *nn_out);
+/* Attach the plan of the partition `group` (n labels in 0 .. n - 1) to a Vecchia handle.  The handle's table must be CLOSED
+ * under it: every member's stored row equals {s in S(block) : s < i}, and |S| <= 64; checked on the host before any device
+ * work on the plan -- the table is downloaded once for the check, so a handle of cocons_fit_create_vecchia_knn is served as
+ * well.  Refused with -1, the entry's name and the first offending row otherwise.  The plan lives on the handle, counts in
+ * cocons_vecchia_info's bytes and is replaced by a second call.  COCONS_VECCHIA_GROUP_ORDER=0 (read here) deals the blocks to
+ * the workgroups by block id instead of largest first; no bit of any output depends on it.                                 */
+int cocons_vecchia_set_groups(cocons_fit *fit, const int *group);
+/* {blocks, rows of the largest block, sum of |S|, pairs, device bytes of the plan} of the handle's plan                    */
+int cocons_vecchia_groups_info(cocons_fit *fit, long long *out5);
+/* cocons_vecchia_group, cocons_vecchia_group_table, cocons_fit_create_vecchia on the expanded table and
+ * cocons_vecchia_set_groups in one call; the other arguments as cocons_fit_create_vecchia.  NULL with cocons_last_error().  */
+cocons_fit *cocons_fit_create_vecchia_grouped(int n, int p, int r, const double *locs, const double *X, const double *z,
+                                              const double *smooth_limits, int device, int m, const int *nn, int max_rows);
+/* cocons_neg2loglik_vecchia and cocons_vecchia_whiten on the grouped schedule: the same arguments, the same return codes --
+ * the smallest failing 1-based row included --, outputs written on 0 only, and THE SAME BITS in value, parts, every whitened
+ * value and every log d.  Refused (-1): a handle without a plan (cocons_vecchia_set_groups attaches one).                   */
+int cocons_neg2loglik_vecchia_grouped(cocons_fit *fit, const double *theta, const double *mean, double *value,
+                                      double *parts /* 1 + r, may be NULL */);
+int cocons_vecchia_whiten_grouped(cocons_fit *fit, const double *theta, int c, const double *B /* n x c */,
+                                  double *out /* n x c */, double *logd /* n, may be NULL */);
+
 /* ---- fit handle: everything that is constant over an optimisation -------------
  * Created once per cocoOptim / getHessian call from the arguments the reference
  * passes unchanged to every GetNeg2loglikelihood* evaluation
