@@ -84,6 +84,7 @@ SIGNATURES = {
                                                  c_int]),
     "cocons_neg2loglik_vecchia_grouped": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp]),
     "cocons_vecchia_whiten_grouped": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_dp]),
+    "cocons_neg2loglik_grad_vecchia_grouped": (c_int, [c_vp, c_dp, c_dp, c_int, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "cocons_cv_vecchia": (c_int, [c_vp, c_dp, c_dp, c_int, ctypes.POINTER(c_int), c_dp, c_dp,
                                   ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_fit_destroy": (None, [c_vp]),

@@ -175,11 +175,13 @@ extern "C" int cocons_neg2loglik_vecchia(cocons_fit *f, const double *theta, con
 // Value and gradient from one launch per chunk of VECCHIA_GRAD_CHUNK observations.  The value's totals are
 // launch_vecchia_sums over log d and the whitened columns of all n rows -- the value entry's tree over the value kernel's
 // numbers --, the gradient's the same tree over the per-observation records, its first stage run chunk by chunk.
-extern "C" int cocons_neg2loglik_grad_vecchia(cocons_fit *f, const double *theta, const double *mean, int c, const double *B,
-                                              double *sum_logliks, double *parts, double *grad_theta, double *grad_quad,
-                                              double *grad_mean)
+//
+// grouped (cocons_neg2loglik_grad_vecchia_grouped): the same arguments, refusals, scratch, value totals and host
+// tail; the launches run over the plan's blocks -- one record per block, chunks and segments of blocks -- instead.
+int vecchia_grad_impl(const char *who, bool grouped, cocons_fit *f, const double *theta, const double *mean, int c,
+                      const double *B, double *sum_logliks, double *parts, double *grad_theta, double *grad_quad,
+                      double *grad_mean)
 {
-    const char *who = "cocons_neg2loglik_grad_vecchia";
     if (!f) return fail(-1, "%s: null fit handle", who);
     if (!theta || !sum_logliks || !grad_theta || (!B && (!mean || !grad_mean))) return fail(-1, "%s: null argument", who);
     if (B && (mean || grad_mean))
@@ -187,9 +189,11 @@ extern "C" int cocons_neg2loglik_grad_vecchia(cocons_fit *f, const double *theta
     if (B && c < 1) return fail(-1, "%s: c = %d (at least one column expected)", who, c);
     FIT_ENTER_ANY(f);
     if (int rc = vecchia_only(f, who)) return rc;
+    if (grouped) if (int rc = vecchia_need_plan(f, who)) return rc;
     VecchiaState *V = f->vecchia.get();
     const int n = f->n, p = f->p, nc = B ? c : f->r, ncol = vecchia_rec_cols(p);
-    const int nseg = (n + VECCHIA_SUM_SEG - 1) / VECCHIA_SUM_SEG, chunk = std::min(n, VECCHIA_GRAD_CHUNK);
+    const int units = grouped ? V->grp->blocks : n;           // what a record stands for: a block, or an observation
+    const int nseg = (units + VECCHIA_SUM_SEG - 1) / VECCHIA_SUM_SEG, chunk = std::min(units, VECCHIA_GRAD_CHUNK);
     hipStream_t s = f->stream;
     HIPCHK_AT(who, V->B.reserve((size_t)n * nc, s, nullptr));
     HIPCHK_AT(who, V->W.reserve((size_t)n * (1 + nc), s, nullptr));
@@ -212,18 +216,21 @@ extern "C" int cocons_neg2loglik_grad_vecchia(cocons_fit *f, const double *theta
     launch_grad_site(loc_args(n, p, f->dX, f->dlocs, V->gsite, f->npad, tv, ms.smooth_kind, f->smooth_limits), V->gsite,
                      f->npad, smooth_free, s);
     launch_vecchia_site_rec(V->gsite, f->npad, n, V->gaos, s);
-    VecchiaArgs a;
-    a.m = V->m; a.kb = V->m + 1; a.nbr = V->nbr; a.aosK = V->aos; a.aosG = V->gaos;
-    a.gr = ms.gr; a.nu_fixed = ms.nu_fixed; a.smooth_free = smooth_free;
-    a.B = V->B; a.ldb = (size_t)n; a.nb = nc;
-    a.logd = V->W; a.Y = V->W + n; a.ldy = (size_t)n;
-    a.X = f->dX; a.ldx = n; a.p = p;
-    a.rec = V->grec; a.ldr = (size_t)chunk;
-    a.fail = f->dinfo;
-    for (int r0 = 0; r0 < n; r0 += chunk) {
-        a.rows = std::min(chunk, n - r0); a.obs0 = r0; a.row0 = r0;
-        launch_vecchia_grad_blocks(ms.mode, a, s);
-        launch_vecchia_chunk_sums(V->grec, (size_t)chunk, a.rows, ncol, V->gpart, r0 / VECCHIA_SUM_SEG, nseg, s);
+    if (grouped) vecchia_group_grad_chunks(f, ms, smooth_free, nc, chunk, nseg);
+    else {
+        VecchiaArgs a;
+        a.m = V->m; a.kb = V->m + 1; a.nbr = V->nbr; a.aosK = V->aos; a.aosG = V->gaos;
+        a.gr = ms.gr; a.nu_fixed = ms.nu_fixed; a.smooth_free = smooth_free;
+        a.B = V->B; a.ldb = (size_t)n; a.nb = nc;
+        a.logd = V->W; a.Y = V->W + n; a.ldy = (size_t)n;
+        a.X = f->dX; a.ldx = n; a.p = p;
+        a.rec = V->grec; a.ldr = (size_t)chunk;
+        a.fail = f->dinfo;
+        for (int r0 = 0; r0 < n; r0 += chunk) {
+            a.rows = std::min(chunk, n - r0); a.obs0 = r0; a.row0 = r0;
+            launch_vecchia_grad_blocks(ms.mode, a, s);
+            launch_vecchia_chunk_sums(V->grec, (size_t)chunk, a.rows, ncol, V->gpart, r0 / VECCHIA_SUM_SEG, nseg, s);
+        }
     }
     launch_vecchia_sums(V->W, (size_t)n, n, 1 + nc, V->part, V->gout, s);
     launch_vecchia_final_sums(V->gpart, nseg, ncol, V->gout + (1 + nc), s);
@@ -248,6 +255,14 @@ extern "C" int cocons_neg2loglik_grad_vecchia(cocons_fit *f, const double *theta
         }
     if (grad_mean) for (int k = 0; k < p; ++k) grad_mean[k] = -2.0 * g[12 * p + 2 + k];
     return 0;
+}
+
+extern "C" int cocons_neg2loglik_grad_vecchia(cocons_fit *f, const double *theta, const double *mean, int c, const double *B,
+                                              double *sum_logliks, double *parts, double *grad_theta, double *grad_quad,
+                                              double *grad_mean)
+{
+    return vecchia_grad_impl("cocons_neg2loglik_grad_vecchia", false, f, theta, mean, c, B, sum_logliks, parts, grad_theta,
+                             grad_quad, grad_mean);
 }
 
 // Expected information of the Vecchia likelihood: one launch per chunk of vecchia_fisher_chunk observations,

@@ -2,8 +2,9 @@
 // the host; cocons_vecchia_group_table, the expanded table of any partition; cocons_vecchia_set_groups, the plan of a
 // partition on a Vecchia handle whose table is closed under it; cocons_fit_create_vecchia_grouped, the three in one call; and
 // cocons_neg2loglik_vecchia_grouped / cocons_vecchia_whiten_grouped, the value and the whitening with one factorisation per
-// block.  A grouped evaluation is the ungrouped one with launch_vecchia_group_blocks in the place of launch_vecchia_blocks:
-// the same records, right-hand sides, per-row arrays, totals and status word, and therefore the same bits.
+// block, and cocons_neg2loglik_grad_vecchia_grouped, the value and the gradient from it.  A grouped evaluation
+// is the ungrouped one with launch_vecchia_group_blocks in the place of launch_vecchia_blocks: the same records, right-hand
+// sides, per-row arrays, totals and status word, and therefore the same bits.
 #include "fit.hpp"
 #include "group_plan.hpp"
 
@@ -54,12 +55,6 @@ template <class T> hipError_t to_device(DevBuf<T> &d, const std::vector<T> &h, h
     return hipMemcpyAsync(d.get(), h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s);
 }
 
-int need_plan(cocons_fit *f, const char *who)
-{
-    if (!f->vecchia->grp) return fail(-1, "%s: the handle has no plan of grouped blocks (cocons_vecchia_set_groups attaches one)", who);
-    return 0;
-}
-
 // the grouped launch over the plan's blocks for nb right-hand sides in V->B: log d and the whitened columns into V->W
 void group_blocks(cocons_fit *f, const ModeSel &ms, int nb)
 {
@@ -76,6 +71,37 @@ void group_blocks(cocons_fit *f, const ModeSel &ms, int nb)
 }
 
 }  // namespace
+
+int vecchia_need_plan(cocons_fit *f, const char *who)
+{
+    if (!f->vecchia->grp) return fail(-1, "%s: the handle has no plan of grouped blocks (cocons_vecchia_set_groups attaches one)", who);
+    return 0;
+}
+
+// The grouped gradient's launches: the blocks by id in chunks of `chunk` records, each chunk summed into its
+// segments of blocks.  One chunk: the launch deals the blocks largest first, as the value launch does; more: by id within a
+// chunk (the records stand at the blocks' ids either way, so the totals do not depend on it).
+void vecchia_group_grad_chunks(cocons_fit *f, const ModeSel &ms, int smooth_free, int nc, int chunk, int nseg)
+{
+    VecchiaState *V = f->vecchia.get();
+    const VecchiaGroupState *G = V->grp.get();
+    const int n = f->n, ncol = vecchia_rec_cols(f->p);
+    VecchiaGroupArgs a;
+    a.kb = G->maxrows;
+    a.off = G->off; a.rows = G->rows; a.mask = G->mask;
+    a.order = (G->by_size && G->blocks <= chunk) ? G->order.get() : nullptr;
+    a.aosK = V->aos; a.aosG = V->gaos; a.gr = ms.gr; a.nu_fixed = ms.nu_fixed; a.smooth_free = smooth_free;
+    a.B = V->B; a.ldb = (size_t)n; a.nb = nc;
+    a.logd = V->W; a.Y = V->W + n; a.ldy = (size_t)n;
+    a.X = f->dX; a.ldx = n; a.p = f->p;
+    a.rec = V->grec; a.ldr = (size_t)chunk;
+    a.fail = f->dinfo;
+    for (int b0 = 0; b0 < G->blocks; b0 += chunk) {
+        a.blocks = std::min(chunk, G->blocks - b0); a.blk0 = b0;
+        launch_vecchia_group_grad_blocks(ms.mode, a, f->stream);
+        launch_vecchia_chunk_sums(V->grec, (size_t)chunk, a.blocks, ncol, V->gpart, b0 / VECCHIA_SUM_SEG, nseg, f->stream);
+    }
+}
 
 extern "C" int cocons_vecchia_group(int n, int m, const int *nn, int max_rows, int *group, long long *out4)
 {
@@ -152,7 +178,7 @@ extern "C" int cocons_vecchia_groups_info(cocons_fit *f, long long *out5)
     if (!out5) return fail(-1, "%s: null argument", who);
     FIT_ENTER_ANY(f);
     if (int rc = vecchia_only(f, who)) return rc;
-    if (int rc = need_plan(f, who)) return rc;
+    if (int rc = vecchia_need_plan(f, who)) return rc;
     const VecchiaGroupState *G = f->vecchia->grp.get();
     out5[0] = G->blocks; out5[1] = G->maxrows; out5[2] = G->sum_rows; out5[3] = G->pairs; out5[4] = G->bytes();
     return 0;
@@ -194,7 +220,7 @@ extern "C" int cocons_neg2loglik_vecchia_grouped(cocons_fit *f, const double *th
     if (!theta || !mean || !value) return fail(-1, "%s: null argument", who);
     FIT_ENTER_ANY(f);
     if (int rc = vecchia_only(f, who)) return rc;
-    if (int rc = need_plan(f, who)) return rc;
+    if (int rc = vecchia_need_plan(f, who)) return rc;
     VecchiaState *V = f->vecchia.get();
     const int n = f->n, r = f->r;
     double hmean[COCONS_P_MAX];
@@ -225,7 +251,7 @@ extern "C" int cocons_vecchia_whiten_grouped(cocons_fit *f, const double *theta,
     if (c < 1) return fail(-1, "%s: c = %d (at least one column expected)", who, c);
     FIT_ENTER_ANY(f);
     if (int rc = vecchia_only(f, who)) return rc;
-    if (int rc = need_plan(f, who)) return rc;
+    if (int rc = vecchia_need_plan(f, who)) return rc;
     VecchiaState *V = f->vecchia.get();
     const size_t n = (size_t)f->n;
     HIPCHK_AT(who, V->B.reserve(n * c, f->stream, nullptr));
@@ -241,4 +267,12 @@ extern "C" int cocons_vecchia_whiten_grouped(cocons_fit *f, const double *theta,
     if (logd) memcpy(logd, h.data(), n * sizeof(double));
     memcpy(out, h.data() + n, n * c * sizeof(double));
     return 0;
+}
+
+extern "C" int cocons_neg2loglik_grad_vecchia_grouped(cocons_fit *f, const double *theta, const double *mean, int c,
+                                                      const double *B, double *sum_logliks, double *parts, double *grad_theta,
+                                                      double *grad_quad, double *grad_mean)
+{
+    return vecchia_grad_impl("cocons_neg2loglik_grad_vecchia_grouped", true, f, theta, mean, c, B, sum_logliks, parts,
+                             grad_theta, grad_quad, grad_mean);
 }

@@ -312,6 +312,7 @@ struct VecchiaState {
     DevBuf<double> gsite;         // GSITE_FIELDS x npad: launch_grad_site's SoA
     DevBuf<double> gaos;          // VECCHIA_GSITE_REC x n: the same as one record per location
     DevBuf<double> grec;          // VECCHIA_GRAD_CHUNK x vecchia_rec_cols(p): the per-observation records of one chunk
+                                  // (the grouped gradient, DESIGN.md 4z: one record per block; gpart and gout serve it too)
     DevBuf<double> gpart;         // their first-stage sums, all segments of n
     DevBuf<double> gout;          // the totals: 1 + c of the value, then vecchia_rec_cols(p)
     // cocons_fisher_vecchia, allocated by its first call (gsite and gaos above are shared with the gradient)
@@ -767,6 +768,14 @@ int vecchia_predict_impl(const char *who, cocons_fit *f, const double *theta, co
 int vecchia_only(cocons_fit *f, const char *who);
 ModeSel vecchia_records(cocons_fit *f, const double *theta, int which, double *aos);
 int vecchia_status(cocons_fit *f, const char *who);
+// ... and what api_vecchia.hip and api_vecchia_group.hip offer each other: cocons_neg2loglik_grad_vecchia with
+// the launches over observations (grouped = false) or over the plan's blocks; the refusal of a handle without a plan; and the
+// grouped launches of one evaluation -- chunks of `chunk` blocks into V->grec, their first-stage sums into V->gpart
+int vecchia_grad_impl(const char *who, bool grouped, cocons_fit *f, const double *theta, const double *mean, int c,
+                      const double *B, double *sum_logliks, double *parts, double *grad_theta, double *grad_quad,
+                      double *grad_mean);
+int vecchia_need_plan(cocons_fit *f, const char *who);
+void vecchia_group_grad_chunks(cocons_fit *f, const ModeSel &ms, int smooth_free, int nc, int chunk, int nseg);
 // ... and what api_vecchia_sim.hip offers api_vecchia_cv.hip: the coefficients of the rows n_fixed .. n - 1 for
 // theta into the handle's sim->coef and the status word home: 0, the smallest failing 1-based row, or < 0
 int vecchia_sim_coefs(cocons_fit *f, const char *who, const double *theta, int n_fixed);

@@ -771,8 +771,21 @@ struct VecchiaGroupArgs {
     double *Y = nullptr; size_t ldy = 0;
     double *logd = nullptr;
     int *fail = nullptr;
+    // the gradient launch only (launch_vecchia_group_grad_blocks): workgroup w of the launch is block
+    // blk0 + order[w] (order null: blk0 + w) and writes column q of its record at rec[q ldr + (block - blk0)]
+    int blk0 = 0;
+    const double *aosG = nullptr;      // launch_vecchia_site_rec's records
+    int smooth_free = 0;
+    const double *X = nullptr; int ldx = 0, p = 0;
+    double *rec = nullptr; size_t ldr = 0;
 };
 void launch_vecchia_group_blocks(int mode, const VecchiaGroupArgs &a, hipStream_t s);
+// The gradient variant of the grouped launch over the blocks blk0 .. blk0 + blocks - 1: logd and Y as there (the same code),
+// and per BLOCK one record of vecchia_rec_cols(p) doubles in launch_vecchia_grad_blocks' layout -- the sum of the records
+// its members would give on the expanded table, from one evaluation of every pair of the block.  The dynamic LDS is
+// vecchia_group_grad_lds_bytes(kb): 78 144 bytes at kb = 64, above 64 KB from kb = 54 on.
+size_t vecchia_group_grad_lds_bytes(int kb);
+void launch_vecchia_group_grad_blocks(int mode, const VecchiaGroupArgs &a, hipStream_t s);
 
 // ---- U^-1 of a Vecchia fit: coefficients, levels and the level solve (vecchia_sim.hip) -------------------------
 constexpr int VECCHIA_SIM_FUSE_ITEMS = 256;     // a level of at most this many (row, column) pairs may join a fused run

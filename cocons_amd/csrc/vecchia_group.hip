@@ -14,10 +14,19 @@
 // A pivot that fails at position q fails every member at a position >= q -- the rows the ungrouped launch reports --, and the
 // smallest of them goes into the failure word by the same integer atomicMin.
 //
+// GRAD: the same gather, pair loop, factorisation and substitution, then the block's share of the gradient.
+// The member at position p is 4s's block on the leading p + 1 rows, so the block's weights are the members' weights summed:
+//   W_log = nb sum_p s_p s_p',   W_quad = sum_p [ -N_pp s_p s_p' - (h_p s_p' + s_p h_p') ],   N = sum_c w_c w_c',
+// with s_p = L^-T e_p (row p of L^-1) and h_p = L_{0..p}^-T N[p, 0..p).  The substitution leaves N's member rows in LDS, the
+// members' backward solves are dealt over the four wavefronts, and every pair's partials are evaluated ONCE by one of the
+// VECCHIA_GROUP_THREADS threads and weighted with the two sums over the members, ascending.  One record per block.
+//
 // Compile with -ffp-contract=off, like vecchia.hip: the products and sums stand as written.
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include "kernels.h"
 #include "matern_device.hpp"
+#include "grad_pair.hpp"
 #include "vecchia_tri.hpp"
 
 namespace cocons {
@@ -30,18 +39,42 @@ namespace cocons {
 // pair values -- the Bessel branch above all -- without anything to hide their latency behind.  The extra wavefronts take
 // pairs (a pair's value does not depend on the thread that evaluates it), pass the barriers of the factorisation with
 // nothing to do (a thread is a row only below nrows <= 64) and end before the substitution, which has no barrier.
-template <int MODE>
+// GRAD (vecchia_group_grad_lds_bytes) keeps tri at VECCHIA_GROUP_STG doubles or more -- once the members' solves are done the
+// factor is dead and the pair walk stages a pass of VECCHIA_GROUP_THREADS pairs there -- and puts behind it:
+//   sm    kb (kb + 1) / 2    row p of a member: s_p;
+//   nm    kb (kb + 1) / 2    row p of a member: N[p, 0..p], then h_p in the places 0 .. p - 1 (the diagonal keeps N_pp);
+//   sp    GSITE_FIELDS x kb  the rows' site derivatives as an SoA of stride kb;
+//   ys, uv  kb each          sum_c y_pc of the members, and u = sum_p ys[p] s_p;
+//   gs    2 GFAM x kb        the rows' site sums: the log-determinant's share per family, then the quadratic forms';
+//   red   2 x 4              the wavefronts' shares of the two global-range sums.
+constexpr int VECCHIA_GROUP_STGF = 2 * GFAM + 2;        // a staged pair: da, db, 2 W_log, 2 W_quad
+constexpr int VECCHIA_GROUP_STG = VECCHIA_GROUP_STGF * VECCHIA_GROUP_THREADS;
+constexpr int VECCHIA_GROUP_GX = GSITE_FIELDS + 2 + 2 * GFAM;
+constexpr int VECCHIA_GROUP_WAVES = VECCHIA_GROUP_THREADS / 64;
+static_assert(2 * GFAM % VECCHIA_GROUP_WAVES == 0, "the site sums are dealt evenly over the wavefronts");
+
+__device__ __forceinline__ double vecchia_group_wave_sum(double v)
+{
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+template <int MODE, bool GRAD = false>
 __global__ void __launch_bounds__(VECCHIA_GROUP_THREADS)
 vecchia_group_kernel(VecchiaGroupArgs a)
 {
     extern __shared__ double vecchia_group_lds[];
     const int lane = threadIdx.x, kb = a.kb;
-    const int blk = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
+    const int blk = (GRAD ? a.blk0 : 0) + (a.order ? a.order[blockIdx.x] : (int)blockIdx.x);
     const int off = a.off[blk], nrows = a.off[blk + 1] - off;
     const unsigned long long members = a.mask[blk];
+    const int ntri = kb * (kb + 1) / 2;
     double *par = vecchia_group_lds;
     double *tri = par + LOCP_FIELDS * kb;
-    int *nb = (int *)(tri + kb * (kb + 1) / 2);
+    [[maybe_unused]] double *sm = tri + ((GRAD && ntri < VECCHIA_GROUP_STG) ? VECCHIA_GROUP_STG : ntri);
+    [[maybe_unused]] double *nm = sm + ntri;
+    [[maybe_unused]] double *sp = nm + ntri;
+    int *nb = GRAD ? (int *)(sp + VECCHIA_GROUP_GX * kb + 2 * VECCHIA_GROUP_WAVES) : (int *)(tri + ntri);
     if (nrows < 1 || nrows > kb) return;          // (a plan the host checked has none)
 
     if (lane < nrows) nb[lane] = a.rows[off + lane];
@@ -50,6 +83,13 @@ vecchia_group_kernel(VecchiaGroupArgs a)
         const int r = e / VECCHIA_REC, f = e % VECCHIA_REC;
         if (f >= LOCP_FIELDS) continue;
         par[f * kb + r] = a.aosK[(size_t)nb[r] * VECCHIA_REC + f];
+    }
+    if constexpr (GRAD) {
+        for (int e = lane; e < nrows * VECCHIA_GSITE_REC; e += VECCHIA_GROUP_THREADS) {
+            const int r = e / VECCHIA_GSITE_REC, f = e % VECCHIA_GSITE_REC;
+            sp[f * kb + r] = a.aosG[(size_t)nb[r] * VECCHIA_GSITE_REC + f];
+        }
+        for (int e = lane; e < nrows * (nrows + 1) / 2; e += VECCHIA_GROUP_THREADS) nm[e] = 0.0;
     }
     __syncthreads();
     // the block: pair t = r (r - 1) / 2 + c is (r, c), r > c, the EARLIER row on the `ii` side (vecchia_block_kernel's order)
@@ -83,13 +123,17 @@ vecchia_group_kernel(VecchiaGroupArgs a)
         if (lane == 0 && q < nrows) atomicMin(a.fail, nb[q] + 1);
         return;
     }
+    if (GRAD && lane < nrows) tri[tri_at(lane, lane)] = piv_mine;     // (the solves of the other wavefronts read the pivots here)
     __syncthreads();
-    if (lane >= 64) return;                        // (no barrier from here on)
+    if (!GRAD && lane >= 64) return;               // (no barrier from here on)
     // forward substitution, VECCHIA_G right-hand sides at a time: lane r ends with b_r - sum_{j < r} C(r, j) y_j, j ascending.
     // A lane at or in front of step j takes no part in it: its value must not see a y_j that is not finite.
+    // GRAD: every lane j ends with the numerator of w_c[j], so N[p, j] = sum_c w_c[p] w_c[j] of the member rows p >= j and
+    // sum_c w_c[p] are formed on the way, the columns ascending.
     const bool member = lane < nrows && ((members >> lane) & 1ull);
     const int site = lane < nrows ? nb[lane] : 0;
-    for (int c0 = 0; c0 < a.nb; c0 += VECCHIA_G) {
+    [[maybe_unused]] double ysum = 0.0;
+    for (int c0 = 0; lane < 64 && c0 < a.nb; c0 += VECCHIA_G) {        // (GRAD: the other wavefronts go on to the barrier)
         double b[VECCHIA_G];
 #pragma unroll
         for (int g = 0; g < VECCHIA_G; ++g)
@@ -110,8 +154,174 @@ vecchia_group_kernel(VecchiaGroupArgs a)
                 a.Y[(size_t)site + (size_t)(c0 + g) * a.ldy] = b[g] / piv_mine;
             }
         }
+        if constexpr (GRAD) {
+            double w[VECCHIA_G];
+#pragma unroll
+            for (int g = 0; g < VECCHIA_G; ++g) w[g] = (lane < nrows && c0 + g < a.nb) ? b[g] / piv_mine : 0.0;
+            for (unsigned long long rest = members; rest; rest &= rest - 1) {
+                const int p = __builtin_ctzll(rest);
+                double acc = lane <= p ? nm[tri_at(p, lane)] : 0.0;
+#pragma unroll
+                for (int g = 0; g < VECCHIA_G; ++g) {
+                    if (c0 + g >= a.nb) break;
+                    const double y = __shfl(w[g], p);
+                    acc += y * w[g];
+                }
+                if (lane <= p) nm[tri_at(p, lane)] = acc;
+            }
+#pragma unroll
+            for (int g = 0; g < VECCHIA_G; ++g) {
+                if (c0 + g >= a.nb) break;
+                ysum += w[g];
+            }
+        }
     }
     if (member && a.logd) a.logd[site] = log(piv_mine);
+    if constexpr (GRAD) {
+        const int wv = lane >> 6, ln = lane & 63, T = VECCHIA_GROUP_THREADS;
+        double *ys = sp + GSITE_FIELDS * kb, *uv = ys + kb, *gs = uv + kb, *red = gs + 2 * GFAM * kb;
+        if (lane < nrows) ys[lane] = ysum;
+        __syncthreads();
+        // The members' backward solves, member i (ascending) on wavefront i mod 4, lane = row: one column of L' (a row of the
+        // packed factor) per step, s_p and h_p together as in 4s.  h_p takes the place of N[p, 0..p) -- the wavefront that
+        // owns the member is the only one that touches its row.
+        {
+            const double ipiv = ln < nrows ? 1.0 / tri[tri_at(ln, ln)] : 0.0;
+            int rank = 0;
+            for (unsigned long long rest = members; rest; rest &= rest - 1, ++rank) {
+                if ((rank & (VECCHIA_GROUP_WAVES - 1)) != wv) continue;
+                const int p = __builtin_ctzll(rest);
+                double rs = ln == p ? 1.0 : 0.0, rh = ln < p ? nm[tri_at(p, ln)] : 0.0, s_mine = 0.0, h_mine = 0.0;
+                for (int j = p; j >= 0; --j) {
+                    const double xs = __shfl(rs * ipiv, j), xh = __shfl(rh * ipiv, j);
+                    if (ln == j) { s_mine = xs; h_mine = xh; }
+                    if (ln < j) {
+                        const double l = tri[tri_at(j, 0) + ln];
+                        rs -= l * xs;
+                        rh -= l * xh;
+                    }
+                }
+                if (ln <= p) sm[tri_at(p, ln)] = s_mine;
+                if (ln < p) nm[tri_at(p, ln)] = h_mine;
+            }
+        }
+        __syncthreads();                   // the factor is dead from here on, tri is the staging of the pair walk
+        // The weights of the pair (r, c), r >= c: the members at the positions p >= r, ascending
+        const double cn = (double)a.nb;
+        auto weights = [&](int r, int c, double &wl, double &wq) {
+            double sl = 0.0, sq = 0.0;
+            for (unsigned long long rest = members & (~0ull << r); rest; rest &= rest - 1) {
+                const int p = __builtin_ctzll(rest), at = tri_at(p, 0);
+                const double zr = sm[at + r], zc = sm[at + c], npp = nm[at + p];
+                const double hr = r < p ? nm[at + r] : 0.0, hc = c < p ? nm[at + c] : 0.0;
+                sl += zr * zc;
+                sq += 0.0 - npp * (zr * zc) - (hr * zc + zr * hc);
+            }
+            wl = cn * sl;
+            wq = sq;
+        };
+        // thread (row ln, wavefront wv) keeps VECCHIA_GROUP_NACC of the row's 2 GFAM site sums, q = wv NACC + i: the
+        // log-determinant's share of family q below GFAM, the quadratic forms' of family q - GFAM from there on
+        constexpr int NACC = 2 * GFAM / VECCHIA_GROUP_WAVES;
+        const int q0 = wv * NACC, f0 = q0 % GFAM, wsel = 2 * GFAM + (q0 >= GFAM ? 1 : 0);
+        double acc[NACC];
+#pragma unroll
+        for (int i = 0; i < NACC; ++i) acc[i] = 0.0;
+        if (ln < nrows) {
+            // the diagonal first: W_aa (exp(eta_sd), nugget)
+            double wl, wq;
+            weights(ln, ln, wl, wq);
+            const double w = q0 >= GFAM ? wq : wl, dsd = sp[3 * kb + ln], dng = par[12 * kb + ln];
+#pragma unroll
+            for (int i = 0; i < NACC; ++i) {
+                if (f0 + i == TH_SD_) acc[i] = w * dsd;
+                if (f0 + i == TH_NG_) acc[i] = w * dng;
+            }
+            if (wv == 0) {
+                // u = sum_p (sum_c y_pc) s_p over the members at the positions p >= ln, ascending
+                double u = 0.0;
+                for (unsigned long long rest = members & (~0ull << ln); rest; rest &= rest - 1) {
+                    const int p = __builtin_ctzll(rest);
+                    u += ys[p] * sm[tri_at(p, ln)];
+                }
+                uv[ln] = u;
+            }
+        }
+        // The pair walk: VECCHIA_GROUP_THREADS pairs a pass, one per thread (the order of the assembly above), each pair's
+        // partials evaluated once and staged with 2 W_log and 2 W_quad; then thread (a, wv) adds what the pass holds for its
+        // site -- its pairs (a, c), c < a ascending (the jj side), then its pairs (r, a), r > a ascending (the ii side).
+        double *stg = tri;
+        double glob_l = 0.0, glob_q = 0.0;
+        for (int t0 = 0; t0 < npairs; t0 += T) {
+            const int t = t0 + lane;
+            double da[GFAM], db[GFAM], dg = 0.0, w2l = 0.0, w2q = 0.0;
+#pragma unroll
+            for (int f = 0; f < GFAM; ++f) { da[f] = 0.0; db[f] = 0.0; }
+            if (t < npairs) {
+                int r, c;
+                tri_pair(t, r, c);
+                pair_partials<MODE>(par, (size_t)kb, sp, (size_t)kb, a.gr, a.nu_fixed, a.smooth_free, c, r, da, db, dg);
+                double wl, wq;
+                weights(r, c, wl, wq);
+                w2l = 2.0 * wl;
+                w2q = 2.0 * wq;
+                glob_l += w2l * dg;
+                glob_q += w2q * dg;
+            }
+#pragma unroll
+            for (int f = 0; f < GFAM; ++f) {
+                stg[f * T + lane] = da[f];
+                stg[(GFAM + f) * T + lane] = db[f];
+            }
+            stg[2 * GFAM * T + lane] = w2l;
+            stg[(2 * GFAM + 1) * T + lane] = w2q;
+            __syncthreads();
+            if (ln < nrows) {
+                const int tend = min(t0 + T, npairs), mine0 = ln * (ln - 1) / 2;
+                for (int u = max(t0, mine0); u < min(tend, mine0 + ln); ++u) {
+                    const double w = stg[wsel * T + (u - t0)];
+#pragma unroll
+                    for (int i = 0; i < NACC; ++i) acc[i] += w * stg[(GFAM + f0 + i) * T + (u - t0)];
+                }
+                int r_lo, r_hi, c_;
+                tri_pair(t0, r_lo, c_);
+                tri_pair(tend - 1, r_hi, c_);
+                for (int r = max(r_lo, ln + 1); r <= r_hi; ++r) {
+                    const int u = r * (r - 1) / 2 + ln;
+                    if (u < t0 || u >= tend) continue;
+                    const double w = stg[wsel * T + (u - t0)];
+#pragma unroll
+                    for (int i = 0; i < NACC; ++i) acc[i] += w * stg[(f0 + i) * T + (u - t0)];
+                }
+            }
+            __syncthreads();
+        }
+        if (ln < nrows) {
+#pragma unroll
+            for (int i = 0; i < NACC; ++i) gs[(q0 + i) * kb + ln] = acc[i];
+        }
+        // the global-range sums: a fixed butterfly per wavefront, the wavefronts' shares added in their order
+        glob_l = vecchia_group_wave_sum(glob_l);
+        glob_q = vecchia_group_wave_sum(glob_q);
+        if (ln == 0) { red[wv] = glob_l; red[VECCHIA_GROUP_WAVES + wv] = glob_q; }
+        __syncthreads();
+        // the record, at the block's id: the site sums contracted with X over the block's rows, ascending
+        const int p = a.p, b = blk - a.blk0;
+        for (int o = lane; o < (2 * GFAM + 1) * p; o += T) {
+            const int q = o / p, kx = o % p;
+            const double *g = q < 2 * GFAM ? gs + q * kb : uv;
+            double s = 0.0;
+            for (int rr = 0; rr < nrows; ++rr) s += g[rr] * a.X[(size_t)nb[rr] + (size_t)kx * a.ldx];
+            if (q < 2 * GFAM) a.rec[(size_t)o * a.ldr + b] = s;
+            else a.rec[(size_t)(2 * GFAM * p + 2 + kx) * a.ldr + b] = s;
+        }
+        if (lane == 0) {
+            double gl = red[0], gq = red[VECCHIA_GROUP_WAVES];
+            for (int w = 1; w < VECCHIA_GROUP_WAVES; ++w) { gl += red[w]; gq += red[VECCHIA_GROUP_WAVES + w]; }
+            a.rec[(size_t)(2 * GFAM * p) * a.ldr + b] = gl;
+            a.rec[(size_t)(2 * GFAM * p + 1) * a.ldr + b] = gq;
+        }
+    }
 }
 
 void launch_vecchia_group_blocks(int mode, const VecchiaGroupArgs &a, hipStream_t s)
@@ -124,6 +334,33 @@ void launch_vecchia_group_blocks(int mode, const VecchiaGroupArgs &a, hipStream_
     case MODE_THREEHALF: hipLaunchKernelGGL((vecchia_group_kernel<MODE_THREEHALF>), grid, block, shm, s, a); break;
     case MODE_FIVEHALF: hipLaunchKernelGGL((vecchia_group_kernel<MODE_FIVEHALF>), grid, block, shm, s, a); break;
     default: hipLaunchKernelGGL((vecchia_group_kernel<MODE_GEOM>), grid, block, shm, s, a); break;
+    }
+}
+
+size_t vecchia_group_grad_lds_bytes(int kb)
+{
+    const size_t k = (size_t)kb, ntri = k * (k + 1) / 2;
+    return (LOCP_FIELDS * k + (ntri < (size_t)VECCHIA_GROUP_STG ? (size_t)VECCHIA_GROUP_STG : ntri) + 2 * ntri +
+            VECCHIA_GROUP_GX * k + 2 * VECCHIA_GROUP_WAVES) * sizeof(double) + k * sizeof(int);
+}
+
+template <int MODE> static void vecchia_group_grad_launch(const VecchiaGroupArgs &a, size_t shm, hipStream_t s)
+{
+    static std::atomic<unsigned long long> attr_done{0};
+    if (shm > 64 * 1024)
+        set_dynamic_lds_once((const void *)vecchia_group_kernel<MODE, true>, vecchia_group_grad_lds_bytes(64), attr_done);
+    hipLaunchKernelGGL((vecchia_group_kernel<MODE, true>), dim3((unsigned)a.blocks), dim3(VECCHIA_GROUP_THREADS), shm, s, a);
+}
+
+void launch_vecchia_group_grad_blocks(int mode, const VecchiaGroupArgs &a, hipStream_t s)
+{
+    if (a.blocks <= 0) return;
+    const size_t shm = vecchia_group_grad_lds_bytes(a.kb);    // kb <= 64: at most 78 144 bytes
+    switch (mode) {
+    case MODE_HALF: vecchia_group_grad_launch<MODE_HALF>(a, shm, s); break;
+    case MODE_THREEHALF: vecchia_group_grad_launch<MODE_THREEHALF>(a, shm, s); break;
+    case MODE_FIVEHALF: vecchia_group_grad_launch<MODE_FIVEHALF>(a, shm, s); break;
+    default: vecchia_group_grad_launch<MODE_GEOM>(a, shm, s); break;
     }
 }
 

@@ -1655,26 +1655,28 @@ class CoconsVecchiaFit(_Handle):
         _lib.check(getattr(self._L, entry)(self._h, _p(T), _p(mean), ctypes.byref(val), _p(parts)), entry)
         return val.value, parts
 
-    def neg2loglik_grad_core(self, theta_list, B=None):
+    def neg2loglik_grad_core(self, theta_list, B=None, grouped=False):
         """(value, parts, grad_table, grad_quad, grad_mean) of cocons_neg2loglik_grad_vecchia: value and parts are
         neg2loglik_core's to the bit, grad_table the 6 x p table of the whole value in the conventions of the dense
         gradient, grad_quad the quadratic forms' share of it (the log-determinant's is grad_table - grad_quad), grad_mean p
         doubles.  With B (n x c, the caller's order) the columns are used as given -- the forms with the mean profiled out
-        --, parts has 1 + c entries and grad_mean is None."""
+        --, parts has 1 + c entries and grad_mean is None.  `grouped`: on the plan of `set_groups`, one factorisation per block
+        and every pair of a block once (cocons_neg2loglik_grad_vecchia_grouped) -- value and parts to the bit, the gradient of
+        the same model to rounding."""
         T = theta_table(theta_list)
         val = ctypes.c_double(0.0)
         gt, gq = np.zeros((6, self.p)), np.zeros((6, self.p))
+        entry = "cocons_neg2loglik_grad_vecchia_grouped" if grouped else "cocons_neg2loglik_grad_vecchia"
+        call = getattr(self._L, entry)
         if B is None:
             mean = np.ascontiguousarray(np.asarray(theta_list["mean"], dtype=np.float64))
             parts, gm = np.zeros(1 + self.r), np.zeros(self.p)
-            st = self._L.cocons_neg2loglik_grad_vecchia(self._h, _p(T), _p(mean), 0, None, ctypes.byref(val), _p(parts),
-                                                        _p(gt), _p(gq), _p(gm))
+            st = call(self._h, _p(T), _p(mean), 0, None, ctypes.byref(val), _p(parts), _p(gt), _p(gq), _p(gm))
         else:
             B = _f(np.asarray(B, dtype=np.float64).reshape(self.n, -1))
             parts, gm = np.zeros(1 + B.shape[1]), None
-            st = self._L.cocons_neg2loglik_grad_vecchia(self._h, _p(T), None, int(B.shape[1]), _p(B), ctypes.byref(val),
-                                                        _p(parts), _p(gt), _p(gq), None)
-        _lib.check(st, "cocons_neg2loglik_grad_vecchia")
+            st = call(self._h, _p(T), None, int(B.shape[1]), _p(B), ctypes.byref(val), _p(parts), _p(gt), _p(gq), None)
+        _lib.check(st, entry)
         return val.value, parts, gt, gq, gm
 
     def fisher_core(self, theta_list, dirs):
@@ -1855,15 +1857,18 @@ def GetNeg2loglikelihoodVecchiaREML(theta, par_pos, nn, locs, x_covariates, x_be
                       core, n - rank)
 
 
-def GetNeg2loglikelihoodVecchia_grad(theta, par_pos, nn, locs, x_covariates, smooth_limits, z, n, lam, safe=True, fit=None):
+def GetNeg2loglikelihoodVecchia_grad(theta, par_pos, nn, locs, x_covariates, smooth_limits, z, n, lam, safe=True, fit=None,
+                                     grouped=False):
     """`GetNeg2loglikelihoodVecchia` and its gradient over the optimiser's vector `theta` in one call: (value, gradient).
     The value is that function's to the bit; the gradient is cocons_neg2loglik_grad_vecchia's plus the penalty's, carried
-    through getModelLists(type="diff") as GetNeg2loglikelihood_grad does.  A failing block gives (1e6, zeros) under `safe`."""
+    through getModelLists(type="diff") as GetNeg2loglikelihood_grad does.  A failing block gives (1e6, zeros) under `safe`.
+    `grouped`: the grouped model of `nn` with value and gradient on the grouped schedule, as in
+    GetNeg2loglikelihoodVecchia."""
     def core(f, tl):
-        val, _, gt, _, gm = f.neg2loglik_grad_core(tl)
+        val, _, gt, _, gm = f.neg2loglik_grad_core(tl, grouped=grouped)
         return val, (gt,), gm
 
-    return _objective(theta, par_pos, lam, smooth_limits, safe, _vecchia(fit, locs, x_covariates, z, smooth_limits, nn),
+    return _objective(theta, par_pos, lam, smooth_limits, safe, _vecchia(fit, locs, x_covariates, z, smooth_limits, nn, grouped),
                       core, n, grad=True)
 
 
@@ -1878,37 +1883,39 @@ def getFisher_vecchia(par, par_pos, locs, x_covariates, smooth_limits, z, n, nn,
     return _fisher_in_par(par, par_pos, _vecchia(fit, locs, x_covariates, z, smooth_limits, nn))
 
 
-def _vecchia_gls_resid(f, tl, z, x_betas):
+def _vecchia_gls_resid(f, tl, z, x_betas, grouped=False):
     """One whitening of [z | x_betas]: (W = Xb' U'U Xb, the residual columns z_k - Xb beta_k at the GLS estimate)."""
     z = np.asarray(z, dtype=np.float64).reshape(f.n, -1)
     xb = np.asarray(x_betas, dtype=np.float64).reshape(f.n, -1)
-    UB, _ = f.whiten_core(tl, np.hstack([z, xb]))
+    UB, _ = (f.whiten_grouped_core if grouped else f.whiten_core)(tl, np.hstack([z, xb]))
     Uz, UX = UB[:, :z.shape[1]], UB[:, z.shape[1]:]
     W = UX.T @ UX
     return W, z - xb @ np.linalg.solve(W, UX.T @ Uz)
 
 
 def GetNeg2loglikelihoodVecchiaProfile_grad(theta, par_pos, nn, locs, x_covariates, smooth_limits, z, n, x_betas, lam,
-                                            safe=True, fit=None):
+                                            safe=True, fit=None, grouped=False):
     """`GetNeg2loglikelihoodVecchiaProfile` and its gradient over the optimiser's vector: (value, gradient).  One whitening
     gives beta-hat; the gradient entry then runs on the columns z_k - Xb beta-hat_k.  By the envelope theorem the gradient
-    at fixed beta-hat is the gradient of the profiled value (the mean is profiled out: `par_pos["mean"]` holds no free entry)."""
+    at fixed beta-hat is the gradient of the profiled value (the mean is profiled out: `par_pos["mean"]` holds no free entry).
+    `grouped` as in GetNeg2loglikelihoodVecchia_grad; the whitening of the GLS step runs on the grouped schedule too."""
     def core(f, tl):
-        _, E = _vecchia_gls_resid(f, tl, z, x_betas)
-        val, _, gt, _, _ = f.neg2loglik_grad_core(tl, B=E)
+        _, E = _vecchia_gls_resid(f, tl, z, x_betas, grouped)
+        val, _, gt, _, _ = f.neg2loglik_grad_core(tl, B=E, grouped=grouped)
         return val, (gt,), None
 
-    return _objective(theta, par_pos, lam, smooth_limits, safe, _vecchia(fit, locs, x_covariates, z, smooth_limits, nn),
+    return _objective(theta, par_pos, lam, smooth_limits, safe, _vecchia(fit, locs, x_covariates, z, smooth_limits, nn, grouped),
                       core, n, grad=True)
 
 
 def GetNeg2loglikelihoodVecchiaREML_grad(theta, par_pos, nn, locs, x_covariates, x_betas, smooth_limits, z, n, lam,
-                                         safe=True, fit=None):
+                                         safe=True, fit=None, grouped=False):
     """`GetNeg2loglikelihoodVecchiaREML` and its gradient over the optimiser's vector: (value, gradient).  Beside the
     residual columns the restricted likelihood has log|X' U'U X|, whose derivative is sum_j d||U v_j||^2 at fixed
     V = X chol(X' U'U X)^-T: the gradient entry runs on B = [residual columns | sqrt(r) V]; the log-determinant's share
     (grad_theta - grad_quad) is scaled from B's columns to the r realisations, the quadratic forms' share taken as it is.
-    x_betas is accepted and unused, as there.  A rank-deficient x_covariates is refused (ValueError)."""
+    x_betas is accepted and unused, as there.  A rank-deficient x_covariates is refused (ValueError).  `grouped` as in
+    GetNeg2loglikelihoodVecchiaProfile_grad."""
     X = np.asarray(x_covariates, dtype=np.float64)
     rank = int(np.linalg.matrix_rank(X))
     if rank < X.shape[1]:
@@ -1917,15 +1924,15 @@ def GetNeg2loglikelihoodVecchiaREML_grad(theta, par_pos, nn, locs, x_covariates,
 
     def core(f, tl):
         r = f.r
-        W, E = _vecchia_gls_resid(f, tl, z, X)
+        W, E = _vecchia_gls_resid(f, tl, z, X, grouped)
         Lw = np.linalg.cholesky(W)
         V = np.linalg.solve(Lw, X.T).T
-        _, parts, gt, gq, _ = f.neg2loglik_grad_core(tl, B=np.hstack([E, np.sqrt(r) * V]))
+        _, parts, gt, gq, _ = f.neg2loglik_grad_core(tl, B=np.hstack([E, np.sqrt(r) * V]), grouped=grouped)
         logdet_w = float(np.sum(np.log(np.diag(Lw))))
         val = float(np.sum((n - rank) * np.log(2 * np.pi) + 2 * parts[0] + 2 * logdet_w + parts[1:1 + r]))
         return val, ((gt - gq) * (r / (r + X.shape[1])) + gq,), None
 
-    return _objective(theta, par_pos, lam, smooth_limits, safe, _vecchia(fit, locs, x_covariates, z, smooth_limits, nn),
+    return _objective(theta, par_pos, lam, smooth_limits, safe, _vecchia(fit, locs, x_covariates, z, smooth_limits, nn, grouped),
                       core, n - rank, grad=True)
 
 

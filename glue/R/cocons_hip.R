@@ -663,6 +663,14 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
   v[1] + .cocons.getPen(n * r, lambda, theta_list, smooth.limits)
 }
 
+# .cocons.hip.vecchia.neg2loglik.grad on the grouped schedule (DESIGN.md 4z): the same list -- the value to the bit, the gradient
+# of the same model to rounding --, from one factorisation per block and every pair of a block evaluated once
+.cocons.hip.vecchia.neg2loglik.grad.grouped <- function(fit, theta_list, safe = TRUE) {
+  res <- .cocons.hip.result(.Call(`_cocons_hip_vecchia_neg2loglik_grad_grouped`, fit, theta_list[-1], theta_list$mean), safe)
+  if (is.null(res)) return(NULL)
+  list(value = res[[1]], table = res[[2]], quad = res[[3]], mean = res[[4]])
+}
+
 # U W for the n x c matrix W and log d on the grouped schedule: list(out, logd)
 .cocons.hip.vecchia.whiten.grouped <- function(fit, theta_list, W) {
   W <- as.matrix(W)

@@ -957,7 +957,7 @@ SEXP _cocons_hip_vecchia_neg2loglik(SEXP fitp, SEXP theta, SEXP mean)
 /* Vecchia value and analytic gradient (cocons_neg2loglik_grad_vecchia, the columns z - X mean): list(status, list(value,
  * grad_table 6 x p, grad_quad 6 x p, grad_mean p)), the tables' rows in the order std.dev, scale, aniso, tilt, smooth,
  * nugget; grad_quad is the quadratic forms' share of grad_table.  status > 0: the first failing row, the gradients zero */
-SEXP _cocons_hip_vecchia_neg2loglik_grad(SEXP fitp, SEXP theta, SEXP mean)
+static SEXP vecchia_neg2loglik_grad(SEXP fitp, SEXP theta, SEXP mean, int grouped)
 {
     cocons_fit *f = fit_of(fitp);
     const int p = fit_p(fitp);
@@ -968,8 +968,9 @@ SEXP _cocons_hip_vecchia_neg2loglik_grad(SEXP fitp, SEXP theta, SEXP mean)
     SEXP gq = PROTECT(Rf_allocMatrix(REALSXP, 6, p));
     SEXP gm = PROTECT(Rf_allocVector(REALSXP, p));
     for (int k = 0; k < p; ++k) REAL(gm)[k] = 0.0;
-    int rc = cocons_neg2loglik_grad_vecchia(f, T, REAL(mean), 0, NULL, &val, NULL, G, Q, REAL(gm));
-    hip_check(rc, "GetNeg2loglikelihoodVecchia (gradient)");
+    int rc = (grouped ? cocons_neg2loglik_grad_vecchia_grouped : cocons_neg2loglik_grad_vecchia)(f, T, REAL(mean), 0, NULL, &val,
+                                                                                                  NULL, G, Q, REAL(gm));
+    hip_check(rc, grouped ? "GetNeg2loglikelihoodVecchia (grouped gradient)" : "GetNeg2loglikelihoodVecchia (gradient)");
     for (int t = 0; t < 6; ++t)         /* (a failing block writes nothing: G and Q stay zero) */
         for (int k = 0; k < p; ++k) {
             REAL(gt)[t + 6 * k] = G[t * p + k];
@@ -983,6 +984,11 @@ SEXP _cocons_hip_vecchia_neg2loglik_grad(SEXP fitp, SEXP theta, SEXP mean)
     SEXP out = status_value(rc, res);
     UNPROTECT(4);
     return out;
+}
+
+SEXP _cocons_hip_vecchia_neg2loglik_grad(SEXP fitp, SEXP theta, SEXP mean)
+{
+    return vecchia_neg2loglik_grad(fitp, theta, mean, 0);
 }
 
 /* expected information of a Vecchia fit (cocons_fisher_vecchia): dirs as for _cocons_hip_fisher; list(status, list(info
@@ -1268,6 +1274,13 @@ SEXP _cocons_hip_vecchia_neg2loglik_grouped(SEXP fitp, SEXP theta, SEXP mean)
     return out;
 }
 
+/* _cocons_hip_vecchia_neg2loglik_grad on the grouped schedule (cocons_neg2loglik_grad_vecchia_grouped): the same
+ * list; the value to the bit, the gradient of the same model to rounding */
+SEXP _cocons_hip_vecchia_neg2loglik_grad_grouped(SEXP fitp, SEXP theta, SEXP mean)
+{
+    return vecchia_neg2loglik_grad(fitp, theta, mean, 1);
+}
+
 /* U W and log d on the grouped schedule (cocons_vecchia_whiten_grouped): W is n x c; list(status, list(the n x c result, the
  * n values log d)); theta without `mean` */
 SEXP _cocons_hip_vecchia_whiten_grouped(SEXP fitp, SEXP theta, SEXP W)
@@ -1513,6 +1526,7 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_vecchia_group_table", (DL_FUNC)&_cocons_hip_vecchia_group_table, 2},
     {"_cocons_hip_vecchia_set_groups", (DL_FUNC)&_cocons_hip_vecchia_set_groups, 2},
     {"_cocons_hip_vecchia_neg2loglik_grouped", (DL_FUNC)&_cocons_hip_vecchia_neg2loglik_grouped, 3},
+    {"_cocons_hip_vecchia_neg2loglik_grad_grouped", (DL_FUNC)&_cocons_hip_vecchia_neg2loglik_grad_grouped, 3},
     {"_cocons_hip_vecchia_whiten_grouped", (DL_FUNC)&_cocons_hip_vecchia_whiten_grouped, 3},
     {"_cocons_hip_fit_close", (DL_FUNC)&_cocons_hip_fit_close, 1},
     {"_cocons_hip_neg2loglik_parts", (DL_FUNC)&_cocons_hip_neg2loglik_parts, 3},

@@ -534,6 +534,16 @@ int cocons_neg2loglik_vecchia_grouped(cocons_fit *fit, const double *theta, cons
                                       double *parts /* 1 + r, may be NULL */);
 int cocons_vecchia_whiten_grouped(cocons_fit *fit, const double *theta, int c, const double *B /* n x c */,
                                   double *out /* n x c */, double *logd /* n, may be NULL */);
+/* cocons_neg2loglik_grad_vecchia on the grouped schedule (value and gradient from one factorisation per BLOCK, every pair
+ * of a block evaluated once): the same arguments, conventions, return codes and refusals -- B == NULL or given columns,
+ * grad_quad and parts may be NULL, outputs written on 0 only, the smallest failing 1-based row.  sum_logliks and parts are
+ * cocons_neg2loglik_vecchia_grouped's bits (and so the ungrouped entries'); the gradient is the same model's -- the handle's
+ * table is the expanded one -- summed in another order: it agrees with cocons_neg2loglik_grad_vecchia on the same handle to
+ * rounding, not to the bit, and repeats to the bit whatever COCONS_VECCHIA_GROUP_ORDER says.  Refused (-1): a handle without
+ * a plan.                                                                                                                    */
+int cocons_neg2loglik_grad_vecchia_grouped(cocons_fit *fit, const double *theta, const double *mean, int c, const double *B,
+                                           double *sum_logliks, double *parts, double *grad_theta, double *grad_quad,
+                                           double *grad_mean);
 
 /* ---- fit handle: everything that is constant over an optimisation -------------
  * Created once per cocoOptim / getHessian call from the arguments the reference
