@@ -99,6 +99,7 @@ SIGNATURES = {
     "cocons_fisher_dense": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_dp]),
     "cocons_fisher_reml": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp]),
     "cocons_fisher_vecchia": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_dp]),
+    "cocons_fisher_vecchia_grouped": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_dp]),
     "cocons_fisher_taper": (c_int, [c_vp, c_dp, c_int, c_dp, c_int, c_dp, c_int, c_dp, c_dp]),
     "cocons_cv_dense": (c_int, [c_vp, c_dp, c_dp, c_int, ctypes.POINTER(c_int), c_dp, c_dp]),
     "cocons_cv_taper": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp]),

@@ -267,25 +267,41 @@ extern "C" int cocons_neg2loglik_grad_vecchia(cocons_fit *f, const double *theta
 
 // Expected information of the Vecchia likelihood: one launch per chunk of vecchia_fisher_chunk observations,
 // one record per observation, and the totals through the gradient's two-stage tree -- a function of n alone, whatever the chunk.
-extern "C" int cocons_fisher_vecchia(cocons_fit *f, const double *theta, int ndir, const double *dirs, double *info,
-                                     double *info_mean)
+//
+// grouped (cocons_fisher_vecchia_grouped): the same arguments, refusals, scratch, totals and host tail; the
+// launches run over the plan's blocks -- one record per block, chunks and segments of blocks -- instead.
+int vecchia_fisher_impl(const char *who, bool grouped, cocons_fit *f, const double *theta, int ndir, const double *dirs,
+                        double *info, double *info_mean)
 {
-    const char *who = "cocons_fisher_vecchia";
     if (int rc = fisher_check_args(who, f, theta, ndir, dirs, info)) return rc;
     FIT_ENTER_ANY(f);
     if (int rc = vecchia_only(f, who)) return rc;
+    if (grouped) if (int rc = vecchia_need_plan(f, who)) return rc;
     VecchiaState *V = f->vecchia.get();
     const int n = f->n, p = f->p, ncol = vecchia_fisher_cols(ndir, p), ng = ndir * (ndir + 1) / 2;
     if (int rc = fisher_check_dirs(who, ndir, dirs, p)) return rc;
-    const int nseg = (n + VECCHIA_SUM_SEG - 1) / VECCHIA_SUM_SEG, chunk = std::min(n, vecchia_fisher_chunk(ndir, p));
-    const int gd = vecchia_fisher_group(V->m, ndir);
-    if (vecchia_fisher_lds_bytes(V->m, ndir, gd) > VECCHIA_FISHER_LDS_MAX)
-        return fail(-1, "%s: %d directions at m = %d need %zu bytes of LDS a workgroup (%zu at most)", who, ndir, V->m,
-                    vecchia_fisher_lds_bytes(V->m, ndir, gd), VECCHIA_FISHER_LDS_MAX);
+    const int units = grouped ? V->grp->blocks : n;           // what a record stands for: a block, or an observation
+    const int nseg = (units + VECCHIA_SUM_SEG - 1) / VECCHIA_SUM_SEG, chunk = std::min(units, vecchia_fisher_chunk(ndir, p));
+    int gd = 0, mc = 0;
+    if (grouped) {
+        const int kb = V->grp->maxrows;
+        vecchia_group_fisher_shape(kb, ndir, &gd, &mc);
+        if (vecchia_group_fisher_lds_bytes(kb, ndir, gd, mc) > VECCHIA_FISHER_LDS_MAX)
+            return fail(-1, "%s: %d directions at blocks of %d rows need %zu bytes of LDS a workgroup (%zu at most)", who, ndir,
+                        kb, vecchia_group_fisher_lds_bytes(kb, ndir, gd, mc), VECCHIA_FISHER_LDS_MAX);
+    } else {
+        gd = vecchia_fisher_group(V->m, ndir);
+        if (vecchia_fisher_lds_bytes(V->m, ndir, gd) > VECCHIA_FISHER_LDS_MAX)
+            return fail(-1, "%s: %d directions at m = %d need %zu bytes of LDS a workgroup (%zu at most)", who, ndir, V->m,
+                        vecchia_fisher_lds_bytes(V->m, ndir, gd), VECCHIA_FISHER_LDS_MAX);
+    }
     hipStream_t s = f->stream;
     const size_t nd = (size_t)ndir * 6 * p;
-    const size_t counts[6] = {(size_t)GSITE_FIELDS * f->npad, (size_t)VECCHIA_GSITE_REC * n, nd, (size_t)chunk * ncol,
-                              (size_t)nseg * ncol, (size_t)ncol};
+    // (the records and their segments are sized by n either way -- blocks <= n --, so the handle holds the same bytes after
+    // the grouped call as after the ungrouped one)
+    const size_t counts[6] = {(size_t)GSITE_FIELDS * f->npad, (size_t)VECCHIA_GSITE_REC * n, nd,
+                              (size_t)std::min(n, vecchia_fisher_chunk(ndir, p)) * ncol,
+                              (size_t)((n + VECCHIA_SUM_SEG - 1) / VECCHIA_SUM_SEG) * ncol, (size_t)ncol};
     DevBuf<double> *bufs[6] = {&V->gsite, &V->gaos, &V->fdirs, &V->frec, &V->fpart, &V->fout};
     size_t bytes = 0;
     for (int b = 0; b < 6; ++b) bytes += std::max(counts[b], bufs[b]->count()) * sizeof(double);
@@ -304,18 +320,21 @@ extern "C" int cocons_fisher_vecchia(cocons_fit *f, const double *theta, int ndi
     launch_grad_site(loc_args(n, p, f->dX, f->dlocs, V->gsite, f->npad, tv, ms.smooth_kind, f->smooth_limits), V->gsite,
                      f->npad, smooth_free, s);
     launch_vecchia_site_rec(V->gsite, f->npad, n, V->gaos, s);
-    VecchiaArgs a;
-    a.m = V->m; a.kb = V->m + 1; a.nbr = V->nbr; a.aosK = V->aos; a.aosG = V->gaos;
-    a.gr = ms.gr; a.nu_fixed = ms.nu_fixed; a.smooth_free = smooth_free;
-    a.nb = 0;                                   // no right-hand sides, no log d
-    a.X = f->dX; a.ldx = n; a.p = p;
-    a.ndir = ndir; a.gd = gd; a.dirs = V->fdirs;
-    a.rec = V->frec; a.ldr = (size_t)chunk;
-    a.fail = f->dinfo;
-    for (int r0 = 0; r0 < n; r0 += chunk) {
-        a.rows = std::min(chunk, n - r0); a.obs0 = r0; a.row0 = r0;
-        launch_vecchia_fisher_blocks(ms.mode, a, s);
-        launch_vecchia_chunk_sums(V->frec, (size_t)chunk, a.rows, ncol, V->fpart, r0 / VECCHIA_SUM_SEG, nseg, s);
+    if (grouped) vecchia_group_fisher_chunks(f, ms, smooth_free, ndir, gd, mc, chunk, nseg);
+    else {
+        VecchiaArgs a;
+        a.m = V->m; a.kb = V->m + 1; a.nbr = V->nbr; a.aosK = V->aos; a.aosG = V->gaos;
+        a.gr = ms.gr; a.nu_fixed = ms.nu_fixed; a.smooth_free = smooth_free;
+        a.nb = 0;                                   // no right-hand sides, no log d
+        a.X = f->dX; a.ldx = n; a.p = p;
+        a.ndir = ndir; a.gd = gd; a.dirs = V->fdirs;
+        a.rec = V->frec; a.ldr = (size_t)chunk;
+        a.fail = f->dinfo;
+        for (int r0 = 0; r0 < n; r0 += chunk) {
+            a.rows = std::min(chunk, n - r0); a.obs0 = r0; a.row0 = r0;
+            launch_vecchia_fisher_blocks(ms.mode, a, s);
+            launch_vecchia_chunk_sums(V->frec, (size_t)chunk, a.rows, ncol, V->fpart, r0 / VECCHIA_SUM_SEG, nseg, s);
+        }
     }
     launch_vecchia_final_sums(V->fpart, nseg, ncol, V->fout, s);
     std::vector<double> h((size_t)ncol);
@@ -329,6 +348,12 @@ extern "C" int cocons_fisher_vecchia(cocons_fit *f, const double *theta, int ndi
         for (int k = 0; k < p; ++k)
             for (int l = 0; l <= k; ++l) info_mean[k * p + l] = info_mean[l * p + k] = r * h[(size_t)ng + k * (k + 1) / 2 + l];
     return 0;
+}
+
+extern "C" int cocons_fisher_vecchia(cocons_fit *f, const double *theta, int ndir, const double *dirs, double *info,
+                                     double *info_mean)
+{
+    return vecchia_fisher_impl("cocons_fisher_vecchia", false, f, theta, ndir, dirs, info, info_mean);
 }
 
 extern "C" int cocons_vecchia_whiten(cocons_fit *f, const double *theta, int c, const double *B, double *out, double *logd)

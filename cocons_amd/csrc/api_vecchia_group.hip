@@ -2,7 +2,8 @@
 // the host; cocons_vecchia_group_table, the expanded table of any partition; cocons_vecchia_set_groups, the plan of a
 // partition on a Vecchia handle whose table is closed under it; cocons_fit_create_vecchia_grouped, the three in one call; and
 // cocons_neg2loglik_vecchia_grouped / cocons_vecchia_whiten_grouped, the value and the whitening with one factorisation per
-// block, and cocons_neg2loglik_grad_vecchia_grouped, the value and the gradient from it.  A grouped evaluation
+// block, cocons_neg2loglik_grad_vecchia_grouped, the value and the gradient from it, and
+// cocons_fisher_vecchia_grouped, the expected information from it.  A grouped evaluation
 // is the ungrouped one with launch_vecchia_group_blocks in the place of launch_vecchia_blocks: the same records, right-hand
 // sides, per-row arrays, totals and status word, and therefore the same bits.
 #include "fit.hpp"
@@ -100,6 +101,29 @@ void vecchia_group_grad_chunks(cocons_fit *f, const ModeSel &ms, int smooth_free
         a.blocks = std::min(chunk, G->blocks - b0); a.blk0 = b0;
         launch_vecchia_group_grad_blocks(ms.mode, a, f->stream);
         launch_vecchia_chunk_sums(V->grec, (size_t)chunk, a.blocks, ncol, V->gpart, b0 / VECCHIA_SUM_SEG, nseg, f->stream);
+    }
+}
+
+// The grouped information's launches: as vecchia_group_grad_chunks, with the information's records and scratch.
+void vecchia_group_fisher_chunks(cocons_fit *f, const ModeSel &ms, int smooth_free, int ndir, int gd, int mc, int chunk, int nseg)
+{
+    VecchiaState *V = f->vecchia.get();
+    const VecchiaGroupState *G = V->grp.get();
+    const int n = f->n, ncol = vecchia_fisher_cols(ndir, f->p);
+    VecchiaGroupArgs a;
+    a.kb = G->maxrows;
+    a.off = G->off; a.rows = G->rows; a.mask = G->mask;
+    a.order = (G->by_size && G->blocks <= chunk) ? G->order.get() : nullptr;
+    a.aosK = V->aos; a.aosG = V->gaos; a.gr = ms.gr; a.nu_fixed = ms.nu_fixed; a.smooth_free = smooth_free;
+    a.nb = 0;                                   // no right-hand sides, no log d
+    a.X = f->dX; a.ldx = n; a.p = f->p;
+    a.ndir = ndir; a.gd = gd; a.mc = mc; a.dirs = V->fdirs;
+    a.rec = V->frec; a.ldr = (size_t)chunk;
+    a.fail = f->dinfo;
+    for (int b0 = 0; b0 < G->blocks; b0 += chunk) {
+        a.blocks = std::min(chunk, G->blocks - b0); a.blk0 = b0;
+        launch_vecchia_group_fisher_blocks(ms.mode, a, f->stream);
+        launch_vecchia_chunk_sums(V->frec, (size_t)chunk, a.blocks, ncol, V->fpart, b0 / VECCHIA_SUM_SEG, nseg, f->stream);
     }
 }
 
@@ -275,4 +299,10 @@ extern "C" int cocons_neg2loglik_grad_vecchia_grouped(cocons_fit *f, const doubl
 {
     return vecchia_grad_impl("cocons_neg2loglik_grad_vecchia_grouped", true, f, theta, mean, c, B, sum_logliks, parts,
                              grad_theta, grad_quad, grad_mean);
+}
+
+extern "C" int cocons_fisher_vecchia_grouped(cocons_fit *f, const double *theta, int ndir, const double *dirs, double *info,
+                                             double *info_mean)
+{
+    return vecchia_fisher_impl("cocons_fisher_vecchia_grouped", true, f, theta, ndir, dirs, info, info_mean);
 }

@@ -318,6 +318,7 @@ struct VecchiaState {
     // cocons_fisher_vecchia, allocated by its first call (gsite and gaos above are shared with the gradient)
     DevBuf<double> fdirs;         // ndir x 6 p: the directions
     DevBuf<double> frec;          // vecchia_fisher_chunk x vecchia_fisher_cols: the per-observation records of one chunk
+                                  // (the grouped information, DESIGN.md 4aa: one record per block; fpart and fout serve it too)
     DevBuf<double> fpart;         // their first-stage sums, all segments of n
     DevBuf<double> fout;          // the totals: vecchia_fisher_cols
     // cocons_vecchia_predict_knn, made by its first call: the grid over the observations
@@ -776,6 +777,11 @@ int vecchia_grad_impl(const char *who, bool grouped, cocons_fit *f, const double
                       double *grad_mean);
 int vecchia_need_plan(cocons_fit *f, const char *who);
 void vecchia_group_grad_chunks(cocons_fit *f, const ModeSel &ms, int smooth_free, int nc, int chunk, int nseg);
+// both information entries of a Vecchia handle (api_vecchia.hip); grouped: the launches over the plan's blocks
+// (api_vecchia_group.hip)
+int vecchia_fisher_impl(const char *who, bool grouped, cocons_fit *f, const double *theta, int ndir, const double *dirs,
+                        double *info, double *info_mean);
+void vecchia_group_fisher_chunks(cocons_fit *f, const ModeSel &ms, int smooth_free, int ndir, int gd, int mc, int chunk, int nseg);
 // ... and what api_vecchia_sim.hip offers api_vecchia_cv.hip: the coefficients of the rows n_fixed .. n - 1 for
 // theta into the handle's sim->coef and the status word home: 0, the smallest failing 1-based row, or < 0
 int vecchia_sim_coefs(cocons_fit *f, const char *who, const double *theta, int n_fixed);

@@ -778,6 +778,10 @@ struct VecchiaGroupArgs {
     int smooth_free = 0;
     const double *X = nullptr; int ldx = 0, p = 0;
     double *rec = nullptr; size_t ldr = 0;
+    // the information launch only (launch_vecchia_group_fisher_blocks); it uses blk0, aosG, smooth_free, X and
+    // rec too, and no right-hand sides (nb = 0, logd null)
+    int ndir = 0, gd = 0, mc = 0;      // directions, directions a group and members a chunk (vecchia_group_fisher_shape)
+    const double *dirs = nullptr;      // ndir tables of 6 x p on the device
 };
 void launch_vecchia_group_blocks(int mode, const VecchiaGroupArgs &a, hipStream_t s);
 // The gradient variant of the grouped launch over the blocks blk0 .. blk0 + blocks - 1: logd and Y as there (the same code),
@@ -786,6 +790,14 @@ void launch_vecchia_group_blocks(int mode, const VecchiaGroupArgs &a, hipStream_
 // vecchia_group_grad_lds_bytes(kb): 78 144 bytes at kb = 64, above 64 KB from kb = 54 on.
 size_t vecchia_group_grad_lds_bytes(int kb);
 void launch_vecchia_group_grad_blocks(int mode, const VecchiaGroupArgs &a, hipStream_t s);
+// The information variant of the grouped launch (no right-hand sides): per BLOCK one record of vecchia_fisher_cols(ndir, p)
+// doubles in launch_vecchia_fisher_blocks' layout -- the sum of the records its members would give on the expanded table, every
+// sum in an order that is a function of the block alone.  vecchia_group_fisher_shape gives gd in {4, 8, 16} and mc >= 1 with
+// gd mc <= 64; the launch's dynamic LDS is vecchia_group_fisher_lds_bytes(kb, ndir, gd, mc), which the caller holds to
+// VECCHIA_FISHER_LDS_MAX (157 952 bytes at kb = 64, ndir = 16: gd = 16, mc = 4).
+size_t vecchia_group_fisher_lds_bytes(int kb, int ndir, int gd, int mc);
+void vecchia_group_fisher_shape(int kb, int ndir, int *gd, int *mc);
+void launch_vecchia_group_fisher_blocks(int mode, const VecchiaGroupArgs &a, hipStream_t s);
 
 // ---- U^-1 of a Vecchia fit: coefficients, levels and the level solve (vecchia_sim.hip) -------------------------
 constexpr int VECCHIA_SIM_FUSE_ITEMS = 256;     // a level of at most this many (row, column) pairs may join a fused run

@@ -119,22 +119,7 @@ constexpr int VECCHIA_GX = GSITE_FIELDS + 2 + 2 * GFAM;
 //   wts   gd x GFAM x kb     the rows' site weights w_a[f][row] of the group's directions;
 //   stg   gd x 64            a pass of 64 pairs: the entry of C_a per direction (then, once, the p sums u of the mean block);
 //   gall  ndir x kb          g_a = L^-1 (C_a s) of every direction, what the Gram is formed of.
-constexpr int VECCHIA_FX = GSITE_FIELDS + 2;
-
-// Forward substitution over the neighbours' rows for VECCHIA_G right-hand sides in registers, lane = row: lane r ends with
-// b_r - sum_{j < r} C(r, j) y_j, j ascending (the numerator of y_r: the steps from r on leave it alone).
-__device__ __forceinline__ void vecchia_forward(double (&b)[VECCHIA_G], const double *tri, int myrow, double piv_mine, int lane,
-                                                int k, int nrows)
-{
-    for (int j = 0; j < k; ++j) {
-        const double l = (lane > j && lane < nrows) ? tri[myrow + j] : 0.0;
-#pragma unroll
-        for (int g = 0; g < VECCHIA_G; ++g) {
-            const double yj = __shfl(lane == j ? b[g] / piv_mine : 0.0, j);
-            b[g] -= l * yj;
-        }
-    }
-}
+//   (VECCHIA_FX = GSITE_FIELDS + 2 and vecchia_forward stand in vecchia_tri.hpp: the grouped launch uses them too)
 
 __device__ __forceinline__ double vecchia_wave_sum(double v)
 {

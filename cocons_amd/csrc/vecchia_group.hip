@@ -21,6 +21,13 @@
 // members' backward solves are dealt over the four wavefronts, and every pair's partials are evaluated ONCE by one of the
 // VECCHIA_GROUP_THREADS threads and weighted with the two sums over the members, ascending.  One record per block.
 //
+//
+// FISH: the same gather, pair loop and factorisation, the members' backward solves without h, then the block's
+// share of the expected information.  The member at position p is 4t's block on the leading p + 1 rows: with
+// q_{a,p} = C_a[0..p, 0..p] s_p and g_{a,p} = L_{0..p}^-1 q_{a,p} it gives sum_{j < p} g_a[j] g_b[j] + g_a[p] g_b[p] / 2, and the
+// block the sum over its members.  The factor stays in LDS for the forward solves; every pair's partials are evaluated once
+// per walk and serve all the members of a chunk and all the directions of a group.  One record per block.
+//
 // Compile with -ffp-contract=off, like vecchia.hip: the products and sums stand as written.
 #include <hip/hip_runtime.h>
 #include <atomic>
@@ -47,6 +54,14 @@ namespace cocons {
 //   ys, uv  kb each          sum_c y_pc of the members, and u = sum_p ys[p] s_p;
 //   gs    2 GFAM x kb        the rows' site sums: the log-determinant's share per family, then the quadratic forms';
 //   red   2 x 4              the wavefronts' shares of the two global-range sums.
+// FISH (vecchia_group_fisher_lds_bytes) keeps the factor in tri and puts behind it, for chunks of mc members and groups of gd
+// directions (vecchia_group_fisher_shape):
+//   sm    kb (kb + 1) / 2    row p of a member: s_p;
+//   sp    VECCHIA_FX x kb    the rows' site derivatives, then the members' positions, ascending (kb ints);
+//   wts   gd x GFAM x kb     the rows' site weights w_a[f][row] of the group's directions;
+//   stg   gd x T             a pass of T = VECCHIA_GROUP_THREADS pairs: the entry of C_a per direction (and, once per chunk,
+//                            the members' sums u_p of the mean block: mc x p <= 4 T doubles);
+//   gall  mc x ndir x kb     g_{a,p} of the chunk's members and every direction, what the Gram is formed of.
 constexpr int VECCHIA_GROUP_STGF = 2 * GFAM + 2;        // a staged pair: da, db, 2 W_log, 2 W_quad
 constexpr int VECCHIA_GROUP_STG = VECCHIA_GROUP_STGF * VECCHIA_GROUP_THREADS;
 constexpr int VECCHIA_GROUP_GX = GSITE_FIELDS + 2 + 2 * GFAM;
@@ -59,13 +74,21 @@ __device__ __forceinline__ double vecchia_group_wave_sum(double v)
     return v;
 }
 
-template <int MODE, bool GRAD = false>
+constexpr int VECCHIA_GROUP_FQ = 16;                   // FISH: (member, direction) accumulators a thread keeps
+static_assert(VECCHIA_GROUP_FQ == VECCHIA_FD && VECCHIA_GROUP_FQ % VECCHIA_G == 0, "a thread's accumulators go through "
+              "vecchia_forward four at a time, and one wavefront can hold a whole group of directions of one member");
+static_assert(COCONS_P_MAX * (VECCHIA_GROUP_FQ * VECCHIA_GROUP_WAVES / VECCHIA_G) <= VECCHIA_G * VECCHIA_GROUP_THREADS,
+              "the members' sums u_p of a chunk fit the staging of the narrowest group");
+
+template <int MODE, bool GRAD = false, bool FISH = false>
 __global__ void __launch_bounds__(VECCHIA_GROUP_THREADS)
 vecchia_group_kernel(VecchiaGroupArgs a)
 {
+    static_assert(!(GRAD && FISH), "the gradient and the information are launches of their own");
+    constexpr bool DER = GRAD || FISH;             // the launches that gather the site derivatives and solve for the s_p
     extern __shared__ double vecchia_group_lds[];
     const int lane = threadIdx.x, kb = a.kb;
-    const int blk = (GRAD ? a.blk0 : 0) + (a.order ? a.order[blockIdx.x] : (int)blockIdx.x);
+    const int blk = (DER ? a.blk0 : 0) + (a.order ? a.order[blockIdx.x] : (int)blockIdx.x);
     const int off = a.off[blk], nrows = a.off[blk + 1] - off;
     const unsigned long long members = a.mask[blk];
     const int ntri = kb * (kb + 1) / 2;
@@ -73,8 +96,10 @@ vecchia_group_kernel(VecchiaGroupArgs a)
     double *tri = par + LOCP_FIELDS * kb;
     [[maybe_unused]] double *sm = tri + ((GRAD && ntri < VECCHIA_GROUP_STG) ? VECCHIA_GROUP_STG : ntri);
     [[maybe_unused]] double *nm = sm + ntri;
-    [[maybe_unused]] double *sp = nm + ntri;
-    int *nb = GRAD ? (int *)(sp + VECCHIA_GROUP_GX * kb + 2 * VECCHIA_GROUP_WAVES) : (int *)(tri + ntri);
+    [[maybe_unused]] double *sp = FISH ? nm : nm + ntri;          // (FISH has no rows of N)
+    int *nb = GRAD   ? (int *)(sp + VECCHIA_GROUP_GX * kb + 2 * VECCHIA_GROUP_WAVES)
+              : FISH ? (int *)(sp + VECCHIA_FX * kb + a.gd * (GFAM * kb + VECCHIA_GROUP_THREADS) + a.ndir * a.mc * kb)
+                     : (int *)(tri + ntri);
     if (nrows < 1 || nrows > kb) return;          // (a plan the host checked has none)
 
     if (lane < nrows) nb[lane] = a.rows[off + lane];
@@ -84,12 +109,13 @@ vecchia_group_kernel(VecchiaGroupArgs a)
         if (f >= LOCP_FIELDS) continue;
         par[f * kb + r] = a.aosK[(size_t)nb[r] * VECCHIA_REC + f];
     }
-    if constexpr (GRAD) {
+    if constexpr (DER) {
         for (int e = lane; e < nrows * VECCHIA_GSITE_REC; e += VECCHIA_GROUP_THREADS) {
             const int r = e / VECCHIA_GSITE_REC, f = e % VECCHIA_GSITE_REC;
             sp[f * kb + r] = a.aosG[(size_t)nb[r] * VECCHIA_GSITE_REC + f];
         }
-        for (int e = lane; e < nrows * (nrows + 1) / 2; e += VECCHIA_GROUP_THREADS) nm[e] = 0.0;
+        if constexpr (GRAD)
+            for (int e = lane; e < nrows * (nrows + 1) / 2; e += VECCHIA_GROUP_THREADS) nm[e] = 0.0;
     }
     __syncthreads();
     // the block: pair t = r (r - 1) / 2 + c is (r, c), r > c, the EARLIER row on the `ii` side (vecchia_block_kernel's order)
@@ -123,9 +149,9 @@ vecchia_group_kernel(VecchiaGroupArgs a)
         if (lane == 0 && q < nrows) atomicMin(a.fail, nb[q] + 1);
         return;
     }
-    if (GRAD && lane < nrows) tri[tri_at(lane, lane)] = piv_mine;     // (the solves of the other wavefronts read the pivots here)
+    if (DER && lane < nrows) tri[tri_at(lane, lane)] = piv_mine;      // (the solves of the other wavefronts read the pivots here)
     __syncthreads();
-    if (!GRAD && lane >= 64) return;               // (no barrier from here on)
+    if (!DER && lane >= 64) return;                // (no barrier from here on)
     // forward substitution, VECCHIA_G right-hand sides at a time: lane r ends with b_r - sum_{j < r} C(r, j) y_j, j ascending.
     // A lane at or in front of step j takes no part in it: its value must not see a y_j that is not finite.
     // GRAD: every lane j ends with the numerator of w_c[j], so N[p, j] = sum_c w_c[p] w_c[j] of the member rows p >= j and
@@ -133,7 +159,7 @@ vecchia_group_kernel(VecchiaGroupArgs a)
     const bool member = lane < nrows && ((members >> lane) & 1ull);
     const int site = lane < nrows ? nb[lane] : 0;
     [[maybe_unused]] double ysum = 0.0;
-    for (int c0 = 0; lane < 64 && c0 < a.nb; c0 += VECCHIA_G) {        // (GRAD: the other wavefronts go on to the barrier)
+    for (int c0 = 0; !FISH && lane < 64 && c0 < a.nb; c0 += VECCHIA_G) {   // (GRAD: the other wavefronts go on to the barrier)
         double b[VECCHIA_G];
 #pragma unroll
         for (int g = 0; g < VECCHIA_G; ++g)
@@ -176,7 +202,7 @@ vecchia_group_kernel(VecchiaGroupArgs a)
             }
         }
     }
-    if (member && a.logd) a.logd[site] = log(piv_mine);
+    if (!FISH && member && a.logd) a.logd[site] = log(piv_mine);
     if constexpr (GRAD) {
         const int wv = lane >> 6, ln = lane & 63, T = VECCHIA_GROUP_THREADS;
         double *ys = sp + GSITE_FIELDS * kb, *uv = ys + kb, *gs = uv + kb, *red = gs + 2 * GFAM * kb;
@@ -322,6 +348,184 @@ vecchia_group_kernel(VecchiaGroupArgs a)
             a.rec[(size_t)(2 * GFAM * p + 1) * a.ldr + b] = gq;
         }
     }
+    if constexpr (FISH) {
+        const int wv = lane >> 6, ln = lane & 63, T = VECCHIA_GROUP_THREADS;
+        const int p = a.p, ndir = a.ndir, gw = a.gd, mc = a.mc, b = blk - a.blk0;
+        const int ng = ndir * (ndir + 1) / 2, nmem = __popcll(members);
+        int *mpos = (int *)(sp + GSITE_FIELDS * kb);
+        double *wts = sp + VECCHIA_FX * kb, *stg = wts + gw * GFAM * kb, *gall = stg + gw * T;
+        if (member) mpos[__popcll(members & ((1ull << lane) - 1ull))] = lane;
+        // The members' backward solves as in GRAD, without h: member i (ascending) on wavefront i mod 4, lane = row.
+        {
+            const double ipiv = ln < nrows ? 1.0 / tri[tri_at(ln, ln)] : 0.0;
+            int rank = 0;
+            for (unsigned long long rest = members; rest; rest &= rest - 1, ++rank) {
+                if ((rank & (VECCHIA_GROUP_WAVES - 1)) != wv) continue;
+                const int pp = __builtin_ctzll(rest);
+                double rs = ln == pp ? 1.0 : 0.0, s_mine = 0.0;
+                for (int j = pp; j >= 0; --j) {
+                    const double xs = __shfl(rs * ipiv, j);
+                    if (ln == j) s_mine = xs;
+                    if (ln < j) rs -= tri[tri_at(j, 0) + ln] * xs;
+                }
+                if (ln <= pp) sm[tri_at(pp, ln)] = s_mine;
+            }
+        }
+        __syncthreads();
+        // every wavefront solves forward with lane = row: its row of the factor and its pivot
+        const int wrow = tri_at(ln, 0);
+        const double wpiv = ln < nrows ? tri[tri_at(ln, ln)] : 1.0;
+        // A thread's VECCHIA_GROUP_FQ accumulators are the slots x = wv FQ + i of the chunk: member x / gw of the chunk,
+        // direction x mod gw of the group.  gw is a multiple of VECCHIA_G, so four slots in a row share their member.
+        constexpr int NQ = VECCHIA_GROUP_FQ, NB = NQ / VECCHIA_G;
+        for (int m0 = 0; m0 < nmem; m0 += mc) {
+            const int cm = min(mc, nmem - m0);
+            // u_p = sum_{row <= p} s_p[row] X[site(row), .] of the chunk's members, the rows ascending, and their share of the
+            // mean block: entry (k, l) is one thread's running sum over all the members, ascending, kept in the record
+            for (int e = lane; e < cm * p; e += T) {
+                const int pp = mpos[m0 + e / p], kx = e % p;
+                const double *sv = sm + tri_at(pp, 0);
+                double s = 0.0;
+                for (int rr = 0; rr <= pp; ++rr) s += sv[rr] * a.X[(size_t)nb[rr] + (size_t)kx * a.ldx];
+                stg[e] = s;
+            }
+            __syncthreads();
+            for (int o = lane; o < p * (p + 1) / 2; o += T) {
+                int ra, cb;
+                tri_pair(o, ra, cb);
+                double *dst = a.rec + (size_t)(ng + o) * a.ldr + b;
+                double s = m0 ? *dst : 0.0;
+                for (int mi = 0; mi < cm; ++mi) s += stg[mi * p + ra - 1] * stg[mi * p + cb];
+                *dst = s;
+            }
+            int pm[NB], db[NB];
+#pragma unroll
+            for (int k = 0; k < NB; ++k) {
+                const int x = wv * NQ + k * VECCHIA_G, mi = x / gw;
+                pm[k] = mi < cm ? mpos[m0 + mi] : -1;
+                db[k] = x % gw;
+            }
+            for (int d0 = 0; d0 < ndir; d0 += gw) {
+                const int gd = min(gw, ndir - d0);
+                __syncthreads();           // the sums u_p, or the previous group's walk, have left wts and stg
+                // the site weights of the group's directions (vecchia_block_kernel's, 4t step 1)
+                for (int e = lane; e < gd * GFAM * nrows; e += T) {
+                    const int rr = e % nrows, f = (e / nrows) % GFAM, d = e / (nrows * GFAM);
+                    const double *v = a.dirs + ((size_t)(d0 + d) * GFAM + f) * p;
+                    double w = 0.0;
+                    for (int kx = (f == TH_SCALE_ ? 1 : 0); kx < p; ++kx) w += a.X[(size_t)nb[rr] + (size_t)kx * a.ldx] * v[kx];
+                    wts[(d * GFAM + f) * kb + rr] = f == TH_SCALE_ ? 2.0 * w : w;
+                }
+                __syncthreads();
+                // q_{a,p}[row] in registers: the diagonal first, then the row's pairs pass by pass (the gradient walk's order)
+                double q[NQ];
+#pragma unroll
+                for (int i = 0; i < NQ; ++i) q[i] = 0.0;
+                if (ln < nrows) {
+                    const double dsd = sp[3 * kb + ln], dng = par[12 * kb + ln];
+#pragma unroll
+                    for (int k = 0; k < NB; ++k) {
+                        if (pm[k] < ln) continue;
+                        const double so = sm[tri_at(pm[k], ln)];
+#pragma unroll
+                        for (int g = 0; g < VECCHIA_G; ++g) {
+                            const int d = db[k] + g;
+                            if (d < gd)
+                                q[k * VECCHIA_G + g] =
+                                    (dsd * wts[(d * GFAM + TH_SD_) * kb + ln] + dng * wts[(d * GFAM + TH_NG_) * kb + ln]) * so;
+                        }
+                    }
+                }
+                for (int t0 = 0; t0 < npairs; t0 += T) {
+                    const int t = t0 + lane;
+                    double da[GFAM], db_[GFAM], dg = 0.0;
+                    int r = 0, c = 0;
+#pragma unroll
+                    for (int f = 0; f < GFAM; ++f) { da[f] = 0.0; db_[f] = 0.0; }
+                    if (t < npairs) {
+                        tri_pair(t, r, c);
+                        pair_partials<MODE>(par, (size_t)kb, sp, (size_t)kb, a.gr, a.nu_fixed, a.smooth_free, c, r, da, db_, dg);
+                    }
+                    for (int d = 0; d < gd; ++d) {
+                        double e = 0.0;
+                        if (t < npairs) {
+                            const double *w = wts + d * GFAM * kb;
+                            e = dg * a.dirs[((size_t)(d0 + d) * GFAM + TH_SCALE_) * p];
+#pragma unroll
+                            for (int f = 0; f < GFAM; ++f) {
+                                e += da[f] * w[f * kb + c];
+                                e += db_[f] * w[f * kb + r];
+                            }
+                        }
+                        stg[d * T + lane] = e;
+                    }
+                    __syncthreads();
+                    if (ln < nrows) {
+                        // the row's pairs (ln, c), c ascending, then (r, ln), r ascending; member p takes the pairs with r <= p
+                        const int tend = min(t0 + T, npairs), mine0 = ln * (ln - 1) / 2;
+                        for (int u = max(t0, mine0); u < min(tend, mine0 + ln); ++u) {
+#pragma unroll
+                            for (int k = 0; k < NB; ++k) {
+                                if (pm[k] < ln) continue;
+                                const double so = sm[tri_at(pm[k], 0) + (u - mine0)];
+#pragma unroll
+                                for (int g = 0; g < VECCHIA_G; ++g)
+                                    if (db[k] + g < gd) q[k * VECCHIA_G + g] += stg[(db[k] + g) * T + (u - t0)] * so;
+                            }
+                        }
+                        int r_lo, r_hi, c_;
+                        tri_pair(t0, r_lo, c_);
+                        tri_pair(tend - 1, r_hi, c_);
+                        for (int rr = max(r_lo, ln + 1); rr <= r_hi; ++rr) {
+                            const int u = rr * (rr - 1) / 2 + ln;
+                            if (u < t0 || u >= tend) continue;
+#pragma unroll
+                            for (int k = 0; k < NB; ++k) {
+                                if (pm[k] < rr) continue;
+                                const double so = sm[tri_at(pm[k], 0) + rr];
+#pragma unroll
+                                for (int g = 0; g < VECCHIA_G; ++g)
+                                    if (db[k] + g < gd) q[k * VECCHIA_G + g] += stg[(db[k] + g) * T + (u - t0)] * so;
+                            }
+                        }
+                    }
+                    __syncthreads();
+                }
+                // g_{a,p} = L_{0..p}^-1 q_{a,p}: the likelihood's substitution on the leading p + 1 rows (pm and db are the
+                // same in every lane of a wavefront)
+#pragma unroll
+                for (int k = 0; k < NB; ++k) {
+                    if (pm[k] < 0 || db[k] >= gd) continue;
+                    double bb[VECCHIA_G];
+#pragma unroll
+                    for (int g = 0; g < VECCHIA_G; ++g) bb[g] = q[k * VECCHIA_G + g];
+                    vecchia_forward(bb, tri, wrow, wpiv, ln, pm[k], pm[k] + 1);
+                    const int mi = (wv * NQ + k * VECCHIA_G) / gw;
+#pragma unroll
+                    for (int g = 0; g < VECCHIA_G; ++g)
+                        if (db[k] + g < gd && ln <= pm[k]) gall[((size_t)mi * ndir + d0 + db[k] + g) * kb + ln] = bb[g] / wpiv;
+                }
+            }
+            __syncthreads();
+            // The chunk's share of the Gram, entry o = a (a + 1) / 2 + b: one thread's running sum over all the members,
+            // ascending, the rows ascending within a member -- kept in the record from chunk to chunk, so it does not depend on
+            // mc
+            for (int o = lane; o < ng; o += T) {
+                int ra, cb;
+                tri_pair(o, ra, cb);       // (the strict triangle's numbering of (a + 1, b))
+                double *dst = a.rec + (size_t)o * a.ldr + b;
+                double s = m0 ? *dst : 0.0;
+                for (int mi = 0; mi < cm; ++mi) {
+                    const int pp = mpos[m0 + mi];
+                    const double *ga = gall + ((size_t)mi * ndir + ra - 1) * kb, *gb = gall + ((size_t)mi * ndir + cb) * kb;
+                    for (int j = 0; j < pp; ++j) s += ga[j] * gb[j];
+                    s += 0.5 * (ga[pp] * gb[pp]);
+                }
+                *dst = s;
+            }
+            __syncthreads();               // (the next chunk writes stg and gall)
+        }
+    }
 }
 
 void launch_vecchia_group_blocks(int mode, const VecchiaGroupArgs &a, hipStream_t s)
@@ -361,6 +565,49 @@ void launch_vecchia_group_grad_blocks(int mode, const VecchiaGroupArgs &a, hipSt
     case MODE_THREEHALF: vecchia_group_grad_launch<MODE_THREEHALF>(a, shm, s); break;
     case MODE_FIVEHALF: vecchia_group_grad_launch<MODE_FIVEHALF>(a, shm, s); break;
     default: vecchia_group_grad_launch<MODE_GEOM>(a, shm, s); break;
+    }
+}
+
+// FISH.  The shape of a launch: a thread keeps VECCHIA_GROUP_FQ = 16 accumulators and the four wavefronts 64 slots, so gd
+// directions a group leave 64 / gd members a chunk.  gd is the smallest of 4, 8, 16 that holds ndir (16 from ndir = 9 on: the
+// fewest pair walks, ceil(members / mc) ceil(ndir / gd)), mc = 64 / gd; while the LDS is above VECCHIA_FISHER_LDS_MAX first mc
+// is halved (gall shrinks), then gd (wts and stg shrink).
+size_t vecchia_group_fisher_lds_bytes(int kb, int ndir, int gd, int mc)
+{
+    const size_t k = (size_t)kb, ntri = k * (k + 1) / 2;
+    return (LOCP_FIELDS * k + 2 * ntri + VECCHIA_FX * k + (size_t)gd * (GFAM * k + VECCHIA_GROUP_THREADS) +
+            (size_t)ndir * mc * k) * sizeof(double) + k * sizeof(int);
+}
+
+void vecchia_group_fisher_shape(int kb, int ndir, int *gd_out, int *mc_out)
+{
+    int gd = VECCHIA_G;
+    while (gd < VECCHIA_GROUP_FQ && gd < ndir) gd *= 2;
+    int mc = VECCHIA_GROUP_FQ * VECCHIA_GROUP_WAVES / gd;
+    while (mc > 1 && vecchia_group_fisher_lds_bytes(kb, ndir, gd, mc) > VECCHIA_FISHER_LDS_MAX) mc /= 2;
+    while (gd > VECCHIA_G && vecchia_group_fisher_lds_bytes(kb, ndir, gd, mc) > VECCHIA_FISHER_LDS_MAX) gd /= 2;
+    *gd_out = gd;
+    *mc_out = mc;
+}
+
+template <int MODE> static void vecchia_group_fisher_launch(const VecchiaGroupArgs &a, size_t shm, hipStream_t s)
+{
+    static std::atomic<unsigned long long> attr_done{0};
+    if (shm > 64 * 1024)
+        set_dynamic_lds_once((const void *)vecchia_group_kernel<MODE, false, true>, VECCHIA_FISHER_LDS_MAX, attr_done);
+    hipLaunchKernelGGL((vecchia_group_kernel<MODE, false, true>), dim3((unsigned)a.blocks), dim3(VECCHIA_GROUP_THREADS), shm, s,
+                       a);
+}
+
+void launch_vecchia_group_fisher_blocks(int mode, const VecchiaGroupArgs &a, hipStream_t s)
+{
+    if (a.blocks <= 0) return;
+    const size_t shm = vecchia_group_fisher_lds_bytes(a.kb, a.ndir, a.gd, a.mc);
+    switch (mode) {
+    case MODE_HALF: vecchia_group_fisher_launch<MODE_HALF>(a, shm, s); break;
+    case MODE_THREEHALF: vecchia_group_fisher_launch<MODE_THREEHALF>(a, shm, s); break;
+    case MODE_FIVEHALF: vecchia_group_fisher_launch<MODE_FIVEHALF>(a, shm, s); break;
+    default: vecchia_group_fisher_launch<MODE_GEOM>(a, shm, s); break;
     }
 }
 

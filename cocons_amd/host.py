@@ -1156,15 +1156,18 @@ def fisher_to_par(info_table, info_mean, par, par_pos):
     return Jt @ np.asarray(info_table, dtype=np.float64) @ Jt.T + Jm @ np.asarray(info_mean, dtype=np.float64) @ Jm.T
 
 
-def _fisher_in_par(par, par_pos, handle, probes=None):
+def _fisher_in_par(par, par_pos, handle, probes=None, grouped=False):
     """A handle's `fisher_core` in the optimiser's coordinates: the rows of `fisher_jacobian` that move the table go to the
     device as directions (a pure mean parameter costs nothing there), J_m info_mean J_m' is added for the mean; the block
-    between them is 0.  `handle`: a `_borrowed`; `probes(f)`: the probes a tapered handle's core takes."""
+    between them is 0.  `handle`: a `_borrowed`; `probes(f)`: the probes a tapered handle's core takes; `grouped`: a Vecchia
+    handle's core on the grouped schedule."""
     par = np.asarray(par, dtype=np.float64).ravel()
     tl = getModelLists(par, par_pos, "diff")
     Jt, Jm = fisher_jacobian(par, par_pos)
     with handle as f:
         more = {} if probes is None else {"probes": probes(f)}
+        if grouped:
+            more["grouped"] = True
         cov = np.flatnonzero(np.any(Jt != 0, axis=1))
         sub, info_mean = f.fisher_core(tl, Jt[cov] if cov.size else Jt[:1], **more)
         info = Jm @ info_mean @ Jm.T
@@ -1679,17 +1682,20 @@ class CoconsVecchiaFit(_Handle):
         _lib.check(st, entry)
         return val.value, parts, gt, gq, gm
 
-    def fisher_core(self, theta_list, dirs):
+    def fisher_core(self, theta_list, dirs, grouped=False):
         """Expected information of the Vecchia likelihood at `theta_list` (cocons_fisher_vecchia), `dirs` as for
         `CoconsFit.fisher_core` (ndir x 6 x p or ndir x 6p).  Returns (info ndir x ndir, info_mean p x p): the sums over the
         n blocks of the block's information minus that of its neighbours alone, and r (U X)'(U X) with U the whitening.
-        Both are Gram matrices, symmetric to the bit; with every predecessor in the table they are the dense ones."""
+        Both are Gram matrices, symmetric to the bit; with every predecessor in the table they are the dense ones.  `grouped`:
+        on the plan of `set_groups`, one factorisation per block and every pair of a block once per walk
+        (cocons_fisher_vecchia_grouped) -- the information of the same model to rounding."""
+        entry = "cocons_fisher_vecchia_grouped" if grouped else "cocons_fisher_vecchia"
         T = theta_table(theta_list)
         D = np.ascontiguousarray(np.asarray(dirs, dtype=np.float64).reshape(-1, 6 * self.p))
         nd = D.shape[0]
         info = np.zeros((nd, nd))
         info_mean = np.zeros((self.p, self.p))
-        _lib.check(self._L.cocons_fisher_vecchia(self._h, _p(T), nd, _p(D), _p(info), _p(info_mean)), "cocons_fisher_vecchia")
+        _lib.check(getattr(self._L, entry)(self._h, _p(T), nd, _p(D), _p(info), _p(info_mean)), entry)
         return info, info_mean
 
     def _whiten(self, theta_list, B, entry):
@@ -1872,15 +1878,16 @@ def GetNeg2loglikelihoodVecchia_grad(theta, par_pos, nn, locs, x_covariates, smo
                       core, n, grad=True)
 
 
-def getFisher_vecchia(par, par_pos, locs, x_covariates, smooth_limits, z, n, nn, fit=None):
+def getFisher_vecchia(par, par_pos, locs, x_covariates, smooth_limits, z, n, nn, fit=None, grouped=False):
     """The P x P expected information of the Vecchia fit for the neighbour table `nn` in the optimiser's coordinates, rows
     and columns in `par`'s order, from ONE pass over the n blocks (cocons_fisher_vecchia): the expectation under the model of
     the Hessian of half of `GetNeg2loglikelihoodVecchia` without its penalty -- what GpGp returns as `info`.  It goes
     through `fisher_jacobian` as `getFisher_dense` does: the covariance block from the Jacobian's rows as directions, then
     J_m info_mean J_m' for the mean; the block between them is 0.  A Gram matrix, so solve() of it gives non-negative
     variances.  It is not the observed Hessian and not the Godambe (sandwich) information of the composite likelihood.
-    A failing block raises CholeskyError."""
-    return _fisher_in_par(par, par_pos, _vecchia(fit, locs, x_covariates, z, smooth_limits, nn))
+    A failing block raises CholeskyError.  `grouped`: the grouped model of `nn` with the information on the grouped schedule
+    (cocons_fisher_vecchia_grouped), as in GetNeg2loglikelihoodVecchia_grad."""
+    return _fisher_in_par(par, par_pos, _vecchia(fit, locs, x_covariates, z, smooth_limits, nn, grouped), grouped=grouped)
 
 
 def _vecchia_gls_resid(f, tl, z, x_betas, grouped=False):

@@ -517,8 +517,9 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
 # expected information of the Vecchia fit over theta (cocons_fisher_vecchia; DESIGN.md 4t), P x P in theta's order, from one
 # pass over the n blocks: the expectation at the model of the Hessian of half of the Vecchia -2 log-likelihood, without the
 # penalty -- what GpGp calls info.  Not the observed Hessian, not the Godambe (sandwich) information.  The Jacobian as in
-# .cocons.hip.fisher; NULL after a failing block under safe.
-.cocons.hip.vecchia.fisher <- function(fit, theta, par.pos, safe = TRUE) {
+# .cocons.hip.fisher; NULL after a failing block under safe.  grouped: on the grouped schedule (what
+# .cocons.hip.vecchia.fisher.grouped passes).
+.cocons.hip.vecchia.fisher <- function(fit, theta, par.pos, safe = TRUE, grouped = FALSE) {
   aspects <- c("std.dev", "scale", "aniso", "tilt", "smooth", "nugget")
   base <- cocons::getModelLists(theta = theta, par.pos = par.pos, type = "diff")
   p <- length(base$mean)
@@ -531,8 +532,9 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
   Jm <- J[seq_len(p), , drop = FALSE]
   Jt <- J[-seq_len(p), , drop = FALSE]
   cov <- which(colSums(Jt != 0) > 0)
-  res <- .cocons.hip.result(.Call(`_cocons_hip_vecchia_fisher`, fit, base[-1], Jt[, if (length(cov)) cov else 1L, drop = FALSE]),
-                            safe)
+  dirs <- Jt[, if (length(cov)) cov else 1L, drop = FALSE]
+  res <- .cocons.hip.result(if (grouped) .Call(`_cocons_hip_vecchia_fisher_grouped`, fit, base[-1], dirs)
+                            else .Call(`_cocons_hip_vecchia_fisher`, fit, base[-1], dirs), safe)
   if (is.null(res)) return(NULL)
   info <- crossprod(Jm, res[[2]] %*% Jm)
   if (length(cov)) info[cov, cov] <- info[cov, cov] + res[[1]]
@@ -669,6 +671,13 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
   res <- .cocons.hip.result(.Call(`_cocons_hip_vecchia_neg2loglik_grad_grouped`, fit, theta_list[-1], theta_list$mean), safe)
   if (is.null(res)) return(NULL)
   list(value = res[[1]], table = res[[2]], quad = res[[3]], mean = res[[4]])
+}
+
+# .cocons.hip.vecchia.fisher on the grouped schedule (cocons_fisher_vecchia_grouped; DESIGN.md 4aa): the same P x P matrix of
+# the same model to rounding, from one factorisation per block; the fit needs a plan (.cocons.hip.vecchia.set.groups
+# attaches one)
+.cocons.hip.vecchia.fisher.grouped <- function(fit, theta, par.pos, safe = TRUE) {
+  .cocons.hip.vecchia.fisher(fit, theta, par.pos, safe, grouped = TRUE)
 }
 
 # U W for the n x c matrix W and log d on the grouped schedule: list(out, logd)

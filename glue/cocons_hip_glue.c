@@ -993,7 +993,7 @@ SEXP _cocons_hip_vecchia_neg2loglik_grad(SEXP fitp, SEXP theta, SEXP mean)
 
 /* expected information of a Vecchia fit (cocons_fisher_vecchia): dirs as for _cocons_hip_fisher; list(status, list(info
  * ndir x ndir, info_mean p x p)); a failing block is a status */
-SEXP _cocons_hip_vecchia_fisher(SEXP fitp, SEXP theta, SEXP dirs)
+static SEXP vecchia_fisher(SEXP fitp, SEXP theta, SEXP dirs, int grouped)
 {
     cocons_fit *f = fit_of(fitp);
     const int p = fit_p(fitp);
@@ -1006,14 +1006,20 @@ SEXP _cocons_hip_vecchia_fisher(SEXP fitp, SEXP theta, SEXP dirs)
     SEXP im = PROTECT(Rf_allocMatrix(REALSXP, p, p));
     for (R_xlen_t e = 0; e < XLENGTH(info); ++e) REAL(info)[e] = 0.0;
     for (R_xlen_t e = 0; e < XLENGTH(im); ++e) REAL(im)[e] = 0.0;
-    int rc = cocons_fisher_vecchia(f, T, nd, REAL(dirs), REAL(info), REAL(im));     /* (both outputs are symmetric) */
-    hip_check(rc, "expected information of the Vecchia fit");
+    int rc = (grouped ? cocons_fisher_vecchia_grouped : cocons_fisher_vecchia)(f, T, nd, REAL(dirs), REAL(info),
+                                                                               REAL(im));     /* (both outputs are symmetric) */
+    hip_check(rc, grouped ? "expected information of the Vecchia fit (grouped)" : "expected information of the Vecchia fit");
     SEXP res = PROTECT(Rf_allocVector(VECSXP, 2));
     SET_VECTOR_ELT(res, 0, info);
     SET_VECTOR_ELT(res, 1, im);
     SEXP out = status_value(rc, res);
     UNPROTECT(3);
     return out;
+}
+
+SEXP _cocons_hip_vecchia_fisher(SEXP fitp, SEXP theta, SEXP dirs)
+{
+    return vecchia_fisher(fitp, theta, dirs, 0);
 }
 
 /* local kriging on a Vecchia handle (cocons_vecchia_predict): list(status, cbind(stochastic, quadform)); theta is the WHOLE
@@ -1281,6 +1287,13 @@ SEXP _cocons_hip_vecchia_neg2loglik_grad_grouped(SEXP fitp, SEXP theta, SEXP mea
     return vecchia_neg2loglik_grad(fitp, theta, mean, 1);
 }
 
+/* _cocons_hip_vecchia_fisher on the grouped schedule (cocons_fisher_vecchia_grouped): the same list; the
+ * information of the same model to rounding */
+SEXP _cocons_hip_vecchia_fisher_grouped(SEXP fitp, SEXP theta, SEXP dirs)
+{
+    return vecchia_fisher(fitp, theta, dirs, 1);
+}
+
 /* U W and log d on the grouped schedule (cocons_vecchia_whiten_grouped): W is n x c; list(status, list(the n x c result, the
  * n values log d)); theta without `mean` */
 SEXP _cocons_hip_vecchia_whiten_grouped(SEXP fitp, SEXP theta, SEXP W)
@@ -1527,6 +1540,7 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_vecchia_set_groups", (DL_FUNC)&_cocons_hip_vecchia_set_groups, 2},
     {"_cocons_hip_vecchia_neg2loglik_grouped", (DL_FUNC)&_cocons_hip_vecchia_neg2loglik_grouped, 3},
     {"_cocons_hip_vecchia_neg2loglik_grad_grouped", (DL_FUNC)&_cocons_hip_vecchia_neg2loglik_grad_grouped, 3},
+    {"_cocons_hip_vecchia_fisher_grouped", (DL_FUNC)&_cocons_hip_vecchia_fisher_grouped, 3},
     {"_cocons_hip_vecchia_whiten_grouped", (DL_FUNC)&_cocons_hip_vecchia_whiten_grouped, 3},
     {"_cocons_hip_fit_close", (DL_FUNC)&_cocons_hip_fit_close, 1},
     {"_cocons_hip_neg2loglik_parts", (DL_FUNC)&_cocons_hip_neg2loglik_parts, 3},

@@ -544,6 +544,19 @@ int cocons_vecchia_whiten_grouped(cocons_fit *fit, const double *theta, int c, c
 int cocons_neg2loglik_grad_vecchia_grouped(cocons_fit *fit, const double *theta, const double *mean, int c, const double *B,
                                            double *sum_logliks, double *parts, double *grad_theta, double *grad_quad,
                                            double *grad_mean);
+/* cocons_fisher_vecchia on the grouped schedule (one factorisation per BLOCK, every pair of a block evaluated
+ * once per walk for all its members): the same arguments, conventions, return codes and refusals -- info_mean may be NULL,
+ * info and info_mean symmetric to the bit, outputs written on 0 only, the smallest failing 1-based row, the same scratch on
+ * the handle (cocons_vecchia_info reports the same bytes).  With rows S ascending, C = L L' and s_p row p of L^-1, the member
+ * at position p gives g_{a,p} = L_{0..p}^-1 (C_a[0..p, 0..p] s_p) and u_p = sum_{row <= p} s_p[row] X[site(row), .]:
+ *   info[a * ndir + b] = r sum_blocks sum_members ( sum_{j < p} g_{a,p}[j] g_{b,p}[j] + g_{a,p}[p] g_{b,p}[p] / 2 ),
+ *   info_mean[k * p + l] = r sum_blocks sum_members u_p[k] u_p[l].
+ * It is the same model's information -- the handle's table is the expanded one -- summed in another order: it agrees with
+ * cocons_fisher_vecchia on the same handle to rounding, not to the bit, and repeats to the bit whatever
+ * COCONS_VECCHIA_GROUP_ORDER says.  A direction count whose launch cannot fit the LDS is refused (-1) with the bytes in the
+ * message.  Refused (-1): a handle without a plan (cocons_vecchia_set_groups attaches one).                                  */
+int cocons_fisher_vecchia_grouped(cocons_fit *fit, const double *theta, int ndir, const double *dirs,
+                                  double *info, double *info_mean);
 
 /* ---- fit handle: everything that is constant over an optimisation -------------
  * Created once per cocoOptim / getHessian call from the arguments the reference
