@@ -87,6 +87,11 @@ SIGNATURES = {
     "cocons_neg2loglik_grad_vecchia_grouped": (c_int, [c_vp, c_dp, c_dp, c_int, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "cocons_cv_vecchia": (c_int, [c_vp, c_dp, c_dp, c_int, ctypes.POINTER(c_int), c_dp, c_dp,
                                   ctypes.POINTER(ctypes.c_longlong)]),
+    "cocons_vecchia_unwhiten_grouped": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp]),
+    "cocons_sim_vecchia_grouped": (c_int, [c_vp, c_dp, c_dp, c_int, c_int, c_int, c_dp, c_dp]),
+    "cocons_vecchia_whiten_t_grouped": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_dp]),
+    "cocons_cv_vecchia_grouped": (c_int, [c_vp, c_dp, c_dp, c_int, ctypes.POINTER(c_int), c_dp, c_dp,
+                                          ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_fit_destroy": (None, [c_vp]),
     "cocons_neg2loglik_dense": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp]),
     "cocons_neg2loglik_grad_dense": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
@@ -165,6 +170,7 @@ DIAG_SIGNATURES = {
     "cocons_debug_order_phases": (c_int, [c_int, c_dp, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_dp,
                                           ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_debug_vecchia_sim_phases": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_dp]),
+    "cocons_debug_vecchia_sim_phases_grouped": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_dp]),
     "cocons_debug_vecchia_transpose_phases": (c_int, [c_vp, c_dp]),
     "cocons_debug_taper_selinv": (c_int, [c_vp, c_dp, c_dp, ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_debug_tune": (c_int, [ctypes.c_char_p, c_int]),

@@ -127,21 +127,23 @@ extern "C" int cocons_debug_vecchia_transpose_phases(cocons_fit *f, double *ms4)
     return t_build(f, who, ms4);
 }
 
-extern "C" int cocons_vecchia_whiten_t(cocons_fit *f, const double *theta, int c, const double *W, double *out, double *qdiag)
+// cocons_vecchia_whiten_t and its grouped twin: the coefficient launch over observations or over the plan's blocks
+int vecchia_whiten_t_impl(const char *who, bool grouped, cocons_fit *f, const double *theta, int c, const double *W, double *out,
+                          double *qdiag)
 {
-    const char *who = "cocons_vecchia_whiten_t";
     if (!f) return fail(-1, "%s: null fit handle", who);
     if (!theta || !W || !out) return fail(-1, "%s: null argument", who);
     if (c < 1) return fail(-1, "%s: c = %d (at least one column expected)", who, c);
     FIT_ENTER_ANY(f);
     if (int rc = vecchia_only(f, who)) return rc;
+    if (grouped) if (int rc = vecchia_need_plan(f, who)) return rc;
     VecchiaState *V = f->vecchia.get();
     const size_t n = (size_t)f->n;
     hipStream_t s = f->stream;
     if (int rc = t_build(f, who, nullptr)) return rc;
     HIPCHK_AT(who, V->B.reserve(n * c, s, nullptr));
     HIPCHK_AT(who, V->W.reserve(n * (1 + c), s, nullptr));
-    if (int st = vecchia_sim_coefs(f, who, theta, 0)) return st;
+    if (int st = vecchia_sim_coefs(f, who, theta, 0, grouped)) return st;
     HIPCHK_AT(who, upload_canon(V->B, W, n * c, s));
     launch_vecchia_ut(t_args(f), c, V->B, n, V->W + n, n, V->W, s);
     std::vector<double> h(n * (1 + c));
@@ -153,10 +155,15 @@ extern "C" int cocons_vecchia_whiten_t(cocons_fit *f, const double *theta, int c
     return 0;
 }
 
-extern "C" int cocons_cv_vecchia(cocons_fit *f, const double *theta, const double *mean, int nfold, const int *fold,
-                                 double *resid, double *var, long long *stats4)
+extern "C" int cocons_vecchia_whiten_t(cocons_fit *f, const double *theta, int c, const double *W, double *out, double *qdiag)
 {
-    const char *who = "cocons_cv_vecchia";
+    return vecchia_whiten_t_impl("cocons_vecchia_whiten_t", false, f, theta, c, W, out, qdiag);
+}
+
+// cocons_cv_vecchia and its grouped twin
+int vecchia_cv_impl(const char *who, bool grouped, cocons_fit *f, const double *theta, const double *mean, int nfold,
+                    const int *fold, double *resid, double *var, long long *stats4)
+{
     if (!f) return fail(-1, "%s: null fit handle", who);
     if (!theta || !mean || !resid || !var) return fail(-1, "%s: null argument", who);
     if (nfold < 0) return fail(-1, "%s: nfold = %d is negative", who, nfold);
@@ -164,6 +171,7 @@ extern "C" int cocons_cv_vecchia(cocons_fit *f, const double *theta, const doubl
         return fail(-1, "%s: fold and nfold disagree (fold = NULL with nfold = 0 is leave-one-out)", who);
     FIT_ENTER_ANY(f);
     if (int rc = vecchia_only(f, who)) return rc;
+    if (grouped) if (int rc = vecchia_need_plan(f, who)) return rc;
     VecchiaState *V = f->vecchia.get();
     const int n = f->n, nr = f->r;
     // ---- the folds (cocons_cv_dense's plan; a Vecchia handle keeps the caller's order, so positions are observations)
@@ -223,7 +231,7 @@ extern "C" int cocons_cv_vecchia(cocons_fit *f, const double *theta, const doubl
     HIPCHK_AT(who, dints.alloc(tot + 1));
     double *dY = dbuf, *dUty = dY + N * nr, *dres = dUty + N * nr, *dq = dres + N * nr, *dvar = dq + N;
     int *dfail = dints + tot;
-    if (int st = vecchia_sim_coefs(f, who, theta, 0)) return st;          // a failing block: its row, nothing written
+    if (int st = vecchia_sim_coefs(f, who, theta, 0, grouped)) return st; // a failing block: its row, nothing written
     HIPCHK_AT(who, hipMemcpyAsync(dints, ints.data(), (tot + 1) * sizeof(int), hipMemcpyHostToDevice, s));
     const VecchiaTArgs ta = t_args(f);
     launch_vecchia_resid(n, f->p, f->dX, n, hmean, f->dz, n, 0, nr, V->B, N, s);
@@ -259,4 +267,10 @@ extern "C" int cocons_cv_vecchia(cocons_fit *f, const double *theta, const doubl
         stats4[3] = (long long)(ndbl * sizeof(double) + (tot + 1) * sizeof(int));
     }
     return 0;
+}
+
+extern "C" int cocons_cv_vecchia(cocons_fit *f, const double *theta, const double *mean, int nfold, const int *fold,
+                                 double *resid, double *var, long long *stats4)
+{
+    return vecchia_cv_impl("cocons_cv_vecchia", false, f, theta, mean, nfold, fold, resid, var, stats4);
 }

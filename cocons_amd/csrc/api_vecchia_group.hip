@@ -3,7 +3,9 @@
 // partition on a Vecchia handle whose table is closed under it; cocons_fit_create_vecchia_grouped, the three in one call; and
 // cocons_neg2loglik_vecchia_grouped / cocons_vecchia_whiten_grouped, the value and the whitening with one factorisation per
 // block, cocons_neg2loglik_grad_vecchia_grouped, the value and the gradient from it, and
-// cocons_fisher_vecchia_grouped, the expected information from it.  A grouped evaluation
+// cocons_fisher_vecchia_grouped, the expected information from it, and cocons_vecchia_unwhiten_grouped,
+// cocons_sim_vecchia_grouped, cocons_vecchia_whiten_t_grouped and cocons_cv_vecchia_grouped, U^-1, U' and
+// cross-validation with their coefficients from it.  A grouped evaluation
 // is the ungrouped one with launch_vecchia_group_blocks in the place of launch_vecchia_blocks: the same records, right-hand
 // sides, per-row arrays, totals and status word, and therefore the same bits.
 #include "fit.hpp"
@@ -305,4 +307,34 @@ extern "C" int cocons_fisher_vecchia_grouped(cocons_fit *f, const double *theta,
                                              double *info_mean)
 {
     return vecchia_fisher_impl("cocons_fisher_vecchia_grouped", true, f, theta, ndir, dirs, info, info_mean);
+}
+
+// the ungrouped entries' bodies with launch_vecchia_group_coefs in the place of launch_vecchia_coefs
+extern "C" int cocons_vecchia_unwhiten_grouped(cocons_fit *f, const double *theta, int c, const double *W, double *out)
+{
+    return vecchia_unwhiten_impl("cocons_vecchia_unwhiten_grouped", true, false, f, theta, c, W, out, nullptr);
+}
+
+extern "C" int cocons_debug_vecchia_sim_phases_grouped(cocons_fit *f, const double *theta, int c, const double *W, double *out,
+                                                       double *ms3)
+{
+    return vecchia_unwhiten_impl("cocons_debug_vecchia_sim_phases_grouped", true, true, f, theta, c, W, out, ms3);
+}
+
+extern "C" int cocons_sim_vecchia_grouped(cocons_fit *f, const double *theta, const double *mean, int n_fixed, int z_col, int nsim,
+                                          const double *iiderrors, double *out)
+{
+    return vecchia_sim_impl("cocons_sim_vecchia_grouped", true, f, theta, mean, n_fixed, z_col, nsim, iiderrors, out);
+}
+
+extern "C" int cocons_vecchia_whiten_t_grouped(cocons_fit *f, const double *theta, int c, const double *W, double *out,
+                                               double *qdiag)
+{
+    return vecchia_whiten_t_impl("cocons_vecchia_whiten_t_grouped", true, f, theta, c, W, out, qdiag);
+}
+
+extern "C" int cocons_cv_vecchia_grouped(cocons_fit *f, const double *theta, const double *mean, int nfold, const int *fold,
+                                         double *resid, double *var, long long *stats4)
+{
+    return vecchia_cv_impl("cocons_cv_vecchia_grouped", true, f, theta, mean, nfold, fold, resid, var, stats4);
 }

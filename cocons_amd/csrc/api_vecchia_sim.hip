@@ -3,7 +3,8 @@
 // level schedule they run on; and cocons_debug_vecchia_sim_phases, which times a call's three phases by events.  One call is:
 // the records for theta and the coefficient launch (one wave per row, no dependency), the status word home -- a failing block
 // ends the call there --, the schedule of (table, n_fixed) unless the handle holds it, and the solve: one launch per level or
-// per run of small levels, in the order of the handle's stream.
+// per run of small levels, in the order of the handle's stream.  The bodies are shared with the grouped entries of
+// api_vecchia_group.hip, whose coefficient launch is one workgroup per block of the handle's plan.
 #include "fit.hpp"
 
 // Events around the three phases (cocons_debug_vecchia_sim_phases); off: nothing is created or recorded
@@ -107,14 +108,25 @@ static int sim_schedule(cocons_fit *f, const char *who, int n_fixed)
 }
 
 // The coefficients of the rows n_fixed .. n - 1 for theta into S->coef and the status word home: 0, the smallest failing
-// 1-based row, or < 0
-int vecchia_sim_coefs(cocons_fit *f, const char *who, const double *theta, int n_fixed)
+// 1-based row, or < 0.  grouped: one workgroup per block of the handle's plan instead of one wavefront per row
+int vecchia_sim_coefs(cocons_fit *f, const char *who, const double *theta, int n_fixed, bool grouped)
 {
     VecchiaState *V = f->vecchia.get();
     if (!V->sim) V->sim.reset(new VecchiaSimState());
     HIPCHK_AT(who, V->sim->coef.reserve((size_t)f->n * (V->m + 1), f->stream, nullptr));
     if (int rc = reset_info(f)) return rc;
     const ModeSel ms = vecchia_records(f, theta, 0, V->aos);
+    if (grouped) {
+        const VecchiaGroupState *G = V->grp.get();
+        VecchiaGroupArgs g;
+        g.blocks = G->blocks; g.kb = G->maxrows;
+        g.off = G->off; g.rows = G->rows; g.order = G->by_size ? G->order.get() : nullptr; g.mask = G->mask;
+        g.aosK = V->aos; g.gr = ms.gr; g.nu_fixed = ms.nu_fixed;
+        g.coef = V->sim->coef; g.ldc = (size_t)V->m + 1; g.row0 = n_fixed;
+        g.fail = f->dinfo;
+        launch_vecchia_group_coefs(ms.mode, g, f->stream);
+        return vecchia_status(f, who);
+    }
     VecchiaArgs a;
     a.rows = f->n - n_fixed; a.obs0 = n_fixed; a.m = V->m; a.kb = V->m + 1; a.nbr = V->nbr; a.aosK = V->aos;
     a.gr = ms.gr; a.nu_fixed = ms.nu_fixed;
@@ -141,8 +153,8 @@ static void sim_solve(cocons_fit *f, int n_fixed, int c)
 }
 
 // mean == NULL: cocons_vecchia_unwhiten (n_fixed = 0, no trend).  E: (n - n_fixed) x c, used as given.
-static int sim_impl(const char *who, cocons_fit *f, const double *theta, const double *mean, int n_fixed, int z_col, int c,
-                    const double *E, double *out, double *phases)
+static int sim_impl(const char *who, bool grouped, cocons_fit *f, const double *theta, const double *mean, int n_fixed, int z_col,
+                    int c, const double *E, double *out, double *phases)
 {
     VecchiaState *V = f->vecchia.get();
     const size_t n = (size_t)f->n, rows = n - (size_t)n_fixed;
@@ -153,7 +165,7 @@ static int sim_impl(const char *who, cocons_fit *f, const double *theta, const d
     double hmean[COCONS_P_MAX] = {};
     if (mean) for (int i = 0; i < f->p; ++i) hmean[i] = canon_nan(mean[i]);
     marks.mark(0);
-    if (int st = vecchia_sim_coefs(f, who, theta, n_fixed)) return st;
+    if (int st = vecchia_sim_coefs(f, who, theta, n_fixed, grouped)) return st;
     marks.mark(1);
     marks.mark(2);
     if (int rc = sim_schedule(f, who, n_fixed)) return rc;
@@ -179,27 +191,28 @@ static int sim_impl(const char *who, cocons_fit *f, const double *theta, const d
     return 0;
 }
 
-extern "C" int cocons_vecchia_unwhiten(cocons_fit *f, const double *theta, int c, const double *W, double *out)
+// cocons_vecchia_unwhiten and cocons_debug_vecchia_sim_phases (timed), and their grouped twins
+int vecchia_unwhiten_impl(const char *who, bool grouped, bool timed, cocons_fit *f, const double *theta, int c, const double *W,
+                          double *out, double *ms3)
 {
-    const char *who = "cocons_vecchia_unwhiten";
     if (!f) return fail(-1, "%s: null fit handle", who);
-    if (!theta || !W || !out) return fail(-1, "%s: null argument", who);
+    if (!theta || !W || !out || (timed && !ms3)) return fail(-1, "%s: null argument", who);
     if (c < 1) return fail(-1, "%s: c = %d (at least one column expected)", who, c);
     FIT_ENTER_ANY(f);
     if (int rc = vecchia_only(f, who)) return rc;
-    return sim_impl(who, f, theta, nullptr, 0, 0, c, W, out, nullptr);
+    if (grouped) if (int rc = vecchia_need_plan(f, who)) return rc;
+    return sim_impl(who, grouped, f, theta, nullptr, 0, 0, c, W, out, timed ? ms3 : nullptr);
+}
+
+extern "C" int cocons_vecchia_unwhiten(cocons_fit *f, const double *theta, int c, const double *W, double *out)
+{
+    return vecchia_unwhiten_impl("cocons_vecchia_unwhiten", false, false, f, theta, c, W, out, nullptr);
 }
 
 extern "C" int cocons_debug_vecchia_sim_phases(cocons_fit *f, const double *theta, int c, const double *W, double *out,
                                                double *ms3)
 {
-    const char *who = "cocons_debug_vecchia_sim_phases";
-    if (!f) return fail(-1, "%s: null fit handle", who);
-    if (!theta || !W || !out || !ms3) return fail(-1, "%s: null argument", who);
-    if (c < 1) return fail(-1, "%s: c = %d (at least one column expected)", who, c);
-    FIT_ENTER_ANY(f);
-    if (int rc = vecchia_only(f, who)) return rc;
-    return sim_impl(who, f, theta, nullptr, 0, 0, c, W, out, ms3);
+    return vecchia_unwhiten_impl("cocons_debug_vecchia_sim_phases", false, true, f, theta, c, W, out, ms3);
 }
 
 static int sim_check_fixed(cocons_fit *f, const char *who, int n_fixed)
@@ -208,10 +221,10 @@ static int sim_check_fixed(cocons_fit *f, const char *who, int n_fixed)
     return 0;
 }
 
-extern "C" int cocons_sim_vecchia(cocons_fit *f, const double *theta, const double *mean, int n_fixed, int z_col, int nsim,
-                                  const double *iiderrors, double *out)
+// cocons_sim_vecchia and its grouped twin
+int vecchia_sim_impl(const char *who, bool grouped, cocons_fit *f, const double *theta, const double *mean, int n_fixed, int z_col,
+                     int nsim, const double *iiderrors, double *out)
 {
-    const char *who = "cocons_sim_vecchia";
     if (!f) return fail(-1, "%s: null fit handle", who);
     if (!theta || !mean || !iiderrors || !out) return fail(-1, "%s: null argument", who);
     if (nsim < 1) return fail(-1, "%s: nsim = %d (at least one field expected)", who, nsim);
@@ -219,9 +232,16 @@ extern "C" int cocons_sim_vecchia(cocons_fit *f, const double *theta, const doub
     if (z_col < 0) return fail(-1, "%s: z_col = %d is outside the realisations", who, z_col);
     FIT_ENTER_ANY(f);
     if (int rc = vecchia_only(f, who)) return rc;
+    if (grouped) if (int rc = vecchia_need_plan(f, who)) return rc;
     if (int rc = sim_check_fixed(f, who, n_fixed)) return rc;
     if (z_col < 0 || z_col >= f->r) return fail(-1, "%s: z_col = %d is outside 0 .. %d", who, z_col, f->r - 1);
-    return sim_impl(who, f, theta, mean, n_fixed, z_col, nsim, iiderrors, out, nullptr);
+    return sim_impl(who, grouped, f, theta, mean, n_fixed, z_col, nsim, iiderrors, out, nullptr);
+}
+
+extern "C" int cocons_sim_vecchia(cocons_fit *f, const double *theta, const double *mean, int n_fixed, int z_col, int nsim,
+                                  const double *iiderrors, double *out)
+{
+    return vecchia_sim_impl("cocons_sim_vecchia", false, f, theta, mean, n_fixed, z_col, nsim, iiderrors, out);
 }
 
 // out4 = {depth, rows of the largest level, launches of one solve of one column, device bytes of the schedule and of the n (m + 1)

@@ -784,7 +784,20 @@ int vecchia_fisher_impl(const char *who, bool grouped, cocons_fit *f, const doub
 void vecchia_group_fisher_chunks(cocons_fit *f, const ModeSel &ms, int smooth_free, int ndir, int gd, int mc, int chunk, int nseg);
 // ... and what api_vecchia_sim.hip offers api_vecchia_cv.hip: the coefficients of the rows n_fixed .. n - 1 for
 // theta into the handle's sim->coef and the status word home: 0, the smallest failing 1-based row, or < 0
-int vecchia_sim_coefs(cocons_fit *f, const char *who, const double *theta, int n_fixed);
+// grouped: launch_vecchia_group_coefs over the plan's blocks -- the caller has asked vecchia_need_plan -- into
+// the same records, the same bits
+int vecchia_sim_coefs(cocons_fit *f, const char *who, const double *theta, int n_fixed, bool grouped = false);
+// ... and what api_vecchia_sim.hip and api_vecchia_cv.hip offer api_vecchia_group.hip: the bodies of
+// cocons_vecchia_unwhiten (timed: cocons_debug_vecchia_sim_phases, ms3 required), cocons_sim_vecchia, cocons_vecchia_whiten_t
+// and cocons_cv_vecchia with the coefficient launch over observations (grouped = false) or over the plan's blocks
+int vecchia_unwhiten_impl(const char *who, bool grouped, bool timed, cocons_fit *f, const double *theta, int c, const double *W,
+                          double *out, double *ms3);
+int vecchia_sim_impl(const char *who, bool grouped, cocons_fit *f, const double *theta, const double *mean, int n_fixed, int z_col,
+                     int nsim, const double *iiderrors, double *out);
+int vecchia_whiten_t_impl(const char *who, bool grouped, cocons_fit *f, const double *theta, int c, const double *W, double *out,
+                          double *qdiag);
+int vecchia_cv_impl(const char *who, bool grouped, cocons_fit *f, const double *theta, const double *mean, int nfold,
+                    const int *fold, double *resid, double *var, long long *stats4);
 // ... and what they call in api_shard.hip: the sharded cocons_neg2loglik_dense, and cocons_fit_destroy's share
 int sharded_eval(cocons_fit *f, const double *theta, const double *mean, double *sum_logliks, double *parts);
 void shard_events_destroy(ShardState *S);

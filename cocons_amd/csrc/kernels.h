@@ -782,8 +782,17 @@ struct VecchiaGroupArgs {
     // rec too, and no right-hand sides (nb = 0, logd null)
     int ndir = 0, gd = 0, mc = 0;      // directions, directions a group and members a chunk (vecchia_group_fisher_shape)
     const double *dirs = nullptr;      // ndir tables of 6 x p on the device
+    // the coefficient launch only (launch_vecchia_group_coefs): the records of launch_vecchia_coefs, row i at
+    // coef[i ldc ..] with ldc = (the handle's table width) + 1 >= kb; the rows below row0 are fixed and get no record
+    double *coef = nullptr; size_t ldc = 0; int row0 = 0;
 };
 void launch_vecchia_group_blocks(int mode, const VecchiaGroupArgs &a, hipStream_t s);
+// The coefficient variant of the grouped launch (no right-hand sides, no log d): every member at position p whose row is >= row0
+// gets its record as launch_vecchia_coefs documents it -- places t < p hold s_p[t] (the row's neighbours are the block's positions
+// 0 .. p - 1), places p .. ldc - 2 hold 0, place ldc - 1 holds s_p[p] -- the same bits, from one factorisation of the block.  A
+// pivot that is not positive and finite at position q: atomicMin(*fail, row + 1) for the first member at a position >= q whose row
+// is >= row0 (none: no failure), nothing written for the block.  The LDS is launch_vecchia_group_blocks'.
+void launch_vecchia_group_coefs(int mode, const VecchiaGroupArgs &a, hipStream_t s);
 // The gradient variant of the grouped launch over the blocks blk0 .. blk0 + blocks - 1: logd and Y as there (the same code),
 // and per BLOCK one record of vecchia_rec_cols(p) doubles in launch_vecchia_grad_blocks' layout -- the sum of the records
 // its members would give on the expanded table, from one evaluation of every pair of the block.  The dynamic LDS is

@@ -28,6 +28,14 @@
 // block the sum over its members.  The factor stays in LDS for the forward solves; every pair's partials are evaluated once
 // per walk and serve all the members of a chunk and all the directions of a group.  One record per block.
 //
+// COEF: the same gather, pair loop and factorisation, then the members' backward solves s_p = L_{0..p}^-T e_p
+// as vecchia_coef_kernel runs them on the leading (p + 1) x (p + 1) sub-block -- component j is
+// (e_p[j] - sum_{i > j} L(i, j) s_p[i]) / L(j, j), i descending from p, DIVIDED by the pivot -- and every s_p goes straight
+// into its row's record of launch_vecchia_coefs.  The factor's bits are the ungrouped leading sub-block's (above), the solve
+// reads nothing else, so the records are the bits of the ungrouped launch on the same table.  The members are dealt over
+// the four wavefronts by rank, and a wavefront solves VECCHIA_G of its members at a time: they share the read of the
+// factor's row and give the shuffles four independent chains.
+//
 // Compile with -ffp-contract=off, like vecchia.hip: the products and sums stand as written.
 #include <hip/hip_runtime.h>
 #include <atomic>
@@ -80,11 +88,12 @@ static_assert(VECCHIA_GROUP_FQ == VECCHIA_FD && VECCHIA_GROUP_FQ % VECCHIA_G == 
 static_assert(COCONS_P_MAX * (VECCHIA_GROUP_FQ * VECCHIA_GROUP_WAVES / VECCHIA_G) <= VECCHIA_G * VECCHIA_GROUP_THREADS,
               "the members' sums u_p of a chunk fit the staging of the narrowest group");
 
-template <int MODE, bool GRAD = false, bool FISH = false>
+template <int MODE, bool GRAD = false, bool FISH = false, bool COEF = false>
 __global__ void __launch_bounds__(VECCHIA_GROUP_THREADS)
 vecchia_group_kernel(VecchiaGroupArgs a)
 {
-    static_assert(!(GRAD && FISH), "the gradient and the information are launches of their own");
+    static_assert(!(GRAD && FISH) && !(COEF && (GRAD || FISH)), "the gradient, the information and the coefficients are "
+                  "launches of their own");
     constexpr bool DER = GRAD || FISH;             // the launches that gather the site derivatives and solve for the s_p
     extern __shared__ double vecchia_group_lds[];
     const int lane = threadIdx.x, kb = a.kb;
@@ -101,6 +110,8 @@ vecchia_group_kernel(VecchiaGroupArgs a)
               : FISH ? (int *)(sp + VECCHIA_FX * kb + a.gd * (GFAM * kb + VECCHIA_GROUP_THREADS) + a.ndir * a.mc * kb)
                      : (int *)(tri + ntri);
     if (nrows < 1 || nrows > kb) return;          // (a plan the host checked has none)
+    // COEF: the rows below row0 are fixed.  The rows ascend, so a block whose last row is fixed has nothing to give
+    if (COEF && a.rows[off + nrows - 1] < a.row0) return;
 
     if (lane < nrows) nb[lane] = a.rows[off + lane];
     __syncthreads();
@@ -143,14 +154,56 @@ vecchia_group_kernel(VecchiaGroupArgs a)
             for (int c = j + 1; c <= lane; ++c) tri[myrow + c] -= lrj * tri[tri_at(c, j)];
     }
     if (bad >= 0) {
-        // the members from position `bad` on fail; the last row of a block is a member, so there is one
-        const unsigned long long late = members >> bad;
+        // the members from position `bad` on fail; the last row of a block is a member, so there is one (COEF: and its row
+        // is not fixed, so the first member from `bad` on that is not fixed exists too)
+        unsigned long long late = members >> bad;
+        if constexpr (COEF)
+            while (late && nb[bad + __builtin_ctzll(late)] < a.row0) late &= late - 1;
         const int q = late ? bad + __builtin_ctzll(late) : nrows;
         if (lane == 0 && q < nrows) atomicMin(a.fail, nb[q] + 1);
         return;
     }
-    if (DER && lane < nrows) tri[tri_at(lane, lane)] = piv_mine;      // (the solves of the other wavefronts read the pivots here)
+    if ((DER || COEF) && lane < nrows) tri[tri_at(lane, lane)] = piv_mine;   // (the solves of the other wavefronts read the pivots here)
     __syncthreads();
+    if constexpr (COEF) {
+        // No barrier from here on: a wavefront that carries no member's solve falls through the loop and ends.
+        // Member i (ascending, among those whose row is not fixed) is wavefront i mod 4's, lane = row; a wavefront takes
+        // VECCHIA_G of its members at a time.  Step j is one column of L' (a row of the packed factor): the lanes read it once
+        // for the members of the batch, a member at a position below j sits the step out.
+        const int wv = lane >> 6, ln = lane & 63;
+        const double pivl = ln < nrows ? tri[tri_at(ln, ln)] : 1.0;
+        const int nfix = __popcll(__ballot(ln < nrows && nb[ln] < a.row0));      // (rows ascending: the fixed ones lead)
+        unsigned long long rest = members & (~0ull << nfix);                     // (nfix <= nrows - 1 <= 63)
+        for (int rank = 0; rest;) {
+            int pg[VECCHIA_G], cnt = 0;
+            for (; rest && cnt < VECCHIA_G; rest &= rest - 1, ++rank)
+                if ((rank & (VECCHIA_GROUP_WAVES - 1)) == wv) pg[cnt++] = __builtin_ctzll(rest);
+            if (!cnt) break;
+            for (int g = cnt; g < VECCHIA_G; ++g) pg[g] = -1;
+            double rs[VECCHIA_G], sv[VECCHIA_G];
+#pragma unroll
+            for (int g = 0; g < VECCHIA_G; ++g) { rs[g] = ln == pg[g] ? 1.0 : 0.0; sv[g] = 0.0; }
+            for (int j = pg[cnt - 1]; j >= 0; --j) {
+                const double l = ln < j ? tri[tri_at(j, 0) + ln] : 0.0;
+#pragma unroll
+                for (int g = 0; g < VECCHIA_G; ++g) {
+                    if (j > pg[g]) continue;                                     // (the same in every lane)
+                    const double xs = __shfl(rs[g] / pivl, j);
+                    if (ln == j) sv[g] = xs;
+                    if (ln < j) rs[g] -= l * xs;
+                }
+            }
+            const int m = (int)a.ldc - 1;
+#pragma unroll
+            for (int g = 0; g < VECCHIA_G; ++g) {
+                if (pg[g] < 0) continue;
+                double *rec = a.coef + (size_t)nb[pg[g]] * a.ldc;
+                if (ln < m) rec[ln] = ln < pg[g] ? sv[g] : 0.0;
+                if (ln == pg[g]) rec[m] = sv[g];
+            }
+        }
+        return;
+    }
     if (!DER && lane >= 64) return;                // (no barrier from here on)
     // forward substitution, VECCHIA_G right-hand sides at a time: lane r ends with b_r - sum_{j < r} C(r, j) y_j, j ascending.
     // A lane at or in front of step j takes no part in it: its value must not see a y_j that is not finite.
@@ -538,6 +591,19 @@ void launch_vecchia_group_blocks(int mode, const VecchiaGroupArgs &a, hipStream_
     case MODE_THREEHALF: hipLaunchKernelGGL((vecchia_group_kernel<MODE_THREEHALF>), grid, block, shm, s, a); break;
     case MODE_FIVEHALF: hipLaunchKernelGGL((vecchia_group_kernel<MODE_FIVEHALF>), grid, block, shm, s, a); break;
     default: hipLaunchKernelGGL((vecchia_group_kernel<MODE_GEOM>), grid, block, shm, s, a); break;
+    }
+}
+
+void launch_vecchia_group_coefs(int mode, const VecchiaGroupArgs &a, hipStream_t s)
+{
+    if (a.blocks <= 0) return;
+    const size_t shm = vecchia_lds_bytes(a.kb - 1, false);    // the value launch's layout: the s_p go straight to memory
+    const dim3 grid((unsigned)a.blocks), block(VECCHIA_GROUP_THREADS);
+    switch (mode) {
+    case MODE_HALF: hipLaunchKernelGGL((vecchia_group_kernel<MODE_HALF, false, false, true>), grid, block, shm, s, a); break;
+    case MODE_THREEHALF: hipLaunchKernelGGL((vecchia_group_kernel<MODE_THREEHALF, false, false, true>), grid, block, shm, s, a); break;
+    case MODE_FIVEHALF: hipLaunchKernelGGL((vecchia_group_kernel<MODE_FIVEHALF, false, false, true>), grid, block, shm, s, a); break;
+    default: hipLaunchKernelGGL((vecchia_group_kernel<MODE_GEOM, false, false, true>), grid, block, shm, s, a); break;
     }
 }
 

@@ -1738,26 +1738,42 @@ class CoconsVecchiaFit(_Handle):
                                                       _p(st), _p(qf)), "cocons_vecchia_predict_knn")
         return st, qf
 
-    def unwhiten_core(self, theta_list, W):
-        """U^-1 W for the columns of W (n x c, the caller's order): the inverse of `whiten_core` for the same theta
-        (cocons_vecchia_unwhiten, DESIGN.md 4v).  With N(0, 1) columns the result has the Vecchia model's covariance."""
+    def _unwhiten(self, theta_list, W, entry):
         T = theta_table(theta_list)
         W = _f(np.asarray(W, dtype=np.float64).reshape(self.n, -1))
         out = np.zeros(W.shape, order="F")
-        _lib.check(self._L.cocons_vecchia_unwhiten(self._h, _p(T), int(W.shape[1]), _p(W), _p(out)), "cocons_vecchia_unwhiten")
+        _lib.check(getattr(self._L, entry)(self._h, _p(T), int(W.shape[1]), _p(W), _p(out)), entry)
+        return out
+
+    def unwhiten_core(self, theta_list, W):
+        """U^-1 W for the columns of W (n x c, the caller's order): the inverse of `whiten_core` for the same theta
+        (cocons_vecchia_unwhiten, DESIGN.md 4v).  With N(0, 1) columns the result has the Vecchia model's covariance."""
+        return self._unwhiten(theta_list, W, "cocons_vecchia_unwhiten")
+
+    def unwhiten_grouped_core(self, theta_list, W):
+        """`unwhiten_core` with the rows' coefficients from one factorisation per block of the plan of `set_groups`
+        (cocons_vecchia_unwhiten_grouped): the same bits.  (A method of its own, as `whiten_grouped_core`.)"""
+        return self._unwhiten(theta_list, W, "cocons_vecchia_unwhiten_grouped")
+
+    def _sim(self, theta_list, iiderrors, n_fixed, z_col, entry):
+        rows = self.n - int(n_fixed)
+        E = _f(np.asarray(iiderrors, dtype=np.float64).reshape(max(rows, 1), -1))
+        T, mean = _table_mean(theta_list)
+        out = np.zeros(E.shape, order="F")
+        _lib.check(getattr(self._L, entry)(self._h, _p(T), _p(mean), int(n_fixed), int(z_col), int(E.shape[1]), _p(E), _p(out)),
+                   entry)
         return out
 
     def sim_core(self, theta_list, iiderrors, n_fixed=0, z_col=0):
         """cocons_sim_vecchia.  n_fixed = 0: X mean + U^-1 E, n x nsim.  1 <= n_fixed < n: the first n_fixed rows are data
         (z[:, z_col] - X mean) and the rows behind them run the recursion; E and the result are (n - n_fixed) x nsim -- the
         joint conditional mean at the later rows for E = 0, a conditional draw for N(0, 1) numbers."""
-        rows = self.n - int(n_fixed)
-        E = _f(np.asarray(iiderrors, dtype=np.float64).reshape(max(rows, 1), -1))
-        T, mean = _table_mean(theta_list)
-        out = np.zeros(E.shape, order="F")
-        _lib.check(self._L.cocons_sim_vecchia(self._h, _p(T), _p(mean), int(n_fixed), int(z_col), int(E.shape[1]), _p(E),
-                                              _p(out)), "cocons_sim_vecchia")
-        return out
+        return self._sim(theta_list, iiderrors, n_fixed, z_col, "cocons_sim_vecchia")
+
+    def sim_grouped_core(self, theta_list, iiderrors, n_fixed=0, z_col=0):
+        """`sim_core` with the coefficients of the rows n_fixed .. n - 1 from one factorisation per block of the plan of
+        `set_groups` (cocons_sim_vecchia_grouped): the same bits."""
+        return self._sim(theta_list, iiderrors, n_fixed, z_col, "cocons_sim_vecchia_grouped")
 
     def schedule(self, n_fixed=0):
         """The level schedule of (table, n_fixed) that `unwhiten_core` and `sim_core` run on (cocons_vecchia_schedule):
@@ -1782,27 +1798,37 @@ class CoconsVecchiaFit(_Handle):
         return {"ptr": ptr, "rows": rows, "entries": int(out[0]), "longest": int(out[1]), "bytes": int(out[2]),
                 "unnamed": int(out[3])}
 
-    def whiten_t_core(self, theta_list, W):
-        """(U'W, diag(U'U)) for the columns of W (n x c, the caller's order): the transpose of `whiten_core`'s U, applied
-        through the transposed lists in a fixed order (cocons_vecchia_whiten_t).  A column's result does not depend on c."""
+    def _whiten_t(self, theta_list, W, entry):
         T = theta_table(theta_list)
         W = _f(np.asarray(W, dtype=np.float64).reshape(self.n, -1))
         out, qd = np.zeros(W.shape, order="F"), np.zeros(self.n)
-        _lib.check(self._L.cocons_vecchia_whiten_t(self._h, _p(T), int(W.shape[1]), _p(W), _p(out), _p(qd)),
-                   "cocons_vecchia_whiten_t")
+        _lib.check(getattr(self._L, entry)(self._h, _p(T), int(W.shape[1]), _p(W), _p(out), _p(qd)), entry)
         return out, qd
 
-    def cv_core(self, theta_list, fold=None, stats=False):
+    def whiten_t_core(self, theta_list, W):
+        """(U'W, diag(U'U)) for the columns of W (n x c, the caller's order): the transpose of `whiten_core`'s U, applied
+        through the transposed lists in a fixed order (cocons_vecchia_whiten_t).  A column's result does not depend on c."""
+        return self._whiten_t(theta_list, W, "cocons_vecchia_whiten_t")
+
+    def whiten_t_grouped_core(self, theta_list, W):
+        """`whiten_t_core` with the rows' coefficients from one factorisation per block of the plan of `set_groups`
+        (cocons_vecchia_whiten_t_grouped): the same bits."""
+        return self._whiten_t(theta_list, W, "cocons_vecchia_whiten_t_grouped")
+
+    def cv_core(self, theta_list, fold=None, stats=False, grouped=False):
         """Cross-validated predictions of the Vecchia model from Q = U'U (cocons_cv_vecchia).  `fold`: n integer labels in
         [0, nfold), every fold of at most 128 observations (None: leave-one-out).  Returns (resid n x r, var n) as
-        `CoconsFit.cv_core`; with `stats` also {"singles", "folds", "entries", "bytes": device bytes of the call}."""
+        `CoconsFit.cv_core`; with `stats` also {"singles", "folds", "entries", "bytes": device bytes of the call}.  `grouped`:
+        the coefficients from one factorisation per block of the plan of `set_groups` (cocons_cv_vecchia_grouped, DESIGN.md
+        4ab) -- the same bits."""
+        entry = "cocons_cv_vecchia_grouped" if grouped else "cocons_cv_vecchia"
         T, mean = _table_mean(theta_list)
         resid = np.zeros((self.n, self.r), order="F")
         var = np.zeros(self.n)
         nfold, lab = (0, None) if fold is None else _fold_labels(fold, self.n)
         st = (ctypes.c_longlong * 4)()
-        _lib.check(self._L.cocons_cv_vecchia(self._h, _p(T), _p(mean), nfold, None if lab is None else _ip(lab), _p(resid),
-                                             _p(var), st), "cocons_cv_vecchia")
+        _lib.check(getattr(self._L, entry)(self._h, _p(T), _p(mean), nfold, None if lab is None else _ip(lab), _p(resid), _p(var),
+                                           st), entry)
         if stats:
             return resid, var, {"singles": int(st[0]), "folds": int(st[1]), "entries": int(st[2]), "bytes": int(st[3])}
         return resid, var
@@ -2004,6 +2030,38 @@ def cocoCV_vecchia(theta_list, locs, X_std, smooth_limits, z, nn=None, m=None, f
 
     with _borrowed(fit, make) as f:
         return _cv_result(f, z, *f.cv_core(theta_list, lab))
+
+
+def _grouped(who, fit, locs, X_std, z, smooth_limits, nn, m, max_rows):
+    """The caller's grouped handle `fit`, or the handle `CoconsVecchiaFit.from_groups` makes of the table `nn` -- with `m` of
+    the m nearest earlier rows found on the device -- for the length of the block."""
+    if fit is None and (nn is None) == (m is None):
+        raise ValueError("%s: give a neighbour table nn, a number of neighbours m, or a fit" % who)
+
+    def make():
+        table = nn if nn is not None else vecchia_neighbours_device(locs, m)
+        return CoconsVecchiaFit.from_groups(locs, X_std, z, smooth_limits, table, max_rows=max_rows)
+
+    return _borrowed(fit, make)
+
+
+def cocoSim_vecchia_grouped(theta_list, locs, X_std, smooth_limits, iiderrors, nn=None, m=None, max_rows=64, fit=None):
+    """`cocoSim_vecchia` for the grouped model of the table, the rows' coefficients from one factorisation per
+    block (cocons_sim_vecchia_grouped): X mean + U^-1 E of the expanded table, n x nsim.  Without `fit` the handle
+    is `CoconsVecchiaFit.from_groups` of `nn` (or of the `m` nearest earlier rows) with blocks of at most `max_rows` rows; `fit`
+    (optional) a CoconsVecchiaFit with a plan of groups, on which this returns `cocoSim_vecchia(..., fit=fit)`'s bits."""
+    n = np.asarray(X_std).shape[0]
+    with _grouped("cocoSim_vecchia_grouped", fit, locs, X_std, np.zeros(n), smooth_limits, nn, m, max_rows) as f, _chol_error():
+        return f.sim_grouped_core(theta_list, np.asarray(iiderrors, dtype=np.float64).reshape(n, -1))
+
+
+def cocoCV_vecchia_grouped(theta_list, locs, X_std, smooth_limits, z, nn=None, m=None, fold=None, max_rows=64, fit=None):
+    """`cocoCV_vecchia` for the grouped model of the table, the rows' coefficients from one factorisation per block
+    (cocons_cv_vecchia_grouped).  The handle as in `cocoSim_vecchia_grouped`; on a `fit` with a plan of groups
+    this returns `cocoCV_vecchia(..., fit=fit)`'s bits."""
+    lab = None if fold is None else np.unique(np.asarray(fold).ravel(), return_inverse=True)[1]
+    with _grouped("cocoCV_vecchia_grouped", fit, locs, X_std, z, smooth_limits, nn, m, max_rows) as f:
+        return _cv_result(f, z, *f.cv_core(theta_list, lab, grouped=True))
 
 
 def cocoSim_cond_vecchia(theta_list, locs, newlocs, X_std, X_pred_std, smooth_limits, z, iiderrors, m, fit=None):

@@ -588,9 +588,14 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
 # .cocons.hip.vecchia.unwhiten: U^-1 W for the n x c matrix W -- with N(0, 1) columns, fields with the Vecchia model's
 # covariance and mean zero, in the rows' (Vecchia) order
 .cocons.hip.vecchia.unwhiten <- function(fit, theta_list, W) {
+  .cocons.hip.vecchia.unwhiten.by(`_cocons_hip_vecchia_unwhiten`, fit, theta_list, W)
+}
+
+# the one body of .cocons.hip.vecchia.unwhiten and .cocons.hip.vecchia.unwhiten.grouped: `shim` switches between them
+.cocons.hip.vecchia.unwhiten.by <- function(shim, fit, theta_list, W) {
   W <- as.matrix(W)
   storage.mode(W) <- "double"
-  res <- .Call(`_cocons_hip_vecchia_unwhiten`, fit, theta_list[names(theta_list) != "mean"], W)
+  res <- .Call(shim, fit, theta_list[names(theta_list) != "mean"], W)
   if (res[[1]] > 0L) stop("Cholesky error")
   res[[2]]
 }
@@ -600,9 +605,14 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
 # is made over rbind(locs, newlocs), rbind(X, X_pred) and rbind(z, anything); iiderrors is (n - n_fixed) x nsim, all zero for
 # the joint conditional mean
 .cocons.hip.vecchia.sim <- function(fit, theta_list, iiderrors, n_fixed = 0L, z_col = 1L) {
+  .cocons.hip.vecchia.sim.by(`_cocons_hip_vecchia_sim`, fit, theta_list, iiderrors, n_fixed, z_col)
+}
+
+# the one body of .cocons.hip.vecchia.sim and .cocons.hip.vecchia.sim.grouped
+.cocons.hip.vecchia.sim.by <- function(shim, fit, theta_list, iiderrors, n_fixed, z_col) {
   iiderrors <- as.matrix(iiderrors)
   storage.mode(iiderrors) <- "double"
-  res <- .Call(`_cocons_hip_vecchia_sim`, fit, theta_list, as.integer(n_fixed), as.integer(z_col), iiderrors)
+  res <- .Call(shim, fit, theta_list, as.integer(n_fixed), as.integer(z_col), iiderrors)
   if (res[[1]] > 0L) stop("Cholesky error")
   res[[2]]
 }
@@ -624,9 +634,14 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
 
 # U'W for the n x c matrix W and diag(U'U): list(out, qdiag)
 .cocons.hip.vecchia.whiten.t <- function(fit, theta_list, W) {
+  .cocons.hip.vecchia.whiten.t.by(`_cocons_hip_vecchia_whiten_t`, fit, theta_list, W)
+}
+
+# the one body of .cocons.hip.vecchia.whiten.t and .cocons.hip.vecchia.whiten.t.grouped
+.cocons.hip.vecchia.whiten.t.by <- function(shim, fit, theta_list, W) {
   W <- as.matrix(W)
   storage.mode(W) <- "double"
-  res <- .Call(`_cocons_hip_vecchia_whiten_t`, fit, theta_list[names(theta_list) != "mean"], W)
+  res <- .Call(shim, fit, theta_list[names(theta_list) != "mean"], W)
   if (res[[1]] > 0L) stop("Cholesky error")
   list(out = res[[2]][[1]], qdiag = res[[2]][[2]])
 }
@@ -692,8 +707,34 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
 # cross-validated predictions of the Vecchia model (cocons_cv_vecchia): what .cocons.hip.cv returns, from U'U -- no refit and
 # no n x n matrix.  fold: one label of any kind per observation, every fold of at most 128 observations (NULL: leave-one-out)
 .cocons.hip.vecchia.cv <- function(fit, theta_list, fold = NULL, safe = TRUE) {
+  .cocons.hip.vecchia.cv.by(`_cocons_hip_vecchia_cv`, fit, theta_list, fold, safe)
+}
+
+# the one body of .cocons.hip.vecchia.cv and .cocons.hip.vecchia.cv.grouped
+.cocons.hip.vecchia.cv.by <- function(shim, fit, theta_list, fold, safe) {
   if (!is.null(fold)) fold <- match(fold, unique(fold)) - 1L
-  res <- .cocons.hip.result(.Call(`_cocons_hip_vecchia_cv`, fit, theta_list, fold), safe)
+  res <- .cocons.hip.result(.Call(shim, fit, theta_list, fold), safe)
   if (is.null(res)) return(NULL)
   list(resid = res[[1]], var = res[[2]], stats = res[[3]])
+}
+
+# U^-1, U' and cross-validation with the rows' coefficients from one factorisation per block (DESIGN.md 4ab;
+# cocons_vecchia_unwhiten_grouped, cocons_sim_vecchia_grouped, cocons_vecchia_whiten_t_grouped, cocons_cv_vecchia_grouped): the
+# bits of the ungrouped wrappers on the same fit, through their bodies (the wrappers' own argument lists are part of the layer's
+# contract, so the switch is the shim that the shared body calls); the fit needs a plan (.cocons.hip.vecchia.set.groups
+# attaches one)
+.cocons.hip.vecchia.unwhiten.grouped <- function(fit, theta_list, W) {
+  .cocons.hip.vecchia.unwhiten.by(`_cocons_hip_vecchia_unwhiten_grouped`, fit, theta_list, W)
+}
+
+.cocons.hip.vecchia.sim.grouped <- function(fit, theta_list, iiderrors, n_fixed = 0L, z_col = 1L) {
+  .cocons.hip.vecchia.sim.by(`_cocons_hip_vecchia_sim_grouped`, fit, theta_list, iiderrors, n_fixed, z_col)
+}
+
+.cocons.hip.vecchia.whiten.t.grouped <- function(fit, theta_list, W) {
+  .cocons.hip.vecchia.whiten.t.by(`_cocons_hip_vecchia_whiten_t_grouped`, fit, theta_list, W)
+}
+
+.cocons.hip.vecchia.cv.grouped <- function(fit, theta_list, fold = NULL, safe = TRUE) {
+  .cocons.hip.vecchia.cv.by(`_cocons_hip_vecchia_cv_grouped`, fit, theta_list, fold, safe)
 }

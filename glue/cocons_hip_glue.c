@@ -1096,8 +1096,9 @@ SEXP _cocons_hip_vecchia_order(SEXP locs, SEXP device)
     return ord;
 }
 
-/* U^-1 W on a Vecchia handle (cocons_vecchia_unwhiten): W is n x c; list(status, the n x c result); theta without `mean` */
-SEXP _cocons_hip_vecchia_unwhiten(SEXP fitp, SEXP theta, SEXP W)
+/* U^-1 W on a Vecchia handle (cocons_vecchia_unwhiten): W is n x c; list(status, the n x c result); theta without `mean`.
+ * grouped: the coefficients from one factorisation per block (cocons_vecchia_unwhiten_grouped) */
+static SEXP vecchia_unwhiten(SEXP fitp, SEXP theta, SEXP W, int grouped)
 {
     cocons_fit *f = fit_of(fitp);
     const int p = fit_p(fitp), n = fit_n(fitp);
@@ -1107,17 +1108,22 @@ SEXP _cocons_hip_vecchia_unwhiten(SEXP fitp, SEXP theta, SEXP W)
     theta_table(theta, p, T);
     SEXP v = PROTECT(Rf_allocMatrix(REALSXP, n, c));
     for (R_xlen_t e = 0; e < XLENGTH(v); ++e) REAL(v)[e] = NA_REAL;
-    int rc = cocons_vecchia_unwhiten(f, T, c, REAL(W), REAL(v));
+    int rc = (grouped ? cocons_vecchia_unwhiten_grouped : cocons_vecchia_unwhiten)(f, T, c, REAL(W), REAL(v));
     hip_check(rc, "cocoSim (Vecchia, unwhiten)");
     SEXP out = status_value(rc, v);
     UNPROTECT(1);
     return out;
 }
 
+SEXP _cocons_hip_vecchia_unwhiten(SEXP fitp, SEXP theta, SEXP W)
+{
+    return vecchia_unwhiten(fitp, theta, W, 0);
+}
+
 /* fields and conditional draws of the Vecchia model (cocons_sim_vecchia): theta is the WHOLE theta_list (`mean` read by name),
  * n_fixed the number of leading rows held at z[, z_col] (z_col 1-based), iiderrors (n - n_fixed) x nsim;
- * list(status, the (n - n_fixed) x nsim result) */
-SEXP _cocons_hip_vecchia_sim(SEXP fitp, SEXP theta, SEXP n_fixed, SEXP z_col, SEXP iiderrors)
+ * list(status, the (n - n_fixed) x nsim result).  grouped: cocons_sim_vecchia_grouped */
+static SEXP vecchia_sim(SEXP fitp, SEXP theta, SEXP n_fixed, SEXP z_col, SEXP iiderrors, int grouped)
 {
     cocons_fit *f = fit_of(fitp);
     const int p = fit_p(fitp), n = fit_n(fitp), nf = Rf_asInteger(n_fixed);
@@ -1131,11 +1137,17 @@ SEXP _cocons_hip_vecchia_sim(SEXP fitp, SEXP theta, SEXP n_fixed, SEXP z_col, SE
     theta_table(theta, p, T);
     SEXP v = PROTECT(Rf_allocMatrix(REALSXP, n - nf, nsim));
     for (R_xlen_t e = 0; e < XLENGTH(v); ++e) REAL(v)[e] = NA_REAL;
-    int rc = cocons_sim_vecchia(f, T, REAL(mean), nf, Rf_asInteger(z_col) - 1, nsim, REAL(iiderrors), REAL(v));
+    int rc = (grouped ? cocons_sim_vecchia_grouped : cocons_sim_vecchia)(f, T, REAL(mean), nf, Rf_asInteger(z_col) - 1, nsim,
+                                                                         REAL(iiderrors), REAL(v));
     hip_check(rc, "cocoSim (Vecchia)");
     SEXP out = status_value(rc, v);
     UNPROTECT(1);
     return out;
+}
+
+SEXP _cocons_hip_vecchia_sim(SEXP fitp, SEXP theta, SEXP n_fixed, SEXP z_col, SEXP iiderrors)
+{
+    return vecchia_sim(fitp, theta, n_fixed, z_col, iiderrors, 0);
 }
 
 /* the level schedule of (table, n_fixed) (cocons_vecchia_schedule): list(levels = n integers, info = c(depth, rows of the
@@ -1183,8 +1195,8 @@ SEXP _cocons_hip_vecchia_transpose(SEXP fitp)
 }
 
 /* U'W and diag(U'U) on a Vecchia handle (cocons_vecchia_whiten_t): W is n x c; list(status, list(the n x c result, the n
- * diagonal entries)); theta without `mean` */
-SEXP _cocons_hip_vecchia_whiten_t(SEXP fitp, SEXP theta, SEXP W)
+ * diagonal entries)); theta without `mean`.  grouped: cocons_vecchia_whiten_t_grouped */
+static SEXP vecchia_whiten_t(SEXP fitp, SEXP theta, SEXP W, int grouped)
 {
     cocons_fit *f = fit_of(fitp);
     const int p = fit_p(fitp), n = fit_n(fitp);
@@ -1196,7 +1208,7 @@ SEXP _cocons_hip_vecchia_whiten_t(SEXP fitp, SEXP theta, SEXP W)
     SEXP q = PROTECT(Rf_allocVector(REALSXP, n));
     for (R_xlen_t e = 0; e < XLENGTH(v); ++e) REAL(v)[e] = NA_REAL;
     for (R_xlen_t e = 0; e < XLENGTH(q); ++e) REAL(q)[e] = NA_REAL;
-    int rc = cocons_vecchia_whiten_t(f, T, c, REAL(W), REAL(v), REAL(q));
+    int rc = (grouped ? cocons_vecchia_whiten_t_grouped : cocons_vecchia_whiten_t)(f, T, c, REAL(W), REAL(v), REAL(q));
     hip_check(rc, "Vecchia whiten (transposed)");
     SEXP res = PROTECT(Rf_allocVector(VECSXP, 2));
     SET_VECTOR_ELT(res, 0, v);
@@ -1204,6 +1216,11 @@ SEXP _cocons_hip_vecchia_whiten_t(SEXP fitp, SEXP theta, SEXP W)
     SEXP out = status_value(rc, res);
     UNPROTECT(3);
     return out;
+}
+
+SEXP _cocons_hip_vecchia_whiten_t(SEXP fitp, SEXP theta, SEXP W)
+{
+    return vecchia_whiten_t(fitp, theta, W, 0);
 }
 
 /* grouped Vecchia blocks.  The greedy groups of the n x m neighbour matrix nn (cocons_vecchia_group; integer, or
@@ -1320,8 +1337,8 @@ SEXP _cocons_hip_vecchia_whiten_grouped(SEXP fitp, SEXP theta, SEXP W)
 
 /* cross-validated predictions of the Vecchia model (cocons_cv_vecchia): theta is the WHOLE theta_list (`mean` read by name),
  * fold NULL (leave-one-out) or n integer labels from 0; list(status, list(resid n x r, var n, stats = c(folds of one, folds
- * of 2 .. 128, entries, device bytes of the call))) */
-SEXP _cocons_hip_vecchia_cv(SEXP fitp, SEXP theta, SEXP fold)
+ * of 2 .. 128, entries, device bytes of the call))).  grouped: cocons_cv_vecchia_grouped */
+static SEXP vecchia_cv(SEXP fitp, SEXP theta, SEXP fold, int grouped)
 {
     cocons_fit *f = fit_of(fitp);
     const int p = fit_p(fitp), n = fit_n(fitp), r = fit_r(fitp);
@@ -1343,7 +1360,7 @@ SEXP _cocons_hip_vecchia_cv(SEXP fitp, SEXP theta, SEXP fold)
     SEXP var = PROTECT(Rf_allocVector(REALSXP, n));
     for (R_xlen_t e = 0; e < XLENGTH(resid); ++e) REAL(resid)[e] = NA_REAL;
     for (R_xlen_t e = 0; e < XLENGTH(var); ++e) REAL(var)[e] = NA_REAL;
-    int rc = cocons_cv_vecchia(f, T, REAL(mean), nfold, lab, REAL(resid), REAL(var), s4);
+    int rc = (grouped ? cocons_cv_vecchia_grouped : cocons_cv_vecchia)(f, T, REAL(mean), nfold, lab, REAL(resid), REAL(var), s4);
     hip_check(rc, "cross-validation (Vecchia)");
     SEXP stats = PROTECT(Rf_allocVector(REALSXP, 4));
     for (int i = 0; i < 4; ++i) REAL(stats)[i] = (double)s4[i];
@@ -1354,6 +1371,34 @@ SEXP _cocons_hip_vecchia_cv(SEXP fitp, SEXP theta, SEXP fold)
     SEXP out = status_value(rc, res);
     UNPROTECT(4);
     return out;
+}
+
+SEXP _cocons_hip_vecchia_cv(SEXP fitp, SEXP theta, SEXP fold)
+{
+    return vecchia_cv(fitp, theta, fold, 0);
+}
+
+/* _cocons_hip_vecchia_unwhiten, _sim, _whiten_t and _cv with the rows' coefficients from one factorisation per block of the
+ * handle's plan (cocons_vecchia_unwhiten_grouped, cocons_sim_vecchia_grouped, cocons_vecchia_whiten_t_grouped,
+ * cocons_cv_vecchia_grouped): the same lists, the same bits */
+SEXP _cocons_hip_vecchia_unwhiten_grouped(SEXP fitp, SEXP theta, SEXP W)
+{
+    return vecchia_unwhiten(fitp, theta, W, 1);
+}
+
+SEXP _cocons_hip_vecchia_sim_grouped(SEXP fitp, SEXP theta, SEXP n_fixed, SEXP z_col, SEXP iiderrors)
+{
+    return vecchia_sim(fitp, theta, n_fixed, z_col, iiderrors, 1);
+}
+
+SEXP _cocons_hip_vecchia_whiten_t_grouped(SEXP fitp, SEXP theta, SEXP W)
+{
+    return vecchia_whiten_t(fitp, theta, W, 1);
+}
+
+SEXP _cocons_hip_vecchia_cv_grouped(SEXP fitp, SEXP theta, SEXP fold)
+{
+    return vecchia_cv(fitp, theta, fold, 1);
 }
 
 /* kriging from a held band factor on a taper handle: factor S(theta) once for realization z_col (1-based) and keep the band
@@ -1541,6 +1586,10 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_vecchia_neg2loglik_grouped", (DL_FUNC)&_cocons_hip_vecchia_neg2loglik_grouped, 3},
     {"_cocons_hip_vecchia_neg2loglik_grad_grouped", (DL_FUNC)&_cocons_hip_vecchia_neg2loglik_grad_grouped, 3},
     {"_cocons_hip_vecchia_fisher_grouped", (DL_FUNC)&_cocons_hip_vecchia_fisher_grouped, 3},
+    {"_cocons_hip_vecchia_unwhiten_grouped", (DL_FUNC)&_cocons_hip_vecchia_unwhiten_grouped, 3},
+    {"_cocons_hip_vecchia_sim_grouped", (DL_FUNC)&_cocons_hip_vecchia_sim_grouped, 5},
+    {"_cocons_hip_vecchia_whiten_t_grouped", (DL_FUNC)&_cocons_hip_vecchia_whiten_t_grouped, 3},
+    {"_cocons_hip_vecchia_cv_grouped", (DL_FUNC)&_cocons_hip_vecchia_cv_grouped, 3},
     {"_cocons_hip_vecchia_whiten_grouped", (DL_FUNC)&_cocons_hip_vecchia_whiten_grouped, 3},
     {"_cocons_hip_fit_close", (DL_FUNC)&_cocons_hip_fit_close, 1},
     {"_cocons_hip_neg2loglik_parts", (DL_FUNC)&_cocons_hip_neg2loglik_parts, 3},

@@ -557,6 +557,26 @@ int cocons_neg2loglik_grad_vecchia_grouped(cocons_fit *fit, const double *theta,
  * message.  Refused (-1): a handle without a plan (cocons_vecchia_set_groups attaches one).                                  */
 int cocons_fisher_vecchia_grouped(cocons_fit *fit, const double *theta, int ndir, const double *dirs,
                                   double *info, double *info_mean);
+/* U^-1, U' and cross-validation on the grouped schedule.  All four entries start from the rows' coefficients
+ * s = C^-T e_last; here they come from one factorisation per BLOCK -- the member at position p solves backward on the leading
+ * (p + 1) x (p + 1) sub-factor, component j = (e_p[j] - sum_{i > j} L(i, j) s[i]) / L(j, j) with i descending -- into the
+ * same records, and everything behind them (the schedule, the level solve, the transposed lists, U'w, the fold blocks) is
+ * the ungrouped entry's code.  Each entry has its twin's arguments, conventions, return codes -- the smallest failing 1-based
+ * row among the rows that are not fixed included -- and refusals under its own name, writes its outputs on 0 only, and
+ * repeats to the bit whatever COCONS_VECCHIA_GROUP_ORDER says.  Refused (-1): a handle without a plan
+ * (cocons_vecchia_set_groups attaches one).
+ * cocons_vecchia_unwhiten_grouped returns the bits of cocons_vecchia_unwhiten on the same handle.                          */
+int cocons_vecchia_unwhiten_grouped(cocons_fit *fit, const double *theta, int c, const double *W, double *out);
+/* cocons_sim_vecchia_grouped returns the bits of cocons_sim_vecchia on the same handle; with n_fixed > 0 the blocks whose
+ * rows are all fixed do no work and a member row below n_fixed gets no record.                                              */
+int cocons_sim_vecchia_grouped(cocons_fit *fit, const double *theta, const double *mean, int n_fixed, int z_col,
+                               int nsim, const double *iiderrors, double *out);
+/* cocons_vecchia_whiten_t_grouped returns the bits of cocons_vecchia_whiten_t on the same handle.                          */
+int cocons_vecchia_whiten_t_grouped(cocons_fit *fit, const double *theta, int c, const double *W, double *out /* n x c: U'W */,
+                                    double *qdiag /* n: diag(U'U), may be NULL */);
+/* cocons_cv_vecchia_grouped returns the bits of cocons_cv_vecchia on the same handle.                                      */
+int cocons_cv_vecchia_grouped(cocons_fit *fit, const double *theta, const double *mean, int nfold, const int *fold,
+                              double *resid /* n x r */, double *var /* n */, long long *stats4 /* may be NULL */);
 
 /* ---- fit handle: everything that is constant over an optimisation -------------
  * Created once per cocoOptim / getHessian call from the arguments the reference

@@ -85,6 +85,11 @@ int cocons_debug_order_phases(int n, const double *locs, int device, int binned_
  * cocons_vecchia_unwhiten's, under this entry's name.                                                                    */
 int cocons_debug_vecchia_sim_phases(struct cocons_fit *fit, const double *theta, int c, const double *W, double *out,
                                     double *ms3);
+/* cocons_debug_vecchia_sim_phases on the grouped schedule (cocons_vecchia_unwhiten_grouped): the first phase is
+ * the records and the grouped coefficient launch.  For tools/vecchia_group_coef_timing.py.  Returns and refusals as
+ * cocons_vecchia_unwhiten_grouped's, under this entry's name.                                                            */
+int cocons_debug_vecchia_sim_phases_grouped(struct cocons_fit *fit, const double *theta, int c, const double *W, double *out,
+                                            double *ms3);
 
 /* The transposed lists of a Vecchia handle's table (cocons_vecchia_transpose) built anew, whether the handle holds them or
  * not, with the build's phases timed by events on the handle's stream: ms4 = { in-degree counts, the scan, the fill, the
