@@ -76,12 +76,18 @@ SIGNATURES = {
     "cocons_vecchia_whiten_t": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_dp]),
     "cocons_vecchia_group": (c_int, [c_int, c_int, ctypes.POINTER(c_int), c_int, ctypes.POINTER(c_int),
                                      ctypes.POINTER(ctypes.c_longlong)]),
+    "cocons_vecchia_group_rounds": (c_int, [c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, ctypes.POINTER(c_int),
+                                            ctypes.POINTER(ctypes.c_longlong)]),
+    "cocons_vecchia_group_device": (c_int, [c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_int, ctypes.POINTER(c_int),
+                                            ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_vecchia_group_table": (c_int, [c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int,
                                            ctypes.POINTER(c_int)]),
     "cocons_vecchia_set_groups": (c_int, [c_vp, ctypes.POINTER(c_int)]),
     "cocons_vecchia_groups_info": (c_int, [c_vp, ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_fit_create_vecchia_grouped": (c_vp, [c_int, c_int, c_int, c_dp, c_dp, c_dp, c_dp, c_int, c_int, ctypes.POINTER(c_int),
                                                  c_int]),
+    "cocons_fit_create_vecchia_grouped_knn": (c_vp, [c_int, c_int, c_int, c_dp, c_dp, c_dp, c_dp, c_int, c_int, c_int, c_int]),
+    "cocons_vecchia_groups_export": (c_int, [c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "cocons_neg2loglik_vecchia_grouped": (c_int, [c_vp, c_dp, c_dp, c_dp, c_dp]),
     "cocons_vecchia_whiten_grouped": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_dp]),
     "cocons_neg2loglik_grad_vecchia_grouped": (c_int, [c_vp, c_dp, c_dp, c_int, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
@@ -166,6 +172,7 @@ DIAG_SIGNATURES = {
     "cocons_debug_knn_plan": (c_int, [c_int, c_dp, c_int, c_int, c_dp, c_int, ctypes.POINTER(c_int), c_dp, ctypes.POINTER(c_int),
                                       c_dp]),
     "cocons_debug_knn_phases": (c_int, [c_int, c_dp, c_int, c_int, c_dp]),
+    "cocons_debug_group_rounds": (c_int, [c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), c_dp]),
     "cocons_debug_order_plan": (c_int, [c_int, c_dp, ctypes.POINTER(c_int), c_dp, c_dp]),
     "cocons_debug_order_phases": (c_int, [c_int, c_dp, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_dp,
                                           ctypes.POINTER(ctypes.c_longlong)]),

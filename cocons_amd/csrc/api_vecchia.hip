@@ -36,8 +36,10 @@ static int vecchia_row(const int *nn, size_t rows, int m, size_t i, int limit, i
 static const char *const vecchia_offence[] = {"", "names an index outside its range", "names an index twice"};
 
 cocons_fit *vecchia_create_impl(const char *who, int n, int p, int r, const double *locs, const double *X, const double *z,
-                                const double *smooth_limits, int device, int m, const int *nn, bool search)
+                                const double *smooth_limits, int device, int m, const int *nn, bool search,
+                                VecchiaTableSource *src)
 {
+    if (src) search = true;                     // (no table comes in either way)
     if (!locs || !X || !z || !smooth_limits || (!search && !nn)) { fail(-1, "%s: null argument", who); return nullptr; }
     if (n < 1) { fail(-1, "%s: n = %d (at least one observation expected)", who, n); return nullptr; }
     if (p < 1 || p > COCONS_P_MAX || r < 1) { fail(-1, "%s: bad argument (p = %d, r = %d)", who, p, r); return nullptr; }
@@ -67,12 +69,21 @@ cocons_fit *vecchia_create_impl(const char *who, int n, int p, int r, const doub
     f->vecchia.reset(new VecchiaState());
     VecchiaState *V = f->vecchia.get();
     V->m = m;
-    if (hipError_t e = V->nbr.alloc((size_t)n * m)) return drop(e);
+    if (!src)
+        if (hipError_t e = V->nbr.alloc((size_t)n * m)) return drop(e);
     if (hipError_t e = V->aos.alloc((size_t)VECCHIA_REC * n)) return drop(e);
     if (hipError_t e = V->B.alloc((size_t)n * r)) return drop(e);
     if (hipError_t e = V->W.alloc((size_t)n * (1 + r))) return drop(e);
     if (hipError_t e = V->part.alloc(vecchia_sum_scratch_doubles(n, 1 + r))) return drop(e);
-    if (search) {
+    if (src) {
+        // the table is made on the device by the caller's source and adopted
+        if (src->make(who, f, locs)) {
+            (void)hipGetLastError();
+            f->op_mu.unlock();
+            cocons_fit_destroy(f);
+            return nullptr;
+        }
+    } else if (search) {
         // the table straight into V->nbr: it never exists on the host
         if (knn_self_search(who, n, locs, locs + n, f->dlocs, f->dlocs + n, m, nullptr, V->nbr, f->stream)) {
             (void)hipGetLastError();

@@ -758,8 +758,16 @@ int knn_grid_build(const char *who, PatternGridBufs &G, int n, const double *hx,
                    const double *dy, hipStream_t s);
 int knn_self_search(const char *who, int n, const double *hx, const double *hy, const double *dx, const double *dy, int m,
                     int *d_nn, int *d_tab, hipStream_t s, KnnPhases *phases = nullptr);
+// src (may be null; nn and search are then not looked at): the table is made on the device by the caller of
+// vecchia_create_impl and adopted -- make() runs with the handle's data on the device and its stream open, leaves V->nbr and
+// V->m (and may attach V->grp), and returns 0 or a failure with the message set; m only bounds the search
+struct VecchiaTableSource {
+    virtual ~VecchiaTableSource() = default;
+    virtual int make(const char *who, cocons_fit *f, const double *locs) = 0;
+};
 cocons_fit *vecchia_create_impl(const char *who, int n, int p, int r, const double *locs, const double *X, const double *z,
-                                const double *smooth_limits, int device, int m, const int *nn, bool search);
+                                const double *smooth_limits, int device, int m, const int *nn, bool search,
+                                VecchiaTableSource *src = nullptr);
 int vecchia_predict_impl(const char *who, cocons_fit *f, const double *theta, const double *mean, int z_col, int mp,
                          const double *locs_pred, const double *X_pred, int m_pred, const int *nn_pred, bool search,
                          double *stochastic, double *quadform);

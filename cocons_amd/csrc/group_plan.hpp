@@ -107,6 +107,108 @@ inline int group_greedy(const GroupTable &t, int max_rows, int *group)
     return next;
 }
 
+// The round rule: a grouping that is a function of the table's neighbour SETS alone, stated so that a device
+// can run it -- every round reads only the state at its start.  A block's id is its smallest member.  One round:
+//   1. every live block A proposes the eligible candidate B (a block that holds a neighbour of a member of A; eligible: the
+//      greedy rule's test, u <= max_rows and u^2 < a^2 + b^2) of the largest gain g = a^2 + b^2 - u^2, ties to the smaller id;
+//      key(A) = (8192 - g) << 32 | A;
+//   2. best(X) = the smallest key(A) over the proposing A with A = X or prop(A) = X;
+//   3. the edge A -> prop(A) = B is realised when best(A) = best(B) = key(A); realised edges share no block, and each merges
+//      its two blocks into the smaller id.
+// The rounds end with the first round without a proposal, or after max_rounds rounds (0: GROUP_ROUNDS_MAX).
+constexpr int GROUP_ROUNDS_MAX = 256;
+constexpr unsigned long long GROUP_NO_KEY = ~0ull;
+
+constexpr unsigned long long group_key(int a, int b, int u, int id)    // (constexpr: the kernels of group.hip call it too)
+{
+    return (unsigned long long)(8192 - (a * a + b * b - u * u)) << 32 | (unsigned)id;
+}
+
+// The state of the round rule after its rounds: blk[n] (row -> id of its block) and S (per id; empty once absorbed).
+// Returns the rounds that merged something.
+inline int group_rounds_state(const GroupTable &t, int max_rows, int max_rounds, std::vector<int> &blk,
+                              std::vector<std::vector<int>> &S)
+{
+    const size_t n = t.n;
+    const int cap = max_rounds > 0 ? max_rounds : GROUP_ROUNDS_MAX;
+    blk.resize(n);
+    S.assign(n, std::vector<int>());
+    std::vector<int> live(n), prop(n, -1), seen, un;
+    std::vector<unsigned long long> key(n, GROUP_NO_KEY), best(n, GROUP_NO_KEY);
+    for (size_t i = 0; i < n; ++i) {
+        blk[i] = live[i] = (int)i;
+        S[i].assign(1, (int)i);
+        t.each(i, [&](int j) { S[i].push_back(j); });
+        std::sort(S[i].begin(), S[i].end());
+    }
+    int rounds = 0;
+    while (rounds < cap) {
+        bool any = false;
+        for (int A : live) {
+            key[(size_t)A] = best[(size_t)A] = GROUP_NO_KEY;
+            prop[(size_t)A] = -1;
+        }
+        for (int A : live) {
+            const std::vector<int> &sa = S[(size_t)A];
+            const int a = (int)sa.size();
+            if (a > max_rows) continue;
+            // every row of S(A) that is no member is a neighbour of one: the candidates are the blocks of S(A)'s rows
+            seen.clear();
+            unsigned long long kb = GROUP_NO_KEY;      // (8192 - g) << 32 | B: the smallest is the largest gain, then the smaller id
+            for (int s : sa) {
+                const int B = blk[(size_t)s];
+                if (B == A || std::find(seen.begin(), seen.end(), B) != seen.end()) continue;
+                seen.push_back(B);
+                const int b = (int)S[(size_t)B].size();
+                if (b > max_rows) continue;
+                const int u = group_union(sa, S[(size_t)B], nullptr);
+                if (u > max_rows || u * u >= a * a + b * b) continue;
+                kb = std::min(kb, group_key(a, b, u, B));
+            }
+            if (kb == GROUP_NO_KEY) continue;
+            any = true;
+            prop[(size_t)A] = (int)(kb & 0xffffffffull);
+            key[(size_t)A] = (kb >> 32) << 32 | (unsigned)A;
+        }
+        if (!any) break;
+        for (int A : live)
+            if (prop[(size_t)A] >= 0) {
+                best[(size_t)A] = std::min(best[(size_t)A], key[(size_t)A]);
+                best[(size_t)prop[(size_t)A]] = std::min(best[(size_t)prop[(size_t)A]], key[(size_t)A]);
+            }
+        for (int A : live) {
+            const int B = prop[(size_t)A];
+            if (B < 0 || best[(size_t)A] != key[(size_t)A] || best[(size_t)B] != key[(size_t)A]) continue;
+            const int lo = std::min(A, B), hi = std::max(A, B);
+            group_union(S[(size_t)lo], S[(size_t)hi], &un);
+            for (int s : S[(size_t)hi]) if (blk[(size_t)s] == hi) blk[(size_t)s] = lo;
+            S[(size_t)lo] = un;
+            std::vector<int>().swap(S[(size_t)hi]);
+        }
+        live.erase(std::remove_if(live.begin(), live.end(), [&](int A) { return blk[(size_t)A] != A; }), live.end());
+        ++rounds;
+    }
+    return rounds;
+}
+
+// group[n]: the labels of the round rule's partition, the blocks numbered by their smallest member, ascending, as
+// group_greedy's are; *rounds_run (may be null): the rounds that merged something.  Returns the number of blocks.
+inline int group_rounds(const GroupTable &t, int max_rows, int max_rounds, int *group, int *rounds_run)
+{
+    std::vector<int> blk;
+    std::vector<std::vector<int>> S;
+    const int rounds = group_rounds_state(t, max_rows, max_rounds, blk, S);
+    if (rounds_run) *rounds_run = rounds;
+    std::vector<int> id(t.n, -1);
+    int next = 0;
+    for (size_t i = 0; i < t.n; ++i) {
+        int &l = id[(size_t)blk[i]];
+        if (l < 0) l = next++;
+        group[i] = l;
+    }
+    return next;
+}
+
 // What the kernel walks: block b holds the rows rows[off[b] .. off[b + 1]) -- S(b), ascending, 0-based --, bit p of mask[b]
 // says whether the row at position p is a member, and order[] lists the blocks largest first (ties: the smaller id first),
 // the sequence a launch deals them to its workgroups in.  The blocks are numbered by their smallest member, ascending,

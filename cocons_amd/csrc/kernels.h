@@ -481,6 +481,50 @@ hipError_t launch_order_emit(const OrderArgs &a, int *cnt, int *first, long long
 // the rest: order[base + j] = orig[rem[j]] + 1
 hipError_t launch_order_rest(const OrderArgs &a, int base, int *order, hipStream_t s);
 
+// ---- grouping Vecchia rows in rounds (group.hip; the rule: group_plan.hpp) ----------------------------------
+// The state, by block id (a block's id is its smallest member): blk[row] = the id of the row's block, sz[id] = |S(id)|,
+// slot[id max_rows ..] = S(id) ascending -- written only while |S| <= max_rows: a larger S belongs to a row that never
+// merges and is never read.  A round is three launches over the live ids: every block proposes (prop, key; the best keys by
+// 64-bit atomic minima into best, all ones = none; *any = 1 when somebody proposed), every realised edge merges, and the
+// survivors are gathered into next (their best words set to all ones again, *count = their number).  No floating point.
+struct GroupArgs {
+    int n = 0, m = 0, max_rows = 0;
+    const int *tab = nullptr;           // n x m, the layout of VecchiaState::nbr
+    int *blk = nullptr, *sz = nullptr, *slot = nullptr, *prop = nullptr;
+    unsigned long long *key = nullptr, *best = nullptr;
+    const int *live = nullptr; int nlive = 0;
+    int *next = nullptr;
+    int *any = nullptr, *count = nullptr;
+};
+// every row a block of its own: blk, sz, slot, best, and live = 0 .. n - 1 written into a.next
+hipError_t launch_group_init(const GroupArgs &a, hipStream_t s);
+hipError_t launch_group_propose(const GroupArgs &a, hipStream_t s);
+hipError_t launch_group_merge(const GroupArgs &a, hipStream_t s);
+hipError_t launch_group_compact(const GroupArgs &a, hipStream_t s);
+
+// The plan and the expanded table of the state the rounds left (group_plan.hpp's group_plan and group_table on the same
+// partition, integer for integer), four launches: flags (flag[i] = row i is a block's id; its exclusive scan num numbers the
+// blocks by smallest member), sizes (ids[b], off[b] = |S(b)| -- scanned in place afterwards -- and hist[k] = the blocks of k
+// rows, from which the host takes the statistics and start[]), fill (one wavefront per block: rows, mask, and the expanded
+// row of every member into nbr, n x m_out in the layout of VecchiaState::nbr) and order (the blocks largest first, stable in
+// the id: one workgroup per size walks the blocks in ascending order, start[64 - k] is where size k begins).
+struct GroupPlanArgs {
+    int n = 0, m = 0, max_rows = 0, blocks = 0, m_out = 0;
+    const int *tab = nullptr, *blk = nullptr, *sz = nullptr, *slot = nullptr;
+    int *flag = nullptr;                // n
+    const int *num = nullptr;           // n + 1
+    int *ids = nullptr;                 // blocks
+    int *off = nullptr;                 // blocks + 1
+    int *hist = nullptr;                // GROUP_ROWS_MAX + 1
+    int *rows = nullptr, *order = nullptr, *nbr = nullptr;
+    unsigned long long *mask = nullptr;
+    int start[65] = {};
+};
+hipError_t launch_group_plan_flags(const GroupPlanArgs &a, hipStream_t s);
+hipError_t launch_group_plan_sizes(const GroupPlanArgs &a, hipStream_t s);
+hipError_t launch_group_plan_fill(const GroupPlanArgs &a, hipStream_t s);
+hipError_t launch_group_plan_order(const GroupPlanArgs &a, hipStream_t s);
+
 // ---- analytic gradient of the dense -2 log-likelihood (grad.hip) ----------------------------------------------------------
 constexpr int GSITE_FIELDS = 4;    // launch_grad_site: dtilt/deta, cot(tilt), dlog(nu_ij)/deta_smooth, exp(eta_sd)
 struct GradArgs {

@@ -1550,6 +1550,34 @@ def vecchia_group(nn, max_rows=64, stats=False):
     return group
 
 
+def _group_rounds(entry, nn, max_rows, max_rounds, stats, *device):
+    L = _lib.load()
+    nn = np.asarray(nn)
+    nn, m = _nn_table(nn, nn.shape[0])
+    group = np.zeros(nn.shape[0], dtype=np.int32)
+    out = (ctypes.c_longlong * 5)()
+    _lib.check(getattr(L, entry)(nn.shape[0], m, _ip(nn), int(max_rows), int(max_rounds), *device, _ip(group), out), entry)
+    if stats:
+        return group, {"blocks": int(out[0]), "rows": int(out[1]), "pairs": int(out[2]), "pairs_ungrouped": int(out[3]),
+                       "rounds": int(out[4])}
+    return group
+
+
+def vecchia_group_rounds(nn, max_rows=64, max_rounds=0, stats=False):
+    """The ROUND rule's grouping of the rows of `nn` (cocons_vecchia_group_rounds): n int32 block ids, 0-based,
+    numbered by their smallest member.  Every round, each block proposes the neighbouring block whose merge saves the most
+    (the gain |S(A)|^2 + |S(B)|^2 - |S(A) u S(B)|^2 under `vecchia_group`'s test, ties to the smaller id), and the proposals
+    that are the best of both their blocks are merged; the rounds end when nobody proposes, or after `max_rounds` (0: 256).
+    The partition is a function of the rows' neighbour sets and is not the greedy one.  `stats` as `vecchia_group`'s, with
+    "rounds", the rounds that merged something.  On the host; nothing here needs a device."""
+    return _group_rounds("cocons_vecchia_group_rounds", nn, max_rows, max_rounds, stats)
+
+
+def vecchia_group_device(nn, max_rows=64, max_rounds=0, stats=False, device=0):
+    """`vecchia_group_rounds` on the device (cocons_vecchia_group_device): the same labels and rounds, integer for integer."""
+    return _group_rounds("cocons_vecchia_group_device", nn, max_rows, max_rounds, stats, int(device))
+
+
 def vecchia_group_table(nn, group, m_out=None) -> np.ndarray:
     """The expanded table of ANY partition `group` of nn's rows (cocons_vecchia_group_table): row i names every earlier row of
     S(block(i)) -- its own neighbours and those of the block's other members --, n x m_out int32 in Fortran order, 1-based,
@@ -1587,18 +1615,44 @@ class CoconsVecchiaFit(_Handle):
         return self
 
     @classmethod
+    def from_groups_knn(cls, locs, x_covariates, z, smooth_limits, m, max_rows=64, max_rounds=0, device=-1):
+        """The grouped handle made on the device (cocons_fit_create_vecchia_grouped_knn): the search of
+        `from_knn`, the round rule of `vecchia_group_device`, the plan and the expanded table, none of which reaches the host.
+        The handle of `vecchia_neighbours_device` -> `vecchia_group_rounds` -> `vecchia_group_table` -> the constructor ->
+        `set_groups` on the same data, to the bit; `groups_export` reads the partition and the table back."""
+        self = cls.__new__(cls)
+        locs, X, z = self._adopt(locs, x_covariates, z, smooth_limits)
+        self._created(self._L.cocons_fit_create_vecchia_grouped_knn(self.n, self.p, self.r, _p(locs), _p(X), _p(z),
+                                                                    _p(self.smooth_limits), int(device), int(m), int(max_rows),
+                                                                    int(max_rounds)), "cocons_fit_create_vecchia_grouped_knn")
+        self.m = self.info()["m"]
+        return self
+
+    @classmethod
     def from_maxmin(cls, locs, x_covariates, z, smooth_limits, m, device=-1):
         """`from_knn` on the rows in the maxmin order of `vecchia_order_device(locs)`: the order is found on the device, the
         data is permuted on the host, and every core gives the bits of `from_knn` on the permuted arrays.  The handle's rows
         are the PERMUTED ones: `maxmin_order` (n int32, 1-based) says which of the caller's rows stands where, `to_maxmin`
         carries per-row arrays of the caller (B of whiten_core, iiderrors, W) into the handle's order and `from_maxmin_order`
-        carries per-row outputs (whitened columns, simulated fields) back."""
+        carries per-row outputs (whitened columns, simulated fields) back.  `from_maxmin_groups` is the grouped form."""
+        return cls._from_maxmin(cls.from_knn, locs, x_covariates, z, smooth_limits, m, device=device)
+
+    @classmethod
+    def from_maxmin_groups(cls, locs, x_covariates, z, smooth_limits, m, max_rows=64, max_rounds=0, device=-1):
+        """`from_maxmin` with `from_groups_knn` in the place of `from_knn`: the order, the search, the round rule, the plan
+        and the expanded table all on the device; the rows are the permuted ones, as `from_maxmin`'s are.  (A method of its
+        own: `from_maxmin`'s argument list is part of the layer's contract.)"""
+        return cls._from_maxmin(cls.from_groups_knn, locs, x_covariates, z, smooth_limits, m, max_rows=max_rows,
+                                max_rounds=max_rounds, device=device)
+
+    @classmethod
+    def _from_maxmin(cls, make, locs, x_covariates, z, smooth_limits, m, device=-1, **more):
         locs = _f(locs)
         order = vecchia_order_device(locs, device=max(int(device), 0))
         o = order.astype(np.int64) - 1
         X = _f(x_covariates)
         z = np.asarray(z, dtype=np.float64).reshape(locs.shape[0], -1)
-        self = cls.from_knn(locs[o], X[o], z[o], smooth_limits, m, device=device)
+        self = make(locs[o], X[o], z[o], smooth_limits, m, device=device, **more)
         self.maxmin_order = order
         return self
 
@@ -1629,6 +1683,15 @@ class CoconsVecchiaFit(_Handle):
         out = (ctypes.c_longlong * 5)()
         _lib.check(self._L.cocons_vecchia_groups_info(self._h, out), "cocons_vecchia_groups_info")
         return {"blocks": int(out[0]), "maxrows": int(out[1]), "rows": int(out[2]), "pairs": int(out[3]), "bytes": int(out[4])}
+
+    def groups_export(self, table=True):
+        """(block, nn): the 0-based block of every row in the plan's numbering and, with `table`, the handle's table (n x m
+        int32 in Fortran order, 1-based, ascending, 0 = none) -- cocons_vecchia_groups_export"""
+        block = np.zeros(self.n, dtype=np.int32)
+        nn = np.zeros((self.n, self.info()["m"]), dtype=np.int32, order="F") if table else None
+        _lib.check(self._L.cocons_vecchia_groups_export(self._h, _ip(block), None if nn is None else _ip(nn)),
+                   "cocons_vecchia_groups_export")
+        return (block, nn) if table else block
 
     def to_maxmin(self, rows):
         """A per-row array in the caller's order (n or n x c) in the handle's order (`from_maxmin`)"""

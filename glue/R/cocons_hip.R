@@ -661,6 +661,35 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
   list(group = res[[1]], info = res[[2]])
 }
 
+# the ROUND rule's groups of the table (DESIGN.md 4ac): every round each block proposes the neighbouring block whose merge saves
+# the most, and the proposals that are the best of both their blocks are merged; a function of the rows' neighbour sets, not the
+# greedy partition.  list(group, info = c(.cocons.hip.vecchia.group's four, the rounds that merged something)); max_rounds = 0:
+# at most 256 rounds.  .cocons.hip.vecchia.group.rounds runs on the host, .cocons.hip.vecchia.group.device on the device -- the
+# same integers
+.cocons.hip.vecchia.group.rounds <- function(nn, max_rows = 64L, max_rounds = 0L) {
+  res <- .Call(`_cocons_hip_vecchia_group_rounds`, as.matrix(nn), as.integer(max_rows), as.integer(max_rounds))
+  list(group = res[[1]], info = res[[2]])
+}
+
+.cocons.hip.vecchia.group.device <- function(nn, max_rows = 64L, max_rounds = 0L, device = 0L) {
+  res <- .Call(`_cocons_hip_vecchia_group_device`, as.matrix(nn), as.integer(max_rows), as.integer(max_rounds), as.integer(device))
+  list(group = res[[1]], info = res[[2]])
+}
+
+# the grouped fit made on the device: the search of .cocons.hip.vecchia.create.knn, the round rule, the plan and the expanded
+# table, none of which comes to the host -- the fit of .cocons.hip.vecchia.neighbours, .group.rounds, .group.table, .create and
+# .set.groups on the same data, to the bit.  .cocons.hip.vecchia.groups.export reads list(group, nn) back from any fit with a plan
+.cocons.hip.vecchia.create.grouped.knn <- function(locs, x_covariates, z, smooth.limits, m, max_rows = 64L, max_rounds = 0L,
+                                                   device = -1L) {
+  .Call(`_cocons_hip_vecchia_create_grouped_knn`, as.matrix(locs), as.matrix(x_covariates), as.matrix(z), as.double(smooth.limits),
+        as.integer(device), as.integer(m), as.integer(max_rows), as.integer(max_rounds))
+}
+
+.cocons.hip.vecchia.groups.export <- function(fit) {
+  res <- .Call(`_cocons_hip_vecchia_groups_export`, fit)
+  list(group = res[[1]], nn = res[[2]])
+}
+
 # the expanded table of ANY partition of nn's rows (labels in 0 .. n - 1): an integer matrix, 1-based, ascending, 0 = none
 .cocons.hip.vecchia.group.table <- function(nn, group) {
   .Call(`_cocons_hip_vecchia_group_table`, as.matrix(nn), as.integer(group))

@@ -384,6 +384,26 @@ SEXP _cocons_hip_vecchia_create_knn(SEXP locs, SEXP X, SEXP z, SEXP smooth_limit
     return ptr;
 }
 
+/* the grouped Vecchia handle made on the device (cocons_fit_create_vecchia_grouped_knn): the search of
+ * _cocons_hip_vecchia_create_knn, the round rule, the plan and the expanded table; nothing of them comes to the host */
+SEXP _cocons_hip_vecchia_create_grouped_knn(SEXP locs, SEXP X, SEXP z, SEXP smooth_limits, SEXP device, SEXP m, SEXP max_rows,
+                                            SEXP max_rounds)
+{
+    const int n = Rf_nrows(X), p = Rf_ncols(X);
+    const int r = Rf_isMatrix(z) ? Rf_ncols(z) : 1;
+    if (Rf_nrows(locs) != n || Rf_ncols(locs) != 2) Rf_error("locs must be n x 2");
+    cocons_fit *f = cocons_fit_create_vecchia_grouped_knn(n, p, r, REAL(locs), REAL(X), REAL(z), REAL(smooth_limits),
+                                                          Rf_asInteger(device), Rf_asInteger(m), Rf_asInteger(max_rows),
+                                                          Rf_asInteger(max_rounds));
+    if (!f) Rf_error("%s", cocons_last_error());
+    SEXP tag = PROTECT(Rf_allocVector(INTSXP, 4));
+    INTEGER(tag)[0] = n; INTEGER(tag)[1] = p; INTEGER(tag)[2] = r; INTEGER(tag)[3] = 0;
+    SEXP ptr = PROTECT(R_MakeExternalPtr(f, tag, R_NilValue));
+    R_RegisterCFinalizerEx(ptr, fit_finalizer, TRUE);
+    UNPROTECT(2);
+    return ptr;
+}
+
 SEXP _cocons_hip_fit_close(SEXP ptr)
 {
     fit_finalizer(ptr);
@@ -1245,6 +1265,42 @@ SEXP _cocons_hip_vecchia_group(SEXP nn, SEXP max_rows)
     return out;
 }
 
+/* the ROUND rule's groups of nn: cocons_vecchia_group_rounds on the host, or with on_device
+ * cocons_vecchia_group_device; list(group, info = c(_cocons_hip_vecchia_group's four, the rounds that merged something)) */
+static SEXP vecchia_group_rounds(SEXP nn, SEXP max_rows, SEXP max_rounds, int on_device, int device)
+{
+    if (!Rf_isMatrix(nn) || Rf_nrows(nn) < 1) Rf_error("nn must be a matrix with one row per observation");
+    const int n = Rf_nrows(nn);
+    R_xlen_t len = 0;
+    const int *tab = as_int_copy(nn, &len);
+    long long o5[5] = {0, 0, 0, 0, 0};
+    SEXP group = PROTECT(Rf_allocVector(INTSXP, n));
+    for (int i = 0; i < n; ++i) INTEGER(group)[i] = 0;
+    if (on_device)
+        hip_check(cocons_vecchia_group_device(n, Rf_ncols(nn), tab, Rf_asInteger(max_rows), Rf_asInteger(max_rounds), device,
+                                              INTEGER(group), o5), "Vecchia groups (rounds, device)");
+    else
+        hip_check(cocons_vecchia_group_rounds(n, Rf_ncols(nn), tab, Rf_asInteger(max_rows), Rf_asInteger(max_rounds),
+                                              INTEGER(group), o5), "Vecchia groups (rounds)");
+    SEXP info = PROTECT(Rf_allocVector(REALSXP, 5));
+    for (int i = 0; i < 5; ++i) REAL(info)[i] = (double)o5[i];
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 2));
+    SET_VECTOR_ELT(out, 0, group);
+    SET_VECTOR_ELT(out, 1, info);
+    UNPROTECT(3);
+    return out;
+}
+
+SEXP _cocons_hip_vecchia_group_rounds(SEXP nn, SEXP max_rows, SEXP max_rounds)
+{
+    return vecchia_group_rounds(nn, max_rows, max_rounds, 0, 0);
+}
+
+SEXP _cocons_hip_vecchia_group_device(SEXP nn, SEXP max_rows, SEXP max_rounds, SEXP device)
+{
+    return vecchia_group_rounds(nn, max_rows, max_rounds, 1, Rf_asInteger(device));
+}
+
 /* the expanded table of any partition of nn's rows (cocons_vecchia_group_table): group holds n integer labels in 0 .. n - 1;
  * an integer matrix of as many columns as the longest expanded row (at least one), 1-based, ascending, 0 = none */
 SEXP _cocons_hip_vecchia_group_table(SEXP nn, SEXP group)
@@ -1262,6 +1318,26 @@ SEXP _cocons_hip_vecchia_group_table(SEXP nn, SEXP group)
     hip_check(cocons_vecchia_group_table(n, Rf_ncols(nn), tab, INTEGER(group), longest, INTEGER(wide)), "Vecchia group table");
     UNPROTECT(1);
     return wide;
+}
+
+/* the partition and the table of a handle with a plan, read back (cocons_vecchia_groups_export): list(group = n integer block
+ * ids from 0, nn = the handle's table as an integer matrix, 1-based, ascending, 0 = none) */
+SEXP _cocons_hip_vecchia_groups_export(SEXP fitp)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int n = fit_n(fitp);
+    long long o4[4] = {0, 0, 0, 0};
+    hip_check(cocons_vecchia_info(f, o4), "Vecchia info");
+    SEXP group = PROTECT(Rf_allocVector(INTSXP, n));
+    SEXP nn = PROTECT(Rf_allocMatrix(INTSXP, n, (int)o4[1]));
+    for (int i = 0; i < n; ++i) INTEGER(group)[i] = 0;
+    for (R_xlen_t e = 0; e < XLENGTH(nn); ++e) INTEGER(nn)[e] = 0;
+    hip_check(cocons_vecchia_groups_export(f, INTEGER(group), INTEGER(nn)), "Vecchia groups export");
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 2));
+    SET_VECTOR_ELT(out, 0, group);
+    SET_VECTOR_ELT(out, 1, nn);
+    UNPROTECT(3);
+    return out;
 }
 
 /* the plan of a partition on a Vecchia handle whose table is closed under it (cocons_vecchia_set_groups): c(blocks, rows of
@@ -1582,6 +1658,10 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_vecchia_cv", (DL_FUNC)&_cocons_hip_vecchia_cv, 3},
     {"_cocons_hip_vecchia_group", (DL_FUNC)&_cocons_hip_vecchia_group, 2},
     {"_cocons_hip_vecchia_group_table", (DL_FUNC)&_cocons_hip_vecchia_group_table, 2},
+    {"_cocons_hip_vecchia_group_rounds", (DL_FUNC)&_cocons_hip_vecchia_group_rounds, 3},
+    {"_cocons_hip_vecchia_create_grouped_knn", (DL_FUNC)&_cocons_hip_vecchia_create_grouped_knn, 8},
+    {"_cocons_hip_vecchia_groups_export", (DL_FUNC)&_cocons_hip_vecchia_groups_export, 1},
+    {"_cocons_hip_vecchia_group_device", (DL_FUNC)&_cocons_hip_vecchia_group_device, 4},
     {"_cocons_hip_vecchia_set_groups", (DL_FUNC)&_cocons_hip_vecchia_set_groups, 2},
     {"_cocons_hip_vecchia_neg2loglik_grouped", (DL_FUNC)&_cocons_hip_vecchia_neg2loglik_grouped, 3},
     {"_cocons_hip_vecchia_neg2loglik_grad_grouped", (DL_FUNC)&_cocons_hip_vecchia_neg2loglik_grad_grouped, 3},

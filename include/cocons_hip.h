@@ -509,6 +509,29 @@ int cocons_cv_vecchia(cocons_fit *fit, const double *theta, const double *mean, 
  * out4 (may be NULL) = {blocks, sum of |S| over the blocks, sum of |S| (|S| - 1) / 2 (the pairs the grouped schedule
  * evaluates), sum over the rows of (k + 1) k / 2 for k neighbours (the pairs of the ungrouped schedule on nn)}.             */
 int cocons_vecchia_group(int n, int m, const int *nn, int max_rows, int *group, long long *out4);
+/* The ROUND rule: another grouping of the same table, a function of the rows' neighbour SETS alone, stated in
+ * synchronous rounds so that a device can run it.  A block's id is its smallest member; at the start every row is a block.
+ * One round reads only the state at its start:
+ *   1. every live block A looks at its candidates, the blocks B != A that hold a neighbour of a member of A.  With
+ *      a = |S(A)|, b = |S(B)|, u = |S(A) u S(B)|, B is eligible when u <= max_rows and u^2 < a^2 + b^2 (the greedy rule's
+ *      test); its gain is g = a^2 + b^2 - u^2.  prop(A) is the eligible candidate of the largest gain, ties to the smaller
+ *      id, and key(A) = (8192 - g) << 32 | A.  A block without an eligible candidate proposes nothing;
+ *   2. best(X) is the smallest key(A) over the proposing blocks A with A = X or prop(A) = X;
+ *   3. the edge A -> prop(A) = B is realised when best(A) = best(B) = key(A).  Realised edges share no block; each merges its
+ *      two blocks into the smaller id.
+ * The rounds end with the first round that has no proposal, or after max_rounds rounds (>= 0; 0 means 256).  Integers only.
+ * The partition is NOT the greedy one.  A row with more than max_rows - 1 neighbours never merges; every block a merge made
+ * has |S| <= max_rows.  group[n] as cocons_vecchia_group's; out5 (may be NULL) = out4, then the rounds that merged something.
+ * cocons_vecchia_group_rounds runs the rule on the host and needs no device.  cocons_vecchia_group_device runs it on the
+ * device: one wavefront per live block proposes, 64-bit atomic minima carry the best keys, one wavefront per block merges;
+ * the same labels and rounds, integer for integer.  Its scratch, n (4 max_rows + 36) + 8 bytes beside the table's 4 n m, is
+ * memory of the call.
+ * Refused (-1, the entry's name in front, outputs untouched, before any device work): a null nn or group, a table that
+ * breaks cocons_fit_create_vecchia's rules, max_rows outside 2 .. 64, max_rounds < 0; cocons_vecchia_group_device also a
+ * device that does not exist.                                                                                               */
+int cocons_vecchia_group_rounds(int n, int m, const int *nn, int max_rows, int max_rounds, int *group, long long *out5);
+int cocons_vecchia_group_device(int n, int m, const int *nn, int max_rows, int max_rounds, int device, int *group,
+                                long long *out5);
 /* The expanded table of ANY partition `group` (labels in 0 .. n - 1) of nn's rows: nn_out is n x m_out column-major, 1-based,
  * ascending, zero padded.  m_out = 0 with nn_out = NULL asks for the longest expanded row alone, which is returned (>= 0);
  * otherwise 0.  Refused (-1, the entry's name in front): a table that breaks the rules, a block with |S| > 64 (its smallest
@@ -527,6 +550,21 @@ int cocons_vecchia_groups_info(cocons_fit *fit, long long *out5);
  * cocons_vecchia_set_groups in one call; the other arguments as cocons_fit_create_vecchia.  NULL with cocons_last_error().  */
 cocons_fit *cocons_fit_create_vecchia_grouped(int n, int p, int r, const double *locs, const double *X, const double *z,
                                               const double *smooth_limits, int device, int m, const int *nn, int max_rows);
+/* The grouped handle made where it is used: the ordered neighbour search (cocons_fit_create_vecchia_knn's),
+ * the round rule, the plan and the expanded table, all on the device -- neither the searched table, nor the partition, nor
+ * the expanded table reaches the host; home come the rounds' counters and the 65 counts of blocks by size.  The handle is the
+ * one that cocons_vecchia_neighbours, cocons_vecchia_group_rounds, cocons_vecchia_group_table (at its longest row),
+ * cocons_fit_create_vecchia and cocons_vecchia_set_groups give on the same data: the same table, the same
+ * cocons_vecchia_groups_info, the same bits from every entry.  The closure check of cocons_vecchia_set_groups is satisfied by
+ * construction and not rerun.  m in 1 .. 63 is the search's; cocons_vecchia_info's m is the expanded table's.  The scratch
+ * of the rounds and of the plan is memory of the call.  NULL with cocons_last_error(); refused before any device work:
+ * max_rows outside 2 .. 64, max_rounds < 0, and what cocons_fit_create_vecchia_knn refuses.                                 */
+cocons_fit *cocons_fit_create_vecchia_grouped_knn(int n, int p, int r, const double *locs, const double *X, const double *z,
+                                                  const double *smooth_limits, int device, int m, int max_rows, int max_rounds);
+/* The partition and the table of a handle with a plan, read back: block[n] = the 0-based block of every row in the plan's
+ * numbering (by smallest member), nn (may be NULL) = the handle's table, n x m column-major with cocons_vecchia_info's m,
+ * 1-based, ascending, 0 = none.  Refused (-1): a null handle or block, a handle that is not a Vecchia handle or has no plan.  */
+int cocons_vecchia_groups_export(cocons_fit *fit, int *block /* n */, int *nn /* n x m, may be NULL */);
 /* cocons_neg2loglik_vecchia and cocons_vecchia_whiten on the grouped schedule: the same arguments, the same return codes --
  * the smallest failing 1-based row included --, outputs written on 0 only, and THE SAME BITS in value, parts, every whitened
  * value and every log d.  Refused (-1): a handle without a plan (cocons_vecchia_set_groups attaches one).                   */

@@ -63,6 +63,16 @@ int cocons_debug_knn_plan(int n, const double *locs, int level, int m, const dou
  * tools/vecchia_knn_timing.py.  0, or < 0 with the refusals of cocons_vecchia_neighbours under this entry's name.        */
 int cocons_debug_knn_phases(int n, const double *locs, int m, int device, double *ms2);
 
+/* The rounds of cocons_vecchia_group_device(n, m, nn, max_rows, max_rounds, device, ..), timed by events on the
+ * call's stream: for every round launched -- the one that finds no proposal included --, live[t] = the blocks alive at its
+ * start and ms[t] = the device milliseconds of its three launches; at most cap rounds are recorded.  The rounds run as they
+ * do there; the labels stay on the device and are dropped.  For tools/vecchia_group_device_timing.py.  Returns the number
+ * of rounds recorded (>= 1: live[0 .. return) and ms[0 .. return) are written) -- one more than the rounds that merged when the
+ * run ended by itself, exactly max_rounds when the cap ended it --, or < 0 with the refusals of cocons_vecchia_group_device
+ * under this entry's name.                                                                                                */
+int cocons_debug_group_rounds(int n, int m, const int *nn, int max_rows, int max_rounds, int device, int cap, int *live,
+                              double *ms);
+
 /* The plan of the maxmin ordering (cocons_vecchia_order) for n points (locs, n x 2 column-major), from the
  * header the kernels use: labels[i] = label(i) for i = 0 .. n - 1; geom3 = { centre x, centre y, L }; levels2 = 64 pairs
  * (l_k, e_k), k = 1 .. 64.  Host only: no HIP call.  0, or -1 with the outputs untouched on a null argument, n < 1, a
