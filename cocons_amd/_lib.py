@@ -74,6 +74,10 @@ SIGNATURES = {
     "cocons_vecchia_schedule": (c_int, [c_vp, c_int, ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_vecchia_transpose": (c_int, [c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_vecchia_whiten_t": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_dp]),
+    "cocons_vecchia_unwhiten_t": (c_int, [c_vp, c_dp, c_int, c_int, c_dp, c_dp]),
+    "cocons_vecchia_cov_mult": (c_int, [c_vp, c_dp, c_int, c_int, c_int, c_dp, c_dp]),
+    "cocons_vecchia_cov_cols": (c_int, [c_vp, c_dp, c_int, c_int, c_int, ctypes.POINTER(c_int), c_dp]),
+    "cocons_vecchia_schedule_t": (c_int, [c_vp, c_int, ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_vecchia_group": (c_int, [c_int, c_int, ctypes.POINTER(c_int), c_int, ctypes.POINTER(c_int),
                                      ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_vecchia_group_rounds": (c_int, [c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, ctypes.POINTER(c_int),
@@ -179,6 +183,8 @@ DIAG_SIGNATURES = {
     "cocons_debug_vecchia_sim_phases": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_dp]),
     "cocons_debug_vecchia_sim_phases_grouped": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_dp]),
     "cocons_debug_vecchia_transpose_phases": (c_int, [c_vp, c_dp]),
+    "cocons_debug_vecchia_solve_t_tiers": (c_int, [ctypes.POINTER(c_int)]),
+    "cocons_debug_vecchia_solve_t_phases": (c_int, [c_vp, c_dp, c_int, c_int, c_dp, c_dp, c_dp]),
     "cocons_debug_taper_selinv": (c_int, [c_vp, c_dp, c_dp, ctypes.POINTER(ctypes.c_longlong)]),
     "cocons_debug_tune": (c_int, [ctypes.c_char_p, c_int]),
     "cocons_debug_dag_replay": (c_int, [c_vp, c_dp, c_dp, c_int, c_dp]),

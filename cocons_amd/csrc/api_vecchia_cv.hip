@@ -98,6 +98,9 @@ VecchiaTArgs t_args(cocons_fit *f)
 
 }  // namespace
 
+int vecchia_t_build(cocons_fit *f, const char *who) { return t_build(f, who, nullptr); }
+VecchiaTArgs vecchia_t_args(cocons_fit *f) { return t_args(f); }
+
 extern "C" int cocons_vecchia_transpose(cocons_fit *f, int *ptr, int *rows, long long *out4)
 {
     const char *who = "cocons_vecchia_transpose";

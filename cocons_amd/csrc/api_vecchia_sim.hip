@@ -54,7 +54,7 @@ static std::vector<SimLaunch> sim_plan(const std::vector<int> &hoff, bool fuse, 
 }
 
 // The schedule of (table, n_fixed) on the handle: levels by relaxation sweeps, then the rows ordered by level.
-static int sim_schedule(cocons_fit *f, const char *who, int n_fixed)
+int vecchia_sim_schedule(cocons_fit *f, const char *who, int n_fixed)
 {
     VecchiaState *V = f->vecchia.get();
     if (!V->sim) V->sim.reset(new VecchiaSimState());
@@ -138,7 +138,7 @@ int vecchia_sim_coefs(cocons_fit *f, const char *who, const double *theta, int n
 
 // x (n x c in V->W, leading dimension n) from the columns in V->B (rows n_fixed .. n - 1, leading dimension n - n_fixed); the
 // fixed rows of x are in place
-static void sim_solve(cocons_fit *f, int n_fixed, int c)
+void vecchia_sim_solve(cocons_fit *f, int n_fixed, int c)
 {
     VecchiaState *V = f->vecchia.get();
     VecchiaSimState *S = V->sim.get();
@@ -168,13 +168,13 @@ static int sim_impl(const char *who, bool grouped, cocons_fit *f, const double *
     if (int st = vecchia_sim_coefs(f, who, theta, n_fixed, grouped)) return st;
     marks.mark(1);
     marks.mark(2);
-    if (int rc = sim_schedule(f, who, n_fixed)) return rc;
+    if (int rc = vecchia_sim_schedule(f, who, n_fixed)) return rc;
     marks.mark(3);
     HIPCHK_AT(who, upload_canon(V->B, E, rows * c, s));
     marks.mark(4);
     if (n_fixed > 0)
         launch_vecchia_sim_ends(true, f->n, f->p, n_fixed, c, f->dX, f->n, hmean, f->dz + (size_t)z_col * n, V->W, n, nullptr, 0, s);
-    sim_solve(f, n_fixed, c);
+    vecchia_sim_solve(f, n_fixed, c);
     marks.mark(5);
     // the result: x itself, or the trend added into the columns' buffer (they are used up)
     const double *res = V->W;
@@ -255,7 +255,7 @@ extern "C" int cocons_vecchia_schedule(cocons_fit *f, int n_fixed, int *levels, 
     FIT_ENTER_ANY(f);
     if (int rc = vecchia_only(f, who)) return rc;
     if (int rc = sim_check_fixed(f, who, n_fixed)) return rc;
-    if (int rc = sim_schedule(f, who, n_fixed)) return rc;
+    if (int rc = vecchia_sim_schedule(f, who, n_fixed)) return rc;
     VecchiaSimState *S = f->vecchia->sim.get();
     if (levels) {
         std::vector<int> h((size_t)f->n);

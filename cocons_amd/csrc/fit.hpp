@@ -282,6 +282,26 @@ struct VecchiaCvState {
     long long bytes() const { return (long long)((ptr.count() + rows.count()) * sizeof(int) + place.count()); }
 };
 
+// U^-T of a Vecchia fit (api_vecchia_cov.hip): the transposed level schedule of (table, n_fixed, tier threshold)
+// -- the last one asked for --, next to the forward one of VecchiaSimState, and the indices of cocons_vecchia_cov_cols.
+struct VecchiaSolveTState {
+    int n_fixed = -1, wide = -1;  // what the schedule below was made for; -1: none yet
+    DevBuf<int> level;            // n: the rows' transposed levels (0: a fixed row)
+    DevBuf<int> key;              // n: 2 level - 1 (one-wave tier) or 2 level (wide tier)
+    DevBuf<int> order;            // n - n_fixed: the rows by key
+    DevBuf<int> off;              // 2 depth + 1 offsets into order (allocated 2 n + 2: the counts are formed in it)
+    DevBuf<int> word;             // {changed, largest key}
+    DevBuf<int> idx;              // the columns' rows of one cocons_vecchia_cov_cols call
+    std::vector<int> hoff;        // off on the host: what the launches are planned from
+    int widest = 0;               // rows of the largest level
+    long long wide_rows = 0;      // rows of the wide tier
+    int depth() const { return hoff.empty() ? 0 : (int)(hoff.size() - 1) / 2; }
+    long long bytes() const
+    {
+        return (long long)((level.count() + key.count() + order.count() + off.count() + word.count() + idx.count()) * sizeof(int));
+    }
+};
+
 // Grouped blocks of a Vecchia fit (api_vecchia_group.hip): the plan of cocons_vecchia_set_groups on the device --
 // group_plan.hpp's GroupPlan --, replaced by a second call.
 struct VecchiaGroupState {
@@ -327,11 +347,14 @@ struct VecchiaState {
     std::unique_ptr<VecchiaSimState> sim;
     // cocons_vecchia_transpose, cocons_vecchia_whiten_t, cocons_cv_vecchia, made by their first call
     std::unique_ptr<VecchiaCvState> cv;
+    // cocons_vecchia_unwhiten_t, cocons_vecchia_cov_mult, cocons_vecchia_cov_cols, cocons_vecchia_schedule_t
+    std::unique_ptr<VecchiaSolveTState> solve_t;
     // cocons_vecchia_set_groups: the plan of the grouped value and whitening
     std::unique_ptr<VecchiaGroupState> grp;
     long long bytes() const
     {
-        return (knn ? knn->bytes : 0) + (sim ? sim->bytes() : 0) + (cv ? cv->bytes() : 0) + (grp ? grp->bytes() : 0) +
+        return (knn ? knn->bytes : 0) + (sim ? sim->bytes() : 0) + (cv ? cv->bytes() : 0) + (solve_t ? solve_t->bytes() : 0) +
+               (grp ? grp->bytes() : 0) +
                (long long)(nbr.count() * sizeof(int) +
                            (aos.count() + aos2.count() + B.count() + W.count() + part.count() + gsite.count() + gaos.count() +
                             grec.count() + gpart.count() + gout.count() + fdirs.count() + frec.count() + fpart.count() +
@@ -795,6 +818,14 @@ void vecchia_group_fisher_chunks(cocons_fit *f, const ModeSel &ms, int smooth_fr
 // grouped: launch_vecchia_group_coefs over the plan's blocks -- the caller has asked vecchia_need_plan -- into
 // the same records, the same bits
 int vecchia_sim_coefs(cocons_fit *f, const char *who, const double *theta, int n_fixed, bool grouped = false);
+// ... and what api_vecchia_sim.hip and api_vecchia_cv.hip offer api_vecchia_cov.hip: the forward schedule of
+// (table, n_fixed) on the handle and the forward solve of c columns -- x (n x c in V->W, leading dimension n, its fixed rows in
+// place) from the columns in V->B (rows n_fixed .. n - 1, leading dimension n - n_fixed) --, and the transposed lists on the
+// handle with the arguments the kernels take them in (the coefficients: V->sim->coef)
+int vecchia_sim_schedule(cocons_fit *f, const char *who, int n_fixed);
+void vecchia_sim_solve(cocons_fit *f, int n_fixed, int c);
+int vecchia_t_build(cocons_fit *f, const char *who);
+VecchiaTArgs vecchia_t_args(cocons_fit *f);
 // ... and what api_vecchia_sim.hip and api_vecchia_cv.hip offer api_vecchia_group.hip: the bodies of
 // cocons_vecchia_unwhiten (timed: cocons_debug_vecchia_sim_phases, ms3 required), cocons_sim_vecchia, cocons_vecchia_whiten_t
 // and cocons_cv_vecchia with the coefficient launch over observations (grouped = false) or over the plan's blocks

@@ -928,4 +928,44 @@ hipError_t launch_vecchia_cv_folds(int cls, const VecchiaTArgs &a, const int *in
                                    const int *idx, const int *off, const int *flist, const int *lab, int nfolds, double *var,
                                    double *res, size_t ldr, int *fail, hipStream_t s);
 
+// ---- U^-T of a Vecchia fit: the descending level solve over the transposed lists (vecchia_solve_t.hip) ----------
+constexpr int VECCHIA_SOLVE_T_COLS = 8;            // columns that share one reading of a list and its coefficients
+constexpr int VECCHIA_SOLVE_T_WIDE = 1024;         // a list of MORE than this many rows is summed by a workgroup, not a wavefront
+constexpr int VECCHIA_SOLVE_T_WIDE_THREADS = 1024; // that workgroup
+constexpr int VECCHIA_SOLVE_T_FUSE_ITEMS = 16;     // a level of at most this many (row, column group) items, none of them wide,
+constexpr int VECCHIA_SOLVE_T_FUSE_THREADS = 1024; // may join a fused run: one workgroup, a wavefront per item of a level
+constexpr int VECCHIA_SOLVE_T_FUSE_ROWS = 1024;    // rows (so levels too) of one fused launch at most: their lists' bounds and
+                                                   // pivots wait in LDS, and a chain-shaped table becomes many short launches
+// tlevel[i] = 1 for n_fixed <= i < n and 0 in front; then one push-form sweep: every row k >= n_fixed raises each neighbour
+// j >= n_fixed to at least tlevel[k] + 1 (integer atomicMax), *changed = 1 where something rose.  The fixed point is
+// tlevel(j) = 1 + the largest tlevel in list(j), 1 for an empty list.
+void launch_vecchia_tlevel_init(int n, int n_fixed, int *tlevel, hipStream_t s);
+void launch_vecchia_tlevel_sweep(const int *nbr, int m, int n, int n_fixed, int *tlevel, int *changed, hipStream_t s);
+// key[i] = 2 tlevel[i] - 1 where list(i) has at most `wide` rows, 2 tlevel[i] where it has more, 0 for i < n_fixed: what
+// launch_vecchia_level_count / _scatter order the rows by -- two offsets per level, the one-wave rows in front of the wide ones
+void launch_vecchia_tkey(const int *tlevel, const int *ptr, int n, int n_fixed, int wide, int *key, hipStream_t s);
+// In place, for q < c:  x[(j - row0) + q ldx] = (x[(j - row0) + q ldx] - sum_{e in list(j)} coef[rows[e] (m + 1) + place[e]]
+// x[(rows[e] - row0) + q ldx]) / coef[j (m + 1) + m].  THE SUM OF A LIST.  With T = 64 (a list of at most VECCHIA_SOLVE_T_WIDE
+// rows: one wavefront) or T = VECCHIA_SOLVE_T_WIDE_THREADS (a longer one: one workgroup): thread t adds the products of the
+// entries t, t + T, .. of the list, in ascending order, to a sum that starts at 0.0; the 64 sums of a wavefront meet in the
+// butterfly s += shfl_xor(s, d), d = 32, 16, .. 1; with T > 64 the wavefronts' sums are then added in ascending order of the
+// wavefront, starting from wavefront 0's.  The rule depends on the list's length and on nothing else: not on c, on the group
+// of VECCHIA_SOLVE_T_COLS columns a column ran in, on the launch, on the fusing or on row0.
+// off: two offsets per level into order -- level l (0-based) = its one-wave rows order[off[2 l] .. off[2 l + 1]), then its wide
+// rows order[off[2 l + 1] .. off[2 l + 2]).
+struct VecchiaSolveTArgs {
+    int m = 0;
+    const int *ptr = nullptr, *rows = nullptr;
+    const unsigned char *place = nullptr;
+    const double *coef = nullptr;
+    const int *order = nullptr, *off = nullptr;
+    double *x = nullptr; size_t ldx = 0; int row0 = 0;
+    int c = 0;
+};
+void launch_vecchia_solve_t_level(const VecchiaSolveTArgs &a, int begin, int rows, hipStream_t s);  // one-wave rows of a level
+void launch_vecchia_solve_t_wide(const VecchiaSolveTArgs &a, int begin, int rows, hipStream_t s);   // wide rows of a level
+void launch_vecchia_solve_t_fused(const VecchiaSolveTArgs &a, int lv0, int lv1, hipStream_t s);     // levels lv0 .. lv1 - 1
+// B[r + q ldb] = 1 where r + row0 == idx[q], else 0, for r < rows, q < nidx (idx: 0-based rows of the table)
+void launch_vecchia_unit_cols(const int *idx, int nidx, int rows, int row0, double *B, size_t ldb, hipStream_t s);
+
 }  // namespace cocons

@@ -1878,6 +1878,49 @@ class CoconsVecchiaFit(_Handle):
         (cocons_vecchia_whiten_t_grouped): the same bits."""
         return self._whiten_t(theta_list, W, "cocons_vecchia_whiten_t_grouped")
 
+    def unwhiten_t_core(self, theta_list, W, grouped=False):
+        """U^-T W for the columns of W (n x c, the caller's order): the inverse of `whiten_t_core` for the same theta, by the
+        descending level solve over the transposed lists (cocons_vecchia_unwhiten_t).  A column's result does
+        not depend on c.  `grouped`: the coefficients from one factorisation per block of the plan of `set_groups` -- the
+        same bits."""
+        T = theta_table(theta_list)
+        W = _f(np.asarray(W, dtype=np.float64).reshape(self.n, -1))
+        out = np.zeros(W.shape, order="F")
+        _lib.check(self._L.cocons_vecchia_unwhiten_t(self._h, _p(T), int(bool(grouped)), int(W.shape[1]), _p(W), _p(out)),
+                   "cocons_vecchia_unwhiten_t")
+        return out
+
+    def cov_mult_core(self, theta_list, B, n_fixed=0, grouped=False):
+        """U_pp^-1 U_pp^-T B for the columns of B ((n - n_fixed) x c), U_pp the block of U on the rows >= n_fixed
+        (cocons_vecchia_cov_mult).  n_fixed = 0: the Vecchia model's own covariance (U'U)^-1 times B; on a joint handle over
+        (observations, then new locations) with n_fixed = the observations: Cov(new | data) B."""
+        T = theta_table(theta_list)
+        B = _f(np.asarray(B, dtype=np.float64).reshape(max(self.n - int(n_fixed), 1), -1))
+        out = np.zeros(B.shape, order="F")
+        _lib.check(self._L.cocons_vecchia_cov_mult(self._h, _p(T), int(bool(grouped)), int(n_fixed), int(B.shape[1]), _p(B),
+                                                   _p(out)), "cocons_vecchia_cov_mult")
+        return out
+
+    def cov_cols_core(self, theta_list, idx, n_fixed=0, grouped=False):
+        """The columns `idx` (1-based rows of the handle, each > n_fixed; repeats allowed) of U_pp^-1 U_pp^-T,
+        (n - n_fixed) x len(idx): `cov_mult_core` on unit columns made on the device, to the bit (cocons_vecchia_cov_cols)."""
+        T = theta_table(theta_list)
+        idx = np.ascontiguousarray(np.asarray(idx).ravel(), dtype=np.int32)
+        out = np.zeros((max(self.n - int(n_fixed), 1), max(idx.size, 1)), order="F")
+        _lib.check(self._L.cocons_vecchia_cov_cols(self._h, _p(T), int(bool(grouped)), int(n_fixed), int(idx.size), _ip(idx),
+                                                   _p(out)), "cocons_vecchia_cov_cols")
+        return out
+
+    def schedule_t(self, n_fixed=0):
+        """The transposed level schedule of (table, n_fixed) that `unwhiten_t_core` and the covariance entries run on
+        (cocons_vecchia_schedule_t): {"levels": n int32 (0: a fixed row), "depth", "widest": rows of the largest level,
+        "launches": of one solve of one column under the current COCONS_VECCHIA_SOLVE_T_FUSE, "bytes": device bytes of the
+        schedule}"""
+        levels = np.zeros(self.n, dtype=np.int32)
+        out = (ctypes.c_longlong * 4)()
+        _lib.check(self._L.cocons_vecchia_schedule_t(self._h, int(n_fixed), _ip(levels), out), "cocons_vecchia_schedule_t")
+        return {"levels": levels, "depth": int(out[0]), "widest": int(out[1]), "launches": int(out[2]), "bytes": int(out[3])}
+
     def cv_core(self, theta_list, fold=None, stats=False, grouped=False):
         """Cross-validated predictions of the Vecchia model from Q = U'U (cocons_cv_vecchia).  `fold`: n integer labels in
         [0, nfold), every fold of at most 128 observations (None: leave-one-out).  Returns (resid n x r, var n) as
@@ -2143,3 +2186,26 @@ def cocoSim_cond_vecchia(theta_list, locs, newlocs, X_std, X_pred_std, smooth_li
 
     with _borrowed(fit, make) as f, _chol_error():
         return f.sim_core(theta_list, np.asarray(iiderrors, dtype=np.float64).reshape(mp, -1), n_fixed=n)
+
+
+def cocoPredict_vecchia_joint(theta_list, locs, newlocs, X_std, X_pred_std, smooth_limits, z, m, cov_idx=None, fit=None):
+    """Joint prediction of the Vecchia model at new locations that depend on each other: the joint handle of
+    `cocoSim_cond_vecchia` over (observations, then new locations), the observations fixed at z (its first column).  Returns
+    {"mean": the joint conditional mean, mp (`cocoSim_cond_vecchia` with zero errors, to the bit), "cov": the columns
+    `cov_idx` (1-based new locations; None: all of them) of the predictive covariance Cov(new | data) = (U_pp' U_pp)^-1,
+    mp x len(cov_idx) (cocons_vecchia_cov_cols)}.  `fit` (optional): such a joint handle, made once."""
+    X, Xp = np.asarray(X_std, dtype=np.float64), np.asarray(X_pred_std, dtype=np.float64)
+    n, mp = X.shape[0], Xp.shape[0]
+    cols = np.arange(1, mp + 1) if cov_idx is None else np.asarray(cov_idx).ravel().astype(np.int64)
+    if cols.size < 1 or cols.min() < 1 or cols.max() > mp:
+        raise ValueError("cocoPredict_vecchia_joint: cov_idx must name new locations 1 .. %d" % mp)
+
+    def make():
+        zz = np.asarray(z, dtype=np.float64).reshape(n, -1)
+        return CoconsVecchiaFit.from_knn(np.vstack([np.asarray(locs, dtype=np.float64), np.asarray(newlocs, dtype=np.float64)]),
+                                         np.vstack([X, Xp]), np.vstack([zz, np.zeros((mp, zz.shape[1]))]), smooth_limits, m)
+
+    with _borrowed(fit, make) as f, _chol_error():
+        mean = f.sim_core(theta_list, np.zeros((mp, 1)), n_fixed=n)[:, 0]
+        cov = f.cov_cols_core(theta_list, cols + n, n_fixed=n)
+    return {"mean": mean, "cov": cov}

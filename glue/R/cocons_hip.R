@@ -646,6 +646,43 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
   list(out = res[[2]][[1]], qdiag = res[[2]][[2]])
 }
 
+# U^-T on a Vecchia handle and the model's own covariance through it (DESIGN.md 4ad; GpGp's L_t_mult).  `grouped`: the rows'
+# coefficients from one factorisation per block of the handle's plan (.cocons.hip.vecchia.set.groups) -- the same bits.
+# .cocons.hip.vecchia.unwhiten.t: U^-T W for the n x c matrix W, the inverse of .cocons.hip.vecchia.whiten.t
+.cocons.hip.vecchia.unwhiten.t <- function(fit, theta_list, W, grouped = FALSE) {
+  W <- as.matrix(W)
+  storage.mode(W) <- "double"
+  res <- .Call(`_cocons_hip_vecchia_unwhiten_t`, fit, theta_list[names(theta_list) != "mean"], W, as.integer(grouped))
+  if (res[[1]] > 0L) stop("Cholesky error")
+  res[[2]]
+}
+
+# .cocons.hip.vecchia.cov.mult: (U_pp' U_pp)^-1 B for the (n - n_fixed) x c matrix B.  n_fixed = 0: the covariance of the
+# Vecchia model times B; on a handle over rbind(locs, newlocs) with n_fixed = nrow(locs): Cov(new | data) B
+.cocons.hip.vecchia.cov.mult <- function(fit, theta_list, B, n_fixed = 0L, grouped = FALSE) {
+  B <- as.matrix(B)
+  storage.mode(B) <- "double"
+  res <- .Call(`_cocons_hip_vecchia_cov_mult`, fit, theta_list[names(theta_list) != "mean"], B, as.integer(n_fixed),
+               as.integer(grouped))
+  if (res[[1]] > 0L) stop("Cholesky error")
+  res[[2]]
+}
+
+# .cocons.hip.vecchia.cov.cols: the columns idx (rows of the handle, each > n_fixed; repeats allowed) of that covariance
+.cocons.hip.vecchia.cov.cols <- function(fit, theta_list, idx, n_fixed = 0L, grouped = FALSE) {
+  res <- .Call(`_cocons_hip_vecchia_cov_cols`, fit, theta_list[names(theta_list) != "mean"], as.integer(idx),
+               as.integer(n_fixed), as.integer(grouped))
+  if (res[[1]] > 0L) stop("Cholesky error")
+  res[[2]]
+}
+
+# .cocons.hip.vecchia.schedule.t: list(levels, info = c(depth, rows of the widest level, launches of one solve, device bytes))
+# of the transposed schedule the three entries above run on
+.cocons.hip.vecchia.schedule.t <- function(fit, n_fixed = 0L) {
+  res <- .Call(`_cocons_hip_vecchia_schedule_t`, fit, as.integer(n_fixed))
+  list(levels = res[[1]], info = res[[2]])
+}
+
 # Grouped Vecchia blocks (DESIGN.md 4y; Guinness 2018, GpGp's group_obs): rows with overlapping neighbour sets share one block,
 # which is assembled and factored once.  Every member then conditions on a superset of its own neighbours: the grouped model is
 # the Vecchia model of the EXPANDED table, and the grouped entries return the bits of the ungrouped ones on that table's handle.

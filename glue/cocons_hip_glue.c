@@ -1190,6 +1190,88 @@ SEXP _cocons_hip_vecchia_schedule(SEXP fitp, SEXP n_fixed)
     return out;
 }
 
+/* U^-T on a Vecchia handle.  All take `grouped` (0 / 1: the coefficients from one factorisation per block of
+ * the handle's plan) and theta without `mean`, and return list(status, value).
+ * _cocons_hip_vecchia_unwhiten_t (cocons_vecchia_unwhiten_t): W is n x c; the n x c result U^-T W */
+SEXP _cocons_hip_vecchia_unwhiten_t(SEXP fitp, SEXP theta, SEXP W, SEXP grouped)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), n = fit_n(fitp);
+    if (!Rf_isReal(W) || !Rf_isMatrix(W) || Rf_nrows(W) != n) Rf_error("W must be a double matrix with %d rows", n);
+    const int c = Rf_ncols(W);
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    SEXP v = PROTECT(Rf_allocMatrix(REALSXP, n, c));
+    for (R_xlen_t e = 0; e < XLENGTH(v); ++e) REAL(v)[e] = NA_REAL;
+    int rc = cocons_vecchia_unwhiten_t(f, T, Rf_asInteger(grouped), c, REAL(W), REAL(v));
+    hip_check(rc, "Vecchia covariance (unwhiten_t)");
+    SEXP out = status_value(rc, v);
+    UNPROTECT(1);
+    return out;
+}
+
+/* _cocons_hip_vecchia_cov_mult (cocons_vecchia_cov_mult): B is (n - n_fixed) x c; the result of the same shape */
+SEXP _cocons_hip_vecchia_cov_mult(SEXP fitp, SEXP theta, SEXP B, SEXP n_fixed, SEXP grouped)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), n = fit_n(fitp), nf = Rf_asInteger(n_fixed);
+    if (nf < 0 || nf >= n) Rf_error("cocons_vecchia_cov_mult: n_fixed = %d is outside 0 .. %d", nf, n - 1);
+    if (!Rf_isReal(B) || !Rf_isMatrix(B) || Rf_nrows(B) != n - nf) Rf_error("B must be a double matrix with %d rows", n - nf);
+    const int c = Rf_ncols(B);
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    SEXP v = PROTECT(Rf_allocMatrix(REALSXP, n - nf, c));
+    for (R_xlen_t e = 0; e < XLENGTH(v); ++e) REAL(v)[e] = NA_REAL;
+    int rc = cocons_vecchia_cov_mult(f, T, Rf_asInteger(grouped), nf, c, REAL(B), REAL(v));
+    hip_check(rc, "Vecchia covariance (cov_mult)");
+    SEXP out = status_value(rc, v);
+    UNPROTECT(1);
+    return out;
+}
+
+/* _cocons_hip_vecchia_cov_cols (cocons_vecchia_cov_cols): idx the 1-based rows, each in n_fixed + 1 .. n; the
+ * (n - n_fixed) x length(idx) columns */
+SEXP _cocons_hip_vecchia_cov_cols(SEXP fitp, SEXP theta, SEXP idx, SEXP n_fixed, SEXP grouped)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int p = fit_p(fitp), n = fit_n(fitp), nf = Rf_asInteger(n_fixed);
+    if (nf < 0 || nf >= n) Rf_error("cocons_vecchia_cov_cols: n_fixed = %d is outside 0 .. %d", nf, n - 1);
+    if (!Rf_isInteger(idx) || XLENGTH(idx) < 1) Rf_error("idx must be an integer vector of at least one row");
+    const int nidx = (int)XLENGTH(idx);
+    for (int q = 0; q < nidx; ++q)
+        if (INTEGER(idx)[q] <= nf || INTEGER(idx)[q] > n)
+            Rf_error("cocons_vecchia_cov_cols: idx[%d] = %d is outside %d .. %d", q + 1, INTEGER(idx)[q], nf + 1, n);
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    SEXP v = PROTECT(Rf_allocMatrix(REALSXP, n - nf, nidx));
+    for (R_xlen_t e = 0; e < XLENGTH(v); ++e) REAL(v)[e] = NA_REAL;
+    int rc = cocons_vecchia_cov_cols(f, T, Rf_asInteger(grouped), nf, nidx, INTEGER(idx), REAL(v));
+    hip_check(rc, "Vecchia covariance (cov_cols)");
+    SEXP out = status_value(rc, v);
+    UNPROTECT(1);
+    return out;
+}
+
+/* the transposed level schedule of (table, n_fixed) (cocons_vecchia_schedule_t): list(levels = n integers, info = c(depth,
+ * rows of the largest level, launches of one solve of one column, device bytes)) */
+SEXP _cocons_hip_vecchia_schedule_t(SEXP fitp, SEXP n_fixed)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int n = fit_n(fitp), nf = Rf_asInteger(n_fixed);
+    if (nf < 0 || nf >= n) Rf_error("cocons_vecchia_schedule_t: n_fixed = %d is outside 0 .. %d", nf, n - 1);
+    long long o4[4] = {0, 0, 0, 0};
+    SEXP lv = PROTECT(Rf_allocVector(INTSXP, n));
+    for (int i = 0; i < n; ++i) INTEGER(lv)[i] = 0;
+    hip_check(cocons_vecchia_schedule_t(f, nf, INTEGER(lv), o4), "Vecchia transposed schedule");
+    SEXP info = PROTECT(Rf_allocVector(REALSXP, 4));
+    for (int i = 0; i < 4; ++i) REAL(info)[i] = (double)o4[i];
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, 2));
+    SET_VECTOR_ELT(out, 0, lv);
+    SET_VECTOR_ELT(out, 1, info);
+    UNPROTECT(3);
+    return out;
+}
+
 /* the transposed lists of a Vecchia handle's table (cocons_vecchia_transpose): list(ptr = n + 1 integers, 0-based offsets,
  * rows = the 1-based rows that name column j at rows[ptr[j] + 1 .. ptr[j + 1]], ascending, info = c(entries, longest list,
  * device bytes of the lists, columns nobody names)) */
@@ -1666,6 +1748,10 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_vecchia_neg2loglik_grouped", (DL_FUNC)&_cocons_hip_vecchia_neg2loglik_grouped, 3},
     {"_cocons_hip_vecchia_neg2loglik_grad_grouped", (DL_FUNC)&_cocons_hip_vecchia_neg2loglik_grad_grouped, 3},
     {"_cocons_hip_vecchia_fisher_grouped", (DL_FUNC)&_cocons_hip_vecchia_fisher_grouped, 3},
+    {"_cocons_hip_vecchia_unwhiten_t", (DL_FUNC)&_cocons_hip_vecchia_unwhiten_t, 4},
+    {"_cocons_hip_vecchia_cov_mult", (DL_FUNC)&_cocons_hip_vecchia_cov_mult, 5},
+    {"_cocons_hip_vecchia_cov_cols", (DL_FUNC)&_cocons_hip_vecchia_cov_cols, 5},
+    {"_cocons_hip_vecchia_schedule_t", (DL_FUNC)&_cocons_hip_vecchia_schedule_t, 2},
     {"_cocons_hip_vecchia_unwhiten_grouped", (DL_FUNC)&_cocons_hip_vecchia_unwhiten_grouped, 3},
     {"_cocons_hip_vecchia_sim_grouped", (DL_FUNC)&_cocons_hip_vecchia_sim_grouped, 5},
     {"_cocons_hip_vecchia_whiten_t_grouped", (DL_FUNC)&_cocons_hip_vecchia_whiten_t_grouped, 3},

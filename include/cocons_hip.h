@@ -616,6 +616,47 @@ int cocons_vecchia_whiten_t_grouped(cocons_fit *fit, const double *theta, int c,
 int cocons_cv_vecchia_grouped(cocons_fit *fit, const double *theta, const double *mean, int nfold, const int *fold,
                               double *resid /* n x r */, double *var /* n */, long long *stats4 /* may be NULL */);
 
+/* U^-T on a Vecchia handle, and the model's own covariance through it (GpGp's L_t_mult).  With the
+ * coefficients of cocons_vecchia_unwhiten, U(i, j_t) = s_t and U(i, i) = s_last(i).  For 0 <= n_fixed < n let U_pp be the
+ * block of U on the rows and columns >= n_fixed; the rows < n_fixed name nobody behind them, so Q_pp = U_pp' U_pp is the
+ * precision of the later rows given the first n_fixed.
+ *   THE TRANSPOSED SOLVE.  v = U_pp^-T w is the recursion in DESCENDING j = n - 1 .. n_fixed
+ *       v_j = (w_j - sum_{k in list(j)} U(k, j) v_k) / s_last(j),
+ * list(j) = the rows that name j (cocons_vecchia_transpose), all > j >= n_fixed: no list is clipped.  THE SUM OF A LIST is a
+ * function of the list alone.  A list of at most W = 1024 rows (cocons_debug_vecchia_solve_t_tiers) is summed by one wavefront,
+ * T = 64; a longer one by one workgroup, T = 1024.  Thread t adds the products U(k, j) v_k of the entries t, t + T, .. of the
+ * ascending list, in that order, to a sum that starts at 0.0; the 64 sums of a wavefront meet in the butterfly
+ * s += s(lane xor d), d = 32, 16, .. 1; with T = 1024 the sixteen wavefronts' sums are then added in ascending order, starting
+ * from wavefront 0's.  One rounded product, one rounded sum (no contraction); no floating-point atomics; no workgroup waits
+ * for another.
+ *   THE TRANSPOSED LEVELS.  tlevel(j) = 0 for j < n_fixed, else 1 + the largest tlevel in list(j), 1 for an empty list; made
+ * on the device (integer atomics) and kept on the handle next to cocons_vecchia_schedule's, keyed by n_fixed.  The rows are
+ * solved level by level in ascending tlevel; runs of narrow levels go as one launch unless COCONS_VECCHIA_SOLVE_T_FUSE=0.
+ * A result does not depend on the number of columns, on the group of 8 columns a column ran in, on the launches, on that
+ * switch or on n_fixed: row j >= n_fixed of U_pp^-T w has the same bits for every n_fixed <= j when w agrees on the rows >= j.
+ *   THE ENTRIES.  `grouped` = 0: the coefficients come from one wavefront per row; 1: from one factorisation per block of the
+ * handle's plan (cocons_vecchia_set_groups; refused without one) -- the same records, the same bits behind them.  These
+ * entries are new and nothing pins their argument lists, so one flag stands where the older entries have a second name.
+ * cocons_vecchia_unwhiten_t: out = U^-T W (n x c, column-major); cocons_vecchia_whiten_t inverts it.
+ * cocons_vecchia_cov_mult: out = U_pp^-1 U_pp^-T B -- one coefficient phase, the transposed solve, then
+ * cocons_vecchia_unwhiten's forward solve with the fixed rows of x at zero.  n_fixed = 0: Sigma~ B, the covariance of the
+ * Vecchia model, Sigma~ = (U'U)^-1; n_fixed > 0 on a handle over (observations, then new locations): Cov(new | data) B.
+ * cocons_vecchia_cov_cols: cocons_vecchia_cov_mult on the unit columns e_(idx[q] - n_fixed), made on the device -- its bits
+ * for those columns; an index may repeat.
+ * cocons_vecchia_schedule_t mirrors cocons_vecchia_schedule: out4 = {depth, rows of the widest level, launches of one solve
+ * of one column under the current switch, device bytes of the transposed schedule}; tlevels (may be NULL): tlevel of every row.
+ * All: 0, or the smallest failing 1-based row that is not fixed (> 0: nothing written, no solve launched), or < 0 with a
+ * message that starts with the entry's name; outputs are written on 0 only.  Refused (-1) before any device work: a null
+ * argument, c or nidx < 1, grouped outside 0 / 1, n_fixed outside 0 .. n - 1, an index outside n_fixed + 1 .. n, a handle that
+ * is not a Vecchia handle, grouped = 1 without a plan.  No other entry returns other bits before or after these calls.     */
+int cocons_vecchia_unwhiten_t(cocons_fit *fit, const double *theta, int grouped, int c,
+                              const double *W /* n x c */, double *out /* n x c: U^-T W */);
+int cocons_vecchia_cov_mult(cocons_fit *fit, const double *theta, int grouped, int n_fixed, int c,
+                            const double *B /* (n - n_fixed) x c */, double *out /* same: U_pp^-1 U_pp^-T B */);
+int cocons_vecchia_cov_cols(cocons_fit *fit, const double *theta, int grouped, int n_fixed, int nidx,
+                            const int *idx /* 1-based rows, each > n_fixed */, double *out /* (n - n_fixed) x nidx */);
+int cocons_vecchia_schedule_t(cocons_fit *fit, int n_fixed, int *tlevels /* n, may be NULL */, long long *out4);
+
 /* ---- fit handle: everything that is constant over an optimisation -------------
  * Created once per cocoOptim / getHessian call from the arguments the reference
  * passes unchanged to every GetNeg2loglikelihood* evaluation

@@ -106,6 +106,19 @@ int cocons_debug_vecchia_sim_phases_grouped(struct cocons_fit *fit, const double
  * sorts and the places }, device milliseconds.  For tools/vecchia_cv_timing.py.                                          */
 int cocons_debug_vecchia_transpose_phases(struct cocons_fit *fit, double *ms4);
 
+/* The tiers of the transposed Vecchia solve (cocons_vecchia_unwhiten_t), from the header the kernels use:
+ * out4 = { VECCHIA_SOLVE_T_WIDE: a list of MORE than this many rows is summed by one workgroup, a shorter one by one
+ * wavefront; the threads of that workgroup; the columns of a column group; the (row, column group) items a level may have to
+ * join a fused run }.  Host only: no HIP call.  0, or -1 on a null argument.                                              */
+int cocons_debug_vecchia_solve_t_tiers(int *out4);
+/* cocons_vecchia_unwhiten_t(fit, theta, grouped, c, W, out) with its three phases timed by events on the handle's stream:
+ * ms3 = { the records and the coefficient launch with the status word's way home, the transposed schedule (0 when the handle
+ * holds it already), the launches of the transposed solve }, device milliseconds.  For tools/vecchia_cov_timing.py, which also
+ * moves the tier threshold for a measurement with COCONS_VECCHIA_SOLVE_T_WIDE=<rows> (read when a schedule is made).  Returns
+ * and refusals as cocons_vecchia_unwhiten_t's, under this entry's name.                                                   */
+int cocons_debug_vecchia_solve_t_phases(struct cocons_fit *fit, const double *theta, int grouped, int c, const double *W,
+                                        double *out, double *ms3);
+
 /* Diagnostics of cocons_neg2loglik_grad_taper: (S(theta)^-1)_ij at every stored entry of the pattern the taper handle was
  * created with, in the caller's CSR order (out_nnz: one double per entry of that pattern), by the gradient's selected
  * inverse; bytes_out (may be NULL): the device bytes the gradient holds on the handle.  0, a failing minor k > 0, or < 0. */
