@@ -1,8 +1,9 @@
 // api_vecchia.hip -- C ABI of the Vecchia approximation: the third kind of handle -- data, a neighbour table and
 // O(n (m + 16)) bytes of scratch, never an n x n buffer -- and the entries on it: the -2 log-likelihood, its analytic gradient
 // (DESIGN.md 4s), its expected information, the whitening of given columns, and local kriging.  One evaluation is: the location parameters for theta (loc_params_kernel, then their
-// transpose to one record per location), the right-hand sides, ONE launch of vecchia_block_kernel with a wavefront per
-// observation, and -- for the value -- the totals as a tree of fixed shape.  Nothing here factors through api.hip.
+// transpose to one record per location), the right-hand sides, ONE launch of a block kernel of vecchia.hip with a wavefront per
+// observation -- or, grouped, of vecchia_group.hip with a workgroup per block of the plan --, and -- for the value -- the totals
+// as a tree of fixed shape.  Nothing here factors through api.hip.
 #include "fit.hpp"
 
 int vecchia_refuse(const char *who)
@@ -145,34 +146,74 @@ int vecchia_status(cocons_fit *f, const char *who)
     return f->hinfo[0];
 }
 
-// the likelihood launch over all n observations for nb right-hand sides in V->B: log d and the whitened columns into V->W
-static void vecchia_blocks(cocons_fit *f, const ModeSel &ms, int nb)
+int vecchia_need_plan(cocons_fit *f, const char *who)
 {
-    VecchiaState *V = f->vecchia.get();
-    VecchiaArgs a;
-    a.rows = f->n; a.m = V->m; a.kb = V->m + 1; a.nbr = V->nbr; a.aosK = V->aos;
-    a.gr = ms.gr; a.nu_fixed = ms.nu_fixed;
-    a.B = V->B; a.ldb = (size_t)f->n; a.nb = nb;
-    a.logd = V->W; a.Y = V->W + f->n; a.ldy = (size_t)f->n;
-    a.fail = f->dinfo;
-    launch_vecchia_blocks(ms.mode, false, a, f->stream);
+    if (!f->vecchia->grp) return fail(-1, "%s: the handle has no plan of grouped blocks (cocons_vecchia_set_groups attaches one)", who);
+    return 0;
 }
 
-extern "C" int cocons_neg2loglik_vecchia(cocons_fit *f, const double *theta, const double *mean, double *value, double *parts)
+// what the ungrouped and the grouped launches' argument blocks share by name
+template <class Args> static void vecchia_common_args(Args &a, cocons_fit *f, const ModeSel &ms)
 {
-    const char *who = "cocons_neg2loglik_vecchia";
+    a.aosK = f->vecchia->aos; a.gr = ms.gr; a.nu_fixed = ms.nu_fixed; a.fail = f->dinfo;
+}
+
+// nb right-hand sides in V->B: log d and the whitened columns into V->W
+template <class Args> static void vecchia_rhs_args(Args &a, cocons_fit *f, int nb)
+{
+    VecchiaState *V = f->vecchia.get();
+    a.B = V->B; a.ldb = (size_t)f->n; a.nb = nb;
+    a.logd = V->W; a.Y = V->W + f->n; a.ldy = (size_t)f->n;
+}
+
+template <class Args> static void vecchia_plan_args(Args &a, const VecchiaGroupState *G, bool by_size)
+{
+    a.kb = G->maxrows; a.off = G->off; a.rows = G->rows; a.mask = G->mask;
+    a.order = by_size ? G->order.get() : nullptr;
+}
+
+// the likelihood launch for nb right-hand sides in V->B: over all n observations, or (grouped) over the plan's blocks with one
+// factorisation per block -- the same records, right-hand sides, per-row arrays and status word, and the same bits
+static void vecchia_blocks(cocons_fit *f, bool grouped, const ModeSel &ms, int nb)
+{
+    VecchiaState *V = f->vecchia.get();
+    if (grouped) {
+        VecchiaGroupArgs a;
+        vecchia_common_args(a, f, ms);
+        vecchia_rhs_args(a, f, nb);
+        vecchia_plan_args(a, V->grp.get(), V->grp->by_size);
+        a.blocks = V->grp->blocks;
+        launch_vecchia_group_blocks(ms.mode, a, f->stream);
+    } else {
+        VecchiaArgs a;
+        vecchia_common_args(a, f, ms);
+        vecchia_rhs_args(a, f, nb);
+        a.rows = f->n; a.m = V->m; a.kb = V->m + 1; a.nbr = V->nbr;
+        launch_vecchia_blocks(ms.mode, false, a, f->stream);
+    }
+}
+
+// cocons_neg2loglik_vecchia and (grouped) cocons_neg2loglik_vecchia_grouped
+int vecchia_value_impl(const char *who, bool grouped, cocons_fit *f, const double *theta, const double *mean, double *value,
+                       double *parts)
+{
     if (!f) return fail(-1, "%s: null fit handle", who);
     if (!theta || !mean || !value) return fail(-1, "%s: null argument", who);
     FIT_ENTER_ANY(f);
     if (int rc = vecchia_only(f, who)) return rc;
+    if (grouped) if (int rc = vecchia_need_plan(f, who)) return rc;
     VecchiaState *V = f->vecchia.get();
     const int n = f->n, r = f->r;
     double hmean[COCONS_P_MAX];
     for (int i = 0; i < f->p; ++i) hmean[i] = canon_nan(mean[i]);
+    // (never shrinks: a handle's scratch holds r columns from its creation on)
+    HIPCHK_AT(who, V->B.reserve((size_t)n * r, f->stream, nullptr));
+    HIPCHK_AT(who, V->W.reserve((size_t)n * (1 + r), f->stream, nullptr));
+    HIPCHK_AT(who, V->part.reserve(vecchia_sum_scratch_doubles(n, 1 + r), f->stream, nullptr));
     if (int rc = reset_info(f)) return rc;
     const ModeSel ms = vecchia_records(f, theta, 0, V->aos);
     launch_vecchia_resid(n, f->p, f->dX, n, hmean, f->dz, n, 0, r, V->B, (size_t)n, f->stream);
-    vecchia_blocks(f, ms, r);
+    vecchia_blocks(f, grouped, ms, r);
     launch_vecchia_sums(V->W, (size_t)n, n, 1 + r, V->part, f->dout, f->stream);
     HIPCHK_AT(who, hipMemcpyAsync(f->hout, f->dout, (size_t)(1 + r) * sizeof(double), hipMemcpyDeviceToHost, f->stream));
     if (int st = vecchia_status(f, who)) return st;
@@ -181,6 +222,53 @@ extern "C" int cocons_neg2loglik_vecchia(cocons_fit *f, const double *theta, con
     if (parts) for (int k = 0; k <= r; ++k) parts[k] = f->hout[k];
     *value = total;
     return 0;
+}
+
+extern "C" int cocons_neg2loglik_vecchia(cocons_fit *f, const double *theta, const double *mean, double *value, double *parts)
+{
+    return vecchia_value_impl("cocons_neg2loglik_vecchia", false, f, theta, mean, value, parts);
+}
+
+// The gradient's or (ndir > 0) the information's launches of one evaluation: the records in chunks of `chunk` -- one per
+// observation, or (grouped) one per block of the plan, by id --, each chunk summed into its segments.
+// Grouped, one chunk: the launch deals the blocks largest first, as the value launch does; more: by id within a chunk (the
+// records stand at the blocks' ids either way, so the totals do not depend on it).
+static void vecchia_record_chunks(cocons_fit *f, bool grouped, const ModeSel &ms, int smooth_free, int nc, int ndir, int gd, int mc,
+                                  int chunk, int nseg)
+{
+    VecchiaState *V = f->vecchia.get();
+    const bool fisher = ndir > 0;
+    const int n = f->n, ncol = fisher ? vecchia_fisher_cols(ndir, f->p) : vecchia_rec_cols(f->p);
+    double *rec = fisher ? V->frec.get() : V->grec.get(), *part = fisher ? V->fpart.get() : V->gpart.get();
+    auto fill = [&](auto &a) {
+        vecchia_common_args(a, f, ms);
+        if (fisher) { a.nb = 0; a.ndir = ndir; a.gd = gd; a.dirs = V->fdirs; }          // no right-hand sides, no log d
+        else vecchia_rhs_args(a, f, nc);
+        a.aosG = V->gaos; a.smooth_free = smooth_free;
+        a.X = f->dX; a.ldx = n; a.p = f->p;
+        a.rec = rec; a.ldr = (size_t)chunk;
+    };
+    if (grouped) {
+        const VecchiaGroupState *G = V->grp.get();
+        VecchiaGroupArgs a;
+        fill(a);
+        vecchia_plan_args(a, G, G->by_size && G->blocks <= chunk);
+        a.mc = mc;
+        for (int b0 = 0; b0 < G->blocks; b0 += chunk) {
+            a.blocks = std::min(chunk, G->blocks - b0); a.blk0 = b0;
+            (fisher ? launch_vecchia_group_fisher_blocks : launch_vecchia_group_grad_blocks)(ms.mode, a, f->stream);
+            launch_vecchia_chunk_sums(rec, (size_t)chunk, a.blocks, ncol, part, b0 / VECCHIA_SUM_SEG, nseg, f->stream);
+        }
+    } else {
+        VecchiaArgs a;
+        fill(a);
+        a.m = V->m; a.kb = V->m + 1; a.nbr = V->nbr;
+        for (int r0 = 0; r0 < n; r0 += chunk) {
+            a.rows = std::min(chunk, n - r0); a.obs0 = r0; a.row0 = r0;
+            (fisher ? launch_vecchia_fisher_blocks : launch_vecchia_grad_blocks)(ms.mode, a, f->stream);
+            launch_vecchia_chunk_sums(rec, (size_t)chunk, a.rows, ncol, part, r0 / VECCHIA_SUM_SEG, nseg, f->stream);
+        }
+    }
 }
 
 // Value and gradient from one launch per chunk of VECCHIA_GRAD_CHUNK observations.  The value's totals are
@@ -227,22 +315,7 @@ int vecchia_grad_impl(const char *who, bool grouped, cocons_fit *f, const double
     launch_grad_site(loc_args(n, p, f->dX, f->dlocs, V->gsite, f->npad, tv, ms.smooth_kind, f->smooth_limits), V->gsite,
                      f->npad, smooth_free, s);
     launch_vecchia_site_rec(V->gsite, f->npad, n, V->gaos, s);
-    if (grouped) vecchia_group_grad_chunks(f, ms, smooth_free, nc, chunk, nseg);
-    else {
-        VecchiaArgs a;
-        a.m = V->m; a.kb = V->m + 1; a.nbr = V->nbr; a.aosK = V->aos; a.aosG = V->gaos;
-        a.gr = ms.gr; a.nu_fixed = ms.nu_fixed; a.smooth_free = smooth_free;
-        a.B = V->B; a.ldb = (size_t)n; a.nb = nc;
-        a.logd = V->W; a.Y = V->W + n; a.ldy = (size_t)n;
-        a.X = f->dX; a.ldx = n; a.p = p;
-        a.rec = V->grec; a.ldr = (size_t)chunk;
-        a.fail = f->dinfo;
-        for (int r0 = 0; r0 < n; r0 += chunk) {
-            a.rows = std::min(chunk, n - r0); a.obs0 = r0; a.row0 = r0;
-            launch_vecchia_grad_blocks(ms.mode, a, s);
-            launch_vecchia_chunk_sums(V->grec, (size_t)chunk, a.rows, ncol, V->gpart, r0 / VECCHIA_SUM_SEG, nseg, s);
-        }
-    }
+    vecchia_record_chunks(f, grouped, ms, smooth_free, nc, 0, 0, 0, chunk, nseg);
     launch_vecchia_sums(V->W, (size_t)n, n, 1 + nc, V->part, V->gout, s);
     launch_vecchia_final_sums(V->gpart, nseg, ncol, V->gout + (1 + nc), s);
     std::vector<double> h((size_t)(1 + nc) + ncol);
@@ -331,22 +404,7 @@ int vecchia_fisher_impl(const char *who, bool grouped, cocons_fit *f, const doub
     launch_grad_site(loc_args(n, p, f->dX, f->dlocs, V->gsite, f->npad, tv, ms.smooth_kind, f->smooth_limits), V->gsite,
                      f->npad, smooth_free, s);
     launch_vecchia_site_rec(V->gsite, f->npad, n, V->gaos, s);
-    if (grouped) vecchia_group_fisher_chunks(f, ms, smooth_free, ndir, gd, mc, chunk, nseg);
-    else {
-        VecchiaArgs a;
-        a.m = V->m; a.kb = V->m + 1; a.nbr = V->nbr; a.aosK = V->aos; a.aosG = V->gaos;
-        a.gr = ms.gr; a.nu_fixed = ms.nu_fixed; a.smooth_free = smooth_free;
-        a.nb = 0;                                   // no right-hand sides, no log d
-        a.X = f->dX; a.ldx = n; a.p = p;
-        a.ndir = ndir; a.gd = gd; a.dirs = V->fdirs;
-        a.rec = V->frec; a.ldr = (size_t)chunk;
-        a.fail = f->dinfo;
-        for (int r0 = 0; r0 < n; r0 += chunk) {
-            a.rows = std::min(chunk, n - r0); a.obs0 = r0; a.row0 = r0;
-            launch_vecchia_fisher_blocks(ms.mode, a, s);
-            launch_vecchia_chunk_sums(V->frec, (size_t)chunk, a.rows, ncol, V->fpart, r0 / VECCHIA_SUM_SEG, nseg, s);
-        }
-    }
+    vecchia_record_chunks(f, grouped, ms, smooth_free, 0, ndir, gd, mc, chunk, nseg);
     launch_vecchia_final_sums(V->fpart, nseg, ncol, V->fout, s);
     std::vector<double> h((size_t)ncol);
     HIPCHK_AT(who, hipMemcpyAsync(h.data(), V->fout, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -367,14 +425,16 @@ extern "C" int cocons_fisher_vecchia(cocons_fit *f, const double *theta, int ndi
     return vecchia_fisher_impl("cocons_fisher_vecchia", false, f, theta, ndir, dirs, info, info_mean);
 }
 
-extern "C" int cocons_vecchia_whiten(cocons_fit *f, const double *theta, int c, const double *B, double *out, double *logd)
+// cocons_vecchia_whiten and (grouped) cocons_vecchia_whiten_grouped
+int vecchia_whiten_impl(const char *who, bool grouped, cocons_fit *f, const double *theta, int c, const double *B, double *out,
+                        double *logd)
 {
-    const char *who = "cocons_vecchia_whiten";
     if (!f) return fail(-1, "%s: null fit handle", who);
     if (!theta || !B || !out) return fail(-1, "%s: null argument", who);
     if (c < 1) return fail(-1, "%s: c = %d (at least one column expected)", who, c);
     FIT_ENTER_ANY(f);
     if (int rc = vecchia_only(f, who)) return rc;
+    if (grouped) if (int rc = vecchia_need_plan(f, who)) return rc;
     VecchiaState *V = f->vecchia.get();
     const size_t n = (size_t)f->n;
     HIPCHK_AT(who, V->B.reserve(n * c, f->stream, nullptr));
@@ -382,7 +442,7 @@ extern "C" int cocons_vecchia_whiten(cocons_fit *f, const double *theta, int c, 
     if (int rc = reset_info(f)) return rc;
     HIPCHK_AT(who, upload_canon(V->B, B, n * c, f->stream));
     const ModeSel ms = vecchia_records(f, theta, 0, V->aos);
-    vecchia_blocks(f, ms, c);
+    vecchia_blocks(f, grouped, ms, c);
     // (into staging of the call: the caller's arrays stay untouched when a block fails)
     std::vector<double> h(n * (1 + c));
     HIPCHK_AT(who, hipMemcpyAsync(h.data(), V->W, h.size() * sizeof(double), hipMemcpyDeviceToHost, f->stream));
@@ -390,6 +450,11 @@ extern "C" int cocons_vecchia_whiten(cocons_fit *f, const double *theta, int c, 
     if (logd) memcpy(logd, h.data(), n * sizeof(double));
     memcpy(out, h.data() + n, n * c * sizeof(double));
     return 0;
+}
+
+extern "C" int cocons_vecchia_whiten(cocons_fit *f, const double *theta, int c, const double *B, double *out, double *logd)
+{
+    return vecchia_whiten_impl("cocons_vecchia_whiten", false, f, theta, c, B, out, logd);
 }
 
 // cocons_vecchia_predict, or with search (cocons_vecchia_predict_knn) the same with every chunk's table found on

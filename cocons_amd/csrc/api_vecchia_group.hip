@@ -8,8 +8,9 @@
 // cross-validation with their coefficients from it; and the round rule: cocons_vecchia_group_rounds on the
 // host, cocons_vecchia_group_device over the launches of group.hip, cocons_fit_create_vecchia_grouped_knn -- search, rounds,
 // plan and expanded table on the device -- and cocons_vecchia_groups_export, the read-back.  A grouped evaluation
-// is the ungrouped one with launch_vecchia_group_blocks in the place of launch_vecchia_blocks: the same records, right-hand
-// sides, per-row arrays, totals and status word, and therefore the same bits.
+// is the ungrouped one's body (the *_impl functions of api_vecchia.hip and its siblings, grouped = true) with
+// launch_vecchia_group_blocks in the place of launch_vecchia_blocks: the same records, right-hand sides, per-row arrays, totals
+// and status word, and therefore the same bits.
 #include "fit.hpp"
 #include "group_plan.hpp"
 #include <climits>
@@ -61,76 +62,7 @@ template <class T> hipError_t to_device(DevBuf<T> &d, const std::vector<T> &h, h
     return hipMemcpyAsync(d.get(), h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s);
 }
 
-// the grouped launch over the plan's blocks for nb right-hand sides in V->B: log d and the whitened columns into V->W
-void group_blocks(cocons_fit *f, const ModeSel &ms, int nb)
-{
-    VecchiaState *V = f->vecchia.get();
-    const VecchiaGroupState *G = V->grp.get();
-    VecchiaGroupArgs a;
-    a.blocks = G->blocks; a.kb = G->maxrows;
-    a.off = G->off; a.rows = G->rows; a.order = G->by_size ? G->order.get() : nullptr; a.mask = G->mask;
-    a.aosK = V->aos; a.gr = ms.gr; a.nu_fixed = ms.nu_fixed;
-    a.B = V->B; a.ldb = (size_t)f->n; a.nb = nb;
-    a.logd = V->W; a.Y = V->W + f->n; a.ldy = (size_t)f->n;
-    a.fail = f->dinfo;
-    launch_vecchia_group_blocks(ms.mode, a, f->stream);
-}
-
 }  // namespace
-
-int vecchia_need_plan(cocons_fit *f, const char *who)
-{
-    if (!f->vecchia->grp) return fail(-1, "%s: the handle has no plan of grouped blocks (cocons_vecchia_set_groups attaches one)", who);
-    return 0;
-}
-
-// The grouped gradient's launches: the blocks by id in chunks of `chunk` records, each chunk summed into its
-// segments of blocks.  One chunk: the launch deals the blocks largest first, as the value launch does; more: by id within a
-// chunk (the records stand at the blocks' ids either way, so the totals do not depend on it).
-void vecchia_group_grad_chunks(cocons_fit *f, const ModeSel &ms, int smooth_free, int nc, int chunk, int nseg)
-{
-    VecchiaState *V = f->vecchia.get();
-    const VecchiaGroupState *G = V->grp.get();
-    const int n = f->n, ncol = vecchia_rec_cols(f->p);
-    VecchiaGroupArgs a;
-    a.kb = G->maxrows;
-    a.off = G->off; a.rows = G->rows; a.mask = G->mask;
-    a.order = (G->by_size && G->blocks <= chunk) ? G->order.get() : nullptr;
-    a.aosK = V->aos; a.aosG = V->gaos; a.gr = ms.gr; a.nu_fixed = ms.nu_fixed; a.smooth_free = smooth_free;
-    a.B = V->B; a.ldb = (size_t)n; a.nb = nc;
-    a.logd = V->W; a.Y = V->W + n; a.ldy = (size_t)n;
-    a.X = f->dX; a.ldx = n; a.p = f->p;
-    a.rec = V->grec; a.ldr = (size_t)chunk;
-    a.fail = f->dinfo;
-    for (int b0 = 0; b0 < G->blocks; b0 += chunk) {
-        a.blocks = std::min(chunk, G->blocks - b0); a.blk0 = b0;
-        launch_vecchia_group_grad_blocks(ms.mode, a, f->stream);
-        launch_vecchia_chunk_sums(V->grec, (size_t)chunk, a.blocks, ncol, V->gpart, b0 / VECCHIA_SUM_SEG, nseg, f->stream);
-    }
-}
-
-// The grouped information's launches: as vecchia_group_grad_chunks, with the information's records and scratch.
-void vecchia_group_fisher_chunks(cocons_fit *f, const ModeSel &ms, int smooth_free, int ndir, int gd, int mc, int chunk, int nseg)
-{
-    VecchiaState *V = f->vecchia.get();
-    const VecchiaGroupState *G = V->grp.get();
-    const int n = f->n, ncol = vecchia_fisher_cols(ndir, f->p);
-    VecchiaGroupArgs a;
-    a.kb = G->maxrows;
-    a.off = G->off; a.rows = G->rows; a.mask = G->mask;
-    a.order = (G->by_size && G->blocks <= chunk) ? G->order.get() : nullptr;
-    a.aosK = V->aos; a.aosG = V->gaos; a.gr = ms.gr; a.nu_fixed = ms.nu_fixed; a.smooth_free = smooth_free;
-    a.nb = 0;                                   // no right-hand sides, no log d
-    a.X = f->dX; a.ldx = n; a.p = f->p;
-    a.ndir = ndir; a.gd = gd; a.mc = mc; a.dirs = V->fdirs;
-    a.rec = V->frec; a.ldr = (size_t)chunk;
-    a.fail = f->dinfo;
-    for (int b0 = 0; b0 < G->blocks; b0 += chunk) {
-        a.blocks = std::min(chunk, G->blocks - b0); a.blk0 = b0;
-        launch_vecchia_group_fisher_blocks(ms.mode, a, f->stream);
-        launch_vecchia_chunk_sums(V->frec, (size_t)chunk, a.blocks, ncol, V->fpart, b0 / VECCHIA_SUM_SEG, nseg, f->stream);
-    }
-}
 
 extern "C" int cocons_vecchia_group(int n, int m, const int *nn, int max_rows, int *group, long long *out4)
 {
@@ -549,58 +481,12 @@ extern "C" int cocons_vecchia_groups_export(cocons_fit *f, int *block, int *nn)
 extern "C" int cocons_neg2loglik_vecchia_grouped(cocons_fit *f, const double *theta, const double *mean, double *value,
                                                  double *parts)
 {
-    const char *who = "cocons_neg2loglik_vecchia_grouped";
-    if (!f) return fail(-1, "%s: null fit handle", who);
-    if (!theta || !mean || !value) return fail(-1, "%s: null argument", who);
-    FIT_ENTER_ANY(f);
-    if (int rc = vecchia_only(f, who)) return rc;
-    if (int rc = vecchia_need_plan(f, who)) return rc;
-    VecchiaState *V = f->vecchia.get();
-    const int n = f->n, r = f->r;
-    double hmean[COCONS_P_MAX];
-    for (int i = 0; i < f->p; ++i) hmean[i] = canon_nan(mean[i]);
-    // (another entry may have left the scratch of its own column count)
-    HIPCHK_AT(who, V->B.reserve((size_t)n * r, f->stream, nullptr));
-    HIPCHK_AT(who, V->W.reserve((size_t)n * (1 + r), f->stream, nullptr));
-    HIPCHK_AT(who, V->part.reserve(vecchia_sum_scratch_doubles(n, 1 + r), f->stream, nullptr));
-    if (int rc = reset_info(f)) return rc;
-    const ModeSel ms = vecchia_records(f, theta, 0, V->aos);
-    launch_vecchia_resid(n, f->p, f->dX, n, hmean, f->dz, n, 0, r, V->B, (size_t)n, f->stream);
-    group_blocks(f, ms, r);
-    launch_vecchia_sums(V->W, (size_t)n, n, 1 + r, V->part, f->dout, f->stream);
-    HIPCHK_AT(who, hipMemcpyAsync(f->hout, f->dout, (size_t)(1 + r) * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-    if (int st = vecchia_status(f, who)) return st;
-    double total = 0.0;
-    for (int k = 0; k < r; ++k) total += n * LOG_2PI + 2 * f->hout[0] + f->hout[1 + k];
-    if (parts) for (int k = 0; k <= r; ++k) parts[k] = f->hout[k];
-    *value = total;
-    return 0;
+    return vecchia_value_impl("cocons_neg2loglik_vecchia_grouped", true, f, theta, mean, value, parts);
 }
 
 extern "C" int cocons_vecchia_whiten_grouped(cocons_fit *f, const double *theta, int c, const double *B, double *out, double *logd)
 {
-    const char *who = "cocons_vecchia_whiten_grouped";
-    if (!f) return fail(-1, "%s: null fit handle", who);
-    if (!theta || !B || !out) return fail(-1, "%s: null argument", who);
-    if (c < 1) return fail(-1, "%s: c = %d (at least one column expected)", who, c);
-    FIT_ENTER_ANY(f);
-    if (int rc = vecchia_only(f, who)) return rc;
-    if (int rc = vecchia_need_plan(f, who)) return rc;
-    VecchiaState *V = f->vecchia.get();
-    const size_t n = (size_t)f->n;
-    HIPCHK_AT(who, V->B.reserve(n * c, f->stream, nullptr));
-    HIPCHK_AT(who, V->W.reserve(n * (1 + c), f->stream, nullptr));
-    if (int rc = reset_info(f)) return rc;
-    HIPCHK_AT(who, upload_canon(V->B, B, n * c, f->stream));
-    const ModeSel ms = vecchia_records(f, theta, 0, V->aos);
-    group_blocks(f, ms, c);
-    // (into staging of the call: the caller's arrays stay untouched when a block fails)
-    std::vector<double> h(n * (1 + c));
-    HIPCHK_AT(who, hipMemcpyAsync(h.data(), V->W, h.size() * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-    if (int st = vecchia_status(f, who)) return st;
-    if (logd) memcpy(logd, h.data(), n * sizeof(double));
-    memcpy(out, h.data() + n, n * c * sizeof(double));
-    return 0;
+    return vecchia_whiten_impl("cocons_vecchia_whiten_grouped", true, f, theta, c, B, out, logd);
 }
 
 extern "C" int cocons_neg2loglik_grad_vecchia_grouped(cocons_fit *f, const double *theta, const double *mean, int c,

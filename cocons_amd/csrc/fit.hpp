@@ -800,19 +800,19 @@ int vecchia_predict_impl(const char *who, cocons_fit *f, const double *theta, co
 int vecchia_only(cocons_fit *f, const char *who);
 ModeSel vecchia_records(cocons_fit *f, const double *theta, int which, double *aos);
 int vecchia_status(cocons_fit *f, const char *who);
-// ... and what api_vecchia.hip and api_vecchia_group.hip offer each other: cocons_neg2loglik_grad_vecchia with
-// the launches over observations (grouped = false) or over the plan's blocks; the refusal of a handle without a plan; and the
-// grouped launches of one evaluation -- chunks of `chunk` blocks into V->grec, their first-stage sums into V->gpart
+// ... and what api_vecchia.hip offers api_vecchia_group.hip: the bodies of the value, the whitening,
+// the gradient and the information with the launches over observations (grouped = false) or over the plan's blocks, and the
+// refusal of a handle without a plan
+int vecchia_value_impl(const char *who, bool grouped, cocons_fit *f, const double *theta, const double *mean, double *value,
+                       double *parts);
+int vecchia_whiten_impl(const char *who, bool grouped, cocons_fit *f, const double *theta, int c, const double *B, double *out,
+                        double *logd);
 int vecchia_grad_impl(const char *who, bool grouped, cocons_fit *f, const double *theta, const double *mean, int c,
                       const double *B, double *sum_logliks, double *parts, double *grad_theta, double *grad_quad,
                       double *grad_mean);
-int vecchia_need_plan(cocons_fit *f, const char *who);
-void vecchia_group_grad_chunks(cocons_fit *f, const ModeSel &ms, int smooth_free, int nc, int chunk, int nseg);
-// both information entries of a Vecchia handle (api_vecchia.hip); grouped: the launches over the plan's blocks
-// (api_vecchia_group.hip)
 int vecchia_fisher_impl(const char *who, bool grouped, cocons_fit *f, const double *theta, int ndir, const double *dirs,
                         double *info, double *info_mean);
-void vecchia_group_fisher_chunks(cocons_fit *f, const ModeSel &ms, int smooth_free, int ndir, int gd, int mc, int chunk, int nseg);
+int vecchia_need_plan(cocons_fit *f, const char *who);
 // ... and what api_vecchia_sim.hip offers api_vecchia_cv.hip: the coefficients of the rows n_fixed .. n - 1 for
 // theta into the handle's sim->coef and the status word home: 0, the smallest failing 1-based row, or < 0
 // grouped: launch_vecchia_group_coefs over the plan's blocks -- the caller has asked vecchia_need_plan -- into

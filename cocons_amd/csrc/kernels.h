@@ -759,7 +759,7 @@ struct VecchiaArgs {
 };
 size_t vecchia_lds_bytes(int m, bool pred);
 void launch_vecchia_blocks(int mode, bool pred, const VecchiaArgs &a, hipStream_t s);
-// The gradient variant of the likelihood launch: logd and Y as there (the same code), and per observation the record of
+// The gradient launch: logd and Y as there (the value kernel's phases, vecchia_block.hpp), and per observation the record of
 // vecchia_rec_cols(p) doubles -- with q = f p + k for family f and column k of X: [q] the log-determinant's share of the
 // site sums contracted with X, [6 p + q] the quadratic forms' share, [12 p] and [12 p + 1] the two shares of the global-range
 // sum, [12 p + 2 + k] = (sum_c y_c) sum_rows s[row] X[site(row), k] (the mean gradient without its factor -2).
@@ -837,7 +837,7 @@ void launch_vecchia_group_blocks(int mode, const VecchiaGroupArgs &a, hipStream_
 // pivot that is not positive and finite at position q: atomicMin(*fail, row + 1) for the first member at a position >= q whose row
 // is >= row0 (none: no failure), nothing written for the block.  The LDS is launch_vecchia_group_blocks'.
 void launch_vecchia_group_coefs(int mode, const VecchiaGroupArgs &a, hipStream_t s);
-// The gradient variant of the grouped launch over the blocks blk0 .. blk0 + blocks - 1: logd and Y as there (the same code),
+// The gradient launch over the blocks blk0 .. blk0 + blocks - 1: logd and Y as there (the value kernel's phases),
 // and per BLOCK one record of vecchia_rec_cols(p) doubles in launch_vecchia_grad_blocks' layout -- the sum of the records
 // its members would give on the expanded table, from one evaluation of every pair of the block.  The dynamic LDS is
 // vecchia_group_grad_lds_bytes(kb): 78 144 bytes at kb = 64, above 64 KB from kb = 54 on.
@@ -852,7 +852,7 @@ size_t vecchia_group_fisher_lds_bytes(int kb, int ndir, int gd, int mc);
 void vecchia_group_fisher_shape(int kb, int ndir, int *gd, int *mc);
 void launch_vecchia_group_fisher_blocks(int mode, const VecchiaGroupArgs &a, hipStream_t s);
 
-// ---- U^-1 of a Vecchia fit: coefficients, levels and the level solve (vecchia_sim.hip) -------------------------
+// ---- U^-1 of a Vecchia fit: coefficients (vecchia.hip), levels and the level solve (vecchia_sim.hip) ------------
 constexpr int VECCHIA_SIM_FUSE_ITEMS = 256;     // a level of at most this many (row, column) pairs may join a fused run
 constexpr int VECCHIA_SIM_FUSE_THREADS = 256;   // the one workgroup of a fused run
 constexpr int VECCHIA_SIM_FUSE_LEVELS = 2048;   // levels one fused launch walks at most: a chain-shaped table becomes many

@@ -3,18 +3,13 @@
 //   vecchia_aos_kernel    : loc_params_kernel's SoA (LOCP_FIELDS x stride) transposed to one 128-byte record of 16 doubles
 //                           per location, so that gathering a neighbour's parameters costs one cache line instead of 13.
 //   vecchia_resid_kernel  : z[:, col0 ..] - X mean in rhs_rows_kernel's arithmetic, one column per realisation.
-//   vecchia_block_kernel  : ONE WAVEFRONT per observation (a workgroup of 64 lanes): the parameters of the observation and
+//   vecchia_value_kernel  : ONE WAVEFRONT per observation (a workgroup of 64 lanes): the parameters of the observation and
 //                           of its k <= 63 neighbours gathered into LDS, the (k + 1) x (k + 1) covariance block assembled with
 //                           pair_value_idx -- the dense assembly's arithmetic -- into a packed lower triangle in LDS, factored
 //                           there column by column with lane = row, and the right-hand sides carried through the forward
-//                           substitution in registers.  PRED: the last row is a prediction site (cov_rns_pred's rule) and stays
-//                           out of the factored block.
-//                           GRAD: the same gather, pair loop, factorisation and substitution, then the block's
-//                           share of the gradient: two backward solves, the pair partials contracted with the block's weights,
-//                           per-site sums in one fixed order, and one record per observation.
-//                           FISH: the same gather, pair loop, factorisation and backward solve for s, then the
-//                           block's share of the expected information: C_a s per direction from the pair partials, forward
-//                           solves against the factor that is still in LDS, and the Gram of the results as one record.
+//                           substitution in registers.  PRED: the last row is a prediction site and stays out of the factor.
+//   vecchia_grad_kernel, vecchia_fisher_kernel, vecchia_coef_kernel : the same phases (vecchia_block.hpp), then the block's
+//                           share of the gradient, of the expected information (4t), or its row of U (4v).
 //   vecchia_sum_kernel    : the totals over the per-observation terms, as a two-stage tree of fixed shape.
 //
 // Every sum of a block runs in ascending row order of the block, which the host makes the ascending order of the caller's
@@ -25,9 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "kernels.h"
-#include "matern_device.hpp"
-#include "grad_pair.hpp"
-#include "vecchia_tri.hpp"
+#include "vecchia_block.hpp"
 
 namespace cocons {
 
@@ -103,106 +96,33 @@ void launch_vecchia_resid(int n, int p, const double *X, int ldx, const double *
 }
 
 // ---------------------------------------------------------------------------
-// Dynamic LDS, sized by kb = m + 1 rows (vecchia_lds_bytes):
-//   par   LOCP_FIELDS x kb   the block's parameters as an SoA of stride kb -- what pair_value_idx reads;
-//   par2  LOCP_FIELDS x kb   PRED only: the same rows in the prediction branch's parameters, the prediction site last;
-//   tri   kb (kb + 1) / 2    the block, then its factor (the pivots stay in registers: lane r keeps C(r, r));
-//   nb    kb ints            the rows' locations.
-// GRAD (vecchia_grad_lds_bytes) keeps tri at VECCHIA_STG doubles or more -- once s and h are known the factor is dead and the
-// pair walk stages its contributions there -- and puts VECCHIA_GX x kb doubles between tri and nb:
-//   sp    GSITE_FIELDS x kb  the rows' site derivatives (grad_site_kernel's fields) as an SoA of stride kb;
-//   sv, hv  kb each          s = L^-T e_last and h = L^-T v;
-//   gs    2 GFAM x kb        the rows' site sums: the log-determinant's share per family, then the quadratic forms'.
-constexpr int VECCHIA_STG = 4 * GFAM * 64;              // a pass of 64 pairs: (ii side, jj side) x (two shares) x GFAM
-constexpr int VECCHIA_GX = GSITE_FIELDS + 2 + 2 * GFAM;
-// FISH (vecchia_fisher_lds_bytes) keeps the factor in tri and puts behind sp, sv, hv, for groups of gd <= VECCHIA_FD directions:
-//   wts   gd x GFAM x kb     the rows' site weights w_a[f][row] of the group's directions;
-//   stg   gd x 64            a pass of 64 pairs: the entry of C_a per direction (then, once, the p sums u of the mean block);
-//   gall  ndir x kb          g_a = L^-1 (C_a s) of every direction, what the Gram is formed of.
-//   (VECCHIA_FX = GSITE_FIELDS + 2 and vecchia_forward stand in vecchia_tri.hpp: the grouped launch uses them too)
+// The block kernels: ONE WAVEFRONT per observation, lane = row.  The LDS layouts stand in vecchia_block.hpp.
 
-__device__ __forceinline__ double vecchia_wave_sum(double v)
+// the row's neighbours -- ascending, the free places (-1) behind them -- and then the row itself (prediction: the prediction
+// site) into nb, behind a barrier; returns k, the number of neighbours
+__device__ __forceinline__ int vecchia_rows(const VecchiaArgs &a, int row, int lane, int *nb)
 {
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-template <int MODE, bool PRED, bool GRAD, bool FISH = false>
-__global__ void __launch_bounds__(64)
-vecchia_block_kernel(VecchiaArgs a)
-{
-    static_assert(!(PRED && (GRAD || FISH)) && !(GRAD && FISH), "the gradient and the information are the likelihood launch's");
-    constexpr bool DER = GRAD || FISH;             // the launches that gather the site derivatives and solve for s
-    extern __shared__ double vecchia_lds[];
-    const int lane = threadIdx.x, row = (DER ? a.obs0 : 0) + blockIdx.x, kb = a.kb;
-    double *par = vecchia_lds;
-    double *par2 = par + (PRED ? LOCP_FIELDS * kb : 0);
-    double *tri = par2 + LOCP_FIELDS * kb;
-    const int ntri = kb * (kb + 1) / 2;
-    double *gx = tri + ((GRAD && ntri < VECCHIA_STG) ? VECCHIA_STG : ntri);
-    int *nb = (int *)(gx + (GRAD ? VECCHIA_GX * kb : FISH ? VECCHIA_FX * kb + a.gd * (GFAM * kb + 64) + a.ndir * kb : 0));
-
-    // the row's neighbours: ascending, the free places (-1) behind them
     const int mine = lane < a.m ? a.nbr[(size_t)row * a.m + lane] : -1;
     const int k = __popcll(__ballot(mine >= 0));
-    const int nrows = k + 1;                   // the neighbours, then the observation (PRED: the prediction site)
     if (lane < k) nb[lane] = mine;
     if (lane == k) nb[lane] = row;
     __syncthreads();
-    for (int e = lane; e < nrows * VECCHIA_REC; e += 64) {
-        const int r = e / VECCHIA_REC, f = e % VECCHIA_REC;
-        if (f >= LOCP_FIELDS) continue;
-        const size_t at = (size_t)nb[r] * VECCHIA_REC + f;
-        if (!PRED) par[f * kb + r] = a.aosK[at];
-        else if (r < k) { par[f * kb + r] = a.aosK[at]; par2[f * kb + r] = a.aosC[at]; }
-        else { par[f * kb + r] = 0.0; par2[f * kb + r] = a.aosP[at]; }
-    }
-    if (DER)
-        for (int e = lane; e < nrows * VECCHIA_GSITE_REC; e += 64) {
-            const int r = e / VECCHIA_GSITE_REC, f = e % VECCHIA_GSITE_REC;
-            gx[f * kb + r] = a.aosG[(size_t)nb[r] * VECCHIA_GSITE_REC + f];
-        }
-    __syncthreads();
-    // the block: pair t = r (r - 1) / 2 + c is (r, c), r > c, evaluated with the EARLIER row on the `ii` side (the reference's
-    // orientation, which the u <= eps rule sees); PRED, last row: the prediction site on the `ii` side, exact coordinate
-    // matches give its own diagonal value (cov_rns_pred)
-    const int npairs = nrows * (nrows - 1) / 2;
-    for (int t = lane; t < npairs; t += 64) {
-        int r, c;
-        tri_pair(t, r, c);
-        double v;
-        if (PRED && r == k) v = pair_value_idx<MODE_GEOM>(par2, (size_t)kb, r, par2, (size_t)kb, c, a.gr, 0.0, true);
-        else v = pair_value_idx<MODE>(par, (size_t)kb, c, par, (size_t)kb, r, a.gr, a.nu_fixed, false);
-        tri[tri_at(r, c)] = v;
-    }
-    if (lane < nrows) tri[tri_at(lane, lane)] = par[11 * kb + lane];
-    // K = C C', right-looking, one column per step; PRED: the k neighbours' block only -- the last row then ends as C^-1 c
-    const int nf = PRED ? k : nrows;
-    const int myrow = tri_at(lane, 0);
-    double piv_mine = 1.0;
-    bool bad = false;
-    for (int j = 0; j < nf; ++j) {
-        __syncthreads();
-        const double d = tri[tri_at(j, j)];
-        if (!(d > 0.0) || !isfinite(d)) { bad = true; break; }       // (the same in every lane)
-        const double piv = sqrt(d);
-        if (lane == j) piv_mine = piv;
-        double lrj = 0.0;
-        if (lane > j && lane < nrows) { lrj = tri[myrow + j] / piv; tri[myrow + j] = lrj; }
-        __syncthreads();
-        if (lane > j && lane < nrows)
-            for (int c = j + 1; c <= lane; ++c) tri[myrow + c] -= lrj * tri[tri_at(c, j)];
-    }
-    if (bad) {
-        if (lane == 0) atomicMin(a.fail, a.row0 + (int)blockIdx.x + 1);
-        return;
-    }
-    __syncthreads();
-    // forward substitution over the neighbours' rows, VECCHIA_G right-hand sides at a time; lane k ends with
-    // b_k - sum_j C(k, j) y_j, j ascending.  GRAD: every lane j ends with the numerator of w_c[j] (the steps from j on
-    // leave it alone), so v = sum_c y_c w_c, sum_c y_c^2 and sum_c y_c are formed on the way, the columns ascending
-    const int site = lane < nrows ? nb[lane] : 0;
-    double vacc = 0.0, ysq = 0.0, ysum = 0.0;
+    return k;
+}
+
+__device__ __forceinline__ void vecchia_report(const VecchiaArgs &a, int lane, int row1)
+{
+    if (lane == 0) atomicMin(a.fail, row1);
+}
+
+// The right-hand sides through the forward substitution over the neighbours' rows, VECCHIA_G at a time; lane k ends with
+// b_k - sum_j C(k, j) y_j, j ascending, and stores Y[row, c] = that / pivot (PRED: stoch[row] = -that) and log d.
+// each(b, c0): the numerators of the columns c0 .. in every lane (lane j: of w_c[j], the steps from j on leave it alone).
+template <bool PRED, class F>
+__device__ __forceinline__ void vecchia_columns(const VecchiaArgs &a, const double *tri, const int *nb, int row, int lane, int k,
+                                                double piv_mine, F &&each)
+{
+    const int nrows = k + 1, myrow = tri_at(lane, 0), site = lane < nrows ? nb[lane] : 0;
     for (int c0 = 0; c0 < a.nb; c0 += VECCHIA_G) {
         double b[VECCHIA_G];
 #pragma unroll
@@ -217,294 +137,269 @@ vecchia_block_kernel(VecchiaArgs a)
                 else a.Y[(size_t)row + (size_t)(c0 + g) * a.ldy] = b[g] / piv_mine;
             }
         }
-        if (GRAD) {
+        each(b, c0);
+    }
+    if (!PRED && lane == k && a.logd) a.logd[row] = log(piv_mine);
+}
+
+// The value.  PRED: the last row is a prediction site (cov_rns_pred's rule) and stays out of the factored block -- K = C C' on
+// the k neighbours' rows only, the last row then ends as C^-1 c.
+template <int MODE, bool PRED>
+__global__ void __launch_bounds__(64)
+vecchia_value_kernel(VecchiaArgs a)
+{
+    extern __shared__ double vecchia_lds[];
+    const int lane = threadIdx.x, row = blockIdx.x, kb = a.kb;
+    const VecchiaValueLds L = vecchia_value_lds(kb, PRED);
+    double *par = vecchia_lds + L.par, *par2 = vecchia_lds + L.par2, *tri = vecchia_lds + L.tri;
+    int *nb = (int *)(vecchia_lds + L.nb);
+    const int k = vecchia_rows(a, row, lane, nb), nrows = k + 1;
+    double piv_mine;
+    int bad;
+    if constexpr (PRED) {
+        // the neighbours in both branches' parameters, the prediction site in its own alone
+        vecchia_gather_params<64>(par, kb, nb, k, a.aosK, lane);
+        vecchia_gather_params<64>(par2, kb, nb, k, a.aosC, lane);
+        if (lane < LOCP_FIELDS) { par[lane * kb + k] = 0.0; par2[lane * kb + k] = a.aosP[(size_t)nb[k] * VECCHIA_REC + lane]; }
+        __syncthreads();
+        vecchia_assemble<MODE, 64, true>(par, par2, tri, kb, nrows, a.gr, a.nu_fixed, lane);
+        bad = vecchia_factor(tri, nrows, k, lane, piv_mine);
+    } else
+        bad = vecchia_open_block<MODE, 64, false>(par, nullptr, tri, kb, nb, nrows, a.aosK, nullptr, a.gr, a.nu_fixed, lane, piv_mine);
+    if (bad >= 0) return vecchia_report(a, lane, a.row0 + (int)blockIdx.x + 1);
+    __syncthreads();
+    vecchia_columns<PRED>(a, tri, nb, row, lane, k, piv_mine, [](const double (&)[VECCHIA_G], int) {});
+    if (PRED && lane == k) {
+        double q = 0.0;
+        for (int j = 0; j < k; ++j) { const double v = tri[tri_at(lane, 0) + j]; q += v * v; }
+        a.quad[row] = q;
+    }
+}
+
+// The coefficients: s = C^-T e_last as one record of kb = m + 1 doubles at rec[row kb ..] -- places t < k hold
+// s_t for the neighbour at place t of the device table, places k .. m - 1 hold 0, place m holds s_last.
+template <int MODE>
+__global__ void __launch_bounds__(64)
+vecchia_coef_kernel(VecchiaArgs a)
+{
+    extern __shared__ double vecchia_lds[];
+    const int lane = threadIdx.x, row = a.obs0 + blockIdx.x, kb = a.kb;
+    const VecchiaValueLds L = vecchia_value_lds(kb, false);
+    double *par = vecchia_lds + L.par, *tri = vecchia_lds + L.tri;
+    int *nb = (int *)(vecchia_lds + L.nb);
+    const int k = vecchia_rows(a, row, lane, nb), nrows = k + 1;
+    double piv_mine;
+    if (vecchia_open_block<MODE, 64, false>(par, nullptr, tri, kb, nb, nrows, a.aosK, nullptr, a.gr, a.nu_fixed, lane, piv_mine) >= 0)
+        return vecchia_report(a, lane, row + 1);
+    __syncthreads();
+    double rs[1] = {lane == k ? 1.0 : 0.0}, s[1] = {0.0};
+    vecchia_backward<PIV_DIVIDE>(rs, s, tri, piv_mine, lane, k);
+    double *rec = a.rec + (size_t)row * kb;
+    if (lane < a.m) rec[lane] = lane < k ? s[0] : 0.0;
+    if (lane == k) rec[a.m] = s[0];
+}
+
+// The gradient: the value's phases, then the block's share of the gradient.  The block's term
+// f = nb 2 log d + sum_c y_c^2 has the derivative <W, dC> with W_log = nb s s' and W_quad = -(sum_c y_c^2) s s' - (h s' + s h'),
+// s = L^-T e_last, h = L^-T v: two backward solves, the pair partials contracted with the block's weights, per-site sums in
+// one fixed order, and one record per observation.
+template <int MODE>
+__global__ void __launch_bounds__(64)
+vecchia_grad_kernel(VecchiaArgs a)
+{
+    extern __shared__ double vecchia_lds[];
+    const int lane = threadIdx.x, row = a.obs0 + blockIdx.x, kb = a.kb;
+    const VecchiaGradLds L = vecchia_grad_lds(kb, false);
+    double *par = vecchia_lds + L.par, *tri = vecchia_lds + L.tri, *sp = vecchia_lds + L.sp, *sv = vecchia_lds + L.v1;
+    double *hv = vecchia_lds + L.v2, *gs = vecchia_lds + L.gs;
+    int *nb = (int *)(vecchia_lds + L.nb);
+    const int k = vecchia_rows(a, row, lane, nb), nrows = k + 1, npairs = nrows * (nrows - 1) / 2;
+    double piv_mine;
+    if (vecchia_open_block<MODE, 64, true>(par, sp, tri, kb, nb, nrows, a.aosK, a.aosG, a.gr, a.nu_fixed, lane, piv_mine) >= 0)
+        return vecchia_report(a, lane, a.row0 + (int)blockIdx.x + 1);
+    __syncthreads();
+    // v = sum_c y_c w_c, sum_c y_c^2 and sum_c y_c are formed on the way, the columns ascending
+    double vacc = 0.0, ysq = 0.0, ysum = 0.0;
+    vecchia_columns<false>(a, tri, nb, row, lane, k, piv_mine, [&](const double (&b)[VECCHIA_G], int c0) {
 #pragma unroll
-            for (int g = 0; g < VECCHIA_G; ++g) {
-                if (c0 + g >= a.nb) break;
-                const double w = b[g] / piv_mine;                     // lane k: the whitened value, as stored above
-                const double y = __shfl(w, k);
-                if (lane < k) vacc += y * w;
-                ysq += y * y;
-                ysum += y;
-            }
+        for (int g = 0; g < VECCHIA_G; ++g) {
+            if (c0 + g >= a.nb) break;
+            const double w = b[g] / piv_mine;                         // lane k: the whitened value, as stored
+            const double y = __shfl(w, k);
+            if (lane < k) vacc += y * w;
+            ysq += y * y;
+            ysum += y;
         }
-    }
-    if (lane == k) {
-        if (PRED) {
-            double q = 0.0;
-            for (int j = 0; j < k; ++j) { const double v = tri[myrow + j]; q += v * v; }
-            a.quad[row] = q;
-        } else if (a.logd) a.logd[row] = log(piv_mine);
-    }
-    // The block's term f = nb 2 log d + sum_c y_c^2 has the derivative <W, dC> with W_log = nb s s' and
-    // W_quad = -(sum_c y_c^2) s s' - (h s' + s h'), s = L^-T e_last, h = L^-T v.  FISH has no right-hand
-    // sides (h = 0) and uses s alone.
-    [[maybe_unused]] double *sp = gx, *sv = sp + GSITE_FIELDS * kb, *hv = sv + kb;
-    [[maybe_unused]] double s_mine = 0.0, h_mine = 0.0;
-    if constexpr (DER) {
-        // the two backward solves, one column of L' (a row of the packed factor) per step; lane j ends with component j
-        double rs = lane == k ? 1.0 : 0.0, rh = lane < k ? vacc : 0.0;
-        for (int j = k; j >= 0; --j) {
-            const double xs = __shfl(rs / piv_mine, j), xh = __shfl(rh / piv_mine, j);
-            if (lane == j) { s_mine = xs; h_mine = xh; }
-            if (lane < j) {
-                const double l = tri[tri_at(j, 0) + lane];
-                rs -= l * xs;
-                rh -= l * xh;
-            }
-        }
-        __syncthreads();                   // GRAD: the factor is dead from here on, tri is the staging of the pair walk
-        if (lane < nrows) { sv[lane] = s_mine; hv[lane] = h_mine; }
-    }
-    if constexpr (GRAD) {
-        double *gs = hv + kb;
-        const double cn = (double)a.nb;
-        auto w_log = [&](double sa, double sb) { return cn * (sa * sb); };
-        auto w_quad = [&](double sa, double ha, double sb, double hb) { return 0.0 - ysq * (sa * sb) - (ha * sb + sa * hb); };
-        // a row's site sums in registers: the diagonal first -- W_aa (exp(eta_sd), nugget) --, then its pairs pass by pass
-        double acc[2 * GFAM];
+    });
+    double rsh[2] = {lane == k ? 1.0 : 0.0, lane < k ? vacc : 0.0}, sh[2] = {0.0, 0.0};
+    vecchia_backward<PIV_DIVIDE>(rsh, sh, tri, piv_mine, lane, k);
+    const double s_mine = sh[0], h_mine = sh[1];
+    __syncthreads();                       // the factor is dead from here on, tri is the staging of the pair walk
+    if (lane < nrows) { sv[lane] = s_mine; hv[lane] = h_mine; }
+    const double cn = (double)a.nb;
+    auto w_log = [&](double sa, double sb) { return cn * (sa * sb); };
+    auto w_quad = [&](double sa, double ha, double sb, double hb) { return 0.0 - ysq * (sa * sb) - (ha * sb + sa * hb); };
+    // a row's site sums in registers: the diagonal first -- W_aa (exp(eta_sd), nugget) --, then its pairs pass by pass
+    double acc[2 * GFAM];
 #pragma unroll
-        for (int f = 0; f < 2 * GFAM; ++f) acc[f] = 0.0;
+    for (int f = 0; f < 2 * GFAM; ++f) acc[f] = 0.0;
+    if (lane < nrows) {
+        const double wl = w_log(s_mine, s_mine), wq = w_quad(s_mine, h_mine, s_mine, h_mine);
+        const double dsd = sp[3 * kb + lane], dng = par[12 * kb + lane];
+        acc[TH_SD_] = wl * dsd; acc[TH_NG_] = wl * dng;
+        acc[GFAM + TH_SD_] = wq * dsd; acc[GFAM + TH_NG_] = wq * dng;
+    }
+    __syncthreads();
+    // The pair walk: 64 pairs a pass, one per lane (the order of the assembly), each pair's partials evaluated once and
+    // weighted with 2 W_log and 2 W_quad into the staging; then lane = row a adds what the pass holds for its site by
+    // vecchia_row_pairs' rule.  A site's sum is therefore formed in one order that is a function of the block alone.
+    double *stg = tri;
+    double glob_l = 0.0, glob_q = 0.0;
+    for (int t0 = 0; t0 < npairs; t0 += 64) {
+        const int t = t0 + lane;
+        double da[GFAM], db[GFAM], dg = 0.0, w2l = 0.0, w2q = 0.0;
+#pragma unroll
+        for (int f = 0; f < GFAM; ++f) { da[f] = 0.0; db[f] = 0.0; }
+        if (t < npairs) {
+            int r, c;
+            tri_pair(t, r, c);
+            pair_partials<MODE>(par, (size_t)kb, sp, (size_t)kb, a.gr, a.nu_fixed, a.smooth_free, c, r, da, db, dg);
+            const double sa = sv[r], ha = hv[r], sb = sv[c], hb = hv[c];
+            w2l = 2.0 * w_log(sa, sb);
+            w2q = 2.0 * w_quad(sa, ha, sb, hb);
+            glob_l += w2l * dg;
+            glob_q += w2q * dg;
+        }
+#pragma unroll
+        for (int f = 0; f < GFAM; ++f) {
+            stg[(0 * GFAM + f) * 64 + lane] = w2l * da[f];
+            stg[(1 * GFAM + f) * 64 + lane] = w2q * da[f];
+            stg[(2 * GFAM + f) * 64 + lane] = w2l * db[f];
+            stg[(3 * GFAM + f) * 64 + lane] = w2q * db[f];
+        }
+        __syncthreads();
         if (lane < nrows) {
-            const double wl = w_log(s_mine, s_mine), wq = w_quad(s_mine, h_mine, s_mine, h_mine);
+            auto add = [&](int side, int slot) {
+#pragma unroll
+                for (int f = 0; f < GFAM; ++f) {
+                    acc[f] += stg[(side * GFAM + f) * 64 + slot];
+                    acc[GFAM + f] += stg[((side + 1) * GFAM + f) * 64 + slot];
+                }
+            };
+            vecchia_row_pairs(lane, t0, min(t0 + 64, npairs), [&](int slot, int) { add(2, slot); },
+                              [&](int slot, int) { add(0, slot); });
+        }
+        __syncthreads();
+    }
+    if (lane < nrows) {
+#pragma unroll
+        for (int f = 0; f < 2 * GFAM; ++f) gs[f * kb + lane] = acc[f];
+    }
+    glob_l = vecchia_wave_sum(glob_l);
+    glob_q = vecchia_wave_sum(glob_q);
+    __syncthreads();
+    // the record: the site sums contracted with X over the block's rows, ascending
+    const int p = a.p, b = blockIdx.x;
+    for (int o = lane; o < (2 * GFAM + 1) * p; o += 64) {
+        const int q = o / p, kx = o % p;
+        const double s = vecchia_dot_x(q < 2 * GFAM ? gs + q * kb : sv, nrows, nb, a.X, a.ldx, kx);
+        if (q < 2 * GFAM) a.rec[(size_t)o * a.ldr + b] = s;
+        else a.rec[(size_t)(2 * GFAM * p + 2 + kx) * a.ldr + b] = ysum * s;
+    }
+    if (lane == 0) {
+        a.rec[(size_t)(2 * GFAM * p) * a.ldr + b] = glob_l;
+        a.rec[(size_t)(2 * GFAM * p + 1) * a.ldr + b] = glob_q;
+    }
+}
+
+// The information: no right-hand sides (h = 0), s alone.  With q_a = C_a s and g_a = L^-1 q_a the block's share
+// is sum_{j < k} g_a[j] g_b[j] + g_a[k] g_b[k] / 2: C_a s per direction from the pair partials, forward solves against the
+// factor that is still in LDS, and the Gram of the results as one record.  Directions in groups of a.gd, so that the weights
+// fit the LDS.
+template <int MODE>
+__global__ void __launch_bounds__(64)
+vecchia_fisher_kernel(VecchiaArgs a)
+{
+    extern __shared__ double vecchia_lds[];
+    const int lane = threadIdx.x, row = a.obs0 + blockIdx.x, kb = a.kb;
+    const VecchiaFisherLds L = vecchia_fisher_lds(kb, a.ndir, a.gd, 1, false);
+    double *par = vecchia_lds + L.par, *tri = vecchia_lds + L.tri, *sp = vecchia_lds + L.sp, *sv = vecchia_lds + L.sv;
+    double *wts = vecchia_lds + L.wts, *stg = vecchia_lds + L.stg, *gall = vecchia_lds + L.gall;
+    int *nb = (int *)(vecchia_lds + L.nb);
+    const int k = vecchia_rows(a, row, lane, nb), nrows = k + 1, npairs = nrows * (nrows - 1) / 2;
+    double piv_mine;
+    if (vecchia_open_block<MODE, 64, true>(par, sp, tri, kb, nb, nrows, a.aosK, a.aosG, a.gr, a.nu_fixed, lane, piv_mine) >= 0)
+        return vecchia_report(a, lane, a.row0 + (int)blockIdx.x + 1);
+    __syncthreads();
+    double rs[1] = {lane == k ? 1.0 : 0.0}, s1[1] = {0.0};
+    vecchia_backward<PIV_DIVIDE>(rs, s1, tri, piv_mine, lane, k);
+    const double s_mine = s1[0];
+    if (lane < nrows) sv[lane] = s_mine;
+    const int p = a.p, ndir = a.ndir, b = blockIdx.x, myrow = tri_at(lane, 0);
+    for (int d0 = 0; d0 < ndir; d0 += a.gd) {
+        const int gd = min(a.gd, ndir - d0);
+        __syncthreads();               // sv is written; the previous group's walk has left wts and stg
+        vecchia_site_weights<64>(wts, kb, nrows, nb, a.X, a.ldx, p, a.dirs, d0, gd, lane);
+        __syncthreads();
+        // q_a[row] in registers: the diagonal first, then the row's pairs pass by pass (the gradient walk's order)
+        double qa[VECCHIA_FD];
+#pragma unroll
+        for (int d = 0; d < VECCHIA_FD; ++d) qa[d] = 0.0;
+        if (lane < nrows) {
             const double dsd = sp[3 * kb + lane], dng = par[12 * kb + lane];
-            acc[TH_SD_] = wl * dsd; acc[TH_NG_] = wl * dng;
-            acc[GFAM + TH_SD_] = wq * dsd; acc[GFAM + TH_NG_] = wq * dng;
+#pragma unroll
+            for (int d = 0; d < VECCHIA_FD; ++d)
+                if (d < gd)
+                    qa[d] = (dsd * wts[(d * GFAM + TH_SD_) * kb + lane] + dng * wts[(d * GFAM + TH_NG_) * kb + lane]) * s_mine;
         }
-        __syncthreads();
-        // The pair walk: 64 pairs a pass, one per lane (the order of the assembly above), each pair's partials evaluated once
-        // and weighted with 2 W_log and 2 W_quad into the staging; then lane = row a adds what the pass holds for its site --
-        // its pairs (a, c), c < a ascending (the jj side), then its pairs (r, a), r > a ascending (the ii side).  A site's sum
-        // is therefore formed in one order that is a function of the block alone.
-        double *stg = tri;
-        double glob_l = 0.0, glob_q = 0.0;
         for (int t0 = 0; t0 < npairs; t0 += 64) {
-            const int t = t0 + lane;
-            double da[GFAM], db[GFAM], dg = 0.0, w2l = 0.0, w2q = 0.0;
-#pragma unroll
-            for (int f = 0; f < GFAM; ++f) { da[f] = 0.0; db[f] = 0.0; }
-            if (t < npairs) {
-                int r, c;
-                tri_pair(t, r, c);
-                pair_partials<MODE>(par, (size_t)kb, sp, (size_t)kb, a.gr, a.nu_fixed, a.smooth_free, c, r, da, db, dg);
-                const double sa = sv[r], ha = hv[r], sb = sv[c], hb = hv[c];
-                w2l = 2.0 * w_log(sa, sb);
-                w2q = 2.0 * w_quad(sa, ha, sb, hb);
-                glob_l += w2l * dg;
-                glob_q += w2q * dg;
-            }
-#pragma unroll
-            for (int f = 0; f < GFAM; ++f) {
-                stg[(0 * GFAM + f) * 64 + lane] = w2l * da[f];
-                stg[(1 * GFAM + f) * 64 + lane] = w2q * da[f];
-                stg[(2 * GFAM + f) * 64 + lane] = w2l * db[f];
-                stg[(3 * GFAM + f) * 64 + lane] = w2q * db[f];
-            }
+            vecchia_stage_dir_entries<MODE, 64>(stg, wts, par, sp, kb, a.gr, a.nu_fixed, a.smooth_free, a.dirs, p, d0, gd,
+                                                t0 + lane, npairs, lane);
             __syncthreads();
             if (lane < nrows) {
-                const int tend = min(t0 + 64, npairs), mine0 = lane * (lane - 1) / 2;
-                for (int u = max(t0, mine0); u < min(tend, mine0 + lane); ++u) {
+                auto add = [&](int slot, int other) {
+                    const double so = sv[other];
 #pragma unroll
-                    for (int f = 0; f < GFAM; ++f) {
-                        acc[f] += stg[(2 * GFAM + f) * 64 + (u - t0)];
-                        acc[GFAM + f] += stg[(3 * GFAM + f) * 64 + (u - t0)];
-                    }
-                }
-                int r_lo, r_hi, c_;
-                tri_pair(t0, r_lo, c_);
-                tri_pair(tend - 1, r_hi, c_);
-                for (int r = max(r_lo, lane + 1); r <= r_hi; ++r) {
-                    const int u = r * (r - 1) / 2 + lane;
-                    if (u < t0 || u >= tend) continue;
-#pragma unroll
-                    for (int f = 0; f < GFAM; ++f) {
-                        acc[f] += stg[(0 * GFAM + f) * 64 + (u - t0)];
-                        acc[GFAM + f] += stg[(1 * GFAM + f) * 64 + (u - t0)];
-                    }
-                }
+                    for (int d = 0; d < VECCHIA_FD; ++d)
+                        if (d < gd) qa[d] += stg[d * 64 + slot] * so;
+                };
+                vecchia_row_pairs(lane, t0, min(t0 + 64, npairs), add, add);
             }
             __syncthreads();
         }
-        if (lane < nrows) {
+        // g_a = L^-1 q_a: the likelihood's substitution with q as the right-hand sides; every lane keeps its component
 #pragma unroll
-            for (int f = 0; f < 2 * GFAM; ++f) gs[f * kb + lane] = acc[f];
-        }
-        glob_l = vecchia_wave_sum(glob_l);
-        glob_q = vecchia_wave_sum(glob_q);
-        __syncthreads();
-        // the record: the site sums contracted with X over the block's rows, ascending
-        const int p = a.p, b = blockIdx.x;
-        for (int o = lane; o < (2 * GFAM + 1) * p; o += 64) {
-            const int q = o / p, kx = o % p;
-            const double *g = q < 2 * GFAM ? gs + q * kb : sv;
-            double s = 0.0;
-            for (int rr = 0; rr < nrows; ++rr) s += g[rr] * a.X[(size_t)nb[rr] + (size_t)kx * a.ldx];
-            if (q < 2 * GFAM) a.rec[(size_t)o * a.ldr + b] = s;
-            else a.rec[(size_t)(2 * GFAM * p + 2 + kx) * a.ldr + b] = ysum * s;
-        }
-        if (lane == 0) {
-            a.rec[(size_t)(2 * GFAM * p) * a.ldr + b] = glob_l;
-            a.rec[(size_t)(2 * GFAM * p + 1) * a.ldr + b] = glob_q;
+        for (int c0 = 0; c0 < VECCHIA_FD; c0 += VECCHIA_G) {
+            if (c0 >= gd) break;
+            double bb[VECCHIA_G];
+#pragma unroll
+            for (int g = 0; g < VECCHIA_G; ++g) bb[g] = qa[c0 + g];
+            vecchia_forward(bb, tri, myrow, piv_mine, lane, k, nrows);
+#pragma unroll
+            for (int g = 0; g < VECCHIA_G; ++g)
+                if (c0 + g < gd && lane < nrows) gall[(d0 + c0 + g) * kb + lane] = bb[g] / piv_mine;
         }
     }
-    if constexpr (FISH) {
-        // The block's share of the expected information: with q_a = C_a s and g_a = L^-1 q_a,
-        // sum_{j < k} g_a[j] g_b[j] + g_a[k] g_b[k] / 2.  Directions in groups of a.gd, so that the weights fit the LDS.
-        const int p = a.p, ndir = a.ndir, b = blockIdx.x;
-        double *wts = hv + kb, *stg = wts + a.gd * GFAM * kb, *gall = stg + a.gd * 64;
-        for (int d0 = 0; d0 < ndir; d0 += a.gd) {
-            const int gd = min(a.gd, ndir - d0);
-            __syncthreads();               // sv is written; the previous group's walk has left wts and stg
-            // the site weights of the group's directions: w_a[f][row] = c_f sum_k X[site(row), k] dirs[a][f, k], k ascending;
-            // scale: c = 2 over k >= 1 (k = 0 is the global range)
-            for (int e = lane; e < gd * GFAM * nrows; e += 64) {
-                const int rr = e % nrows, f = (e / nrows) % GFAM, d = e / (nrows * GFAM);
-                const double *v = a.dirs + ((size_t)(d0 + d) * GFAM + f) * p;
-                double w = 0.0;
-                for (int kx = (f == TH_SCALE_ ? 1 : 0); kx < p; ++kx) w += a.X[(size_t)nb[rr] + (size_t)kx * a.ldx] * v[kx];
-                wts[(d * GFAM + f) * kb + rr] = f == TH_SCALE_ ? 2.0 * w : w;
-            }
-            __syncthreads();
-            // q_a[row] in registers: the diagonal first, then the row's pairs pass by pass (the gradient walk's order)
-            double qa[VECCHIA_FD];
-#pragma unroll
-            for (int d = 0; d < VECCHIA_FD; ++d) qa[d] = 0.0;
-            if (lane < nrows) {
-                const double dsd = sp[3 * kb + lane], dng = par[12 * kb + lane];
-#pragma unroll
-                for (int d = 0; d < VECCHIA_FD; ++d)
-                    if (d < gd)
-                        qa[d] = (dsd * wts[(d * GFAM + TH_SD_) * kb + lane] + dng * wts[(d * GFAM + TH_NG_) * kb + lane]) * s_mine;
-            }
-            for (int t0 = 0; t0 < npairs; t0 += 64) {
-                const int t = t0 + lane;
-                double da[GFAM], db[GFAM], dg = 0.0;
-                int r = 0, c = 0;
-#pragma unroll
-                for (int f = 0; f < GFAM; ++f) { da[f] = 0.0; db[f] = 0.0; }
-                if (t < npairs) {
-                    tri_pair(t, r, c);
-                    pair_partials<MODE>(par, (size_t)kb, sp, (size_t)kb, a.gr, a.nu_fixed, a.smooth_free, c, r, da, db, dg);
-                }
-                for (int d = 0; d < gd; ++d) {
-                    double e = 0.0;
-                    if (t < npairs) {
-                        const double *w = wts + d * GFAM * kb;
-                        e = dg * a.dirs[((size_t)(d0 + d) * GFAM + TH_SCALE_) * p];
-#pragma unroll
-                        for (int f = 0; f < GFAM; ++f) {
-                            e += da[f] * w[f * kb + c];
-                            e += db[f] * w[f * kb + r];
-                        }
-                    }
-                    stg[d * 64 + lane] = e;
-                }
-                __syncthreads();
-                if (lane < nrows) {
-                    const int tend = min(t0 + 64, npairs), mine0 = lane * (lane - 1) / 2;
-                    for (int u = max(t0, mine0); u < min(tend, mine0 + lane); ++u) {
-                        const double so = sv[u - mine0];
-#pragma unroll
-                        for (int d = 0; d < VECCHIA_FD; ++d)
-                            if (d < gd) qa[d] += stg[d * 64 + (u - t0)] * so;
-                    }
-                    int r_lo, r_hi, c_;
-                    tri_pair(t0, r_lo, c_);
-                    tri_pair(tend - 1, r_hi, c_);
-                    for (int rr = max(r_lo, lane + 1); rr <= r_hi; ++rr) {
-                        const int u = rr * (rr - 1) / 2 + lane;
-                        if (u < t0 || u >= tend) continue;
-                        const double so = sv[rr];
-#pragma unroll
-                        for (int d = 0; d < VECCHIA_FD; ++d)
-                            if (d < gd) qa[d] += stg[d * 64 + (u - t0)] * so;
-                    }
-                }
-                __syncthreads();
-            }
-            // g_a = L^-1 q_a: the likelihood's substitution with q as the right-hand sides; every lane keeps its component
-#pragma unroll
-            for (int c0 = 0; c0 < VECCHIA_FD; c0 += VECCHIA_G) {
-                if (c0 >= gd) break;
-                double bb[VECCHIA_G];
-#pragma unroll
-                for (int g = 0; g < VECCHIA_G; ++g) bb[g] = qa[c0 + g];
-                vecchia_forward(bb, tri, myrow, piv_mine, lane, k, nrows);
-#pragma unroll
-                for (int g = 0; g < VECCHIA_G; ++g)
-                    if (c0 + g < gd && lane < nrows) gall[(d0 + c0 + g) * kb + lane] = bb[g] / piv_mine;
-            }
-        }
-        // u = sum_rows s[row] X[site(row), .], the rows ascending (the mean gradient's sum)
-        if (lane < p) {
-            double s = 0.0;
-            for (int rr = 0; rr < nrows; ++rr) s += sv[rr] * a.X[(size_t)nb[rr] + (size_t)lane * a.ldx];
-            stg[lane] = s;
-        }
-        __syncthreads();
-        // the record: the lower triangle of the Gram, entry o = a (a + 1) / 2 + b, then that of u u'
-        const int ng = ndir * (ndir + 1) / 2;
-        for (int o = lane; o < ng; o += 64) {
-            int ra, cb;
-            tri_pair(o, ra, cb);           // (the strict triangle's numbering of (a + 1, b))
-            const double *ga = gall + (ra - 1) * kb, *gb = gall + cb * kb;
-            double s = 0.0;
-            for (int j = 0; j < k; ++j) s += ga[j] * gb[j];
-            s += 0.5 * (ga[k] * gb[k]);
-            a.rec[(size_t)o * a.ldr + b] = s;
-        }
-        for (int o = lane; o < p * (p + 1) / 2; o += 64) {
-            int ra, cb;
-            tri_pair(o, ra, cb);
-            a.rec[(size_t)(ng + o) * a.ldr + b] = stg[ra - 1] * stg[cb];
-        }
+    // u = sum_rows s[row] X[site(row), .], the rows ascending (the mean gradient's sum)
+    if (lane < p) stg[lane] = vecchia_dot_x(sv, nrows, nb, a.X, a.ldx, lane);
+    __syncthreads();
+    // the record: the lower triangle of the Gram, entry o = a (a + 1) / 2 + b, then that of u u'
+    const int ng = ndir * (ndir + 1) / 2;
+    for (int o = lane; o < ng; o += 64) {
+        int ra, cb;
+        tri_pair(o, ra, cb);           // (the strict triangle's numbering of (a + 1, b))
+        a.rec[(size_t)o * a.ldr + b] = vecchia_gram_add(0.0, gall + (ra - 1) * kb, gall + cb * kb, k);
+    }
+    for (int o = lane; o < p * (p + 1) / 2; o += 64) {
+        int ra, cb;
+        tri_pair(o, ra, cb);
+        a.rec[(size_t)(ng + o) * a.ldr + b] = stg[ra - 1] * stg[cb];
     }
 }
 
-size_t vecchia_lds_bytes(int m, bool pred)
-{
-    const size_t kb = (size_t)m + 1;
-    return ((pred ? 2 : 1) * LOCP_FIELDS * kb + kb * (kb + 1) / 2) * sizeof(double) + kb * sizeof(int);
-}
-
-template <bool PRED> static void vecchia_launch(int mode, const VecchiaArgs &a, hipStream_t s)
-{
-    const size_t shm = vecchia_lds_bytes(a.m, PRED);          // m <= 63: at most 31 KB, no attribute needed
-    const dim3 grid((unsigned)a.rows), block(64);
-    switch (mode) {
-    case MODE_HALF: hipLaunchKernelGGL((vecchia_block_kernel<MODE_HALF, PRED, false>), grid, block, shm, s, a); break;
-    case MODE_THREEHALF: hipLaunchKernelGGL((vecchia_block_kernel<MODE_THREEHALF, PRED, false>), grid, block, shm, s, a); break;
-    case MODE_FIVEHALF: hipLaunchKernelGGL((vecchia_block_kernel<MODE_FIVEHALF, PRED, false>), grid, block, shm, s, a); break;
-    default: hipLaunchKernelGGL((vecchia_block_kernel<MODE_GEOM, PRED, false>), grid, block, shm, s, a); break;
-    }
-}
-
-size_t vecchia_grad_lds_bytes(int m)
-{
-    const size_t kb = (size_t)m + 1, ntri = kb * (kb + 1) / 2;
-    return (LOCP_FIELDS * kb + (ntri < (size_t)VECCHIA_STG ? (size_t)VECCHIA_STG : ntri) + VECCHIA_GX * kb) * sizeof(double) +
-           kb * sizeof(int);
-}
-
-void launch_vecchia_grad_blocks(int mode, const VecchiaArgs &a, hipStream_t s)
-{
-    if (a.rows <= 0) return;
-    const size_t shm = vecchia_grad_lds_bytes(a.m);           // m <= 63: at most 32 KB, no attribute needed
-    const dim3 grid((unsigned)a.rows), block(64);
-    switch (mode) {
-    case MODE_HALF: hipLaunchKernelGGL((vecchia_block_kernel<MODE_HALF, false, true>), grid, block, shm, s, a); break;
-    case MODE_THREEHALF: hipLaunchKernelGGL((vecchia_block_kernel<MODE_THREEHALF, false, true>), grid, block, shm, s, a); break;
-    case MODE_FIVEHALF: hipLaunchKernelGGL((vecchia_block_kernel<MODE_FIVEHALF, false, true>), grid, block, shm, s, a); break;
-    default: hipLaunchKernelGGL((vecchia_block_kernel<MODE_GEOM, false, true>), grid, block, shm, s, a); break;
-    }
-}
-
-size_t vecchia_fisher_lds_bytes(int m, int ndir, int gd)
-{
-    const size_t kb = (size_t)m + 1;
-    return (LOCP_FIELDS * kb + kb * (kb + 1) / 2 + VECCHIA_FX * kb + (size_t)gd * (GFAM * kb + 64) + (size_t)ndir * kb) *
-               sizeof(double) + kb * sizeof(int);
-}
+size_t vecchia_lds_bytes(int m, bool pred) { return vecchia_value_lds(m + 1, pred).bytes; }
+size_t vecchia_grad_lds_bytes(int m) { return vecchia_grad_lds(m + 1, false).bytes; }
+size_t vecchia_fisher_lds_bytes(int m, int ndir, int gd) { return vecchia_fisher_lds(m + 1, ndir, gd, 1, false).bytes; }
 
 int vecchia_fisher_group(int m, int ndir)
 {
@@ -513,31 +408,41 @@ int vecchia_fisher_group(int m, int ndir)
     return std::min(gd, std::max(ndir, 1));
 }
 
-template <int MODE> static void vecchia_fisher_launch(const VecchiaArgs &a, size_t shm, hipStream_t s)
+// m <= 63: the value's and the coefficients' LDS is at most 31 KB, the gradient's at most 32 KB -- no attribute needed
+void launch_vecchia_blocks(int mode, bool pred, const VecchiaArgs &a, hipStream_t s)
 {
-    static std::atomic<unsigned long long> attr_done{0};
-    if (shm > 64 * 1024)
-        set_dynamic_lds_once((const void *)vecchia_block_kernel<MODE, false, false, true>, VECCHIA_FISHER_LDS_MAX, attr_done);
-    hipLaunchKernelGGL((vecchia_block_kernel<MODE, false, false, true>), dim3((unsigned)a.rows), dim3(64), shm, s, a);
+    if (a.rows <= 0) return;
+    vecchia_with_mode(mode, [&](auto M) {
+        constexpr int MODE = decltype(M)::value;
+        vecchia_launch_kernel(pred ? vecchia_value_kernel<MODE, true> : vecchia_value_kernel<MODE, false>, a, a.rows, 64,
+                              vecchia_lds_bytes(a.m, pred), s);
+    });
+}
+
+void launch_vecchia_coefs(int mode, const VecchiaArgs &a, hipStream_t s)
+{
+    if (a.rows <= 0) return;
+    vecchia_with_mode(mode, [&](auto M) {
+        vecchia_launch_kernel(vecchia_coef_kernel<decltype(M)::value>, a, a.rows, 64, vecchia_lds_bytes(a.m, false), s);
+    });
+}
+
+void launch_vecchia_grad_blocks(int mode, const VecchiaArgs &a, hipStream_t s)
+{
+    if (a.rows <= 0) return;
+    vecchia_with_mode(mode, [&](auto M) {
+        vecchia_launch_kernel(vecchia_grad_kernel<decltype(M)::value>, a, a.rows, 64, vecchia_grad_lds_bytes(a.m), s);
+    });
 }
 
 void launch_vecchia_fisher_blocks(int mode, const VecchiaArgs &a, hipStream_t s)
 {
     if (a.rows <= 0) return;
-    const size_t shm = vecchia_fisher_lds_bytes(a.m, a.ndir, a.gd);
-    switch (mode) {
-    case MODE_HALF: vecchia_fisher_launch<MODE_HALF>(a, shm, s); break;
-    case MODE_THREEHALF: vecchia_fisher_launch<MODE_THREEHALF>(a, shm, s); break;
-    case MODE_FIVEHALF: vecchia_fisher_launch<MODE_FIVEHALF>(a, shm, s); break;
-    default: vecchia_fisher_launch<MODE_GEOM>(a, shm, s); break;
-    }
-}
-
-void launch_vecchia_blocks(int mode, bool pred, const VecchiaArgs &a, hipStream_t s)
-{
-    if (a.rows <= 0) return;
-    if (pred) vecchia_launch<true>(mode, a, s);
-    else vecchia_launch<false>(mode, a, s);
+    vecchia_with_mode(mode, [&](auto M) {
+        static std::atomic<unsigned long long> attr_done{0};           // (one per instantiation)
+        vecchia_launch_kernel(vecchia_fisher_kernel<decltype(M)::value>, a, a.rows, 64,
+                              vecchia_fisher_lds_bytes(a.m, a.ndir, a.gd), s, &attr_done, VECCHIA_FISHER_LDS_MAX);
+    });
 }
 
 // ---------------------------------------------------------------------------

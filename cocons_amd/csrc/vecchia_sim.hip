@@ -1,8 +1,6 @@
-// vecchia_sim.hip -- U^-1 for a Vecchia fit (gfx950): the inverse of vecchia_block_kernel's whitening.
+// vecchia_sim.hip -- U^-1 for a Vecchia fit (gfx950): the inverse of vecchia_value_kernel's whitening, from the
+// records of vecchia_coef_kernel (vecchia.hip) or of the grouped coefficient launch.
 //
-//   vecchia_coef_kernel        : ONE WAVEFRONT per observation, the gather, pair loop and factorisation of vecchia_block_kernel
-//                                and the backward solve for s = C^-T e_last of its gradient launch; the row's s as one record
-//                                of m + 1 doubles.  No dependency between the rows.
 //   vecchia_level_sweep_kernel : one relaxation sweep of level(i) = 1 + max level(neighbours) over all rows, in place.
 //   vecchia_level_count_kernel, vecchia_level_scatter_kernel : the rows ordered by level (histogram and scatter; the prefix sum
 //                                of the few hundred counts is the host's).
@@ -16,89 +14,8 @@
 // Compile with -ffp-contract=off (see matern_device.hpp).
 #include <hip/hip_runtime.h>
 #include "kernels.h"
-#include "matern_device.hpp"
-#include "vecchia_tri.hpp"
 
 namespace cocons {
-
-// ---------------------------------------------------------------------------
-// Block b of the launch is observation a.obs0 + b.  a.rec: the records, row i at rec[i kb ..]: places t < k hold s_t for the
-// neighbour at place t of the device table, places k .. m - 1 hold 0, place m holds s_last.
-template <int MODE>
-__global__ void __launch_bounds__(64)
-vecchia_coef_kernel(VecchiaArgs a)
-{
-    extern __shared__ double vecchia_sim_lds[];
-    const int lane = threadIdx.x, row = a.obs0 + blockIdx.x, kb = a.kb;
-    double *par = vecchia_sim_lds;
-    double *tri = par + LOCP_FIELDS * kb;
-    int *nb = (int *)(tri + kb * (kb + 1) / 2);
-
-    const int mine = lane < a.m ? a.nbr[(size_t)row * a.m + lane] : -1;
-    const int k = __popcll(__ballot(mine >= 0));
-    const int nrows = k + 1;
-    if (lane < k) nb[lane] = mine;
-    if (lane == k) nb[lane] = row;
-    __syncthreads();
-    for (int e = lane; e < nrows * VECCHIA_REC; e += 64) {
-        const int r = e / VECCHIA_REC, f = e % VECCHIA_REC;
-        if (f >= LOCP_FIELDS) continue;
-        par[f * kb + r] = a.aosK[(size_t)nb[r] * VECCHIA_REC + f];
-    }
-    __syncthreads();
-    // the block, the earlier row on the `ii` side (vecchia_block_kernel's assembly)
-    const int npairs = nrows * (nrows - 1) / 2;
-    for (int t = lane; t < npairs; t += 64) {
-        int r, c;
-        tri_pair(t, r, c);
-        tri[tri_at(r, c)] = pair_value_idx<MODE>(par, (size_t)kb, c, par, (size_t)kb, r, a.gr, a.nu_fixed, false);
-    }
-    if (lane < nrows) tri[tri_at(lane, lane)] = par[11 * kb + lane];
-    // K = C C', right-looking, one column per step, lane = row
-    const int myrow = tri_at(lane, 0);
-    double piv_mine = 1.0;
-    bool bad = false;
-    for (int j = 0; j < nrows; ++j) {
-        __syncthreads();
-        const double d = tri[tri_at(j, j)];
-        if (!(d > 0.0) || !isfinite(d)) { bad = true; break; }       // (the same in every lane)
-        const double piv = sqrt(d);
-        if (lane == j) piv_mine = piv;
-        double lrj = 0.0;
-        if (lane > j && lane < nrows) { lrj = tri[myrow + j] / piv; tri[myrow + j] = lrj; }
-        __syncthreads();
-        if (lane > j && lane < nrows)
-            for (int c = j + 1; c <= lane; ++c) tri[myrow + c] -= lrj * tri[tri_at(c, j)];
-    }
-    if (bad) {
-        if (lane == 0) atomicMin(a.fail, row + 1);
-        return;
-    }
-    __syncthreads();
-    // s = C^-T e_last: one column of C' (a row of the packed factor) per step; lane j ends with component j
-    double rs = lane == k ? 1.0 : 0.0, s_mine = 0.0;
-    for (int j = k; j >= 0; --j) {
-        const double xs = __shfl(rs / piv_mine, j);
-        if (lane == j) s_mine = xs;
-        if (lane < j) rs -= tri[tri_at(j, 0) + lane] * xs;
-    }
-    double *rec = a.rec + (size_t)row * kb;
-    if (lane < a.m) rec[lane] = lane < k ? s_mine : 0.0;
-    if (lane == k) rec[a.m] = s_mine;
-}
-
-void launch_vecchia_coefs(int mode, const VecchiaArgs &a, hipStream_t s)
-{
-    if (a.rows <= 0) return;
-    const size_t shm = vecchia_lds_bytes(a.m, false);         // m <= 63: at most 23 KB, no attribute needed
-    const dim3 grid((unsigned)a.rows), block(64);
-    switch (mode) {
-    case MODE_HALF: hipLaunchKernelGGL((vecchia_coef_kernel<MODE_HALF>), grid, block, shm, s, a); break;
-    case MODE_THREEHALF: hipLaunchKernelGGL((vecchia_coef_kernel<MODE_THREEHALF>), grid, block, shm, s, a); break;
-    case MODE_FIVEHALF: hipLaunchKernelGGL((vecchia_coef_kernel<MODE_FIVEHALF>), grid, block, shm, s, a); break;
-    default: hipLaunchKernelGGL((vecchia_coef_kernel<MODE_GEOM>), grid, block, shm, s, a); break;
-    }
-}
 
 // ---------------------------------------------------------------------------
 // Levels.  level[i] = 0 for the fixed rows i < n_fixed and never touched; every other row starts at 0 and only grows towards
