@@ -68,6 +68,8 @@ SIGNATURES = {
     "cocons_vecchia_neighbours": (c_int, [c_int, c_dp, c_int, c_dp, c_int, c_int, ctypes.POINTER(c_int)]),
     "cocons_fit_create_vecchia_knn": (c_vp, [c_int, c_int, c_int, c_dp, c_dp, c_dp, c_dp, c_int, c_int]),
     "cocons_vecchia_predict_knn": (c_int, [c_vp, c_dp, c_dp, c_int, c_int, c_dp, c_dp, c_int, c_dp, c_dp]),
+    "cocons_vecchia_neighbours_corr": (c_int, [c_vp, c_dp, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
+    "cocons_fit_create_vecchia_corr_knn": (c_vp, [c_int, c_int, c_int, c_dp, c_dp, c_dp, c_dp, c_int, c_dp, c_int, c_int, c_int]),
     "cocons_vecchia_order": (c_int, [c_int, c_dp, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "cocons_vecchia_unwhiten": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp]),
     "cocons_sim_vecchia": (c_int, [c_vp, c_dp, c_dp, c_int, c_int, c_int, c_dp, c_dp]),
@@ -176,6 +178,7 @@ DIAG_SIGNATURES = {
     "cocons_debug_knn_plan": (c_int, [c_int, c_dp, c_int, c_int, c_dp, c_int, ctypes.POINTER(c_int), c_dp, ctypes.POINTER(c_int),
                                       c_dp]),
     "cocons_debug_knn_phases": (c_int, [c_int, c_dp, c_int, c_int, c_dp]),
+    "cocons_debug_knn_corr_phases": (c_int, [c_vp, c_dp, c_int, c_int, c_int, c_dp]),
     "cocons_debug_group_rounds": (c_int, [c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), c_dp]),
     "cocons_debug_order_plan": (c_int, [c_int, c_dp, ctypes.POINTER(c_int), c_dp, c_dp]),
     "cocons_debug_order_phases": (c_int, [c_int, c_dp, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_dp,

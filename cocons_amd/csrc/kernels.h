@@ -433,6 +433,36 @@ struct KnnArgs {
 };
 hipError_t launch_knn_query(const KnnArgs &a, int rows, hipStream_t s);
 
+// ---- Vecchia neighbours by model correlation (knn_corr.hip; the rule: include/cocons_hip.h) -----------------
+// One wave per row: block b of the launch is row i = b of n.  cand: the Euclidean ordered table of width mc in the layout of
+// VecchiaArgs::nbr (row after row, 0-based, ascending, -1 behind the last).  The candidates of row i are cand's row i and,
+// with hops = 2, the rows of its members, each index once; their key is (rho descending, index ascending), rho = v / sqrt(d_i
+// d_j) from the records aos (launch_vecchia_aos) -- v the pair value with the earlier row on the `ii` side, d field 11.
+// nn (may be null): nn[i + j ldn] = the candidate with the j-th largest key + 1, 0 behind the last.  tab (may be null):
+// tab[i m + j] = the same m candidates 0-based and ascending by index, -1 behind the last.  fail: atomicMin of the 1-based
+// rows with a rho that is not finite (such a row writes nothing).
+constexpr int KNN_CORR_CAND_MAX = 63 + 63 * 63;       // indices that reach the deduplication of one row
+struct KnnCorrArgs {
+    int n = 0, mc = 0, hops = 1, m = 0;
+    const int *cand = nullptr;
+    const double *aos = nullptr;
+    double gr = 0.0, nu_fixed = 0.0;
+    int *nn = nullptr; size_t ldn = 0;
+    int *tab = nullptr;
+    int *fail = nullptr;
+};
+// slots of the row's set of indices in LDS: a power of two above the indices that can reach it, so a free slot always ends
+// a probe.  (Neighbouring rows' lists overlap: at m_cand = 60 some 400 of the 3660 are distinct, and the LDS a row holds
+// bounds the wavefronts a CU keeps in flight.)
+__host__ __device__ inline int knn_corr_slots(int mc, int hops)
+{
+    int s = 64;
+    while (s <= mc + (hops > 1 ? mc * mc : 0)) s <<= 1;
+    return s;
+}
+size_t knn_corr_lds_bytes(int mc, int hops);
+hipError_t launch_knn_corr(int mode, const KnnCorrArgs &a, hipStream_t s);
+
 // ---- maxmin ordering by scale-halving nets (order.hip; the rule: order_plan.hpp) -------------------------------
 // The points live in LABEL order (px, py, orig: the caller's index), so a lower index is a higher priority.  state[p], by
 // label: ORDER_FREE (not ordered, undecided at this level), ORDER_DONE (ordered), ORDER_DROPPED (conflicts with an ordered

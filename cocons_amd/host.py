@@ -1434,6 +1434,39 @@ def vecchia_neighbours_pred_device(locs, newlocs, m, device=0) -> np.ndarray:
     return _neighbours_device(locs, newlocs, m, device)
 
 
+def vecchia_neighbours_corr(S, nn_cand, m, hops=2) -> np.ndarray:
+    """The Vecchia neighbours by model correlation (the rule: include/cocons_hip.h), restated on the host:
+    S the n x n covariance of the observations at theta in the Vecchia order (`cov_rns`), nn_cand the Euclidean ordered table
+    (n x m_cand, 1-based, 0 = none; `vecchia_neighbours_device`).  The candidates of row i are nn_cand's row i and, with
+    hops = 2, the rows of its members, each index once; row i lists the m of them with the largest key (rho, then the lower
+    index), rho = S[j, i] / sqrt(S[i, i] S[j, j]) with one rounding per operation, compared by the total order of its bit
+    patterns (for rho >= 0: by value): n x m int32 in Fortran order, 1-based, largest rho first, zero-padded.  ValueError
+    names the first row with a rho that is not finite."""
+    S = np.asarray(S, dtype=np.float64)
+    n, m, hops = S.shape[0], int(m), int(hops)
+    cand = np.asarray(nn_cand, dtype=np.int64).reshape(n, -1)
+    if hops not in (1, 2) or m < 1:
+        raise ValueError("hops must be 1 or 2 and m at least 1")
+    d = np.ascontiguousarray(np.diagonal(S))
+    out = np.zeros((n, m), dtype=np.int32, order="F")
+    top = np.uint64(1) << np.uint64(63)
+    for i in range(n):
+        c = cand[i][cand[i] > 0]
+        if hops == 2 and c.size:
+            c = np.concatenate([c, cand[c - 1].ravel()])
+        c = np.unique(c[c > 0]) - 1
+        if not c.size:
+            continue
+        rho = S[c, i] / np.sqrt(d[i] * d[c])
+        if not np.all(np.isfinite(rho)):
+            raise ValueError("row %d has a candidate whose correlation is not finite" % (i + 1))
+        b = rho.view(np.uint64)
+        key = ~np.where(b >> np.uint64(63) != 0, ~b, b | top)          # ascends as rho descends
+        o = np.lexsort((c, key))[:m]
+        out[i, :o.size] = c[o] + 1
+    return out
+
+
 _ORDER_LEVELS = 64
 _ORDER_MIX = (0x9E3779B1, 0x85EBCA6B, 0xC2B2AE35)
 
@@ -1655,6 +1688,45 @@ class CoconsVecchiaFit(_Handle):
         self = make(locs[o], X[o], z[o], smooth_limits, m, device=device, **more)
         self.maxmin_order = order
         return self
+
+    @classmethod
+    def from_corr_knn(cls, locs, x_covariates, z, smooth_limits, theta_list, m, m_cand=None, hops=2, device=-1):
+        """The handle of the table `neighbours_corr(theta_list, m, m_cand, hops)` (cocons_fit_create_vecchia_corr_knn, DESIGN.md
+        4af): the Euclidean search of width m_cand (default min(2 m, 63)), the records at theta and the re-ranking by model
+        correlation all on the device; neither table reaches the host, and every core gives the bits of the handle made
+        from the exported table.  A grouped handle on such a table goes through `vecchia_group_device` / `from_groups` on
+        the exported table."""
+        self = cls.__new__(cls)
+        locs, X, z = self._adopt(locs, x_covariates, z, smooth_limits)
+        self.m = int(m)
+        mc = min(2 * self.m, 63) if m_cand is None else int(m_cand)
+        T = theta_table(theta_list)
+        self._created(self._L.cocons_fit_create_vecchia_corr_knn(self.n, self.p, self.r, _p(locs), _p(X), _p(z),
+                                                                 _p(self.smooth_limits), int(device), _p(T), mc, int(hops),
+                                                                 self.m), "cocons_fit_create_vecchia_corr_knn")
+        return self
+
+    @classmethod
+    def from_maxmin_corr(cls, locs, x_covariates, z, smooth_limits, theta_list, m, m_cand=None, hops=2, device=-1):
+        """`from_maxmin` with `from_corr_knn` in the place of `from_knn`: the maxmin order, then the correlation table of the
+        permuted rows at theta; the rows are the permuted ones, as `from_maxmin`'s are."""
+        def make(locs_, X_, z_, sl_, m_, device=-1):
+            return cls.from_corr_knn(locs_, X_, z_, sl_, theta_list, m_, m_cand=m_cand, hops=hops, device=device)
+        return cls._from_maxmin(make, locs, x_covariates, z, smooth_limits, m, device=device)
+
+    def neighbours_corr(self, theta_list, m, m_cand=None, hops=2):
+        """The Vecchia neighbours of the handle's observations by model correlation at theta (cocons_vecchia_neighbours_corr,
+        DESIGN.md 4af): among the candidates -- the m_cand (default min(2 m, 63)) Euclidean-nearest predecessors and, with
+        hops = 2, theirs -- the m with the largest correlation under Sigma(theta), largest first: n x m int32 in Fortran
+        order, 1-based, zero-padded.  `vecchia_neighbours_corr` restates the rule on the host.  The handle's own table is
+        neither read nor changed.  CholeskyError(i): row i has a candidate whose correlation is not finite."""
+        m = int(m)
+        mc = min(2 * m, 63) if m_cand is None else int(m_cand)
+        T = theta_table(theta_list)
+        nn = np.zeros((self.n, m), dtype=np.int32, order="F")
+        _lib.check(self._L.cocons_vecchia_neighbours_corr(self._h, _p(T), mc, int(hops), m, _ip(nn)),
+                   "cocons_vecchia_neighbours_corr")
+        return nn
 
     @classmethod
     def from_groups(cls, locs, x_covariates, z, smooth_limits, nn, max_rows=64, device=-1):

@@ -575,6 +575,26 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
         as.integer(device), as.integer(m))
 }
 
+# the neighbours by MODEL CORRELATION (DESIGN.md 4af): under local anisotropy the predecessors that matter lie along the long
+# axis of the local kernel, not inside the Euclidean m-nearest.  Among the m_cand Euclidean-nearest predecessors of a row and
+# (hops = 2) theirs, row i lists the m most correlated with it under Sigma(theta), largest first, ties to the lower index.
+#   fit0 <- .cocons.hip.vecchia.create.knn(locs[ord, ], X[ord, ], z[ord, , drop = FALSE], smooth.limits, m)   # a first fit
+#   nn   <- .cocons.hip.vecchia.neighbours.corr(fit0, theta_list, m)                                          # re-ranked at its optimum
+#   fit  <- .cocons.hip.vecchia.create.corr.knn(locs[ord, ], X[ord, ], z[ord, , drop = FALSE], smooth.limits, theta_list, m)
+# (the second is .cocons.hip.vecchia.create with nn, made on the device).  A grouped fit on such a table:
+# .cocons.hip.vecchia.group.device(nn) and .cocons.hip.vecchia.create.grouped; new locations keep the Euclidean search.
+.cocons.hip.vecchia.neighbours.corr <- function(fit, theta_list, m, m_cand = min(2L * as.integer(m), 63L), hops = 2L) {
+  res <- .Call(`_cocons_hip_vecchia_neighbours_corr`, fit, theta_list, as.integer(m_cand), as.integer(hops), as.integer(m))
+  if (res[[1]] > 0L) stop("the correlation of row ", res[[1]], " with a candidate is not finite")
+  res[[2]]
+}
+
+.cocons.hip.vecchia.create.corr.knn <- function(locs, x_covariates, z, smooth.limits, theta_list, m,
+                                                m_cand = min(2L * as.integer(m), 63L), hops = 2L, device = -1L) {
+  .Call(`_cocons_hip_vecchia_create_corr_knn`, as.matrix(locs), as.matrix(x_covariates), as.matrix(z), as.double(smooth.limits),
+        as.integer(device), theta_list, as.integer(m_cand), as.integer(hops), as.integer(m))
+}
+
 # .cocons.hip.vecchia.predict without nn_pred: every new location is predicted from its m_pred nearest observations, found
 # on the device chunk by chunk
 .cocons.hip.vecchia.predict.knn <- function(fit, theta_list, newlocs, X_pred, m_pred, z_col = 1L) {

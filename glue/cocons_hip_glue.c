@@ -1104,6 +1104,50 @@ SEXP _cocons_hip_vecchia_neighbours(SEXP locs, SEXP newlocs, SEXP m, SEXP device
     return nn;
 }
 
+/* the Vecchia neighbours of a fit's observations by model correlation at theta (cocons_vecchia_neighbours_corr):
+ * among the m_cand Euclidean-nearest predecessors of a row and (hops = 2) theirs, the m most correlated with it under
+ * Sigma(theta).  list(status, integer matrix n x m, 1-based, largest correlation first, 0 = none); status > 0: the row whose
+ * correlation with a candidate is not finite */
+SEXP _cocons_hip_vecchia_neighbours_corr(SEXP fitp, SEXP theta, SEXP m_cand, SEXP hops, SEXP m)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int n = fit_n(fitp), mc = Rf_asInteger(m_cand), h = Rf_asInteger(hops), k = Rf_asInteger(m);
+    if (mc < 1 || mc > 63) Rf_error("cocons_vecchia_neighbours_corr: m_cand = %d is outside 1 .. 63", mc);
+    if (h < 1 || h > 2) Rf_error("cocons_vecchia_neighbours_corr: hops = %d is outside 1 .. 2", h);
+    if (k < 1 || k > 63) Rf_error("cocons_vecchia_neighbours_corr: m = %d is outside 1 .. 63", k);
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, fit_p(fitp), T);
+    SEXP nn = PROTECT(Rf_allocMatrix(INTSXP, n, k));
+    memset(INTEGER(nn), 0, (size_t)n * k * sizeof(int));
+    int rc = cocons_vecchia_neighbours_corr(f, T, mc, h, k, INTEGER(nn));
+    hip_check(rc, "Vecchia neighbours by correlation");
+    SEXP out = status_value(rc, nn);
+    UNPROTECT(1);
+    return out;
+}
+
+/* Vecchia handle whose table is _cocons_hip_vecchia_neighbours_corr's for the same data (cocons_fit_create_vecchia_corr_knn):
+ * search, records at theta, re-ranking and adoption on the device; neither table comes to the host */
+SEXP _cocons_hip_vecchia_create_corr_knn(SEXP locs, SEXP X, SEXP z, SEXP smooth_limits, SEXP device, SEXP theta, SEXP m_cand,
+                                         SEXP hops, SEXP m)
+{
+    const int n = Rf_nrows(X), p = Rf_ncols(X);
+    const int r = Rf_isMatrix(z) ? Rf_ncols(z) : 1;
+    if (Rf_nrows(locs) != n || Rf_ncols(locs) != 2) Rf_error("locs must be n x 2");
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    cocons_fit *f = cocons_fit_create_vecchia_corr_knn(n, p, r, REAL(locs), REAL(X), REAL(z), REAL(smooth_limits),
+                                                       Rf_asInteger(device), T, Rf_asInteger(m_cand), Rf_asInteger(hops),
+                                                       Rf_asInteger(m));
+    if (!f) Rf_error("%s", cocons_last_error());
+    SEXP tag = PROTECT(Rf_allocVector(INTSXP, 4));
+    INTEGER(tag)[0] = n; INTEGER(tag)[1] = p; INTEGER(tag)[2] = r; INTEGER(tag)[3] = 0;
+    SEXP ptr = PROTECT(R_MakeExternalPtr(f, tag, R_NilValue));
+    R_RegisterCFinalizerEx(ptr, fit_finalizer, TRUE);
+    UNPROTECT(2);
+    return ptr;
+}
+
 /* the maxmin order of the rows of locs (n x 2) found on the device (cocons_vecchia_order): an integer vector, 1-based,
  * ord[t] the row at position t */
 SEXP _cocons_hip_vecchia_order(SEXP locs, SEXP device)
@@ -1731,6 +1775,8 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_vecchia_neighbours", (DL_FUNC)&_cocons_hip_vecchia_neighbours, 4},
     {"_cocons_hip_vecchia_order", (DL_FUNC)&_cocons_hip_vecchia_order, 2},
     {"_cocons_hip_vecchia_create_knn", (DL_FUNC)&_cocons_hip_vecchia_create_knn, 6},
+    {"_cocons_hip_vecchia_neighbours_corr", (DL_FUNC)&_cocons_hip_vecchia_neighbours_corr, 5},
+    {"_cocons_hip_vecchia_create_corr_knn", (DL_FUNC)&_cocons_hip_vecchia_create_corr_knn, 9},
     {"_cocons_hip_vecchia_predict_knn", (DL_FUNC)&_cocons_hip_vecchia_predict_knn, 6},
     {"_cocons_hip_vecchia_unwhiten", (DL_FUNC)&_cocons_hip_vecchia_unwhiten, 3},
     {"_cocons_hip_vecchia_sim", (DL_FUNC)&_cocons_hip_vecchia_sim, 5},

@@ -387,6 +387,48 @@ int cocons_vecchia_predict_knn(cocons_fit *fit, const double *theta, const doubl
                                const double *locs_pred, const double *X_pred, int m_pred,
                                double *stochastic, double *quadform);
 
+/* ---- Vecchia neighbours by model correlation ----------------------------------------------------------------
+ * Under a covariance with local anisotropy the predecessors that matter for row i are those most CORRELATED with it under
+ * Sigma(theta), which lie along the long axis of the local kernel and may be far outside its m Euclidean-nearest.  The rule,
+ * here and in every reference, for the observations in the caller's order, theta, m_cand in 1 .. 63, hops in {1, 2}, m in
+ * 1 .. 63:
+ *  1. N(i) is row i of the Euclidean ordered table of width m_cand: cocons_vecchia_neighbours(n, locs, 0, NULL, m_cand, ..).
+ *  2. The candidates C(i): N(i) for hops = 1; N(i) and the N(j) of every j in N(i) for hops = 2.  Zeros are dropped, every
+ *     member is earlier than i, and an index counts once however many lists name it (at most 63 + 63^2 = 4032 reach the
+ *     deduplication).
+ *  3. The key of a candidate j is (rho descending, index ascending), rho(i, j) = fl(v / fl(sqrt(fl(d_i d_j)))): v the entry the
+ *     Vecchia block of row i holds for (j, i) -- the pair value with the EARLIER row j on the `ii` side, the bits of
+ *     cocons_cov_rns's entry --, d the rows' diagonal values (cocons_cov_rns's diagonal); fp64, one rounding per operation,
+ *     no contraction.  rho is compared by the total order of its bit patterns, which for rho >= 0 -- every rho of a valid
+ *     model -- is the order of its values.
+ *  4. Row i lists the m candidates with the largest key, largest rho first, 1-based, zero-padded.
+ * So the output is a function of the inputs alone, the same bits from run to run; the table for m is the first m columns of
+ * the table for any m' > m at the same m_cand and hops; a row i <= m_cand + 1 ranks all its predecessors; hops = 1 with
+ * m = m_cand returns N(i) as a set; and under an isotropic stationary theta every setting returns the Euclidean table's sets
+ * (up to ties of rho's rounding).  host.vecchia_neighbours_corr restates the rule in numpy.
+ *
+ * cocons_vecchia_neighbours_corr: on any Vecchia handle, which supplies locs, X and smooth_limits in its order; the handle's own
+ * table is neither read nor changed.  nn_out: n x m column-major.  The Euclidean candidates are searched on the device, the
+ * records of theta are those of every Vecchia evaluation.  The scratch -- n (m_cand + m) ints -- belongs to the call and is
+ * freed before it returns: cocons_vecchia_info's bytes are the same before and after.  Returns 0; the smallest 1-based row
+ * with a rho that is not finite (nn_out untouched: the failing-block convention); -1 before any device work, nn_out
+ * untouched, with a message that starts with the entry's name for: a null argument, a handle that is not a Vecchia handle,
+ * m_cand, hops or m out of range, m > min(4032, m_cand + m_cand^2 (hops - 1)), a theta that is not finite.
+ *
+ * cocons_fit_create_vecchia_corr_knn: cocons_fit_create_vecchia with the table cocons_vecchia_neighbours_corr returns for the
+ * same data -- the same bits from every Vecchia entry --, made in one chain on the device: search, records at theta, re-rank,
+ * adoption.  Neither table reaches the host.  NULL with the refusals above and cocons_fit_create_vecchia's, under this
+ * entry's name, or when a rho is not finite.
+ *
+ * Out of scope: a fused device chain to a GROUPED handle on such a table (export the table, then cocons_vecchia_group_rounds
+ * / cocons_fit_create_vecchia_grouped), and correlation-ranked neighbours of NEW locations in cocons_vecchia_predict_knn.
+ * These two entries add to the ABI and change no existing one: cocons_abi_version stays 1.                                */
+int cocons_vecchia_neighbours_corr(cocons_fit *fit, const double *theta, int m_cand, int hops, int m,
+                                   int *nn_out /* n x m column-major, 1-based, largest rho first, 0 = none */);
+cocons_fit *cocons_fit_create_vecchia_corr_knn(int n, int p, int r, const double *locs, const double *X, const double *z,
+                                               const double *smooth_limits, int device, const double *theta, int m_cand,
+                                               int hops, int m);
+
 /* ---- Maxmin ordering on the device: scale-halving nets ------------------------------------------------------
  * The order of the observations a Vecchia fit wants: coarse to fine, every point at least half as far from its predecessors
  * as the farthest remaining point is.  The rule, here and in every reference (d2 as above: fl(fl(dx dx) + fl(dy dy)), fp64,

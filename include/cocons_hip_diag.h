@@ -63,6 +63,12 @@ int cocons_debug_knn_plan(int n, const double *locs, int level, int m, const dou
  * tools/vecchia_knn_timing.py.  0, or < 0 with the refusals of cocons_vecchia_neighbours under this entry's name.        */
 int cocons_debug_knn_phases(int n, const double *locs, int m, int device, double *ms2);
 
+/* The three phases of cocons_vecchia_neighbours_corr(fit, theta, m_cand, hops, m, ..), timed by events on the
+ * handle's stream: ms3 = { device milliseconds of the Euclidean search of width m_cand, of the records at theta, of the
+ * re-ranking launch }.  The call runs as it does there; its table stays on the device and is dropped.  For
+ * tools/vecchia_corr_timing.py.  0, or the returns and refusals of cocons_vecchia_neighbours_corr under this entry's name.   */
+int cocons_debug_knn_corr_phases(cocons_fit *fit, const double *theta, int m_cand, int hops, int m, double *ms3);
+
 /* The rounds of cocons_vecchia_group_device(n, m, nn, max_rows, max_rounds, device, ..), timed by events on the
  * call's stream: for every round launched -- the one that finds no proposal included --, live[t] = the blocks alive at its
  * start and ms[t] = the device milliseconds of its three launches; at most cap rounds are recorded.  The rounds run as they
