@@ -70,6 +70,10 @@ SIGNATURES = {
     "cocons_vecchia_predict_knn": (c_int, [c_vp, c_dp, c_dp, c_int, c_int, c_dp, c_dp, c_int, c_dp, c_dp]),
     "cocons_vecchia_neighbours_corr": (c_int, [c_vp, c_dp, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
     "cocons_fit_create_vecchia_corr_knn": (c_vp, [c_int, c_int, c_int, c_dp, c_dp, c_dp, c_dp, c_int, c_dp, c_int, c_int, c_int]),
+    "cocons_vecchia_neighbours_corr_pred": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
+    "cocons_vecchia_predict_corr_knn": (c_int, [c_vp, c_dp, c_dp, c_int, c_int, c_dp, c_dp, c_int, c_int, c_int, c_dp, c_dp]),
+    "cocons_fit_create_vecchia_grouped_corr_knn": (c_vp, [c_int, c_int, c_int, c_dp, c_dp, c_dp, c_dp, c_int, c_dp, c_int, c_int,
+                                                          c_int, c_int, c_int]),
     "cocons_vecchia_order": (c_int, [c_int, c_dp, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "cocons_vecchia_unwhiten": (c_int, [c_vp, c_dp, c_int, c_dp, c_dp]),
     "cocons_sim_vecchia": (c_int, [c_vp, c_dp, c_dp, c_int, c_int, c_int, c_dp, c_dp]),

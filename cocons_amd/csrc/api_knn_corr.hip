@@ -2,12 +2,14 @@
 // cocons_vecchia_neighbours_corr, the table of a Vecchia handle's observations at theta, and cocons_fit_create_vecchia_corr_knn,
 // the handle whose table it is.  Both run one chain on the handle's stream -- the ordered Euclidean search of width m_cand
 // (knn_self_search), the records at theta (vecchia_records), the re-ranking (launch_knn_corr) -- and neither table reaches
-// the host on the way to a handle; cocons_debug_knn_corr_phases times the three by events.  The scratch (the candidate table,
+// the host on the way to a handle, plain or grouped (cocons_fit_create_vecchia_grouped_corr_knn: the chain of
+// cocons_fit_create_vecchia_grouped_knn with this table in the place of its search); cocons_debug_knn_corr_phases times the
+// three by events.  New locations: cocons_vecchia_neighbours_corr_pred and cocons_vecchia_predict_corr_knn
+// are vecchia_predict_impl with a third table source, whose per-chunk step (corr_pred_chunk) and handle-held lists
+// (corr_pred_prepare) live here.  The scratch (the candidate table,
 // the table that goes home) belongs to the call; the records land in the handle's own per-evaluation buffer, which every
 // evaluation rewrites.  No existing entry comes here.
 #include "fit.hpp"
-
-namespace {
 
 int corr_check_shape(const char *who, int m_cand, int hops, int m)
 {
@@ -25,6 +27,8 @@ int corr_check_theta(const char *who, const double *theta, int p)
         if (!std::isfinite(theta[k])) return fail(-1, "%s: theta[%d] is not finite", who, k);
     return 0;
 }
+
+namespace {
 
 // search -> records at theta -> re-rank on the handle's stream, drained.  d_nn (n x m column-major, 1-based, largest rho
 // first; may be null), d_tab (the layout of VecchiaState::nbr; may be null).  0, or the smallest 1-based row with a rho that
@@ -81,7 +85,97 @@ struct CorrKnnSource : VecchiaTableSource {
     }
 };
 
+// cocons_fit_create_vecchia_grouped_knn's chain with the correlation table at the handle's theta in the place of the search
+struct CorrTableStep : GroupedTableStep {
+    const double *theta = nullptr;
+    int m_cand = 0, hops = 0;
+    int table(const char *who, cocons_fit *f, const double *, int m, int *d_tab) override
+    {
+        return corr_table(who, f, theta, m_cand, hops, m, nullptr, d_tab);
+    }
+};
+
 }  // namespace
+
+// ---- new locations ------------------------------------------------------------------------------------------
+int corr_pred_prepare(const char *who, cocons_fit *f, int m_cand, int hops, hipStream_t s)
+{
+    VecchiaState *V = f->vecchia.get();
+    if (int rc = vecchia_need_grid(who, f, s)) return rc;
+    if (hops < 2 || (V->corr_all.get() && V->corr_all_mc == m_cand)) return 0;
+    // the second-hop lists: every observation's plain kNN among all observations, the handle's from here on (counted by
+    // cocons_vecchia_info, freed with it): n x m_cand ints -- 120 MB at n = 10^6, m_cand = 30
+    const int n = f->n;
+    V->corr_all_mc = 0;
+    if (hipError_t e = V->corr_all.alloc((size_t)n * m_cand)) {
+        V->corr_all.reset();
+        (void)hipGetLastError();
+        return fail(-100 - (int)e, "%s: %s", who, hipGetErrorString(e));
+    }
+    KnnArgs k;
+    k.t = V->knn->t; k.qx = f->dlocs; k.qy = f->dlocs + n; k.m = m_cand; k.tab = V->corr_all;
+    hipError_t e = launch_knn_query(k, n, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        V->corr_all.reset();
+        (void)hipGetLastError();
+        return fail(-100 - (int)e, "%s: %s", who, hipGetErrorString(e));
+    }
+    V->corr_all_mc = m_cand;
+    return 0;
+}
+
+int corr_pred_chunk(const char *who, cocons_fit *f, const CorrPredSource &c, int m, int mc, int row0, const double *dlp,
+                    const double *drec, const double *aosC, double gr, int *d_first, int *d_tab, int *d_nn, hipStream_t s)
+{
+    VecchiaState *V = f->vecchia.get();
+    KnnArgs k;
+    k.t = V->knn->t; k.qx = dlp; k.qy = dlp + mc; k.m = c.m_cand; k.tab = d_first;
+    HIPCHK_AT(who, launch_knn_query(k, mc, s));
+    KnnCorrPredArgs a;
+    a.rows = mc; a.mc = c.m_cand; a.hops = c.hops; a.m = m; a.row0 = row0;
+    a.first = d_first; a.all = c.hops > 1 ? V->corr_all.get() : nullptr;
+    a.aosC = aosC; a.aosP = drec; a.gr = gr;
+    a.nn = d_nn; a.ldn = (size_t)mc; a.tab = d_tab; a.fail = f->dinfo;
+    HIPCHK_AT(who, launch_knn_corr_pred(a, s));
+    return 0;
+}
+
+extern "C" int cocons_vecchia_neighbours_corr_pred(cocons_fit *f, const double *theta, int mp, const double *locs_pred,
+                                                   const double *X_pred, int m_cand, int hops, int m, int *nn_out)
+{
+    const char *who = "cocons_vecchia_neighbours_corr_pred";
+    if (!f) return fail(-1, "%s: null fit handle", who);
+    if (mp > 0 && !nn_out) return fail(-1, "%s: bad argument (mp < 0 or a null pointer)", who);
+    int none = 0;
+    CorrPredSource c;
+    c.m_cand = m_cand; c.hops = hops; c.nn_out = nn_out ? nn_out : &none;      // (mp = 0: nothing is written)
+    return vecchia_predict_impl(who, f, theta, nullptr, 0, mp, locs_pred, X_pred, m, nullptr, true, nullptr, nullptr, &c);
+}
+
+extern "C" int cocons_vecchia_predict_corr_knn(cocons_fit *f, const double *theta, const double *mean, int z_col, int mp,
+                                               const double *locs_pred, const double *X_pred, int m_cand, int hops, int m_pred,
+                                               double *stochastic, double *quadform)
+{
+    CorrPredSource c;
+    c.m_cand = m_cand; c.hops = hops;
+    return vecchia_predict_impl("cocons_vecchia_predict_corr_knn", f, theta, mean, z_col, mp, locs_pred, X_pred, m_pred, nullptr,
+                                true, stochastic, quadform, &c);
+}
+
+extern "C" cocons_fit *cocons_fit_create_vecchia_grouped_corr_knn(int n, int p, int r, const double *locs, const double *X,
+                                                                  const double *z, const double *smooth_limits, int device,
+                                                                  const double *theta, int m_cand, int hops, int m,
+                                                                  int max_rows, int max_rounds)
+{
+    const char *who = "cocons_fit_create_vecchia_grouped_corr_knn";
+    if (!theta) { fail(-1, "%s: null argument", who); return nullptr; }
+    if (p < 1 || p > COCONS_P_MAX) { fail(-1, "%s: bad argument (p = %d)", who, p); return nullptr; }
+    if (corr_check_shape(who, m_cand, hops, m) || corr_check_theta(who, theta, p)) return nullptr;
+    CorrTableStep step;
+    step.theta = theta; step.m_cand = m_cand; step.hops = hops;
+    return vecchia_create_grouped_device(who, n, p, r, locs, X, z, smooth_limits, device, m, max_rows, max_rounds, step);
+}
 
 extern "C" int cocons_vecchia_neighbours_corr(cocons_fit *f, const double *theta, int m_cand, int hops, int m, int *nn_out)
 {

@@ -458,21 +458,30 @@ extern "C" int cocons_vecchia_whiten(cocons_fit *f, const double *theta, int c, 
 }
 
 // cocons_vecchia_predict, or with search (cocons_vecchia_predict_knn) the same with every chunk's table found on
-// the device: the neighbours land ascending in the chunk's table buffer, no table is uploaded and none is sorted on the host
+// the device: the neighbours land ascending in the chunk's table buffer, no table is uploaded and none is sorted on the host;
+// or with corr the same with the chunk's table re-ranked by model correlation, or that table alone
+// (corr->nn_out)
 int vecchia_predict_impl(const char *who, cocons_fit *f, const double *theta, const double *mean, int z_col, int mp,
                          const double *locs_pred, const double *X_pred, int m_pred, const int *nn_pred, bool search,
-                         double *stochastic, double *quadform)
+                         double *stochastic, double *quadform, const CorrPredSource *corr)
 {
+    const bool table_only = corr && corr->nn_out;
+    if (corr) search = true;                    // (no table comes in either way)
     if (!f) return fail(-1, "%s: null fit handle", who);
-    if (!theta || !mean) return fail(-1, "%s: null argument", who);
-    if (mp < 0 || (mp > 0 && (!locs_pred || !X_pred || (!search && !nn_pred) || !stochastic || !quadform)))
+    if (!theta || (!table_only && !mean)) return fail(-1, "%s: null argument", who);
+    if (mp < 0 || (mp > 0 && (!locs_pred || !X_pred || (!search && !nn_pred) || (!table_only && (!stochastic || !quadform)))))
         return fail(-1, "%s: bad argument (mp < 0 or a null pointer)", who);
-    if (m_pred < 1 || m_pred > VECCHIA_M_MAX) return fail(-1, "%s: m_pred = %d is outside 1 .. %d", who, m_pred, VECCHIA_M_MAX);
+    if (corr) {
+        if (int rc = corr_check_shape(who, corr->m_cand, corr->hops, m_pred)) return rc;
+    } else if (m_pred < 1 || m_pred > VECCHIA_M_MAX)
+        return fail(-1, "%s: m_pred = %d is outside 1 .. %d", who, m_pred, VECCHIA_M_MAX);
     if (mp > 0)
         if (int rc = pattern_check_finite(who, "locs_pred", (size_t)mp, locs_pred)) return rc;
     FIT_ENTER_ANY(f);
     if (int rc = vecchia_only(f, who)) return rc;
-    if (z_col < 0 || z_col >= f->r) return fail(-1, "%s: z_col = %d is outside 0 .. %d", who, z_col, f->r - 1);
+    if (!table_only && (z_col < 0 || z_col >= f->r)) return fail(-1, "%s: z_col = %d is outside 0 .. %d", who, z_col, f->r - 1);
+    if (corr)
+        if (int rc = corr_check_theta(who, theta, f->p)) return rc;
     VecchiaState *V = f->vecchia.get();
     const int n = f->n, p = f->p, rows = VECCHIA_PRED_ROWS;
     std::vector<int> tab;
@@ -483,11 +492,11 @@ int vecchia_predict_impl(const char *who, cocons_fit *f, const double *theta, co
                 return fail(-1, "%s: row %d of nn_pred %s (1-based indices in 1 .. n, 0 = none)", who, i + 1, vecchia_offence[bad]);
     }
     if (mp == 0) return 0;
-    double hmean[COCONS_P_MAX];
-    for (int i = 0; i < p; ++i) hmean[i] = canon_nan(mean[i]);
+    double hmean[COCONS_P_MAX] = {};
+    for (int i = 0; i < p && !table_only; ++i) hmean[i] = canon_nan(mean[i]);
     // the chunk's buffers: locals of the call (device memory does not grow with mp)
     DevBuf<double> dXp, dlp, dsoa, drec, dst, dqd;
-    DevBuf<int> dnb;
+    DevBuf<int> dnb, dfirst, dnn;
     HIPCHK_AT(who, dXp.alloc((size_t)rows * p));
     HIPCHK_AT(who, dlp.alloc((size_t)rows * 2));
     HIPCHK_AT(who, dsoa.alloc((size_t)rows * LOCP_FIELDS));
@@ -495,16 +504,14 @@ int vecchia_predict_impl(const char *who, cocons_fit *f, const double *theta, co
     HIPCHK_AT(who, dst.alloc((size_t)rows));
     HIPCHK_AT(who, dqd.alloc((size_t)rows));
     HIPCHK_AT(who, dnb.alloc((size_t)rows * m_pred));
+    if (corr) HIPCHK_AT(who, dfirst.alloc((size_t)rows * corr->m_cand));
+    if (table_only) HIPCHK_AT(who, dnn.alloc((size_t)rows * m_pred));
     StreamDrain s{f->stream, false};
     if (int rc = reset_info(f)) return rc;
-    if (search && !V->knn) {
-        // the grid over the observations: the handle's from here on (counted by cocons_vecchia_info, freed with it)
-        V->knn.reset(new PatternGridBufs());
-        if (int rc = knn_grid_build(who, *V->knn, n, f->h_locs.data(), f->h_locs.data() + n, f->dlocs, f->dlocs + n, s)) {
-            (void)hipStreamSynchronize(s);
-            V->knn.reset();
-            return rc;
-        }
+    if (corr) {
+        if (int rc = corr_pred_prepare(who, f, corr->m_cand, corr->hops, s)) return rc;
+    } else if (search) {
+        if (int rc = vecchia_need_grid(who, f, s)) return rc;
     }
     // K from cov_rns's records; c from the prediction branch's (always logistic + sqrt, see cocons_predict_dense): a second
     // set of records only where the two differ (a fixed smoothness)
@@ -516,25 +523,42 @@ int vecchia_predict_impl(const char *who, cocons_fit *f, const double *theta, co
         aosC = V->aos2;
     }
     const ModeSel ms = vecchia_records(f, theta, 0, V->aos);
-    launch_vecchia_resid(n, p, f->dX, n, hmean, f->dz, n, z_col, 1, V->B, (size_t)n, s);
+    if (!table_only) launch_vecchia_resid(n, p, f->dX, n, hmean, f->dz, n, z_col, 1, V->B, (size_t)n, s);
     ThetaVecs tv;
     make_theta_vecs(theta, p, tv);
-    std::vector<double> hX((size_t)rows * p), hl((size_t)rows * 2), hst((size_t)mp), hqd((size_t)mp);
+    std::vector<double> hX((size_t)rows * p), hl((size_t)rows * 2), hst(table_only ? 0 : (size_t)mp), hqd(hst.size());
+    std::vector<int> hnn(table_only ? (size_t)mp * m_pred : 0), hnc(table_only ? (size_t)rows * m_pred : 0);
     for (int b = 0; b < mp; b += rows) {
         const int mc = std::min(rows, mp - b);
         for (int j = 0; j < p; ++j) memcpy(&hX[(size_t)j * mc], X_pred + b + (size_t)j * mp, (size_t)mc * sizeof(double));
         for (int j = 0; j < 2; ++j) memcpy(&hl[(size_t)j * mc], locs_pred + b + (size_t)j * mp, (size_t)mc * sizeof(double));
         HIPCHK_AT(who, upload_canon(dXp, hX.data(), (size_t)mc * p, s));
         HIPCHK_AT(who, upload_canon(dlp, hl.data(), (size_t)mc * 2, s));
-        if (search) {
+        // the chunk's records in front of the table step: they do not depend on the table, and the third source reads them
+        launch_loc_params(loc_args(mc, p, dXp, dlp, dsoa, rows, tv, ms2.smooth_kind, f->smooth_limits), s);
+        launch_vecchia_aos(dsoa, rows, mc, drec, s);
+        if (corr) {
+            if (int rc = corr_pred_chunk(who, f, *corr, m_pred, mc, b, dlp, drec, aosC, ms.gr, dfirst, dnb, dnn, s)) return rc;
+            // a rho that is not finite leaves its row of the table unwritten: nothing may read the table then
+            HIPCHK_AT(who, hipMemcpyAsync(f->hinfo, f->dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+            if (table_only)
+                HIPCHK_AT(who, hipMemcpyAsync(hnc.data(), dnn, (size_t)mc * m_pred * sizeof(int), hipMemcpyDeviceToHost, s));
+            HIPCHK_AT(who, hipStreamSynchronize(s));
+            if (f->hinfo[0] != 0x7f7f7f7f) {
+                if (f->hinfo[0] <= b) break;             // (a block of an earlier chunk: vecchia_status names it)
+                return fail(f->hinfo[0], "%s: row %d has a candidate whose correlation is not finite", who, f->hinfo[0]);
+            }
+            if (table_only) {
+                for (int j = 0; j < m_pred; ++j) memcpy(&hnn[b + (size_t)j * mp], &hnc[(size_t)j * mc], (size_t)mc * sizeof(int));
+                continue;
+            }
+        } else if (search) {
             KnnArgs k;
             k.t = V->knn->t; k.qx = dlp; k.qy = dlp + mc; k.m = m_pred; k.tab = dnb;
             HIPCHK_AT(who, launch_knn_query(k, mc, s));
         } else {
             HIPCHK_AT(who, hipMemcpyAsync(dnb, &tab[(size_t)b * m_pred], (size_t)mc * m_pred * sizeof(int), hipMemcpyHostToDevice, s));
         }
-        launch_loc_params(loc_args(mc, p, dXp, dlp, dsoa, rows, tv, ms2.smooth_kind, f->smooth_limits), s);
-        launch_vecchia_aos(dsoa, rows, mc, drec, s);
         VecchiaArgs a;
         a.rows = mc; a.m = m_pred; a.kb = m_pred + 1; a.nbr = dnb;
         a.aosK = V->aos; a.aosC = aosC; a.aosP = drec;
@@ -549,8 +573,27 @@ int vecchia_predict_impl(const char *who, cocons_fit *f, const double *theta, co
         HIPCHK_AT(who, hipStreamSynchronize(s));         // the staging is used again
     }
     if (int st = vecchia_status(f, who)) return st;
+    if (table_only) {
+        std::copy(hnn.begin(), hnn.end(), corr->nn_out);
+        return 0;
+    }
     memcpy(stochastic, hst.data(), (size_t)mp * sizeof(double));
     memcpy(quadform, hqd.data(), (size_t)mp * sizeof(double));
+    return 0;
+}
+
+int vecchia_need_grid(const char *who, cocons_fit *f, hipStream_t s)
+{
+    VecchiaState *V = f->vecchia.get();
+    if (V->knn) return 0;
+    // the grid over the observations: the handle's from here on (counted by cocons_vecchia_info, freed with it)
+    const int n = f->n;
+    V->knn.reset(new PatternGridBufs());
+    if (int rc = knn_grid_build(who, *V->knn, n, f->h_locs.data(), f->h_locs.data() + n, f->dlocs, f->dlocs + n, s)) {
+        (void)hipStreamSynchronize(s);
+        V->knn.reset();
+        return rc;
+    }
     return 0;
 }
 

@@ -355,8 +355,10 @@ namespace {
 // cocons_vecchia_group_rounds, cocons_vecchia_group_table and cocons_vecchia_set_groups leave on a handle, made where it is
 // used.  Home come the counters of the rounds and the 65 counts of blocks by size -- never a table or a label.  The closure
 // check of cocons_vecchia_set_groups needs no rerun: the table is written from the plan's own rows.
+// The table step is a parameter (GroupedTableStep): the Euclidean search here, the correlation table in api_knn_corr.hip.
 struct GroupedKnnSource : VecchiaTableSource {
     int m = 0, max_rows = 0, max_rounds = 0;
+    GroupedTableStep *step = nullptr;
     int make(const char *who, cocons_fit *f, const double *locs) override
     {
         VecchiaState *V = f->vecchia.get();
@@ -367,7 +369,7 @@ struct GroupedKnnSource : VecchiaTableSource {
         std::unique_ptr<VecchiaGroupState> G(new VecchiaGroupState());
         StreamDrain drain{s, false};
         HIPCHK_AT(who, tab.alloc((size_t)n * m));
-        if (int rc = knn_self_search(who, n, locs, locs + n, f->dlocs, f->dlocs + n, m, nullptr, tab, s)) return rc;
+        if (int rc = step->table(who, f, locs, m, tab)) return rc;
         int rounds = 0;
         if (int rc = group_rounds_device(who, n, m, tab, max_rows, max_rounds, R, s, &rounds)) return rc;
         const int blocks = R.nlive, H = cocons::GROUP_ROWS_MAX + 1;
@@ -419,13 +421,20 @@ struct GroupedKnnSource : VecchiaTableSource {
     }
 };
 
+struct EuclideanTableStep : GroupedTableStep {
+    int table(const char *who, cocons_fit *f, const double *locs, int m, int *d_tab) override
+    {
+        const int n = f->n;
+        return knn_self_search(who, n, locs, locs + n, f->dlocs, f->dlocs + n, m, nullptr, d_tab, f->stream);
+    }
+};
+
 }  // namespace
 
-extern "C" cocons_fit *cocons_fit_create_vecchia_grouped_knn(int n, int p, int r, const double *locs, const double *X,
-                                                             const double *z, const double *smooth_limits, int device, int m,
-                                                             int max_rows, int max_rounds)
+cocons_fit *vecchia_create_grouped_device(const char *who, int n, int p, int r, const double *locs, const double *X,
+                                          const double *z, const double *smooth_limits, int device, int m, int max_rows,
+                                          int max_rounds, GroupedTableStep &step)
 {
-    const char *who = "cocons_fit_create_vecchia_grouped_knn";
     if (max_rows < 2 || max_rows > cocons::GROUP_ROWS_MAX) {
         fail(-1, "%s: max_rows = %d is outside 2 .. %d", who, max_rows, cocons::GROUP_ROWS_MAX);
         return nullptr;
@@ -435,10 +444,19 @@ extern "C" cocons_fit *cocons_fit_create_vecchia_grouped_knn(int n, int p, int r
         return nullptr;
     }
     GroupedKnnSource src;
-    src.m = m; src.max_rows = max_rows; src.max_rounds = max_rounds;
+    src.m = m; src.max_rows = max_rows; src.max_rounds = max_rounds; src.step = &step;
     cocons_fit *f = vecchia_create_impl(who, n, p, r, locs, X, z, smooth_limits, device, m, nullptr, true, &src);
     if (!f) (void)hipGetLastError();             // (a refused device is this call's alone: the next launch must not find it)
     return f;
+}
+
+extern "C" cocons_fit *cocons_fit_create_vecchia_grouped_knn(int n, int p, int r, const double *locs, const double *X,
+                                                             const double *z, const double *smooth_limits, int device, int m,
+                                                             int max_rows, int max_rounds)
+{
+    EuclideanTableStep step;
+    return vecchia_create_grouped_device("cocons_fit_create_vecchia_grouped_knn", n, p, r, locs, X, z, smooth_limits, device, m,
+                                         max_rows, max_rounds, step);
 }
 
 extern "C" int cocons_vecchia_groups_export(cocons_fit *f, int *block, int *nn)

@@ -343,6 +343,11 @@ struct VecchiaState {
     DevBuf<double> fout;          // the totals: vecchia_fisher_cols
     // cocons_vecchia_predict_knn, made by its first call: the grid over the observations
     std::unique_ptr<PatternGridBufs> knn;
+    // cocons_vecchia_predict_corr_knn, cocons_vecchia_neighbours_corr_pred with hops = 2, made by the first
+    // such call and made again by a call at another width: the plain kNN of every observation's own coordinates among all
+    // observations, n x corr_all_mc in the layout of nbr
+    DevBuf<int> corr_all;
+    int corr_all_mc = 0;
     // cocons_vecchia_unwhiten, cocons_sim_vecchia, cocons_vecchia_schedule, made by their first call
     std::unique_ptr<VecchiaSimState> sim;
     // cocons_vecchia_transpose, cocons_vecchia_whiten_t, cocons_cv_vecchia, made by their first call
@@ -355,7 +360,7 @@ struct VecchiaState {
     {
         return (knn ? knn->bytes : 0) + (sim ? sim->bytes() : 0) + (cv ? cv->bytes() : 0) + (solve_t ? solve_t->bytes() : 0) +
                (grp ? grp->bytes() : 0) +
-               (long long)(nbr.count() * sizeof(int) +
+               (long long)((nbr.count() + corr_all.count()) * sizeof(int) +
                            (aos.count() + aos2.count() + B.count() + W.count() + part.count() + gsite.count() + gaos.count() +
                             grec.count() + gpart.count() + gout.count() + fdirs.count() + frec.count() + fpart.count() +
                             fout.count()) * sizeof(double));
@@ -791,9 +796,39 @@ struct VecchiaTableSource {
 cocons_fit *vecchia_create_impl(const char *who, int n, int p, int r, const double *locs, const double *X, const double *z,
                                 const double *smooth_limits, int device, int m, const int *nn, bool search,
                                 VecchiaTableSource *src = nullptr);
+// corr (may be null; nn_pred and search are then not looked at): the third source of a chunk's table, the neighbours of the
+// new locations by model correlation (api_knn_corr.hip) -- the query at width m_cand, the chunk's records, the
+// re-ranking into the chunk's table.  With nn_out the table of width m_pred goes home instead of a prediction (mp x m_pred
+// column-major, 1-based, largest rho first): mean, z_col, stochastic and quadform are then not looked at.
+struct CorrPredSource {
+    int m_cand = 0, hops = 0;
+    int *nn_out = nullptr;
+};
 int vecchia_predict_impl(const char *who, cocons_fit *f, const double *theta, const double *mean, int z_col, int mp,
                          const double *locs_pred, const double *X_pred, int m_pred, const int *nn_pred, bool search,
-                         double *stochastic, double *quadform);
+                         double *stochastic, double *quadform, const CorrPredSource *corr = nullptr);
+// ... and what api_knn_corr.hip offers it: the shape and theta checks of the correlation entries under the name of the entry
+// that asks; what a call at (m_cand, hops) needs on the handle -- the grid and, with two hops, the all-observations table --
+// made on s where it is missing (drained where something was made); and one chunk's step on s, not waited for: the query of
+// the mc rows at (dlp, dlp + mc) into d_first (mc x m_cand), then the re-ranking with the chunk's records drec and the
+// observations' aosC into d_tab (mc x m, the layout of VecchiaArgs::nbr) and d_nn (may be null: mc x m column-major, 1-based,
+// largest rho first); the failure word gets row0 + the row of a rho that is not finite
+int corr_check_shape(const char *who, int m_cand, int hops, int m);
+int corr_check_theta(const char *who, const double *theta, int p);
+int vecchia_need_grid(const char *who, cocons_fit *f, hipStream_t s);
+int corr_pred_prepare(const char *who, cocons_fit *f, int m_cand, int hops, hipStream_t s);
+int corr_pred_chunk(const char *who, cocons_fit *f, const CorrPredSource &c, int m, int mc, int row0, const double *dlp,
+                    const double *drec, const double *aosC, double gr, int *d_first, int *d_tab, int *d_nn, hipStream_t s);
+// ... and what api_vecchia_group.hip offers api_knn_corr.hip: the grouped handle made on the device
+// from a table that `table` leaves in d_tab (n x m, the layout of VecchiaState::nbr) on the handle's stream -- the rounds,
+// the plan and the expanded table follow it there; table returns 0 or a failure with the message set
+struct GroupedTableStep {
+    virtual ~GroupedTableStep() = default;
+    virtual int table(const char *who, cocons_fit *f, const double *locs, int m, int *d_tab) = 0;
+};
+cocons_fit *vecchia_create_grouped_device(const char *who, int n, int p, int r, const double *locs, const double *X,
+                                          const double *z, const double *smooth_limits, int device, int m, int max_rows,
+                                          int max_rounds, GroupedTableStep &step);
 // ... and what api_vecchia.hip offers api_vecchia_sim.hip: the refusal of the other kinds of handle, the
 // observations' records for theta (which = 0: cov_rns's parameters) and the info words home with the stream drained (0, or the
 // smallest 1-based row whose block failed)

@@ -463,6 +463,24 @@ __host__ __device__ inline int knn_corr_slots(int mc, int hops)
 size_t knn_corr_lds_bytes(int mc, int hops);
 hipError_t launch_knn_corr(int mode, const KnnCorrArgs &a, hipStream_t s);
 
+// ... of NEW locations (the rule: include/cocons_hip.h).  One wave per row: block b is row q = b of a chunk of
+// `rows` new locations.  first: the chunk's plain kNN table among all n observations, rows x mc in the layout above; all (read
+// with hops = 2 only): the same table of the observations' own coordinates, n x mc.  The candidates of row q are first's row
+// q and, with hops = 2, the rows of `all` that its members name, each index once; their key is (rho descending, index
+// ascending), rho = v / sqrt(d_q d_j) -- v the entry (j, q) of the prediction block (the site on the `ii` side, the prediction
+// branch's records aosC of the observations and aosP of the chunk, an exact coordinate match gives the site's field 11), d
+// field 11 of those records.  nn, ldn, tab as above with row q of the chunk; fail: atomicMin of row0 + q + 1.
+struct KnnCorrPredArgs {
+    int rows = 0, mc = 0, hops = 1, m = 0, row0 = 0;
+    const int *first = nullptr, *all = nullptr;
+    const double *aosC = nullptr, *aosP = nullptr;
+    double gr = 0.0;
+    int *nn = nullptr; size_t ldn = 0;
+    int *tab = nullptr;
+    int *fail = nullptr;
+};
+hipError_t launch_knn_corr_pred(const KnnCorrPredArgs &a, hipStream_t s);
+
 // ---- maxmin ordering by scale-halving nets (order.hip; the rule: order_plan.hpp) -------------------------------
 // The points live in LABEL order (px, py, orig: the caller's index), so a lower index is a higher priority.  state[p], by
 // label: ORDER_FREE (not ordered, undecided at this level), ORDER_DONE (ordered), ORDER_DROPPED (conflicts with an ordered

@@ -1467,6 +1467,43 @@ def vecchia_neighbours_corr(S, nn_cand, m, hops=2) -> np.ndarray:
     return out
 
 
+def vecchia_neighbours_corr_pred(Cq, dq, d, nn_pred, nn_all, m, hops=2) -> np.ndarray:
+    """The neighbours of NEW locations by model correlation (the rule: include/cocons_hip.h), restated on the
+    host: Cq the mp x n cross-covariance of the new locations with the observations at theta (`cov_rns_pred`), dq (mp) and
+    d (n) the diagonal values of the prediction branch -- `cov_rns_pred`'s entries for the new locations, and for the
+    observations, predicted onto themselves --, nn_pred the plain kNN table of the new locations among all observations
+    (mp x m_cand, 1-based, 0 = none; `vecchia_neighbours_pred_device(locs, newlocs, m_cand)`) and nn_all that of the
+    observations' own coordinates (n x m_cand; `vecchia_neighbours_pred_device(locs, locs, m_cand)`; read with hops = 2
+    only).  The candidates of row q are nn_pred's row q and, with hops = 2, the rows of nn_all that its members name, each
+    index once; row q lists the m of them with the largest key (rho, then the lower index), rho = Cq[q, j] / sqrt(dq[q] d[j])
+    with one rounding per operation, compared by the total order of its bit patterns: mp x m int32 in Fortran order,
+    1-based, largest rho first, zero-padded.  ValueError names the first row with a rho that is not finite."""
+    Cq = np.asarray(Cq, dtype=np.float64)
+    mp, m, hops = Cq.shape[0], int(m), int(hops)
+    dq, d = np.asarray(dq, dtype=np.float64).reshape(mp), np.asarray(d, dtype=np.float64).reshape(Cq.shape[1])
+    first = np.asarray(nn_pred, dtype=np.int64).reshape(mp, -1)
+    if hops not in (1, 2) or m < 1:
+        raise ValueError("hops must be 1 or 2 and m at least 1")
+    lists = np.asarray(nn_all, dtype=np.int64).reshape(Cq.shape[1], -1) if hops == 2 else None
+    out = np.zeros((mp, m), dtype=np.int32, order="F")
+    top = np.uint64(1) << np.uint64(63)
+    for q in range(mp):
+        c = first[q][first[q] > 0]
+        if hops == 2 and c.size:
+            c = np.concatenate([c, lists[c - 1].ravel()])
+        c = np.unique(c[c > 0]) - 1
+        if not c.size:
+            continue
+        rho = Cq[q, c] / np.sqrt(dq[q] * d[c])
+        if not np.all(np.isfinite(rho)):
+            raise ValueError("row %d has a candidate whose correlation is not finite" % (q + 1))
+        b = rho.view(np.uint64)
+        key = ~np.where(b >> np.uint64(63) != 0, ~b, b | top)          # ascends as rho descends
+        o = np.lexsort((c, key))[:m]
+        out[q, :o.size] = c[o] + 1
+    return out
+
+
 _ORDER_LEVELS = 64
 _ORDER_MIX = (0x9E3779B1, 0x85EBCA6B, 0xC2B2AE35)
 
@@ -1694,8 +1731,7 @@ class CoconsVecchiaFit(_Handle):
         """The handle of the table `neighbours_corr(theta_list, m, m_cand, hops)` (cocons_fit_create_vecchia_corr_knn, DESIGN.md
         4af): the Euclidean search of width m_cand (default min(2 m, 63)), the records at theta and the re-ranking by model
         correlation all on the device; neither table reaches the host, and every core gives the bits of the handle made
-        from the exported table.  A grouped handle on such a table goes through `vecchia_group_device` / `from_groups` on
-        the exported table."""
+        from the exported table.  `from_groups_corr_knn` is the grouped handle on such a table."""
         self = cls.__new__(cls)
         locs, X, z = self._adopt(locs, x_covariates, z, smooth_limits)
         self.m = int(m)
@@ -1727,6 +1763,53 @@ class CoconsVecchiaFit(_Handle):
         _lib.check(self._L.cocons_vecchia_neighbours_corr(self._h, _p(T), mc, int(hops), m, _ip(nn)),
                    "cocons_vecchia_neighbours_corr")
         return nn
+
+    def neighbours_corr_pred(self, theta_list, locs_pred, x_covariates_pred, m, m_cand=None, hops=2):
+        """The neighbours of new locations by model correlation at theta (cocons_vecchia_neighbours_corr_pred):
+        among the candidates -- the m_cand (default min(2 m, 63)) nearest observations and, with hops = 2, the m_cand
+        nearest observations of each of those -- the m with the largest correlation with the new location under the
+        prediction's covariance, largest first: mp x m int32 in Fortran order, 1-based, zero-padded.
+        `vecchia_neighbours_corr_pred` restates the rule on the host.  The first call builds the grid over the observations
+        and, with hops = 2, their own kNN table of width m_cand, which the handle keeps (`info()["bytes"]` counts them).
+        CholeskyError(q): row q has a candidate whose correlation is not finite."""
+        m = int(m)
+        mc = min(2 * m, 63) if m_cand is None else int(m_cand)
+        T = theta_table(theta_list)
+        lp, Xp = _f(locs_pred), _f(x_covariates_pred)
+        mp = lp.shape[0]
+        nn = np.zeros((mp, m), dtype=np.int32, order="F")
+        _lib.check(self._L.cocons_vecchia_neighbours_corr_pred(self._h, _p(T), mp, _p(lp), _p(Xp), mc, int(hops), m, _ip(nn)),
+                   "cocons_vecchia_neighbours_corr_pred")
+        return nn
+
+    @classmethod
+    def from_groups_corr_knn(cls, locs, x_covariates, z, smooth_limits, theta_list, m, m_cand=None, hops=2, max_rows=64,
+                             max_rounds=0, device=-1):
+        """`from_groups_knn` on the table `neighbours_corr(theta_list, m, m_cand, hops)` in the place of the Euclidean one
+        (cocons_fit_create_vecchia_grouped_corr_knn): search, records at theta, re-ranking, round rule, plan
+        and expanded table on the device, none of which reaches the host.  The handle of `neighbours_corr` ->
+        `vecchia_group_rounds` -> `vecchia_group_table` -> the constructor -> `set_groups` on the same data, to the bit."""
+        self = cls.__new__(cls)
+        locs, X, z = self._adopt(locs, x_covariates, z, smooth_limits)
+        m = int(m)
+        mc = min(2 * m, 63) if m_cand is None else int(m_cand)
+        T = theta_table(theta_list)
+        self._created(self._L.cocons_fit_create_vecchia_grouped_corr_knn(self.n, self.p, self.r, _p(locs), _p(X), _p(z),
+                                                                         _p(self.smooth_limits), int(device), _p(T), mc,
+                                                                         int(hops), m, int(max_rows), int(max_rounds)),
+                      "cocons_fit_create_vecchia_grouped_corr_knn")
+        self.m = self.info()["m"]
+        return self
+
+    @classmethod
+    def from_maxmin_groups_corr(cls, locs, x_covariates, z, smooth_limits, theta_list, m, m_cand=None, hops=2, max_rows=64,
+                                max_rounds=0, device=-1):
+        """`from_maxmin` with `from_groups_corr_knn` in the place of `from_knn`: the maxmin order, then the grouped handle
+        on the correlation table of the permuted rows at theta; the rows are the permuted ones, as `from_maxmin`'s are."""
+        def make(locs_, X_, z_, sl_, m_, device=-1):
+            return cls.from_groups_corr_knn(locs_, X_, z_, sl_, theta_list, m_, m_cand=m_cand, hops=hops, max_rows=max_rows,
+                                            max_rounds=max_rounds, device=device)
+        return cls._from_maxmin(make, locs, x_covariates, z, smooth_limits, m, device=device)
 
     @classmethod
     def from_groups(cls, locs, x_covariates, z, smooth_limits, nn, max_rows=64, device=-1):
@@ -1871,6 +1954,20 @@ class CoconsVecchiaFit(_Handle):
         st, qf = np.zeros(mp), np.zeros(mp)
         _lib.check(self._L.cocons_vecchia_predict_knn(self._h, _p(T), _p(mean), int(z_col), mp, _p(lp), _p(Xp), int(m_pred),
                                                       _p(st), _p(qf)), "cocons_vecchia_predict_knn")
+        return st, qf
+
+    def predict_corr_knn_core(self, theta_list, locs_pred, x_covariates_pred, m_pred, m_cand=None, hops=2, z_col=0):
+        """`predict_core` with the table `neighbours_corr_pred(theta_list, locs_pred, x_covariates_pred, m_pred, m_cand,
+        hops)`, to the bit (cocons_vecchia_predict_corr_knn): every chunk's neighbours are found and ranked by
+        model correlation on the device, and no table goes up or down.  What the handle keeps is `neighbours_corr_pred`'s."""
+        T, mean = _table_mean(theta_list)
+        lp, Xp = _f(locs_pred), _f(x_covariates_pred)
+        mp, m_pred = lp.shape[0], int(m_pred)
+        mc = min(2 * m_pred, 63) if m_cand is None else int(m_cand)
+        st, qf = np.zeros(mp), np.zeros(mp)
+        _lib.check(self._L.cocons_vecchia_predict_corr_knn(self._h, _p(T), _p(mean), int(z_col), mp, _p(lp), _p(Xp), mc,
+                                                           int(hops), m_pred, _p(st), _p(qf)),
+                   "cocons_vecchia_predict_corr_knn")
         return st, qf
 
     def _unwhiten(self, theta_list, W, entry):
@@ -2169,6 +2266,21 @@ def cocoPredict_vecchia_knn(theta_list, locs, newlocs, X_std, X_pred_std, smooth
 
     with _borrowed(fit, one_column) as f:
         st, qf = f.predict_knn_core(theta_list, newlocs, X_pred_std, m_pred)
+    return _predict_outputs(theta_list, X_pred_std, st, qf, type)
+
+
+def cocoPredict_vecchia_corr_knn(theta_list, locs, newlocs, X_std, X_pred_std, smooth_limits, z, m_pred, m_cand=None, hops=2,
+                                 type="pred", fit=None):
+    """`cocoPredict_vecchia_knn` with every new location predicted from the m_pred observations most correlated with it
+    under the model at theta, not its m_pred nearest (cocons_vecchia_predict_corr_knn): the fit made with
+    `from_corr_knn` and the kriging then condition by the same criterion.  m_cand, hops as in
+    `CoconsVecchiaFit.neighbours_corr_pred`; `fit` as there."""
+    def one_column():
+        # (see cocoPredict_vecchia_knn)
+        return CoconsVecchiaFit(locs, X_std, z, smooth_limits, np.zeros((np.asarray(X_std).shape[0], 1), dtype=np.int32))
+
+    with _borrowed(fit, one_column) as f:
+        st, qf = f.predict_corr_knn_core(theta_list, newlocs, X_pred_std, m_pred, m_cand=m_cand, hops=hops)
     return _predict_outputs(theta_list, X_pred_std, st, qf, type)
 
 

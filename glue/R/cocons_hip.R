@@ -582,7 +582,7 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
 #   nn   <- .cocons.hip.vecchia.neighbours.corr(fit0, theta_list, m)                                          # re-ranked at its optimum
 #   fit  <- .cocons.hip.vecchia.create.corr.knn(locs[ord, ], X[ord, ], z[ord, , drop = FALSE], smooth.limits, theta_list, m)
 # (the second is .cocons.hip.vecchia.create with nn, made on the device).  A grouped fit on such a table:
-# .cocons.hip.vecchia.group.device(nn) and .cocons.hip.vecchia.create.grouped; new locations keep the Euclidean search.
+# .cocons.hip.vecchia.create.grouped.corr.knn; new locations: .cocons.hip.vecchia.predict.corr.knn (both below).
 .cocons.hip.vecchia.neighbours.corr <- function(fit, theta_list, m, m_cand = min(2L * as.integer(m), 63L), hops = 2L) {
   res <- .Call(`_cocons_hip_vecchia_neighbours_corr`, fit, theta_list, as.integer(m_cand), as.integer(hops), as.integer(m))
   if (res[[1]] > 0L) stop("the correlation of row ", res[[1]], " with a candidate is not finite")
@@ -600,6 +600,27 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
 .cocons.hip.vecchia.predict.knn <- function(fit, theta_list, newlocs, X_pred, m_pred, z_col = 1L) {
   res <- .Call(`_cocons_hip_vecchia_predict_knn`, fit, theta_list, as.integer(z_col), as.matrix(newlocs), as.matrix(X_pred),
                as.integer(m_pred))
+  if (res[[1]] > 0L) stop("Cholesky error")
+  res[[2]]
+}
+
+# the neighbours of NEW locations by model correlation (DESIGN.md 4ag): among the m_cand nearest observations of a new
+# location and (hops = 2) the m_cand nearest observations of each of those, the m most correlated with it under the
+# prediction's covariance at theta, largest first; and local kriging on them, found and ranked on the device chunk by chunk --
+# .cocons.hip.vecchia.predict with that table, to the bit.  The fit keeps the grid over the observations and (hops = 2) their
+# own neighbour table of width m_cand for later calls
+.cocons.hip.vecchia.neighbours.corr.pred <- function(fit, theta_list, newlocs, X_pred, m,
+                                                     m_cand = min(2L * as.integer(m), 63L), hops = 2L) {
+  res <- .Call(`_cocons_hip_vecchia_neighbours_corr_pred`, fit, theta_list, as.matrix(newlocs), as.matrix(X_pred),
+               c(as.integer(m_cand), as.integer(hops), as.integer(m)))
+  if (res[[1]] > 0L) stop("the correlation of new location ", res[[1]], " with a candidate is not finite")
+  res[[2]]
+}
+
+.cocons.hip.vecchia.predict.corr.knn <- function(fit, theta_list, newlocs, X_pred, m_pred,
+                                                 m_cand = min(2L * as.integer(m_pred), 63L), hops = 2L, z_col = 1L) {
+  res <- .Call(`_cocons_hip_vecchia_predict_corr_knn`, fit, theta_list, as.integer(z_col), as.matrix(newlocs), as.matrix(X_pred),
+               c(as.integer(m_cand), as.integer(hops), as.integer(m_pred)))
   if (res[[1]] > 0L) stop("Cholesky error")
   res[[2]]
 }
@@ -740,6 +761,16 @@ cocons_hip_taper_fit <- function(locs, x_covariates, z, smooth.limits, ref_taper
                                                    device = -1L) {
   .Call(`_cocons_hip_vecchia_create_grouped_knn`, as.matrix(locs), as.matrix(x_covariates), as.matrix(z), as.double(smooth.limits),
         as.integer(device), as.integer(m), as.integer(max_rows), as.integer(max_rounds))
+}
+
+# the same on the table of .cocons.hip.vecchia.neighbours.corr at theta (DESIGN.md 4ag) in the place of the Euclidean search:
+# the fit of .neighbours.corr, .group.rounds, .group.table, .create and .set.groups on the same data, to the bit
+.cocons.hip.vecchia.create.grouped.corr.knn <- function(locs, x_covariates, z, smooth.limits, theta_list, m,
+                                                        m_cand = min(2L * as.integer(m), 63L), hops = 2L, max_rows = 64L,
+                                                        max_rounds = 0L, device = -1L) {
+  .Call(`_cocons_hip_vecchia_create_grouped_corr_knn`, as.matrix(locs), as.matrix(x_covariates), as.matrix(z),
+        as.double(smooth.limits), as.integer(device), theta_list, c(as.integer(m_cand), as.integer(hops), as.integer(m)),
+        as.integer(max_rows), as.integer(max_rounds))
 }
 
 .cocons.hip.vecchia.groups.export <- function(fit) {

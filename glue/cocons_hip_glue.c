@@ -1148,6 +1148,83 @@ SEXP _cocons_hip_vecchia_create_corr_knn(SEXP locs, SEXP X, SEXP z, SEXP smooth_
     return ptr;
 }
 
+/* the neighbours of NEW locations by model correlation at theta (cocons_vecchia_neighbours_corr_pred): among
+ * the m_cand nearest observations of a new location and (hops = 2) the m_cand nearest observations of each of those, the m
+ * most correlated with it under the prediction's covariance.  list(status, integer matrix mp x m, 1-based, largest
+ * correlation first, 0 = none); status > 0: the row whose correlation with a candidate is not finite.  shape: the integer
+ * vector c(m_cand, hops, m) */
+static const int *corr_shape(SEXP shape)
+{
+    if (!Rf_isInteger(shape) || XLENGTH(shape) != 3) Rf_error("shape must be the integer vector c(m_cand, hops, m)");
+    return INTEGER(shape);
+}
+
+SEXP _cocons_hip_vecchia_neighbours_corr_pred(SEXP fitp, SEXP theta, SEXP locs_pred, SEXP X_pred, SEXP shape)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int *sh = corr_shape(shape);
+    const int p = fit_p(fitp), mp = Rf_nrows(X_pred), k = sh[2];
+    if (Rf_ncols(X_pred) != p || Rf_nrows(locs_pred) != mp || Rf_ncols(locs_pred) != 2)
+        Rf_error("prediction design / locations do not match the fit");
+    if (k < 1 || k > 63) Rf_error("cocons_vecchia_neighbours_corr_pred: m = %d is outside 1 .. 63", k);
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    SEXP nn = PROTECT(Rf_allocMatrix(INTSXP, mp, k));
+    memset(INTEGER(nn), 0, (size_t)mp * k * sizeof(int));
+    int rc = cocons_vecchia_neighbours_corr_pred(f, T, mp, REAL(locs_pred), REAL(X_pred), sh[0], sh[1], k, INTEGER(nn));
+    hip_check(rc, "Vecchia neighbours of new locations by correlation");
+    SEXP out = status_value(rc, nn);
+    UNPROTECT(1);
+    return out;
+}
+
+/* _cocons_hip_vecchia_predict_knn on the neighbours _cocons_hip_vecchia_neighbours_corr_pred returns, found and ranked on the
+ * device chunk by chunk (cocons_vecchia_predict_corr_knn).  list(status, cbind(stochastic, quadform)); shape: c(m_cand, hops,
+ * m_pred) */
+SEXP _cocons_hip_vecchia_predict_corr_knn(SEXP fitp, SEXP theta, SEXP z_col, SEXP locs_pred, SEXP X_pred, SEXP shape)
+{
+    cocons_fit *f = fit_of(fitp);
+    const int *sh = corr_shape(shape);
+    const int p = fit_p(fitp), m = Rf_nrows(X_pred);
+    if (Rf_ncols(X_pred) != p || Rf_nrows(locs_pred) != m || Rf_ncols(locs_pred) != 2)
+        Rf_error("prediction design / locations do not match the fit");
+    SEXP mean = list_get(theta, "mean");
+    if (!Rf_isReal(mean) || XLENGTH(mean) != p) Rf_error("theta$mean must be a double vector of length %d", p);
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    SEXP v = PROTECT(Rf_allocMatrix(REALSXP, m, 2));
+    int rc = cocons_vecchia_predict_corr_knn(f, T, REAL(mean), Rf_asInteger(z_col) - 1, m, REAL(locs_pred), REAL(X_pred),
+                                             sh[0], sh[1], sh[2], REAL(v), REAL(v) + m);
+    hip_check(rc, "cocoPredict (Vecchia, neighbours by correlation)");
+    SEXP out = status_value(rc, v);
+    UNPROTECT(1);
+    return out;
+}
+
+/* the grouped Vecchia handle on the table of _cocons_hip_vecchia_neighbours_corr (cocons_fit_create_vecchia_grouped_corr_knn,
+ * DESIGN.md 4ag): search, records at theta, re-ranking, round rule, plan and expanded table on the device; shape: c(m_cand,
+ * hops, m) */
+SEXP _cocons_hip_vecchia_create_grouped_corr_knn(SEXP locs, SEXP X, SEXP z, SEXP smooth_limits, SEXP device, SEXP theta,
+                                                 SEXP shape, SEXP max_rows, SEXP max_rounds)
+{
+    const int *sh = corr_shape(shape);
+    const int n = Rf_nrows(X), p = Rf_ncols(X);
+    const int r = Rf_isMatrix(z) ? Rf_ncols(z) : 1;
+    if (Rf_nrows(locs) != n || Rf_ncols(locs) != 2) Rf_error("locs must be n x 2");
+    double T[6 * COCONS_P_MAX];
+    theta_table(theta, p, T);
+    cocons_fit *f = cocons_fit_create_vecchia_grouped_corr_knn(n, p, r, REAL(locs), REAL(X), REAL(z), REAL(smooth_limits),
+                                                               Rf_asInteger(device), T, sh[0], sh[1], sh[2],
+                                                               Rf_asInteger(max_rows), Rf_asInteger(max_rounds));
+    if (!f) Rf_error("%s", cocons_last_error());
+    SEXP tag = PROTECT(Rf_allocVector(INTSXP, 4));
+    INTEGER(tag)[0] = n; INTEGER(tag)[1] = p; INTEGER(tag)[2] = r; INTEGER(tag)[3] = 0;
+    SEXP ptr = PROTECT(R_MakeExternalPtr(f, tag, R_NilValue));
+    R_RegisterCFinalizerEx(ptr, fit_finalizer, TRUE);
+    UNPROTECT(2);
+    return ptr;
+}
+
 /* the maxmin order of the rows of locs (n x 2) found on the device (cocons_vecchia_order): an integer vector, 1-based,
  * ord[t] the row at position t */
 SEXP _cocons_hip_vecchia_order(SEXP locs, SEXP device)
@@ -1777,6 +1854,9 @@ static const R_CallMethodDef CallEntries[] = {
     {"_cocons_hip_vecchia_create_knn", (DL_FUNC)&_cocons_hip_vecchia_create_knn, 6},
     {"_cocons_hip_vecchia_neighbours_corr", (DL_FUNC)&_cocons_hip_vecchia_neighbours_corr, 5},
     {"_cocons_hip_vecchia_create_corr_knn", (DL_FUNC)&_cocons_hip_vecchia_create_corr_knn, 9},
+    {"_cocons_hip_vecchia_neighbours_corr_pred", (DL_FUNC)&_cocons_hip_vecchia_neighbours_corr_pred, 5},
+    {"_cocons_hip_vecchia_predict_corr_knn", (DL_FUNC)&_cocons_hip_vecchia_predict_corr_knn, 6},
+    {"_cocons_hip_vecchia_create_grouped_corr_knn", (DL_FUNC)&_cocons_hip_vecchia_create_grouped_corr_knn, 9},
     {"_cocons_hip_vecchia_predict_knn", (DL_FUNC)&_cocons_hip_vecchia_predict_knn, 6},
     {"_cocons_hip_vecchia_unwhiten", (DL_FUNC)&_cocons_hip_vecchia_unwhiten, 3},
     {"_cocons_hip_vecchia_sim", (DL_FUNC)&_cocons_hip_vecchia_sim, 5},

@@ -420,14 +420,70 @@ int cocons_vecchia_predict_knn(cocons_fit *fit, const double *theta, const doubl
  * adoption.  Neither table reaches the host.  NULL with the refusals above and cocons_fit_create_vecchia's, under this
  * entry's name, or when a rho is not finite.
  *
- * Out of scope: a fused device chain to a GROUPED handle on such a table (export the table, then cocons_vecchia_group_rounds
- * / cocons_fit_create_vecchia_grouped), and correlation-ranked neighbours of NEW locations in cocons_vecchia_predict_knn.
- * These two entries add to the ABI and change no existing one: cocons_abi_version stays 1.                                */
+ * Out of scope: correlation-ranked neighbours inside the joint handle of cocoPredict_vecchia_joint.
+ * These entries add to the ABI and change no existing one: cocons_abi_version stays 1.                                    */
 int cocons_vecchia_neighbours_corr(cocons_fit *fit, const double *theta, int m_cand, int hops, int m,
                                    int *nn_out /* n x m column-major, 1-based, largest rho first, 0 = none */);
 cocons_fit *cocons_fit_create_vecchia_corr_knn(int n, int p, int r, const double *locs, const double *X, const double *z,
                                                const double *smooth_limits, int device, const double *theta, int m_cand,
                                                int hops, int m);
+
+/* ---- ... of NEW locations, and the grouped handle on a correlation table ---------------------------------------
+ * Local kriging conditions a new location q on observations; the ones that matter are again the most correlated with q, not
+ * the Euclidean-nearest.  The rule, here and in every reference, for a Vecchia handle with n observations, a new location q
+ * with its covariates, theta, m_cand in 1 .. 63, hops in {1, 2}, m in 1 .. 63:
+ *  1. P(q) is the row cocons_vecchia_neighbours(n, locs, 1, q, m_cand, ..) returns: the plain kNN of q among ALL observations
+ *     by the key (d2, index).
+ *  2. The candidates C(q): P(q) for hops = 1; P(q) and, for every j in P(q), the row A(j) =
+ *     cocons_vecchia_neighbours(n, locs, 1, loc_j, m_cand, ..) for hops = 2 -- the plain kNN of observation j's own
+ *     coordinates among all observations, UNORDERED on purpose: a prediction must not depend on the order the observations
+ *     were fitted in, and a new location has no predecessors.  j itself (or a coincident twin) may stand in A(j); zeros are
+ *     dropped, and an index counts once however many lists name it.
+ *  3. The key of a candidate j is (rho descending, index ascending), rho(q, j) = fl(v / fl(sqrt(fl(d_q d_j)))): v the entry the
+ *     prediction block of cocons_vecchia_predict holds for (j, q) -- cocons_cov_rns_pred's entry for the new location q and
+ *     observation j: the new location on the `ii` side, the prediction branch's parameters (logistic + sqrt smoothness), an
+ *     exact coordinate match gives the new location's diagonal value --; d_q the diagonal value of the prediction branch for
+ *     q, d_j that for observation j: the bits cocons_cov_rns_pred returns for a new location placed ON an observation with
+ *     that observation's covariates (there the coordinates match, and the entry is the diagonal value), so d_q comes from
+ *     the new locations predicted "onto themselves" and d_j from the observations predicted onto themselves.  fp64, one
+ *     rounding per operation, no contraction; rho is compared by the total order of its bit patterns, as above.
+ *  4. Row q lists the m candidates with the largest key, largest rho first, 1-based, zero-padded.
+ * So the output is a function of the inputs alone; a row depends on no other row of the query set and on no chunking; the
+ * table for m is the first m columns of the table for any m' > m; hops = 1 with m = m_cand returns P(q) as a set; under an
+ * isotropic stationary theta every setting returns the Euclidean set (up to ties of rho's rounding); and n <= m_cand ranks
+ * every observation.  host.vecchia_neighbours_corr_pred restates the rule in numpy.
+ *
+ * cocons_vecchia_neighbours_corr_pred: the table of mp new locations (locs_pred mp x 2, X_pred mp x p, column-major) on any
+ * Vecchia handle; nn_out mp x m column-major.  The work runs in chunks of cocons_vecchia_info's out4[3] rows with device
+ * memory that does not grow with mp.  The handle keeps what later calls use again and cocons_vecchia_info counts it: the grid
+ * over the observations (cocons_vecchia_predict_knn's) and, with hops = 2, the table A -- n x m_cand ints, 120 MB at
+ * n = 10^6 and m_cand = 30 --, made by the first call with two hops, made again by a call at another m_cand, freed with the
+ * handle; hops = 1 never makes it.  Returns 0 (mp = 0: at once); the smallest 1-based row with a rho that is not finite
+ * (nn_out untouched); -1 before any device work, nn_out untouched, for: a null argument, mp < 0, a handle that is not a
+ * Vecchia handle, m_cand, hops or m out of range, m > min(4032, m_cand + m_cand^2 (hops - 1)), a theta or a coordinate that
+ * is not finite.
+ *
+ * cocons_vecchia_predict_corr_knn: cocons_vecchia_predict with the table cocons_vecchia_neighbours_corr_pred returns, to the
+ * bit, every chunk's table made on the device -- the query at m_cand, the chunk's records, the re-ranking, the prediction
+ * launch --; no table goes up or down, and a row's outputs depend neither on the chunking nor on the other rows.  Refusals
+ * as above and cocons_vecchia_predict_knn's, under this entry's name, outputs untouched; a rho that is not finite or a
+ * failing block returns its 1-based row.
+ *
+ * cocons_fit_create_vecchia_grouped_corr_knn: cocons_fit_create_vecchia_grouped_knn with the table of
+ * cocons_vecchia_neighbours_corr(theta, m_cand, hops, m) in the place of the Euclidean search: search, records at theta,
+ * re-rank, rounds, plan, expanded table and adoption in one chain on the device.  The handle gives, in every entry grouped or
+ * not, the bits of cocons_vecchia_neighbours_corr -> cocons_vecchia_group_rounds -> cocons_vecchia_group_table ->
+ * cocons_fit_create_vecchia -> cocons_vecchia_set_groups.  NULL with the refusals of both parents under this entry's name. */
+int cocons_vecchia_neighbours_corr_pred(cocons_fit *fit, const double *theta, int mp, const double *locs_pred,
+                                        const double *X_pred, int m_cand, int hops, int m,
+                                        int *nn_out /* mp x m column-major, 1-based, largest rho first, 0 = none */);
+int cocons_vecchia_predict_corr_knn(cocons_fit *fit, const double *theta, const double *mean, int z_col, int mp,
+                                    const double *locs_pred, const double *X_pred, int m_cand, int hops, int m_pred,
+                                    double *stochastic, double *quadform);
+cocons_fit *cocons_fit_create_vecchia_grouped_corr_knn(int n, int p, int r, const double *locs, const double *X,
+                                                       const double *z, const double *smooth_limits, int device,
+                                                       const double *theta, int m_cand, int hops, int m,
+                                                       int max_rows, int max_rounds);
 
 /* ---- Maxmin ordering on the device: scale-halving nets ------------------------------------------------------
  * The order of the observations a Vecchia fit wants: coarse to fine, every point at least half as far from its predecessors
